@@ -22,6 +22,10 @@ configuration (graph replay for samplers of at least 200 steps, i.e. every 1000-
 single-crystal config): `loop_mode` names it, `eager_loop` / `graph_loop` hold both.
 
 Prints ONE JSON line on rank 0 (see the keys at the bottom).
+
+`--dump-outputs DIR` also writes what the timed loop handed back after its last step as DIR/<name>.npy (sampling: frac,
+types, lengths, lattice; c5: loss, parameters), so that two builds can be compared output for output: the inputs are
+seeded, identical from run to run for the same arguments.
 """
 import argparse
 import json
@@ -134,6 +138,31 @@ def emit(result):
     out.flush()
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, rank=0, world=1, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: {name: host array} -> out_dir/<name>.npy, float64 arrays as float64, everything else as float32
+    (atom types are small integers: exact).  The ranks share the budget; an array set over a rank's share keeps the same
+    fixed, seeded sample of each array's rows (leading dimension), so that two runs still compare element for element.
+    Rank r > 0 of a multi-rank run writes <name>.rank<r>.npy."""
+    import numpy as np
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: v.astype(np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    share = budget // world
+    total = sum(v.nbytes for v in arrays.values())
+    if total > share:
+        for k, v in arrays.items():
+            if v.ndim and v.shape[0] > 1:
+                keep = max(1, v.shape[0] * share // total)
+                arrays[k] = v[np.sort(np.random.RandomState(0).choice(v.shape[0], keep, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, (k if rank == 0 else f"{k}.rank{rank}") + ".npy"), v)
+    log(f"rank {rank}: outputs of the last timed step -> {out_dir}: "
+        + ", ".join(f"{k} {list(v.shape)} {v.dtype}" for k, v in arrays.items()))
+
+
 def host_cores():
     """CPU threads this process may really use: affinity mask, capped by the cgroup CPU quota."""
     n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
@@ -171,6 +200,8 @@ def parse_args(argv=None):
                     "configurations (c1, c4, c5) that the one-GPU default run appends as `other_configs`")
     ap.add_argument("--groups", type=int, default=0, help="experiment, needs ARREAU_ALLOW_MULTISTREAM=1: slices of the batch on separate streams "
                     "(0 = the product: one stream; 2 was 3 %% faster at 256 x 20 but is not run-to-run reproducible)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the timed loop's last step as "
+                    "DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     args = ap.parse_args(argv)
     B, n, T = CONFIGS[args.config or "c2"]
     args.batch_per_gpu = args.batch_per_gpu or B
@@ -460,6 +491,16 @@ def run_rank(args, rank, local_rank, world):
         sync()
         return time.perf_counter() - t0
 
+    # `value` is the loop the product runs for THIS configuration: the same policy as DiffusionLoss.sample's default
+    # (graph replay from 200 sampler steps on; the 100-step single-crystal config runs eagerly).
+    production_graph = (T - 1) >= 200 and not args.eager_value and not args.no_graph_loop
+    outputs = None
+
+    def step_outputs():
+        """what arreau_sample_loop hands back: the state it updates in place and the last step's lattice"""
+        return {"frac": frac_d.cpu().numpy(), "types": types_d.cpu().numpy(), "lengths": len_d.cpu().numpy(),
+                "lattice": lat_d.cpu().numpy()}
+
     log(f"rank {rank}: model packed, state ready (B={B}, n={n}, T={T}); warm-up {args.warmup} steps")
     run_steps(args.warmup)
     torch.cuda.synchronize(dev)
@@ -477,6 +518,8 @@ def run_rank(args, rank, local_rank, world):
     e_start = degree_sum()
     _hip.check(_hip.lib().arreau_profile_edge_kernel(1), "profile on")
     el_eager = timed_loop(args.steps)
+    if args.dump_outputs and not production_graph:
+        outputs = step_outputs()
     mean_ms, launches = ctypes.c_double(), ctypes.c_int64()
     _hip.check(_hip.lib().arreau_edge_kernel_time_ms(ctypes.byref(mean_ms), ctypes.byref(launches)), "edge time")
     conv_ms, conv_launches = ctypes.c_double(), ctypes.c_int64()
@@ -498,12 +541,13 @@ def run_rank(args, rank, local_rank, world):
     else:
         run_steps(3, use_graph=True)  # warm-up of the graph path (capture, instantiation, stream / event creation)
         el_graph = timed_loop(args.steps, use_graph=True)
+        if args.dump_outputs and production_graph:
+            outputs = step_outputs()
         per_rank_graph, el_graph = gather(local_elapsed[0], el_graph)
         check()
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs, rank, world)
 
-    # `value` is the loop the product runs for THIS configuration: the same policy as DiffusionLoss.sample's default
-    # (graph replay from 200 sampler steps on; the 100-step single-crystal config runs eagerly).
-    production_graph = (T - 1) >= 200 and not args.eager_value and not args.no_graph_loop
     elapsed, per_rank = (el_graph, per_rank_graph) if production_graph else (el_eager, per_rank_eager)
     loop_mode = ("hipGraph replay of the captured step" + (f", {groups} pipelined slices per GPU" if groups > 1 else "")
                  if production_graph
@@ -796,6 +840,10 @@ def run_rank_c5(args, rank, local_rank, world):
         dist.all_gather(gathered, tt)
         per_rank = [float(g[0]) for g in gathered]
         elapsed = max(float(g[1]) for g in gathered)
+    if args.dump_outputs:  # the last step's loss and the parameters its optimizer step left (before the loop below recomputes gradients)
+        params = torch.cat([p.detach().reshape(-1).float() for p in model.parameters() if p.requires_grad])
+        dump_outputs(args.dump_outputs, {"loss": loss.detach().reshape(1).cpu().numpy(), "parameters": params.cpu().numpy()},
+                     rank, world)
     # device-only part (forward + backward, no optimizer / collective), for the roofline line
     torch.cuda.synchronize(dev)
     t1 = time.perf_counter()

@@ -55,6 +55,35 @@ def test_gpu_count_comes_from_sysfs_and_visibility_lists(monkeypatch):
     assert "import torch" not in body and "device_count" not in body
 
 
+def test_dump_outputs_files_dtypes_and_budget(tmp_path):
+    """--dump-outputs: one <name>.npy per output in float32 (float64 kept); over the budget every array keeps the same seeded
+    sample of its rows, identical from call to call; rank r > 0 writes <name>.rank<r>.npy within its share of the budget."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    frac = np.arange(3000, dtype=np.float32).reshape(1000, 3)
+    types = np.arange(1000, dtype=np.int32)
+    loss = np.array([0.25])
+    bench.dump_outputs(str(tmp_path / "all"), {"frac": frac, "types": types, "loss": loss})
+    got = {k: np.load(tmp_path / "all" / f"{k}.npy") for k in ("frac", "types", "loss")}
+    assert got["frac"].dtype == np.float32 and got["types"].dtype == np.float32 and got["loss"].dtype == np.float64
+    np.testing.assert_array_equal(got["frac"], frac)
+    np.testing.assert_array_equal(got["types"], types)
+    assert float(got["loss"][0]) == 0.25
+    budget = 8000
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"frac": frac, "types": types}, budget=budget)
+    a = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in ("frac", "types")}
+    b = {k: np.load(tmp_path / "b" / f"{k}.npy") for k in ("frac", "types")}
+    assert 0 < sum(v.nbytes for v in a.values()) <= budget
+    for k in a:
+        np.testing.assert_array_equal(a[k], b[k])
+    np.testing.assert_array_equal(a["frac"], frac[a["types"].astype(np.int64)])  # the same rows of every array
+    bench.dump_outputs(str(tmp_path / "r1"), {"frac": frac}, rank=1, world=2, budget=budget)
+    r1 = np.load(tmp_path / "r1" / "frac.rank1.npy")
+    assert os.listdir(tmp_path / "r1") == ["frac.rank1.npy"] and 0 < r1.nbytes <= budget // 2
+
+
 def test_world_size_mismatch_is_an_error():
     p = _run(["--gpus", "1", "--steps", "1", "--warmup", "0"], ARREAU_BENCH_STUB="1", WORLD_SIZE="2", RANK="0")
     assert p.returncode != 0 and "WORLD_SIZE" in p.stderr

@@ -1,6 +1,6 @@
 """What arreau_model_create's calibration batch measures for several weight sets (GPU box): ARREAU_VERBOSE_CALIBRATION=1 python3 tools/exp/calib_probe.py"""
-import sys, torch
-sys.path.insert(0, "/root/repo")
+import os, sys, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from arreau_amd.checkpoint import make_synthetic_model
 from tests.helpers import make_heavy_tailed
 dev = torch.device("cuda", 0)
