@@ -23,7 +23,7 @@ EXPORTS = [
     "arreau_train_forward", "arreau_train_backward", "arreau_train_conv_stats", "arreau_model_update_train_weights",
     "arreau_debug_sgemm", "arreau_optimizer_create", "arreau_optimizer_step", "arreau_optimizer_destroy",
     "arreau_model_train_weight_pointers", "arreau_model_refresh_derived_train_weights",
-    "arreau_model_set_batch_layout", "arreau_model_set_formats", "arreau_debug_set_pollution", "arreau_debug_leftover_fraction",
+    "arreau_model_set_formats", "arreau_debug_set_pollution", "arreau_debug_leftover_fraction",
 ]
 
 STATUS_NONFINITE, STATUS_BAD_TIMESTEP, STATUS_BAD_TYPE = 1, 2, 4
@@ -118,7 +118,6 @@ def lib():
     L.arreau_debug_sgemm.argtypes = [c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int32,
                                      c_float, c_float, c_void_p]
     L.arreau_model_update_train_weights.argtypes = [c_void_p, POINTER(StateDict), c_void_p]
-    L.arreau_model_set_batch_layout.argtypes = [c_void_p, c_void_p, c_int32, c_int32]
     if hasattr(L, "arreau_model_set_formats") or not os.environ.get("ARREAU_HIP_LIB"):  # (an older build under test: tools/ab.sh)
         L.arreau_model_set_formats.argtypes = [c_void_p, c_int32, c_int32]
     if hasattr(L, "arreau_optimizer_create") or not os.environ.get("ARREAU_HIP_LIB"):

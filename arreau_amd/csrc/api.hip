@@ -58,86 +58,6 @@ Workspace carve(const arreau_config* cfg, int64_t N, int64_t B, void* base, size
     return w;
 }
 
-constexpr int MAX_GROUPS = 8;
-}  // namespace
-
-// Crystal-aligned slices of a batch (host copy of the CSR offsets -> G ranges of about N / G atoms each) and the streams
-// / events the slices run on.  Crystals are independent and every kernel of the network takes a node range over
-// whole-batch arrays (NodeRange), so slice g computes bit for bit what the whole-batch launches compute for its atoms;
-// what changes is WHEN: slices in different phases overlap the HBM-bound message-passing kernel of one with the
-// matrix-bound edge / MLP kernels of another.
-struct arreau_partition {
-    int B = 0, N = 0, G = 1;
-    int eager = 0;  // 1: also slice single evaluations / eager loops (fork-join per step; host-bound, for tests: ARREAU_SLICE_EAGER)
-    int nb[MAX_GROUPS + 1], bb[MAX_GROUPS + 1];
-    hipStream_t stream[MAX_GROUPS] = {};
-    hipEvent_t fork = nullptr, join[MAX_GROUPS] = {}, stagger[MAX_GROUPS] = {};
-    hipGraphExec_t exec[MAX_GROUPS] = {};  // per-slice step graphs of the pipelined sampling loop (cached on graph_key)
-    uint64_t graph_key[12] = {};
-};
-void arreau_partition_destroy(arreau_partition* p) {
-    if (!p) return;
-    for (int g = 0; g < MAX_GROUPS; ++g) {
-        if (p->stream[g]) { (void)hipStreamSynchronize(p->stream[g]); (void)hipStreamDestroy(p->stream[g]); }
-        if (p->join[g]) (void)hipEventDestroy(p->join[g]);
-        if (p->stagger[g]) (void)hipEventDestroy(p->stagger[g]);
-        if (p->exec[g]) (void)hipGraphExecDestroy(p->exec[g]);
-    }
-    if (p->fork) (void)hipEventDestroy(p->fork);
-    delete p;
-}
-
-extern "C" int arreau_model_set_batch_layout(arreau_model* m, const int32_t* h_off, int32_t B, int32_t groups) {
-    ARREAU_REQUIRE(m && (B == 0 || h_off), "arreau_model_set_batch_layout: null pointer");
-    static const int env_groups = [] { const char* e = getenv("ARREAU_GROUPS"); return e ? atoi(e) : 0; }();
-    int G = groups > 0 ? groups : (env_groups > 0 ? env_groups : 1);
-    G = G > MAX_GROUPS ? MAX_GROUPS : G;
-    if (B <= 0 || G <= 1 || B < 2 * G) {  // nothing to slice
-        if (m->part) m->part->G = 1, m->part->B = -1;
-        return ARREAU_OK;
-    }
-    // Slices on SEPARATE STREAMS are an experiment, not a product mode: with kernels of two streams (or two processes)
-    // sharing CUs, one crystal in a few runs came out different at the 1e-8 .. 1e-4 level, and the cause is not known
-    // (DESIGN.md section 8 lists what was ruled out: wait-state hazards around the inline asm -- tools/isa_lint.py --,
-    // miscounted waits, leftover LDS / register / workspace state).  The library refuses them unless the caller opts in
-    // explicitly; ARREAU_SLICE_EAGER=serial (the slices' range launches one after another on ONE stream: what the range
-    // launches compute, without any concurrency) stays available to the tests.
-    const char* se = getenv("ARREAU_SLICE_EAGER");
-    const bool serial_only = se != nullptr && strcmp(se, "serial") == 0;
-    const char* allow = getenv("ARREAU_ALLOW_MULTISTREAM");
-    ARREAU_REQUIRE(serial_only || (allow && atoi(allow) != 0),
-                   "arreau_model_set_batch_layout: slices on separate streams are not reproducible on MI355X (DESIGN.md "
-                   "section 8) and are disabled; ARREAU_ALLOW_MULTISTREAM=1 opts in to the experiment");
-    arreau_partition* p = m->part ? m->part : new arreau_partition();
-    m->part = p;
-    const int N = h_off[B];
-    p->B = B; p->N = N; p->G = G;
-    // ARREAU_SLICE_EAGER: also slice single evaluations (tests).  "serial" = the slices' range launches one after another on
-    // the caller's stream (what the range launches compute, without any concurrency); anything else = fork-join on the
-    // slice streams.
-    p->eager = se == nullptr ? 0 : (serial_only ? 2 : 1);
-    p->bb[0] = 0; p->nb[0] = 0;
-    int b = 0;
-    for (int g = 1; g < G; ++g) {  // cut at the crystal boundary nearest to g N / G (at least one crystal per slice)
-        const long long target = (long long)N * g / G;
-        while (b < B - (G - g) && h_off[b + 1] <= target) ++b;
-        if (b < B - (G - g) && b + 1 <= B && (target - h_off[b]) > (h_off[b + 1] - target)) ++b;
-        if (b <= p->bb[g - 1]) b = p->bb[g - 1] + 1;
-        p->bb[g] = b;
-        p->nb[g] = h_off[b];
-    }
-    p->bb[G] = B; p->nb[G] = N;
-    for (int g = 0; g < G; ++g) {
-        if (!p->stream[g]) ARREAU_CHECK_HIP(hipStreamCreateWithFlags(&p->stream[g], hipStreamNonBlocking));
-        if (!p->join[g]) ARREAU_CHECK_HIP(hipEventCreateWithFlags(&p->join[g], hipEventDisableTiming));
-        if (!p->stagger[g]) ARREAU_CHECK_HIP(hipEventCreateWithFlags(&p->stagger[g], hipEventDisableTiming));
-    }
-    memset(p->graph_key, 0, sizeof(p->graph_key));  // a new layout invalidates the cached slice graphs
-    if (!p->fork) ARREAU_CHECK_HIP(hipEventCreateWithFlags(&p->fork, hipEventDisableTiming));
-    return ARREAU_OK;
-}
-
-namespace {
 // hipEvent pairs around the edge kernel, on the stream it is launched on
 struct EdgeProfile {
     std::mutex mu;
@@ -225,7 +145,7 @@ extern "C" int arreau_edge_kernel_time_ms(double* mean_ms, int64_t* launches) {
 namespace {
 // the edge kernel, bracketed by hipEvents on its own stream when bench.py asked for its launch time
 int run_edge_kernel(const arreau_model* m, const float* dir, const float* dist, const int32_t* deg, const Workspace& w,
-                    int N, hipStream_t s, NodeRange r = NodeRange()) {
+                    int N, hipStream_t s) {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     bool prof = false;
     {
@@ -237,7 +157,7 @@ int run_edge_kernel(const arreau_model* m, const float* dir, const float* dist, 
         ARREAU_CHECK_HIP(hipEventCreate(&e1));
         ARREAU_CHECK_HIP(hipEventRecord(e0, s));
     }
-    const int rc = arreau_launch_edge(m, dir, dist, deg, w.batch, w.lattice, N, w.kbuf, s, r);
+    const int rc = arreau_launch_edge(m, dir, dist, deg, w.batch, w.lattice, N, w.kbuf, s);
     if (prof) {
         ARREAU_CHECK_HIP(hipEventRecord(e1, s));
         std::lock_guard<std::mutex> lock(g_prof.mu);
@@ -249,20 +169,19 @@ int run_edge_kernel(const arreau_model* m, const float* dir, const float* dist, 
 // interaction layers (conv.py:105-129 + convnext.py:20-33) on the embedded features in w.xa, then the read-outs
 int run_layers_and_readout(const arreau_model* m, const Workspace& w, const int32_t* deg, const int32_t* src,
                            const int32_t* d_off, int B, int N, float* d_eps, float* d_logits, float* d_len0,
-                           hipStream_t s, NodeRange r = NodeRange()) {
+                           hipStream_t s) {
     int rc;
     float* xin = w.xa;
     float* xout = w.xb;
     for (int l = 0; l < m->L; ++l) {
-        if ((rc = arreau_launch_node_layer(m, l, w.kbuf, deg, src, xin, w.xc, xout, w.xbar, w.vsum, N, s, r))) return rc;
+        if ((rc = arreau_launch_node_layer(m, l, w.kbuf, deg, src, xin, w.xc, xout, w.xbar, w.vsum, N, s))) return rc;
         float* tmp = xin; xin = xout; xout = tmp;
     }
-    return arreau_launch_readout(m, w.xbar, w.vsum, d_off, B, N, w.gs, d_eps, d_logits, d_len0, s, r);
+    return arreau_launch_readout(m, w.xbar, w.vsum, d_off, B, N, w.gs, d_eps, d_logits, d_len0, s);
 }
 
 // The score network after prep_kernel: neighbour list (unless given), edge kernel, embedding, interaction layers,
-// read-outs -- for the whole batch on `s`, or slice by slice on the partition's streams (forked from / joined to `s`
-// by events, so the caller's stream order is kept and nothing synchronises with the host).
+// read-outs, for the whole batch on `s`.
 int run_network(const arreau_model* m, const Workspace& w, bool given, int32_t* deg, int32_t* src, float* dir, float* dist,
                 const float* d_frac, const int32_t* d_types, const int32_t* d_off, int B, int N, float* d_eps,
                 float* d_logits, float* d_len0, hipStream_t s) {
@@ -278,75 +197,17 @@ int run_network(const arreau_model* m, const Workspace& w, bool given, int32_t* 
         return arreau_general_network(mm, arreau_graph_view{w.batch, deg, src, w.lattice, dir, dist}, d_off, B, N, d_eps, d_logits,
                                       d_len0, s);
     }
-    arreau_partition* p = m->part;
-    // Fork-join slicing of a single evaluation keeps the slices in lockstep (they start together and have the same work),
-    // so it overlaps nothing and costs 4 G extra host calls per step: measured 1.70 / 2.59 ms per step at G = 2 / 4 against
-    // 1.66 ms unsliced (256 x 20, eager).  It stays as the test vehicle of the range launches (ARREAU_SLICE_EAGER); the
-    // sampling loop uses the pipelined form (arreau_sample_loop).
-    const bool sliced = p && p->eager && p->G > 1 && p->B == B && p->N == N && arreau_range_launches_supported(m);
-    if (!sliced) {
-        if (!given) {
-            // neighbour list and embedding side by side in one launch (both need prep_kernel's outputs only)
-            if ((rc = arreau_launch_neighbor_embed(m, w.cart, w.lattice, d_off, w.batch, B, N, deg, src, w.cell, dir, dist, d_frac, d_types,
-                                                   w.cvec, w.xa, s)))
-                return rc;
-            if ((rc = run_edge_kernel(m, dir, dist, deg, w, N, s))) return rc;
-        } else {
-            if ((rc = run_edge_kernel(m, dir, dist, deg, w, N, s))) return rc;
-            if ((rc = arreau_launch_embed(m, d_frac, d_types, w.lattice, w.batch, w.cvec, N, w.xa, s))) return rc;
-        }
-        return run_layers_and_readout(m, w, deg, src, d_off, B, N, d_eps, d_logits, d_len0, s);
-    }
-    static const int n_cu = [] {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-            return (int)prop.multiProcessorCount;
-        return 256;
-    }();
-    static const int cap_env = [] { const char* e = getenv("ARREAU_GROUP_WGS"); return e ? atoi(e) : 0; }();
-    const int cap = cap_env > 0 ? cap_env : (n_cu + p->G - 1) / p->G;
-    static const int dbg_mode = [] { const char* e = getenv("ARREAU_DEBUG_SLICE_MODE"); return e ? atoi(e) : 0; }();
-    if (dbg_mode) {
-        // debugging aid: 1 = only the edge kernels run sliced (neighbour lists before, everything else after, on `s`);
-        //                2 = neighbour list + edge kernel sliced, the rest whole-batch on `s`
-        if (dbg_mode == 1 && !given &&
-            (rc = arreau_launch_neighbor(w.cart, w.lattice, d_off, w.batch, B, N, m->cfg.radius, m->k, deg, src, w.cell, dir, dist, s)))
+    if (!given) {
+        // neighbour list and embedding side by side in one launch (both need prep_kernel's outputs only)
+        if ((rc = arreau_launch_neighbor_embed(m, w.cart, w.lattice, d_off, w.batch, B, N, deg, src, w.cell, dir, dist, d_frac, d_types,
+                                               w.cvec, w.xa, s)))
             return rc;
-        ARREAU_CHECK_HIP(hipEventRecord(p->fork, s));
-        for (int g = 0; g < p->G; ++g) {
-            hipStream_t sg = p->stream[g];
-            ARREAU_CHECK_HIP(hipStreamWaitEvent(sg, p->fork, 0));
-            NodeRange r;
-            r.n0 = p->nb[g]; r.n1 = p->nb[g + 1]; r.b0 = p->bb[g]; r.b1 = p->bb[g + 1]; r.wg_cap = cap;
-            if (dbg_mode == 2 && !given &&
-                (rc = arreau_launch_neighbor(w.cart, w.lattice, d_off, w.batch, B, N, m->cfg.radius, m->k, deg, src, w.cell, dir, dist, sg, r)))
-                return rc;
-            if ((rc = run_edge_kernel(m, dir, dist, deg, w, N, sg, r))) return rc;
-            ARREAU_CHECK_HIP(hipEventRecord(p->join[g], sg));
-            ARREAU_CHECK_HIP(hipStreamWaitEvent(s, p->join[g], 0));
-        }
+        if ((rc = run_edge_kernel(m, dir, dist, deg, w, N, s))) return rc;
+    } else {
+        if ((rc = run_edge_kernel(m, dir, dist, deg, w, N, s))) return rc;
         if ((rc = arreau_launch_embed(m, d_frac, d_types, w.lattice, w.batch, w.cvec, N, w.xa, s))) return rc;
-        return run_layers_and_readout(m, w, deg, src, d_off, B, N, d_eps, d_logits, d_len0, s);
     }
-    const bool serial = p->eager == 2;
-    if (!serial) ARREAU_CHECK_HIP(hipEventRecord(p->fork, s));
-    for (int g = 0; g < p->G; ++g) {
-        hipStream_t sg = serial ? s : p->stream[g];
-        if (!serial) ARREAU_CHECK_HIP(hipStreamWaitEvent(sg, p->fork, 0));
-        NodeRange r;
-        r.n0 = p->nb[g]; r.n1 = p->nb[g + 1]; r.b0 = p->bb[g]; r.b1 = p->bb[g + 1]; r.wg_cap = cap;
-        if (!given && (rc = arreau_launch_neighbor(w.cart, w.lattice, d_off, w.batch, B, N, m->cfg.radius, m->k, deg, src, w.cell, dir, dist, sg, r)))
-            return rc;
-        if ((rc = run_edge_kernel(m, dir, dist, deg, w, N, sg, r))) return rc;
-        if ((rc = arreau_launch_embed(m, d_frac, d_types, w.lattice, w.batch, w.cvec, N, w.xa, sg, r))) return rc;
-        if ((rc = run_layers_and_readout(m, w, deg, src, d_off, B, N, d_eps, d_logits, d_len0, sg, r))) return rc;
-        if (!serial) {
-            ARREAU_CHECK_HIP(hipEventRecord(p->join[g], sg));
-            ARREAU_CHECK_HIP(hipStreamWaitEvent(s, p->join[g], 0));
-        }
-    }
-    return ARREAU_OK;
+    return run_layers_and_readout(m, w, deg, src, d_off, B, N, d_eps, d_logits, d_len0, s);
 }
 }  // namespace
 
@@ -425,28 +286,6 @@ __global__ void fill_i32_kernel(int32_t* __restrict__ p, int32_t v, int n) {
     if (i < n) p[i] = v;
 }
 
-// One step of ONE slice of the batch, entirely on stream `s` (prep, network and updates restricted to the slice's crystals
-// and atoms): slices are independent samplers that share the weights, so their chains need no synchronisation at all.
-int enqueue_slice_step(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
-                       const int32_t* d_off, int B, int N, uint64_t seed, const int32_t* d_const_types,
-                       const float* d_fixed_lengths, float* d_lattice, const Workspace& w, hipStream_t s, NodeRange r,
-                       hipEvent_t after_edge) {
-    int rc;
-    if ((rc = arreau_launch_prep(m, d_frac, d_lengths, d_angles, nullptr, d_off, B, N, w.lattice, w.cart, w.batch, w.cvec, s,
-                                 w.t_next, w.t_cur, r)))
-        return rc;
-    if ((rc = arreau_launch_neighbor_embed(m, w.cart, w.lattice, d_off, w.batch, B, N, w.deg, w.src, w.cell, w.dir, w.dist, d_frac,
-                                           d_types, w.cvec, w.xa, s, r)))
-        return rc;
-    if ((rc = run_edge_kernel(m, w.dir, w.dist, w.deg, w, N, s, r))) return rc;
-    if (after_edge) ARREAU_CHECK_HIP(hipEventRecord(after_edge, s));
-    // (the per-crystal pooling of the lattice read-out happens inside the lattice update: no launch of its own)
-    if ((rc = run_layers_and_readout(m, w, w.deg, w.src, d_off, B, N, w.eps, w.logits, nullptr, s, r))) return rc;
-    return arreau_launch_reverse(m, d_frac, d_types, d_lengths, d_angles, w.t_cur, d_off, B, N, w.eps, w.logits, w.len0,
-                                 StepNoiseSrc{nullptr, nullptr, nullptr, seed}, d_const_types, d_lattice, s, d_fixed_lengths, r,
-                                 w.gs, w.batch);
-}
-
 // The single-stream product loop runs WITHOUT a prep launch per step (round 3) when it can: the update launch of step i
 // leaves the lattice and the per-crystal embedding of step i + 1 behind (reverse_crystal_block), the neighbour-list waves form
 // the Cartesian positions themselves and advance the device-side timestep (neighbor_embed_kernel<LOOP>), and ONE prep launch
@@ -454,8 +293,7 @@ int enqueue_slice_step(const arreau_model* m, float* d_frac, int32_t* d_types, f
 // (A/B, tests: the two loops are bit-identical).
 bool loop_without_prep(const arreau_model* m) {
     const char* e = getenv("ARREAU_LOOP_PREP");
-    const arreau_partition* p = m->part;
-    return !(e && atoi(e) != 0) && !arreau_general_path(m) && !(p && p->eager && p->G > 1);
+    return !(e && atoi(e) != 0) && !arreau_general_path(m);
 }
 
 int enqueue_sample_step(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
@@ -464,13 +302,13 @@ int enqueue_sample_step(const arreau_model* m, float* d_frac, int32_t* d_types, 
     int rc;
     if (no_prep) {
         if ((rc = arreau_launch_neighbor_embed(m, nullptr, w.lattice, d_off, w.batch, B, N, w.deg, w.src, w.cell, w.dir, w.dist, d_frac,
-                                               d_types, w.cvec, w.xa, s, NodeRange(), w.t_cur)))
+                                               d_types, w.cvec, w.xa, s, w.t_cur)))
             return rc;
         if ((rc = run_edge_kernel(m, w.dir, w.dist, w.deg, w, N, s))) return rc;
         if ((rc = run_layers_and_readout(m, w, w.deg, w.src, d_off, B, N, w.eps, w.logits, nullptr, s))) return rc;
         return arreau_launch_reverse(m, d_frac, d_types, d_lengths, d_angles, w.t_cur, d_off, B, N, w.eps, w.logits, w.len0,
                                      StepNoiseSrc{nullptr, nullptr, nullptr, seed}, d_const_types, d_lattice, s, d_fixed_lengths,
-                                     NodeRange(), w.gs, w.batch, w.lattice, w.cvec);
+                                     w.gs, w.batch, w.lattice, w.cvec);
     }
     if ((rc = arreau_launch_prep(m, d_frac, d_lengths, d_angles, nullptr, d_off, B, N, w.lattice, w.cart, w.batch, w.cvec, s,
                                  w.t_next, w.t_cur)))
@@ -482,7 +320,7 @@ int enqueue_sample_step(const arreau_model* m, float* d_frac, int32_t* d_types, 
         return rc;
     return arreau_launch_reverse(m, d_frac, d_types, d_lengths, d_angles, w.t_cur, d_off, B, N, w.eps, w.logits, w.len0,
                                  StepNoiseSrc{nullptr, nullptr, nullptr, seed}, d_const_types, d_lattice, s, d_fixed_lengths,
-                                 NodeRange(), pool_in_update ? w.gs : nullptr, w.batch);
+                                 pool_in_update ? w.gs : nullptr, w.batch);
 }
 }  // namespace
 
@@ -504,16 +342,13 @@ extern "C" int arreau_sample_loop(arreau_model* m, float* d_frac, int32_t* d_typ
     if (n_steps == 0) return ARREAU_OK;
     hipStream_t s = (hipStream_t)stream;
     int rc;
-    // (slices on their own streams -- the opt-in experiment below -- keep the prep launch per step)
-    const bool sliced_loop = use_graph && n_steps >= 3 && m->part && m->part->G > 1 && m->part->eager != 2 && m->part->B == B &&
-                             m->part->N == N && arreau_range_launches_supported(m);
-    const bool no_prep = !sliced_loop && loop_without_prep(m);
+    const bool no_prep = loop_without_prep(m);
     if (no_prep) {
         // t_cur holds the timestep of the step in progress; every step's first launch advances it, so it starts one above
         ARREAU_LAUNCH(fill_i32_kernel, dim3((B + 255) / 256), dim3(256), 0, s, w.t_cur, t_start + 1, B);
         ARREAU_CHECK_HIP(hipGetLastError());
         if ((rc = arreau_launch_prep(m, d_frac, d_lengths, d_angles, w.t_cur, d_off, B, N, w.lattice, w.cart, w.batch, w.cvec, s, nullptr,
-                                     nullptr, NodeRange(), -1)))
+                                     nullptr, -1)))
             return rc;
     } else {
         ARREAU_LAUNCH(fill_i32_kernel, dim3((B + 255) / 256), dim3(256), 0, s, w.t_next, t_start, B);
@@ -524,71 +359,6 @@ extern "C" int arreau_sample_loop(arreau_model* m, float* d_frac, int32_t* d_typ
             if ((rc = enqueue_sample_step(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types, d_fixed_lengths, d_lattice, w, s, no_prep)))
                 return rc;
         return ARREAU_OK;
-    }
-    // Pipelined slices: when the batch has a layout with G > 1 slices (arreau_model_set_batch_layout), every slice runs its
-    // own chain of steps on its own stream -- one captured graph per slice, replayed n_steps - 1 times -- with NO
-    // synchronisation between slices until the end of the loop.  The first steps are staggered (slice g starts when slice
-    // g - 1 has finished its edge kernel), so the slices stay in different phases: while one is in its matrix-bound edge
-    // kernel another streams its K blocks from HBM.  Every slice computes exactly what it computes in the whole-batch run.
-    {
-        arreau_partition* p = m->part;
-        if (p && p->G > 1 && p->eager != 2 && p->B == B && p->N == N && arreau_range_launches_supported(m)) {
-            static const int n_cu = [] {
-                int dev = 0;
-                hipDeviceProp_t prop;
-                if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-                    return (int)prop.multiProcessorCount;
-                return 256;
-            }();
-            static const int cap_env = [] { const char* e = getenv("ARREAU_GROUP_WGS"); return e ? atoi(e) : 0; }();
-            const int cap = cap_env > 0 ? cap_env : (n_cu + p->G - 1) / p->G;
-            const uint64_t key[12] = {(uint64_t)d_frac, (uint64_t)d_types, (uint64_t)d_lengths, (uint64_t)d_angles, (uint64_t)d_off,
-                                      ((uint64_t)(uint32_t)B << 32) | (uint32_t)N, seed, (uint64_t)d_const_types,
-                                      (uint64_t)d_fixed_lengths, (uint64_t)d_lattice, (uint64_t)d_workspace,
-                                      ((uint64_t)(uint32_t)p->G << 32) | (uint32_t)cap};
-            const bool cached = p->exec[0] && memcmp(key, p->graph_key, sizeof(key)) == 0;
-            ARREAU_CHECK_HIP(hipEventRecord(p->fork, s));
-            NodeRange r[MAX_GROUPS];
-            for (int g = 0; g < p->G; ++g) {
-                r[g].n0 = p->nb[g]; r[g].n1 = p->nb[g + 1]; r[g].b0 = p->bb[g]; r[g].b1 = p->bb[g + 1]; r[g].wg_cap = cap;
-                ARREAU_CHECK_HIP(hipStreamWaitEvent(p->stream[g], p->fork, 0));
-                if (g > 0) ARREAU_CHECK_HIP(hipStreamWaitEvent(p->stream[g], p->stagger[g - 1], 0));
-                // first step eagerly (stagger point + lazy module loading outside any capture)
-                if ((rc = enqueue_slice_step(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types,
-                                             d_fixed_lengths, d_lattice, w, p->stream[g], r[g], p->stagger[g])))
-                    return rc;
-            }
-            if (!cached) {
-                for (int g = 0; g < p->G; ++g) {
-                    if (p->exec[g]) {
-                        (void)hipStreamSynchronize(p->stream[g]);
-                        (void)hipGraphExecDestroy(p->exec[g]);
-                        p->exec[g] = nullptr;
-                    }
-                    hipGraph_t graph = nullptr;
-                    ARREAU_CHECK_HIP(hipStreamBeginCapture(p->stream[g], hipStreamCaptureModeThreadLocal));
-                    rc = enqueue_slice_step(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types,
-                                            d_fixed_lengths, d_lattice, w, p->stream[g], r[g], nullptr);
-                    hipError_t e = hipStreamEndCapture(p->stream[g], &graph);
-                    if (rc) {
-                        if (graph) (void)hipGraphDestroy(graph);
-                        return rc;
-                    }
-                    ARREAU_CHECK_HIP(e);
-                    e = hipGraphInstantiate(&p->exec[g], graph, nullptr, nullptr, 0);
-                    (void)hipGraphDestroy(graph);
-                    ARREAU_CHECK_HIP(e);
-                }
-                memcpy(p->graph_key, key, sizeof(key));
-            }
-            for (int i = 1; i < n_steps; ++i)
-                for (int g = 0; g < p->G; ++g) ARREAU_CHECK_HIP(hipGraphLaunch(p->exec[g], p->stream[g]));
-            for (int g = 0; g < p->G; ++g) {
-                ARREAU_CHECK_HIP(hipEventRecord(p->join[g], p->stream[g]));
-                ARREAU_CHECK_HIP(hipStreamWaitEvent(s, p->join[g], 0));
-            }
-            return ARREAU_OK;
-        }
     }
     // One step captured into a hipGraph and replayed: the timestep lives on the device (prep_kernel advances it), the noise
     // is a function of (seed, timestep, element), so every replay is the next step of the same trajectory as the eager loop.
@@ -618,7 +388,7 @@ extern "C" int arreau_sample_loop(arreau_model* m, float* d_frac, int32_t* d_typ
                                                     // (ARREAU_BASIS_MIN_RECEIVERS, ARREAU_FUSE_SMALL) and on the conv variant:
                                                     // a changed switch must not replay the stale graph
                                                     (arreau_basis_form(m, N) ? 0x20000 : 0) | (arreau_basis_fp8(m) ? 0x40000 : 0) | (arreau_cross_fp8(m) ? 0x400000 : 0) |
-                                                    (arreau_small_layer_fusable(m, N, NodeRange()) ? 0x80000 : 0) |
+                                                    (arreau_small_layer_fusable(m, N) ? 0x80000 : 0) |
                                                     ((m->conv_variant & 3) << 20)) << 32) | (uint32_t)m->mlp_variant};
     hipGraphExec_t exec = (hipGraphExec_t)m->retired_graph;
     int first_replay = 0;
@@ -684,13 +454,7 @@ unsigned g_pollute_launches = 0;
 }  // namespace
 
 int arreau_debug_pollute(hipStream_t s) {
-    static const int n_cu = [] {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-            return (int)prop.multiProcessorCount;
-        return 256;
-    }();
+    const int n_cu = arreau_cu_count();
     if (!g_pollute_counter) {
         ARREAU_CHECK_HIP(hipMalloc(&g_pollute_counter, 8));
         ARREAU_CHECK_HIP(hipMemset(g_pollute_counter, 0, 8));
@@ -727,10 +491,7 @@ __global__ __launch_bounds__(1024) void leftover_kernel(unsigned pattern, unsign
 
 extern "C" int arreau_debug_leftover_fraction(uint32_t pattern, double* lds_fraction, double* reg_fraction, void* stream) {
     ARREAU_REQUIRE(lds_fraction && reg_fraction, "arreau_debug_leftover_fraction: null pointer");
-    int dev = 0, n_cu = 256;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-        n_cu = prop.multiProcessorCount;
+    const int n_cu = arreau_cu_count();
     unsigned long long* d_counts = nullptr;
     ARREAU_CHECK_HIP(hipMalloc(&d_counts, 16));
     hipStream_t s = (hipStream_t)stream;

@@ -581,23 +581,14 @@ __global__ __launch_bounds__(64 * (PW + 4), (PW + 4) / 4) void conv_proj_kernel(
 
 // the launcher: one persistent workgroup per CU (a multiple of 8 workgroups keeps the XCD-aware order)
 int arreau_launch_conv_proj(const arreau_model* m, int layer, const float* basis, const int32_t* deg, const int32_t* src,
-                            const float* x_in, float* x_conv, int N, hipStream_t s, NodeRange r) {
-    const int n0 = r.n0, n1 = r.n1 < 0 ? N : r.n1;
-    const int Ng = n1 - n0;
-    if (Ng <= 0) return ARREAU_OK;
+                            const float* x_in, float* x_conv, int N, hipStream_t s) {
+    if (N <= 0) return ARREAU_OK;
     if (!(m->C == 128 && m->D == 256 && m->k == 8 && m->f16_ok)) {
         arreau_set_error("conv_proj kernel: unsupported (hidden_dim, basis_dim, max_neighbors) or weights beyond the fp16 range");
         return ARREAU_EINVAL;
     }
-    static const int n_cu = [] {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-            return (int)prop.multiProcessorCount;
-        return 256;
-    }();
-    int blocks = Ng < n_cu ? Ng : n_cu;
-    if (r.wg_cap > 0 && blocks > r.wg_cap) blocks = r.wg_cap;
+    const int n_cu = arreau_cu_count();
+    const int blocks = N < n_cu ? N : n_cu;
     constexpr int TC = 4, TD = 8, NF1 = 12, NF2 = 16, NF3 = 32;  // chunk geometry of the packed edge stream (edge_f16.hip)
     const u32x4* stream = reinterpret_cast<const u32x4*>(m->edge_f16);
     const u32x4* wchunks = stream + ((size_t)TC * NF1 + (size_t)TD * NF2 + (size_t)layer * TC * NF3) * 64;
@@ -611,7 +602,7 @@ int arreau_launch_conv_proj(const arreau_model* m, int layer, const float* basis
     const u32x4* x8w = reinterpret_cast<const u32x4*>(m->conv_x8) + (size_t)layer * (m->C / 16) * (m->D / 64) * 2 * 64;
     auto launch = [&](auto kernel, int threads) {
         ARREAU_LAUNCH(kernel, dim3(blocks), dim3(threads), 0, s, reinterpret_cast<const u32x4*>(basis), wchunks, x8w, deg, src, x_in,
-                      m->fk + (size_t)layer * 16 * 16 * m->C, m->conv_bias + (size_t)layer * m->C, n0, Ng, x_conv, reverse);
+                      m->fk + (size_t)layer * 16 * 16 * m->C, m->conv_bias + (size_t)layer * m->C, 0, N, x_conv, reverse);
     };
     const bool fp8 = arreau_basis_fp8(m);
     arreau_prof_conv(0, s);

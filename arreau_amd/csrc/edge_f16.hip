@@ -774,9 +774,8 @@ __global__ __launch_bounds__(512) void edge_kernel_f16x3_split(
 }
 
 int arreau_launch_edge_f16x3(const arreau_model* m, const float* dir, const float* dist, const int32_t* deg,
-                             const int32_t* batch, const float* lattice, int N, float* kbuf, hipStream_t s, NodeRange r) {
-    const int n0 = r.n0, n1 = r.n1 < 0 ? N : r.n1;
-    if (n1 <= n0) return ARREAU_OK;
+                             const int32_t* batch, const float* lattice, int N, float* kbuf, hipStream_t s) {
+    if (N <= 0) return ARREAU_OK;
     if (!(m->C == 128 && m->D == 256 && m->k <= 8)) {
         arreau_set_error("edge kernel (fp16x3): unsupported (hidden_dim, basis_dim, max_neighbors)");
         return ARREAU_EINVAL;
@@ -786,55 +785,41 @@ int arreau_launch_edge_f16x3(const arreau_model* m, const float* dir, const floa
     // Persistent: one workgroup per CU walks the receiver pairs with stride gridDim (ARREAU_EDGE_WGS overrides the
     // workgroup count, e.g. to (N+1)/2 for one pair per workgroup).
     static const int wgs_env = [] { const char* e = getenv("ARREAU_EDGE_WGS"); return e ? atoi(e) : 0; }();
-    static const int n_cu = [] {  // CUs of the current device (one process drives one GPU)
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-            return (int)prop.multiProcessorCount;
-        return 256;
-    }();
     // Small launches: one tile per workgroup, output chunks split over its waves (bit-identical K tiles): while the tiles
     // are fewer than the chip's wave slots the persistent form above is one wave's latency (62 us at 1 x 8 atoms).
     static const int split_env = [] { const char* e = getenv("ARREAU_EDGE_SPLIT"); return e ? atoi(e) : -1; }();
     const bool split_ok = m->L * 4 >= 8 && m->L * 4 <= 24;
-    // Whole-batch launches only: in every single-stream test the K tiles are bit-identical to the persistent form's, but when
-    // two slices of a batch run on separate streams (arreau_model_set_batch_layout) and one slice's neighbour-list kernel
-    // overlaps the other's tile-per-workgroup edge kernel, about one evaluation in ten came out different at the 1e-5
-    // level (tools/exp/debug_sliced4.py / debug_sliced5.py; never with the persistent form, never when the neighbour lists
-    // were built before the fork): one receiver of the later slice gets a neighbour list without its nearest candidate.
-    // Inputs are identical from evaluation to evaluation; the cause is not found.  Slices exist for batches of thousands of
-    // atoms, far above the switch-over, so nothing is lost by keeping the small-launch form to unsliced launches.
-    const bool whole_batch = n0 == 0 && n1 == N && r.wg_cap == 0;
+    // The K tiles are bit-identical to the persistent form's on one stream.  Beside another stream's neighbour-list kernel
+    // (the withdrawn batch-slicing experiment) about one evaluation in ten came out different at the 1e-5 level, never with
+    // the persistent form; the cause is not found.  The library runs one stream.
     const bool use_split = split_ok && !arreau_basis_form(m, N) &&
-                           (split_env >= 0 ? split_env != 0 : (whole_batch && (n1 - n0) <= ARREAU_EDGE_SPLIT_MAX_NODES));
+                           (split_env >= 0 ? split_env != 0 : N <= ARREAU_EDGE_SPLIT_MAX_NODES);
     if (use_split) {
         auto launch = [&](auto kernel) {
-            ARREAU_LAUNCH(kernel, dim3((unsigned)(n1 - n0) * 4), dim3(512), 0, s, dir, dist, deg, batch, lattice, m->ori,
-                               reinterpret_cast<const u32x4*>(m->edge_f16), m->b1, m->b2, m->cfg.radius, N, m->k, m->L, kbuf, n0);
+            ARREAU_LAUNCH(kernel, dim3((unsigned)N * 4), dim3(512), 0, s, dir, dist, deg, batch, lattice, m->ori,
+                               reinterpret_cast<const u32x4*>(m->edge_f16), m->b1, m->b2, m->cfg.radius, N, m->k, m->L, kbuf, 0);
         };
         if (arreau_basis_fp8(m)) launch(edge_kernel_f16x3_split<128, 256, false, true>);
         else launch(edge_kernel_f16x3_split<128, 256, false, false>);
         ARREAU_CHECK_HIP(hipGetLastError());
         return ARREAU_OK;
     }
-    const int npairs = (n1 - n0 + 1) / 2;
-    int wgs = wgs_env > 0 ? (wgs_env < npairs ? wgs_env : npairs) : (npairs < n_cu ? npairs : n_cu);
-    if (r.wg_cap > 0 && wgs > r.wg_cap) wgs = r.wg_cap;
-    // (decided from the WHOLE batch, not from this launch's range: the two forms lay the shared kbuf region out differently,
-    // so slices of one batch on either side of the threshold must not mix them -- ADVICE round 3)
+    const int npairs = (N + 1) / 2;
+    const int n_cu = arreau_cu_count();
+    const int wgs = wgs_env > 0 ? (wgs_env < npairs ? wgs_env : npairs) : (npairs < n_cu ? npairs : n_cu);
     if (arreau_basis_form(m, N)) {  // stop after layer 2, store the basis planes (the node-layer launcher projects them)
         if (arreau_basis_fp8(m))
             ARREAU_LAUNCH((edge_kernel_f16x3<128, 256, 8, false, false, true>), dim3(wgs), dim3(512), 0, s, dir, dist, deg, batch, lattice, m->ori,
-                          reinterpret_cast<const u32x4*>(m->edge_f16), m->b1, m->b2, m->cfg.radius, N, m->k, m->L, kbuf, n0, n1);
+                          reinterpret_cast<const u32x4*>(m->edge_f16), m->b1, m->b2, m->cfg.radius, N, m->k, m->L, kbuf, 0, N);
         else
             ARREAU_LAUNCH((edge_kernel_f16x3<128, 256, 8, false, false, false>), dim3(wgs), dim3(512), 0, s, dir, dist, deg, batch, lattice, m->ori,
-                          reinterpret_cast<const u32x4*>(m->edge_f16), m->b1, m->b2, m->cfg.radius, N, m->k, m->L, kbuf, n0, n1);
+                          reinterpret_cast<const u32x4*>(m->edge_f16), m->b1, m->b2, m->cfg.radius, N, m->k, m->L, kbuf, 0, N);
         ARREAU_CHECK_HIP(hipGetLastError());
         return ARREAU_OK;
     }
     auto launch = [&](auto kernel) {
         ARREAU_LAUNCH(kernel, dim3(wgs), dim3(512), 0, s, dir, dist, deg, batch, lattice, m->ori,
-                           reinterpret_cast<const u32x4*>(m->edge_f16), m->b1, m->b2, m->cfg.radius, N, m->k, m->L, kbuf, n0, n1);
+                           reinterpret_cast<const u32x4*>(m->edge_f16), m->b1, m->b2, m->cfg.radius, N, m->k, m->L, kbuf, 0, N);
     };
     if (arreau_basis_fp8(m)) launch(edge_kernel_f16x3<128, 256, 8, false, true, true>);
     else launch(edge_kernel_f16x3<128, 256, 8, false, true, false>);

@@ -112,13 +112,12 @@ __global__ __launch_bounds__(256) void neighbor_embed_kernel(
 
 int arreau_launch_neighbor(const float* cart, const float* lattice, const int32_t* offsets, const int32_t* batch,
                            int B, int N, float radius, int k, int32_t* deg, int32_t* src, int32_t* cell, float* dir, float* dist,
-                           hipStream_t s, NodeRange r) {
-    const int n0 = r.n0, n1 = r.n1 < 0 ? N : r.n1;
-    if (n1 <= n0) return ARREAU_OK;
+                           hipStream_t s) {
+    if (N <= 0) return ARREAU_OK;
     const float r2 = (float)((double)radius * (double)radius);
     const int waves_per_block = 4;
-    ARREAU_LAUNCH(neighbor_kernel, dim3((n1 - n0 + waves_per_block - 1) / waves_per_block), dim3(64 * waves_per_block),
-                       0, s, cart, lattice, offsets, batch, B, n0, n1, r2, k, deg, src, cell, dir, dist);
+    ARREAU_LAUNCH(neighbor_kernel, dim3((N + waves_per_block - 1) / waves_per_block), dim3(64 * waves_per_block),
+                       0, s, cart, lattice, offsets, batch, B, 0, N, r2, k, deg, src, cell, dir, dist);
     ARREAU_CHECK_HIP(hipGetLastError());
     return ARREAU_OK;
 }
@@ -126,27 +125,25 @@ int arreau_launch_neighbor(const float* cart, const float* lattice, const int32_
 int arreau_launch_neighbor_embed(const arreau_model* m, const float* cart, const float* lattice, const int32_t* offsets,
                                  const int32_t* batch, int B, int N, int32_t* deg, int32_t* src, int32_t* cell, float* dir,
                                  float* dist, const float* frac, const int32_t* types, const float* cvec, float* x0, hipStream_t s,
-                                 NodeRange r, int32_t* tick) {
-    const int n0 = r.n0, n1 = r.n1 < 0 ? N : r.n1;
-    if (n1 <= n0 && tick == nullptr) return ARREAU_OK;
+                                 int32_t* tick) {
+    if (N <= 0 && tick == nullptr) return ARREAU_OK;
     ARREAU_REQUIRE(batch != nullptr, "neighbour list + embedding: the atom -> crystal map is required");
     const float r2 = (float)((double)m->cfg.radius * (double)m->cfg.radius);
-    const long long pairs = (long long)(n1 - n0) * (m->C / 4);
+    const long long pairs = (long long)N * (m->C / 4);
     if (pairs >= (1ll << 31)) {
         arreau_set_error("embed kernel: more than 2^31 (atom, channel group) pairs in one launch");
         return ARREAU_EINVAL;
     }
-    const unsigned embed_blocks = (unsigned)((pairs + 255) / 256), nbr_blocks = (unsigned)((n1 - n0 + 3) / 4);
+    const unsigned embed_blocks = (unsigned)((pairs + 255) / 256), nbr_blocks = (unsigned)((N + 3) / 4);
     if (tick != nullptr) {
-        // sampling loop: positions from `frac` (the `cart` argument is not read), timesteps of crystals b0 .. b1-1 advanced
-        const int b0 = r.b0, b1 = r.b1 < 0 ? B : r.b1;
-        const unsigned tick_blocks = (unsigned)((b1 - b0 + 255) / 256);
+        // sampling loop: positions from `frac` (the `cart` argument is not read), every crystal's timestep advanced
+        const unsigned tick_blocks = (unsigned)((B + 255) / 256);
         const unsigned grid = embed_blocks + nbr_blocks > tick_blocks ? embed_blocks + nbr_blocks : tick_blocks;  // (extra workgroups only tick)
-        ARREAU_LAUNCH(neighbor_embed_kernel<true>, dim3(grid), dim3(256), 0, s, embed_blocks, frac, lattice, offsets, batch, B, n0, n1, r2,
-                      m->k, deg, src, cell, dir, dist, frac, types, cvec, m->ori, m->embT, m->S, m->C, x0, m->status, tick, b0, b1);
+        ARREAU_LAUNCH(neighbor_embed_kernel<true>, dim3(grid), dim3(256), 0, s, embed_blocks, frac, lattice, offsets, batch, B, 0, N, r2,
+                      m->k, deg, src, cell, dir, dist, frac, types, cvec, m->ori, m->embT, m->S, m->C, x0, m->status, tick, 0, B);
     } else {
         ARREAU_LAUNCH(neighbor_embed_kernel<false>, dim3(embed_blocks + nbr_blocks), dim3(256), 0, s, embed_blocks, cart, lattice, offsets,
-                      batch, B, n0, n1, r2, m->k, deg, src, cell, dir, dist, frac, types, cvec, m->ori, m->embT, m->S, m->C, x0, m->status,
+                      batch, B, 0, N, r2, m->k, deg, src, cell, dir, dist, frac, types, cvec, m->ori, m->embT, m->S, m->C, x0, m->status,
                       (int32_t*)nullptr, 0, 0);
     }
     ARREAU_CHECK_HIP(hipGetLastError());

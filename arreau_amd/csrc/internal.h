@@ -14,8 +14,6 @@
 #define ARREAU_ORI 16
 
 struct arreau_train_ctx;
-struct arreau_partition;
-void arreau_partition_destroy(struct arreau_partition* p);
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -69,9 +67,6 @@ struct arreau_model {
     // form, and the step's activation buffers (created on first use)
     const float *t_w1f, *t_w2, *t_wk, *t_lin1, *t_lin2, *t_ro_w;
     struct arreau_train_ctx* train;
-    // crystal-aligned slices of the batch the score network may be run in, on separate streams (api.hip: set by
-    // arreau_model_set_batch_layout; used when (B, N) of a call match and the default kernel set is selected)
-    struct arreau_partition* part;
     int fused;               // 1: shape (C, D, W) = (128, 256, 4), the fused kernels' packed weights exist
     int packed_stale;        // 1 after arreau_model_update_train_weights: the sampling kernels' packed planes are out of date
     void* loop_stream;       // hipStream_t / hipEvent_t of arreau_sample_loop's graph mode (capture is not allowed on the
@@ -230,13 +225,18 @@ int arreau_general_network(arreau_model* m, const arreau_graph_view& g, const in
 float* arreau_general_x0(arreau_model* m, int N, int B, hipStream_t s);  // (re)sizes the context; returns its layer-0 feature buffer
 void arreau_model_retire_graph(arreau_model* m, void* exec, void* stream);  // takes ownership; frees the previous one
 
-// A launch over part of the batch: receivers / atoms n0 .. n1-1 (n1 < 0: all), crystals b0 .. b1-1, and for the persistent
-// kernels a cap on the workgroup count (0: one per CU).  All arrays stay whole-batch arrays with absolute indices, so a
-// range launch computes bit for bit what the whole-batch launch computes for those atoms: arreau_predict_scores uses it
-// to run crystal-aligned slices of the batch on separate streams (api.hip).
-struct NodeRange {
-    int n0 = 0, n1 = -1, b0 = 0, b1 = -1, wg_cap = 0;
-};
+// CUs of the current device, queried once per process (one process drives one GPU); 256 if the query fails.  The persistent
+// kernels launch one workgroup per CU.
+inline int arreau_cu_count() {
+    static const int n_cu = [] {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
+            return (int)prop.multiProcessorCount;
+        return 256;
+    }();
+    return n_cu;
+}
 
 // Debug aid (api.hip, "uninitialised-state probe"): when a pollution pattern is set (arreau_debug_set_pollution), every
 // kernel launch of the sampling path is preceded, on the same stream, by a kernel that fills every CU's LDS and vector
@@ -257,37 +257,37 @@ int arreau_debug_pollute(hipStream_t s);
 int arreau_launch_fiber_precompute(arreau_model* m, hipStream_t s);
 int arreau_launch_neighbor(const float* cart, const float* lattice, const int32_t* offsets, const int32_t* batch, int B, int N,
                            float radius, int k, int32_t* deg, int32_t* src, int32_t* cell, float* dir, float* dist,
-                           hipStream_t s, NodeRange r = NodeRange());
+                           hipStream_t s);
 // neighbour list + embedding of the sampler's node features in one launch (graph.hip; both read prep_kernel's outputs only)
 int arreau_launch_neighbor_embed(const arreau_model* m, const float* cart, const float* lattice, const int32_t* offsets,
                                  const int32_t* batch, int B, int N, int32_t* deg, int32_t* src, int32_t* cell, float* dir,
                                  float* dist, const float* frac, const int32_t* types, const float* cvec, float* x0, hipStream_t s,
-                                 NodeRange r = NodeRange(), int32_t* tick = nullptr /* sampling loop without a prep launch: see the kernel */);
+                                 int32_t* tick = nullptr /* sampling loop without a prep launch: see the kernel */);
 int arreau_launch_prep(const arreau_model* m, const float* frac, const float* lengths, const float* angles,
                        const int32_t* t, const int32_t* offsets, int B, int N, float* lattice, float* cart,
                        int32_t* batch, float* cvec, hipStream_t s, int32_t* t_next = nullptr, int32_t* t_cur = nullptr,
-                       NodeRange r = NodeRange(), int t_offset = 0);
+                       int t_offset = 0);
 int arreau_launch_reverse(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
                           const int32_t* d_t, const int32_t* d_off, int B, int N, const float* d_eps,
                           const float* d_logits, const float* d_len0, StepNoiseSrc noise, const int32_t* d_const_types,
-                          float* d_lattice, hipStream_t s, const float* d_fixed_lengths = nullptr, NodeRange r = NodeRange(),
+                          float* d_lattice, hipStream_t s, const float* d_fixed_lengths = nullptr,
                           const float* d_gs_atoms = nullptr /* pool these per-atom read-outs into d_len0 first */,
                           const int32_t* d_batch = nullptr /* crystal index of each atom, if the caller has it */,
                           float* d_lattice_ws = nullptr, float* d_cvec_next = nullptr /* sampling loop: also prepare the next step
                           (workspace lattice + per-crystal embedding for timestep t - 1), see reverse_crystal_block */);
 int arreau_launch_edge(const arreau_model* m, const float* dir, const float* dist, const int32_t* deg,
-                       const int32_t* batch, const float* lattice, int N, float* kbuf, hipStream_t s, NodeRange r = NodeRange());
+                       const int32_t* batch, const float* lattice, int N, float* kbuf, hipStream_t s);
 int arreau_launch_edge_bf16x6(const arreau_model* m, const float* dir, const float* dist, const int32_t* deg,
                               const int32_t* batch, const float* lattice, int N, float* kbuf, hipStream_t s);
 int arreau_launch_edge_f16x3(const arreau_model* m, const float* dir, const float* dist, const int32_t* deg,
-                             const int32_t* batch, const float* lattice, int N, float* kbuf, hipStream_t s, NodeRange r = NodeRange());
+                             const int32_t* batch, const float* lattice, int N, float* kbuf, hipStream_t s);
 int arreau_launch_embed(const arreau_model* m, const float* frac, const int32_t* types, const float* lattice,
-                        const int32_t* batch, const float* cvec, int N, float* x0, hipStream_t s, NodeRange r = NodeRange());
+                        const int32_t* batch, const float* cvec, int N, float* x0, hipStream_t s);
 int arreau_launch_embed_general(const arreau_model* m, const float* x, const float* vec, int N, float* x0, hipStream_t s);
 int arreau_launch_batch_index(const int32_t* offsets, int B, int N, int32_t* batch, hipStream_t s);
 int arreau_launch_node_layer(const arreau_model* m, int layer, const float* kbuf, const int32_t* deg,
                              const int32_t* src, const float* x_in, float* x_conv, float* x_out, float* xbar,
-                             float* vsum, int N, hipStream_t s, NodeRange r = NodeRange());
+                             float* vsum, int N, hipStream_t s);
 // ---- K stash format ------------------------------------------------------------------------------------------------
 // The per-layer edge kernels K [L][N*k*16][C] are the only large intermediate of a sampling step.  With the split-precision
 // edge kernel and the streamed conv kernel (the default pair) they are held as 3-BYTE floats: the top three bytes of the
@@ -329,7 +329,7 @@ bool arreau_basis_fp8(const arreau_model* m);
 bool arreau_cross_fp8(const arreau_model* m);
 void arreau_prof_conv(int end, hipStream_t s);  // api.hip: hipEvents around the message kernel while bench.py profiles
 int arreau_launch_conv_proj(const arreau_model* m, int layer, const float* basis, const int32_t* deg, const int32_t* src,
-                            const float* x_in, float* x_conv, int N, hipStream_t s, NodeRange r = NodeRange());
+                            const float* x_in, float* x_conv, int N, hipStream_t s);
 
 int arreau_launch_mlp_bf16x6(const arreau_model* m, int layer, const float* x_conv, const float* x_in, float* x_out,
                              float* xbar, float* vsum, int N, hipStream_t s);
@@ -342,13 +342,12 @@ int arreau_launch_mlp_train_forward(const arreau_model* m, int layer, const floa
                                     const float* fk = nullptr, float* x1 = nullptr);
 int arreau_repack_mlp_f16x3_m16(arreau_model* m, hipStream_t s);
 int arreau_launch_mlp_f16x3_m16(const arreau_model* m, int layer, const float* x_conv, const float* x_in, float* x_out,
-                                float* xbar, float* vsum, int N, hipStream_t s, NodeRange r = NodeRange());
-// one launch per layer for small unsliced launches (node_f16m.hip): conv_kernel_streamed<128, false> + the split MLP form
-bool arreau_small_layer_fusable(const arreau_model* m, int N, NodeRange r);
+                                float* xbar, float* vsum, int N, hipStream_t s);
+// one launch per layer for small launches (node_f16m.hip): conv_kernel_streamed<128, false> + the split MLP form
+bool arreau_small_layer_fusable(const arreau_model* m, int N);
 int arreau_launch_small_layer(const arreau_model* m, int layer, const float* kbuf, const int32_t* deg, const int32_t* src,
                               const float* x_in, float* x_out, float* xbar, float* vsum, int Ntot, hipStream_t s);
 int arreau_launch_mlp_f16x3_m16_split(const arreau_model* m, int layer, const float* x_conv, const float* x_in, float* x_out,
-                                      float* xbar, float* vsum, int N, hipStream_t s, NodeRange r = NodeRange());
+                                      float* xbar, float* vsum, int N, hipStream_t s);
 int arreau_launch_readout(const arreau_model* m, const float* xbar, const float* vsum, const int32_t* offsets,
-                          int B, int N, float* gs, float* eps, float* logits, float* len0, hipStream_t s, NodeRange r = NodeRange());
-bool arreau_range_launches_supported(const arreau_model* m);  // the default kernel set (fp16x3 edge + MLP, streamed conv, MFMA read-out)
+                          int B, int N, float* gs, float* eps, float* logits, float* len0, hipStream_t s);

@@ -61,11 +61,10 @@ __global__ __launch_bounds__(128) void prep_kernel(
 
 int arreau_launch_prep(const arreau_model* m, const float* frac, const float* lengths, const float* angles,
                        const int32_t* t, const int32_t* offsets, int B, int N, float* lattice, float* cart,
-                       int32_t* batch, float* cvec, hipStream_t s, int32_t* t_next, int32_t* t_cur, NodeRange r, int t_offset) {
-    const int b0 = r.b0, b1 = r.b1 < 0 ? B : r.b1;
-    if (b1 <= b0) return ARREAU_OK;
-    ARREAU_LAUNCH(prep_kernel, dim3(b1 - b0), dim3(128), 0, s, frac, lengths, angles, t, offsets, m->vp_betas,
-                       m->t_emb_w, m->embT, m->S, m->C, m->T, lattice, cart, batch, cvec, m->status, t_next, t_cur, b0, t_offset);
+                       int32_t* batch, float* cvec, hipStream_t s, int32_t* t_next, int32_t* t_cur, int t_offset) {
+    if (B <= 0) return ARREAU_OK;
+    ARREAU_LAUNCH(prep_kernel, dim3(B), dim3(128), 0, s, frac, lengths, angles, t, offsets, m->vp_betas,
+                       m->t_emb_w, m->embT, m->S, m->C, m->T, lattice, cart, batch, cvec, m->status, t_next, t_cur, 0, t_offset);
     ARREAU_CHECK_HIP(hipGetLastError());
     return ARREAU_OK;
 }
@@ -73,7 +72,7 @@ int arreau_launch_prep(const arreau_model* m, const float* frac, const float* le
 // ---------------------------------------------------------------------------------------------
 // Embedding (body in embed_dev.h): x0[n][o][c] = embT[type_n][c] + cvec[b][c] + sum_v embT[S+74+v][c] * (vec[n][v] . ori[o])
 // with vec[n] = (frac_n, lattice rows a, b, c)  (diffusion_loss.py:158; to_from_sphere.py:4-5).  Stand-alone launch: the
-// teacher-forced and sliced paths; the sampler's step embeds inside the neighbour-list launch (graph.hip).
+// teacher-forced path; the sampler's step embeds inside the neighbour-list launch (graph.hip).
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void embed_kernel(
     const float* __restrict__ frac, const int32_t* __restrict__ types, const float* __restrict__ lattice,
@@ -84,16 +83,15 @@ __global__ __launch_bounds__(256) void embed_kernel(
 }
 
 int arreau_launch_embed(const arreau_model* m, const float* frac, const int32_t* types, const float* lattice,
-                        const int32_t* batch, const float* cvec, int N, float* x0, hipStream_t s, NodeRange r) {
-    const int n0 = r.n0, n1 = r.n1 < 0 ? N : r.n1;
-    if (n1 <= n0) return ARREAU_OK;
-    const long long total = (long long)(n1 - n0) * (m->C / 4);
+                        const int32_t* batch, const float* cvec, int N, float* x0, hipStream_t s) {
+    if (N <= 0) return ARREAU_OK;
+    const long long total = (long long)N * (m->C / 4);
     if (total >= (1ll << 31)) {
         arreau_set_error("embed kernel: more than 2^31 (atom, channel group) pairs in one launch");
         return ARREAU_EINVAL;
     }
     ARREAU_LAUNCH(embed_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, frac, types, lattice, batch,
-                       cvec, m->ori, m->embT, m->S, m->C, n0, n1, x0, m->status);
+                       cvec, m->ori, m->embT, m->S, m->C, 0, N, x0, m->status);
     ARREAU_CHECK_HIP(hipGetLastError());
     return ARREAU_OK;
 }
@@ -619,11 +617,8 @@ __global__ __launch_bounds__(256, 2) void mlp_kernel(
 
 int arreau_launch_node_layer(const arreau_model* m, int layer, const float* kbuf, const int32_t* deg,
                              const int32_t* src, const float* x_in, float* x_conv, float* x_out, float* xbar,
-                             float* vsum, int N, hipStream_t s, NodeRange r) {
-    const int n0 = r.n0, n1 = r.n1 < 0 ? N : r.n1;
-    const int Ng = n1 - n0;
-    if (Ng <= 0) return ARREAU_OK;
-    const bool whole = n0 == 0 && n1 == N;
+                             float* vsum, int N, hipStream_t s) {
+    if (N <= 0) return ARREAU_OK;
     const int C = m->C, H = m->H, S = m->S;
     if (!(C == 128 && H == 512)) {
         arreau_set_error("node kernels: unsupported (hidden_dim, widening_factor)");
@@ -633,26 +628,22 @@ int arreau_launch_node_layer(const arreau_model* m, int layer, const float* kbuf
     const size_t mlp_layer = (size_t)2 * H * C;  // floats of W1 + W2, packed
     const int conv_blocks = N < 512 ? N : 512;   // persistent: 2 workgroups of 512 threads per CU (a multiple of 8: XCD-aware order)
     // conv variant: 1 (default, k = 8 only) = streamed form (K blocks by LDS-DMA, one workgroup per CU); 0 = register form
-    const bool basis_form = arreau_basis_form(m, N);  // whole-batch decision (one kbuf layout per evaluation)
+    const bool basis_form = arreau_basis_form(m, N);
     const int conv_variant = m->conv_variant == 2 ? 1 : m->conv_variant;  // (2 without the basis form = the streamed K pair)
     m->ran_conv = basis_form ? 2 : (conv_variant == 1 && m->k == 8) ? 1 : 0;
-    if (arreau_small_layer_fusable(m, N, r)) {  // small launch: both halves of the layer in one kernel (bit-identical)
+    if (arreau_small_layer_fusable(m, N)) {  // small launch: both halves of the layer in one kernel (bit-identical)
         m->ran_mlp = 3;
         return arreau_launch_small_layer(m, layer, kbuf, deg, src, x_in, x_out, xbar, vsum, N, s);
     }
     if (basis_form) {
-        const int rc = arreau_launch_conv_proj(m, layer, kbuf, deg, src, x_in, x_conv, N, s, r);
+        const int rc = arreau_launch_conv_proj(m, layer, kbuf, deg, src, x_in, x_conv, N, s);
         if (rc) return rc;
     } else if (conv_variant == 1 && m->k == 8) {
-        int blocks = Ng < 256 ? Ng : 256;
-        if (r.wg_cap > 0 && blocks > r.wg_cap) blocks = r.wg_cap;
-        ARREAU_LAUNCH((conv_kernel_streamed<128, false>), dim3(blocks), dim3(512), 0, s, kbuf + (size_t)layer * layer_stride, deg,
-                               src, x_in, m->fk + (size_t)layer * 16 * 16 * C, m->conv_bias + (size_t)layer * C, n0, Ng, x_conv);
+        ARREAU_LAUNCH((conv_kernel_streamed<128, false>), dim3(N < 256 ? N : 256), dim3(512), 0, s, kbuf + (size_t)layer * layer_stride, deg,
+                               src, x_in, m->fk + (size_t)layer * 16 * 16 * C, m->conv_bias + (size_t)layer * C, 0, N, x_conv);
     } else {
-        int blocks = Ng < 512 ? Ng : 512;
-        if (r.wg_cap > 0 && blocks > r.wg_cap) blocks = r.wg_cap;
-        ARREAU_LAUNCH((conv_kernel<128>), dim3(whole ? conv_blocks : blocks), dim3(512), 0, s, kbuf + (size_t)layer * layer_stride,
-                           deg, src, x_in, m->fk + (size_t)layer * 16 * 16 * C, m->conv_bias + (size_t)layer * C, n0, Ng, m->k, x_conv);
+        ARREAU_LAUNCH((conv_kernel<128>), dim3(conv_blocks), dim3(512), 0, s, kbuf + (size_t)layer * layer_stride,
+                           deg, src, x_in, m->fk + (size_t)layer * 16 * 16 * C, m->conv_bias + (size_t)layer * C, 0, N, m->k, x_conv);
     }
     ARREAU_CHECK_HIP(hipGetLastError());
     // variant switch: 3 (default) = fp16x3 on 16x16x32 MFMAs (node_f16m.hip; needs weights that fit fp16); 1 = bf16x6 split-precision
@@ -661,15 +652,11 @@ int arreau_launch_node_layer(const arreau_model* m, int layer, const float* kbuf
     const int mlp_variant = m->mlp_variant;
     if (mlp_variant == 4 && m->f16_ok) {
         m->ran_mlp = 3;
-        return arreau_launch_mlp_f16x3_m16_split(m, layer, x_conv, x_in, x_out, xbar, vsum, N, s, r);
+        return arreau_launch_mlp_f16x3_m16_split(m, layer, x_conv, x_in, x_out, xbar, vsum, N, s);
     }
     if (mlp_variant == 3 && m->f16_ok) {
         m->ran_mlp = 3;
-        return arreau_launch_mlp_f16x3_m16(m, layer, x_conv, x_in, x_out, xbar, vsum, N, s, r);
-    }
-    if (!whole) {
-        arreau_set_error("mlp kernel: range launches are implemented for the fp16x3 16x16x32 kernel only");
-        return ARREAU_EINVAL;
+        return arreau_launch_mlp_f16x3_m16(m, layer, x_conv, x_in, x_out, xbar, vsum, N, s);
     }
     if (mlp_variant >= 1) {
         m->ran_mlp = 1;
@@ -836,17 +823,10 @@ bool arreau_cross_fp8(const arreau_model* m) {
     return (e == nullptr || atoi(e) != 0 || m->calibrating) && m->x8_ok && arreau_basis_fp8(m);
 }
 
-bool arreau_range_launches_supported(const arreau_model* m) {
-    return m->edge_variant == 4 && (m->mlp_variant == 3 || m->mlp_variant == 4) && m->f16_ok && (m->conv_variant == 1 || m->conv_variant == 2) && m->k == 8 &&
-           m->readout_variant == 1 && m->S + 4 <= 96 && m->L <= 8 && m->C == 128;
-}
-
 int arreau_launch_readout(const arreau_model* m, const float* xbar, const float* vsum, const int32_t* offsets, int B,
-                          int N, float* gs, float* eps, float* logits, float* len0, hipStream_t s, NodeRange r) {
+                          int N, float* gs, float* eps, float* logits, float* len0, hipStream_t s) {
     if (B == 0) return ARREAU_OK;
-    const int n0 = r.n0, n1 = r.n1 < 0 ? N : r.n1, b0 = r.b0, b1 = r.b1 < 0 ? B : r.b1;
-    const bool whole = n0 == 0 && n1 == N;
-    if (n1 > n0) {
+    if (N > 0) {
         const size_t smem = ((size_t)RO_ATOMS * m->L * m->C + (size_t)m->L * RO_ATOMS * RO_COLS) * sizeof(float);
         if (m->L * RO_COLS > 1024 || m->S + 4 > RO_COLS) {
             arreau_set_error("readout kernel: num_layers * 128 threads must fit one workgroup");
@@ -862,28 +842,24 @@ int arreau_launch_readout(const arreau_model* m, const float* xbar, const float*
             static const hipError_t attr_s = hipFuncSetAttribute(reinterpret_cast<const void*>(&readout_mfma_kernel<128, 3, 1>),
                                                                  hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 3 * 64 * 16 * 4);
             ARREAU_CHECK_HIP(attr_s);
-            const unsigned blocks32 = (unsigned)((n1 - n0 + 31) / 32);
+            const unsigned blocks32 = (unsigned)((N + 31) / 32);
             static const int split_env = [] { const char* e = getenv("ARREAU_READOUT_SPLIT"); return e ? atoi(e) : -1; }();
-            // unsliced launch of fewer workgroups than the chip has CUs: one workgroup per output tile (measured, round 3: 160
+            // launch of fewer workgroups than the chip has CUs: one workgroup per output tile (measured, round 3: 160
             // workgroups -- 256 x 20 -- 18.7 us split against 21.6; 640 -- 1024 x 20 -- 75 against 65; 2048: 220 against 169)
-            if (split_env >= 0 ? split_env != 0 : (whole && r.wg_cap == 0 && blocks32 < 256))
+            if (split_env >= 0 ? split_env != 0 : blocks32 < 256)
                 ARREAU_LAUNCH((readout_mfma_kernel<128, 3, 1>), dim3(blocks32, 3), dim3(64 * m->L), smem_m, s, xbar, vsum,
-                                   m->ro_pack, m->ro_b, m->ori, m->S, m->L, N, n0, n1, eps, logits, gs, m->status);
+                                   m->ro_pack, m->ro_b, m->ori, m->S, m->L, N, 0, N, eps, logits, gs, m->status);
             else
                 ARREAU_LAUNCH((readout_mfma_kernel<128, 3>), dim3(blocks32), dim3(64 * m->L), smem_m, s, xbar, vsum,
-                                   m->ro_pack, m->ro_b, m->ori, m->S, m->L, N, n0, n1, eps, logits, gs, m->status);
+                                   m->ro_pack, m->ro_b, m->ori, m->S, m->L, N, 0, N, eps, logits, gs, m->status);
         } else {
-            if (!whole) {
-                arreau_set_error("read-out: range launches are implemented for the MFMA kernel only");
-                return ARREAU_EINVAL;
-            }
             ARREAU_LAUNCH(readout_nodes_kernel, dim3((N + RO_ATOMS - 1) / RO_ATOMS), dim3(RO_COLS * m->L), smem, s, xbar, vsum,
                                m->ro_wT, m->ro_b, m->ori, m->S, m->C, m->L, N, eps, logits, gs, m->status);
         }
         ARREAU_CHECK_HIP(hipGetLastError());
     }
-    if (b1 > b0 && len0 != nullptr)  // (len0 == nullptr: the caller pools the crystals itself -- the sampling loop's lattice update)
-        ARREAU_LAUNCH(readout_crystals_kernel, dim3((3 * (b1 - b0) + 127) / 128), dim3(128), 0, s, gs, offsets, b0, b1, len0);
+    if (len0 != nullptr)  // (len0 == nullptr: the caller pools the crystals itself -- the sampling loop's lattice update)
+        ARREAU_LAUNCH(readout_crystals_kernel, dim3((3 * B + 127) / 128), dim3(128), 0, s, gs, offsets, 0, B, len0);
     ARREAU_CHECK_HIP(hipGetLastError());
     return ARREAU_OK;
 }

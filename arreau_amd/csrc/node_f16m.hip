@@ -590,9 +590,8 @@ __global__ __launch_bounds__(512) void mlp_kernel_f16x3_m16_split(
 
 #define ARREAU_MLP_SPLIT_MAX_NODES 512
 int arreau_launch_mlp_f16x3_m16_split(const arreau_model* m, int layer, const float* x_conv, const float* x_in, float* x_out,
-                                      float* xbar, float* vsum, int Ntot, hipStream_t s, NodeRange r) {
-    const int n0 = r.n0, n1 = r.n1 < 0 ? Ntot : r.n1;
-    if (n1 <= n0) return ARREAU_OK;
+                                      float* xbar, float* vsum, int N, hipStream_t s) {
+    if (N <= 0) return ARREAU_OK;
     const int C = m->C, H = m->H;
     if (!(C == 128 && H == 512)) {
         arreau_set_error("mlp kernel (fp16x3, hidden split): unsupported (hidden_dim, widening_factor)");
@@ -600,23 +599,21 @@ int arreau_launch_mlp_f16x3_m16_split(const arreau_model* m, int layer, const fl
     }
     const size_t layer_u32x4 = (size_t)2 * H * C * 2 * 2 / 16;
     const u32x4* stream = reinterpret_cast<const u32x4*>(m->mlp_f16m) + (size_t)layer * layer_u32x4;
-    ARREAU_LAUNCH((mlp_kernel_f16x3_m16_split<128, 512>), dim3((unsigned)(n1 - n0)), dim3(512), 0, s, x_conv, x_in, x_out,
+    ARREAU_LAUNCH((mlp_kernel_f16x3_m16_split<128, 512>), dim3((unsigned)N), dim3(512), 0, s, x_conv, x_in, x_out,
                        m->ln_w + (size_t)layer * C, m->ln_b + (size_t)layer * C, stream, m->mb1 + (size_t)layer * H,
                        m->mb2 + (size_t)layer * C, m->ls + (size_t)layer * C, m->ro_wv + (size_t)layer * C, m->ro_bv_host[layer],
-                       n0, layer == 0 ? 1 : 0, xbar + (size_t)layer * Ntot * C, vsum, (const float*)nullptr, (const int32_t*)nullptr,
+                       0, layer == 0 ? 1 : 0, xbar + (size_t)layer * N * C, vsum, (const float*)nullptr, (const int32_t*)nullptr,
                        (const int32_t*)nullptr, (const float*)nullptr, (const float*)nullptr, MlpTrainSave{});
     ARREAU_CHECK_HIP(hipGetLastError());
     return ARREAU_OK;
 }
 
-// Message passing + spherical convolution + ConvNext block of one layer in ONE launch (small unsliced launches on an fp32 K
+// Message passing + spherical convolution + ConvNext block of one layer in ONE launch (small launches on an fp32 K
 // buffer with k = 8; see the kernel): what conv_kernel_streamed<128, false> followed by the launch above computes, bit for bit.
-bool arreau_small_layer_fusable(const arreau_model* m, int N, NodeRange r) {
+bool arreau_small_layer_fusable(const arreau_model* m, int N) {
     const char* e = getenv("ARREAU_FUSE_SMALL");  // 0: two launches per layer (A/B, tests); read per call
     static const int split_env = [] { const char* v = getenv("ARREAU_MLP_SPLIT"); return v ? atoi(v) : -1; }();
-    const int n0 = r.n0, n1 = r.n1 < 0 ? N : r.n1;
-    const bool whole_batch = n0 == 0 && n1 == N && r.wg_cap == 0;
-    return (e == nullptr || atoi(e) != 0) && split_env < 0 && whole_batch && N <= ARREAU_MLP_SPLIT_MAX_NODES && m->mlp_variant == 3 &&
+    return (e == nullptr || atoi(e) != 0) && split_env < 0 && N <= ARREAU_MLP_SPLIT_MAX_NODES && m->mlp_variant == 3 &&
            m->f16_ok && m->k == 8 && m->C == 128 && m->H == 512 && (m->conv_variant == 1 || m->conv_variant == 2) && !arreau_k3(m) &&
            !arreau_basis_form(m, N);
 }
@@ -703,9 +700,7 @@ int arreau_repack_mlp_f16x3_m16(arreau_model* m, hipStream_t s) {
 }
 
 int arreau_launch_mlp_f16x3_m16(const arreau_model* m, int layer, const float* x_conv, const float* x_in, float* x_out,
-                                float* xbar, float* vsum, int Ntot, hipStream_t s, NodeRange r) {
-    const int n0 = r.n0, n1 = r.n1 < 0 ? Ntot : r.n1;
-    const int N = n1 - n0;  // nodes of this launch (tile geometry is chosen for them)
+                                float* xbar, float* vsum, int N, hipStream_t s) {
     if (N <= 0) return ARREAU_OK;
     const int C = m->C, H = m->H;
     if (!(C == 128 && H == 512)) {
@@ -724,18 +719,10 @@ int arreau_launch_mlp_f16x3_m16(const arreau_model* m, int layer, const float* x
     // MI355X: 10.7 us per layer at 8 nodes against 22.5 us; the forms cross where the node-per-workgroup form needs more
     // than about two rounds of the chip.  ARREAU_MLP_SPLIT = 0 / 1 forces a form (tests).
     static const int split_env = [] { const char* e = getenv("ARREAU_MLP_SPLIT"); return e ? atoi(e) : -1; }();
-    // (unsliced launches only, like the edge kernel's small-launch form: edge_f16.hip)
-    const bool whole_batch = n0 == 0 && n1 == Ntot && r.wg_cap == 0;
-    if (split_env >= 0 ? split_env != 0 : (whole_batch && N <= ARREAU_MLP_SPLIT_MAX_NODES))
-        return arreau_launch_mlp_f16x3_m16_split(m, layer, x_conv, x_in, x_out, xbar, vsum, Ntot, s, r);
+    if (split_env >= 0 ? split_env != 0 : N <= ARREAU_MLP_SPLIT_MAX_NODES)
+        return arreau_launch_mlp_f16x3_m16_split(m, layer, x_conv, x_in, x_out, xbar, vsum, N, s);
     static const int nb_env = [] { const char* e = getenv("ARREAU_MLP_NB"); return e ? atoi(e) : 0; }();
-    static const int wave_slots = [] {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-            return 8 * (int)prop.multiProcessorCount;
-        return 2048;
-    }();
+    const int wave_slots = 8 * arreau_cu_count();
     const long long rounds1 = ((long long)N + wave_slots - 1) / wave_slots;
     const long long rounds2 = (((long long)N + 1) / 2 + wave_slots - 1) / wave_slots;
     const int nb = nb_env == 1 || nb_env == 2 ? nb_env : (6 * rounds1 < 10 * rounds2 ? 1 : 2);
@@ -750,7 +737,7 @@ int arreau_launch_mlp_f16x3_m16(const arreau_model* m, int layer, const float* x
     auto launch = [&](auto kernel) {
         ARREAU_LAUNCH(kernel, grid, block, 0, s, x_conv, x_in, x_out, lnw, lnb, stream, m->mb1 + (size_t)layer * H,
                            m->mb2 + (size_t)layer * C, m->ls + (size_t)layer * C, m->ro_wv + (size_t)layer * C,
-                           m->ro_bv_host[layer], n0, n1, layer == 0 ? 1 : 0, xbar + (size_t)layer * Ntot * C, vsum);
+                           m->ro_bv_host[layer], 0, N, layer == 0 ? 1 : 0, xbar + (size_t)layer * N * C, vsum);
     };
     if (nb == 1 && slots == 4) launch(mlp_kernel_f16x3_m16<128, 512, NW, 1, 4>);
     else if (nb == 1) launch(mlp_kernel_f16x3_m16<128, 512, NW, 1, 3>);

@@ -72,18 +72,17 @@ __global__ __launch_bounds__(256) void reverse_kernel(
 int arreau_launch_reverse(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
                           const int32_t* d_t, const int32_t* d_off, int B, int N, const float* d_eps,
                           const float* d_logits, const float* d_len0, StepNoiseSrc noise, const int32_t* d_const_types,
-                          float* d_lattice, hipStream_t s, const float* d_fixed_lengths, NodeRange r, const float* d_gs_atoms,
+                          float* d_lattice, hipStream_t s, const float* d_fixed_lengths, const float* d_gs_atoms,
                           const int32_t* d_batch, float* d_lattice_ws, float* d_cvec_next) {
-    const int n0 = r.n0, n1 = r.n1 < 0 ? N : r.n1, b0 = r.b0, b1 = r.b1 < 0 ? B : r.b1;
     const bool prep_next = d_cvec_next != nullptr;  // one workgroup per crystal, which also prepares the next step
     ARREAU_REQUIRE(!prep_next || d_lattice_ws != nullptr, "reverse update: the next step's set-up needs the workspace lattice");
-    const int lat_blocks = b1 > b0 ? (prep_next ? b1 - b0 : (4 * (b1 - b0) + 255) / 256) : 0;
-    const int atom_blocks = n1 > n0 ? (n1 - n0 + 3) / 4 : 0;
+    const int lat_blocks = B > 0 ? (prep_next ? B : (4 * B + 255) / 256) : 0;
+    const int atom_blocks = N > 0 ? (N + 3) / 4 : 0;
     if (lat_blocks + atom_blocks > 0) {
         ARREAU_LAUNCH(reverse_kernel, dim3(lat_blocks + atom_blocks), dim3(256), 0, s, lat_blocks, d_lengths, d_angles, d_t, d_off, d_len0,
-                      noise, m->vp_alpha_bars, m->vp_betas, b1, m->T, d_lattice, d_fixed_lengths, m->status, b0, d_gs_atoms,
-                      d_gs_atoms ? const_cast<float*>(d_len0) : nullptr, d_frac, d_types, B, n1, d_eps, d_logits, m->ve_sigmas, m->q1t,
-                      m->qmats, m->S, d_const_types, m->qmats_absorbing, n0, d_batch, d_lattice_ws, d_cvec_next, m->t_emb_w, m->embT, m->C);
+                      noise, m->vp_alpha_bars, m->vp_betas, B, m->T, d_lattice, d_fixed_lengths, m->status, 0, d_gs_atoms,
+                      d_gs_atoms ? const_cast<float*>(d_len0) : nullptr, d_frac, d_types, B, N, d_eps, d_logits, m->ve_sigmas, m->q1t,
+                      m->qmats, m->S, d_const_types, m->qmats_absorbing, 0, d_batch, d_lattice_ws, d_cvec_next, m->t_emb_w, m->embT, m->C);
         ARREAU_CHECK_HIP(hipGetLastError());
     }
     return ARREAU_OK;

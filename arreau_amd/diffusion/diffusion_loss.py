@@ -256,7 +256,7 @@ class DiffusionLoss(nn.Module):
                num_samples_in_batch: int, vis_name: str = "", visualization_setting=VisualizationSetting.NONE,
                show_bonds: bool = False, constant_atoms: Optional[torch.Tensor] = None, noise: str = "philox",
                max_steps: Optional[int] = None, use_graph: Optional[bool] = None, seed: Optional[int] = None,
-               fixed_cell: bool = False, pipelined_slices: int = 1) -> SampleResult:
+               fixed_cell: bool = False) -> SampleResult:
         """diffusion_loss.py:276-377.  The initial state is drawn on the host exactly like the reference (numpy
         uniforms for the angles, then randn lengths, randn fractional coordinates from torch's global CPU generator).
         Per-step noise:
@@ -316,10 +316,6 @@ class DiffusionLoss(nn.Module):
         if (use_graph or fixed_cell) and noise != "philox":
             raise ValueError("graph replay and fixed-cell sampling need noise='philox' (the in-kernel generator)")
 
-        # One stream.  Running the batch as two pipelined slices on separate streams (`pipelined_slices=2`) was 3 % faster
-        # at 256 x 20 on MI355X, but its results are not reproducible -- in about one run in four one crystal differs at the
-        # 1e-5 level from the one-stream loop, cause unknown -- and parity comes first: the library
-        # refuses the mode unless ARREAU_ALLOW_MULTISTREAM=1 is set (an experiment, not a product mode).
         # The loop as a function of the state buffers: it runs a second time, from the saved initial state, when the default
         # fp16x3 kernels flag an overflow (see below).
         init_state = (frac_d.clone(), types_d.clone(), len_d.clone())
@@ -330,7 +326,6 @@ class DiffusionLoss(nn.Module):
             rng_state = torch.random.get_rng_state()
 
         def run_loop(use_graph):
-            eng.set_batch_layout(num_atoms, groups=max(1, int(pipelined_slices)))
             if noise == "philox":
                 if use_graph is None:
                     use_graph = n_steps >= 200  # capture + instantiation (about 2 ms) against ~4 us saved per kernel boundary

@@ -156,16 +156,12 @@ class HipEngine:
         return out
 
     def set_batch_layout(self, num_atoms, groups=0):
-        """Tell the library the (host-side) atom count of every crystal of the batches that follow, so that it may run
-        the score network as `groups` crystal-aligned slices (arreau_model_set_batch_layout; groups = 0: the library's
-        default, ARREAU_GROUPS or off).  Slices on SEPARATE STREAMS are an experiment the library refuses unless
-        ARREAU_ALLOW_MULTISTREAM=1 is set: with kernels of two streams sharing CUs results were seen to change at the
-        1e-8 .. 1e-4 level in rare runs, cause unknown."""
-        n = torch.as_tensor(num_atoms).to("cpu", torch.int64).reshape(-1)
-        off = torch.zeros(n.numel() + 1, dtype=torch.int32)
-        off[1:] = torch.cumsum(n, 0).to(torch.int32)
-        _hip.check(_hip.lib().arreau_model_set_batch_layout(self._handle, ctypes.c_void_p(off.data_ptr()), int(n.numel()),
-                                                            int(groups)), "arreau_model_set_batch_layout")
+        """Kept for callers of the former batch-slicing experiment: the library runs the score network as one stream
+        over the whole batch, so `groups` 0 and 1 change nothing and larger values raise ValueError.  (Slices on
+        separate streams were not reproducible on MI355X, cause unknown: DESIGN.md section 8.)"""
+        if int(groups) > 1:
+            raise ValueError(f"set_batch_layout: groups={int(groups)} is not supported; the library runs one stream over "
+                             "the whole batch")
 
     def set_variant(self, edge=-1, mlp=-1):
         """Select the arithmetic of the dense kernels (edge: 0 fp32 MFMA, 3 bf16x6, 4 fp16x3; mlp: 0 fp32 MFMA,

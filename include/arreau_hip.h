@@ -162,21 +162,6 @@ int arreau_model_set_formats(arreau_model* model, int32_t basis_fp8, int32_t cro
  * arreau_model_update_train_weights refreshes, so with variant 5 a model keeps sampling between optimiser steps. */
 int arreau_model_set_variant(arreau_model* model, int32_t edge_variant, int32_t mlp_variant);
 
-/* Optional: tell the library how the batch is laid out (HOST copy of d_crystal_offsets[B+1]) so that the score network
- * of subsequent arreau_predict_scores / arreau_sample_loop calls with the same (B, N) may run as `groups`
- * crystal-aligned slices on separate internal streams (forked from and joined to the caller's stream by events; no host
- * synchronisation).  Crystals are independent and every kernel takes a node range over whole-batch arrays, so
- * every slice computes what the unsliced run computes for its atoms; the slices drift into different phases and the
- * HBM-bound message-passing kernel of one overlaps the matrix-bound edge / MLP kernels of another (3-5 % at 256 x 20).
- * EXPERIMENT, refused by default (ARREAU_EINVAL for groups > 1 unless the environment holds ARREAU_ALLOW_MULTISTREAM=1):
- * on MI355X, with kernels of two streams or two processes sharing CUs, one crystal in a few runs came out different at
- * the 1e-8 .. 1e-4 level and the cause is not known, so a sliced multi-stream run is not
- * guaranteed identical to the unsliced one.  ARREAU_SLICE_EAGER=serial runs the slices' range launches one after another
- * on the caller's stream (bit-identical to the unsliced run; what the tests of the range launches use).
- * groups <= 0: the library's default (environment ARREAU_GROUPS, else 1 = off).  Used only with the default kernel set;
- * ignored otherwise. */
-int arreau_model_set_batch_layout(arreau_model* model, const int32_t* h_crystal_offsets, int32_t B, int32_t groups);
-
 /* Scratch for one step over at most max_atoms atoms / max_crystals crystals. */
 size_t arreau_workspace_bytes(const arreau_config* cfg, int64_t max_atoms, int64_t max_crystals);
 

@@ -1388,43 +1388,20 @@ def test_sample_loop_without_and_with_a_prep_launch_per_step(dev, small_model, m
             assert torch.equal(a, b), key
 
 
-def _ragged_37(dev):
+def test_one_stream_graph_replay_is_bitwise_the_eager_loop(dev, full_model):
+    """On a ragged 37-crystal batch the sampling loop as a one-stream hipGraph replay is bit-identical to the eager loop,
+    and the engine refuses to cut the batch into slices (the library runs one stream over the whole batch)."""
     from arreau_amd.diffusion.diffusion_helpers import crystal_offsets
+    m, _ = full_model
+    eng = m.engine()
     rng = np.random.RandomState(3)
     counts = [int(v) for v in rng.randint(3, 21, size=37)]
     frac, types, lengths, angles, na = random_state(90, counts, 12, sampler_like=True)
     d = lambda v: v.to(dev).contiguous()
     off = crystal_offsets(na, dev)
-    return counts, (frac, types, lengths, angles, na), d, off
-
-
-@pytest.mark.parametrize("groups", [2, 4])
-def test_range_launches_are_bitwise_the_whole_batch(dev, full_model, groups):
-    """Every kernel of the score network takes a node range over whole-batch arrays (NodeRange).  The batch cut into
-    crystal-aligned slices (ragged batch, uneven slices) and run slice after slice on ONE stream gives bit for bit the
-    whole-batch result; the sampling loop as a one-stream hipGraph replay is bit-identical to the eager loop; and slices on
-    SEPARATE streams are refused unless the caller opts in to the experiment (next test)."""
-    from arreau_amd import _hip
-    m, _ = full_model
-    eng = m.engine()
-    counts, (frac, types, lengths, angles, na), d, off = _ragged_37(dev)
     B = len(counts)
-    t_c = torch.full((B,), 700, device=dev, dtype=torch.int32)
-    args = (d(frac), d(types.to(torch.int32)), d(lengths), d(angles), t_c, off)
-    eng.set_batch_layout(na, groups=1)
-    whole = eng.predict_scores(*args)
-    os.environ["ARREAU_SLICE_EAGER"] = "serial"  # (read when the layout is set)
-    try:
-        eng.set_batch_layout(na, groups=groups)
-        sliced = eng.predict_scores(*args)
-    finally:
-        del os.environ["ARREAU_SLICE_EAGER"]
-        eng.set_batch_layout(na, groups=1)
-    for x, y in zip(whole, sliced):
-        assert torch.equal(x, y)
-    assert "ARREAU_ALLOW_MULTISTREAM" not in os.environ
-    with pytest.raises(_hip.ArreauHipError, match="ARREAU_ALLOW_MULTISTREAM"):
-        eng.set_batch_layout(na, groups=groups)
+    with pytest.raises(ValueError, match="one stream"):
+        eng.set_batch_layout(na, groups=2)
 
     def loop(use_graph):
         f, ty, le, lat = d(frac.clone()), d(types.to(torch.int32)), d(lengths.clone()), torch.zeros(B, 3, 3, device=dev)
@@ -1437,11 +1414,10 @@ def test_range_launches_are_bitwise_the_whole_batch(dev, full_model, groups):
     eng.check_status()
 
 
-def test_range_launches_of_the_basis_form(dev, full_model, monkeypatch):
-    """The same property for slices large enough to take the basis form themselves (more than 240 receivers each: the edge
-    kernel stores the basis planes for receivers n0 .. n1-1 into the whole-batch stash, conv_proj_kernel walks that range
-    with absolute indices): three uneven slices of a ragged 1,500-atom batch, one after another on one stream, against the
-    whole-batch launch -- bit for bit -- and a degree-starved batch (huge cells: most receivers have no or few in-edges)."""
+def test_basis_form_on_ragged_and_degree_starved_batches(dev, full_model, monkeypatch):
+    """The basis form (the edge kernel stores the basis planes, conv_proj_kernel projects them) on a ragged 1,500-atom batch
+    and on a degree-starved one (huge cells: most receivers have no or few in-edges): finite outputs, and the message
+    kernel of the basis form really ran."""
     from arreau_amd.diffusion.diffusion_helpers import crystal_offsets
     monkeypatch.setenv("ARREAU_BASIS_MIN_RECEIVERS", "240")  # (read per launch; the product's switch is at 2,000 receivers)
     m, _ = full_model
@@ -1456,20 +1432,12 @@ def test_range_launches_of_the_basis_form(dev, full_model, monkeypatch):
         off = crystal_offsets(na, dev)
         t_c = torch.full((B,), t, device=dev, dtype=torch.int32)
         args = (d(frac), d(types.to(torch.int32)), d(lengths), d(angles), t_c, off)
-        eng.set_batch_layout(na, groups=1)
         whole = eng.predict_scores(*args, return_edges=True)
         deg = whole[3][0]
         if cell[0] > 10:
             assert int((deg == 0).sum()) > 0 and int(deg.max()) <= 8  # receivers without in-edges are in the batch
-        os.environ["ARREAU_SLICE_EAGER"] = "serial"
-        try:
-            eng.set_batch_layout(na, groups=3)
-            sliced = eng.predict_scores(*args)
-        finally:
-            del os.environ["ARREAU_SLICE_EAGER"]
-            eng.set_batch_layout(na, groups=1)
-        for x, y in zip(whole[:3], sliced):
-            assert torch.isfinite(x).all() and torch.equal(x, y)
+        for x in whole[:3]:
+            assert torch.isfinite(x).all()
         st = eng.check_status()
         assert st["conv_variant"] == 2  # the message kernel of the basis form really ran
     # just above the switch-over: 260 receivers = one receiver per workgroup (every workgroup's first receiver is its last:
@@ -1480,61 +1448,6 @@ def test_range_launches_of_the_basis_form(dev, full_model, monkeypatch):
     got = _engine_scores(m2, dev, state, 300)
     assert eng.check_status()["conv_variant"] == 2
     assert_scores_close(got, (eps_o, logits_o, len0_o), tag="260 receivers")
-
-
-@pytest.mark.multistream
-def test_multi_stream_experiment_report(dev, full_model):
-    """The opt-in experiment (ARREAU_ALLOW_MULTISTREAM=1): the same slices forked onto their own streams, and the pipelined
-    sampling loop (own stream and step graph per slice, no per-step join).  Every slice computes what the whole batch
-    computes for its crystals, so the results SHOULD be bit-identical -- on MI355X, with kernels of two streams sharing CUs,
-    one crystal in a few runs was not.  Opt-in (tests/conftest.py: ARREAU_TEST_MULTISTREAM=1 or
-    -m multistream; skipped otherwise, because the library refuses the mode by default): it asserts bit-equality, prints
-    which crystals differed per run, and a mismatch FAILS (round 3 reported it as an expected failure, which kept a
-    recurrence green)."""
-    m, _ = full_model
-    eng = m.engine()
-    counts, (frac, types, lengths, angles, na), d, off = _ragged_37(dev)
-    B = len(counts)
-    offs = off.cpu().numpy()
-    t_c = torch.full((B,), 700, device=dev, dtype=torch.int32)
-    args = (d(frac), d(types.to(torch.int32)), d(lengths), d(angles), t_c, off)
-
-    def loop(use_graph):
-        f, ty, le, lat = d(frac.clone()), d(types.to(torch.int32)), d(lengths.clone()), torch.zeros(B, 3, 3, device=dev)
-        eng.sample_loop(f, ty, le, d(angles), off, 999, 5, 4242, None, lat, use_graph=use_graph)
-        return f, ty, le, lat
-
-    def crystals_differing(per_atom, per_crystal):
-        bad = {int(np.searchsorted(offs, i, side="right") - 1) for i in np.nonzero(per_atom.cpu().numpy())[0]}
-        return bad | set(np.nonzero(per_crystal.cpu().numpy())[0].tolist())
-
-    eng.set_batch_layout(na, groups=1)
-    whole = eng.predict_scores(*args)
-    ref = loop(False)
-    report = {}
-    os.environ["ARREAU_ALLOW_MULTISTREAM"] = "1"
-    try:
-        os.environ["ARREAU_SLICE_EAGER"] = "1"
-        try:
-            eng.set_batch_layout(na, groups=2)
-        finally:
-            del os.environ["ARREAU_SLICE_EAGER"]
-        forked = eng.predict_scores(*args)
-        report["fork-join scores"] = sorted(crystals_differing((whole[0] != forked[0]).any(1) | (whole[1] != forked[1]).any(1),
-                                                               (whole[2] != forked[2]).any(1)))
-        eng.set_batch_layout(na, groups=2)
-        for i in range(3):  # (the later graph runs reuse the cached per-slice graphs)
-            out = loop(True)
-            report[f"pipelined loop {i}"] = sorted(crystals_differing((ref[0] != out[0]).any(1) | (ref[1] != out[1]),
-                                                                      (ref[2] != out[2]).any(1)))
-            assert torch.isfinite(out[0]).all() and torch.isfinite(out[2]).all()
-    finally:
-        del os.environ["ARREAU_ALLOW_MULTISTREAM"]
-        eng.set_batch_layout(na, groups=1)
-    eng.check_status()
-    n_bad = sum(len(v) for v in report.values())
-    print(f"[multi-stream experiment] crystals that differ from the one-stream result, per run: {report}")
-    assert n_bad == 0, f"multi-stream slices not bit-identical in this run: {report}"
 
 
 @pytest.mark.parametrize("case", ["small-launch forms (3 crystals)", "throughput forms (ragged 64 crystals)", "large cells (2 x 64 atoms)"])

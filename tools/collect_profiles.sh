@@ -18,4 +18,3 @@ cp gpurun_out/${p}_parity.json profiles/parity_${r}.json
 cp gpurun_out/${p}_parity_heavy_tailed.json profiles/parity_${r}_heavy_tailed.json
 tail -n 3 gpurun_out/${b}_pytest.log > profiles/${b}_pytest_tail.txt
 grep -h "^\[plain 1e-5\]\|^\[gradients\|^\[fp8 cross\|^\[lone crystal\|^\[basis stash\|^\[bench path\|^   \[fp64 ref\]\|^\[loss" gpurun_out/${b}_pytest.log > profiles/${b}_pytest_parity_lines.txt
-cp gpurun_out/${b}_multistream.log profiles/${b}_multistream_optin.txt 2>/dev/null

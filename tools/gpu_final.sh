@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage (GPU box): tools/gpu_final.sh <tag> [benches|profiles]  -- everything a round's record needs (two calls when one would exceed a box's limit):
-#   benches:  GPU suite (+ the opt-in multi-stream experiment, its own log), smoke, bench.py as the driver runs it (c2), the other BASELINE
+#   benches:  GPU suite, smoke, bench.py as the driver runs it (c2), the other BASELINE
 #             configurations, the training step with exact and with split-precision forward products
 #   profiles: rocprofv3 kernel statistics at c2 and of the training step, its launch list, HBM-traffic PMC passes at c2 / c4 / c5, the
 #             parity report (default and heavy-tailed weights)
@@ -11,8 +11,6 @@ timeout -k 10 1100 python3 -m pytest tests -m gpu -x -q -s > gpurun_out/${tag}_p
 tail -n 3 gpurun_out/${tag}_pytest.log
 grep -h "^\[plain 1e-5\]\|^\[gradients\|^\[fp8 cross\|^\[lone crystal\|^\[basis stash\|^\[bench path\|^   \[fp64 ref\]\|^\[loss" gpurun_out/${tag}_pytest.log
 [ $rc -eq 0 ] || { grep -n "Error\|assert \|FAILED" gpurun_out/${tag}_pytest.log | tail -n 30; exit $rc; }
-ARREAU_TEST_MULTISTREAM=1 timeout -k 10 300 python3 -m pytest tests/test_gpu_parity.py -m gpu -q -s -k multi_stream_experiment > gpurun_out/${tag}_multistream.log 2>&1
-echo "multistream rc=$?"; grep -h "multi-stream experiment\|passed\|failed" gpurun_out/${tag}_multistream.log | tail -n 3
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -n 1 || exit 1
 # (the default run = what the driver times: c2 + cpu_baseline + the short legs of c1 / c4 / c5 as `other_configs`)
 timeout -k 10 500 python3 bench.py > gpurun_out/${tag}_bench_c2.json 2> gpurun_out/${tag}_bench_c2.err || { tail -n 30 gpurun_out/${tag}_bench_c2.err; exit 1; }
