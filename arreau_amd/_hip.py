@@ -24,6 +24,7 @@ EXPORTS = [
     "arreau_debug_sgemm", "arreau_optimizer_create", "arreau_optimizer_step", "arreau_optimizer_destroy",
     "arreau_model_train_weight_pointers", "arreau_model_refresh_derived_train_weights",
     "arreau_model_set_formats", "arreau_debug_set_pollution", "arreau_debug_leftover_fraction",
+    "arreau_sample_loop_conditioned", "arreau_condition_initial_state",
 ]
 
 STATUS_NONFINITE, STATUS_BAD_TIMESTEP, STATUS_BAD_TYPE = 1, 2, 4
@@ -44,6 +45,12 @@ class AdamArgs(Structure):
     """arreau_adam_args (include/arreau_hip.h)"""
     _fields_ = [("step", c_int64), ("lr", c_double * OPT_MAX_GROUPS), ("weight_decay", c_double * OPT_MAX_GROUPS),
                 ("beta1", c_double), ("beta2", c_double), ("eps", c_double), ("max_norm", c_double)]
+
+
+class SampleConditionC(Structure):
+    """arreau_sample_condition (include/arreau_hip.h): device pointers, each may be NULL."""
+    _fields_ = [("x0", c_void_p), ("pos_mask", c_void_p), ("a0", c_void_p), ("type_mask", c_void_p), ("l0", c_void_p),
+                ("len_mask", c_void_p)]
 
 
 class Config(Structure):
@@ -111,6 +118,10 @@ def lib():
     L.arreau_diffusion_losses.argtypes = [c_void_p] * 10 + [c_int32, c_int32] + [c_void_p] * 6
     L.arreau_sample_loop.argtypes = ([c_void_p] * 6 + [c_int32, c_int32, c_int32, c_int32, ctypes.c_uint64] +
                                      [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int32, c_void_p])
+    if hasattr(L, "arreau_sample_loop_conditioned") or not os.environ.get("ARREAU_HIP_LIB"):  # (an older build under test)
+        L.arreau_sample_loop_conditioned.argtypes = (L.arreau_sample_loop.argtypes[:-1] + [POINTER(SampleConditionC), c_void_p])
+        L.arreau_condition_initial_state.argtypes = ([c_void_p] * 4 + [c_int32, c_int32, c_int32, ctypes.c_uint64] +
+                                                     [POINTER(SampleConditionC), c_void_p])
     L.arreau_philox_fill.argtypes = [ctypes.c_uint64, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_void_p]
     L.arreau_train_forward.argtypes = [c_void_p] * 7 + [c_int32, c_int32] + [c_void_p] * 4
     L.arreau_train_backward.argtypes = [c_void_p] * 4 + [POINTER(StateDict), c_void_p]

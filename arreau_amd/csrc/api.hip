@@ -298,7 +298,8 @@ bool loop_without_prep(const arreau_model* m) {
 
 int enqueue_sample_step(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
                         const int32_t* d_off, int B, int N, uint64_t seed, const int32_t* d_const_types,
-                        const float* d_fixed_lengths, float* d_lattice, const Workspace& w, hipStream_t s, bool no_prep) {
+                        const float* d_fixed_lengths, float* d_lattice, const Workspace& w, hipStream_t s, bool no_prep,
+                        const SampleConditionDev* cond) {
     int rc;
     if (no_prep) {
         if ((rc = arreau_launch_neighbor_embed(m, nullptr, w.lattice, d_off, w.batch, B, N, w.deg, w.src, w.cell, w.dir, w.dist, d_frac,
@@ -308,7 +309,7 @@ int enqueue_sample_step(const arreau_model* m, float* d_frac, int32_t* d_types, 
         if ((rc = run_layers_and_readout(m, w, w.deg, w.src, d_off, B, N, w.eps, w.logits, nullptr, s))) return rc;
         return arreau_launch_reverse(m, d_frac, d_types, d_lengths, d_angles, w.t_cur, d_off, B, N, w.eps, w.logits, w.len0,
                                      StepNoiseSrc{nullptr, nullptr, nullptr, seed}, d_const_types, d_lattice, s, d_fixed_lengths,
-                                     w.gs, w.batch, w.lattice, w.cvec);
+                                     w.gs, w.batch, w.lattice, w.cvec, cond);
     }
     if ((rc = arreau_launch_prep(m, d_frac, d_lengths, d_angles, nullptr, d_off, B, N, w.lattice, w.cart, w.batch, w.cvec, s,
                                  w.t_next, w.t_cur)))
@@ -320,7 +321,7 @@ int enqueue_sample_step(const arreau_model* m, float* d_frac, int32_t* d_types, 
         return rc;
     return arreau_launch_reverse(m, d_frac, d_types, d_lengths, d_angles, w.t_cur, d_off, B, N, w.eps, w.logits, w.len0,
                                  StepNoiseSrc{nullptr, nullptr, nullptr, seed}, d_const_types, d_lattice, s, d_fixed_lengths,
-                                 pool_in_update ? w.gs : nullptr, w.batch);
+                                 pool_in_update ? w.gs : nullptr, w.batch, nullptr, nullptr, cond);
 }
 }  // namespace
 
@@ -328,6 +329,15 @@ extern "C" int arreau_sample_loop(arreau_model* m, float* d_frac, int32_t* d_typ
                                   const float* d_angles, const int32_t* d_off, int32_t B, int32_t N, int32_t t_start,
                                   int32_t n_steps, uint64_t seed, const int32_t* d_const_types,
                                   const float* d_fixed_lengths, float* d_lattice, void* d_workspace, size_t workspace_bytes, int32_t use_graph, void* stream) {
+    return arreau_sample_loop_conditioned(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, t_start, n_steps, seed, d_const_types,
+                                          d_fixed_lengths, d_lattice, d_workspace, workspace_bytes, use_graph, nullptr, stream);
+}
+
+extern "C" int arreau_sample_loop_conditioned(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths,
+                                              const float* d_angles, const int32_t* d_off, int32_t B, int32_t N, int32_t t_start,
+                                              int32_t n_steps, uint64_t seed, const int32_t* d_const_types,
+                                              const float* d_fixed_lengths, float* d_lattice, void* d_workspace, size_t workspace_bytes,
+                                              int32_t use_graph, const arreau_sample_condition* condition, void* stream) {
     ARREAU_REQUIRE(m && d_frac && d_types && d_lengths && d_angles && d_off && d_lattice, "arreau_sample_loop: null pointer");
     ARREAU_REQUIRE(B >= 1 && N >= 0 && n_steps >= 0, "arreau_sample_loop: bad size");
     ARREAU_REQUIRE(!m->packed_stale || arreau_general_path(m),
@@ -339,9 +349,12 @@ extern "C" int arreau_sample_loop(arreau_model* m, float* d_frac, int32_t* d_typ
         arreau_set_error("arreau_sample_loop: workspace too small");
         return ARREAU_ECAPACITY;
     }
+    SampleConditionDev cond_dev;
+    int rc;
+    if ((rc = arreau_condition_to_dev(condition, &cond_dev))) return rc;
+    const SampleConditionDev* cond = arreau_condition_empty(&cond_dev) ? nullptr : &cond_dev;  // empty: the unconditioned loop
     if (n_steps == 0) return ARREAU_OK;
     hipStream_t s = (hipStream_t)stream;
-    int rc;
     const bool no_prep = loop_without_prep(m);
     if (no_prep) {
         // t_cur holds the timestep of the step in progress; every step's first launch advances it, so it starts one above
@@ -356,7 +369,7 @@ extern "C" int arreau_sample_loop(arreau_model* m, float* d_frac, int32_t* d_typ
     }
     if (!use_graph || n_steps < 3) {
         for (int i = 0; i < n_steps; ++i)
-            if ((rc = enqueue_sample_step(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types, d_fixed_lengths, d_lattice, w, s, no_prep)))
+            if ((rc = enqueue_sample_step(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types, d_fixed_lengths, d_lattice, w, s, no_prep, cond)))
                 return rc;
         return ARREAU_OK;
     }
@@ -379,8 +392,9 @@ extern "C" int arreau_sample_loop(arreau_model* m, float* d_frac, int32_t* d_typ
     ARREAU_CHECK_HIP(hipStreamWaitEvent(s, ev, 0));
     // The executable graph is kept with the model and reused while the next call names the same buffers, sizes and seed
     // (a sampler drawing sub-batch after sub-batch through the caching allocator does): capture + instantiation, about
-    // 2 ms, are then paid once.  The timestep is not part of the graph (it lives in t_next / t_cur, set above).
-    const uint64_t key[12] = {(uint64_t)d_frac, (uint64_t)d_types, (uint64_t)d_lengths, (uint64_t)d_angles, (uint64_t)d_off,
+    // 2 ms, are then paid once.  The timestep is not part of the graph (it lives in t_next / t_cur, set above).  The condition's
+    // pointers are kernel arguments of the capture: another condition is another graph.
+    const uint64_t key[18] = {(uint64_t)d_frac, (uint64_t)d_types, (uint64_t)d_lengths, (uint64_t)d_angles, (uint64_t)d_off,
                               ((uint64_t)(uint32_t)B << 32) | (uint32_t)N, seed, (uint64_t)d_const_types, (uint64_t)d_fixed_lengths,
                               (uint64_t)d_lattice, (uint64_t)d_workspace,
                               ((uint64_t)(uint32_t)(m->edge_variant | (no_prep ? 0x10000 : 0) |
@@ -389,18 +403,21 @@ extern "C" int arreau_sample_loop(arreau_model* m, float* d_frac, int32_t* d_typ
                                                     // a changed switch must not replay the stale graph
                                                     (arreau_basis_form(m, N) ? 0x20000 : 0) | (arreau_basis_fp8(m) ? 0x40000 : 0) | (arreau_cross_fp8(m) ? 0x400000 : 0) |
                                                     (arreau_small_layer_fusable(m, N) ? 0x80000 : 0) |
-                                                    ((m->conv_variant & 3) << 20)) << 32) | (uint32_t)m->mlp_variant};
+                                                    ((m->conv_variant & 3) << 20)) << 32) | (uint32_t)m->mlp_variant,
+                              (uint64_t)cond_dev.x0, (uint64_t)cond_dev.pos_mask, (uint64_t)cond_dev.a0, (uint64_t)cond_dev.type_mask,
+                              (uint64_t)cond_dev.l0, (uint64_t)cond_dev.len_mask};
     hipGraphExec_t exec = (hipGraphExec_t)m->retired_graph;
     int first_replay = 0;
     hipError_t e = hipSuccess;
+    static_assert(sizeof(key) == sizeof(m->graph_key), "graph key size");
     if (!exec || memcmp(key, m->graph_key, sizeof(key)) != 0) {
         // The first step runs eagerly (it also forces lazy module loading, which must not happen inside a capture).
-        if ((rc = enqueue_sample_step(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types, d_fixed_lengths, d_lattice, w, s, no_prep)))
+        if ((rc = enqueue_sample_step(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types, d_fixed_lengths, d_lattice, w, s, no_prep, cond)))
             return rc;
         first_replay = 1;
         hipGraph_t graph = nullptr;
         ARREAU_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        rc = enqueue_sample_step(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types, d_fixed_lengths, d_lattice, w, s, no_prep);
+        rc = enqueue_sample_step(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types, d_fixed_lengths, d_lattice, w, s, no_prep, cond);
         e = hipStreamEndCapture(s, &graph);
         if (rc) {
             if (graph) (void)hipGraphDestroy(graph);

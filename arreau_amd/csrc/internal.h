@@ -71,7 +71,7 @@ struct arreau_model {
     int packed_stale;        // 1 after arreau_model_update_train_weights: the sampling kernels' packed planes are out of date
     void* loop_stream;       // hipStream_t / hipEvent_t of arreau_sample_loop's graph mode (capture is not allowed on the
     void* loop_event;        //   legacy default stream callers usually pass); created on first use
-    uint64_t graph_key[12];  // what the cached executable graph of arreau_sample_loop was captured for
+    uint64_t graph_key[18];  // what the cached executable graph of arreau_sample_loop was captured for
     void* retired_graph;     // hipGraphExec_t of the last arreau_sample_loop (+ the stream it was launched on): destroyed,
     void* retired_stream;    //   after that stream has drained, by the next loop or by arreau_model_destroy
     int32_t* status;         // device word of sticky ARREAU_STATUS_* bits (written by the kernels with atomicOr)
@@ -209,6 +209,22 @@ struct StepNoiseSrc {
     uint64_t seed;           // used when the arrays are null
 };
 
+// Conditioned sampling (arreau_sample_condition, include/arreau_hip.h): the known components of the state, device pointers, each
+// may be null.  Masks are one byte per atom / crystal, nonzero = known.  Kernels take it by value and hand their helpers a pointer
+// to it, or null when the launch has no condition (then the helpers compile to the unconditioned code).
+struct SampleConditionDev {
+    const float* x0;          // [N,3] known fractional coordinates
+    const uint8_t* pos_mask;  // [N]
+    const int32_t* a0;        // [N]   known class indices
+    const uint8_t* type_mask; // [N]
+    const float* l0;          // [B,3] known cell lengths
+    const uint8_t* len_mask;  // [B]
+};
+inline bool arreau_condition_empty(const SampleConditionDev* c) {
+    return !c || !((c->x0 && c->pos_mask) || (c->a0 && c->type_mask) || (c->l0 && c->len_mask));
+}
+int arreau_condition_to_dev(const arreau_sample_condition* c, SampleConditionDev* out);  // update.hip
+
 void arreau_train_ctx_destroy(struct arreau_train_ctx* t);
 // edge_variant value that selects the shape-general fp32 network (train_net.hip) for the whole evaluation
 #define ARREAU_VARIANT_GENERAL 5
@@ -274,7 +290,8 @@ int arreau_launch_reverse(const arreau_model* m, float* d_frac, int32_t* d_types
                           const float* d_gs_atoms = nullptr /* pool these per-atom read-outs into d_len0 first */,
                           const int32_t* d_batch = nullptr /* crystal index of each atom, if the caller has it */,
                           float* d_lattice_ws = nullptr, float* d_cvec_next = nullptr /* sampling loop: also prepare the next step
-                          (workspace lattice + per-crystal embedding for timestep t - 1), see reverse_crystal_block */);
+                          (workspace lattice + per-crystal embedding for timestep t - 1), see reverse_crystal_block */,
+                          const SampleConditionDev* cond = nullptr /* conditioned sampling; needs Philox noise (noise.seed) */);
 int arreau_launch_edge(const arreau_model* m, const float* dir, const float* dist, const int32_t* deg,
                        const int32_t* batch, const float* lattice, int N, float* kbuf, hipStream_t s);
 int arreau_launch_edge_bf16x6(const arreau_model* m, const float* dir, const float* dist, const int32_t* deg,

@@ -10,6 +10,9 @@
 #define ARREAU_DRAW_Z_LATTICE 0u  // randn [B,3]
 #define ARREAU_DRAW_Z_FRAC 1u     // randn [N,3]
 #define ARREAU_DRAW_U_TYPES 2u    // rand  [N,S]
+// conditioned sampling (arreau_sample_loop_conditioned): the forward-noising draws of the known components
+#define ARREAU_DRAW_Z_KNOWN_FRAC 3u     // randn [N,3]  VE_pbc.forward of a known position (diffusion_helpers.py:43-47)
+#define ARREAU_DRAW_Z_KNOWN_LENGTHS 4u  // randn [B,3]  VP_lattice.forward of a known length (diffusion_helpers.py:156-163)
 
 struct Philox4 { uint32_t x[4]; };
 

@@ -12,7 +12,7 @@ __device__ __forceinline__ void reverse_lattice_body(int gt /* global thread of 
                                        int32_t* __restrict__ status, int b0,
                                        // sampling loop: pool the per-atom read-out here (same ordered sum as
                                        // readout_crystals_kernel) instead of a launch of its own; len0_out receives it
-                                       const float* __restrict__ gs_atoms, float* __restrict__ len0_out) {
+                                       const float* __restrict__ gs_atoms, float* __restrict__ len0_out, const SampleConditionDev* cond) {
     // four lanes per crystal: lane i < 3 owns length component i (pooling, update), lane 0 then writes the cell
     const int b = b0 + (gt >> 2), i = gt & 3;
     const bool live = b < B;  // (whole groups of four are live or not; the shuffles below need every lane)
@@ -22,7 +22,7 @@ __device__ __forceinline__ void reverse_lattice_body(int gt /* global thread of 
     t = t < 1 ? 1 : (t > T ? T : t);
     const int first = offsets[bc], last = offsets[bc + 1];
     float mylen = 0.f;
-    if (live && i < 3) mylen = reverse_length_component(b, i, t, first, last, lengths, len0, noise, alpha_bars, betas, fixed_lengths, gs_atoms, len0_out);
+    if (live && i < 3) mylen = reverse_length_component(b, i, t, first, last, lengths, len0, noise, alpha_bars, betas, fixed_lengths, gs_atoms, len0_out, cond);
     const int base = (threadIdx.x & 63) & ~3;
     float newlen[3];
 #pragma unroll
@@ -44,6 +44,9 @@ __device__ __forceinline__ void reverse_lattice_body(int gt /* global thread of 
 // ONE launch for the four updates of a step (round 3; they were two): the first `lat_blocks` workgroups (256 threads = 64
 // crystals, four lanes each) run the lattice update, the others the atom update, one wave per atom.  The two parts touch
 // disjoint data (lengths / lattice / pooled read-out against coordinates / types), so nothing orders them.
+// COND: conditioned sampling (the last argument is read); reverse_kernel<false> is the unconditioned kernel, whose helpers
+// see a null condition and compile to what they were before conditioning existed.
+template <bool COND>
 __global__ __launch_bounds__(256) void reverse_kernel(
     int lat_blocks, float* __restrict__ lengths, const float* __restrict__ angles, const int32_t* __restrict__ tstep,
     const int32_t* __restrict__ offsets, const float* __restrict__ len0, StepNoiseSrc noise, const float* __restrict__ alpha_bars,
@@ -54,35 +57,48 @@ __global__ __launch_bounds__(256) void reverse_kernel(
     const float* __restrict__ qmats, int S, const int32_t* __restrict__ const_types, int absorbing, int n0,
     const int32_t* __restrict__ batch,
     // sampling loop: the lattice part is one workgroup per crystal, which also prepares the next step (reverse_crystal_block)
-    float* __restrict__ lattice_ws, float* __restrict__ cvec_next, const float* __restrict__ t_emb_w, const float* __restrict__ embT, int C) {
+    float* __restrict__ lattice_ws, float* __restrict__ cvec_next, const float* __restrict__ t_emb_w, const float* __restrict__ embT, int C,
+    SampleConditionDev cond_arg) {
+    const SampleConditionDev* cond = COND ? &cond_arg : nullptr;
     if ((int)blockIdx.x < lat_blocks && cvec_next != nullptr) {  // (kernel argument: uniform)
         reverse_crystal_block(b0 + (int)blockIdx.x, lengths, angles, tstep, offsets, len0, noise, alpha_bars, betas, T, lattice, fixed_lengths,
-                              status, gs_atoms, len0_out, lattice_ws, cvec_next, t_emb_w, embT, S, C);
+                              status, gs_atoms, len0_out, lattice_ws, cvec_next, t_emb_w, embT, S, C, cond);
         return;
     }
     if ((int)blockIdx.x < lat_blocks) {
         reverse_lattice_body(blockIdx.x * blockDim.x + threadIdx.x, lengths, angles, tstep, offsets, len0, noise, alpha_bars, betas, B_lat, T,
-                             lattice, fixed_lengths, status, b0, gs_atoms, len0_out);
+                             lattice, fixed_lengths, status, b0, gs_atoms, len0_out, cond);
         return;
     }
     reverse_atoms_body((int)blockIdx.x - lat_blocks, frac, types, tstep, offsets, B, N, eps, logits, noise, ve_sigmas, q1t, qmats, S, T,
-                       const_types, absorbing, status, n0, batch);
+                       const_types, absorbing, status, n0, batch, cond);
 }
 
 int arreau_launch_reverse(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
                           const int32_t* d_t, const int32_t* d_off, int B, int N, const float* d_eps,
                           const float* d_logits, const float* d_len0, StepNoiseSrc noise, const int32_t* d_const_types,
                           float* d_lattice, hipStream_t s, const float* d_fixed_lengths, const float* d_gs_atoms,
-                          const int32_t* d_batch, float* d_lattice_ws, float* d_cvec_next) {
+                          const int32_t* d_batch, float* d_lattice_ws, float* d_cvec_next, const SampleConditionDev* cond) {
     const bool prep_next = d_cvec_next != nullptr;  // one workgroup per crystal, which also prepares the next step
     ARREAU_REQUIRE(!prep_next || d_lattice_ws != nullptr, "reverse update: the next step's set-up needs the workspace lattice");
     const int lat_blocks = B > 0 ? (prep_next ? B : (4 * B + 255) / 256) : 0;
     const int atom_blocks = N > 0 ? (N + 3) / 4 : 0;
-    if (lat_blocks + atom_blocks > 0) {
-        ARREAU_LAUNCH(reverse_kernel, dim3(lat_blocks + atom_blocks), dim3(256), 0, s, lat_blocks, d_lengths, d_angles, d_t, d_off, d_len0,
+    const bool conditioned = !arreau_condition_empty(cond);
+    ARREAU_REQUIRE(!conditioned || (!noise.z_lattice && !noise.z_frac && !noise.u_types),
+                   "reverse update: conditioned sampling needs the in-kernel (Philox) noise");
+    if (lat_blocks + atom_blocks > 0 && conditioned) {
+        ARREAU_LAUNCH(reverse_kernel<true>, dim3(lat_blocks + atom_blocks), dim3(256), 0, s, lat_blocks, d_lengths, d_angles, d_t, d_off, d_len0,
                       noise, m->vp_alpha_bars, m->vp_betas, B, m->T, d_lattice, d_fixed_lengths, m->status, 0, d_gs_atoms,
                       d_gs_atoms ? const_cast<float*>(d_len0) : nullptr, d_frac, d_types, B, N, d_eps, d_logits, m->ve_sigmas, m->q1t,
-                      m->qmats, m->S, d_const_types, m->qmats_absorbing, 0, d_batch, d_lattice_ws, d_cvec_next, m->t_emb_w, m->embT, m->C);
+                      m->qmats, m->S, d_const_types, m->qmats_absorbing, 0, d_batch, d_lattice_ws, d_cvec_next, m->t_emb_w, m->embT, m->C,
+                      *cond);
+        ARREAU_CHECK_HIP(hipGetLastError());
+    } else if (lat_blocks + atom_blocks > 0) {
+        ARREAU_LAUNCH(reverse_kernel<false>, dim3(lat_blocks + atom_blocks), dim3(256), 0, s, lat_blocks, d_lengths, d_angles, d_t, d_off, d_len0,
+                      noise, m->vp_alpha_bars, m->vp_betas, B, m->T, d_lattice, d_fixed_lengths, m->status, 0, d_gs_atoms,
+                      d_gs_atoms ? const_cast<float*>(d_len0) : nullptr, d_frac, d_types, B, N, d_eps, d_logits, m->ve_sigmas, m->q1t,
+                      m->qmats, m->S, d_const_types, m->qmats_absorbing, 0, d_batch, d_lattice_ws, d_cvec_next, m->t_emb_w, m->embT, m->C,
+                      SampleConditionDev{});
         ARREAU_CHECK_HIP(hipGetLastError());
     }
     return ARREAU_OK;
@@ -101,7 +117,7 @@ extern "C" int arreau_reverse_step(const arreau_model* m, float* d_frac, int32_t
 }
 
 // The sampler's in-kernel noise, written out: out[i] = the draw (seed, timestep, kind, element i) -- standard normal for
-// kinds 0/1, uniform [0,1) for kind 2.  For tests (known-answer / statistics) and for reproducing a Philox trajectory
+// kinds 0/1/3/4, uniform [0,1) for kind 2.  For tests (known-answer / statistics) and for reproducing a Philox trajectory
 // through arreau_reverse_step.
 __global__ void philox_fill_kernel(uint64_t seed, uint32_t timestep, uint32_t kind, int64_t n, float* __restrict__ out,
                                    uint32_t* __restrict__ raw) {
@@ -117,10 +133,56 @@ __global__ void philox_fill_kernel(uint64_t seed, uint32_t timestep, uint32_t ki
 
 extern "C" int arreau_philox_fill(uint64_t seed, int32_t timestep, int32_t kind, int64_t n, float* d_out, uint32_t* d_raw,
                                   void* stream) {
-    ARREAU_REQUIRE((d_out || d_raw) && n >= 0 && kind >= 0 && kind <= 2, "arreau_philox_fill: bad argument");
+    ARREAU_REQUIRE((d_out || d_raw) && n >= 0 && kind >= 0 && kind <= 4, "arreau_philox_fill: bad argument");
     if (n == 0) return ARREAU_OK;
     ARREAU_LAUNCH(philox_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, seed,
                        (uint32_t)timestep, (uint32_t)kind, n, d_out, d_raw);
+    ARREAU_CHECK_HIP(hipGetLastError());
+    return ARREAU_OK;
+}
+
+// Conditioned sampling, rule 5 (include/arreau_hip.h): the known components of the initial state at tau = t_start, i.e. the
+// helpers of the in-loop replacement with Philox timestep key t_start + 1.  One thread per known-position component (3 N),
+// per known-length component (3 B) and per known species (N).
+__global__ void condition_initial_state_kernel(float* __restrict__ frac, int32_t* __restrict__ types, float* __restrict__ lengths,
+                                               int B, int N, int t_key, uint64_t seed, SampleConditionDev cond,
+                                               const float* __restrict__ ve_sigmas, const float* __restrict__ alpha_bars) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g < 3 * (int64_t)N) {
+        if (cond.pos_mask && cond.pos_mask[g / 3]) frac[g] = known_frac_component(&cond, (size_t)g, t_key, seed, ve_sigmas);
+    } else if (g < 3 * (int64_t)N + 3 * (int64_t)B) {
+        const int c = (int)(g - 3 * (int64_t)N), b = c / 3;
+        if (cond.len_mask && cond.len_mask[b]) lengths[c] = known_length_component(&cond, b, c - 3 * b, t_key, seed, alpha_bars);
+    } else if (g < 4 * (int64_t)N + 3 * (int64_t)B) {
+        const int i = (int)(g - 3 * (int64_t)N - 3 * (int64_t)B);
+        if (cond.type_mask && cond.type_mask[i]) types[i] = cond.a0[i];
+    }
+}
+
+// the host struct -> the kernels' by-value form; a mask without its values is an error, values without a mask are ignored
+int arreau_condition_to_dev(const arreau_sample_condition* c, SampleConditionDev* out) {
+    *out = SampleConditionDev{};
+    if (!c) return ARREAU_OK;
+    ARREAU_REQUIRE(!(c->pos_mask && !c->x0) && !(c->type_mask && !c->a0) && !(c->len_mask && !c->l0),
+                   "sample condition: a mask is given without the known values it selects");
+    *out = SampleConditionDev{c->pos_mask ? c->x0 : nullptr, c->pos_mask, c->type_mask ? c->a0 : nullptr, c->type_mask,
+                              c->len_mask ? c->l0 : nullptr, c->len_mask};
+    return ARREAU_OK;
+}
+
+extern "C" int arreau_condition_initial_state(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, int32_t B,
+                                              int32_t N, int32_t t_start, uint64_t seed, const arreau_sample_condition* cond,
+                                              void* stream) {
+    ARREAU_REQUIRE(m && d_frac && d_types && d_lengths, "arreau_condition_initial_state: null pointer");
+    ARREAU_REQUIRE(B >= 1 && N >= 0, "arreau_condition_initial_state: bad size");
+    ARREAU_REQUIRE(t_start >= 1 && t_start <= m->T, "arreau_condition_initial_state: t_start must lie in 1..T");
+    SampleConditionDev c;
+    int rc;
+    if ((rc = arreau_condition_to_dev(cond, &c))) return rc;
+    if (arreau_condition_empty(&c)) return ARREAU_OK;
+    const int64_t n = 4 * (int64_t)N + 3 * (int64_t)B;
+    ARREAU_LAUNCH(condition_initial_state_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_frac, d_types,
+                  d_lengths, B, N, t_start + 1, seed, c, m->ve_sigmas, m->vp_alpha_bars);
     ARREAU_CHECK_HIP(hipGetLastError());
     return ARREAU_OK;
 }

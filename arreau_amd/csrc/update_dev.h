@@ -7,13 +7,42 @@
 
 #define D3PM_EPS 1e-6f  // d3pm.py:23
 
+// torch.remainder(x, 1) for floats: fmod, then shift negatives up by one (can return exactly 1.0f
+// for tiny negative x, like the reference's `% 1`).
+__device__ __forceinline__ float remainder_one(float x) {
+    float m = fmodf(x, 1.0f);
+    if (m != 0.0f && m < 0.0f) m += 1.0f;
+    return m;
+}
+
+// Conditioned sampling (arreau_sample_loop_conditioned; the rules are stated in include/arreau_hip.h).  The step that leaves
+// timestep t produces tau = t - 1; a known component is the template forward-noised to tau with the Philox draw of (seed, t),
+// and the template itself at tau = 0.  The initial state uses the same helpers with t = t_start + 1.
+// Rule 1, VE_pbc.forward (diffusion_helpers.py:43-47): component g = 3 i + d of a known position.
+__device__ __forceinline__ float known_frac_component(const SampleConditionDev* c, size_t g, int t, uint64_t seed,
+                                                      const float* __restrict__ ve_sigmas) {
+    const float x0 = c->x0[g];
+    if (t - 1 == 0) return remainder_one(x0);
+    const float z = philox_normal(seed, (uint32_t)t, ARREAU_DRAW_Z_KNOWN_FRAC, (uint32_t)g);
+    return remainder_one(x0 + ve_sigmas[t - 1] * z);
+}
+// Rule 2, VP_lattice.forward (diffusion_helpers.py:156-163): component i of crystal b's known lengths.
+__device__ __forceinline__ float known_length_component(const SampleConditionDev* c, int b, int i, int t, uint64_t seed,
+                                                        const float* __restrict__ alpha_bars) {
+    const float l0 = c->l0[3 * b + i];
+    if (t - 1 == 0) return l0;
+    const float ab = alpha_bars[t - 1];
+    const float z = philox_normal(seed, (uint32_t)t, ARREAU_DRAW_Z_KNOWN_LENGTHS, 3u * b + i);
+    return sqrtf(ab) * l0 + sqrtf(1.0f - ab) * z;
+}
+
 // One component of the length update of crystal b at timestep t (VP_lattice.reverse_given_x0; the per-atom read-out is pooled
 // here when gs_atoms is given: the ordered sum of readout_crystals_kernel).  Writes lengths[3 b + i] and returns it.
 __device__ __forceinline__ float reverse_length_component(int b, int i, int t, int first, int last, float* __restrict__ lengths,
                                                           const float* __restrict__ len0, StepNoiseSrc noise,
                                                           const float* __restrict__ alpha_bars, const float* __restrict__ betas,
                                                           const float* __restrict__ fixed_lengths, const float* __restrict__ gs_atoms,
-                                                          float* __restrict__ len0_out) {
+                                                          float* __restrict__ len0_out, const SampleConditionDev* cond) {
     const float* __restrict__ z = noise.z_lattice;
     const float n = (float)(last - first);
     const float ab_t = alpha_bars[t], ab_p = alpha_bars[t - 1], beta = betas[t];
@@ -42,17 +71,11 @@ __device__ __forceinline__ float reverse_length_component(int b, int i, int t, i
     const float zdraw = z ? z[3 * b + i] : philox_normal(noise.seed, (uint32_t)t, ARREAU_DRAW_Z_LATTICE, 3u * b + i);
     const float zz = t > 1 ? zdraw : 0.0f;
     // fixed-cell sampling (arreau_sample_loop, d_fixed_lengths): the given lengths are re-imposed after the update
-    const float mylen = fixed_lengths ? fixed_lengths[3 * b + i] : mean + variance * zz;
+    float mylen = fixed_lengths ? fixed_lengths[3 * b + i] : mean + variance * zz;
+    // conditioned sampling, rule 2: a known length is replaced before the cell is formed from it
+    if (cond && cond->len_mask && cond->len_mask[b]) mylen = known_length_component(cond, b, i, t, noise.seed, alpha_bars);
     lengths[3 * b + i] = mylen;
     return mylen;
-}
-
-// torch.remainder(x, 1) for floats: fmod, then shift negatives up by one (can return exactly 1.0f
-// for tiny negative x, like the reference's `% 1`).
-__device__ __forceinline__ float remainder_one(float x) {
-    float m = fmodf(x, 1.0f);
-    if (m != 0.0f && m < 0.0f) m += 1.0f;
-    return m;
 }
 
 // One wave per atom: VE_pbc.reverse on the fractional coordinates (diffusion_helpers.py:65-81) and
@@ -63,7 +86,8 @@ __device__ __forceinline__ void reverse_one_atom(
     const float* __restrict__ logits, StepNoiseSrc noise,
     const float* __restrict__ ve_sigmas, const float* __restrict__ q1t, const float* __restrict__ qmats, int S,
     int T, const int32_t* __restrict__ const_types, int absorbing, int32_t* __restrict__ status,
-    const int32_t* __restrict__ batch /* crystal of each atom, or null: searched in `offsets` */) {
+    const int32_t* __restrict__ batch /* crystal of each atom, or null: searched in `offsets` */,
+    const SampleConditionDev* cond /* conditioned sampling, or null */) {
     const float* __restrict__ z_frac = noise.z_frac;
     const float* __restrict__ u_types = noise.u_types;
     // crystal of this atom = largest b with offsets[b] <= i: a 64-ary search by the whole wave (each level one
@@ -91,7 +115,9 @@ __device__ __forceinline__ void reverse_one_atom(
         const float mean = frac[g] - eps[g] * (s2 - sp2);
         const float stdv = sqrtf((sp2 * (s2 - sp2)) / s2);
         const float zf = z_frac ? z_frac[g] : philox_normal(noise.seed, (uint32_t)t, ARREAU_DRAW_Z_FRAC, (uint32_t)g);
-        frac[g] = remainder_one(mean + stdv * zf);
+        float fv = remainder_one(mean + stdv * zf);
+        if (cond && cond->pos_mask && cond->pos_mask[i]) fv = known_frac_component(cond, g, t, noise.seed, ve_sigmas);  // rule 1
+        frac[g] = fv;
     }
 
     // ---- D3PM posterior logits ------------------------------------------------------------------
@@ -190,7 +216,8 @@ __device__ __forceinline__ void reverse_one_atom(
         if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }  // first index wins ties
     }
     // use_constant_atomic_symbols (lightning_wrappers/diffusion.py:231-236): the fixed species are re-imposed each step
-    if (lane == 0) types[i] = const_types ? const_types[i] : besti;
+    // conditioned sampling, rule 4: a known species is re-imposed the same way, per atom
+    if (lane == 0) types[i] = (cond && cond->type_mask && cond->type_mask[i]) ? cond->a0[i] : (const_types ? const_types[i] : besti);
 }
 
 // the form the stand-alone kernel uses: workgroup `blk` of four waves, one atom each
@@ -200,11 +227,11 @@ __device__ __forceinline__ void reverse_atoms_body(
     const float* __restrict__ logits, StepNoiseSrc noise,
     const float* __restrict__ ve_sigmas, const float* __restrict__ q1t, const float* __restrict__ qmats, int S,
     int T, const int32_t* __restrict__ const_types, int absorbing, int32_t* __restrict__ status, int n0,
-    const int32_t* __restrict__ batch) {
+    const int32_t* __restrict__ batch, const SampleConditionDev* cond) {
     const int i = n0 + blk * 4 + (int)(threadIdx.x >> 6);  // atoms n0 .. N-1
     if (i >= N) return;  // wave-uniform; no block-level barrier below
     reverse_one_atom(i, threadIdx.x & 63, frac, types, tstep, offsets, B, eps, logits, noise, ve_sigmas, q1t, qmats, S, T, const_types, absorbing,
-                     status, batch);
+                     status, batch, cond);
 }
 
 // Sampling loop (round 3): the lattice update of a crystal by ONE workgroup that then also prepares the crystal's NEXT step --
@@ -220,7 +247,7 @@ __device__ __forceinline__ void reverse_crystal_block(int b, float* __restrict__
                                                       int32_t* __restrict__ status, const float* __restrict__ gs_atoms,
                                                       float* __restrict__ len0_out, float* __restrict__ lattice_ws,
                                                       float* __restrict__ cvec_next, const float* __restrict__ t_emb_w,
-                                                      const float* __restrict__ embT, int S, int C) {
+                                                      const float* __restrict__ embT, int S, int C, const SampleConditionDev* cond) {
     __shared__ float newlen[3];
     __shared__ float feat[ARREAU_T_EMB_DIM + ARREAU_N_CRYSTAL_FEATS];
     const int t_raw = tstep[b];
@@ -229,7 +256,7 @@ __device__ __forceinline__ void reverse_crystal_block(int b, float* __restrict__
     const int first = offsets[b], last = offsets[b + 1];
     if (threadIdx.x < 3)
         newlen[threadIdx.x] = reverse_length_component(b, threadIdx.x, t, first, last, lengths, len0, noise, alpha_bars, betas, fixed_lengths,
-                                                       gs_atoms, len0_out);
+                                                       gs_atoms, len0_out, cond);
     __syncthreads();
     const float* ang = angles + 3 * b;
     if (threadIdx.x == 0) {

@@ -252,11 +252,11 @@ class DiffusionLoss(nn.Module):
         return eng.predict_scores(frac, ty, lengths, ang, t_c, off, edges=edges)
 
     @torch.no_grad()
-    def sample(self, *, model, z_table: AtomicNumberTable, t_emb_weights=None, num_atoms_per_sample,
-               num_samples_in_batch: int, vis_name: str = "", visualization_setting=VisualizationSetting.NONE,
+    def sample(self, *, model, z_table: AtomicNumberTable, t_emb_weights=None, num_atoms_per_sample=None,
+               num_samples_in_batch: Optional[int] = None, vis_name: str = "", visualization_setting=VisualizationSetting.NONE,
                show_bonds: bool = False, constant_atoms: Optional[torch.Tensor] = None, noise: str = "philox",
                max_steps: Optional[int] = None, use_graph: Optional[bool] = None, seed: Optional[int] = None,
-               fixed_cell: bool = False) -> SampleResult:
+               fixed_cell: bool = False, condition=None) -> SampleResult:
         """diffusion_loss.py:276-377.  The initial state is drawn on the host exactly like the reference (numpy
         uniforms for the angles, then randn lengths, randn fractional coordinates from torch's global CPU generator).
         Per-step noise:
@@ -274,12 +274,21 @@ class DiffusionLoss(nn.Module):
         (the reference's schedule, diffusion_loss.py:351-370), as `<vis_name>_<timestep>.cif` / `<vis_name>_final.cif`
         structure files (inference/visualize_crystal.py; the reference renders PNGs through plotly + pymatgen).
         `fixed_cell=True` (extension, noise="philox" only): fixed-cell sampling -- the initial cell lengths are re-imposed
-        after every step (arreau_sample_loop's d_fixed_lengths); coordinates and species are sampled as usual."""
+        after every step (arreau_sample_loop's d_fixed_lengths); coordinates and species are sampled as usual.
+        `condition` (extension, noise="philox" only): a conditioning.SampleCondition -- known positions, species and cells held
+        to a template while the rest is generated (arreau_sample_loop_conditioned; rules in include/arreau_hip.h).  It defines
+        the batch: num_atoms_per_sample / num_samples_in_batch may be omitted or must agree with it.  The initial state is
+        drawn exactly as without it; the known components are then overwritten on the device."""
         frames = visualization_setting != VisualizationSetting.NONE
         if frames and not vis_name:
             raise ValueError("visualization_setting other than NONE needs vis_name (prefix of the frame files)")
         if noise not in ("philox", "device", "reference"):
             raise ValueError("noise must be 'philox', 'device' or 'reference'")
+        if condition is not None:  # validated before the engine is touched
+            num_atoms_per_sample, num_samples_in_batch = condition.resolve_batch(num_atoms_per_sample, num_samples_in_batch)
+            condition.check_sampling(z_table, noise=noise, fixed_cell=fixed_cell, constant_species=constant_atoms is not None)
+        elif num_atoms_per_sample is None or num_samples_in_batch is None:
+            raise ValueError("num_atoms_per_sample and num_samples_in_batch are needed without a condition")
         eng = model.engine()
         dev = eng.device
         S = len(z_table)
@@ -295,6 +304,9 @@ class DiffusionLoss(nn.Module):
         N = int(num_atoms.sum())
         dt = torch.get_default_dtype()
         angles = torch.tensor(np.array([sample_bravais_angles("monoclinic") for _ in range(B)]))
+        if condition is not None and condition.lattice_known().any():  # rule 3: the template's angles (radians)
+            known = torch.as_tensor(condition.lattice_known())
+            angles[known] = torch.as_tensor(condition.known_angles(), dtype=angles.dtype)[known]
         lengths = torch.randn([B, 3])
         frac_x = torch.randn([N, 3], dtype=dt) * pos_sigma_max
         if constant_atoms is not None:
@@ -324,6 +336,13 @@ class DiffusionLoss(nn.Module):
         if noise == "philox" and seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
             rng_state = torch.random.get_rng_state()
+        cond_d = None
+        if condition is not None:
+            # rule 5: the known components of the drawn initial state, at timestep T - 1 (Philox key T); the saved initial
+            # state of a re-run below includes them
+            cond_d = condition.device_arrays(z_table, dev)
+            eng.condition_initial_state(frac_d, types_d, len_d, self.T - 1, seed, cond_d)
+            init_state = (frac_d.clone(), types_d.clone(), len_d.clone())
 
         def run_loop(use_graph):
             if noise == "philox":
@@ -342,7 +361,7 @@ class DiffusionLoss(nn.Module):
                     n_seg = (t_cur - t_stop + 1) if t_stop is not None else (t_cur - t_last + 1)
                     if n_seg > 0:
                         eng.sample_loop(frac_d, types_d, len_d, ang_d, off_d, t_cur, n_seg, seed, const_d, lattice_d,
-                                        use_graph=bool(use_graph), fixed_lengths=fixed)
+                                        use_graph=bool(use_graph), fixed_lengths=fixed, condition=cond_d)
                         t_cur -= n_seg
                     if t_stop is not None:
                         vis_crystal_during_sampling(z_table, types_d.cpu().numpy(), lattice_d.cpu().numpy(),

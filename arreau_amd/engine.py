@@ -191,18 +191,52 @@ class HipEngine:
         return logits, vec_out, gscalar
 
     def sample_loop(self, frac, types, lengths, angles, offsets, t_start, n_steps, seed, const_types, lattice_out,
-                    use_graph=False, fixed_lengths=None):
+                    use_graph=False, fixed_lengths=None, condition=None):
         """n_steps iterations of the sampling loop in one library call (arreau_sample_loop): in-place update of
-        (frac, types, lengths); Philox noise keyed by (seed, timestep, draw, element)."""
+        (frac, types, lengths); Philox noise keyed by (seed, timestep, draw, element).  `condition`: the device arrays of a
+        conditioned run (SampleCondition.device_arrays: x0, pos_mask, a0, type_mask, l0, len_mask; None entries allowed),
+        through arreau_sample_loop_conditioned."""
         N, B = frac.shape[0], lengths.shape[0]
         ws = self.workspace(N, B)
-        _hip.check(_hip.lib().arreau_sample_loop(
-            self._handle, _hip.ptr(frac), _hip.ptr(types), _hip.ptr(lengths), _hip.ptr(angles), _hip.ptr(offsets), B, N,
-            int(t_start), int(n_steps), int(seed) & (2 ** 64 - 1), _hip.ptr(const_types), _hip.ptr(fixed_lengths), _hip.ptr(lattice_out), _hip.ptr(ws),
-            ws.numel(), int(bool(use_graph)), _hip.stream_ptr(self.device)), "arreau_sample_loop")
+        args = (self._handle, _hip.ptr(frac), _hip.ptr(types), _hip.ptr(lengths), _hip.ptr(angles), _hip.ptr(offsets), B, N,
+                int(t_start), int(n_steps), int(seed) & (2 ** 64 - 1), _hip.ptr(const_types), _hip.ptr(fixed_lengths),
+                _hip.ptr(lattice_out), _hip.ptr(ws), ws.numel(), int(bool(use_graph)))
+        if condition is None:
+            _hip.check(_hip.lib().arreau_sample_loop(*args, _hip.stream_ptr(self.device)), "arreau_sample_loop")
+        else:
+            cond = self._condition_struct(condition, N, B)
+            _hip.check(_hip.lib().arreau_sample_loop_conditioned(*args, ctypes.byref(cond), _hip.stream_ptr(self.device)),
+                       "arreau_sample_loop_conditioned")
+
+    def condition_initial_state(self, frac, types, lengths, t_start, seed, condition):
+        """Rule 5 of conditioned sampling (arreau_condition_initial_state): the known components of an initial state drawn
+        for timestep t_start, in place."""
+        N, B = frac.shape[0], lengths.shape[0]
+        cond = self._condition_struct(condition, N, B)
+        _hip.check(_hip.lib().arreau_condition_initial_state(
+            self._handle, _hip.ptr(frac), _hip.ptr(types), _hip.ptr(lengths), B, N, int(t_start), int(seed) & (2 ** 64 - 1),
+            ctypes.byref(cond), _hip.stream_ptr(self.device)), "arreau_condition_initial_state")
+
+    def _condition_struct(self, condition, N, B):
+        """arreau_sample_condition of a dict of device tensors, with their shapes, dtypes and device checked."""
+        spec = {"x0": ((N, 3), torch.float32), "pos_mask": ((N,), torch.uint8), "a0": ((N,), torch.int32),
+                "type_mask": ((N,), torch.uint8), "l0": ((B, 3), torch.float32), "len_mask": ((B,), torch.uint8)}
+        unknown = set(condition) - set(spec)
+        if unknown:
+            raise ValueError(f"condition: unknown entries {sorted(unknown)}")
+        c = _hip.SampleConditionC()
+        for name, (shape, dtype) in spec.items():
+            t = condition.get(name)
+            if t is None:
+                continue
+            if tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"condition: {name} must be a contiguous {dtype} tensor of shape {shape} on {self.device}")
+            setattr(c, name, _hip.ptr(t))
+        return c
 
     def philox_fill(self, seed, timestep, kind, n, raw=False):
-        """The sampler's in-kernel noise written out (arreau_philox_fill): kind 0/1 standard normal, 2 uniform [0,1)."""
+        """The sampler's in-kernel noise written out (arreau_philox_fill): kinds 0/1 (and 3/4, the draws of conditioned
+        sampling) standard normal, 2 uniform [0,1)."""
         out = torch.empty(n, device=self.device, dtype=torch.float32)
         words = torch.empty((n, 4), device=self.device, dtype=torch.int32) if raw else None
         _hip.check(_hip.lib().arreau_philox_fill(int(seed) & (2 ** 64 - 1), int(timestep), int(kind), int(n), _hip.ptr(out),

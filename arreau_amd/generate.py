@@ -7,6 +7,10 @@ in crystal order.  The only communication is that final gather of host arrays
 
     python -m torch.distributed.run --nproc-per-node 8 -m arreau_amd.generate --model_path last.ckpt \
         --num_crystals 8192 --num_atoms 20 --out out/crystals.npz
+
+Conditioned generation (structure completion): `--template crystals.npz` (the wire format below, plus optional
+`position_mask` [N] / `species_mask` [N] / `lattice_mask` [B] arrays) gives the batch; `--fix positions,species,lattice`
+fixes those components wherever the file has no mask for them; `--samples_per_template K` tiles the templates K times.
 """
 import argparse
 import os
@@ -37,16 +41,46 @@ def concat_results(parts) -> SampleResult:
         idx_start=np.cumsum(num_atoms) - num_atoms)
 
 
-def generate_n_crystals(sample_fn: Callable[[int, int], SampleResult], num_crystals: int, num_atoms_per_sample: int,
-                        num_crystals_per_batch: int = 256, rank: int = 0, world_size: int = 1,
-                        gather: Optional[Callable] = None) -> Optional[SampleResult]:
-    """sample_fn(num_atoms_per_sample, num_samples_in_batch) -> SampleResult  (e.g. PONITA_DIFFUSION.sample).
-    Returns the concatenated result on rank 0 (None elsewhere when world_size > 1)."""
+FIX_KINDS = ("positions", "species", "lattice")
+
+
+def parse_fix(text: str):
+    """'positions,lattice' -> {'positions': True, 'species': False, 'lattice': True}."""
+    kinds = [k.strip() for k in (text or "").split(",") if k.strip()]
+    bad = [k for k in kinds if k not in FIX_KINDS]
+    if bad:
+        raise ValueError(f"--fix: unknown component(s) {bad}; choose from {list(FIX_KINDS)}")
+    return {k: k in kinds for k in FIX_KINDS}
+
+
+def load_template(filename: str, fix: dict):
+    """A SampleCondition from a crystals.npz / .h5 file.  Mask arrays in the file win; otherwise `fix[kind]` (bool) applies
+    to every atom / crystal."""
+    from .diffusion.conditioning import SampleCondition
+    from .diffusion.inference.process_generated_crystals import load_sample_results_from_hdf5
+    res = load_sample_results_from_hdf5(filename)
+    masks = {}
+    names = ("position_mask", "species_mask", "lattice_mask")
+    if str(filename).endswith((".h5", ".hdf5")):
+        import h5py
+        with h5py.File(filename, "r") as fh:
+            masks = {k: fh["crystals"][k][:] for k in names if k in fh["crystals"]}
+    else:
+        with np.load(filename) as z:
+            masks = {k: z[k] for k in names if k in z.files}
+    return SampleCondition.from_sample_result(res, fix_positions=masks.get("position_mask", fix["positions"]),
+                                              fix_species=masks.get("species_mask", fix["species"]),
+                                              fix_lattice=masks.get("lattice_mask", fix["lattice"]))
+
+
+def template_batches(num_crystals: int, batch: int, rank: int = 0, world_size: int = 1):
+    """The sub-batches [start, stop) of the (tiled) template crystals that `rank` samples: its contiguous shard_range slice,
+    cut into pieces of at most `batch` crystals."""
     start, stop = shard_range(num_crystals, world_size, rank)
-    mine = []
-    for s in range(start, stop, num_crystals_per_batch):
-        mine.append(sample_fn(num_atoms_per_sample, min(num_crystals_per_batch, stop - s)))
-    local = concat_results(mine)
+    return [(s, min(s + batch, stop)) for s in range(start, stop, batch)]
+
+
+def _gather_results(local: SampleResult, rank: int, world_size: int, gather: Optional[Callable]):
     if world_size == 1:
         return local
     if gather is None:
@@ -58,6 +92,26 @@ def generate_n_crystals(sample_fn: Callable[[int, int], SampleResult], num_cryst
             return out
     parts = gather(local)
     return concat_results(parts) if rank == 0 else None
+
+
+def generate_from_template(sample_fn: Callable, condition, num_crystals_per_batch: int = 256, rank: int = 0,
+                           world_size: int = 1, gather: Optional[Callable] = None) -> Optional[SampleResult]:
+    """sample_fn(condition) -> SampleResult (e.g. PONITA_DIFFUSION.sample(condition=...)) over this rank's slice of the
+    condition's crystals.  Returns the concatenated result on rank 0 (None elsewhere when world_size > 1)."""
+    mine = [sample_fn(condition.slice(a, b)) for a, b in template_batches(condition.B, num_crystals_per_batch, rank, world_size)]
+    return _gather_results(concat_results(mine), rank, world_size, gather)
+
+
+def generate_n_crystals(sample_fn: Callable[[int, int], SampleResult], num_crystals: int, num_atoms_per_sample: int,
+                        num_crystals_per_batch: int = 256, rank: int = 0, world_size: int = 1,
+                        gather: Optional[Callable] = None) -> Optional[SampleResult]:
+    """sample_fn(num_atoms_per_sample, num_samples_in_batch) -> SampleResult  (e.g. PONITA_DIFFUSION.sample).
+    Returns the concatenated result on rank 0 (None elsewhere when world_size > 1)."""
+    start, stop = shard_range(num_crystals, world_size, rank)
+    mine = []
+    for s in range(start, stop, num_crystals_per_batch):
+        mine.append(sample_fn(num_atoms_per_sample, min(num_crystals_per_batch, stop - s)))
+    return _gather_results(concat_results(mine), rank, world_size, gather)
 
 
 def save_sample_results(crystals: SampleResult, filename: str):
@@ -75,7 +129,13 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--out", type=str, default="out/crystals.npz")
     ap.add_argument("--seed", type=int, default=None, help="seed of the host/device generators (rank is added)")
+    ap.add_argument("--template", type=str, default=None,
+                    help="crystals.npz / .h5 of templates (optional position_mask / species_mask / lattice_mask arrays)")
+    ap.add_argument("--fix", type=str, default="", help="components fixed where the template has no mask: "
+                    "comma-separated subset of positions,species,lattice")
+    ap.add_argument("--samples_per_template", type=int, default=1, help="the templates are tiled this many times")
     args = ap.parse_args()
+    condition = load_template(args.template, parse_fix(args.fix)).tile(args.samples_per_template) if args.template else None
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     # ARREAU_GENERATE_BACKEND=gloo + ARREAU_GENERATE_ONE_DEVICE=1 rehearse several ranks on a one-GPU box (the only
@@ -102,19 +162,22 @@ def main():
     # lock held around each sampler call.  On a node every rank owns its GPU and the variable is not set.
     lock_path = os.environ.get("ARREAU_GENERATE_GPU_LOCK")
 
-    def fn(n, b):
+    def fn(n, b, cond=None):
         if not lock_path:
-            return model.sample(n, b, VisualizationSetting.NONE, False)
+            return model.sample(n, b, VisualizationSetting.NONE, False, condition=cond)
         import fcntl
         with open(lock_path, "a") as lock:
             fcntl.flock(lock, fcntl.LOCK_EX)
             try:
-                out = model.sample(n, b, VisualizationSetting.NONE, False)
+                out = model.sample(n, b, VisualizationSetting.NONE, False, condition=cond)
                 torch.cuda.synchronize()
                 return out
             finally:
                 fcntl.flock(lock, fcntl.LOCK_UN)
-    res = generate_n_crystals(fn, args.num_crystals, args.num_atoms, args.batch, rank, world)
+    if condition is not None:
+        res = generate_from_template(lambda c: fn(None, None, c), condition, args.batch, rank, world)
+    else:
+        res = generate_n_crystals(fn, args.num_crystals, args.num_atoms, args.batch, rank, world)
     if rank == 0:
         print("wrote", save_sample_results(res, args.out))
     if world > 1:

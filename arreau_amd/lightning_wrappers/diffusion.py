@@ -307,15 +307,19 @@ class PONITA_DIFFUSION(nn.Module):
         return logits, vec_out, gscalar, None, [None] * self.model.num_layers
 
     @torch.no_grad()
-    def sample(self, num_atoms_per_sample, num_samples_in_batch: int,
+    def sample(self, num_atoms_per_sample=None, num_samples_in_batch: Optional[int] = None,
                visualization_setting: VisualizationSetting = VisualizationSetting.NONE, show_bonds: bool = False,
                use_constant_atomic_symbols: Optional[list] = None, noise: str = "philox",
                max_steps: Optional[int] = None, use_graph: Optional[bool] = None,
-               seed: Optional[int] = None, fixed_cell: bool = False, vis_name: Optional[str] = None) -> SampleResult:
+               seed: Optional[int] = None, fixed_cell: bool = False, vis_name: Optional[str] = None,
+               condition=None) -> SampleResult:
         """lightning_wrappers/diffusion.py:220-253.  `num_atoms_per_sample` may also be a sequence with one atom count
         per crystal of the batch (extension; the reference supports a single int).  Frames of a visualization_setting
         other than NONE go to `<DIFFUSION_DIR>/step_<timestep>.cif` like the reference's PNGs (`vis_name` overrides the
-        prefix)."""
+        prefix).  `condition` (extension): a diffusion.conditioning.SampleCondition -- structure completion from a
+        template (DiffusionLoss.sample); it defines the batch, so the two counts may be omitted."""
+        if condition is not None and use_constant_atomic_symbols is not None and condition.species_known().any():
+            raise ValueError("use_constant_atomic_symbols and a species mask both fix the species; give one of them")
         z_table = AtomicNumberTable(self.z_table_zs.tolist())
         if use_constant_atomic_symbols is not None:
             if not isinstance(num_atoms_per_sample, (int, np.integer)):
@@ -330,4 +334,4 @@ class PONITA_DIFFUSION(nn.Module):
             model=self, z_table=z_table, t_emb_weights=self.t_emb, num_atoms_per_sample=num_atoms_per_sample,
             num_samples_in_batch=num_samples_in_batch, vis_name=self._frame_prefix(vis_name, visualization_setting),
             visualization_setting=visualization_setting, show_bonds=show_bonds, constant_atoms=constant_atoms,
-            noise=noise, max_steps=max_steps, use_graph=use_graph, seed=seed, fixed_cell=fixed_cell)
+            noise=noise, max_steps=max_steps, use_graph=use_graph, seed=seed, fixed_cell=fixed_cell, condition=condition)

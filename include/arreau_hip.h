@@ -275,8 +275,51 @@ int arreau_sample_loop(arreau_model* model, float* d_frac, int32_t* d_types, flo
                        uint64_t seed, const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice,
                        void* d_workspace, size_t workspace_bytes, int32_t use_graph, void* stream);
 
+/* ---- conditioned sampling (structure completion) ---------------------------------------------------------------
+ * Known atoms, species and cells held to a template while the rest is generated: RePaint-style replacement (Lugmayr et
+ * al., CVPR 2022) without resampling jumps.  Every pointer is a DEVICE pointer and may be NULL; masks hold one byte per
+ * atom / crystal, nonzero = known; a mask needs its values, values without a mask are ignored.
+ *   x0[N,3], pos_mask[N]: known fractional coordinates;  a0[N], type_mask[N]: known class indices (z-table indices);
+ *   l0[B,3], len_mask[B]: known cell lengths.
+ * The state at time tau is (frac, types, lengths); the update of the step that leaves timestep t produces tau = t - 1.
+ *   1. positions: after the VE reverse update, frac = remainder(x0 + ve_sigmas[tau] * z, 1),
+ *      z = Philox normal (seed, t, kind 3, element 3 i + d); at tau = 0 exactly remainder(x0, 1).  This is VE_pbc.forward
+ *      at tau (diffusion/diffusion_helpers.py:43-47).
+ *   2. lengths: after VP_lattice.reverse_given_x0, l = sqrt(abar[tau]) l0 + sqrt(1 - abar[tau]) z,
+ *      z = Philox normal (seed, t, kind 4, element 3 b + d); at tau = 0 exactly l0.  This is VP_lattice.forward
+ *      (diffusion_helpers.py:156-163).  The replacement comes before the cell (and the next step's set-up) is formed.
+ *   3. angles: the caller writes the template's angles (radians, matrix_to_params of the template cell,
+ *      lattice_helpers.py:16-35) into d_angles for the known cells; the others keep the host-drawn monoclinic angles.
+ *   4. species: the known class is re-imposed after every D3PM update (per atom, like d_const_types, which it overrides).
+ *   5. initial state: arreau_condition_initial_state overwrites the known components of a drawn initial state at
+ *      tau = t_start by rules 1, 2 and 4 with Philox timestep key t_start + 1.
+ * Kinds 3 and 4 are draws of their own: every unknown atom or crystal draws exactly what it draws without a condition.
+ * The reference's constant_atoms (diffusion/diffusion_loss.py:289, 311-312, 345-346) is the case "every species known". */
+typedef struct arreau_sample_condition {
+    const float* x0;
+    const uint8_t* pos_mask;
+    const int32_t* a0;
+    const uint8_t* type_mask;
+    const float* l0;
+    const uint8_t* len_mask;
+} arreau_sample_condition;
+
+/* arreau_sample_loop with a condition (rules above; `cond` is a host pointer to the struct, NULL = unconditioned).  The
+ * condition's device pointers are part of what a cached hipGraph was captured for: another condition is captured anew. */
+int arreau_sample_loop_conditioned(arreau_model* model, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                                   const int32_t* d_crystal_offsets, int32_t B, int32_t N, int32_t t_start, int32_t n_steps,
+                                   uint64_t seed, const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice,
+                                   void* d_workspace, size_t workspace_bytes, int32_t use_graph,
+                                   const arreau_sample_condition* cond, void* stream);
+
+/* Rule 5: the known components of an initial state drawn for timestep t_start (in place, d_frac[N,3], d_types[N],
+ * d_lengths[B,3]), before the first arreau_sample_loop_conditioned call of the run. */
+int arreau_condition_initial_state(const arreau_model* model, float* d_frac, int32_t* d_types, float* d_lengths, int32_t B,
+                                   int32_t N, int32_t t_start, uint64_t seed, const arreau_sample_condition* cond,
+                                   void* stream);
+
 /* The sampler's in-kernel noise written out: d_out[i] = draw (seed, timestep, kind, element i) -- standard normal for
- * kind 0 (z_lattice) and 1 (z_frac), uniform [0,1) for kind 2 (u_types); d_raw[4 i .. 4 i + 3] (may be NULL) = the raw
+ * kind 0 (z_lattice), 1 (z_frac), 3 (known positions) and 4 (known lengths), uniform [0,1) for kind 2 (u_types); d_raw[4 i .. 4 i + 3] (may be NULL) = the raw
  * Philox4x32-10 words of counter (i, timestep, kind, 0), key = seed.  Feeding these arrays to arreau_reverse_step
  * reproduces arreau_sample_loop's update bit for bit. */
 int arreau_philox_fill(uint64_t seed, int32_t timestep, int32_t kind, int64_t n, float* d_out, uint32_t* d_raw,
