@@ -25,6 +25,7 @@ EXPORTS = [
     "arreau_model_train_weight_pointers", "arreau_model_refresh_derived_train_weights",
     "arreau_model_set_formats", "arreau_debug_set_pollution", "arreau_debug_leftover_fraction",
     "arreau_sample_loop_conditioned", "arreau_condition_initial_state",
+    "arreau_sample_loop_scheduled", "arreau_reverse_step_to",
 ]
 
 STATUS_NONFINITE, STATUS_BAD_TIMESTEP, STATUS_BAD_TYPE = 1, 2, 4
@@ -51,6 +52,11 @@ class SampleConditionC(Structure):
     """arreau_sample_condition (include/arreau_hip.h): device pointers, each may be NULL."""
     _fields_ = [("x0", c_void_p), ("pos_mask", c_void_p), ("a0", c_void_p), ("type_mask", c_void_p), ("l0", c_void_p),
                 ("len_mask", c_void_p)]
+
+
+class SampleScheduleC(Structure):
+    """arreau_sample_schedule: the device next-timestep table [T+1] of a respaced loop and VP_lattice's clipmax."""
+    _fields_ = [("d_next", c_void_p), ("lattice_clipmax", ctypes.c_float)]
 
 
 class Config(Structure):
@@ -122,6 +128,10 @@ def lib():
         L.arreau_sample_loop_conditioned.argtypes = (L.arreau_sample_loop.argtypes[:-1] + [POINTER(SampleConditionC), c_void_p])
         L.arreau_condition_initial_state.argtypes = ([c_void_p] * 4 + [c_int32, c_int32, c_int32, ctypes.c_uint64] +
                                                      [POINTER(SampleConditionC), c_void_p])
+    if hasattr(L, "arreau_sample_loop_scheduled") or not os.environ.get("ARREAU_HIP_LIB"):  # (an older build under test)
+        L.arreau_sample_loop_scheduled.argtypes = (L.arreau_sample_loop_conditioned.argtypes[:-1] +
+                                                   [POINTER(SampleScheduleC), c_void_p])
+        L.arreau_reverse_step_to.argtypes = [c_void_p] * 8 + [c_int32, c_int32] + [c_void_p] * 7 + [ctypes.c_float, c_void_p]
     L.arreau_philox_fill.argtypes = [ctypes.c_uint64, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_void_p]
     L.arreau_train_forward.argtypes = [c_void_p] * 7 + [c_int32, c_int32] + [c_void_p] * 4
     L.arreau_train_backward.argtypes = [c_void_p] * 4 + [POINTER(StateDict), c_void_p]

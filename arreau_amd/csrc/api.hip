@@ -299,20 +299,21 @@ bool loop_without_prep(const arreau_model* m) {
 int enqueue_sample_step(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
                         const int32_t* d_off, int B, int N, uint64_t seed, const int32_t* d_const_types,
                         const float* d_fixed_lengths, float* d_lattice, const Workspace& w, hipStream_t s, bool no_prep,
-                        const SampleConditionDev* cond) {
+                        const SampleConditionDev* cond, const StepScheduleDev* sched) {
     int rc;
+    const int32_t* next_t = sched ? sched->next : nullptr;  // respaced loop: the device timestep follows the table
     if (no_prep) {
         if ((rc = arreau_launch_neighbor_embed(m, nullptr, w.lattice, d_off, w.batch, B, N, w.deg, w.src, w.cell, w.dir, w.dist, d_frac,
-                                               d_types, w.cvec, w.xa, s, w.t_cur)))
+                                               d_types, w.cvec, w.xa, s, w.t_cur, next_t)))
             return rc;
         if ((rc = run_edge_kernel(m, w.dir, w.dist, w.deg, w, N, s))) return rc;
         if ((rc = run_layers_and_readout(m, w, w.deg, w.src, d_off, B, N, w.eps, w.logits, nullptr, s))) return rc;
         return arreau_launch_reverse(m, d_frac, d_types, d_lengths, d_angles, w.t_cur, d_off, B, N, w.eps, w.logits, w.len0,
                                      StepNoiseSrc{nullptr, nullptr, nullptr, seed}, d_const_types, d_lattice, s, d_fixed_lengths,
-                                     w.gs, w.batch, w.lattice, w.cvec, cond);
+                                     w.gs, w.batch, w.lattice, w.cvec, cond, sched);
     }
     if ((rc = arreau_launch_prep(m, d_frac, d_lengths, d_angles, nullptr, d_off, B, N, w.lattice, w.cart, w.batch, w.cvec, s,
-                                 w.t_next, w.t_cur)))
+                                 w.t_next, w.t_cur, 0, next_t)))
         return rc;
     // fused kernels: the per-crystal pooling of the lattice read-out happens inside the lattice update (no launch of its own)
     const bool pool_in_update = !arreau_general_path(m);
@@ -321,7 +322,7 @@ int enqueue_sample_step(const arreau_model* m, float* d_frac, int32_t* d_types, 
         return rc;
     return arreau_launch_reverse(m, d_frac, d_types, d_lengths, d_angles, w.t_cur, d_off, B, N, w.eps, w.logits, w.len0,
                                  StepNoiseSrc{nullptr, nullptr, nullptr, seed}, d_const_types, d_lattice, s, d_fixed_lengths,
-                                 pool_in_update ? w.gs : nullptr, w.batch, nullptr, nullptr, cond);
+                                 pool_in_update ? w.gs : nullptr, w.batch, nullptr, nullptr, cond, sched);
 }
 }  // namespace
 
@@ -338,11 +339,29 @@ extern "C" int arreau_sample_loop_conditioned(arreau_model* m, float* d_frac, in
                                               int32_t n_steps, uint64_t seed, const int32_t* d_const_types,
                                               const float* d_fixed_lengths, float* d_lattice, void* d_workspace, size_t workspace_bytes,
                                               int32_t use_graph, const arreau_sample_condition* condition, void* stream) {
+    return arreau_sample_loop_scheduled(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, t_start, n_steps, seed, d_const_types,
+                                        d_fixed_lengths, d_lattice, d_workspace, workspace_bytes, use_graph, condition, nullptr, stream);
+}
+
+extern "C" int arreau_sample_loop_scheduled(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths,
+                                            const float* d_angles, const int32_t* d_off, int32_t B, int32_t N, int32_t t_start,
+                                            int32_t n_steps, uint64_t seed, const int32_t* d_const_types,
+                                            const float* d_fixed_lengths, float* d_lattice, void* d_workspace, size_t workspace_bytes,
+                                            int32_t use_graph, const arreau_sample_condition* condition,
+                                            const arreau_sample_schedule* schedule, void* stream) {
     ARREAU_REQUIRE(m && d_frac && d_types && d_lengths && d_angles && d_off && d_lattice, "arreau_sample_loop: null pointer");
     ARREAU_REQUIRE(B >= 1 && N >= 0 && n_steps >= 0, "arreau_sample_loop: bad size");
     ARREAU_REQUIRE(!m->packed_stale || arreau_general_path(m),
                    "arreau_sample_loop: weights were updated for training only; re-create the model or select the general path");
-    ARREAU_REQUIRE(t_start <= m->T && t_start - n_steps >= 0, "arreau_sample_loop: timesteps t_start .. t_start-n_steps+1 must lie in 1..T");
+    if (schedule) {
+        ARREAU_REQUIRE(schedule->d_next != nullptr, "arreau_sample_loop_scheduled: null next-timestep table");
+        ARREAU_REQUIRE(schedule->lattice_clipmax > 0.0f && schedule->lattice_clipmax <= 1.0f,
+                       "arreau_sample_loop_scheduled: lattice_clipmax must lie in (0, 1]");
+        // the loop starts one above t_start (d_next[t_start + 1] == t_start, include/arreau_hip.h), so t_start + 1 <= T
+        ARREAU_REQUIRE(n_steps == 0 || (t_start >= 1 && t_start <= m->T - 1), "arreau_sample_loop_scheduled: t_start must lie in 1..T-1");
+    } else {
+        ARREAU_REQUIRE(t_start <= m->T && t_start - n_steps >= 0, "arreau_sample_loop: timesteps t_start .. t_start-n_steps+1 must lie in 1..T");
+    }
     ARREAU_REQUIRE(d_workspace != nullptr, "arreau_sample_loop: null workspace");
     Workspace w = carve(&m->cfg, N, B, d_workspace, workspace_bytes);
     if (w.bytes > workspace_bytes) {
@@ -353,11 +372,14 @@ extern "C" int arreau_sample_loop_conditioned(arreau_model* m, float* d_frac, in
     int rc;
     if ((rc = arreau_condition_to_dev(condition, &cond_dev))) return rc;
     const SampleConditionDev* cond = arreau_condition_empty(&cond_dev) ? nullptr : &cond_dev;  // empty: the unconditioned loop
+    const StepScheduleDev sched_dev{schedule ? schedule->d_next : nullptr, nullptr, schedule ? schedule->lattice_clipmax : 0.0f};
+    const StepScheduleDev* sched = schedule ? &sched_dev : nullptr;  // null: every timestep, t_start down
     if (n_steps == 0) return ARREAU_OK;
     hipStream_t s = (hipStream_t)stream;
     const bool no_prep = loop_without_prep(m);
     if (no_prep) {
-        // t_cur holds the timestep of the step in progress; every step's first launch advances it, so it starts one above
+        // t_cur holds the timestep of the step in progress; every step's first launch advances it, so it starts one above (in a
+        // respaced loop at the table entry t_start + 1, whose successor is t_start)
         ARREAU_LAUNCH(fill_i32_kernel, dim3((B + 255) / 256), dim3(256), 0, s, w.t_cur, t_start + 1, B);
         ARREAU_CHECK_HIP(hipGetLastError());
         if ((rc = arreau_launch_prep(m, d_frac, d_lengths, d_angles, w.t_cur, d_off, B, N, w.lattice, w.cart, w.batch, w.cvec, s, nullptr,
@@ -369,7 +391,7 @@ extern "C" int arreau_sample_loop_conditioned(arreau_model* m, float* d_frac, in
     }
     if (!use_graph || n_steps < 3) {
         for (int i = 0; i < n_steps; ++i)
-            if ((rc = enqueue_sample_step(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types, d_fixed_lengths, d_lattice, w, s, no_prep, cond)))
+            if ((rc = enqueue_sample_step(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types, d_fixed_lengths, d_lattice, w, s, no_prep, cond, sched)))
                 return rc;
         return ARREAU_OK;
     }
@@ -393,8 +415,10 @@ extern "C" int arreau_sample_loop_conditioned(arreau_model* m, float* d_frac, in
     // The executable graph is kept with the model and reused while the next call names the same buffers, sizes and seed
     // (a sampler drawing sub-batch after sub-batch through the caching allocator does): capture + instantiation, about
     // 2 ms, are then paid once.  The timestep is not part of the graph (it lives in t_next / t_cur, set above).  The condition's
-    // pointers are kernel arguments of the capture: another condition is another graph.
-    const uint64_t key[18] = {(uint64_t)d_frac, (uint64_t)d_types, (uint64_t)d_lengths, (uint64_t)d_angles, (uint64_t)d_off,
+    // pointers are kernel arguments of the capture: another condition is another graph; so are the schedule's table and clip.
+    uint32_t clip_bits = 0;
+    memcpy(&clip_bits, &sched_dev.clipmax, sizeof(clip_bits));
+    const uint64_t key[20] = {(uint64_t)d_frac, (uint64_t)d_types, (uint64_t)d_lengths, (uint64_t)d_angles, (uint64_t)d_off,
                               ((uint64_t)(uint32_t)B << 32) | (uint32_t)N, seed, (uint64_t)d_const_types, (uint64_t)d_fixed_lengths,
                               (uint64_t)d_lattice, (uint64_t)d_workspace,
                               ((uint64_t)(uint32_t)(m->edge_variant | (no_prep ? 0x10000 : 0) |
@@ -405,19 +429,20 @@ extern "C" int arreau_sample_loop_conditioned(arreau_model* m, float* d_frac, in
                                                     (arreau_small_layer_fusable(m, N) ? 0x80000 : 0) |
                                                     ((m->conv_variant & 3) << 20)) << 32) | (uint32_t)m->mlp_variant,
                               (uint64_t)cond_dev.x0, (uint64_t)cond_dev.pos_mask, (uint64_t)cond_dev.a0, (uint64_t)cond_dev.type_mask,
-                              (uint64_t)cond_dev.l0, (uint64_t)cond_dev.len_mask};
+                              (uint64_t)cond_dev.l0, (uint64_t)cond_dev.len_mask, (uint64_t)sched_dev.next,
+                              ((uint64_t)(schedule ? 1 : 0) << 32) | clip_bits};
     hipGraphExec_t exec = (hipGraphExec_t)m->retired_graph;
     int first_replay = 0;
     hipError_t e = hipSuccess;
     static_assert(sizeof(key) == sizeof(m->graph_key), "graph key size");
     if (!exec || memcmp(key, m->graph_key, sizeof(key)) != 0) {
         // The first step runs eagerly (it also forces lazy module loading, which must not happen inside a capture).
-        if ((rc = enqueue_sample_step(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types, d_fixed_lengths, d_lattice, w, s, no_prep, cond)))
+        if ((rc = enqueue_sample_step(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types, d_fixed_lengths, d_lattice, w, s, no_prep, cond, sched)))
             return rc;
         first_replay = 1;
         hipGraph_t graph = nullptr;
         ARREAU_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        rc = enqueue_sample_step(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types, d_fixed_lengths, d_lattice, w, s, no_prep, cond);
+        rc = enqueue_sample_step(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types, d_fixed_lengths, d_lattice, w, s, no_prep, cond, sched);
         e = hipStreamEndCapture(s, &graph);
         if (rc) {
             if (graph) (void)hipGraphDestroy(graph);

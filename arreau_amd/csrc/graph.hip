@@ -91,17 +91,28 @@ __global__ __launch_bounds__(256) void neighbor_kernel(
 // LOOP (sampling loop, round 3): no prep launch in the step.  `cart` holds the fractional coordinates (positions are formed by
 // the waves that need them, with prep_kernel's expression); the lattice and the per-crystal embedding were left by the
 // previous step's update launch (reverse_crystal_block) or by the one prep launch in front of the loop; and the first
-// workgroups advance the device-side timestep of every crystal by one (`tick`: read only by the update launch).
+// workgroups advance the device-side timestep of every crystal (`tick`: read only by the update launch) by one, or in a
+// respaced loop to its successor in the device-side next-timestep table (`next_t`, [T+1]).  Like the prep path, the loop's
+// first launch starts one above the first timestep (an entry of the table whose successor is that timestep).
 template <bool LOOP = false>
 __global__ __launch_bounds__(256) void neighbor_embed_kernel(
     unsigned embed_blocks, const float* __restrict__ cart, const float* __restrict__ lattice, const int32_t* __restrict__ offsets,
     const int32_t* __restrict__ batch, int B, int n0, int N, float r2, int k, int32_t* __restrict__ deg, int32_t* __restrict__ src,
     int32_t* __restrict__ cell, float* __restrict__ dir, float* __restrict__ dist, const float* __restrict__ frac,
     const int32_t* __restrict__ types, const float* __restrict__ cvec, const float* __restrict__ ori, const float* __restrict__ embT,
-    int S, int C, float* __restrict__ x0, int32_t* __restrict__ status, int32_t* __restrict__ tick, int tick_b0, int tick_b1) {
+    int S, int C, float* __restrict__ x0, int32_t* __restrict__ status, int32_t* __restrict__ tick, int tick_b0, int tick_b1,
+    const int32_t* __restrict__ next_t, int T) {
     if constexpr (LOOP) {
         const int b = tick_b0 + (int)(blockIdx.x * blockDim.x + threadIdx.x);
-        if (b < tick_b1) tick[b] -= 1;  // (nobody else reads or writes it in this launch)
+        if (b < tick_b1) {  // (nobody else reads or writes it in this launch)
+            if (next_t != nullptr) {  // (kernel argument: uniform)
+                const int t = tick[b];
+                if (t < 0 || t > T) atomicOr(status, ARREAU_STATUS_BAD_TIMESTEP);  // clamped, but flagged
+                tick[b] = next_t[t < 0 ? 0 : (t > T ? T : t)];
+            } else {
+                tick[b] -= 1;
+            }
+        }
     }
     if (blockIdx.x < embed_blocks) {
         arreau_embed_body(blockIdx.x * blockDim.x + threadIdx.x, frac, types, lattice, batch, cvec, ori, embT, S, C, n0, N, x0, status);
@@ -125,7 +136,7 @@ int arreau_launch_neighbor(const float* cart, const float* lattice, const int32_
 int arreau_launch_neighbor_embed(const arreau_model* m, const float* cart, const float* lattice, const int32_t* offsets,
                                  const int32_t* batch, int B, int N, int32_t* deg, int32_t* src, int32_t* cell, float* dir,
                                  float* dist, const float* frac, const int32_t* types, const float* cvec, float* x0, hipStream_t s,
-                                 int32_t* tick) {
+                                 int32_t* tick, const int32_t* next_t) {
     if (N <= 0 && tick == nullptr) return ARREAU_OK;
     ARREAU_REQUIRE(batch != nullptr, "neighbour list + embedding: the atom -> crystal map is required");
     const float r2 = (float)((double)m->cfg.radius * (double)m->cfg.radius);
@@ -140,11 +151,11 @@ int arreau_launch_neighbor_embed(const arreau_model* m, const float* cart, const
         const unsigned tick_blocks = (unsigned)((B + 255) / 256);
         const unsigned grid = embed_blocks + nbr_blocks > tick_blocks ? embed_blocks + nbr_blocks : tick_blocks;  // (extra workgroups only tick)
         ARREAU_LAUNCH(neighbor_embed_kernel<true>, dim3(grid), dim3(256), 0, s, embed_blocks, frac, lattice, offsets, batch, B, 0, N, r2,
-                      m->k, deg, src, cell, dir, dist, frac, types, cvec, m->ori, m->embT, m->S, m->C, x0, m->status, tick, 0, B);
+                      m->k, deg, src, cell, dir, dist, frac, types, cvec, m->ori, m->embT, m->S, m->C, x0, m->status, tick, 0, B, next_t, m->T);
     } else {
         ARREAU_LAUNCH(neighbor_embed_kernel<false>, dim3(embed_blocks + nbr_blocks), dim3(256), 0, s, embed_blocks, cart, lattice, offsets,
                       batch, B, 0, N, r2, m->k, deg, src, cell, dir, dist, frac, types, cvec, m->ori, m->embT, m->S, m->C, x0, m->status,
-                      (int32_t*)nullptr, 0, 0);
+                      (int32_t*)nullptr, 0, 0, (const int32_t*)nullptr, m->T);
     }
     ARREAU_CHECK_HIP(hipGetLastError());
     return ARREAU_OK;

@@ -71,7 +71,7 @@ struct arreau_model {
     int packed_stale;        // 1 after arreau_model_update_train_weights: the sampling kernels' packed planes are out of date
     void* loop_stream;       // hipStream_t / hipEvent_t of arreau_sample_loop's graph mode (capture is not allowed on the
     void* loop_event;        //   legacy default stream callers usually pass); created on first use
-    uint64_t graph_key[18];  // what the cached executable graph of arreau_sample_loop was captured for
+    uint64_t graph_key[20];  // what the cached executable graph of arreau_sample_loop was captured for
     void* retired_graph;     // hipGraphExec_t of the last arreau_sample_loop (+ the stream it was launched on): destroyed,
     void* retired_stream;    //   after that stream has drained, by the next loop or by arreau_model_destroy
     int32_t* status;         // device word of sticky ARREAU_STATUS_* bits (written by the kernels with atomicOr)
@@ -225,6 +225,16 @@ inline bool arreau_condition_empty(const SampleConditionDev* c) {
 }
 int arreau_condition_to_dev(const arreau_sample_condition* c, SampleConditionDev* out);  // update.hip
 
+// Respaced sampling (arreau_sample_loop_scheduled, arreau_reverse_step_to; the rules are stated in include/arreau_hip.h): the step
+// that leaves timestep t of crystal b produces the state at s = s_of[b] when s_of is given, else s = next[t] (the device-side
+// next-timestep table [T+1] of the loop).  Kernels take it by value and hand their helpers a pointer to it, or null when the
+// launch has no schedule (then s = t - 1 and the helpers compile to the schedule-less code).
+struct StepScheduleDev {
+    const int32_t* next;  // [T+1] or null
+    const int32_t* s_of;  // [B]   or null
+    float clipmax;        // the VP schedule's beta clip (VP_lattice clipmax)
+};
+
 void arreau_train_ctx_destroy(struct arreau_train_ctx* t);
 // edge_variant value that selects the shape-general fp32 network (train_net.hip) for the whole evaluation
 #define ARREAU_VARIANT_GENERAL 5
@@ -278,11 +288,12 @@ int arreau_launch_neighbor(const float* cart, const float* lattice, const int32_
 int arreau_launch_neighbor_embed(const arreau_model* m, const float* cart, const float* lattice, const int32_t* offsets,
                                  const int32_t* batch, int B, int N, int32_t* deg, int32_t* src, int32_t* cell, float* dir,
                                  float* dist, const float* frac, const int32_t* types, const float* cvec, float* x0, hipStream_t s,
-                                 int32_t* tick = nullptr /* sampling loop without a prep launch: see the kernel */);
+                                 int32_t* tick = nullptr /* sampling loop without a prep launch: see the kernel */,
+                                 const int32_t* next_t = nullptr /* respaced loop: tick[b] = next_t[tick[b]] */);
 int arreau_launch_prep(const arreau_model* m, const float* frac, const float* lengths, const float* angles,
                        const int32_t* t, const int32_t* offsets, int B, int N, float* lattice, float* cart,
                        int32_t* batch, float* cvec, hipStream_t s, int32_t* t_next = nullptr, int32_t* t_cur = nullptr,
-                       int t_offset = 0);
+                       int t_offset = 0, const int32_t* next_t = nullptr /* respaced loop: t_next[b] = next_t[t] */);
 int arreau_launch_reverse(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
                           const int32_t* d_t, const int32_t* d_off, int B, int N, const float* d_eps,
                           const float* d_logits, const float* d_len0, StepNoiseSrc noise, const int32_t* d_const_types,
@@ -291,7 +302,8 @@ int arreau_launch_reverse(const arreau_model* m, float* d_frac, int32_t* d_types
                           const int32_t* d_batch = nullptr /* crystal index of each atom, if the caller has it */,
                           float* d_lattice_ws = nullptr, float* d_cvec_next = nullptr /* sampling loop: also prepare the next step
                           (workspace lattice + per-crystal embedding for timestep t - 1), see reverse_crystal_block */,
-                          const SampleConditionDev* cond = nullptr /* conditioned sampling; needs Philox noise (noise.seed) */);
+                          const SampleConditionDev* cond = nullptr /* conditioned sampling; needs Philox noise (noise.seed) */,
+                          const StepScheduleDev* sched = nullptr /* respaced step (s from a table or per crystal), null: s = t - 1 */);
 int arreau_launch_edge(const arreau_model* m, const float* dir, const float* dist, const int32_t* deg,
                        const int32_t* batch, const float* lattice, int N, float* kbuf, hipStream_t s);
 int arreau_launch_edge_bf16x6(const arreau_model* m, const float* dir, const float* dist, const int32_t* deg,

@@ -23,18 +23,25 @@ __global__ __launch_bounds__(128) void prep_kernel(
     const float* __restrict__ t_emb_w, const float* __restrict__ embT, int S, int C, int T,
     float* __restrict__ lattice, float* __restrict__ cart, int32_t* __restrict__ batch, float* __restrict__ cvec,
     int32_t* __restrict__ status, int32_t* __restrict__ t_next, int32_t* __restrict__ t_cur, int b0,
-    int t_offset /* added to the timestep read (the sampling loop's first set-up: -1, see arreau_sample_loop) */) {
+    int t_offset /* added to the timestep read (the sampling loop's first set-up: -1, see arreau_sample_loop) */,
+    const int32_t* __restrict__ next_t /* respaced loop: the next-timestep table [T+1], or null: t - 1 */) {
     __shared__ float feat[ARREAU_T_EMB_DIM + ARREAU_N_CRYSTAL_FEATS];
     // Sampling loop on device time (arreau_sample_loop): this workgroup is the only reader of its crystal's entry of
     // t_next in this launch; it publishes the timestep of the step in t_cur (read by the later kernels of the step) and
-    // leaves the next one behind, so a captured step can be replayed without host-side bookkeeping.
+    // leaves the next one behind (t - 1, or the schedule's successor next_t[t]), so a captured step can be replayed without
+    // host-side bookkeeping.
     __shared__ int t_sh;
     const int b = b0 + blockIdx.x;
     if (threadIdx.x == 0) {
         if (t_next != nullptr) {
             t_sh = t_next[b];
             t_cur[b] = t_sh;
-            t_next[b] = t_sh - 1;
+            if (next_t != nullptr) {
+                if (t_sh < 0 || t_sh > T) atomicOr(status, ARREAU_STATUS_BAD_TIMESTEP);  // clamped, but flagged
+                t_next[b] = next_t[t_sh < 0 ? 0 : (t_sh > T ? T : t_sh)];
+            } else {
+                t_next[b] = t_sh - 1;
+            }
         } else {
             t_sh = tstep[b];
         }
@@ -61,10 +68,11 @@ __global__ __launch_bounds__(128) void prep_kernel(
 
 int arreau_launch_prep(const arreau_model* m, const float* frac, const float* lengths, const float* angles,
                        const int32_t* t, const int32_t* offsets, int B, int N, float* lattice, float* cart,
-                       int32_t* batch, float* cvec, hipStream_t s, int32_t* t_next, int32_t* t_cur, int t_offset) {
+                       int32_t* batch, float* cvec, hipStream_t s, int32_t* t_next, int32_t* t_cur, int t_offset,
+                       const int32_t* next_t) {
     if (B <= 0) return ARREAU_OK;
     ARREAU_LAUNCH(prep_kernel, dim3(B), dim3(128), 0, s, frac, lengths, angles, t, offsets, m->vp_betas,
-                       m->t_emb_w, m->embT, m->S, m->C, m->T, lattice, cart, batch, cvec, m->status, t_next, t_cur, 0, t_offset);
+                       m->t_emb_w, m->embT, m->S, m->C, m->T, lattice, cart, batch, cvec, m->status, t_next, t_cur, 0, t_offset, next_t);
     ARREAU_CHECK_HIP(hipGetLastError());
     return ARREAU_OK;
 }

@@ -12,7 +12,8 @@ __device__ __forceinline__ void reverse_lattice_body(int gt /* global thread of 
                                        int32_t* __restrict__ status, int b0,
                                        // sampling loop: pool the per-atom read-out here (same ordered sum as
                                        // readout_crystals_kernel) instead of a launch of its own; len0_out receives it
-                                       const float* __restrict__ gs_atoms, float* __restrict__ len0_out, const SampleConditionDev* cond) {
+                                       const float* __restrict__ gs_atoms, float* __restrict__ len0_out, const SampleConditionDev* cond,
+                                       const StepScheduleDev* sched) {
     // four lanes per crystal: lane i < 3 owns length component i (pooling, update), lane 0 then writes the cell
     const int b = b0 + (gt >> 2), i = gt & 3;
     const bool live = b < B;  // (whole groups of four are live or not; the shuffles below need every lane)
@@ -20,9 +21,12 @@ __device__ __forceinline__ void reverse_lattice_body(int gt /* global thread of 
     int t = tstep[bc];
     if (live && i == 0 && (t < 1 || t > T)) atomicOr(status, ARREAU_STATUS_BAD_TIMESTEP);  // clamped, but flagged
     t = t < 1 ? 1 : (t > T ? T : t);
+    const int s_to = step_target(sched, bc, t, status, live && i == 0);
     const int first = offsets[bc], last = offsets[bc + 1];
     float mylen = 0.f;
-    if (live && i < 3) mylen = reverse_length_component(b, i, t, first, last, lengths, len0, noise, alpha_bars, betas, fixed_lengths, gs_atoms, len0_out, cond);
+    if (live && i < 3)
+        mylen = reverse_length_component(b, i, t, s_to, sched, first, last, lengths, len0, noise, alpha_bars, betas, fixed_lengths, gs_atoms,
+                                         len0_out, cond);
     const int base = (threadIdx.x & 63) & ~3;
     float newlen[3];
 #pragma unroll
@@ -44,9 +48,10 @@ __device__ __forceinline__ void reverse_lattice_body(int gt /* global thread of 
 // ONE launch for the four updates of a step (round 3; they were two): the first `lat_blocks` workgroups (256 threads = 64
 // crystals, four lanes each) run the lattice update, the others the atom update, one wave per atom.  The two parts touch
 // disjoint data (lengths / lattice / pooled read-out against coordinates / types), so nothing orders them.
-// COND: conditioned sampling (the last argument is read); reverse_kernel<false> is the unconditioned kernel, whose helpers
-// see a null condition and compile to what they were before conditioning existed.
-template <bool COND>
+// COND: conditioned sampling (the condition argument is read); SCHED: a respaced step (the schedule argument is read: s from a
+// per-crystal array or the loop's next-timestep table).  reverse_kernel<false, false> is the plain kernel, whose helpers see a
+// null condition and a null schedule and compile to what they were before either existed.
+template <bool COND, bool SCHED>
 __global__ __launch_bounds__(256) void reverse_kernel(
     int lat_blocks, float* __restrict__ lengths, const float* __restrict__ angles, const int32_t* __restrict__ tstep,
     const int32_t* __restrict__ offsets, const float* __restrict__ len0, StepNoiseSrc noise, const float* __restrict__ alpha_bars,
@@ -58,27 +63,46 @@ __global__ __launch_bounds__(256) void reverse_kernel(
     const int32_t* __restrict__ batch,
     // sampling loop: the lattice part is one workgroup per crystal, which also prepares the next step (reverse_crystal_block)
     float* __restrict__ lattice_ws, float* __restrict__ cvec_next, const float* __restrict__ t_emb_w, const float* __restrict__ embT, int C,
-    SampleConditionDev cond_arg) {
+    SampleConditionDev cond_arg, StepScheduleDev sched_arg) {
     const SampleConditionDev* cond = COND ? &cond_arg : nullptr;
+    const StepScheduleDev* sched = SCHED ? &sched_arg : nullptr;
     if ((int)blockIdx.x < lat_blocks && cvec_next != nullptr) {  // (kernel argument: uniform)
         reverse_crystal_block(b0 + (int)blockIdx.x, lengths, angles, tstep, offsets, len0, noise, alpha_bars, betas, T, lattice, fixed_lengths,
-                              status, gs_atoms, len0_out, lattice_ws, cvec_next, t_emb_w, embT, S, C, cond);
+                              status, gs_atoms, len0_out, lattice_ws, cvec_next, t_emb_w, embT, S, C, cond, sched);
         return;
     }
     if ((int)blockIdx.x < lat_blocks) {
         reverse_lattice_body(blockIdx.x * blockDim.x + threadIdx.x, lengths, angles, tstep, offsets, len0, noise, alpha_bars, betas, B_lat, T,
-                             lattice, fixed_lengths, status, b0, gs_atoms, len0_out, cond);
+                             lattice, fixed_lengths, status, b0, gs_atoms, len0_out, cond, sched);
         return;
     }
     reverse_atoms_body((int)blockIdx.x - lat_blocks, frac, types, tstep, offsets, B, N, eps, logits, noise, ve_sigmas, q1t, qmats, S, T,
-                       const_types, absorbing, status, n0, batch, cond);
+                       const_types, absorbing, status, n0, batch, cond, sched);
 }
+
+namespace {
+template <bool COND, bool SCHED>
+void enqueue_reverse_kernel(const arreau_model* m, int lat_blocks, int atom_blocks, float* d_frac, int32_t* d_types, float* d_lengths,
+                            const float* d_angles, const int32_t* d_t, const int32_t* d_off, int B, int N, const float* d_eps,
+                            const float* d_logits, const float* d_len0, StepNoiseSrc noise, const int32_t* d_const_types,
+                            float* d_lattice, hipStream_t s, const float* d_fixed_lengths, const float* d_gs_atoms,
+                            const int32_t* d_batch, float* d_lattice_ws, float* d_cvec_next, const SampleConditionDev& cond,
+                            const StepScheduleDev& sched) {
+    auto kernel = reverse_kernel<COND, SCHED>;
+    ARREAU_LAUNCH(kernel, dim3(lat_blocks + atom_blocks), dim3(256), 0, s, lat_blocks, d_lengths, d_angles, d_t, d_off, d_len0,
+                  noise, m->vp_alpha_bars, m->vp_betas, B, m->T, d_lattice, d_fixed_lengths, m->status, 0, d_gs_atoms,
+                  d_gs_atoms ? const_cast<float*>(d_len0) : nullptr, d_frac, d_types, B, N, d_eps, d_logits, m->ve_sigmas, m->q1t,
+                  m->qmats, m->S, d_const_types, m->qmats_absorbing, 0, d_batch, d_lattice_ws, d_cvec_next, m->t_emb_w, m->embT, m->C,
+                  cond, sched);
+}
+}  // namespace
 
 int arreau_launch_reverse(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
                           const int32_t* d_t, const int32_t* d_off, int B, int N, const float* d_eps,
                           const float* d_logits, const float* d_len0, StepNoiseSrc noise, const int32_t* d_const_types,
                           float* d_lattice, hipStream_t s, const float* d_fixed_lengths, const float* d_gs_atoms,
-                          const int32_t* d_batch, float* d_lattice_ws, float* d_cvec_next, const SampleConditionDev* cond) {
+                          const int32_t* d_batch, float* d_lattice_ws, float* d_cvec_next, const SampleConditionDev* cond,
+                          const StepScheduleDev* sched) {
     const bool prep_next = d_cvec_next != nullptr;  // one workgroup per crystal, which also prepares the next step
     ARREAU_REQUIRE(!prep_next || d_lattice_ws != nullptr, "reverse update: the next step's set-up needs the workspace lattice");
     const int lat_blocks = B > 0 ? (prep_next ? B : (4 * B + 255) / 256) : 0;
@@ -86,21 +110,20 @@ int arreau_launch_reverse(const arreau_model* m, float* d_frac, int32_t* d_types
     const bool conditioned = !arreau_condition_empty(cond);
     ARREAU_REQUIRE(!conditioned || (!noise.z_lattice && !noise.z_frac && !noise.u_types),
                    "reverse update: conditioned sampling needs the in-kernel (Philox) noise");
-    if (lat_blocks + atom_blocks > 0 && conditioned) {
-        ARREAU_LAUNCH(reverse_kernel<true>, dim3(lat_blocks + atom_blocks), dim3(256), 0, s, lat_blocks, d_lengths, d_angles, d_t, d_off, d_len0,
-                      noise, m->vp_alpha_bars, m->vp_betas, B, m->T, d_lattice, d_fixed_lengths, m->status, 0, d_gs_atoms,
-                      d_gs_atoms ? const_cast<float*>(d_len0) : nullptr, d_frac, d_types, B, N, d_eps, d_logits, m->ve_sigmas, m->q1t,
-                      m->qmats, m->S, d_const_types, m->qmats_absorbing, 0, d_batch, d_lattice_ws, d_cvec_next, m->t_emb_w, m->embT, m->C,
-                      *cond);
-        ARREAU_CHECK_HIP(hipGetLastError());
-    } else if (lat_blocks + atom_blocks > 0) {
-        ARREAU_LAUNCH(reverse_kernel<false>, dim3(lat_blocks + atom_blocks), dim3(256), 0, s, lat_blocks, d_lengths, d_angles, d_t, d_off, d_len0,
-                      noise, m->vp_alpha_bars, m->vp_betas, B, m->T, d_lattice, d_fixed_lengths, m->status, 0, d_gs_atoms,
-                      d_gs_atoms ? const_cast<float*>(d_len0) : nullptr, d_frac, d_types, B, N, d_eps, d_logits, m->ve_sigmas, m->q1t,
-                      m->qmats, m->S, d_const_types, m->qmats_absorbing, 0, d_batch, d_lattice_ws, d_cvec_next, m->t_emb_w, m->embT, m->C,
-                      SampleConditionDev{});
-        ARREAU_CHECK_HIP(hipGetLastError());
-    }
+    const bool scheduled = sched != nullptr;
+    ARREAU_REQUIRE(!scheduled || (sched->next != nullptr) != (sched->s_of != nullptr),
+                   "reverse update: a respaced step takes either the next-timestep table or the per-crystal targets");
+    if (lat_blocks + atom_blocks == 0) return ARREAU_OK;
+    const SampleConditionDev c = conditioned ? *cond : SampleConditionDev{};
+    const StepScheduleDev sc = scheduled ? *sched : StepScheduleDev{};
+#define ARREAU_REVERSE_ARGS m, lat_blocks, atom_blocks, d_frac, d_types, d_lengths, d_angles, d_t, d_off, B, N, d_eps, d_logits, d_len0, \
+        noise, d_const_types, d_lattice, s, d_fixed_lengths, d_gs_atoms, d_batch, d_lattice_ws, d_cvec_next, c, sc
+    if (conditioned && scheduled) enqueue_reverse_kernel<true, true>(ARREAU_REVERSE_ARGS);
+    else if (conditioned) enqueue_reverse_kernel<true, false>(ARREAU_REVERSE_ARGS);
+    else if (scheduled) enqueue_reverse_kernel<false, true>(ARREAU_REVERSE_ARGS);
+    else enqueue_reverse_kernel<false, false>(ARREAU_REVERSE_ARGS);
+#undef ARREAU_REVERSE_ARGS
+    ARREAU_CHECK_HIP(hipGetLastError());
     return ARREAU_OK;
 }
 
@@ -114,6 +137,22 @@ extern "C" int arreau_reverse_step(const arreau_model* m, float* d_frac, int32_t
     ARREAU_REQUIRE(B >= 1 && N >= 0, "arreau_reverse_step: bad size");
     return arreau_launch_reverse(m, d_frac, d_types, d_lengths, d_angles, d_t, d_off, B, N, d_eps, d_logits, d_len0,
                                  StepNoiseSrc{d_z_lattice, d_z_frac, d_u_types, 0}, nullptr, d_lattice, (hipStream_t)stream);
+}
+
+// arreau_reverse_step from timestep t to a per-crystal target s (respaced sampling; rules in include/arreau_hip.h).
+extern "C" int arreau_reverse_step_to(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths,
+                                      const float* d_angles, const int32_t* d_t, const int32_t* d_s, const int32_t* d_off, int32_t B,
+                                      int32_t N, const float* d_eps, const float* d_logits, const float* d_len0,
+                                      const float* d_z_lattice, const float* d_z_frac, const float* d_u_types, float* d_lattice,
+                                      float lattice_clipmax, void* stream) {
+    ARREAU_REQUIRE(m && d_frac && d_types && d_lengths && d_angles && d_t && d_s && d_off && d_eps && d_logits && d_len0 &&
+                       d_z_lattice && d_z_frac && d_u_types && d_lattice, "arreau_reverse_step_to: null pointer");
+    ARREAU_REQUIRE(B >= 1 && N >= 0, "arreau_reverse_step_to: bad size");
+    ARREAU_REQUIRE(lattice_clipmax > 0.0f && lattice_clipmax <= 1.0f, "arreau_reverse_step_to: lattice_clipmax must lie in (0, 1]");
+    const StepScheduleDev sched{nullptr, d_s, lattice_clipmax};
+    return arreau_launch_reverse(m, d_frac, d_types, d_lengths, d_angles, d_t, d_off, B, N, d_eps, d_logits, d_len0,
+                                 StepNoiseSrc{d_z_lattice, d_z_frac, d_u_types, 0}, nullptr, d_lattice, (hipStream_t)stream, nullptr,
+                                 nullptr, nullptr, nullptr, nullptr, nullptr, &sched);
 }
 
 // The sampler's in-kernel noise, written out: out[i] = the draw (seed, timestep, kind, element i) -- standard normal for
@@ -149,10 +188,10 @@ __global__ void condition_initial_state_kernel(float* __restrict__ frac, int32_t
                                                const float* __restrict__ ve_sigmas, const float* __restrict__ alpha_bars) {
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g < 3 * (int64_t)N) {
-        if (cond.pos_mask && cond.pos_mask[g / 3]) frac[g] = known_frac_component(&cond, (size_t)g, t_key, seed, ve_sigmas);
+        if (cond.pos_mask && cond.pos_mask[g / 3]) frac[g] = known_frac_component(&cond, (size_t)g, t_key, t_key - 1, seed, ve_sigmas);
     } else if (g < 3 * (int64_t)N + 3 * (int64_t)B) {
         const int c = (int)(g - 3 * (int64_t)N), b = c / 3;
-        if (cond.len_mask && cond.len_mask[b]) lengths[c] = known_length_component(&cond, b, c - 3 * b, t_key, seed, alpha_bars);
+        if (cond.len_mask && cond.len_mask[b]) lengths[c] = known_length_component(&cond, b, c - 3 * b, t_key, t_key - 1, seed, alpha_bars);
     } else if (g < 4 * (int64_t)N + 3 * (int64_t)B) {
         const int i = (int)(g - 3 * (int64_t)N - 3 * (int64_t)B);
         if (cond.type_mask && cond.type_mask[i]) types[i] = cond.a0[i];

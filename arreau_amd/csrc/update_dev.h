@@ -15,37 +15,55 @@ __device__ __forceinline__ float remainder_one(float x) {
     return m;
 }
 
+// Respaced sampling (arreau_sample_loop_scheduled / arreau_reverse_step_to; rules in include/arreau_hip.h): the timestep s that
+// the step leaving t (crystal b, t already clamped to 1..T) produces.  Without a schedule s = t - 1.  Valid targets are s = 0 at
+// t = 1 and 1 <= s <= t - 1 above it; anything else is clamped into that range and flagged (by the caller's one thread per
+// crystal: `flag`).
+__device__ __forceinline__ int step_target(const StepScheduleDev* sc, int b, int t, int32_t* __restrict__ status, bool flag) {
+    if (!sc) return t - 1;
+    int s = sc->s_of ? sc->s_of[b] : sc->next[t];
+    const int lo = t > 1 ? 1 : 0;
+    if (s < lo || s > t - 1) {
+        if (flag) atomicOr(status, ARREAU_STATUS_BAD_TIMESTEP);  // clamped, but flagged
+        s = s < lo ? lo : t - 1;
+    }
+    return s;
+}
+
 // Conditioned sampling (arreau_sample_loop_conditioned; the rules are stated in include/arreau_hip.h).  The step that leaves
-// timestep t produces tau = t - 1; a known component is the template forward-noised to tau with the Philox draw of (seed, t),
-// and the template itself at tau = 0.  The initial state uses the same helpers with t = t_start + 1.
+// timestep t produces tau (t - 1, or the scheduled s); a known component is the template forward-noised to tau with the Philox
+// draw of (seed, t), and the template itself at tau = 0.  The initial state uses the same helpers with t = t_start + 1,
+// tau = t_start.
 // Rule 1, VE_pbc.forward (diffusion_helpers.py:43-47): component g = 3 i + d of a known position.
-__device__ __forceinline__ float known_frac_component(const SampleConditionDev* c, size_t g, int t, uint64_t seed,
+__device__ __forceinline__ float known_frac_component(const SampleConditionDev* c, size_t g, int t, int tau, uint64_t seed,
                                                       const float* __restrict__ ve_sigmas) {
     const float x0 = c->x0[g];
-    if (t - 1 == 0) return remainder_one(x0);
+    if (tau == 0) return remainder_one(x0);
     const float z = philox_normal(seed, (uint32_t)t, ARREAU_DRAW_Z_KNOWN_FRAC, (uint32_t)g);
-    return remainder_one(x0 + ve_sigmas[t - 1] * z);
+    return remainder_one(x0 + ve_sigmas[tau] * z);
 }
 // Rule 2, VP_lattice.forward (diffusion_helpers.py:156-163): component i of crystal b's known lengths.
-__device__ __forceinline__ float known_length_component(const SampleConditionDev* c, int b, int i, int t, uint64_t seed,
+__device__ __forceinline__ float known_length_component(const SampleConditionDev* c, int b, int i, int t, int tau, uint64_t seed,
                                                         const float* __restrict__ alpha_bars) {
     const float l0 = c->l0[3 * b + i];
-    if (t - 1 == 0) return l0;
-    const float ab = alpha_bars[t - 1];
+    if (tau == 0) return l0;
+    const float ab = alpha_bars[tau];
     const float z = philox_normal(seed, (uint32_t)t, ARREAU_DRAW_Z_KNOWN_LENGTHS, 3u * b + i);
     return sqrtf(ab) * l0 + sqrtf(1.0f - ab) * z;
 }
 
-// One component of the length update of crystal b at timestep t (VP_lattice.reverse_given_x0; the per-atom read-out is pooled
-// here when gs_atoms is given: the ordered sum of readout_crystals_kernel).  Writes lengths[3 b + i] and returns it.
-__device__ __forceinline__ float reverse_length_component(int b, int i, int t, int first, int last, float* __restrict__ lengths,
+// One component of the length update of crystal b from timestep t to s (VP_lattice.reverse_given_x0 with t - 1 replaced by s;
+// the per-atom read-out is pooled here when gs_atoms is given: the ordered sum of readout_crystals_kernel).  Writes
+// lengths[3 b + i] and returns it.  A stride-1 step (always, without a schedule) takes beta from the model's betas table.
+__device__ __forceinline__ float reverse_length_component(int b, int i, int t, int s, const StepScheduleDev* sched, int first, int last, float* __restrict__ lengths,
                                                           const float* __restrict__ len0, StepNoiseSrc noise,
                                                           const float* __restrict__ alpha_bars, const float* __restrict__ betas,
                                                           const float* __restrict__ fixed_lengths, const float* __restrict__ gs_atoms,
                                                           float* __restrict__ len0_out, const SampleConditionDev* cond) {
     const float* __restrict__ z = noise.z_lattice;
     const float n = (float)(last - first);
-    const float ab_t = alpha_bars[t], ab_p = alpha_bars[t - 1], beta = betas[t];
+    const float ab_t = alpha_bars[t], ab_p = alpha_bars[s];
+    const float beta = (sched == nullptr || s == t - 1) ? betas[t] : fminf(1.0f - ab_t / ab_p, sched->clipmax);
     const float denom = 1.0f - ab_t;
     const float alpha_t = 1.0f - beta;
     const float c0 = sqrtf(ab_p) * beta;
@@ -73,13 +91,14 @@ __device__ __forceinline__ float reverse_length_component(int b, int i, int t, i
     // fixed-cell sampling (arreau_sample_loop, d_fixed_lengths): the given lengths are re-imposed after the update
     float mylen = fixed_lengths ? fixed_lengths[3 * b + i] : mean + variance * zz;
     // conditioned sampling, rule 2: a known length is replaced before the cell is formed from it
-    if (cond && cond->len_mask && cond->len_mask[b]) mylen = known_length_component(cond, b, i, t, noise.seed, alpha_bars);
+    if (cond && cond->len_mask && cond->len_mask[b]) mylen = known_length_component(cond, b, i, t, s, noise.seed, alpha_bars);
     lengths[3 * b + i] = mylen;
     return mylen;
 }
 
 // One wave per atom: VE_pbc.reverse on the fractional coordinates (diffusion_helpers.py:65-81) and
-// D3PM.reverse on the atom type (d3pm.py:74-110, 198-215).  Lanes span the S classes (2 per lane).
+// D3PM.reverse on the atom type (d3pm.py:74-110, 198-215), from timestep t to s (t - 1 without a schedule).  Lanes span the S
+// classes (2 per lane).
 __device__ __forceinline__ void reverse_one_atom(
     int i /* atom (wave-uniform) */, int lane, float* __restrict__ frac, int32_t* __restrict__ types, const int32_t* __restrict__ tstep,
     const int32_t* __restrict__ offsets, int B, const float* __restrict__ eps,
@@ -87,7 +106,7 @@ __device__ __forceinline__ void reverse_one_atom(
     const float* __restrict__ ve_sigmas, const float* __restrict__ q1t, const float* __restrict__ qmats, int S,
     int T, const int32_t* __restrict__ const_types, int absorbing, int32_t* __restrict__ status,
     const int32_t* __restrict__ batch /* crystal of each atom, or null: searched in `offsets` */,
-    const SampleConditionDev* cond /* conditioned sampling, or null */) {
+    const SampleConditionDev* cond /* conditioned sampling, or null */, const StepScheduleDev* sched /* respaced, or null */) {
     const float* __restrict__ z_frac = noise.z_frac;
     const float* __restrict__ u_types = noise.u_types;
     // crystal of this atom = largest b with offsets[b] <= i: a 64-ary search by the whole wave (each level one
@@ -106,17 +125,18 @@ __device__ __forceinline__ void reverse_one_atom(
     }
     int t = tstep[lo];
     t = t < 1 ? 1 : (t > T ? T : t);
+    const int s_to = step_target(sched, lo, t, status, false);  // (flagged by the crystal's lattice thread)
 
     if (lane < 3) {
         const float s = ve_sigmas[t];
-        const float sp = ve_sigmas[t - 1];  // t >= 1 here; the reference's t == 0 branch is unreachable in sampling
+        const float sp = ve_sigmas[s_to];  // t >= 1 here; the reference's t == 0 branch is unreachable in sampling
         const float s2 = s * s, sp2 = sp * sp;
         const size_t g = 3 * (size_t)i + lane;
         const float mean = frac[g] - eps[g] * (s2 - sp2);
         const float stdv = sqrtf((sp2 * (s2 - sp2)) / s2);
         const float zf = z_frac ? z_frac[g] : philox_normal(noise.seed, (uint32_t)t, ARREAU_DRAW_Z_FRAC, (uint32_t)g);
         float fv = remainder_one(mean + stdv * zf);
-        if (cond && cond->pos_mask && cond->pos_mask[i]) fv = known_frac_component(cond, g, t, noise.seed, ve_sigmas);  // rule 1
+        if (cond && cond->pos_mask && cond->pos_mask[i]) fv = known_frac_component(cond, g, t, s_to, noise.seed, ve_sigmas);  // rule 1
         frac[g] = fv;
     }
 
@@ -140,8 +160,9 @@ __device__ __forceinline__ void reverse_one_atom(
         int xt = types[i];
         if ((xt < 0 || xt >= S) && lane == 0) atomicOr(status, ARREAU_STATUS_BAD_TYPE);  // clamped, but flagged
         xt = xt < 0 ? 0 : (xt >= S ? S - 1 : xt);
-        const float* q1row = q1t + ((size_t)(t - 1) * S + xt) * S;  // fact1 = Q_t^T[x_t, :]
-        const float* qm = qmats + (size_t)(t - 2) * S * S;          // Qbar_{t-1} (reference index t-2)
+        const bool unit = sched == nullptr || s_to == t - 1;
+        const float* q1row = q1t + ((size_t)(t - 1) * S + xt) * S;  // fact1 = Q_t^T[x_t, :] (stride 1)
+        const float* qm = qmats + (size_t)(s_to - 1) * S * S;  // Qbar_s (reference index t-2 at stride 1)
         float f2a = 0.f, f2b = 0.f;
         if (absorbing) {
             // Absorbing ("mask") chain: Qbar_t is diagonal plus the mask column (checked on the host for every t at model
@@ -185,8 +206,20 @@ __device__ __forceinline__ void reverse_one_atom(
                 f2b = fmaf(sc, qb[i], f2b);
             }
         }
-        post0 = v0 ? logf(q1row[s0] + D3PM_EPS) + logf(f2a + D3PM_EPS) : -INFINITY;
-        post1 = v1 ? logf(q1row[s1] + D3PM_EPS) + logf(f2b + D3PM_EPS) : -INFINITY;
+        if (unit) {
+            post0 = v0 ? logf(q1row[s0] + D3PM_EPS) + logf(f2a + D3PM_EPS) : -INFINITY;
+            post1 = v1 ? logf(q1row[s1] + D3PM_EPS) + logf(f2b + D3PM_EPS) : -INFINITY;
+        } else {
+            // respaced: fact1 = Qbar_{t-s}[:, x_t], the column x_t of q_mats[t-s-1] (the mask chain is time-homogeneous, so the
+            // (t-s)-step transition is the (t-s)-step product).  Absorbing chain: that column is zero off the diagonal unless
+            // x_t is the mask class -- the entries skipped are exact zeros, as in the shortcut above.
+            const float* qcol = qmats + (size_t)(t - s_to - 1) * S * S + xt;
+            const bool all = !absorbing || xt == S - 1;
+            const float fa = (v0 && (all || s0 == xt)) ? qcol[(size_t)s0 * S] : 0.f;
+            const float fb = (v1 && (all || s1 == xt)) ? qcol[(size_t)s1 * S] : 0.f;
+            post0 = v0 ? logf(fa + D3PM_EPS) + logf(f2a + D3PM_EPS) : -INFINITY;
+            post1 = v1 ? logf(fb + D3PM_EPS) + logf(f2b + D3PM_EPS) : -INFINITY;
+        }
     }
     // ---- Gumbel arg-max (d3pm.py:206-214) ----------------------------------------------------------
     const float scale = (t != 1) ? 1.0f : 0.2f;
@@ -227,16 +260,17 @@ __device__ __forceinline__ void reverse_atoms_body(
     const float* __restrict__ logits, StepNoiseSrc noise,
     const float* __restrict__ ve_sigmas, const float* __restrict__ q1t, const float* __restrict__ qmats, int S,
     int T, const int32_t* __restrict__ const_types, int absorbing, int32_t* __restrict__ status, int n0,
-    const int32_t* __restrict__ batch, const SampleConditionDev* cond) {
+    const int32_t* __restrict__ batch, const SampleConditionDev* cond, const StepScheduleDev* sched) {
     const int i = n0 + blk * 4 + (int)(threadIdx.x >> 6);  // atoms n0 .. N-1
     if (i >= N) return;  // wave-uniform; no block-level barrier below
     reverse_one_atom(i, threadIdx.x & 63, frac, types, tstep, offsets, B, eps, logits, noise, ve_sigmas, q1t, qmats, S, T, const_types, absorbing,
-                     status, batch, cond);
+                     status, batch, cond, sched);
 }
 
 // Sampling loop (round 3): the lattice update of a crystal by ONE workgroup that then also prepares the crystal's NEXT step --
 // what prep_kernel (node.hip) would compute at the top of that step from the lengths just written: the cell (into the
-// caller's lattice AND the workspace copy the network reads) and the per-crystal part of the embedding for timestep t - 1.
+// caller's lattice AND the workspace copy the network reads) and the per-crystal part of the embedding for timestep t - 1 (the
+// scheduled successor of t in a respaced loop).
 // The step then needs no prep launch (the Cartesian positions, prep's other product, are formed by the neighbour-list waves
 // from the fractional coordinates).  Same arithmetic as reverse_lattice_body + prep_kernel, thread for thread.
 __device__ __forceinline__ void reverse_crystal_block(int b, float* __restrict__ lengths, const float* __restrict__ angles,
@@ -247,15 +281,17 @@ __device__ __forceinline__ void reverse_crystal_block(int b, float* __restrict__
                                                       int32_t* __restrict__ status, const float* __restrict__ gs_atoms,
                                                       float* __restrict__ len0_out, float* __restrict__ lattice_ws,
                                                       float* __restrict__ cvec_next, const float* __restrict__ t_emb_w,
-                                                      const float* __restrict__ embT, int S, int C, const SampleConditionDev* cond) {
+                                                      const float* __restrict__ embT, int S, int C, const SampleConditionDev* cond,
+                                                      const StepScheduleDev* sched) {
     __shared__ float newlen[3];
     __shared__ float feat[ARREAU_T_EMB_DIM + ARREAU_N_CRYSTAL_FEATS];
     const int t_raw = tstep[b];
     if (threadIdx.x == 0 && (t_raw < 1 || t_raw > T)) atomicOr(status, ARREAU_STATUS_BAD_TIMESTEP);  // clamped, but flagged
     const int t = t_raw < 1 ? 1 : (t_raw > T ? T : t_raw);
+    const int s = step_target(sched, b, t, status, threadIdx.x == 0);
     const int first = offsets[b], last = offsets[b + 1];
     if (threadIdx.x < 3)
-        newlen[threadIdx.x] = reverse_length_component(b, threadIdx.x, t, first, last, lengths, len0, noise, alpha_bars, betas, fixed_lengths,
+        newlen[threadIdx.x] = reverse_length_component(b, threadIdx.x, t, s, sched, first, last, lengths, len0, noise, alpha_bars, betas, fixed_lengths,
                                                        gs_atoms, len0_out, cond);
     __syncthreads();
     const float* ang = angles + 3 * b;
@@ -265,6 +301,6 @@ __device__ __forceinline__ void reverse_crystal_block(int b, float* __restrict__
 #pragma unroll
         for (int q = 0; q < 9; ++q) { lattice[9 * b + q] = Lm[q]; lattice_ws[9 * b + q] = Lm[q]; }
     }
-    arreau_prep_cvec(t_raw - 1, last - first, newlen, ang, betas, t_emb_w, embT, S, C, T, feat, cvec_next + (size_t)b * C, status);
+    arreau_prep_cvec(sched ? s : t_raw - 1, last - first, newlen, ang, betas, t_emb_w, embT, S, C, T, feat, cvec_next + (size_t)b * C, status);
 }
 

@@ -32,6 +32,7 @@ class VP_lattice(nn.Module):
 
     def __init__(self, num_steps=1000, s=0.0001, power=2, clipmax=0.999):
         super().__init__()
+        self.clipmax = clipmax  # (a respaced step clips its beta the same way: arreau_sample_loop_scheduled)
         t = torch.arange(0, num_steps + 1, dtype=torch.float)
         f_t = torch.cos((np.pi / 2) * ((t / num_steps) + s) / (1 + s)) ** power
         alpha_bars = f_t / f_t[0]

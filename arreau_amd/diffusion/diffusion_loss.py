@@ -3,7 +3,7 @@ its training loss (`__call__`, :204-274) driving the HIP engine.  The backward p
 built yet, so `__call__` returns the loss value (and the gradients with respect to the network outputs), not an
 autograd graph."""
 from dataclasses import dataclass
-from typing import Optional
+from typing import Optional, Sequence
 
 import numpy as np
 import os
@@ -11,6 +11,7 @@ import os
 import torch
 import torch.nn as nn
 
+from . import respacing
 from .d3pm import D3PM
 from .diffusion_helpers import VE_pbc, VP_lattice, crystal_offsets, sample_bravais_angles
 from .inference.visualize_crystal import VisualizationSetting, vis_crystal_during_sampling
@@ -256,7 +257,8 @@ class DiffusionLoss(nn.Module):
                num_samples_in_batch: Optional[int] = None, vis_name: str = "", visualization_setting=VisualizationSetting.NONE,
                show_bonds: bool = False, constant_atoms: Optional[torch.Tensor] = None, noise: str = "philox",
                max_steps: Optional[int] = None, use_graph: Optional[bool] = None, seed: Optional[int] = None,
-               fixed_cell: bool = False, condition=None) -> SampleResult:
+               fixed_cell: bool = False, condition=None, num_steps: Optional[int] = None,
+               timesteps: Optional[Sequence[int]] = None) -> SampleResult:
         """diffusion_loss.py:276-377.  The initial state is drawn on the host exactly like the reference (numpy
         uniforms for the angles, then randn lengths, randn fractional coordinates from torch's global CPU generator).
         Per-step noise:
@@ -278,12 +280,20 @@ class DiffusionLoss(nn.Module):
         `condition` (extension, noise="philox" only): a conditioning.SampleCondition -- known positions, species and cells held
         to a template while the rest is generated (arreau_sample_loop_conditioned; rules in include/arreau_hip.h).  It defines
         the batch: num_atoms_per_sample / num_samples_in_batch may be omitted or must agree with it.  The initial state is
-        drawn exactly as without it; the known components are then overwritten on the device."""
+        drawn exactly as without it; the known components are then overwritten on the device.
+        `num_steps` / `timesteps` (extension, every noise mode; mutually exclusive): respaced sampling -- the loop visits only
+        the timesteps of a schedule (respacing.respaced_timesteps(T, num_steps), evenly spaced, or an explicit strictly
+        descending list from at most T-1 down to 1) and jumps from each to the next in closed form (rules in
+        include/arreau_hip.h; arreau_sample_loop_scheduled / arreau_reverse_step_to).  The step at a visited timestep draws
+        what a full run draws there.  `max_steps` keeps the schedule's first max_steps steps; frames follow the schedule
+        (ALL: the visited multiples of 10, ALL_DETAILED: every visited timestep).  The full schedule T-1, ..., 1 given
+        explicitly is the plain loop bit for bit.  No claim on sample quality at a given number of steps is made."""
         frames = visualization_setting != VisualizationSetting.NONE
         if frames and not vis_name:
             raise ValueError("visualization_setting other than NONE needs vis_name (prefix of the frame files)")
         if noise not in ("philox", "device", "reference"):
             raise ValueError("noise must be 'philox', 'device' or 'reference'")
+        schedule = respacing.resolve_schedule(self.T, num_steps=num_steps, timesteps=timesteps)  # None: every timestep
         if condition is not None:  # validated before the engine is touched
             num_atoms_per_sample, num_samples_in_batch = condition.resolve_batch(num_atoms_per_sample, num_samples_in_batch)
             condition.check_sampling(z_table, noise=noise, fixed_cell=fixed_cell, constant_species=constant_atoms is not None)
@@ -324,7 +334,14 @@ class DiffusionLoss(nn.Module):
         const_d = types_d.clone() if constant_atoms is not None else None
         off_d = crystal_offsets(num_atoms, dev)
         lattice_d = torch.zeros((B, 3, 3), **f32)
-        n_steps = self.T - 1 if max_steps is None else min(self.T - 1, int(max_steps))
+        # the timesteps this run visits, in order: every one (T-1 .. 1) or the schedule's, cut to max_steps
+        steps = list(range(self.T - 1, 0, -1)) if schedule is None else schedule
+        steps = steps if max_steps is None else steps[:max(0, int(max_steps))]
+        n_steps = len(steps)
+        t_first = self.T - 1 if schedule is None else schedule[0]
+        successor = None if schedule is None else dict(zip(schedule, schedule[1:] + [0]))
+        clipmax = float(getattr(self.lattice_diffusion, "clipmax", lattice_clipmax))
+        next_d = respacing.next_table(self.T, schedule).to(dev) if schedule is not None and noise == "philox" else None
         if (use_graph or fixed_cell) and noise != "philox":
             raise ValueError("graph replay and fixed-cell sampling need noise='philox' (the in-kernel generator)")
 
@@ -338,10 +355,10 @@ class DiffusionLoss(nn.Module):
             rng_state = torch.random.get_rng_state()
         cond_d = None
         if condition is not None:
-            # rule 5: the known components of the drawn initial state, at timestep T - 1 (Philox key T); the saved initial
-            # state of a re-run below includes them
+            # rule 5: the known components of the drawn initial state, at the first timestep t_1 (T - 1 without a schedule;
+            # Philox key t_1 + 1); the saved initial state of a re-run below includes them
             cond_d = condition.device_arrays(z_table, dev)
-            eng.condition_initial_state(frac_d, types_d, len_d, self.T - 1, seed, cond_d)
+            eng.condition_initial_state(frac_d, types_d, len_d, t_first, seed, cond_d)
             init_state = (frac_d.clone(), types_d.clone(), len_d.clone())
 
         def run_loop(use_graph):
@@ -349,29 +366,28 @@ class DiffusionLoss(nn.Module):
                 if use_graph is None:
                     use_graph = n_steps >= 200  # capture + instantiation (about 2 ms) against ~4 us saved per kernel boundary
                 fixed = len_d.clone() if fixed_cell else None
-                # Frames (diffusion_loss.py:351-370): the loop is cut at the timesteps the reference visualises -- every 10th
-                # for ALL, every one for ALL_DETAILED, never the first (T - 1).  The noise is a function of (seed, timestep),
-                # so a run in segments is the same trajectory as a run in one call.
-                t_first, t_last = self.T - 1, self.T - n_steps
-                stops = [t for t in range(t_first - 1, t_last - 1, -1)
-                         if (visualization_setting == VisualizationSetting.ALL and t % 10 == 0)
+                # Frames (diffusion_loss.py:351-370): the loop is cut after the steps at the timesteps the reference
+                # visualises -- every 10th for ALL, every one for ALL_DETAILED, never the first -- of those this run visits.
+                # The noise is a function of (seed, timestep), so a run in segments is the same trajectory as a run in one
+                # call; a respaced segment starts at any scheduled timestep (respacing.next_table).
+                stops = [j for j in range(1, n_steps)
+                         if (visualization_setting == VisualizationSetting.ALL and steps[j] % 10 == 0)
                          or visualization_setting == VisualizationSetting.ALL_DETAILED]
-                t_cur = t_first
-                for t_stop in stops + [None]:
-                    n_seg = (t_cur - t_stop + 1) if t_stop is not None else (t_cur - t_last + 1)
-                    if n_seg > 0:
-                        eng.sample_loop(frac_d, types_d, len_d, ang_d, off_d, t_cur, n_seg, seed, const_d, lattice_d,
-                                        use_graph=bool(use_graph), fixed_lengths=fixed, condition=cond_d)
-                        t_cur -= n_seg
-                    if t_stop is not None:
+                start = 0
+                for j in stops + [None]:
+                    end = j + 1 if j is not None else n_steps
+                    if end > start:
+                        eng.sample_loop(frac_d, types_d, len_d, ang_d, off_d, steps[start], end - start, seed, const_d, lattice_d,
+                                        use_graph=bool(use_graph), fixed_lengths=fixed, condition=cond_d, next_table=next_d,
+                                        lattice_clipmax=clipmax)
+                        start = end
+                    if j is not None:
                         vis_crystal_during_sampling(z_table, types_d.cpu().numpy(), lattice_d.cpu().numpy(),
-                                                    frac_d.cpu().numpy(), vis_name + f"_{t_stop}", show_bonds, num_atoms.numpy())
+                                                    frac_d.cpu().numpy(), vis_name + f"_{steps[j]}", show_bonds, num_atoms.numpy())
             else:
                 t_d = torch.empty(B, device=dev, dtype=torch.int32)
-                done = 0
-                for timestep in reversed(range(1, self.T)):
-                    if done >= n_steps:
-                        break
+                s_d = torch.empty(B, device=dev, dtype=torch.int32)
+                for timestep in steps:
                     t_d.fill_(timestep)
                     eps, logits, len0 = eng.predict_scores(frac_d, types_d, len_d, ang_d, t_d, off_d)
                     if noise == "device":
@@ -382,11 +398,15 @@ class DiffusionLoss(nn.Module):
                         z_l = torch.randn([B, 3]).to(**f32)
                         z_f = torch.randn([N, 3], dtype=dt).to(**f32)
                         u_t = torch.rand([N, S]).to(**f32)
-                    eng.reverse_step(frac_d, types_d, len_d, ang_d, t_d, off_d, eps, logits, len0, z_l, z_f, u_t, lattice_d)
+                    if schedule is None:
+                        eng.reverse_step(frac_d, types_d, len_d, ang_d, t_d, off_d, eps, logits, len0, z_l, z_f, u_t, lattice_d)
+                    else:
+                        s_d.fill_(successor[timestep])
+                        eng.reverse_step_to(frac_d, types_d, len_d, ang_d, t_d, s_d, off_d, eps, logits, len0, z_l, z_f, u_t,
+                                            lattice_d, clipmax)
                     if const_d is not None:
                         types_d.copy_(const_d)
-                    done += 1
-                    if timestep != self.T - 1 and ((visualization_setting == VisualizationSetting.ALL and timestep % 10 == 0)
+                    if timestep != t_first and ((visualization_setting == VisualizationSetting.ALL and timestep % 10 == 0)
                                                    or visualization_setting == VisualizationSetting.ALL_DETAILED):
                         vis_crystal_during_sampling(z_table, types_d.cpu().numpy(), lattice_d.cpu().numpy(),
                                                     frac_d.cpu().numpy(), vis_name + f"_{timestep}", show_bonds, num_atoms.numpy())

@@ -191,17 +191,28 @@ class HipEngine:
         return logits, vec_out, gscalar
 
     def sample_loop(self, frac, types, lengths, angles, offsets, t_start, n_steps, seed, const_types, lattice_out,
-                    use_graph=False, fixed_lengths=None, condition=None):
+                    use_graph=False, fixed_lengths=None, condition=None, next_table=None, lattice_clipmax=0.999):
         """n_steps iterations of the sampling loop in one library call (arreau_sample_loop): in-place update of
         (frac, types, lengths); Philox noise keyed by (seed, timestep, draw, element).  `condition`: the device arrays of a
         conditioned run (SampleCondition.device_arrays: x0, pos_mask, a0, type_mask, l0, len_mask; None entries allowed),
-        through arreau_sample_loop_conditioned."""
+        through arreau_sample_loop_conditioned.  `next_table`: a respaced run (arreau_sample_loop_scheduled): the device
+        int32 [T+1] table of respacing.next_table, with VP_lattice's clipmax; t_start is then a scheduled timestep."""
         N, B = frac.shape[0], lengths.shape[0]
         ws = self.workspace(N, B)
         args = (self._handle, _hip.ptr(frac), _hip.ptr(types), _hip.ptr(lengths), _hip.ptr(angles), _hip.ptr(offsets), B, N,
                 int(t_start), int(n_steps), int(seed) & (2 ** 64 - 1), _hip.ptr(const_types), _hip.ptr(fixed_lengths),
                 _hip.ptr(lattice_out), _hip.ptr(ws), ws.numel(), int(bool(use_graph)))
-        if condition is None:
+        if next_table is not None:
+            T = int(self.cfg.num_timesteps)
+            if (tuple(next_table.shape) != (T + 1,) or next_table.dtype != torch.int32 or next_table.device != self.device
+                    or not next_table.is_contiguous()):
+                raise ValueError(f"next_table must be a contiguous int32 tensor of shape ({T + 1},) on {self.device}")
+            cond = self._condition_struct(condition, N, B) if condition is not None else None
+            sched = _hip.SampleScheduleC(_hip.ptr(next_table).value, float(lattice_clipmax))
+            _hip.check(_hip.lib().arreau_sample_loop_scheduled(*args, ctypes.byref(cond) if cond is not None else None,
+                                                               ctypes.byref(sched), _hip.stream_ptr(self.device)),
+                       "arreau_sample_loop_scheduled")
+        elif condition is None:
             _hip.check(_hip.lib().arreau_sample_loop(*args, _hip.stream_ptr(self.device)), "arreau_sample_loop")
         else:
             cond = self._condition_struct(condition, N, B)
@@ -471,6 +482,16 @@ class HipEngine:
             _hip.ptr(offsets), B, N, _hip.ptr(eps), _hip.ptr(logits), _hip.ptr(len0), _hip.ptr(z_lattice),
             _hip.ptr(z_frac), _hip.ptr(u_types), _hip.ptr(lattice_out), _hip.stream_ptr(self.device)),
             "arreau_reverse_step")
+
+    def reverse_step_to(self, frac, types, lengths, angles, t_crystal, s_crystal, offsets, eps, logits, len0, z_lattice, z_frac,
+                        u_types, lattice_out, lattice_clipmax=0.999):
+        """reverse_step from timestep t_crystal[b] to s_crystal[b] (arreau_reverse_step_to: a respaced step)."""
+        B, N = lengths.shape[0], frac.shape[0]
+        _hip.check(_hip.lib().arreau_reverse_step_to(
+            self._handle, _hip.ptr(frac), _hip.ptr(types), _hip.ptr(lengths), _hip.ptr(angles), _hip.ptr(t_crystal),
+            _hip.ptr(s_crystal), _hip.ptr(offsets), B, N, _hip.ptr(eps), _hip.ptr(logits), _hip.ptr(len0), _hip.ptr(z_lattice),
+            _hip.ptr(z_frac), _hip.ptr(u_types), _hip.ptr(lattice_out), float(lattice_clipmax), _hip.stream_ptr(self.device)),
+            "arreau_reverse_step_to")
 
     def edges_to_slots(self, edge_index, dists, direction, N):
         """Receiver-sorted COO edges -> slot form (deg, src, dir, dist)."""

@@ -11,6 +11,8 @@ in crystal order.  The only communication is that final gather of host arrays
 Conditioned generation (structure completion): `--template crystals.npz` (the wire format below, plus optional
 `position_mask` [N] / `species_mask` [N] / `lattice_mask` [B] arrays) gives the batch; `--fix positions,species,lattice`
 fixes those components wherever the file has no mask for them; `--samples_per_template K` tiles the templates K times.
+
+Respaced sampling: `--num_steps K` runs K evenly spaced denoising steps instead of every timestep (DiffusionLoss.sample).
 """
 import argparse
 import os
@@ -120,8 +122,7 @@ def save_sample_results(crystals: SampleResult, filename: str):
     return save_sample_results_to_hdf5(crystals, filename)
 
 
-def main():
-    import torch
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--model_path", type=str, required=True)
     ap.add_argument("--num_crystals", type=int, default=10)
@@ -134,7 +135,14 @@ def main():
     ap.add_argument("--fix", type=str, default="", help="components fixed where the template has no mask: "
                     "comma-separated subset of positions,species,lattice")
     ap.add_argument("--samples_per_template", type=int, default=1, help="the templates are tiled this many times")
-    args = ap.parse_args()
+    ap.add_argument("--num_steps", type=int, default=None,
+                    help="respaced sampling: this many evenly spaced denoising steps (2..T-1; default: every timestep)")
+    return ap
+
+
+def main():
+    import torch
+    args = build_parser().parse_args()
     condition = load_template(args.template, parse_fix(args.fix)).tile(args.samples_per_template) if args.template else None
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -154,6 +162,9 @@ def main():
     from .diffusion.inference.visualize_crystal import VisualizationSetting
     from .lightning_wrappers.diffusion import PONITA_DIFFUSION
     model = PONITA_DIFFUSION.load_from_checkpoint(args.model_path, map_location=f"cuda:{local_rank}", strict=False)
+    if args.num_steps is not None:
+        from .diffusion import respacing
+        respacing.resolve_schedule(model.diffusion_loss.T, num_steps=args.num_steps)  # (a bad --num_steps fails before sampling)
     if args.seed is not None:
         import numpy as np
         torch.manual_seed(args.seed + rank)
@@ -164,12 +175,12 @@ def main():
 
     def fn(n, b, cond=None):
         if not lock_path:
-            return model.sample(n, b, VisualizationSetting.NONE, False, condition=cond)
+            return model.sample(n, b, VisualizationSetting.NONE, False, condition=cond, num_steps=args.num_steps)
         import fcntl
         with open(lock_path, "a") as lock:
             fcntl.flock(lock, fcntl.LOCK_EX)
             try:
-                out = model.sample(n, b, VisualizationSetting.NONE, False, condition=cond)
+                out = model.sample(n, b, VisualizationSetting.NONE, False, condition=cond, num_steps=args.num_steps)
                 torch.cuda.synchronize()
                 return out
             finally:

@@ -116,7 +116,8 @@ int arreau_model_config(const arreau_model* model, arreau_config* out_cfg);
  *   NONFINITE    a network output (eps, logits, pred_lengths_0) was inf/NaN -- this is how an activation beyond the
  *                fp16 range of the split-precision kernels (|v| >= 65520) surfaces: the planes overflow to inf and the
  *                value propagates as NaN instead of being clamped silently;
- *   BAD_TIMESTEP a timestep outside [0, T] (predict_scores) / [1, T] (reverse_step) was clamped;
+ *   BAD_TIMESTEP a timestep outside [0, T] (predict_scores) / [1, T] (reverse_step) was clamped, or a respaced step's
+ *                target s outside its range (arreau_reverse_step_to, arreau_sample_loop_scheduled);
  *   BAD_TYPE     an atom-type index outside [0, S) was clamped.
  * edge_kernel / mlp_kernel / conv_kernel name the kernel family the last arreau_predict_scores really launched
  * (edge: 0-2 fp32 MFMA, 3 bf16x6, 4 fp16x3; mlp: 0 fp32 MFMA, 1 bf16x6, 2 fp16x3 32x32x16, 3 fp16x3 16x16x32;
@@ -281,7 +282,8 @@ int arreau_sample_loop(arreau_model* model, float* d_frac, int32_t* d_types, flo
  * atom / crystal, nonzero = known; a mask needs its values, values without a mask are ignored.
  *   x0[N,3], pos_mask[N]: known fractional coordinates;  a0[N], type_mask[N]: known class indices (z-table indices);
  *   l0[B,3], len_mask[B]: known cell lengths.
- * The state at time tau is (frac, types, lengths); the update of the step that leaves timestep t produces tau = t - 1.
+ * The state at time tau is (frac, types, lengths); the update of the step that leaves timestep t produces tau = t - 1 (in a
+ * respaced loop, tau = s, the scheduled successor of t: see the section below).
  *   1. positions: after the VE reverse update, frac = remainder(x0 + ve_sigmas[tau] * z, 1),
  *      z = Philox normal (seed, t, kind 3, element 3 i + d); at tau = 0 exactly remainder(x0, 1).  This is VE_pbc.forward
  *      at tau (diffusion/diffusion_helpers.py:43-47).
@@ -317,6 +319,57 @@ int arreau_sample_loop_conditioned(arreau_model* model, float* d_frac, int32_t* 
 int arreau_condition_initial_state(const arreau_model* model, float* d_frac, int32_t* d_types, float* d_lengths, int32_t B,
                                    int32_t N, int32_t t_start, uint64_t seed, const arreau_sample_condition* cond,
                                    void* stream);
+
+/* ---- respaced sampling (fewer denoising steps) -----------------------------------------------------------------
+ * The loop runs on a strictly descending schedule t_1 > t_2 > ... > t_K of trained timesteps with t_1 <= T-1 and t_K = 1
+ * ("respacing", Nichol & Dhariwal 2021, section 4).  The step that leaves t_i produces the state at s = t_{i+1}; the step at
+ * t_K = 1 produces s = 0.  The network is evaluated at t as before; every process jumps from t to s in closed form, float32,
+ * the reference's own formulas with t - 1 replaced by s:
+ *   1. VE positions (diffusion_helpers.py:65-81): mean = x_t - eps (sig_t^2 - sig_s^2),
+ *      std = sqrt(sig_s^2 (sig_t^2 - sig_s^2) / sig_t^2), x_s = remainder(mean + std z, 1), sig = ve_sigmas.
+ *   2. VP lengths (reverse_given_x0, :185-199): beta = min(1 - abar_t / abar_s, lattice_clipmax), alpha = 1 - beta,
+ *      mean = (sqrt(abar_s) beta x0 + sqrt(alpha) (1 - abar_s) x_t) / (1 - abar_t), var = (1 - abar_s) beta / (1 - abar_t),
+ *      l_s = mean + var z (the reference's variance, not its square root), z = 0 for t <= 1.
+ *   3. D3PM species (d3pm.py:74-110, 198-215): for t > 1 the posterior logits are
+ *      log(Qbar_{t-s}[:, x_t] + eps) + log(softmax(x0_logits) . Qbar_s + eps), Qbar_k = q_mats[k-1] (the mask chain is
+ *      time-homogeneous, so the (t-s)-step transition is Qbar_{t-s}); at t = 1 the raw x0 logits.  Gumbel scale and tie rule
+ *      as in arreau_reverse_step.
+ *   4. a stride-1 step (s = t - 1) uses the model's tables as arreau_reverse_step does (betas[t], q_one_step_transposed,
+ *      q_mats[t-2]): the full schedule T-1, ..., 1 is the schedule-less loop bit for bit.
+ *   5. the network input of the next step is evaluated at s (its per-crystal embedding is prepared for s).
+ *   6. conditioned sampling: a known component is the template noised to tau = s (rules 1, 2 of the section above, with the
+ *      draw (seed, t, kind 3/4)), exactly the template at s = 0; rule 5 (the initial state) uses t_start = t_1.
+ *   7. noise keys do not change: the step at t draws (seed, t, kind, element), so a respaced run uses, at every timestep it
+ *      visits, the draws a full run uses there.
+ * Valid targets are s = 0 at t = 1 and 1 <= s <= t - 1 for t > 1; any other s is clamped into that range and sets
+ * ARREAU_STATUS_BAD_TIMESTEP.  No claim on sample quality at a given K is made here (there is no trained checkpoint to judge it).
+ *
+ * d_next[T+1] (device, int32): the schedule as a next-timestep table, d_next[t_i] = t_{i+1}, d_next[1] = 0, and for every
+ * t_i also d_next[t_i + 1] = t_i (a loop starts "one above" its first timestep: its first launch advances the device
+ * timestep; when t_i + 1 is itself scheduled this holds already).  A loop call may then start at any scheduled timestep,
+ * which is how a run is cut into segments (frames).  lattice_clipmax: VP_lattice's clipmax (0.999 by default). */
+typedef struct arreau_sample_schedule {
+    const int32_t* d_next;
+    float lattice_clipmax;
+} arreau_sample_schedule;
+
+/* arreau_sample_loop_conditioned on a schedule: n_steps steps from t_start (a scheduled timestep, 1 <= t_start <= T-1) along
+ * d_next.  `schedule` is a host pointer, NULL = every timestep (arreau_sample_loop_conditioned).  The table pointer and the
+ * clip are part of what a cached hipGraph was captured for. */
+int arreau_sample_loop_scheduled(arreau_model* model, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                                 const int32_t* d_crystal_offsets, int32_t B, int32_t N, int32_t t_start, int32_t n_steps,
+                                 uint64_t seed, const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice,
+                                 void* d_workspace, size_t workspace_bytes, int32_t use_graph,
+                                 const arreau_sample_condition* cond, const arreau_sample_schedule* schedule, void* stream);
+
+/* arreau_reverse_step from timestep d_t[b] to d_s[B] (per crystal, rules above): the respaced step with the caller's noise,
+ * for the loops with host-side noise and for parity tests.  At d_s[b] = d_t[b] - 1 it is arreau_reverse_step bit for bit. */
+int arreau_reverse_step_to(const arreau_model* model,
+                           float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                           const int32_t* d_t, const int32_t* d_s, const int32_t* d_crystal_offsets, int32_t B, int32_t N,
+                           const float* d_eps, const float* d_logits, const float* d_len0,
+                           const float* d_z_lattice, const float* d_z_frac, const float* d_u_types,
+                           float* d_lattice, float lattice_clipmax, void* stream);
 
 /* The sampler's in-kernel noise written out: d_out[i] = draw (seed, timestep, kind, element i) -- standard normal for
  * kind 0 (z_lattice), 1 (z_frac), 3 (known positions) and 4 (known lengths), uniform [0,1) for kind 2 (u_types); d_raw[4 i .. 4 i + 3] (may be NULL) = the raw
