@@ -26,6 +26,7 @@ EXPORTS = [
     "arreau_model_set_formats", "arreau_debug_set_pollution", "arreau_debug_leftover_fraction",
     "arreau_sample_loop_conditioned", "arreau_condition_initial_state",
     "arreau_sample_loop_scheduled", "arreau_reverse_step_to",
+    "arreau_sample_loop_corrected", "arreau_corrector_step", "arreau_philox_fill_word",
 ]
 
 STATUS_NONFINITE, STATUS_BAD_TIMESTEP, STATUS_BAD_TYPE = 1, 2, 4
@@ -57,6 +58,11 @@ class SampleConditionC(Structure):
 class SampleScheduleC(Structure):
     """arreau_sample_schedule: the device next-timestep table [T+1] of a respaced loop and VP_lattice's clipmax."""
     _fields_ = [("d_next", c_void_p), ("lattice_clipmax", ctypes.c_float)]
+
+
+class CorrectorC(Structure):
+    """arreau_corrector: M Langevin corrector steps per visited timestep and the SNR of their step-size rule."""
+    _fields_ = [("steps", c_int32), ("snr", ctypes.c_float)]
 
 
 class Config(Structure):
@@ -132,6 +138,13 @@ def lib():
         L.arreau_sample_loop_scheduled.argtypes = (L.arreau_sample_loop_conditioned.argtypes[:-1] +
                                                    [POINTER(SampleScheduleC), c_void_p])
         L.arreau_reverse_step_to.argtypes = [c_void_p] * 8 + [c_int32, c_int32] + [c_void_p] * 7 + [ctypes.c_float, c_void_p]
+    if hasattr(L, "arreau_sample_loop_corrected") or not os.environ.get("ARREAU_HIP_LIB"):  # (an older build under test)
+        L.arreau_sample_loop_corrected.argtypes = (L.arreau_sample_loop_scheduled.argtypes[:-1] +
+                                                   [POINTER(CorrectorC), c_void_p])
+        L.arreau_corrector_step.argtypes = [c_void_p] * 4 + [c_int32, c_int32] + [c_void_p] * 2 + [ctypes.c_float,
+                                                                                                   POINTER(SampleConditionC), c_void_p]
+        L.arreau_philox_fill_word.argtypes = [ctypes.c_uint64, c_int32, c_int32, ctypes.c_uint32, c_int64, c_void_p, c_void_p,
+                                              c_void_p]
     L.arreau_philox_fill.argtypes = [ctypes.c_uint64, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_void_p]
     L.arreau_train_forward.argtypes = [c_void_p] * 7 + [c_int32, c_int32] + [c_void_p] * 4
     L.arreau_train_backward.argtypes = [c_void_p] * 4 + [POINTER(StateDict), c_void_p]

@@ -296,30 +296,51 @@ bool loop_without_prep(const arreau_model* m) {
     return !(e && atoi(e) != 0) && !arreau_general_path(m);
 }
 
+// Predictor-corrector sampling (arreau_sample_loop_corrected): M corrector moves at the step's timestep come before the
+// predictor, each after a full network evaluation on the current state.  Only the first evaluation of a step advances the
+// device timestep; the later ones rebuild the neighbour list and the per-atom embedding from the moved positions at the same
+// timestep.  The lattice and the per-crystal embedding stay valid: a corrector moves fractional coordinates only.
+struct CorrectorDev {
+    int steps;  // M (0: the plain step)
+    float snr;
+};
+
 int enqueue_sample_step(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
                         const int32_t* d_off, int B, int N, uint64_t seed, const int32_t* d_const_types,
                         const float* d_fixed_lengths, float* d_lattice, const Workspace& w, hipStream_t s, bool no_prep,
-                        const SampleConditionDev* cond, const StepScheduleDev* sched) {
+                        const SampleConditionDev* cond, const StepScheduleDev* sched, CorrectorDev corr) {
     int rc;
     const int32_t* next_t = sched ? sched->next : nullptr;  // respaced loop: the device timestep follows the table
     if (no_prep) {
-        if ((rc = arreau_launch_neighbor_embed(m, nullptr, w.lattice, d_off, w.batch, B, N, w.deg, w.src, w.cell, w.dir, w.dist, d_frac,
-                                               d_types, w.cvec, w.xa, s, w.t_cur, next_t)))
-            return rc;
-        if ((rc = run_edge_kernel(m, w.dir, w.dist, w.deg, w, N, s))) return rc;
-        if ((rc = run_layers_and_readout(m, w, w.deg, w.src, d_off, B, N, w.eps, w.logits, nullptr, s))) return rc;
+        for (int j = 0; j <= corr.steps; ++j) {
+            if ((rc = arreau_launch_neighbor_embed(m, nullptr, w.lattice, d_off, w.batch, B, N, w.deg, w.src, w.cell, w.dir, w.dist, d_frac,
+                                                   d_types, w.cvec, w.xa, s, w.t_cur, next_t, /*advance=*/j == 0)))
+                return rc;
+            if ((rc = run_edge_kernel(m, w.dir, w.dist, w.deg, w, N, s))) return rc;
+            if ((rc = run_layers_and_readout(m, w, w.deg, w.src, d_off, B, N, w.eps, w.logits, nullptr, s))) return rc;
+            if (j < corr.steps &&
+                (rc = arreau_launch_corrector(m, d_frac, w.t_cur, d_off, B, N, w.eps, nullptr, seed, (uint32_t)j, corr.snr, cond, s)))
+                return rc;
+        }
         return arreau_launch_reverse(m, d_frac, d_types, d_lengths, d_angles, w.t_cur, d_off, B, N, w.eps, w.logits, w.len0,
                                      StepNoiseSrc{nullptr, nullptr, nullptr, seed}, d_const_types, d_lattice, s, d_fixed_lengths,
                                      w.gs, w.batch, w.lattice, w.cvec, cond, sched);
     }
-    if ((rc = arreau_launch_prep(m, d_frac, d_lengths, d_angles, nullptr, d_off, B, N, w.lattice, w.cart, w.batch, w.cvec, s,
-                                 w.t_next, w.t_cur, 0, next_t)))
-        return rc;
     // fused kernels: the per-crystal pooling of the lattice read-out happens inside the lattice update (no launch of its own)
     const bool pool_in_update = !arreau_general_path(m);
-    if ((rc = run_network(m, w, false, w.deg, w.src, w.dir, w.dist, d_frac, d_types, d_off, B, N, w.eps, w.logits,
-                          pool_in_update ? nullptr : w.len0, s)))
-        return rc;
+    for (int j = 0; j <= corr.steps; ++j) {
+        // the first set-up of the step advances the device timestep; a corrector's re-evaluation reads it (t_cur)
+        if ((rc = j == 0 ? arreau_launch_prep(m, d_frac, d_lengths, d_angles, nullptr, d_off, B, N, w.lattice, w.cart, w.batch, w.cvec, s,
+                                              w.t_next, w.t_cur, 0, next_t)
+                         : arreau_launch_prep(m, d_frac, d_lengths, d_angles, w.t_cur, d_off, B, N, w.lattice, w.cart, w.batch, w.cvec, s)))
+            return rc;
+        if ((rc = run_network(m, w, false, w.deg, w.src, w.dir, w.dist, d_frac, d_types, d_off, B, N, w.eps, w.logits,
+                              pool_in_update ? nullptr : w.len0, s)))
+            return rc;
+        if (j < corr.steps &&
+            (rc = arreau_launch_corrector(m, d_frac, w.t_cur, d_off, B, N, w.eps, nullptr, seed, (uint32_t)j, corr.snr, cond, s)))
+            return rc;
+    }
     return arreau_launch_reverse(m, d_frac, d_types, d_lengths, d_angles, w.t_cur, d_off, B, N, w.eps, w.logits, w.len0,
                                  StepNoiseSrc{nullptr, nullptr, nullptr, seed}, d_const_types, d_lattice, s, d_fixed_lengths,
                                  pool_in_update ? w.gs : nullptr, w.batch, nullptr, nullptr, cond, sched);
@@ -349,6 +370,23 @@ extern "C" int arreau_sample_loop_scheduled(arreau_model* m, float* d_frac, int3
                                             const float* d_fixed_lengths, float* d_lattice, void* d_workspace, size_t workspace_bytes,
                                             int32_t use_graph, const arreau_sample_condition* condition,
                                             const arreau_sample_schedule* schedule, void* stream) {
+    return arreau_sample_loop_corrected(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, t_start, n_steps, seed, d_const_types,
+                                        d_fixed_lengths, d_lattice, d_workspace, workspace_bytes, use_graph, condition, schedule, nullptr,
+                                        stream);
+}
+
+extern "C" int arreau_sample_loop_corrected(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths,
+                                            const float* d_angles, const int32_t* d_off, int32_t B, int32_t N, int32_t t_start,
+                                            int32_t n_steps, uint64_t seed, const int32_t* d_const_types,
+                                            const float* d_fixed_lengths, float* d_lattice, void* d_workspace, size_t workspace_bytes,
+                                            int32_t use_graph, const arreau_sample_condition* condition,
+                                            const arreau_sample_schedule* schedule, const arreau_corrector* corrector, void* stream) {
+    if (corrector) {
+        const int rc = arreau_corrector_check(corrector->steps, corrector->snr, "arreau_sample_loop_corrected");
+        if (rc) return rc;
+    }
+    // NULL and steps == 0 are the same loop (and the same graph key): the snr is then not read
+    const CorrectorDev corr = (corrector && corrector->steps > 0) ? CorrectorDev{corrector->steps, corrector->snr} : CorrectorDev{0, 0.0f};
     ARREAU_REQUIRE(m && d_frac && d_types && d_lengths && d_angles && d_off && d_lattice, "arreau_sample_loop: null pointer");
     ARREAU_REQUIRE(B >= 1 && N >= 0 && n_steps >= 0, "arreau_sample_loop: bad size");
     ARREAU_REQUIRE(!m->packed_stale || arreau_general_path(m),
@@ -391,7 +429,7 @@ extern "C" int arreau_sample_loop_scheduled(arreau_model* m, float* d_frac, int3
     }
     if (!use_graph || n_steps < 3) {
         for (int i = 0; i < n_steps; ++i)
-            if ((rc = enqueue_sample_step(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types, d_fixed_lengths, d_lattice, w, s, no_prep, cond, sched)))
+            if ((rc = enqueue_sample_step(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types, d_fixed_lengths, d_lattice, w, s, no_prep, cond, sched, corr)))
                 return rc;
         return ARREAU_OK;
     }
@@ -415,10 +453,12 @@ extern "C" int arreau_sample_loop_scheduled(arreau_model* m, float* d_frac, int3
     // The executable graph is kept with the model and reused while the next call names the same buffers, sizes and seed
     // (a sampler drawing sub-batch after sub-batch through the caching allocator does): capture + instantiation, about
     // 2 ms, are then paid once.  The timestep is not part of the graph (it lives in t_next / t_cur, set above).  The condition's
-    // pointers are kernel arguments of the capture: another condition is another graph; so are the schedule's table and clip.
-    uint32_t clip_bits = 0;
+    // pointers are kernel arguments of the capture: another condition is another graph; so are the schedule's table and clip,
+    // and the corrector's step count and snr.
+    uint32_t clip_bits = 0, snr_bits = 0;
     memcpy(&clip_bits, &sched_dev.clipmax, sizeof(clip_bits));
-    const uint64_t key[20] = {(uint64_t)d_frac, (uint64_t)d_types, (uint64_t)d_lengths, (uint64_t)d_angles, (uint64_t)d_off,
+    memcpy(&snr_bits, &corr.snr, sizeof(snr_bits));
+    const uint64_t key[21] = {(uint64_t)d_frac, (uint64_t)d_types, (uint64_t)d_lengths, (uint64_t)d_angles, (uint64_t)d_off,
                               ((uint64_t)(uint32_t)B << 32) | (uint32_t)N, seed, (uint64_t)d_const_types, (uint64_t)d_fixed_lengths,
                               (uint64_t)d_lattice, (uint64_t)d_workspace,
                               ((uint64_t)(uint32_t)(m->edge_variant | (no_prep ? 0x10000 : 0) |
@@ -430,19 +470,19 @@ extern "C" int arreau_sample_loop_scheduled(arreau_model* m, float* d_frac, int3
                                                     ((m->conv_variant & 3) << 20)) << 32) | (uint32_t)m->mlp_variant,
                               (uint64_t)cond_dev.x0, (uint64_t)cond_dev.pos_mask, (uint64_t)cond_dev.a0, (uint64_t)cond_dev.type_mask,
                               (uint64_t)cond_dev.l0, (uint64_t)cond_dev.len_mask, (uint64_t)sched_dev.next,
-                              ((uint64_t)(schedule ? 1 : 0) << 32) | clip_bits};
+                              ((uint64_t)(schedule ? 1 : 0) << 32) | clip_bits, ((uint64_t)(uint32_t)corr.steps << 32) | snr_bits};
     hipGraphExec_t exec = (hipGraphExec_t)m->retired_graph;
     int first_replay = 0;
     hipError_t e = hipSuccess;
     static_assert(sizeof(key) == sizeof(m->graph_key), "graph key size");
     if (!exec || memcmp(key, m->graph_key, sizeof(key)) != 0) {
         // The first step runs eagerly (it also forces lazy module loading, which must not happen inside a capture).
-        if ((rc = enqueue_sample_step(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types, d_fixed_lengths, d_lattice, w, s, no_prep, cond, sched)))
+        if ((rc = enqueue_sample_step(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types, d_fixed_lengths, d_lattice, w, s, no_prep, cond, sched, corr)))
             return rc;
         first_replay = 1;
         hipGraph_t graph = nullptr;
         ARREAU_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        rc = enqueue_sample_step(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types, d_fixed_lengths, d_lattice, w, s, no_prep, cond, sched);
+        rc = enqueue_sample_step(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types, d_fixed_lengths, d_lattice, w, s, no_prep, cond, sched, corr);
         e = hipStreamEndCapture(s, &graph);
         if (rc) {
             if (graph) (void)hipGraphDestroy(graph);

@@ -136,7 +136,7 @@ int arreau_launch_neighbor(const float* cart, const float* lattice, const int32_
 int arreau_launch_neighbor_embed(const arreau_model* m, const float* cart, const float* lattice, const int32_t* offsets,
                                  const int32_t* batch, int B, int N, int32_t* deg, int32_t* src, int32_t* cell, float* dir,
                                  float* dist, const float* frac, const int32_t* types, const float* cvec, float* x0, hipStream_t s,
-                                 int32_t* tick, const int32_t* next_t) {
+                                 int32_t* tick, const int32_t* next_t, bool advance) {
     if (N <= 0 && tick == nullptr) return ARREAU_OK;
     ARREAU_REQUIRE(batch != nullptr, "neighbour list + embedding: the atom -> crystal map is required");
     const float r2 = (float)((double)m->cfg.radius * (double)m->cfg.radius);
@@ -147,11 +147,14 @@ int arreau_launch_neighbor_embed(const arreau_model* m, const float* cart, const
     }
     const unsigned embed_blocks = (unsigned)((pairs + 255) / 256), nbr_blocks = (unsigned)((N + 3) / 4);
     if (tick != nullptr) {
-        // sampling loop: positions from `frac` (the `cart` argument is not read), every crystal's timestep advanced
-        const unsigned tick_blocks = (unsigned)((B + 255) / 256);
+        // sampling loop: positions from `frac` (the `cart` argument is not read), every crystal's timestep advanced -- or,
+        // for the re-evaluations of a predictor-corrector step at the same timestep, none (an empty tick range)
+        const unsigned tick_blocks = advance ? (unsigned)((B + 255) / 256) : 0u;
+        if (N <= 0 && !advance) return ARREAU_OK;
         const unsigned grid = embed_blocks + nbr_blocks > tick_blocks ? embed_blocks + nbr_blocks : tick_blocks;  // (extra workgroups only tick)
         ARREAU_LAUNCH(neighbor_embed_kernel<true>, dim3(grid), dim3(256), 0, s, embed_blocks, frac, lattice, offsets, batch, B, 0, N, r2,
-                      m->k, deg, src, cell, dir, dist, frac, types, cvec, m->ori, m->embT, m->S, m->C, x0, m->status, tick, 0, B, next_t, m->T);
+                      m->k, deg, src, cell, dir, dist, frac, types, cvec, m->ori, m->embT, m->S, m->C, x0, m->status, tick, 0, advance ? B : 0,
+                      next_t, m->T);
     } else {
         ARREAU_LAUNCH(neighbor_embed_kernel<false>, dim3(embed_blocks + nbr_blocks), dim3(256), 0, s, embed_blocks, cart, lattice, offsets,
                       batch, B, 0, N, r2, m->k, deg, src, cell, dir, dist, frac, types, cvec, m->ori, m->embT, m->S, m->C, x0, m->status,

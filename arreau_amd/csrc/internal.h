@@ -71,7 +71,7 @@ struct arreau_model {
     int packed_stale;        // 1 after arreau_model_update_train_weights: the sampling kernels' packed planes are out of date
     void* loop_stream;       // hipStream_t / hipEvent_t of arreau_sample_loop's graph mode (capture is not allowed on the
     void* loop_event;        //   legacy default stream callers usually pass); created on first use
-    uint64_t graph_key[20];  // what the cached executable graph of arreau_sample_loop was captured for
+    uint64_t graph_key[21];  // what the cached executable graph of arreau_sample_loop was captured for
     void* retired_graph;     // hipGraphExec_t of the last arreau_sample_loop (+ the stream it was launched on): destroyed,
     void* retired_stream;    //   after that stream has drained, by the next loop or by arreau_model_destroy
     int32_t* status;         // device word of sticky ARREAU_STATUS_* bits (written by the kernels with atomicOr)
@@ -235,6 +235,15 @@ struct StepScheduleDev {
     float clipmax;        // the VP schedule's beta clip (VP_lattice clipmax)
 };
 
+// Predictor-corrector sampling (arreau_sample_loop_corrected, arreau_corrector_step; the rule is stated in include/arreau_hip.h).
+// arreau_corrector_check: ARREAU_EINVAL unless 0 <= steps <= ARREAU_MAX_CORRECTOR_STEPS and (steps == 0 or snr finite and > 0).
+int arreau_corrector_check(int32_t steps, float snr, const char* who);
+// One corrector move per crystal at timestep d_t[b]: z from the caller's d_z_frac [N,3], or (d_z_frac null) the Philox draw
+// (seed, t, ARREAU_DRAW_Z_CORRECTOR, element, iter).  cond: only its position mask is read (null / no mask: every atom moves).
+int arreau_launch_corrector(const arreau_model* m, float* d_frac, const int32_t* d_t, const int32_t* d_off, int B, int N,
+                            const float* d_eps, const float* d_z_frac, uint64_t seed, uint32_t iter, float snr,
+                            const SampleConditionDev* cond, hipStream_t s);
+
 void arreau_train_ctx_destroy(struct arreau_train_ctx* t);
 // edge_variant value that selects the shape-general fp32 network (train_net.hip) for the whole evaluation
 #define ARREAU_VARIANT_GENERAL 5
@@ -289,7 +298,8 @@ int arreau_launch_neighbor_embed(const arreau_model* m, const float* cart, const
                                  const int32_t* batch, int B, int N, int32_t* deg, int32_t* src, int32_t* cell, float* dir,
                                  float* dist, const float* frac, const int32_t* types, const float* cvec, float* x0, hipStream_t s,
                                  int32_t* tick = nullptr /* sampling loop without a prep launch: see the kernel */,
-                                 const int32_t* next_t = nullptr /* respaced loop: tick[b] = next_t[tick[b]] */);
+                                 const int32_t* next_t = nullptr /* respaced loop: tick[b] = next_t[tick[b]] */,
+                                 bool advance = true /* false: the loop form without advancing tick (a corrector's re-evaluation) */);
 int arreau_launch_prep(const arreau_model* m, const float* frac, const float* lengths, const float* angles,
                        const int32_t* t, const int32_t* offsets, int B, int N, float* lattice, float* cart,
                        int32_t* batch, float* cvec, hipStream_t s, int32_t* t_next = nullptr, int32_t* t_cur = nullptr,

@@ -1,7 +1,8 @@
 // Counter-based random numbers for the in-kernel noise of the sampling loop: Philox4x32-10 (Salmon et al., SC'11;
 // checked against the Random123 known-answer vectors in tests/test_cabi_exports.py via arreau_philox_fill).
 // One call per drawn element, keyed by what the number is FOR, never by which thread draws it:
-//     counter = (element index, timestep, draw kind, 0),  key = the 64-bit seed
+//     counter = (element index, timestep, draw kind, word3),  key = the 64-bit seed
+// (word3 = 0 for every draw but the corrector's, whose iteration index it holds)
 // so the noise of (seed, timestep, kind, element) is the same whatever the batch composition, launch geometry or
 // replay mechanism (eager loop or hipGraph).  The three draws of a step (diffusion_helpers.py:193-197, :79; d3pm.py:206):
 #pragma once
@@ -13,6 +14,8 @@
 // conditioned sampling (arreau_sample_loop_conditioned): the forward-noising draws of the known components
 #define ARREAU_DRAW_Z_KNOWN_FRAC 3u     // randn [N,3]  VE_pbc.forward of a known position (diffusion_helpers.py:43-47)
 #define ARREAU_DRAW_Z_KNOWN_LENGTHS 4u  // randn [B,3]  VP_lattice.forward of a known length (diffusion_helpers.py:156-163)
+// predictor-corrector sampling (arreau_sample_loop_corrected): the Langevin noise of corrector iteration j, counter word3 = j
+#define ARREAU_DRAW_Z_CORRECTOR 5u      // randn [N,3]
 
 struct Philox4 { uint32_t x[4]; };
 
@@ -32,15 +35,15 @@ __host__ __device__ inline Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint3
 }
 
 // uniform in [0, 1) with 24 random bits (every value exactly representable; 1.0 cannot occur)
-__host__ __device__ inline float philox_uniform(uint64_t seed, uint32_t timestep, uint32_t kind, uint32_t element) {
-    const Philox4 r = philox4x32_10(element, timestep, kind, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
+__host__ __device__ inline float philox_uniform(uint64_t seed, uint32_t timestep, uint32_t kind, uint32_t element, uint32_t word3 = 0u) {
+    const Philox4 r = philox4x32_10(element, timestep, kind, word3, (uint32_t)seed, (uint32_t)(seed >> 32));
     return (float)(r.x[0] >> 8) * (1.0f / 16777216.0f);
 }
 
 #ifdef __HIPCC__
 // standard normal by Box-Muller from two words of one Philox call: u1 in (0, 1], u2 in [0, 1)
-__device__ inline float philox_normal(uint64_t seed, uint32_t timestep, uint32_t kind, uint32_t element) {
-    const Philox4 r = philox4x32_10(element, timestep, kind, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
+__device__ inline float philox_normal(uint64_t seed, uint32_t timestep, uint32_t kind, uint32_t element, uint32_t word3 = 0u) {
+    const Philox4 r = philox4x32_10(element, timestep, kind, word3, (uint32_t)seed, (uint32_t)(seed >> 32));
     const float u1 = ((float)(r.x[0] >> 8) + 1.0f) * (1.0f / 16777216.0f);
     const float u2 = (float)(r.x[1] >> 8) * (1.0f / 16777216.0f);
     return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);

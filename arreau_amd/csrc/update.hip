@@ -155,29 +155,36 @@ extern "C" int arreau_reverse_step_to(const arreau_model* m, float* d_frac, int3
                                  nullptr, nullptr, nullptr, nullptr, nullptr, &sched);
 }
 
-// The sampler's in-kernel noise, written out: out[i] = the draw (seed, timestep, kind, element i) -- standard normal for
-// kinds 0/1/3/4, uniform [0,1) for kind 2.  For tests (known-answer / statistics) and for reproducing a Philox trajectory
-// through arreau_reverse_step.
-__global__ void philox_fill_kernel(uint64_t seed, uint32_t timestep, uint32_t kind, int64_t n, float* __restrict__ out,
+// The sampler's in-kernel noise, written out: out[i] = the draw (seed, timestep, kind, element i, word3) -- standard normal for
+// kinds 0/1/3/4/5, uniform [0,1) for kind 2.  For tests (known-answer / statistics) and for reproducing a Philox trajectory
+// through arreau_reverse_step / arreau_corrector_step.
+__global__ void philox_fill_kernel(uint64_t seed, uint32_t timestep, uint32_t kind, uint32_t word3, int64_t n, float* __restrict__ out,
                                    uint32_t* __restrict__ raw) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     if (raw) {
-        const Philox4 r = philox4x32_10((uint32_t)i, timestep, kind, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
+        const Philox4 r = philox4x32_10((uint32_t)i, timestep, kind, word3, (uint32_t)seed, (uint32_t)(seed >> 32));
         for (int j = 0; j < 4; ++j) raw[4 * i + j] = r.x[j];
     }
-    if (out) out[i] = kind == ARREAU_DRAW_U_TYPES ? philox_uniform(seed, timestep, kind, (uint32_t)i)
-                                                  : philox_normal(seed, timestep, kind, (uint32_t)i);
+    if (out) out[i] = kind == ARREAU_DRAW_U_TYPES ? philox_uniform(seed, timestep, kind, (uint32_t)i, word3)
+                                                  : philox_normal(seed, timestep, kind, (uint32_t)i, word3);
+}
+
+extern "C" int arreau_philox_fill_word(uint64_t seed, int32_t timestep, int32_t kind, uint32_t word3, int64_t n, float* d_out,
+                                       uint32_t* d_raw, void* stream) {
+    ARREAU_REQUIRE((d_out || d_raw) && n >= 0 && kind >= 0 && kind <= (int32_t)ARREAU_DRAW_Z_CORRECTOR,
+                   "arreau_philox_fill_word: bad argument");
+    if (n == 0) return ARREAU_OK;
+    ARREAU_LAUNCH(philox_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, seed,
+                  (uint32_t)timestep, (uint32_t)kind, word3, n, d_out, d_raw);
+    ARREAU_CHECK_HIP(hipGetLastError());
+    return ARREAU_OK;
 }
 
 extern "C" int arreau_philox_fill(uint64_t seed, int32_t timestep, int32_t kind, int64_t n, float* d_out, uint32_t* d_raw,
                                   void* stream) {
     ARREAU_REQUIRE((d_out || d_raw) && n >= 0 && kind >= 0 && kind <= 4, "arreau_philox_fill: bad argument");
-    if (n == 0) return ARREAU_OK;
-    ARREAU_LAUNCH(philox_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, seed,
-                       (uint32_t)timestep, (uint32_t)kind, n, d_out, d_raw);
-    ARREAU_CHECK_HIP(hipGetLastError());
-    return ARREAU_OK;
+    return arreau_philox_fill_word(seed, timestep, kind, 0u, n, d_out, d_raw, stream);
 }
 
 // Conditioned sampling, rule 5 (include/arreau_hip.h): the known components of the initial state at tau = t_start, i.e. the

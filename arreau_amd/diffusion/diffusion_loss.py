@@ -11,6 +11,7 @@ import os
 import torch
 import torch.nn as nn
 
+from . import corrector as pc
 from . import respacing
 from .d3pm import D3PM
 from .diffusion_helpers import VE_pbc, VP_lattice, crystal_offsets, sample_bravais_angles
@@ -258,7 +259,8 @@ class DiffusionLoss(nn.Module):
                show_bonds: bool = False, constant_atoms: Optional[torch.Tensor] = None, noise: str = "philox",
                max_steps: Optional[int] = None, use_graph: Optional[bool] = None, seed: Optional[int] = None,
                fixed_cell: bool = False, condition=None, num_steps: Optional[int] = None,
-               timesteps: Optional[Sequence[int]] = None) -> SampleResult:
+               timesteps: Optional[Sequence[int]] = None, corrector_steps: int = 0,
+               corrector_snr: float = pc.DEFAULT_SNR) -> SampleResult:
         """diffusion_loss.py:276-377.  The initial state is drawn on the host exactly like the reference (numpy
         uniforms for the angles, then randn lengths, randn fractional coordinates from torch's global CPU generator).
         Per-step noise:
@@ -287,13 +289,20 @@ class DiffusionLoss(nn.Module):
         include/arreau_hip.h; arreau_sample_loop_scheduled / arreau_reverse_step_to).  The step at a visited timestep draws
         what a full run draws there.  `max_steps` keeps the schedule's first max_steps steps; frames follow the schedule
         (ALL: the visited multiples of 10, ALL_DETAILED: every visited timestep).  The full schedule T-1, ..., 1 given
-        explicitly is the plain loop bit for bit.  No claim on sample quality at a given number of steps is made."""
+        explicitly is the plain loop bit for bit.  No claim on sample quality at a given number of steps is made.
+        `corrector_steps` / `corrector_snr` (extension, every noise mode): predictor-corrector sampling -- M = corrector_steps
+        (0..16) Langevin moves on the positions at every visited timestep before its predictor step, each after a network
+        evaluation, with the SNR step-size rule r = corrector_snr (rules in include/arreau_hip.h; arreau_sample_loop_corrected).
+        philox: the moves run in the library loop, their noise is Philox kind 5; reference / device: arreau_corrector_step
+        with randn[N,3] from that mode's generator, drawn per move before the step's three predictor draws.  M = 0 is the
+        sampler without correctors bit for bit (and draws nothing extra).  No sample-quality claim is made."""
         frames = visualization_setting != VisualizationSetting.NONE
         if frames and not vis_name:
             raise ValueError("visualization_setting other than NONE needs vis_name (prefix of the frame files)")
         if noise not in ("philox", "device", "reference"):
             raise ValueError("noise must be 'philox', 'device' or 'reference'")
         schedule = respacing.resolve_schedule(self.T, num_steps=num_steps, timesteps=timesteps)  # None: every timestep
+        corrector_steps, corrector_snr = pc.check_corrector(corrector_steps, corrector_snr)
         if condition is not None:  # validated before the engine is touched
             num_atoms_per_sample, num_samples_in_batch = condition.resolve_batch(num_atoms_per_sample, num_samples_in_batch)
             condition.check_sampling(z_table, noise=noise, fixed_cell=fixed_cell, constant_species=constant_atoms is not None)
@@ -361,6 +370,8 @@ class DiffusionLoss(nn.Module):
             eng.condition_initial_state(frac_d, types_d, len_d, t_first, seed, cond_d)
             init_state = (frac_d.clone(), types_d.clone(), len_d.clone())
 
+        corrector = (corrector_steps, corrector_snr) if corrector_steps > 0 else None
+
         def run_loop(use_graph):
             if noise == "philox":
                 if use_graph is None:
@@ -379,7 +390,7 @@ class DiffusionLoss(nn.Module):
                     if end > start:
                         eng.sample_loop(frac_d, types_d, len_d, ang_d, off_d, steps[start], end - start, seed, const_d, lattice_d,
                                         use_graph=bool(use_graph), fixed_lengths=fixed, condition=cond_d, next_table=next_d,
-                                        lattice_clipmax=clipmax)
+                                        lattice_clipmax=clipmax, corrector=corrector)
                         start = end
                     if j is not None:
                         vis_crystal_during_sampling(z_table, types_d.cpu().numpy(), lattice_d.cpu().numpy(),
@@ -390,6 +401,10 @@ class DiffusionLoss(nn.Module):
                 for timestep in steps:
                     t_d.fill_(timestep)
                     eps, logits, len0 = eng.predict_scores(frac_d, types_d, len_d, ang_d, t_d, off_d)
+                    for _ in range(corrector_steps):  # predictor-corrector: the moves at t, each followed by a new evaluation
+                        z_c = torch.randn((N, 3), **f32) if noise == "device" else torch.randn([N, 3], dtype=dt).to(**f32)
+                        eng.corrector_step(frac_d, t_d, off_d, eps, z_c, corrector_snr)
+                        eps, logits, len0 = eng.predict_scores(frac_d, types_d, len_d, ang_d, t_d, off_d)
                     if noise == "device":
                         z_l = torch.randn((B, 3), **f32)
                         z_f = torch.randn((N, 3), **f32)

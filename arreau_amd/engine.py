@@ -191,24 +191,38 @@ class HipEngine:
         return logits, vec_out, gscalar
 
     def sample_loop(self, frac, types, lengths, angles, offsets, t_start, n_steps, seed, const_types, lattice_out,
-                    use_graph=False, fixed_lengths=None, condition=None, next_table=None, lattice_clipmax=0.999):
+                    use_graph=False, fixed_lengths=None, condition=None, next_table=None, lattice_clipmax=0.999, corrector=None):
         """n_steps iterations of the sampling loop in one library call (arreau_sample_loop): in-place update of
         (frac, types, lengths); Philox noise keyed by (seed, timestep, draw, element).  `condition`: the device arrays of a
         conditioned run (SampleCondition.device_arrays: x0, pos_mask, a0, type_mask, l0, len_mask; None entries allowed),
         through arreau_sample_loop_conditioned.  `next_table`: a respaced run (arreau_sample_loop_scheduled): the device
-        int32 [T+1] table of respacing.next_table, with VP_lattice's clipmax; t_start is then a scheduled timestep."""
+        int32 [T+1] table of respacing.next_table, with VP_lattice's clipmax; t_start is then a scheduled timestep.
+        `corrector`: (steps, snr) -- predictor-corrector sampling (arreau_sample_loop_corrected): `steps` Langevin corrector
+        moves on the positions before every step's predictor; None is the loop without them."""
+        if corrector is not None:
+            from .diffusion.corrector import check_corrector
+            corrector = check_corrector(*corrector)
         N, B = frac.shape[0], lengths.shape[0]
         ws = self.workspace(N, B)
         args = (self._handle, _hip.ptr(frac), _hip.ptr(types), _hip.ptr(lengths), _hip.ptr(angles), _hip.ptr(offsets), B, N,
                 int(t_start), int(n_steps), int(seed) & (2 ** 64 - 1), _hip.ptr(const_types), _hip.ptr(fixed_lengths),
                 _hip.ptr(lattice_out), _hip.ptr(ws), ws.numel(), int(bool(use_graph)))
+        sched = None
         if next_table is not None:
             T = int(self.cfg.num_timesteps)
             if (tuple(next_table.shape) != (T + 1,) or next_table.dtype != torch.int32 or next_table.device != self.device
                     or not next_table.is_contiguous()):
                 raise ValueError(f"next_table must be a contiguous int32 tensor of shape ({T + 1},) on {self.device}")
-            cond = self._condition_struct(condition, N, B) if condition is not None else None
             sched = _hip.SampleScheduleC(_hip.ptr(next_table).value, float(lattice_clipmax))
+        if corrector is not None:
+            cond = self._condition_struct(condition, N, B) if condition is not None else None
+            corr = _hip.CorrectorC(corrector[0], corrector[1])
+            _hip.check(_hip.lib().arreau_sample_loop_corrected(*args, ctypes.byref(cond) if cond is not None else None,
+                                                               ctypes.byref(sched) if sched is not None else None,
+                                                               ctypes.byref(corr), _hip.stream_ptr(self.device)),
+                       "arreau_sample_loop_corrected")
+        elif sched is not None:
+            cond = self._condition_struct(condition, N, B) if condition is not None else None
             _hip.check(_hip.lib().arreau_sample_loop_scheduled(*args, ctypes.byref(cond) if cond is not None else None,
                                                                ctypes.byref(sched), _hip.stream_ptr(self.device)),
                        "arreau_sample_loop_scheduled")
@@ -253,6 +267,28 @@ class HipEngine:
         _hip.check(_hip.lib().arreau_philox_fill(int(seed) & (2 ** 64 - 1), int(timestep), int(kind), int(n), _hip.ptr(out),
                                                  _hip.ptr(words), _hip.stream_ptr(self.device)), "arreau_philox_fill")
         return (out, words) if raw else out
+
+    def philox_fill_word(self, seed, timestep, kind, word3, n, raw=False):
+        """arreau_philox_fill with the counter's fourth word (arreau_philox_fill_word): kind 5 with word3 = j is the Langevin
+        noise of the loop's j-th corrector move at `timestep`."""
+        out = torch.empty(n, device=self.device, dtype=torch.float32)
+        words = torch.empty((n, 4), device=self.device, dtype=torch.int32) if raw else None
+        _hip.check(_hip.lib().arreau_philox_fill_word(int(seed) & (2 ** 64 - 1), int(timestep), int(kind), int(word3) & (2 ** 32 - 1),
+                                                      int(n), _hip.ptr(out), _hip.ptr(words), _hip.stream_ptr(self.device)),
+                   "arreau_philox_fill_word")
+        return (out, words) if raw else out
+
+    def corrector_step(self, frac, t_crystal, offsets, eps, z_frac, snr, condition=None):
+        """One Langevin corrector move on frac [N,3] in place (arreau_corrector_step): per crystal at timestep t_crystal[b],
+        from the network's eps [N,3] and the caller's standard-normal z_frac [N,3].  `condition`: as in sample_loop; its
+        position mask keeps those atoms fixed and out of the norms."""
+        from .diffusion.corrector import check_corrector
+        _, snr = check_corrector(1, snr)
+        N, B = frac.shape[0], t_crystal.shape[0]
+        cond = self._condition_struct(condition, N, B) if condition is not None else None
+        _hip.check(_hip.lib().arreau_corrector_step(
+            self._handle, _hip.ptr(frac), _hip.ptr(t_crystal), _hip.ptr(offsets), B, N, _hip.ptr(eps), _hip.ptr(z_frac), snr,
+            ctypes.byref(cond) if cond is not None else None, _hip.stream_ptr(self.device)), "arreau_corrector_step")
 
     def diffusion_noise(self, frac0, types0, lattice0, t_crystal, offsets, z_frac, u_types, z_lengths):
         """Forward noising of a clean batch (arreau_diffusion_noise).  Returns dict(noisy_frac, target_eps, noisy_types,

@@ -13,6 +13,9 @@ Conditioned generation (structure completion): `--template crystals.npz` (the wi
 fixes those components wherever the file has no mask for them; `--samples_per_template K` tiles the templates K times.
 
 Respaced sampling: `--num_steps K` runs K evenly spaced denoising steps instead of every timestep (DiffusionLoss.sample).
+
+Predictor-corrector sampling: `--corrector_steps M` runs M Langevin corrector moves on the positions before every denoising
+step, with the step-size rule's `--corrector_snr` (default 0.16; DiffusionLoss.sample).
 """
 import argparse
 import os
@@ -122,6 +125,22 @@ def save_sample_results(crystals: SampleResult, filename: str):
     return save_sample_results_to_hdf5(crystals, filename)
 
 
+def _corrector_steps_arg(text: str) -> int:
+    from .diffusion.corrector import check_corrector
+    try:
+        return check_corrector(int(text), 1.0)[0]
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
+def _corrector_snr_arg(text: str) -> float:
+    from .diffusion.corrector import check_corrector
+    try:
+        return check_corrector(1, float(text))[1]
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--model_path", type=str, required=True)
@@ -137,6 +156,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--samples_per_template", type=int, default=1, help="the templates are tiled this many times")
     ap.add_argument("--num_steps", type=int, default=None,
                     help="respaced sampling: this many evenly spaced denoising steps (2..T-1; default: every timestep)")
+    ap.add_argument("--corrector_steps", type=_corrector_steps_arg, default=0,
+                    help="predictor-corrector sampling: Langevin corrector moves on the positions per denoising step (0..16)")
+    ap.add_argument("--corrector_snr", type=_corrector_snr_arg, default=0.16,
+                    help="signal-to-noise ratio of the corrector's step-size rule (finite, > 0)")
     return ap
 
 
@@ -175,12 +198,14 @@ def main():
 
     def fn(n, b, cond=None):
         if not lock_path:
-            return model.sample(n, b, VisualizationSetting.NONE, False, condition=cond, num_steps=args.num_steps)
+            return model.sample(n, b, VisualizationSetting.NONE, False, condition=cond, num_steps=args.num_steps,
+                                corrector_steps=args.corrector_steps, corrector_snr=args.corrector_snr)
         import fcntl
         with open(lock_path, "a") as lock:
             fcntl.flock(lock, fcntl.LOCK_EX)
             try:
-                out = model.sample(n, b, VisualizationSetting.NONE, False, condition=cond, num_steps=args.num_steps)
+                out = model.sample(n, b, VisualizationSetting.NONE, False, condition=cond, num_steps=args.num_steps,
+                                corrector_steps=args.corrector_steps, corrector_snr=args.corrector_snr)
                 torch.cuda.synchronize()
                 return out
             finally:

@@ -371,12 +371,59 @@ int arreau_reverse_step_to(const arreau_model* model,
                            const float* d_z_lattice, const float* d_z_frac, const float* d_u_types,
                            float* d_lattice, float lattice_clipmax, void* stream);
 
+/* ---- predictor-corrector sampling (Langevin corrector steps on positions) ----------------------------------------
+ * Song et al. 2021 ("Score-Based Generative Modeling through SDEs", Algorithms 2 and 5): at every visited timestep t, M
+ * Langevin "corrector" moves on the fractional coordinates come before the predictor step that leaves t.  The reference has
+ * no corrector; this rule is the library's own.  Lengths, angles and species are never moved by a corrector.
+ *   1. score: the network's eps for positions is trained on the wrapped displacement VE_pbc.forward returns (std sig_t;
+ *      diffusion/diffusion_helpers.py:43-63, the loss at diffusion_loss.py:94-110) and the predictor moves against it, so the
+ *      score estimate is g = -eps / sig_t^2, sig = ve_sigmas.
+ *   2. step size (SNR rule, Algorithm 5), per crystal b: gamma_b = 2 (r |z_b| / |g_b|)^2, the norms over the 3 n components
+ *      of the atoms the corrector moves in b; then x <- remainder(x + gamma_b g + sqrt(2 gamma_b) z, 1).  Evaluated as
+ *      x <- remainder(x - a eps + c z, 1) with q = |z| / |eps|, a = 2 r^2 sig_t^2 q^2, c = 2 r sig_t^2 q (no quantity of size
+ *      1 / sig^2 is formed).  A crystal whose |eps|^2 is 0 or not finite (or whose a, c are not finite) is left unmoved.
+ *      r = snr (0.16 is Song et al.'s VE setting).
+ *   3. order: "the step at t" = M corrections at t (each after a full network evaluation on the current state at t), then the
+ *      predictor step that leaves t, on the network evaluated after the last correction.  Segment, frame and graph-replay
+ *      boundaries stay between steps.  No corrector runs on the final state.
+ *   4. noise: z = Philox normal (seed, t, kind 5, element 3 i + d) with the iteration index j = 0..M-1 in the counter's fourth
+ *      word (0 for every other draw), so the predictor draws exactly what an uncorrected run draws.
+ *   5. respacing: corrections run at every scheduled t.  Conditioning: known positions are not moved and are left out of the
+ *      norms (a crystal with every position known is untouched); they keep the values the conditioning rules give them.
+ *   6. limits: 0 <= M <= ARREAU_MAX_CORRECTOR_STEPS, and snr finite and > 0 when M > 0 (ARREAU_EINVAL otherwise). */
+#define ARREAU_MAX_CORRECTOR_STEPS 16
+typedef struct {
+    int32_t steps; /* M */
+    float snr;     /* r */
+} arreau_corrector;
+
+/* arreau_sample_loop_scheduled with M corrector steps per visited timestep (rules above; `corrector` is a host pointer, NULL or
+ * steps == 0 = arreau_sample_loop_scheduled).  M and the snr are part of what a cached hipGraph was captured for. */
+int arreau_sample_loop_corrected(arreau_model* model, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                                 const int32_t* d_crystal_offsets, int32_t B, int32_t N, int32_t t_start, int32_t n_steps,
+                                 uint64_t seed, const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice,
+                                 void* d_workspace, size_t workspace_bytes, int32_t use_graph,
+                                 const arreau_sample_condition* cond, const arreau_sample_schedule* schedule,
+                                 const arreau_corrector* corrector, void* stream);
+
+/* One corrector move (rule 2) with the caller's noise d_z_frac[N,3], at timestep d_t[b] (1..T; another value is clamped and
+ * sets ARREAU_STATUS_BAD_TIMESTEP) per crystal, in place on d_frac[N,3], from the network's d_eps[N,3]: for the loops with
+ * host-side noise and for parity tests.  `condition` (host pointer, may be NULL): its position mask keeps those atoms unmoved
+ * and out of the norms.  Fed arreau_philox_fill_word(seed, t, 5, j, ...), it is the loop's j-th correction bit for bit. */
+int arreau_corrector_step(const arreau_model* model, float* d_frac, const int32_t* d_t, const int32_t* d_crystal_offsets,
+                          int32_t B, int32_t N, const float* d_eps, const float* d_z_frac, float snr,
+                          const arreau_sample_condition* condition, void* stream);
+
 /* The sampler's in-kernel noise written out: d_out[i] = draw (seed, timestep, kind, element i) -- standard normal for
  * kind 0 (z_lattice), 1 (z_frac), 3 (known positions) and 4 (known lengths), uniform [0,1) for kind 2 (u_types); d_raw[4 i .. 4 i + 3] (may be NULL) = the raw
  * Philox4x32-10 words of counter (i, timestep, kind, 0), key = seed.  Feeding these arrays to arreau_reverse_step
- * reproduces arreau_sample_loop's update bit for bit. */
+ * reproduces arreau_sample_loop's update bit for bit.  Kinds above 4 are rejected (arreau_philox_fill_word). */
 int arreau_philox_fill(uint64_t seed, int32_t timestep, int32_t kind, int64_t n, float* d_out, uint32_t* d_raw,
                        void* stream);
+/* arreau_philox_fill with the counter's fourth word given: counter (i, timestep, kind, word3).  Kinds 0..5; kind 5 (the
+ * corrector's Langevin noise, standard normal) with word3 = j is what the loop's j-th correction at `timestep` draws. */
+int arreau_philox_fill_word(uint64_t seed, int32_t timestep, int32_t kind, uint32_t word3, int64_t n, float* d_out,
+                            uint32_t* d_raw, void* stream);
 
 /* ---- score-matching training loss, forward part (BASELINE config 5) ------------------------------------------ */
 
