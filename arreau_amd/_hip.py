@@ -27,6 +27,7 @@ EXPORTS = [
     "arreau_sample_loop_conditioned", "arreau_condition_initial_state",
     "arreau_sample_loop_scheduled", "arreau_reverse_step_to",
     "arreau_sample_loop_corrected", "arreau_corrector_step", "arreau_philox_fill_word",
+    "arreau_sample_loop_resampled", "arreau_resample_jump",
 ]
 
 STATUS_NONFINITE, STATUS_BAD_TIMESTEP, STATUS_BAD_TYPE = 1, 2, 4
@@ -63,6 +64,11 @@ class SampleScheduleC(Structure):
 class CorrectorC(Structure):
     """arreau_corrector: M Langevin corrector steps per visited timestep and the SNR of their step-size rule."""
     _fields_ = [("steps", c_int32), ("snr", ctypes.c_float)]
+
+
+class ResamplingC(Structure):
+    """arreau_resampling: R passes per block of J steps, and the host copy of the schedule (block tops and bottoms)."""
+    _fields_ = [("passes", c_int32), ("jump_length", c_int32), ("timesteps", POINTER(c_int32)), ("n_timesteps", c_int32)]
 
 
 class Config(Structure):
@@ -145,6 +151,11 @@ def lib():
                                                                                                    POINTER(SampleConditionC), c_void_p]
         L.arreau_philox_fill_word.argtypes = [ctypes.c_uint64, c_int32, c_int32, ctypes.c_uint32, c_int64, c_void_p, c_void_p,
                                               c_void_p]
+    if hasattr(L, "arreau_sample_loop_resampled") or not os.environ.get("ARREAU_HIP_LIB"):  # (an older build under test)
+        L.arreau_sample_loop_resampled.argtypes = (L.arreau_sample_loop_corrected.argtypes[:-1] +
+                                                   [POINTER(ResamplingC), c_void_p])
+        L.arreau_resample_jump.argtypes = [c_void_p] * 8 + [c_int32, c_int32] + [c_void_p] * 5 + [POINTER(SampleConditionC),
+                                                                                                   c_void_p, c_void_p]
     L.arreau_philox_fill.argtypes = [ctypes.c_uint64, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_void_p]
     L.arreau_train_forward.argtypes = [c_void_p] * 7 + [c_int32, c_int32] + [c_void_p] * 4
     L.arreau_train_backward.argtypes = [c_void_p] * 4 + [POINTER(StateDict), c_void_p]

@@ -26,6 +26,7 @@ struct Workspace {
     float *lattice, *cart, *cvec, *dir, *dist, *kbuf, *xa, *xb, *xc, *xbar, *vsum, *gs;
     float *eps, *logits, *len0;  // network outputs of the sampling loop (arreau_sample_loop)
     int32_t *batch, *deg, *src, *cell, *t_next, *t_cur;
+    int32_t* pass;  // the resampled loop's pass index (arreau_sample_loop_resampled)
     size_t bytes;
 };
 
@@ -54,6 +55,7 @@ Workspace carve(const arreau_config* cfg, int64_t N, int64_t B, void* base, size
     w.len0 = c.take<float>(B * 3);
     w.t_next = c.take<int32_t>(B);
     w.t_cur = c.take<int32_t>(B);
+    w.pass = c.take<int32_t>(1);
     w.bytes = (c.off + 255) & ~(size_t)255;
     return w;
 }
@@ -308,7 +310,8 @@ struct CorrectorDev {
 int enqueue_sample_step(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
                         const int32_t* d_off, int B, int N, uint64_t seed, const int32_t* d_const_types,
                         const float* d_fixed_lengths, float* d_lattice, const Workspace& w, hipStream_t s, bool no_prep,
-                        const SampleConditionDev* cond, const StepScheduleDev* sched, CorrectorDev corr) {
+                        const SampleConditionDev* cond, const StepScheduleDev* sched, CorrectorDev corr,
+                        const int32_t* pass /* resampled loop: the device word of the pass index (RESAMPLE instances), or null */) {
     int rc;
     const int32_t* next_t = sched ? sched->next : nullptr;  // respaced loop: the device timestep follows the table
     if (no_prep) {
@@ -319,12 +322,12 @@ int enqueue_sample_step(const arreau_model* m, float* d_frac, int32_t* d_types, 
             if ((rc = run_edge_kernel(m, w.dir, w.dist, w.deg, w, N, s))) return rc;
             if ((rc = run_layers_and_readout(m, w, w.deg, w.src, d_off, B, N, w.eps, w.logits, nullptr, s))) return rc;
             if (j < corr.steps &&
-                (rc = arreau_launch_corrector(m, d_frac, w.t_cur, d_off, B, N, w.eps, nullptr, seed, (uint32_t)j, corr.snr, cond, s)))
+                (rc = arreau_launch_corrector(m, d_frac, w.t_cur, d_off, B, N, w.eps, nullptr, seed, (uint32_t)j, corr.snr, cond, s, pass)))
                 return rc;
         }
         return arreau_launch_reverse(m, d_frac, d_types, d_lengths, d_angles, w.t_cur, d_off, B, N, w.eps, w.logits, w.len0,
                                      StepNoiseSrc{nullptr, nullptr, nullptr, seed}, d_const_types, d_lattice, s, d_fixed_lengths,
-                                     w.gs, w.batch, w.lattice, w.cvec, cond, sched);
+                                     w.gs, w.batch, w.lattice, w.cvec, cond, sched, pass);
     }
     // fused kernels: the per-crystal pooling of the lattice read-out happens inside the lattice update (no launch of its own)
     const bool pool_in_update = !arreau_general_path(m);
@@ -338,13 +341,24 @@ int enqueue_sample_step(const arreau_model* m, float* d_frac, int32_t* d_types, 
                               pool_in_update ? nullptr : w.len0, s)))
             return rc;
         if (j < corr.steps &&
-            (rc = arreau_launch_corrector(m, d_frac, w.t_cur, d_off, B, N, w.eps, nullptr, seed, (uint32_t)j, corr.snr, cond, s)))
+            (rc = arreau_launch_corrector(m, d_frac, w.t_cur, d_off, B, N, w.eps, nullptr, seed, (uint32_t)j, corr.snr, cond, s, pass)))
             return rc;
     }
     return arreau_launch_reverse(m, d_frac, d_types, d_lengths, d_angles, w.t_cur, d_off, B, N, w.eps, w.logits, w.len0,
                                  StepNoiseSrc{nullptr, nullptr, nullptr, seed}, d_const_types, d_lattice, s, d_fixed_lengths,
-                                 pool_in_update ? w.gs : nullptr, w.batch, nullptr, nullptr, cond, sched);
+                                 pool_in_update ? w.gs : nullptr, w.batch, nullptr, nullptr, cond, sched, pass);
 }
+
+// RePaint resampling (arreau_sample_loop_resampled): the blocks of one loop call, from the host's list of the steps it visits.
+// Block k runs steps first .. first + count - 1 (indices into the visited list), R times; passes 1..R-1 start with the jump
+// bottom -> top.
+struct ResampleBlock {
+    int first, count, top, bottom;
+};
+struct ResamplePlan {
+    int passes, jump;
+    std::vector<ResampleBlock> blocks;
+};
 }  // namespace
 
 extern "C" int arreau_sample_loop(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths,
@@ -375,12 +389,12 @@ extern "C" int arreau_sample_loop_scheduled(arreau_model* m, float* d_frac, int3
                                         stream);
 }
 
-extern "C" int arreau_sample_loop_corrected(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths,
-                                            const float* d_angles, const int32_t* d_off, int32_t B, int32_t N, int32_t t_start,
-                                            int32_t n_steps, uint64_t seed, const int32_t* d_const_types,
-                                            const float* d_fixed_lengths, float* d_lattice, void* d_workspace, size_t workspace_bytes,
-                                            int32_t use_graph, const arreau_sample_condition* condition,
-                                            const arreau_sample_schedule* schedule, const arreau_corrector* corrector, void* stream) {
+namespace {
+int sample_loop_impl(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles, const int32_t* d_off,
+                     int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed, const int32_t* d_const_types,
+                     const float* d_fixed_lengths, float* d_lattice, void* d_workspace, size_t workspace_bytes, int32_t use_graph,
+                     const arreau_sample_condition* condition, const arreau_sample_schedule* schedule, const arreau_corrector* corrector,
+                     const ResamplePlan* plan /* null: no resampling */, void* stream) {
     if (corrector) {
         const int rc = arreau_corrector_check(corrector->steps, corrector->snr, "arreau_sample_loop_corrected");
         if (rc) return rc;
@@ -427,83 +441,178 @@ extern "C" int arreau_sample_loop_corrected(arreau_model* m, float* d_frac, int3
         ARREAU_LAUNCH(fill_i32_kernel, dim3((B + 255) / 256), dim3(256), 0, s, w.t_next, t_start, B);
         ARREAU_CHECK_HIP(hipGetLastError());
     }
-    if (!use_graph || n_steps < 3) {
-        for (int i = 0; i < n_steps; ++i)
-            if ((rc = enqueue_sample_step(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types, d_fixed_lengths, d_lattice, w, s, no_prep, cond, sched, corr)))
-                return rc;
-        return ARREAU_OK;
+    // steps run (every pass of every block counts)
+    int64_t n_runs = n_steps;
+    if (plan) {
+        n_runs = 0;
+        for (const ResampleBlock& bl : plan->blocks) n_runs += (int64_t)plan->passes * bl.count;
     }
-    // One step captured into a hipGraph and replayed: the timestep lives on the device (prep_kernel advances it), the noise
-    // is a function of (seed, timestep, element), so every replay is the next step of the same trajectory as the eager loop.
-    // Capture is not allowed on the legacy default stream (which is what callers usually pass), so the loop runs on a
-    // stream of the model's own, joined to the caller's stream by events on both sides: still no host synchronisation.
-    if (!m->loop_stream) {
-        hipStream_t ls = nullptr;
-        ARREAU_CHECK_HIP(hipStreamCreateWithFlags(&ls, hipStreamNonBlocking));
-        hipEvent_t ev = nullptr;
-        ARREAU_CHECK_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        m->loop_stream = (void*)ls;
-        m->loop_event = (void*)ev;
-    }
+    const bool graph_mode = use_graph && n_runs >= 3;
     hipStream_t user = s;
-    hipEvent_t ev = (hipEvent_t)m->loop_event;
-    s = (hipStream_t)m->loop_stream;
-    ARREAU_CHECK_HIP(hipEventRecord(ev, user));
-    ARREAU_CHECK_HIP(hipStreamWaitEvent(s, ev, 0));
-    // The executable graph is kept with the model and reused while the next call names the same buffers, sizes and seed
-    // (a sampler drawing sub-batch after sub-batch through the caching allocator does): capture + instantiation, about
-    // 2 ms, are then paid once.  The timestep is not part of the graph (it lives in t_next / t_cur, set above).  The condition's
-    // pointers are kernel arguments of the capture: another condition is another graph; so are the schedule's table and clip,
-    // and the corrector's step count and snr.
-    uint32_t clip_bits = 0, snr_bits = 0;
-    memcpy(&clip_bits, &sched_dev.clipmax, sizeof(clip_bits));
-    memcpy(&snr_bits, &corr.snr, sizeof(snr_bits));
-    const uint64_t key[21] = {(uint64_t)d_frac, (uint64_t)d_types, (uint64_t)d_lengths, (uint64_t)d_angles, (uint64_t)d_off,
-                              ((uint64_t)(uint32_t)B << 32) | (uint32_t)N, seed, (uint64_t)d_const_types, (uint64_t)d_fixed_lengths,
-                              (uint64_t)d_lattice, (uint64_t)d_workspace,
-                              ((uint64_t)(uint32_t)(m->edge_variant | (no_prep ? 0x10000 : 0) |
-                                                    // which kernels a capture holds also depends on switches read per call
-                                                    // (ARREAU_BASIS_MIN_RECEIVERS, ARREAU_FUSE_SMALL) and on the conv variant:
-                                                    // a changed switch must not replay the stale graph
-                                                    (arreau_basis_form(m, N) ? 0x20000 : 0) | (arreau_basis_fp8(m) ? 0x40000 : 0) | (arreau_cross_fp8(m) ? 0x400000 : 0) |
-                                                    (arreau_small_layer_fusable(m, N) ? 0x80000 : 0) |
-                                                    ((m->conv_variant & 3) << 20)) << 32) | (uint32_t)m->mlp_variant,
-                              (uint64_t)cond_dev.x0, (uint64_t)cond_dev.pos_mask, (uint64_t)cond_dev.a0, (uint64_t)cond_dev.type_mask,
-                              (uint64_t)cond_dev.l0, (uint64_t)cond_dev.len_mask, (uint64_t)sched_dev.next,
-                              ((uint64_t)(schedule ? 1 : 0) << 32) | clip_bits, ((uint64_t)(uint32_t)corr.steps << 32) | snr_bits};
-    hipGraphExec_t exec = (hipGraphExec_t)m->retired_graph;
-    int first_replay = 0;
-    hipError_t e = hipSuccess;
-    static_assert(sizeof(key) == sizeof(m->graph_key), "graph key size");
-    if (!exec || memcmp(key, m->graph_key, sizeof(key)) != 0) {
-        // The first step runs eagerly (it also forces lazy module loading, which must not happen inside a capture).
-        if ((rc = enqueue_sample_step(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types, d_fixed_lengths, d_lattice, w, s, no_prep, cond, sched, corr)))
-            return rc;
-        first_replay = 1;
-        hipGraph_t graph = nullptr;
-        ARREAU_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-        rc = enqueue_sample_step(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types, d_fixed_lengths, d_lattice, w, s, no_prep, cond, sched, corr);
-        e = hipStreamEndCapture(s, &graph);
-        if (rc) {
-            if (graph) (void)hipGraphDestroy(graph);
-            return rc;
+    hipEvent_t ev = nullptr;
+    uint64_t key[22] = {};
+    hipGraphExec_t exec = nullptr;
+    bool have_exec = false;
+    if (graph_mode) {
+        // One step captured into a hipGraph and replayed: the timestep lives on the device (prep_kernel advances it), the noise
+        // is a function of (seed, timestep, element) -- and in a resampled loop of the pass index, another device word -- so every
+        // replay is the next step of the same trajectory as the eager loop.
+        // Capture is not allowed on the legacy default stream (which is what callers usually pass), so the loop runs on a
+        // stream of the model's own, joined to the caller's stream by events on both sides: still no host synchronisation.
+        if (!m->loop_stream) {
+            hipStream_t ls = nullptr;
+            ARREAU_CHECK_HIP(hipStreamCreateWithFlags(&ls, hipStreamNonBlocking));
+            hipEvent_t e0 = nullptr;
+            ARREAU_CHECK_HIP(hipEventCreateWithFlags(&e0, hipEventDisableTiming));
+            m->loop_stream = (void*)ls;
+            m->loop_event = (void*)e0;
         }
-        ARREAU_CHECK_HIP(e);
-        exec = nullptr;
-        e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        ARREAU_CHECK_HIP(e);
-        arreau_model_retire_graph(m, (void*)exec, (void*)s);  // takes ownership; frees the previous one after its stream drained
-        memcpy(m->graph_key, key, sizeof(key));
+        ev = (hipEvent_t)m->loop_event;
+        s = (hipStream_t)m->loop_stream;
+        ARREAU_CHECK_HIP(hipEventRecord(ev, user));
+        ARREAU_CHECK_HIP(hipStreamWaitEvent(s, ev, 0));
+        // The executable graph is kept with the model and reused while the next call names the same buffers, sizes and seed
+        // (a sampler drawing sub-batch after sub-batch through the caching allocator does): capture + instantiation, about
+        // 2 ms, are then paid once.  The timestep is not part of the graph (it lives in t_next / t_cur, set above).  The condition's
+        // pointers are kernel arguments of the capture: another condition is another graph; so are the schedule's table and clip,
+        // the corrector's step count and snr, and the resampling's R and J (a resampled step reads the pass word).
+        uint32_t clip_bits = 0, snr_bits = 0;
+        memcpy(&clip_bits, &sched_dev.clipmax, sizeof(clip_bits));
+        memcpy(&snr_bits, &corr.snr, sizeof(snr_bits));
+        const uint64_t k[22] = {(uint64_t)d_frac, (uint64_t)d_types, (uint64_t)d_lengths, (uint64_t)d_angles, (uint64_t)d_off,
+                                ((uint64_t)(uint32_t)B << 32) | (uint32_t)N, seed, (uint64_t)d_const_types, (uint64_t)d_fixed_lengths,
+                                (uint64_t)d_lattice, (uint64_t)d_workspace,
+                                ((uint64_t)(uint32_t)(m->edge_variant | (no_prep ? 0x10000 : 0) |
+                                                      // which kernels a capture holds also depends on switches read per call
+                                                      // (ARREAU_BASIS_MIN_RECEIVERS, ARREAU_FUSE_SMALL) and on the conv variant:
+                                                      // a changed switch must not replay the stale graph
+                                                      (arreau_basis_form(m, N) ? 0x20000 : 0) | (arreau_basis_fp8(m) ? 0x40000 : 0) | (arreau_cross_fp8(m) ? 0x400000 : 0) |
+                                                      (arreau_small_layer_fusable(m, N) ? 0x80000 : 0) |
+                                                      ((m->conv_variant & 3) << 20)) << 32) | (uint32_t)m->mlp_variant,
+                                (uint64_t)cond_dev.x0, (uint64_t)cond_dev.pos_mask, (uint64_t)cond_dev.a0, (uint64_t)cond_dev.type_mask,
+                                (uint64_t)cond_dev.l0, (uint64_t)cond_dev.len_mask, (uint64_t)sched_dev.next,
+                                ((uint64_t)(schedule ? 1 : 0) << 32) | clip_bits, ((uint64_t)(uint32_t)corr.steps << 32) | snr_bits,
+                                plan ? (((uint64_t)(uint32_t)plan->passes << 32) | (uint32_t)plan->jump) : 0};
+        static_assert(sizeof(k) == sizeof(m->graph_key), "graph key size");
+        memcpy(key, k, sizeof(k));
+        exec = (hipGraphExec_t)m->retired_graph;
+        have_exec = exec && memcmp(key, m->graph_key, sizeof(key)) == 0;
     }
-    for (int i = first_replay; i < n_steps; ++i) {
-        e = hipGraphLaunch(exec, s);
-        if (e != hipSuccess) break;
+    const int32_t* pass = plan ? w.pass : nullptr;
+    // one step of the trajectory: eager, or (graph mode) the first one eager and captured behind it, then replays
+    auto run_step = [&]() -> int {
+        int r;
+        if (!graph_mode || !have_exec) {
+            // (eager: the first step of a capture also forces lazy module loading, which must not happen inside a capture)
+            if ((r = enqueue_sample_step(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types, d_fixed_lengths,
+                                         d_lattice, w, s, no_prep, cond, sched, corr, pass)))
+                return r;
+            if (!graph_mode) return ARREAU_OK;
+            hipGraph_t graph = nullptr;
+            ARREAU_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+            r = enqueue_sample_step(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types, d_fixed_lengths, d_lattice,
+                                    w, s, no_prep, cond, sched, corr, pass);
+            hipError_t e = hipStreamEndCapture(s, &graph);
+            if (r) {
+                if (graph) (void)hipGraphDestroy(graph);
+                return r;
+            }
+            ARREAU_CHECK_HIP(e);
+            exec = nullptr;
+            e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+            (void)hipGraphDestroy(graph);
+            ARREAU_CHECK_HIP(e);
+            arreau_model_retire_graph(m, (void*)exec, (void*)s);  // takes ownership; frees the previous one after its stream drained
+            memcpy(m->graph_key, key, sizeof(key));
+            have_exec = true;
+            return ARREAU_OK;
+        }
+        ARREAU_CHECK_HIP(hipGraphLaunch(exec, s));
+        return ARREAU_OK;
+    };
+    if (!plan) {
+        for (int i = 0; i < n_steps; ++i)
+            if ((rc = run_step())) return rc;
+    } else {
+        // every block runs R passes; pass r >= 1 starts with the jump bottom -> top, which also sets the device timestep to the
+        // top, prepares the next step for it and sets the pass word to r; the word goes back to 0 after the block
+        const JumpLoopDev loop{w.lattice, w.cvec, w.t_next, w.t_cur, w.pass};
+        ARREAU_LAUNCH(fill_i32_kernel, dim3(1), dim3(256), 0, s, w.pass, 0, 1);
+        ARREAU_CHECK_HIP(hipGetLastError());
+        for (const ResampleBlock& bl : plan->blocks) {
+            for (int r = 0; r < plan->passes; ++r) {
+                if (r > 0 &&
+                    (rc = arreau_launch_resample_jump(m, d_frac, d_types, d_lengths, d_angles, nullptr, nullptr, bl.bottom, bl.top, d_off,
+                                                      w.batch, B, N, nullptr, nullptr, nullptr, seed, (uint32_t)r, d_const_types,
+                                                      d_fixed_lengths, cond, d_lattice, &loop, s)))
+                    return rc;
+                for (int i = 0; i < bl.count; ++i)
+                    if ((rc = run_step())) return rc;
+            }
+            ARREAU_LAUNCH(fill_i32_kernel, dim3(1), dim3(256), 0, s, w.pass, 0, 1);
+            ARREAU_CHECK_HIP(hipGetLastError());
+        }
     }
-    if (e == hipSuccess) e = hipEventRecord(ev, s);
-    if (e == hipSuccess) e = hipStreamWaitEvent(user, ev, 0);  // the caller's stream continues after the loop
-    ARREAU_CHECK_HIP(e);
+    if (!graph_mode) return ARREAU_OK;
+    ARREAU_CHECK_HIP(hipEventRecord(ev, s));
+    ARREAU_CHECK_HIP(hipStreamWaitEvent(user, ev, 0));  // the caller's stream continues after the loop
     return ARREAU_OK;
+}
+}  // namespace
+
+extern "C" int arreau_sample_loop_corrected(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths,
+                                            const float* d_angles, const int32_t* d_off, int32_t B, int32_t N, int32_t t_start,
+                                            int32_t n_steps, uint64_t seed, const int32_t* d_const_types,
+                                            const float* d_fixed_lengths, float* d_lattice, void* d_workspace, size_t workspace_bytes,
+                                            int32_t use_graph, const arreau_sample_condition* condition,
+                                            const arreau_sample_schedule* schedule, const arreau_corrector* corrector, void* stream) {
+    return sample_loop_impl(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, t_start, n_steps, seed, d_const_types, d_fixed_lengths,
+                            d_lattice, d_workspace, workspace_bytes, use_graph, condition, schedule, corrector, nullptr, stream);
+}
+
+extern "C" int arreau_sample_loop_resampled(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths,
+                                            const float* d_angles, const int32_t* d_off, int32_t B, int32_t N, int32_t t_start,
+                                            int32_t n_steps, uint64_t seed, const int32_t* d_const_types,
+                                            const float* d_fixed_lengths, float* d_lattice, void* d_workspace, size_t workspace_bytes,
+                                            int32_t use_graph, const arreau_sample_condition* condition,
+                                            const arreau_sample_schedule* schedule, const arreau_corrector* corrector,
+                                            const arreau_resampling* resampling, void* stream) {
+    static const char* who = "arreau_sample_loop_resampled";
+    ResamplePlan plan{1, 1, {}};
+    if (resampling) {
+        int rc;
+        if ((rc = arreau_resampling_check(resampling->passes, resampling->jump_length, who))) return rc;
+        plan.passes = resampling->passes;
+        plan.jump = resampling->jump_length;
+    }
+    if (plan.passes > 1 && n_steps > 0) {
+        // the visited steps t_1 .. t_n and the successor of t_n, from the host copy of the schedule (or t - 1 without one)
+        std::vector<int> steps;
+        int last_succ = 0;
+        if (schedule) {
+            ARREAU_REQUIRE(resampling->timesteps != nullptr && resampling->n_timesteps >= 1,
+                           "arreau_sample_loop_resampled: a respaced loop needs the host copy of its schedule (timesteps)");
+            const int32_t* ts = resampling->timesteps;
+            const int K = resampling->n_timesteps;
+            int i0 = -1;
+            for (int i = 0; i < K; ++i)
+                if (ts[i] == t_start) { i0 = i; break; }
+            ARREAU_REQUIRE(i0 >= 0 && (int64_t)i0 + n_steps <= K,
+                           "arreau_sample_loop_resampled: the host schedule does not hold t_start followed by n_steps - 1 timesteps");
+            steps.assign(ts + i0, ts + i0 + n_steps);
+            last_succ = i0 + n_steps < K ? ts[i0 + n_steps] : 0;
+        } else {
+            for (int i = 0; i < n_steps; ++i) steps.push_back(t_start - i);
+            last_succ = t_start - n_steps;
+        }
+        for (int a = 0; a < n_steps; a += plan.jump) {
+            const int cnt = n_steps - a < plan.jump ? n_steps - a : plan.jump;
+            plan.blocks.push_back(ResampleBlock{a, cnt, steps[a], a + cnt < n_steps ? steps[a + cnt] : last_succ});
+        }
+    }
+    return sample_loop_impl(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, t_start, n_steps, seed, d_const_types, d_fixed_lengths,
+                            d_lattice, d_workspace, workspace_bytes, use_graph, condition, schedule, corrector,
+                            plan.passes > 1 ? &plan : nullptr, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

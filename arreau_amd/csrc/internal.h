@@ -71,7 +71,7 @@ struct arreau_model {
     int packed_stale;        // 1 after arreau_model_update_train_weights: the sampling kernels' packed planes are out of date
     void* loop_stream;       // hipStream_t / hipEvent_t of arreau_sample_loop's graph mode (capture is not allowed on the
     void* loop_event;        //   legacy default stream callers usually pass); created on first use
-    uint64_t graph_key[21];  // what the cached executable graph of arreau_sample_loop was captured for
+    uint64_t graph_key[22];  // what the cached executable graph of arreau_sample_loop was captured for
     void* retired_graph;     // hipGraphExec_t of the last arreau_sample_loop (+ the stream it was launched on): destroyed,
     void* retired_stream;    //   after that stream has drained, by the next loop or by arreau_model_destroy
     int32_t* status;         // device word of sticky ARREAU_STATUS_* bits (written by the kernels with atomicOr)
@@ -242,7 +242,28 @@ int arreau_corrector_check(int32_t steps, float snr, const char* who);
 // (seed, t, ARREAU_DRAW_Z_CORRECTOR, element, iter).  cond: only its position mask is read (null / no mask: every atom moves).
 int arreau_launch_corrector(const arreau_model* m, float* d_frac, const int32_t* d_t, const int32_t* d_off, int B, int N,
                             const float* d_eps, const float* d_z_frac, uint64_t seed, uint32_t iter, float snr,
-                            const SampleConditionDev* cond, hipStream_t s);
+                            const SampleConditionDev* cond, hipStream_t s,
+                            const int32_t* d_pass = nullptr /* resampled loop: word3 = 256 pass[0] + iter (the RESAMPLE instance) */);
+
+// RePaint resampling (arreau_sample_loop_resampled, arreau_resample_jump; the rules are stated in include/arreau_hip.h).
+// arreau_resampling_check: ARREAU_EINVAL unless 1 <= passes <= ARREAU_MAX_RESAMPLE_PASSES and jump_length >= 1.
+int arreau_resampling_check(int32_t passes, int32_t jump_length, const char* who);
+// The jump s -> t of every crystal: (s, t) from the per-crystal arrays d_s / d_t, or, when those are null, the scalars s / t
+// (the loop's block bottom and top).  Noise from the caller's arrays, or (all null) Philox (seed, t, kinds 6-8, element, pass).
+// Loop form (loop != null): also the workspace cell and the per-crystal embedding of the next step for t, the device timestep
+// set to t (loop->t_next = t, loop->t_cur = t + 1: the entry from which the next step advances) and loop->pass = `pass`.
+struct JumpLoopDev {
+    float* lattice_ws;  // [B,9]
+    float* cvec;        // [B,C]
+    int32_t* t_next;    // [B]
+    int32_t* t_cur;     // [B]
+    int32_t* pass;      // [1]
+};
+int arreau_launch_resample_jump(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                                const int32_t* d_s, const int32_t* d_t, int s, int t, const int32_t* d_off, const int32_t* d_batch,
+                                int B, int N, const float* d_z_frac, const float* d_z_lengths, const float* d_u_types, uint64_t seed,
+                                uint32_t pass, const int32_t* d_const_types, const float* d_fixed_lengths,
+                                const SampleConditionDev* cond, float* d_lattice, const JumpLoopDev* loop, hipStream_t st);
 
 void arreau_train_ctx_destroy(struct arreau_train_ctx* t);
 // edge_variant value that selects the shape-general fp32 network (train_net.hip) for the whole evaluation
@@ -313,7 +334,8 @@ int arreau_launch_reverse(const arreau_model* m, float* d_frac, int32_t* d_types
                           float* d_lattice_ws = nullptr, float* d_cvec_next = nullptr /* sampling loop: also prepare the next step
                           (workspace lattice + per-crystal embedding for timestep t - 1), see reverse_crystal_block */,
                           const SampleConditionDev* cond = nullptr /* conditioned sampling; needs Philox noise (noise.seed) */,
-                          const StepScheduleDev* sched = nullptr /* respaced step (s from a table or per crystal), null: s = t - 1 */);
+                          const StepScheduleDev* sched = nullptr /* respaced step (s from a table or per crystal), null: s = t - 1 */,
+                          const int32_t* d_pass = nullptr /* resampled loop: word3 = 256 pass[0] (the RESAMPLE instance) */);
 int arreau_launch_edge(const arreau_model* m, const float* dir, const float* dist, const int32_t* deg,
                        const int32_t* batch, const float* lattice, int N, float* kbuf, hipStream_t s);
 int arreau_launch_edge_bf16x6(const arreau_model* m, const float* dir, const float* dist, const int32_t* deg,

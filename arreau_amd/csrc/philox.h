@@ -2,7 +2,8 @@
 // checked against the Random123 known-answer vectors in tests/test_cabi_exports.py via arreau_philox_fill).
 // One call per drawn element, keyed by what the number is FOR, never by which thread draws it:
 //     counter = (element index, timestep, draw kind, word3),  key = the 64-bit seed
-// (word3 = 0 for every draw but the corrector's, whose iteration index it holds)
+// (word3 = 0 for every draw but the corrector's, whose iteration index it holds, and those of a resampled loop: pass r of a block
+// adds 256 r, and the jump in front of pass r draws with word3 = r)
 // so the noise of (seed, timestep, kind, element) is the same whatever the batch composition, launch geometry or
 // replay mechanism (eager loop or hipGraph).  The three draws of a step (diffusion_helpers.py:193-197, :79; d3pm.py:206):
 #pragma once
@@ -16,6 +17,11 @@
 #define ARREAU_DRAW_Z_KNOWN_LENGTHS 4u  // randn [B,3]  VP_lattice.forward of a known length (diffusion_helpers.py:156-163)
 // predictor-corrector sampling (arreau_sample_loop_corrected): the Langevin noise of corrector iteration j, counter word3 = j
 #define ARREAU_DRAW_Z_CORRECTOR 5u      // randn [N,3]
+// RePaint resampling (arreau_sample_loop_resampled, arreau_resample_jump): the forward jump from a block's bottom s to its top t,
+// keyed by t, word3 = the pass r the jump precedes
+#define ARREAU_DRAW_Z_JUMP_FRAC 6u      // randn [N,3]  VE_pbc.forward s -> t of the positions
+#define ARREAU_DRAW_Z_JUMP_LENGTHS 7u   // randn [B,3]  VP_lattice.forward s -> t of the lengths
+#define ARREAU_DRAW_U_JUMP_TYPES 8u     // rand  [N,S]  D3PM.q_sample s -> t of the species
 
 struct Philox4 { uint32_t x[4]; };
 

@@ -13,7 +13,7 @@ __device__ __forceinline__ void reverse_lattice_body(int gt /* global thread of 
                                        // sampling loop: pool the per-atom read-out here (same ordered sum as
                                        // readout_crystals_kernel) instead of a launch of its own; len0_out receives it
                                        const float* __restrict__ gs_atoms, float* __restrict__ len0_out, const SampleConditionDev* cond,
-                                       const StepScheduleDev* sched) {
+                                       const StepScheduleDev* sched, uint32_t word3) {
     // four lanes per crystal: lane i < 3 owns length component i (pooling, update), lane 0 then writes the cell
     const int b = b0 + (gt >> 2), i = gt & 3;
     const bool live = b < B;  // (whole groups of four are live or not; the shuffles below need every lane)
@@ -26,7 +26,7 @@ __device__ __forceinline__ void reverse_lattice_body(int gt /* global thread of 
     float mylen = 0.f;
     if (live && i < 3)
         mylen = reverse_length_component(b, i, t, s_to, sched, first, last, lengths, len0, noise, alpha_bars, betas, fixed_lengths, gs_atoms,
-                                         len0_out, cond);
+                                         len0_out, cond, word3);
     const int base = (threadIdx.x & 63) & ~3;
     float newlen[3];
 #pragma unroll
@@ -51,6 +51,7 @@ __device__ __forceinline__ void reverse_lattice_body(int gt /* global thread of 
 // COND: conditioned sampling (the condition argument is read); SCHED: a respaced step (the schedule argument is read: s from a
 // per-crystal array or the loop's next-timestep table).  reverse_kernel<false, false> is the plain kernel, whose helpers see a
 // null condition and a null schedule and compile to what they were before either existed.
+// Its twin reverse_resample_kernel (below) is a copy with the pass word: a change here belongs there too.
 template <bool COND, bool SCHED>
 __global__ __launch_bounds__(256) void reverse_kernel(
     int lat_blocks, float* __restrict__ lengths, const float* __restrict__ angles, const int32_t* __restrict__ tstep,
@@ -68,16 +69,50 @@ __global__ __launch_bounds__(256) void reverse_kernel(
     const StepScheduleDev* sched = SCHED ? &sched_arg : nullptr;
     if ((int)blockIdx.x < lat_blocks && cvec_next != nullptr) {  // (kernel argument: uniform)
         reverse_crystal_block(b0 + (int)blockIdx.x, lengths, angles, tstep, offsets, len0, noise, alpha_bars, betas, T, lattice, fixed_lengths,
-                              status, gs_atoms, len0_out, lattice_ws, cvec_next, t_emb_w, embT, S, C, cond, sched);
+                              status, gs_atoms, len0_out, lattice_ws, cvec_next, t_emb_w, embT, S, C, cond, sched, 0u);
         return;
     }
     if ((int)blockIdx.x < lat_blocks) {
         reverse_lattice_body(blockIdx.x * blockDim.x + threadIdx.x, lengths, angles, tstep, offsets, len0, noise, alpha_bars, betas, B_lat, T,
-                             lattice, fixed_lengths, status, b0, gs_atoms, len0_out, cond, sched);
+                             lattice, fixed_lengths, status, b0, gs_atoms, len0_out, cond, sched, 0u);
         return;
     }
     reverse_atoms_body((int)blockIdx.x - lat_blocks, frac, types, tstep, offsets, B, N, eps, logits, noise, ve_sigmas, q1t, qmats, S, T,
-                       const_types, absorbing, status, n0, batch, cond, sched);
+                       const_types, absorbing, status, n0, batch, cond, sched, 0u);
+}
+
+// Resampled loop (arreau_sample_loop_resampled): reverse_kernel in pass r of a block, r read from the loop's device word `pass`
+// (set by the jump in front of the pass, reset after the block), so one captured step serves every pass.  Every draw of the
+// step takes counter word3 = 256 r; pass 0 draws what reverse_kernel draws.  A copy, not a shared inline body: the existing
+// instances keep their instructions.
+template <bool COND, bool SCHED>
+__global__ __launch_bounds__(256) void reverse_resample_kernel(
+    int lat_blocks, float* __restrict__ lengths, const float* __restrict__ angles, const int32_t* __restrict__ tstep,
+    const int32_t* __restrict__ offsets, const float* __restrict__ len0, StepNoiseSrc noise, const float* __restrict__ alpha_bars,
+    const float* __restrict__ betas, int B_lat, int T, float* __restrict__ lattice, const float* __restrict__ fixed_lengths,
+    int32_t* __restrict__ status, int b0, const float* __restrict__ gs_atoms, float* __restrict__ len0_out,
+    float* __restrict__ frac, int32_t* __restrict__ types, int B, int N, const float* __restrict__ eps,
+    const float* __restrict__ logits, const float* __restrict__ ve_sigmas, const float* __restrict__ q1t,
+    const float* __restrict__ qmats, int S, const int32_t* __restrict__ const_types, int absorbing, int n0,
+    const int32_t* __restrict__ batch,
+    // sampling loop: the lattice part is one workgroup per crystal, which also prepares the next step (reverse_crystal_block)
+    float* __restrict__ lattice_ws, float* __restrict__ cvec_next, const float* __restrict__ t_emb_w, const float* __restrict__ embT, int C,
+    SampleConditionDev cond_arg, StepScheduleDev sched_arg, const int32_t* __restrict__ pass) {
+    const uint32_t word3 = 256u * (uint32_t)pass[0];  // the counter word of pass r
+    const SampleConditionDev* cond = COND ? &cond_arg : nullptr;
+    const StepScheduleDev* sched = SCHED ? &sched_arg : nullptr;
+    if ((int)blockIdx.x < lat_blocks && cvec_next != nullptr) {  // (kernel argument: uniform)
+        reverse_crystal_block(b0 + (int)blockIdx.x, lengths, angles, tstep, offsets, len0, noise, alpha_bars, betas, T, lattice, fixed_lengths,
+                              status, gs_atoms, len0_out, lattice_ws, cvec_next, t_emb_w, embT, S, C, cond, sched, word3);
+        return;
+    }
+    if ((int)blockIdx.x < lat_blocks) {
+        reverse_lattice_body(blockIdx.x * blockDim.x + threadIdx.x, lengths, angles, tstep, offsets, len0, noise, alpha_bars, betas, B_lat, T,
+                             lattice, fixed_lengths, status, b0, gs_atoms, len0_out, cond, sched, word3);
+        return;
+    }
+    reverse_atoms_body((int)blockIdx.x - lat_blocks, frac, types, tstep, offsets, B, N, eps, logits, noise, ve_sigmas, q1t, qmats, S, T,
+                       const_types, absorbing, status, n0, batch, cond, sched, word3);
 }
 
 namespace {
@@ -87,13 +122,20 @@ void enqueue_reverse_kernel(const arreau_model* m, int lat_blocks, int atom_bloc
                             const float* d_logits, const float* d_len0, StepNoiseSrc noise, const int32_t* d_const_types,
                             float* d_lattice, hipStream_t s, const float* d_fixed_lengths, const float* d_gs_atoms,
                             const int32_t* d_batch, float* d_lattice_ws, float* d_cvec_next, const SampleConditionDev& cond,
-                            const StepScheduleDev& sched) {
-    auto kernel = reverse_kernel<COND, SCHED>;
-    ARREAU_LAUNCH(kernel, dim3(lat_blocks + atom_blocks), dim3(256), 0, s, lat_blocks, d_lengths, d_angles, d_t, d_off, d_len0,
-                  noise, m->vp_alpha_bars, m->vp_betas, B, m->T, d_lattice, d_fixed_lengths, m->status, 0, d_gs_atoms,
-                  d_gs_atoms ? const_cast<float*>(d_len0) : nullptr, d_frac, d_types, B, N, d_eps, d_logits, m->ve_sigmas, m->q1t,
-                  m->qmats, m->S, d_const_types, m->qmats_absorbing, 0, d_batch, d_lattice_ws, d_cvec_next, m->t_emb_w, m->embT, m->C,
-                  cond, sched);
+                            const StepScheduleDev& sched, const int32_t* d_pass) {
+#define ARREAU_REVERSE_LAUNCH_ARGS                                                                                                 \
+    lat_blocks, d_lengths, d_angles, d_t, d_off, d_len0, noise, m->vp_alpha_bars, m->vp_betas, B, m->T, d_lattice, d_fixed_lengths, \
+        m->status, 0, d_gs_atoms, d_gs_atoms ? const_cast<float*>(d_len0) : nullptr, d_frac, d_types, B, N, d_eps, d_logits,        \
+        m->ve_sigmas, m->q1t, m->qmats, m->S, d_const_types, m->qmats_absorbing, 0, d_batch, d_lattice_ws, d_cvec_next, m->t_emb_w, \
+        m->embT, m->C, cond, sched
+    if (d_pass) {
+        auto kernel = reverse_resample_kernel<COND, SCHED>;
+        ARREAU_LAUNCH(kernel, dim3(lat_blocks + atom_blocks), dim3(256), 0, s, ARREAU_REVERSE_LAUNCH_ARGS, d_pass);
+    } else {
+        auto kernel = reverse_kernel<COND, SCHED>;
+        ARREAU_LAUNCH(kernel, dim3(lat_blocks + atom_blocks), dim3(256), 0, s, ARREAU_REVERSE_LAUNCH_ARGS);
+    }
+#undef ARREAU_REVERSE_LAUNCH_ARGS
 }
 }  // namespace
 
@@ -102,7 +144,7 @@ int arreau_launch_reverse(const arreau_model* m, float* d_frac, int32_t* d_types
                           const float* d_logits, const float* d_len0, StepNoiseSrc noise, const int32_t* d_const_types,
                           float* d_lattice, hipStream_t s, const float* d_fixed_lengths, const float* d_gs_atoms,
                           const int32_t* d_batch, float* d_lattice_ws, float* d_cvec_next, const SampleConditionDev* cond,
-                          const StepScheduleDev* sched) {
+                          const StepScheduleDev* sched, const int32_t* d_pass) {
     const bool prep_next = d_cvec_next != nullptr;  // one workgroup per crystal, which also prepares the next step
     ARREAU_REQUIRE(!prep_next || d_lattice_ws != nullptr, "reverse update: the next step's set-up needs the workspace lattice");
     const int lat_blocks = B > 0 ? (prep_next ? B : (4 * B + 255) / 256) : 0;
@@ -117,7 +159,7 @@ int arreau_launch_reverse(const arreau_model* m, float* d_frac, int32_t* d_types
     const SampleConditionDev c = conditioned ? *cond : SampleConditionDev{};
     const StepScheduleDev sc = scheduled ? *sched : StepScheduleDev{};
 #define ARREAU_REVERSE_ARGS m, lat_blocks, atom_blocks, d_frac, d_types, d_lengths, d_angles, d_t, d_off, B, N, d_eps, d_logits, d_len0, \
-        noise, d_const_types, d_lattice, s, d_fixed_lengths, d_gs_atoms, d_batch, d_lattice_ws, d_cvec_next, c, sc
+        noise, d_const_types, d_lattice, s, d_fixed_lengths, d_gs_atoms, d_batch, d_lattice_ws, d_cvec_next, c, sc, d_pass
     if (conditioned && scheduled) enqueue_reverse_kernel<true, true>(ARREAU_REVERSE_ARGS);
     else if (conditioned) enqueue_reverse_kernel<true, false>(ARREAU_REVERSE_ARGS);
     else if (scheduled) enqueue_reverse_kernel<false, true>(ARREAU_REVERSE_ARGS);
@@ -156,7 +198,7 @@ extern "C" int arreau_reverse_step_to(const arreau_model* m, float* d_frac, int3
 }
 
 // The sampler's in-kernel noise, written out: out[i] = the draw (seed, timestep, kind, element i, word3) -- standard normal for
-// kinds 0/1/3/4/5, uniform [0,1) for kind 2.  For tests (known-answer / statistics) and for reproducing a Philox trajectory
+// kinds 0/1/3/4/5/6/7, uniform [0,1) for kinds 2 and 8.  For tests (known-answer / statistics) and for reproducing a Philox trajectory
 // through arreau_reverse_step / arreau_corrector_step.
 __global__ void philox_fill_kernel(uint64_t seed, uint32_t timestep, uint32_t kind, uint32_t word3, int64_t n, float* __restrict__ out,
                                    uint32_t* __restrict__ raw) {
@@ -166,13 +208,13 @@ __global__ void philox_fill_kernel(uint64_t seed, uint32_t timestep, uint32_t ki
         const Philox4 r = philox4x32_10((uint32_t)i, timestep, kind, word3, (uint32_t)seed, (uint32_t)(seed >> 32));
         for (int j = 0; j < 4; ++j) raw[4 * i + j] = r.x[j];
     }
-    if (out) out[i] = kind == ARREAU_DRAW_U_TYPES ? philox_uniform(seed, timestep, kind, (uint32_t)i, word3)
+    if (out) out[i] = (kind == ARREAU_DRAW_U_TYPES || kind == ARREAU_DRAW_U_JUMP_TYPES) ? philox_uniform(seed, timestep, kind, (uint32_t)i, word3)
                                                   : philox_normal(seed, timestep, kind, (uint32_t)i, word3);
 }
 
 extern "C" int arreau_philox_fill_word(uint64_t seed, int32_t timestep, int32_t kind, uint32_t word3, int64_t n, float* d_out,
                                        uint32_t* d_raw, void* stream) {
-    ARREAU_REQUIRE((d_out || d_raw) && n >= 0 && kind >= 0 && kind <= (int32_t)ARREAU_DRAW_Z_CORRECTOR,
+    ARREAU_REQUIRE((d_out || d_raw) && n >= 0 && kind >= 0 && kind <= (int32_t)ARREAU_DRAW_U_JUMP_TYPES,
                    "arreau_philox_fill_word: bad argument");
     if (n == 0) return ARREAU_OK;
     ARREAU_LAUNCH(philox_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, seed,
@@ -195,10 +237,10 @@ __global__ void condition_initial_state_kernel(float* __restrict__ frac, int32_t
                                                const float* __restrict__ ve_sigmas, const float* __restrict__ alpha_bars) {
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g < 3 * (int64_t)N) {
-        if (cond.pos_mask && cond.pos_mask[g / 3]) frac[g] = known_frac_component(&cond, (size_t)g, t_key, t_key - 1, seed, ve_sigmas);
+        if (cond.pos_mask && cond.pos_mask[g / 3]) frac[g] = known_frac_component(&cond, (size_t)g, t_key, t_key - 1, seed, ve_sigmas, 0u);
     } else if (g < 3 * (int64_t)N + 3 * (int64_t)B) {
         const int c = (int)(g - 3 * (int64_t)N), b = c / 3;
-        if (cond.len_mask && cond.len_mask[b]) lengths[c] = known_length_component(&cond, b, c - 3 * b, t_key, t_key - 1, seed, alpha_bars);
+        if (cond.len_mask && cond.len_mask[b]) lengths[c] = known_length_component(&cond, b, c - 3 * b, t_key, t_key - 1, seed, alpha_bars, 0u);
     } else if (g < 4 * (int64_t)N + 3 * (int64_t)B) {
         const int i = (int)(g - 3 * (int64_t)N - 3 * (int64_t)B);
         if (cond.type_mask && cond.type_mask[i]) types[i] = cond.a0[i];

@@ -33,22 +33,23 @@ __device__ __forceinline__ int step_target(const StepScheduleDev* sc, int b, int
 // Conditioned sampling (arreau_sample_loop_conditioned; the rules are stated in include/arreau_hip.h).  The step that leaves
 // timestep t produces tau (t - 1, or the scheduled s); a known component is the template forward-noised to tau with the Philox
 // draw of (seed, t), and the template itself at tau = 0.  The initial state uses the same helpers with t = t_start + 1,
-// tau = t_start.
+// tau = t_start.  word3: the counter word of the draw (0; 256 r in pass r of a resampled loop) -- no default, so that every
+// call site says which.
 // Rule 1, VE_pbc.forward (diffusion_helpers.py:43-47): component g = 3 i + d of a known position.
 __device__ __forceinline__ float known_frac_component(const SampleConditionDev* c, size_t g, int t, int tau, uint64_t seed,
-                                                      const float* __restrict__ ve_sigmas) {
+                                                      const float* __restrict__ ve_sigmas, uint32_t word3) {
     const float x0 = c->x0[g];
     if (tau == 0) return remainder_one(x0);
-    const float z = philox_normal(seed, (uint32_t)t, ARREAU_DRAW_Z_KNOWN_FRAC, (uint32_t)g);
+    const float z = philox_normal(seed, (uint32_t)t, ARREAU_DRAW_Z_KNOWN_FRAC, (uint32_t)g, word3);
     return remainder_one(x0 + ve_sigmas[tau] * z);
 }
 // Rule 2, VP_lattice.forward (diffusion_helpers.py:156-163): component i of crystal b's known lengths.
 __device__ __forceinline__ float known_length_component(const SampleConditionDev* c, int b, int i, int t, int tau, uint64_t seed,
-                                                        const float* __restrict__ alpha_bars) {
+                                                        const float* __restrict__ alpha_bars, uint32_t word3) {
     const float l0 = c->l0[3 * b + i];
     if (tau == 0) return l0;
     const float ab = alpha_bars[tau];
-    const float z = philox_normal(seed, (uint32_t)t, ARREAU_DRAW_Z_KNOWN_LENGTHS, 3u * b + i);
+    const float z = philox_normal(seed, (uint32_t)t, ARREAU_DRAW_Z_KNOWN_LENGTHS, 3u * b + i, word3);
     return sqrtf(ab) * l0 + sqrtf(1.0f - ab) * z;
 }
 
@@ -59,7 +60,8 @@ __device__ __forceinline__ float reverse_length_component(int b, int i, int t, i
                                                           const float* __restrict__ len0, StepNoiseSrc noise,
                                                           const float* __restrict__ alpha_bars, const float* __restrict__ betas,
                                                           const float* __restrict__ fixed_lengths, const float* __restrict__ gs_atoms,
-                                                          float* __restrict__ len0_out, const SampleConditionDev* cond) {
+                                                          float* __restrict__ len0_out, const SampleConditionDev* cond,
+                                                          uint32_t word3 /* resampled loop: 256 r in pass r; else 0 */) {
     const float* __restrict__ z = noise.z_lattice;
     const float n = (float)(last - first);
     const float ab_t = alpha_bars[t], ab_p = alpha_bars[s];
@@ -86,12 +88,12 @@ __device__ __forceinline__ float reverse_length_component(int b, int i, int t, i
     const float x0 = pooled * n;  // pred_lengths_0 * num_atoms (diffusion_loss.py:338)
     const float xt = lengths[3 * b + i];
     const float mean = (c0 * x0 + c1 * xt) / denom;
-    const float zdraw = z ? z[3 * b + i] : philox_normal(noise.seed, (uint32_t)t, ARREAU_DRAW_Z_LATTICE, 3u * b + i);
+    const float zdraw = z ? z[3 * b + i] : philox_normal(noise.seed, (uint32_t)t, ARREAU_DRAW_Z_LATTICE, 3u * b + i, word3);
     const float zz = t > 1 ? zdraw : 0.0f;
     // fixed-cell sampling (arreau_sample_loop, d_fixed_lengths): the given lengths are re-imposed after the update
     float mylen = fixed_lengths ? fixed_lengths[3 * b + i] : mean + variance * zz;
     // conditioned sampling, rule 2: a known length is replaced before the cell is formed from it
-    if (cond && cond->len_mask && cond->len_mask[b]) mylen = known_length_component(cond, b, i, t, s, noise.seed, alpha_bars);
+    if (cond && cond->len_mask && cond->len_mask[b]) mylen = known_length_component(cond, b, i, t, s, noise.seed, alpha_bars, word3);
     lengths[3 * b + i] = mylen;
     return mylen;
 }
@@ -106,7 +108,8 @@ __device__ __forceinline__ void reverse_one_atom(
     const float* __restrict__ ve_sigmas, const float* __restrict__ q1t, const float* __restrict__ qmats, int S,
     int T, const int32_t* __restrict__ const_types, int absorbing, int32_t* __restrict__ status,
     const int32_t* __restrict__ batch /* crystal of each atom, or null: searched in `offsets` */,
-    const SampleConditionDev* cond /* conditioned sampling, or null */, const StepScheduleDev* sched /* respaced, or null */) {
+    const SampleConditionDev* cond /* conditioned sampling, or null */, const StepScheduleDev* sched /* respaced, or null */,
+    uint32_t word3 /* resampled loop: 256 r in pass r; else 0 */) {
     const float* __restrict__ z_frac = noise.z_frac;
     const float* __restrict__ u_types = noise.u_types;
     // crystal of this atom = largest b with offsets[b] <= i: a 64-ary search by the whole wave (each level one
@@ -134,9 +137,9 @@ __device__ __forceinline__ void reverse_one_atom(
         const size_t g = 3 * (size_t)i + lane;
         const float mean = frac[g] - eps[g] * (s2 - sp2);
         const float stdv = sqrtf((sp2 * (s2 - sp2)) / s2);
-        const float zf = z_frac ? z_frac[g] : philox_normal(noise.seed, (uint32_t)t, ARREAU_DRAW_Z_FRAC, (uint32_t)g);
+        const float zf = z_frac ? z_frac[g] : philox_normal(noise.seed, (uint32_t)t, ARREAU_DRAW_Z_FRAC, (uint32_t)g, word3);
         float fv = remainder_one(mean + stdv * zf);
-        if (cond && cond->pos_mask && cond->pos_mask[i]) fv = known_frac_component(cond, g, t, s_to, noise.seed, ve_sigmas);  // rule 1
+        if (cond && cond->pos_mask && cond->pos_mask[i]) fv = known_frac_component(cond, g, t, s_to, noise.seed, ve_sigmas, word3);  // rule 1
         frac[g] = fv;
     }
 
@@ -228,7 +231,7 @@ __device__ __forceinline__ void reverse_one_atom(
     const bool have_u = u_types != nullptr;
     const float* un = u_types + (have_u ? (size_t)i * S : 0);
     auto draw_u = [&](int s_) {
-        return have_u ? un[s_] : philox_uniform(noise.seed, (uint32_t)t, ARREAU_DRAW_U_TYPES, (uint32_t)((size_t)i * S + s_));
+        return have_u ? un[s_] : philox_uniform(noise.seed, (uint32_t)t, ARREAU_DRAW_U_TYPES, (uint32_t)((size_t)i * S + s_), word3);
     };
     float best = -INFINITY;
     int besti = 0x7fffffff;
@@ -260,11 +263,11 @@ __device__ __forceinline__ void reverse_atoms_body(
     const float* __restrict__ logits, StepNoiseSrc noise,
     const float* __restrict__ ve_sigmas, const float* __restrict__ q1t, const float* __restrict__ qmats, int S,
     int T, const int32_t* __restrict__ const_types, int absorbing, int32_t* __restrict__ status, int n0,
-    const int32_t* __restrict__ batch, const SampleConditionDev* cond, const StepScheduleDev* sched) {
+    const int32_t* __restrict__ batch, const SampleConditionDev* cond, const StepScheduleDev* sched, uint32_t word3) {
     const int i = n0 + blk * 4 + (int)(threadIdx.x >> 6);  // atoms n0 .. N-1
     if (i >= N) return;  // wave-uniform; no block-level barrier below
     reverse_one_atom(i, threadIdx.x & 63, frac, types, tstep, offsets, B, eps, logits, noise, ve_sigmas, q1t, qmats, S, T, const_types, absorbing,
-                     status, batch, cond, sched);
+                     status, batch, cond, sched, word3);
 }
 
 // Sampling loop (round 3): the lattice update of a crystal by ONE workgroup that then also prepares the crystal's NEXT step --
@@ -282,7 +285,7 @@ __device__ __forceinline__ void reverse_crystal_block(int b, float* __restrict__
                                                       float* __restrict__ len0_out, float* __restrict__ lattice_ws,
                                                       float* __restrict__ cvec_next, const float* __restrict__ t_emb_w,
                                                       const float* __restrict__ embT, int S, int C, const SampleConditionDev* cond,
-                                                      const StepScheduleDev* sched) {
+                                                      const StepScheduleDev* sched, uint32_t word3) {
     __shared__ float newlen[3];
     __shared__ float feat[ARREAU_T_EMB_DIM + ARREAU_N_CRYSTAL_FEATS];
     const int t_raw = tstep[b];
@@ -292,7 +295,7 @@ __device__ __forceinline__ void reverse_crystal_block(int b, float* __restrict__
     const int first = offsets[b], last = offsets[b + 1];
     if (threadIdx.x < 3)
         newlen[threadIdx.x] = reverse_length_component(b, threadIdx.x, t, s, sched, first, last, lengths, len0, noise, alpha_bars, betas, fixed_lengths,
-                                                       gs_atoms, len0_out, cond);
+                                                       gs_atoms, len0_out, cond, word3);
     __syncthreads();
     const float* ang = angles + 3 * b;
     if (threadIdx.x == 0) {

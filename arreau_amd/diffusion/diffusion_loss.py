@@ -12,6 +12,7 @@ import torch
 import torch.nn as nn
 
 from . import corrector as pc
+from . import resampling as rs
 from . import respacing
 from .d3pm import D3PM
 from .diffusion_helpers import VE_pbc, VP_lattice, crystal_offsets, sample_bravais_angles
@@ -260,7 +261,7 @@ class DiffusionLoss(nn.Module):
                max_steps: Optional[int] = None, use_graph: Optional[bool] = None, seed: Optional[int] = None,
                fixed_cell: bool = False, condition=None, num_steps: Optional[int] = None,
                timesteps: Optional[Sequence[int]] = None, corrector_steps: int = 0,
-               corrector_snr: float = pc.DEFAULT_SNR) -> SampleResult:
+               corrector_snr: float = pc.DEFAULT_SNR, resample_passes: int = 1, jump_length: int = 10) -> SampleResult:
         """diffusion_loss.py:276-377.  The initial state is drawn on the host exactly like the reference (numpy
         uniforms for the angles, then randn lengths, randn fractional coordinates from torch's global CPU generator).
         Per-step noise:
@@ -295,7 +296,15 @@ class DiffusionLoss(nn.Module):
         evaluation, with the SNR step-size rule r = corrector_snr (rules in include/arreau_hip.h; arreau_sample_loop_corrected).
         philox: the moves run in the library loop, their noise is Philox kind 5; reference / device: arreau_corrector_step
         with randn[N,3] from that mode's generator, drawn per move before the step's three predictor draws.  M = 0 is the
-        sampler without correctors bit for bit (and draws nothing extra).  No sample-quality claim is made."""
+        sampler without correctors bit for bit (and draws nothing extra).  No sample-quality claim is made.
+        `resample_passes` / `jump_length` (extension, every noise mode): RePaint resampling -- the visited steps (after
+        `max_steps` has cut them) in blocks of J = jump_length, every block run R = resample_passes (1..64) times, and every pass
+        after the first starts with a forward jump of the whole state from the block's bottom back up to its top (rules in
+        include/arreau_hip.h; arreau_sample_loop_resampled).  philox: the blocks run in the library loop; reference / device: the
+        events of resampling.plan on the host, each jump (arreau_resample_jump) drawing randn[N,3], randn[B,3], rand[N,S] from
+        that mode's generator just before the pass it precedes.  R = 1 is the sampler without resampling bit for bit (and draws
+        nothing extra).  With R > 1 only visualization_setting NONE or LAST is accepted (a frame inside a block would be
+        overwritten by the next pass).  No sample-quality claim is made."""
         frames = visualization_setting != VisualizationSetting.NONE
         if frames and not vis_name:
             raise ValueError("visualization_setting other than NONE needs vis_name (prefix of the frame files)")
@@ -303,6 +312,10 @@ class DiffusionLoss(nn.Module):
             raise ValueError("noise must be 'philox', 'device' or 'reference'")
         schedule = respacing.resolve_schedule(self.T, num_steps=num_steps, timesteps=timesteps)  # None: every timestep
         corrector_steps, corrector_snr = pc.check_corrector(corrector_steps, corrector_snr)
+        resample_passes, jump_length = rs.check_resampling(resample_passes, jump_length)
+        if resample_passes > 1 and visualization_setting in (VisualizationSetting.ALL, VisualizationSetting.ALL_DETAILED):
+            raise ValueError("resampling (resample_passes > 1) takes visualization_setting NONE or LAST: a frame inside a block "
+                             "would be overwritten by the block's next pass")
         if condition is not None:  # validated before the engine is touched
             num_atoms_per_sample, num_samples_in_batch = condition.resolve_batch(num_atoms_per_sample, num_samples_in_batch)
             condition.check_sampling(z_table, noise=noise, fixed_cell=fixed_cell, constant_species=constant_atoms is not None)
@@ -371,11 +384,16 @@ class DiffusionLoss(nn.Module):
             init_state = (frac_d.clone(), types_d.clone(), len_d.clone())
 
         corrector = (corrector_steps, corrector_snr) if corrector_steps > 0 else None
+        resampling = (resample_passes, jump_length, schedule) if resample_passes > 1 else None
+        # the events of the host-noise modes: the visited steps, with jumps when resampling (the successor of the last step is
+        # the timestep it produces)
+        last_succ = (steps[-1] - 1 if schedule is None else successor[steps[-1]]) if steps else 0
+        events = rs.plan(steps, last_succ, resample_passes, jump_length)
 
         def run_loop(use_graph):
             if noise == "philox":
                 if use_graph is None:
-                    use_graph = n_steps >= 200  # capture + instantiation (about 2 ms) against ~4 us saved per kernel boundary
+                    use_graph = n_steps * resample_passes >= 200  # capture + instantiation (about 2 ms) against ~4 us saved per kernel boundary
                 fixed = len_d.clone() if fixed_cell else None
                 # Frames (diffusion_loss.py:351-370): the loop is cut after the steps at the timesteps the reference
                 # visualises -- every 10th for ALL, every one for ALL_DETAILED, never the first -- of those this run visits.
@@ -390,7 +408,7 @@ class DiffusionLoss(nn.Module):
                     if end > start:
                         eng.sample_loop(frac_d, types_d, len_d, ang_d, off_d, steps[start], end - start, seed, const_d, lattice_d,
                                         use_graph=bool(use_graph), fixed_lengths=fixed, condition=cond_d, next_table=next_d,
-                                        lattice_clipmax=clipmax, corrector=corrector)
+                                        lattice_clipmax=clipmax, corrector=corrector, resampling=resampling)
                         start = end
                     if j is not None:
                         vis_crystal_during_sampling(z_table, types_d.cpu().numpy(), lattice_d.cpu().numpy(),
@@ -398,7 +416,19 @@ class DiffusionLoss(nn.Module):
             else:
                 t_d = torch.empty(B, device=dev, dtype=torch.int32)
                 s_d = torch.empty(B, device=dev, dtype=torch.int32)
-                for timestep in steps:
+                for ev in events:
+                    timestep = ev.t
+                    if ev.kind == "jump":  # resampling: the state back up to the block's top, in front of pass ev.r
+                        if noise == "device":
+                            z_f, z_l, u_t = torch.randn((N, 3), **f32), torch.randn((B, 3), **f32), torch.rand((N, S), **f32)
+                        else:
+                            z_f = torch.randn([N, 3], dtype=dt).to(**f32)
+                            z_l = torch.randn([B, 3]).to(**f32)
+                            u_t = torch.rand([N, S]).to(**f32)
+                        s_d.fill_(ev.s)
+                        t_d.fill_(ev.t)
+                        eng.resample_jump(frac_d, types_d, len_d, ang_d, s_d, t_d, off_d, z_f, z_l, u_t, lattice_d, const_types=const_d)
+                        continue
                     t_d.fill_(timestep)
                     eps, logits, len0 = eng.predict_scores(frac_d, types_d, len_d, ang_d, t_d, off_d)
                     for _ in range(corrector_steps):  # predictor-corrector: the moves at t, each followed by a new evaluation

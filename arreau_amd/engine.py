@@ -191,14 +191,30 @@ class HipEngine:
         return logits, vec_out, gscalar
 
     def sample_loop(self, frac, types, lengths, angles, offsets, t_start, n_steps, seed, const_types, lattice_out,
-                    use_graph=False, fixed_lengths=None, condition=None, next_table=None, lattice_clipmax=0.999, corrector=None):
+                    use_graph=False, fixed_lengths=None, condition=None, next_table=None, lattice_clipmax=0.999, corrector=None,
+                    resampling=None):
         """n_steps iterations of the sampling loop in one library call (arreau_sample_loop): in-place update of
         (frac, types, lengths); Philox noise keyed by (seed, timestep, draw, element).  `condition`: the device arrays of a
         conditioned run (SampleCondition.device_arrays: x0, pos_mask, a0, type_mask, l0, len_mask; None entries allowed),
         through arreau_sample_loop_conditioned.  `next_table`: a respaced run (arreau_sample_loop_scheduled): the device
         int32 [T+1] table of respacing.next_table, with VP_lattice's clipmax; t_start is then a scheduled timestep.
         `corrector`: (steps, snr) -- predictor-corrector sampling (arreau_sample_loop_corrected): `steps` Langevin corrector
-        moves on the positions before every step's predictor; None is the loop without them."""
+        moves on the positions before every step's predictor; None is the loop without them.
+        `resampling`: (passes, jump_length[, timesteps]) -- RePaint resampling (arreau_sample_loop_resampled): the call's steps in
+        blocks of jump_length, each run `passes` times with a forward jump back to the block's top in front of every pass after
+        the first; `timesteps` is the host list of the schedule behind next_table (required with it).  None or passes == 1 is
+        the loop without resampling."""
+        res = None
+        if resampling is not None:
+            from .diffusion.resampling import check_resampling
+            passes, jump = check_resampling(*resampling[:2])
+            ts = list(resampling[2]) if len(resampling) > 2 and resampling[2] is not None else None
+            if passes > 1:
+                if next_table is not None and ts is None:
+                    raise ValueError("resampling on a respaced loop needs the host list of its timesteps")
+                ts_arr = (ctypes.c_int32 * len(ts))(*ts) if ts else None  # (alive until the call returns)
+                res = _hip.ResamplingC(passes, jump, ctypes.cast(ts_arr, ctypes.POINTER(ctypes.c_int32)) if ts else None,
+                                       len(ts) if ts else 0)
         if corrector is not None:
             from .diffusion.corrector import check_corrector
             corrector = check_corrector(*corrector)
@@ -214,7 +230,15 @@ class HipEngine:
                     or not next_table.is_contiguous()):
                 raise ValueError(f"next_table must be a contiguous int32 tensor of shape ({T + 1},) on {self.device}")
             sched = _hip.SampleScheduleC(_hip.ptr(next_table).value, float(lattice_clipmax))
-        if corrector is not None:
+        if res is not None:
+            cond = self._condition_struct(condition, N, B) if condition is not None else None
+            corr = _hip.CorrectorC(corrector[0], corrector[1]) if corrector is not None else None
+            _hip.check(_hip.lib().arreau_sample_loop_resampled(*args, ctypes.byref(cond) if cond is not None else None,
+                                                               ctypes.byref(sched) if sched is not None else None,
+                                                               ctypes.byref(corr) if corr is not None else None,
+                                                               ctypes.byref(res), _hip.stream_ptr(self.device)),
+                       "arreau_sample_loop_resampled")
+        elif corrector is not None:
             cond = self._condition_struct(condition, N, B) if condition is not None else None
             corr = _hip.CorrectorC(corrector[0], corrector[1])
             _hip.check(_hip.lib().arreau_sample_loop_corrected(*args, ctypes.byref(cond) if cond is not None else None,
@@ -528,6 +552,19 @@ class HipEngine:
             _hip.ptr(s_crystal), _hip.ptr(offsets), B, N, _hip.ptr(eps), _hip.ptr(logits), _hip.ptr(len0), _hip.ptr(z_lattice),
             _hip.ptr(z_frac), _hip.ptr(u_types), _hip.ptr(lattice_out), float(lattice_clipmax), _hip.stream_ptr(self.device)),
             "arreau_reverse_step_to")
+
+    def resample_jump(self, frac, types, lengths, angles, s_crystal, t_crystal, offsets, z_frac, z_lengths, u_types, lattice_out,
+                      const_types=None, fixed_lengths=None, condition=None):
+        """One RePaint jump of the whole state from timestep s_crystal[b] up to t_crystal[b] (arreau_resample_jump), in place,
+        with the caller's noise: z_frac [N,3] and z_lengths [B,3] standard normal, u_types [N,S] uniform.  Held: const_types,
+        fixed_lengths, and the species of `condition`'s type mask (a dict as in sample_loop)."""
+        B, N = lengths.shape[0], frac.shape[0]
+        cond = self._condition_struct(condition, N, B) if condition is not None else None
+        _hip.check(_hip.lib().arreau_resample_jump(
+            self._handle, _hip.ptr(frac), _hip.ptr(types), _hip.ptr(lengths), _hip.ptr(angles), _hip.ptr(s_crystal),
+            _hip.ptr(t_crystal), _hip.ptr(offsets), B, N, _hip.ptr(z_frac), _hip.ptr(z_lengths), _hip.ptr(u_types),
+            _hip.ptr(const_types), _hip.ptr(fixed_lengths), ctypes.byref(cond) if cond is not None else None,
+            _hip.ptr(lattice_out), _hip.stream_ptr(self.device)), "arreau_resample_jump")
 
     def edges_to_slots(self, edge_index, dists, direction, N):
         """Receiver-sorted COO edges -> slot form (deg, src, dir, dist)."""

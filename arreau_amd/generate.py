@@ -16,6 +16,9 @@ Respaced sampling: `--num_steps K` runs K evenly spaced denoising steps instead 
 
 Predictor-corrector sampling: `--corrector_steps M` runs M Langevin corrector moves on the positions before every denoising
 step, with the step-size rule's `--corrector_snr` (default 0.16; DiffusionLoss.sample).
+
+RePaint resampling: `--resample_passes R --jump_length J` runs the denoising steps in blocks of J, each R times, jumping the
+state back to the block's top before every pass after the first (DiffusionLoss.sample).
 """
 import argparse
 import os
@@ -141,6 +144,22 @@ def _corrector_snr_arg(text: str) -> float:
         raise argparse.ArgumentTypeError(str(e)) from None
 
 
+def _resample_passes_arg(text: str) -> int:
+    from .diffusion.resampling import check_resampling
+    try:
+        return check_resampling(int(text), 1)[0]
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
+def _jump_length_arg(text: str) -> int:
+    from .diffusion.resampling import check_resampling
+    try:
+        return check_resampling(1, int(text))[1]
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--model_path", type=str, required=True)
@@ -160,6 +179,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="predictor-corrector sampling: Langevin corrector moves on the positions per denoising step (0..16)")
     ap.add_argument("--corrector_snr", type=_corrector_snr_arg, default=0.16,
                     help="signal-to-noise ratio of the corrector's step-size rule (finite, > 0)")
+    ap.add_argument("--resample_passes", type=_resample_passes_arg, default=1,
+                    help="RePaint resampling: passes per block of denoising steps (1..64; 1 = no resampling)")
+    ap.add_argument("--jump_length", type=_jump_length_arg, default=10,
+                    help="RePaint resampling: denoising steps per block (>= 1)")
     return ap
 
 
@@ -199,13 +222,15 @@ def main():
     def fn(n, b, cond=None):
         if not lock_path:
             return model.sample(n, b, VisualizationSetting.NONE, False, condition=cond, num_steps=args.num_steps,
-                                corrector_steps=args.corrector_steps, corrector_snr=args.corrector_snr)
+                                corrector_steps=args.corrector_steps, corrector_snr=args.corrector_snr,
+                                resample_passes=args.resample_passes, jump_length=args.jump_length)
         import fcntl
         with open(lock_path, "a") as lock:
             fcntl.flock(lock, fcntl.LOCK_EX)
             try:
                 out = model.sample(n, b, VisualizationSetting.NONE, False, condition=cond, num_steps=args.num_steps,
-                                corrector_steps=args.corrector_steps, corrector_snr=args.corrector_snr)
+                                corrector_steps=args.corrector_steps, corrector_snr=args.corrector_snr,
+                                resample_passes=args.resample_passes, jump_length=args.jump_length)
                 torch.cuda.synchronize()
                 return out
             finally:

@@ -313,14 +313,18 @@ class PONITA_DIFFUSION(nn.Module):
                max_steps: Optional[int] = None, use_graph: Optional[bool] = None,
                seed: Optional[int] = None, fixed_cell: bool = False, vis_name: Optional[str] = None,
                condition=None, num_steps: Optional[int] = None, timesteps=None, corrector_steps: int = 0,
-               corrector_snr: float = 0.16) -> SampleResult:
+               corrector_snr: float = 0.16, resample_passes: int = 1, jump_length: int = 10) -> SampleResult:
         """lightning_wrappers/diffusion.py:220-253.  `num_atoms_per_sample` may also be a sequence with one atom count
         per crystal of the batch (extension; the reference supports a single int).  Frames of a visualization_setting
         other than NONE go to `<DIFFUSION_DIR>/step_<timestep>.cif` like the reference's PNGs (`vis_name` overrides the
         prefix).  `condition` (extension): a diffusion.conditioning.SampleCondition -- structure completion from a
         template (DiffusionLoss.sample); it defines the batch, so the two counts may be omitted.  `num_steps` / `timesteps`
         (extension): respaced sampling on fewer timesteps (DiffusionLoss.sample).  `corrector_steps` / `corrector_snr`
-        (extension): predictor-corrector sampling, Langevin moves on the positions before each step (DiffusionLoss.sample)."""
+        (extension): predictor-corrector sampling, Langevin moves on the positions before each step (DiffusionLoss.sample).
+        `resample_passes` / `jump_length` (extension): RePaint resampling, blocks of steps re-denoised after a forward jump back
+        to their top (DiffusionLoss.sample)."""
+        from ..diffusion import resampling
+        resampling.check_resampling(resample_passes, jump_length)  # (raises before any work)
         if num_steps is not None or timesteps is not None:
             from ..diffusion import respacing
             respacing.resolve_schedule(self.diffusion_loss.T, num_steps=num_steps, timesteps=timesteps)  # (raises before any work)
@@ -341,4 +345,5 @@ class PONITA_DIFFUSION(nn.Module):
             num_samples_in_batch=num_samples_in_batch, vis_name=self._frame_prefix(vis_name, visualization_setting),
             visualization_setting=visualization_setting, show_bonds=show_bonds, constant_atoms=constant_atoms,
             noise=noise, max_steps=max_steps, use_graph=use_graph, seed=seed, fixed_cell=fixed_cell, condition=condition,
-            num_steps=num_steps, timesteps=timesteps, corrector_steps=corrector_steps, corrector_snr=corrector_snr)
+            num_steps=num_steps, timesteps=timesteps, corrector_steps=corrector_steps, corrector_snr=corrector_snr,
+            resample_passes=resample_passes, jump_length=jump_length)

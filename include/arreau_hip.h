@@ -414,14 +414,79 @@ int arreau_corrector_step(const arreau_model* model, float* d_frac, const int32_
                           int32_t B, int32_t N, const float* d_eps, const float* d_z_frac, float snr,
                           const arreau_sample_condition* condition, void* stream);
 
+/* ---- RePaint resampling (jump back and re-denoise blocks of steps) ------------------------------------------------
+ * Lugmayr et al., CVPR 2022, section 4.2 ("resampling"): the visited steps are cut into blocks of J; every block is run R
+ * times, and every pass after the first starts with a jump of the whole state from the block's bottom back up to its top by
+ * the forward process.  Replacement alone (conditioned sampling above) never pulls the unknown atoms into agreement with the
+ * known ones; the jumps do.
+ *   R = passes per block (RePaint's jump_n_sample; R = 1: no resampling), J = jump length in schedule steps (J >= 1).
+ *   1. blocks: the steps a call visits are t_1 > ... > t_n (t_1 = t_start, n = n_steps); t_{n+1} is the successor of t_n (the
+ *      schedule's next timestep, t - 1 without a schedule, 0 after 1).  Block k covers steps kJ+1 .. min(kJ+J, n); its top is
+ *      t_{kJ+1}, its bottom t_{min(kJ+J,n)+1}.  Every block runs R passes; passes r = 1..R-1 each start with a jump from the
+ *      bottom s up to the top t.  The last block may be shorter; the final block, whose bottom is 0, is resampled too.
+ *   2. jump s -> t (0 <= s < t <= T, float32, per crystal), the forward process in closed form:
+ *      positions  x <- remainder(x + sqrt(sig_t^2 - sig_s^2) z, 1), sig = ve_sigmas (sig_0 = ve_sigmas[0] = sigma_min), the
+ *                 difference of squares formed as (sig_t - sig_s)(sig_t + sig_s) (VE_pbc.forward composed,
+ *                 diffusion_helpers.py:43-47);
+ *      lengths    l <- sqrt(abar_t / abar_s) l + sqrt(1 - abar_t / abar_s) z, abar_0 = 1 (VP_lattice.forward composed,
+ *                 :156-163), then the cell by lattice_from_params into d_lattice;
+ *      species    x <- argmax_c [log(Qbar_{t-s}[x, c] + eps) - log(-log(clip(u_c, eps, 1)))], Qbar_k = q_mats[k-1]
+ *                 (D3PM.q_sample, d3pm.py:119-127: the rule and tie rule of the training forward), S uniforms per atom; the
+ *                 absorbing fast path and the dense path give the same bits.
+ *   3. held, not jumped: the lengths of a fixed cell (d_fixed_lengths), species given by d_const_types, known species of a
+ *      condition (type_mask).  Known positions and known lengths ARE jumped (RePaint noises the whole state); the block's next
+ *      update re-imposes them under conditioning rules 1-2.
+ *   4. noise: the jump in front of pass r draws Philox (seed, t = block top, kind, element) with counter word3 = r: kind 6
+ *      positions (normal, element 3 i + d), kind 7 lengths (normal, 3 b + d), kind 8 species (uniform, i S + c).  Inside pass r
+ *      the predictor kinds 0-2 and the conditioning kinds 3-4 draw with word3 = 256 r, the corrector (kind 5) with 256 r + j.
+ *      Pass 0 therefore draws exactly what a run without resampling draws, and R = 1 is arreau_sample_loop_corrected bit for
+ *      bit, for any J.
+ *   5. after a jump the device timestep is the block's top (in a respaced loop through the table's "one above" entry), in
+ *      both loop forms and on the shape-general path; the next step's cell and per-crystal embedding are prepared for it.
+ *   6. resampling combines with respacing, conditioning, corrector steps, fixed cells, constant species, ragged batches and graph
+ *      replay (one captured step serves every pass and block; jumps are launched between replays).  No sample-quality claim is
+ *      made: there is no trained checkpoint here.
+ * The loop cuts blocks from the steps of ONE call: a run cut into calls at block boundaries is the run in one call. */
+#define ARREAU_MAX_RESAMPLE_PASSES 64
+typedef struct {
+    int32_t passes;            /* R, 1..ARREAU_MAX_RESAMPLE_PASSES */
+    int32_t jump_length;       /* J >= 1 */
+    const int32_t* timesteps;  /* HOST copy of the schedule t_1..t_K behind `schedule` (NULL without one): block tops/bottoms */
+    int32_t n_timesteps;
+} arreau_resampling;
+
+/* arreau_sample_loop_corrected with RePaint resampling (rules above; `resampling` is a host pointer, NULL or passes == 1 =
+ * arreau_sample_loop_corrected).  Bad R or J, or (with a schedule and R > 1) a host copy that does not hold t_start followed by
+ * at least n_steps - 1 further timesteps, return ARREAU_EINVAL before any work.  That the host copy matches the device table d_next
+ * is not checked: the blocks follow the host copy, the device timestep the table.  R and J are part of what a cached hipGraph
+ * was captured for. */
+int arreau_sample_loop_resampled(arreau_model* model, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                                 const int32_t* d_crystal_offsets, int32_t B, int32_t N, int32_t t_start, int32_t n_steps,
+                                 uint64_t seed, const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice,
+                                 void* d_workspace, size_t workspace_bytes, int32_t use_graph,
+                                 const arreau_sample_condition* cond, const arreau_sample_schedule* schedule,
+                                 const arreau_corrector* corrector, const arreau_resampling* resampling, void* stream);
+
+/* One jump (rule 2) from d_s[b] up to d_t[b] per crystal with the caller's noise d_z_frac[N,3], d_z_lengths[B,3] and
+ * d_u_types[N,S], in place on (d_frac, d_types, d_lengths); d_lattice[B,3,3] receives the cells.  Held components (rule 3):
+ * d_const_types, d_fixed_lengths (may be NULL) and the type mask of `cond` (host pointer, may be NULL).  A pair outside
+ * 0 <= s < t <= T is clamped into it and sets ARREAU_STATUS_BAD_TIMESTEP.  For the loops with host-side noise and for parity
+ * tests: fed arreau_philox_fill_word(seed, t, 6 / 7 / 8, r, ...), it is the loop's jump in front of pass r bit for bit. */
+int arreau_resample_jump(const arreau_model* model, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                         const int32_t* d_s, const int32_t* d_t, const int32_t* d_crystal_offsets, int32_t B, int32_t N,
+                         const float* d_z_frac, const float* d_z_lengths, const float* d_u_types,
+                         const int32_t* d_const_types, const float* d_fixed_lengths,
+                         const arreau_sample_condition* cond, float* d_lattice, void* stream);
+
 /* The sampler's in-kernel noise written out: d_out[i] = draw (seed, timestep, kind, element i) -- standard normal for
  * kind 0 (z_lattice), 1 (z_frac), 3 (known positions) and 4 (known lengths), uniform [0,1) for kind 2 (u_types); d_raw[4 i .. 4 i + 3] (may be NULL) = the raw
  * Philox4x32-10 words of counter (i, timestep, kind, 0), key = seed.  Feeding these arrays to arreau_reverse_step
  * reproduces arreau_sample_loop's update bit for bit.  Kinds above 4 are rejected (arreau_philox_fill_word). */
 int arreau_philox_fill(uint64_t seed, int32_t timestep, int32_t kind, int64_t n, float* d_out, uint32_t* d_raw,
                        void* stream);
-/* arreau_philox_fill with the counter's fourth word given: counter (i, timestep, kind, word3).  Kinds 0..5; kind 5 (the
- * corrector's Langevin noise, standard normal) with word3 = j is what the loop's j-th correction at `timestep` draws. */
+/* arreau_philox_fill with the counter's fourth word given: counter (i, timestep, kind, word3).  Kinds 0..8; kind 5 (the
+ * corrector's Langevin noise, standard normal) with word3 = j is what the loop's j-th correction at `timestep` draws; kinds 6, 7
+ * (standard normal) and 8 (uniform [0,1)) with word3 = r are the draws of a resampled loop's jump in front of pass r. */
 int arreau_philox_fill_word(uint64_t seed, int32_t timestep, int32_t kind, uint32_t word3, int64_t n, float* d_out,
                             uint32_t* d_raw, void* stream);
 
