@@ -83,7 +83,7 @@ class Config(Structure):
 class Status(Structure):
     _fields_ = [("flags", c_int32), ("edge_kernel", c_int32), ("mlp_kernel", c_int32), ("conv_kernel", c_int32),
                 ("basis_row_bytes", c_int32), ("conv_cross_fp8", c_int32), ("edge_activation_bound", c_float), ("node_activation_bound", c_float),
-                ("basis_fp8_share", c_float), ("cross_fp8_share", c_float)]
+                ("basis_fp8_share", c_float), ("cross_fp8_share", c_float), ("readout_kernel", c_int32)]
 
 
 _SD_FIELDS = [

@@ -62,7 +62,7 @@ struct arreau_model {
     // Arithmetic / geometry variants requested for this model (defaults from ARREAU_*_VARIANT at create,
     // arreau_model_set_variant overrides) and what the last arreau_predict_scores actually launched.
     int edge_variant, mlp_variant, conv_variant, readout_variant;
-    mutable int ran_edge, ran_mlp, ran_conv, ran_x8;
+    mutable int ran_edge, ran_mlp, ran_conv, ran_x8, ran_readout;
     // training (train_net.hip): plain row-major fp32 copies of the weights the sampling kernels hold only in packed
     // form, and the step's activation buffers (created on first use)
     const float *t_w1f, *t_w2, *t_wk, *t_lin1, *t_lin2, *t_ro_w;

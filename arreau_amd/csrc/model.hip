@@ -372,7 +372,7 @@ static int calibrate_message_formats(arreau_model* m, hipStream_t s) {
     }
     (void)hipStreamSynchronize(s);
     (void)hipFree(dev);
-    m->ran_edge = m->ran_mlp = m->ran_conv = -1;
+    m->ran_edge = m->ran_mlp = m->ran_conv = m->ran_readout = -1;
     m->ran_x8 = 0;
     if (rc != ARREAU_OK) { arreau_set_error(std::string("format calibration: ") + arreau_last_error()); return rc; }
     (void)flags;
@@ -692,7 +692,7 @@ extern "C" int arreau_model_create(const arreau_config* cfg, const arreau_state_
     m->mlp_variant = env_int("ARREAU_MLP_VARIANT", node_bound <= f16_slack ? 3 : 1);
     m->conv_variant = env_int("ARREAU_CONV_VARIANT", 2);  // 2: basis form + conv_proj.hip; 1: K stash + streamed conv; 0: register conv
     m->readout_variant = env_int("ARREAU_READOUT_VARIANT", 1);
-    m->ran_edge = m->ran_mlp = m->ran_conv = -1;
+    m->ran_edge = m->ran_mlp = m->ran_conv = m->ran_readout = -1;
     m->ran_x8 = 0;
     m->fused = fused ? 1 : 0;
     // ARREAU_GENERAL_PATH=1 (or edge variant 5): run the shape-general fp32 kernels also for the fused shape (cross-check)
@@ -782,6 +782,7 @@ extern "C" int arreau_model_status(const arreau_model* model, arreau_status* out
     out->edge_kernel = model->ran_edge;
     out->mlp_kernel = model->ran_mlp;
     out->conv_kernel = model->ran_conv;
+    out->readout_kernel = model->ran_readout;
     out->basis_row_bytes = model->ran_conv == 2 ? (arreau_basis_fp8(model) ? 768 : 1024) : 0;
     out->conv_cross_fp8 = model->ran_conv == 2 ? model->ran_x8 : 0;
     out->edge_activation_bound = model->edge_act_bound;

@@ -860,9 +860,11 @@ int arreau_launch_readout(const arreau_model* m, const float* xbar, const float*
             else
                 ARREAU_LAUNCH((readout_mfma_kernel<128, 3>), dim3(blocks32), dim3(64 * m->L), smem_m, s, xbar, vsum,
                                    m->ro_pack, m->ro_b, m->ori, m->S, m->L, N, 0, N, eps, logits, gs, m->status);
+            m->ran_readout = 1;
         } else {
             ARREAU_LAUNCH(readout_nodes_kernel, dim3((N + RO_ATOMS - 1) / RO_ATOMS), dim3(RO_COLS * m->L), smem, s, xbar, vsum,
                                m->ro_wT, m->ro_b, m->ori, m->S, m->C, m->L, N, eps, logits, gs, m->status);
+            m->ran_readout = 0;
         }
         ARREAU_CHECK_HIP(hipGetLastError());
     }

@@ -81,8 +81,10 @@ __device__ __forceinline__ void arreau_readout_tile(
         }
     }
     // vector channel: eps component d of atom a (sphere_to_vec of the per-orientation dot products)
-    if (threadIdx.x < 96 && (!USPLIT || utile == 0)) {
-        const int a = threadIdx.x / 3, dd = threadIdx.x - 3 * a;
+    // (32 atoms x 3 components = 96 values: a loop, since a one-layer model's workgroup is a single wave of 64 threads --
+    // with one value per thread the tile's last 11 atoms kept whatever their eps held before)
+    for (int i = threadIdx.x; i < 96 && (!USPLIT || utile == 0); i += blockDim.x) {
+        const int a = i / 3, dd = i - 3 * a;
         const int ni = n0 + a;  // (32-bit bounds check: no per-lane 64-bit integer compares on this path)
         if (ni < N) {
             const size_t n = (size_t)ni;

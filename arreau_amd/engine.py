@@ -110,7 +110,8 @@ class HipEngine:
                 "mlp_variant": int(st.mlp_kernel), "conv_variant": int(st.conv_kernel),
                 "basis_row_bytes": int(st.basis_row_bytes), "conv_cross_fp8": int(st.conv_cross_fp8), "edge_activation_bound": float(st.edge_activation_bound),
                 "node_activation_bound": float(st.node_activation_bound),
-                "basis_fp8_share": float(st.basis_fp8_share), "cross_fp8_share": float(st.cross_fp8_share)}
+                "basis_fp8_share": float(st.basis_fp8_share), "cross_fp8_share": float(st.cross_fp8_share),
+                "readout_kernel": int(st.readout_kernel)}
 
     def check_status(self, reset=True):
         """Raise if a kernel flagged a condition under which its results must not be trusted."""

@@ -122,7 +122,9 @@ int arreau_model_config(const arreau_model* model, arreau_config* out_cfg);
  * edge_kernel / mlp_kernel / conv_kernel name the kernel family the last arreau_predict_scores really launched
  * (edge: 0-2 fp32 MFMA, 3 bf16x6, 4 fp16x3; mlp: 0 fp32 MFMA, 1 bf16x6, 2 fp16x3 32x32x16, 3 fp16x3 16x16x32;
  * conv: 0 register form, 1 streamed form, 2 fused into the MLP kernel) -- e.g. 3/1 instead of 4/3 when a weight does not
- * fit fp16.  The reference has no counterpart (Python raises on bad indices: F.one_hot, tensor indexing). */
+ * fit fp16.  readout_kernel names the read-out the last arreau_predict_scores launched: 1 the fp32-MFMA kernel (S + 4 <= 96),
+ * 0 the vector kernel (readout_nodes_kernel: wider species tables, or ARREAU_READOUT_VARIANT=0), 5 the shape-general path's
+ * train_outputs_kernel; -1 none yet.  The reference has no counterpart (Python raises on bad indices: F.one_hot, tensor indexing). */
 #define ARREAU_STATUS_NONFINITE 1
 #define ARREAU_STATUS_BAD_TIMESTEP 2
 #define ARREAU_STATUS_BAD_TYPE 4
@@ -144,6 +146,7 @@ typedef struct arreau_status {
                               * (1e-5 max(1, |eps|), 1e-5 max(1, |logits| / 8)) the fp8 residual plane of the stash, resp. that plane + */
     float cross_fp8_share;   /* the fp8 cross products used up against two fp16 planes + three fp16 products; a format above 0.1 is not
                               * used for this model (basis_row_bytes 1024 / conv_cross_fp8 0 then); -1: not measured */
+    int32_t readout_kernel;  /* 1 fp32-MFMA read-out, 0 readout_nodes_kernel, 5 the general path's train_outputs_kernel, -1 not run */
 } arreau_status;
 /* Reads (and with reset != 0 clears) the status word; synchronises `stream`. */
 int arreau_model_status(const arreau_model* model, arreau_status* out, int32_t reset, void* stream);

@@ -66,6 +66,20 @@ def test_weight_gradient_shapes_take_split_k_and_stay_deterministic(mode):
     assert _run(mode, 640, 256, 20000, False, False, seed=3) == errs[0]   # same sums in the same order
 
 
+@pytest.mark.parametrize("layout", list(LAYOUTS))
+@pytest.mark.parametrize("mode", [0, 1, 2], ids=["exact fp32", "fp16x3", "bf16x6"])
+def test_tiny_products_of_the_general_path(layout, mode):
+    """The sizes the shape-general network hands down at its smallest hidden / basis widths (C = 4 and 12, D = 4): K or N far
+    below one tile, a single row, K below one 32-wide k-step, and one weight gradient with N = 4 under a long K (split-K
+    reducing into a single narrow tile)."""
+    a_k, b_k = LAYOUTS[layout]
+    worst = 0.0
+    for M, N, K in ((1, 4, 4), (17, 4, 12), (63, 36, 4), (65, 12, 33), (300, 1024, 4), (12, 4, 20000)):
+        worst = max(worst, _run(mode, M, N, K, a_k, b_k, seed=M + N + K))
+    print(f"\n[sgemm tiny {layout}, mode {mode}] worst error relative to the largest entry: {worst:.2e}")
+    assert worst <= TOL
+
+
 def test_alpha_and_beta():
     for mode in (0, 1, 2):
         assert _run(mode, 300, 200, 256, True, True, alpha=0.2, beta=1.0) <= TOL
