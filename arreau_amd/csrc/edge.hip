@@ -126,7 +126,10 @@ __global__ __launch_bounds__(256, OCC) void edge_kernel(
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb) {
         slot[cb] = slot0 + 2 * cb + (j >> 4);
-        const int sc = min(slot[cb], k - 1);  // padding rows (k not a multiple of 4) read a valid slot
+        // padding rows (k not a multiple of 4) read a valid slot.  A slot in [nd, k) computes on whatever the caller left in it,
+        // NaN included, and its K rows are stored; the conv kernels behind this kernel drop them by a select on the degree (never
+        // a multiply by zero), so the unused slots of a given graph do not change an output bit (include/arreau_hip.h).
+        const int sc = min(slot[cb], k - 1);
         er[cb] = edge_row(nbr_dir, nbr_dist, ori, Lm, (size_t)node * k + sc, o, r_max, slot[cb] < nd);
         row[cb] = ((size_t)node * k + sc) * 16 + o;
     }

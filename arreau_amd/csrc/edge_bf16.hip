@@ -78,6 +78,10 @@ __global__ __launch_bounds__(256, 1) void edge_kernel_bf16x6(
     const bool active = 2 * wave < nd;  // wave-uniform; inactive waves still stage weights and meet the barriers
     const int slot = 2 * wave + (j >> 4);
     const int o = j & 15;
+    // A slot past the degree (the odd slot of this wave's pair when nd is odd) computes on whatever the caller left in it, NaN
+    // included: that reaches only its own columns of the MFMA tiles, and store_tile writes no row of a slot >= nd.  The K pair
+    // conv behind this kernel drops those rows by a select on the degree, so the unused slots of a given graph do not change an
+    // output bit (include/arreau_hip.h).
     const int slot_c = min(slot, k - 1);
 
     // first chunk on its way while the row attributes are computed

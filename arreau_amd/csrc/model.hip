@@ -690,6 +690,9 @@ extern "C" int arreau_model_create(const arreau_config* cfg, const arreau_state_
     const float f16_slack = 64.0f * 65504.0f;
     m->edge_variant = env_int("ARREAU_EDGE_VARIANT", edge_bound <= f16_slack ? 4 : 3);
     m->mlp_variant = env_int("ARREAU_MLP_VARIANT", node_bound <= f16_slack ? 3 : 1);
+    // the training forward's fp16x3 products take the same operands: a model that starts a chain on bf16x6 trains on bf16x6
+    // products too (the fp16x3 training GEMM would overflow on its first step; arreau_model_set_variant overrides)
+    m->train_full_range = edge_bound > f16_slack || node_bound > f16_slack ? 1 : 0;
     m->conv_variant = env_int("ARREAU_CONV_VARIANT", 2);  // 2: basis form + conv_proj.hip; 1: K stash + streamed conv; 0: register conv
     m->readout_variant = env_int("ARREAU_READOUT_VARIANT", 1);
     m->ran_edge = m->ran_mlp = m->ran_conv = m->ran_readout = -1;

@@ -1601,7 +1601,7 @@ extern "C" int arreau_train_forward(arreau_model* m, const float* d_frac, const 
         }();
         // (fp16x3 while the weights fit fp16 and the caller has not asked for the full-range kernels -- arreau_model_set_variant(-1 or 3, 1),
         // what PONITA_DIFFUSION.training_step does after a non-finite step: the operand bounds of arreau_model_create do not follow
-        // the optimizer)
+        // the optimizer; arreau_model_create itself sets train_full_range for a model whose bounds start a chain on bf16x6)
         t.fwd_mode = env == 0 ? 0 : (m->f16_ok && !m->train_full_range ? 1 : 2);
         t.bwd_mode = env == 0 ? 0 : (env == 2 && m->f16_ok ? 1 : 2);
     }

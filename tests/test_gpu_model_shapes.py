@@ -4,7 +4,9 @@ the register conv and the k < 8 edge tiles, a single layer (no calibration, no b
 shortest schedule, and the shape-general fp32 path at C = 4, C = 12 and C = 1024 -- plus the values just past each edge,
 which must be refused before anything launches.  Every shape: scores (teacher-forced and own neighbour list), the kernel
 families the library reports, one reverse step at t = 1 and t = T, one training step against oracle autograd, and a
-short sample eager against graph replay.  Needs an MI355X: run with `-m gpu`."""
+short sample eager against graph replay.  Every fused shape runs twice: on the default kernels (fp16x3) and on the
+full-range ones (bf16x6: `set_variant(3, 1)`, what the library falls back to when a model outgrows fp16), which are
+documented as fp32-grade and so are held to the same bounds.  Needs an MI355X: run with `-m gpu`."""
 import copy
 from types import SimpleNamespace
 
@@ -40,8 +42,14 @@ SHAPES = {
 }
 
 
-def _shape(request):
-    kw = dict(SHAPES[request.param])
+# (shape, arithmetic): the fused shapes on both kernel sets (a full-range case's id carries "-full-range"; the default
+# cases keep the shape's id), the general shapes, which have no bf16x6 form, on their one path
+CASES = [(name, arith) for name in SHAPES for arith in ("default", "full range") if arith == "default" or name.startswith("fused")]
+CASE_IDS = [name if arith == "default" else name + "-full-range" for name, arith in CASES]
+
+
+def _shape(name):
+    kw = dict(SHAPES[name])
     kw.setdefault("num_timesteps", 20)
     S = kw.pop("S")
     hp = dict(S=S, T=kw["num_timesteps"], L=kw.get("layers", 5), k=kw.get("max_neighbors", 8), C=kw.get("hidden_dim", 128))
@@ -55,12 +63,17 @@ def dev():
     return torch.device("cuda", 0)
 
 
-@pytest.fixture(scope="module", params=list(SHAPES), ids=list(SHAPES))
+@pytest.fixture(scope="module", params=CASES, ids=CASE_IDS)
 def shape_model(dev, request):
     from arreau_amd.checkpoint import make_synthetic_model
-    S, kw, hp = _shape(request)
+    name, arith = request.param
+    S, kw, hp = _shape(name)
     m = make_synthetic_model(S=S, seed=2024, trained_like=True, **kw).to(dev)
-    return SimpleNamespace(m=m, om=oracle_from_module(m, F64), om32=oracle_from_module(m, torch.float32), name=request.param, **hp)
+    full_range = arith == "full range"
+    if full_range:
+        m.engine().set_variant(3, 1)
+    return SimpleNamespace(m=m, om=oracle_from_module(m, F64), om32=oracle_from_module(m, torch.float32),
+                           name=name + (" full range" if full_range else ""), full_range=full_range, **hp)
 
 
 def _concat(*states):
@@ -71,7 +84,8 @@ def _concat(*states):
 def _ragged_state(S, seed):
     """Physical cells (no exact image ties, so both neighbour lists choose the same set): a crystal of 33 atoms (two
     32-atom read-out tiles, five 8-atom vector read-out tiles), a 1-atom crystal in a 12-14 A cell (no neighbour within the
-    radius: fewer than k for every k), a 5-atom crystal and a sparse 3-atom crystal in a 10-12 A cell."""
+    radius: fewer than k for every k), a 5-atom crystal and a sparse 3-atom crystal in a 10-12 A cell.  42 atoms: not a
+    multiple of the 8 nodes per workgroup of the bf16x6 MLP kernel."""
     return _concat(random_state(S, [33], seed), random_state(S, [1], seed + 1, cell=(12.0, 14.0)),
                    random_state(S, [5], seed + 2), random_state(S, [3], seed + 3, cell=(10.0, 12.0)))
 
@@ -108,6 +122,9 @@ def _assert_scores_close_to_float64(got, want64, want32, tag, atoms_per_crystal=
 def _expected_families(sm, basis_form=False):
     if not sm.fused:
         return dict(edge_kernel="general-fp32-gemm", mlp_kernel="general-fp32-gemm", conv_variant=5, readout_kernel=5)
+    if sm.full_range:  # no basis form without the fp16x3 edge kernel (node.hip: arreau_basis_form): K pair at k = 8, else register
+        return dict(edge_kernel="bf16x6", mlp_kernel="bf16x6", conv_variant=1 if sm.k == 8 else 0,
+                    readout_kernel=1 if sm.S + 4 <= 96 else 0)
     # conv: 2 basis form (k = 8, L >= 2, enough receivers), 1 streamed K pair (k = 8), 0 register form (any k)
     conv = (2 if basis_form and sm.L >= 2 else 1) if sm.k == 8 else 0
     return dict(edge_kernel="fp16x3", mlp_kernel="fp16x3-16x16x32", conv_variant=conv,
@@ -131,6 +148,7 @@ def test_scores_match_float64_oracle(dev, shape_model, t_end):
     for teacher_forced in (True, False):
         got, want, want32, deg = _engine_scores(sm, dev, state, t, teacher_forced)
         assert int(deg.min()) == 0 and bool((deg < sm.k).any())  # the isolated atom, and atoms short of k neighbours
+        assert len(deg) % 8 != 0
         errs = _assert_scores_close_to_float64(got, want, want32, (sm.name, t, "given edges" if teacher_forced else "own edges"),
                                                atoms_per_crystal=33)
         worst = np.maximum(worst, errs)
@@ -160,8 +178,12 @@ def test_basis_form_when_enough_receivers(dev, shape_model, monkeypatch):
 @pytest.mark.parametrize("t_end", ["t=1", "t=T"])
 def test_reverse_step_matches_float64_oracle(dev, shape_model, t_end):
     """test_gpu_parity.py: test_reverse_step_matches_oracle at this shape's S and T, against the float64 oracle."""
-    sm = shape_model
-    S, t = sm.S, 1 if t_end == "t=1" else sm.T
+    _check_reverse_step(shape_model, dev, 1 if t_end == "t=1" else shape_model.T)
+
+
+def _check_reverse_step(sm, dev, t):
+    """One reverse step of the model `sm` (attributes m, om = float64 oracle, S) at timestep t against the float64 oracle."""
+    S = sm.S
     frac, types, lengths, angles, na = random_state(S, [4, 7, 1, 33], 50 + t, sampler_like=True)
     frac = frac % 1
     N, B = frac.shape[0], len(na)
@@ -198,9 +220,8 @@ def test_reverse_step_matches_float64_oracle(dev, shape_model, t_end):
 
 
 # ------------------------------------------------------------------------------------------- d. one training step
-def test_training_step_matches_float64_oracle_autograd(dev, shape_model):
-    sm = shape_model
-    S, T = sm.S, sm.T
+def _training_inputs(S, T):
+    """(batch, lattice0, timestep, noise) of a 4-crystal training step of 15 atoms, every random draw injected"""
     rng = np.random.RandomState(8)
     num_atoms = [3, 5, 1, 6]
     B, N = len(num_atoms), sum(num_atoms)
@@ -217,9 +238,18 @@ def test_training_step_matches_float64_oracle_autograd(dev, shape_model):
     # z_lengths: at t = T the noised cell IS this draw (alpha_bar ~ 0), so it is drawn as cell lengths of 6-8 A rather than N(0, 1),
     # which would give sub-angstrom cells full of exactly tied periodic images
     noise = (torch.randn(N, 3, generator=g), torch.rand(N, S, generator=g), 6.0 + 2.0 * torch.rand(B, 3, generator=g))
-    mm = copy.deepcopy(sm.m)
+    return batch, lattice0, timestep, noise
+
+
+def test_training_step_matches_float64_oracle_autograd(dev, shape_model):
+    """Under "full range" the training forward leaves the fused ConvNext launch for bf16x6 products (train_net.hip: fwd_mode 2)."""
+    sm = shape_model
+    batch, lattice0, timestep, noise = _training_inputs(sm.S, sm.T)
+    mm = copy.deepcopy(sm.m)  # (the copy packs its own engine: the arithmetic is chosen on it)
     for layer in mm.model.interaction_layers:
         layer.conv.callibrated.fill_(True)
+    if sm.full_range:
+        mm.engine(for_training=True).set_variant(3, 1)
     loss = mm.training_step(batch, timestep=timestep, noise=noise)
     om = sm.om
     for v in om.sd.values():
@@ -264,7 +294,8 @@ def test_sample_eager_and_graph_replay_agree(dev, shape_model):
     for use_graph in (False, True):
         torch.manual_seed(11); np.random.seed(11)
         runs.append(sm.m.sample(6, 5, VisualizationSetting.NONE, False, use_graph=use_graph, seed=123))
-        assert sm.m.engine().status()["flags"] == 0
+        st = sm.m.engine().status()
+        assert st["flags"] == 0 and st["edge_kernel"] == _expected_families(sm)["edge_kernel"], (sm.name, st)
     a, b = runs
     assert np.isfinite(a.frac_x).all() and np.isfinite(a.lattice).all()
     assert np.array_equal(a.frac_x, b.frac_x) and np.array_equal(a.atomic_numbers, b.atomic_numbers)

@@ -518,10 +518,17 @@ def test_loop_at_the_benchmark_size_is_bitwise_across_eager_graph_and_per_step(d
     from t = 999 through (i) the per-step entry points predict_scores + reverse_step fed with arreau_philox_fill's draws,
     (ii) arreau_sample_loop eager, (iii) arreau_sample_loop replayed as a hipGraph: the state after the stretch must be
     bit-identical in all three, and with fixed cell lengths (bench.py's d_fixed_lengths) eager and replay must agree."""
-    from arreau_amd.diffusion.diffusion_helpers import crystal_offsets
     m, _ = full_model
     eng = m.engine()
     eng.set_variant(4, 3)
+    loop_bitwise_across_eager_graph_and_per_step(eng, dict(conv_variant=2, edge_kernel="fp16x3", basis_row_bytes=768))
+
+
+def loop_bitwise_across_eager_graph_and_per_step(eng, families):
+    """The body of the test above on the engine `eng` (an S = 90, T = 1000 model) as it is set up; `families` are the
+    arreau_model_status entries its first step must report."""
+    from arreau_amd.diffusion.diffusion_helpers import crystal_offsets
+    dev = eng.device
     B, n, S, T, seed, steps = 256, 20, 90, 1000, 424242, 5
     N = B * n
     rng = np.random.RandomState(1000)
@@ -540,7 +547,7 @@ def test_loop_at_the_benchmark_size_is_bitwise_across_eager_graph_and_per_step(d
         eps, logits, len0 = eng.predict_scores(f, ty, le, an, t_c, off)
         if t == T - 1:
             st = eng.check_status()
-            assert st["conv_variant"] == 2 and st["edge_kernel"] == "fp16x3" and st["basis_row_bytes"] == 768, st
+            assert {k: st[k] for k in families} == families, st
         eng.reverse_step(f, ty, le, an, t_c, off, eps, logits, len0, eng.philox_fill(seed, t, 0, 3 * B).view(B, 3),
                          eng.philox_fill(seed, t, 1, 3 * N).view(N, 3), eng.philox_fill(seed, t, 2, N * S).view(N, S), lat)
     ref = (f, ty, le, lat)
@@ -548,7 +555,7 @@ def test_loop_at_the_benchmark_size_is_bitwise_across_eager_graph_and_per_step(d
     for use_graph in (False, True):
         out = fresh()
         eng.sample_loop(out[0], out[1], out[2], an, off, T - 1, steps, seed, None, out[3], use_graph=use_graph)
-        assert eng.check_status()["conv_variant"] == 2
+        assert eng.check_status()["conv_variant"] == families["conv_variant"]
         for name, a, b in zip(("frac", "types", "lengths", "lattice"), out, ref):
             assert torch.equal(a, b), (use_graph, name, int((a != b).sum()))
     fixed = d(lengths.clone())
@@ -946,16 +953,32 @@ def test_atom_permutation_equivariance(dev, small_model):
     assert_scores_close((b[0], b[1], b[2]), (a[0][perm].cpu(), a[1][perm].cpu(), a[2].cpu()))
 
 
-@pytest.mark.parametrize("message_path", ["K pair (the product's choice at this size)", "basis form"])
+# message path -> edge variant behind it
+EDGE_PATHS = {"K pair (the product's choice at this size)": 4, "basis form": 4, "K pair, bf16x6 edge kernel (variant 3)": 3,
+              "K pair, fp32-MFMA edge kernel (variant 0)": 0}
+
+
+@pytest.mark.parametrize("message_path", list(EDGE_PATHS))
 def test_many_ragged_crystals_persistent_edge_workgroups(dev, small_model, message_path, monkeypatch):
     """(Both message paths: below 2,000 receivers the product runs the K pair; ARREAU_BASIS_MIN_RECEIVERS=240 puts the same
-    batch through the basis form -- idle waves that store nothing, receivers of every degree in conv_proj_kernel.)
+    batch through the basis form -- idle waves that store nothing, receivers of every degree in conv_proj_kernel.  The K pair
+    also behind the two other edge kernels, edge_bf16.hip and edge.hip, which have no basis form: the unused-slot contract
+    holds for every edge kernel.)
     More receiver pairs than CUs, with degrees from 0 to the cap: every persistent edge-kernel workgroup walks
     several pairs (the weight ring wraps from one pair into the next) and mixes waves that have slots with waves
     that only keep the ring turning.  The network (edges teacher-forced) against the oracle."""
     if message_path == "basis form":
         monkeypatch.setenv("ARREAU_BASIS_MIN_RECEIVERS", "240")
     m, om32, _ = small_model
+    edge_variant = EDGE_PATHS[message_path]
+    m.engine().set_variant(edge_variant, -1)
+    try:
+        _many_ragged_crystals(dev, m, om32, edge_variant)
+    finally:
+        m.engine().set_variant(4, -1)
+
+
+def _many_ragged_crystals(dev, m, om32, edge_variant):
     rng = np.random.RandomState(5)
     num_atoms = [int(v) for v in rng.randint(1, 7, size=420)]  # about 1470 atoms -> about 735 pairs on 256 CUs
     state = random_state(12, num_atoms, 91, cell=(3.5, 9.0))
@@ -968,7 +991,9 @@ def test_many_ragged_crystals_persistent_edge_workgroups(dev, small_model, messa
     edges = tuple(x.to(dev).contiguous() for x in (deg, src, sdir, sdist))
     eps, logits, len0 = _engine_scores(m, dev, state, 60, edges=edges)
     assert_scores_close((eps, logits, len0), (eps_o, logits_o, len0_o))
-    assert m.engine().check_status()["conv_variant"] == (2 if message_path == "basis form" else 1)
+    st = m.engine().check_status()
+    assert st["conv_variant"] == (2 if os.environ.get("ARREAU_BASIS_MIN_RECEIVERS") else 1), st
+    assert st["edge_variant"] == edge_variant, st
     # slots past a receiver's degree are not inputs (include/arreau_hip.h, arreau_predict_scores): whatever a caller leaves
     # there -- NaN, infinities, a stale index -- the outputs are the same bits (the basis form's projection adds every slot's
     # block without a test, so the edge kernel must store exact zeros for those)

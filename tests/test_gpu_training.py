@@ -131,6 +131,42 @@ def _oracle_grads(om, batch, lattice0, timestep, noise):
     return float(loss), grads
 
 
+def _float64_oracle_grads(module, batch, lattice0, timestep, noise):
+    """(loss, gradients) of autograd through the oracle built from `module`'s current weights in float64"""
+    om64 = oracle_from_module(module, torch.float64)
+    b64 = SimpleNamespace(X0=batch.X0.double(), A0=batch.A0, L0=batch.L0.double(), num_atoms=batch.num_atoms)
+    torch.set_default_dtype(torch.float64)  # (the oracle, like the reference, builds its constant tables in the default dtype)
+    try:
+        return _oracle_grads(om64, b64, lattice0.double(), timestep, tuple(x.double() for x in noise))
+    finally:
+        torch.set_default_dtype(torch.float32)
+
+
+def assert_step_close_to_float64(module, loss, grads, batch, lattice0, timestep, noise, tag):
+    """One training step of the library -- `loss` and `grads` (name -> gradient) at `module`'s current weights -- against float64
+    oracle autograd: the loss within TOL of its magnitude, every gradient tensor within GRAD_TOL of its largest entry, each plus
+    twice the distance of float32 oracle autograd from float64 on the same inputs (what any float32 evaluation of this model
+    costs).  Every trainable tensor must be compared.  Returns (worst gradient error relative to its tensor's largest entry,
+    the float32 oracle's at the same tensor, name)."""
+    loss32, want32 = _oracle_grads(oracle_from_module(module, torch.float32), batch, lattice0, timestep, noise)
+    loss64, want64 = _float64_oracle_grads(module, batch, lattice0, timestep, noise)
+    err, err_o = abs(float(loss) - loss64), abs(loss32 - loss64)
+    assert err <= TOL * max(1.0, abs(loss64)) + 2 * err_o, (tag, "loss", float(loss), loss64, loss32)
+    params = {n for n, p in module.named_parameters() if p.requires_grad and p.numel() > 0}
+    checked, worst = set(), (0.0, 0.0, "")
+    for name, w64 in want64.items():
+        if w64.numel() == 0:
+            continue
+        scale = max(float(w64.abs().max()), 1e-7)
+        err = float((grads[name].cpu().double() - w64).abs().max())
+        err_o = float((want32[name].double() - w64).abs().max())
+        assert err <= GRAD_TOL * scale + 2 * err_o + 1e-7, (tag, name, err, err_o, scale)
+        worst = max(worst, (err / scale, err_o / scale, name))
+        checked.add(name)
+    assert checked == params, (tag, sorted(params ^ checked))
+    return worst
+
+
 def test_training_forward_matches_sampling_kernels(setup):
     """arreau_train_forward (fp32 GEMM form, activations kept) and arreau_predict_scores (fused fp16x3 kernels) evaluate
     the same network: outputs agree to the parity bound."""
@@ -383,7 +419,8 @@ def test_training_survives_weights_that_outgrow_the_fp16_forward(setup):
     moves the weights afterwards.  Here they are moved far beyond the fp16 range of the hidden activations between two steps:
     the step comes out non-finite, the optimizer driver turns it into a no-op on the device (no NaN reaches the parameters or
     Adam's moments), the periodic status check switches the engine to the full-range bf16x6 products instead of raising, and the
-    next step is finite again."""
+    next step is finite again -- and right: its loss and every gradient on the blown-up weights against float64 oracle autograd
+    (assert_step_close_to_float64), the same bits when it is repeated."""
     import copy
     import warnings
     from arreau_amd.train import optimizer_step
@@ -414,6 +451,18 @@ def test_training_survives_weights_that_outgrow_the_fp16_forward(setup):
     after_first = [p.detach() for p in mm.parameters()]
     assert all(torch.isfinite(a).all() for a in after_first) and len(before) == len(after_first)
     assert mm._engine.status()["flags"] == 0
+    # the full-range step against float64 (the gradients are views of the engine's buffer: copied before the next step)
+    grads = {n: p.grad.clone() for n, p in mm.named_parameters() if p.grad is not None}
+    worst = assert_step_close_to_float64(mm, loss3, grads, batch, lattice0, timestep, noise, "after the switch")
+    for _ in range(2):
+        again = mm.training_step(batch, timestep=timestep, noise=noise)
+        assert float(again) == float(loss3)
+        for n, p in mm.named_parameters():
+            if p.grad is not None:
+                assert torch.equal(p.grad, grads[n]), ("full-range step not bitwise repeatable", n)
+    assert mm._engine.status()["flags"] == 0
+    print(f"\n[full-range step after the switch] loss {float(loss3):.6f}; worst gradient error relative to its largest entry "
+          f"{worst[0]:.2e}, float32 oracle autograd {worst[1]:.2e} ({worst[2]})")
 
 
 def test_two_rank_training_loop_reduces_the_loss(tmp_path):
