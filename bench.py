@@ -23,6 +23,13 @@ single-crystal config): `loop_mode` names it, `eager_loop` / `graph_loop` hold b
 
 Prints ONE JSON line on rank 0 (see the keys at the bottom).
 
+A plain run sets up, warms up, times the K steps and prints the line: the headline and nothing else.  `--full` adds what
+the headline does not need: the CPU baseline, the step on the fp32-MFMA kernels, one whole measured sampler, the timed loop
+that is not the headline (graph replay for c1), the short legs of the other configurations that the one-GPU default run
+carries as `other_configs`, and c5's forward + backward loop with its roofline.  The default configuration's eager loop
+runs in a plain run too: its steps lead up to the timed graph replay, so they stay, and the roofline figure is read from
+them.
+
 `--dump-outputs DIR` also writes what the timed loop handed back after its last step as DIR/<name>.npy (sampling: frac,
 types, lengths, lattice; c5: loss, parameters), so that two builds can be compared output for output: the inputs are
 seeded, identical from run to run for the same arguments.
@@ -184,19 +191,22 @@ def parse_args(argv=None):
     ap.add_argument("--config", choices=sorted(CONFIGS), default=None, help="BASELINE configuration (default c2)")
     ap.add_argument("--batch-per-gpu", type=int, default=None, help="crystals per GPU (configs[1]: 256)")
     ap.add_argument("--atoms", type=int, default=None, help="atoms per crystal (configs[1]: 20)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fp32-variant", action="store_true", help="skip the second timed loop on the fp32-MFMA kernels")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need (CPU baseline, fp32-MFMA "
+                    "variant, whole sampler, the loop that is not the headline, other configurations, c5's forward + backward "
+                    "roofline); the --no-* options leave parts of it out")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-fp32-variant", action="store_true", help="--full: skip the second timed loop on the fp32-MFMA kernels")
     ap.add_argument("--cpu-steps", type=int, default=2)
     ap.add_argument("--hidden-dim", type=int, default=128, help="c5 only: hidden_dim of the trained network (the reference's "
                     "`make train` preset is 200; shapes other than 128 run on the shape-general kernels)")
-    ap.add_argument("--no-full-sampler", action="store_true", help="skip the measured run of the whole T-1 step sampler")
+    ap.add_argument("--no-full-sampler", action="store_true", help="--full: skip the measured run of the whole T-1 step sampler")
     ap.add_argument("--mlp-variant", type=int, default=3, help="ConvNext kernel set (3: default, picks its small-launch form by "
                     "size; 4: always the small-launch form; 0-2: cross-check arithmetic)")
     ap.add_argument("--no-graph-loop", action="store_true", help="time only the eager loop (profiling runs: per-kernel "
                     "statistics and PMC counters of whole-batch launches only); implies --eager-value")
     ap.add_argument("--eager-value", action="store_true", help="report the eager loop as `value` even where the product "
                     "defaults to graph replay")
-    ap.add_argument("--no-other-configs", action="store_true", help="default run only: skip the short legs of the other BASELINE "
+    ap.add_argument("--no-other-configs", action="store_true", help="--full default run only: skip the short legs of the other BASELINE "
                     "configurations (c1, c4, c5) that the one-GPU default run appends as `other_configs`")
     ap.add_argument("--groups", type=int, default=0, help="experiment, needs ARREAU_ALLOW_MULTISTREAM=1: slices of the batch on separate streams "
                     "(0 = the product: one stream; 2 was 3 %% faster at 256 x 20 but is not run-to-run reproducible)")
@@ -364,15 +374,15 @@ def gather_json(dist, where, world, obj, cap=2048):
 
 def other_config_legs():
     """Short legs of the other BASELINE configurations, each in a child process of its own (a fresh library state, the same
-    `python bench.py --config ...` a user would run; the parent has finished its GPU work), so that ONE default run -- the
-    command the driver times -- carries a measured figure for every configuration: c1 (configs[0]: 99 eager steps = one whole
+    `python bench.py --full --config ...` a user would run; the parent has finished its GPU work), so that ONE `--full` default
+    run carries a measured figure for every configuration: c1 (configs[0]: 99 eager steps = one whole
     sampler), c4 (configs[3]: graph replay at 1024 x 64), c5 (configs[4]: training steps).  No CPU baseline in the legs;
     `steps` / `warmup` of the headline are untouched.  Each record: ms_per_step, value, unit, loop_mode, the leg's own
     `roofline` block and config.workload."""
     legs = (("c1", ["--steps", "99", "--warmup", "20"]), ("c4", ["--steps", "5", "--warmup", "2"]), ("c5", ["--steps", "30", "--warmup", "8"]))
     out = {}
     for name, extra in legs:
-        cmd = [sys.executable, os.path.abspath(__file__), "--config", name, "--no-cpu-baseline", "--no-fp32-variant",
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--config", name, "--no-cpu-baseline", "--no-fp32-variant",
                "--no-full-sampler", "--no-other-configs"] + extra
         t0 = time.perf_counter()
         try:
@@ -535,8 +545,9 @@ def run_rank(args, rank, local_rank, world):
 
     # Loop 2, hipGraph replay of the captured step (arreau_sample_loop use_graph = 1) on one stream: bit-identical results,
     # what PONITA_DIFFUSION.sample runs by default for samplers of at least 200 steps (DiffusionLoss.sample).
-    # (--groups 2: the opt-in pipelined slices on two streams.)
-    if args.no_graph_loop:
+    # (--groups 2: the opt-in pipelined slices on two streams.)  A plain run times it only where it is the headline.
+    run_graph = not args.no_graph_loop and (args.full or production_graph)
+    if not run_graph:
         el_graph, per_rank_graph = el_eager, per_rank_eager
     else:
         run_steps(3, use_graph=True)  # warm-up of the graph path (capture, instantiation, stream / event creation)
@@ -554,7 +565,7 @@ def run_rank(args, rank, local_rank, world):
                  else "eager launches")
     eager_loop = {"steps": args.steps, "ms_per_step": 1e3 * el_eager / args.steps,
                   "note": "one launch per kernel and step; the edge-kernel hipEvents (roofline) are taken here"}
-    graph_loop = None if args.no_graph_loop else {"steps": args.steps, "ms_per_step": 1e3 * el_graph / args.steps, "slices": groups,
+    graph_loop = None if not run_graph else {"steps": args.steps, "ms_per_step": 1e3 * el_graph / args.steps, "slices": groups,
                   "note": "hipGraph replay of the captured step on one stream (bit-identical to the eager loop): "
                           "PONITA_DIFFUSION.sample's default for >= 200 sampler steps"}
 
@@ -563,7 +574,7 @@ def run_rank(args, rank, local_rank, world):
     # SampleResult copied back to the host), wall clock.  fixed_cell keeps the synthetic checkpoint's cells at the
     # sampler-start density, as in the timed loop above.
     full_sampler = None
-    if world == 1 and not args.no_full_sampler and B * n <= 256 * 20:
+    if args.full and world == 1 and not args.no_full_sampler and B * n <= 256 * 20:
         from arreau_amd.diffusion.inference.visualize_crystal import VisualizationSetting
         torch.manual_seed(5)
         np.random.seed(5)
@@ -579,7 +590,7 @@ def run_rank(args, rank, local_rank, world):
     # second, short timed loop on the exact fp32-MFMA kernels (v_mfma_f32_32x32x2_f32): what the same step costs
     # without the split-precision scheme, priced against the 157.3 TFLOP/s fp32 matrix peak
     fp32_variant = None
-    if not args.no_fp32_variant and world == 1:
+    if args.full and not args.no_fp32_variant and world == 1:
         eng.set_variant(0, 0)
         k32 = max(3, min(10, args.steps))
         run_steps(2)
@@ -748,9 +759,9 @@ def run_rank(args, rank, local_rank, world):
         }
         if timing_only:
             out["INVALID_timing_only_experiment"] = True
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(model, B, n, T, args.cpu_steps)
-        if args.config is None and world == 1 and not args.no_other_configs and not args.no_graph_loop and (B, n) == CONFIGS["c2"][:2]:
+        if args.full and args.config is None and world == 1 and not args.no_other_configs and not args.no_graph_loop and (B, n) == CONFIGS["c2"][:2]:
             del eng, model
             torch.cuda.empty_cache()
             out["other_configs"] = other_config_legs()
@@ -844,13 +855,15 @@ def run_rank_c5(args, rank, local_rank, world):
         params = torch.cat([p.detach().reshape(-1).float() for p in model.parameters() if p.requires_grad])
         dump_outputs(args.dump_outputs, {"loss": loss.detach().reshape(1).cpu().numpy(), "parameters": params.cpu().numpy()},
                      rank, world)
-    # device-only part (forward + backward, no optimizer / collective), for the roofline line
-    torch.cuda.synchronize(dev)
-    t1 = time.perf_counter()
-    for i in range(args.steps):
-        model.training_step(batches[i % len(batches)])
-    torch.cuda.synchronize(dev)
-    fb_ms = 1e3 * (time.perf_counter() - t1) / args.steps
+    # --full: device-only part (forward + backward, no optimizer / collective), for the roofline line
+    fb_ms = None
+    if args.full:
+        torch.cuda.synchronize(dev)
+        t1 = time.perf_counter()
+        for i in range(args.steps):
+            model.training_step(batches[i % len(batches)])
+        torch.cuda.synchronize(dev)
+        fb_ms = 1e3 * (time.perf_counter() - t1) / args.steps
     ranks_info = {"backend": (dist.get_backend() if dist is not None else None),
                   "world_size": (dist.get_world_size() if dist is not None else 1),
                   "data_path_collectives": 1 if (world > 1 or force_dist) else 0,
@@ -874,9 +887,10 @@ def run_rank_c5(args, rank, local_rank, world):
             "last_loss": float(loss),
             "ranks": ranks_info,
             "forward_backward_ms": fb_ms,
-            "roofline": training_roofline(flops, fb_ms, args.hidden_dim, B, alg_bytes=3.0 * step_bytes(n_atoms, 8 * n_atoms, B, C=args.hidden_dim)),
+            "roofline": None if fb_ms is None else training_roofline(flops, fb_ms, args.hidden_dim, B,
+                                                                     alg_bytes=3.0 * step_bytes(n_atoms, 8 * n_atoms, B, C=args.hidden_dim)),
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline_training(model, batches[0], args.cpu_steps)
         emit(out)
     if dist is not None:

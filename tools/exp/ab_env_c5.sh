@@ -11,7 +11,7 @@ envs, rep, i = sys.argv[1], sys.argv[2], sys.argv[3]
 env = dict(os.environ)
 for kv in envs.split():
     k, v = kv.split("=", 1); env[k] = v
-out = subprocess.run([sys.executable, "bench.py", "--config", "c5", "--steps", "60", "--warmup", "10", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=300)
+out = subprocess.run([sys.executable, "bench.py", "--full", "--config", "c5", "--steps", "60", "--warmup", "10", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=300)
 if out.returncode:
     print(out.stderr[-800:]); sys.exit(1)
 d = json.loads(out.stdout.strip().splitlines()[-1])

@@ -1,6 +1,6 @@
 """One training step of bench.py --config c5 as a launch list: kernel, grid, duration, gap to the previous launch.
 
-    rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 bench.py --config c5 --steps 4 --warmup 2 --no-cpu-baseline
+    rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 bench.py --full --config c5 --steps 4 --warmup 2 --no-cpu-baseline
     python3 tools/exp/c5_step_trace.py DIR  > step.txt
 
 The step is cut out of the trace as the launches between the last two `features_kernel` dispatches (first kernel of

@@ -1,23 +1,24 @@
 #!/bin/bash
 # usage: tools/hbm_traffic.sh [config]   (GPU box; config = c2 (default) | c3 | c4).  Two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE)
-# over the bench workload -> gpurun_out/hbm_traffic_pmc_<config>.json, one entry of the list bench.py reads from
+# over the bench workload -> $ARREAU_OUT/hbm_traffic_pmc_<config>.json, one entry of the list bench.py reads from
 # profiles/hbm_traffic_pmc.json.
 cfg=${1:-c2}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
+out=${ARREAU_OUT:-results}; mkdir -p "$out"  # where the results go (relative to the repository root)
 # (per-kernel means and counters of the WORKLOAD: without the three small evaluations of arreau_model_create's calibration batch, which
 # launch the same kernels on 320 atoms; the synthetic checkpoint keeps both fp8 formats either way)
 export ARREAU_CALIBRATE=0
 for c in FETCH_SIZE WRITE_SIZE; do
-  rm -rf gpurun_out/pmc_traffic_${cfg}_$c
-  timeout -k 10 400 rocprofv3 --kernel-trace --pmc $c --output-format csv -d gpurun_out/pmc_traffic_${cfg}_$c -- python3 bench.py --config $cfg --steps 4 --warmup 2 --no-cpu-baseline --no-graph-loop --no-full-sampler --no-fp32-variant > gpurun_out/pmc_traffic_${cfg}_$c.json 2> gpurun_out/pmc_traffic_${cfg}_$c.err || exit 1
+  rm -rf $out/pmc_traffic_${cfg}_$c
+  timeout -k 10 400 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $out/pmc_traffic_${cfg}_$c -- python3 bench.py --config $cfg --steps 4 --warmup 2 --no-cpu-baseline --no-graph-loop --no-full-sampler --no-fp32-variant > $out/pmc_traffic_${cfg}_$c.json 2> $out/pmc_traffic_${cfg}_$c.err || exit 1
 done
-python3 - $cfg <<'PY'
+python3 - $cfg "$out" <<'PY'
 import csv, glob, json, collections, sys
-cfg = sys.argv[1]
+cfg, res = sys.argv[1], sys.argv[2]
 B, n = {"c2": (256, 20), "c3": (1024, 20), "c4": (1024, 64)}[cfg]
 acc = collections.defaultdict(lambda: collections.defaultdict(list))
 for c in ("FETCH_SIZE", "WRITE_SIZE"):
-    for f in glob.glob("gpurun_out/pmc_traffic_%s_%s/*/*counter_collection.csv" % (cfg, c)):
+    for f in glob.glob("%s/pmc_traffic_%s_%s/*/*counter_collection.csv" % (res, cfg, c)):
         for r in csv.DictReader(open(f)):
             if r["Counter_Name"] == c:
                 acc[r["Kernel_Name"].split("(")[0]][c].append(float(r["Counter_Value"]))
@@ -42,7 +43,7 @@ for k, v in out["kernels"].items():
             step += mult * v["hbm_bytes_corrected"]
             break
 out["hbm_bytes_per_step_sampling_kernels"] = step
-json.dump(out, open("gpurun_out/hbm_traffic_pmc_%s.json" % cfg, "w"), indent=1)
+json.dump(out, open("%s/hbm_traffic_pmc_%s.json" % (res, cfg), "w"), indent=1)
 for k in ("edge_kernel", "conv_proj", "conv_kernel", "mlp_kernel"):
     for nme, v in out["kernels"].items():
         if k in nme:
