@@ -390,6 +390,37 @@ extern "C" int arreau_sample_loop_scheduled(arreau_model* m, float* d_frac, int3
 }
 
 namespace {
+// The key of a captured step: besides the buffers, sizes and seed, which kernels it holds depends on switches read per call
+// (ARREAU_BASIS_MIN_RECEIVERS, ARREAU_FUSE_SMALL) and on the variants, and the condition's pointers, the schedule's table and
+// clip, the corrector's step count and snr and the resampling's R and J (a resampled step reads the pass word) are kernel
+// arguments or launch choices of the capture: a change of any of them must not replay the stale graph.
+SampleGraphKey sample_graph_key(const arreau_model* m, const float* d_frac, const int32_t* d_types, const float* d_lengths,
+                                const float* d_angles, const int32_t* d_off, int32_t B, int32_t N, uint64_t seed,
+                                const int32_t* d_const_types, const float* d_fixed_lengths, const float* d_lattice,
+                                const void* d_workspace, bool no_prep, const SampleConditionDev& cond, bool scheduled,
+                                const StepScheduleDev& sched, const CorrectorDev& corr, const ResamplePlan* plan) {
+    SampleGraphKey k{};
+    k.frac = (uint64_t)d_frac; k.types = (uint64_t)d_types; k.lengths = (uint64_t)d_lengths; k.angles = (uint64_t)d_angles;
+    k.offsets = (uint64_t)d_off; k.const_types = (uint64_t)d_const_types; k.fixed_lengths = (uint64_t)d_fixed_lengths;
+    k.lattice = (uint64_t)d_lattice; k.workspace = (uint64_t)d_workspace; k.seed = seed;
+    k.cond_x0 = (uint64_t)cond.x0; k.cond_pos_mask = (uint64_t)cond.pos_mask; k.cond_a0 = (uint64_t)cond.a0;
+    k.cond_type_mask = (uint64_t)cond.type_mask; k.cond_l0 = (uint64_t)cond.l0; k.cond_len_mask = (uint64_t)cond.len_mask;
+    k.sched_next = (uint64_t)sched.next;
+    k.B = B; k.N = N;
+    k.edge_variant = m->edge_variant; k.mlp_variant = m->mlp_variant; k.conv_variant = m->conv_variant; k.no_prep = no_prep;
+    k.basis_form = arreau_basis_form(m, N); k.basis_fp8 = arreau_basis_fp8(m); k.cross_fp8 = arreau_cross_fp8(m);
+    k.small_layer_fusion = arreau_small_layer_fusable(m, N);
+    k.scheduled = scheduled;
+    memcpy(&k.clip_bits, &sched.clipmax, sizeof(k.clip_bits));
+    k.corrector_steps = corr.steps;
+    memcpy(&k.snr_bits, &corr.snr, sizeof(k.snr_bits));
+    if (plan) {
+        k.resample_passes = plan->passes;
+        k.resample_jump = plan->jump;
+    }
+    return k;
+}
+
 int sample_loop_impl(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles, const int32_t* d_off,
                      int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed, const int32_t* d_const_types,
                      const float* d_fixed_lengths, float* d_lattice, void* d_workspace, size_t workspace_bytes, int32_t use_graph,
@@ -450,7 +481,7 @@ int sample_loop_impl(arreau_model* m, float* d_frac, int32_t* d_types, float* d_
     const bool graph_mode = use_graph && n_runs >= 3;
     hipStream_t user = s;
     hipEvent_t ev = nullptr;
-    uint64_t key[22] = {};
+    SampleGraphKey key{};
     hipGraphExec_t exec = nullptr;
     bool have_exec = false;
     if (graph_mode) {
@@ -473,30 +504,11 @@ int sample_loop_impl(arreau_model* m, float* d_frac, int32_t* d_types, float* d_
         ARREAU_CHECK_HIP(hipStreamWaitEvent(s, ev, 0));
         // The executable graph is kept with the model and reused while the next call names the same buffers, sizes and seed
         // (a sampler drawing sub-batch after sub-batch through the caching allocator does): capture + instantiation, about
-        // 2 ms, are then paid once.  The timestep is not part of the graph (it lives in t_next / t_cur, set above).  The condition's
-        // pointers are kernel arguments of the capture: another condition is another graph; so are the schedule's table and clip,
-        // the corrector's step count and snr, and the resampling's R and J (a resampled step reads the pass word).
-        uint32_t clip_bits = 0, snr_bits = 0;
-        memcpy(&clip_bits, &sched_dev.clipmax, sizeof(clip_bits));
-        memcpy(&snr_bits, &corr.snr, sizeof(snr_bits));
-        const uint64_t k[22] = {(uint64_t)d_frac, (uint64_t)d_types, (uint64_t)d_lengths, (uint64_t)d_angles, (uint64_t)d_off,
-                                ((uint64_t)(uint32_t)B << 32) | (uint32_t)N, seed, (uint64_t)d_const_types, (uint64_t)d_fixed_lengths,
-                                (uint64_t)d_lattice, (uint64_t)d_workspace,
-                                ((uint64_t)(uint32_t)(m->edge_variant | (no_prep ? 0x10000 : 0) |
-                                                      // which kernels a capture holds also depends on switches read per call
-                                                      // (ARREAU_BASIS_MIN_RECEIVERS, ARREAU_FUSE_SMALL) and on the conv variant:
-                                                      // a changed switch must not replay the stale graph
-                                                      (arreau_basis_form(m, N) ? 0x20000 : 0) | (arreau_basis_fp8(m) ? 0x40000 : 0) | (arreau_cross_fp8(m) ? 0x400000 : 0) |
-                                                      (arreau_small_layer_fusable(m, N) ? 0x80000 : 0) |
-                                                      ((m->conv_variant & 3) << 20)) << 32) | (uint32_t)m->mlp_variant,
-                                (uint64_t)cond_dev.x0, (uint64_t)cond_dev.pos_mask, (uint64_t)cond_dev.a0, (uint64_t)cond_dev.type_mask,
-                                (uint64_t)cond_dev.l0, (uint64_t)cond_dev.len_mask, (uint64_t)sched_dev.next,
-                                ((uint64_t)(schedule ? 1 : 0) << 32) | clip_bits, ((uint64_t)(uint32_t)corr.steps << 32) | snr_bits,
-                                plan ? (((uint64_t)(uint32_t)plan->passes << 32) | (uint32_t)plan->jump) : 0};
-        static_assert(sizeof(k) == sizeof(m->graph_key), "graph key size");
-        memcpy(key, k, sizeof(k));
+        // 2 ms, are then paid once.  The timestep is not part of the graph (it lives in t_next / t_cur, set above).
+        key = sample_graph_key(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types, d_fixed_lengths, d_lattice,
+                               d_workspace, no_prep, cond_dev, schedule != nullptr, sched_dev, corr, plan);
         exec = (hipGraphExec_t)m->retired_graph;
-        have_exec = exec && memcmp(key, m->graph_key, sizeof(key)) == 0;
+        have_exec = exec && memcmp(&key, &m->graph_key, sizeof(key)) == 0;
     }
     const int32_t* pass = plan ? w.pass : nullptr;
     // one step of the trajectory: eager, or (graph mode) the first one eager and captured behind it, then replays
@@ -523,7 +535,7 @@ int sample_loop_impl(arreau_model* m, float* d_frac, int32_t* d_types, float* d_
             (void)hipGraphDestroy(graph);
             ARREAU_CHECK_HIP(e);
             arreau_model_retire_graph(m, (void*)exec, (void*)s);  // takes ownership; frees the previous one after its stream drained
-            memcpy(m->graph_key, key, sizeof(key));
+            m->graph_key = key;
             have_exec = true;
             return ARREAU_OK;
         }

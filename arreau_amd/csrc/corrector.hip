@@ -5,7 +5,7 @@
 //          segmented runs give the same bits);
 //   pass 2 applies x <- remainder(x - a eps + c z, 1), drawing z again instead of staging it (no size cap on the crystal).
 // z comes from the caller's array (arreau_corrector_step) or from Philox (seed, t, kind 5, element, iteration) in the loop
-// (256 r + iteration in pass r of a resampled loop: corrector_resample_kernel).
+// (256 r + iteration in pass r of a resampled loop: the RESAMPLE instance).
 #include <cmath>
 
 #include "update_dev.h"
@@ -13,15 +13,18 @@
 namespace {
 constexpr int CORR_THREADS = 256;
 
-// COND: a position mask is read (known atoms are not moved and not counted).  corrector_kernel<false> reads no mask.
-// Its twin corrector_resample_kernel (below) is a copy with the pass word: a change here belongs there too.
-template <bool COND>
+// COND: a position mask is read (known atoms are not moved and not counted).  corrector_kernel<false, ...> reads no mask.
+// RESAMPLE: a move of a resampled loop (arreau_sample_loop_resampled) in pass r of a block, r read from the loop's device word
+// `pass` (see reverse_kernel); its draws take counter word3 = 256 r + iter.  Without RESAMPLE `pass` is not read.
+template <bool COND, bool RESAMPLE>
 __global__ __launch_bounds__(CORR_THREADS) void corrector_kernel(float* __restrict__ frac, const int32_t* __restrict__ tstep,
                                                                  const int32_t* __restrict__ offsets, int T,
                                                                  const float* __restrict__ eps, const float* __restrict__ z_frac,
                                                                  uint64_t seed, uint32_t iter, float snr,
                                                                  const float* __restrict__ ve_sigmas,
-                                                                 const uint8_t* __restrict__ pos_mask, int32_t* __restrict__ status) {
+                                                                 const uint8_t* __restrict__ pos_mask, int32_t* __restrict__ status,
+                                                                 const int32_t* __restrict__ pass) {
+    if constexpr (RESAMPLE) iter += 256u * (uint32_t)pass[0];  // the counter word of pass r
     __shared__ float part[2][CORR_THREADS / 64];
     const int b = blockIdx.x;
     const int t_raw = tstep[b];
@@ -71,66 +74,6 @@ __global__ __launch_bounds__(CORR_THREADS) void corrector_kernel(float* __restri
     }
 }
 
-// Resampled loop (arreau_sample_loop_resampled): corrector_kernel in pass r of a block, r read from the loop's device word `pass`
-// (see reverse_resample_kernel); its draws take counter word3 = 256 r + iter.  A copy, not a shared inline body: the
-// existing instances keep their instructions.
-template <bool COND>
-__global__ __launch_bounds__(CORR_THREADS) void corrector_resample_kernel(float* __restrict__ frac, const int32_t* __restrict__ tstep,
-                                                                          const int32_t* __restrict__ offsets, int T,
-                                                                          const float* __restrict__ eps, const float* __restrict__ z_frac,
-                                                                          uint64_t seed, uint32_t iter, float snr,
-                                                                          const float* __restrict__ ve_sigmas,
-                                                                          const uint8_t* __restrict__ pos_mask, int32_t* __restrict__ status,
-                                                                          const int32_t* __restrict__ pass) {
-    iter += 256u * (uint32_t)pass[0];  // the counter word of pass r
-    __shared__ float part[2][CORR_THREADS / 64];
-    const int b = blockIdx.x;
-    const int t_raw = tstep[b];
-    if (threadIdx.x == 0 && (t_raw < 1 || t_raw > T)) atomicOr(status, ARREAU_STATUS_BAD_TIMESTEP);  // clamped, but flagged
-    const int t = t_raw < 1 ? 1 : (t_raw > T ? T : t_raw);
-    const int first = offsets[b], last = offsets[b + 1];
-    const size_t g0 = 3 * (size_t)first;
-    const int n3 = 3 * (last - first);
-    // (the array-or-generator choice is made on the kernel argument itself, as in reverse_one_atom)
-    const bool have_z = z_frac != nullptr;
-    auto draw_z = [&](size_t g) {
-        return have_z ? z_frac[g] : philox_normal(seed, (uint32_t)t, ARREAU_DRAW_Z_CORRECTOR, (uint32_t)g, iter);
-    };
-    float ee = 0.0f, zz = 0.0f;
-    for (int c = threadIdx.x; c < n3; c += CORR_THREADS) {
-        const size_t g = g0 + c;
-        if (COND && pos_mask[g / 3]) continue;
-        const float e = eps[g], z = draw_z(g);
-        ee = fmaf(e, e, ee);
-        zz = fmaf(z, z, zz);
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        ee += __shfl_xor(ee, off, 64);
-        zz += __shfl_xor(zz, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        part[0][threadIdx.x >> 6] = ee;
-        part[1][threadIdx.x >> 6] = zz;
-    }
-    __syncthreads();
-    ee = ((part[0][0] + part[0][1]) + part[0][2]) + part[0][3];
-    zz = ((part[1][0] + part[1][1]) + part[1][2]) + part[1][3];
-    // a = 2 r^2 sig^2 q^2, c = 2 r sig^2 q with q = |z| / |eps|: never 1 / sig^2 (the score's own size) at small sig
-    const float sig = ve_sigmas[t];
-    const float sig2 = sig * sig;
-    const float q = sqrtf(zz) / sqrtf(ee);
-    const float cz = 2.0f * snr * sig2 * q;
-    const float a = cz * snr * q;
-    // |eps|^2 of 0 or not finite (also: nothing to move), or coefficients beyond fp32: the crystal is left unmoved
-    if (!(ee > 0.0f && isfinite(ee) && isfinite(a) && isfinite(cz))) return;  // (block-uniform)
-    for (int c = threadIdx.x; c < n3; c += CORR_THREADS) {
-        const size_t g = g0 + c;
-        if (COND && pos_mask[g / 3]) continue;
-        const float d = cz * draw_z(g) - a * eps[g];
-        frac[g] = remainder_one(frac[g] + d);
-    }
-}
 }  // namespace
 
 int arreau_corrector_check(int32_t steps, float snr, const char* who) {
@@ -150,18 +93,10 @@ int arreau_launch_corrector(const arreau_model* m, float* d_frac, const int32_t*
                             const SampleConditionDev* cond, hipStream_t s, const int32_t* d_pass) {
     if (B <= 0 || N <= 0) return ARREAU_OK;
     const uint8_t* mask = (cond && cond->x0 && cond->pos_mask) ? cond->pos_mask : nullptr;
-    if (d_pass && mask)
-        ARREAU_LAUNCH(corrector_resample_kernel<true>, dim3(B), dim3(CORR_THREADS), 0, s, d_frac, d_t, d_off, m->T, d_eps, d_z_frac, seed,
-                      iter, snr, m->ve_sigmas, mask, m->status, d_pass);
-    else if (d_pass)
-        ARREAU_LAUNCH(corrector_resample_kernel<false>, dim3(B), dim3(CORR_THREADS), 0, s, d_frac, d_t, d_off, m->T, d_eps, d_z_frac, seed,
-                      iter, snr, m->ve_sigmas, (const uint8_t*)nullptr, m->status, d_pass);
-    else if (mask)
-        ARREAU_LAUNCH(corrector_kernel<true>, dim3(B), dim3(CORR_THREADS), 0, s, d_frac, d_t, d_off, m->T, d_eps, d_z_frac, seed, iter,
-                      snr, m->ve_sigmas, mask, m->status);
-    else
-        ARREAU_LAUNCH(corrector_kernel<false>, dim3(B), dim3(CORR_THREADS), 0, s, d_frac, d_t, d_off, m->T, d_eps, d_z_frac, seed,
-                      iter, snr, m->ve_sigmas, (const uint8_t*)nullptr, m->status);
+    auto kernel = mask ? (d_pass ? corrector_kernel<true, true> : corrector_kernel<true, false>)
+                       : (d_pass ? corrector_kernel<false, true> : corrector_kernel<false, false>);
+    ARREAU_LAUNCH(kernel, dim3(B), dim3(CORR_THREADS), 0, s, d_frac, d_t, d_off, m->T, d_eps, d_z_frac, seed, iter, snr, m->ve_sigmas,
+                  mask, m->status, d_pass);
     ARREAU_CHECK_HIP(hipGetLastError());
     return ARREAU_OK;
 }

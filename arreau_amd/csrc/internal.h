@@ -37,6 +37,26 @@ void arreau_set_error(const std::string& msg);
     } while (0)
 
 // Packed weights resident in HBM.  All pointers are device pointers into `blob`.
+// What the cached executable graph of arreau_sample_loop was captured for (api.hip: sample_graph_key): every input that decides
+// the kernels of a captured step or their arguments, one field each.  Only 64-bit and 32-bit words, no padding, so that a
+// value-initialised key compares with memcmp.
+struct SampleGraphKey {
+    // buffers and the Philox seed
+    uint64_t frac, types, lengths, angles, offsets, const_types, fixed_lengths, lattice, workspace, seed;
+    // conditioned sampling: the six pointers of the condition (null: none)
+    uint64_t cond_x0, cond_pos_mask, cond_a0, cond_type_mask, cond_l0, cond_len_mask;
+    uint64_t sched_next;  // respaced sampling: the next-timestep table
+    int32_t B, N;
+    // kernel choices: the variants, and the switches read per call (ARREAU_BASIS_MIN_RECEIVERS, ARREAU_FUSE_SMALL)
+    int32_t edge_variant, mlp_variant, conv_variant, no_prep, basis_form, basis_fp8, cross_fp8, small_layer_fusion;
+    int32_t scheduled;
+    uint32_t clip_bits;        // the schedule's lattice_clipmax
+    int32_t corrector_steps;
+    uint32_t snr_bits;         // the corrector's snr
+    int32_t resample_passes, resample_jump;  // 0, 0: no resampling
+};
+static_assert(sizeof(SampleGraphKey) == 17 * 8 + 16 * 4, "SampleGraphKey must have no padding (it is compared with memcmp)");
+
 struct arreau_model {
     arreau_config cfg;
     int S, C, D, L, O, W, H, k, T;
@@ -71,7 +91,7 @@ struct arreau_model {
     int packed_stale;        // 1 after arreau_model_update_train_weights: the sampling kernels' packed planes are out of date
     void* loop_stream;       // hipStream_t / hipEvent_t of arreau_sample_loop's graph mode (capture is not allowed on the
     void* loop_event;        //   legacy default stream callers usually pass); created on first use
-    uint64_t graph_key[22];  // what the cached executable graph of arreau_sample_loop was captured for
+    SampleGraphKey graph_key;  // what the cached executable graph of arreau_sample_loop was captured for
     void* retired_graph;     // hipGraphExec_t of the last arreau_sample_loop (+ the stream it was launched on): destroyed,
     void* retired_stream;    //   after that stream has drained, by the next loop or by arreau_model_destroy
     int32_t* status;         // device word of sticky ARREAU_STATUS_* bits (written by the kernels with atomicOr)

@@ -1416,7 +1416,7 @@ static int ensure_ctx(arreau_model* m, int N, int B, hipStream_t s) {
         arreau_train_ctx_destroy(t);
         m->train = nullptr;
         // a cached step graph of arreau_sample_loop (general path) points into the block just freed: never replay it
-        memset(m->graph_key, 0, sizeof(m->graph_key));
+        m->graph_key = SampleGraphKey{};
     }
     t = new arreau_train_ctx();
     t->defer = new arreau_train_ctx::Deferred();

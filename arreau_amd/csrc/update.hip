@@ -49,10 +49,12 @@ __device__ __forceinline__ void reverse_lattice_body(int gt /* global thread of 
 // crystals, four lanes each) run the lattice update, the others the atom update, one wave per atom.  The two parts touch
 // disjoint data (lengths / lattice / pooled read-out against coordinates / types), so nothing orders them.
 // COND: conditioned sampling (the condition argument is read); SCHED: a respaced step (the schedule argument is read: s from a
-// per-crystal array or the loop's next-timestep table).  reverse_kernel<false, false> is the plain kernel, whose helpers see a
-// null condition and a null schedule and compile to what they were before either existed.
-// Its twin reverse_resample_kernel (below) is a copy with the pass word: a change here belongs there too.
-template <bool COND, bool SCHED>
+// per-crystal array or the loop's next-timestep table).  reverse_kernel<false, false, false> is the plain kernel, whose helpers
+// see a null condition and a null schedule and compile to what they were before either existed.
+// RESAMPLE: a step of a resampled loop (arreau_sample_loop_resampled) in pass r of a block, r read from the loop's device word
+// `pass` (set by the jump in front of the pass, reset after the block), so one captured step serves every pass.  Every draw of
+// the step takes counter word3 = 256 r; pass 0 draws what the plain kernel draws.  Without RESAMPLE `pass` is not read.
+template <bool COND, bool SCHED, bool RESAMPLE>
 __global__ __launch_bounds__(256) void reverse_kernel(
     int lat_blocks, float* __restrict__ lengths, const float* __restrict__ angles, const int32_t* __restrict__ tstep,
     const int32_t* __restrict__ offsets, const float* __restrict__ len0, StepNoiseSrc noise, const float* __restrict__ alpha_bars,
@@ -64,41 +66,8 @@ __global__ __launch_bounds__(256) void reverse_kernel(
     const int32_t* __restrict__ batch,
     // sampling loop: the lattice part is one workgroup per crystal, which also prepares the next step (reverse_crystal_block)
     float* __restrict__ lattice_ws, float* __restrict__ cvec_next, const float* __restrict__ t_emb_w, const float* __restrict__ embT, int C,
-    SampleConditionDev cond_arg, StepScheduleDev sched_arg) {
-    const SampleConditionDev* cond = COND ? &cond_arg : nullptr;
-    const StepScheduleDev* sched = SCHED ? &sched_arg : nullptr;
-    if ((int)blockIdx.x < lat_blocks && cvec_next != nullptr) {  // (kernel argument: uniform)
-        reverse_crystal_block(b0 + (int)blockIdx.x, lengths, angles, tstep, offsets, len0, noise, alpha_bars, betas, T, lattice, fixed_lengths,
-                              status, gs_atoms, len0_out, lattice_ws, cvec_next, t_emb_w, embT, S, C, cond, sched, 0u);
-        return;
-    }
-    if ((int)blockIdx.x < lat_blocks) {
-        reverse_lattice_body(blockIdx.x * blockDim.x + threadIdx.x, lengths, angles, tstep, offsets, len0, noise, alpha_bars, betas, B_lat, T,
-                             lattice, fixed_lengths, status, b0, gs_atoms, len0_out, cond, sched, 0u);
-        return;
-    }
-    reverse_atoms_body((int)blockIdx.x - lat_blocks, frac, types, tstep, offsets, B, N, eps, logits, noise, ve_sigmas, q1t, qmats, S, T,
-                       const_types, absorbing, status, n0, batch, cond, sched, 0u);
-}
-
-// Resampled loop (arreau_sample_loop_resampled): reverse_kernel in pass r of a block, r read from the loop's device word `pass`
-// (set by the jump in front of the pass, reset after the block), so one captured step serves every pass.  Every draw of the
-// step takes counter word3 = 256 r; pass 0 draws what reverse_kernel draws.  A copy, not a shared inline body: the existing
-// instances keep their instructions.
-template <bool COND, bool SCHED>
-__global__ __launch_bounds__(256) void reverse_resample_kernel(
-    int lat_blocks, float* __restrict__ lengths, const float* __restrict__ angles, const int32_t* __restrict__ tstep,
-    const int32_t* __restrict__ offsets, const float* __restrict__ len0, StepNoiseSrc noise, const float* __restrict__ alpha_bars,
-    const float* __restrict__ betas, int B_lat, int T, float* __restrict__ lattice, const float* __restrict__ fixed_lengths,
-    int32_t* __restrict__ status, int b0, const float* __restrict__ gs_atoms, float* __restrict__ len0_out,
-    float* __restrict__ frac, int32_t* __restrict__ types, int B, int N, const float* __restrict__ eps,
-    const float* __restrict__ logits, const float* __restrict__ ve_sigmas, const float* __restrict__ q1t,
-    const float* __restrict__ qmats, int S, const int32_t* __restrict__ const_types, int absorbing, int n0,
-    const int32_t* __restrict__ batch,
-    // sampling loop: the lattice part is one workgroup per crystal, which also prepares the next step (reverse_crystal_block)
-    float* __restrict__ lattice_ws, float* __restrict__ cvec_next, const float* __restrict__ t_emb_w, const float* __restrict__ embT, int C,
     SampleConditionDev cond_arg, StepScheduleDev sched_arg, const int32_t* __restrict__ pass) {
-    const uint32_t word3 = 256u * (uint32_t)pass[0];  // the counter word of pass r
+    const uint32_t word3 = RESAMPLE ? 256u * (uint32_t)pass[0] : 0u;  // the counter word of pass r
     const SampleConditionDev* cond = COND ? &cond_arg : nullptr;
     const StepScheduleDev* sched = SCHED ? &sched_arg : nullptr;
     if ((int)blockIdx.x < lat_blocks && cvec_next != nullptr) {  // (kernel argument: uniform)
@@ -123,19 +92,12 @@ void enqueue_reverse_kernel(const arreau_model* m, int lat_blocks, int atom_bloc
                             float* d_lattice, hipStream_t s, const float* d_fixed_lengths, const float* d_gs_atoms,
                             const int32_t* d_batch, float* d_lattice_ws, float* d_cvec_next, const SampleConditionDev& cond,
                             const StepScheduleDev& sched, const int32_t* d_pass) {
-#define ARREAU_REVERSE_LAUNCH_ARGS                                                                                                 \
-    lat_blocks, d_lengths, d_angles, d_t, d_off, d_len0, noise, m->vp_alpha_bars, m->vp_betas, B, m->T, d_lattice, d_fixed_lengths, \
-        m->status, 0, d_gs_atoms, d_gs_atoms ? const_cast<float*>(d_len0) : nullptr, d_frac, d_types, B, N, d_eps, d_logits,        \
-        m->ve_sigmas, m->q1t, m->qmats, m->S, d_const_types, m->qmats_absorbing, 0, d_batch, d_lattice_ws, d_cvec_next, m->t_emb_w, \
-        m->embT, m->C, cond, sched
-    if (d_pass) {
-        auto kernel = reverse_resample_kernel<COND, SCHED>;
-        ARREAU_LAUNCH(kernel, dim3(lat_blocks + atom_blocks), dim3(256), 0, s, ARREAU_REVERSE_LAUNCH_ARGS, d_pass);
-    } else {
-        auto kernel = reverse_kernel<COND, SCHED>;
-        ARREAU_LAUNCH(kernel, dim3(lat_blocks + atom_blocks), dim3(256), 0, s, ARREAU_REVERSE_LAUNCH_ARGS);
-    }
-#undef ARREAU_REVERSE_LAUNCH_ARGS
+    auto kernel = d_pass ? reverse_kernel<COND, SCHED, true> : reverse_kernel<COND, SCHED, false>;
+    ARREAU_LAUNCH(kernel, dim3(lat_blocks + atom_blocks), dim3(256), 0, s, lat_blocks, d_lengths, d_angles, d_t, d_off, d_len0, noise,
+                  m->vp_alpha_bars, m->vp_betas, B, m->T, d_lattice, d_fixed_lengths, m->status, 0, d_gs_atoms,
+                  d_gs_atoms ? const_cast<float*>(d_len0) : nullptr, d_frac, d_types, B, N, d_eps, d_logits, m->ve_sigmas, m->q1t,
+                  m->qmats, m->S, d_const_types, m->qmats_absorbing, 0, d_batch, d_lattice_ws, d_cvec_next, m->t_emb_w, m->embT, m->C,
+                  cond, sched, d_pass);
 }
 }  // namespace
 

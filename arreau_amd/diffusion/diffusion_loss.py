@@ -414,17 +414,24 @@ class DiffusionLoss(nn.Module):
                         vis_crystal_during_sampling(z_table, types_d.cpu().numpy(), lattice_d.cpu().numpy(),
                                                     frac_d.cpu().numpy(), vis_name + f"_{steps[j]}", show_bonds, num_atoms.numpy())
             else:
+                if noise == "device":  # torch's device generator, in float32
+                    def gauss(*shape):
+                        return torch.randn(shape, **f32)
+
+                    def unif(*shape):
+                        return torch.rand(shape, **f32)
+                else:  # the global CPU generator in the default dtype, as the reference draws
+                    def gauss(*shape):
+                        return torch.randn(shape, dtype=dt).to(**f32)
+
+                    def unif(*shape):
+                        return torch.rand(shape, dtype=dt).to(**f32)
                 t_d = torch.empty(B, device=dev, dtype=torch.int32)
                 s_d = torch.empty(B, device=dev, dtype=torch.int32)
                 for ev in events:
                     timestep = ev.t
                     if ev.kind == "jump":  # resampling: the state back up to the block's top, in front of pass ev.r
-                        if noise == "device":
-                            z_f, z_l, u_t = torch.randn((N, 3), **f32), torch.randn((B, 3), **f32), torch.rand((N, S), **f32)
-                        else:
-                            z_f = torch.randn([N, 3], dtype=dt).to(**f32)
-                            z_l = torch.randn([B, 3]).to(**f32)
-                            u_t = torch.rand([N, S]).to(**f32)
+                        z_f, z_l, u_t = gauss(N, 3), gauss(B, 3), unif(N, S)
                         s_d.fill_(ev.s)
                         t_d.fill_(ev.t)
                         eng.resample_jump(frac_d, types_d, len_d, ang_d, s_d, t_d, off_d, z_f, z_l, u_t, lattice_d, const_types=const_d)
@@ -432,17 +439,9 @@ class DiffusionLoss(nn.Module):
                     t_d.fill_(timestep)
                     eps, logits, len0 = eng.predict_scores(frac_d, types_d, len_d, ang_d, t_d, off_d)
                     for _ in range(corrector_steps):  # predictor-corrector: the moves at t, each followed by a new evaluation
-                        z_c = torch.randn((N, 3), **f32) if noise == "device" else torch.randn([N, 3], dtype=dt).to(**f32)
-                        eng.corrector_step(frac_d, t_d, off_d, eps, z_c, corrector_snr)
+                        eng.corrector_step(frac_d, t_d, off_d, eps, gauss(N, 3), corrector_snr)
                         eps, logits, len0 = eng.predict_scores(frac_d, types_d, len_d, ang_d, t_d, off_d)
-                    if noise == "device":
-                        z_l = torch.randn((B, 3), **f32)
-                        z_f = torch.randn((N, 3), **f32)
-                        u_t = torch.rand((N, S), **f32)
-                    else:
-                        z_l = torch.randn([B, 3]).to(**f32)
-                        z_f = torch.randn([N, 3], dtype=dt).to(**f32)
-                        u_t = torch.rand([N, S]).to(**f32)
+                    z_l, z_f, u_t = gauss(B, 3), gauss(N, 3), unif(N, S)
                     if schedule is None:
                         eng.reverse_step(frac_d, types_d, len_d, ang_d, t_d, off_d, eps, logits, len0, z_l, z_f, u_t, lattice_d)
                     else:

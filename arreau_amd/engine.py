@@ -194,7 +194,8 @@ class HipEngine:
     def sample_loop(self, frac, types, lengths, angles, offsets, t_start, n_steps, seed, const_types, lattice_out,
                     use_graph=False, fixed_lengths=None, condition=None, next_table=None, lattice_clipmax=0.999, corrector=None,
                     resampling=None):
-        """n_steps iterations of the sampling loop in one library call (arreau_sample_loop): in-place update of
+        """n_steps iterations of the sampling loop in one library call (arreau_sample_loop; with any of the options below
+        arreau_sample_loop_resampled, whose NULL options are the loop without them): in-place update of
         (frac, types, lengths); Philox noise keyed by (seed, timestep, draw, element).  `condition`: the device arrays of a
         conditioned run (SampleCondition.device_arrays: x0, pos_mask, a0, type_mask, l0, len_mask; None entries allowed),
         through arreau_sample_loop_conditioned.  `next_table`: a respaced run (arreau_sample_loop_scheduled): the device
@@ -231,32 +232,15 @@ class HipEngine:
                     or not next_table.is_contiguous()):
                 raise ValueError(f"next_table must be a contiguous int32 tensor of shape ({T + 1},) on {self.device}")
             sched = _hip.SampleScheduleC(_hip.ptr(next_table).value, float(lattice_clipmax))
-        if res is not None:
-            cond = self._condition_struct(condition, N, B) if condition is not None else None
-            corr = _hip.CorrectorC(corrector[0], corrector[1]) if corrector is not None else None
-            _hip.check(_hip.lib().arreau_sample_loop_resampled(*args, ctypes.byref(cond) if cond is not None else None,
-                                                               ctypes.byref(sched) if sched is not None else None,
-                                                               ctypes.byref(corr) if corr is not None else None,
-                                                               ctypes.byref(res), _hip.stream_ptr(self.device)),
-                       "arreau_sample_loop_resampled")
-        elif corrector is not None:
-            cond = self._condition_struct(condition, N, B) if condition is not None else None
-            corr = _hip.CorrectorC(corrector[0], corrector[1])
-            _hip.check(_hip.lib().arreau_sample_loop_corrected(*args, ctypes.byref(cond) if cond is not None else None,
-                                                               ctypes.byref(sched) if sched is not None else None,
-                                                               ctypes.byref(corr), _hip.stream_ptr(self.device)),
-                       "arreau_sample_loop_corrected")
-        elif sched is not None:
-            cond = self._condition_struct(condition, N, B) if condition is not None else None
-            _hip.check(_hip.lib().arreau_sample_loop_scheduled(*args, ctypes.byref(cond) if cond is not None else None,
-                                                               ctypes.byref(sched), _hip.stream_ptr(self.device)),
-                       "arreau_sample_loop_scheduled")
-        elif condition is None:
+        cond = self._condition_struct(condition, N, B) if condition is not None else None
+        corr = _hip.CorrectorC(corrector[0], corrector[1]) if corrector is not None else None
+        if cond is None and sched is None and corr is None and res is None:
+            # (the plain entry point: A/B runs against an older library through ARREAU_HIP_LIB call it)
             _hip.check(_hip.lib().arreau_sample_loop(*args, _hip.stream_ptr(self.device)), "arreau_sample_loop")
-        else:
-            cond = self._condition_struct(condition, N, B)
-            _hip.check(_hip.lib().arreau_sample_loop_conditioned(*args, ctypes.byref(cond), _hip.stream_ptr(self.device)),
-                       "arreau_sample_loop_conditioned")
+            return
+        byref = lambda v: ctypes.byref(v) if v is not None else None
+        _hip.check(_hip.lib().arreau_sample_loop_resampled(*args, byref(cond), byref(sched), byref(corr), byref(res),
+                                                           _hip.stream_ptr(self.device)), "arreau_sample_loop_resampled")
 
     def condition_initial_state(self, frac, types, lengths, t_start, seed, condition):
         """Rule 5 of conditioned sampling (arreau_condition_initial_state): the known components of an initial state drawn

@@ -14,64 +14,40 @@ import torch.nn.functional as F
 
 from oracle import geometry as OG
 from oracle import sampler as OS
-from tests.helpers import oracle_from_module, random_state
+from tests.sampling_helpers import Case as _Case, S, T, any_model, dev, fused_model, wrapped_dist  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
-S, T = 12, 100
 COUNTS = [4, 7, 2, 150]  # ragged, one crystal above 128 atoms; crystal 2 is never conditioned
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch.device("cuda", 0)
+def model_seed():
+    return 1234
 
 
-def _model(dev, kind):
-    from arreau_amd.checkpoint import make_synthetic_model
-    shape = {} if kind == "fused" else dict(hidden_dim=64, basis_dim=96, widening_factor=2, layers=3)
-    m = make_synthetic_model(S=S, seed=1234, num_timesteps=T, **shape).to(dev)
-    return m, oracle_from_module(m, torch.float32)
-
-
-@pytest.fixture(scope="module")
-def fused_model(dev):
-    return _model(dev, "fused")
-
-
-@pytest.fixture(scope="module", params=["fused", "general-C64"])
-def any_model(dev, request, fused_model):
-    return fused_model if request.param == "fused" else _model(dev, request.param)
-
-
-class Case:
+class Case(_Case):
     """A ragged sampler-like state and a mixed condition: half the atoms of crystals 0 and 3 placed, crystal 1's species and
     some of crystal 3's known, the cells of crystals 0 and 1 known.  Crystal 2 is unconditioned."""
+    COUNTS = COUNTS
 
     def __init__(self, dev, seed=5):
-        frac, types, lengths, angles, na = random_state(S, COUNTS, seed, sampler_like=True)
+        super().__init__(dev, seed)
+        B, N = self.B, self.N
         rng = np.random.RandomState(seed + 100)
-        B, N = len(COUNTS), sum(COUNTS)
         first = np.concatenate([[0], np.cumsum(COUNTS)])
-        crystal = np.repeat(np.arange(B), COUNTS)
-        local = np.arange(N) - first[crystal]
-        self.pm = ((crystal == 0) | (crystal == 3)) & (local % 2 == 0)
-        self.tm = (crystal == 1) | ((crystal == 3) & (local % 3 == 1))
+        local = np.arange(N) - first[self.crystal]
+        self.pm = ((self.crystal == 0) | (self.crystal == 3)) & (local % 2 == 0)
+        self.tm = (self.crystal == 1) | ((self.crystal == 3) & (local % 3 == 1))
         self.lm = np.array([True, True, False, False])
         self.x0 = rng.uniform(0, 1, (N, 3)).astype(np.float32)
         self.a0 = rng.randint(0, S - 1, N).astype(np.int32)
         self.l0 = rng.uniform(3, 6, (B, 3)).astype(np.float32)
         self.g0 = np.deg2rad(rng.uniform(75, 105, (B, 3))).astype(np.float32)
-        angles = angles.clone()
-        angles[torch.as_tensor(self.lm)] = torch.as_tensor(self.g0)[torch.as_tensor(self.lm)]  # rule 3 (host side)
-        self.frac, self.types, self.lengths, self.angles, self.na = frac, types, lengths, angles, na
-        self.B, self.N, self.dev = B, N, dev
-        from arreau_amd.diffusion.diffusion_helpers import crystal_offsets
-        self.off = crystal_offsets(na, dev)
-        self.an = angles.to(dev).contiguous()
-        self.crystal = crystal
+        self.angles = self.angles.clone()
+        self.angles[torch.as_tensor(self.lm)] = torch.as_tensor(self.g0)[torch.as_tensor(self.lm)]  # rule 3 (host side)
+        self.an = self.angles.to(dev).contiguous()
 
     def cond(self, pm=None, tm=None, lm=None, x0=None):
         d = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a)).to(device=self.dev, dtype=dt).contiguous()
@@ -81,11 +57,6 @@ class Case:
         return dict(x0=d(self.x0 if x0 is None else x0, torch.float32), pos_mask=d(pm.astype(np.uint8), torch.uint8),
                     a0=d(self.a0, torch.int32), type_mask=d(tm.astype(np.uint8), torch.uint8), l0=d(self.l0, torch.float32),
                     len_mask=d(lm.astype(np.uint8), torch.uint8))
-
-    def fresh(self):
-        d = lambda v: v.to(self.dev).contiguous()
-        return (d(self.frac.clone()), d(self.types.to(torch.int32)), d(self.lengths.clone()),
-                torch.zeros(self.B, 3, 3, device=self.dev))
 
 
 def _run(eng, case, t_start, n_steps, seed, cond, use_graph=False, init=True, const=None, state=None):
@@ -116,11 +87,6 @@ def _rules_cpu(om, eng, seed, t, case, frac, types, lengths):
     return frac, types, lengths
 
 
-def _wrapped(a, b):
-    d = (a - b).abs()
-    return float(torch.minimum(d, 1 - d).max())
-
-
 # ----------------------------------------------------------------------------------------------------------------- 1, 6
 def test_conditioned_steps_against_a_cpu_restatement(dev, any_model):
     """Six conditioned steps (the initial state included), each from the device's state: the oracle's predict_scores +
@@ -133,7 +99,7 @@ def test_conditioned_steps_against_a_cpu_restatement(dev, any_model):
     f, ty, le, lat = case.fresh()
     eng.condition_initial_state(f, ty, le, T - 1, seed, cond)
     f_o, ty_o, le_o = _rules_cpu(om, eng, seed, T, case, case.frac, case.types, case.lengths)  # rule 5
-    assert _wrapped(f.cpu(), f_o) <= 1e-6 and torch.equal(ty.cpu().long(), ty_o)
+    assert float(wrapped_dist(f.cpu(), f_o).max()) <= 1e-6 and torch.equal(ty.cpu().long(), ty_o)
     assert float((le.cpu() - le_o).abs().max()) <= 1e-6 * max(1.0, float(le_o.abs().max()))
     for t in range(T - 1, T - 7, -1):
         frac, types, lengths = f.cpu(), ty.cpu().long(), le.cpu()
@@ -157,7 +123,7 @@ def test_conditioned_steps_against_a_cpu_restatement(dev, any_model):
         assert float((le.cpu() - le_o).abs().max()) <= TOL * max(1.0, float(le_o.abs().max())), t
         assert float((lat.cpu() - lat_o).abs().max()) <= TOL * max(1.0, float(lat_o.abs().max())), t
         pm, tm = torch.as_tensor(case.pm), torch.as_tensor(case.tm)
-        assert _wrapped(f.cpu()[pm], f_o[pm]) <= 1e-6, t  # the replaced components: the rules, to fp32 rounding
+        assert float(wrapped_dist(f.cpu()[pm], f_o[pm]).max()) <= 1e-6, t  # the replaced components: the rules, to fp32 rounding
         assert torch.equal(ty.cpu().long()[tm], ty_o[tm]), t
         assert int((ty.cpu().long() != ty_o).sum()) <= 1, t  # a Gumbel arg-max within rounding of a tie may go either way
     eng.check_status()

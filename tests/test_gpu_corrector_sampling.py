@@ -17,73 +17,19 @@ import torch.nn.functional as F
 from arreau_amd.diffusion import corrector as pc
 from arreau_amd.diffusion import respacing
 from oracle import sampler as OS
-from tests.helpers import oracle_from_module, random_state
+from tests.sampling_helpers import (Case as _Case, S, T, any_model, assert_same_bits, dev, full_i32, fused_model,  # noqa: F401
+                                     model_seed, wrapped_dist)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
-S, T = 12, 100
 COUNTS = [4, 7, 2, 150, 1]  # ragged, one crystal above 128 atoms, one single atom
 SNR = 0.16
 KIND = 5  # ARREAU_DRAW_Z_CORRECTOR
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch.device("cuda", 0)
-
-
-def _model(dev, kind):
-    from arreau_amd.checkpoint import make_synthetic_model
-    shape = {} if kind == "fused" else dict(hidden_dim=64, basis_dim=96, widening_factor=2, layers=3)
-    m = make_synthetic_model(S=S, seed=4321, num_timesteps=T, **shape).to(dev)
-    return m, oracle_from_module(m, torch.float32)
-
-
-@pytest.fixture(scope="module")
-def fused_model(dev):
-    return _model(dev, "fused")
-
-
-@pytest.fixture(scope="module", params=["fused", "general-C64"])
-def any_model(dev, request, fused_model):
-    return fused_model if request.param == "fused" else _model(dev, request.param)
-
-
-class Case:
-    def __init__(self, dev, seed=5, counts=COUNTS, sampler_like=True):
-        self.frac, self.types, self.lengths, self.angles, self.na = random_state(S, counts, seed, sampler_like=sampler_like)
-        from arreau_amd.diffusion.diffusion_helpers import crystal_offsets
-        self.B, self.N, self.dev = len(counts), sum(counts), dev
-        self.off = crystal_offsets(self.na, dev)
-        self.an = self.angles.to(dev).contiguous()
-        self.crystal = np.repeat(np.arange(self.B), counts)
-
-    def fresh(self):
-        d = lambda v: v.to(self.dev).contiguous()
-        return (d(self.frac.clone()), d(self.types.to(torch.int32)), d(self.lengths.clone()),
-                torch.zeros(self.B, 3, 3, device=self.dev))
-
-    def load(self, bufs):
-        """The initial state into existing buffers (a graph is cached for the buffers it was captured on)."""
-        for a, b in zip(bufs, self.fresh()):
-            a.copy_(b)
-        return bufs
-
-
-def _full(n, v, dev):
-    return torch.full((n,), v, device=dev, dtype=torch.int32)
-
-
-def _wrapped_dist(a, b):
-    dd = (a.double() - b.double()).abs()
-    return torch.minimum(dd, 1 - dd)
-
-
-def _same(got, want, what):
-    for a, b in zip(got, want):
-        assert torch.equal(a, b), what
+class Case(_Case):
+    COUNTS = COUNTS
 
 
 # -------------------------------------------------------------------------------------------------------------- 1
@@ -109,11 +55,11 @@ def test_corrector_step_against_the_restatement(dev, any_model, t, masked):
         cond = {"x0": x0.to(dev).contiguous(), "pos_mask": known.to(torch.uint8).to(dev).contiguous()}
     fd = f.to(dev).contiguous()
     eng.status(reset=True)
-    eng.corrector_step(fd, _full(B, t, dev), case.off, eps.to(dev).contiguous(), z.to(dev).contiguous(), SNR, condition=cond)
+    eng.corrector_step(fd, full_i32(B, t, dev), case.off, eps.to(dev).contiguous(), z.to(dev).contiguous(), SNR, condition=cond)
     want = pc.corrector_move(f.double().numpy(), eps.double().numpy(), z.double().numpy(), float(om.ve_sigmas[t]), SNR,
                              case.na.numpy(), known=None if known is None else known.numpy())
     got = fd.cpu()
-    assert float(_wrapped_dist(got, torch.from_numpy(want)).max()) <= TOL
+    assert float(wrapped_dist(got, torch.from_numpy(want)).max()) <= TOL
     unmoved = torch.as_tensor(case.crystal == 2)
     if masked:
         unmoved = unmoved | known
@@ -131,7 +77,7 @@ def test_out_of_range_timestep_is_flagged(dev, fused_model):
     for t in (0, T + 1, -4):
         eng.status(reset=True)
         f = case.fresh()[0]
-        eng.corrector_step(f, _full(case.B, t, dev), case.off, torch.ones(case.N, 3, device=dev), torch.ones(case.N, 3, device=dev),
+        eng.corrector_step(f, full_i32(case.B, t, dev), case.off, torch.ones(case.N, 3, device=dev), torch.ones(case.N, 3, device=dev),
                            SNR)
         assert eng.status(reset=True)["flags"] & _hip.STATUS_BAD_TIMESTEP, t
 
@@ -146,7 +92,7 @@ def test_bad_arguments_raise(dev, fused_model):
         with pytest.raises(ValueError):
             eng.sample_loop(f, ty, le, case.an, case.off, T - 1, 2, 1, None, lat, corrector=corr)
         with pytest.raises(ValueError):
-            eng.corrector_step(f, _full(case.B, 5, dev), case.off, f, f, corr[1] if corr[0] == 1 else -1.0)
+            eng.corrector_step(f, full_i32(case.B, 5, dev), case.off, f, f, corr[1] if corr[0] == 1 else -1.0)
     # the C entry point itself refuses them too (before it looks at anything else)
     lib = _hip.lib()
     for steps, snr in ((17, SNR), (1, float("inf")), (3, -1.0)):
@@ -182,7 +128,7 @@ def _one_by_one(eng, case, seed, M, schedule, respaced, snr=SNR):
     B, N = case.B, case.N
     f, ty, le, lat = case.fresh()
     for t, s in zip(schedule, schedule[1:] + [schedule[-1] - 1]):
-        t_c = _full(B, t, eng.device)
+        t_c = full_i32(B, t, eng.device)
         eps, logits, len0 = eng.predict_scores(f, ty, le, case.an, t_c, case.off)
         for j in range(M):
             eng.corrector_step(f, t_c, case.off, eps, eng.philox_fill_word(seed, t, KIND, j, 3 * N).view(N, 3), snr)
@@ -192,7 +138,7 @@ def _one_by_one(eng, case, seed, M, schedule, respaced, snr=SNR):
         if not respaced:
             eng.reverse_step(f, ty, le, case.an, t_c, case.off, eps, logits, len0, *noise, lat)
         else:
-            eng.reverse_step_to(f, ty, le, case.an, t_c, _full(B, s, eng.device), case.off, eps, logits, len0, *noise, lat, 0.999)
+            eng.reverse_step_to(f, ty, le, case.an, t_c, full_i32(B, s, eng.device), case.off, eps, logits, len0, *noise, lat, 0.999)
     return f, ty, le, lat
 
 
@@ -212,12 +158,12 @@ def test_corrected_loop_is_its_steps_one_by_one(dev, any_model, loop_prep, M, mo
     for use_graph in (False, True):
         got = case.fresh()
         eng.sample_loop(*got[:3], case.an, case.off, plain[0], k, seed, None, got[3], use_graph=use_graph, corrector=(M, SNR))
-        _same(got, want, ("one call", use_graph))
+        assert_same_bits(got, want, ("one call", use_graph))
     got = case.fresh()
     for lo, hi in ((0, 1), (1, 4), (4, 5)):  # segments (frames)
         eng.sample_loop(*got[:3], case.an, case.off, plain[lo], hi - lo, seed, None, got[3], use_graph=hi - lo >= 3,
                         corrector=(M, SNR))
-    _same(got, want, "segments")
+    assert_same_bits(got, want, "segments")
     # respaced: a correction at every scheduled timestep
     sched = [99, 80, 61, 40, 3, 2, 1]
     want = _one_by_one(eng, case, seed, M, sched, respaced=True)
@@ -226,12 +172,12 @@ def test_corrected_loop_is_its_steps_one_by_one(dev, any_model, loop_prep, M, mo
         got = case.fresh()
         eng.sample_loop(*got[:3], case.an, case.off, sched[0], len(sched), seed, None, got[3], use_graph=use_graph,
                         next_table=nxt, lattice_clipmax=0.999, corrector=(M, SNR))
-        _same(got, want, ("respaced", use_graph))
+        assert_same_bits(got, want, ("respaced", use_graph))
     got = case.fresh()
     for lo, hi in ((0, 3), (3, 4), (4, 7)):
         eng.sample_loop(*got[:3], case.an, case.off, sched[lo], hi - lo, seed, None, got[3], use_graph=hi - lo >= 3,
                         next_table=nxt, lattice_clipmax=0.999, corrector=(M, SNR))
-    _same(got, want, "respaced segments")
+    assert_same_bits(got, want, "respaced segments")
     eng.check_status()
 
 
@@ -245,7 +191,7 @@ def test_changed_corrector_never_replays_a_stale_graph(dev, any_model):
         eng.sample_loop(*bufs[:3], case.an, case.off, T - 1, k, seed, None, bufs[3], use_graph=True, corrector=corr)
         want = case.fresh()
         eng.sample_loop(*want[:3], case.an, case.off, T - 1, k, seed, None, want[3], use_graph=False, corrector=corr)
-        _same(bufs, want, corr)
+        assert_same_bits(bufs, want, corr)
     eng.check_status()
 
 
@@ -268,8 +214,8 @@ def test_zero_steps_is_todays_sampler(dev, any_model):
                             next_table=nxt, corrector=corr)
             runs.append(got)
         for r in runs[1:3]:
-            _same(r, runs[0], ("plain", use_graph))
-        _same(runs[4], runs[3], ("scheduled", use_graph))
+            assert_same_bits(r, runs[0], ("plain", use_graph))
+        assert_same_bits(runs[4], runs[3], ("scheduled", use_graph))
     torch.manual_seed(3)
     np.random.seed(3)
     a = m.sample([4, 7, 1], 3, seed=777, max_steps=30, fixed_cell=True)
@@ -347,7 +293,7 @@ def test_corrected_trajectory_against_the_oracle(dev, any_model, counts):
     fixed = le.clone()
     for t in range(T - 1, T - 6, -1):
         frac, types, lengths = f.cpu(), ty.cpu().long(), le.cpu()
-        t_c = _full(B, t, dev)
+        t_c = full_i32(B, t, dev)
         onehot = F.one_hot(types, S)
         # the corrector move: the restatement on the oracle's eps against the device's move on its own eps
         sig = float(om.ve_sigmas[t])
@@ -362,11 +308,11 @@ def test_corrected_trajectory_against_the_oracle(dev, any_model, counts):
         # 1e-5 relative to the unwrapped value, plus the eps bound carried through the step size
         move, carried = _move_and_bound(eps_o, z.cpu(), sig, case.na, eps_tol)
         pre = frac.double() + move
-        assert (_wrapped_dist(fc.cpu(), torch.from_numpy(want)) <= TOL * pre.abs().clamp(min=1.0) + carried).all(), t
+        assert (wrapped_dist(fc.cpu(), torch.from_numpy(want)) <= TOL * pre.abs().clamp(min=1.0) + carried).all(), t
         # ... and the move itself, restated on the device's eps: within 1e-5 of the unwrapped value
         own = pc.corrector_move(frac.double().numpy(), eps_d.cpu().double().numpy(), z.cpu().double().numpy(), sig, SNR,
                                 case.na.numpy())
-        assert (_wrapped_dist(fc.cpu(), torch.from_numpy(own)) <= TOL * pre.abs().clamp(min=1.0)).all(), t
+        assert (wrapped_dist(fc.cpu(), torch.from_numpy(own)) <= TOL * pre.abs().clamp(min=1.0)).all(), t
         # the predictor, on the device's corrected state
         frac_c = fc.cpu()
         scores = OS.predict_scores(om, frac_c, onehot, torch.full((N,), t), case.na, lengths, case.angles, batch)
@@ -377,7 +323,7 @@ def test_corrected_trajectory_against_the_oracle(dev, any_model, counts):
         s2, sp2 = float(om.ve_sigmas[t]) ** 2, float(om.ve_sigmas[t - 1]) ** 2
         pre = frac_c.double() - scores[0].double() * (s2 - sp2)
         bound = TOL * pre.abs().clamp(min=1.0) + TOL * max(1.0, float(scores[0].abs().max())) * (s2 - sp2)
-        assert (_wrapped_dist(f.cpu(), fr_o) <= bound).all(), t
+        assert (wrapped_dist(f.cpu(), fr_o) <= bound).all(), t
         assert torch.equal(le, fixed), t
         assert int((ty.cpu().long() != ty_o).sum()) <= 1, t  # a Gumbel arg-max within rounding of a tie may go either way
         ty.copy_(ty_o.to(torch.int32).to(dev))  # (teacher-forced: such a tie must not fork the rest of the trajectory)

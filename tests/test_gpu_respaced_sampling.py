@@ -16,56 +16,17 @@ import torch.nn.functional as F
 from arreau_amd.diffusion import respacing
 from oracle import geometry as OG
 from oracle import sampler as OS
-from tests.helpers import oracle_from_module, random_state
+from tests.sampling_helpers import Case as _Case, S, T, any_model, dev, full_i32, fused_model, model_seed, wrapped_dist  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
-S, T = 12, 100
 COUNTS = [4, 7, 2, 150]  # ragged, one crystal above 128 atoms
 CLIP = 0.999
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.fixture(scope="module")
-def dev():
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch.device("cuda", 0)
-
-
-def _model(dev, kind):
-    from arreau_amd.checkpoint import make_synthetic_model
-    shape = {} if kind == "fused" else dict(hidden_dim=64, basis_dim=96, widening_factor=2, layers=3)
-    m = make_synthetic_model(S=S, seed=4321, num_timesteps=T, **shape).to(dev)
-    return m, oracle_from_module(m, torch.float32)
-
-
-@pytest.fixture(scope="module")
-def fused_model(dev):
-    return _model(dev, "fused")
-
-
-@pytest.fixture(scope="module", params=["fused", "general-C64"])
-def any_model(dev, request, fused_model):
-    return fused_model if request.param == "fused" else _model(dev, request.param)
-
-
-class Case:
-    def __init__(self, dev, seed=5, counts=COUNTS):
-        self.frac, self.types, self.lengths, self.angles, self.na = random_state(S, counts, seed, sampler_like=True)
-        from arreau_amd.diffusion.diffusion_helpers import crystal_offsets
-        self.B, self.N, self.dev = len(counts), sum(counts), dev
-        self.off = crystal_offsets(self.na, dev)
-        self.an = self.angles.to(dev).contiguous()
-        self.crystal = np.repeat(np.arange(self.B), counts)
-
-    def fresh(self):
-        d = lambda v: v.to(self.dev).contiguous()
-        return (d(self.frac.clone()), d(self.types.to(torch.int32)), d(self.lengths.clone()),
-                torch.zeros(self.B, 3, 3, device=self.dev))
-
-
-def _full(n, v, dev):
-    return torch.full((n,), v, device=dev, dtype=torch.int32)
+class Case(_Case):
+    COUNTS = COUNTS
 
 
 # ---------------------------------------------------------------------------------- the rules, restated in float64
@@ -101,11 +62,6 @@ def _step_cpu(om, frac, types, lengths, angles, na, scores, t, s, z_l, z_f, u):
     return fr, torch.argmax(val, dim=-1), le, OG.lattice_from_params(le, d(angles)), top2[:, 0] - top2[:, 1]
 
 
-def _wrapped_close(a, b, atol):
-    dd = (a.double() - b.double()).abs()
-    return float(torch.minimum(dd, 1 - dd).max()) <= atol
-
-
 # -------------------------------------------------------------------------------------------------------------- 1
 @pytest.mark.parametrize("t,s", [(99, 80), (50, 10), (7, 1), (2, 1), (1, 0), (60, 59)])
 def test_reverse_step_to_against_the_restatement(dev, fused_model, t, s):
@@ -122,11 +78,11 @@ def test_reverse_step_to_against_the_restatement(dev, fused_model, t, s):
     f, ty, le, lat = case.fresh()
     ty.copy_(torch.randint(0, S, (N,), generator=g).to(dev))  # every class as x_t, the mask class included
     x_t = ty.cpu().long()
-    eng.reverse_step_to(f, ty, le, case.an, _full(B, t, dev), _full(B, s, dev), case.off, dd(eps), dd(logits), dd(len0),
+    eng.reverse_step_to(f, ty, le, case.an, full_i32(B, t, dev), full_i32(B, s, dev), case.off, dd(eps), dd(logits), dd(len0),
                         dd(z_l), dd(z_f), dd(u), lat, CLIP)
     fr_o, ty_o, le_o, lat_o, margin = _step_cpu(om, case.frac, x_t, case.lengths, case.angles, case.na,
                                                 (eps, logits, len0), t, s, z_l, z_f, u)
-    assert _wrapped_close(f.cpu(), fr_o, TOL), float((f.cpu().double() - fr_o).abs().max())
+    assert float(wrapped_dist(f.cpu(), fr_o).max()) <= TOL, float((f.cpu().double() - fr_o).abs().max())
     assert float((le.cpu().double() - le_o).abs().max()) <= TOL * max(1.0, float(le_o.abs().max()))
     assert float((lat.cpu().double() - lat_o).abs().max()) <= TOL * max(1.0, float(lat_o.abs().max()))
     diff = ty.cpu().long() != ty_o
@@ -135,7 +91,7 @@ def test_reverse_step_to_against_the_restatement(dev, fused_model, t, s):
     if s == t - 1:  # rule 4: bit for bit arreau_reverse_step
         f2, ty2, le2, lat2 = case.fresh()
         ty2.copy_(dd(x_t.to(torch.int32)))
-        eng.reverse_step(f2, ty2, le2, case.an, _full(B, t, dev), case.off, dd(eps), dd(logits), dd(len0), dd(z_l), dd(z_f),
+        eng.reverse_step(f2, ty2, le2, case.an, full_i32(B, t, dev), case.off, dd(eps), dd(logits), dd(len0), dd(z_l), dd(z_f),
                          dd(u), lat2)
         for a, b in zip((f, ty, le, lat), (f2, ty2, le2, lat2)):
             assert torch.equal(a, b)
@@ -152,7 +108,7 @@ def test_bad_targets_are_flagged(dev, fused_model):
     for t, s in ((10, 10), (10, -1), (10, 0), (1, 1)):
         eng.status(reset=True)
         f, ty, le, lat = case.fresh()
-        eng.reverse_step_to(f, ty, le, case.an, _full(B, t, dev), _full(B, s, dev), case.off, z(N, 3), z(N, S), z(B, 3),
+        eng.reverse_step_to(f, ty, le, case.an, full_i32(B, t, dev), full_i32(B, s, dev), case.off, z(N, 3), z(N, S), z(B, 3),
                             z(B, 3), z(N, 3), z(N, S) + 0.5, lat, CLIP)
         assert eng.status(reset=True)["flags"] & _hip.STATUS_BAD_TIMESTEP, (t, s)
 
@@ -174,9 +130,9 @@ def test_respaced_loop_is_its_steps_one_by_one(dev, any_model, loop_prep, monkey
     nxt = respacing.next_table(T, sched).to(dev)
     f, ty, le, lat = case.fresh()
     for t, s in zip(sched, sched[1:] + [0]):
-        t_c = _full(B, t, dev)
+        t_c = full_i32(B, t, dev)
         eps, logits, len0 = eng.predict_scores(f, ty, le, case.an, t_c, case.off)
-        eng.reverse_step_to(f, ty, le, case.an, t_c, _full(B, s, dev), case.off, eps, logits, len0,
+        eng.reverse_step_to(f, ty, le, case.an, t_c, full_i32(B, s, dev), case.off, eps, logits, len0,
                             eng.philox_fill(seed, t, 0, 3 * B).view(B, 3), eng.philox_fill(seed, t, 1, 3 * N).view(N, 3),
                             eng.philox_fill(seed, t, 2, N * S).view(N, S), lat, CLIP)
     want = (f, ty, le, lat)
