@@ -27,7 +27,7 @@ EXPORTS = [
     "arreau_sample_loop_conditioned", "arreau_condition_initial_state",
     "arreau_sample_loop_scheduled", "arreau_reverse_step_to",
     "arreau_sample_loop_corrected", "arreau_corrector_step", "arreau_philox_fill_word",
-    "arreau_sample_loop_resampled", "arreau_resample_jump",
+    "arreau_sample_loop_resampled", "arreau_resample_jump", "arreau_optimizer_step_ema",
 ]
 
 STATUS_NONFINITE, STATUS_BAD_TIMESTEP, STATUS_BAD_TYPE = 1, 2, 4
@@ -173,6 +173,9 @@ def lib():
         L.arreau_optimizer_step.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(AdamArgs), c_void_p, c_void_p]
         L.arreau_optimizer_destroy.argtypes = [c_void_p]
         L.arreau_optimizer_destroy.restype = None
+    if hasattr(L, "arreau_optimizer_step_ema") or not os.environ.get("ARREAU_HIP_LIB"):  # (an older build under test)
+        L.arreau_optimizer_step_ema.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(AdamArgs), c_void_p, c_double, c_void_p,
+                                                c_void_p]
     L.arreau_debug_set_pollution.argtypes = [ctypes.c_uint32]
     L.arreau_debug_leftover_fraction.argtypes = [ctypes.c_uint32, POINTER(c_double), POINTER(c_double), c_void_p]
     L.arreau_profile_edge_kernel.argtypes = [c_int32]

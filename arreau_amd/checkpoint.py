@@ -8,6 +8,7 @@ package's class when loading and restored when saving, so files round-trip with 
 """
 import argparse
 import contextlib
+import os
 import pickle
 import sys
 import types
@@ -81,10 +82,15 @@ def _reference_class_paths():
                 sys.modules[name] = mod
 
 
-def save_lightning_checkpoint(path, module, include_ori_grid=True):
-    """Write `module` (a PONITA_DIFFUSION) as a Lightning-format checkpoint."""
+def save_lightning_checkpoint(path, module, include_ori_grid=True, weights=None):
+    """Write `module` (a PONITA_DIFFUSION) as a Lightning-format checkpoint.  `weights` {state_dict key: tensor}: values written in
+    place of the module's own (save_ema_checkpoint)."""
     from .lightning_wrappers.diffusion import ORI_GRID_KEY
     sd = {k: v.detach().cpu() for k, v in module.state_dict().items()}
+    for k, v in (weights or {}).items():
+        if k not in sd or tuple(v.shape) != tuple(sd[k].shape):
+            raise ValueError(f"{k}: not an entry of the module's state_dict with shape {tuple(v.shape)}")
+        sd[k] = v.detach().to("cpu", sd[k].dtype).clone()
     if include_ori_grid:
         sd[ORI_GRID_KEY] = module.model.ori_grid.detach().cpu().clone()
     ckpt = {
@@ -96,6 +102,23 @@ def save_lightning_checkpoint(path, module, include_ori_grid=True):
     with _reference_class_paths():
         torch.save(ckpt, path)
     return path
+
+
+def ema_checkpoint_path(path):
+    """Where the EMA twin of checkpoint `path` goes: the extension replaced by `-EMA` plus the extension (the reference's EMA
+    callback, lightning_wrappers/callbacks.py:113-170: `model.ckpt` -> `model-EMA.ckpt`)."""
+    root, ext = os.path.splitext(os.fspath(path))
+    return f"{root}-EMA{ext}"
+
+
+def save_ema_checkpoint(path, module, ema_optimizer):
+    """Write the EMA twin of checkpoint `path` (ema_checkpoint_path) for `module` trained with `ema_optimizer`
+    (arreau_amd.optim.EMAOptimizer): its state_dict holds the average of every parameter the optimizer steps; buffers, the
+    orientation grid and the hyper-parameters are the module's.  PONITA_DIFFUSION.load_from_checkpoint reads it as it reads any
+    checkpoint.  Returns the path written."""
+    names = {id(p): k for k, p in module.named_parameters()}
+    weights = {names[id(p)]: e for p, e in zip(ema_optimizer.all_parameters(), ema_optimizer.ema_params) if id(p) in names}
+    return save_lightning_checkpoint(ema_checkpoint_path(path), module, weights=weights)
 
 
 def default_args(**overrides):

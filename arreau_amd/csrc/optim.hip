@@ -16,6 +16,12 @@
 //     p -= (lr / (1 - beta1^t)) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
 // The moments live in two flat buffers of the CALLER (torch tensors: they are the optimizer's state_dict), laid out like the
 // gradient buffer; parameters stay where the module keeps them (a table of device pointers, built once).
+//
+// arreau_optimizer_step_ema is the same launch pair with one more flat stream of the caller, an exponential moving average of the
+// weights (NeMo's EMAOptimizer, lightning_wrappers/callbacks.py:173-180: torch._foreach_mul_ then torch._foreach_add_ with
+// alpha = 1 - decay), updated from the new value while it is still in a register:
+//     e = e * d + w * p_new          (d = decay, w = 1 - decay, both formed in double and rounded once)
+// It is a second instance of adam_kernel (EMA = true): the instance without it has no per-element branch and gives the bits it gave.
 #include <stdint.h>
 
 #include <vector>
@@ -66,9 +72,11 @@ struct AdamHyper {
     float max_norm;                             // <= 0: no clipping (the norm is still reported)
 };
 
+template <bool EMA>
 __global__ __launch_bounds__(256) void adam_kernel(const OptChunk* __restrict__ chunks, const float* __restrict__ grad,
                                                    float* __restrict__ exp_avg, float* __restrict__ exp_avg_sq,
-                                                   const double* __restrict__ part, AdamHyper h, float* __restrict__ norm_out) {
+                                                   const double* __restrict__ part, AdamHyper h, float* __restrict__ norm_out,
+                                                   float* __restrict__ ema, float ema_d, float ema_w) {
     __shared__ double sh[256];
     sh[threadIdx.x] = threadIdx.x < OPT_PARTS ? part[threadIdx.x] : 0.0;
     __syncthreads();
@@ -98,6 +106,7 @@ __global__ __launch_bounds__(256) void adam_kernel(const OptChunk* __restrict__ 
         const float pn = p - step_size * (m / denom);
         c.p[i] = pn;
         if (c.mirror) c.mirror[i] = pn;
+        if constexpr (EMA) ema[c.off + i] = fmaf(ema_w, pn, ema[c.off + i] * ema_d);  // (torch: mul_ rounds, then add_ with alpha)
     }
 }
 }  // namespace
@@ -160,12 +169,14 @@ extern "C" void arreau_optimizer_destroy(arreau_optimizer* o) {
     delete o;
 }
 
-extern "C" int arreau_optimizer_step(arreau_optimizer* o, const float* d_flat_grad, float* d_exp_avg, float* d_exp_avg_sq,
-                                     const arreau_adam_args* a, float* d_norm_out, void* stream) {
-    ARREAU_REQUIRE(o && d_flat_grad && d_exp_avg && d_exp_avg_sq && a, "arreau_optimizer_step: null pointer");
-    ARREAU_REQUIRE((size_t)d_flat_grad % 16 == 0, "arreau_optimizer_step: the flat gradient buffer must be 16-byte aligned");
-    ARREAU_REQUIRE(a->step >= 1, "arreau_optimizer_step: step counts from 1");
-    ARREAU_REQUIRE(a->beta1 >= 0.0 && a->beta1 < 1.0 && a->beta2 >= 0.0 && a->beta2 < 1.0 && a->eps >= 0.0, "arreau_optimizer_step: bad hyper-parameters");
+namespace {
+int optimizer_launch(const char* what, arreau_optimizer* o, const float* d_flat_grad, float* d_exp_avg, float* d_exp_avg_sq,
+                     const arreau_adam_args* a, float* d_ema, double decay, float* d_norm_out, void* stream) {
+    ARREAU_REQUIRE(o && d_flat_grad && d_exp_avg && d_exp_avg_sq && a, std::string(what) + ": null pointer");
+    ARREAU_REQUIRE((size_t)d_flat_grad % 16 == 0, std::string(what) + ": the flat gradient buffer must be 16-byte aligned");
+    ARREAU_REQUIRE(a->step >= 1, std::string(what) + ": step counts from 1");
+    ARREAU_REQUIRE(a->beta1 >= 0.0 && a->beta1 < 1.0 && a->beta2 >= 0.0 && a->beta2 < 1.0 && a->eps >= 0.0,
+                   std::string(what) + ": bad hyper-parameters");
     hipStream_t s = (hipStream_t)stream;
     AdamHyper h;
     // bias corrections in double, as torch's host arithmetic (1 - beta ** step)
@@ -179,8 +190,26 @@ extern "C" int arreau_optimizer_step(arreau_optimizer* o, const float* d_flat_gr
     h.sqrt_bc2 = (float)sqrt(bc2);
     h.max_norm = (float)a->max_norm;
     ARREAU_LAUNCH(sqnorm_partial_kernel, dim3(OPT_PARTS), dim3(256), 0, s, d_flat_grad, (long)o->flat_len, o->d_part);
-    ARREAU_LAUNCH(adam_kernel, dim3((unsigned)o->n_chunks), dim3(256), 0, s, o->d_chunks, d_flat_grad, d_exp_avg, d_exp_avg_sq, o->d_part, h,
-                  d_norm_out);
+    if (d_ema) {
+        ARREAU_LAUNCH(adam_kernel<true>, dim3((unsigned)o->n_chunks), dim3(256), 0, s, o->d_chunks, d_flat_grad, d_exp_avg, d_exp_avg_sq,
+                      o->d_part, h, d_norm_out, d_ema, (float)decay, (float)(1.0 - decay));
+    } else {
+        ARREAU_LAUNCH(adam_kernel<false>, dim3((unsigned)o->n_chunks), dim3(256), 0, s, o->d_chunks, d_flat_grad, d_exp_avg, d_exp_avg_sq,
+                      o->d_part, h, d_norm_out, nullptr, 0.f, 0.f);
+    }
     ARREAU_CHECK_HIP(hipGetLastError());
     return ARREAU_OK;
+}
+}  // namespace
+
+extern "C" int arreau_optimizer_step(arreau_optimizer* o, const float* d_flat_grad, float* d_exp_avg, float* d_exp_avg_sq,
+                                     const arreau_adam_args* a, float* d_norm_out, void* stream) {
+    return optimizer_launch("arreau_optimizer_step", o, d_flat_grad, d_exp_avg, d_exp_avg_sq, a, nullptr, 0.0, d_norm_out, stream);
+}
+
+extern "C" int arreau_optimizer_step_ema(arreau_optimizer* o, const float* d_flat_grad, float* d_exp_avg, float* d_exp_avg_sq,
+                                         const arreau_adam_args* a, float* d_ema, double decay, float* d_norm_out, void* stream) {
+    ARREAU_REQUIRE(d_ema, "arreau_optimizer_step_ema: null EMA buffer");
+    ARREAU_REQUIRE(decay >= 0.0 && decay <= 1.0, "arreau_optimizer_step_ema: decay outside [0, 1]");
+    return optimizer_launch("arreau_optimizer_step_ema", o, d_flat_grad, d_exp_avg, d_exp_avg_sq, a, d_ema, decay, d_norm_out, stream);
 }

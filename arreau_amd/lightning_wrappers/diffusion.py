@@ -3,6 +3,7 @@
 with the per-step work running in libarreau_hip.so.  pytorch_lightning is not required; the class
 is a plain nn.Module that reads and writes Lightning-format checkpoint dicts."""
 import collections
+import contextlib
 import os
 import pathlib
 from types import SimpleNamespace
@@ -107,6 +108,19 @@ class PONITA_DIFFUSION(nn.Module):
             dev = self._device if self._device.type == "cuda" else torch.device("cuda", 0)
             self._engine = HipEngine(self, dev)
         return self._engine
+
+    @contextlib.contextmanager
+    def parameters_swapped(self):
+        """For a block that changes the parameters in place and puts them back bit for bit on exit (arreau_amd.optim.EMAOptimizer.
+        swap_ema_weights).  The engine is set aside on entry: whatever runs inside (forward, validation_step, sample) packs a fresh one
+        from the values in place.  On exit that one is dropped and the set-aside engine comes back untouched -- its own fp32 copies
+        and fp16 planes of the training weights, its flat gradient buffer and its products (the full-range ones after a non-finite
+        training step) --, so the next training step gives the bits it would have given without the block."""
+        eng, self._engine = self._engine, None
+        try:
+            yield
+        finally:
+            self._engine = eng
 
     # ---- checkpoint I/O (Lightning dict format) --------------------------------------------------
     @classmethod

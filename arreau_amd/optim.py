@@ -7,8 +7,14 @@ and the Adam update of all 70 tensors), where torch takes a norm, nine scalar la
 launches.  Everything else is torch.optim.Adam: parameter groups, the LR scheduler's view of them, `state_dict()` /
 `load_state_dict()` (the moments are ordinary per-parameter tensors -- views of two flat buffers), and `step()` itself, which stays
 the generic path for gradients that are not views of one buffer (and the only one on the CPU).
+
+`EMAOptimizer` keeps an exponential moving average of the weights around any optimizer (the reference's NeMo EMAOptimizer); around a
+ClipAdam its update rides in the same launch (arreau_optimizer_step_ema).
 """
+import contextlib
+import copy
 import ctypes
+import numbers
 
 import torch
 
@@ -57,10 +63,12 @@ class ClipAdam(torch.optim.Adam):
                 entries.append((p, off, gi))
         return entries or None
 
-    def step_flat(self, flat, max_norm=None, mirrors=None):
+    def step_flat(self, flat, max_norm=None, mirrors=None, ema=None):
         """Clip `flat` (the buffer all `.grad`s are views of) to `max_norm` and step.  Returns the gradient norm (0-d device tensor),
         or None when the gradients are not laid out that way -- the caller then clips and calls step().
-        `mirrors` {parameter: device address}: a second destination for the updated values (HipEngine.train_weight_mirrors)."""
+        `mirrors` {parameter: device address}: a second destination for the updated values (HipEngine.train_weight_mirrors).
+        `ema` (buffer, decay): a flat fp32 buffer laid out like `flat` whose elements become buffer * decay + (1 - decay) * p in the
+        same launch (arreau_optimizer_step_ema; EMAOptimizer.step_flat)."""
         from . import _hip
         entries = self._flat_entries(flat)
         if entries is None:
@@ -116,6 +124,165 @@ class ClipAdam(torch.optim.Adam):
         args.beta1, args.beta2, args.eps = float(b1), float(b2), float(next(iter(epss)))
         args.max_norm = float(max_norm) if max_norm else 0.0
         norm = torch.empty((), device=flat.device, dtype=torch.float32)
-        _hip.check(L.arreau_optimizer_step(self._table[1], _hip.ptr(flat), _hip.ptr(self._m_flat), _hip.ptr(self._v_flat), ctypes.byref(args),
-                                           _hip.ptr(norm), _hip.stream_ptr(flat.device)), "arreau_optimizer_step")
+        if ema is None:
+            _hip.check(L.arreau_optimizer_step(self._table[1], _hip.ptr(flat), _hip.ptr(self._m_flat), _hip.ptr(self._v_flat),
+                                               ctypes.byref(args), _hip.ptr(norm), _hip.stream_ptr(flat.device)), "arreau_optimizer_step")
+        else:
+            buf, decay = ema
+            assert buf.dtype == torch.float32 and buf.device == flat.device and buf.numel() == flat.numel() and buf.is_contiguous()
+            _hip.check(L.arreau_optimizer_step_ema(self._table[1], _hip.ptr(flat), _hip.ptr(self._m_flat), _hip.ptr(self._v_flat),
+                                                   ctypes.byref(args), _hip.ptr(buf), float(decay), _hip.ptr(norm),
+                                                   _hip.stream_ptr(flat.device)), "arreau_optimizer_step_ema")
         return norm
+
+
+class EMAOptimizer(torch.optim.Optimizer):
+    """An exponential moving average of the weights around any torch.optim.Optimizer: NeMo's EMAOptimizer, which the reference
+    carries (lightning_wrappers/callbacks.py:192-392; `EMA(0.99)` is commented out in main_diffusion.py:263-267), with its
+    semantics and state_dict format.
+
+    At the first step the average becomes a copy of every parameter of the optimizer's groups (group order, then parameter order),
+    taken before the update.  Every step runs the inner step, then -- when `current_step % every_n_steps == 0` --
+    ema = decay * ema + (1 - decay) * p, and counts `current_step` up.  A step whose gradient norm was not finite is no exception: the
+    average follows the values that step leaves.  `swap_ema_weights()` puts the average into the parameters for the length of a
+    block.  The LR scheduler stays on the inner optimizer; anything not defined here is the inner optimizer's.
+
+    The average of a frozen parameter (requires_grad False) is the copy of the first step: the optimizer never changes it.
+    Unlike the reference there is no side stream or thread: on the GPU the update runs on the current stream, and on the training
+    step's flat gradient buffer it is not a launch of its own at all -- `step_flat` hands the average, homed in a flat buffer laid
+    out like the gradients, to ClipAdam's launch (arreau_optimizer_step_ema), where the new parameter value is still in a register.
+    Where the flat path declines, arreau_amd.train.optimizer_step calls step(), whose update is the reference's _foreach pair.
+
+    `module`: the PONITA_DIFFUSION the parameters belong to.  Swapping values under its HIP engine would leave the engine on the
+    wrong weights, so the swap runs inside `module.parameters_swapped()`."""
+
+    def __init__(self, optimizer, decay, every_n_steps=1, current_step=0, module=None):
+        if not isinstance(optimizer, torch.optim.Optimizer):
+            raise TypeError(f"EMAOptimizer wraps a torch.optim.Optimizer, not {type(optimizer).__name__}")
+        if isinstance(decay, bool) or not isinstance(decay, numbers.Real) or not 0.0 <= decay <= 1.0:
+            raise ValueError(f"EMA decay must be a number in [0, 1], got {decay!r}")
+        if isinstance(every_n_steps, bool) or not isinstance(every_n_steps, numbers.Integral) or every_n_steps < 1:
+            raise ValueError(f"every_n_steps must be an integer >= 1, got {every_n_steps!r}")
+        self.optimizer = optimizer
+        self.decay = float(decay)
+        self.every_n_steps = int(every_n_steps)
+        self.current_step = int(current_step)
+        self.module = module
+        self.ema_params = ()
+        self.rebuild_ema_params = True
+        self._ema_flat = None
+
+    def __getattr__(self, name):
+        if name == "optimizer":  # (not set yet: no recursion through the delegation below)
+            raise AttributeError(name)
+        return getattr(self.optimizer, name)
+
+    def all_parameters(self):
+        return (p for group in self.optimizer.param_groups for p in group["params"])
+
+    def _build_ema(self):
+        if self.rebuild_ema_params:
+            params = list(self.all_parameters())
+            self.ema_params += tuple(p.detach().clone() for p in params[len(self.ema_params):])
+            self.rebuild_ema_params = False
+
+    def _should_update_at_step(self):
+        return self.current_step % self.every_n_steps == 0
+
+    @torch.no_grad()
+    def update(self):
+        """ema = decay * ema + (1 - decay) * p (callbacks.py:173-180) for every parameter the optimizer may change.  A frozen one
+        (requires_grad False: the module's Fourier projection) never changes, so its average stays the exact copy of the first step
+        -- the reference would round it through the recurrence; the fused launch has no slot for it in the flat buffer."""
+        pairs = [(e, p.detach()) for p, e in zip(self.all_parameters(), self.ema_params) if p.requires_grad]
+        if pairs:
+            ema, cur = (list(t) for t in zip(*pairs))
+            torch._foreach_mul_(ema, self.decay)
+            torch._foreach_add_(ema, cur, alpha=1.0 - self.decay)
+
+    def step(self, closure=None):
+        self._build_ema()
+        loss = self.optimizer.step(closure)
+        if self._should_update_at_step():
+            self.update()
+        self.current_step += 1
+        return loss
+
+    def step_flat(self, flat, max_norm=None, mirrors=None):
+        """ClipAdam.step_flat with the average updated in the same launch.  Returns the gradient norm, or None when the flat path
+        declines (another optimizer, a gradient that is not a view of `flat`, a trainable parameter with elements but without a
+        gradient): the caller then clips and calls step(), which updates the average instead."""
+        if not isinstance(self.optimizer, ClipAdam):
+            return None
+        entries = self.optimizer._flat_entries(flat)
+        params = list(self.all_parameters())
+        if entries is None or {id(p) for p, _, _ in entries} != {id(p) for p in params if p.requires_grad and p.numel()}:
+            return None
+        self._build_ema()
+        # the average lives in a flat buffer laid out like the gradients, as ClipAdam's moments do; a new gradient buffer (the engine
+        # was rebuilt) or a loaded state_dict moves the values into place (frozen parameters keep theirs apart: see update())
+        offset = {id(p): off for p, off, _ in entries}
+        buf = self._ema_flat
+        if (buf is None or buf.numel() != flat.numel() or buf.device != flat.device or
+                any(e.data_ptr() != buf[offset[id(p)]:].data_ptr() for p, e in zip(params, self.ema_params) if id(p) in offset)):
+            buf = torch.zeros_like(flat)
+            homed = []
+            for p, e in zip(params, self.ema_params):
+                if id(p) in offset:
+                    view = buf[offset[id(p)]:offset[id(p)] + p.numel()].view_as(p)
+                    view.copy_(e)
+                    e = view
+                homed.append(e)
+            self._ema_flat, self.ema_params = buf, tuple(homed)
+        norm = self.optimizer.step_flat(flat, max_norm, mirrors, ema=(buf, self.decay) if self._should_update_at_step() else None)
+        if norm is not None:
+            self.current_step += 1
+        return norm
+
+    def zero_grad(self, set_to_none=True):
+        self.optimizer.zero_grad(set_to_none=set_to_none)
+
+    def add_param_group(self, param_group):
+        self.optimizer.add_param_group(param_group)
+        self.rebuild_ema_params = True
+
+    @staticmethod
+    def swap_tensors(tensor1, tensor2):
+        tmp = torch.empty_like(tensor1)
+        tmp.copy_(tensor1)
+        tensor1.copy_(tensor2)
+        tensor2.copy_(tmp)
+
+    @torch.no_grad()
+    def switch_main_parameter_weights(self):
+        for p, e in zip(self.all_parameters(), self.ema_params):
+            self.swap_tensors(p.data, e)
+
+    @contextlib.contextmanager
+    def swap_ema_weights(self, enabled=True):
+        """Within the block the parameters hold the average and the average the training values; both are swapped back on exit,
+        on an exception too."""
+        if not enabled:
+            yield
+            return
+        guard = self.module.parameters_swapped() if self.module is not None else contextlib.nullcontext()
+        with guard:
+            self.switch_main_parameter_weights()
+            try:
+                yield
+            finally:
+                self.switch_main_parameter_weights()
+
+    def state_dict(self):
+        return {"opt": self.optimizer.state_dict(), "ema": self.ema_params, "current_step": self.current_step,
+                "decay": self.decay, "every_n_steps": self.every_n_steps}
+
+    def load_state_dict(self, state_dict):
+        self.optimizer.load_state_dict(state_dict["opt"])
+        params = list(self.all_parameters())
+        ema = copy.deepcopy(tuple(state_dict["ema"]))
+        self.ema_params = tuple(e.to(p.device) for e, p in zip(ema, params)) + tuple(ema[len(params):])
+        self.current_step = state_dict["current_step"]
+        self.decay = state_dict["decay"]
+        self.every_n_steps = state_dict["every_n_steps"]
+        self.rebuild_ema_params = False

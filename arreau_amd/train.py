@@ -7,6 +7,9 @@ of a flat fp32 bucket (1.17 M parameters = 4.7 MB; RCCL when the process group i
 (main_diffusion.py:297) and applied by Adam (decay / no-decay groups) with the cosine warm-up schedule stepped per epoch.
 
     python -m torch.distributed.run --nproc-per-node 8 -m arreau_amd.train --epochs 2 --batch_size 64
+
+`--ema_decay D` keeps an exponential moving average of the weights (arreau_amd.optim.EMAOptimizer, updated inside the optimizer's
+launch); with `--out X.ckpt` rank 0 then also writes the averaged weights to `X-EMA.ckpt`, the checkpoint to sample from.
 """
 import argparse
 import os
@@ -93,13 +96,25 @@ def optimizer_step(model, optimizer, world_size: int = 1, clip: Optional[float] 
     return norm
 
 
-def train_epochs(model, dataset, epochs: int, batch_size: int, rank: int = 0, world_size: int = 1, seed: int = 0,
-                 log=print):
-    """`batch_size` is per rank (global batch = batch_size * world_size).  Returns the list of per-step losses."""
-    from .diffusion.lattice_dataset import iterate_batches
-    from .diffusion.diffusion_loss import DiffusionLossMetric
+def configure_training(model, epochs: int, ema_decay: Optional[float] = None, ema_every_n_steps: int = 1):
+    """(optimizer, LR scheduler) of configure_optimizers; with `ema_decay`, the optimizer is wrapped in an EMAOptimizer
+    (arreau_amd.optim) -- the role of the reference's EMA callback -- and the scheduler stays on the inner one."""
     opt = model.configure_optimizers(max_epochs=epochs)
     optimizer, scheduler = opt["optimizer"], opt["lr_scheduler"]
+    if ema_decay is not None:
+        from .optim import EMAOptimizer
+        optimizer = EMAOptimizer(optimizer, ema_decay, every_n_steps=ema_every_n_steps, module=model)
+    return optimizer, scheduler
+
+
+def train_epochs(model, dataset, epochs: int, batch_size: int, rank: int = 0, world_size: int = 1, seed: int = 0,
+                 log=print, optimizer=None, scheduler=None):
+    """`batch_size` is per rank (global batch = batch_size * world_size).  Returns the list of per-step losses.
+    `optimizer` / `scheduler`: from configure_training (default: configure_optimizers' own, no EMA)."""
+    from .diffusion.lattice_dataset import iterate_batches
+    from .diffusion.diffusion_loss import DiffusionLossMetric
+    if optimizer is None:
+        optimizer, scheduler = configure_training(model, epochs)
     losses = []
     for epoch in range(epochs):
         metric = DiffusionLossMetric()  # (diffusion_loss.py:52-65; the reference logs it per epoch with sync_dist)
@@ -141,7 +156,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--weight_decay", type=float, default=1e-10)
     ap.add_argument("--out", type=str, default=None, help="write a Lightning-format checkpoint here (rank 0)")
+    ap.add_argument("--ema_decay", type=float, default=None,
+                    help="keep an exponential moving average of the weights with this decay; --out then also writes X-EMA.ckpt")
+    ap.add_argument("--ema_every_n_steps", type=int, default=1, help="update the average every N optimizer steps")
     args = ap.parse_args()
+    if args.ema_decay is not None and not 0.0 <= args.ema_decay <= 1.0:
+        ap.error("--ema_decay must lie in [0, 1]")
+    if args.ema_every_n_steps < 1:
+        ap.error("--ema_every_n_steps must be at least 1")
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if os.environ.get("ARREAU_TRAIN_ONE_DEVICE", "0") == "1":
@@ -155,7 +177,7 @@ def main():
             dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
         else:
             dist.init_process_group(backend)
-    from .checkpoint import default_args, save_lightning_checkpoint
+    from .checkpoint import default_args, save_ema_checkpoint, save_lightning_checkpoint
     from .diffusion.lattice_dataset import CrystalDataset, synthetic_alexandria_like
     from .lightning_wrappers.diffusion import PONITA_DIFFUSION
     ds = CrystalDataset(args.data) if args.data else CrystalDataset(configs=synthetic_alexandria_like(args.num_synthetic, args.seed))
@@ -166,25 +188,33 @@ def main():
                             weight_decay=args.weight_decay)
     model = PONITA_DIFFUSION(net_args, ds.z_table).to(f"cuda:{local_rank}")
     torch.manual_seed(args.seed + 1000 + rank)  # different noise per rank
-    train_epochs(model, ds, args.epochs, args.batch_size, rank, world, args.seed)
+    optimizer, scheduler = configure_training(model, args.epochs, args.ema_decay, args.ema_every_n_steps)
+    train_epochs(model, ds, args.epochs, args.batch_size, rank, world, args.seed, optimizer=optimizer, scheduler=scheduler)
     # data-parallel invariant: the replicas hold the same weights (same initial weights, same averaged gradients, ONE set
-    # of calibration ratios); a drift here means a rank applied something its peers did not
-    check = torch.stack([p.detach().double().sum() for p in model.parameters()]).sum().reshape(1)
-    if world > 1:
-        sums = [torch.zeros_like(check) for _ in range(world)]
-        if dist.get_backend() == "nccl":
-            dist.all_gather(sums, check)
-        else:
-            host = [s.cpu() for s in sums]
-            dist.all_gather(host, check.cpu())
-            sums = host
-        vals = [float(s) for s in sums]
-        if rank == 0:
-            print("replica parameter checksums:", " ".join(f"{v:.12e}" for v in vals))
-        if max(vals) - min(vals) > 1e-9 * max(1.0, abs(vals[0])):
-            raise SystemExit(f"rank {rank}: data-parallel replicas diverged: {vals}")
+    # of calibration ratios); a drift here means a rank applied something its peers did not.  Each rank keeps its own average
+    # of the weights (no collective): the averages of identical weights agree too.
+    checks = [("parameter", list(model.parameters()))]
+    if args.ema_decay is not None:
+        checks.append(("EMA", list(optimizer.ema_params)))
+    for what, tensors in checks:
+        check = torch.stack([t.detach().double().sum() for t in tensors]).sum().reshape(1)
+        if world > 1:
+            sums = [torch.zeros_like(check) for _ in range(world)]
+            if dist.get_backend() == "nccl":
+                dist.all_gather(sums, check)
+            else:
+                host = [s.cpu() for s in sums]
+                dist.all_gather(host, check.cpu())
+                sums = host
+            vals = [float(s) for s in sums]
+            if rank == 0:
+                print(f"replica {what} checksums:", " ".join(f"{v:.12e}" for v in vals))
+            if max(vals) - min(vals) > 1e-9 * max(1.0, abs(vals[0])):
+                raise SystemExit(f"rank {rank}: data-parallel replicas diverged ({what}): {vals}")
     if rank == 0 and args.out:
         print("wrote", save_lightning_checkpoint(args.out, model))
+        if args.ema_decay is not None:
+            print("wrote", save_ema_checkpoint(args.out, model, optimizer))
     if world > 1:
         dist.destroy_process_group()
 

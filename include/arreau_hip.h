@@ -565,7 +565,13 @@ int arreau_train_conv_stats(arreau_model* model, float* d_stats, void* stream);
  * d_mirrors (may be NULL, entries may be NULL): a second destination per tensor for the updated values -- the model's own fp32
  * copy of that tensor (arreau_model_train_weight_pointers), which makes arreau_model_update_train_weights' copies unnecessary;
  * arreau_model_refresh_derived_train_weights then rebuilds the two weights the training entry points read in a derived form
- * (the folded polynomial weight of basis_fn.1, the transposed embedder) from the caller's updated tensors. */
+ * (the folded polynomial weight of basis_fn.1, the transposed embedder) from the caller's updated tensors.
+ * step_ema: the same step (the same bits in parameters, moments, mirrors and norm), and in the same pass an exponential moving
+ * average of the weights (NeMo's EMAOptimizer, lightning_wrappers/callbacks.py:173-180), per element after p is updated:
+ *   e = e * d + w * p_new,   d = decay, w = 1 - decay (both formed in double, each rounded to fp32 once; e * d is rounded, then
+ *   one fused multiply-add).
+ * d_ema: flat_len floats laid out like the gradient buffer (caller-owned, like the moments); 0 <= decay <= 1.  A step whose
+ * norm is not finite updates the average too, from the values the step leaves. */
 #define ARREAU_OPT_MAX_GROUPS 4
 typedef struct arreau_optimizer arreau_optimizer;
 typedef struct {   /* doubles: torch forms 1 - beta, 1 - beta^t and lr / (1 - beta1^t) from Python floats before anything is rounded to fp32 */
@@ -580,6 +586,8 @@ int arreau_optimizer_create(int32_t n_tensors, void* const* d_params, void* cons
                             arreau_optimizer** out);
 int arreau_optimizer_step(arreau_optimizer* opt, const float* d_flat_grad, float* d_exp_avg, float* d_exp_avg_sq,
                           const arreau_adam_args* args, float* d_norm_out, void* stream);
+int arreau_optimizer_step_ema(arreau_optimizer* opt, const float* d_flat_grad, float* d_exp_avg, float* d_exp_avg_sq,
+                              const arreau_adam_args* args, float* d_ema, double decay, float* d_norm_out, void* stream);
 void arreau_optimizer_destroy(arreau_optimizer* opt);
 /* DEVICE pointers of the model's own fp32 training weights, stacked [L, ...] in the state_dict layout (NULL: basis_w1,
  * x_embedder_w and every buffer entry). */
