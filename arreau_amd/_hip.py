@@ -28,9 +28,10 @@ EXPORTS = [
     "arreau_sample_loop_scheduled", "arreau_reverse_step_to",
     "arreau_sample_loop_corrected", "arreau_corrector_step", "arreau_philox_fill_word",
     "arreau_sample_loop_resampled", "arreau_resample_jump", "arreau_optimizer_step_ema",
+    "arreau_sample_loop_tied", "arreau_reverse_step_tied", "arreau_resample_jump_tied",
 ]
 
-STATUS_NONFINITE, STATUS_BAD_TIMESTEP, STATUS_BAD_TYPE = 1, 2, 4
+STATUS_NONFINITE, STATUS_BAD_TIMESTEP, STATUS_BAD_TYPE, STATUS_BAD_TIE = 1, 2, 4, 8
 EDGE_KERNELS = {0: "fp32-mfma", 1: "fp32-mfma", 2: "fp32-mfma", 3: "bf16x6", 4: "fp16x3", 5: "general-fp32-gemm"}
 MLP_KERNELS = {0: "fp32-mfma", 1: "bf16x6", 2: "fp16x3-32x32x16", 3: "fp16x3-16x16x32",
                5: "general-fp32-gemm"}
@@ -156,6 +157,10 @@ def lib():
                                                    [POINTER(ResamplingC), c_void_p])
         L.arreau_resample_jump.argtypes = [c_void_p] * 8 + [c_int32, c_int32] + [c_void_p] * 5 + [POINTER(SampleConditionC),
                                                                                                    c_void_p, c_void_p]
+    if hasattr(L, "arreau_sample_loop_tied") or not os.environ.get("ARREAU_HIP_LIB"):  # (an older build under test)
+        L.arreau_sample_loop_tied.argtypes = L.arreau_sample_loop_resampled.argtypes[:-1] + [c_void_p, c_void_p]
+        L.arreau_reverse_step_tied.argtypes = L.arreau_reverse_step_to.argtypes[:-1] + [c_void_p, c_void_p]
+        L.arreau_resample_jump_tied.argtypes = L.arreau_resample_jump.argtypes[:-1] + [c_void_p, c_void_p]
     L.arreau_philox_fill.argtypes = [ctypes.c_uint64, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_void_p]
     L.arreau_train_forward.argtypes = [c_void_p] * 7 + [c_int32, c_int32] + [c_void_p] * 4
     L.arreau_train_backward.argtypes = [c_void_p] * 4 + [POINTER(StateDict), c_void_p]

@@ -311,7 +311,8 @@ int enqueue_sample_step(const arreau_model* m, float* d_frac, int32_t* d_types, 
                         const int32_t* d_off, int B, int N, uint64_t seed, const int32_t* d_const_types,
                         const float* d_fixed_lengths, float* d_lattice, const Workspace& w, hipStream_t s, bool no_prep,
                         const SampleConditionDev* cond, const StepScheduleDev* sched, CorrectorDev corr,
-                        const int32_t* pass /* resampled loop: the device word of the pass index (RESAMPLE instances), or null */) {
+                        const int32_t* pass /* resampled loop: the device word of the pass index (RESAMPLE instances), or null */,
+                        const int32_t* length_tie /* lattice systems: the tie codes (TIE instances), or null */) {
     int rc;
     const int32_t* next_t = sched ? sched->next : nullptr;  // respaced loop: the device timestep follows the table
     if (no_prep) {
@@ -327,7 +328,7 @@ int enqueue_sample_step(const arreau_model* m, float* d_frac, int32_t* d_types, 
         }
         return arreau_launch_reverse(m, d_frac, d_types, d_lengths, d_angles, w.t_cur, d_off, B, N, w.eps, w.logits, w.len0,
                                      StepNoiseSrc{nullptr, nullptr, nullptr, seed}, d_const_types, d_lattice, s, d_fixed_lengths,
-                                     w.gs, w.batch, w.lattice, w.cvec, cond, sched, pass);
+                                     w.gs, w.batch, w.lattice, w.cvec, cond, sched, pass, length_tie);
     }
     // fused kernels: the per-crystal pooling of the lattice read-out happens inside the lattice update (no launch of its own)
     const bool pool_in_update = !arreau_general_path(m);
@@ -346,7 +347,7 @@ int enqueue_sample_step(const arreau_model* m, float* d_frac, int32_t* d_types, 
     }
     return arreau_launch_reverse(m, d_frac, d_types, d_lengths, d_angles, w.t_cur, d_off, B, N, w.eps, w.logits, w.len0,
                                  StepNoiseSrc{nullptr, nullptr, nullptr, seed}, d_const_types, d_lattice, s, d_fixed_lengths,
-                                 pool_in_update ? w.gs : nullptr, w.batch, nullptr, nullptr, cond, sched, pass);
+                                 pool_in_update ? w.gs : nullptr, w.batch, nullptr, nullptr, cond, sched, pass, length_tie);
 }
 
 // RePaint resampling (arreau_sample_loop_resampled): the blocks of one loop call, from the host's list of the steps it visits.
@@ -392,13 +393,14 @@ extern "C" int arreau_sample_loop_scheduled(arreau_model* m, float* d_frac, int3
 namespace {
 // The key of a captured step: besides the buffers, sizes and seed, which kernels it holds depends on switches read per call
 // (ARREAU_BASIS_MIN_RECEIVERS, ARREAU_FUSE_SMALL) and on the variants, and the condition's pointers, the schedule's table and
-// clip, the corrector's step count and snr and the resampling's R and J (a resampled step reads the pass word) are kernel
-// arguments or launch choices of the capture: a change of any of them must not replay the stale graph.
+// clip, the corrector's step count and snr, the resampling's R and J (a resampled step reads the pass word) and the lattice
+// systems' tie array are kernel arguments or launch choices of the capture: a change of any of them must not replay the stale graph.
 SampleGraphKey sample_graph_key(const arreau_model* m, const float* d_frac, const int32_t* d_types, const float* d_lengths,
                                 const float* d_angles, const int32_t* d_off, int32_t B, int32_t N, uint64_t seed,
                                 const int32_t* d_const_types, const float* d_fixed_lengths, const float* d_lattice,
                                 const void* d_workspace, bool no_prep, const SampleConditionDev& cond, bool scheduled,
-                                const StepScheduleDev& sched, const CorrectorDev& corr, const ResamplePlan* plan) {
+                                const StepScheduleDev& sched, const CorrectorDev& corr, const ResamplePlan* plan,
+                                const int32_t* d_length_tie) {
     SampleGraphKey k{};
     k.frac = (uint64_t)d_frac; k.types = (uint64_t)d_types; k.lengths = (uint64_t)d_lengths; k.angles = (uint64_t)d_angles;
     k.offsets = (uint64_t)d_off; k.const_types = (uint64_t)d_const_types; k.fixed_lengths = (uint64_t)d_fixed_lengths;
@@ -406,6 +408,7 @@ SampleGraphKey sample_graph_key(const arreau_model* m, const float* d_frac, cons
     k.cond_x0 = (uint64_t)cond.x0; k.cond_pos_mask = (uint64_t)cond.pos_mask; k.cond_a0 = (uint64_t)cond.a0;
     k.cond_type_mask = (uint64_t)cond.type_mask; k.cond_l0 = (uint64_t)cond.l0; k.cond_len_mask = (uint64_t)cond.len_mask;
     k.sched_next = (uint64_t)sched.next;
+    k.length_tie = (uint64_t)d_length_tie;
     k.B = B; k.N = N;
     k.edge_variant = m->edge_variant; k.mlp_variant = m->mlp_variant; k.conv_variant = m->conv_variant; k.no_prep = no_prep;
     k.basis_form = arreau_basis_form(m, N); k.basis_fp8 = arreau_basis_fp8(m); k.cross_fp8 = arreau_cross_fp8(m);
@@ -425,7 +428,8 @@ int sample_loop_impl(arreau_model* m, float* d_frac, int32_t* d_types, float* d_
                      int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed, const int32_t* d_const_types,
                      const float* d_fixed_lengths, float* d_lattice, void* d_workspace, size_t workspace_bytes, int32_t use_graph,
                      const arreau_sample_condition* condition, const arreau_sample_schedule* schedule, const arreau_corrector* corrector,
-                     const ResamplePlan* plan /* null: no resampling */, void* stream) {
+                     const ResamplePlan* plan /* null: no resampling */, const int32_t* d_length_tie /* null: untied */,
+                     void* stream) {
     if (corrector) {
         const int rc = arreau_corrector_check(corrector->steps, corrector->snr, "arreau_sample_loop_corrected");
         if (rc) return rc;
@@ -506,7 +510,7 @@ int sample_loop_impl(arreau_model* m, float* d_frac, int32_t* d_types, float* d_
         // (a sampler drawing sub-batch after sub-batch through the caching allocator does): capture + instantiation, about
         // 2 ms, are then paid once.  The timestep is not part of the graph (it lives in t_next / t_cur, set above).
         key = sample_graph_key(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types, d_fixed_lengths, d_lattice,
-                               d_workspace, no_prep, cond_dev, schedule != nullptr, sched_dev, corr, plan);
+                               d_workspace, no_prep, cond_dev, schedule != nullptr, sched_dev, corr, plan, d_length_tie);
         exec = (hipGraphExec_t)m->retired_graph;
         have_exec = exec && memcmp(&key, &m->graph_key, sizeof(key)) == 0;
     }
@@ -517,13 +521,13 @@ int sample_loop_impl(arreau_model* m, float* d_frac, int32_t* d_types, float* d_
         if (!graph_mode || !have_exec) {
             // (eager: the first step of a capture also forces lazy module loading, which must not happen inside a capture)
             if ((r = enqueue_sample_step(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types, d_fixed_lengths,
-                                         d_lattice, w, s, no_prep, cond, sched, corr, pass)))
+                                         d_lattice, w, s, no_prep, cond, sched, corr, pass, d_length_tie)))
                 return r;
             if (!graph_mode) return ARREAU_OK;
             hipGraph_t graph = nullptr;
             ARREAU_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
             r = enqueue_sample_step(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types, d_fixed_lengths, d_lattice,
-                                    w, s, no_prep, cond, sched, corr, pass);
+                                    w, s, no_prep, cond, sched, corr, pass, d_length_tie);
             hipError_t e = hipStreamEndCapture(s, &graph);
             if (r) {
                 if (graph) (void)hipGraphDestroy(graph);
@@ -556,7 +560,7 @@ int sample_loop_impl(arreau_model* m, float* d_frac, int32_t* d_types, float* d_
                 if (r > 0 &&
                     (rc = arreau_launch_resample_jump(m, d_frac, d_types, d_lengths, d_angles, nullptr, nullptr, bl.bottom, bl.top, d_off,
                                                       w.batch, B, N, nullptr, nullptr, nullptr, seed, (uint32_t)r, d_const_types,
-                                                      d_fixed_lengths, cond, d_lattice, &loop, s)))
+                                                      d_fixed_lengths, cond, d_lattice, &loop, s, d_length_tie)))
                     return rc;
                 for (int i = 0; i < bl.count; ++i)
                     if ((rc = run_step())) return rc;
@@ -579,17 +583,16 @@ extern "C" int arreau_sample_loop_corrected(arreau_model* m, float* d_frac, int3
                                             int32_t use_graph, const arreau_sample_condition* condition,
                                             const arreau_sample_schedule* schedule, const arreau_corrector* corrector, void* stream) {
     return sample_loop_impl(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, t_start, n_steps, seed, d_const_types, d_fixed_lengths,
-                            d_lattice, d_workspace, workspace_bytes, use_graph, condition, schedule, corrector, nullptr, stream);
+                            d_lattice, d_workspace, workspace_bytes, use_graph, condition, schedule, corrector, nullptr, nullptr, stream);
 }
 
-extern "C" int arreau_sample_loop_resampled(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths,
-                                            const float* d_angles, const int32_t* d_off, int32_t B, int32_t N, int32_t t_start,
-                                            int32_t n_steps, uint64_t seed, const int32_t* d_const_types,
-                                            const float* d_fixed_lengths, float* d_lattice, void* d_workspace, size_t workspace_bytes,
-                                            int32_t use_graph, const arreau_sample_condition* condition,
-                                            const arreau_sample_schedule* schedule, const arreau_corrector* corrector,
-                                            const arreau_resampling* resampling, void* stream) {
-    static const char* who = "arreau_sample_loop_resampled";
+namespace {
+int sample_loop_resampled(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles, const int32_t* d_off,
+                          int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed, const int32_t* d_const_types,
+                          const float* d_fixed_lengths, float* d_lattice, void* d_workspace, size_t workspace_bytes, int32_t use_graph,
+                          const arreau_sample_condition* condition, const arreau_sample_schedule* schedule,
+                          const arreau_corrector* corrector, const arreau_resampling* resampling, const int32_t* d_length_tie,
+                          const char* who, void* stream) {
     ResamplePlan plan{1, 1, {}};
     if (resampling) {
         int rc;
@@ -603,14 +606,14 @@ extern "C" int arreau_sample_loop_resampled(arreau_model* m, float* d_frac, int3
         int last_succ = 0;
         if (schedule) {
             ARREAU_REQUIRE(resampling->timesteps != nullptr && resampling->n_timesteps >= 1,
-                           "arreau_sample_loop_resampled: a respaced loop needs the host copy of its schedule (timesteps)");
+                           std::string(who) + ": a respaced loop needs the host copy of its schedule (timesteps)");
             const int32_t* ts = resampling->timesteps;
             const int K = resampling->n_timesteps;
             int i0 = -1;
             for (int i = 0; i < K; ++i)
                 if (ts[i] == t_start) { i0 = i; break; }
             ARREAU_REQUIRE(i0 >= 0 && (int64_t)i0 + n_steps <= K,
-                           "arreau_sample_loop_resampled: the host schedule does not hold t_start followed by n_steps - 1 timesteps");
+                           std::string(who) + ": the host schedule does not hold t_start followed by n_steps - 1 timesteps");
             steps.assign(ts + i0, ts + i0 + n_steps);
             last_succ = i0 + n_steps < K ? ts[i0 + n_steps] : 0;
         } else {
@@ -624,7 +627,32 @@ extern "C" int arreau_sample_loop_resampled(arreau_model* m, float* d_frac, int3
     }
     return sample_loop_impl(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, t_start, n_steps, seed, d_const_types, d_fixed_lengths,
                             d_lattice, d_workspace, workspace_bytes, use_graph, condition, schedule, corrector,
-                            plan.passes > 1 ? &plan : nullptr, stream);
+                            plan.passes > 1 ? &plan : nullptr, d_length_tie, stream);
+}
+}  // namespace
+
+extern "C" int arreau_sample_loop_resampled(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths,
+                                            const float* d_angles, const int32_t* d_off, int32_t B, int32_t N, int32_t t_start,
+                                            int32_t n_steps, uint64_t seed, const int32_t* d_const_types,
+                                            const float* d_fixed_lengths, float* d_lattice, void* d_workspace, size_t workspace_bytes,
+                                            int32_t use_graph, const arreau_sample_condition* condition,
+                                            const arreau_sample_schedule* schedule, const arreau_corrector* corrector,
+                                            const arreau_resampling* resampling, void* stream) {
+    return sample_loop_resampled(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, t_start, n_steps, seed, d_const_types,
+                                 d_fixed_lengths, d_lattice, d_workspace, workspace_bytes, use_graph, condition, schedule, corrector,
+                                 resampling, nullptr, "arreau_sample_loop_resampled", stream);
+}
+
+// arreau_sample_loop_resampled with the lattice-system tie of the lengths (rules in include/arreau_hip.h); NULL = that loop.
+extern "C" int arreau_sample_loop_tied(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                                       const int32_t* d_off, int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed,
+                                       const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice, void* d_workspace,
+                                       size_t workspace_bytes, int32_t use_graph, const arreau_sample_condition* condition,
+                                       const arreau_sample_schedule* schedule, const arreau_corrector* corrector,
+                                       const arreau_resampling* resampling, const int32_t* d_length_tie, void* stream) {
+    return sample_loop_resampled(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, t_start, n_steps, seed, d_const_types,
+                                 d_fixed_lengths, d_lattice, d_workspace, workspace_bytes, use_graph, condition, schedule, corrector,
+                                 resampling, d_length_tie, "arreau_sample_loop_tied", stream);
 }
 
 // ---------------------------------------------------------------------------------------------

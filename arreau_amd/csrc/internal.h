@@ -46,6 +46,7 @@ struct SampleGraphKey {
     // conditioned sampling: the six pointers of the condition (null: none)
     uint64_t cond_x0, cond_pos_mask, cond_a0, cond_type_mask, cond_l0, cond_len_mask;
     uint64_t sched_next;  // respaced sampling: the next-timestep table
+    uint64_t length_tie;  // lattice systems: the per-crystal tie codes (null: untied)
     int32_t B, N;
     // kernel choices: the variants, and the switches read per call (ARREAU_BASIS_MIN_RECEIVERS, ARREAU_FUSE_SMALL)
     int32_t edge_variant, mlp_variant, conv_variant, no_prep, basis_form, basis_fp8, cross_fp8, small_layer_fusion;
@@ -55,7 +56,7 @@ struct SampleGraphKey {
     uint32_t snr_bits;         // the corrector's snr
     int32_t resample_passes, resample_jump;  // 0, 0: no resampling
 };
-static_assert(sizeof(SampleGraphKey) == 17 * 8 + 16 * 4, "SampleGraphKey must have no padding (it is compared with memcmp)");
+static_assert(sizeof(SampleGraphKey) == 18 * 8 + 16 * 4, "SampleGraphKey must have no padding (it is compared with memcmp)");
 
 struct arreau_model {
     arreau_config cfg;
@@ -283,7 +284,8 @@ int arreau_launch_resample_jump(const arreau_model* m, float* d_frac, int32_t* d
                                 const int32_t* d_s, const int32_t* d_t, int s, int t, const int32_t* d_off, const int32_t* d_batch,
                                 int B, int N, const float* d_z_frac, const float* d_z_lengths, const float* d_u_types, uint64_t seed,
                                 uint32_t pass, const int32_t* d_const_types, const float* d_fixed_lengths,
-                                const SampleConditionDev* cond, float* d_lattice, const JumpLoopDev* loop, hipStream_t st);
+                                const SampleConditionDev* cond, float* d_lattice, const JumpLoopDev* loop, hipStream_t st,
+                                const int32_t* d_length_tie = nullptr /* lattice systems: the tie code per crystal (the TIE instance) */);
 
 void arreau_train_ctx_destroy(struct arreau_train_ctx* t);
 // edge_variant value that selects the shape-general fp32 network (train_net.hip) for the whole evaluation
@@ -355,7 +357,8 @@ int arreau_launch_reverse(const arreau_model* m, float* d_frac, int32_t* d_types
                           (workspace lattice + per-crystal embedding for timestep t - 1), see reverse_crystal_block */,
                           const SampleConditionDev* cond = nullptr /* conditioned sampling; needs Philox noise (noise.seed) */,
                           const StepScheduleDev* sched = nullptr /* respaced step (s from a table or per crystal), null: s = t - 1 */,
-                          const int32_t* d_pass = nullptr /* resampled loop: word3 = 256 pass[0] (the RESAMPLE instance) */);
+                          const int32_t* d_pass = nullptr /* resampled loop: word3 = 256 pass[0] (the RESAMPLE instance) */,
+                          const int32_t* d_length_tie = nullptr /* lattice systems: the tie code per crystal (the TIE instance) */);
 int arreau_launch_edge(const arreau_model* m, const float* dir, const float* dist, const int32_t* deg,
                        const int32_t* batch, const float* lattice, int N, float* kbuf, hipStream_t s);
 int arreau_launch_edge_bf16x6(const arreau_model* m, const float* dir, const float* dist, const int32_t* deg,

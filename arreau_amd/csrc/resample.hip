@@ -35,13 +35,18 @@ struct JumpNoise {
     uint32_t pass;           // counter word3 of the Philox draws
 };
 
+// TIE: lattice systems (arreau_resample_jump_tied, the tied loop): the axes tied by length_tie[b] jump together from the leader's
+// length with the leader's draw (rule 2 of the section in include/arreau_hip.h); a crystal whose lengths len_mask knows is not tied.
+// Without TIE neither pointer is read.
+template <bool TIE>
 __global__ __launch_bounds__(JUMP_THREADS) void resample_jump_kernel(
     int B, int N, float* __restrict__ frac, int32_t* __restrict__ types, float* __restrict__ lengths, const float* __restrict__ angles,
     JumpTimes jt, const int32_t* __restrict__ offsets, const int32_t* __restrict__ batch, JumpNoise noise,
     const float* __restrict__ ve_sigmas, const float* __restrict__ alpha_bars, const float* __restrict__ qmats, int S, int T,
     int absorbing, const int32_t* __restrict__ const_types, const float* __restrict__ fixed_lengths,
     const uint8_t* __restrict__ type_mask, float* __restrict__ lattice, JumpLoopDev loop, const float* __restrict__ betas,
-    const float* __restrict__ t_emb_w, const float* __restrict__ embT, int C, int32_t* __restrict__ status) {
+    const float* __restrict__ t_emb_w, const float* __restrict__ embT, int C, int32_t* __restrict__ status,
+    const int32_t* __restrict__ length_tie, const uint8_t* __restrict__ len_mask) {
     if ((int)blockIdx.x < B) {
         // ---- lattice part: crystal b ----------------------------------------------------------------------------------
         __shared__ float newlen[3];
@@ -51,6 +56,27 @@ __global__ __launch_bounds__(JUMP_THREADS) void resample_jump_kernel(
         bool bad;
         jump_pair(jt, b, T, s, t, bad);
         if (threadIdx.x == 0 && bad) atomicOr(status, ARREAU_STATUS_BAD_TIMESTEP);  // clamped, but flagged
+        if constexpr (TIE) {
+            // the tied axes jump from the leader's length with the leader's draw (element 3 b): every one computes the same bits
+            __shared__ float oldlen[3];
+            const int code = length_tie_code(length_tie, len_mask, b, status, threadIdx.x == 0);
+            if (threadIdx.x < 3) oldlen[threadIdx.x] = lengths[3 * b + threadIdx.x];
+            __syncthreads();
+            if (threadIdx.x < 3) {
+                const int g = 3 * b + (int)threadIdx.x;
+                const bool tied = length_tied(code, threadIdx.x);
+                float l = oldlen[threadIdx.x];
+                if (fixed_lengths == nullptr) {  // a fixed cell is held (kernel argument: uniform)
+                    const float ratio = s > 0 ? alpha_bars[t] / alpha_bars[s] : alpha_bars[t];
+                    const int e = tied ? 3 * b : g;
+                    const float z = noise.z_lengths ? noise.z_lengths[e]
+                                                    : philox_normal(noise.seed, (uint32_t)t, ARREAU_DRAW_Z_JUMP_LENGTHS, (uint32_t)e, noise.pass);
+                    l = sqrtf(ratio) * (tied ? oldlen[0] : l) + sqrtf(1.0f - ratio) * z;
+                    lengths[g] = l;
+                }
+                newlen[threadIdx.x] = l;
+            }
+        } else
         if (threadIdx.x < 3) {
             const int g = 3 * b + (int)threadIdx.x;
             float l = lengths[g];
@@ -160,17 +186,36 @@ int arreau_launch_resample_jump(const arreau_model* m, float* d_frac, int32_t* d
                                 const int32_t* d_s, const int32_t* d_t, int s, int t, const int32_t* d_off, const int32_t* d_batch,
                                 int B, int N, const float* d_z_frac, const float* d_z_lengths, const float* d_u_types, uint64_t seed,
                                 uint32_t pass, const int32_t* d_const_types, const float* d_fixed_lengths,
-                                const SampleConditionDev* cond, float* d_lattice, const JumpLoopDev* loop, hipStream_t st) {
+                                const SampleConditionDev* cond, float* d_lattice, const JumpLoopDev* loop, hipStream_t st,
+                                const int32_t* d_length_tie) {
     if (B <= 0) return ARREAU_OK;
     const uint8_t* type_mask = (cond && cond->a0 && cond->type_mask) ? cond->type_mask : nullptr;
+    const uint8_t* len_mask = (cond && cond->l0 && cond->len_mask) ? cond->len_mask : nullptr;
     const JumpLoopDev lp = loop ? *loop : JumpLoopDev{};
     const unsigned blocks = (unsigned)B + (unsigned)((N + 3) / 4);
-    ARREAU_LAUNCH(resample_jump_kernel, dim3(blocks), dim3(JUMP_THREADS), 0, st, B, N, d_frac, d_types, d_lengths, d_angles,
+    auto kernel = d_length_tie ? resample_jump_kernel<true> : resample_jump_kernel<false>;
+    ARREAU_LAUNCH(kernel, dim3(blocks), dim3(JUMP_THREADS), 0, st, B, N, d_frac, d_types, d_lengths, d_angles,
                   JumpTimes{d_s, d_t, s, t}, d_off, d_batch, JumpNoise{d_z_frac, d_z_lengths, d_u_types, seed, pass}, m->ve_sigmas,
                   m->vp_alpha_bars, m->qmats, m->S, m->T, m->qmats_absorbing, d_const_types, d_fixed_lengths, type_mask, d_lattice, lp,
-                  m->vp_betas, m->t_emb_w, m->embT, m->C, m->status);
+                  m->vp_betas, m->t_emb_w, m->embT, m->C, m->status, d_length_tie, len_mask);
     ARREAU_CHECK_HIP(hipGetLastError());
     return ARREAU_OK;
+}
+
+static int resample_jump(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                         const int32_t* d_s, const int32_t* d_t, const int32_t* d_off, int32_t B, int32_t N, const float* d_z_frac,
+                         const float* d_z_lengths, const float* d_u_types, const int32_t* d_const_types, const float* d_fixed_lengths,
+                         const arreau_sample_condition* cond, float* d_lattice, const int32_t* d_length_tie, void* stream,
+                         const char* who) {
+    ARREAU_REQUIRE(m && d_frac && d_types && d_lengths && d_angles && d_s && d_t && d_off && d_z_frac && d_z_lengths && d_u_types &&
+                       d_lattice, std::string(who) + ": null pointer");
+    ARREAU_REQUIRE(B >= 1 && N >= 0, std::string(who) + ": bad size");
+    SampleConditionDev c;
+    int rc;
+    if ((rc = arreau_condition_to_dev(cond, &c))) return rc;
+    return arreau_launch_resample_jump(m, d_frac, d_types, d_lengths, d_angles, d_s, d_t, 0, 0, d_off, nullptr, B, N, d_z_frac,
+                                       d_z_lengths, d_u_types, 0, 0u, d_const_types, d_fixed_lengths, &c, d_lattice, nullptr,
+                                       (hipStream_t)stream, d_length_tie);
 }
 
 extern "C" int arreau_resample_jump(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
@@ -178,13 +223,16 @@ extern "C" int arreau_resample_jump(const arreau_model* m, float* d_frac, int32_
                                     const float* d_z_frac, const float* d_z_lengths, const float* d_u_types,
                                     const int32_t* d_const_types, const float* d_fixed_lengths, const arreau_sample_condition* cond,
                                     float* d_lattice, void* stream) {
-    ARREAU_REQUIRE(m && d_frac && d_types && d_lengths && d_angles && d_s && d_t && d_off && d_z_frac && d_z_lengths && d_u_types &&
-                       d_lattice, "arreau_resample_jump: null pointer");
-    ARREAU_REQUIRE(B >= 1 && N >= 0, "arreau_resample_jump: bad size");
-    SampleConditionDev c;
-    int rc;
-    if ((rc = arreau_condition_to_dev(cond, &c))) return rc;
-    return arreau_launch_resample_jump(m, d_frac, d_types, d_lengths, d_angles, d_s, d_t, 0, 0, d_off, nullptr, B, N, d_z_frac,
-                                       d_z_lengths, d_u_types, 0, 0u, d_const_types, d_fixed_lengths, &c, d_lattice, nullptr,
-                                       (hipStream_t)stream);
+    return resample_jump(m, d_frac, d_types, d_lengths, d_angles, d_s, d_t, d_off, B, N, d_z_frac, d_z_lengths, d_u_types, d_const_types,
+                         d_fixed_lengths, cond, d_lattice, nullptr, stream, "arreau_resample_jump");
+}
+
+// arreau_resample_jump with the lattice-system tie of the lengths (rules in include/arreau_hip.h); NULL = arreau_resample_jump.
+extern "C" int arreau_resample_jump_tied(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                                         const int32_t* d_s, const int32_t* d_t, const int32_t* d_off, int32_t B, int32_t N,
+                                         const float* d_z_frac, const float* d_z_lengths, const float* d_u_types,
+                                         const int32_t* d_const_types, const float* d_fixed_lengths, const arreau_sample_condition* cond,
+                                         float* d_lattice, const int32_t* d_length_tie, void* stream) {
+    return resample_jump(m, d_frac, d_types, d_lengths, d_angles, d_s, d_t, d_off, B, N, d_z_frac, d_z_lengths, d_u_types, d_const_types,
+                         d_fixed_lengths, cond, d_lattice, d_length_tie, stream, "arreau_resample_jump_tied");
 }

@@ -4,6 +4,8 @@
 
 // VP_lattice.reverse_given_x0 (diffusion_helpers.py:185-199) on lengths, then lattice_from_params.
 // Note the reference adds `variance * z` (not sqrt(variance)) and zeroes z when t <= 1.
+// TIE: the lattice-system tie of the lengths (length_tie[b]); the three x0 and current lengths are exchanged by shuffles.
+template <bool TIE>
 __device__ __forceinline__ void reverse_lattice_body(int gt /* global thread of the lattice part */, float* __restrict__ lengths, const float* __restrict__ angles,
                                        const int32_t* __restrict__ tstep, const int32_t* __restrict__ offsets,
                                        const float* __restrict__ len0, StepNoiseSrc noise,
@@ -13,7 +15,7 @@ __device__ __forceinline__ void reverse_lattice_body(int gt /* global thread of 
                                        // sampling loop: pool the per-atom read-out here (same ordered sum as
                                        // readout_crystals_kernel) instead of a launch of its own; len0_out receives it
                                        const float* __restrict__ gs_atoms, float* __restrict__ len0_out, const SampleConditionDev* cond,
-                                       const StepScheduleDev* sched, uint32_t word3) {
+                                       const StepScheduleDev* sched, uint32_t word3, const int32_t* __restrict__ length_tie) {
     // four lanes per crystal: lane i < 3 owns length component i (pooling, update), lane 0 then writes the cell
     const int b = b0 + (gt >> 2), i = gt & 3;
     const bool live = b < B;  // (whole groups of four are live or not; the shuffles below need every lane)
@@ -24,9 +26,27 @@ __device__ __forceinline__ void reverse_lattice_body(int gt /* global thread of 
     const int s_to = step_target(sched, bc, t, status, live && i == 0);
     const int first = offsets[bc], last = offsets[bc + 1];
     float mylen = 0.f;
-    if (live && i < 3)
-        mylen = reverse_length_component(b, i, t, s_to, sched, first, last, lengths, len0, noise, alpha_bars, betas, fixed_lengths, gs_atoms,
-                                         len0_out, cond, word3);
+    if constexpr (TIE) {
+        const int code = length_tie_code(length_tie, cond ? cond->len_mask : nullptr, bc, status, live && i == 0);
+        float x0 = 0.f, xt = 0.f;
+        if (live && i < 3) {
+            x0 = length_x0_component(b, i, first, last, len0, gs_atoms, len0_out);
+            xt = lengths[3 * b + i];
+        }
+        const int lead = (threadIdx.x & 63) & ~3;
+        float x0s[3], xts[3];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            x0s[q] = __shfl(x0, lead + q, 64);
+            xts[q] = __shfl(xt, lead + q, 64);
+        }
+        if (live && i < 3)
+            mylen = tied_length_component(b, i, code, x0s, xts, t, s_to, sched, lengths, noise, alpha_bars, betas, fixed_lengths, cond, word3);
+    } else {
+        if (live && i < 3)
+            mylen = reverse_length_component(b, i, t, s_to, sched, first, last, lengths, len0, noise, alpha_bars, betas, fixed_lengths,
+                                             gs_atoms, len0_out, cond, word3);
+    }
     const int base = (threadIdx.x & 63) & ~3;
     float newlen[3];
 #pragma unroll
@@ -54,7 +74,9 @@ __device__ __forceinline__ void reverse_lattice_body(int gt /* global thread of 
 // RESAMPLE: a step of a resampled loop (arreau_sample_loop_resampled) in pass r of a block, r read from the loop's device word
 // `pass` (set by the jump in front of the pass, reset after the block), so one captured step serves every pass.  Every draw of
 // the step takes counter word3 = 256 r; pass 0 draws what the plain kernel draws.  Without RESAMPLE `pass` is not read.
-template <bool COND, bool SCHED, bool RESAMPLE>
+// TIE: lattice systems (arreau_sample_loop_tied): the lengths of crystal b are tied by the code length_tie[b] (0 none, 1 a = b,
+// 2 a = b = c; rules in include/arreau_hip.h).  Without TIE `length_tie` is not read.
+template <bool COND, bool SCHED, bool RESAMPLE, bool TIE>
 __global__ __launch_bounds__(256) void reverse_kernel(
     int lat_blocks, float* __restrict__ lengths, const float* __restrict__ angles, const int32_t* __restrict__ tstep,
     const int32_t* __restrict__ offsets, const float* __restrict__ len0, StepNoiseSrc noise, const float* __restrict__ alpha_bars,
@@ -66,18 +88,19 @@ __global__ __launch_bounds__(256) void reverse_kernel(
     const int32_t* __restrict__ batch,
     // sampling loop: the lattice part is one workgroup per crystal, which also prepares the next step (reverse_crystal_block)
     float* __restrict__ lattice_ws, float* __restrict__ cvec_next, const float* __restrict__ t_emb_w, const float* __restrict__ embT, int C,
-    SampleConditionDev cond_arg, StepScheduleDev sched_arg, const int32_t* __restrict__ pass) {
+    SampleConditionDev cond_arg, StepScheduleDev sched_arg, const int32_t* __restrict__ pass, const int32_t* __restrict__ length_tie) {
     const uint32_t word3 = RESAMPLE ? 256u * (uint32_t)pass[0] : 0u;  // the counter word of pass r
     const SampleConditionDev* cond = COND ? &cond_arg : nullptr;
     const StepScheduleDev* sched = SCHED ? &sched_arg : nullptr;
     if ((int)blockIdx.x < lat_blocks && cvec_next != nullptr) {  // (kernel argument: uniform)
-        reverse_crystal_block(b0 + (int)blockIdx.x, lengths, angles, tstep, offsets, len0, noise, alpha_bars, betas, T, lattice, fixed_lengths,
-                              status, gs_atoms, len0_out, lattice_ws, cvec_next, t_emb_w, embT, S, C, cond, sched, word3);
+        reverse_crystal_block<TIE>(b0 + (int)blockIdx.x, lengths, angles, tstep, offsets, len0, noise, alpha_bars, betas, T, lattice,
+                                   fixed_lengths, status, gs_atoms, len0_out, lattice_ws, cvec_next, t_emb_w, embT, S, C, cond, sched, word3,
+                                   length_tie);
         return;
     }
     if ((int)blockIdx.x < lat_blocks) {
-        reverse_lattice_body(blockIdx.x * blockDim.x + threadIdx.x, lengths, angles, tstep, offsets, len0, noise, alpha_bars, betas, B_lat, T,
-                             lattice, fixed_lengths, status, b0, gs_atoms, len0_out, cond, sched, word3);
+        reverse_lattice_body<TIE>(blockIdx.x * blockDim.x + threadIdx.x, lengths, angles, tstep, offsets, len0, noise, alpha_bars, betas, B_lat,
+                                  T, lattice, fixed_lengths, status, b0, gs_atoms, len0_out, cond, sched, word3, length_tie);
         return;
     }
     reverse_atoms_body((int)blockIdx.x - lat_blocks, frac, types, tstep, offsets, B, N, eps, logits, noise, ve_sigmas, q1t, qmats, S, T,
@@ -91,13 +114,14 @@ void enqueue_reverse_kernel(const arreau_model* m, int lat_blocks, int atom_bloc
                             const float* d_logits, const float* d_len0, StepNoiseSrc noise, const int32_t* d_const_types,
                             float* d_lattice, hipStream_t s, const float* d_fixed_lengths, const float* d_gs_atoms,
                             const int32_t* d_batch, float* d_lattice_ws, float* d_cvec_next, const SampleConditionDev& cond,
-                            const StepScheduleDev& sched, const int32_t* d_pass) {
-    auto kernel = d_pass ? reverse_kernel<COND, SCHED, true> : reverse_kernel<COND, SCHED, false>;
+                            const StepScheduleDev& sched, const int32_t* d_pass, const int32_t* d_length_tie) {
+    auto kernel = d_length_tie ? (d_pass ? reverse_kernel<COND, SCHED, true, true> : reverse_kernel<COND, SCHED, false, true>)
+                               : (d_pass ? reverse_kernel<COND, SCHED, true, false> : reverse_kernel<COND, SCHED, false, false>);
     ARREAU_LAUNCH(kernel, dim3(lat_blocks + atom_blocks), dim3(256), 0, s, lat_blocks, d_lengths, d_angles, d_t, d_off, d_len0, noise,
                   m->vp_alpha_bars, m->vp_betas, B, m->T, d_lattice, d_fixed_lengths, m->status, 0, d_gs_atoms,
                   d_gs_atoms ? const_cast<float*>(d_len0) : nullptr, d_frac, d_types, B, N, d_eps, d_logits, m->ve_sigmas, m->q1t,
                   m->qmats, m->S, d_const_types, m->qmats_absorbing, 0, d_batch, d_lattice_ws, d_cvec_next, m->t_emb_w, m->embT, m->C,
-                  cond, sched, d_pass);
+                  cond, sched, d_pass, d_length_tie);
 }
 }  // namespace
 
@@ -106,7 +130,7 @@ int arreau_launch_reverse(const arreau_model* m, float* d_frac, int32_t* d_types
                           const float* d_logits, const float* d_len0, StepNoiseSrc noise, const int32_t* d_const_types,
                           float* d_lattice, hipStream_t s, const float* d_fixed_lengths, const float* d_gs_atoms,
                           const int32_t* d_batch, float* d_lattice_ws, float* d_cvec_next, const SampleConditionDev* cond,
-                          const StepScheduleDev* sched, const int32_t* d_pass) {
+                          const StepScheduleDev* sched, const int32_t* d_pass, const int32_t* d_length_tie) {
     const bool prep_next = d_cvec_next != nullptr;  // one workgroup per crystal, which also prepares the next step
     ARREAU_REQUIRE(!prep_next || d_lattice_ws != nullptr, "reverse update: the next step's set-up needs the workspace lattice");
     const int lat_blocks = B > 0 ? (prep_next ? B : (4 * B + 255) / 256) : 0;
@@ -121,7 +145,7 @@ int arreau_launch_reverse(const arreau_model* m, float* d_frac, int32_t* d_types
     const SampleConditionDev c = conditioned ? *cond : SampleConditionDev{};
     const StepScheduleDev sc = scheduled ? *sched : StepScheduleDev{};
 #define ARREAU_REVERSE_ARGS m, lat_blocks, atom_blocks, d_frac, d_types, d_lengths, d_angles, d_t, d_off, B, N, d_eps, d_logits, d_len0, \
-        noise, d_const_types, d_lattice, s, d_fixed_lengths, d_gs_atoms, d_batch, d_lattice_ws, d_cvec_next, c, sc, d_pass
+        noise, d_const_types, d_lattice, s, d_fixed_lengths, d_gs_atoms, d_batch, d_lattice_ws, d_cvec_next, c, sc, d_pass, d_length_tie
     if (conditioned && scheduled) enqueue_reverse_kernel<true, true>(ARREAU_REVERSE_ARGS);
     else if (conditioned) enqueue_reverse_kernel<true, false>(ARREAU_REVERSE_ARGS);
     else if (scheduled) enqueue_reverse_kernel<false, true>(ARREAU_REVERSE_ARGS);
@@ -144,19 +168,38 @@ extern "C" int arreau_reverse_step(const arreau_model* m, float* d_frac, int32_t
 }
 
 // arreau_reverse_step from timestep t to a per-crystal target s (respaced sampling; rules in include/arreau_hip.h).
+static int reverse_step_to(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                           const int32_t* d_t, const int32_t* d_s, const int32_t* d_off, int32_t B, int32_t N, const float* d_eps,
+                           const float* d_logits, const float* d_len0, const float* d_z_lattice, const float* d_z_frac,
+                           const float* d_u_types, float* d_lattice, float lattice_clipmax, const int32_t* d_length_tie, void* stream,
+                           const char* who) {
+    ARREAU_REQUIRE(m && d_frac && d_types && d_lengths && d_angles && d_t && d_s && d_off && d_eps && d_logits && d_len0 &&
+                       d_z_lattice && d_z_frac && d_u_types && d_lattice, std::string(who) + ": null pointer");
+    ARREAU_REQUIRE(B >= 1 && N >= 0, std::string(who) + ": bad size");
+    ARREAU_REQUIRE(lattice_clipmax > 0.0f && lattice_clipmax <= 1.0f, std::string(who) + ": lattice_clipmax must lie in (0, 1]");
+    const StepScheduleDev sched{nullptr, d_s, lattice_clipmax};
+    return arreau_launch_reverse(m, d_frac, d_types, d_lengths, d_angles, d_t, d_off, B, N, d_eps, d_logits, d_len0,
+                                 StepNoiseSrc{d_z_lattice, d_z_frac, d_u_types, 0}, nullptr, d_lattice, (hipStream_t)stream, nullptr,
+                                 nullptr, nullptr, nullptr, nullptr, nullptr, &sched, nullptr, d_length_tie);
+}
+
 extern "C" int arreau_reverse_step_to(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths,
                                       const float* d_angles, const int32_t* d_t, const int32_t* d_s, const int32_t* d_off, int32_t B,
                                       int32_t N, const float* d_eps, const float* d_logits, const float* d_len0,
                                       const float* d_z_lattice, const float* d_z_frac, const float* d_u_types, float* d_lattice,
                                       float lattice_clipmax, void* stream) {
-    ARREAU_REQUIRE(m && d_frac && d_types && d_lengths && d_angles && d_t && d_s && d_off && d_eps && d_logits && d_len0 &&
-                       d_z_lattice && d_z_frac && d_u_types && d_lattice, "arreau_reverse_step_to: null pointer");
-    ARREAU_REQUIRE(B >= 1 && N >= 0, "arreau_reverse_step_to: bad size");
-    ARREAU_REQUIRE(lattice_clipmax > 0.0f && lattice_clipmax <= 1.0f, "arreau_reverse_step_to: lattice_clipmax must lie in (0, 1]");
-    const StepScheduleDev sched{nullptr, d_s, lattice_clipmax};
-    return arreau_launch_reverse(m, d_frac, d_types, d_lengths, d_angles, d_t, d_off, B, N, d_eps, d_logits, d_len0,
-                                 StepNoiseSrc{d_z_lattice, d_z_frac, d_u_types, 0}, nullptr, d_lattice, (hipStream_t)stream, nullptr,
-                                 nullptr, nullptr, nullptr, nullptr, nullptr, &sched);
+    return reverse_step_to(m, d_frac, d_types, d_lengths, d_angles, d_t, d_s, d_off, B, N, d_eps, d_logits, d_len0, d_z_lattice, d_z_frac,
+                           d_u_types, d_lattice, lattice_clipmax, nullptr, stream, "arreau_reverse_step_to");
+}
+
+// arreau_reverse_step_to with the lattice-system tie of the lengths (rules in include/arreau_hip.h); NULL = arreau_reverse_step_to.
+extern "C" int arreau_reverse_step_tied(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths,
+                                        const float* d_angles, const int32_t* d_t, const int32_t* d_s, const int32_t* d_off, int32_t B,
+                                        int32_t N, const float* d_eps, const float* d_logits, const float* d_len0,
+                                        const float* d_z_lattice, const float* d_z_frac, const float* d_u_types, float* d_lattice,
+                                        float lattice_clipmax, const int32_t* d_length_tie, void* stream) {
+    return reverse_step_to(m, d_frac, d_types, d_lengths, d_angles, d_t, d_s, d_off, B, N, d_eps, d_logits, d_len0, d_z_lattice, d_z_frac,
+                           d_u_types, d_lattice, lattice_clipmax, d_length_tie, stream, "arreau_reverse_step_tied");
 }
 
 // The sampler's in-kernel noise, written out: out[i] = the draw (seed, timestep, kind, element i, word3) -- standard normal for

@@ -98,6 +98,73 @@ __device__ __forceinline__ float reverse_length_component(int b, int i, int t, i
     return mylen;
 }
 
+// Lattice systems (arreau_sample_loop_tied; the rules are stated in include/arreau_hip.h): the tie code of crystal b -- 0 none,
+// 1 a = b, 2 a = b = c.  A code outside 0..2 counts as 0 and is flagged (by the crystal's one thread: `flag`); a crystal whose
+// lengths a condition knows is not tied (rule 4).
+__device__ __forceinline__ int length_tie_code(const int32_t* __restrict__ tie, const uint8_t* __restrict__ len_mask, int b,
+                                               int32_t* __restrict__ status, bool flag) {
+    int code = tie[b];
+    if (code < 0 || code > 2) {
+        if (flag) atomicOr(status, ARREAU_STATUS_BAD_TIE);  // untied, but flagged
+        code = 0;
+    }
+    return (len_mask && len_mask[b]) ? 0 : code;
+}
+// Axis i is in the tied group G of code `code` (G = {0 .. code} for code >= 1; axis 0 leads).
+__device__ __forceinline__ bool length_tied(int code, int i) { return code > 0 && i <= code; }
+
+// Lattice systems, the length update of crystal b in two halves around the exchange of the three components (LDS or shuffles):
+// the x0 of component i (pooled from gs_atoms when given, len0_out receiving the pooled value), then the tied update.  The
+// arithmetic is reverse_length_component's, operation for operation (a code-0 crystal computes the same bits); it is kept apart so
+// that the untied kernel instances keep their instructions.
+__device__ __forceinline__ float length_x0_component(int b, int i, int first, int last, const float* __restrict__ len0,
+                                                     const float* __restrict__ gs_atoms, float* __restrict__ len0_out) {
+    const float n = (float)(last - first);
+    float pooled;
+    if (gs_atoms != nullptr) {
+        pooled = 0.f;  // the ordered sum of readout_crystals_kernel
+        int a = first;
+        for (; a + 3 < last; a += 4) {
+            const float v0 = gs_atoms[(size_t)a * 3 + i], v1 = gs_atoms[(size_t)(a + 1) * 3 + i];
+            const float v2 = gs_atoms[(size_t)(a + 2) * 3 + i], v3 = gs_atoms[(size_t)(a + 3) * 3 + i];
+            pooled = (((pooled + v0) + v1) + v2) + v3;
+        }
+        for (; a < last; ++a) pooled += gs_atoms[(size_t)a * 3 + i];
+        len0_out[3 * b + i] = pooled;
+    } else {
+        pooled = len0[3 * b + i];
+    }
+    return pooled * n;  // pred_lengths_0 * num_atoms (diffusion_loss.py:338)
+}
+// Component i of the tied update (rule 1): an axis of the tied group G takes the leader's x_t and draw (element 3 b) and the group's
+// mean x0 (summed in axis order, divided by |G|), so every axis of G computes the same bits; the others their own.  x0s / xts: the
+// crystal's three x0 and current lengths.  Writes lengths[3 b + i] and returns it.
+__device__ __forceinline__ float tied_length_component(int b, int i, int code, const float* x0s, const float* xts, int t, int s,
+                                                       const StepScheduleDev* sched, float* __restrict__ lengths, StepNoiseSrc noise,
+                                                       const float* __restrict__ alpha_bars, const float* __restrict__ betas,
+                                                       const float* __restrict__ fixed_lengths, const SampleConditionDev* cond,
+                                                       uint32_t word3) {
+    const bool tied = length_tied(code, i);
+    const float* __restrict__ z = noise.z_lattice;
+    const float ab_t = alpha_bars[t], ab_p = alpha_bars[s];
+    const float beta = (sched == nullptr || s == t - 1) ? betas[t] : fminf(1.0f - ab_t / ab_p, sched->clipmax);
+    const float denom = 1.0f - ab_t;
+    const float alpha_t = 1.0f - beta;
+    const float c0 = sqrtf(ab_p) * beta;
+    const float c1 = sqrtf(alpha_t) * (1.0f - ab_p);
+    const float variance = (1.0f - ab_p) * beta / denom;
+    const float x0 = !tied ? x0s[i] : (code == 1 ? (x0s[0] + x0s[1]) / 2.0f : ((x0s[0] + x0s[1]) + x0s[2]) / 3.0f);
+    const float xt = tied ? xts[0] : xts[i];
+    const float mean = (c0 * x0 + c1 * xt) / denom;
+    const uint32_t e = 3u * b + (tied ? 0u : (uint32_t)i);
+    const float zdraw = z ? z[e] : philox_normal(noise.seed, (uint32_t)t, ARREAU_DRAW_Z_LATTICE, e, word3);
+    const float zz = t > 1 ? zdraw : 0.0f;
+    float mylen = fixed_lengths ? fixed_lengths[3 * b + i] : mean + variance * zz;  // a fixed cell: the (host-tied) given lengths
+    if (cond && cond->len_mask && cond->len_mask[b]) mylen = known_length_component(cond, b, i, t, s, noise.seed, alpha_bars, word3);
+    lengths[3 * b + i] = mylen;
+    return mylen;
+}
+
 // One wave per atom: VE_pbc.reverse on the fractional coordinates (diffusion_helpers.py:65-81) and
 // D3PM.reverse on the atom type (d3pm.py:74-110, 198-215), from timestep t to s (t - 1 without a schedule).  Lanes span the S
 // classes (2 per lane).
@@ -276,6 +343,8 @@ __device__ __forceinline__ void reverse_atoms_body(
 // scheduled successor of t in a respaced loop).
 // The step then needs no prep launch (the Cartesian positions, prep's other product, are formed by the neighbour-list waves
 // from the fractional coordinates).  Same arithmetic as reverse_lattice_body + prep_kernel, thread for thread.
+// TIE: the lattice-system tie of the lengths (length_tie[b]); the three x0 and current lengths are exchanged through LDS.
+template <bool TIE>
 __device__ __forceinline__ void reverse_crystal_block(int b, float* __restrict__ lengths, const float* __restrict__ angles,
                                                       const int32_t* __restrict__ tstep, const int32_t* __restrict__ offsets,
                                                       const float* __restrict__ len0, StepNoiseSrc noise,
@@ -285,7 +354,7 @@ __device__ __forceinline__ void reverse_crystal_block(int b, float* __restrict__
                                                       float* __restrict__ len0_out, float* __restrict__ lattice_ws,
                                                       float* __restrict__ cvec_next, const float* __restrict__ t_emb_w,
                                                       const float* __restrict__ embT, int S, int C, const SampleConditionDev* cond,
-                                                      const StepScheduleDev* sched, uint32_t word3) {
+                                                      const StepScheduleDev* sched, uint32_t word3, const int32_t* __restrict__ length_tie) {
     __shared__ float newlen[3];
     __shared__ float feat[ARREAU_T_EMB_DIM + ARREAU_N_CRYSTAL_FEATS];
     const int t_raw = tstep[b];
@@ -293,9 +362,22 @@ __device__ __forceinline__ void reverse_crystal_block(int b, float* __restrict__
     const int t = t_raw < 1 ? 1 : (t_raw > T ? T : t_raw);
     const int s = step_target(sched, b, t, status, threadIdx.x == 0);
     const int first = offsets[b], last = offsets[b + 1];
-    if (threadIdx.x < 3)
-        newlen[threadIdx.x] = reverse_length_component(b, threadIdx.x, t, s, sched, first, last, lengths, len0, noise, alpha_bars, betas, fixed_lengths,
-                                                       gs_atoms, len0_out, cond, word3);
+    if constexpr (TIE) {
+        __shared__ float x0s[3], xts[3];
+        const int code = length_tie_code(length_tie, cond ? cond->len_mask : nullptr, b, status, threadIdx.x == 0);
+        if (threadIdx.x < 3) {
+            x0s[threadIdx.x] = length_x0_component(b, threadIdx.x, first, last, len0, gs_atoms, len0_out);
+            xts[threadIdx.x] = lengths[3 * b + threadIdx.x];
+        }
+        __syncthreads();
+        if (threadIdx.x < 3)
+            newlen[threadIdx.x] = tied_length_component(b, threadIdx.x, code, x0s, xts, t, s, sched, lengths, noise, alpha_bars, betas,
+                                                        fixed_lengths, cond, word3);
+    } else {
+        if (threadIdx.x < 3)
+            newlen[threadIdx.x] = reverse_length_component(b, threadIdx.x, t, s, sched, first, last, lengths, len0, noise, alpha_bars, betas,
+                                                           fixed_lengths, gs_atoms, len0_out, cond, word3);
+    }
     __syncthreads();
     const float* ang = angles + 3 * b;
     if (threadIdx.x == 0) {

@@ -15,7 +15,8 @@ from . import corrector as pc
 from . import resampling as rs
 from . import respacing
 from .d3pm import D3PM
-from .diffusion_helpers import VE_pbc, VP_lattice, crystal_offsets, sample_bravais_angles
+from . import lattice_systems
+from .diffusion_helpers import VE_pbc, VP_lattice, crystal_offsets
 from .inference.visualize_crystal import VisualizationSetting, vis_crystal_during_sampling
 from .tools.atomic_number_table import AtomicNumberTable, atomic_number_indexes_to_atomic_numbers
 
@@ -261,7 +262,8 @@ class DiffusionLoss(nn.Module):
                max_steps: Optional[int] = None, use_graph: Optional[bool] = None, seed: Optional[int] = None,
                fixed_cell: bool = False, condition=None, num_steps: Optional[int] = None,
                timesteps: Optional[Sequence[int]] = None, corrector_steps: int = 0,
-               corrector_snr: float = pc.DEFAULT_SNR, resample_passes: int = 1, jump_length: int = 10) -> SampleResult:
+               corrector_snr: float = pc.DEFAULT_SNR, resample_passes: int = 1, jump_length: int = 10,
+               lattice_system=None) -> SampleResult:
         """diffusion_loss.py:276-377.  The initial state is drawn on the host exactly like the reference (numpy
         uniforms for the angles, then randn lengths, randn fractional coordinates from torch's global CPU generator).
         Per-step noise:
@@ -304,7 +306,14 @@ class DiffusionLoss(nn.Module):
         events of resampling.plan on the host, each jump (arreau_resample_jump) drawing randn[N,3], randn[B,3], rand[N,S] from
         that mode's generator just before the pass it precedes.  R = 1 is the sampler without resampling bit for bit (and draws
         nothing extra).  With R > 1 only visualization_setting NONE or LAST is accepted (a frame inside a block would be
-        overwritten by the next pass).  No sample-quality claim is made."""
+        overwritten by the next pass).  No sample-quality claim is made.
+        `lattice_system` (extension, every noise mode): crystals of a chosen lattice system -- one of lattice_systems.SYSTEMS for
+        every crystal, or a sequence with one name (or None) per crystal.  A crystal of a system gets the system's angles in
+        radians (np.deg2rad of sample_bravais_angles) and its tied lengths (a = b, or a = b = c) are kept bitwise equal at every
+        step on the device (arreau_sample_loop_tied; rules in include/arreau_hip.h), the initial lengths tied on the host.
+        None keeps the sampler as it was, bit for bit: monoclinic angles drawn in DEGREES and read as radians, the reference's
+        own behaviour -- so None and "monoclinic" differ.  A system on a crystal whose cell a condition knows is rejected.  No
+        sample-quality claim is made."""
         frames = visualization_setting != VisualizationSetting.NONE
         if frames and not vis_name:
             raise ValueError("visualization_setting other than NONE needs vis_name (prefix of the frame files)")
@@ -321,10 +330,11 @@ class DiffusionLoss(nn.Module):
             condition.check_sampling(z_table, noise=noise, fixed_cell=fixed_cell, constant_species=constant_atoms is not None)
         elif num_atoms_per_sample is None or num_samples_in_batch is None:
             raise ValueError("num_atoms_per_sample and num_samples_in_batch are needed without a condition")
+        B = int(num_samples_in_batch)
+        lattice_systems.check(lattice_system, B, condition.lattice_known() if condition is not None else None)
         eng = model.engine()
         dev = eng.device
         S = len(z_table)
-        B = int(num_samples_in_batch)
         # Extension over the reference (uniform n only, diffusion_loss.py:308): a sequence gives each crystal of
         # the batch its own atom count (the HIP path works on CSR offsets, so ragged batches cost nothing extra).
         if isinstance(num_atoms_per_sample, (int, np.integer)):
@@ -335,11 +345,15 @@ class DiffusionLoss(nn.Module):
                 raise ValueError("num_atoms_per_sample must be an int or hold one positive count per crystal of the batch")
         N = int(num_atoms.sum())
         dt = torch.get_default_dtype()
-        angles = torch.tensor(np.array([sample_bravais_angles("monoclinic") for _ in range(B)]))
+        # the angles per crystal (numpy's generator; lattice_system=None: the monoclinic draw in degrees, as the reference)
+        angles_np, tie = lattice_systems.resolve(lattice_system, B, condition.lattice_known() if condition is not None else None)
+        angles = torch.tensor(angles_np)
         if condition is not None and condition.lattice_known().any():  # rule 3: the template's angles (radians)
             known = torch.as_tensor(condition.lattice_known())
             angles[known] = torch.as_tensor(condition.known_angles(), dtype=angles.dtype)[known]
         lengths = torch.randn([B, 3])
+        if tie is not None:
+            lattice_systems.tie_lengths(lengths, tie)  # the initial state's tie; the device keeps it at every step
         frac_x = torch.randn([N, 3], dtype=dt) * pos_sigma_max
         if constant_atoms is not None:
             atom_types = torch.as_tensor(constant_atoms).reshape(-1).long()
@@ -356,6 +370,7 @@ class DiffusionLoss(nn.Module):
         const_d = types_d.clone() if constant_atoms is not None else None
         off_d = crystal_offsets(num_atoms, dev)
         lattice_d = torch.zeros((B, 3, 3), **f32)
+        tie_d = torch.as_tensor(tie, device=dev, dtype=torch.int32).contiguous() if tie is not None else None
         # the timesteps this run visits, in order: every one (T-1 .. 1) or the schedule's, cut to max_steps
         steps = list(range(self.T - 1, 0, -1)) if schedule is None else schedule
         steps = steps if max_steps is None else steps[:max(0, int(max_steps))]
@@ -408,7 +423,7 @@ class DiffusionLoss(nn.Module):
                     if end > start:
                         eng.sample_loop(frac_d, types_d, len_d, ang_d, off_d, steps[start], end - start, seed, const_d, lattice_d,
                                         use_graph=bool(use_graph), fixed_lengths=fixed, condition=cond_d, next_table=next_d,
-                                        lattice_clipmax=clipmax, corrector=corrector, resampling=resampling)
+                                        lattice_clipmax=clipmax, corrector=corrector, resampling=resampling, length_tie=tie_d)
                         start = end
                     if j is not None:
                         vis_crystal_during_sampling(z_table, types_d.cpu().numpy(), lattice_d.cpu().numpy(),
@@ -434,7 +449,8 @@ class DiffusionLoss(nn.Module):
                         z_f, z_l, u_t = gauss(N, 3), gauss(B, 3), unif(N, S)
                         s_d.fill_(ev.s)
                         t_d.fill_(ev.t)
-                        eng.resample_jump(frac_d, types_d, len_d, ang_d, s_d, t_d, off_d, z_f, z_l, u_t, lattice_d, const_types=const_d)
+                        eng.resample_jump(frac_d, types_d, len_d, ang_d, s_d, t_d, off_d, z_f, z_l, u_t, lattice_d, const_types=const_d,
+                                          length_tie=tie_d)
                         continue
                     t_d.fill_(timestep)
                     eps, logits, len0 = eng.predict_scores(frac_d, types_d, len_d, ang_d, t_d, off_d)
@@ -442,7 +458,11 @@ class DiffusionLoss(nn.Module):
                         eng.corrector_step(frac_d, t_d, off_d, eps, gauss(N, 3), corrector_snr)
                         eps, logits, len0 = eng.predict_scores(frac_d, types_d, len_d, ang_d, t_d, off_d)
                     z_l, z_f, u_t = gauss(B, 3), gauss(N, 3), unif(N, S)
-                    if schedule is None:
+                    if tie_d is not None:  # lattice systems: the tied step (s = t - 1 without a schedule is the plain step)
+                        s_d.fill_(timestep - 1 if schedule is None else successor[timestep])
+                        eng.reverse_step_tied(frac_d, types_d, len_d, ang_d, t_d, s_d, off_d, eps, logits, len0, z_l, z_f, u_t,
+                                              lattice_d, tie_d, clipmax)
+                    elif schedule is None:
                         eng.reverse_step(frac_d, types_d, len_d, ang_d, t_d, off_d, eps, logits, len0, z_l, z_f, u_t, lattice_d)
                     else:
                         s_d.fill_(successor[timestep])

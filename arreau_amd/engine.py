@@ -127,6 +127,8 @@ class HipEngine:
                 why.append("a timestep index was outside the schedule")
             if f & _hip.STATUS_BAD_TYPE:
                 why.append("an atom-type index was outside [0, num_atomic_states)")
+            if f & _hip.STATUS_BAD_TIE:
+                why.append("a lattice-system tie code was outside 0..2")
             raise _hip.ArreauHipError("arreau_hip status flags %d: %s" % (f, "; ".join(why)))
         return st
 
@@ -193,7 +195,7 @@ class HipEngine:
 
     def sample_loop(self, frac, types, lengths, angles, offsets, t_start, n_steps, seed, const_types, lattice_out,
                     use_graph=False, fixed_lengths=None, condition=None, next_table=None, lattice_clipmax=0.999, corrector=None,
-                    resampling=None):
+                    resampling=None, length_tie=None):
         """n_steps iterations of the sampling loop in one library call (arreau_sample_loop; with any of the options below
         arreau_sample_loop_resampled, whose NULL options are the loop without them): in-place update of
         (frac, types, lengths); Philox noise keyed by (seed, timestep, draw, element).  `condition`: the device arrays of a
@@ -205,7 +207,9 @@ class HipEngine:
         `resampling`: (passes, jump_length[, timesteps]) -- RePaint resampling (arreau_sample_loop_resampled): the call's steps in
         blocks of jump_length, each run `passes` times with a forward jump back to the block's top in front of every pass after
         the first; `timesteps` is the host list of the schedule behind next_table (required with it).  None or passes == 1 is
-        the loop without resampling."""
+        the loop without resampling.
+        `length_tie`: lattice systems (arreau_sample_loop_tied): a contiguous int32 [B] tensor on the device, the tie code of every
+        crystal's lengths (0 none, 1 a = b, 2 a = b = c; lattice_systems.py); None is the loop without it."""
         res = None
         if resampling is not None:
             from .diffusion.resampling import check_resampling
@@ -234,6 +238,13 @@ class HipEngine:
             sched = _hip.SampleScheduleC(_hip.ptr(next_table).value, float(lattice_clipmax))
         cond = self._condition_struct(condition, N, B) if condition is not None else None
         corr = _hip.CorrectorC(corrector[0], corrector[1]) if corrector is not None else None
+        if length_tie is not None:
+            self._check_tie(length_tie, B)
+            _hip.check(_hip.lib().arreau_sample_loop_tied(
+                *args, ctypes.byref(cond) if cond is not None else None, ctypes.byref(sched) if sched is not None else None,
+                ctypes.byref(corr) if corr is not None else None, ctypes.byref(res) if res is not None else None, _hip.ptr(length_tie),
+                _hip.stream_ptr(self.device)), "arreau_sample_loop_tied")
+            return
         if cond is None and sched is None and corr is None and res is None:
             # (the plain entry point: A/B runs against an older library through ARREAU_HIP_LIB call it)
             _hip.check(_hip.lib().arreau_sample_loop(*args, _hip.stream_ptr(self.device)), "arreau_sample_loop")
@@ -241,6 +252,11 @@ class HipEngine:
         byref = lambda v: ctypes.byref(v) if v is not None else None
         _hip.check(_hip.lib().arreau_sample_loop_resampled(*args, byref(cond), byref(sched), byref(corr), byref(res),
                                                            _hip.stream_ptr(self.device)), "arreau_sample_loop_resampled")
+
+    def _check_tie(self, length_tie, B):
+        if (tuple(length_tie.shape) != (B,) or length_tie.dtype != torch.int32 or length_tie.device != self.device
+                or not length_tie.is_contiguous()):
+            raise ValueError(f"length_tie must be a contiguous int32 tensor of shape ({B},) on {self.device}")
 
     def condition_initial_state(self, frac, types, lengths, t_start, seed, condition):
         """Rule 5 of conditioned sampling (arreau_condition_initial_state): the known components of an initial state drawn
@@ -538,13 +554,33 @@ class HipEngine:
             _hip.ptr(z_frac), _hip.ptr(u_types), _hip.ptr(lattice_out), float(lattice_clipmax), _hip.stream_ptr(self.device)),
             "arreau_reverse_step_to")
 
+    def reverse_step_tied(self, frac, types, lengths, angles, t_crystal, s_crystal, offsets, eps, logits, len0, z_lattice, z_frac,
+                          u_types, lattice_out, length_tie, lattice_clipmax=0.999):
+        """reverse_step_to with the lattice-system tie of the lengths (arreau_reverse_step_tied): length_tie [B] int32 codes."""
+        B, N = lengths.shape[0], frac.shape[0]
+        self._check_tie(length_tie, B)
+        _hip.check(_hip.lib().arreau_reverse_step_tied(
+            self._handle, _hip.ptr(frac), _hip.ptr(types), _hip.ptr(lengths), _hip.ptr(angles), _hip.ptr(t_crystal),
+            _hip.ptr(s_crystal), _hip.ptr(offsets), B, N, _hip.ptr(eps), _hip.ptr(logits), _hip.ptr(len0), _hip.ptr(z_lattice),
+            _hip.ptr(z_frac), _hip.ptr(u_types), _hip.ptr(lattice_out), float(lattice_clipmax), _hip.ptr(length_tie),
+            _hip.stream_ptr(self.device)), "arreau_reverse_step_tied")
+
     def resample_jump(self, frac, types, lengths, angles, s_crystal, t_crystal, offsets, z_frac, z_lengths, u_types, lattice_out,
-                      const_types=None, fixed_lengths=None, condition=None):
+                      const_types=None, fixed_lengths=None, condition=None, length_tie=None):
         """One RePaint jump of the whole state from timestep s_crystal[b] up to t_crystal[b] (arreau_resample_jump), in place,
         with the caller's noise: z_frac [N,3] and z_lengths [B,3] standard normal, u_types [N,S] uniform.  Held: const_types,
-        fixed_lengths, and the species of `condition`'s type mask (a dict as in sample_loop)."""
+        fixed_lengths, and the species of `condition`'s type mask (a dict as in sample_loop).  `length_tie`: the lattice-system
+        tie codes [B] int32 (arreau_resample_jump_tied); None is the jump without them."""
         B, N = lengths.shape[0], frac.shape[0]
         cond = self._condition_struct(condition, N, B) if condition is not None else None
+        if length_tie is not None:
+            self._check_tie(length_tie, B)
+            _hip.check(_hip.lib().arreau_resample_jump_tied(
+                self._handle, _hip.ptr(frac), _hip.ptr(types), _hip.ptr(lengths), _hip.ptr(angles), _hip.ptr(s_crystal),
+                _hip.ptr(t_crystal), _hip.ptr(offsets), B, N, _hip.ptr(z_frac), _hip.ptr(z_lengths), _hip.ptr(u_types),
+                _hip.ptr(const_types), _hip.ptr(fixed_lengths), ctypes.byref(cond) if cond is not None else None,
+                _hip.ptr(lattice_out), _hip.ptr(length_tie), _hip.stream_ptr(self.device)), "arreau_resample_jump_tied")
+            return
         _hip.check(_hip.lib().arreau_resample_jump(
             self._handle, _hip.ptr(frac), _hip.ptr(types), _hip.ptr(lengths), _hip.ptr(angles), _hip.ptr(s_crystal),
             _hip.ptr(t_crystal), _hip.ptr(offsets), B, N, _hip.ptr(z_frac), _hip.ptr(z_lengths), _hip.ptr(u_types),

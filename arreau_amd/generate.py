@@ -19,6 +19,9 @@ step, with the step-size rule's `--corrector_snr` (default 0.16; DiffusionLoss.s
 
 RePaint resampling: `--resample_passes R --jump_length J` runs the denoising steps in blocks of J, each R times, jumping the
 state back to the block's top before every pass after the first (DiffusionLoss.sample).
+
+Lattice systems: `--lattice_system NAME` (cubic, tetragonal, orthorhombic, hexagonal, rhombohedral, monoclinic, triclinic) gives
+every crystal that system's angles and tied lengths (DiffusionLoss.sample).
 """
 import argparse
 import os
@@ -183,7 +186,14 @@ def build_parser() -> argparse.ArgumentParser:
                     help="RePaint resampling: passes per block of denoising steps (1..64; 1 = no resampling)")
     ap.add_argument("--jump_length", type=_jump_length_arg, default=10,
                     help="RePaint resampling: denoising steps per block (>= 1)")
+    ap.add_argument("--lattice_system", type=str, default=None, choices=_lattice_system_choices(),
+                    help="sample crystals of this lattice system: its angles, tied lengths (default: the reference's angles)")
     return ap
+
+
+def _lattice_system_choices():
+    from .diffusion.lattice_systems import SYSTEMS
+    return SYSTEMS
 
 
 def main():
@@ -223,14 +233,16 @@ def main():
         if not lock_path:
             return model.sample(n, b, VisualizationSetting.NONE, False, condition=cond, num_steps=args.num_steps,
                                 corrector_steps=args.corrector_steps, corrector_snr=args.corrector_snr,
-                                resample_passes=args.resample_passes, jump_length=args.jump_length)
+                                resample_passes=args.resample_passes, jump_length=args.jump_length,
+                                lattice_system=args.lattice_system)
         import fcntl
         with open(lock_path, "a") as lock:
             fcntl.flock(lock, fcntl.LOCK_EX)
             try:
                 out = model.sample(n, b, VisualizationSetting.NONE, False, condition=cond, num_steps=args.num_steps,
                                 corrector_steps=args.corrector_steps, corrector_snr=args.corrector_snr,
-                                resample_passes=args.resample_passes, jump_length=args.jump_length)
+                                resample_passes=args.resample_passes, jump_length=args.jump_length,
+                                lattice_system=args.lattice_system)
                 torch.cuda.synchronize()
                 return out
             finally:

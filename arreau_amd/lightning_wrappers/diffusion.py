@@ -327,7 +327,8 @@ class PONITA_DIFFUSION(nn.Module):
                max_steps: Optional[int] = None, use_graph: Optional[bool] = None,
                seed: Optional[int] = None, fixed_cell: bool = False, vis_name: Optional[str] = None,
                condition=None, num_steps: Optional[int] = None, timesteps=None, corrector_steps: int = 0,
-               corrector_snr: float = 0.16, resample_passes: int = 1, jump_length: int = 10) -> SampleResult:
+               corrector_snr: float = 0.16, resample_passes: int = 1, jump_length: int = 10,
+               lattice_system=None) -> SampleResult:
         """lightning_wrappers/diffusion.py:220-253.  `num_atoms_per_sample` may also be a sequence with one atom count
         per crystal of the batch (extension; the reference supports a single int).  Frames of a visualization_setting
         other than NONE go to `<DIFFUSION_DIR>/step_<timestep>.cif` like the reference's PNGs (`vis_name` overrides the
@@ -336,7 +337,10 @@ class PONITA_DIFFUSION(nn.Module):
         (extension): respaced sampling on fewer timesteps (DiffusionLoss.sample).  `corrector_steps` / `corrector_snr`
         (extension): predictor-corrector sampling, Langevin moves on the positions before each step (DiffusionLoss.sample).
         `resample_passes` / `jump_length` (extension): RePaint resampling, blocks of steps re-denoised after a forward jump back
-        to their top (DiffusionLoss.sample)."""
+        to their top (DiffusionLoss.sample).  `lattice_system` (extension): crystals of a chosen lattice system -- one name
+        (lattice_systems.SYSTEMS) for the batch or one per crystal: the system's angles, in radians, and tied lengths kept equal at
+        every step (DiffusionLoss.sample).  None is the sampler as it was: monoclinic angles in degrees read as radians, the
+        reference's behaviour, which is not "monoclinic"."""
         from ..diffusion import resampling
         resampling.check_resampling(resample_passes, jump_length)  # (raises before any work)
         if num_steps is not None or timesteps is not None:
@@ -360,4 +364,4 @@ class PONITA_DIFFUSION(nn.Module):
             visualization_setting=visualization_setting, show_bonds=show_bonds, constant_atoms=constant_atoms,
             noise=noise, max_steps=max_steps, use_graph=use_graph, seed=seed, fixed_cell=fixed_cell, condition=condition,
             num_steps=num_steps, timesteps=timesteps, corrector_steps=corrector_steps, corrector_snr=corrector_snr,
-            resample_passes=resample_passes, jump_length=jump_length)
+            resample_passes=resample_passes, jump_length=jump_length, lattice_system=lattice_system)

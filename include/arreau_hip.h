@@ -118,7 +118,8 @@ int arreau_model_config(const arreau_model* model, arreau_config* out_cfg);
  *                value propagates as NaN instead of being clamped silently;
  *   BAD_TIMESTEP a timestep outside [0, T] (predict_scores) / [1, T] (reverse_step) was clamped, or a respaced step's
  *                target s outside its range (arreau_reverse_step_to, arreau_sample_loop_scheduled);
- *   BAD_TYPE     an atom-type index outside [0, S) was clamped.
+ *   BAD_TYPE     an atom-type index outside [0, S) was clamped;
+ *   BAD_TIE      a lattice-system tie code outside 0..2 was treated as 0 (arreau_sample_loop_tied and its step / jump).
  * edge_kernel / mlp_kernel / conv_kernel name the kernel family the last arreau_predict_scores really launched
  * (edge: 0-2 fp32 MFMA, 3 bf16x6, 4 fp16x3; mlp: 0 fp32 MFMA, 1 bf16x6, 2 fp16x3 32x32x16, 3 fp16x3 16x16x32;
  * conv: 0 register form, 1 streamed form, 2 fused into the MLP kernel) -- e.g. 3/1 instead of 4/3 when a weight does not
@@ -128,6 +129,7 @@ int arreau_model_config(const arreau_model* model, arreau_config* out_cfg);
 #define ARREAU_STATUS_NONFINITE 1
 #define ARREAU_STATUS_BAD_TIMESTEP 2
 #define ARREAU_STATUS_BAD_TYPE 4
+#define ARREAU_STATUS_BAD_TIE 8
 typedef struct arreau_status {
     int32_t flags;
     int32_t edge_kernel;
@@ -480,6 +482,51 @@ int arreau_resample_jump(const arreau_model* model, float* d_frac, int32_t* d_ty
                          const float* d_z_frac, const float* d_z_lengths, const float* d_u_types,
                          const int32_t* d_const_types, const float* d_fixed_lengths,
                          const arreau_sample_condition* cond, float* d_lattice, void* stream);
+
+/* ---- lattice systems (tied cell lengths) --------------------------------------------------------------------------
+ * A crystal of a chosen lattice system gets that system's angles from the host (d_angles, radians) and a tie code for its lengths:
+ * 0 none (orthorhombic, monoclinic, triclinic), 1 a = b (tetragonal, hexagonal), 2 a = b = c (cubic, rhombohedral).  gamma is the
+ * angle between a and b in lattice_from_params, so the tied pair is axes 0 and 1.  Angles are never diffused; lengths are, per
+ * axis, so the tie is kept on the device at every step.  Per crystal b with code g, G = the tied set (empty, {0, 1} or {0, 1, 2});
+ * axis 0 is the group's leader.
+ *   1. update: the length update of a step (rule 2 of the respaced section; the stride-1 step as in arreau_reverse_step) is computed
+ *      once for the axes in G with x_t = the leader's current length, x0 = the mean of the group's x0 (x0_i = pred_lengths_0_i *
+ *      num_atoms, summed in axis order and divided by |G|) and z = the leader's draw (Philox kind 0, element 3 b + 0, or
+ *      d_z_lattice[3 b + 0]), and written to every axis of G: tied axes are bitwise equal after every step, whatever the input.
+ *      Axes outside G are updated as without a tie; d_len0 (the pooled network output in the loop) stays per axis.
+ *   2. jump (RePaint resampling): the axes of G jump from the leader's length with the leader's draw (kind 7, element 3 b + 0, or
+ *      d_z_lengths[3 b + 0]).
+ *   3. fixed cell: the fixed lengths are re-imposed as without a tie (the caller ties them).
+ *   4. a crystal whose lengths a condition knows (len_mask[b]) is not tied: the conditioning rule wins.
+ *   5. a code outside 0..2 counts as 0 and sets ARREAU_STATUS_BAD_TIE.
+ *   6. noise keys do not change: a crystal with code 0 draws, and computes, exactly what it does without a tie.
+ * The initial lengths of a run are the caller's; tie them (lengths[b, G] = lengths[b, 0]) before the first call. */
+
+/* arreau_sample_loop_resampled with the tie rules above.  d_length_tie[B] (device, int32) holds the code per crystal; NULL is
+ * arreau_sample_loop_resampled bit for bit.  Both loop forms and the shape-general path apply it; the pointer is part of what a
+ * cached hipGraph was captured for. */
+int arreau_sample_loop_tied(arreau_model* model, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                            const int32_t* d_crystal_offsets, int32_t B, int32_t N, int32_t t_start, int32_t n_steps,
+                            uint64_t seed, const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice,
+                            void* d_workspace, size_t workspace_bytes, int32_t use_graph,
+                            const arreau_sample_condition* cond, const arreau_sample_schedule* schedule,
+                            const arreau_corrector* corrector, const arreau_resampling* resampling, const int32_t* d_length_tie,
+                            void* stream);
+
+/* arreau_reverse_step_to with the tie rules above (the caller's noise; d_length_tie may be NULL = arreau_reverse_step_to). */
+int arreau_reverse_step_tied(const arreau_model* model,
+                             float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                             const int32_t* d_t, const int32_t* d_s, const int32_t* d_crystal_offsets, int32_t B, int32_t N,
+                             const float* d_eps, const float* d_logits, const float* d_len0,
+                             const float* d_z_lattice, const float* d_z_frac, const float* d_u_types,
+                             float* d_lattice, float lattice_clipmax, const int32_t* d_length_tie, void* stream);
+
+/* arreau_resample_jump with the tie rules above (the caller's noise; d_length_tie may be NULL = arreau_resample_jump). */
+int arreau_resample_jump_tied(const arreau_model* model, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                              const int32_t* d_s, const int32_t* d_t, const int32_t* d_crystal_offsets, int32_t B, int32_t N,
+                              const float* d_z_frac, const float* d_z_lengths, const float* d_u_types,
+                              const int32_t* d_const_types, const float* d_fixed_lengths,
+                              const arreau_sample_condition* cond, float* d_lattice, const int32_t* d_length_tie, void* stream);
 
 /* The sampler's in-kernel noise written out: d_out[i] = draw (seed, timestep, kind, element i) -- standard normal for
  * kind 0 (z_lattice), 1 (z_frac), 3 (known positions) and 4 (known lengths), uniform [0,1) for kind 2 (u_types); d_raw[4 i .. 4 i + 3] (may be NULL) = the raw
