@@ -29,9 +29,10 @@ EXPORTS = [
     "arreau_sample_loop_corrected", "arreau_corrector_step", "arreau_philox_fill_word",
     "arreau_sample_loop_resampled", "arreau_resample_jump", "arreau_optimizer_step_ema",
     "arreau_sample_loop_tied", "arreau_reverse_step_tied", "arreau_resample_jump_tied",
+    "arreau_sample_loop_sym", "arreau_reverse_step_sym",
 ]
 
-STATUS_NONFINITE, STATUS_BAD_TIMESTEP, STATUS_BAD_TYPE, STATUS_BAD_TIE = 1, 2, 4, 8
+STATUS_NONFINITE, STATUS_BAD_TIMESTEP, STATUS_BAD_TYPE, STATUS_BAD_TIE, STATUS_BAD_SYMMETRY = 1, 2, 4, 8, 16
 EDGE_KERNELS = {0: "fp32-mfma", 1: "fp32-mfma", 2: "fp32-mfma", 3: "bf16x6", 4: "fp16x3", 5: "general-fp32-gemm"}
 MLP_KERNELS = {0: "fp32-mfma", 1: "bf16x6", 2: "fp16x3-32x32x16", 3: "fp16x3-16x16x32",
                5: "general-fp32-gemm"}
@@ -70,6 +71,13 @@ class CorrectorC(Structure):
 class ResamplingC(Structure):
     """arreau_resampling: R passes per block of J steps, and the host copy of the schedule (block tops and bottoms)."""
     _fields_ = [("passes", c_int32), ("jump_length", c_int32), ("timesteps", POINTER(c_int32)), ("n_timesteps", c_int32)]
+
+
+class SymmetryC(Structure):
+    """arreau_symmetry: the orbit tables of space-group symmetry (device pointers) and their sizes."""
+    _fields_ = [(name, c_void_p) for name in ("leader", "op", "orbit", "orbit_ptr", "orbit_atoms", "stab_ptr", "stab_ops", "rot",
+                                                "rot_inv", "trans")] + [(name, c_int32) for name in ("n_orbits", "n_orbit_atoms",
+                                                                                                     "n_stab_ops", "n_ops")]
 
 
 class Config(Structure):
@@ -161,6 +169,9 @@ def lib():
         L.arreau_sample_loop_tied.argtypes = L.arreau_sample_loop_resampled.argtypes[:-1] + [c_void_p, c_void_p]
         L.arreau_reverse_step_tied.argtypes = L.arreau_reverse_step_to.argtypes[:-1] + [c_void_p, c_void_p]
         L.arreau_resample_jump_tied.argtypes = L.arreau_resample_jump.argtypes[:-1] + [c_void_p, c_void_p]
+    if hasattr(L, "arreau_sample_loop_sym") or not os.environ.get("ARREAU_HIP_LIB"):  # (an older build under test)
+        L.arreau_sample_loop_sym.argtypes = L.arreau_sample_loop_tied.argtypes[:-1] + [POINTER(SymmetryC), c_void_p]
+        L.arreau_reverse_step_sym.argtypes = L.arreau_reverse_step_tied.argtypes[:-1] + [POINTER(SymmetryC), c_void_p]
     L.arreau_philox_fill.argtypes = [ctypes.c_uint64, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_void_p]
     L.arreau_train_forward.argtypes = [c_void_p] * 7 + [c_int32, c_int32] + [c_void_p] * 4
     L.arreau_train_backward.argtypes = [c_void_p] * 4 + [POINTER(StateDict), c_void_p]

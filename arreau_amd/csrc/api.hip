@@ -312,7 +312,8 @@ int enqueue_sample_step(const arreau_model* m, float* d_frac, int32_t* d_types, 
                         const float* d_fixed_lengths, float* d_lattice, const Workspace& w, hipStream_t s, bool no_prep,
                         const SampleConditionDev* cond, const StepScheduleDev* sched, CorrectorDev corr,
                         const int32_t* pass /* resampled loop: the device word of the pass index (RESAMPLE instances), or null */,
-                        const int32_t* length_tie /* lattice systems: the tie codes (TIE instances), or null */) {
+                        const int32_t* length_tie /* lattice systems: the tie codes (TIE instances), or null */,
+                        const arreau_symmetry* sym /* space-group symmetry: the orbit tables (SYM instances), or null */) {
     int rc;
     const int32_t* next_t = sched ? sched->next : nullptr;  // respaced loop: the device timestep follows the table
     if (no_prep) {
@@ -328,7 +329,7 @@ int enqueue_sample_step(const arreau_model* m, float* d_frac, int32_t* d_types, 
         }
         return arreau_launch_reverse(m, d_frac, d_types, d_lengths, d_angles, w.t_cur, d_off, B, N, w.eps, w.logits, w.len0,
                                      StepNoiseSrc{nullptr, nullptr, nullptr, seed}, d_const_types, d_lattice, s, d_fixed_lengths,
-                                     w.gs, w.batch, w.lattice, w.cvec, cond, sched, pass, length_tie);
+                                     w.gs, w.batch, w.lattice, w.cvec, cond, sched, pass, length_tie, sym);
     }
     // fused kernels: the per-crystal pooling of the lattice read-out happens inside the lattice update (no launch of its own)
     const bool pool_in_update = !arreau_general_path(m);
@@ -347,7 +348,7 @@ int enqueue_sample_step(const arreau_model* m, float* d_frac, int32_t* d_types, 
     }
     return arreau_launch_reverse(m, d_frac, d_types, d_lengths, d_angles, w.t_cur, d_off, B, N, w.eps, w.logits, w.len0,
                                  StepNoiseSrc{nullptr, nullptr, nullptr, seed}, d_const_types, d_lattice, s, d_fixed_lengths,
-                                 pool_in_update ? w.gs : nullptr, w.batch, nullptr, nullptr, cond, sched, pass, length_tie);
+                                 pool_in_update ? w.gs : nullptr, w.batch, nullptr, nullptr, cond, sched, pass, length_tie, sym);
 }
 
 // RePaint resampling (arreau_sample_loop_resampled): the blocks of one loop call, from the host's list of the steps it visits.
@@ -394,13 +395,14 @@ namespace {
 // The key of a captured step: besides the buffers, sizes and seed, which kernels it holds depends on switches read per call
 // (ARREAU_BASIS_MIN_RECEIVERS, ARREAU_FUSE_SMALL) and on the variants, and the condition's pointers, the schedule's table and
 // clip, the corrector's step count and snr, the resampling's R and J (a resampled step reads the pass word) and the lattice
-// systems' tie array are kernel arguments or launch choices of the capture: a change of any of them must not replay the stale graph.
+// systems' tie array and the symmetry tables are kernel arguments or launch choices of the capture: a change of any of them must
+// not replay the stale graph.
 SampleGraphKey sample_graph_key(const arreau_model* m, const float* d_frac, const int32_t* d_types, const float* d_lengths,
                                 const float* d_angles, const int32_t* d_off, int32_t B, int32_t N, uint64_t seed,
                                 const int32_t* d_const_types, const float* d_fixed_lengths, const float* d_lattice,
                                 const void* d_workspace, bool no_prep, const SampleConditionDev& cond, bool scheduled,
                                 const StepScheduleDev& sched, const CorrectorDev& corr, const ResamplePlan* plan,
-                                const int32_t* d_length_tie) {
+                                const int32_t* d_length_tie, const arreau_symmetry* sym) {
     SampleGraphKey k{};
     k.frac = (uint64_t)d_frac; k.types = (uint64_t)d_types; k.lengths = (uint64_t)d_lengths; k.angles = (uint64_t)d_angles;
     k.offsets = (uint64_t)d_off; k.const_types = (uint64_t)d_const_types; k.fixed_lengths = (uint64_t)d_fixed_lengths;
@@ -409,6 +411,13 @@ SampleGraphKey sample_graph_key(const arreau_model* m, const float* d_frac, cons
     k.cond_type_mask = (uint64_t)cond.type_mask; k.cond_l0 = (uint64_t)cond.l0; k.cond_len_mask = (uint64_t)cond.len_mask;
     k.sched_next = (uint64_t)sched.next;
     k.length_tie = (uint64_t)d_length_tie;
+    if (sym) {
+        k.sym_leader = (uint64_t)sym->leader; k.sym_op = (uint64_t)sym->op; k.sym_orbit = (uint64_t)sym->orbit;
+        k.sym_orbit_ptr = (uint64_t)sym->orbit_ptr; k.sym_orbit_atoms = (uint64_t)sym->orbit_atoms; k.sym_stab_ptr = (uint64_t)sym->stab_ptr;
+        k.sym_stab_ops = (uint64_t)sym->stab_ops; k.sym_rot = (uint64_t)sym->rot; k.sym_rot_inv = (uint64_t)sym->rot_inv;
+        k.sym_trans = (uint64_t)sym->trans;
+        k.sym_n_orbits = sym->n_orbits; k.sym_n_orbit_atoms = sym->n_orbit_atoms; k.sym_n_stab_ops = sym->n_stab_ops; k.sym_n_ops = sym->n_ops;
+    }
     k.B = B; k.N = N;
     k.edge_variant = m->edge_variant; k.mlp_variant = m->mlp_variant; k.conv_variant = m->conv_variant; k.no_prep = no_prep;
     k.basis_form = arreau_basis_form(m, N); k.basis_fp8 = arreau_basis_fp8(m); k.cross_fp8 = arreau_cross_fp8(m);
@@ -429,7 +438,7 @@ int sample_loop_impl(arreau_model* m, float* d_frac, int32_t* d_types, float* d_
                      const float* d_fixed_lengths, float* d_lattice, void* d_workspace, size_t workspace_bytes, int32_t use_graph,
                      const arreau_sample_condition* condition, const arreau_sample_schedule* schedule, const arreau_corrector* corrector,
                      const ResamplePlan* plan /* null: no resampling */, const int32_t* d_length_tie /* null: untied */,
-                     void* stream) {
+                     const arreau_symmetry* sym /* null: no symmetry */, void* stream) {
     if (corrector) {
         const int rc = arreau_corrector_check(corrector->steps, corrector->snr, "arreau_sample_loop_corrected");
         if (rc) return rc;
@@ -463,6 +472,8 @@ int sample_loop_impl(arreau_model* m, float* d_frac, int32_t* d_types, float* d_
     const StepScheduleDev* sched = schedule ? &sched_dev : nullptr;  // null: every timestep, t_start down
     if (n_steps == 0) return ARREAU_OK;
     hipStream_t s = (hipStream_t)stream;
+    ARREAU_REQUIRE(!sym || (cond == nullptr && corr.steps == 0 && plan == nullptr),
+                   "arreau_sample_loop_sym: space-group symmetry is not combined with a condition, corrector steps or resampling");
     const bool no_prep = loop_without_prep(m);
     if (no_prep) {
         // t_cur holds the timestep of the step in progress; every step's first launch advances it, so it starts one above (in a
@@ -510,7 +521,7 @@ int sample_loop_impl(arreau_model* m, float* d_frac, int32_t* d_types, float* d_
         // (a sampler drawing sub-batch after sub-batch through the caching allocator does): capture + instantiation, about
         // 2 ms, are then paid once.  The timestep is not part of the graph (it lives in t_next / t_cur, set above).
         key = sample_graph_key(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types, d_fixed_lengths, d_lattice,
-                               d_workspace, no_prep, cond_dev, schedule != nullptr, sched_dev, corr, plan, d_length_tie);
+                               d_workspace, no_prep, cond_dev, schedule != nullptr, sched_dev, corr, plan, d_length_tie, sym);
         exec = (hipGraphExec_t)m->retired_graph;
         have_exec = exec && memcmp(&key, &m->graph_key, sizeof(key)) == 0;
     }
@@ -521,13 +532,13 @@ int sample_loop_impl(arreau_model* m, float* d_frac, int32_t* d_types, float* d_
         if (!graph_mode || !have_exec) {
             // (eager: the first step of a capture also forces lazy module loading, which must not happen inside a capture)
             if ((r = enqueue_sample_step(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types, d_fixed_lengths,
-                                         d_lattice, w, s, no_prep, cond, sched, corr, pass, d_length_tie)))
+                                         d_lattice, w, s, no_prep, cond, sched, corr, pass, d_length_tie, sym)))
                 return r;
             if (!graph_mode) return ARREAU_OK;
             hipGraph_t graph = nullptr;
             ARREAU_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
             r = enqueue_sample_step(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types, d_fixed_lengths, d_lattice,
-                                    w, s, no_prep, cond, sched, corr, pass, d_length_tie);
+                                    w, s, no_prep, cond, sched, corr, pass, d_length_tie, sym);
             hipError_t e = hipStreamEndCapture(s, &graph);
             if (r) {
                 if (graph) (void)hipGraphDestroy(graph);
@@ -583,7 +594,8 @@ extern "C" int arreau_sample_loop_corrected(arreau_model* m, float* d_frac, int3
                                             int32_t use_graph, const arreau_sample_condition* condition,
                                             const arreau_sample_schedule* schedule, const arreau_corrector* corrector, void* stream) {
     return sample_loop_impl(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, t_start, n_steps, seed, d_const_types, d_fixed_lengths,
-                            d_lattice, d_workspace, workspace_bytes, use_graph, condition, schedule, corrector, nullptr, nullptr, stream);
+                            d_lattice, d_workspace, workspace_bytes, use_graph, condition, schedule, corrector, nullptr, nullptr, nullptr,
+                            stream);
 }
 
 namespace {
@@ -592,7 +604,7 @@ int sample_loop_resampled(arreau_model* m, float* d_frac, int32_t* d_types, floa
                           const float* d_fixed_lengths, float* d_lattice, void* d_workspace, size_t workspace_bytes, int32_t use_graph,
                           const arreau_sample_condition* condition, const arreau_sample_schedule* schedule,
                           const arreau_corrector* corrector, const arreau_resampling* resampling, const int32_t* d_length_tie,
-                          const char* who, void* stream) {
+                          const char* who, void* stream, const arreau_symmetry* sym = nullptr) {
     ResamplePlan plan{1, 1, {}};
     if (resampling) {
         int rc;
@@ -627,7 +639,7 @@ int sample_loop_resampled(arreau_model* m, float* d_frac, int32_t* d_types, floa
     }
     return sample_loop_impl(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, t_start, n_steps, seed, d_const_types, d_fixed_lengths,
                             d_lattice, d_workspace, workspace_bytes, use_graph, condition, schedule, corrector,
-                            plan.passes > 1 ? &plan : nullptr, d_length_tie, stream);
+                            plan.passes > 1 ? &plan : nullptr, d_length_tie, sym, stream);
 }
 }  // namespace
 
@@ -653,6 +665,25 @@ extern "C" int arreau_sample_loop_tied(arreau_model* m, float* d_frac, int32_t* 
     return sample_loop_resampled(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, t_start, n_steps, seed, d_const_types,
                                  d_fixed_lengths, d_lattice, d_workspace, workspace_bytes, use_graph, condition, schedule, corrector,
                                  resampling, d_length_tie, "arreau_sample_loop_tied", stream);
+}
+
+// arreau_sample_loop_tied with space-group symmetry (rules in include/arreau_hip.h); NULL = that loop.
+extern "C" int arreau_sample_loop_sym(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                                      const int32_t* d_off, int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed,
+                                      const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice, void* d_workspace,
+                                      size_t workspace_bytes, int32_t use_graph, const arreau_sample_condition* condition,
+                                      const arreau_sample_schedule* schedule, const arreau_corrector* corrector,
+                                      const arreau_resampling* resampling, const int32_t* d_length_tie, const arreau_symmetry* symmetry,
+                                      void* stream) {
+    if (symmetry) {
+        int rc;
+        if ((rc = arreau_symmetry_check(symmetry, "arreau_sample_loop_sym"))) return rc;
+        ARREAU_REQUIRE(!resampling || resampling->passes <= 1,
+                       "arreau_sample_loop_sym: space-group symmetry is not combined with resampling (passes > 1)");
+    }
+    return sample_loop_resampled(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, t_start, n_steps, seed, d_const_types,
+                                 d_fixed_lengths, d_lattice, d_workspace, workspace_bytes, use_graph, condition, schedule, corrector,
+                                 resampling, d_length_tie, "arreau_sample_loop_sym", stream, symmetry);
 }
 
 // ---------------------------------------------------------------------------------------------

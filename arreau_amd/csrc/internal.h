@@ -47,6 +47,8 @@ struct SampleGraphKey {
     uint64_t cond_x0, cond_pos_mask, cond_a0, cond_type_mask, cond_l0, cond_len_mask;
     uint64_t sched_next;  // respaced sampling: the next-timestep table
     uint64_t length_tie;  // lattice systems: the per-crystal tie codes (null: untied)
+    // space-group symmetry: the ten table pointers (null: no symmetry)
+    uint64_t sym_leader, sym_op, sym_orbit, sym_orbit_ptr, sym_orbit_atoms, sym_stab_ptr, sym_stab_ops, sym_rot, sym_rot_inv, sym_trans;
     int32_t B, N;
     // kernel choices: the variants, and the switches read per call (ARREAU_BASIS_MIN_RECEIVERS, ARREAU_FUSE_SMALL)
     int32_t edge_variant, mlp_variant, conv_variant, no_prep, basis_form, basis_fp8, cross_fp8, small_layer_fusion;
@@ -55,8 +57,9 @@ struct SampleGraphKey {
     int32_t corrector_steps;
     uint32_t snr_bits;         // the corrector's snr
     int32_t resample_passes, resample_jump;  // 0, 0: no resampling
+    int32_t sym_n_orbits, sym_n_orbit_atoms, sym_n_stab_ops, sym_n_ops;  // the symmetry tables' sizes
 };
-static_assert(sizeof(SampleGraphKey) == 18 * 8 + 16 * 4, "SampleGraphKey must have no padding (it is compared with memcmp)");
+static_assert(sizeof(SampleGraphKey) == 28 * 8 + 20 * 4, "SampleGraphKey must have no padding (it is compared with memcmp)");
 
 struct arreau_model {
     arreau_config cfg;
@@ -245,6 +248,9 @@ inline bool arreau_condition_empty(const SampleConditionDev* c) {
     return !c || !((c->x0 && c->pos_mask) || (c->a0 && c->type_mask) || (c->l0 && c->len_mask));
 }
 int arreau_condition_to_dev(const arreau_sample_condition* c, SampleConditionDev* out);  // update.hip
+// Space-group symmetry (arreau_sample_loop_sym, arreau_reverse_step_sym): ARREAU_EINVAL unless every table pointer is given and
+// every size is positive.  The kernels take the table struct by value and check every index before they follow it.
+int arreau_symmetry_check(const arreau_symmetry* y, const char* who);  // update.hip
 
 // Respaced sampling (arreau_sample_loop_scheduled, arreau_reverse_step_to; the rules are stated in include/arreau_hip.h): the step
 // that leaves timestep t of crystal b produces the state at s = s_of[b] when s_of is given, else s = next[t] (the device-side
@@ -358,7 +364,9 @@ int arreau_launch_reverse(const arreau_model* m, float* d_frac, int32_t* d_types
                           const SampleConditionDev* cond = nullptr /* conditioned sampling; needs Philox noise (noise.seed) */,
                           const StepScheduleDev* sched = nullptr /* respaced step (s from a table or per crystal), null: s = t - 1 */,
                           const int32_t* d_pass = nullptr /* resampled loop: word3 = 256 pass[0] (the RESAMPLE instance) */,
-                          const int32_t* d_length_tie = nullptr /* lattice systems: the tie code per crystal (the TIE instance) */);
+                          const int32_t* d_length_tie = nullptr /* lattice systems: the tie code per crystal (the TIE instance) */,
+                          const arreau_symmetry* sym = nullptr /* space-group symmetry: the orbit tables (the SYM instance); not
+                          with a condition or a resampled loop */);
 int arreau_launch_edge(const arreau_model* m, const float* dir, const float* dist, const int32_t* deg,
                        const int32_t* batch, const float* lattice, int N, float* kbuf, hipStream_t s);
 int arreau_launch_edge_bf16x6(const arreau_model* m, const float* dir, const float* dist, const int32_t* deg,

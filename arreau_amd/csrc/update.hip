@@ -76,7 +76,9 @@ __device__ __forceinline__ void reverse_lattice_body(int gt /* global thread of 
 // the step takes counter word3 = 256 r; pass 0 draws what the plain kernel draws.  Without RESAMPLE `pass` is not read.
 // TIE: lattice systems (arreau_sample_loop_tied): the lengths of crystal b are tied by the code length_tie[b] (0 none, 1 a = b,
 // 2 a = b = c; rules in include/arreau_hip.h).  Without TIE `length_tie` is not read.
-template <bool COND, bool SCHED, bool RESAMPLE, bool TIE>
+// SYM: space-group symmetry (arreau_sample_loop_sym): the atom part runs reverse_atoms_body_sym on the orbit tables `sym_arg`
+// (a leader's wave updates its whole orbit, members leave).  Only without COND and RESAMPLE.  Without SYM `sym_arg` is not read.
+template <bool COND, bool SCHED, bool RESAMPLE, bool TIE, bool SYM>
 __global__ __launch_bounds__(256) void reverse_kernel(
     int lat_blocks, float* __restrict__ lengths, const float* __restrict__ angles, const int32_t* __restrict__ tstep,
     const int32_t* __restrict__ offsets, const float* __restrict__ len0, StepNoiseSrc noise, const float* __restrict__ alpha_bars,
@@ -88,7 +90,8 @@ __global__ __launch_bounds__(256) void reverse_kernel(
     const int32_t* __restrict__ batch,
     // sampling loop: the lattice part is one workgroup per crystal, which also prepares the next step (reverse_crystal_block)
     float* __restrict__ lattice_ws, float* __restrict__ cvec_next, const float* __restrict__ t_emb_w, const float* __restrict__ embT, int C,
-    SampleConditionDev cond_arg, StepScheduleDev sched_arg, const int32_t* __restrict__ pass, const int32_t* __restrict__ length_tie) {
+    SampleConditionDev cond_arg, StepScheduleDev sched_arg, const int32_t* __restrict__ pass, const int32_t* __restrict__ length_tie,
+    arreau_symmetry sym_arg) {
     const uint32_t word3 = RESAMPLE ? 256u * (uint32_t)pass[0] : 0u;  // the counter word of pass r
     const SampleConditionDev* cond = COND ? &cond_arg : nullptr;
     const StepScheduleDev* sched = SCHED ? &sched_arg : nullptr;
@@ -103,8 +106,14 @@ __global__ __launch_bounds__(256) void reverse_kernel(
                                   T, lattice, fixed_lengths, status, b0, gs_atoms, len0_out, cond, sched, word3, length_tie);
         return;
     }
-    reverse_atoms_body((int)blockIdx.x - lat_blocks, frac, types, tstep, offsets, B, N, eps, logits, noise, ve_sigmas, q1t, qmats, S, T,
-                       const_types, absorbing, status, n0, batch, cond, sched, word3);
+    if constexpr (SYM) {
+        static_assert(!COND && !RESAMPLE, "the SYM instances are unconditioned and not resampled");
+        reverse_atoms_body_sym((int)blockIdx.x - lat_blocks, frac, types, tstep, offsets, B, N, eps, logits, noise, ve_sigmas, q1t, qmats, S,
+                               T, const_types, absorbing, status, n0, batch, sched, sym_arg);
+    } else {
+        reverse_atoms_body((int)blockIdx.x - lat_blocks, frac, types, tstep, offsets, B, N, eps, logits, noise, ve_sigmas, q1t, qmats, S, T,
+                           const_types, absorbing, status, n0, batch, cond, sched, word3);
+    }
 }
 
 namespace {
@@ -114,14 +123,17 @@ void enqueue_reverse_kernel(const arreau_model* m, int lat_blocks, int atom_bloc
                             const float* d_logits, const float* d_len0, StepNoiseSrc noise, const int32_t* d_const_types,
                             float* d_lattice, hipStream_t s, const float* d_fixed_lengths, const float* d_gs_atoms,
                             const int32_t* d_batch, float* d_lattice_ws, float* d_cvec_next, const SampleConditionDev& cond,
-                            const StepScheduleDev& sched, const int32_t* d_pass, const int32_t* d_length_tie) {
-    auto kernel = d_length_tie ? (d_pass ? reverse_kernel<COND, SCHED, true, true> : reverse_kernel<COND, SCHED, false, true>)
-                               : (d_pass ? reverse_kernel<COND, SCHED, true, false> : reverse_kernel<COND, SCHED, false, false>);
+                            const StepScheduleDev& sched, const int32_t* d_pass, const int32_t* d_length_tie, const arreau_symmetry* sym) {
+    auto kernel = d_length_tie ? (d_pass ? reverse_kernel<COND, SCHED, true, true, false> : reverse_kernel<COND, SCHED, false, true, false>)
+                               : (d_pass ? reverse_kernel<COND, SCHED, true, false, false> : reverse_kernel<COND, SCHED, false, false, false>);
+    if constexpr (!COND) {
+        if (sym) kernel = d_length_tie ? reverse_kernel<false, SCHED, false, true, true> : reverse_kernel<false, SCHED, false, false, true>;
+    }
     ARREAU_LAUNCH(kernel, dim3(lat_blocks + atom_blocks), dim3(256), 0, s, lat_blocks, d_lengths, d_angles, d_t, d_off, d_len0, noise,
                   m->vp_alpha_bars, m->vp_betas, B, m->T, d_lattice, d_fixed_lengths, m->status, 0, d_gs_atoms,
                   d_gs_atoms ? const_cast<float*>(d_len0) : nullptr, d_frac, d_types, B, N, d_eps, d_logits, m->ve_sigmas, m->q1t,
                   m->qmats, m->S, d_const_types, m->qmats_absorbing, 0, d_batch, d_lattice_ws, d_cvec_next, m->t_emb_w, m->embT, m->C,
-                  cond, sched, d_pass, d_length_tie);
+                  cond, sched, d_pass, d_length_tie, sym ? *sym : arreau_symmetry{});
 }
 }  // namespace
 
@@ -130,7 +142,7 @@ int arreau_launch_reverse(const arreau_model* m, float* d_frac, int32_t* d_types
                           const float* d_logits, const float* d_len0, StepNoiseSrc noise, const int32_t* d_const_types,
                           float* d_lattice, hipStream_t s, const float* d_fixed_lengths, const float* d_gs_atoms,
                           const int32_t* d_batch, float* d_lattice_ws, float* d_cvec_next, const SampleConditionDev* cond,
-                          const StepScheduleDev* sched, const int32_t* d_pass, const int32_t* d_length_tie) {
+                          const StepScheduleDev* sched, const int32_t* d_pass, const int32_t* d_length_tie, const arreau_symmetry* sym) {
     const bool prep_next = d_cvec_next != nullptr;  // one workgroup per crystal, which also prepares the next step
     ARREAU_REQUIRE(!prep_next || d_lattice_ws != nullptr, "reverse update: the next step's set-up needs the workspace lattice");
     const int lat_blocks = B > 0 ? (prep_next ? B : (4 * B + 255) / 256) : 0;
@@ -141,11 +153,14 @@ int arreau_launch_reverse(const arreau_model* m, float* d_frac, int32_t* d_types
     const bool scheduled = sched != nullptr;
     ARREAU_REQUIRE(!scheduled || (sched->next != nullptr) != (sched->s_of != nullptr),
                    "reverse update: a respaced step takes either the next-timestep table or the per-crystal targets");
+    ARREAU_REQUIRE(!sym || (!conditioned && d_pass == nullptr),
+                   "reverse update: space-group symmetry is not combined with a condition or a resampled loop");
     if (lat_blocks + atom_blocks == 0) return ARREAU_OK;
     const SampleConditionDev c = conditioned ? *cond : SampleConditionDev{};
     const StepScheduleDev sc = scheduled ? *sched : StepScheduleDev{};
 #define ARREAU_REVERSE_ARGS m, lat_blocks, atom_blocks, d_frac, d_types, d_lengths, d_angles, d_t, d_off, B, N, d_eps, d_logits, d_len0, \
-        noise, d_const_types, d_lattice, s, d_fixed_lengths, d_gs_atoms, d_batch, d_lattice_ws, d_cvec_next, c, sc, d_pass, d_length_tie
+        noise, d_const_types, d_lattice, s, d_fixed_lengths, d_gs_atoms, d_batch, d_lattice_ws, d_cvec_next, c, sc, d_pass, d_length_tie, \
+        sym
     if (conditioned && scheduled) enqueue_reverse_kernel<true, true>(ARREAU_REVERSE_ARGS);
     else if (conditioned) enqueue_reverse_kernel<true, false>(ARREAU_REVERSE_ARGS);
     else if (scheduled) enqueue_reverse_kernel<false, true>(ARREAU_REVERSE_ARGS);
@@ -172,7 +187,7 @@ static int reverse_step_to(const arreau_model* m, float* d_frac, int32_t* d_type
                            const int32_t* d_t, const int32_t* d_s, const int32_t* d_off, int32_t B, int32_t N, const float* d_eps,
                            const float* d_logits, const float* d_len0, const float* d_z_lattice, const float* d_z_frac,
                            const float* d_u_types, float* d_lattice, float lattice_clipmax, const int32_t* d_length_tie, void* stream,
-                           const char* who) {
+                           const char* who, const arreau_symmetry* sym = nullptr) {
     ARREAU_REQUIRE(m && d_frac && d_types && d_lengths && d_angles && d_t && d_s && d_off && d_eps && d_logits && d_len0 &&
                        d_z_lattice && d_z_frac && d_u_types && d_lattice, std::string(who) + ": null pointer");
     ARREAU_REQUIRE(B >= 1 && N >= 0, std::string(who) + ": bad size");
@@ -180,7 +195,7 @@ static int reverse_step_to(const arreau_model* m, float* d_frac, int32_t* d_type
     const StepScheduleDev sched{nullptr, d_s, lattice_clipmax};
     return arreau_launch_reverse(m, d_frac, d_types, d_lengths, d_angles, d_t, d_off, B, N, d_eps, d_logits, d_len0,
                                  StepNoiseSrc{d_z_lattice, d_z_frac, d_u_types, 0}, nullptr, d_lattice, (hipStream_t)stream, nullptr,
-                                 nullptr, nullptr, nullptr, nullptr, nullptr, &sched, nullptr, d_length_tie);
+                                 nullptr, nullptr, nullptr, nullptr, nullptr, &sched, nullptr, d_length_tie, sym);
 }
 
 extern "C" int arreau_reverse_step_to(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths,
@@ -200,6 +215,27 @@ extern "C" int arreau_reverse_step_tied(const arreau_model* m, float* d_frac, in
                                         float lattice_clipmax, const int32_t* d_length_tie, void* stream) {
     return reverse_step_to(m, d_frac, d_types, d_lengths, d_angles, d_t, d_s, d_off, B, N, d_eps, d_logits, d_len0, d_z_lattice, d_z_frac,
                            d_u_types, d_lattice, lattice_clipmax, d_length_tie, stream, "arreau_reverse_step_tied");
+}
+
+// arreau_reverse_step_tied with space-group symmetry (rules in include/arreau_hip.h); NULL = arreau_reverse_step_tied.
+extern "C" int arreau_reverse_step_sym(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths,
+                                       const float* d_angles, const int32_t* d_t, const int32_t* d_s, const int32_t* d_off, int32_t B,
+                                       int32_t N, const float* d_eps, const float* d_logits, const float* d_len0,
+                                       const float* d_z_lattice, const float* d_z_frac, const float* d_u_types, float* d_lattice,
+                                       float lattice_clipmax, const int32_t* d_length_tie, const arreau_symmetry* symmetry, void* stream) {
+    int rc;
+    if (symmetry && (rc = arreau_symmetry_check(symmetry, "arreau_reverse_step_sym"))) return rc;
+    return reverse_step_to(m, d_frac, d_types, d_lengths, d_angles, d_t, d_s, d_off, B, N, d_eps, d_logits, d_len0, d_z_lattice, d_z_frac,
+                           d_u_types, d_lattice, lattice_clipmax, d_length_tie, stream, "arreau_reverse_step_sym", symmetry);
+}
+
+// the host checks of a symmetry table set: every pointer given, sizes positive (the kernel checks every index it follows)
+int arreau_symmetry_check(const arreau_symmetry* y, const char* who) {
+    ARREAU_REQUIRE(y->leader && y->op && y->orbit && y->orbit_ptr && y->orbit_atoms && y->stab_ptr && y->stab_ops && y->rot && y->rot_inv &&
+                       y->trans, std::string(who) + ": a symmetry table is null");
+    ARREAU_REQUIRE(y->n_orbits >= 1 && y->n_orbit_atoms >= 1 && y->n_stab_ops >= 1 && y->n_ops >= 1,
+                   std::string(who) + ": symmetry table sizes must be positive");
+    return ARREAU_OK;
 }
 
 // The sampler's in-kernel noise, written out: out[i] = the draw (seed, timestep, kind, element i, word3) -- standard normal for

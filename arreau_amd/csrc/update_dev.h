@@ -323,6 +323,123 @@ __device__ __forceinline__ void reverse_one_atom(
     if (lane == 0) types[i] = (cond && cond->type_mask && cond->type_mask[i]) ? cond->a0[i] : (const_types ? const_types[i] : besti);
 }
 
+// Space-group symmetry: D3PM.reverse on the class of atom i (d3pm.py:74-110, 198-215) from given x0 logits l0 / l1 of classes
+// lane / lane + 64 (-inf beyond S), from timestep t to s_to: the new class (wave-uniform), drawn with atom i's uniforms (elements
+// i S + s).  The arithmetic of reverse_one_atom's species half, operation for operation; it is kept apart so that the existing
+// kernel instances keep their instructions.
+__device__ __forceinline__ int d3pm_reverse_class(int i, int lane, float l0, float l1, int t, int s_to, const int32_t* __restrict__ types,
+                                                  StepNoiseSrc noise, const float* __restrict__ q1t, const float* __restrict__ qmats, int S,
+                                                  int absorbing, int32_t* __restrict__ status, const StepScheduleDev* sched, uint32_t word3) {
+    const float* __restrict__ u_types = noise.u_types;
+    // ---- D3PM posterior logits ------------------------------------------------------------------
+    const int s0 = lane, s1 = lane + 64;
+    const bool v0 = s0 < S, v1 = s1 < S;
+    float post0, post1;
+    if (t == 1) {
+        post0 = l0; post1 = l1;  // raw x0 logits at the last step (d3pm.py:106-108)
+    } else {
+        float mx = fmaxf(l0, l1);
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+        const float e0 = v0 ? expf(l0 - mx) : 0.f, e1 = v1 ? expf(l1 - mx) : 0.f;
+        float sum = e0 + e1;
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off, 64);
+        const float p0 = e0 / sum, p1 = e1 / sum;  // softmax of the x0 logits; lane holds classes s0, s1
+        int xt = types[i];
+        if ((xt < 0 || xt >= S) && lane == 0) atomicOr(status, ARREAU_STATUS_BAD_TYPE);  // clamped, but flagged
+        xt = xt < 0 ? 0 : (xt >= S ? S - 1 : xt);
+        const bool unit = sched == nullptr || s_to == t - 1;
+        const float* q1row = q1t + ((size_t)(t - 1) * S + xt) * S;  // fact1 = Q_t^T[x_t, :] (stride 1)
+        const float* qm = qmats + (size_t)(s_to - 1) * S * S;  // Qbar_s (reference index t-2 at stride 1)
+        float f2a = 0.f, f2b = 0.f;
+        if (absorbing) {
+            // Absorbing ("mask") chain: Qbar_t is diagonal plus the mask column (checked on the host for every t at model
+            // creation).  The dense loop below adds exact zeros everywhere else, so these are bit for bit its sums: for an
+            // ordinary class s only the term c = s, for the mask class the whole column in class order -- without the
+            // S x S read per atom.
+            const int mask = S - 1;
+            const float d0 = v0 ? qm[(size_t)s0 * S + s0] : 0.f, d1 = v1 ? qm[(size_t)s1 * S + s1] : 0.f;
+            const float c0 = v0 ? qm[(size_t)s0 * S + mask] : 0.f, c1 = v1 ? qm[(size_t)s1 * S + mask] : 0.f;
+            f2a = fmaf(p0, d0, 0.f);
+            f2b = fmaf(p1, d1, 0.f);
+            float fm = 0.f;
+            // (c is wave-uniform: the broadcasts are v_readlane, not LDS-crossbar permutes -- round 3: the 2 S permutes per atom
+            // were most of this kernel's time)
+            auto lane_value = [](float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); };
+            for (int c = 0; c < S; ++c) {
+                const float pc = c < 64 ? lane_value(p0, c) : lane_value(p1, c - 64);
+                const float qc = c < 64 ? lane_value(c0, c) : lane_value(c1, c - 64);
+                fm = fmaf(pc, qc, fm);
+            }
+            if (s0 == mask) f2a = fm;
+            if (s1 == mask) f2b = fm;
+        } else
+        // fact2 = softmax . Qbar: rows of Qbar are fetched 16 at a time (independent loads in flight), then the
+        // softmax entries are broadcast from the lanes that hold them
+        for (int c0 = 0; c0 < S; c0 += 16) {
+            float qa[16], qb[16];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int c = min(c0 + i, S - 1);
+                qa[i] = v0 ? qm[(size_t)c * S + s0] : 0.f;
+                qb[i] = v1 ? qm[(size_t)c * S + s1] : 0.f;
+            }
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int c = c0 + i;  // wave-uniform
+                float sc = c < 64 ? __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p0), c))
+                                  : __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p1), c - 64));
+                sc = c < S ? sc : 0.f;
+                f2a = fmaf(sc, qa[i], f2a);
+                f2b = fmaf(sc, qb[i], f2b);
+            }
+        }
+        if (unit) {
+            post0 = v0 ? logf(q1row[s0] + D3PM_EPS) + logf(f2a + D3PM_EPS) : -INFINITY;
+            post1 = v1 ? logf(q1row[s1] + D3PM_EPS) + logf(f2b + D3PM_EPS) : -INFINITY;
+        } else {
+            // respaced: fact1 = Qbar_{t-s}[:, x_t], the column x_t of q_mats[t-s-1] (the mask chain is time-homogeneous, so the
+            // (t-s)-step transition is the (t-s)-step product).  Absorbing chain: that column is zero off the diagonal unless
+            // x_t is the mask class -- the entries skipped are exact zeros, as in the shortcut above.
+            const float* qcol = qmats + (size_t)(t - s_to - 1) * S * S + xt;
+            const bool all = !absorbing || xt == S - 1;
+            const float fa = (v0 && (all || s0 == xt)) ? qcol[(size_t)s0 * S] : 0.f;
+            const float fb = (v1 && (all || s1 == xt)) ? qcol[(size_t)s1 * S] : 0.f;
+            post0 = v0 ? logf(fa + D3PM_EPS) + logf(f2a + D3PM_EPS) : -INFINITY;
+            post1 = v1 ? logf(fb + D3PM_EPS) + logf(f2b + D3PM_EPS) : -INFINITY;
+        }
+    }
+    // ---- Gumbel arg-max (d3pm.py:206-214) ----------------------------------------------------------
+    const float scale = (t != 1) ? 1.0f : 0.2f;
+    // (the array-or-generator choice is made on the kernel argument itself -- a scalar compare -- not on a per-lane pointer:
+    // no per-lane 64-bit integer compares on this path)
+    const bool have_u = u_types != nullptr;
+    const float* un = u_types + (have_u ? (size_t)i * S : 0);
+    auto draw_u = [&](int s_) {
+        return have_u ? un[s_] : philox_uniform(noise.seed, (uint32_t)t, ARREAU_DRAW_U_TYPES, (uint32_t)((size_t)i * S + s_), word3);
+    };
+    float best = -INFINITY;
+    int besti = 0x7fffffff;
+    if (v0) {
+        const float u = fminf(fmaxf(draw_u(s0), D3PM_EPS), 1.0f);
+        best = post0 + (-logf(-logf(u))) * scale;
+        besti = s0;
+    }
+    if (v1) {
+        const float u = fminf(fmaxf(draw_u(s1), D3PM_EPS), 1.0f);
+        const float val = post1 + (-logf(-logf(u))) * scale;
+        if (val > best) { best = val; besti = s1; }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const float ob = __shfl_xor(best, off, 64);
+        const int oi = __shfl_xor(besti, off, 64);
+        if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }  // first index wins ties
+    }
+    return besti;
+}
+
 // the form the stand-alone kernel uses: workgroup `blk` of four waves, one atom each
 __device__ __forceinline__ void reverse_atoms_body(
     int blk /* block of the atom part */, float* __restrict__ frac, int32_t* __restrict__ types, const int32_t* __restrict__ tstep,
@@ -335,6 +452,159 @@ __device__ __forceinline__ void reverse_atoms_body(
     if (i >= N) return;  // wave-uniform; no block-level barrier below
     reverse_one_atom(i, threadIdx.x & 63, frac, types, tstep, offsets, B, eps, logits, noise, ve_sigmas, q1t, qmats, S, T, const_types, absorbing,
                      status, batch, cond, sched, word3);
+}
+
+// ---- space-group symmetry (arreau_sample_loop_sym / arreau_reverse_step_sym; rules in include/arreau_hip.h) -----------------
+// Crystal of atom i: the caller's index, or the 64-ary search of reverse_one_atom.
+__device__ __forceinline__ int sym_atom_crystal(int i, int lane, const int32_t* __restrict__ offsets, int B, const int32_t* __restrict__ batch) {
+    if (batch != nullptr) return batch[i];
+    int lo = 0, hi = B;
+    while (hi - lo > 1) {
+        const int span = hi - lo, step = (span + 63) >> 6;
+        const int probe = lo + lane * step;
+        const bool le = probe < hi && offsets[probe] <= i;
+        const int c = __builtin_popcountll(__ballot(le));
+        lo = lo + (c - 1) * step;
+        hi = min(lo + step, hi);
+    }
+    return lo;
+}
+
+// The tables of orbit o, led by atom i of the crystal [first, last), before any of them is followed: its CSR ranges in bounds
+// and non-empty, every member in the crystal, naming i as its leader and with an operation row in range, i among the members,
+// every stabilizer row in range.  Whole wave (o is wave-uniform); false: the orbit is rejected (the caller flags it).
+__device__ __forceinline__ bool sym_orbit_ok(const arreau_symmetry& sy, int i, int o, int first, int last, int lane) {
+    if (o < 0 || o >= sy.n_orbits) return false;
+    const int a0 = sy.orbit_ptr[o], a1 = sy.orbit_ptr[o + 1], h0 = sy.stab_ptr[o], h1 = sy.stab_ptr[o + 1];
+    if (!(a0 >= 0 && a0 < a1 && a1 <= sy.n_orbit_atoms && h0 >= 0 && h0 < h1 && h1 <= sy.n_stab_ops)) return false;
+    bool bad = false, self = false;
+    for (int a = a0 + lane; a < a1; a += 64) {
+        const int j = sy.orbit_atoms[a];
+        if (j < first || j >= last) { bad = true; continue; }
+        const int k = sy.op[j];
+        bad |= sy.leader[j] != i || k < 0 || k >= sy.n_ops;
+        self |= j == i;
+    }
+    for (int h = h0 + lane; h < h1; h += 64) {
+        const int k = sy.stab_ops[h];
+        bad |= k < 0 || k >= sy.n_ops;
+    }
+    return __ballot(bad) == 0 && __ballot(self) != 0;
+}
+
+// philox_normal (philox.h) with word3 = 0, forced inline: the SYM instances hold a second copy of the position update (the
+// unconstrained atoms' reverse_one_atom), past the inliner's budget for philox_normal.
+__device__ __forceinline__ float sym_philox_normal(uint64_t seed, uint32_t timestep, uint32_t kind, uint32_t element) {
+    const Philox4 r = philox4x32_10(element, timestep, kind, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const float u1 = ((float)(r.x[0] >> 8) + 1.0f) * (1.0f / 16777216.0f);
+    const float u2 = (float)(r.x[1] >> 8) * (1.0f / 16777216.0f);
+    return sqrtf(-2.0f * logf(u1)) * cosf(6.28318530717958647692f * u2);
+}
+
+__device__ __forceinline__ float sym_lane_value(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
+
+// The SYM form of reverse_atoms_body: one wave per atom.  An unconstrained atom (leader -1) runs reverse_one_atom as the plain
+// kernel does; a member leaves (its leader's wave writes it); a leader updates its whole orbit (rules 1-5).
+__device__ __forceinline__ void reverse_atoms_body_sym(
+    int blk, float* __restrict__ frac, int32_t* __restrict__ types, const int32_t* __restrict__ tstep, const int32_t* __restrict__ offsets,
+    int B, int N, const float* __restrict__ eps, const float* __restrict__ logits, StepNoiseSrc noise, const float* __restrict__ ve_sigmas,
+    const float* __restrict__ q1t, const float* __restrict__ qmats, int S, int T, const int32_t* __restrict__ const_types, int absorbing,
+    int32_t* __restrict__ status, int n0, const int32_t* __restrict__ batch, const StepScheduleDev* sched, const arreau_symmetry& sy) {
+    const int i = n0 + blk * 4 + (int)(threadIdx.x >> 6);
+    if (i >= N) return;  // wave-uniform; no block-level barrier below
+    const int lane = threadIdx.x & 63;
+    int lead = sy.leader[i];
+    if (lead != -1 && (lead < 0 || lead >= N || sy.leader[lead] != lead)) {  // a leader out of range, or one that does not lead
+        if (lane == 0) atomicOr(status, ARREAU_STATUS_BAD_SYMMETRY);
+        lead = -1;
+    }
+    if (lead >= 0 && lead != i) return;  // a member: written by its leader's wave
+    int b = 0, o = -1;
+    bool orbit_ok = false;
+    if (lead == i) {
+        b = sym_atom_crystal(i, lane, offsets, B, batch);
+        o = sy.orbit[i];
+        orbit_ok = sym_orbit_ok(sy, i, o, offsets[b], offsets[b + 1], lane);
+        if (!orbit_ok && lane == 0) atomicOr(status, ARREAU_STATUS_BAD_SYMMETRY);
+    }
+    if (!orbit_ok) {  // rule 7: unconstrained (or a rejected orbit's leader alone)
+        reverse_one_atom(i, lane, frac, types, tstep, offsets, B, eps, logits, noise, ve_sigmas, q1t, qmats, S, T, const_types, absorbing,
+                         status, batch, nullptr, sched, 0u);
+        return;
+    }
+    int t = tstep[b];
+    t = t < 1 ? 1 : (t > T ? T : t);
+    const int s_to = step_target(sched, b, t, status, false);  // (flagged by the crystal's lattice thread)
+    const int a0 = sy.orbit_ptr[o], a1 = sy.orbit_ptr[o + 1], h0 = sy.stab_ptr[o], h1 = sy.stab_ptr[o + 1];
+    const float inv_o = 1.0f / (float)(a1 - a0);
+    // rules 1-2, lane d < 3 owns component d: the pulled-back mean noise, then the leader's VE reverse update without the wrap
+    float y = 0.f, xc = 0.f;
+    if (lane < 3) {
+        float acc = 0.f;
+        for (int a = a0; a < a1; ++a) {
+            const int j = sy.orbit_atoms[a];
+            const float* Ri = sy.rot_inv + 9 * (size_t)sy.op[j] + 3 * lane;
+            const float* e = eps + 3 * (size_t)j;
+            acc += Ri[0] * e[0] + Ri[1] * e[1] + Ri[2] * e[2];
+        }
+        const float ebar = acc * inv_o;
+        const float sg = ve_sigmas[t], sp = ve_sigmas[s_to];
+        const float s2 = sg * sg, sp2 = sp * sp;
+        const size_t g = 3 * (size_t)i + lane;
+        xc = frac[g];
+        const float mean = xc - ebar * (s2 - sp2);
+        const float stdv = sqrtf((sp2 * (s2 - sp2)) / s2);
+        const float zf = noise.z_frac ? noise.z_frac[g] : sym_philox_normal(noise.seed, (uint32_t)t, ARREAU_DRAW_Z_FRAC, (uint32_t)g);
+        y = mean + stdv * zf;
+    }
+    const float ys[3] = {sym_lane_value(y, 0), sym_lane_value(y, 1), sym_lane_value(y, 2)};
+    const float xs[3] = {sym_lane_value(xc, 0), sym_lane_value(xc, 1), sym_lane_value(xc, 2)};
+    // rule 3: onto the site, anchored at the current position
+    float xn = 0.f;
+    if (lane < 3) {
+        if (h1 - h0 == 1) {
+            xn = remainder_one(y);
+        } else {
+            float acc = 0.f;
+            for (int h = h0; h < h1; ++h) {
+                const int k = sy.stab_ops[h];
+                const float* R = sy.rot + 9 * (size_t)k + 3 * lane;
+                const float tk = sy.trans[3 * (size_t)k + lane];
+                const float n = rintf(xc - (R[0] * xs[0] + R[1] * xs[1] + R[2] * xs[2]) - tk);
+                acc += ((R[0] * ys[0] + R[1] * ys[1] + R[2] * ys[2]) + tk) + n;
+            }
+            xn = remainder_one(acc / (float)(h1 - h0));
+        }
+    }
+    const float xl[3] = {sym_lane_value(xn, 0), sym_lane_value(xn, 1), sym_lane_value(xn, 2)};
+    // rule 5 (before any write): the orbit's mean logits, the leader's draw
+    const int s0 = lane, s1 = lane + 64;
+    const bool v0 = s0 < S, v1 = s1 < S;
+    float l0 = 0.f, l1 = 0.f;
+    for (int a = a0; a < a1; ++a) {
+        const float* lg = logits + (size_t)sy.orbit_atoms[a] * S;
+        if (v0) l0 += lg[s0];
+        if (v1) l1 += lg[s1];
+    }
+    l0 = v0 ? l0 * inv_o : -INFINITY;
+    l1 = v1 ? l1 * inv_o : -INFINITY;
+    const int cls = d3pm_reverse_class(i, lane, l0, l1, t, s_to, types, noise, q1t, qmats, S, absorbing, status, sched, 0u);
+    const int newt = const_types ? const_types[i] : cls;
+    // rule 4 and the members' species: lanes over the members
+    for (int a = a0 + lane; a < a1; a += 64) {
+        const int j = sy.orbit_atoms[a];
+        float* fj = frac + 3 * (size_t)j;
+        if (j == i) {
+            fj[0] = xl[0]; fj[1] = xl[1]; fj[2] = xl[2];
+        } else {
+            const int k = sy.op[j];
+            const float* R = sy.rot + 9 * (size_t)k;
+            const float* tk = sy.trans + 3 * (size_t)k;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) fj[c] = remainder_one((R[3 * c] * xl[0] + R[3 * c + 1] * xl[1] + R[3 * c + 2] * xl[2]) + tk[c]);
+        }
+        types[j] = newt;
+    }
 }
 
 // Sampling loop (round 3): the lattice update of a crystal by ONE workgroup that then also prepares the crystal's NEXT step --

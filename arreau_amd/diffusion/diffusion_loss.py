@@ -16,6 +16,7 @@ from . import resampling as rs
 from . import respacing
 from .d3pm import D3PM
 from . import lattice_systems
+from . import symmetry as sym_mod
 from .diffusion_helpers import VE_pbc, VP_lattice, crystal_offsets
 from .inference.visualize_crystal import VisualizationSetting, vis_crystal_during_sampling
 from .tools.atomic_number_table import AtomicNumberTable, atomic_number_indexes_to_atomic_numbers
@@ -263,7 +264,7 @@ class DiffusionLoss(nn.Module):
                fixed_cell: bool = False, condition=None, num_steps: Optional[int] = None,
                timesteps: Optional[Sequence[int]] = None, corrector_steps: int = 0,
                corrector_snr: float = pc.DEFAULT_SNR, resample_passes: int = 1, jump_length: int = 10,
-               lattice_system=None) -> SampleResult:
+               lattice_system=None, symmetry=None) -> SampleResult:
         """diffusion_loss.py:276-377.  The initial state is drawn on the host exactly like the reference (numpy
         uniforms for the angles, then randn lengths, randn fractional coordinates from torch's global CPU generator).
         Per-step noise:
@@ -313,6 +314,17 @@ class DiffusionLoss(nn.Module):
         step on the device (arreau_sample_loop_tied; rules in include/arreau_hip.h), the initial lengths tied on the host.
         None keeps the sampler as it was, bit for bit: monoclinic angles drawn in DEGREES and read as radians, the reference's
         own behaviour -- so None and "monoclinic" differ.  A system on a crystal whose cell a condition knows is rejected.  No
+        sample-quality claim is made.
+        `symmetry` (extension, noise="philox" only): space-group symmetry -- a symmetry.SymmetrySpec for every crystal of the batch
+        (num_samples_in_batch needed), or a sequence with one spec (or None, unconstrained) per crystal.  A constrained crystal's
+        atoms sit in the Wyckoff orbits of the spec's group at every step: the leader of each orbit is updated from the orbit's
+        pulled-back mean position noise and projected onto its site, the members are its images, and the orbit shares the
+        species the leader draws from the orbit's mean logits (arreau_sample_loop_sym; rules in include/arreau_hip.h).  The specs
+        decide the atom counts and lattice systems: num_atoms_per_sample and lattice_system, if given, must agree with them (and
+        give those of the None crystals).  The initial positions are drawn as without it, then every leader is projected onto
+        its site (anchored at the template's leader) and the members expanded, unwrapped.  Constant species must be constant
+        per orbit.  Works with graph replay, respaced schedules, fixed cells, max_steps and frames; a condition, corrector steps,
+        resampling and the host-noise modes are rejected.  None, or a sequence of None only, is the sampler as it was.  No
         sample-quality claim is made."""
         frames = visualization_setting != VisualizationSetting.NONE
         if frames and not vis_name:
@@ -325,6 +337,28 @@ class DiffusionLoss(nn.Module):
         if resample_passes > 1 and visualization_setting in (VisualizationSetting.ALL, VisualizationSetting.ALL_DETAILED):
             raise ValueError("resampling (resample_passes > 1) takes visualization_setting NONE or LAST: a frame inside a block "
                              "would be overwritten by the block's next pass")
+        if symmetry is not None and not isinstance(symmetry, sym_mod.SymmetrySpec) and num_samples_in_batch is None:
+            try:
+                num_samples_in_batch = len(symmetry)
+            except TypeError:
+                pass
+        specs = sym_mod.resolve(symmetry, num_samples_in_batch)  # None: no crystal is constrained (validated before any work)
+        if specs is not None:
+            unsupported = [name for name, on in (("condition", condition is not None), ("corrector_steps > 0", corrector_steps > 0),
+                                                 ("resample_passes > 1", resample_passes > 1), (f"noise={noise!r}", noise != "philox"))
+                           if on]
+            if unsupported:
+                raise ValueError("symmetry= is not supported with " + ", ".join(unsupported) + " yet (a follow-up); it runs in the "
+                                 "Philox loop without a condition, correctors or resampling")
+            num_atoms_per_sample, lattice_system = sym_mod.batch_layout(specs, num_atoms_per_sample, lattice_system)
+            num_samples_in_batch = len(specs)
+            if constant_atoms is not None:
+                ca = np.asarray(torch.as_tensor(constant_atoms).reshape(-1))
+                if ca.size == sum(num_atoms_per_sample):
+                    first = np.concatenate([[0], np.cumsum(num_atoms_per_sample)])
+                    for b, s_b in enumerate(specs):
+                        if s_b is not None:
+                            s_b.check_species(ca[first[b]:first[b + 1]], f"constant species of crystal {b}")
         if condition is not None:  # validated before the engine is touched
             num_atoms_per_sample, num_samples_in_batch = condition.resolve_batch(num_atoms_per_sample, num_samples_in_batch)
             condition.check_sampling(z_table, noise=noise, fixed_cell=fixed_cell, constant_species=constant_atoms is not None)
@@ -355,6 +389,13 @@ class DiffusionLoss(nn.Module):
         if tie is not None:
             lattice_systems.tie_lengths(lengths, tie)  # the initial state's tie; the device keeps it at every step
         frac_x = torch.randn([N, 3], dtype=dt) * pos_sigma_max
+        if specs is not None:  # leaders onto their sites, members their images (unwrapped, as the draw)
+            fx = frac_x.double().numpy()
+            first = np.concatenate([[0], np.cumsum(num_atoms.numpy())])
+            for b, s_b in enumerate(specs):
+                if s_b is not None:
+                    fx[first[b]:first[b + 1]] = s_b.initial_positions(fx[first[b]:first[b + 1]])
+            frac_x = torch.as_tensor(fx).to(dt)
         if constant_atoms is not None:
             atom_types = torch.as_tensor(constant_atoms).reshape(-1).long()
             if atom_types.numel() != N:
@@ -371,6 +412,7 @@ class DiffusionLoss(nn.Module):
         off_d = crystal_offsets(num_atoms, dev)
         lattice_d = torch.zeros((B, 3, 3), **f32)
         tie_d = torch.as_tensor(tie, device=dev, dtype=torch.int32).contiguous() if tie is not None else None
+        sym_d = sym_mod.device_arrays(specs, off_d, dev) if specs is not None else None
         # the timesteps this run visits, in order: every one (T-1 .. 1) or the schedule's, cut to max_steps
         steps = list(range(self.T - 1, 0, -1)) if schedule is None else schedule
         steps = steps if max_steps is None else steps[:max(0, int(max_steps))]
@@ -423,7 +465,8 @@ class DiffusionLoss(nn.Module):
                     if end > start:
                         eng.sample_loop(frac_d, types_d, len_d, ang_d, off_d, steps[start], end - start, seed, const_d, lattice_d,
                                         use_graph=bool(use_graph), fixed_lengths=fixed, condition=cond_d, next_table=next_d,
-                                        lattice_clipmax=clipmax, corrector=corrector, resampling=resampling, length_tie=tie_d)
+                                        lattice_clipmax=clipmax, corrector=corrector, resampling=resampling, length_tie=tie_d,
+                                        symmetry=sym_d)
                         start = end
                     if j is not None:
                         vis_crystal_during_sampling(z_table, types_d.cpu().numpy(), lattice_d.cpu().numpy(),

@@ -129,6 +129,8 @@ class HipEngine:
                 why.append("an atom-type index was outside [0, num_atomic_states)")
             if f & _hip.STATUS_BAD_TIE:
                 why.append("a lattice-system tie code was outside 0..2")
+            if f & _hip.STATUS_BAD_SYMMETRY:
+                why.append("a space-group symmetry table entry was out of range or inconsistent")
             raise _hip.ArreauHipError("arreau_hip status flags %d: %s" % (f, "; ".join(why)))
         return st
 
@@ -195,7 +197,7 @@ class HipEngine:
 
     def sample_loop(self, frac, types, lengths, angles, offsets, t_start, n_steps, seed, const_types, lattice_out,
                     use_graph=False, fixed_lengths=None, condition=None, next_table=None, lattice_clipmax=0.999, corrector=None,
-                    resampling=None, length_tie=None):
+                    resampling=None, length_tie=None, symmetry=None):
         """n_steps iterations of the sampling loop in one library call (arreau_sample_loop; with any of the options below
         arreau_sample_loop_resampled, whose NULL options are the loop without them): in-place update of
         (frac, types, lengths); Philox noise keyed by (seed, timestep, draw, element).  `condition`: the device arrays of a
@@ -209,7 +211,9 @@ class HipEngine:
         the first; `timesteps` is the host list of the schedule behind next_table (required with it).  None or passes == 1 is
         the loop without resampling.
         `length_tie`: lattice systems (arreau_sample_loop_tied): a contiguous int32 [B] tensor on the device, the tie code of every
-        crystal's lengths (0 none, 1 a = b, 2 a = b = c; lattice_systems.py); None is the loop without it."""
+        crystal's lengths (0 none, 1 a = b, 2 a = b = c; lattice_systems.py); None is the loop without it.
+        `symmetry`: space-group symmetry (arreau_sample_loop_sym): the dict of device tables of symmetry.device_arrays; None is
+        the loop without it.  Not with `condition`, corrector steps or resampling passes > 1 (the library rejects them)."""
         res = None
         if resampling is not None:
             from .diffusion.resampling import check_resampling
@@ -238,6 +242,14 @@ class HipEngine:
             sched = _hip.SampleScheduleC(_hip.ptr(next_table).value, float(lattice_clipmax))
         cond = self._condition_struct(condition, N, B) if condition is not None else None
         corr = _hip.CorrectorC(corrector[0], corrector[1]) if corrector is not None else None
+        if symmetry is not None:
+            if length_tie is not None:
+                self._check_tie(length_tie, B)
+            sym = self._symmetry_struct(symmetry, N)
+            byref = lambda v: ctypes.byref(v) if v is not None else None
+            _hip.check(_hip.lib().arreau_sample_loop_sym(*args, byref(cond), byref(sched), byref(corr), byref(res), _hip.ptr(length_tie),
+                                                         ctypes.byref(sym), _hip.stream_ptr(self.device)), "arreau_sample_loop_sym")
+            return
         if length_tie is not None:
             self._check_tie(length_tie, B)
             _hip.check(_hip.lib().arreau_sample_loop_tied(
@@ -257,6 +269,30 @@ class HipEngine:
         if (tuple(length_tie.shape) != (B,) or length_tie.dtype != torch.int32 or length_tie.device != self.device
                 or not length_tie.is_contiguous()):
             raise ValueError(f"length_tie must be a contiguous int32 tensor of shape ({B},) on {self.device}")
+
+    def _symmetry_struct(self, tables, N):
+        """arreau_symmetry of the dict of device tables of symmetry.device_arrays, with shapes, dtypes and device checked."""
+        names = ("leader", "op", "orbit", "orbit_ptr", "orbit_atoms", "stab_ptr", "stab_ops", "rot", "rot_inv", "trans")
+        missing = [n for n in names if tables.get(n) is None]
+        if missing or set(tables) - set(names):
+            raise ValueError(f"symmetry tables: expected exactly {names}")
+        for n in names:
+            t = tables[n]
+            want = torch.float32 if n in ("rot", "rot_inv", "trans") else torch.int32
+            if t.dtype != want or t.device != self.device or not t.is_contiguous() or t.numel() == 0:
+                raise ValueError(f"symmetry tables: {n} must be a non-empty contiguous {want} tensor on {self.device}")
+        for n in ("leader", "op", "orbit"):
+            if tuple(tables[n].shape) != (N,):
+                raise ValueError(f"symmetry tables: {n} must have shape ({N},)")
+        n_orb = tables["orbit_ptr"].numel() - 1
+        if tables["stab_ptr"].numel() != n_orb + 1 or n_orb < 1:
+            raise ValueError("symmetry tables: orbit_ptr and stab_ptr must both hold n_orbits + 1 >= 2 entries")
+        n_ops = tables["rot"].numel() // 9
+        if tuple(tables["rot"].shape) != (n_ops, 9) or tuple(tables["rot_inv"].shape) != (n_ops, 9) or \
+                tuple(tables["trans"].shape) != (n_ops, 3):
+            raise ValueError("symmetry tables: rot / rot_inv must be [n_ops, 9] and trans [n_ops, 3]")
+        return _hip.SymmetryC(*[_hip.ptr(tables[n]).value for n in names], n_orb, tables["orbit_atoms"].numel(),
+                              tables["stab_ops"].numel(), n_ops)
 
     def condition_initial_state(self, frac, types, lengths, t_start, seed, condition):
         """Rule 5 of conditioned sampling (arreau_condition_initial_state): the known components of an initial state drawn
@@ -564,6 +600,20 @@ class HipEngine:
             _hip.ptr(s_crystal), _hip.ptr(offsets), B, N, _hip.ptr(eps), _hip.ptr(logits), _hip.ptr(len0), _hip.ptr(z_lattice),
             _hip.ptr(z_frac), _hip.ptr(u_types), _hip.ptr(lattice_out), float(lattice_clipmax), _hip.ptr(length_tie),
             _hip.stream_ptr(self.device)), "arreau_reverse_step_tied")
+
+    def reverse_step_sym(self, frac, types, lengths, angles, t_crystal, s_crystal, offsets, eps, logits, len0, z_lattice, z_frac,
+                         u_types, lattice_out, length_tie, symmetry, lattice_clipmax=0.999):
+        """reverse_step_tied with space-group symmetry (arreau_reverse_step_sym): `symmetry` the dict of symmetry.device_arrays
+        (None: the tied step); length_tie may be None."""
+        B, N = lengths.shape[0], frac.shape[0]
+        if length_tie is not None:
+            self._check_tie(length_tie, B)
+        sym = self._symmetry_struct(symmetry, N) if symmetry is not None else None
+        _hip.check(_hip.lib().arreau_reverse_step_sym(
+            self._handle, _hip.ptr(frac), _hip.ptr(types), _hip.ptr(lengths), _hip.ptr(angles), _hip.ptr(t_crystal),
+            _hip.ptr(s_crystal), _hip.ptr(offsets), B, N, _hip.ptr(eps), _hip.ptr(logits), _hip.ptr(len0), _hip.ptr(z_lattice),
+            _hip.ptr(z_frac), _hip.ptr(u_types), _hip.ptr(lattice_out), float(lattice_clipmax), _hip.ptr(length_tie),
+            ctypes.byref(sym) if sym is not None else None, _hip.stream_ptr(self.device)), "arreau_reverse_step_sym")
 
     def resample_jump(self, frac, types, lengths, angles, s_crystal, t_crystal, offsets, z_frac, z_lengths, u_types, lattice_out,
                       const_types=None, fixed_lengths=None, condition=None, length_tie=None):

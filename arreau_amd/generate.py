@@ -22,6 +22,11 @@ state back to the block's top before every pass after the first (DiffusionLoss.s
 
 Lattice systems: `--lattice_system NAME` (cubic, tetragonal, orthorhombic, hexagonal, rhombohedral, monoclinic, triclinic) gives
 every crystal that system's angles and tied lengths (DiffusionLoss.sample).
+
+Space-group symmetry: `--symops FILE` (one operation per line in xyz form, e.g. `-x,y+1/2,-z+1/2`; `#` starts a comment) with
+`--lattice_system NAME` and exactly one of `--orbits K` (K orbits of general positions) or `--symmetry_template crystals.npz`
+(the first crystal's positions define the orbits) samples every crystal with its atoms in the orbits of the group the operations
+generate (DiffusionLoss.sample).  The spec decides the atom count (`--num_atoms` is not used).  Not with `--template`.
 """
 import argparse
 import os
@@ -188,7 +193,41 @@ def build_parser() -> argparse.ArgumentParser:
                     help="RePaint resampling: denoising steps per block (>= 1)")
     ap.add_argument("--lattice_system", type=str, default=None, choices=_lattice_system_choices(),
                     help="sample crystals of this lattice system: its angles, tied lengths (default: the reference's angles)")
+    ap.add_argument("--symops", type=str, default=None,
+                    help="space-group symmetry: a file of generators in xyz form, one per line (needs --lattice_system and one of "
+                         "--orbits / --symmetry_template)")
+    ap.add_argument("--orbits", type=int, default=None, help="space-group symmetry: K orbits of general positions")
+    ap.add_argument("--symmetry_template", type=str, default=None,
+                    help="space-group symmetry: crystals.npz / .h5 whose first crystal's positions define the orbits")
     return ap
+
+
+def load_symmetry(args, error):
+    """The SymmetrySpec of the --symops options (None without them); `error(message)` reports a bad combination."""
+    if args.symops is None:
+        if args.orbits is not None or args.symmetry_template is not None:
+            error("--orbits / --symmetry_template need --symops")
+        return None
+    if args.template is not None:
+        error("--symops cannot be combined with --template (conditioned generation)")
+    if args.lattice_system is None:
+        error("--symops needs --lattice_system")
+    if (args.orbits is None) == (args.symmetry_template is None):
+        error("--symops needs exactly one of --orbits K and --symmetry_template FILE")
+    from .diffusion import symmetry
+    try:
+        ops = symmetry.read_symops(args.symops)
+        if args.orbits is not None:
+            if args.orbits < 1:
+                error("--orbits must be >= 1")
+            return symmetry.SymmetrySpec.general_positions(ops, args.orbits, args.lattice_system)
+        from .diffusion.inference.process_generated_crystals import load_sample_results_from_hdf5
+        tmpl = load_sample_results_from_hdf5(args.symmetry_template)
+        n0 = int(np.asarray(tmpl.num_atoms)[0])
+        frac = np.asarray(tmpl.frac_x)[:n0]
+        return symmetry.SymmetrySpec.from_template(frac, ops, args.lattice_system)
+    except (OSError, ValueError) as e:
+        error(f"--symops: {e}")
 
 
 def _lattice_system_choices():
@@ -198,7 +237,9 @@ def _lattice_system_choices():
 
 def main():
     import torch
-    args = build_parser().parse_args()
+    ap = build_parser()
+    args = ap.parse_args()
+    spec = load_symmetry(args, ap.error)
     condition = load_template(args.template, parse_fix(args.fix)).tile(args.samples_per_template) if args.template else None
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -234,7 +275,7 @@ def main():
             return model.sample(n, b, VisualizationSetting.NONE, False, condition=cond, num_steps=args.num_steps,
                                 corrector_steps=args.corrector_steps, corrector_snr=args.corrector_snr,
                                 resample_passes=args.resample_passes, jump_length=args.jump_length,
-                                lattice_system=args.lattice_system)
+                                lattice_system=args.lattice_system, symmetry=spec)
         import fcntl
         with open(lock_path, "a") as lock:
             fcntl.flock(lock, fcntl.LOCK_EX)
@@ -242,7 +283,7 @@ def main():
                 out = model.sample(n, b, VisualizationSetting.NONE, False, condition=cond, num_steps=args.num_steps,
                                 corrector_steps=args.corrector_steps, corrector_snr=args.corrector_snr,
                                 resample_passes=args.resample_passes, jump_length=args.jump_length,
-                                lattice_system=args.lattice_system)
+                                lattice_system=args.lattice_system, symmetry=spec)
                 torch.cuda.synchronize()
                 return out
             finally:
@@ -250,7 +291,8 @@ def main():
     if condition is not None:
         res = generate_from_template(lambda c: fn(None, None, c), condition, args.batch, rank, world)
     else:
-        res = generate_n_crystals(fn, args.num_crystals, args.num_atoms, args.batch, rank, world)
+        res = generate_n_crystals(fn, args.num_crystals, spec.n_atoms if spec is not None else args.num_atoms, args.batch, rank,
+                                  world)
     if rank == 0:
         print("wrote", save_sample_results(res, args.out))
     if world > 1:

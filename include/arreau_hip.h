@@ -119,7 +119,9 @@ int arreau_model_config(const arreau_model* model, arreau_config* out_cfg);
  *   BAD_TIMESTEP a timestep outside [0, T] (predict_scores) / [1, T] (reverse_step) was clamped, or a respaced step's
  *                target s outside its range (arreau_reverse_step_to, arreau_sample_loop_scheduled);
  *   BAD_TYPE     an atom-type index outside [0, S) was clamped;
- *   BAD_TIE      a lattice-system tie code outside 0..2 was treated as 0 (arreau_sample_loop_tied and its step / jump).
+ *   BAD_TIE      a lattice-system tie code outside 0..2 was treated as 0 (arreau_sample_loop_tied and its step / jump);
+ *   BAD_SYMMETRY a symmetry table entry was out of range or inconsistent: the atoms it names were updated without symmetry
+ *                (arreau_sample_loop_sym, arreau_reverse_step_sym).
  * edge_kernel / mlp_kernel / conv_kernel name the kernel family the last arreau_predict_scores really launched
  * (edge: 0-2 fp32 MFMA, 3 bf16x6, 4 fp16x3; mlp: 0 fp32 MFMA, 1 bf16x6, 2 fp16x3 32x32x16, 3 fp16x3 16x16x32;
  * conv: 0 register form, 1 streamed form, 2 fused into the MLP kernel) -- e.g. 3/1 instead of 4/3 when a weight does not
@@ -130,6 +132,7 @@ int arreau_model_config(const arreau_model* model, arreau_config* out_cfg);
 #define ARREAU_STATUS_BAD_TIMESTEP 2
 #define ARREAU_STATUS_BAD_TYPE 4
 #define ARREAU_STATUS_BAD_TIE 8
+#define ARREAU_STATUS_BAD_SYMMETRY 16
 typedef struct arreau_status {
     int32_t flags;
     int32_t edge_kernel;
@@ -527,6 +530,64 @@ int arreau_resample_jump_tied(const arreau_model* model, float* d_frac, int32_t*
                               const float* d_z_frac, const float* d_z_lengths, const float* d_u_types,
                               const int32_t* d_const_types, const float* d_fixed_lengths,
                               const arreau_sample_condition* cond, float* d_lattice, const int32_t* d_length_tie, void* stream);
+
+/* ---- space-group symmetry (atoms tied in Wyckoff orbits) -------------------------------------------------------------
+ * A space-group operation g acts on fractional coordinates as x -> R x + t (R integer, det +-1).  A constrained crystal's atoms
+ * form orbits: each orbit O has a leader l (in the host's layout its lowest atom index), every atom j of O an operation k(j) with
+ * g_k(j)(x_l) = x_j (mod 1), and l a stabilizer H_l (the operations that fix x_l mod 1).  At every step, per orbit:
+ *   1. eps_bar = (1/|O|) sum_{j in O} R_k(j)^-1 eps_j, summed in the order of the orbit's member list (a displacement: no wrap).
+ *   2. y = the VE reverse update of x_l (arreau_reverse_step's arithmetic, or the respaced step's) with eps_bar and the LEADER's
+ *      draw (Philox kind 1, elements 3 l + d, or d_z_frac row l), without the wrap.  The members' draws are not used.
+ *   3. x_l' = remainder_1( (1/|H_l|) sum_{h in H_l} (R_h y + t_h + n_h) ), n_h = rint(x_l - R_h x_l - t_h) (x_l the current,
+ *      on-site position: the n_h are exact integers and the average is the affine projection onto the site, whatever the step);
+ *      for |H_l| = 1 (a general position) x_l' = remainder_1(y).
+ *   4. every other member: x_j' = remainder_1(R_k(j) x_l' + t_k(j)).
+ *   5. species: the leader draws from the D3PM reverse with the orbit's MEAN logits (summed in member order, times 1/|O|) and
+ *      its own uniforms (kind 2, elements l S + s, or d_u_types row l); every member takes the leader's new class.  Constant
+ *      species (d_const_types) are re-imposed at the leader; the caller keeps them constant per orbit.
+ *   6. lengths and angles: the lattice-system tie (d_length_tie, rules above), as without symmetry.
+ *   7. an atom with leader -1 (an unconstrained crystal) computes exactly what it computes without the tables, bit for bit.
+ * Tables (device pointers, all int32 unless stated): leader[N] (global atom index, -1 unconstrained), op[N] (k(j), a row of the
+ * operation tables), orbit[N] (the orbit of a leader); orbit_ptr[n_orbits + 1] / orbit_atoms[n_orbit_atoms] (CSR: the members of
+ * every orbit, leader included), stab_ptr[n_orbits + 1] / stab_ops[n_stab_ops] (CSR: H_l as operation rows); rot[n_ops, 9],
+ * rot_inv[n_ops, 9], trans[n_ops, 3] (float32, row-major R, R^-1 and t).  Every index is checked before it is followed: a leader
+ * outside -1..N-1, an orbit whose ranges, member atoms (all in the leader's crystal, all naming it as leader) or operation rows
+ * are out of range, or a member whose leader does not lead itself, sets ARREAU_STATUS_BAD_SYMMETRY, and the atoms concerned are
+ * updated without symmetry (the members of a rejected orbit are left as they were).  The initial state is the caller's: leaders
+ * on their sites, members their images. */
+typedef struct arreau_symmetry {
+    const int32_t* leader;
+    const int32_t* op;
+    const int32_t* orbit;
+    const int32_t* orbit_ptr;
+    const int32_t* orbit_atoms;
+    const int32_t* stab_ptr;
+    const int32_t* stab_ops;
+    const float* rot;
+    const float* rot_inv;
+    const float* trans;
+    int32_t n_orbits, n_orbit_atoms, n_stab_ops, n_ops;
+} arreau_symmetry;
+
+/* arreau_sample_loop_tied with the symmetry rules above: the Philox loop (eager or graph replay, respaced schedules, fixed cells).
+ * `symmetry` NULL is arreau_sample_loop_tied bit for bit.  With tables, `cond`, a corrector with steps > 0 and resampling with
+ * passes > 1 are rejected (ARREAU_EINVAL).  The table pointers are part of what a cached hipGraph was captured for. */
+int arreau_sample_loop_sym(arreau_model* model, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                           const int32_t* d_crystal_offsets, int32_t B, int32_t N, int32_t t_start, int32_t n_steps,
+                           uint64_t seed, const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice,
+                           void* d_workspace, size_t workspace_bytes, int32_t use_graph,
+                           const arreau_sample_condition* cond, const arreau_sample_schedule* schedule,
+                           const arreau_corrector* corrector, const arreau_resampling* resampling, const int32_t* d_length_tie,
+                           const arreau_symmetry* symmetry, void* stream);
+
+/* arreau_reverse_step_tied with the symmetry rules above (the caller's noise; `symmetry` NULL = arreau_reverse_step_tied). */
+int arreau_reverse_step_sym(const arreau_model* model,
+                            float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                            const int32_t* d_t, const int32_t* d_s, const int32_t* d_crystal_offsets, int32_t B, int32_t N,
+                            const float* d_eps, const float* d_logits, const float* d_len0,
+                            const float* d_z_lattice, const float* d_z_frac, const float* d_u_types,
+                            float* d_lattice, float lattice_clipmax, const int32_t* d_length_tie, const arreau_symmetry* symmetry,
+                            void* stream);
 
 /* The sampler's in-kernel noise written out: d_out[i] = draw (seed, timestep, kind, element i) -- standard normal for
  * kind 0 (z_lattice), 1 (z_frac), 3 (known positions) and 4 (known lengths), uniform [0,1) for kind 2 (u_types); d_raw[4 i .. 4 i + 3] (may be NULL) = the raw
