@@ -234,7 +234,8 @@ __device__ __forceinline__ void arreau_neighbor_receiver(
             src[o] = first + (int)(myc / 27u);
             cell[o] = (int)(myc % 27u);
             dir[3 * o + 0] = cd.dx; dir[3 * o + 1] = cd.dy; dir[3 * o + 2] = cd.dz;
-            dist[o] = __fsqrt_rn(cd.d2);
+            // sqrtf is correctly rounded like the reference's sqrt; HIP's __fsqrt_rn is the 1-ulp hardware v_sqrt_f32
+            dist[o] = sqrtf(cd.d2);
         } else {
             const size_t o = base + lane;  // lanes count..k-1 clear the unused slots
             src[o] = -1; cell[o] = -1;

@@ -190,8 +190,17 @@ int arreau_frac_to_cart(const float* d_frac, const float* d_lattice, const int32
  * Outputs: d_deg[N]; d_src[N,k] (global sender index, -1 when unused); d_cell[N,k] image code
  * 0..26 in the reference's SUPERCELLS order (diffusion_helpers.py:10), -1 when unused;
  * d_dir[N,k,3] = pos_sender + image_offset - pos_receiver; d_dist[N,k].
- * Tie rule (the reference leaves it to an unstable sort): smaller d^2 first, then smaller
- * enumeration index (sender, image). */
+ * A candidate (sender, image) is in range when 1e-4f < d^2 <= (float)((double)radius * radius),
+ * d^2 = (dx*dx + dy*dy) + dz*dz in float32 without contraction.  k may be 1 .. 64: per receiver
+ * the k in-range candidates with the smallest keys are kept and written in ascending
+ * enumeration index c = 27 * (sender - first atom of the crystal) + image; unused slots are
+ * cleared.
+ * Tie rule (the reference leaves it to an unstable sort): the key is (bits of d^2, c), so among
+ * candidates whose float32 d^2 are EQUAL the smaller c wins -- the earlier sender, then the
+ * earlier image.  The oracle's radius_graph_pbc(stable_ties=True) states the same rule.
+ * Limit: the key holds c in 21 bits, c < 2^21, i.e. at most 77 672 atoms in one crystal
+ * (27 * 77 672 = 2 097 144).  The limit is NOT checked: a larger crystal gives a wrong list
+ * without a status flag. */
 int arreau_radius_graph_pbc(const float* d_cart, const float* d_lattice,
                             const int32_t* d_crystal_offsets, int32_t B, int32_t N,
                             float radius, int32_t k,

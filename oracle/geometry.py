@@ -52,7 +52,7 @@ def frac_to_cart_coords(frac: torch.Tensor, lattice: torch.Tensor, num_atoms: to
     return torch.einsum("bi,bij->bj", frac, per_node)
 
 
-def radius_graph_pbc(cart, lattice, num_atoms, radius, max_neighbors, remove_self_edges=True):
+def radius_graph_pbc(cart, lattice, num_atoms, radius, max_neighbors, remove_self_edges=True, stable_ties=False):
     """Periodic radius graph with a per-receiver neighbour cap.
 
     Restates diffusion/diffusion_helpers.py:328-564 (topk_per_pair=None path):
@@ -66,7 +66,10 @@ def radius_graph_pbc(cart, lattice, num_atoms, radius, max_neighbors, remove_sel
       receiver the ``max_neighbors`` smallest d2 using a sort over a padded
       [N, max_count] matrix filled with radius^2+1 (:494-528).  The sort is
       torch's default (unstable) sort exactly as in the reference, so the
-      choice among exactly tied d2 values is torch-build dependent;
+      choice among exactly tied d2 values is torch-build dependent.  With
+      ``stable_ties=True`` the sort is stable instead: among exactly tied d2
+      the candidate enumerated first wins, which is the rule of the HIP
+      kernel, (bits of d2, enumeration index);
     * surviving edges keep the enumeration order (masking preserves order).
 
     Returns (edge_index [2,E] = (sender, receiver), cell_offsets [E,3] (the
@@ -124,7 +127,7 @@ def radius_graph_pbc(cart, lattice, num_atoms, radius, max_neighbors, remove_sel
         first_edge = torch.cumsum(count, 0) - count
         slot = torch.arange(recv_k.numel(), device=dev) - first_edge[recv_k]
         pad[recv_k * max_count + slot] = d2_k
-        sorted_d2, order = torch.sort(pad.view(N, max_count), dim=1)
+        sorted_d2, order = torch.sort(pad.view(N, max_count), dim=1, stable=bool(stable_ties))
         sorted_d2 = sorted_d2[:, :max_neighbors]
         order = order[:, :max_neighbors] + first_edge.view(-1, 1)
         chosen = order[sorted_d2 <= radius * radius]

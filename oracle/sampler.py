@@ -68,18 +68,20 @@ def assemble_features(m: OracleModel, frac, types_onehot, t_feat, num_atoms, len
 
 
 def predict_scores(m: OracleModel, frac, types_onehot, t_feat, num_atoms, lengths, angles,
-                   batch, edges=None, return_graph=False):
+                   batch, edges=None, return_graph=False, stable_ties=False):
     """diffusion/diffusion_loss.py:112-197.
 
     ``edges`` = (edge_index, dists, direction) teacher-forces a neighbour list
     (used for parity of the network independent of tie-breaking); otherwise the
-    oracle's own radius_graph_pbc is used like the reference does at :164-174.
+    oracle's own radius_graph_pbc is used like the reference does at :164-174
+    (``stable_ties``: its stable-sort variant, see geometry.radius_graph_pbc).
     Returns (pred_frac_eps [N,3], logits [N,S], pred_lengths_0 [B,3]).
     """
     x, cart, vec, lattice = assemble_features(m, frac, types_onehot, t_feat, num_atoms, lengths, angles)
     if edges is None:
         edge_index, _cells, _cnt, dists, direction = G.radius_graph_pbc(
-            cart, lattice, num_atoms, m.hp["radius"], m.hp["max_neighbors"], remove_self_edges=True)
+            cart, lattice, num_atoms, m.hp["radius"], m.hp["max_neighbors"], remove_self_edges=True,
+            stable_ties=stable_ties)
     else:
         edge_index, dists, direction = edges
     batch_of_edge = batch[edge_index[0]]
@@ -139,7 +141,7 @@ def init_state(m: OracleModel, n_per: int, B: int, dtype, np_rng=None):
 
 
 def sample(m: OracleModel, n_per: int, B: int, dtype=torch.float32, trace: Optional[SampleTrace] = None,
-           max_steps: Optional[int] = None, state=None):
+           max_steps: Optional[int] = None, state=None, stable_ties=False):
     """DiffusionLoss.sample, diffusion/diffusion_loss.py:276-377 (no visualisation).
 
     Runs timesteps T-1 .. 1 (T-1 iterations, :318) drawing noise from torch's
@@ -156,7 +158,8 @@ def sample(m: OracleModel, n_per: int, B: int, dtype=torch.float32, trace: Optio
     done = 0
     for timestep in reversed(range(1, T)):
         t = torch.full((N,), timestep)
-        scores = predict_scores(m, frac, F.one_hot(atom_types, S), t, num_atoms, lengths, angles, batch)
+        scores = predict_scores(m, frac, F.one_hot(atom_types, S), t, num_atoms, lengths, angles, batch,
+                                stable_ties=stable_ties)
         noise = StepNoise(torch.randn([B, 3], dtype=dtype), torch.randn([N, 3], dtype=dtype),
                           torch.rand([N, S], dtype=dtype))
         if trace is not None:

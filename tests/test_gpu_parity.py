@@ -15,43 +15,10 @@ import torch.nn.functional as F
 from oracle import diffusion as OD
 from oracle import geometry as OG
 from oracle import sampler as OS
-from tests.helpers import oracle_from_module, random_state, slots_from_edges
+from tests.helpers import TOL, assert_scores_close, oracle_from_module, pooled_bound, random_state, slots_from_edges, ulp32
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-TOL = 1e-5
-
-
-def ulp32(x):
-    """Spacing of float32 numbers at magnitude x."""
-    return float(np.spacing(np.float32(abs(float(x)))))
-
-
-def pooled_bound(ref, atoms_per_crystal=20, ulps=4):
-    """Bound for a per-crystal pooled read-out (len0 / global_scalar): a SUM over the crystal's atoms, so its error is a
-    few fp32 ulps of the sum, not a fraction of 1e-5 of it -- 4 ulps of the largest value for crystals of up to 20 atoms
-    (measured: 3 ulps at |len0| ~ 58; the fp32 oracle is as far from fp64), growing with the square root of the atom
-    count; never below the plain 1e-5 of an order-one quantity."""
-    scale = max(1.0, (atoms_per_crystal / 20.0) ** 0.5)
-    return max(TOL, ulps * scale * ulp32(float(ref.abs().max())))
-
-
-def assert_scores_close(got, want, tag="", atoms_per_crystal=20):
-    """The north-star bound -- per-step scores, type logits and lattice predictions within 1e-5 of the fp32 CPU path --
-    as plain absolute 1e-5 wherever the quantity is of order one.  Measured (profiles/parity_r02.json, S = 90 model):
-    eps <= 2.3e-7, logits <= 2.6e-6 at |logits| ~ 6, len0 <= 1.2e-5 at |len0| ~ 58.  A quantity larger than order one is
-    allowed the same RELATIVE error against its own magnitude: logits 1e-5 * max(1, |logits|max / 8), eps 1e-5 * max(1,
-    |eps|max); len0, a sum over the crystal's atoms, is bounded in fp32 ulps of that sum (pooled_bound: 4 ulps = 1.5e-5
-    at |len0| = 58, where round 2 allowed 5.8e-4)."""
-    (eps, logits, len0), (eps_o, logits_o, len0_o) = got, want
-    e = float((eps.detach().cpu() - eps_o).abs().max())
-    l = float((logits.detach().cpu() - logits_o).abs().max())
-    g = float((len0.detach().cpu() - len0_o).abs().max())
-    assert e <= TOL * max(1.0, float(eps_o.abs().max())), (tag, "eps", e)
-    assert l <= TOL * max(1.0, float(logits_o.abs().max()) / 8.0), (tag, "logits", l, float(logits_o.abs().max()))
-    assert g <= pooled_bound(len0_o, atoms_per_crystal), (tag, "len0", g, float(len0_o.abs().max()), pooled_bound(len0_o, atoms_per_crystal))
-    return e, l, g
-
 
 @pytest.fixture(scope="module")
 def dev():
@@ -132,8 +99,10 @@ def test_radius_graph_matches_reference_fixture(dev, i):
 @pytest.mark.parametrize("num_atoms,cell,seed", [
     ([20] * 16, (4.0, 8.0), 0), ([1, 2, 3, 5, 8, 13, 20, 7], (3.0, 6.0), 1), ([64, 64], (6.0, 9.0), 2),
     ([2] * 5, (9.0, 12.0), 3), ([33], (2.5, 4.0), 4),
-    # crystals beyond the register-resident candidate set: in-range keys compacted through LDS (relaxed cells) and the
-    # re-evaluating rounds (more than 768 candidates inside the cutoff)
+    # crystals beyond the register-resident candidate set (more than 28 atoms): the in-range keys at or below the two-pass
+    # threshold are compacted through the LDS list.  ([64], (2.0, 3.0), 6) has more than 768 candidates inside the cutoff, but
+    # its threshold lets about ten keys through: it takes the LDS list as well.  The re-evaluating rounds (more than 384 keys
+    # at or below the threshold) take a built input: test_gpu_neighbor_list.py
     ([48, 64, 29, 57], (7.0, 11.0), 5), ([64], (2.0, 3.0), 6), ([40, 40], (3.5, 5.0), 7),
     # a crystal beyond the LDS copy of the positions (more than 128 atoms: candidates read from global memory), next to one inside it
     ([150, 3, 128, 129], (8.0, 12.0), 8)])
