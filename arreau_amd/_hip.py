@@ -29,7 +29,7 @@ EXPORTS = [
     "arreau_sample_loop_corrected", "arreau_corrector_step", "arreau_philox_fill_word",
     "arreau_sample_loop_resampled", "arreau_resample_jump", "arreau_optimizer_step_ema",
     "arreau_sample_loop_tied", "arreau_reverse_step_tied", "arreau_resample_jump_tied",
-    "arreau_sample_loop_sym", "arreau_reverse_step_sym",
+    "arreau_sample_loop_sym", "arreau_reverse_step_sym", "arreau_crystal_screen",
 ]
 
 STATUS_NONFINITE, STATUS_BAD_TIMESTEP, STATUS_BAD_TYPE, STATUS_BAD_TIE, STATUS_BAD_SYMMETRY = 1, 2, 4, 8, 16
@@ -78,6 +78,17 @@ class SymmetryC(Structure):
     _fields_ = [(name, c_void_p) for name in ("leader", "op", "orbit", "orbit_ptr", "orbit_atoms", "stab_ptr", "stab_ops", "rot",
                                                 "rot_inv", "trans")] + [(name, c_int32) for name in ("n_orbits", "n_orbit_atoms",
                                                                                                      "n_stab_ops", "n_ops")]
+
+
+class ScreenCriteriaC(Structure):
+    """arreau_screen_criteria: the thresholds of the structural screen."""
+    _fields_ = [("min_distance", c_float), ("min_volume", c_float), ("search_radius", c_float), ("mask_type", c_int32),
+                ("max_shells", c_int32)]
+
+
+class ScreenResultC(Structure):
+    """arreau_screen_result: the six device arrays the screen writes, one entry per crystal."""
+    _fields_ = [(name, c_void_p) for name in ("min_distance", "pair", "n_close", "volume", "number_density", "flags")]
 
 
 class Config(Structure):
@@ -172,6 +183,8 @@ def lib():
     if hasattr(L, "arreau_sample_loop_sym") or not os.environ.get("ARREAU_HIP_LIB"):  # (an older build under test)
         L.arreau_sample_loop_sym.argtypes = L.arreau_sample_loop_tied.argtypes[:-1] + [POINTER(SymmetryC), c_void_p]
         L.arreau_reverse_step_sym.argtypes = L.arreau_reverse_step_tied.argtypes[:-1] + [POINTER(SymmetryC), c_void_p]
+    if hasattr(L, "arreau_crystal_screen") or not os.environ.get("ARREAU_HIP_LIB"):  # (an older build under test)
+        L.arreau_crystal_screen.argtypes = [c_void_p] * 4 + [c_int32, c_int32, POINTER(ScreenCriteriaC), POINTER(ScreenResultC), c_void_p]
     L.arreau_philox_fill.argtypes = [ctypes.c_uint64, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_void_p]
     L.arreau_train_forward.argtypes = [c_void_p] * 7 + [c_int32, c_int32] + [c_void_p] * 4
     L.arreau_train_backward.argtypes = [c_void_p] * 4 + [POINTER(StateDict), c_void_p]

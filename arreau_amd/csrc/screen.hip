@@ -1,0 +1,222 @@
+// Structural screen of a batch of crystals (arreau_crystal_screen; the rules are written out in include/arreau_hip.h): the
+// shortest interatomic contact over every periodic image within a search radius, the cell volume, the mask state.  An exact
+// search of its own: the sampling step's neighbour list looks at 27 images, stops at k inside a radius and skips overlapping
+// pairs.  One launch, one workgroup of four waves per crystal, no atomics; needs no arreau_model.
+#include "internal.h"
+#include "graph_dev.h"
+#include <cmath>
+
+#define SCREEN_LDS_ATOMS 256  // crystals of up to this many atoms keep their Cartesian positions in LDS (3 KiB)
+#define SCREEN_WAVES 4
+
+namespace {
+
+// every fp32 operation below is spelled out (__fmul_rn / __fadd_rn / __fsub_rn / __fdiv_rn): one rounding each, no contraction
+// to an FMA, so that the float32 host restatement (arreau_amd/diffusion/screening.py) matches bit for bit
+__device__ __forceinline__ float dot3_rn(float ax, float ay, float az, float bx, float by, float bz) {
+    return __fadd_rn(__fadd_rn(__fmul_rn(ax, bx), __fmul_rn(ay, by)), __fmul_rn(az, bz));
+}
+
+__device__ __forceinline__ void cross_rn(const float* u, const float* v, float* o) {
+    o[0] = __fsub_rn(__fmul_rn(u[1], v[2]), __fmul_rn(u[2], v[1]));
+    o[1] = __fsub_rn(__fmul_rn(u[2], v[0]), __fmul_rn(u[0], v[2]));
+    o[2] = __fsub_rn(__fmul_rn(u[0], v[1]), __fmul_rn(u[1], v[0]));
+}
+
+// w = f - floor(f), a result of 1 (a tiny negative f) becomes 0; then arreau_cart_component's expression on the wrapped
+// coordinates, uncontracted
+__device__ __forceinline__ float screen_wrap(float f) {
+    const float w = __fsub_rn(f, floorf(f));
+    return w >= 1.0f ? 0.0f : w;
+}
+
+__device__ __forceinline__ float screen_cart(const float* __restrict__ frac, const float* Lm, size_t atom, int d) {
+    const float w0 = screen_wrap(frac[3 * atom]), w1 = screen_wrap(frac[3 * atom + 1]), w2 = screen_wrap(frac[3 * atom + 2]);
+    return __fadd_rn(__fadd_rn(__fmul_rn(w0, Lm[d]), __fmul_rn(w1, Lm[3 + d])), __fmul_rn(w2, Lm[6 + d]));
+}
+
+__global__ __launch_bounds__(64 * SCREEN_WAVES) void crystal_screen_kernel(
+    const float* __restrict__ frac, const int32_t* __restrict__ types, const float* __restrict__ lattice,
+    const int32_t* __restrict__ offsets, int B, int N, float min_volume, float md2 /* min_distance^2 */, float r2 /* search_radius^2 */,
+    float radius, int mask_type, int max_shells, float* __restrict__ o_dist, int32_t* __restrict__ o_pair,
+    int32_t* __restrict__ o_close, float* __restrict__ o_volume, float* __restrict__ o_density, int32_t* __restrict__ o_flags) {
+    const int b = blockIdx.x;
+    if (b >= B) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // the crystal's atom range, clamped into [0, N]: a bad offset table cannot make the kernel read outside frac / types
+    int first = offsets[b], last = offsets[b + 1];
+    first = first < 0 ? 0 : (first > N ? N : first);
+    last = last < first ? first : (last > N ? N : last);
+    const int n = last - first;
+    float Lm[9];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) Lm[q] = lattice[9 * (size_t)b + q];
+
+    __shared__ float spos[3 * SCREEN_LDS_ATOMS];
+    __shared__ unsigned s_d2[SCREEN_WAVES];
+    __shared__ unsigned long long s_ij[SCREEN_WAVES];
+    __shared__ unsigned s_m[SCREEN_WAVES];
+    __shared__ int s_close[SCREEN_WAVES];
+
+    // ---- NONFINITE / MASKED: one pass over the crystal's inputs
+    int bad = 0, masked = 0;
+#pragma unroll
+    for (int q = 0; q < 9; ++q) bad |= !isfinite(Lm[q]);
+    for (int a = tid; a < 3 * n; a += 64 * SCREEN_WAVES) bad |= !isfinite(frac[3 * (size_t)first + a]);
+    if (types != nullptr && mask_type >= 0)
+        for (int a = tid; a < n; a += 64 * SCREEN_WAVES) masked |= types[(size_t)first + a] == mask_type;
+    bad = __syncthreads_or(bad);
+    masked = __syncthreads_or(masked);
+    const float qnan = __int_as_float(0x7fc00000);
+    if (bad) {  // (workgroup-uniform) nothing else is computed
+        if (tid == 0) {
+            o_dist[b] = qnan; o_volume[b] = qnan; o_density[b] = qnan;
+            o_close[b] = 0; o_flags[b] = ARREAU_SCREEN_NONFINITE;
+        }
+        if (tid < 5) o_pair[5 * (size_t)b + tid] = -1;
+        return;
+    }
+
+    // ---- the cell: volume, plane spacings, images per axis (every thread computes the same values)
+    float c0[3], c1[3], c2[3];
+    cross_rn(Lm + 3, Lm + 6, c0);
+    cross_rn(Lm + 6, Lm + 0, c1);
+    cross_rn(Lm + 0, Lm + 3, c2);
+    const float volume = fabsf(dot3_rn(Lm[0], Lm[1], Lm[2], c0[0], c0[1], c0[2]));
+    const float density = __fdiv_rn((float)n, volume);
+    const float q0 = __fdiv_rn(radius, __fdiv_rn(volume, sqrtf(dot3_rn(c0[0], c0[1], c0[2], c0[0], c0[1], c0[2]))));
+    const float q1 = __fdiv_rn(radius, __fdiv_rn(volume, sqrtf(dot3_rn(c1[0], c1[1], c1[2], c1[0], c1[1], c1[2]))));
+    const float q2 = __fdiv_rn(radius, __fdiv_rn(volume, sqrtf(dot3_rn(c2[0], c2[1], c2[2], c2[0], c2[1], c2[2]))));
+    const float cap = (float)max_shells;
+    const bool cell_bad = !(volume >= min_volume) || !isfinite(volume) || !(q0 <= cap) || !(q1 <= cap) || !(q2 <= cap);
+    int flags = masked ? ARREAU_SCREEN_MASKED : 0;
+    if (cell_bad) {  // (workgroup-uniform) the search is skipped
+        if (tid == 0) {
+            o_dist[b] = qnan; o_volume[b] = volume; o_density[b] = density;
+            o_close[b] = 0; o_flags[b] = flags | ARREAU_SCREEN_CELL;
+        }
+        if (tid < 5) o_pair[5 * (size_t)b + tid] = -1;
+        return;
+    }
+    // q_k <= max_shells <= 8 here, so n_k <= 8 and M <= 17^3
+    const int N1 = max(1, (int)ceilf(q0)), N2 = max(1, (int)ceilf(q1)), N3 = max(1, (int)ceilf(q2));
+    const unsigned W2 = 2u * N2 + 1u, W3 = 2u * N3 + 1u, M = (2u * N1 + 1u) * W2 * W3;
+    const unsigned centre = ((unsigned)N1 * W2 + (unsigned)N2) * W3 + (unsigned)N3;
+
+    // ---- positions: staged in LDS when the crystal fits, else formed from global memory where they are used (same values)
+    const bool staged = n <= SCREEN_LDS_ATOMS;
+    if (staged)
+        for (int a = tid; a < 3 * n; a += 64 * SCREEN_WAVES) spos[a] = screen_cart(frac, Lm, (size_t)first + a / 3, a % 3);
+    __syncthreads();
+    auto position = [&](int atom, int d) -> float { return staged ? spos[3 * atom + d] : screen_cart(frac, Lm, (size_t)first + atom, d); };
+
+    // ---- the search.  Receiver i (uniform), then the flattened (j >= i, image m) range dealt to the 256 threads: every thread
+    // meets its contacts in ascending (i, j, m), so a strict "<" on the bits of d2 keeps the first of equal minima.
+    unsigned best_d2 = 0xffffffffu, best_m = 0;  // bits of d2 (d2 >= +0: the bits order like the values; NaN cannot arise from
+    unsigned long long best_ij = ~0ull;          // finite inputs, inf keeps its place above every finite value)
+    int close = 0;
+    for (int i = 0; i < n; ++i) {
+        const float pix = position(i, 0), piy = position(i, 1), piz = position(i, 2);
+        auto contact = [&](unsigned dj, unsigned m) {
+            if (dj == 0 && m <= centre) return;  // an atom with itself: only the images after (0, 0, 0)
+            const int j = i + (int)dj;
+            const unsigned m12 = m / W3;
+            const float n3 = (float)((int)(m - m12 * W3) - N3), n2 = (float)((int)(m12 % W2) - N2), n1 = (float)((int)(m12 / W2) - N1);
+            const float sx = __fadd_rn(__fadd_rn(__fmul_rn(n1, Lm[0]), __fmul_rn(n2, Lm[3])), __fmul_rn(n3, Lm[6]));
+            const float sy = __fadd_rn(__fadd_rn(__fmul_rn(n1, Lm[1]), __fmul_rn(n2, Lm[4])), __fmul_rn(n3, Lm[7]));
+            const float sz = __fadd_rn(__fadd_rn(__fmul_rn(n1, Lm[2]), __fmul_rn(n2, Lm[5])), __fmul_rn(n3, Lm[8]));
+            const float dx = __fsub_rn(__fadd_rn(position(j, 0), sx), pix);
+            const float dy = __fsub_rn(__fadd_rn(position(j, 1), sy), piy);
+            const float dz = __fsub_rn(__fadd_rn(position(j, 2), sz), piz);
+            const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+            close += d2 < md2 ? 1 : 0;
+            const unsigned bits = __float_as_uint(d2);
+            if (bits < best_d2) {
+                best_d2 = bits;
+                best_ij = ((unsigned long long)i << 24) | (unsigned long long)j;
+                best_m = m;
+            }
+        };
+        const unsigned long long span = (unsigned long long)(n - i) * M;
+        if (span <= 0xffffffffull - 64 * SCREEN_WAVES) {  // (uniform) the usual case: 32-bit index arithmetic
+            for (unsigned e = (unsigned)tid; e < (unsigned)span; e += 64 * SCREEN_WAVES) {
+                const unsigned dj = e / M;
+                contact(dj, e - dj * M);
+            }
+        } else {
+            for (unsigned long long e = (unsigned long long)tid; e < span; e += 64 * SCREEN_WAVES) {
+                const unsigned long long dj = e / M;
+                contact((unsigned)dj, (unsigned)(e - dj * M));
+            }
+        }
+    }
+
+    // ---- deterministic reduction: the wave minimum of the ordered key (bits of d2; i, j; m), one exact double each
+    // (arreau_wave_min_f64, graph_dev.h), then the four waves through LDS.  A lane without a contact holds the largest key.
+    constexpr double NONE = 1.0e300;
+    const double wd2 = arreau_wave_min_f64((double)best_d2);
+    const double wij = arreau_wave_min_f64((double)best_d2 == wd2 && best_ij != ~0ull ? (double)best_ij : NONE);  // i, j < 2^24: exact
+    const double wm = arreau_wave_min_f64((double)best_d2 == wd2 && (double)best_ij == wij ? (double)best_m : NONE);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) close += __shfl_xor(close, off);  // (an integer sum: any order gives the same value)
+    if (lane == 0) {
+        s_d2[wave] = (unsigned)wd2;
+        s_ij[wave] = wij == NONE ? ~0ull : (unsigned long long)wij;
+        s_m[wave] = wm == NONE ? 0xffffffffu : (unsigned)wm;
+        s_close[wave] = close;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        unsigned d2b = s_d2[0], mm = s_m[0];
+        unsigned long long ij = s_ij[0];
+        int total = s_close[0];
+        for (int w = 1; w < SCREEN_WAVES; ++w) {
+            total += s_close[w];
+            const bool less = s_d2[w] < d2b || (s_d2[w] == d2b && (s_ij[w] < ij || (s_ij[w] == ij && s_m[w] < mm)));
+            if (less) { d2b = s_d2[w]; ij = s_ij[w]; mm = s_m[w]; }
+        }
+        int32_t* pr = o_pair + 5 * (size_t)b;
+        if (total > 0) flags |= ARREAU_SCREEN_CLOSE;
+        if (ij == ~0ull) {  // no contact at all (an empty crystal)
+            o_dist[b] = __int_as_float(0x7f800000);
+            pr[0] = pr[1] = pr[2] = pr[3] = pr[4] = -1;
+            flags |= ARREAU_SCREEN_BEYOND;
+        } else {
+            const float d2 = __uint_as_float(d2b);
+            o_dist[b] = sqrtf(d2);  // correctly rounded, like the neighbour list's distance
+            const unsigned m12 = mm / W3;
+            pr[0] = (int)(ij >> 24); pr[1] = (int)(ij & 0xffffffull);
+            pr[2] = (int)(m12 / W2) - N1; pr[3] = (int)(m12 % W2) - N2; pr[4] = (int)(mm - m12 * W3) - N3;
+            if (!(d2 <= r2)) flags |= ARREAU_SCREEN_BEYOND;
+        }
+        o_volume[b] = volume; o_density[b] = density;
+        o_close[b] = total; o_flags[b] = flags;
+    }
+}
+
+}  // namespace
+
+extern "C" int arreau_crystal_screen(const float* d_frac, const int32_t* d_types, const float* d_lattice,
+                                     const int32_t* d_crystal_offsets, int32_t B, int32_t N, const arreau_screen_criteria* crit,
+                                     arreau_screen_result* out, void* stream) {
+    ARREAU_REQUIRE(crit != nullptr && out != nullptr, "arreau_crystal_screen: null criteria or result");
+    ARREAU_REQUIRE(B >= 0 && N >= 0, "arreau_crystal_screen: bad size");
+    ARREAU_REQUIRE(std::isfinite(crit->min_distance) && crit->min_distance >= 0.f && std::isfinite(crit->min_volume) && crit->min_volume >= 0.f,
+                   "arreau_crystal_screen: min_distance and min_volume must be finite and >= 0");
+    ARREAU_REQUIRE(std::isfinite(crit->search_radius) && crit->search_radius > 0.f && crit->search_radius >= crit->min_distance,
+                   "arreau_crystal_screen: search_radius must be finite, > 0 and at least min_distance");
+    ARREAU_REQUIRE(crit->max_shells >= 1 && crit->max_shells <= ARREAU_SCREEN_MAX_SHELLS,
+                   "arreau_crystal_screen: max_shells must lie in 1..8");
+    ARREAU_REQUIRE(crit->mask_type >= -1, "arreau_crystal_screen: mask_type must be -1 (none) or a class index");
+    if (B == 0) return ARREAU_OK;
+    ARREAU_REQUIRE(d_lattice && d_crystal_offsets && (d_frac || N == 0), "arreau_crystal_screen: null pointer");
+    ARREAU_REQUIRE(out->min_distance && out->pair && out->n_close && out->volume && out->number_density && out->flags,
+                   "arreau_crystal_screen: null result array");
+    const float md2 = (float)((double)crit->min_distance * (double)crit->min_distance);
+    const float r2 = (float)((double)crit->search_radius * (double)crit->search_radius);
+    ARREAU_LAUNCH(crystal_screen_kernel, dim3((unsigned)B), dim3(64 * SCREEN_WAVES), 0, (hipStream_t)stream, d_frac, d_types, d_lattice,
+                  d_crystal_offsets, (int)B, (int)N, crit->min_volume, md2, r2, crit->search_radius, (int)crit->mask_type,
+                  (int)crit->max_shells, out->min_distance, out->pair, out->n_close, out->volume, out->number_density, out->flags);
+    ARREAU_CHECK_HIP(hipGetLastError());
+    return ARREAU_OK;
+}

@@ -14,6 +14,7 @@ import torch.nn as nn
 from . import corrector as pc
 from . import resampling as rs
 from . import respacing
+from . import screening
 from .d3pm import D3PM
 from . import lattice_systems
 from . import symmetry as sym_mod
@@ -40,6 +41,9 @@ class SampleResult:
     # extension (not in the reference): what the library did to produce this batch -- e.g. {"full_range_rerun": True} when an
     # activation left the fp16 range of the default kernels and the batch was re-run on the full-range bf16x6 kernels
     info: Optional[dict] = None
+    # extension: the structural screen of the final state (sample(screen=...); diffusion/screening.py) -- numpy arrays min_distance,
+    # pair, n_close, volume, number_density, flags and valid, one entry per crystal; None when no screen was asked for
+    metrics: Optional[dict] = None
 
 
 class _PinnedRing:
@@ -264,7 +268,7 @@ class DiffusionLoss(nn.Module):
                fixed_cell: bool = False, condition=None, num_steps: Optional[int] = None,
                timesteps: Optional[Sequence[int]] = None, corrector_steps: int = 0,
                corrector_snr: float = pc.DEFAULT_SNR, resample_passes: int = 1, jump_length: int = 10,
-               lattice_system=None, symmetry=None) -> SampleResult:
+               lattice_system=None, symmetry=None, screen=None) -> SampleResult:
         """diffusion_loss.py:276-377.  The initial state is drawn on the host exactly like the reference (numpy
         uniforms for the angles, then randn lengths, randn fractional coordinates from torch's global CPU generator).
         Per-step noise:
@@ -325,7 +329,13 @@ class DiffusionLoss(nn.Module):
         its site (anchored at the template's leader) and the members expanded, unwrapped.  Constant species must be constant
         per orbit.  Works with graph replay, respaced schedules, fixed cells, max_steps and frames; a condition, corrector steps,
         resampling and the host-noise modes are rejected.  None, or a sequence of None only, is the sampler as it was.  No
-        sample-quality claim is made."""
+        sample-quality claim is made.
+        `screen` (extension, every noise mode and option): a screening.ScreenCriteria, or True for its defaults -- the final
+        device state is screened in one launch before it is copied back (arreau_crystal_screen; rules in include/arreau_hip.h):
+        shortest contact over all periodic images, cell volume, number density, mask state.  SampleResult.metrics then holds the
+        six arrays and `valid`.  A criteria without a mask_type checks for the D3PM mask state S - 1, or for none when
+        constant_atoms is given.  None: no launch is added, metrics is None and the results are what they were, bit for bit."""
+        screen = screening.resolve(screen)
         frames = visualization_setting != VisualizationSetting.NONE
         if frames and not vis_name:
             raise ValueError("visualization_setting other than NONE needs vis_name (prefix of the frame files)")
@@ -563,6 +573,11 @@ class DiffusionLoss(nn.Module):
         if frames:
             vis_crystal_during_sampling(z_table, types_d.cpu().numpy(), lattice_d.cpu().numpy(), frac_d.cpu().numpy(),
                                         vis_name + "_final", show_bonds, num_atoms.numpy())
+        metrics = None
+        if screen is not None:  # the final state, where it is: one launch, then the host copies below
+            crit = screen.with_mask_type(-1 if constant_atoms is not None else S - 1)
+            metrics = screening.metrics_to_numpy(eng.screen(frac_d, lattice_d, off_d, types_d, crit))
         atomic_numbers = atomic_number_indexes_to_atomic_numbers(z_table, types_d.cpu().numpy())
         return SampleResult(num_atoms=num_atoms.numpy(), frac_x=frac_d.cpu().numpy().astype(np.float64),
-                            atomic_numbers=atomic_numbers, lattice=lattice_d.cpu().numpy().astype(np.float64), info=info)
+                            atomic_numbers=atomic_numbers, lattice=lattice_d.cpu().numpy().astype(np.float64), info=info,
+                            metrics=metrics)

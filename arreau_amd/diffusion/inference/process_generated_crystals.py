@@ -6,7 +6,12 @@ relaxation of the reference keep working on files written here.
 Layout (main_diffusion_generate.py:67-92): frac_x [sum n, 3] float64, atomic_numbers [sum n] float64 (the
 reference fills an `np.empty` float array), lattice [B, 3, 3] float64, idx_start [B] int64 (first atom of
 each crystal), num_atoms [B] int64.  HDF5 when h5py is importable (it is not in this image); `.npz`
-with the same five keys otherwise."""
+with the same five keys otherwise.
+
+A result that carries the structural screen's metrics (SampleResult.metrics, diffusion/screening.py) gets seven more arrays,
+one entry per crystal: screen_min_distance, screen_pair [B,5], screen_n_close, screen_volume, screen_number_density,
+screen_flags, screen_valid.  Readers of the five keys above are not affected; a result without metrics is written with
+exactly those five."""
 import os
 
 import numpy as np
@@ -14,6 +19,8 @@ import numpy as np
 from ..diffusion_loss import SampleResult
 
 KEYS = ("frac_x", "atomic_numbers", "lattice", "idx_start", "num_atoms")
+METRIC_KEYS = ("min_distance", "pair", "n_close", "volume", "number_density", "flags", "valid")
+METRIC_PREFIX = "screen_"
 _DTYPES = dict(frac_x=np.float64, atomic_numbers=np.float64, lattice=np.float64, idx_start=np.int64,
                num_atoms=np.int64)
 
@@ -30,7 +37,23 @@ def _fields(crystals: SampleResult):
     if out["frac_x"].shape != (n_tot, 3) or out["atomic_numbers"].shape != (n_tot,) or \
             out["lattice"].shape != (B, 3, 3) or out["idx_start"].shape != (B,):
         raise ValueError("SampleResult arrays do not have the crystals.h5 layout")
+    metrics = getattr(crystals, "metrics", None)
+    if metrics is not None:
+        for k in METRIC_KEYS:
+            if k not in metrics:
+                raise ValueError(f"SampleResult.metrics[{k!r}] is missing")
+            v = np.asarray(metrics[k])
+            if v.shape != ((B, 5) if k == "pair" else (B,)):
+                raise ValueError(f"SampleResult.metrics[{k!r}] does not hold one entry per crystal")
+            out[METRIC_PREFIX + k] = v
     return out
+
+
+def _metrics_from(has, get):
+    """The metrics dict of a file's screen_* arrays, or None when the file has none."""
+    if not all(has(METRIC_PREFIX + k) for k in METRIC_KEYS):
+        return None
+    return {k: get(METRIC_PREFIX + k) for k in METRIC_KEYS}
 
 
 def _is_h5(filename):
@@ -59,10 +82,12 @@ def load_sample_results_from_hdf5(filename: str) -> SampleResult:
         import h5py
         with h5py.File(filename, "r") as fh:
             data = {k: fh["crystals"][k][:] for k in KEYS}
+            metrics = _metrics_from(lambda k: k in fh["crystals"], lambda k: fh["crystals"][k][:])
     else:
         with np.load(filename) as z:
             data = {k: z[k] for k in KEYS}
-    return SampleResult(**data)
+            metrics = _metrics_from(lambda k: k in z.files, lambda k: z[k])
+    return SampleResult(**data, metrics=metrics)
 
 
 def get_crystal_indexes(sample_result: SampleResult, sample_idx: int):

@@ -16,6 +16,12 @@ def _f32(t):
     return t.detach().to("cpu", torch.float32).contiguous()
 
 
+def screen(frac, lattice, offsets, types=None, criteria=None):
+    """The structural screen without an engine (arreau_crystal_screen needs no model): diffusion.screening.screen."""
+    from .diffusion import screening
+    return screening.screen(frac, lattice, offsets, types, criteria)
+
+
 def pack_state(module):
     """(Config, host tensors, StateDict of their pointers) of a PONITA_DIFFUSION in the reference's state_dict layout: what
     arreau_model_create and arreau_calibrate_formats take.  Host side only; the tensors must outlive every use of the struct."""
@@ -636,6 +642,16 @@ class HipEngine:
             _hip.ptr(t_crystal), _hip.ptr(offsets), B, N, _hip.ptr(z_frac), _hip.ptr(z_lengths), _hip.ptr(u_types),
             _hip.ptr(const_types), _hip.ptr(fixed_lengths), ctypes.byref(cond) if cond is not None else None,
             _hip.ptr(lattice_out), _hip.stream_ptr(self.device)), "arreau_resample_jump")
+
+    def screen(self, frac, lattice, offsets, types=None, criteria=None):
+        """The structural screen of a batch on this engine's device (arreau_crystal_screen; diffusion/screening.py: `screen`,
+        which needs no engine): frac [N,3] f32, lattice [B,3,3] f32, offsets [B+1] i32, types [N] i32 or None, criteria a
+        ScreenCriteria (None: the defaults; mask_type None: no species check).  One launch on the current stream; returns the
+        dict of device tensors min_distance, pair, n_close, volume, number_density, flags, valid."""
+        from .diffusion import screening
+        if frac.device != self.device:
+            raise ValueError(f"screen: the state must be on {self.device}")
+        return screening.screen(frac, lattice, offsets, types, criteria)
 
     def edges_to_slots(self, edge_index, dists, direction, N):
         """Receiver-sorted COO edges -> slot form (deg, src, dir, dist)."""

@@ -27,6 +27,12 @@ Space-group symmetry: `--symops FILE` (one operation per line in xyz form, e.g. 
 `--lattice_system NAME` and exactly one of `--orbits K` (K orbits of general positions) or `--symmetry_template crystals.npz`
 (the first crystal's positions define the orbits) samples every crystal with its atoms in the orbits of the group the operations
 generate (DiffusionLoss.sample).  The spec decides the atom count (`--num_atoms` is not used).  Not with `--template`.
+
+Structural screen: `--screen` (thresholds `--min_distance`, `--min_volume`, `--search_radius`) screens every generated crystal on
+the device at the end of its sampling call -- shortest contact over all periodic images, cell volume, mask state
+(diffusion/screening.py) --, prints accepted / attempted and the count per flag for every rank and in total, and stores the
+metrics as screen_* arrays in the output file.  `--require_valid [--max_rounds R]` (implies --screen) keeps generating until every
+rank has its share of VALID crystals, or R rounds have passed (generate_valid_crystals); a shortfall is reported, not padded.
 """
 import argparse
 import os
@@ -44,17 +50,39 @@ def shard_range(num_items: int, world_size: int, rank: int):
     return start, start + base + (1 if rank < rem else 0)
 
 
+def _screen_stats(parts):
+    """The per-rank screen statistics the parts carry (SampleResult.info["screen_stats"]), in one list; None when none does."""
+    stats = [st for p in parts if p is not None and p.info for st in p.info.get("screen_stats", [])]
+    return {"screen_stats": stats} if stats else None
+
+
 def concat_results(parts) -> SampleResult:
-    """Crystal-order concatenation with the reference's index arrays (main_diffusion_generate.py:67-92)."""
+    """Crystal-order concatenation with the reference's index arrays (main_diffusion_generate.py:67-92).  The screen's metrics
+    are concatenated when every part has them, and the parts' screen statistics are collected."""
+    info = _screen_stats(parts)
     parts = [p for p in parts if p is not None and p.num_atoms is not None and len(p.num_atoms)]
     if not parts:
         return SampleResult(frac_x=np.empty((0, 3)), atomic_numbers=np.empty((0,)), lattice=np.empty((0, 3, 3)),
-                            idx_start=np.empty((0,), dtype=np.int64), num_atoms=np.empty((0,), dtype=np.int64))
+                            idx_start=np.empty((0,), dtype=np.int64), num_atoms=np.empty((0,), dtype=np.int64), info=info)
     num_atoms = np.concatenate([np.asarray(p.num_atoms) for p in parts])
+    metrics = None
+    if all(p.metrics is not None for p in parts):
+        metrics = {k: np.concatenate([np.asarray(p.metrics[k]) for p in parts]) for k in parts[0].metrics}
     return SampleResult(
         frac_x=np.concatenate([p.frac_x for p in parts]), atomic_numbers=np.concatenate([p.atomic_numbers for p in parts]),
         lattice=np.concatenate([p.lattice for p in parts]), num_atoms=num_atoms,
-        idx_start=np.cumsum(num_atoms) - num_atoms)
+        idx_start=np.cumsum(num_atoms) - num_atoms, info=info, metrics=metrics)
+
+
+def select_crystals(res: SampleResult, keep) -> SampleResult:
+    """The crystals of `res` where keep [B] is true, in their order (atoms, cells, metrics; idx_start rebuilt)."""
+    keep = np.asarray(keep, dtype=bool).reshape(-1)
+    num_atoms = np.asarray(res.num_atoms, dtype=np.int64)
+    atoms = np.repeat(keep, num_atoms)
+    kept = num_atoms[keep]
+    metrics = None if res.metrics is None else {k: np.asarray(v)[keep] for k, v in res.metrics.items()}
+    return SampleResult(frac_x=np.asarray(res.frac_x)[atoms], atomic_numbers=np.asarray(res.atomic_numbers)[atoms],
+                        lattice=np.asarray(res.lattice)[keep], num_atoms=kept, idx_start=np.cumsum(kept) - kept, metrics=metrics)
 
 
 FIX_KINDS = ("positions", "species", "lattice")
@@ -97,6 +125,9 @@ def template_batches(num_crystals: int, batch: int, rank: int = 0, world_size: i
 
 
 def _gather_results(local: SampleResult, rank: int, world_size: int, gather: Optional[Callable]):
+    if local.metrics is not None and not (local.info or {}).get("screen_stats"):  # a screened run: this rank's statistics
+        from .diffusion.screening import stats_of
+        local.info = dict(local.info or {}, screen_stats=[stats_of(local.metrics["flags"], rank)])
     if world_size == 1:
         return local
     if gather is None:
@@ -128,6 +159,43 @@ def generate_n_crystals(sample_fn: Callable[[int, int], SampleResult], num_cryst
     for s in range(start, stop, num_crystals_per_batch):
         mine.append(sample_fn(num_atoms_per_sample, min(num_crystals_per_batch, stop - s)))
     return _gather_results(concat_results(mine), rank, world_size, gather)
+
+
+def generate_valid_crystals(sample_fn: Callable[[int, int], SampleResult], num_crystals: int, num_atoms_per_sample: int,
+                            num_crystals_per_batch: int = 256, rank: int = 0, world_size: int = 1,
+                            gather: Optional[Callable] = None, max_rounds: int = 10) -> Optional[SampleResult]:
+    """generate_n_crystals that returns VALID crystals only.  sample_fn(num_atoms_per_sample, num_samples_in_batch) ->
+    SampleResult WITH metrics (e.g. PONITA_DIFFUSION.sample(..., screen=criteria)).  Every rank refills its own shard_range slice: in
+    each round it samples as many crystals as it still misses (in sub-batches of at most num_crystals_per_batch), keeps the
+    valid ones in generation order, and stops when the slice is full or after `max_rounds` rounds.  Ranks do not talk to each
+    other until the final gather, so a rank's crystals depend on its own generator state alone.  A shortfall is warned about
+    and left in the statistics (SampleResult.info["screen_stats"], one entry per rank: attempted, accepted, the count per flag
+    over every attempt, requested, rounds); nothing is padded."""
+    import warnings
+
+    from .diffusion.screening import stats_of
+    if int(max_rounds) < 1:
+        raise ValueError(f"max_rounds must be >= 1, got {max_rounds}")
+    start, stop = shard_range(num_crystals, world_size, rank)
+    want, kept, flags, have, rounds = stop - start, [], [], 0, 0
+    while have < want and rounds < int(max_rounds):
+        rounds += 1
+        missing = want - have
+        for s in range(0, missing, num_crystals_per_batch):
+            res = sample_fn(num_atoms_per_sample, min(num_crystals_per_batch, missing - s))
+            if res.metrics is None:
+                raise ValueError("generate_valid_crystals: sample_fn must return the screen's metrics (sample(..., screen=...))")
+            flags.append(np.asarray(res.metrics["flags"]))
+            good = select_crystals(res, res.metrics["valid"])
+            kept.append(good)
+            have += len(good.num_atoms)
+    local = concat_results(kept)
+    local.info = {"screen_stats": [stats_of(np.concatenate(flags) if flags else np.empty(0, np.int64), rank, requested=want,
+                                            rounds=rounds)]}
+    if have < want:
+        warnings.warn(f"generate_valid_crystals: rank {rank} has {have} valid crystals of the {want} requested after {rounds} "
+                      f"round(s); the result is {want - have} short")
+    return _gather_results(local, rank, world_size, gather)
 
 
 def save_sample_results(crystals: SampleResult, filename: str):
@@ -199,7 +267,41 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--orbits", type=int, default=None, help="space-group symmetry: K orbits of general positions")
     ap.add_argument("--symmetry_template", type=str, default=None,
                     help="space-group symmetry: crystals.npz / .h5 whose first crystal's positions define the orbits")
+    add_screen_arguments(ap)
+    ap.add_argument("--screen", action="store_true",
+                    help="screen every generated crystal on the device (shortest contact, cell volume, mask state): summary + "
+                         "screen_* arrays in the output file")
+    ap.add_argument("--require_valid", action="store_true",
+                    help="keep generating until every rank has its share of valid crystals (implies --screen; not with --template)")
+    ap.add_argument("--max_rounds", type=int, default=10, help="--require_valid: refill rounds per rank (>= 1)")
     return ap
+
+
+def add_screen_arguments(ap):
+    """The criteria flags shared with `python -m arreau_amd.screen`."""
+    ap.add_argument("--min_distance", type=float, default=0.5, help="screen: contacts below this many A are CLOSE")
+    ap.add_argument("--min_volume", type=float, default=0.1, help="screen: cells below this many A^3 are flagged CELL")
+    ap.add_argument("--search_radius", type=float, default=3.0, help="screen: periodic images are searched out to this many A")
+
+
+def screen_criteria(args, error):
+    """The ScreenCriteria of the criteria flags; `error(message)` reports a bad value."""
+    from .diffusion.screening import ScreenCriteria
+    try:
+        return ScreenCriteria(min_distance=args.min_distance, min_volume=args.min_volume, search_radius=args.search_radius)
+    except ValueError as e:
+        error(f"screen criteria: {e}")
+
+
+def check_screen_arguments(args, error):
+    """The ScreenCriteria --screen / --require_valid ask for, or None; `error(message)` reports a bad combination."""
+    if args.require_valid and args.template is not None:
+        error("--require_valid cannot be combined with --template (conditioned generation)")
+    if args.max_rounds < 1:
+        error("--max_rounds must be >= 1")
+    if not (args.screen or args.require_valid):
+        return None
+    return screen_criteria(args, error)
 
 
 def load_symmetry(args, error):
@@ -240,6 +342,7 @@ def main():
     ap = build_parser()
     args = ap.parse_args()
     spec = load_symmetry(args, ap.error)
+    criteria = check_screen_arguments(args, ap.error)
     condition = load_template(args.template, parse_fix(args.fix)).tile(args.samples_per_template) if args.template else None
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -275,7 +378,7 @@ def main():
             return model.sample(n, b, VisualizationSetting.NONE, False, condition=cond, num_steps=args.num_steps,
                                 corrector_steps=args.corrector_steps, corrector_snr=args.corrector_snr,
                                 resample_passes=args.resample_passes, jump_length=args.jump_length,
-                                lattice_system=args.lattice_system, symmetry=spec)
+                                lattice_system=args.lattice_system, symmetry=spec, screen=criteria)
         import fcntl
         with open(lock_path, "a") as lock:
             fcntl.flock(lock, fcntl.LOCK_EX)
@@ -283,17 +386,24 @@ def main():
                 out = model.sample(n, b, VisualizationSetting.NONE, False, condition=cond, num_steps=args.num_steps,
                                 corrector_steps=args.corrector_steps, corrector_snr=args.corrector_snr,
                                 resample_passes=args.resample_passes, jump_length=args.jump_length,
-                                lattice_system=args.lattice_system, symmetry=spec)
+                                lattice_system=args.lattice_system, symmetry=spec, screen=criteria)
                 torch.cuda.synchronize()
                 return out
             finally:
                 fcntl.flock(lock, fcntl.LOCK_UN)
     if condition is not None:
         res = generate_from_template(lambda c: fn(None, None, c), condition, args.batch, rank, world)
+    elif args.require_valid:
+        res = generate_valid_crystals(fn, args.num_crystals, spec.n_atoms if spec is not None else args.num_atoms, args.batch, rank,
+                                      world, max_rounds=args.max_rounds)
     else:
         res = generate_n_crystals(fn, args.num_crystals, spec.n_atoms if spec is not None else args.num_atoms, args.batch, rank,
                                   world)
     if rank == 0:
+        if criteria is not None:
+            from .diffusion.screening import summary_lines
+            for line in summary_lines((res.info or {}).get("screen_stats", [])):
+                print(line)
         print("wrote", save_sample_results(res, args.out))
     if world > 1:
         dist.destroy_process_group()

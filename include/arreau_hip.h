@@ -226,6 +226,71 @@ int arreau_edges_to_slots(const int64_t* d_edge_index /*[2,E]*/, const float* d_
                           int32_t* d_deg, int32_t* d_src, float* d_slot_dir, float* d_slot_dist,
                           int32_t* d_status, void* stream);
 
+/* ---- structural screen of generated crystals ---------------------------------------------------------------------
+ * Per crystal: the shortest interatomic contact over every periodic image within a search radius, the cell volume and the
+ * mask state, against thresholds (the validity screen of CDVAE / DiffCSP / MatterGen; the reference has no counterpart, its
+ * post-processing assumes filtered input).  An exact search of its own -- arreau_radius_graph_pbc looks at 27 images only,
+ * stops at k and skips d^2 <= 1e-4.  One launch, one workgroup of four waves per crystal, no atomics, no second stream, no
+ * arreau_model.  Every arithmetic step below is ONE float32 operation rounded to nearest, in the order written, never
+ * contracted to a fused multiply-add, so a float32 host restatement (arreau_amd/diffusion/screening.py) matches bit for bit.
+ *   1. cell (rows a_0, a_1, a_2 of d_lattice): c_0 = a_1 x a_2, c_1 = a_2 x a_0, c_2 = a_0 x a_1, each component
+ *      u_p v_q - u_q v_p; det = (a_0x c_0x + a_0y c_0y) + a_0z c_0z; volume = |det|; |c_k| = sqrt((c_kx^2 + c_ky^2) + c_kz^2);
+ *      plane spacing h_k = volume / |c_k|; number_density = n / volume (n atoms); q_k = search_radius / h_k.
+ *   2. NONFINITE: a cell entry or a coordinate of the crystal is inf / NaN.  Nothing else is computed: the three reals are
+ *      NaN, pair is -1, n_close 0, no other flag.
+ *   3. CELL: not (volume >= min_volume), volume not finite, or not (q_k <= max_shells) for an axis.  The search is skipped:
+ *      min_distance is NaN, pair -1, n_close 0; volume, number_density and MASKED are still reported.
+ *   4. images per axis n_k = max(1, ceil(q_k)), shifts (n_1, n_2, n_3) with |n_k'| <= n_k in lexicographic order, index
+ *      m = ((n_1 + N_1)(2 N_2 + 1) + (n_2 + N_2))(2 N_3 + 1) + (n_3 + N_3).  Two wrapped positions differ by less than one
+ *      cell along every axis and a displacement of length <= R has a fractional component of at most R / h_k, so this
+ *      range contains every pair within search_radius for any cell shape.
+ *   5. positions: w = f - floor(f), a result >= 1 becomes 0; p_d = (w_0 L_0d + w_1 L_1d) + w_2 L_2d -- the expression of
+ *      frac_to_cart_coords, on the wrapped coordinates.  Kept in LDS for crystals of up to 256 atoms; larger crystals form
+ *      them from global memory where they are used (the same values).
+ *   6. contacts: pairs i <= j (local atom indices); for i < j every shift, for i == j only the shifts after (0, 0, 0) in
+ *      the order of 4 (an atom meets its own images, each once, never itself).  s_d = (n_1 L_0d + n_2 L_1d) + n_3 L_2d,
+ *      disp = (p_j + s) - p_i, d2 = (dx dx + dy dy) + dz dz.
+ *   7. the reported contact is the smallest by the key (bits of d2, i, j, m): among equal float32 d2 the smaller i, then the
+ *      smaller j, then the earlier shift.  min_distance = sqrt(d2) (correctly rounded); pair = (i, j, n_1, n_2, n_3).
+ *      n_close = the number of contacts with d2 < (float)((double)min_distance * min_distance) -- unordered contacts, each
+ *      counted once.  The reduction is a wave minimum over the key, then the four waves through LDS: deterministic.
+ *   8. flags: CLOSE n_close > 0;  MASKED d_types given, mask_type >= 0 and an atom of the crystal has it;  BEYOND not
+ *      (d2_min <= (float)((double)search_radius * search_radius)) -- no contact within the search radius; min_distance is
+ *      then the minimum over the enumerated images, an upper bound of the true one only (informational).  A crystal without
+ *      atoms has no contact: min_distance +inf, pair -1, BEYOND.  A crystal is VALID when (flags & 15) == 0.
+ * Limits: at most 2^24 atoms in one crystal (the key holds i and j in 24 bits each; not checked).  Offsets outside [0, N] or
+ * descending are clamped, so a bad table reads no memory outside the arrays.
+ * Argument errors (ARREAU_EINVAL, nothing launched): NULL criteria / result / arrays, negative sizes, a threshold that is
+ * not finite or negative, search_radius <= 0 or below min_distance, max_shells outside 1..ARREAU_SCREEN_MAX_SHELLS,
+ * mask_type < -1. */
+#define ARREAU_SCREEN_NONFINITE 1
+#define ARREAU_SCREEN_CELL 2
+#define ARREAU_SCREEN_CLOSE 4
+#define ARREAU_SCREEN_MASKED 8
+#define ARREAU_SCREEN_BEYOND 16
+#define ARREAU_SCREEN_INVALID_MASK 15
+#define ARREAU_SCREEN_MAX_SHELLS 8
+typedef struct arreau_screen_criteria {
+    float min_distance;   /* A; default 0.5 */
+    float min_volume;     /* A^3; default 0.1 */
+    float search_radius;  /* A; default 3.0, at least min_distance */
+    int32_t mask_type;    /* class index of the D3PM mask state, -1: none */
+    int32_t max_shells;   /* cap on the images per axis, 1..ARREAU_SCREEN_MAX_SHELLS; default 8 */
+} arreau_screen_criteria;
+typedef struct arreau_screen_result { /* DEVICE arrays, one entry per crystal */
+    float* min_distance;    /* [B]   */
+    int32_t* pair;          /* [B,5] i, j (local to the crystal), n_1, n_2, n_3 */
+    int32_t* n_close;       /* [B]   */
+    float* volume;          /* [B]   */
+    float* number_density;  /* [B]   */
+    int32_t* flags;         /* [B]   ARREAU_SCREEN_* */
+} arreau_screen_result;
+/* d_frac[N,3] fractional coordinates (any real: wrapped by rule 5), d_types[N] class indices (may be NULL: no species check),
+ * d_lattice[B,3,3] rows a, b, c.  `crit` and `out` are HOST pointers to the structs; the arrays `out` names are device arrays. */
+int arreau_crystal_screen(const float* d_frac, const int32_t* d_types /* may be NULL */, const float* d_lattice /* [B,3,3] rows a,b,c */,
+                          const int32_t* d_crystal_offsets, int32_t B, int32_t N, const arreau_screen_criteria* crit,
+                          arreau_screen_result* out /* device arrays, each [B] (pair: [B,5]) */, void* stream);
+
 /* ---- the score network ---------------------------------------------------------------------- */
 
 /* One evaluation of DiffusionLoss.predict_scores (diffusion/diffusion_loss.py:112-197):
