@@ -118,6 +118,73 @@ class StateDict(Structure):
     _fields_ = [(name, c_void_p) for name in _SD_FIELDS]
 
 
+def _prototypes():
+    """{symbol: argtypes} of every export.  Each sampling entry point is the one before it plus one option in front of the stream."""
+    vp, i32, i64, u32, u64, f32, f64 = c_void_p, c_int32, c_int64, ctypes.c_uint32, ctypes.c_uint64, c_float, c_double
+    cond, sched, corr, res, sym = (POINTER(t) for t in (SampleConditionC, SampleScheduleC, CorrectorC, ResamplingC, SymmetryC))
+    loop = [vp] * 6 + [i32] * 4 + [u64] + [vp] * 4 + [c_size_t, i32]
+    step_to = [vp] * 8 + [i32, i32] + [vp] * 7 + [f32]
+    jump = [vp] * 8 + [i32, i32] + [vp] * 5 + [cond, vp]
+    adam = [vp] * 4 + [POINTER(AdamArgs), vp]
+    return {
+        "arreau_last_error": [], "arreau_version": [],
+        "arreau_model_create": [POINTER(Config), POINTER(StateDict), vp, POINTER(vp)],
+        "arreau_model_destroy": [vp],
+        "arreau_model_config": [vp, POINTER(Config)],
+        "arreau_workspace_bytes": [POINTER(Config), i64, i64],
+        "arreau_lattice_from_params": [vp, vp, i32, vp, vp],
+        "arreau_frac_to_cart": [vp, vp, vp, i32, i32, vp, vp],
+        "arreau_radius_graph_pbc": [vp, vp, vp, i32, i32, f32, i32] + [vp] * 6,
+        "arreau_compact_edges": [vp] * 5 + [i32, i32] + [vp] * 6,
+        "arreau_edges_to_slots": [vp, vp, vp, i64, i32, i32] + [vp] * 6,
+        "arreau_predict_scores": [vp] * 7 + [i32, i32, i32] + [vp] * 7 + [vp, c_size_t, vp],
+        "arreau_reverse_step": [vp] * 7 + [i32, i32] + [vp] * 8,
+        "arreau_model_status": [vp, POINTER(Status), i32, vp],
+        "arreau_model_set_variant": [vp, i32, i32],
+        "arreau_model_set_formats": [vp, i32, i32],
+        "arreau_ponita_forward": [vp] * 5 + [i32, i32] + [vp] * 7 + [vp, c_size_t, vp],
+        "arreau_diffusion_noise": [vp] * 6 + [i32, i32] + [vp] * 11,
+        "arreau_diffusion_losses": [vp] * 10 + [i32, i32] + [vp] * 6,
+        "arreau_sample_loop": loop + [vp],
+        "arreau_sample_loop_conditioned": loop + [cond, vp],
+        "arreau_sample_loop_scheduled": loop + [cond, sched, vp],
+        "arreau_sample_loop_corrected": loop + [cond, sched, corr, vp],
+        "arreau_sample_loop_resampled": loop + [cond, sched, corr, res, vp],
+        "arreau_sample_loop_tied": loop + [cond, sched, corr, res, vp, vp],
+        "arreau_sample_loop_sym": loop + [cond, sched, corr, res, vp, sym, vp],
+        "arreau_condition_initial_state": [vp] * 4 + [i32, i32, i32, u64, cond, vp],
+        "arreau_reverse_step_to": step_to + [vp],
+        "arreau_reverse_step_tied": step_to + [vp, vp],
+        "arreau_reverse_step_sym": step_to + [vp, sym, vp],
+        "arreau_corrector_step": [vp] * 4 + [i32, i32, vp, vp, f32, cond, vp],
+        "arreau_resample_jump": jump + [vp],
+        "arreau_resample_jump_tied": jump + [vp, vp],
+        "arreau_philox_fill": [u64, i32, i32, i64, vp, vp, vp],
+        "arreau_philox_fill_word": [u64, i32, i32, u32, i64, vp, vp, vp],
+        "arreau_crystal_screen": [vp] * 4 + [i32, i32, POINTER(ScreenCriteriaC), POINTER(ScreenResultC), vp],
+        "arreau_train_forward": [vp] * 7 + [i32, i32] + [vp] * 4,
+        "arreau_train_backward": [vp] * 4 + [POINTER(StateDict), vp],
+        "arreau_train_conv_stats": [vp, vp, vp],
+        "arreau_debug_sgemm": [i32, i32, i32, i32, vp, i64, i64, vp, i64, i64, vp, i32, f32, f32, vp],
+        "arreau_model_update_train_weights": [vp, POINTER(StateDict), vp],
+        "arreau_model_train_weight_pointers": [vp, POINTER(StateDict)],
+        "arreau_model_refresh_derived_train_weights": [vp, vp, vp, vp],
+        "arreau_optimizer_create": [i32, POINTER(vp), POINTER(vp), POINTER(i64), POINTER(i64), POINTER(i32), i32, i64, POINTER(vp)],
+        "arreau_optimizer_step": adam + [vp],
+        "arreau_optimizer_step_ema": adam + [f64, vp, vp],
+        "arreau_optimizer_destroy": [vp],
+        "arreau_debug_set_pollution": [u32],
+        "arreau_debug_leftover_fraction": [u32, POINTER(f64), POINTER(f64), vp],
+        "arreau_profile_edge_kernel": [i32],
+        "arreau_edge_kernel_time_ms": [POINTER(f64), POINTER(i64)],
+        "arreau_conv_kernel_time_ms": [POINTER(f64), POINTER(i64)],
+    }
+
+
+# every other export returns the int32 error code
+_RESTYPES = {"arreau_last_error": c_char_p, "arreau_version": c_char_p, "arreau_model_destroy": None,
+             "arreau_workspace_bytes": c_size_t, "arreau_optimizer_destroy": None}
+
 _lib = None
 
 
@@ -131,91 +198,14 @@ def lib():
             f"{LIB_PATH} not found: build it with `python -m arreau_amd.build` (hipcc, gfx950). "
             "arreau_amd has no CPU fallback.")
     L = ctypes.CDLL(LIB_PATH)
-    L.arreau_last_error.restype = c_char_p
-    L.arreau_version.restype = c_char_p
-    L.arreau_model_create.argtypes = [POINTER(Config), POINTER(StateDict), c_void_p, POINTER(c_void_p)]
-    L.arreau_model_destroy.argtypes = [c_void_p]
-    L.arreau_model_destroy.restype = None
-    L.arreau_model_config.argtypes = [c_void_p, POINTER(Config)]
-    L.arreau_workspace_bytes.argtypes = [POINTER(Config), c_int64, c_int64]
-    L.arreau_workspace_bytes.restype = c_size_t
-    L.arreau_lattice_from_params.argtypes = [c_void_p, c_void_p, c_int32, c_void_p, c_void_p]
-    L.arreau_frac_to_cart.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]
-    L.arreau_radius_graph_pbc.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_float, c_int32,
-                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-    L.arreau_compact_edges.argtypes = [c_void_p] * 5 + [c_int32, c_int32] + [c_void_p] * 6
-    L.arreau_edges_to_slots.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32] + [c_void_p] * 6
-    L.arreau_predict_scores.argtypes = ([c_void_p] * 7 + [c_int32, c_int32, c_int32] + [c_void_p] * 7 +
-                                        [c_void_p, c_size_t, c_void_p])
-    L.arreau_reverse_step.argtypes = [c_void_p] * 7 + [c_int32, c_int32] + [c_void_p] * 8
-    L.arreau_model_status.argtypes = [c_void_p, POINTER(Status), c_int32, c_void_p]
-    L.arreau_model_set_variant.argtypes = [c_void_p, c_int32, c_int32]
-    L.arreau_ponita_forward.argtypes = ([c_void_p] * 5 + [c_int32, c_int32] + [c_void_p] * 7 +
-                                        [c_void_p, c_size_t, c_void_p])
-    L.arreau_diffusion_noise.argtypes = [c_void_p] * 6 + [c_int32, c_int32] + [c_void_p] * 11
-    L.arreau_diffusion_losses.argtypes = [c_void_p] * 10 + [c_int32, c_int32] + [c_void_p] * 6
-    L.arreau_sample_loop.argtypes = ([c_void_p] * 6 + [c_int32, c_int32, c_int32, c_int32, ctypes.c_uint64] +
-                                     [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int32, c_void_p])
-    if hasattr(L, "arreau_sample_loop_conditioned") or not os.environ.get("ARREAU_HIP_LIB"):  # (an older build under test)
-        L.arreau_sample_loop_conditioned.argtypes = (L.arreau_sample_loop.argtypes[:-1] + [POINTER(SampleConditionC), c_void_p])
-        L.arreau_condition_initial_state.argtypes = ([c_void_p] * 4 + [c_int32, c_int32, c_int32, ctypes.c_uint64] +
-                                                     [POINTER(SampleConditionC), c_void_p])
-    if hasattr(L, "arreau_sample_loop_scheduled") or not os.environ.get("ARREAU_HIP_LIB"):  # (an older build under test)
-        L.arreau_sample_loop_scheduled.argtypes = (L.arreau_sample_loop_conditioned.argtypes[:-1] +
-                                                   [POINTER(SampleScheduleC), c_void_p])
-        L.arreau_reverse_step_to.argtypes = [c_void_p] * 8 + [c_int32, c_int32] + [c_void_p] * 7 + [ctypes.c_float, c_void_p]
-    if hasattr(L, "arreau_sample_loop_corrected") or not os.environ.get("ARREAU_HIP_LIB"):  # (an older build under test)
-        L.arreau_sample_loop_corrected.argtypes = (L.arreau_sample_loop_scheduled.argtypes[:-1] +
-                                                   [POINTER(CorrectorC), c_void_p])
-        L.arreau_corrector_step.argtypes = [c_void_p] * 4 + [c_int32, c_int32] + [c_void_p] * 2 + [ctypes.c_float,
-                                                                                                   POINTER(SampleConditionC), c_void_p]
-        L.arreau_philox_fill_word.argtypes = [ctypes.c_uint64, c_int32, c_int32, ctypes.c_uint32, c_int64, c_void_p, c_void_p,
-                                              c_void_p]
-    if hasattr(L, "arreau_sample_loop_resampled") or not os.environ.get("ARREAU_HIP_LIB"):  # (an older build under test)
-        L.arreau_sample_loop_resampled.argtypes = (L.arreau_sample_loop_corrected.argtypes[:-1] +
-                                                   [POINTER(ResamplingC), c_void_p])
-        L.arreau_resample_jump.argtypes = [c_void_p] * 8 + [c_int32, c_int32] + [c_void_p] * 5 + [POINTER(SampleConditionC),
-                                                                                                   c_void_p, c_void_p]
-    if hasattr(L, "arreau_sample_loop_tied") or not os.environ.get("ARREAU_HIP_LIB"):  # (an older build under test)
-        L.arreau_sample_loop_tied.argtypes = L.arreau_sample_loop_resampled.argtypes[:-1] + [c_void_p, c_void_p]
-        L.arreau_reverse_step_tied.argtypes = L.arreau_reverse_step_to.argtypes[:-1] + [c_void_p, c_void_p]
-        L.arreau_resample_jump_tied.argtypes = L.arreau_resample_jump.argtypes[:-1] + [c_void_p, c_void_p]
-    if hasattr(L, "arreau_sample_loop_sym") or not os.environ.get("ARREAU_HIP_LIB"):  # (an older build under test)
-        L.arreau_sample_loop_sym.argtypes = L.arreau_sample_loop_tied.argtypes[:-1] + [POINTER(SymmetryC), c_void_p]
-        L.arreau_reverse_step_sym.argtypes = L.arreau_reverse_step_tied.argtypes[:-1] + [POINTER(SymmetryC), c_void_p]
-    if hasattr(L, "arreau_crystal_screen") or not os.environ.get("ARREAU_HIP_LIB"):  # (an older build under test)
-        L.arreau_crystal_screen.argtypes = [c_void_p] * 4 + [c_int32, c_int32, POINTER(ScreenCriteriaC), POINTER(ScreenResultC), c_void_p]
-    L.arreau_philox_fill.argtypes = [ctypes.c_uint64, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_void_p]
-    L.arreau_train_forward.argtypes = [c_void_p] * 7 + [c_int32, c_int32] + [c_void_p] * 4
-    L.arreau_train_backward.argtypes = [c_void_p] * 4 + [POINTER(StateDict), c_void_p]
-    L.arreau_train_conv_stats.argtypes = [c_void_p, c_void_p, c_void_p]
-    L.arreau_debug_sgemm.argtypes = [c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int32,
-                                     c_float, c_float, c_void_p]
-    L.arreau_model_update_train_weights.argtypes = [c_void_p, POINTER(StateDict), c_void_p]
-    if hasattr(L, "arreau_model_set_formats") or not os.environ.get("ARREAU_HIP_LIB"):  # (an older build under test: tools/ab.sh)
-        L.arreau_model_set_formats.argtypes = [c_void_p, c_int32, c_int32]
-    if hasattr(L, "arreau_optimizer_create") or not os.environ.get("ARREAU_HIP_LIB"):
-        L.arreau_optimizer_create.argtypes = [c_int32, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int64), POINTER(c_int64), POINTER(c_int32),
-                                              c_int32, c_int64, POINTER(c_void_p)]
-        L.arreau_model_train_weight_pointers.argtypes = [c_void_p, POINTER(StateDict)]
-        L.arreau_model_refresh_derived_train_weights.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
-        L.arreau_optimizer_step.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(AdamArgs), c_void_p, c_void_p]
-        L.arreau_optimizer_destroy.argtypes = [c_void_p]
-        L.arreau_optimizer_destroy.restype = None
-    if hasattr(L, "arreau_optimizer_step_ema") or not os.environ.get("ARREAU_HIP_LIB"):  # (an older build under test)
-        L.arreau_optimizer_step_ema.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(AdamArgs), c_void_p, c_double, c_void_p,
-                                                c_void_p]
-    L.arreau_debug_set_pollution.argtypes = [ctypes.c_uint32]
-    L.arreau_debug_leftover_fraction.argtypes = [ctypes.c_uint32, POINTER(c_double), POINTER(c_double), c_void_p]
-    L.arreau_profile_edge_kernel.argtypes = [c_int32]
-    L.arreau_edge_kernel_time_ms.argtypes = [POINTER(c_double), POINTER(c_int64)]
-    L.arreau_conv_kernel_time_ms.argtypes = [POINTER(c_double), POINTER(c_int64)]
+    prototypes = _prototypes()
     for name in EXPORTS:
+        # a missing symbol is tolerated only in another build loaded through ARREAU_HIP_LIB (an older one under test: tools/ab.sh)
         if os.environ.get("ARREAU_HIP_LIB") and not hasattr(L, name):
             continue
         fn = getattr(L, name)
-        if fn.restype is ctypes.c_int:
-            fn.restype = c_int32
+        fn.argtypes = prototypes[name]
+        fn.restype = _RESTYPES.get(name, c_int32)
     _lib = L
     return L
 

@@ -1,8 +1,8 @@
 // arreau_predict_scores: one evaluation of the score network on the current sampler state, plus the
 // workspace carve-up and the hipEvent timing hook for the dominant (edge) kernel.
 #include <stdlib.h>
-#include <string.h>
 
+#include <bit>
 #include <mutex>
 #include <vector>
 
@@ -298,57 +298,42 @@ bool loop_without_prep(const arreau_model* m) {
     return !(e && atoi(e) != 0) && !arreau_general_path(m);
 }
 
-// Predictor-corrector sampling (arreau_sample_loop_corrected): M corrector moves at the step's timestep come before the
-// predictor, each after a full network evaluation on the current state.  Only the first evaluation of a step advances the
-// device timestep; the later ones rebuild the neighbour list and the per-atom embedding from the moved positions at the same
-// timestep.  The lattice and the per-crystal embedding stay valid: a corrector moves fractional coordinates only.
-struct CorrectorDev {
-    int steps;  // M (0: the plain step)
-    float snr;
-};
-
-int enqueue_sample_step(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
-                        const int32_t* d_off, int B, int N, uint64_t seed, const int32_t* d_const_types,
-                        const float* d_fixed_lengths, float* d_lattice, const Workspace& w, hipStream_t s, bool no_prep,
-                        const SampleConditionDev* cond, const StepScheduleDev* sched, CorrectorDev corr,
-                        const int32_t* pass /* resampled loop: the device word of the pass index (RESAMPLE instances), or null */,
-                        const int32_t* length_tie /* lattice systems: the tie codes (TIE instances), or null */,
-                        const arreau_symmetry* sym /* space-group symmetry: the orbit tables (SYM instances), or null */) {
+// Predictor-corrector sampling (arreau_sample_loop_corrected, opt.corr): only the first evaluation of a step advances the device
+// timestep; the later ones rebuild the neighbour list and the per-atom embedding from the moved positions at the same timestep.
+// The lattice and the per-crystal embedding stay valid: a corrector moves fractional coordinates only.
+int enqueue_sample_step(const arreau_model* m, const SampleState& st, const Workspace& w, hipStream_t s, bool no_prep, uint64_t seed,
+                        const StepOptions& opt) {
     int rc;
-    const int32_t* next_t = sched ? sched->next : nullptr;  // respaced loop: the device timestep follows the table
-    if (no_prep) {
-        for (int j = 0; j <= corr.steps; ++j) {
-            if ((rc = arreau_launch_neighbor_embed(m, nullptr, w.lattice, d_off, w.batch, B, N, w.deg, w.src, w.cell, w.dir, w.dist, d_frac,
-                                                   d_types, w.cvec, w.xa, s, w.t_cur, next_t, /*advance=*/j == 0)))
-                return rc;
-            if ((rc = run_edge_kernel(m, w.dir, w.dist, w.deg, w, N, s))) return rc;
-            if ((rc = run_layers_and_readout(m, w, w.deg, w.src, d_off, B, N, w.eps, w.logits, nullptr, s))) return rc;
-            if (j < corr.steps &&
-                (rc = arreau_launch_corrector(m, d_frac, w.t_cur, d_off, B, N, w.eps, nullptr, seed, (uint32_t)j, corr.snr, cond, s, pass)))
-                return rc;
-        }
-        return arreau_launch_reverse(m, d_frac, d_types, d_lengths, d_angles, w.t_cur, d_off, B, N, w.eps, w.logits, w.len0,
-                                     StepNoiseSrc{nullptr, nullptr, nullptr, seed}, d_const_types, d_lattice, s, d_fixed_lengths,
-                                     w.gs, w.batch, w.lattice, w.cvec, cond, sched, pass, length_tie, sym);
-    }
+    const int32_t* next_t = opt.sched ? opt.sched->next : nullptr;  // respaced loop: the device timestep follows the table
     // fused kernels: the per-crystal pooling of the lattice read-out happens inside the lattice update (no launch of its own)
     const bool pool_in_update = !arreau_general_path(m);
-    for (int j = 0; j <= corr.steps; ++j) {
-        // the first set-up of the step advances the device timestep; a corrector's re-evaluation reads it (t_cur)
-        if ((rc = j == 0 ? arreau_launch_prep(m, d_frac, d_lengths, d_angles, nullptr, d_off, B, N, w.lattice, w.cart, w.batch, w.cvec, s,
-                                              w.t_next, w.t_cur, 0, next_t)
-                         : arreau_launch_prep(m, d_frac, d_lengths, d_angles, w.t_cur, d_off, B, N, w.lattice, w.cart, w.batch, w.cvec, s)))
-            return rc;
-        if ((rc = run_network(m, w, false, w.deg, w.src, w.dir, w.dist, d_frac, d_types, d_off, B, N, w.eps, w.logits,
-                              pool_in_update ? nullptr : w.len0, s)))
-            return rc;
-        if (j < corr.steps &&
-            (rc = arreau_launch_corrector(m, d_frac, w.t_cur, d_off, B, N, w.eps, nullptr, seed, (uint32_t)j, corr.snr, cond, s, pass)))
-            return rc;
+    for (int j = 0; j <= opt.corr.steps; ++j) {
+        if (no_prep) {
+            if ((rc = arreau_launch_neighbor_embed(m, nullptr, w.lattice, st.offsets, w.batch, st.B, st.N, w.deg, w.src, w.cell, w.dir, w.dist,
+                                                   st.frac, st.types, w.cvec, w.xa, s, w.t_cur, next_t, /*advance=*/j == 0)))
+                return rc;
+            if ((rc = run_edge_kernel(m, w.dir, w.dist, w.deg, w, st.N, s))) return rc;
+            if ((rc = run_layers_and_readout(m, w, w.deg, w.src, st.offsets, st.B, st.N, w.eps, w.logits, nullptr, s))) return rc;
+        } else {
+            // the first set-up of the step advances the device timestep; a corrector's re-evaluation reads it (t_cur)
+            if ((rc = j == 0 ? arreau_launch_prep(m, st.frac, st.lengths, st.angles, nullptr, st.offsets, st.B, st.N, w.lattice, w.cart, w.batch,
+                                                  w.cvec, s, w.t_next, w.t_cur, 0, next_t)
+                             : arreau_launch_prep(m, st.frac, st.lengths, st.angles, w.t_cur, st.offsets, st.B, st.N, w.lattice, w.cart, w.batch,
+                                                  w.cvec, s)))
+                return rc;
+            if ((rc = run_network(m, w, false, w.deg, w.src, w.dir, w.dist, st.frac, st.types, st.offsets, st.B, st.N, w.eps, w.logits,
+                                  pool_in_update ? nullptr : w.len0, s)))
+                return rc;
+        }
+        if (j < opt.corr.steps && (rc = arreau_launch_corrector(m, st, w.t_cur, w.eps, nullptr, seed, (uint32_t)j, opt, s))) return rc;
     }
-    return arreau_launch_reverse(m, d_frac, d_types, d_lengths, d_angles, w.t_cur, d_off, B, N, w.eps, w.logits, w.len0,
-                                 StepNoiseSrc{nullptr, nullptr, nullptr, seed}, d_const_types, d_lattice, s, d_fixed_lengths,
-                                 pool_in_update ? w.gs : nullptr, w.batch, nullptr, nullptr, cond, sched, pass, length_tie, sym);
+    // without a prep launch per step (fused kernels only) the update also leaves the next step's lattice and embedding behind
+    ReverseInputs in{w.t_cur, w.eps, w.logits, w.len0, StepNoiseSrc{.seed = seed}, pool_in_update ? w.gs : nullptr, w.batch};
+    if (no_prep) {
+        in.lattice_ws = w.lattice;
+        in.cvec_next = w.cvec;
+    }
+    return arreau_launch_reverse(m, st, in, opt, s);
 }
 
 // RePaint resampling (arreau_sample_loop_resampled): the blocks of one loop call, from the host's list of the steps it visits.
@@ -361,71 +346,29 @@ struct ResamplePlan {
     int passes, jump;
     std::vector<ResampleBlock> blocks;
 };
-}  // namespace
 
-extern "C" int arreau_sample_loop(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths,
-                                  const float* d_angles, const int32_t* d_off, int32_t B, int32_t N, int32_t t_start,
-                                  int32_t n_steps, uint64_t seed, const int32_t* d_const_types,
-                                  const float* d_fixed_lengths, float* d_lattice, void* d_workspace, size_t workspace_bytes, int32_t use_graph, void* stream) {
-    return arreau_sample_loop_conditioned(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, t_start, n_steps, seed, d_const_types,
-                                          d_fixed_lengths, d_lattice, d_workspace, workspace_bytes, use_graph, nullptr, stream);
-}
-
-extern "C" int arreau_sample_loop_conditioned(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths,
-                                              const float* d_angles, const int32_t* d_off, int32_t B, int32_t N, int32_t t_start,
-                                              int32_t n_steps, uint64_t seed, const int32_t* d_const_types,
-                                              const float* d_fixed_lengths, float* d_lattice, void* d_workspace, size_t workspace_bytes,
-                                              int32_t use_graph, const arreau_sample_condition* condition, void* stream) {
-    return arreau_sample_loop_scheduled(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, t_start, n_steps, seed, d_const_types,
-                                        d_fixed_lengths, d_lattice, d_workspace, workspace_bytes, use_graph, condition, nullptr, stream);
-}
-
-extern "C" int arreau_sample_loop_scheduled(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths,
-                                            const float* d_angles, const int32_t* d_off, int32_t B, int32_t N, int32_t t_start,
-                                            int32_t n_steps, uint64_t seed, const int32_t* d_const_types,
-                                            const float* d_fixed_lengths, float* d_lattice, void* d_workspace, size_t workspace_bytes,
-                                            int32_t use_graph, const arreau_sample_condition* condition,
-                                            const arreau_sample_schedule* schedule, void* stream) {
-    return arreau_sample_loop_corrected(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, t_start, n_steps, seed, d_const_types,
-                                        d_fixed_lengths, d_lattice, d_workspace, workspace_bytes, use_graph, condition, schedule, nullptr,
-                                        stream);
-}
-
-namespace {
 // The key of a captured step: besides the buffers, sizes and seed, which kernels it holds depends on switches read per call
 // (ARREAU_BASIS_MIN_RECEIVERS, ARREAU_FUSE_SMALL) and on the variants, and the condition's pointers, the schedule's table and
 // clip, the corrector's step count and snr, the resampling's R and J (a resampled step reads the pass word) and the lattice
 // systems' tie array and the symmetry tables are kernel arguments or launch choices of the capture: a change of any of them must
 // not replay the stale graph.
-SampleGraphKey sample_graph_key(const arreau_model* m, const float* d_frac, const int32_t* d_types, const float* d_lengths,
-                                const float* d_angles, const int32_t* d_off, int32_t B, int32_t N, uint64_t seed,
-                                const int32_t* d_const_types, const float* d_fixed_lengths, const float* d_lattice,
-                                const void* d_workspace, bool no_prep, const SampleConditionDev& cond, bool scheduled,
-                                const StepScheduleDev& sched, const CorrectorDev& corr, const ResamplePlan* plan,
-                                const int32_t* d_length_tie, const arreau_symmetry* sym) {
+SampleGraphKey sample_graph_key(const arreau_model* m, const SampleState& st, const void* d_workspace, uint64_t seed, bool no_prep,
+                                const StepOptions& opt, const ResamplePlan* plan) {
     SampleGraphKey k{};
-    k.frac = (uint64_t)d_frac; k.types = (uint64_t)d_types; k.lengths = (uint64_t)d_lengths; k.angles = (uint64_t)d_angles;
-    k.offsets = (uint64_t)d_off; k.const_types = (uint64_t)d_const_types; k.fixed_lengths = (uint64_t)d_fixed_lengths;
-    k.lattice = (uint64_t)d_lattice; k.workspace = (uint64_t)d_workspace; k.seed = seed;
-    k.cond_x0 = (uint64_t)cond.x0; k.cond_pos_mask = (uint64_t)cond.pos_mask; k.cond_a0 = (uint64_t)cond.a0;
-    k.cond_type_mask = (uint64_t)cond.type_mask; k.cond_l0 = (uint64_t)cond.l0; k.cond_len_mask = (uint64_t)cond.len_mask;
-    k.sched_next = (uint64_t)sched.next;
-    k.length_tie = (uint64_t)d_length_tie;
-    if (sym) {
-        k.sym_leader = (uint64_t)sym->leader; k.sym_op = (uint64_t)sym->op; k.sym_orbit = (uint64_t)sym->orbit;
-        k.sym_orbit_ptr = (uint64_t)sym->orbit_ptr; k.sym_orbit_atoms = (uint64_t)sym->orbit_atoms; k.sym_stab_ptr = (uint64_t)sym->stab_ptr;
-        k.sym_stab_ops = (uint64_t)sym->stab_ops; k.sym_rot = (uint64_t)sym->rot; k.sym_rot_inv = (uint64_t)sym->rot_inv;
-        k.sym_trans = (uint64_t)sym->trans;
-        k.sym_n_orbits = sym->n_orbits; k.sym_n_orbit_atoms = sym->n_orbit_atoms; k.sym_n_stab_ops = sym->n_stab_ops; k.sym_n_ops = sym->n_ops;
-    }
-    k.B = B; k.N = N;
+    k.state = st; k.workspace = d_workspace; k.seed = seed;
+    if (opt.cond) k.cond = *opt.cond;
+    if (opt.sym) k.sym = *opt.sym;
+    k.length_tie = opt.length_tie;
     k.edge_variant = m->edge_variant; k.mlp_variant = m->mlp_variant; k.conv_variant = m->conv_variant; k.no_prep = no_prep;
-    k.basis_form = arreau_basis_form(m, N); k.basis_fp8 = arreau_basis_fp8(m); k.cross_fp8 = arreau_cross_fp8(m);
-    k.small_layer_fusion = arreau_small_layer_fusable(m, N);
-    k.scheduled = scheduled;
-    memcpy(&k.clip_bits, &sched.clipmax, sizeof(k.clip_bits));
-    k.corrector_steps = corr.steps;
-    memcpy(&k.snr_bits, &corr.snr, sizeof(k.snr_bits));
+    k.basis_form = arreau_basis_form(m, st.N); k.basis_fp8 = arreau_basis_fp8(m); k.cross_fp8 = arreau_cross_fp8(m);
+    k.small_layer_fusion = arreau_small_layer_fusable(m, st.N);
+    k.scheduled = opt.sched != nullptr;
+    if (opt.sched) {
+        k.sched_next = opt.sched->next;
+        k.clip_bits = std::bit_cast<uint32_t>(opt.sched->clipmax);
+    }
+    k.corrector_steps = opt.corr.steps;
+    k.snr_bits = std::bit_cast<uint32_t>(opt.corr.snr);
     if (plan) {
         k.resample_passes = plan->passes;
         k.resample_jump = plan->jump;
@@ -433,19 +376,17 @@ SampleGraphKey sample_graph_key(const arreau_model* m, const float* d_frac, cons
     return k;
 }
 
-int sample_loop_impl(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles, const int32_t* d_off,
-                     int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed, const int32_t* d_const_types,
-                     const float* d_fixed_lengths, float* d_lattice, void* d_workspace, size_t workspace_bytes, int32_t use_graph,
-                     const arreau_sample_condition* condition, const arreau_sample_schedule* schedule, const arreau_corrector* corrector,
+int sample_loop_impl(arreau_model* m, const SampleState& st, int32_t t_start, int32_t n_steps, uint64_t seed, void* d_workspace,
+                     size_t workspace_bytes, int32_t use_graph, const arreau_sample_condition* condition,
+                     const arreau_sample_schedule* schedule, const arreau_corrector* corrector,
                      const ResamplePlan* plan /* null: no resampling */, const int32_t* d_length_tie /* null: untied */,
                      const arreau_symmetry* sym /* null: no symmetry */, void* stream) {
     if (corrector) {
         const int rc = arreau_corrector_check(corrector->steps, corrector->snr, "arreau_sample_loop_corrected");
         if (rc) return rc;
     }
-    // NULL and steps == 0 are the same loop (and the same graph key): the snr is then not read
-    const CorrectorDev corr = (corrector && corrector->steps > 0) ? CorrectorDev{corrector->steps, corrector->snr} : CorrectorDev{0, 0.0f};
-    ARREAU_REQUIRE(m && d_frac && d_types && d_lengths && d_angles && d_off && d_lattice, "arreau_sample_loop: null pointer");
+    const int B = st.B, N = st.N;
+    ARREAU_REQUIRE(m && st.frac && st.types && st.lengths && st.angles && st.offsets && st.lattice, "arreau_sample_loop: null pointer");
     ARREAU_REQUIRE(B >= 1 && N >= 0 && n_steps >= 0, "arreau_sample_loop: bad size");
     ARREAU_REQUIRE(!m->packed_stale || arreau_general_path(m),
                    "arreau_sample_loop: weights were updated for training only; re-create the model or select the general path");
@@ -467,21 +408,28 @@ int sample_loop_impl(arreau_model* m, float* d_frac, int32_t* d_types, float* d_
     SampleConditionDev cond_dev;
     int rc;
     if ((rc = arreau_condition_to_dev(condition, &cond_dev))) return rc;
-    const SampleConditionDev* cond = arreau_condition_empty(&cond_dev) ? nullptr : &cond_dev;  // empty: the unconditioned loop
     const StepScheduleDev sched_dev{schedule ? schedule->d_next : nullptr, nullptr, schedule ? schedule->lattice_clipmax : 0.0f};
-    const StepScheduleDev* sched = schedule ? &sched_dev : nullptr;  // null: every timestep, t_start down
+    // the options of every step of this call, built once
+    StepOptions opt;
+    opt.cond = arreau_condition_empty(&cond_dev) ? nullptr : &cond_dev;  // empty: the unconditioned loop
+    opt.sched = schedule ? &sched_dev : nullptr;                         // null: every timestep, t_start down
+    // a NULL corrector and steps == 0 are the same loop (and the same graph key): the snr is then not read
+    if (corrector && corrector->steps > 0) opt.corr = CorrectorDev{corrector->steps, corrector->snr};
+    opt.length_tie = d_length_tie;
+    opt.sym = sym;
     if (n_steps == 0) return ARREAU_OK;
     hipStream_t s = (hipStream_t)stream;
-    ARREAU_REQUIRE(!sym || (cond == nullptr && corr.steps == 0 && plan == nullptr),
+    ARREAU_REQUIRE(!sym || (opt.cond == nullptr && opt.corr.steps == 0 && plan == nullptr),
                    "arreau_sample_loop_sym: space-group symmetry is not combined with a condition, corrector steps or resampling");
+    opt.pass = plan ? w.pass : nullptr;
     const bool no_prep = loop_without_prep(m);
     if (no_prep) {
         // t_cur holds the timestep of the step in progress; every step's first launch advances it, so it starts one above (in a
         // respaced loop at the table entry t_start + 1, whose successor is t_start)
         ARREAU_LAUNCH(fill_i32_kernel, dim3((B + 255) / 256), dim3(256), 0, s, w.t_cur, t_start + 1, B);
         ARREAU_CHECK_HIP(hipGetLastError());
-        if ((rc = arreau_launch_prep(m, d_frac, d_lengths, d_angles, w.t_cur, d_off, B, N, w.lattice, w.cart, w.batch, w.cvec, s, nullptr,
-                                     nullptr, -1)))
+        if ((rc = arreau_launch_prep(m, st.frac, st.lengths, st.angles, w.t_cur, st.offsets, B, N, w.lattice, w.cart, w.batch, w.cvec, s,
+                                     nullptr, nullptr, -1)))
             return rc;
     } else {
         ARREAU_LAUNCH(fill_i32_kernel, dim3((B + 255) / 256), dim3(256), 0, s, w.t_next, t_start, B);
@@ -520,25 +468,20 @@ int sample_loop_impl(arreau_model* m, float* d_frac, int32_t* d_types, float* d_
         // The executable graph is kept with the model and reused while the next call names the same buffers, sizes and seed
         // (a sampler drawing sub-batch after sub-batch through the caching allocator does): capture + instantiation, about
         // 2 ms, are then paid once.  The timestep is not part of the graph (it lives in t_next / t_cur, set above).
-        key = sample_graph_key(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types, d_fixed_lengths, d_lattice,
-                               d_workspace, no_prep, cond_dev, schedule != nullptr, sched_dev, corr, plan, d_length_tie, sym);
+        key = sample_graph_key(m, st, d_workspace, seed, no_prep, opt, plan);
         exec = (hipGraphExec_t)m->retired_graph;
-        have_exec = exec && memcmp(&key, &m->graph_key, sizeof(key)) == 0;
+        have_exec = exec && key == m->graph_key;
     }
-    const int32_t* pass = plan ? w.pass : nullptr;
     // one step of the trajectory: eager, or (graph mode) the first one eager and captured behind it, then replays
     auto run_step = [&]() -> int {
         int r;
         if (!graph_mode || !have_exec) {
             // (eager: the first step of a capture also forces lazy module loading, which must not happen inside a capture)
-            if ((r = enqueue_sample_step(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types, d_fixed_lengths,
-                                         d_lattice, w, s, no_prep, cond, sched, corr, pass, d_length_tie, sym)))
-                return r;
+            if ((r = enqueue_sample_step(m, st, w, s, no_prep, seed, opt))) return r;
             if (!graph_mode) return ARREAU_OK;
             hipGraph_t graph = nullptr;
             ARREAU_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-            r = enqueue_sample_step(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, seed, d_const_types, d_fixed_lengths, d_lattice,
-                                    w, s, no_prep, cond, sched, corr, pass, d_length_tie, sym);
+            r = enqueue_sample_step(m, st, w, s, no_prep, seed, opt);
             hipError_t e = hipStreamEndCapture(s, &graph);
             if (r) {
                 if (graph) (void)hipGraphDestroy(graph);
@@ -568,10 +511,8 @@ int sample_loop_impl(arreau_model* m, float* d_frac, int32_t* d_types, float* d_
         ARREAU_CHECK_HIP(hipGetLastError());
         for (const ResampleBlock& bl : plan->blocks) {
             for (int r = 0; r < plan->passes; ++r) {
-                if (r > 0 &&
-                    (rc = arreau_launch_resample_jump(m, d_frac, d_types, d_lengths, d_angles, nullptr, nullptr, bl.bottom, bl.top, d_off,
-                                                      w.batch, B, N, nullptr, nullptr, nullptr, seed, (uint32_t)r, d_const_types,
-                                                      d_fixed_lengths, cond, d_lattice, &loop, s, d_length_tie)))
+                if (r > 0 && (rc = arreau_launch_resample_jump(m, st, /*d_s=*/nullptr, /*d_t=*/nullptr, bl.bottom, bl.top, w.batch,
+                                                               StepNoiseSrc{.seed = seed}, (uint32_t)r, opt.cond, &loop, d_length_tie, s)))
                     return rc;
                 for (int i = 0; i < bl.count; ++i)
                     if ((rc = run_step())) return rc;
@@ -585,26 +526,13 @@ int sample_loop_impl(arreau_model* m, float* d_frac, int32_t* d_types, float* d_
     ARREAU_CHECK_HIP(hipStreamWaitEvent(user, ev, 0));  // the caller's stream continues after the loop
     return ARREAU_OK;
 }
-}  // namespace
 
-extern "C" int arreau_sample_loop_corrected(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths,
-                                            const float* d_angles, const int32_t* d_off, int32_t B, int32_t N, int32_t t_start,
-                                            int32_t n_steps, uint64_t seed, const int32_t* d_const_types,
-                                            const float* d_fixed_lengths, float* d_lattice, void* d_workspace, size_t workspace_bytes,
-                                            int32_t use_graph, const arreau_sample_condition* condition,
-                                            const arreau_sample_schedule* schedule, const arreau_corrector* corrector, void* stream) {
-    return sample_loop_impl(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, t_start, n_steps, seed, d_const_types, d_fixed_lengths,
-                            d_lattice, d_workspace, workspace_bytes, use_graph, condition, schedule, corrector, nullptr, nullptr, nullptr,
-                            stream);
-}
-
-namespace {
-int sample_loop_resampled(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles, const int32_t* d_off,
-                          int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed, const int32_t* d_const_types,
-                          const float* d_fixed_lengths, float* d_lattice, void* d_workspace, size_t workspace_bytes, int32_t use_graph,
-                          const arreau_sample_condition* condition, const arreau_sample_schedule* schedule,
-                          const arreau_corrector* corrector, const arreau_resampling* resampling, const int32_t* d_length_tie,
-                          const char* who, void* stream, const arreau_symmetry* sym = nullptr) {
+// What every arreau_sample_loop* export runs, `who` being the export: the resampling plan (none without `resampling`), then the loop.
+int sample_loop(const char* who, arreau_model* m, const SampleState& st, int32_t t_start, int32_t n_steps, uint64_t seed,
+                void* d_workspace, size_t workspace_bytes, int32_t use_graph, void* stream,
+                const arreau_sample_condition* condition = nullptr, const arreau_sample_schedule* schedule = nullptr,
+                const arreau_corrector* corrector = nullptr, const arreau_resampling* resampling = nullptr,
+                const int32_t* d_length_tie = nullptr, const arreau_symmetry* sym = nullptr) {
     ResamplePlan plan{1, 1, {}};
     if (resampling) {
         int rc;
@@ -637,37 +565,74 @@ int sample_loop_resampled(arreau_model* m, float* d_frac, int32_t* d_types, floa
             plan.blocks.push_back(ResampleBlock{a, cnt, steps[a], a + cnt < n_steps ? steps[a + cnt] : last_succ});
         }
     }
-    return sample_loop_impl(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, t_start, n_steps, seed, d_const_types, d_fixed_lengths,
-                            d_lattice, d_workspace, workspace_bytes, use_graph, condition, schedule, corrector,
+    return sample_loop_impl(m, st, t_start, n_steps, seed, d_workspace, workspace_bytes, use_graph, condition, schedule, corrector,
                             plan.passes > 1 ? &plan : nullptr, d_length_tie, sym, stream);
 }
 }  // namespace
 
-extern "C" int arreau_sample_loop_resampled(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths,
-                                            const float* d_angles, const int32_t* d_off, int32_t B, int32_t N, int32_t t_start,
-                                            int32_t n_steps, uint64_t seed, const int32_t* d_const_types,
-                                            const float* d_fixed_lengths, float* d_lattice, void* d_workspace, size_t workspace_bytes,
-                                            int32_t use_graph, const arreau_sample_condition* condition,
-                                            const arreau_sample_schedule* schedule, const arreau_corrector* corrector,
-                                            const arreau_resampling* resampling, void* stream) {
-    return sample_loop_resampled(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, t_start, n_steps, seed, d_const_types,
-                                 d_fixed_lengths, d_lattice, d_workspace, workspace_bytes, use_graph, condition, schedule, corrector,
-                                 resampling, nullptr, "arreau_sample_loop_resampled", stream);
+// The seven exports: each is the one before it plus one option (NULL: the loop without it), a thin adapter onto sample_loop.  The
+// rules of the options are stated in include/arreau_hip.h.
+extern "C" int arreau_sample_loop(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                                  const int32_t* d_off, int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed,
+                                  const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice, void* d_workspace,
+                                  size_t workspace_bytes, int32_t use_graph, void* stream) {
+    const SampleState st{d_frac, d_types, d_lengths, d_angles, d_off, B, N, d_const_types, d_fixed_lengths, d_lattice};
+    return sample_loop("arreau_sample_loop", m, st, t_start, n_steps, seed, d_workspace, workspace_bytes, use_graph, stream);
 }
 
-// arreau_sample_loop_resampled with the lattice-system tie of the lengths (rules in include/arreau_hip.h); NULL = that loop.
+extern "C" int arreau_sample_loop_conditioned(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                                              const int32_t* d_off, int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed,
+                                              const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice,
+                                              void* d_workspace, size_t workspace_bytes, int32_t use_graph,
+                                              const arreau_sample_condition* condition, void* stream) {
+    const SampleState st{d_frac, d_types, d_lengths, d_angles, d_off, B, N, d_const_types, d_fixed_lengths, d_lattice};
+    return sample_loop("arreau_sample_loop_conditioned", m, st, t_start, n_steps, seed, d_workspace, workspace_bytes, use_graph, stream,
+                       condition);
+}
+
+extern "C" int arreau_sample_loop_scheduled(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                                            const int32_t* d_off, int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed,
+                                            const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice,
+                                            void* d_workspace, size_t workspace_bytes, int32_t use_graph,
+                                            const arreau_sample_condition* condition, const arreau_sample_schedule* schedule, void* stream) {
+    const SampleState st{d_frac, d_types, d_lengths, d_angles, d_off, B, N, d_const_types, d_fixed_lengths, d_lattice};
+    return sample_loop("arreau_sample_loop_scheduled", m, st, t_start, n_steps, seed, d_workspace, workspace_bytes, use_graph, stream,
+                       condition, schedule);
+}
+
+extern "C" int arreau_sample_loop_corrected(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                                            const int32_t* d_off, int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed,
+                                            const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice,
+                                            void* d_workspace, size_t workspace_bytes, int32_t use_graph,
+                                            const arreau_sample_condition* condition, const arreau_sample_schedule* schedule,
+                                            const arreau_corrector* corrector, void* stream) {
+    const SampleState st{d_frac, d_types, d_lengths, d_angles, d_off, B, N, d_const_types, d_fixed_lengths, d_lattice};
+    return sample_loop("arreau_sample_loop_corrected", m, st, t_start, n_steps, seed, d_workspace, workspace_bytes, use_graph, stream,
+                       condition, schedule, corrector);
+}
+
+extern "C" int arreau_sample_loop_resampled(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                                            const int32_t* d_off, int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed,
+                                            const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice,
+                                            void* d_workspace, size_t workspace_bytes, int32_t use_graph,
+                                            const arreau_sample_condition* condition, const arreau_sample_schedule* schedule,
+                                            const arreau_corrector* corrector, const arreau_resampling* resampling, void* stream) {
+    const SampleState st{d_frac, d_types, d_lengths, d_angles, d_off, B, N, d_const_types, d_fixed_lengths, d_lattice};
+    return sample_loop("arreau_sample_loop_resampled", m, st, t_start, n_steps, seed, d_workspace, workspace_bytes, use_graph, stream,
+                       condition, schedule, corrector, resampling);
+}
+
 extern "C" int arreau_sample_loop_tied(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
                                        const int32_t* d_off, int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed,
                                        const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice, void* d_workspace,
                                        size_t workspace_bytes, int32_t use_graph, const arreau_sample_condition* condition,
                                        const arreau_sample_schedule* schedule, const arreau_corrector* corrector,
                                        const arreau_resampling* resampling, const int32_t* d_length_tie, void* stream) {
-    return sample_loop_resampled(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, t_start, n_steps, seed, d_const_types,
-                                 d_fixed_lengths, d_lattice, d_workspace, workspace_bytes, use_graph, condition, schedule, corrector,
-                                 resampling, d_length_tie, "arreau_sample_loop_tied", stream);
+    const SampleState st{d_frac, d_types, d_lengths, d_angles, d_off, B, N, d_const_types, d_fixed_lengths, d_lattice};
+    return sample_loop("arreau_sample_loop_tied", m, st, t_start, n_steps, seed, d_workspace, workspace_bytes, use_graph, stream,
+                       condition, schedule, corrector, resampling, d_length_tie);
 }
 
-// arreau_sample_loop_tied with space-group symmetry (rules in include/arreau_hip.h); NULL = that loop.
 extern "C" int arreau_sample_loop_sym(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
                                       const int32_t* d_off, int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed,
                                       const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice, void* d_workspace,
@@ -681,9 +646,9 @@ extern "C" int arreau_sample_loop_sym(arreau_model* m, float* d_frac, int32_t* d
         ARREAU_REQUIRE(!resampling || resampling->passes <= 1,
                        "arreau_sample_loop_sym: space-group symmetry is not combined with resampling (passes > 1)");
     }
-    return sample_loop_resampled(m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, t_start, n_steps, seed, d_const_types,
-                                 d_fixed_lengths, d_lattice, d_workspace, workspace_bytes, use_graph, condition, schedule, corrector,
-                                 resampling, d_length_tie, "arreau_sample_loop_sym", stream, symmetry);
+    const SampleState st{d_frac, d_types, d_lengths, d_angles, d_off, B, N, d_const_types, d_fixed_lengths, d_lattice};
+    return sample_loop("arreau_sample_loop_sym", m, st, t_start, n_steps, seed, d_workspace, workspace_bytes, use_graph, stream, condition,
+                       schedule, corrector, resampling, d_length_tie, symmetry);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -88,15 +88,14 @@ int arreau_corrector_check(int32_t steps, float snr, const char* who) {
     return ARREAU_OK;
 }
 
-int arreau_launch_corrector(const arreau_model* m, float* d_frac, const int32_t* d_t, const int32_t* d_off, int B, int N,
-                            const float* d_eps, const float* d_z_frac, uint64_t seed, uint32_t iter, float snr,
-                            const SampleConditionDev* cond, hipStream_t s, const int32_t* d_pass) {
-    if (B <= 0 || N <= 0) return ARREAU_OK;
-    const uint8_t* mask = (cond && cond->x0 && cond->pos_mask) ? cond->pos_mask : nullptr;
-    auto kernel = mask ? (d_pass ? corrector_kernel<true, true> : corrector_kernel<true, false>)
-                       : (d_pass ? corrector_kernel<false, true> : corrector_kernel<false, false>);
-    ARREAU_LAUNCH(kernel, dim3(B), dim3(CORR_THREADS), 0, s, d_frac, d_t, d_off, m->T, d_eps, d_z_frac, seed, iter, snr, m->ve_sigmas,
-                  mask, m->status, d_pass);
+int arreau_launch_corrector(const arreau_model* m, const SampleState& st, const int32_t* d_t, const float* d_eps, const float* d_z_frac,
+                            uint64_t seed, uint32_t iter, const StepOptions& opt, hipStream_t s) {
+    if (st.B <= 0 || st.N <= 0) return ARREAU_OK;
+    const uint8_t* mask = (opt.cond && opt.cond->x0 && opt.cond->pos_mask) ? opt.cond->pos_mask : nullptr;
+    auto kernel = mask ? (opt.pass ? corrector_kernel<true, true> : corrector_kernel<true, false>)
+                       : (opt.pass ? corrector_kernel<false, true> : corrector_kernel<false, false>);
+    ARREAU_LAUNCH(kernel, dim3(st.B), dim3(CORR_THREADS), 0, s, st.frac, d_t, st.offsets, m->T, d_eps, d_z_frac, seed, iter, opt.corr.snr,
+                  m->ve_sigmas, mask, m->status, opt.pass);
     ARREAU_CHECK_HIP(hipGetLastError());
     return ARREAU_OK;
 }
@@ -110,5 +109,6 @@ extern "C" int arreau_corrector_step(const arreau_model* m, float* d_frac, const
     if ((rc = arreau_corrector_check(1, snr, "arreau_corrector_step"))) return rc;
     SampleConditionDev c;
     if ((rc = arreau_condition_to_dev(condition, &c))) return rc;
-    return arreau_launch_corrector(m, d_frac, d_t, d_off, B, N, d_eps, d_z_frac, 0, 0u, snr, &c, (hipStream_t)stream);
+    return arreau_launch_corrector(m, SampleState{.frac = d_frac, .offsets = d_off, .B = B, .N = N}, d_t, d_eps, d_z_frac, 0, 0u,
+                                   StepOptions{.cond = &c, .corr = {1, snr}}, (hipStream_t)stream);
 }

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
+#include <tuple>
 
 #include "../../include/arreau_hip.h"
 
@@ -36,20 +37,63 @@ void arreau_set_error(const std::string& msg);
         }                                                                                   \
     } while (0)
 
-// Packed weights resident in HBM.  All pointers are device pointers into `blob`.
+// Conditioned sampling (arreau_sample_condition, include/arreau_hip.h): the known components of the state, device pointers, each
+// may be null.  Masks are one byte per atom / crystal, nonzero = known.  Kernels take it by value and hand their helpers a pointer
+// to it, or null when the launch has no condition (then the helpers compile to the unconditioned code).
+struct SampleConditionDev {
+    const float* x0;          // [N,3] known fractional coordinates
+    const uint8_t* pos_mask;  // [N]
+    const int32_t* a0;        // [N]   known class indices
+    const uint8_t* type_mask; // [N]
+    const float* l0;          // [B,3] known cell lengths
+    const uint8_t* len_mask;  // [B]
+};
+
+// The sampler state a loop call or a single update works on: device pointers and sizes, the caller's.  Host side only: launchers
+// take it by const reference and hand the kernels its members.
+struct SampleState {
+    float* frac;                 // [N,3]
+    int32_t* types;              // [N]
+    float* lengths;              // [B,3]
+    const float* angles;         // [B,3]
+    const int32_t* offsets;      // [B+1]
+    int B, N;
+    const int32_t* const_types;  // [N] or null: species held
+    const float* fixed_lengths;  // [B,3] or null: cell held
+    float* lattice;              // [B,3,3] the caller's output cell
+    bool operator==(const SampleState&) const = default;
+};
+
+// Member-wise equality of the two plain structs SampleGraphKey holds that are not ours to extend (a kernel argument, a struct of
+// the public header).  The structured bindings stop compiling when a member is added, so none can be left out of the comparison.
+inline bool operator==(const SampleConditionDev& a, const SampleConditionDev& b) {
+    auto members = [](const SampleConditionDev& c) {
+        const auto& [x0, pos_mask, a0, type_mask, l0, len_mask] = c;
+        return std::tie(x0, pos_mask, a0, type_mask, l0, len_mask);
+    };
+    return members(a) == members(b);
+}
+inline bool operator==(const arreau_symmetry& a, const arreau_symmetry& b) {
+    auto members = [](const arreau_symmetry& y) {
+        const auto& [leader, op, orbit, orbit_ptr, orbit_atoms, stab_ptr, stab_ops, rot, rot_inv, trans, n_orbits, n_orbit_atoms,
+                     n_stab_ops, n_ops] = y;
+        return std::tie(leader, op, orbit, orbit_ptr, orbit_atoms, stab_ptr, stab_ops, rot, rot_inv, trans, n_orbits, n_orbit_atoms,
+                        n_stab_ops, n_ops);
+    };
+    return members(a) == members(b);
+}
+
 // What the cached executable graph of arreau_sample_loop was captured for (api.hip: sample_graph_key): every input that decides
-// the kernels of a captured step or their arguments, one field each.  Only 64-bit and 32-bit words, no padding, so that a
-// value-initialised key compares with memcmp.
+// the kernels of a captured step or their arguments.  Compared member by member; the two floats by their bits.  No member
+// initialisers: arreau_model_create zero-fills the model, and SampleGraphKey{} is the key no call has.
 struct SampleGraphKey {
-    // buffers and the Philox seed
-    uint64_t frac, types, lengths, angles, offsets, const_types, fixed_lengths, lattice, workspace, seed;
-    // conditioned sampling: the six pointers of the condition (null: none)
-    uint64_t cond_x0, cond_pos_mask, cond_a0, cond_type_mask, cond_l0, cond_len_mask;
-    uint64_t sched_next;  // respaced sampling: the next-timestep table
-    uint64_t length_tie;  // lattice systems: the per-crystal tie codes (null: untied)
-    // space-group symmetry: the ten table pointers (null: no symmetry)
-    uint64_t sym_leader, sym_op, sym_orbit, sym_orbit_ptr, sym_orbit_atoms, sym_stab_ptr, sym_stab_ops, sym_rot, sym_rot_inv, sym_trans;
-    int32_t B, N;
+    SampleState state;        // buffers and sizes
+    const void* workspace;
+    uint64_t seed;            // the Philox seed
+    SampleConditionDev cond;  // conditioned sampling: the six pointers of the condition (all null: none)
+    const int32_t* sched_next;  // respaced sampling: the next-timestep table
+    const int32_t* length_tie;  // lattice systems: the per-crystal tie codes (null: untied)
+    arreau_symmetry sym;      // space-group symmetry: the ten table pointers and their sizes (all zero: no symmetry)
     // kernel choices: the variants, and the switches read per call (ARREAU_BASIS_MIN_RECEIVERS, ARREAU_FUSE_SMALL)
     int32_t edge_variant, mlp_variant, conv_variant, no_prep, basis_form, basis_fp8, cross_fp8, small_layer_fusion;
     int32_t scheduled;
@@ -57,10 +101,10 @@ struct SampleGraphKey {
     int32_t corrector_steps;
     uint32_t snr_bits;         // the corrector's snr
     int32_t resample_passes, resample_jump;  // 0, 0: no resampling
-    int32_t sym_n_orbits, sym_n_orbit_atoms, sym_n_stab_ops, sym_n_ops;  // the symmetry tables' sizes
+    bool operator==(const SampleGraphKey&) const = default;
 };
-static_assert(sizeof(SampleGraphKey) == 28 * 8 + 20 * 4, "SampleGraphKey must have no padding (it is compared with memcmp)");
 
+// Packed weights resident in HBM.  All pointers are device pointers into `blob`.
 struct arreau_model {
     arreau_config cfg;
     int S, C, D, L, O, W, H, k, T;
@@ -233,17 +277,6 @@ struct StepNoiseSrc {
     uint64_t seed;           // used when the arrays are null
 };
 
-// Conditioned sampling (arreau_sample_condition, include/arreau_hip.h): the known components of the state, device pointers, each
-// may be null.  Masks are one byte per atom / crystal, nonzero = known.  Kernels take it by value and hand their helpers a pointer
-// to it, or null when the launch has no condition (then the helpers compile to the unconditioned code).
-struct SampleConditionDev {
-    const float* x0;          // [N,3] known fractional coordinates
-    const uint8_t* pos_mask;  // [N]
-    const int32_t* a0;        // [N]   known class indices
-    const uint8_t* type_mask; // [N]
-    const float* l0;          // [B,3] known cell lengths
-    const uint8_t* len_mask;  // [B]
-};
 inline bool arreau_condition_empty(const SampleConditionDev* c) {
     return !c || !((c->x0 && c->pos_mask) || (c->a0 && c->type_mask) || (c->l0 && c->len_mask));
 }
@@ -265,17 +298,33 @@ struct StepScheduleDev {
 // Predictor-corrector sampling (arreau_sample_loop_corrected, arreau_corrector_step; the rule is stated in include/arreau_hip.h).
 // arreau_corrector_check: ARREAU_EINVAL unless 0 <= steps <= ARREAU_MAX_CORRECTOR_STEPS and (steps == 0 or snr finite and > 0).
 int arreau_corrector_check(int32_t steps, float snr, const char* who);
+// M corrector moves at the step's timestep come before the predictor, each after a full network evaluation on the current state.
+struct CorrectorDev {
+    int steps;  // M (0: the plain step)
+    float snr;
+};
+
+// What modifies a step of the sampler, on the host side; all null / zero is the plain step.  Built once per library call and handed
+// down by const reference; the launchers pick the kernel instance from it.
+struct StepOptions {
+    const SampleConditionDev* cond = nullptr;  // conditioned sampling (the COND instances); needs Philox noise
+    const StepScheduleDev* sched = nullptr;    // respaced step: s from a table or per crystal; null: s = t - 1
+    CorrectorDev corr{};                       // corrector moves before the predictor
+    const int32_t* pass = nullptr;        // resampled loop: the device word of the pass index, word3 = 256 pass[0] (RESAMPLE)
+    const int32_t* length_tie = nullptr;  // lattice systems: the tie code per crystal (TIE)
+    const arreau_symmetry* sym = nullptr; // space-group symmetry: the orbit tables (SYM); not with a condition or a resampled loop
+};
+
 // One corrector move per crystal at timestep d_t[b]: z from the caller's d_z_frac [N,3], or (d_z_frac null) the Philox draw
-// (seed, t, ARREAU_DRAW_Z_CORRECTOR, element, iter).  cond: only its position mask is read (null / no mask: every atom moves).
-int arreau_launch_corrector(const arreau_model* m, float* d_frac, const int32_t* d_t, const int32_t* d_off, int B, int N,
-                            const float* d_eps, const float* d_z_frac, uint64_t seed, uint32_t iter, float snr,
-                            const SampleConditionDev* cond, hipStream_t s,
-                            const int32_t* d_pass = nullptr /* resampled loop: word3 = 256 pass[0] + iter (the RESAMPLE instance) */);
+// (seed, t, ARREAU_DRAW_Z_CORRECTOR, element, iter; 256 pass[0] + iter with opt.pass).  Reads st.frac / offsets / B / N, opt.corr.snr,
+// opt.pass and of opt.cond the position mask (null / no mask: every atom moves).
+int arreau_launch_corrector(const arreau_model* m, const SampleState& st, const int32_t* d_t, const float* d_eps, const float* d_z_frac,
+                            uint64_t seed, uint32_t iter, const StepOptions& opt, hipStream_t s);
 
 // RePaint resampling (arreau_sample_loop_resampled, arreau_resample_jump; the rules are stated in include/arreau_hip.h).
 // arreau_resampling_check: ARREAU_EINVAL unless 1 <= passes <= ARREAU_MAX_RESAMPLE_PASSES and jump_length >= 1.
 int arreau_resampling_check(int32_t passes, int32_t jump_length, const char* who);
-// The jump s -> t of every crystal: (s, t) from the per-crystal arrays d_s / d_t, or, when those are null, the scalars s / t
+// The jump s -> t of every crystal of `st`: (s, t) from the per-crystal arrays d_s / d_t, or, when those are null, the scalars s / t
 // (the loop's block bottom and top).  Noise from the caller's arrays, or (all null) Philox (seed, t, kinds 6-8, element, pass).
 // Loop form (loop != null): also the workspace cell and the per-crystal embedding of the next step for t, the device timestep
 // set to t (loop->t_next = t, loop->t_cur = t + 1: the entry from which the next step advances) and loop->pass = `pass`.
@@ -286,12 +335,11 @@ struct JumpLoopDev {
     int32_t* t_cur;     // [B]
     int32_t* pass;      // [1]
 };
-int arreau_launch_resample_jump(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
-                                const int32_t* d_s, const int32_t* d_t, int s, int t, const int32_t* d_off, const int32_t* d_batch,
-                                int B, int N, const float* d_z_frac, const float* d_z_lengths, const float* d_u_types, uint64_t seed,
-                                uint32_t pass, const int32_t* d_const_types, const float* d_fixed_lengths,
-                                const SampleConditionDev* cond, float* d_lattice, const JumpLoopDev* loop, hipStream_t st,
-                                const int32_t* d_length_tie = nullptr /* lattice systems: the tie code per crystal (the TIE instance) */);
+int arreau_launch_resample_jump(const arreau_model* m, const SampleState& st, const int32_t* d_s, const int32_t* d_t, int s, int t,
+                                const int32_t* d_batch, const StepNoiseSrc& noise /* z_lattice: the lengths' draws */, uint32_t pass,
+                                const SampleConditionDev* cond, const JumpLoopDev* loop,
+                                const int32_t* d_length_tie /* lattice systems: the tie code per crystal (the TIE instance), or null */,
+                                hipStream_t stream);
 
 void arreau_train_ctx_destroy(struct arreau_train_ctx* t);
 // edge_variant value that selects the shape-general fp32 network (train_net.hip) for the whole evaluation
@@ -353,20 +401,18 @@ int arreau_launch_prep(const arreau_model* m, const float* frac, const float* le
                        const int32_t* t, const int32_t* offsets, int B, int N, float* lattice, float* cart,
                        int32_t* batch, float* cvec, hipStream_t s, int32_t* t_next = nullptr, int32_t* t_cur = nullptr,
                        int t_offset = 0, const int32_t* next_t = nullptr /* respaced loop: t_next[b] = next_t[t] */);
-int arreau_launch_reverse(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
-                          const int32_t* d_t, const int32_t* d_off, int B, int N, const float* d_eps,
-                          const float* d_logits, const float* d_len0, StepNoiseSrc noise, const int32_t* d_const_types,
-                          float* d_lattice, hipStream_t s, const float* d_fixed_lengths = nullptr,
-                          const float* d_gs_atoms = nullptr /* pool these per-atom read-outs into d_len0 first */,
-                          const int32_t* d_batch = nullptr /* crystal index of each atom, if the caller has it */,
-                          float* d_lattice_ws = nullptr, float* d_cvec_next = nullptr /* sampling loop: also prepare the next step
-                          (workspace lattice + per-crystal embedding for timestep t - 1), see reverse_crystal_block */,
-                          const SampleConditionDev* cond = nullptr /* conditioned sampling; needs Philox noise (noise.seed) */,
-                          const StepScheduleDev* sched = nullptr /* respaced step (s from a table or per crystal), null: s = t - 1 */,
-                          const int32_t* d_pass = nullptr /* resampled loop: word3 = 256 pass[0] (the RESAMPLE instance) */,
-                          const int32_t* d_length_tie = nullptr /* lattice systems: the tie code per crystal (the TIE instance) */,
-                          const arreau_symmetry* sym = nullptr /* space-group symmetry: the orbit tables (the SYM instance); not
-                          with a condition or a resampled loop */);
+// What one reverse-update launch reads besides the state and the options.
+struct ReverseInputs {
+    const int32_t* t;                  // [B] the timestep each crystal leaves
+    const float *eps, *logits, *len0;  // the network's outputs
+    StepNoiseSrc noise;
+    const float* gs_atoms = nullptr;   // pool these per-atom read-outs into len0 first
+    const int32_t* batch = nullptr;    // crystal index of each atom, if the caller has it
+    // sampling loop: also prepare the next step (workspace lattice + per-crystal embedding for timestep t - 1), see reverse_crystal_block
+    float* lattice_ws = nullptr;
+    float* cvec_next = nullptr;
+};
+int arreau_launch_reverse(const arreau_model* m, const SampleState& st, const ReverseInputs& in, const StepOptions& opt, hipStream_t s);
 int arreau_launch_edge(const arreau_model* m, const float* dir, const float* dist, const int32_t* deg,
                        const int32_t* batch, const float* lattice, int N, float* kbuf, hipStream_t s);
 int arreau_launch_edge_bf16x6(const arreau_model* m, const float* dir, const float* dist, const int32_t* deg,

@@ -182,22 +182,19 @@ int arreau_resampling_check(int32_t passes, int32_t jump_length, const char* who
     return ARREAU_OK;
 }
 
-int arreau_launch_resample_jump(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
-                                const int32_t* d_s, const int32_t* d_t, int s, int t, const int32_t* d_off, const int32_t* d_batch,
-                                int B, int N, const float* d_z_frac, const float* d_z_lengths, const float* d_u_types, uint64_t seed,
-                                uint32_t pass, const int32_t* d_const_types, const float* d_fixed_lengths,
-                                const SampleConditionDev* cond, float* d_lattice, const JumpLoopDev* loop, hipStream_t st,
-                                const int32_t* d_length_tie) {
-    if (B <= 0) return ARREAU_OK;
+int arreau_launch_resample_jump(const arreau_model* m, const SampleState& st, const int32_t* d_s, const int32_t* d_t, int s, int t,
+                                const int32_t* d_batch, const StepNoiseSrc& noise, uint32_t pass, const SampleConditionDev* cond,
+                                const JumpLoopDev* loop, const int32_t* d_length_tie, hipStream_t stream) {
+    if (st.B <= 0) return ARREAU_OK;
     const uint8_t* type_mask = (cond && cond->a0 && cond->type_mask) ? cond->type_mask : nullptr;
     const uint8_t* len_mask = (cond && cond->l0 && cond->len_mask) ? cond->len_mask : nullptr;
     const JumpLoopDev lp = loop ? *loop : JumpLoopDev{};
-    const unsigned blocks = (unsigned)B + (unsigned)((N + 3) / 4);
+    const unsigned blocks = (unsigned)st.B + (unsigned)((st.N + 3) / 4);
     auto kernel = d_length_tie ? resample_jump_kernel<true> : resample_jump_kernel<false>;
-    ARREAU_LAUNCH(kernel, dim3(blocks), dim3(JUMP_THREADS), 0, st, B, N, d_frac, d_types, d_lengths, d_angles,
-                  JumpTimes{d_s, d_t, s, t}, d_off, d_batch, JumpNoise{d_z_frac, d_z_lengths, d_u_types, seed, pass}, m->ve_sigmas,
-                  m->vp_alpha_bars, m->qmats, m->S, m->T, m->qmats_absorbing, d_const_types, d_fixed_lengths, type_mask, d_lattice, lp,
-                  m->vp_betas, m->t_emb_w, m->embT, m->C, m->status, d_length_tie, len_mask);
+    ARREAU_LAUNCH(kernel, dim3(blocks), dim3(JUMP_THREADS), 0, stream, st.B, st.N, st.frac, st.types, st.lengths, st.angles,
+                  JumpTimes{d_s, d_t, s, t}, st.offsets, d_batch, JumpNoise{noise.z_frac, noise.z_lattice, noise.u_types, noise.seed, pass},
+                  m->ve_sigmas, m->vp_alpha_bars, m->qmats, m->S, m->T, m->qmats_absorbing, st.const_types, st.fixed_lengths, type_mask,
+                  st.lattice, lp, m->vp_betas, m->t_emb_w, m->embT, m->C, m->status, d_length_tie, len_mask);
     ARREAU_CHECK_HIP(hipGetLastError());
     return ARREAU_OK;
 }
@@ -213,9 +210,9 @@ static int resample_jump(const arreau_model* m, float* d_frac, int32_t* d_types,
     SampleConditionDev c;
     int rc;
     if ((rc = arreau_condition_to_dev(cond, &c))) return rc;
-    return arreau_launch_resample_jump(m, d_frac, d_types, d_lengths, d_angles, d_s, d_t, 0, 0, d_off, nullptr, B, N, d_z_frac,
-                                       d_z_lengths, d_u_types, 0, 0u, d_const_types, d_fixed_lengths, &c, d_lattice, nullptr,
-                                       (hipStream_t)stream, d_length_tie);
+    const SampleState st{d_frac, d_types, d_lengths, d_angles, d_off, B, N, d_const_types, d_fixed_lengths, d_lattice};
+    return arreau_launch_resample_jump(m, st, d_s, d_t, 0, 0, /*d_batch=*/nullptr, StepNoiseSrc{d_z_lengths, d_z_frac, d_u_types, 0}, 0u, &c,
+                                       /*loop=*/nullptr, d_length_tie, (hipStream_t)stream);
 }
 
 extern "C" int arreau_resample_jump(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,

@@ -118,54 +118,40 @@ __global__ __launch_bounds__(256) void reverse_kernel(
 
 namespace {
 template <bool COND, bool SCHED>
-void enqueue_reverse_kernel(const arreau_model* m, int lat_blocks, int atom_blocks, float* d_frac, int32_t* d_types, float* d_lengths,
-                            const float* d_angles, const int32_t* d_t, const int32_t* d_off, int B, int N, const float* d_eps,
-                            const float* d_logits, const float* d_len0, StepNoiseSrc noise, const int32_t* d_const_types,
-                            float* d_lattice, hipStream_t s, const float* d_fixed_lengths, const float* d_gs_atoms,
-                            const int32_t* d_batch, float* d_lattice_ws, float* d_cvec_next, const SampleConditionDev& cond,
-                            const StepScheduleDev& sched, const int32_t* d_pass, const int32_t* d_length_tie, const arreau_symmetry* sym) {
-    auto kernel = d_length_tie ? (d_pass ? reverse_kernel<COND, SCHED, true, true, false> : reverse_kernel<COND, SCHED, false, true, false>)
-                               : (d_pass ? reverse_kernel<COND, SCHED, true, false, false> : reverse_kernel<COND, SCHED, false, false, false>);
+void enqueue_reverse_kernel(const arreau_model* m, int lat_blocks, int atom_blocks, const SampleState& st, const ReverseInputs& in,
+                            const SampleConditionDev& cond, const StepScheduleDev& sched, const StepOptions& opt, hipStream_t s) {
+    auto kernel = opt.length_tie ? (opt.pass ? reverse_kernel<COND, SCHED, true, true, false> : reverse_kernel<COND, SCHED, false, true, false>)
+                                 : (opt.pass ? reverse_kernel<COND, SCHED, true, false, false> : reverse_kernel<COND, SCHED, false, false, false>);
     if constexpr (!COND) {
-        if (sym) kernel = d_length_tie ? reverse_kernel<false, SCHED, false, true, true> : reverse_kernel<false, SCHED, false, false, true>;
+        if (opt.sym) kernel = opt.length_tie ? reverse_kernel<false, SCHED, false, true, true> : reverse_kernel<false, SCHED, false, false, true>;
     }
-    ARREAU_LAUNCH(kernel, dim3(lat_blocks + atom_blocks), dim3(256), 0, s, lat_blocks, d_lengths, d_angles, d_t, d_off, d_len0, noise,
-                  m->vp_alpha_bars, m->vp_betas, B, m->T, d_lattice, d_fixed_lengths, m->status, 0, d_gs_atoms,
-                  d_gs_atoms ? const_cast<float*>(d_len0) : nullptr, d_frac, d_types, B, N, d_eps, d_logits, m->ve_sigmas, m->q1t,
-                  m->qmats, m->S, d_const_types, m->qmats_absorbing, 0, d_batch, d_lattice_ws, d_cvec_next, m->t_emb_w, m->embT, m->C,
-                  cond, sched, d_pass, d_length_tie, sym ? *sym : arreau_symmetry{});
+    ARREAU_LAUNCH(kernel, dim3(lat_blocks + atom_blocks), dim3(256), 0, s, lat_blocks, st.lengths, st.angles, in.t, st.offsets, in.len0, in.noise,
+                  m->vp_alpha_bars, m->vp_betas, st.B, m->T, st.lattice, st.fixed_lengths, m->status, 0, in.gs_atoms,
+                  in.gs_atoms ? const_cast<float*>(in.len0) : nullptr, st.frac, st.types, st.B, st.N, in.eps, in.logits, m->ve_sigmas, m->q1t,
+                  m->qmats, m->S, st.const_types, m->qmats_absorbing, 0, in.batch, in.lattice_ws, in.cvec_next, m->t_emb_w, m->embT, m->C,
+                  cond, sched, opt.pass, opt.length_tie, opt.sym ? *opt.sym : arreau_symmetry{});
 }
 }  // namespace
 
-int arreau_launch_reverse(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
-                          const int32_t* d_t, const int32_t* d_off, int B, int N, const float* d_eps,
-                          const float* d_logits, const float* d_len0, StepNoiseSrc noise, const int32_t* d_const_types,
-                          float* d_lattice, hipStream_t s, const float* d_fixed_lengths, const float* d_gs_atoms,
-                          const int32_t* d_batch, float* d_lattice_ws, float* d_cvec_next, const SampleConditionDev* cond,
-                          const StepScheduleDev* sched, const int32_t* d_pass, const int32_t* d_length_tie, const arreau_symmetry* sym) {
-    const bool prep_next = d_cvec_next != nullptr;  // one workgroup per crystal, which also prepares the next step
-    ARREAU_REQUIRE(!prep_next || d_lattice_ws != nullptr, "reverse update: the next step's set-up needs the workspace lattice");
-    const int lat_blocks = B > 0 ? (prep_next ? B : (4 * B + 255) / 256) : 0;
-    const int atom_blocks = N > 0 ? (N + 3) / 4 : 0;
-    const bool conditioned = !arreau_condition_empty(cond);
-    ARREAU_REQUIRE(!conditioned || (!noise.z_lattice && !noise.z_frac && !noise.u_types),
+int arreau_launch_reverse(const arreau_model* m, const SampleState& st, const ReverseInputs& in, const StepOptions& opt, hipStream_t s) {
+    const bool prep_next = in.cvec_next != nullptr;  // one workgroup per crystal, which also prepares the next step
+    ARREAU_REQUIRE(!prep_next || in.lattice_ws != nullptr, "reverse update: the next step's set-up needs the workspace lattice");
+    const int lat_blocks = st.B > 0 ? (prep_next ? st.B : (4 * st.B + 255) / 256) : 0;
+    const int atom_blocks = st.N > 0 ? (st.N + 3) / 4 : 0;
+    const bool conditioned = !arreau_condition_empty(opt.cond);
+    ARREAU_REQUIRE(!conditioned || (!in.noise.z_lattice && !in.noise.z_frac && !in.noise.u_types),
                    "reverse update: conditioned sampling needs the in-kernel (Philox) noise");
-    const bool scheduled = sched != nullptr;
-    ARREAU_REQUIRE(!scheduled || (sched->next != nullptr) != (sched->s_of != nullptr),
+    const bool scheduled = opt.sched != nullptr;
+    ARREAU_REQUIRE(!scheduled || (opt.sched->next != nullptr) != (opt.sched->s_of != nullptr),
                    "reverse update: a respaced step takes either the next-timestep table or the per-crystal targets");
-    ARREAU_REQUIRE(!sym || (!conditioned && d_pass == nullptr),
+    ARREAU_REQUIRE(!opt.sym || (!conditioned && opt.pass == nullptr),
                    "reverse update: space-group symmetry is not combined with a condition or a resampled loop");
     if (lat_blocks + atom_blocks == 0) return ARREAU_OK;
-    const SampleConditionDev c = conditioned ? *cond : SampleConditionDev{};
-    const StepScheduleDev sc = scheduled ? *sched : StepScheduleDev{};
-#define ARREAU_REVERSE_ARGS m, lat_blocks, atom_blocks, d_frac, d_types, d_lengths, d_angles, d_t, d_off, B, N, d_eps, d_logits, d_len0, \
-        noise, d_const_types, d_lattice, s, d_fixed_lengths, d_gs_atoms, d_batch, d_lattice_ws, d_cvec_next, c, sc, d_pass, d_length_tie, \
-        sym
-    if (conditioned && scheduled) enqueue_reverse_kernel<true, true>(ARREAU_REVERSE_ARGS);
-    else if (conditioned) enqueue_reverse_kernel<true, false>(ARREAU_REVERSE_ARGS);
-    else if (scheduled) enqueue_reverse_kernel<false, true>(ARREAU_REVERSE_ARGS);
-    else enqueue_reverse_kernel<false, false>(ARREAU_REVERSE_ARGS);
-#undef ARREAU_REVERSE_ARGS
+    const SampleConditionDev c = conditioned ? *opt.cond : SampleConditionDev{};
+    const StepScheduleDev sc = scheduled ? *opt.sched : StepScheduleDev{};
+    auto enqueue = conditioned ? (scheduled ? enqueue_reverse_kernel<true, true> : enqueue_reverse_kernel<true, false>)
+                               : (scheduled ? enqueue_reverse_kernel<false, true> : enqueue_reverse_kernel<false, false>);
+    enqueue(m, lat_blocks, atom_blocks, st, in, c, sc, opt, s);
     ARREAU_CHECK_HIP(hipGetLastError());
     return ARREAU_OK;
 }
@@ -178,24 +164,27 @@ extern "C" int arreau_reverse_step(const arreau_model* m, float* d_frac, int32_t
     ARREAU_REQUIRE(m && d_frac && d_types && d_lengths && d_angles && d_t && d_off && d_eps && d_logits && d_len0 &&
                        d_z_lattice && d_z_frac && d_u_types && d_lattice, "arreau_reverse_step: null pointer");
     ARREAU_REQUIRE(B >= 1 && N >= 0, "arreau_reverse_step: bad size");
-    return arreau_launch_reverse(m, d_frac, d_types, d_lengths, d_angles, d_t, d_off, B, N, d_eps, d_logits, d_len0,
-                                 StepNoiseSrc{d_z_lattice, d_z_frac, d_u_types, 0}, nullptr, d_lattice, (hipStream_t)stream);
+    const SampleState st{.frac = d_frac, .types = d_types, .lengths = d_lengths, .angles = d_angles, .offsets = d_off, .B = B, .N = N,
+                         .lattice = d_lattice};
+    const ReverseInputs in{d_t, d_eps, d_logits, d_len0, StepNoiseSrc{d_z_lattice, d_z_frac, d_u_types, 0}};
+    return arreau_launch_reverse(m, st, in, StepOptions{}, (hipStream_t)stream);
 }
 
 // arreau_reverse_step from timestep t to a per-crystal target s (respaced sampling; rules in include/arreau_hip.h).
 static int reverse_step_to(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
                            const int32_t* d_t, const int32_t* d_s, const int32_t* d_off, int32_t B, int32_t N, const float* d_eps,
                            const float* d_logits, const float* d_len0, const float* d_z_lattice, const float* d_z_frac,
-                           const float* d_u_types, float* d_lattice, float lattice_clipmax, const int32_t* d_length_tie, void* stream,
-                           const char* who, const arreau_symmetry* sym = nullptr) {
+                           const float* d_u_types, float* d_lattice, float lattice_clipmax, const int32_t* d_length_tie,
+                           const arreau_symmetry* sym, void* stream, const char* who) {
     ARREAU_REQUIRE(m && d_frac && d_types && d_lengths && d_angles && d_t && d_s && d_off && d_eps && d_logits && d_len0 &&
                        d_z_lattice && d_z_frac && d_u_types && d_lattice, std::string(who) + ": null pointer");
     ARREAU_REQUIRE(B >= 1 && N >= 0, std::string(who) + ": bad size");
     ARREAU_REQUIRE(lattice_clipmax > 0.0f && lattice_clipmax <= 1.0f, std::string(who) + ": lattice_clipmax must lie in (0, 1]");
+    const SampleState st{.frac = d_frac, .types = d_types, .lengths = d_lengths, .angles = d_angles, .offsets = d_off, .B = B, .N = N,
+                         .lattice = d_lattice};
+    const ReverseInputs in{d_t, d_eps, d_logits, d_len0, StepNoiseSrc{d_z_lattice, d_z_frac, d_u_types, 0}};
     const StepScheduleDev sched{nullptr, d_s, lattice_clipmax};
-    return arreau_launch_reverse(m, d_frac, d_types, d_lengths, d_angles, d_t, d_off, B, N, d_eps, d_logits, d_len0,
-                                 StepNoiseSrc{d_z_lattice, d_z_frac, d_u_types, 0}, nullptr, d_lattice, (hipStream_t)stream, nullptr,
-                                 nullptr, nullptr, nullptr, nullptr, nullptr, &sched, nullptr, d_length_tie, sym);
+    return arreau_launch_reverse(m, st, in, StepOptions{.sched = &sched, .length_tie = d_length_tie, .sym = sym}, (hipStream_t)stream);
 }
 
 extern "C" int arreau_reverse_step_to(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths,
@@ -204,7 +193,7 @@ extern "C" int arreau_reverse_step_to(const arreau_model* m, float* d_frac, int3
                                       const float* d_z_lattice, const float* d_z_frac, const float* d_u_types, float* d_lattice,
                                       float lattice_clipmax, void* stream) {
     return reverse_step_to(m, d_frac, d_types, d_lengths, d_angles, d_t, d_s, d_off, B, N, d_eps, d_logits, d_len0, d_z_lattice, d_z_frac,
-                           d_u_types, d_lattice, lattice_clipmax, nullptr, stream, "arreau_reverse_step_to");
+                           d_u_types, d_lattice, lattice_clipmax, /*d_length_tie=*/nullptr, /*sym=*/nullptr, stream, "arreau_reverse_step_to");
 }
 
 // arreau_reverse_step_to with the lattice-system tie of the lengths (rules in include/arreau_hip.h); NULL = arreau_reverse_step_to.
@@ -214,7 +203,7 @@ extern "C" int arreau_reverse_step_tied(const arreau_model* m, float* d_frac, in
                                         const float* d_z_lattice, const float* d_z_frac, const float* d_u_types, float* d_lattice,
                                         float lattice_clipmax, const int32_t* d_length_tie, void* stream) {
     return reverse_step_to(m, d_frac, d_types, d_lengths, d_angles, d_t, d_s, d_off, B, N, d_eps, d_logits, d_len0, d_z_lattice, d_z_frac,
-                           d_u_types, d_lattice, lattice_clipmax, d_length_tie, stream, "arreau_reverse_step_tied");
+                           d_u_types, d_lattice, lattice_clipmax, d_length_tie, /*sym=*/nullptr, stream, "arreau_reverse_step_tied");
 }
 
 // arreau_reverse_step_tied with space-group symmetry (rules in include/arreau_hip.h); NULL = arreau_reverse_step_tied.
@@ -226,7 +215,7 @@ extern "C" int arreau_reverse_step_sym(const arreau_model* m, float* d_frac, int
     int rc;
     if (symmetry && (rc = arreau_symmetry_check(symmetry, "arreau_reverse_step_sym"))) return rc;
     return reverse_step_to(m, d_frac, d_types, d_lengths, d_angles, d_t, d_s, d_off, B, N, d_eps, d_logits, d_len0, d_z_lattice, d_z_frac,
-                           d_u_types, d_lattice, lattice_clipmax, d_length_tie, stream, "arreau_reverse_step_sym", symmetry);
+                           d_u_types, d_lattice, lattice_clipmax, d_length_tie, symmetry, stream, "arreau_reverse_step_sym");
 }
 
 // the host checks of a symmetry table set: every pointer given, sizes positive (the kernel checks every index it follows)

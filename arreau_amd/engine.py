@@ -16,6 +16,11 @@ def _f32(t):
     return t.detach().to("cpu", torch.float32).contiguous()
 
 
+def _byref(struct):
+    """A ctypes struct by reference, or NULL for None."""
+    return ctypes.byref(struct) if struct is not None else None
+
+
 def screen(frac, lattice, offsets, types=None, criteria=None):
     """The structural screen without an engine (arreau_crystal_screen needs no model): diffusion.screening.screen."""
     from .diffusion import screening
@@ -248,28 +253,18 @@ class HipEngine:
             sched = _hip.SampleScheduleC(_hip.ptr(next_table).value, float(lattice_clipmax))
         cond = self._condition_struct(condition, N, B) if condition is not None else None
         corr = _hip.CorrectorC(corrector[0], corrector[1]) if corrector is not None else None
-        if symmetry is not None:
-            if length_tie is not None:
-                self._check_tie(length_tie, B)
-            sym = self._symmetry_struct(symmetry, N)
-            byref = lambda v: ctypes.byref(v) if v is not None else None
-            _hip.check(_hip.lib().arreau_sample_loop_sym(*args, byref(cond), byref(sched), byref(corr), byref(res), _hip.ptr(length_tie),
-                                                         ctypes.byref(sym), _hip.stream_ptr(self.device)), "arreau_sample_loop_sym")
-            return
         if length_tie is not None:
             self._check_tie(length_tie, B)
-            _hip.check(_hip.lib().arreau_sample_loop_tied(
-                *args, ctypes.byref(cond) if cond is not None else None, ctypes.byref(sched) if sched is not None else None,
-                ctypes.byref(corr) if corr is not None else None, ctypes.byref(res) if res is not None else None, _hip.ptr(length_tie),
-                _hip.stream_ptr(self.device)), "arreau_sample_loop_tied")
-            return
-        if cond is None and sched is None and corr is None and res is None:
-            # (the plain entry point: A/B runs against an older library through ARREAU_HIP_LIB call it)
-            _hip.check(_hip.lib().arreau_sample_loop(*args, _hip.stream_ptr(self.device)), "arreau_sample_loop")
-            return
-        byref = lambda v: ctypes.byref(v) if v is not None else None
-        _hip.check(_hip.lib().arreau_sample_loop_resampled(*args, byref(cond), byref(sched), byref(corr), byref(res),
-                                                           _hip.stream_ptr(self.device)), "arreau_sample_loop_resampled")
+        opts = (_byref(cond), _byref(sched), _byref(corr), _byref(res))
+        if symmetry is not None:
+            name, opts = "arreau_sample_loop_sym", opts + (_hip.ptr(length_tie), _byref(self._symmetry_struct(symmetry, N)))
+        elif length_tie is not None:
+            name, opts = "arreau_sample_loop_tied", opts + (_hip.ptr(length_tie),)
+        elif any(o is not None for o in opts):
+            name = "arreau_sample_loop_resampled"
+        else:  # (the plain entry point: A/B runs against an older library through ARREAU_HIP_LIB call it)
+            name, opts = "arreau_sample_loop", ()
+        _hip.check(getattr(_hip.lib(), name)(*args, *opts, _hip.stream_ptr(self.device)), name)
 
     def _check_tie(self, length_tie, B):
         if (tuple(length_tie.shape) != (B,) or length_tie.dtype != torch.int32 or length_tie.device != self.device
@@ -355,7 +350,7 @@ class HipEngine:
         cond = self._condition_struct(condition, N, B) if condition is not None else None
         _hip.check(_hip.lib().arreau_corrector_step(
             self._handle, _hip.ptr(frac), _hip.ptr(t_crystal), _hip.ptr(offsets), B, N, _hip.ptr(eps), _hip.ptr(z_frac), snr,
-            ctypes.byref(cond) if cond is not None else None, _hip.stream_ptr(self.device)), "arreau_corrector_step")
+            _byref(cond), _hip.stream_ptr(self.device)), "arreau_corrector_step")
 
     def diffusion_noise(self, frac0, types0, lattice0, t_crystal, offsets, z_frac, u_types, z_lengths):
         """Forward noising of a clean batch (arreau_diffusion_noise).  Returns dict(noisy_frac, target_eps, noisy_types,
@@ -586,40 +581,38 @@ class HipEngine:
             _hip.ptr(z_frac), _hip.ptr(u_types), _hip.ptr(lattice_out), _hip.stream_ptr(self.device)),
             "arreau_reverse_step")
 
+    def _reverse_step_to(self, name, frac, types, lengths, angles, t_crystal, s_crystal, offsets, eps, logits, len0, z_lattice, z_frac,
+                         u_types, lattice_out, lattice_clipmax, *options):
+        """arreau_reverse_step_to / _tied / _sym: the arguments they share, then each one's own options."""
+        B, N = lengths.shape[0], frac.shape[0]
+        _hip.check(getattr(_hip.lib(), name)(
+            self._handle, _hip.ptr(frac), _hip.ptr(types), _hip.ptr(lengths), _hip.ptr(angles), _hip.ptr(t_crystal),
+            _hip.ptr(s_crystal), _hip.ptr(offsets), B, N, _hip.ptr(eps), _hip.ptr(logits), _hip.ptr(len0), _hip.ptr(z_lattice),
+            _hip.ptr(z_frac), _hip.ptr(u_types), _hip.ptr(lattice_out), float(lattice_clipmax), *options,
+            _hip.stream_ptr(self.device)), name)
+
     def reverse_step_to(self, frac, types, lengths, angles, t_crystal, s_crystal, offsets, eps, logits, len0, z_lattice, z_frac,
                         u_types, lattice_out, lattice_clipmax=0.999):
         """reverse_step from timestep t_crystal[b] to s_crystal[b] (arreau_reverse_step_to: a respaced step)."""
-        B, N = lengths.shape[0], frac.shape[0]
-        _hip.check(_hip.lib().arreau_reverse_step_to(
-            self._handle, _hip.ptr(frac), _hip.ptr(types), _hip.ptr(lengths), _hip.ptr(angles), _hip.ptr(t_crystal),
-            _hip.ptr(s_crystal), _hip.ptr(offsets), B, N, _hip.ptr(eps), _hip.ptr(logits), _hip.ptr(len0), _hip.ptr(z_lattice),
-            _hip.ptr(z_frac), _hip.ptr(u_types), _hip.ptr(lattice_out), float(lattice_clipmax), _hip.stream_ptr(self.device)),
-            "arreau_reverse_step_to")
+        self._reverse_step_to("arreau_reverse_step_to", frac, types, lengths, angles, t_crystal, s_crystal, offsets, eps, logits, len0,
+                              z_lattice, z_frac, u_types, lattice_out, lattice_clipmax)
 
     def reverse_step_tied(self, frac, types, lengths, angles, t_crystal, s_crystal, offsets, eps, logits, len0, z_lattice, z_frac,
                           u_types, lattice_out, length_tie, lattice_clipmax=0.999):
         """reverse_step_to with the lattice-system tie of the lengths (arreau_reverse_step_tied): length_tie [B] int32 codes."""
-        B, N = lengths.shape[0], frac.shape[0]
-        self._check_tie(length_tie, B)
-        _hip.check(_hip.lib().arreau_reverse_step_tied(
-            self._handle, _hip.ptr(frac), _hip.ptr(types), _hip.ptr(lengths), _hip.ptr(angles), _hip.ptr(t_crystal),
-            _hip.ptr(s_crystal), _hip.ptr(offsets), B, N, _hip.ptr(eps), _hip.ptr(logits), _hip.ptr(len0), _hip.ptr(z_lattice),
-            _hip.ptr(z_frac), _hip.ptr(u_types), _hip.ptr(lattice_out), float(lattice_clipmax), _hip.ptr(length_tie),
-            _hip.stream_ptr(self.device)), "arreau_reverse_step_tied")
+        self._check_tie(length_tie, lengths.shape[0])
+        self._reverse_step_to("arreau_reverse_step_tied", frac, types, lengths, angles, t_crystal, s_crystal, offsets, eps, logits, len0,
+                              z_lattice, z_frac, u_types, lattice_out, lattice_clipmax, _hip.ptr(length_tie))
 
     def reverse_step_sym(self, frac, types, lengths, angles, t_crystal, s_crystal, offsets, eps, logits, len0, z_lattice, z_frac,
                          u_types, lattice_out, length_tie, symmetry, lattice_clipmax=0.999):
         """reverse_step_tied with space-group symmetry (arreau_reverse_step_sym): `symmetry` the dict of symmetry.device_arrays
         (None: the tied step); length_tie may be None."""
-        B, N = lengths.shape[0], frac.shape[0]
         if length_tie is not None:
-            self._check_tie(length_tie, B)
-        sym = self._symmetry_struct(symmetry, N) if symmetry is not None else None
-        _hip.check(_hip.lib().arreau_reverse_step_sym(
-            self._handle, _hip.ptr(frac), _hip.ptr(types), _hip.ptr(lengths), _hip.ptr(angles), _hip.ptr(t_crystal),
-            _hip.ptr(s_crystal), _hip.ptr(offsets), B, N, _hip.ptr(eps), _hip.ptr(logits), _hip.ptr(len0), _hip.ptr(z_lattice),
-            _hip.ptr(z_frac), _hip.ptr(u_types), _hip.ptr(lattice_out), float(lattice_clipmax), _hip.ptr(length_tie),
-            ctypes.byref(sym) if sym is not None else None, _hip.stream_ptr(self.device)), "arreau_reverse_step_sym")
+            self._check_tie(length_tie, lengths.shape[0])
+        sym = self._symmetry_struct(symmetry, frac.shape[0]) if symmetry is not None else None
+        self._reverse_step_to("arreau_reverse_step_sym", frac, types, lengths, angles, t_crystal, s_crystal, offsets, eps, logits, len0,
+                              z_lattice, z_frac, u_types, lattice_out, lattice_clipmax, _hip.ptr(length_tie), _byref(sym))
 
     def resample_jump(self, frac, types, lengths, angles, s_crystal, t_crystal, offsets, z_frac, z_lengths, u_types, lattice_out,
                       const_types=None, fixed_lengths=None, condition=None, length_tie=None):
@@ -629,19 +622,15 @@ class HipEngine:
         tie codes [B] int32 (arreau_resample_jump_tied); None is the jump without them."""
         B, N = lengths.shape[0], frac.shape[0]
         cond = self._condition_struct(condition, N, B) if condition is not None else None
+        name, tie = "arreau_resample_jump", ()
         if length_tie is not None:
             self._check_tie(length_tie, B)
-            _hip.check(_hip.lib().arreau_resample_jump_tied(
-                self._handle, _hip.ptr(frac), _hip.ptr(types), _hip.ptr(lengths), _hip.ptr(angles), _hip.ptr(s_crystal),
-                _hip.ptr(t_crystal), _hip.ptr(offsets), B, N, _hip.ptr(z_frac), _hip.ptr(z_lengths), _hip.ptr(u_types),
-                _hip.ptr(const_types), _hip.ptr(fixed_lengths), ctypes.byref(cond) if cond is not None else None,
-                _hip.ptr(lattice_out), _hip.ptr(length_tie), _hip.stream_ptr(self.device)), "arreau_resample_jump_tied")
-            return
-        _hip.check(_hip.lib().arreau_resample_jump(
+            name, tie = "arreau_resample_jump_tied", (_hip.ptr(length_tie),)
+        _hip.check(getattr(_hip.lib(), name)(
             self._handle, _hip.ptr(frac), _hip.ptr(types), _hip.ptr(lengths), _hip.ptr(angles), _hip.ptr(s_crystal),
             _hip.ptr(t_crystal), _hip.ptr(offsets), B, N, _hip.ptr(z_frac), _hip.ptr(z_lengths), _hip.ptr(u_types),
-            _hip.ptr(const_types), _hip.ptr(fixed_lengths), ctypes.byref(cond) if cond is not None else None,
-            _hip.ptr(lattice_out), _hip.stream_ptr(self.device)), "arreau_resample_jump")
+            _hip.ptr(const_types), _hip.ptr(fixed_lengths), _byref(cond), _hip.ptr(lattice_out), *tie,
+            _hip.stream_ptr(self.device)), name)
 
     def screen(self, frac, lattice, offsets, types=None, criteria=None):
         """The structural screen of a batch on this engine's device (arreau_crystal_screen; diffusion/screening.py: `screen`,
