@@ -14,7 +14,7 @@ a template (`from_template`: the template's Wyckoff structure) or as general pos
 On the device the orbit is kept at every step: the network's position noise is pulled back to the leader and averaged, the leader
 takes the VE reverse update with its own draw, is projected onto its site (the average over H_l of the affine images), and the
 members are the images of the new leader.  Species: the leader draws from the orbit's mean logits, the members copy it.
-`project_leader`, `expand` and `step_positions` restate that in float64; the GPU tests compare the kernels against them."""
+`project_leader`, `expand`, `step_positions` and `step_species` restate that in float64; the GPU tests compare the kernels against them."""
 import re
 from fractions import Fraction
 from typing import List, Optional, Sequence
@@ -295,10 +295,11 @@ class SymmetrySpec:
                                            wrap=False) for o, m in enumerate(self.orbits)])
         return self.expand(xl, wrap=False)
 
-    def step_positions(self, x, eps, z, sigma_t: float, sigma_s: float):
+    def step_positions(self, x, eps, z, sigma_t: float, sigma_s: float, wrap: bool = True):
         """The position part of one symmetric step of this crystal, in float64: x [n,3] the current (on-site) positions, eps
         [n,3] the network's position noise, z [n,3] the step's draws (only the leaders' rows are used), sigma_t / sigma_s the VE
-        sigmas of the timesteps t and s.  Rules 1-4."""
+        sigmas of the timesteps t and s.  Rules 1-4.  wrap=False leaves the leaders and their images unwrapped (which shows
+        the leaders that left the cell, where the anchoring of rule 3 matters)."""
         x, eps, z = (np.asarray(a, dtype=np.float64).reshape(-1, 3) for a in (x, eps, z))
         s2, sp2 = float(sigma_t) ** 2, float(sigma_s) ** 2
         std = np.sqrt(sp2 * (s2 - sp2) / s2)
@@ -307,8 +308,44 @@ class SymmetrySpec:
             l = int(members[0])
             ebar = sum(self.R_inv[self.op[j]] @ eps[j] for j in members) / len(members)
             y = x[l] - ebar * (s2 - sp2) + std * z[l]
-            xl[o] = self.project_leader(o, y, x[l])
-        return self.expand(xl)
+            xl[o] = self.project_leader(o, y, x[l], wrap=wrap)
+        return self.expand(xl, wrap=wrap)
+
+    def step_species(self, logits, types, u, t: int, s: int, q_one_step_transposed, q_mats):
+        """The species part of one symmetric step of this crystal from timestep t to s, in float64 (rule 5): logits [n,S] the
+        network's x0 logits, types [n] the current classes (only the leaders' are used), u [n,S] the step's uniforms (only the
+        leaders' rows are used), q_one_step_transposed [T,S,S] and q_mats [T,S,S] the D3PM tables.  Per orbit: the mean logits
+        over the members in member order; the posterior of the D3PM reverse with the leader's class as x_t -- the raw logits at
+        t = 1, else log(fact1 + 1e-6) + log(fact2 + 1e-6) with fact1 row x_t of q_one_step_transposed[t-1] at stride 1 and column
+        x_t of q_mats[t-s-1] on a strided step, fact2 = softmax . q_mats[s-1]; plus the Gumbel noise of the leader's uniforms
+        clipped to [1e-6, 1], scaled by 0.2 at t = 1; the first arg-max, which every member takes.  Returns (classes int64 [n],
+        margins float64 [n_orbits]: the distance between the two best values)."""
+        lg = np.asarray(logits, dtype=np.float64)
+        ty = np.asarray(types).reshape(-1).astype(np.int64)
+        un = np.asarray(u, dtype=np.float64)
+        q1t, qm = np.asarray(q_one_step_transposed, dtype=np.float64), np.asarray(q_mats, dtype=np.float64)
+        t, s = int(t), int(s)
+        out = np.empty(self.n_atoms, dtype=np.int64)
+        margins = np.empty(len(self.orbits))
+        for o, members in enumerate(self.orbits):
+            l = int(members[0])
+            mean = np.zeros(lg.shape[1])
+            for j in members:
+                mean += lg[int(j)]
+            mean /= len(members)
+            if t == 1:
+                post = mean
+            else:
+                xt = int(ty[l])
+                fact1 = q1t[t - 1, xt, :] if s == t - 1 else qm[t - s - 1][:, xt]
+                p = np.exp(mean - mean.max())
+                fact2 = (p / p.sum()) @ qm[s - 1]
+                post = np.log(fact1 + 1e-6) + np.log(fact2 + 1e-6)
+            val = post - np.log(-np.log(np.clip(un[l], 1e-6, 1.0))) * (0.2 if t == 1 else 1.0)
+            best = int(np.argmax(val))  # (the first of equal values)
+            out[members] = best
+            margins[o] = val[best] - np.delete(val, best).max() if val.shape[0] > 1 else np.inf
+        return out, margins
 
     def check_species(self, types, what="constant species"):
         """Raise ValueError unless the species [n] are constant on every orbit."""
