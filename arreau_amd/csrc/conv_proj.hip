@@ -550,8 +550,14 @@ __global__ __launch_bounds__(64 * (PW + 4), (PW + 4) / 4) void conv_proj_kernel(
                 for (int oo = 0; oo < 2; ++oo) {
                     const int o = 2 * s + oo;
                     const float xo = tv[o];
+                    // (one v_fmac_f32 per value, pinned: left alone hipcc's SLP pass pairs them into v_pk_fma_f32, which on a SIMD
+                    // shared with a projection wave measured slower -- profiles/r06b_conv_proj_unpacked_mix_ab.txt; the same fused
+                    // multiply-adds in the same order either way: bit-identical)
 #pragma unroll
-                    for (int p = 0; p < 8; ++p) out[p] = fmaf(xo, fkr[o][p], out[p]);
+                    for (int p = 0; p < 8; ++p) {
+                        out[p] = fmaf(xo, fkr[o][p], out[p]);
+                        asm volatile("" : "+v"(out[p]));
+                    }
                 }
                 if (s == K - 1) {
                     store_out(n_prev, out);
