@@ -30,6 +30,7 @@ EXPORTS = [
     "arreau_sample_loop_resampled", "arreau_resample_jump", "arreau_optimizer_step_ema",
     "arreau_sample_loop_tied", "arreau_reverse_step_tied", "arreau_resample_jump_tied",
     "arreau_sample_loop_sym", "arreau_reverse_step_sym", "arreau_crystal_screen",
+    "arreau_crystal_fingerprint", "arreau_fingerprint_match",
 ]
 
 STATUS_NONFINITE, STATUS_BAD_TIMESTEP, STATUS_BAD_TYPE, STATUS_BAD_TIE, STATUS_BAD_SYMMETRY = 1, 2, 4, 8, 16
@@ -89,6 +90,21 @@ class ScreenCriteriaC(Structure):
 class ScreenResultC(Structure):
     """arreau_screen_result: the six device arrays the screen writes, one entry per crystal."""
     _fields_ = [(name, c_void_p) for name in ("min_distance", "pair", "n_close", "volume", "number_density", "flags")]
+
+
+class FingerprintParamsC(Structure):
+    """arreau_fingerprint_params: the radial grid and smearing of the structure fingerprint."""
+    _fields_ = [("r_max", c_float), ("sigma", c_float), ("n_bins", c_int32), ("max_shells", c_int32)]
+
+
+class FingerprintResultC(Structure):
+    """arreau_fingerprint_result: the four device arrays of a fingerprinted set, one row per crystal."""
+    _fields_ = [(name, c_void_p) for name in ("fingerprint", "species", "counts", "flags")]
+
+
+class MatchResultC(Structure):
+    """arreau_match_result: the four device arrays the match writes, one entry per crystal of X."""
+    _fields_ = [(name, c_void_p) for name in ("duplicate_of", "distance", "nearest", "nearest_distance")]
 
 
 class Config(Structure):
@@ -162,6 +178,8 @@ def _prototypes():
         "arreau_philox_fill": [u64, i32, i32, i64, vp, vp, vp],
         "arreau_philox_fill_word": [u64, i32, i32, u32, i64, vp, vp, vp],
         "arreau_crystal_screen": [vp] * 4 + [i32, i32, POINTER(ScreenCriteriaC), POINTER(ScreenResultC), vp],
+        "arreau_crystal_fingerprint": [vp] * 4 + [i32, i32, POINTER(FingerprintParamsC), POINTER(FingerprintResultC), vp],
+        "arreau_fingerprint_match": [POINTER(FingerprintResultC), i32, POINTER(FingerprintResultC), i32, f32, POINTER(MatchResultC), vp],
         "arreau_train_forward": [vp] * 7 + [i32, i32] + [vp] * 4,
         "arreau_train_backward": [vp] * 4 + [POINTER(StateDict), vp],
         "arreau_train_conv_stats": [vp, vp, vp],

@@ -4,36 +4,13 @@
 // pairs.  One launch, one workgroup of four waves per crystal, no atomics; needs no arreau_model.
 #include "internal.h"
 #include "graph_dev.h"
+#include "crystal_dev.h"
 #include <cmath>
 
 #define SCREEN_LDS_ATOMS 256  // crystals of up to this many atoms keep their Cartesian positions in LDS (3 KiB)
 #define SCREEN_WAVES 4
 
 namespace {
-
-// every fp32 operation below is spelled out (__fmul_rn / __fadd_rn / __fsub_rn / __fdiv_rn): one rounding each, no contraction
-// to an FMA, so that the float32 host restatement (arreau_amd/diffusion/screening.py) matches bit for bit
-__device__ __forceinline__ float dot3_rn(float ax, float ay, float az, float bx, float by, float bz) {
-    return __fadd_rn(__fadd_rn(__fmul_rn(ax, bx), __fmul_rn(ay, by)), __fmul_rn(az, bz));
-}
-
-__device__ __forceinline__ void cross_rn(const float* u, const float* v, float* o) {
-    o[0] = __fsub_rn(__fmul_rn(u[1], v[2]), __fmul_rn(u[2], v[1]));
-    o[1] = __fsub_rn(__fmul_rn(u[2], v[0]), __fmul_rn(u[0], v[2]));
-    o[2] = __fsub_rn(__fmul_rn(u[0], v[1]), __fmul_rn(u[1], v[0]));
-}
-
-// w = f - floor(f), a result of 1 (a tiny negative f) becomes 0; then arreau_cart_component's expression on the wrapped
-// coordinates, uncontracted
-__device__ __forceinline__ float screen_wrap(float f) {
-    const float w = __fsub_rn(f, floorf(f));
-    return w >= 1.0f ? 0.0f : w;
-}
-
-__device__ __forceinline__ float screen_cart(const float* __restrict__ frac, const float* Lm, size_t atom, int d) {
-    const float w0 = screen_wrap(frac[3 * atom]), w1 = screen_wrap(frac[3 * atom + 1]), w2 = screen_wrap(frac[3 * atom + 2]);
-    return __fadd_rn(__fadd_rn(__fmul_rn(w0, Lm[d]), __fmul_rn(w1, Lm[3 + d])), __fmul_rn(w2, Lm[6 + d]));
-}
 
 __global__ __launch_bounds__(64 * SCREEN_WAVES) void crystal_screen_kernel(
     const float* __restrict__ frac, const int32_t* __restrict__ types, const float* __restrict__ lattice,
@@ -106,9 +83,9 @@ __global__ __launch_bounds__(64 * SCREEN_WAVES) void crystal_screen_kernel(
     // ---- positions: staged in LDS when the crystal fits, else formed from global memory where they are used (same values)
     const bool staged = n <= SCREEN_LDS_ATOMS;
     if (staged)
-        for (int a = tid; a < 3 * n; a += 64 * SCREEN_WAVES) spos[a] = screen_cart(frac, Lm, (size_t)first + a / 3, a % 3);
+        for (int a = tid; a < 3 * n; a += 64 * SCREEN_WAVES) spos[a] = crystal_cart(frac, Lm, (size_t)first + a / 3, a % 3);
     __syncthreads();
-    auto position = [&](int atom, int d) -> float { return staged ? spos[3 * atom + d] : screen_cart(frac, Lm, (size_t)first + atom, d); };
+    auto position = [&](int atom, int d) -> float { return staged ? spos[3 * atom + d] : crystal_cart(frac, Lm, (size_t)first + atom, d); };
 
     // ---- the search.  Receiver i (uniform), then the flattened (j >= i, image m) range dealt to the 256 threads: every thread
     // meets its contacts in ascending (i, j, m), so a strict "<" on the bits of d2 keeps the first of equal minima.

@@ -15,6 +15,7 @@ from . import corrector as pc
 from . import resampling as rs
 from . import respacing
 from . import screening
+from . import uniqueness as uniqueness_mod
 from .d3pm import D3PM
 from . import lattice_systems
 from . import symmetry as sym_mod
@@ -44,6 +45,9 @@ class SampleResult:
     # extension: the structural screen of the final state (sample(screen=...); diffusion/screening.py) -- numpy arrays min_distance,
     # pair, n_close, volume, number_density, flags and valid, one entry per crystal; None when no screen was asked for
     metrics: Optional[dict] = None
+    # extension: duplicate detection on the final state (sample(unique=...); diffusion/uniqueness.py) -- numpy arrays duplicate_of,
+    # distance, nearest, nearest_distance, flags and unique, one entry per crystal; None when it was not asked for
+    uniqueness: Optional[dict] = None
 
 
 class _PinnedRing:
@@ -268,7 +272,7 @@ class DiffusionLoss(nn.Module):
                fixed_cell: bool = False, condition=None, num_steps: Optional[int] = None,
                timesteps: Optional[Sequence[int]] = None, corrector_steps: int = 0,
                corrector_snr: float = pc.DEFAULT_SNR, resample_passes: int = 1, jump_length: int = 10,
-               lattice_system=None, symmetry=None, screen=None) -> SampleResult:
+               lattice_system=None, symmetry=None, screen=None, unique=None) -> SampleResult:
         """diffusion_loss.py:276-377.  The initial state is drawn on the host exactly like the reference (numpy
         uniforms for the angles, then randn lengths, randn fractional coordinates from torch's global CPU generator).
         Per-step noise:
@@ -334,8 +338,14 @@ class DiffusionLoss(nn.Module):
         device state is screened in one launch before it is copied back (arreau_crystal_screen; rules in include/arreau_hip.h):
         shortest contact over all periodic images, cell volume, number density, mask state.  SampleResult.metrics then holds the
         six arrays and `valid`.  A criteria without a mask_type checks for the D3PM mask state S - 1, or for none when
-        constant_atoms is given.  None: no launch is added, metrics is None and the results are what they were, bit for bit."""
+        constant_atoms is given.  None: no launch is added, metrics is None and the results are what they were, bit for bit.
+        `unique` (extension, every noise mode and option): a uniqueness.FingerprintParams, or True for its defaults -- two more
+        launches on the final device state (arreau_crystal_fingerprint, arreau_fingerprint_match) give every crystal a structure
+        fingerprint and the earliest crystal of the batch it duplicates; the class indices are the species ids.
+        SampleResult.uniqueness then holds duplicate_of, distance, nearest, nearest_distance, flags and unique.  None: no launch
+        is added and uniqueness is None."""
         screen = screening.resolve(screen)
+        unique = uniqueness_mod.resolve(unique)
         frames = visualization_setting != VisualizationSetting.NONE
         if frames and not vis_name:
             raise ValueError("visualization_setting other than NONE needs vis_name (prefix of the frame files)")
@@ -577,7 +587,10 @@ class DiffusionLoss(nn.Module):
         if screen is not None:  # the final state, where it is: one launch, then the host copies below
             crit = screen.with_mask_type(-1 if constant_atoms is not None else S - 1)
             metrics = screening.metrics_to_numpy(eng.screen(frac_d, lattice_d, off_d, types_d, crit))
+        uniqueness = None
+        if unique is not None:
+            uniqueness = uniqueness_mod.uniqueness_to_numpy(uniqueness_mod.unique_batch(frac_d, lattice_d, off_d, types_d, unique))
         atomic_numbers = atomic_number_indexes_to_atomic_numbers(z_table, types_d.cpu().numpy())
         return SampleResult(num_atoms=num_atoms.numpy(), frac_x=frac_d.cpu().numpy().astype(np.float64),
                             atomic_numbers=atomic_numbers, lattice=lattice_d.cpu().numpy().astype(np.float64), info=info,
-                            metrics=metrics)
+                            metrics=metrics, uniqueness=uniqueness)

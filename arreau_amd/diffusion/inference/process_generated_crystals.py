@@ -11,7 +11,9 @@ with the same five keys otherwise.
 A result that carries the structural screen's metrics (SampleResult.metrics, diffusion/screening.py) gets seven more arrays,
 one entry per crystal: screen_min_distance, screen_pair [B,5], screen_n_close, screen_volume, screen_number_density,
 screen_flags, screen_valid.  Readers of the five keys above are not affected; a result without metrics is written with
-exactly those five."""
+exactly those five.  A result that carries duplicate detection's arrays (SampleResult.uniqueness, diffusion/uniqueness.py) gets
+six more in the same way: unique_duplicate_of, unique_distance, unique_nearest, unique_nearest_distance, unique_flags,
+unique_unique; without them none is written."""
 import os
 
 import numpy as np
@@ -21,6 +23,8 @@ from ..diffusion_loss import SampleResult
 KEYS = ("frac_x", "atomic_numbers", "lattice", "idx_start", "num_atoms")
 METRIC_KEYS = ("min_distance", "pair", "n_close", "volume", "number_density", "flags", "valid")
 METRIC_PREFIX = "screen_"
+UNIQUE_KEYS = ("duplicate_of", "distance", "nearest", "nearest_distance", "flags", "unique")
+UNIQUE_PREFIX = "unique_"
 _DTYPES = dict(frac_x=np.float64, atomic_numbers=np.float64, lattice=np.float64, idx_start=np.int64,
                num_atoms=np.int64)
 
@@ -46,14 +50,23 @@ def _fields(crystals: SampleResult):
             if v.shape != ((B, 5) if k == "pair" else (B,)):
                 raise ValueError(f"SampleResult.metrics[{k!r}] does not hold one entry per crystal")
             out[METRIC_PREFIX + k] = v
+    uniqueness = getattr(crystals, "uniqueness", None)
+    if uniqueness is not None:
+        for k in UNIQUE_KEYS:
+            if k not in uniqueness:
+                raise ValueError(f"SampleResult.uniqueness[{k!r}] is missing")
+            v = np.asarray(uniqueness[k])
+            if v.shape != (B,):
+                raise ValueError(f"SampleResult.uniqueness[{k!r}] does not hold one entry per crystal")
+            out[UNIQUE_PREFIX + k] = v
     return out
 
 
-def _metrics_from(has, get):
-    """The metrics dict of a file's screen_* arrays, or None when the file has none."""
-    if not all(has(METRIC_PREFIX + k) for k in METRIC_KEYS):
+def _metrics_from(has, get, prefix=METRIC_PREFIX, keys=METRIC_KEYS):
+    """The metrics dict of a file's screen_* arrays (or the uniqueness dict of its unique_* arrays), or None when the file has none."""
+    if not all(has(prefix + k) for k in keys):
         return None
-    return {k: get(METRIC_PREFIX + k) for k in METRIC_KEYS}
+    return {k: get(prefix + k) for k in keys}
 
 
 def _is_h5(filename):
@@ -83,11 +96,13 @@ def load_sample_results_from_hdf5(filename: str) -> SampleResult:
         with h5py.File(filename, "r") as fh:
             data = {k: fh["crystals"][k][:] for k in KEYS}
             metrics = _metrics_from(lambda k: k in fh["crystals"], lambda k: fh["crystals"][k][:])
+            uniqueness = _metrics_from(lambda k: k in fh["crystals"], lambda k: fh["crystals"][k][:], UNIQUE_PREFIX, UNIQUE_KEYS)
     else:
         with np.load(filename) as z:
             data = {k: z[k] for k in KEYS}
             metrics = _metrics_from(lambda k: k in z.files, lambda k: z[k])
-    return SampleResult(**data, metrics=metrics)
+            uniqueness = _metrics_from(lambda k: k in z.files, lambda k: z[k], UNIQUE_PREFIX, UNIQUE_KEYS)
+    return SampleResult(**data, metrics=metrics, uniqueness=uniqueness)
 
 
 def get_crystal_indexes(sample_result: SampleResult, sample_idx: int):

@@ -33,6 +33,11 @@ the device at the end of its sampling call -- shortest contact over all periodic
 (diffusion/screening.py) --, prints accepted / attempted and the count per flag for every rank and in total, and stores the
 metrics as screen_* arrays in the output file.  `--require_valid [--max_rounds R]` (implies --screen) keeps generating until every
 rank has its share of VALID crystals, or R rounds have passed (generate_valid_crystals); a shortfall is reported, not padded.
+
+Duplicate detection: `--unique` (`--fp_r_max`, `--fp_sigma`, `--fp_tolerance`) fingerprints the crystals on the device
+(diffusion/uniqueness.py).  Every rank reports unique / attempted within its own crystals; rank 0, after the gather of host arrays,
+matches the whole set once on its own GPU, prints the total and stores those arrays as unique_* in the output file.  May be
+combined with --screen / --require_valid; the two do not interact.
 """
 import argparse
 import os
@@ -51,9 +56,14 @@ def shard_range(num_items: int, world_size: int, rank: int):
 
 
 def _screen_stats(parts):
-    """The per-rank screen statistics the parts carry (SampleResult.info["screen_stats"]), in one list; None when none does."""
-    stats = [st for p in parts if p is not None and p.info for st in p.info.get("screen_stats", [])]
-    return {"screen_stats": stats} if stats else None
+    """The per-rank screen and uniqueness statistics the parts carry (SampleResult.info["screen_stats"] / ["unique_stats"]), each
+    in one list; None when no part has any."""
+    out = {}
+    for key in ("screen_stats", "unique_stats"):
+        stats = [st for p in parts if p is not None and p.info for st in p.info.get(key, [])]
+        if stats:
+            out[key] = stats
+    return out or None
 
 
 def concat_results(parts) -> SampleResult:
@@ -124,10 +134,13 @@ def template_batches(num_crystals: int, batch: int, rank: int = 0, world_size: i
     return [(s, min(s + batch, stop)) for s in range(start, stop, batch)]
 
 
-def _gather_results(local: SampleResult, rank: int, world_size: int, gather: Optional[Callable]):
+def _gather_results(local: SampleResult, rank: int, world_size: int, gather: Optional[Callable], unique=None):
     if local.metrics is not None and not (local.info or {}).get("screen_stats"):  # a screened run: this rank's statistics
         from .diffusion.screening import stats_of
         local.info = dict(local.info or {}, screen_stats=[stats_of(local.metrics["flags"], rank)])
+    if unique is not None:  # duplicates within this rank's crystals, on its own device
+        from .diffusion import uniqueness
+        local.info = dict(local.info or {}, unique_stats=[uniqueness.stats_of(uniqueness.unique_sample_result(local, unique), rank)])
     if world_size == 1:
         return local
     if gather is None:
@@ -142,28 +155,29 @@ def _gather_results(local: SampleResult, rank: int, world_size: int, gather: Opt
 
 
 def generate_from_template(sample_fn: Callable, condition, num_crystals_per_batch: int = 256, rank: int = 0,
-                           world_size: int = 1, gather: Optional[Callable] = None) -> Optional[SampleResult]:
+                           world_size: int = 1, gather: Optional[Callable] = None, unique=None) -> Optional[SampleResult]:
     """sample_fn(condition) -> SampleResult (e.g. PONITA_DIFFUSION.sample(condition=...)) over this rank's slice of the
-    condition's crystals.  Returns the concatenated result on rank 0 (None elsewhere when world_size > 1)."""
+    condition's crystals.  Returns the concatenated result on rank 0 (None elsewhere when world_size > 1).  `unique` (a
+    uniqueness.FingerprintParams): every rank also counts the duplicates among its own crystals (info["unique_stats"])."""
     mine = [sample_fn(condition.slice(a, b)) for a, b in template_batches(condition.B, num_crystals_per_batch, rank, world_size)]
-    return _gather_results(concat_results(mine), rank, world_size, gather)
+    return _gather_results(concat_results(mine), rank, world_size, gather, unique)
 
 
 def generate_n_crystals(sample_fn: Callable[[int, int], SampleResult], num_crystals: int, num_atoms_per_sample: int,
                         num_crystals_per_batch: int = 256, rank: int = 0, world_size: int = 1,
-                        gather: Optional[Callable] = None) -> Optional[SampleResult]:
+                        gather: Optional[Callable] = None, unique=None) -> Optional[SampleResult]:
     """sample_fn(num_atoms_per_sample, num_samples_in_batch) -> SampleResult  (e.g. PONITA_DIFFUSION.sample).
-    Returns the concatenated result on rank 0 (None elsewhere when world_size > 1)."""
+    Returns the concatenated result on rank 0 (None elsewhere when world_size > 1).  `unique`: as in generate_from_template."""
     start, stop = shard_range(num_crystals, world_size, rank)
     mine = []
     for s in range(start, stop, num_crystals_per_batch):
         mine.append(sample_fn(num_atoms_per_sample, min(num_crystals_per_batch, stop - s)))
-    return _gather_results(concat_results(mine), rank, world_size, gather)
+    return _gather_results(concat_results(mine), rank, world_size, gather, unique)
 
 
 def generate_valid_crystals(sample_fn: Callable[[int, int], SampleResult], num_crystals: int, num_atoms_per_sample: int,
                             num_crystals_per_batch: int = 256, rank: int = 0, world_size: int = 1,
-                            gather: Optional[Callable] = None, max_rounds: int = 10) -> Optional[SampleResult]:
+                            gather: Optional[Callable] = None, max_rounds: int = 10, unique=None) -> Optional[SampleResult]:
     """generate_n_crystals that returns VALID crystals only.  sample_fn(num_atoms_per_sample, num_samples_in_batch) ->
     SampleResult WITH metrics (e.g. PONITA_DIFFUSION.sample(..., screen=criteria)).  Every rank refills its own shard_range slice: in
     each round it samples as many crystals as it still misses (in sub-batches of at most num_crystals_per_batch), keeps the
@@ -195,7 +209,7 @@ def generate_valid_crystals(sample_fn: Callable[[int, int], SampleResult], num_c
     if have < want:
         warnings.warn(f"generate_valid_crystals: rank {rank} has {have} valid crystals of the {want} requested after {rounds} "
                       f"round(s); the result is {want - have} short")
-    return _gather_results(local, rank, world_size, gather)
+    return _gather_results(local, rank, world_size, gather, unique)
 
 
 def save_sample_results(crystals: SampleResult, filename: str):
@@ -274,7 +288,39 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--require_valid", action="store_true",
                     help="keep generating until every rank has its share of valid crystals (implies --screen; not with --template)")
     ap.add_argument("--max_rounds", type=int, default=10, help="--require_valid: refill rounds per rank (>= 1)")
+    ap.add_argument("--unique", action="store_true",
+                    help="duplicate detection on the device: unique / attempted per rank and in total + unique_* arrays in the output file")
+    add_fingerprint_arguments(ap)
     return ap
+
+
+def add_fingerprint_arguments(ap):
+    """The fingerprint flags shared with `python -m arreau_amd.screen`."""
+    ap.add_argument("--fp_r_max", type=float, default=6.0, help="unique: the fingerprint covers distances up to this many A")
+    ap.add_argument("--fp_sigma", type=float, default=0.1, help="unique: Gaussian smearing of a contact, A")
+    ap.add_argument("--fp_tolerance", type=float, default=0.01, help="unique: crystals of one formula within this distance (1 - cos) / 2 are duplicates")
+
+
+def fingerprint_params(args, error):
+    """The FingerprintParams of the fingerprint flags; `error(message)` reports a bad value."""
+    from .diffusion.uniqueness import FingerprintParams
+    try:
+        return FingerprintParams(r_max=args.fp_r_max, sigma=args.fp_sigma, tolerance=args.fp_tolerance)
+    except ValueError as e:
+        error(f"fingerprint parameters: {e}")
+
+
+def unique_lines(res, params, against=None, device="cuda"):
+    """Match the whole set once (with itself; with `against`, also with that set) and return the lines to print: the per-rank
+    lines the parts carried, the total, and the novelty line.  Stores the whole-set arrays in res.uniqueness."""
+    from .diffusion import uniqueness
+    res.uniqueness = uniqueness.unique_sample_result(res, params, device=device)
+    parts = sorted((res.info or {}).get("unique_stats", []), key=lambda st: st["rank"])
+    lines = [uniqueness.format_stats(st) for st in parts] + [uniqueness.format_stats(uniqueness.stats_of(res.uniqueness, "total"))]
+    if against is not None:
+        novel = uniqueness.unique_sample_result(res, params, against=against, device=device)
+        lines.append(uniqueness.format_stats(uniqueness.stats_of(novel, "total"), "novel") + f"; against {len(against.num_atoms)} crystals")
+    return lines
 
 
 def add_screen_arguments(ap):
@@ -343,6 +389,7 @@ def main():
     args = ap.parse_args()
     spec = load_symmetry(args, ap.error)
     criteria = check_screen_arguments(args, ap.error)
+    unique = fingerprint_params(args, ap.error) if args.unique else None
     condition = load_template(args.template, parse_fix(args.fix)).tile(args.samples_per_template) if args.template else None
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -392,17 +439,20 @@ def main():
             finally:
                 fcntl.flock(lock, fcntl.LOCK_UN)
     if condition is not None:
-        res = generate_from_template(lambda c: fn(None, None, c), condition, args.batch, rank, world)
+        res = generate_from_template(lambda c: fn(None, None, c), condition, args.batch, rank, world, unique=unique)
     elif args.require_valid:
         res = generate_valid_crystals(fn, args.num_crystals, spec.n_atoms if spec is not None else args.num_atoms, args.batch, rank,
-                                      world, max_rounds=args.max_rounds)
+                                      world, max_rounds=args.max_rounds, unique=unique)
     else:
         res = generate_n_crystals(fn, args.num_crystals, spec.n_atoms if spec is not None else args.num_atoms, args.batch, rank,
-                                  world)
+                                  world, unique=unique)
     if rank == 0:
         if criteria is not None:
             from .diffusion.screening import summary_lines
             for line in summary_lines((res.info or {}).get("screen_stats", [])):
+                print(line)
+        if unique is not None:
+            for line in unique_lines(res, unique, device=f"cuda:{local_rank}"):
                 print(line)
         print("wrote", save_sample_results(res, args.out))
     if world > 1:

@@ -1,38 +1,56 @@
 """Screen an existing file of crystals on the GPU: generated crystals or a training set in the crystals.npz / .h5 layout.
 
     python -m arreau_amd.screen out/crystals.npz [--min_distance 0.5] [--min_volume 0.1] [--search_radius 3.0] [--out screened.npz]
+    python -m arreau_amd.screen out/crystals.npz --unique [--against train.npz] [--fp_r_max 6] [--fp_sigma 0.1] [--fp_tolerance 0.01]
 
 Prints the summary `python -m arreau_amd.generate --screen` prints (accepted / attempted and the count per flag) and, with
 `--out`, writes the crystals again with the screen_* arrays (diffusion/inference/process_generated_crystals.py).  The species
 check looks for the mask state's atomic number (2001).  The rules are in include/arreau_hip.h (arreau_crystal_screen).
+`--unique` adds duplicate detection (diffusion/uniqueness.py): unique / attempted of the file, the unique_* arrays with `--out`,
+and with `--against FILE` the novelty -- the share of crystals with no match in that other set.
 """
 import argparse
 
 
 def build_parser() -> argparse.ArgumentParser:
-    from .generate import add_screen_arguments
+    from .generate import add_fingerprint_arguments, add_screen_arguments
     ap = argparse.ArgumentParser(prog="python -m arreau_amd.screen", description="structural screen of a crystals file")
     ap.add_argument("file", type=str, help="crystals.npz / .h5")
     add_screen_arguments(ap)
     ap.add_argument("--out", type=str, default=None, help="write the crystals with their screen_* arrays to this file")
     ap.add_argument("--device", type=str, default="cuda")
+    ap.add_argument("--unique", action="store_true", help="also detect duplicates within the file")
+    ap.add_argument("--against", type=str, default=None, help="--unique: a second crystals file (e.g. the training set) for novelty")
+    add_fingerprint_arguments(ap)
     return ap
 
 
 def main(argv=None):
     from .diffusion import screening
     from .diffusion.inference.process_generated_crystals import load_sample_results_from_hdf5, save_sample_results_to_hdf5
-    from .generate import screen_criteria
+    from .generate import fingerprint_params, screen_criteria, unique_lines
     ap = build_parser()
     args = ap.parse_args(argv)
     criteria = screen_criteria(args, ap.error)
-    try:
-        res = load_sample_results_from_hdf5(args.file)
-    except (OSError, KeyError) as e:
-        ap.error(f"{args.file}: {e}")
+    if args.against is not None and not args.unique:
+        ap.error("--against needs --unique")
+    unique = fingerprint_params(args, ap.error) if args.unique else None
+
+    def load(name):
+        try:
+            return load_sample_results_from_hdf5(name)
+        except (OSError, KeyError) as e:
+            ap.error(f"{name}: {e}")
+
+    res = load(args.file)
+    against = load(args.against) if args.against is not None else None
     res.metrics = screening.screen_sample_result(res, criteria, args.device)
     for line in screening.summary_lines([screening.stats_of(res.metrics["flags"])]):
         print(line)
+    if unique is not None:
+        res.info = None  # (no per-rank parts: the file is one set)
+        for line in unique_lines(res, unique, against, args.device):
+            print(line)
     if args.out:
         print("wrote", save_sample_results_to_hdf5(res, args.out))
     return res

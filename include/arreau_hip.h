@@ -291,6 +291,76 @@ int arreau_crystal_screen(const float* d_frac, const int32_t* d_types /* may be 
                           const int32_t* d_crystal_offsets, int32_t B, int32_t N, const arreau_screen_criteria* crit,
                           arreau_screen_result* out /* device arrays, each [B] (pair: [B,5]) */, void* stream);
 
+/* ---- duplicate detection: structure fingerprints and their all-pairs match ------------------------------------------
+ * The screen's sibling: per crystal a reduced formula and a fingerprint of its pair distribution (Oganov & Valle, J. Chem.
+ * Phys. 130, 104504 (2009), with the normalisation taken at the bin centre so that it is finite for every input), and for
+ * every crystal of a set the earliest crystal of that set -- or of another set -- it duplicates.  Two launches, no atomics,
+ * no arreau_model, nothing copied to the host; no order of summation depends on the batch or the grid, so a crystal's row is
+ * the same bits wherever it sits.
+ *   1. reduced formula: the distinct species ids of the crystal (d_types: any int32, non-negative by convention -- class
+ *      indices in the sampler, atomic numbers in a file) sorted ascending, at most ARREAU_FP_MAX_SPECIES; their counts N_A
+ *      divided by the gcd of the counts.  species is padded with -1, counts with 0.  Two crystals are COMPARABLE when neither
+ *      is flagged and both arrays are equal (the arrays are compared, not a hash).
+ *   2. parameters r_max, n_bins (1..ARREAU_FP_BINS), sigma: delta = r_max / n_bins, R_k = (k + 1/2) delta, cut-off
+ *      r_cut = (float)((double)r_max + 5 (double)sigma).
+ *   3. contacts are enumerated exactly as arreau_crystal_screen enumerates them (its rules 1, 4, 5, 6 with search_radius =
+ *      r_cut, the same float32 operations): wrapped positions, pairs i <= j, every image for i < j and the images after
+ *      (0, 0, 0) for i == j, shells per axis from the plane spacings.  R = sqrt(d2) (correctly rounded); a contact counts
+ *      when d2 < (float)((double)r_cut * r_cut).
+ *   4. a contact between species ranks A <= B adds c g(R_k - R) to EVERY bin k of component (A, B), g(x) = exp(-x^2 /
+ *      (2 sigma^2)) / (sigma sqrt(2 pi)), c = 1 for A != B and 2 for A == B (the ordered double sum meets such a contact
+ *      twice).  Every (component, bin) cell adds its contacts in the enumeration order (i, j, m), one float32 accumulator.
+ *   5. F_AB[k] = V S_AB[k] / (4 pi R_k^2 N_A N_B) - 1 (V the cell volume, N_A the unreduced counts); weights w_AB = N_A N_B /
+ *      N^2; |F|_w^2 = sum_AB sum_k w_AB F_AB[k]^2 (a fixed-order sum); the stored vector is f_AB[k] = sqrt(w_AB) F_AB[k] /
+ *      |F|_w, a unit vector.  Component (A, B) lies at index B (B + 1) / 2 + A of the row; the row has the fixed stride
+ *      ARREAU_FP_ROW = 36 x 64 floats, unused components and bins >= n_bins are zero.
+ *   6. flags (a flagged crystal has a zero row, species -1, counts 0, and neither matches nor is matched): NONFINITE a cell
+ *      entry or a coordinate is inf / NaN (no other flag is then computed); EMPTY no atoms; MANY_SPECIES more than 8 distinct
+ *      species; CELL volume not finite or not positive, or more than max_shells (1..8) images needed on an axis.
+ *   7. distance d(x, y) = (1 - f_x . f_y) / 2, the dot product in float32 in ascending index order.  By construction it is
+ *      invariant under atom permutation, a common translation, lattice translations of single atoms, rigid rotation, a change
+ *      of cell basis and supercells (N_A N_B / V and the sum scale together).
+ *   8. match of set X against set Y (NULL: X itself, and then only candidates a < x): duplicate_of = the smallest index a of
+ *      Y comparable with x and d <= tolerance, else -1; distance = d to it (+inf when none); nearest / nearest_distance = the
+ *      comparable candidate of smallest d, ties to the smaller index (-1 / +inf when none).  In self mode a crystal is UNIQUE
+ *      when duplicate_of < 0 and flags == 0: the first member of each cluster is kept.
+ * Offsets outside [0, N] or descending are clamped as in the screen.  Neither call synchronises.
+ * Argument errors (ARREAU_EINVAL, nothing launched): NULL params / result / arrays, negative sizes, n_bins outside 1..64,
+ * r_max or sigma not finite or not positive, max_shells outside 1..8, tolerance outside [0, 1]. */
+#define ARREAU_FP_NONFINITE 1
+#define ARREAU_FP_CELL 2
+#define ARREAU_FP_MANY_SPECIES 4
+#define ARREAU_FP_EMPTY 8
+#define ARREAU_FP_MAX_SPECIES 8
+#define ARREAU_FP_BINS 64
+#define ARREAU_FP_COMPONENTS 36
+#define ARREAU_FP_ROW (ARREAU_FP_COMPONENTS * ARREAU_FP_BINS)
+typedef struct arreau_fingerprint_params {
+    float r_max;         /* A; default 6 */
+    float sigma;         /* A; default 0.1 */
+    int32_t n_bins;      /* 1..ARREAU_FP_BINS; default 64 */
+    int32_t max_shells;  /* cap on the images per axis, 1..ARREAU_SCREEN_MAX_SHELLS; default 8 */
+} arreau_fingerprint_params;
+typedef struct arreau_fingerprint_result { /* DEVICE arrays, one row per crystal: what the fingerprint writes, what the match reads */
+    float* fingerprint;  /* [B, ARREAU_FP_ROW] */
+    int32_t* species;    /* [B, 8] ascending, padded with -1 */
+    int32_t* counts;     /* [B, 8] reduced counts, padded with 0 */
+    int32_t* flags;      /* [B]    ARREAU_FP_* */
+} arreau_fingerprint_result;
+typedef struct arreau_match_result { /* DEVICE arrays, one entry per crystal of X */
+    int32_t* duplicate_of;
+    float* distance;
+    int32_t* nearest;
+    float* nearest_distance;
+} arreau_match_result;
+/* d_frac[N,3], d_types[N] species ids (required), d_lattice[B,3,3] rows a, b, c.  `params` and `out` are HOST pointers. */
+int arreau_crystal_fingerprint(const float* d_frac, const int32_t* d_types, const float* d_lattice, const int32_t* d_crystal_offsets,
+                               int32_t B, int32_t N, const arreau_fingerprint_params* params, arreau_fingerprint_result* out,
+                               void* stream);
+/* x, y: HOST pointers to the structs of two fingerprinted sets (y NULL: x against itself, By ignored); out: device arrays [Bx]. */
+int arreau_fingerprint_match(const arreau_fingerprint_result* x, int32_t Bx, const arreau_fingerprint_result* y, int32_t By,
+                             float tolerance, arreau_match_result* out, void* stream);
+
 /* ---- the score network ---------------------------------------------------------------------- */
 
 /* One evaluation of DiffusionLoss.predict_scores (diffusion/diffusion_loss.py:112-197):
