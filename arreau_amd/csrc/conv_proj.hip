@@ -1,4 +1,4 @@
-// K3+K4a fused per layer (round 3): kernel projection + message passing + spherical convolution of ONE layer, without the
+// Kernels 3 + 4a of SURVEY.md fused per layer (round 3): kernel projection + message passing + spherical convolution of ONE layer, without the
 // K round trip through HBM.
 //
 //   K_l[(n,s,o), c] = sum_d basis[(n,s,o), d] * Wk_l[c, d]                    (ponita/nn/conv.py:110)

@@ -1,4 +1,4 @@
-// K2+K3: pair invariants -> polynomial features -> basis MLP -> window -> per-layer kernel
+// Kernels 2 + 3 of SURVEY.md: pair invariants -> polynomial features -> basis MLP -> window -> per-layer kernel
 // projection, fused in registers, one wave per 64 (edge, orientation) rows.
 //
 // Replaces, per denoising step (sizes for B=256, n=20: 655 360 rows):
@@ -11,39 +11,7 @@
 #include <utility>
 
 #include "internal.h"
-
-// ---- compile-time monomial table: index f -> (degree, i, j, k), canonical order ----------------
-struct MonoIdx { int n, i, j, k; };
-__host__ __device__ constexpr MonoIdx mono_idx(int f) {
-    int p = 0;
-    for (int i = 0; i < 6; ++i, ++p)
-        if (p == f) return {1, i, 0, 0};
-    for (int i = 0; i < 6; ++i)
-        for (int j = i; j < 6; ++j, ++p)
-            if (p == f) return {2, i, j, 0};
-    for (int i = 0; i < 6; ++i)
-        for (int j = i; j < 6; ++j)
-            for (int k = j; k < 6; ++k, ++p)
-                if (p == f) return {3, i, j, k};
-    return {0, 0, 0, 0};  // padding columns 83..95
-}
-
-template <int F>
-__device__ __forceinline__ float mono_at(const float (&a)[6]) {
-    constexpr MonoIdx m = mono_idx(F);
-    if constexpr (m.n == 1) return a[m.i];
-    else if constexpr (m.n == 2) return a[m.i] * a[m.j];
-    else if constexpr (m.n == 3) return (a[m.i] * a[m.j]) * a[m.k];
-    else return 0.0f;
-}
-
-// register r of input tile T feeds feature 32T + 8(r>>2) + (r&3) on lane half 0 and that + 4 on half 1
-template <int T, int... R>
-__device__ __forceinline__ f32x16 mono_tile(const float (&a)[6], int h, std::integer_sequence<int, R...>) {
-    f32x16 v;
-    ((v[R] = h ? mono_at<32 * T + 8 * (R >> 2) + (R & 3) + 4>(a) : mono_at<32 * T + 8 * (R >> 2) + (R & 3)>(a)), ...);
-    return v;
-}
+#include "edge_rows.h"
 
 // One wave owns 64 rows = 4 edge slots x 16 orientations of one receiver, as two 32-row column
 // blocks cb = 0, 1 (row j of block cb: slot = slot0 + 2 cb + (j >> 4), orientation = j & 15; both lane
@@ -54,37 +22,6 @@ __device__ __forceinline__ f32x16 mono_tile(const float (&a)[6], int h, std::int
 // GEMM and the three weight matrices become ONE linear stream of 16-byte fragments (w1 | w2 | wk_0..L-1,
 // 1 KiB per wave-load, each fragment feeding 8 MFMAs).  The stream is prefetched PF groups ahead through
 // a register ring, so L2 latency hides behind PF * 8 MFMAs (= 4096 cycles at PF = 8); no LDS, no barrier.
-struct EdgeRow { float a[6]; float window; };
-
-// attributes of one (edge slot, orientation) row  (transforms/invariants.py:82-88)
-__device__ __forceinline__ EdgeRow edge_row(const float* __restrict__ nbr_dir, const float* __restrict__ nbr_dist,
-                                            const float* __restrict__ ori, const float* __restrict__ Lm, size_t e,
-                                            int o, float r_max, bool valid) {
-    EdgeRow r;
-    const float dx = nbr_dir[3 * e + 0], dy = nbr_dir[3 * e + 1], dz = nbr_dir[3 * e + 2];
-    const float dist = nbr_dist[e];
-    const float ox = ori[3 * o + 0], oy = ori[3 * o + 1], oz = ori[3 * o + 2];
-    r.a[0] = (dx * ox + dy * oy) + dz * oz;  // inv1 = dir . o
-    const float rx = dx - r.a[0] * ox, ry = dy - r.a[0] * oy, rz = dz - r.a[0] * oz;
-    r.a[1] = sqrtf((rx * rx + ry * ry) + rz * rz);  // inv2 = |dir - inv1 o|
-    r.a[2] = dist;
-    // torch CosineSimilarity(dim=-1, eps=1e-8): normalise each vector by max(|v|, eps), then dot
-    const float dn = fmaxf(sqrtf((dx * dx + dy * dy) + dz * dz), 1e-8f);
-    const float ux = dx / dn, uy = dy / dn, uz = dz / dn;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const float lx = Lm[3 * i], ly = Lm[3 * i + 1], lz = Lm[3 * i + 2];
-        const float ln = fmaxf(sqrtf((lx * lx + ly * ly) + lz * lz), 1e-8f);
-        r.a[3 + i] = (ux * (lx / ln) + uy * (ly / ln)) + uz * (lz / ln);
-    }
-    // smooth cutoff (utils/windowing.py:21-29, p = 6), times (d < r_max)
-    const float u = dist / r_max;
-    const float u2 = u * u, u6 = u2 * u2 * u2;
-    const float w = 1.0f - 28.0f * u6 + 48.0f * u6 * u - 21.0f * u6 * u2;
-    r.window = (valid && dist < r_max) ? w : 0.0f;
-    return r;
-}
-
 template <int C, int D, int NCB, int OCC>
 __global__ __launch_bounds__(256, OCC) void edge_kernel(
     const float* __restrict__ nbr_dir,   // [N][k][3]
@@ -130,7 +67,7 @@ __global__ __launch_bounds__(256, OCC) void edge_kernel(
         // NaN included, and its K rows are stored; the conv kernels behind this kernel drop them by a select on the degree (never
         // a multiply by zero), so the unused slots of a given graph do not change an output bit (include/arreau_hip.h).
         const int sc = min(slot[cb], k - 1);
-        er[cb] = edge_row(nbr_dir, nbr_dist, ori, Lm, (size_t)node * k + sc, o, r_max, slot[cb] < nd);
+        er[cb] = edge_row<false>(nbr_dir, nbr_dist, ori, Lm, (size_t)node * k + sc, o, r_max, slot[cb] < nd);
         row[cb] = ((size_t)node * k + sc) * 16 + o;
     }
 

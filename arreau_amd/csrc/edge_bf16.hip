@@ -1,4 +1,4 @@
-// K2+K3, split-precision variant: the same fused edge pipeline as edge.hip (pair invariants ->
+// Kernels 2 + 3 of SURVEY.md, split-precision variant: the same fused edge pipeline as edge.hip (pair invariants ->
 // monomials -> basis MLP -> window -> L kernel projections, everything in registers), but every fp32
 // product is evaluated as six bf16 products on v_mfma_f32_32x32x16_bf16:
 //     a = a1 + a2 + a3,  b = b1 + b2 + b3   (exact 8+8+8-bit truncation splits)
@@ -19,37 +19,7 @@
 
 #include "internal.h"
 #include "bf16x6.h"
-
-// ---- compile-time monomial table (same canonical order as fold_poly_weight in model.hip) -------------
-struct MonoIdxB { int n, i, j, k; };
-__host__ __device__ constexpr MonoIdxB mono_idx_b(int f) {
-    int p = 0;
-    for (int i = 0; i < 6; ++i, ++p)
-        if (p == f) return {1, i, 0, 0};
-    for (int i = 0; i < 6; ++i)
-        for (int j = i; j < 6; ++j, ++p)
-            if (p == f) return {2, i, j, 0};
-    for (int i = 0; i < 6; ++i)
-        for (int j = i; j < 6; ++j)
-            for (int k = j; k < 6; ++k, ++p)
-                if (p == f) return {3, i, j, k};
-    return {0, 0, 0, 0};
-}
-template <int F>
-__device__ __forceinline__ float mono_at_b(const float (&a)[6]) {
-    constexpr MonoIdxB m = mono_idx_b(F);
-    if constexpr (m.n == 1) return a[m.i];
-    else if constexpr (m.n == 2) return a[m.i] * a[m.j];
-    else if constexpr (m.n == 3) return (a[m.i] * a[m.j]) * a[m.k];
-    else return 0.0f;
-}
-// "accumulator-layout" tile of monomials: register r of tile T holds feature 32T + (r&3) + 8(r>>2) + 4h
-template <int T, int... R>
-__device__ __forceinline__ f32x16 mono_tile_b(const float (&a)[6], int h, std::integer_sequence<int, R...>) {
-    f32x16 v;
-    ((v[R] = h ? mono_at_b<32 * T + 8 * (R >> 2) + (R & 3) + 4>(a) : mono_at_b<32 * T + 8 * (R >> 2) + (R & 3)>(a)), ...);
-    return v;
-}
+#include "edge_rows.h"
 
 template <int C, int D>
 __global__ __launch_bounds__(256, 1) void edge_kernel_bf16x6(
@@ -61,7 +31,7 @@ __global__ __launch_bounds__(256, 1) void edge_kernel_bf16x6(
     const float* __restrict__ ori,       // [16][3]
     const u32x4* __restrict__ stream,    // bf16x3 chunks: w1 (C/32 chunks) | w2 (D/32) | wk_l (L * C/32)
     const float* __restrict__ b1, const float* __restrict__ b2, float r_max, int N, int k, int L,
-    float* __restrict__ kbuf, int dbg)   // [L][N*k*16][C]
+    float* __restrict__ kbuf)            // [L][N*k*16][C]
 {
     constexpr int TC = C / 32, TD = D / 32, TM = ARREAU_MONO_PAD / 32;
     constexpr int NF1 = TM * 6, NF2 = TC * 6, NF3 = TD * 6;  // fragments per chunk
@@ -90,34 +60,14 @@ __global__ __launch_bounds__(256, 1) void edge_kernel_bf16x6(
     stage_load<NF1>(st, chunk, wave, lane);
 
     // ---- per-row attributes (transforms/invariants.py:82-88) ------------------------------------------
-    float a[6], window;
-    {
-        const size_t e = (size_t)node * k + slot_c;
-        const float dx = nbr_dir[3 * e + 0], dy = nbr_dir[3 * e + 1], dz = nbr_dir[3 * e + 2];
-        const float dist = nbr_dist[e];
-        const float ox = ori[3 * o + 0], oy = ori[3 * o + 1], oz = ori[3 * o + 2];
-        a[0] = (dx * ox + dy * oy) + dz * oz;
-        const float rx = dx - a[0] * ox, ry = dy - a[0] * oy, rz = dz - a[0] * oz;
-        a[1] = sqrtf((rx * rx + ry * ry) + rz * rz);
-        a[2] = dist;
-        const float* Lm = lattice + 9 * (size_t)batch[node];
-        const float dn = fmaxf(sqrtf((dx * dx + dy * dy) + dz * dz), 1e-8f);
-        const float ux = dx / dn, uy = dy / dn, uz = dz / dn;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const float lx = Lm[3 * i], ly = Lm[3 * i + 1], lz = Lm[3 * i + 2];
-            const float ln = fmaxf(sqrtf((lx * lx + ly * ly) + lz * lz), 1e-8f);
-            a[3 + i] = (ux * (lx / ln) + uy * (ly / ln)) + uz * (lz / ln);
-        }
-        const float u = dist / r_max;
-        const float u2 = u * u, u6 = u2 * u2 * u2;
-        const float w = 1.0f - 28.0f * u6 + 48.0f * u6 * u - 21.0f * u6 * u2;
-        window = (slot < nd && dist < r_max) ? w : 0.0f;
-    }
+    // ---- per-row attributes (edge_rows.h) --------------------------------------------------------------
+    const float* Lm = lattice + 9 * (size_t)batch[node];
+    const EdgeRow er = edge_row<false>(nbr_dir, nbr_dist, ori, Lm, (size_t)node * k + slot_c, o, r_max, slot < nd);
+    const float window = er.window;
     Planes bm[TM];
-    bm[0] = split_tile(mono_tile_b<0>(a, h, std::make_integer_sequence<int, 16>{}));
-    bm[1] = split_tile(mono_tile_b<1>(a, h, std::make_integer_sequence<int, 16>{}));
-    bm[2] = split_tile(mono_tile_b<2>(a, h, std::make_integer_sequence<int, 16>{}));
+    bm[0] = split_tile(mono_tile<0>(er.a, h, std::make_integer_sequence<int, 16>{}));
+    bm[1] = split_tile(mono_tile<1>(er.a, h, std::make_integer_sequence<int, 16>{}));
+    bm[2] = split_tile(mono_tile<2>(er.a, h, std::make_integer_sequence<int, 16>{}));
 
     stage_store<NF1>(st, lds[0], wave, lane);
     __syncthreads();
@@ -207,21 +157,21 @@ __global__ __launch_bounds__(256, 1) void edge_kernel_bf16x6(
         const bool more = cidx + 1 < nchunks;  // workgroup-uniform
         // vmcnt retires in order: the next chunk's fragment loads are issued BEFORE the previous tile's stores,
         // so waiting for the fragments (mid-chunk) never waits for the stores' HBM round trip.
-        if (more && !(dbg & 1)) stage_load<NF3>(st, chunk, wave, lane);
-        if (active && cidx > 0 && !(dbg & 4)) store_tile(done, cidx - 1);
+        if (more) stage_load<NF3>(st, chunk, wave, lane);
+        if (active && cidx > 0) store_tile(done, cidx - 1);
         f32x16 acc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
         // the next chunk's fragments go to the idle buffer in the middle of this chunk's MFMA stream, so the
         // LDS write burst (48 KiB per workgroup) overlaps matrix work instead of sitting in front of the barrier
         if (active) mma_range<TD, 0, TD>(acc, lds[cur], basis, lane);
-        if (more && !(dbg & 1)) stage_store<NF3>(st, lds[cur ^ 1], wave, lane);
+        if (more) stage_store<NF3>(st, lds[cur ^ 1], wave, lane);
         if (active) mma_range<TD, TD, 2 * TD>(acc, lds[cur], basis, lane);
-        if (!(dbg & 2)) __syncthreads();
+        __syncthreads();
         done = acc;
         cur ^= 1;
     }
-    if (active && !(dbg & 4)) store_tile(done, nchunks - 1);
+    if (active) store_tile(done, nchunks - 1);
 }
 
 int arreau_launch_edge_bf16x6(const arreau_model* m, const float* dir, const float* dist, const int32_t* deg,
@@ -231,9 +181,8 @@ int arreau_launch_edge_bf16x6(const arreau_model* m, const float* dir, const flo
         arreau_set_error("edge kernel (bf16x6): unsupported (hidden_dim, basis_dim, max_neighbors)");
         return ARREAU_EINVAL;
     }
-    static const int dbg = [] { const char* e = getenv("ARREAU_EDGE_DBG"); return e ? atoi(e) : 0; }();
     ARREAU_LAUNCH((edge_kernel_bf16x6<128, 256>), dim3(N), dim3(256), 0, s, dir, dist, deg, batch, lattice, m->ori,
-                       reinterpret_cast<const u32x4*>(m->edge_bf16), m->b1, m->b2, m->cfg.radius, N, m->k, m->L, kbuf, dbg);
+                       reinterpret_cast<const u32x4*>(m->edge_bf16), m->b1, m->b2, m->cfg.radius, N, m->k, m->L, kbuf);
     ARREAU_CHECK_HIP(hipGetLastError());
     return ARREAU_OK;
 }

@@ -1,4 +1,4 @@
-// K2+K3, fp16x3 split-precision variant (default): the fused edge pipeline (pair invariants -> monomials ->
+// Kernels 2 + 3 of SURVEY.md, fp16x3 split-precision variant (default): the fused edge pipeline (pair invariants -> monomials ->
 // basis MLP -> window -> L kernel projections, activations in registers) with every fp32 product evaluated
 // as three fp16 MFMA products (f16x3.h): half the matrix-pipe work and two thirds of the operand bytes of
 // the bf16x6 kernel (edge_bf16.hip), 16 registers per activation tile instead of 24 -- which is what lets
@@ -18,43 +18,12 @@
 #define ARREAU_K_STORE_POLICY ""
 // Hazard of the hand-written K-tile stores: a VMEM store of more than 64 bits reads its data registers AFTER it has issued,
 // and a VALU write to those registers too soon afterwards corrupts the stored data.  hipcc inserts the wait states for its
-// own stores; it does not look inside inline asm.  Found with the 3-byte K format, whose packed data registers the
-// compiler re-uses for the next store at once (non-reproducible NaNs; a plain C++ store or four wait states cure it);
-// the 16-byte form carries the same wait states although its data registers were never re-used that fast.
+// own stores; it does not look inside inline asm.  Found with the former 3-byte K format (DESIGN_HISTORY.md), whose packed data
+// registers the compiler re-used for the next store at once (non-reproducible NaNs; a plain C++ store or four wait states
+// cured it); the 16-byte stores carry the same wait states although their data registers were never re-used that fast.
 #define ARREAU_K_STORE_TAIL "\n\ts_nop 3"
 #include "internal.h"
-
-// ---- compile-time monomial table (same canonical order as fold_poly_weight in model.hip) -------------
-struct MonoIdxH { int n, i, j, k; };
-__host__ __device__ constexpr MonoIdxH mono_idx_h(int f) {
-    int p = 0;
-    for (int i = 0; i < 6; ++i, ++p)
-        if (p == f) return {1, i, 0, 0};
-    for (int i = 0; i < 6; ++i)
-        for (int j = i; j < 6; ++j, ++p)
-            if (p == f) return {2, i, j, 0};
-    for (int i = 0; i < 6; ++i)
-        for (int j = i; j < 6; ++j)
-            for (int k = j; k < 6; ++k, ++p)
-                if (p == f) return {3, i, j, k};
-    return {0, 0, 0, 0};
-}
-template <int F>
-__device__ __forceinline__ float mono_at_h(const float (&a)[6]) {
-    constexpr MonoIdxH m = mono_idx_h(F);
-    if constexpr (m.n == 1) return a[m.i];
-    else if constexpr (m.n == 2) return a[m.i] * a[m.j];
-    else if constexpr (m.n == 3) return (a[m.i] * a[m.j]) * a[m.k];
-    else return 0.0f;
-}
-// "accumulator-layout" tile of monomials: register r of tile T holds feature 32T + (r&3) + 8(r>>2) + 4h
-template <int T, int... R>
-__device__ __forceinline__ f32x16 mono_tile_h(const float (&a)[6], int h, std::integer_sequence<int, R...>) {
-    f32x16 v;
-    ((v[R] = h ? mono_at_h<32 * T + 8 * (R >> 2) + (R & 3) + 4>(a) : mono_at_h<32 * T + 8 * (R >> 2) + (R & 3)>(a)), ...);
-    return v;
-}
-
+#include "edge_rows.h"
 
 // Phase timing (tools/edge_timing.py; compiled in only with -DARREAU_EDGE_TIMING): wave 0 of every workgroup adds
 // the shader-clock ticks it spent in [set-up, layer 1, layer 2, projections, tail] to these counters.
@@ -107,7 +76,7 @@ __device__ __forceinline__ unsigned round_lo_fp8(unsigned lo_pair) {
 // consecutive rows cover all eight groups for writers and readers alike.
 __device__ __forceinline__ int relayout_cell(int plane, int row, int slot) { return 128 * plane + 4 * row + (slot ^ ((row >> 1) & 3)); }
 
-template <int C, int D, int EH_WAVES, bool K3 /* K tiles as 3-byte floats (internal.h) */, bool PROJ = true, bool BFP8 = false>
+template <int C, int D, int EH_WAVES, bool PROJ = true, bool BFP8 = false>
 __global__ __launch_bounds__(64 * EH_WAVES, 2) void edge_kernel_f16x3(
     const float* __restrict__ nbr_dir,   // [N][k][3]
     const float* __restrict__ nbr_dist,  // [N][k]
@@ -163,7 +132,10 @@ __global__ __launch_bounds__(64 * EH_WAVES, 2) void edge_kernel_f16x3(
         // through: hoisted out of the pair loop those addresses and constants would stay in registers through the
         // matrix phases, and this kernel must not spill (scratch traffic would count in vmcnt).
         int lane = lane0, wave = wave0;
-        asm volatile("" : "+v"(lane), "+s"(wave));
+        // (two statements: the optimiser may freeze an asm result, and a frozen (vector, scalar) pair counts as divergent as a whole --
+        // `wave` would leave the scalar registers, and with it every "s" operand of the asm copies and stores below)
+        asm volatile("" : "+v"(lane));
+        asm volatile("" : "+s"(wave));
         const int h = lane >> 5, j = lane & 31;
         const int wn = wave & 3;                       // wave within its node: slots 2wn, 2wn+1
         const unsigned lane16 = 16u * lane;            // per-lane byte offset inside a 1 KiB fragment
@@ -243,38 +215,16 @@ __global__ __launch_bounds__(64 * EH_WAVES, 2) void edge_kernel_f16x3(
         // block is zeros, which conv_proj.hip's unconditional sum counts on.  (Not `slot < nd ? load : 0`: hipcc turns that into
         // four exec-masked loads in a row, +8 us per launch at 256 x 20; a mask on the loaded words measured +3 us.)
         const int slot_c = min(slot, nd - 1);
-        // ---- per-row attributes (transforms/invariants.py:82-88) ------------------------------------------
-        float a[6], window;
-        {
-            const size_t e = (size_t)node * k + slot_c;
-            // slots past the degree read as zeros whatever the caller left there: their window is zero below, and a
-            // non-finite attribute would turn the stash block into NaN instead of the zeros conv_proj.hip counts on
-            const float dx = nbr_dir[3 * e + 0], dy = nbr_dir[3 * e + 1], dz = nbr_dir[3 * e + 2];
-            const float dist = nbr_dist[e];
-            const float ox = ori[3 * o + 0], oy = ori[3 * o + 1], oz = ori[3 * o + 2];
-            a[0] = (dx * ox + dy * oy) + dz * oz;
-            const float rx = dx - a[0] * ox, ry = dy - a[0] * oy, rz = dz - a[0] * oz;
-            a[1] = sqrtf((rx * rx + ry * ry) + rz * rz);
-            a[2] = dist;
-            const float* Lm = lattice + 9 * (size_t)batch[node];
-            // reciprocals by v_rcp_f32 (1 ulp) instead of IEEE division sequences: far inside the 1e-5 parity budget
-            const float inv_dn = __builtin_amdgcn_rcpf(fmaxf(sqrtf((dx * dx + dy * dy) + dz * dz), 1e-8f));
-            const float ux = dx * inv_dn, uy = dy * inv_dn, uz = dz * inv_dn;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const float lx = Lm[3 * i], ly = Lm[3 * i + 1], lz = Lm[3 * i + 2];
-                const float inv_ln = __builtin_amdgcn_rcpf(fmaxf(sqrtf((lx * lx + ly * ly) + lz * lz), 1e-8f));
-                a[3 + i] = (ux * (lx * inv_ln) + uy * (ly * inv_ln)) + uz * (lz * inv_ln);
-            }
-            const float u = dist * __builtin_amdgcn_rcpf(r_max);
-            const float u2 = u * u, u6 = u2 * u2 * u2;
-            const float w = 1.0f - 28.0f * u6 + 48.0f * u6 * u - 21.0f * u6 * u2;
-            window = (slot < nd && dist < r_max) ? w : 0.0f;
-        }
+        // ---- per-row attributes (edge_rows.h; reciprocals by v_rcp_f32, see there) -------------------------------
+        // slots past the degree read as zeros whatever the caller left there: their window is zero, and a
+        // non-finite attribute would turn the stash block into NaN instead of the zeros conv_proj.hip counts on
+        const float* Lm = lattice + 9 * (size_t)batch[node];
+        const EdgeRow er = edge_row<true>(nbr_dir, nbr_dist, ori, Lm, (size_t)node * k + slot_c, o, r_max, slot < nd);
+        const float window = er.window;
         Planes2 bm[TM];
-        bm[0] = split_tile2(mono_tile_h<0>(a, h, std::make_integer_sequence<int, 16>{}));
-        bm[1] = split_tile2(mono_tile_h<1>(a, h, std::make_integer_sequence<int, 16>{}));
-        bm[2] = split_tile2(mono_tile_h<2>(a, h, std::make_integer_sequence<int, 16>{}));
+        bm[0] = split_tile2(mono_tile<0>(er.a, h, std::make_integer_sequence<int, 16>{}));
+        bm[1] = split_tile2(mono_tile<1>(er.a, h, std::make_integer_sequence<int, 16>{}));
+        bm[2] = split_tile2(mono_tile<2>(er.a, h, std::make_integer_sequence<int, 16>{}));
         EDGE_TICK(0);
 
         // `go` is always 1 but opaque to the compiler: guarding the two MFMA halves of a tile with it keeps every half
@@ -429,7 +379,6 @@ __global__ __launch_bounds__(64 * EH_WAVES, 2) void edge_kernel_f16x3(
         EDGE_TICK(2);
         if constexpr (!PROJ) continue;  // basis form: the projections run in the message kernel of each layer (conv_proj.hip)
         // ---- per layer: kernel_l = Wk_l . basis  (conv.py:110), one output tile per chunk ---------------------
-        constexpr int KB = K3 ? 3 : 4;  // bytes per K value
         const size_t layer_stride = (size_t)N * k * 16 * C;
         const size_t row0 = ((size_t)node * k + 2 * wn) * 16;  // first K row of this wave's 32-row tile
         const bool full = 2 * wn + 1 < k;  // wave-uniform: the wave's second slot (column block 1) exists
@@ -438,7 +387,7 @@ __global__ __launch_bounds__(64 * EH_WAVES, 2) void edge_kernel_f16x3(
         // row's 128-byte line).  Not predicated on the degree: a slot beyond it gets the zeros its window produced
         // (those rows of the K buffer are never read), so a wave issues a FIXED number of stores per tile (4, or 2 for
         // the wave whose second slot does not exist when k is odd) -- which the counted wait at SYNC relies on.
-        const unsigned st_off = (unsigned)KB * (c16 * C + 4 * g16);
+        const unsigned st_off = 4u * (c16 * C + 4 * g16);  // bytes (fp32 K)
         auto store_tile16 = [&](const Acc16& a, const char* tile_base /* wave-uniform */) {
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb)
@@ -449,27 +398,18 @@ __global__ __launch_bounds__(64 * EH_WAVES, 2) void edge_kernel_f16x3(
                     for (int r = 0; r < 4; ++r) v[r] = fmaf(a.x[mt][nb][r], F16X3_INV_SCALE, a.m[mt][nb][r]);
                     // asm store: the counted wait at SYNC assumes exactly 4 (or 2) store instructions per tile
                     // (scalar base + one per-lane 32-bit offset + immediate: no 64-bit vector address arithmetic)
-                    if (nb == 0 || full) {
-                        if constexpr (K3) {
-                            const u32x3_k d = arreau_pack_k3(v[0], v[1], v[2], v[3]);
-                            asm volatile("global_store_dwordx3 %0, %1, %2 offset:%3" ARREAU_K_STORE_POLICY ARREAU_K_STORE_TAIL
-                                         :
-                                         : "v"(st_off), "v"(d), "s"(tile_base + 16 * KB * nb * C), "n"(16 * 3 * mt)
-                                         : "memory");
-                        } else {
-                            asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3" ARREAU_K_STORE_POLICY ARREAU_K_STORE_TAIL
-                                         :
-                                         : "v"(st_off), "v"(v), "s"(tile_base + 64 * nb * C), "n"(64 * mt)
-                                         : "memory");
-                        }
-                    }
+                    if (nb == 0 || full)
+                        asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3" ARREAU_K_STORE_POLICY ARREAU_K_STORE_TAIL
+                                     :
+                                     : "v"(st_off), "v"(v), "s"(tile_base + 64 * nb * C), "n"(64 * mt)
+                                     : "memory");
                 }
         };
         // ST = step (of 2 TD) at which the chunk's barrier is taken (mid-chunk).  At SYNC the wave's queue holds, oldest
         // first, its DMA copies of the next chunk and -- from the second chunk on -- the stores of the previous tile
         // (issued two steps into this chunk): the counted wait retires the copies and leaves the stores in flight.
         constexpr int ST = TD;
-        const char* tile_base = reinterpret_cast<const char*>(kbuf) + row0 * C * KB;  // tile the next store_tile16 writes
+        const char* tile_base = reinterpret_cast<const char*>(kbuf) + row0 * C * 4;  // tile the next store_tile16 writes
         int u_cur = 0;
         Acc16 prev;  // accumulators of the previous tile (folded and stored two steps into the next one)
 #pragma unroll
@@ -488,7 +428,7 @@ __global__ __launch_bounds__(64 * EH_WAVES, 2) void edge_kernel_f16x3(
             if (cidx > 0) {  // the previous tile leaves while this tile's first MFMAs run
                 store_tile16(prv, tile_base);
                 // next tile: 32 columns on, or the first column tile of the next layer
-                tile_base += (++u_cur == TC) ? (u_cur = 0, (ptrdiff_t)layer_stride * KB - (TC - 1) * 32 * KB) : 32 * KB;
+                tile_base += (++u_cur == TC) ? (u_cur = 0, (ptrdiff_t)layer_stride * 4 - (TC - 1) * 32 * 4) : 32 * 4;
             }
             ms.template run<2, ST>(acc, b16);
             if (cidx == 0) dma_wait();
@@ -535,7 +475,7 @@ __global__ __launch_bounds__(64 * EH_WAVES, 2) void edge_kernel_f16x3(
 // measured on MI355X (tools/gpu_edge_split_sweep.sh): 60 / 120 / 200 / 260 / 380 receivers: 19.8 / 31.8 / 56.9 / 71.0 / 88.1 us
 // against 65.9 / 67.0 / 69.0 / 71.8 / 74.0 us of the persistent form
 #define ARREAU_EDGE_SPLIT_MAX_NODES 240
-template <int C, int D, bool K3, bool BFP8>
+template <int C, int D, bool BFP8>
 __global__ __launch_bounds__(512) void edge_kernel_f16x3_split(
     const float* __restrict__ nbr_dir, const float* __restrict__ nbr_dist, const int32_t* __restrict__ deg,
     const int32_t* __restrict__ batch, const float* __restrict__ lattice, const float* __restrict__ ori,
@@ -577,30 +517,9 @@ __global__ __launch_bounds__(512) void edge_kernel_f16x3_split(
     const int slot = 2 * wn + (j >> 4);
     const int o = j & 15;
     const int slot_c = min(slot, nd - 1);  // (as above: an unused slot computes on its receiver's last edge, window zero)
-    float a[6], window;
-    {
-        const size_t e = (size_t)node * k + slot_c;
-        const float dx = nbr_dir[3 * e + 0], dy = nbr_dir[3 * e + 1], dz = nbr_dir[3 * e + 2];
-        const float dist = nbr_dist[e];
-        const float ox = ori[3 * o + 0], oy = ori[3 * o + 1], oz = ori[3 * o + 2];
-        a[0] = (dx * ox + dy * oy) + dz * oz;
-        const float rx = dx - a[0] * ox, ry = dy - a[0] * oy, rz = dz - a[0] * oz;
-        a[1] = sqrtf((rx * rx + ry * ry) + rz * rz);
-        a[2] = dist;
-        const float* Lm = lattice + 9 * (size_t)batch[node];
-        const float inv_dn = __builtin_amdgcn_rcpf(fmaxf(sqrtf((dx * dx + dy * dy) + dz * dz), 1e-8f));
-        const float ux = dx * inv_dn, uy = dy * inv_dn, uz = dz * inv_dn;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const float lx = Lm[3 * i], ly = Lm[3 * i + 1], lz = Lm[3 * i + 2];
-            const float inv_ln = __builtin_amdgcn_rcpf(fmaxf(sqrtf((lx * lx + ly * ly) + lz * lz), 1e-8f));
-            a[3 + i] = (ux * (lx * inv_ln) + uy * (ly * inv_ln)) + uz * (lz * inv_ln);
-        }
-        const float u = dist * __builtin_amdgcn_rcpf(r_max);
-        const float u2 = u * u, u6 = u2 * u2 * u2;
-        const float w = 1.0f - 28.0f * u6 + 48.0f * u6 * u - 21.0f * u6 * u2;
-        window = (slot < nd && dist < r_max) ? w : 0.0f;
-    }
+    const float* Lm = lattice + 9 * (size_t)batch[node];
+    const EdgeRow er = edge_row<true>(nbr_dir, nbr_dist, ori, Lm, (size_t)node * k + slot_c, o, r_max, slot < nd);
+    const float window = er.window;
     float win16[2];
     win16[0] = __shfl(window, c16, 64);
     win16[1] = __shfl(window, 16 + c16, 64);
@@ -608,9 +527,9 @@ __global__ __launch_bounds__(512) void edge_kernel_f16x3_split(
     // ---- layer 1, chunk u = wave (waves 0-3): h = GELU(W1f . mono + b1), into the shared re-layout pad -------------
     if (wave < TC) {
         Planes2 bm[TM];
-        bm[0] = split_tile2(mono_tile_h<0>(a, h, std::make_integer_sequence<int, 16>{}));
-        bm[1] = split_tile2(mono_tile_h<1>(a, h, std::make_integer_sequence<int, 16>{}));
-        bm[2] = split_tile2(mono_tile_h<2>(a, h, std::make_integer_sequence<int, 16>{}));
+        bm[0] = split_tile2(mono_tile<0>(er.a, h, std::make_integer_sequence<int, 16>{}));
+        bm[1] = split_tile2(mono_tile<1>(er.a, h, std::make_integer_sequence<int, 16>{}));
+        bm[2] = split_tile2(mono_tile<2>(er.a, h, std::make_integer_sequence<int, 16>{}));
         f32x16 acc = arreau_bias_tile(b1, wave, h), cross;
 #pragma unroll
         for (int r = 0; r < 16; ++r) cross[r] = 0.f;
@@ -732,7 +651,6 @@ __global__ __launch_bounds__(512) void edge_kernel_f16x3_split(
     auto store_tile = [&](int cidx) {
         const int l = cidx / TC, u = cidx % TC;
         float* tile = kbuf + (size_t)l * layer_stride + row0 * C + 32 * u;
-        char* tile3 = reinterpret_cast<char*>(kbuf) + ((size_t)l * layer_stride + row0 * C + 32 * u) * 3;
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
@@ -740,13 +658,7 @@ __global__ __launch_bounds__(512) void edge_kernel_f16x3_split(
                 f32x4 v;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = fmaf(acc.x[mt][nb][r], F16X3_INV_SCALE, acc.m[mt][nb][r]);
-                if (nb == 0 || full) {
-                    if constexpr (K3)
-                        *reinterpret_cast<u32x3_k*>(tile3 + ((size_t)(16 * nb + c16) * C + 16 * mt + 4 * g16) * 3) =
-                            arreau_pack_k3(v[0], v[1], v[2], v[3]);
-                    else
-                        *reinterpret_cast<f32x4*>(tile + (size_t)(16 * nb + c16) * C + 16 * mt + 4 * g16) = v;
-                }
+                if (nb == 0 || full) *reinterpret_cast<f32x4*>(tile + (size_t)(16 * nb + c16) * C + 16 * mt + 4 * g16) = v;
             }
     };
     // two register buffers of half a chunk each: while one is consumed the other is in flight (a third would hide more of
@@ -799,8 +711,8 @@ int arreau_launch_edge_f16x3(const arreau_model* m, const float* dir, const floa
             ARREAU_LAUNCH(kernel, dim3((unsigned)N * 4), dim3(512), 0, s, dir, dist, deg, batch, lattice, m->ori,
                                reinterpret_cast<const u32x4*>(m->edge_f16), m->b1, m->b2, m->cfg.radius, N, m->k, m->L, kbuf, 0);
         };
-        if (arreau_basis_fp8(m)) launch(edge_kernel_f16x3_split<128, 256, false, true>);
-        else launch(edge_kernel_f16x3_split<128, 256, false, false>);
+        if (arreau_basis_fp8(m)) launch(edge_kernel_f16x3_split<128, 256, true>);
+        else launch(edge_kernel_f16x3_split<128, 256, false>);
         ARREAU_CHECK_HIP(hipGetLastError());
         return ARREAU_OK;
     }
@@ -809,10 +721,10 @@ int arreau_launch_edge_f16x3(const arreau_model* m, const float* dir, const floa
     const int wgs = wgs_env > 0 ? (wgs_env < npairs ? wgs_env : npairs) : (npairs < n_cu ? npairs : n_cu);
     if (arreau_basis_form(m, N)) {  // stop after layer 2, store the basis planes (the node-layer launcher projects them)
         if (arreau_basis_fp8(m))
-            ARREAU_LAUNCH((edge_kernel_f16x3<128, 256, 8, false, false, true>), dim3(wgs), dim3(512), 0, s, dir, dist, deg, batch, lattice, m->ori,
+            ARREAU_LAUNCH((edge_kernel_f16x3<128, 256, 8, false, true>), dim3(wgs), dim3(512), 0, s, dir, dist, deg, batch, lattice, m->ori,
                           reinterpret_cast<const u32x4*>(m->edge_f16), m->b1, m->b2, m->cfg.radius, N, m->k, m->L, kbuf, 0, N);
         else
-            ARREAU_LAUNCH((edge_kernel_f16x3<128, 256, 8, false, false, false>), dim3(wgs), dim3(512), 0, s, dir, dist, deg, batch, lattice, m->ori,
+            ARREAU_LAUNCH((edge_kernel_f16x3<128, 256, 8, false, false>), dim3(wgs), dim3(512), 0, s, dir, dist, deg, batch, lattice, m->ori,
                           reinterpret_cast<const u32x4*>(m->edge_f16), m->b1, m->b2, m->cfg.radius, N, m->k, m->L, kbuf, 0, N);
         ARREAU_CHECK_HIP(hipGetLastError());
         return ARREAU_OK;
@@ -821,8 +733,8 @@ int arreau_launch_edge_f16x3(const arreau_model* m, const float* dir, const floa
         ARREAU_LAUNCH(kernel, dim3(wgs), dim3(512), 0, s, dir, dist, deg, batch, lattice, m->ori,
                            reinterpret_cast<const u32x4*>(m->edge_f16), m->b1, m->b2, m->cfg.radius, N, m->k, m->L, kbuf, 0, N);
     };
-    if (arreau_basis_fp8(m)) launch(edge_kernel_f16x3<128, 256, 8, false, true, true>);
-    else launch(edge_kernel_f16x3<128, 256, 8, false, true, false>);
+    if (arreau_basis_fp8(m)) launch(edge_kernel_f16x3<128, 256, 8, true, true>);
+    else launch(edge_kernel_f16x3<128, 256, 8, true, false>);
     ARREAU_CHECK_HIP(hipGetLastError());
     return ARREAU_OK;
 }

@@ -289,9 +289,9 @@ template <int IMM>
 __device__ __forceinline__ void conv_store4(const float* base_uniform, unsigned lane_off, float v) {
     asm volatile("global_store_dword %0, %1, %2 offset:%3" : : "v"(lane_off), "v"(v), "s"(base_uniform), "n"(IMM) : "memory");
 }
-template <int C, bool K3 /* K as 3-byte floats (internal.h: "K stash format") */>
+template <int C>
 __global__ __launch_bounds__(512, 2) void conv_kernel_streamed(
-    const float* __restrict__ kl,        // this layer's kernels [N*8*16][C] (fp32, or 3 bytes per value)
+    const float* __restrict__ kl,        // this layer's kernels [N*8*16][C] (fp32)
     const int32_t* __restrict__ deg, const int32_t* __restrict__ src,
     const float* __restrict__ x_in,      // [N][16][C]
     const float* __restrict__ fk,        // [16(o)][16(p)][C]
@@ -300,8 +300,8 @@ __global__ __launch_bounds__(512, 2) void conv_kernel_streamed(
 {
     static_assert(C == 128, "thread mapping assumes C = 128");
     constexpr int K = 8;
-    constexpr unsigned KBLOCK = K * 16 * C * (K3 ? 3 : 4);  // 64 KiB (48 KiB) per receiver
-    constexpr int NDMA = KBLOCK / 8 / 1024;                 // 1 KiB copies per wave and receiver: 8 (6)
+    constexpr unsigned KBLOCK = K * 16 * C * 4;            // 64 KiB per receiver
+    constexpr int NDMA = KBLOCK / 8 / 1024;                 // 1 KiB copies per wave and receiver: 8
     __shared__ __attribute__((aligned(16))) float kbuf_s[2][KBLOCK / 4];
     __shared__ __attribute__((aligned(16))) float tile[2][16 * CONV_LDS_STRIDE];
     const int tid = threadIdx.x;
@@ -389,17 +389,10 @@ __global__ __launch_bounds__(512, 2) void conv_kernel_streamed(
         __syncthreads();  // every wave's share of K(n) has landed
         // ---- multiply . ordered sum over the in-edges -----------------------------------------------------
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        const float* kb = &kbuf_s[PAR][K3 ? o_row * (C * 3 / 4) + 3 * c4 : o_row * C + 4 * c4];
+        const float* kb = &kbuf_s[PAR][o_row * C + 4 * c4];
 #pragma unroll
         for (int s_ = 0; s_ < K; ++s_) {
-            float kv[4];
-            if constexpr (K3) {
-                const unsigned* kq = reinterpret_cast<const unsigned*>(kb) + s_ * (16 * C * 3 / 4);
-                arreau_unpack_k3(kq[0], kq[1], kq[2], kv);
-            } else {
-                const f32x4 kf = *reinterpret_cast<const f32x4*>(kb + s_ * 16 * C);
-                kv[0] = kf[0]; kv[1] = kf[1]; kv[2] = kf[2]; kv[3] = kf[3];
-            }
+            const f32x4 kv = *reinterpret_cast<const f32x4*>(kb + s_ * 16 * C);
             const bool on = s_ < nd;  // product rounded, then added in edge order (messages -> index_add_)
             acc[0] = on ? __fadd_rn(acc[0], __fmul_rn(kv[0], xv[PAR][s_][0])) : acc[0];
             acc[1] = on ? __fadd_rn(acc[1], __fmul_rn(kv[1], xv[PAR][s_][1])) : acc[1];
@@ -647,7 +640,7 @@ int arreau_launch_node_layer(const arreau_model* m, int layer, const float* kbuf
         const int rc = arreau_launch_conv_proj(m, layer, kbuf, deg, src, x_in, x_conv, N, s);
         if (rc) return rc;
     } else if (conv_variant == 1 && m->k == 8) {
-        ARREAU_LAUNCH((conv_kernel_streamed<128, false>), dim3(N < 256 ? N : 256), dim3(512), 0, s, kbuf + (size_t)layer * layer_stride, deg,
+        ARREAU_LAUNCH((conv_kernel_streamed<128>), dim3(N < 256 ? N : 256), dim3(512), 0, s, kbuf + (size_t)layer * layer_stride, deg,
                                src, x_in, m->fk + (size_t)layer * 16 * 16 * C, m->conv_bias + (size_t)layer * C, 0, N, x_conv);
     } else {
         ARREAU_LAUNCH((conv_kernel<128>), dim3(conv_blocks), dim3(512), 0, s, kbuf + (size_t)layer * layer_stride,
@@ -801,10 +794,6 @@ __global__ void readout_crystals_kernel(const float* __restrict__ gs, const int3
     for (int n = offsets[b]; n < offsets[b + 1]; ++n) acc += gs[(size_t)n * 3 + g];
     len0[idx] = acc;
 }
-
-// (Round 5: the 3-byte K stash of round 2 -- ARREAU_K3, the K pair's format when it ran at every size -- is gone with that mode:
-// the K pair now only serves launches too small for the basis form, on an fp32 K buffer, bit-identical to the basis form.)
-bool arreau_k3(const arreau_model*) { return false; }
 
 // conv_variant 2 (default): basis form wherever it applies -- the fused shape, k = 8, fp16-representable weights, the
 // split-precision edge kernel -- and a launch large enough for it to pay: measured at n = 20 (graph replay, one box), the

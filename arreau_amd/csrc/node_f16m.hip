@@ -609,12 +609,12 @@ int arreau_launch_mlp_f16x3_m16_split(const arreau_model* m, int layer, const fl
 }
 
 // Message passing + spherical convolution + ConvNext block of one layer in ONE launch (small launches on an fp32 K
-// buffer with k = 8; see the kernel): what conv_kernel_streamed<128, false> followed by the launch above computes, bit for bit.
+// buffer with k = 8; see the kernel): what conv_kernel_streamed<128> followed by the launch above computes, bit for bit.
 bool arreau_small_layer_fusable(const arreau_model* m, int N) {
     const char* e = getenv("ARREAU_FUSE_SMALL");  // 0: two launches per layer (A/B, tests); read per call
     static const int split_env = [] { const char* v = getenv("ARREAU_MLP_SPLIT"); return v ? atoi(v) : -1; }();
     return (e == nullptr || atoi(e) != 0) && split_env < 0 && N <= ARREAU_MLP_SPLIT_MAX_NODES && m->mlp_variant == 3 &&
-           m->f16_ok && m->k == 8 && m->C == 128 && m->H == 512 && (m->conv_variant == 1 || m->conv_variant == 2) && !arreau_k3(m) &&
+           m->f16_ok && m->k == 8 && m->C == 128 && m->H == 512 && (m->conv_variant == 1 || m->conv_variant == 2) &&
            !arreau_basis_form(m, N);
 }
 int arreau_launch_small_layer(const arreau_model* m, int layer, const float* kbuf, const int32_t* deg, const int32_t* src,

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "internal.h"
+#include "edge_rows.h"
 #include "sgemm.h"
 
 namespace {
@@ -363,22 +364,9 @@ __global__ void edge_rows_kernel(const float* __restrict__ dir, const float* __r
     const int o = (int)(r & 15);
     const long e = r >> 4;
     const int n = (int)(e / k), s = (int)(e % k);
-    const float dx = dir[3 * e], dy = dir[3 * e + 1], dz = dir[3 * e + 2], d = dist[e];
-    const float ox = ori[3 * o], oy = ori[3 * o + 1], oz = ori[3 * o + 2];
-    float a[6];
-    a[0] = (dx * ox + dy * oy) + dz * oz;
-    const float rx = dx - a[0] * ox, ry = dy - a[0] * oy, rz = dz - a[0] * oz;
-    a[1] = sqrtf((rx * rx + ry * ry) + rz * rz);
-    a[2] = d;
-    const float* Lm = lattice + 9 * (size_t)batch[n];
-    const float dn = fmaxf(sqrtf((dx * dx + dy * dy) + dz * dz), 1e-8f);
-    for (int i = 0; i < 3; ++i) {
-        const float lx = Lm[3 * i], ly = Lm[3 * i + 1], lz = Lm[3 * i + 2];
-        const float ln = fmaxf(sqrtf((lx * lx + ly * ly) + lz * lz), 1e-8f);
-        a[3 + i] = ((dx / dn) * (lx / ln) + (dy / dn) * (ly / ln)) + (dz / dn) * (lz / ln);
-    }
-    const float u = d / r_max, u2 = u * u, u6 = u2 * u2 * u2;
-    window[r] = (s < deg[n] && d < r_max) ? 1.0f - 28.0f * u6 + 48.0f * u6 * u - 21.0f * u6 * u2 : 0.0f;
+    const EdgeRow er = edge_row<false>(dir, dist, ori, lattice + 9 * (size_t)batch[n], (size_t)e, o, r_max, s < deg[n]);
+    const float (&a)[6] = er.a;
+    window[r] = er.window;
     float* mrow = mono + r * ARREAU_MONO_PAD;
     int p = 0;
     for (int i = 0; i < 6; ++i) mrow[p++] = a[i];
