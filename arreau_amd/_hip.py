@@ -30,7 +30,7 @@ EXPORTS = [
     "arreau_sample_loop_resampled", "arreau_resample_jump", "arreau_optimizer_step_ema",
     "arreau_sample_loop_tied", "arreau_reverse_step_tied", "arreau_resample_jump_tied",
     "arreau_sample_loop_sym", "arreau_reverse_step_sym", "arreau_crystal_screen",
-    "arreau_crystal_fingerprint", "arreau_fingerprint_match",
+    "arreau_crystal_fingerprint", "arreau_fingerprint_match", "arreau_crystal_symmetry",
 ]
 
 STATUS_NONFINITE, STATUS_BAD_TIMESTEP, STATUS_BAD_TYPE, STATUS_BAD_TIE, STATUS_BAD_SYMMETRY = 1, 2, 4, 8, 16
@@ -107,6 +107,17 @@ class MatchResultC(Structure):
     _fields_ = [(name, c_void_p) for name in ("duplicate_of", "distance", "nearest", "nearest_distance")]
 
 
+class SymmetryParamsC(Structure):
+    """arreau_symmetry_params: the tolerance of the symmetry search and the operations stored per crystal."""
+    _fields_ = [("symprec", c_float), ("max_ops", c_int32)]
+
+
+class SymmetryResultC(Structure):
+    """arreau_symmetry_result: the nine device arrays the symmetry search writes, one row per crystal."""
+    _fields_ = [(name, c_void_p) for name in ("n_lattice", "n_ops", "n_translations", "ops_rotation", "ops_translation",
+                                                "ops_residual", "residual", "point_group", "flags")]
+
+
 class Config(Structure):
     _fields_ = [
         ("num_atomic_states", c_int32), ("hidden_dim", c_int32), ("basis_dim", c_int32),
@@ -180,6 +191,7 @@ def _prototypes():
         "arreau_crystal_screen": [vp] * 4 + [i32, i32, POINTER(ScreenCriteriaC), POINTER(ScreenResultC), vp],
         "arreau_crystal_fingerprint": [vp] * 4 + [i32, i32, POINTER(FingerprintParamsC), POINTER(FingerprintResultC), vp],
         "arreau_fingerprint_match": [POINTER(FingerprintResultC), i32, POINTER(FingerprintResultC), i32, f32, POINTER(MatchResultC), vp],
+        "arreau_crystal_symmetry": [vp] * 4 + [i32, i32, POINTER(SymmetryParamsC), POINTER(SymmetryResultC), vp],
         "arreau_train_forward": [vp] * 7 + [i32, i32] + [vp] * 4,
         "arreau_train_backward": [vp] * 4 + [POINTER(StateDict), vp],
         "arreau_train_conv_stats": [vp, vp, vp],

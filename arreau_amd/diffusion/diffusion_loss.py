@@ -16,6 +16,7 @@ from . import resampling as rs
 from . import respacing
 from . import screening
 from . import uniqueness as uniqueness_mod
+from . import symmetry_search
 from .d3pm import D3PM
 from . import lattice_systems
 from . import symmetry as sym_mod
@@ -48,6 +49,10 @@ class SampleResult:
     # extension: duplicate detection on the final state (sample(unique=...); diffusion/uniqueness.py) -- numpy arrays duplicate_of,
     # distance, nearest, nearest_distance, flags and unique, one entry per crystal; None when it was not asked for
     uniqueness: Optional[dict] = None
+    # extension: the symmetry search of the final state (sample(find_symmetry=...); diffusion/symmetry_search.py) -- numpy arrays
+    # n_lattice, n_ops, n_translations, ops_rotation, ops_translation, ops_residual, residual, point_group, flags, symprec and the
+    # float32 lattice the search saw; None when it was not asked for
+    symmetry: Optional[dict] = None
 
 
 class _PinnedRing:
@@ -272,7 +277,7 @@ class DiffusionLoss(nn.Module):
                fixed_cell: bool = False, condition=None, num_steps: Optional[int] = None,
                timesteps: Optional[Sequence[int]] = None, corrector_steps: int = 0,
                corrector_snr: float = pc.DEFAULT_SNR, resample_passes: int = 1, jump_length: int = 10,
-               lattice_system=None, symmetry=None, screen=None, unique=None) -> SampleResult:
+               lattice_system=None, symmetry=None, screen=None, unique=None, find_symmetry=None) -> SampleResult:
         """diffusion_loss.py:276-377.  The initial state is drawn on the host exactly like the reference (numpy
         uniforms for the angles, then randn lengths, randn fractional coordinates from torch's global CPU generator).
         Per-step noise:
@@ -343,9 +348,15 @@ class DiffusionLoss(nn.Module):
         launches on the final device state (arreau_crystal_fingerprint, arreau_fingerprint_match) give every crystal a structure
         fingerprint and the earliest crystal of the batch it duplicates; the class indices are the species ids.
         SampleResult.uniqueness then holds duplicate_of, distance, nearest, nearest_distance, flags and unique.  None: no launch
-        is added and uniqueness is None."""
+        is added and uniqueness is None.
+        `find_symmetry` (extension, every noise mode and option): a symmetry_search.SymmetrySearchParams, or True for its
+        defaults -- one more launch on the final device state (arreau_crystal_symmetry; rules in include/arreau_hip.h) finds the
+        operations x' = W x + t every crystal has in its cell and the point group of their rotations; the class indices are the
+        species ids.  SampleResult.symmetry then holds the arrays (symmetry_search.contains / stats_of read them).  No space-group
+        number, no standardised cell.  None: no launch is added, symmetry is None and the results are what they were, bit for bit."""
         screen = screening.resolve(screen)
         unique = uniqueness_mod.resolve(unique)
+        find_symmetry = symmetry_search.resolve(find_symmetry)
         frames = visualization_setting != VisualizationSetting.NONE
         if frames and not vis_name:
             raise ValueError("visualization_setting other than NONE needs vis_name (prefix of the frame files)")
@@ -590,7 +601,10 @@ class DiffusionLoss(nn.Module):
         uniqueness = None
         if unique is not None:
             uniqueness = uniqueness_mod.uniqueness_to_numpy(uniqueness_mod.unique_batch(frac_d, lattice_d, off_d, types_d, unique))
+        found = None
+        if find_symmetry is not None:
+            found = symmetry_search.result_to_numpy(eng.find_symmetry(frac_d, lattice_d, off_d, types_d, find_symmetry))
         atomic_numbers = atomic_number_indexes_to_atomic_numbers(z_table, types_d.cpu().numpy())
         return SampleResult(num_atoms=num_atoms.numpy(), frac_x=frac_d.cpu().numpy().astype(np.float64),
                             atomic_numbers=atomic_numbers, lattice=lattice_d.cpu().numpy().astype(np.float64), info=info,
-                            metrics=metrics, uniqueness=uniqueness)
+                            metrics=metrics, uniqueness=uniqueness, symmetry=found)

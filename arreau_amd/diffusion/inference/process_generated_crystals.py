@@ -13,7 +13,10 @@ one entry per crystal: screen_min_distance, screen_pair [B,5], screen_n_close, s
 screen_flags, screen_valid.  Readers of the five keys above are not affected; a result without metrics is written with
 exactly those five.  A result that carries duplicate detection's arrays (SampleResult.uniqueness, diffusion/uniqueness.py) gets
 six more in the same way: unique_duplicate_of, unique_distance, unique_nearest, unique_nearest_distance, unique_flags,
-unique_unique; without them none is written."""
+unique_unique; without them none is written.  A result that carries the symmetry search's arrays (SampleResult.symmetry,
+diffusion/symmetry_search.py) gets sym_n_lattice, sym_n_ops, sym_n_translations, sym_ops_rotation [B,max_ops], sym_ops_translation
+[B,max_ops,3], sym_ops_residual [B,max_ops], sym_residual, sym_point_group, sym_flags and sym_symprec; a reader gets them back with
+`lattice` filled in from the file's cells."""
 import os
 
 import numpy as np
@@ -25,6 +28,9 @@ METRIC_KEYS = ("min_distance", "pair", "n_close", "volume", "number_density", "f
 METRIC_PREFIX = "screen_"
 UNIQUE_KEYS = ("duplicate_of", "distance", "nearest", "nearest_distance", "flags", "unique")
 UNIQUE_PREFIX = "unique_"
+SYM_KEYS = ("n_lattice", "n_ops", "n_translations", "ops_rotation", "ops_translation", "ops_residual", "residual", "point_group",
+            "flags", "symprec")
+SYM_PREFIX = "sym_"
 _DTYPES = dict(frac_x=np.float64, atomic_numbers=np.float64, lattice=np.float64, idx_start=np.int64,
                num_atoms=np.int64)
 
@@ -59,6 +65,15 @@ def _fields(crystals: SampleResult):
             if v.shape != (B,):
                 raise ValueError(f"SampleResult.uniqueness[{k!r}] does not hold one entry per crystal")
             out[UNIQUE_PREFIX + k] = v
+    symmetry = getattr(crystals, "symmetry", None)
+    if symmetry is not None:
+        for k in SYM_KEYS:
+            if k not in symmetry:
+                raise ValueError(f"SampleResult.symmetry[{k!r}] is missing")
+            v = np.asarray(symmetry[k])
+            if v.shape[:1] != (B,) or v.ndim != {"ops_rotation": 2, "ops_translation": 3, "ops_residual": 2}.get(k, 1):
+                raise ValueError(f"SampleResult.symmetry[{k!r}] does not hold one row per crystal")
+            out[SYM_PREFIX + k] = v
     return out
 
 
@@ -97,12 +112,16 @@ def load_sample_results_from_hdf5(filename: str) -> SampleResult:
             data = {k: fh["crystals"][k][:] for k in KEYS}
             metrics = _metrics_from(lambda k: k in fh["crystals"], lambda k: fh["crystals"][k][:])
             uniqueness = _metrics_from(lambda k: k in fh["crystals"], lambda k: fh["crystals"][k][:], UNIQUE_PREFIX, UNIQUE_KEYS)
+            symmetry = _metrics_from(lambda k: k in fh["crystals"], lambda k: fh["crystals"][k][:], SYM_PREFIX, SYM_KEYS)
     else:
         with np.load(filename) as z:
             data = {k: z[k] for k in KEYS}
             metrics = _metrics_from(lambda k: k in z.files, lambda k: z[k])
             uniqueness = _metrics_from(lambda k: k in z.files, lambda k: z[k], UNIQUE_PREFIX, UNIQUE_KEYS)
-    return SampleResult(**data, metrics=metrics, uniqueness=uniqueness)
+            symmetry = _metrics_from(lambda k: k in z.files, lambda k: z[k], SYM_PREFIX, SYM_KEYS)
+    if symmetry is not None:  # (the search saw the float32 cells)
+        symmetry["lattice"] = np.asarray(data["lattice"], dtype=np.float32).reshape(-1, 3, 3)
+    return SampleResult(**data, metrics=metrics, uniqueness=uniqueness, symmetry=symmetry)
 
 
 def get_crystal_indexes(sample_result: SampleResult, sample_idx: int):

@@ -27,6 +27,12 @@ def screen(frac, lattice, offsets, types=None, criteria=None):
     return screening.screen(frac, lattice, offsets, types, criteria)
 
 
+def find_symmetry(frac, lattice, offsets, types, params=None):
+    """The symmetry search without an engine (arreau_crystal_symmetry needs no model): diffusion.symmetry_search.find_symmetry."""
+    from .diffusion import symmetry_search
+    return symmetry_search.find_symmetry(frac, lattice, offsets, types, params)
+
+
 def pack_state(module):
     """(Config, host tensors, StateDict of their pointers) of a PONITA_DIFFUSION in the reference's state_dict layout: what
     arreau_model_create and arreau_calibrate_formats take.  Host side only; the tensors must outlive every use of the struct."""
@@ -641,6 +647,15 @@ class HipEngine:
         if frac.device != self.device:
             raise ValueError(f"screen: the state must be on {self.device}")
         return screening.screen(frac, lattice, offsets, types, criteria)
+
+    def find_symmetry(self, frac, lattice, offsets, types, params=None):
+        """The symmetry search of a batch on this engine's device (arreau_crystal_symmetry; diffusion/symmetry_search.py:
+        `find_symmetry`, which needs no engine): frac [N,3] f32, lattice [B,3,3] f32, offsets [B+1] i32, types [N] i32, params
+        a SymmetrySearchParams (None: the defaults).  One launch on the current stream; returns the dict of device tensors."""
+        from .diffusion import symmetry_search
+        if frac.device != self.device:
+            raise ValueError(f"find_symmetry: the state must be on {self.device}")
+        return symmetry_search.find_symmetry(frac, lattice, offsets, types, params)
 
     def edges_to_slots(self, edge_index, dists, direction, N):
         """Receiver-sorted COO edges -> slot form (deg, src, dir, dist)."""

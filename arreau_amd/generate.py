@@ -59,7 +59,7 @@ def _screen_stats(parts):
     """The per-rank screen and uniqueness statistics the parts carry (SampleResult.info["screen_stats"] / ["unique_stats"]), each
     in one list; None when no part has any."""
     out = {}
-    for key in ("screen_stats", "unique_stats"):
+    for key in ("screen_stats", "unique_stats", "symmetry_stats"):
         stats = [st for p in parts if p is not None and p.info for st in p.info.get(key, [])]
         if stats:
             out[key] = stats
@@ -78,10 +78,13 @@ def concat_results(parts) -> SampleResult:
     metrics = None
     if all(p.metrics is not None for p in parts):
         metrics = {k: np.concatenate([np.asarray(p.metrics[k]) for p in parts]) for k in parts[0].metrics}
+    symmetry = None
+    if all(p.symmetry is not None for p in parts):  # (one --symprec and max_ops for the run: the rows have one width)
+        symmetry = {k: np.concatenate([np.asarray(p.symmetry[k]) for p in parts]) for k in parts[0].symmetry}
     return SampleResult(
         frac_x=np.concatenate([p.frac_x for p in parts]), atomic_numbers=np.concatenate([p.atomic_numbers for p in parts]),
         lattice=np.concatenate([p.lattice for p in parts]), num_atoms=num_atoms,
-        idx_start=np.cumsum(num_atoms) - num_atoms, info=info, metrics=metrics)
+        idx_start=np.cumsum(num_atoms) - num_atoms, info=info, metrics=metrics, symmetry=symmetry)
 
 
 def select_crystals(res: SampleResult, keep) -> SampleResult:
@@ -91,8 +94,10 @@ def select_crystals(res: SampleResult, keep) -> SampleResult:
     atoms = np.repeat(keep, num_atoms)
     kept = num_atoms[keep]
     metrics = None if res.metrics is None else {k: np.asarray(v)[keep] for k, v in res.metrics.items()}
+    symmetry = None if res.symmetry is None else {k: np.asarray(v)[keep] for k, v in res.symmetry.items()}
     return SampleResult(frac_x=np.asarray(res.frac_x)[atoms], atomic_numbers=np.asarray(res.atomic_numbers)[atoms],
-                        lattice=np.asarray(res.lattice)[keep], num_atoms=kept, idx_start=np.cumsum(kept) - kept, metrics=metrics)
+                        lattice=np.asarray(res.lattice)[keep], num_atoms=kept, idx_start=np.cumsum(kept) - kept, metrics=metrics,
+                        symmetry=symmetry)
 
 
 FIX_KINDS = ("positions", "species", "lattice")
@@ -138,6 +143,9 @@ def _gather_results(local: SampleResult, rank: int, world_size: int, gather: Opt
     if local.metrics is not None and not (local.info or {}).get("screen_stats"):  # a screened run: this rank's statistics
         from .diffusion.screening import stats_of
         local.info = dict(local.info or {}, screen_stats=[stats_of(local.metrics["flags"], rank)])
+    if local.symmetry is not None and not (local.info or {}).get("symmetry_stats"):  # a searched run: this rank's histogram
+        from .diffusion import symmetry_search
+        local.info = dict(local.info or {}, symmetry_stats=[symmetry_search.stats_of(local.symmetry, rank)])
     if unique is not None:  # duplicates within this rank's crystals, on its own device
         from .diffusion import uniqueness
         local.info = dict(local.info or {}, unique_stats=[uniqueness.stats_of(uniqueness.unique_sample_result(local, unique), rank)])
@@ -291,7 +299,36 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--unique", action="store_true",
                     help="duplicate detection on the device: unique / attempted per rank and in total + unique_* arrays in the output file")
     add_fingerprint_arguments(ap)
+    ap.add_argument("--find_symmetry", action="store_true",
+                    help="find every generated crystal's symmetry operations and point group on the device: histogram per rank and "
+                         "in total + sym_* arrays in the output file; with --symops, how many crystals contain that group")
+    add_symmetry_search_arguments(ap)
     return ap
+
+
+def add_symmetry_search_arguments(ap):
+    """The symmetry-search flag shared with `python -m arreau_amd.screen`."""
+    ap.add_argument("--symprec", type=float, default=0.1,
+                    help="find_symmetry: tolerance in A on cell lengths and atom distances (0.1: a starting value, not a claim)")
+
+
+def symmetry_search_params(args, error):
+    """The SymmetrySearchParams of the symmetry-search flag; `error(message)` reports a bad value."""
+    from .diffusion.symmetry_search import SymmetrySearchParams
+    try:
+        return SymmetrySearchParams(symprec=args.symprec)
+    except ValueError as e:
+        error(f"symmetry search: {e}")
+
+
+def symmetry_lines(res, parts=None, spec=None):
+    """The lines `--find_symmetry` prints for a result that holds the search's arrays: the histogram per rank (`parts`: the
+    statistics the ranks carried; None: the result as one set) and in total, and with `spec` the crystals that contain its group."""
+    from .diffusion import symmetry_search
+    lines = symmetry_search.summary_lines(parts if parts else [symmetry_search.stats_of(res.symmetry)])
+    if spec is not None:
+        lines.append(symmetry_search.contains_line(res.symmetry, spec))
+    return lines
 
 
 def add_fingerprint_arguments(ap):
@@ -390,6 +427,7 @@ def main():
     spec = load_symmetry(args, ap.error)
     criteria = check_screen_arguments(args, ap.error)
     unique = fingerprint_params(args, ap.error) if args.unique else None
+    find_sym = symmetry_search_params(args, ap.error) if args.find_symmetry else None
     condition = load_template(args.template, parse_fix(args.fix)).tile(args.samples_per_template) if args.template else None
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -425,7 +463,8 @@ def main():
             return model.sample(n, b, VisualizationSetting.NONE, False, condition=cond, num_steps=args.num_steps,
                                 corrector_steps=args.corrector_steps, corrector_snr=args.corrector_snr,
                                 resample_passes=args.resample_passes, jump_length=args.jump_length,
-                                lattice_system=args.lattice_system, symmetry=spec, screen=criteria)
+                                lattice_system=args.lattice_system, symmetry=spec, screen=criteria,
+                                find_symmetry=find_sym)
         import fcntl
         with open(lock_path, "a") as lock:
             fcntl.flock(lock, fcntl.LOCK_EX)
@@ -433,7 +472,8 @@ def main():
                 out = model.sample(n, b, VisualizationSetting.NONE, False, condition=cond, num_steps=args.num_steps,
                                 corrector_steps=args.corrector_steps, corrector_snr=args.corrector_snr,
                                 resample_passes=args.resample_passes, jump_length=args.jump_length,
-                                lattice_system=args.lattice_system, symmetry=spec, screen=criteria)
+                                lattice_system=args.lattice_system, symmetry=spec, screen=criteria,
+                                find_symmetry=find_sym)
                 torch.cuda.synchronize()
                 return out
             finally:
@@ -453,6 +493,9 @@ def main():
                 print(line)
         if unique is not None:
             for line in unique_lines(res, unique, device=f"cuda:{local_rank}"):
+                print(line)
+        if find_sym is not None:
+            for line in symmetry_lines(res, (res.info or {}).get("symmetry_stats"), spec):
                 print(line)
         print("wrote", save_sample_results(res, args.out))
     if world > 1:

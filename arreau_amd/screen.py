@@ -1,6 +1,7 @@
 """Screen an existing file of crystals on the GPU: generated crystals or a training set in the crystals.npz / .h5 layout.
 
     python -m arreau_amd.screen out/crystals.npz [--min_distance 0.5] [--min_volume 0.1] [--search_radius 3.0] [--out screened.npz]
+    python -m arreau_amd.screen out/crystals.npz --find_symmetry [--symprec 0.1]
     python -m arreau_amd.screen out/crystals.npz --unique [--against train.npz] [--fp_r_max 6] [--fp_sigma 0.1] [--fp_tolerance 0.01]
 
 Prints the summary `python -m arreau_amd.generate --screen` prints (accepted / attempted and the count per flag) and, with
@@ -8,12 +9,14 @@ Prints the summary `python -m arreau_amd.generate --screen` prints (accepted / a
 check looks for the mask state's atomic number (2001).  The rules are in include/arreau_hip.h (arreau_crystal_screen).
 `--unique` adds duplicate detection (diffusion/uniqueness.py): unique / attempted of the file, the unique_* arrays with `--out`,
 and with `--against FILE` the novelty -- the share of crystals with no match in that other set.
+`--find_symmetry [--symprec 0.1]` adds the symmetry search (diffusion/symmetry_search.py): the count per crystal system, point
+group and flag, and the sym_* arrays with `--out`.  No space-group number, no standardised cell.
 """
 import argparse
 
 
 def build_parser() -> argparse.ArgumentParser:
-    from .generate import add_fingerprint_arguments, add_screen_arguments
+    from .generate import add_fingerprint_arguments, add_screen_arguments, add_symmetry_search_arguments
     ap = argparse.ArgumentParser(prog="python -m arreau_amd.screen", description="structural screen of a crystals file")
     ap.add_argument("file", type=str, help="crystals.npz / .h5")
     add_screen_arguments(ap)
@@ -22,19 +25,22 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--unique", action="store_true", help="also detect duplicates within the file")
     ap.add_argument("--against", type=str, default=None, help="--unique: a second crystals file (e.g. the training set) for novelty")
     add_fingerprint_arguments(ap)
+    ap.add_argument("--find_symmetry", action="store_true", help="also find every crystal's symmetry operations and point group")
+    add_symmetry_search_arguments(ap)
     return ap
 
 
 def main(argv=None):
     from .diffusion import screening
     from .diffusion.inference.process_generated_crystals import load_sample_results_from_hdf5, save_sample_results_to_hdf5
-    from .generate import fingerprint_params, screen_criteria, unique_lines
+    from .generate import fingerprint_params, screen_criteria, symmetry_lines, symmetry_search_params, unique_lines
     ap = build_parser()
     args = ap.parse_args(argv)
     criteria = screen_criteria(args, ap.error)
     if args.against is not None and not args.unique:
         ap.error("--against needs --unique")
     unique = fingerprint_params(args, ap.error) if args.unique else None
+    find_sym = symmetry_search_params(args, ap.error) if args.find_symmetry else None
 
     def load(name):
         try:
@@ -50,6 +56,11 @@ def main(argv=None):
     if unique is not None:
         res.info = None  # (no per-rank parts: the file is one set)
         for line in unique_lines(res, unique, against, args.device):
+            print(line)
+    if find_sym is not None:
+        from .diffusion import symmetry_search
+        res.symmetry = symmetry_search.symmetry_sample_result(res, find_sym, args.device)
+        for line in symmetry_lines(res):
             print(line)
     if args.out:
         print("wrote", save_sample_results_to_hdf5(res, args.out))

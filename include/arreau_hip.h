@@ -361,6 +361,76 @@ int arreau_crystal_fingerprint(const float* d_frac, const int32_t* d_types, cons
 int arreau_fingerprint_match(const arreau_fingerprint_result* x, int32_t Bx, const arreau_fingerprint_result* y, int32_t By,
                              float tolerance, arreau_match_result* out, void* stream);
 
+/* ---- symmetry search: the operations of a crystal in the cell it is given, its point group ----------------------------
+ * The third instrument beside the screen and the fingerprint: which operations x' = W x + t (on fractional columns, modulo
+ * lattice translations) map the crystal onto itself within a tolerance symprec (A), and which of the 32 point groups their
+ * rotations form.  One launch, one workgroup of four waves per crystal, no atomics, no second stream, no arreau_model;
+ * deterministic.  NOT computed: a space-group number, a standardised or primitive cell.
+ * Conventions: the cell rows are a_0, a_1, a_2 (d_lattice); the Cartesian position of x is r_d = sum_k x_k L_kd.  Column j of W
+ * holds the image of basis vector j, a'_j = sum_k W_kj a_k; with G_ij = a_i . a_j the image basis has the metric G' = W^T G W.
+ * The rotation code of W is sum_{r,c} (W_rc + 1) 3^(3r + c) (W_00 the least significant base-3 digit; identity: 16484).
+ *   1. cell checks.  NONFINITE: a cell entry or a coordinate of the crystal is inf / NaN (no other flag is then set).  CELL:
+ *      the volume |a_0 . (a_1 x a_2)| (the screen's rule 1) is not positive or not finite.  EMPTY: no atoms.  Positions are
+ *      wrapped as in the screen's rule 5: w = f - floor(f), a result >= 1 becomes 0.
+ *   2. lattice candidates: every W with entries in {-1, 0, 1} (3^9 codes, in code order) and det = +-1 for which
+ *      | sqrt(G'_ii) - sqrt(G_ii) | <= symprec for every i and | G'_ij - G_ij | <= symprec (|a_i| + |a_j|) / 2 for i < j.
+ *      n_lattice counts them.  A lattice has at most 48 isometries: more than 48 means symprec is too loose for this cell --
+ *      AMBIGUOUS, and beside n_lattice nothing is reported.  Limitation: an operation whose matrix in the given basis has an
+ *      entry outside {-1, 0, 1} is not found; every conventional setting and the rhombohedral axes are covered, a badly skewed
+ *      cell may not be.
+ *   3. candidate translations: the species with the fewest atoms (the smallest id on ties), its first atom p0; for every atom q
+ *      of that species, in ascending order, t = wrap(w_q - W w_p0), wrapped to [0, 1) as in 1.
+ *   4. the test of (W, t): delta = (W w_i + t) - w_j, each component minus its nearest integer (rintf), c = delta's Cartesian
+ *      image, d = |c|; the residual of the operation is the maximum over the atoms i of the minimum over the atoms j of the
+ *      species of i; accepted when residual <= symprec.  The nearest image by components is the nearest image as long as the
+ *      cell is not flatter than symprec, which is assumed.
+ *   5. output: the accepted operations in the order (code of W ascending, q ascending): n_ops counts all of them, the first
+ *      max_ops are stored (ops_rotation: the code; ops_translation; ops_residual), OVERFLOW when there are more; unused slots
+ *      hold code -1 and zeros.  n_translations: the accepted operations with W = identity.  residual: the largest accepted one.
+ *   6. point group: every distinct accepted W has a type from (det, trace): det +1 and trace 3, -1, 0, 1, 2 -> 1, 2, 3, 4, 6;
+ *      det -1 and trace -3, 1, 0, -1, -2 -> -1, m, -3, -4, -6.  The ten counts are looked up among the 32 point groups
+ *      (csrc/symfind_table.h, generated by closing each group's generators): point_group = 0..31 in the order 1, -1, 2, m, 2/m,
+ *      222, mm2, mmm, 4, -4, 4/m, 422, 4mm, -42m, 4/mmm, 3, -3, 32, 3m, -3m, 6, -6, 6/m, 622, 6mm, -6m2, 6/mmm, 23, m-3, 432,
+ *      -43m, m-3m.  point_group = -1 and NOT_A_GROUP when the counts match no row or n_ops != distinct rotations x
+ *      n_translations (a tolerance can accept a set that is not closed).  The crystal system follows on the host.
+ *   7. arithmetic: every step is one float32 operation rounded to nearest, in the order written, never contracted to a fused
+ *      multiply-add: (W v)_r = (W_r0 v_0 + W_r1 v_1) + W_r2 v_2; a'_j likewise; dot products (x x' + y y') + z z'; c_d =
+ *      (delta_0 L_0d + delta_1 L_1d) + delta_2 L_2d; square roots correctly rounded.  No float32 restatement is kept: the
+ *      integer outputs are compared with the float64 restatement (arreau_amd/diffusion/symmetry_search.py) on guarded inputs,
+ *      every decision quantity at most symprec / 2 or at least 2 symprec; the reals to 64 x 2^-24 x max_d sum_k |L_kd| (residuals)
+ *      and 16 x 2^-24 (translations, modulo 1), derived there.
+ * A crystal flagged NONFINITE, CELL, EMPTY or AMBIGUOUS has n_ops = n_translations = 0, residual NaN, point_group -1 and no stored
+ * operation.  Crystals of up to 256 atoms keep their coordinates and species in LDS; larger ones read them from global memory
+ * (the same values).  Cost: n_lattice x n_rarest x n^2 distance evaluations per crystal.  Offsets outside [0, N] or descending
+ * are clamped as in the screen.  Does not synchronise.
+ * Argument errors (ARREAU_EINVAL, nothing launched): NULL params / result / arrays, negative sizes, symprec not finite or not
+ * positive, max_ops outside 1..ARREAU_SYM_MAX_OPS_CAP. */
+#define ARREAU_SYM_NONFINITE 1
+#define ARREAU_SYM_CELL 2
+#define ARREAU_SYM_EMPTY 4
+#define ARREAU_SYM_AMBIGUOUS 8
+#define ARREAU_SYM_OVERFLOW 16
+#define ARREAU_SYM_NOT_A_GROUP 32
+#define ARREAU_SYM_MAX_OPS_CAP 4096
+typedef struct arreau_symmetry_params {
+    float symprec;   /* A; default 0.1 (what CDVAE and MatterGen evaluate with: a starting value, not a claim) */
+    int32_t max_ops; /* operations stored per crystal, 1..ARREAU_SYM_MAX_OPS_CAP; default 192 */
+} arreau_symmetry_params;
+typedef struct arreau_symmetry_result { /* DEVICE arrays, one row per crystal */
+    int32_t* n_lattice;      /* [B] */
+    int32_t* n_ops;          /* [B] every accepted operation, also beyond max_ops */
+    int32_t* n_translations; /* [B] */
+    int32_t* ops_rotation;   /* [B, max_ops] rotation codes, -1 in unused slots */
+    float* ops_translation;  /* [B, max_ops, 3] */
+    float* ops_residual;     /* [B, max_ops] */
+    float* residual;         /* [B] */
+    int32_t* point_group;    /* [B] 0..31, -1: none */
+    int32_t* flags;          /* [B] ARREAU_SYM_* */
+} arreau_symmetry_result;
+/* d_frac[N,3], d_types[N] species ids (required), d_lattice[B,3,3] rows a, b, c.  `params` and `out` are HOST pointers. */
+int arreau_crystal_symmetry(const float* d_frac, const int32_t* d_types, const float* d_lattice, const int32_t* d_crystal_offsets,
+                            int32_t B, int32_t N, const arreau_symmetry_params* params, arreau_symmetry_result* out, void* stream);
+
 /* ---- the score network ---------------------------------------------------------------------- */
 
 /* One evaluation of DiffusionLoss.predict_scores (diffusion/diffusion_loss.py:112-197):
