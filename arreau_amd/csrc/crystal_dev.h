@@ -1,10 +1,15 @@
-// Device helpers shared by the kernels that enumerate a crystal's periodic contacts (screen.hip, fingerprint.hip): the cell's
-// cross products, the wrap of a fractional coordinate and the Cartesian position, one float32 rounding per operation.
+// Device helpers shared by the per-crystal kernels (screen.hip, fingerprint.hip, symfind.hip; one workgroup of CRYSTAL_WAVES waves
+// per crystal): the launch shape, the prologue, the cell and its image range, the wrap of a fractional coordinate and the Cartesian
+// position, one periodic contact, the compaction of a workgroup's hits in thread order.  One float32 rounding per operation.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#define CRYSTAL_WAVES 4
+#define CRYSTAL_THREADS (64 * CRYSTAL_WAVES)
+#define CRYSTAL_LDS_ATOMS 256  // crystals of up to this many atoms keep their per-atom data in LDS
+
 // every fp32 operation below is spelled out (__fmul_rn / __fadd_rn / __fsub_rn / __fdiv_rn): one rounding each, no contraction
-// to an FMA, so that the float32 host restatement (arreau_amd/diffusion/screening.py) matches bit for bit
+// to an FMA, so that the float32 host restatement (arreau_amd/diffusion/crystal_batch.py, screening.py) matches bit for bit
 __device__ __forceinline__ float dot3_rn(float ax, float ay, float az, float bx, float by, float bz) {
     return __fadd_rn(__fadd_rn(__fmul_rn(ax, bx), __fmul_rn(ay, by)), __fmul_rn(az, bz));
 }
@@ -15,6 +20,11 @@ __device__ __forceinline__ void cross_rn(const float* u, const float* v, float* 
     o[2] = __fsub_rn(__fmul_rn(u[0], v[1]), __fmul_rn(u[1], v[0]));
 }
 
+// (n_0 L_0d + n_1 L_1d) + n_2 L_2d: component d of a combination of the cell rows
+__device__ __forceinline__ float rows_rn(const float* Lm, int d, float n0, float n1, float n2) {
+    return __fadd_rn(__fadd_rn(__fmul_rn(n0, Lm[d]), __fmul_rn(n1, Lm[3 + d])), __fmul_rn(n2, Lm[6 + d]));
+}
+
 // w = f - floor(f), a result of 1 (a tiny negative f) becomes 0; then arreau_cart_component's expression on the wrapped
 // coordinates, uncontracted
 __device__ __forceinline__ float crystal_wrap(float f) {
@@ -23,6 +33,96 @@ __device__ __forceinline__ float crystal_wrap(float f) {
 }
 
 __device__ __forceinline__ float crystal_cart(const float* __restrict__ frac, const float* Lm, size_t atom, int d) {
-    const float w0 = crystal_wrap(frac[3 * atom]), w1 = crystal_wrap(frac[3 * atom + 1]), w2 = crystal_wrap(frac[3 * atom + 2]);
-    return __fadd_rn(__fadd_rn(__fmul_rn(w0, Lm[d]), __fmul_rn(w1, Lm[3 + d])), __fmul_rn(w2, Lm[6 + d]));
+    return rows_rn(Lm, d, crystal_wrap(frac[3 * atom]), crystal_wrap(frac[3 * atom + 1]), crystal_wrap(frac[3 * atom + 2]));
+}
+
+// Crystal b's atom range (first, n), clamped into [0, N] so that a bad offset table cannot make a kernel read outside frac / types,
+// its cell Lm[9], and whether a cell entry or a coordinate is not finite (workgroup-uniform: one barrier, every thread calls it);
+// `before_barrier` is a caller's own pass over its inputs, run ahead of that barrier so that its loads overlap the others.
+template <class Extra>
+__device__ __forceinline__ bool crystal_prologue(const float* __restrict__ frac, const float* __restrict__ lattice, const int32_t* __restrict__ offsets,
+                                                 int b, int N, int& first, int& n, float* Lm, Extra&& before_barrier) {
+    first = offsets[b];
+    int last = offsets[b + 1];
+    first = first < 0 ? 0 : (first > N ? N : first);
+    last = last < first ? first : (last > N ? N : last);
+    n = last - first;
+    int bad = 0;
+#pragma unroll
+    for (int q = 0; q < 9; ++q) {
+        Lm[q] = lattice[9 * (size_t)b + q];
+        bad |= !isfinite(Lm[q]);
+    }
+    for (int a = threadIdx.x; a < 3 * n; a += CRYSTAL_THREADS) bad |= !isfinite(frac[3 * (size_t)first + a]);
+    before_barrier();
+    return __syncthreads_or(bad);
+}
+
+// The cell as the contact search sees it: volume, shell quotients q_k = radius / (spacing of the planes across axis k); once the
+// caller has accepted the cell by its own rule, the images per axis N_k, W_k = 2 N_k + 1, their number M, the index of (0, 0, 0).
+struct crystal_cell {
+    float volume, q[3];
+    int N1, N2, N3;
+    unsigned W2, W3, M, centre;
+};
+
+__device__ __forceinline__ float crystal_volume(const float* Lm) {
+    float c0[3];
+    cross_rn(Lm + 3, Lm + 6, c0);
+    return fabsf(dot3_rn(Lm[0], Lm[1], Lm[2], c0[0], c0[1], c0[2]));
+}
+
+// fills volume and q; true when the volume is not finite or an axis needs more than max_shells images (every caller's CELL rule)
+__device__ __forceinline__ bool crystal_cell_measure(const float* Lm, float radius, int max_shells, crystal_cell& c) {
+    c.volume = crystal_volume(Lm);
+    bool unbounded = !isfinite(c.volume);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        float ck[3];
+        cross_rn(Lm + 3 * ((k + 1) % 3), Lm + 3 * ((k + 2) % 3), ck);
+        c.q[k] = __fdiv_rn(radius, __fdiv_rn(c.volume, sqrtf(dot3_rn(ck[0], ck[1], ck[2], ck[0], ck[1], ck[2]))));
+        unbounded |= !(c.q[k] <= (float)max_shells);
+    }
+    return unbounded;
+}
+
+// q_k <= max_shells <= 8 in an accepted cell, so N_k <= 8 and M <= 17^3
+__device__ __forceinline__ void crystal_cell_images(crystal_cell& c) {
+    c.N1 = max(1, (int)ceilf(c.q[0])); c.N2 = max(1, (int)ceilf(c.q[1])); c.N3 = max(1, (int)ceilf(c.q[2]));
+    c.W2 = 2u * c.N2 + 1u; c.W3 = 2u * c.N3 + 1u; c.M = (2u * c.N1 + 1u) * c.W2 * c.W3;
+    c.centre = ((unsigned)c.N1 * c.W2 + (unsigned)c.N2) * c.W3 + (unsigned)c.N3;
+}
+
+// image m -> (n1, n2, n3), images in lexicographic order
+__device__ __forceinline__ void crystal_image(const crystal_cell& c, unsigned m, int* im) {
+    const unsigned m12 = m / c.W3;
+    im[0] = (int)(m12 / c.W2) - c.N1; im[1] = (int)(m12 % c.W2) - c.N2; im[2] = (int)(m - m12 * c.W3) - c.N3;
+}
+
+// an atom at pi and image m of an atom at pj: s = (n1 L_0 + n2 L_1) + n3 L_2, disp = (pj + s) - pi, d2 = (dx dx + dy dy) + dz dz.
+// (screen.hip spells these operations out: through a helper they are packed in pairs, which costs its loop moves and wait states)
+__device__ __forceinline__ float contact_d2(const crystal_cell& c, const float* Lm, const float* pi, const float* pj, unsigned m) {
+    int im[3];
+    crystal_image(c, m, im);
+    float disp[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) disp[d] = __fsub_rn(__fadd_rn(pj[d], rows_rn(Lm, d, (float)im[0], (float)im[1], (float)im[2])), pi[d]);
+    return dot3_rn(disp[0], disp[1], disp[2], disp[0], disp[1], disp[2]);
+}
+
+// This thread's rank among the workgroup's hits, in thread order, and their number.  One barrier, every thread calls it; `slots`
+// are CRYSTAL_WAVES ints in LDS which the caller keeps unwritten until every thread has read them.
+__device__ __forceinline__ int crystal_compact(bool hit, int lane, int wave, int* slots, int& total) {
+    const unsigned long long mask = __ballot(hit);
+    if (lane == 0) slots[wave] = __popcll(mask);
+    __syncthreads();
+    int before = 0;
+    total = 0;
+#pragma unroll
+    for (int w = 0; w < CRYSTAL_WAVES; ++w) {
+        const int k = slots[w];
+        before += w < wave ? k : 0;
+        total += k;
+    }
+    return before + __popcll(mask & ((1ull << lane) - 1ull));
 }

@@ -1,23 +1,21 @@
 // Duplicate detection (arreau_crystal_fingerprint, arreau_fingerprint_match; the rules are written out in include/arreau_hip.h):
 // a reduced formula and a pair-distribution fingerprint per crystal, then for every crystal the earliest comparable crystal within
-// a tolerance.  Contacts are enumerated exactly as screen.hip enumerates them.  No atomics; no order of summation depends on where
-// a crystal sits in the batch.  Needs no arreau_model.
+// a tolerance.  Contacts are enumerated as screen.hip enumerates them: the cell and the image decode are crystal_dev.h's in both; the
+// contact's arithmetic is contact_d2 here and the same operations spelled out in screen.hip.  No atomics; no order of
+// summation depends on where a crystal sits in the batch.  Needs no arreau_model.
 #include "internal.h"
 #include "crystal_dev.h"
 #include <cmath>
 
-#define FP_LDS_ATOMS 256  // crystals of up to this many atoms keep their Cartesian positions and species ranks in LDS
-#define FP_WAVES 4
-#define FP_THREADS (64 * FP_WAVES)
-#define FP_LIST 1024                                  // contacts the LDS list holds; it is drained when a further round of
-#define FP_DRAIN (FP_LIST - FP_THREADS)               // FP_THREADS candidates might not fit
-#define FP_CELLS (ARREAU_FP_COMPONENTS / FP_WAVES)    // (component, bin) cells a thread owns: components wave, wave + 4, ...
-#define MATCH_TILE 16                                 // the match kernel's tile: 16 rows of X by 16 rows of Y
+#define FP_LIST 1024                                     // contacts the LDS list holds; it is drained when a further round of
+#define FP_DRAIN (FP_LIST - CRYSTAL_THREADS)             // CRYSTAL_THREADS candidates might not fit
+#define FP_CELLS (ARREAU_FP_COMPONENTS / CRYSTAL_WAVES)  // (component, bin) cells a thread owns: components wave, wave + 4, ...
+#define MATCH_TILE 16                                    // the match kernel's tile: 16 rows of X by 16 rows of Y
 #define MATCH_PAD (ARREAU_FP_BINS + 1)
 
 namespace {
 
-__global__ __launch_bounds__(FP_THREADS) void crystal_fingerprint_kernel(
+__global__ __launch_bounds__(CRYSTAL_THREADS) void crystal_fingerprint_kernel(
     const float* __restrict__ frac, const int32_t* __restrict__ types, const float* __restrict__ lattice,
     const int32_t* __restrict__ offsets, int B, int N, float r_cut, float rc2 /* r_cut^2 */, float delta, float coef /* log2(e) / (2 sigma^2) */,
     float gnorm /* 1 / (sigma sqrt(2 pi)) */, int n_bins, int max_shells, float* __restrict__ o_fp, int32_t* __restrict__ o_species,
@@ -25,26 +23,22 @@ __global__ __launch_bounds__(FP_THREADS) void crystal_fingerprint_kernel(
     const int b = blockIdx.x;
     if (b >= B) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int first = offsets[b], last = offsets[b + 1];  // clamped into [0, N] as in the screen
-    first = first < 0 ? 0 : (first > N ? N : first);
-    last = last < first ? first : (last > N ? N : last);
-    const int n = last - first;
+    int first, n;
     float Lm[9];
-#pragma unroll
-    for (int q = 0; q < 9; ++q) Lm[q] = lattice[9 * (size_t)b + q];
+    const bool bad = crystal_prologue(frac, lattice, offsets, b, N, first, n, Lm, [] {});
 
-    __shared__ float spos[3 * FP_LDS_ATOMS];
-    __shared__ unsigned char srank[FP_LDS_ATOMS];
+    __shared__ float spos[3 * CRYSTAL_LDS_ATOMS];
+    __shared__ unsigned char srank[CRYSTAL_LDS_ATOMS];
     __shared__ int s_species[ARREAU_FP_MAX_SPECIES], s_count[ARREAU_FP_MAX_SPECIES], s_K;
     __shared__ float s_R[FP_LIST];
     __shared__ unsigned char s_c[FP_LIST];  // component in the low six bits, 64: both atoms of one species (c = 2)
-    __shared__ int s_wcnt[2][FP_WAVES];
-    __shared__ float s_part[FP_WAVES];
+    __shared__ int s_wcnt[2][CRYSTAL_WAVES];
+    __shared__ float s_part[CRYSTAL_WAVES];
 
     float* row = o_fp + (size_t)b * ARREAU_FP_ROW;
     auto flagged = [&](int flags) {  // (workgroup-uniform) a zero row, no formula
 #pragma unroll
-        for (int q = 0; q < FP_CELLS; ++q) row[(wave + FP_WAVES * q) * ARREAU_FP_BINS + lane] = 0.0f;
+        for (int q = 0; q < FP_CELLS; ++q) row[(wave + CRYSTAL_WAVES * q) * ARREAU_FP_BINS + lane] = 0.0f;
         if (tid < ARREAU_FP_MAX_SPECIES) {
             o_species[ARREAU_FP_MAX_SPECIES * (size_t)b + tid] = -1;
             o_counts[ARREAU_FP_MAX_SPECIES * (size_t)b + tid] = 0;
@@ -52,12 +46,7 @@ __global__ __launch_bounds__(FP_THREADS) void crystal_fingerprint_kernel(
         if (tid == 0) o_flags[b] = flags;
     };
 
-    // ---- NONFINITE
-    int bad = 0;
-#pragma unroll
-    for (int q = 0; q < 9; ++q) bad |= !isfinite(Lm[q]);
-    for (int a = tid; a < 3 * n; a += FP_THREADS) bad |= !isfinite(frac[3 * (size_t)first + a]);
-    if (__syncthreads_or(bad)) return flagged(ARREAU_FP_NONFINITE);
+    if (bad) return flagged(ARREAU_FP_NONFINITE);
 
     // ---- the formula: thread 0 inserts the species into a sorted list of at most eight (K = 9: a ninth was met)
     if (tid == 0) {
@@ -77,21 +66,11 @@ __global__ __launch_bounds__(FP_THREADS) void crystal_fingerprint_kernel(
     const int K = s_K;
 
     // ---- the cell, as in the screen with search_radius = r_cut (every thread computes the same values)
-    float c0[3], c1[3], c2[3];
-    cross_rn(Lm + 3, Lm + 6, c0);
-    cross_rn(Lm + 6, Lm + 0, c1);
-    cross_rn(Lm + 0, Lm + 3, c2);
-    const float volume = fabsf(dot3_rn(Lm[0], Lm[1], Lm[2], c0[0], c0[1], c0[2]));
-    const float q0 = __fdiv_rn(r_cut, __fdiv_rn(volume, sqrtf(dot3_rn(c0[0], c0[1], c0[2], c0[0], c0[1], c0[2]))));
-    const float q1 = __fdiv_rn(r_cut, __fdiv_rn(volume, sqrtf(dot3_rn(c1[0], c1[1], c1[2], c1[0], c1[1], c1[2]))));
-    const float q2 = __fdiv_rn(r_cut, __fdiv_rn(volume, sqrtf(dot3_rn(c2[0], c2[1], c2[2], c2[0], c2[1], c2[2]))));
-    const float cap = (float)max_shells;
-    const bool cell_bad = !(volume > 0.0f) || !isfinite(volume) || !(q0 <= cap) || !(q1 <= cap) || !(q2 <= cap);
+    crystal_cell cell;
+    const bool cell_bad = crystal_cell_measure(Lm, r_cut, max_shells, cell) || !(cell.volume > 0.0f);
     const int flags = (n == 0 ? ARREAU_FP_EMPTY : 0) | (K > ARREAU_FP_MAX_SPECIES ? ARREAU_FP_MANY_SPECIES : 0) | (cell_bad ? ARREAU_FP_CELL : 0);
     if (flags) return flagged(flags);
-    const int N1 = max(1, (int)ceilf(q0)), N2 = max(1, (int)ceilf(q1)), N3 = max(1, (int)ceilf(q2));
-    const unsigned W2 = 2u * N2 + 1u, W3 = 2u * N3 + 1u, M = (2u * N1 + 1u) * W2 * W3;
-    const unsigned centre = ((unsigned)N1 * W2 + (unsigned)N2) * W3 + (unsigned)N3;
+    crystal_cell_images(cell);
 
     // ---- positions and species ranks: staged in LDS when the crystal fits, else formed from global memory where they are used
     auto rank_of = [&](int t) -> int {
@@ -99,10 +78,10 @@ __global__ __launch_bounds__(FP_THREADS) void crystal_fingerprint_kernel(
         for (int q = 0; q < K; ++q) r = s_species[q] == t ? q : r;
         return r;
     };
-    const bool staged = n <= FP_LDS_ATOMS;
+    const bool staged = n <= CRYSTAL_LDS_ATOMS;
     if (staged) {
-        for (int a = tid; a < 3 * n; a += FP_THREADS) spos[a] = crystal_cart(frac, Lm, (size_t)first + a / 3, a % 3);
-        for (int a = tid; a < n; a += FP_THREADS) srank[a] = (unsigned char)rank_of(types[(size_t)first + a]);
+        for (int a = tid; a < 3 * n; a += CRYSTAL_THREADS) spos[a] = crystal_cart(frac, Lm, (size_t)first + a / 3, a % 3);
+        for (int a = tid; a < n; a += CRYSTAL_THREADS) srank[a] = (unsigned char)rank_of(types[(size_t)first + a]);
     }
     __syncthreads();
     auto position = [&](int atom, int d) -> float { return staged ? spos[3 * atom + d] : crystal_cart(frac, Lm, (size_t)first + atom, d); };
@@ -119,7 +98,7 @@ __global__ __launch_bounds__(FP_THREADS) void crystal_fingerprint_kernel(
         __syncthreads();  // the list is complete
         for (int e = 0; e < cnt; ++e) {
             const int c = __builtin_amdgcn_readfirstlane((int)s_c[e]);
-            if ((c & (FP_WAVES - 1)) != wave) continue;  // (uniform) another wave's component
+            if ((c & (CRYSTAL_WAVES - 1)) != wave) continue;  // (uniform) another wave's component
             const float x = Rk - s_R[e];
             const float g = __builtin_amdgcn_exp2f(-(x * x) * coef);  // one v_exp_f32
             const float v = (c & 64) ? g + g : g;
@@ -133,29 +112,22 @@ __global__ __launch_bounds__(FP_THREADS) void crystal_fingerprint_kernel(
     };
     int parity = 0;
     for (int i = 0; i < n; ++i) {
-        const float pix = position(i, 0), piy = position(i, 1), piz = position(i, 2);
+        const float pi[3] = {position(i, 0), position(i, 1), position(i, 2)};
         const int ri = species_rank(i);
-        const unsigned long long span = (unsigned long long)(n - i) * M;
-        const bool narrow = span <= 0xffffffffull - FP_THREADS;  // (uniform) the usual case: 32-bit index arithmetic
-        for (unsigned long long base = 0; base < span; base += FP_THREADS) {
+        const unsigned long long span = (unsigned long long)(n - i) * cell.M;
+        const bool narrow = span <= 0xffffffffull - CRYSTAL_THREADS;  // (uniform) the usual case: 32-bit index arithmetic
+        for (unsigned long long base = 0; base < span; base += CRYSTAL_THREADS) {
             const unsigned long long e = base + (unsigned)tid;
             bool hit = false;
             float R = 0.0f;
             int comp = 0;
             if (e < span) {
-                const unsigned dj = narrow ? (unsigned)e / M : (unsigned)(e / M);
-                const unsigned m = narrow ? (unsigned)e - dj * M : (unsigned)(e - (unsigned long long)dj * M);
-                if (!(dj == 0 && m <= centre)) {  // an atom with itself: only the images after (0, 0, 0)
+                const unsigned dj = narrow ? (unsigned)e / cell.M : (unsigned)(e / cell.M);
+                const unsigned m = narrow ? (unsigned)e - dj * cell.M : (unsigned)(e - (unsigned long long)dj * cell.M);
+                if (!(dj == 0 && m <= cell.centre)) {  // an atom with itself: only the images after (0, 0, 0)
                     const int j = i + (int)dj;
-                    const unsigned m12 = m / W3;
-                    const float n3 = (float)((int)(m - m12 * W3) - N3), n2 = (float)((int)(m12 % W2) - N2), n1 = (float)((int)(m12 / W2) - N1);
-                    const float sx = __fadd_rn(__fadd_rn(__fmul_rn(n1, Lm[0]), __fmul_rn(n2, Lm[3])), __fmul_rn(n3, Lm[6]));
-                    const float sy = __fadd_rn(__fadd_rn(__fmul_rn(n1, Lm[1]), __fmul_rn(n2, Lm[4])), __fmul_rn(n3, Lm[7]));
-                    const float sz = __fadd_rn(__fadd_rn(__fmul_rn(n1, Lm[2]), __fmul_rn(n2, Lm[5])), __fmul_rn(n3, Lm[8]));
-                    const float dx = __fsub_rn(__fadd_rn(position(j, 0), sx), pix);
-                    const float dy = __fsub_rn(__fadd_rn(position(j, 1), sy), piy);
-                    const float dz = __fsub_rn(__fadd_rn(position(j, 2), sz), piz);
-                    const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+                    const float pj[3] = {position(j, 0), position(j, 1), position(j, 2)};
+                    const float d2 = contact_d2(cell, Lm, pi, pj, m);
                     if (d2 < rc2) {
                         hit = true;
                         R = sqrtf(d2);
@@ -165,18 +137,10 @@ __global__ __launch_bounds__(FP_THREADS) void crystal_fingerprint_kernel(
                 }
             }
             // the hits of this round, in thread order: the wave's ballot, then a prefix over the four waves
-            const unsigned long long mask = __ballot(hit);
-            if (lane == 0) s_wcnt[parity][wave] = __popcll(mask);
-            __syncthreads();  // (the other parity's counts are not written before every thread has passed this barrier again)
-            int before = 0, total = 0;
-#pragma unroll
-            for (int w = 0; w < FP_WAVES; ++w) {
-                const int k = s_wcnt[parity][w];
-                before += w < wave ? k : 0;
-                total += k;
-            }
+            // (the other parity's counts are not written before every thread has passed the helper's barrier again)
+            int total;
+            const int at = cnt + crystal_compact(hit, lane, wave, s_wcnt[parity], total);  // < FP_LIST: cnt <= FP_DRAIN here
             if (hit) {
-                const int at = cnt + before + __popcll(mask & ((1ull << lane) - 1ull));  // < FP_LIST: cnt <= FP_DRAIN here
                 s_R[at] = R;
                 s_c[at] = (unsigned char)comp;
             }
@@ -188,12 +152,12 @@ __global__ __launch_bounds__(FP_THREADS) void crystal_fingerprint_kernel(
     drain();
 
     // ---- F, its weighted norm (a fixed-order sum: the thread's cells, the wave's lanes, the four waves) and the stored row
-    const float pref = volume * gnorm / (4.0f * 3.14159265358979323846f);
+    const float pref = cell.volume * gnorm / (4.0f * 3.14159265358979323846f);
     const float fn = (float)n;
     float Fv[FP_CELLS], sw[FP_CELLS], part = 0.0f;
 #pragma unroll
     for (int q = 0; q < FP_CELLS; ++q) {
-        const int c = wave + FP_WAVES * q;
+        const int c = wave + CRYSTAL_WAVES * q;
         int Bq = 0;
         while ((Bq + 1) * (Bq + 2) / 2 <= c) ++Bq;
         const int A = c - Bq * (Bq + 1) / 2;
@@ -213,7 +177,7 @@ __global__ __launch_bounds__(FP_THREADS) void crystal_fingerprint_kernel(
     const float norm2 = ((s_part[0] + s_part[1]) + s_part[2]) + s_part[3];
     const float inv = norm2 > 0.0f ? 1.0f / sqrtf(norm2) : 0.0f;
 #pragma unroll
-    for (int q = 0; q < FP_CELLS; ++q) row[(wave + FP_WAVES * q) * ARREAU_FP_BINS + lane] = sw[q] * Fv[q] * inv;
+    for (int q = 0; q < FP_CELLS; ++q) row[(wave + CRYSTAL_WAVES * q) * ARREAU_FP_BINS + lane] = sw[q] * Fv[q] * inv;
     if (tid < ARREAU_FP_MAX_SPECIES) {
         int g = 0;  // gcd of the counts
         for (int q = 0; q < K; ++q) {
@@ -327,7 +291,7 @@ extern "C" int arreau_crystal_fingerprint(const float* d_frac, const int32_t* d_
     const float delta = params->r_max / (float)params->n_bins;
     const float coef = (float)(1.4426950408889634 / (2.0 * sigma * sigma));
     const float gnorm = (float)(1.0 / (sigma * 2.5066282746310002));
-    ARREAU_LAUNCH(crystal_fingerprint_kernel, dim3((unsigned)B), dim3(FP_THREADS), 0, (hipStream_t)stream, d_frac, d_types, d_lattice,
+    ARREAU_LAUNCH(crystal_fingerprint_kernel, dim3((unsigned)B), dim3(CRYSTAL_THREADS), 0, (hipStream_t)stream, d_frac, d_types, d_lattice,
                   d_crystal_offsets, (int)B, (int)N, r_cut, rc2, delta, coef, gnorm, (int)params->n_bins, (int)params->max_shells,
                   out->fingerprint, out->species, out->counts, out->flags);
     ARREAU_CHECK_HIP(hipGetLastError());

@@ -7,12 +7,9 @@
 #include "crystal_dev.h"
 #include <cmath>
 
-#define SCREEN_LDS_ATOMS 256  // crystals of up to this many atoms keep their Cartesian positions in LDS (3 KiB)
-#define SCREEN_WAVES 4
-
 namespace {
 
-__global__ __launch_bounds__(64 * SCREEN_WAVES) void crystal_screen_kernel(
+__global__ __launch_bounds__(CRYSTAL_THREADS) void crystal_screen_kernel(
     const float* __restrict__ frac, const int32_t* __restrict__ types, const float* __restrict__ lattice,
     const int32_t* __restrict__ offsets, int B, int N, float min_volume, float md2 /* min_distance^2 */, float r2 /* search_radius^2 */,
     float radius, int mask_type, int max_shells, float* __restrict__ o_dist, int32_t* __restrict__ o_pair,
@@ -20,30 +17,21 @@ __global__ __launch_bounds__(64 * SCREEN_WAVES) void crystal_screen_kernel(
     const int b = blockIdx.x;
     if (b >= B) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // the crystal's atom range, clamped into [0, N]: a bad offset table cannot make the kernel read outside frac / types
-    int first = offsets[b], last = offsets[b + 1];
-    first = first < 0 ? 0 : (first > N ? N : first);
-    last = last < first ? first : (last > N ? N : last);
-    const int n = last - first;
+    int first, n;
     float Lm[9];
-#pragma unroll
-    for (int q = 0; q < 9; ++q) Lm[q] = lattice[9 * (size_t)b + q];
-
-    __shared__ float spos[3 * SCREEN_LDS_ATOMS];
-    __shared__ unsigned s_d2[SCREEN_WAVES];
-    __shared__ unsigned long long s_ij[SCREEN_WAVES];
-    __shared__ unsigned s_m[SCREEN_WAVES];
-    __shared__ int s_close[SCREEN_WAVES];
-
-    // ---- NONFINITE / MASKED: one pass over the crystal's inputs
-    int bad = 0, masked = 0;
-#pragma unroll
-    for (int q = 0; q < 9; ++q) bad |= !isfinite(Lm[q]);
-    for (int a = tid; a < 3 * n; a += 64 * SCREEN_WAVES) bad |= !isfinite(frac[3 * (size_t)first + a]);
-    if (types != nullptr && mask_type >= 0)
-        for (int a = tid; a < n; a += 64 * SCREEN_WAVES) masked |= types[(size_t)first + a] == mask_type;
-    bad = __syncthreads_or(bad);
+    int masked = 0;
+    const bool bad = crystal_prologue(frac, lattice, offsets, b, N, first, n, Lm, [&] {  // NONFINITE, and MASKED ahead of its barrier
+        if (types != nullptr && mask_type >= 0)
+            for (int a = tid; a < n; a += CRYSTAL_THREADS) masked |= types[(size_t)first + a] == mask_type;
+    });
     masked = __syncthreads_or(masked);
+
+    __shared__ float spos[3 * CRYSTAL_LDS_ATOMS];
+    __shared__ unsigned s_d2[CRYSTAL_WAVES];
+    __shared__ unsigned long long s_ij[CRYSTAL_WAVES];
+    __shared__ unsigned s_m[CRYSTAL_WAVES];
+    __shared__ int s_close[CRYSTAL_WAVES];
+
     const float qnan = __int_as_float(0x7fc00000);
     if (bad) {  // (workgroup-uniform) nothing else is computed
         if (tid == 0) {
@@ -55,17 +43,9 @@ __global__ __launch_bounds__(64 * SCREEN_WAVES) void crystal_screen_kernel(
     }
 
     // ---- the cell: volume, plane spacings, images per axis (every thread computes the same values)
-    float c0[3], c1[3], c2[3];
-    cross_rn(Lm + 3, Lm + 6, c0);
-    cross_rn(Lm + 6, Lm + 0, c1);
-    cross_rn(Lm + 0, Lm + 3, c2);
-    const float volume = fabsf(dot3_rn(Lm[0], Lm[1], Lm[2], c0[0], c0[1], c0[2]));
-    const float density = __fdiv_rn((float)n, volume);
-    const float q0 = __fdiv_rn(radius, __fdiv_rn(volume, sqrtf(dot3_rn(c0[0], c0[1], c0[2], c0[0], c0[1], c0[2]))));
-    const float q1 = __fdiv_rn(radius, __fdiv_rn(volume, sqrtf(dot3_rn(c1[0], c1[1], c1[2], c1[0], c1[1], c1[2]))));
-    const float q2 = __fdiv_rn(radius, __fdiv_rn(volume, sqrtf(dot3_rn(c2[0], c2[1], c2[2], c2[0], c2[1], c2[2]))));
-    const float cap = (float)max_shells;
-    const bool cell_bad = !(volume >= min_volume) || !isfinite(volume) || !(q0 <= cap) || !(q1 <= cap) || !(q2 <= cap);
+    crystal_cell cell;
+    const bool cell_bad = crystal_cell_measure(Lm, radius, max_shells, cell) || !(cell.volume >= min_volume);
+    const float volume = cell.volume, density = __fdiv_rn((float)n, volume);
     int flags = masked ? ARREAU_SCREEN_MASKED : 0;
     if (cell_bad) {  // (workgroup-uniform) the search is skipped
         if (tid == 0) {
@@ -75,15 +55,12 @@ __global__ __launch_bounds__(64 * SCREEN_WAVES) void crystal_screen_kernel(
         if (tid < 5) o_pair[5 * (size_t)b + tid] = -1;
         return;
     }
-    // q_k <= max_shells <= 8 here, so n_k <= 8 and M <= 17^3
-    const int N1 = max(1, (int)ceilf(q0)), N2 = max(1, (int)ceilf(q1)), N3 = max(1, (int)ceilf(q2));
-    const unsigned W2 = 2u * N2 + 1u, W3 = 2u * N3 + 1u, M = (2u * N1 + 1u) * W2 * W3;
-    const unsigned centre = ((unsigned)N1 * W2 + (unsigned)N2) * W3 + (unsigned)N3;
+    crystal_cell_images(cell);
 
     // ---- positions: staged in LDS when the crystal fits, else formed from global memory where they are used (same values)
-    const bool staged = n <= SCREEN_LDS_ATOMS;
+    const bool staged = n <= CRYSTAL_LDS_ATOMS;
     if (staged)
-        for (int a = tid; a < 3 * n; a += 64 * SCREEN_WAVES) spos[a] = crystal_cart(frac, Lm, (size_t)first + a / 3, a % 3);
+        for (int a = tid; a < 3 * n; a += CRYSTAL_THREADS) spos[a] = crystal_cart(frac, Lm, (size_t)first + a / 3, a % 3);
     __syncthreads();
     auto position = [&](int atom, int d) -> float { return staged ? spos[3 * atom + d] : crystal_cart(frac, Lm, (size_t)first + atom, d); };
 
@@ -95,10 +72,11 @@ __global__ __launch_bounds__(64 * SCREEN_WAVES) void crystal_screen_kernel(
     for (int i = 0; i < n; ++i) {
         const float pix = position(i, 0), piy = position(i, 1), piz = position(i, 2);
         auto contact = [&](unsigned dj, unsigned m) {
-            if (dj == 0 && m <= centre) return;  // an atom with itself: only the images after (0, 0, 0)
+            if (dj == 0 && m <= cell.centre) return;  // an atom with itself: only the images after (0, 0, 0)
             const int j = i + (int)dj;
-            const unsigned m12 = m / W3;
-            const float n3 = (float)((int)(m - m12 * W3) - N3), n2 = (float)((int)(m12 % W2) - N2), n1 = (float)((int)(m12 / W2) - N1);
+            // contact_d2's operations, spelled out: called through the helper they are packed in pairs and this loop is slower
+            const unsigned m12 = m / cell.W3;
+            const float n3 = (float)((int)(m - m12 * cell.W3) - cell.N3), n2 = (float)((int)(m12 % cell.W2) - cell.N2), n1 = (float)((int)(m12 / cell.W2) - cell.N1);
             const float sx = __fadd_rn(__fadd_rn(__fmul_rn(n1, Lm[0]), __fmul_rn(n2, Lm[3])), __fmul_rn(n3, Lm[6]));
             const float sy = __fadd_rn(__fadd_rn(__fmul_rn(n1, Lm[1]), __fmul_rn(n2, Lm[4])), __fmul_rn(n3, Lm[7]));
             const float sz = __fadd_rn(__fadd_rn(__fmul_rn(n1, Lm[2]), __fmul_rn(n2, Lm[5])), __fmul_rn(n3, Lm[8]));
@@ -114,16 +92,16 @@ __global__ __launch_bounds__(64 * SCREEN_WAVES) void crystal_screen_kernel(
                 best_m = m;
             }
         };
-        const unsigned long long span = (unsigned long long)(n - i) * M;
-        if (span <= 0xffffffffull - 64 * SCREEN_WAVES) {  // (uniform) the usual case: 32-bit index arithmetic
-            for (unsigned e = (unsigned)tid; e < (unsigned)span; e += 64 * SCREEN_WAVES) {
-                const unsigned dj = e / M;
-                contact(dj, e - dj * M);
+        const unsigned long long span = (unsigned long long)(n - i) * cell.M;
+        if (span <= 0xffffffffull - CRYSTAL_THREADS) {  // (uniform) the usual case: 32-bit index arithmetic
+            for (unsigned e = (unsigned)tid; e < (unsigned)span; e += CRYSTAL_THREADS) {
+                const unsigned dj = e / cell.M;
+                contact(dj, e - dj * cell.M);
             }
         } else {
-            for (unsigned long long e = (unsigned long long)tid; e < span; e += 64 * SCREEN_WAVES) {
-                const unsigned long long dj = e / M;
-                contact((unsigned)dj, (unsigned)(e - dj * M));
+            for (unsigned long long e = (unsigned long long)tid; e < span; e += CRYSTAL_THREADS) {
+                const unsigned long long dj = e / cell.M;
+                contact((unsigned)dj, (unsigned)(e - dj * cell.M));
             }
         }
     }
@@ -147,7 +125,7 @@ __global__ __launch_bounds__(64 * SCREEN_WAVES) void crystal_screen_kernel(
         unsigned d2b = s_d2[0], mm = s_m[0];
         unsigned long long ij = s_ij[0];
         int total = s_close[0];
-        for (int w = 1; w < SCREEN_WAVES; ++w) {
+        for (int w = 1; w < CRYSTAL_WAVES; ++w) {
             total += s_close[w];
             const bool less = s_d2[w] < d2b || (s_d2[w] == d2b && (s_ij[w] < ij || (s_ij[w] == ij && s_m[w] < mm)));
             if (less) { d2b = s_d2[w]; ij = s_ij[w]; mm = s_m[w]; }
@@ -161,9 +139,8 @@ __global__ __launch_bounds__(64 * SCREEN_WAVES) void crystal_screen_kernel(
         } else {
             const float d2 = __uint_as_float(d2b);
             o_dist[b] = sqrtf(d2);  // correctly rounded, like the neighbour list's distance
-            const unsigned m12 = mm / W3;
             pr[0] = (int)(ij >> 24); pr[1] = (int)(ij & 0xffffffull);
-            pr[2] = (int)(m12 / W2) - N1; pr[3] = (int)(m12 % W2) - N2; pr[4] = (int)(mm - m12 * W3) - N3;
+            crystal_image(cell, mm, pr + 2);
             if (!(d2 <= r2)) flags |= ARREAU_SCREEN_BEYOND;
         }
         o_volume[b] = volume; o_density[b] = density;
@@ -191,7 +168,7 @@ extern "C" int arreau_crystal_screen(const float* d_frac, const int32_t* d_types
                    "arreau_crystal_screen: null result array");
     const float md2 = (float)((double)crit->min_distance * (double)crit->min_distance);
     const float r2 = (float)((double)crit->search_radius * (double)crit->search_radius);
-    ARREAU_LAUNCH(crystal_screen_kernel, dim3((unsigned)B), dim3(64 * SCREEN_WAVES), 0, (hipStream_t)stream, d_frac, d_types, d_lattice,
+    ARREAU_LAUNCH(crystal_screen_kernel, dim3((unsigned)B), dim3(CRYSTAL_THREADS), 0, (hipStream_t)stream, d_frac, d_types, d_lattice,
                   d_crystal_offsets, (int)B, (int)N, crit->min_volume, md2, r2, crit->search_radius, (int)crit->mask_type,
                   (int)crit->max_shells, out->min_distance, out->pair, out->n_close, out->volume, out->number_density, out->flags);
     ARREAU_CHECK_HIP(hipGetLastError());

@@ -12,10 +12,7 @@
 #include "symfind_table.h"
 #include <cmath>
 
-#define SYM_LDS_ATOMS 256  // crystals of up to this many atoms keep their wrapped coordinates and species in LDS (4 KiB)
-#define SYM_WAVES 4
-#define SYM_THREADS (64 * SYM_WAVES)
-#define SYM_ROUND SYM_THREADS  // candidate translations per round: one compaction pass of the workgroup
+#define SYM_ROUND CRYSTAL_THREADS  // candidate translations per round: one compaction pass of the workgroup
 #define SYM_CODES 19683        // 3^9
 #define SYM_IDENTITY 16484
 #define SYM_MAX_LATTICE 48
@@ -78,36 +75,31 @@ __device__ __forceinline__ int rotation_type(int det, int trace) {
     return trace >= -3 && trace <= 1 ? (trace == -3 ? 5 : 7 - trace) : -1;
 }
 
-__global__ __launch_bounds__(SYM_THREADS) void crystal_symmetry_kernel(
+__global__ __launch_bounds__(CRYSTAL_THREADS) void crystal_symmetry_kernel(
     const float* __restrict__ frac, const int32_t* __restrict__ types, const float* __restrict__ lattice,
     const int32_t* __restrict__ offsets, int B, int N, float symprec, int max_ops, sym_out o) {
     const int b = blockIdx.x;
     if (b >= B) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // the crystal's atom range, clamped into [0, N]: a bad offset table cannot make the kernel read outside frac / types
-    int first = offsets[b], last = offsets[b + 1];
-    first = first < 0 ? 0 : (first > N ? N : first);
-    last = last < first ? first : (last > N ? N : last);
-    const int n = last - first;
+    int first, n;
     float Lm[9];
-#pragma unroll
-    for (int q = 0; q < 9; ++q) Lm[q] = lattice[9 * (size_t)b + q];
+    const bool bad = crystal_prologue(frac, lattice, offsets, b, N, first, n, Lm, [] {});
 
-    __shared__ float sw[3 * SYM_LDS_ATOMS];
-    __shared__ int sty[SYM_LDS_ATOMS];
+    __shared__ float sw[3 * CRYSTAL_LDS_ATOMS];
+    __shared__ int sty[CRYSTAL_LDS_ATOMS];
     __shared__ int s_codes[SYM_MAX_LATTICE];
     __shared__ int s_q[SYM_ROUND];
     __shared__ float s_res[SYM_ROUND];
-    __shared__ int s_cnt[SYM_WAVES];
-    __shared__ unsigned s_ka[SYM_WAVES], s_kb[SYM_WAVES];
-    __shared__ float s_max[SYM_WAVES];
+    __shared__ int s_cnt[CRYSTAL_WAVES];
+    __shared__ unsigned s_ka[CRYSTAL_WAVES], s_kb[CRYSTAL_WAVES];
+    __shared__ float s_max[CRYSTAL_WAVES];
 
     int32_t* o_rot = o.ops_rotation + (size_t)b * max_ops;
     float* o_trans = o.ops_translation + 3 * (size_t)b * max_ops;
     float* o_res = o.ops_residual + (size_t)b * max_ops;
     const float qnan = __int_as_float(0x7fc00000);
     auto clear_ops = [&](int from) {  // the slots no operation was stored in
-        for (int k = from + tid; k < max_ops; k += SYM_THREADS) {
+        for (int k = from + tid; k < max_ops; k += CRYSTAL_THREADS) {
             o_rot[k] = -1; o_res[k] = 0.f;
             o_trans[3 * (size_t)k] = 0.f; o_trans[3 * (size_t)k + 1] = 0.f; o_trans[3 * (size_t)k + 2] = 0.f;
         }
@@ -121,18 +113,11 @@ __global__ __launch_bounds__(SYM_THREADS) void crystal_symmetry_kernel(
     };
 
     // ---- rule 1: NONFINITE, CELL, EMPTY (workgroup-uniform; nothing else is computed)
-    int bad = 0;
-#pragma unroll
-    for (int q = 0; q < 9; ++q) bad |= !isfinite(Lm[q]);
-    for (int a = tid; a < 3 * n; a += SYM_THREADS) bad |= !isfinite(frac[3 * (size_t)first + a]);
-    bad = __syncthreads_or(bad);
     if (bad) {
         no_result(ARREAU_SYM_NONFINITE, 0);
         return;
     }
-    float c0[3];
-    cross_rn(Lm + 3, Lm + 6, c0);
-    const float volume = fabsf(dot3_rn(Lm[0], Lm[1], Lm[2], c0[0], c0[1], c0[2]));
+    const float volume = crystal_volume(Lm);
     const int early = ((!(volume > 0.f) || !isfinite(volume)) ? ARREAU_SYM_CELL : 0) | (n == 0 ? ARREAU_SYM_EMPTY : 0);
     if (early) {
         no_result(early, 0);
@@ -146,7 +131,7 @@ __global__ __launch_bounds__(SYM_THREADS) void crystal_symmetry_kernel(
     G[0] = dot3_rn(Lm[0], Lm[1], Lm[2], Lm[3], Lm[4], Lm[5]);
     G[1] = dot3_rn(Lm[0], Lm[1], Lm[2], Lm[6], Lm[7], Lm[8]);
     G[2] = dot3_rn(Lm[3], Lm[4], Lm[5], Lm[6], Lm[7], Lm[8]);
-    constexpr int PER = (SYM_CODES + SYM_THREADS - 1) / SYM_THREADS;
+    constexpr int PER = (SYM_CODES + CRYSTAL_THREADS - 1) / CRYSTAL_THREADS;
     const int code0 = tid * PER, code1 = min(code0 + PER, SYM_CODES);
     int mine = 0;
     for (int c = code0; c < code1; ++c) mine += lattice_candidate(c, Lm, G, len, symprec) ? 1 : 0;
@@ -160,7 +145,7 @@ __global__ __launch_bounds__(SYM_THREADS) void crystal_symmetry_kernel(
     __syncthreads();
     int n_lattice = 0, before = 0;
 #pragma unroll
-    for (int w = 0; w < SYM_WAVES; ++w) {
+    for (int w = 0; w < CRYSTAL_WAVES; ++w) {
         before += w < wave ? s_cnt[w] : 0;
         n_lattice += s_cnt[w];
     }
@@ -175,10 +160,10 @@ __global__ __launch_bounds__(SYM_THREADS) void crystal_symmetry_kernel(
     }
 
     // ---- positions and species: staged in LDS when the crystal fits, else read where they are used (the same values)
-    const bool staged = n <= SYM_LDS_ATOMS;
+    const bool staged = n <= CRYSTAL_LDS_ATOMS;
     if (staged) {
-        for (int a = tid; a < 3 * n; a += SYM_THREADS) sw[a] = crystal_wrap(frac[3 * (size_t)first + a]);
-        for (int a = tid; a < n; a += SYM_THREADS) sty[a] = types[(size_t)first + a];
+        for (int a = tid; a < 3 * n; a += CRYSTAL_THREADS) sw[a] = crystal_wrap(frac[3 * (size_t)first + a]);
+        for (int a = tid; a < n; a += CRYSTAL_THREADS) sty[a] = types[(size_t)first + a];
     }
     __syncthreads();
     auto wpos = [&](int atom, int d) -> float { return staged ? sw[3 * atom + d] : crystal_wrap(frac[3 * ((size_t)first + atom) + d]); };
@@ -187,7 +172,7 @@ __global__ __launch_bounds__(SYM_THREADS) void crystal_symmetry_kernel(
     // ---- rule 3: the rarest species (fewest atoms, then the smallest id) and its first atom p0.  Key (count, id with the sign
     // bit flipped: unsigned order = signed order), minimum over the wave by shuffles, over the waves through LDS.
     unsigned ka = 0xffffffffu, kb = 0xffffffffu;
-    for (int a = tid; a < n; a += SYM_THREADS) {
+    for (int a = tid; a < n; a += CRYSTAL_THREADS) {
         const int ta = species(a);
         unsigned cnt = 0;
         for (int j = 0; j < n; ++j) cnt += species(j) == ta ? 1u : 0u;
@@ -202,19 +187,19 @@ __global__ __launch_bounds__(SYM_THREADS) void crystal_symmetry_kernel(
     if (lane == 0) { s_ka[wave] = ka; s_kb[wave] = kb; }
     __syncthreads();
 #pragma unroll
-    for (int w = 0; w < SYM_WAVES; ++w)
+    for (int w = 0; w < CRYSTAL_WAVES; ++w)
         if (s_ka[w] < ka || (s_ka[w] == ka && s_kb[w] < kb)) { ka = s_ka[w]; kb = s_kb[w]; }
     const int rare = (int)(kb ^ 0x80000000u);
     __syncthreads();  // (s_ka is written again below)
     unsigned p0u = 0xffffffffu;
-    for (int a = tid; a < n; a += SYM_THREADS)
+    for (int a = tid; a < n; a += CRYSTAL_THREADS)
         if (species(a) == rare) { p0u = (unsigned)a; break; }  // (ascending a: the thread's first is its smallest)
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) p0u = min(p0u, (unsigned)__shfl_xor(p0u, off));
     if (lane == 0) s_ka[wave] = p0u;
     __syncthreads();
 #pragma unroll
-    for (int w = 0; w < SYM_WAVES; ++w) p0u = min(p0u, s_ka[w]);
+    for (int w = 0; w < CRYSTAL_WAVES; ++w) p0u = min(p0u, s_ka[w]);
     const int p0 = (int)p0u;  // n >= 1, so the species exists
     const float wp0[3] = {wpos(p0, 0), wpos(p0, 1), wpos(p0, 2)};
 
@@ -237,21 +222,12 @@ __global__ __launch_bounds__(SYM_THREADS) void crystal_symmetry_kernel(
             if (n_rounds > 1 || wi == 0) {  // (uniform) the rarest species' atoms of this round, ascending: one list serves every W
                 const int a = round * SYM_ROUND + tid;
                 const bool is = a < n && species(a) == rare;
-                const unsigned long long mask = __ballot(is);
-                if (lane == 0) s_cnt[wave] = __popcll(mask);
-                __syncthreads();
-                int base = 0;
-                nq = 0;
-#pragma unroll
-                for (int w = 0; w < SYM_WAVES; ++w) {
-                    base += w < wave ? s_cnt[w] : 0;
-                    nq += s_cnt[w];
-                }
-                if (is) s_q[base + __popcll(mask & ((1ull << lane) - 1ull))] = a;
+                const int at = crystal_compact(is, lane, wave, s_cnt, nq);
+                if (is) s_q[at] = a;
                 __syncthreads();
             }
             // the round's pairs dealt to the waves: residual = max over i of min over j of the same species
-            for (int k = wave; k < nq; k += SYM_WAVES) {
+            for (int k = wave; k < nq; k += CRYSTAL_WAVES) {
                 const int q = s_q[k];
                 const float t0 = translation(q, 0), t1 = translation(q, 1), t2 = translation(q, 2);
                 float worst2 = 0.f;
@@ -287,26 +263,18 @@ __global__ __launch_bounds__(SYM_THREADS) void crystal_symmetry_kernel(
             // the accepted operations of the round, compacted in q order (nq <= SYM_ROUND: one pass)
             const bool acc = tid < nq && s_res[tid] >= 0.f;
             const float res = acc ? s_res[tid] : 0.f;
-            const unsigned long long mask = __ballot(acc);
             float rmax = res;
 #pragma unroll
             for (int off = 32; off >= 1; off >>= 1) rmax = fmaxf(rmax, __shfl_xor(rmax, off));
-            if (lane == 0) { s_cnt[wave] = __popcll(mask); s_max[wave] = rmax; }
-            __syncthreads();
-            int base = 0, accepted = 0;
+            if (lane == 0) s_max[wave] = rmax;
+            int accepted;
+            const long long slot = (long long)total + crystal_compact(acc, lane, wave, s_cnt, accepted);
 #pragma unroll
-            for (int w = 0; w < SYM_WAVES; ++w) {
-                base += w < wave ? s_cnt[w] : 0;
-                accepted += s_cnt[w];
-                worst = fmaxf(worst, s_max[w]);
-            }
-            if (acc) {
-                const long long slot = (long long)total + base + __popcll(mask & ((1ull << lane) - 1ull));
-                if (slot < max_ops) {
-                    const int q = s_q[tid];
-                    o_rot[slot] = code; o_res[slot] = res;
-                    o_trans[3 * slot] = translation(q, 0); o_trans[3 * slot + 1] = translation(q, 1); o_trans[3 * slot + 2] = translation(q, 2);
-                }
+            for (int w = 0; w < CRYSTAL_WAVES; ++w) worst = fmaxf(worst, s_max[w]);
+            if (acc && slot < max_ops) {
+                const int q = s_q[tid];
+                o_rot[slot] = code; o_res[slot] = res;
+                o_trans[3 * slot] = translation(q, 0); o_trans[3 * slot + 1] = translation(q, 1); o_trans[3 * slot + 2] = translation(q, 2);
             }
             total += accepted;
             __syncthreads();  // s_q, s_res, s_cnt and s_max are written again in the next round
@@ -356,7 +324,7 @@ extern "C" int arreau_crystal_symmetry(const float* d_frac, const int32_t* d_typ
                    "arreau_crystal_symmetry: null result array");
     sym_out o{out->n_lattice, out->n_ops, out->n_translations, out->ops_rotation, out->ops_translation, out->ops_residual,
               out->residual, out->point_group, out->flags};
-    ARREAU_LAUNCH(crystal_symmetry_kernel, dim3((unsigned)B), dim3(SYM_THREADS), 0, (hipStream_t)stream, d_frac, d_types, d_lattice,
+    ARREAU_LAUNCH(crystal_symmetry_kernel, dim3((unsigned)B), dim3(CRYSTAL_THREADS), 0, (hipStream_t)stream, d_frac, d_types, d_lattice,
                   d_crystal_offsets, (int)B, (int)N, params->symprec, (int)params->max_ops, o);
     ARREAU_CHECK_HIP(hipGetLastError());
     return ARREAU_OK;

@@ -40,11 +40,13 @@ from typing import Optional
 
 import numpy as np
 
+from . import crystal_batch as cb
+
 NONFINITE, CELL, CLOSE, MASKED, BEYOND = 1, 2, 4, 8, 16
 FLAG_NAMES = ((NONFINITE, "NONFINITE"), (CELL, "CELL"), (CLOSE, "CLOSE"), (MASKED, "MASKED"), (BEYOND, "BEYOND"))
 INVALID_MASK = NONFINITE | CELL | CLOSE | MASKED  # BEYOND is informational
 MAX_SHELLS = 8
-STAGED_ATOMS = 256  # crystals of up to this many atoms keep their positions in LDS (screen.hip: SCREEN_LDS_ATOMS)
+STAGED_ATOMS = cb.STAGED_ATOMS
 METRIC_KEYS = ("min_distance", "pair", "n_close", "volume", "number_density", "flags")
 DISTANCE_BOUND_FACTOR = 32.0
 F32 = np.float32
@@ -103,13 +105,7 @@ class ScreenCriteria:
 
 def resolve(screen):
     """sample(screen=...): None / False -> None, True -> the defaults, a ScreenCriteria -> itself."""
-    if screen is None or screen is False:
-        return None
-    if screen is True:
-        return ScreenCriteria()
-    if isinstance(screen, ScreenCriteria):
-        return screen
-    raise ValueError(f"screen must be None, True or a ScreenCriteria, got {screen!r}")
+    return cb.resolve(screen, ScreenCriteria, "screen")
 
 
 def screen(frac, lattice, offsets, types=None, criteria=None):
@@ -124,13 +120,7 @@ def screen(frac, lattice, offsets, types=None, criteria=None):
     from .. import _hip
     _hip.require_gpu()
     crit = (criteria if criteria is not None else ScreenCriteria()).with_mask_type(-1)
-    dev = frac.device
-    B, N = int(lattice.shape[0]), int(frac.shape[0])
-    want = [("frac", frac, (N, 3), torch.float32), ("lattice", lattice, (B, 3, 3), torch.float32),
-            ("offsets", offsets, (B + 1,), torch.int32)] + ([("types", types, (N,), torch.int32)] if types is not None else [])
-    for name, t, shape, dtype in want:
-        if tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous() or dev.type != "cuda":
-            raise ValueError(f"screen: {name} must be a contiguous {dtype} tensor of shape {shape} on the cuda device of frac")
+    dev, B, N = cb.check_batch("screen", frac, lattice, offsets, types, types_optional=True)
     f32, i32 = dict(device=dev, dtype=torch.float32), dict(device=dev, dtype=torch.int32)
     out = {"min_distance": torch.empty(B, **f32), "pair": torch.empty((B, 5), **i32), "n_close": torch.empty(B, **i32),
            "volume": torch.empty(B, **f32), "number_density": torch.empty(B, **f32), "flags": torch.empty(B, **i32)}
@@ -157,19 +147,11 @@ def screen_sample_result(result, criteria=None, device="cuda"):
 
     from .tools.atomic_number_table import AtomicNumberTable
     crit = criteria if criteria is not None else ScreenCriteria()
-    num_atoms = np.asarray(result.num_atoms, dtype=np.int64)
-    off = np.concatenate([[0], np.cumsum(num_atoms)]).astype(np.int32)
-    dev = torch.device(device)
-    numbers = np.asarray(result.atomic_numbers).reshape(-1)
+    frac, lattice, off, types = cb.upload(result, device)
     if crit.mask_type is None:  # 1 where the atom is the mask state, looked for as class 1
-        types = (np.rint(numbers) == AtomicNumberTable.MASK_ATOMIC_NUMBER).astype(np.int32)
+        types = (types == AtomicNumberTable.MASK_ATOMIC_NUMBER).to(torch.int32)
         crit = crit.with_mask_type(1)
-    else:
-        types = np.rint(numbers).astype(np.int32)
-    lattice = np.asarray(result.lattice, dtype=np.float32).reshape(-1, 3, 3)
-    out = screen(torch.as_tensor(np.ascontiguousarray(result.frac_x, dtype=np.float32).reshape(-1, 3), device=dev),
-                 torch.as_tensor(np.ascontiguousarray(lattice), device=dev), torch.as_tensor(off, device=dev),
-                 torch.as_tensor(types, device=dev), crit)
+    out = screen(frac, lattice, off, types, crit)
     return metrics_to_numpy(out)
 
 
@@ -219,41 +201,6 @@ def _cutoff2(x):
     return F32(np.float64(F32(x)) ** 2)
 
 
-def _cell_f32(L, crit):
-    """Volume, shells and the CELL decision of one finite cell [3,3] float32: (volume, q [3] float32, cell_bad)."""
-    a = [L[0], L[1], L[2]]
-    cross = lambda u, v: np.array([u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]], dtype=F32)
-    c = [cross(a[1], a[2]), cross(a[2], a[0]), cross(a[0], a[1])]
-    det = (a[0][0] * c[0][0] + a[0][1] * c[0][1]) + a[0][2] * c[0][2]
-    vol = np.abs(det)
-    with np.errstate(all="ignore"):
-        q = np.array([F32(crit.search_radius) / (vol / np.sqrt((ck[0] * ck[0] + ck[1] * ck[1]) + ck[2] * ck[2])) for ck in c], dtype=F32)
-    bad = (not vol >= F32(crit.min_volume)) or (not np.isfinite(vol)) or any(not qk <= F32(crit.max_shells) for qk in q)
-    return vol, q, bad
-
-
-def _shift_table(nk):
-    """[M,3] integer images in lexicographic order and the index of (0, 0, 0)."""
-    g = np.stack(np.meshgrid(*[np.arange(-k, k + 1) for k in nk], indexing="ij"), -1).reshape(-1, 3)
-    return g, int(((nk[0] * (2 * nk[1] + 1)) + nk[1]) * (2 * nk[2] + 1) + nk[2])
-
-
-def _contacts(p, s, centre, dtype, chunk=1 << 19):
-    """Every contact of one crystal in the rule's enumeration order: yields (i [K], j [K], m [K], d2 [K]) blocks; p [n,3]
-    positions, s [M,3] shift vectors, both of `dtype`, every operation rounded to it."""
-    n, M = p.shape[0], s.shape[0]
-    iu, ju = np.triu_indices(n)  # row-major: lexicographic (i, j), i <= j
-    step = max(1, chunk // M)
-    for a in range(0, iu.size, step):
-        i, j = iu[a:a + step], ju[a:a + step]
-        disp = ((p[j][:, None, :] + s[None, :, :]).astype(dtype) - p[i][:, None, :]).astype(dtype)
-        sq = (disp * disp).astype(dtype)
-        d2 = ((sq[..., 0] + sq[..., 1]).astype(dtype) + sq[..., 2]).astype(dtype)
-        m = np.broadcast_to(np.arange(M)[None, :], d2.shape)
-        keep = (i != j)[:, None] | (m > centre)
-        yield (np.broadcast_to(i[:, None], d2.shape)[keep], np.broadcast_to(j[:, None], d2.shape)[keep], m[keep], d2[keep])
-
-
 def _empty_result(B):
     return SimpleNamespace(min_distance=np.full(B, np.nan, F32), pair=np.full((B, 5), -1, np.int32), n_close=np.zeros(B, np.int32),
                            volume=np.full(B, np.nan, F32), number_density=np.full(B, np.nan, F32), flags=np.zeros(B, np.int32))
@@ -264,21 +211,12 @@ def _finish(out):
     return out
 
 
-def _inputs(frac, lattice, counts, types, criteria):
-    frac = np.ascontiguousarray(frac, dtype=F32).reshape(-1, 3)
-    lattice = np.ascontiguousarray(lattice, dtype=F32).reshape(-1, 3, 3)
-    counts = [int(n) for n in counts]
-    assert sum(counts) == frac.shape[0] and len(counts) == lattice.shape[0]
-    types = None if types is None else np.asarray(types, dtype=np.int64).reshape(-1)
-    crit = (criteria if criteria is not None else ScreenCriteria()).with_mask_type(-1)
-    return frac, lattice, counts, types, crit, np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-
-
 def screen_reference_f32(frac, lattice, counts, types=None, criteria=None):
     """The kernel's rule in numpy float32, one operation at a time in the kernel's order (numpy never contracts to an FMA):
     frac [N,3], lattice [B,3,3], counts [B] atoms per crystal, types [N] or None.  Returns a namespace of the six outputs
     (+ valid), to be compared with the kernel's bit for bit."""
-    frac, lattice, counts, types, crit, first = _inputs(frac, lattice, counts, types, criteria)
+    frac, lattice, counts, types, first = cb.inputs(frac, lattice, counts, types)
+    crit = (criteria if criteria is not None else ScreenCriteria()).with_mask_type(-1)
     out = _empty_result(len(counts))
     md2, r2 = _cutoff2(crit.min_distance), _cutoff2(crit.search_radius)
     for b, n in enumerate(counts):
@@ -286,7 +224,7 @@ def screen_reference_f32(frac, lattice, counts, types=None, criteria=None):
         if not (np.isfinite(L).all() and np.isfinite(f).all()):
             out.flags[b] = NONFINITE
             continue
-        vol, q, bad = _cell_f32(L, crit)
+        vol, q, bad = cb.cell_f32(L, crit.search_radius, crit.min_volume, crit.max_shells)
         out.volume[b] = vol
         with np.errstate(all="ignore"):
             out.number_density[b] = F32(n) / vol
@@ -296,14 +234,9 @@ def screen_reference_f32(frac, lattice, counts, types=None, criteria=None):
             out.flags[b] |= CELL
             continue
         nk = [max(1, int(np.ceil(qk))) for qk in q]
-        w = (f - np.floor(f)).astype(F32)
-        w[w >= F32(1)] = F32(0)
-        p = ((w[:, 0:1] * L[0][None] + w[:, 1:2] * L[1][None]) + w[:, 2:3] * L[2][None]).astype(F32)
-        g, centre = _shift_table(nk)
-        gf = g.astype(F32)
-        s = ((gf[:, 0:1] * L[0][None] + gf[:, 1:2] * L[1][None]) + gf[:, 2:3] * L[2][None]).astype(F32)
+        p, g, centre, s = cb.positions_and_shifts(f, L, nk, F32)
         best, close = None, 0
-        for i, j, m, d2 in _contacts(p, s, centre, F32):
+        for i, j, m, d2 in cb.contacts(p, s, centre, F32):
             close += int((d2 < md2).sum())
             if d2.size:
                 e = int(np.argmin(d2))  # the first of equal minima: the enumeration order is (i, j, m)
@@ -337,7 +270,8 @@ def screen_reference_f64(frac, lattice, counts, types=None, criteria=None, widen
     show).  Outputs are float64 / integers.  details=True adds `shells` [B,3] (n_k without the widening), `bound` [B]
     (distance_bound), `q` [B,3] (search_radius / h_k), `nearest` (per crystal, the up to 8 smallest contact distances) and
     `near_threshold` [B] (contacts whose distance lies within 2 bound of min_distance: n_close may differ in float32)."""
-    frac, lattice, counts, types, crit, first = _inputs(frac, lattice, counts, types, criteria)
+    frac, lattice, counts, types, first = cb.inputs(frac, lattice, counts, types)
+    crit = (criteria if criteria is not None else ScreenCriteria()).with_mask_type(-1)
     B = len(counts)
     out = _empty_result(B)
     out.min_distance, out.volume, out.number_density = (np.full(B, np.nan) for _ in range(3))
@@ -349,12 +283,10 @@ def screen_reference_f64(frac, lattice, counts, types=None, criteria=None, widen
         if not (np.isfinite(L).all() and np.isfinite(f).all()):
             out.flags[b] = NONFINITE
             continue
-        c = np.array([np.cross(L[1], L[2]), np.cross(L[2], L[0]), np.cross(L[0], L[1])])
-        vol = abs(float(np.dot(L[0], c[0])))
+        vol, q = cb.cell_f64(L, R)
         out.volume[b] = vol
         with np.errstate(all="ignore"):
             out.number_density[b] = n / vol if vol > 0 else np.inf
-            q = R * np.linalg.norm(c, axis=1) / vol if vol > 0 else np.full(3, np.inf)
         out.q[b] = q
         if types is not None and crit.mask_type >= 0 and (types[first[b]:first[b + 1]] == crit.mask_type).any():
             out.flags[b] |= MASKED
@@ -363,13 +295,9 @@ def screen_reference_f64(frac, lattice, counts, types=None, criteria=None, widen
             continue
         nk = np.maximum(1, np.ceil(q).astype(np.int64))
         out.shells[b], out.bound[b] = nk, distance_bound(L, nk)
-        w = f - np.floor(f)
-        w[w >= 1.0] = 0.0
-        p = w @ L
-        g, centre = _shift_table(nk + int(widen))
-        s = g.astype(np.float64) @ L
+        p, g, centre, s = cb.positions_and_shifts(f, L, nk + int(widen), np.float64)
         best, close, nearest = None, 0, np.empty(0)
-        for i, j, m, d2 in _contacts(p, s, centre, np.float64):
+        for i, j, m, d2 in cb.contacts(p, s, centre, np.float64):
             close += int((d2 < md * md).sum())
             out.near_threshold[b] += int((np.abs(np.sqrt(d2) - md) <= 2 * out.bound[b]).sum())
             if d2.size:

@@ -37,6 +37,7 @@ from types import SimpleNamespace
 
 import numpy as np
 
+from . import crystal_batch as cb
 from . import symmetry as sym_mod
 
 NONFINITE, CELL, EMPTY, AMBIGUOUS, OVERFLOW, NOT_A_GROUP = 1, 2, 4, 8, 16, 32
@@ -45,7 +46,7 @@ FLAG_NAMES = ((NONFINITE, "NONFINITE"), (CELL, "CELL"), (EMPTY, "EMPTY"), (AMBIG
 NO_RESULT_MASK = NONFINITE | CELL | EMPTY | AMBIGUOUS  # nothing else is reported for such a crystal
 MAX_OPS_CAP = 4096        # symfind.hip / arreau_hip.h: ARREAU_SYM_MAX_OPS_CAP
 MAX_LATTICE = 48          # a lattice has at most 48 isometries
-STAGED_ATOMS = 256        # symfind.hip: SYM_LDS_ATOMS -- also the number of candidate translations handled per round
+STAGED_ATOMS = cb.STAGED_ATOMS  # also the number of candidate translations handled per round (symfind.hip: SYM_ROUND)
 N_CODES = 3 ** 9
 IDENTITY_CODE = 16484
 DEFAULT_SYMPREC, DEFAULT_MAX_OPS = 0.1, 192
@@ -194,13 +195,7 @@ class SymmetrySearchParams:
 
 def resolve(find_symmetry):
     """sample(find_symmetry=...): None / False -> None, True -> the defaults, a SymmetrySearchParams -> itself."""
-    if find_symmetry is None or find_symmetry is False:
-        return None
-    if find_symmetry is True:
-        return SymmetrySearchParams()
-    if isinstance(find_symmetry, SymmetrySearchParams):
-        return find_symmetry
-    raise ValueError(f"find_symmetry must be None, True or a SymmetrySearchParams, got {find_symmetry!r}")
+    return cb.resolve(find_symmetry, SymmetrySearchParams, "find_symmetry")
 
 
 # ------------------------------------------------------------------------------------------------------- the device call
@@ -217,12 +212,7 @@ def find_symmetry(frac, lattice, offsets, types, params=None):
     from .. import _hip
     _hip.require_gpu()
     p = params if params is not None else SymmetrySearchParams()
-    dev = frac.device
-    B, N = int(lattice.shape[0]), int(frac.shape[0])
-    for name, t, shape, dtype in [("frac", frac, (N, 3), torch.float32), ("lattice", lattice, (B, 3, 3), torch.float32),
-                                  ("offsets", offsets, (B + 1,), torch.int32), ("types", types, (N,), torch.int32)]:
-        if t is None or tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous() or dev.type != "cuda":
-            raise ValueError(f"find_symmetry: {name} must be a contiguous {dtype} tensor of shape {shape} on the cuda device of frac")
+    dev, B, N = cb.check_batch("find_symmetry", frac, lattice, offsets, types)
     f32, i32 = dict(device=dev, dtype=torch.float32), dict(device=dev, dtype=torch.int32)
     M = p.max_ops
     out = {"n_lattice": torch.empty(B, **i32), "n_ops": torch.empty(B, **i32), "n_translations": torch.empty(B, **i32),
@@ -248,8 +238,7 @@ def result_to_numpy(result):
 def symmetry_sample_result(result, params=None, device="cuda"):
     """The symmetry of a SampleResult (or a loaded crystals file) on the GPU, its float64 arrays cast to float32 and its atomic
     numbers taken as species ids: the dict of `find_symmetry` as numpy arrays."""
-    from .uniqueness import _upload
-    return result_to_numpy(find_symmetry(*_upload(result, device), params))
+    return result_to_numpy(find_symmetry(*cb.upload(result, device), params))
 
 
 # ------------------------------------------------------------------------------------------------------------- contains
@@ -394,12 +383,8 @@ def symmetry_reference_f64(frac, lattice, counts, types, params=None, details=Fa
     of every candidate of det +-1) and `all_residuals` (the residual of every (W, t) the search evaluates): what the guard of
     the test cases looks at."""
     p = params if params is not None else SymmetrySearchParams()
-    frac = np.ascontiguousarray(frac, dtype=F32).reshape(-1, 3)
-    lattice = np.ascontiguousarray(lattice, dtype=F32).reshape(-1, 3, 3)
-    counts = [int(n) for n in counts]
-    types = np.asarray(types, dtype=np.int64).reshape(-1)
-    assert sum(counts) == frac.shape[0] == types.shape[0] and len(counts) == lattice.shape[0]
-    first = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    frac, lattice, counts, types, first = cb.inputs(frac, lattice, counts, types)
+    assert frac.shape[0] == types.shape[0]
     B, M, symprec = len(counts), p.max_ops, float(F32(p.symprec))
     out = SimpleNamespace(n_lattice=np.zeros(B, np.int32), n_ops=np.zeros(B, np.int32), n_translations=np.zeros(B, np.int32),
                           ops_rotation=np.full((B, M), -1, np.int32), ops_translation=np.zeros((B, M, 3)), ops_residual=np.zeros((B, M)),

@@ -23,13 +23,14 @@ from types import SimpleNamespace
 
 import numpy as np
 
-from . import screening as sc
+from . import crystal_batch as cb
+from .screening import MAX_SHELLS, distance_bound
 
 NONFINITE, CELL, MANY_SPECIES, EMPTY = 1, 2, 4, 8
 FLAG_NAMES = ((NONFINITE, "NONFINITE"), (CELL, "CELL"), (MANY_SPECIES, "MANY_SPECIES"), (EMPTY, "EMPTY"))
 MAX_SPECIES, BINS, COMPONENTS = 8, 64, 36
 ROW = COMPONENTS * BINS
-STAGED_ATOMS = 256        # fingerprint.hip: FP_LDS_ATOMS
+STAGED_ATOMS = cb.STAGED_ATOMS
 LIST, DRAIN = 1024, 768   # fingerprint.hip: FP_LIST, FP_DRAIN -- the contact list is drained once it holds more than DRAIN
 MATCH_TILE = 16           # fingerprint.hip: MATCH_TILE
 UNIQUE_KEYS = ("duplicate_of", "distance", "nearest", "nearest_distance", "flags", "unique")
@@ -48,7 +49,7 @@ class FingerprintParams:
     n_bins: int = BINS
     sigma: float = 0.1
     tolerance: float = DEFAULT_TOLERANCE
-    max_shells: int = sc.MAX_SHELLS
+    max_shells: int = MAX_SHELLS
 
     def __post_init__(self):
         for name in ("r_max", "sigma", "tolerance"):
@@ -61,7 +62,7 @@ class FingerprintParams:
         if not self.r_max > 0.0 or not self.sigma > 0.0:
             raise ValueError(f"r_max and sigma must be > 0, got {self.r_max} and {self.sigma}")
         check_tolerance(self.tolerance)
-        for name, top in (("n_bins", BINS), ("max_shells", sc.MAX_SHELLS)):
+        for name, top in (("n_bins", BINS), ("max_shells", MAX_SHELLS)):
             v = getattr(self, name)
             if not isinstance(v, Integral) or isinstance(v, bool) or not 1 <= int(v) <= top:
                 raise ValueError(f"{name} must lie in 1..{top}, got {v!r}")
@@ -81,13 +82,7 @@ def check_tolerance(tolerance):
 
 def resolve(unique):
     """sample(unique=...): None / False -> None, True -> the defaults, a FingerprintParams -> itself."""
-    if unique is None or unique is False:
-        return None
-    if unique is True:
-        return FingerprintParams()
-    if isinstance(unique, FingerprintParams):
-        return unique
-    raise ValueError(f"unique must be None, True or a FingerprintParams, got {unique!r}")
+    return cb.resolve(unique, FingerprintParams, "unique")
 
 
 def describe(flags) -> str:
@@ -108,12 +103,7 @@ def fingerprint(frac, lattice, offsets, types, params=None):
     from .. import _hip
     _hip.require_gpu()
     p = params if params is not None else FingerprintParams()
-    dev = frac.device
-    B, N = int(lattice.shape[0]), int(frac.shape[0])
-    for name, t, shape, dtype in [("frac", frac, (N, 3), torch.float32), ("lattice", lattice, (B, 3, 3), torch.float32),
-                                  ("offsets", offsets, (B + 1,), torch.int32), ("types", types, (N,), torch.int32)]:
-        if t is None or tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous() or dev.type != "cuda":
-            raise ValueError(f"fingerprint: {name} must be a contiguous {dtype} tensor of shape {shape} on the cuda device of frac")
+    dev, B, N = cb.check_batch("fingerprint", frac, lattice, offsets, types)
     i32 = dict(device=dev, dtype=torch.int32)
     out = {"fingerprint": torch.empty((B, ROW), device=dev, dtype=torch.float32), "species": torch.empty((B, MAX_SPECIES), **i32),
            "counts": torch.empty((B, MAX_SPECIES), **i32), "flags": torch.empty(B, **i32)}
@@ -178,23 +168,13 @@ def uniqueness_to_numpy(u):
     return {k: u[k].cpu().numpy() for k in UNIQUE_KEYS}
 
 
-def _upload(result, device):
-    import torch
-    num_atoms = np.asarray(result.num_atoms, dtype=np.int64)
-    off = np.concatenate([[0], np.cumsum(num_atoms)]).astype(np.int32)
-    dev = torch.device(device)
-    up = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=dev)
-    return (up(np.asarray(result.frac_x, dtype=np.float32).reshape(-1, 3)), up(np.asarray(result.lattice, dtype=np.float32).reshape(-1, 3, 3)),
-            up(off), up(np.rint(np.asarray(result.atomic_numbers).reshape(-1)).astype(np.int32)))
-
-
 def unique_sample_result(result, params=None, against=None, device="cuda"):
     """Uniqueness of a SampleResult (or a loaded crystals file) on the GPU, its float64 arrays cast to float32 and its atomic
     numbers taken as species ids: the UNIQUE_KEYS as numpy arrays.  With `against` (another SampleResult, e.g. a training set)
     the set is matched with that one instead: `unique` then says the crystal has no match there (it is novel)."""
     p = params if params is not None else FingerprintParams()
-    x = fingerprint(*_upload(result, device), p)
-    y = fingerprint(*_upload(against, device), p) if against is not None else None
+    x = fingerprint(*cb.upload(result, device), p)
+    y = fingerprint(*cb.upload(against, device), p) if against is not None else None
     return uniqueness_to_numpy(match(x, y, p.tolerance))
 
 
@@ -231,11 +211,6 @@ def _empty(B, dtype):
                            counts=np.zeros((B, MAX_SPECIES), np.int32), flags=np.zeros(B, np.int32))
 
 
-def _inputs(frac, lattice, counts, types, params):
-    frac, lattice, counts, types, _, first = sc._inputs(frac, lattice, counts, types, None)
-    return frac, lattice, counts, types, params if params is not None else FingerprintParams(), first
-
-
 def _components(ranks, i, j):
     A, Bq = np.minimum(ranks[i], ranks[j]), np.maximum(ranks[i], ranks[j])
     return Bq * (Bq + 1) // 2 + A, A == Bq
@@ -245,11 +220,11 @@ def fingerprint_reference_f32(frac, lattice, counts, types, params=None):
     """The kernel's rule in numpy float32: the screen restatement's float32 contacts, then every sum in the rule's naive order
     (a cell adds its contacts in enumeration order; the norm adds component by component, bin by bin).  numpy's exp stands where
     the kernel has one v_exp_f32.  Returns a namespace fingerprint [B, 2304] float32, species, counts [B,8], flags [B]."""
-    frac, lattice, counts, types, p, first = _inputs(frac, lattice, counts, types, params)
+    frac, lattice, counts, types, first = cb.inputs(frac, lattice, counts, types)
+    p = params if params is not None else FingerprintParams()
     out = _empty(len(counts), F32)
     r_cut = p.r_cut
     rc2 = F32(np.float64(r_cut) ** 2)
-    cell = SimpleNamespace(search_radius=r_cut, min_volume=0.0, max_shells=p.max_shells)
     sigma = np.float64(F32(p.sigma))
     inv2s2, gnorm = F32(1.0 / (2.0 * sigma * sigma)), F32(1.0 / (sigma * math.sqrt(2.0 * math.pi)))
     Rk = ((np.arange(BINS, dtype=F32) + F32(0.5)) * (F32(p.r_max) / F32(p.n_bins))).astype(F32)
@@ -259,20 +234,15 @@ def fingerprint_reference_f32(frac, lattice, counts, types, params=None):
             out.flags[b] = NONFINITE
             continue
         species, cnt, ranks = _formula(t)
-        vol, q, bad = sc._cell_f32(L, cell)
+        vol, q, bad = cb.cell_f32(L, r_cut, 0.0, p.max_shells)
         flags = (EMPTY if n == 0 else 0) | (MANY_SPECIES if len(species) > MAX_SPECIES else 0) | (CELL if bad or not vol > 0 else 0)
         if flags:
             out.flags[b] = flags
             continue
         nk = [max(1, int(np.ceil(qk))) for qk in q]
-        w = (f - np.floor(f)).astype(F32)
-        w[w >= F32(1)] = F32(0)
-        pos = ((w[:, 0:1] * L[0][None] + w[:, 1:2] * L[1][None]) + w[:, 2:3] * L[2][None]).astype(F32)
-        g, centre = sc._shift_table(nk)
-        gf = g.astype(F32)
-        s = ((gf[:, 0:1] * L[0][None] + gf[:, 1:2] * L[1][None]) + gf[:, 2:3] * L[2][None]).astype(F32)
+        pos, g, centre, s = cb.positions_and_shifts(f, L, nk, F32)
         S = np.zeros((COMPONENTS, BINS), F32)
-        for i, j, m, d2 in sc._contacts(pos, s, centre, F32):
+        for i, j, m, d2 in cb.contacts(pos, s, centre, F32):
             keep = d2 < rc2
             R = np.sqrt(d2[keep]).astype(F32)
             comp, same = _components(ranks, i[keep], j[keep])
@@ -302,7 +272,8 @@ def fingerprint_reference_f64(frac, lattice, counts, types, params=None, widen=1
     """The same rule in float64 from the same float32 inputs; the image range is n_k + `widen` per axis (one shell wider than
     the kernel's by default).  details=True adds `bound` [B] (screening.distance_bound of the crystal), `near_cut` [B] (contacts
     whose distance lies within that bound of r_cut: float32 may disagree on whether they count) and `n_contacts` [B]."""
-    frac, lattice, counts, types, p, first = _inputs(frac, lattice, counts, types, params)
+    frac, lattice, counts, types, first = cb.inputs(frac, lattice, counts, types)
+    p = params if params is not None else FingerprintParams()
     B = len(counts)
     out = _empty(B, np.float64)
     out.bound, out.near_cut, out.n_contacts = np.full(B, np.nan), np.zeros(B, np.int64), np.zeros(B, np.int64)
@@ -314,24 +285,17 @@ def fingerprint_reference_f64(frac, lattice, counts, types, params=None, widen=1
             out.flags[b] = NONFINITE
             continue
         species, cnt, ranks = _formula(t)
-        c = np.array([np.cross(L[1], L[2]), np.cross(L[2], L[0]), np.cross(L[0], L[1])])
-        vol = abs(float(np.dot(L[0], c[0])))
-        with np.errstate(all="ignore"):
-            q = r_cut * np.linalg.norm(c, axis=1) / vol if vol > 0 else np.full(3, np.inf)
+        vol, q = cb.cell_f64(L, r_cut)
         bad = not vol > 0 or not np.isfinite(vol) or not (q <= p.max_shells).all()
         flags = (EMPTY if n == 0 else 0) | (MANY_SPECIES if len(species) > MAX_SPECIES else 0) | (CELL if bad else 0)
         if flags:
             out.flags[b] = flags
             continue
         nk = np.maximum(1, np.ceil(q).astype(np.int64))
-        out.bound[b] = sc.distance_bound(L, nk)
-        w = f - np.floor(f)
-        w[w >= 1.0] = 0.0
-        pos = w @ L
-        g, centre = sc._shift_table(nk + int(widen))
-        s = g.astype(np.float64) @ L
+        out.bound[b] = distance_bound(L, nk)
+        pos, g, centre, s = cb.positions_and_shifts(f, L, nk + int(widen), np.float64)
         S = np.zeros((COMPONENTS, BINS))
-        for i, j, m, d2 in sc._contacts(pos, s, centre, np.float64):
+        for i, j, m, d2 in cb.contacts(pos, s, centre, np.float64):
             R = np.sqrt(d2)
             out.near_cut[b] += int((np.abs(R - r_cut) <= out.bound[b]).sum())
             keep = R < r_cut
