@@ -88,3 +88,80 @@ def test_default_args_match_reference_cli_defaults():
     a = default_args()
     assert (a.num_ori, a.hidden_dim, a.basis_dim, a.degree, a.layers, a.widening_factor) == (16, 128, 256, 3, 5, 4)
     assert (a.radius, a.max_neighbors, a.num_timesteps, a.layer_scale) == (5, 8, 1000, 1e-6)
+
+
+# ------------------------------------------------------------------------------------------- layer_scale absent; radius
+def _reloaded(m, tmp_path, name):
+    path = save_lightning_checkpoint(str(tmp_path / name), m)
+    m2 = PONITA_DIFFUSION.load_from_checkpoint(path, strict=True).cpu()
+    sd, sd2 = m.state_dict(), m2.state_dict()
+    assert list(sd2) == list(sd)  # the same keys (strict: none missing, none unexpected) ...
+    for k, v in sd.items():       # ... and the same bits
+        assert v.dtype == sd2[k].dtype and torch.equal(v, sd2[k]), k
+    assert torch.equal(m2.model.ori_grid, m.model.ori_grid)
+    return path, m2
+
+
+def test_round_trip_of_a_model_without_layer_scale(tmp_path):
+    """--layer_scale 0 (lightning_wrappers/diffusion.py:42-43): the constructor rewrites args.layer_scale to None in place, so
+    None is what the saved hyper-parameters hold; a reload -- from None, or from the 0.0 a checkpoint may hold if its
+    hyper-parameters were copied before the rewrite -- builds the same model: no such parameter, no such state_dict key."""
+    from arreau_amd.engine import pack_state
+    m = make_synthetic_model(S=12, seed=7, num_timesteps=50, layer_scale=0.0)
+    with_ls = make_synthetic_model(S=12, seed=7, num_timesteps=50)
+    assert len(list(m.parameters())) == len(list(with_ls.parameters())) - 5 == 75
+    assert set(with_ls.state_dict()) - set(m.state_dict()) == {f"model.interaction_layers.{l}.layer_scale" for l in range(5)}
+    assert m.hparams.args.layer_scale is None
+    path, m2 = _reloaded(m, tmp_path, "no_ls.ckpt")
+    assert load_lightning_checkpoint(path)["hyper_parameters"]["args"].layer_scale is None
+    ckpt = load_lightning_checkpoint(path)
+    ckpt["hyper_parameters"]["args"].layer_scale = 0.0
+    from arreau_amd.checkpoint import _reference_class_paths
+    with _reference_class_paths():
+        torch.save(ckpt, str(tmp_path / "no_ls_zero.ckpt"))
+    m3 = PONITA_DIFFUSION.load_from_checkpoint(str(tmp_path / "no_ls_zero.ckpt"), strict=True).cpu()
+    for mm in (m, m2, m3):
+        assert all(layer.layer_scale is None for layer in mm.model.interaction_layers)
+        assert not any("layer_scale" in n for n, _ in mm.named_parameters())
+        assert not any("layer_scale" in k for k in mm.state_dict())
+        cfg, host, csd, S, L = pack_state(mm)
+        assert cfg.has_layer_scale == 0 and "layer_scale" not in host and not csd.layer_scale
+        assert (cfg.radius, S, L) == (5.0, 12, 5)
+    assert list(m3.state_dict()) == list(m.state_dict())
+    assert all(torch.equal(v, m3.state_dict()[k]) for k, v in m.state_dict().items())
+    cfg, host, csd, _, _ = pack_state(with_ls)
+    assert cfg.has_layer_scale == 1 and tuple(host["layer_scale"].shape) == (5, 128) and csd.layer_scale
+
+
+def test_round_trip_of_a_model_with_another_radius(tmp_path):
+    """--radius 3.5 (train.py:187): the cut-off of the loss's neighbour list, the window's r_max and the engine's config."""
+    from arreau_amd.engine import pack_state
+    m = make_synthetic_model(S=12, seed=7, num_timesteps=50, radius=3.5)
+    path, m2 = _reloaded(m, tmp_path, "r35.ckpt")
+    assert load_lightning_checkpoint(path)["hyper_parameters"]["args"].radius == 3.5
+    for mm in (m, m2):
+        assert mm.diffusion_loss.cutoff == 3.5
+        assert float(mm.state_dict()["model.windowing_fn.r_max"]) == 3.5
+        cfg = pack_state(mm)[0]
+        assert cfg.radius == 3.5 and cfg.has_layer_scale == 1
+
+
+def test_optimizer_groups_of_a_model_without_layer_scale():
+    """configure_optimizers (lightning_wrappers/diffusion.py:152-218): every parameter in exactly one group; the non-decayed
+    group holds the biases, the LayerNorm weights and the Fourier projection, and nothing that ends in layer_scale; the
+    decayed group is the Linear weights -- what the same model with layer_scale has there."""
+    m = make_synthetic_model(S=12, seed=7, num_timesteps=50, layer_scale=0.0)
+    decayed, plain = m.configure_optimizers(max_epochs=10)["optimizer"].param_groups
+    assert decayed["weight_decay"] == m.weight_decay and plain["weight_decay"] == 0.0
+    names = {id(p): n for n, p in m.named_parameters()}
+    in_decayed, in_plain = [names[id(p)] for p in decayed["params"]], [names[id(p)] for p in plain["params"]]
+    assert sorted(in_decayed + in_plain) == sorted(names.values()) and len(names) == 75  # each exactly once
+    assert "t_emb.gaussian_fourier_proj_w" in in_plain
+    assert not any(n.endswith("layer_scale") for n in in_decayed + in_plain)
+    assert all(n.endswith("bias") or ".norm." in n or n.endswith("gaussian_fourier_proj_w") for n in in_plain), in_plain
+    assert all(n.endswith("weight") and ".norm." not in n for n in in_decayed), in_decayed
+    ls = make_synthetic_model(S=12, seed=7, num_timesteps=50)
+    d2, p2 = ls.configure_optimizers(max_epochs=10)["optimizer"].param_groups
+    names2 = {id(p): n for n, p in ls.named_parameters()}
+    assert [names2[id(p)] for p in d2["params"]] == in_decayed
+    assert [n for n in (names2[id(p)] for p in p2["params"]) if not n.endswith("layer_scale")] == in_plain

@@ -18,12 +18,13 @@ TOL = 1e-5
 GRAD_TOL = 1e-4
 
 
-@pytest.fixture(scope="module")
-def setup():
+def make_setup(**model_args):
+    """(model, float32 oracle, batch, lattice0, timestep, noise): a synthetic S = 12, T = 100 model (`model_args`: further
+    make_synthetic_model arguments) and a 17-atom training batch of five crystals with every random draw injected"""
     from arreau_amd.checkpoint import make_synthetic_model
     from oracle import geometry as OG
     dev = torch.device("cuda", 0)
-    m = make_synthetic_model(S=12, seed=1234, num_timesteps=100).to(dev)
+    m = make_synthetic_model(S=12, seed=1234, num_timesteps=100, **model_args).to(dev)
     om = oracle_from_module(m, torch.float32)
     rng = np.random.RandomState(8)
     num_atoms = [3, 5, 2, 1, 6]
@@ -38,6 +39,11 @@ def setup():
     noise = (torch.randn(N, 3, generator=g), torch.rand(N, S, generator=g), torch.randn(B, 3, generator=g))
     batch = SimpleNamespace(X0=frac0, A0=types0, L0=lattice0.reshape(-1, 3), num_atoms=torch.tensor(num_atoms))
     return m, om, batch, lattice0, timestep, noise
+
+
+@pytest.fixture(scope="module")
+def setup():
+    return make_setup()
 
 
 def test_forward_noising_matches_oracle(setup):
