@@ -30,7 +30,7 @@ EXPORTS = [
     "arreau_sample_loop_resampled", "arreau_resample_jump", "arreau_optimizer_step_ema",
     "arreau_sample_loop_tied", "arreau_reverse_step_tied", "arreau_resample_jump_tied",
     "arreau_sample_loop_sym", "arreau_reverse_step_sym", "arreau_crystal_screen",
-    "arreau_crystal_fingerprint", "arreau_fingerprint_match", "arreau_crystal_symmetry",
+    "arreau_crystal_fingerprint", "arreau_fingerprint_match", "arreau_crystal_symmetry", "arreau_crystal_reduce",
 ]
 
 STATUS_NONFINITE, STATUS_BAD_TIMESTEP, STATUS_BAD_TYPE, STATUS_BAD_TIE, STATUS_BAD_SYMMETRY = 1, 2, 4, 8, 16
@@ -118,6 +118,17 @@ class SymmetryResultC(Structure):
                                                 "ops_residual", "residual", "point_group", "flags")]
 
 
+class ReduceParamsC(Structure):
+    """arreau_reduce_params: the tolerance of the cell reduction."""
+    _fields_ = [("symprec", c_float)]
+
+
+class ReduceResultC(Structure):
+    """arreau_reduce_result: the seven per-crystal and three per-atom device arrays the cell reduction writes."""
+    _fields_ = [(name, c_void_p) for name in ("multiplicity", "n_translations", "lattice_out", "transform", "n_out", "flags",
+                                                "selling_steps", "frac_out", "types_out", "keep")]
+
+
 class Config(Structure):
     _fields_ = [
         ("num_atomic_states", c_int32), ("hidden_dim", c_int32), ("basis_dim", c_int32),
@@ -192,6 +203,7 @@ def _prototypes():
         "arreau_crystal_fingerprint": [vp] * 4 + [i32, i32, POINTER(FingerprintParamsC), POINTER(FingerprintResultC), vp],
         "arreau_fingerprint_match": [POINTER(FingerprintResultC), i32, POINTER(FingerprintResultC), i32, f32, POINTER(MatchResultC), vp],
         "arreau_crystal_symmetry": [vp] * 4 + [i32, i32, POINTER(SymmetryParamsC), POINTER(SymmetryResultC), vp],
+        "arreau_crystal_reduce": [vp] * 4 + [i32, i32, POINTER(ReduceParamsC), POINTER(ReduceResultC), vp],
         "arreau_train_forward": [vp] * 7 + [i32, i32] + [vp] * 4,
         "arreau_train_backward": [vp] * 4 + [POINTER(StateDict), vp],
         "arreau_train_conv_stats": [vp, vp, vp],

@@ -1,6 +1,7 @@
-// Device helpers shared by the per-crystal kernels (screen.hip, fingerprint.hip, symfind.hip; one workgroup of CRYSTAL_WAVES waves
+// Device helpers shared by the per-crystal kernels (screen.hip, fingerprint.hip, symfind.hip, reduce.hip; one workgroup of CRYSTAL_WAVES waves
 // per crystal): the launch shape, the prologue, the cell and its image range, the wrap of a fractional coordinate and the Cartesian
-// position, one periodic contact, the compaction of a workgroup's hits in thread order.  One float32 rounding per operation.
+// position, one periodic contact, the compaction of a workgroup's hits in thread order, the rarest species and the squared
+// length of a fractional difference.  One float32 rounding per operation.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -125,4 +126,50 @@ __device__ __forceinline__ int crystal_compact(bool hit, int lane, int wave, int
         total += k;
     }
     return before + __popcll(mask & ((1ull << lane) - 1ull));
+}
+
+// The species with the fewest atoms (the smallest id on ties) and p0, its first atom (n >= 1): what the candidate translations of
+// symfind.hip and reduce.hip start from.  Key (count, id with the sign bit flipped: unsigned order = signed order), minimum over
+// the wave by shuffles, over the waves through LDS.  Two barriers inside, every thread calls it; s_ka / s_kb are CRYSTAL_WAVES
+// words of LDS each, read by every thread until its return.
+template <class Species>
+__device__ __forceinline__ int crystal_rarest_species(int n, int lane, int wave, Species&& species, unsigned* s_ka, unsigned* s_kb, int& p0) {
+    const int tid = threadIdx.x;
+    unsigned ka = 0xffffffffu, kb = 0xffffffffu;
+    for (int a = tid; a < n; a += CRYSTAL_THREADS) {
+        const int ta = species(a);
+        unsigned cnt = 0;
+        for (int j = 0; j < n; ++j) cnt += species(j) == ta ? 1u : 0u;
+        const unsigned tb = (unsigned)ta ^ 0x80000000u;
+        if (cnt < ka || (cnt == ka && tb < kb)) { ka = cnt; kb = tb; }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const unsigned oa = __shfl_xor(ka, off), ob = __shfl_xor(kb, off);
+        if (oa < ka || (oa == ka && ob < kb)) { ka = oa; kb = ob; }
+    }
+    if (lane == 0) { s_ka[wave] = ka; s_kb[wave] = kb; }
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < CRYSTAL_WAVES; ++w)
+        if (s_ka[w] < ka || (s_ka[w] == ka && s_kb[w] < kb)) { ka = s_ka[w]; kb = s_kb[w]; }
+    const int rare = (int)(kb ^ 0x80000000u);
+    __syncthreads();  // (s_ka is written again below)
+    unsigned p0u = 0xffffffffu;
+    for (int a = tid; a < n; a += CRYSTAL_THREADS)
+        if (species(a) == rare) { p0u = (unsigned)a; break; }  // (ascending a: the thread's first is its smallest)
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) p0u = min(p0u, (unsigned)__shfl_xor(p0u, off));
+    if (lane == 0) s_ka[wave] = p0u;
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < CRYSTAL_WAVES; ++w) p0u = min(p0u, s_ka[w]);
+    p0 = (int)p0u;  // n >= 1, so the species exists
+    return rare;
+}
+
+// |c|^2 of c_d = (e_0 L_0d + e_1 L_1d) + e_2 L_2d: the Cartesian image of a fractional difference (the symmetry search's rule 4)
+__device__ __forceinline__ float crystal_frac_d2(float e0, float e1, float e2, const float* Lm) {
+    const float cx = rows_rn(Lm, 0, e0, e1, e2), cy = rows_rn(Lm, 1, e0, e1, e2), cz = rows_rn(Lm, 2, e0, e1, e2);
+    return dot3_rn(cx, cy, cz, cx, cy, cz);
 }

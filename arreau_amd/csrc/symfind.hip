@@ -169,38 +169,9 @@ __global__ __launch_bounds__(CRYSTAL_THREADS) void crystal_symmetry_kernel(
     auto wpos = [&](int atom, int d) -> float { return staged ? sw[3 * atom + d] : crystal_wrap(frac[3 * ((size_t)first + atom) + d]); };
     auto species = [&](int atom) -> int { return staged ? sty[atom] : types[(size_t)first + atom]; };
 
-    // ---- rule 3: the rarest species (fewest atoms, then the smallest id) and its first atom p0.  Key (count, id with the sign
-    // bit flipped: unsigned order = signed order), minimum over the wave by shuffles, over the waves through LDS.
-    unsigned ka = 0xffffffffu, kb = 0xffffffffu;
-    for (int a = tid; a < n; a += CRYSTAL_THREADS) {
-        const int ta = species(a);
-        unsigned cnt = 0;
-        for (int j = 0; j < n; ++j) cnt += species(j) == ta ? 1u : 0u;
-        const unsigned tb = (unsigned)ta ^ 0x80000000u;
-        if (cnt < ka || (cnt == ka && tb < kb)) { ka = cnt; kb = tb; }
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const unsigned oa = __shfl_xor(ka, off), ob = __shfl_xor(kb, off);
-        if (oa < ka || (oa == ka && ob < kb)) { ka = oa; kb = ob; }
-    }
-    if (lane == 0) { s_ka[wave] = ka; s_kb[wave] = kb; }
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < CRYSTAL_WAVES; ++w)
-        if (s_ka[w] < ka || (s_ka[w] == ka && s_kb[w] < kb)) { ka = s_ka[w]; kb = s_kb[w]; }
-    const int rare = (int)(kb ^ 0x80000000u);
-    __syncthreads();  // (s_ka is written again below)
-    unsigned p0u = 0xffffffffu;
-    for (int a = tid; a < n; a += CRYSTAL_THREADS)
-        if (species(a) == rare) { p0u = (unsigned)a; break; }  // (ascending a: the thread's first is its smallest)
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) p0u = min(p0u, (unsigned)__shfl_xor(p0u, off));
-    if (lane == 0) s_ka[wave] = p0u;
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < CRYSTAL_WAVES; ++w) p0u = min(p0u, s_ka[w]);
-    const int p0 = (int)p0u;  // n >= 1, so the species exists
+    // ---- rule 3: the rarest species (fewest atoms, then the smallest id) and its first atom p0
+    int p0;
+    const int rare = crystal_rarest_species(n, lane, wave, species, s_ka, s_kb, p0);
     const float wp0[3] = {wpos(p0, 0), wpos(p0, 1), wpos(p0, 2)};
 
     // ---- rules 3-5 (phase 2): every (W, q), W in code order, q ascending

@@ -1,4 +1,4 @@
-"""What the per-crystal analysis modules share (screening.py, uniqueness.py, symmetry_search.py; their kernels share
+"""What the per-crystal analysis modules share (screening.py, uniqueness.py, symmetry_search.py, cell_reduction.py; their kernels share
 arreau_amd/csrc/crystal_dev.h in the same way): the check and the upload of a device batch, `resolve`, and the numpy pieces of the
 restatements.  Needs numpy alone at import; torch is imported where a device is used."""
 import numpy as np
@@ -30,6 +30,15 @@ def upload(result, device):
     up = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=dev)
     return (up(np.asarray(result.frac_x, dtype=np.float32).reshape(-1, 3)), up(np.asarray(result.lattice, dtype=np.float32).reshape(-1, 3, 3)),
             up(off), up(np.rint(np.asarray(result.atomic_numbers).reshape(-1)).astype(np.int32)))
+
+
+def compact_ragged(offsets, n_out, *arrays):
+    """Per-atom outputs laid out at the input's offsets, crystal b using its first n_out[b] slots, as a dense ragged batch:
+    (offsets_out [B+1] int64, [array rows of the used slots, in order])."""
+    offsets, n_out = np.asarray(offsets, dtype=np.int64).reshape(-1), np.asarray(n_out, dtype=np.int64).reshape(-1)
+    assert offsets.size == n_out.size + 1 and (n_out >= 0).all() and (n_out <= np.diff(offsets)).all()
+    rows = np.concatenate([np.arange(a, a + k) for a, k in zip(offsets[:-1], n_out)] + [np.empty(0, dtype=np.int64)]).astype(np.int64)
+    return np.concatenate([[0], np.cumsum(n_out)]), [np.asarray(a)[rows] for a in arrays]
 
 
 def resolve(value, cls, name):

@@ -16,6 +16,7 @@ from . import resampling as rs
 from . import respacing
 from . import screening
 from . import uniqueness as uniqueness_mod
+from . import cell_reduction
 from . import symmetry_search
 from .d3pm import D3PM
 from . import lattice_systems
@@ -53,6 +54,10 @@ class SampleResult:
     # n_lattice, n_ops, n_translations, ops_rotation, ops_translation, ops_residual, residual, point_group, flags, symprec and the
     # float32 lattice the search saw; None when it was not asked for
     symmetry: Optional[dict] = None
+    # extension: the cell reduction of the final state (sample(reduce_cell=...); diffusion/cell_reduction.py) -- numpy arrays
+    # multiplicity, n_translations, lattice, transform, num_atoms, flags, selling_steps and symprec, one row per crystal, and the
+    # reduced crystals' frac_x, atomic_numbers and keep as a dense ragged batch; None when it was not asked for
+    reduced: Optional[dict] = None
 
 
 class _PinnedRing:
@@ -277,7 +282,7 @@ class DiffusionLoss(nn.Module):
                fixed_cell: bool = False, condition=None, num_steps: Optional[int] = None,
                timesteps: Optional[Sequence[int]] = None, corrector_steps: int = 0,
                corrector_snr: float = pc.DEFAULT_SNR, resample_passes: int = 1, jump_length: int = 10,
-               lattice_system=None, symmetry=None, screen=None, unique=None, find_symmetry=None) -> SampleResult:
+               lattice_system=None, symmetry=None, screen=None, unique=None, find_symmetry=None, reduce_cell=None) -> SampleResult:
         """diffusion_loss.py:276-377.  The initial state is drawn on the host exactly like the reference (numpy
         uniforms for the angles, then randn lengths, randn fractional coordinates from torch's global CPU generator).
         Per-step noise:
@@ -353,7 +358,14 @@ class DiffusionLoss(nn.Module):
         defaults -- one more launch on the final device state (arreau_crystal_symmetry; rules in include/arreau_hip.h) finds the
         operations x' = W x + t every crystal has in its cell and the point group of their rotations; the class indices are the
         species ids.  SampleResult.symmetry then holds the arrays (symmetry_search.contains / stats_of read them).  No space-group
-        number, no standardised cell.  None: no launch is added, symmetry is None and the results are what they were, bit for bit."""
+        number, no standardised cell.  None: no launch is added, symmetry is None and the results are what they were, bit for bit.
+        `reduce_cell` (extension, every noise mode and option): a cell_reduction.CellReductionParams, or True for its defaults --
+        one more launch on the final device state (arreau_crystal_reduce; rules in include/arreau_hip.h) finds every crystal's pure
+        translations, its primitive cell, a Delaunay-reduced basis of it and the atoms in that basis.  SampleResult.reduced then
+        holds the arrays (cell_reduction.REDUCED_KEYS); frac_x, lattice and every other field stay in the cell as sampled, and
+        screen, unique and find_symmetry still read that cell.  No Niggli form, no standardised setting.  None: no launch is added,
+        reduced is None and the results are what they were, bit for bit."""
+        reduce_cell = cell_reduction.resolve(reduce_cell)
         screen = screening.resolve(screen)
         unique = uniqueness_mod.resolve(unique)
         find_symmetry = symmetry_search.resolve(find_symmetry)
@@ -604,7 +616,11 @@ class DiffusionLoss(nn.Module):
         found = None
         if find_symmetry is not None:
             found = symmetry_search.result_to_numpy(eng.find_symmetry(frac_d, lattice_d, off_d, types_d, find_symmetry))
+        reduced = None
+        if reduce_cell is not None:
+            reduced = cell_reduction.result_to_numpy(eng.reduce_cells(frac_d, lattice_d, off_d, types_d, reduce_cell))
+            reduced = cell_reduction.sample_arrays(reduced, atomic_number_indexes_to_atomic_numbers(z_table, reduced["types"]))
         atomic_numbers = atomic_number_indexes_to_atomic_numbers(z_table, types_d.cpu().numpy())
         return SampleResult(num_atoms=num_atoms.numpy(), frac_x=frac_d.cpu().numpy().astype(np.float64),
                             atomic_numbers=atomic_numbers, lattice=lattice_d.cpu().numpy().astype(np.float64), info=info,
-                            metrics=metrics, uniqueness=uniqueness, symmetry=found)
+                            metrics=metrics, uniqueness=uniqueness, symmetry=found, reduced=reduced)

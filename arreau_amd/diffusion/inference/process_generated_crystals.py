@@ -16,7 +16,10 @@ six more in the same way: unique_duplicate_of, unique_distance, unique_nearest, 
 unique_unique; without them none is written.  A result that carries the symmetry search's arrays (SampleResult.symmetry,
 diffusion/symmetry_search.py) gets sym_n_lattice, sym_n_ops, sym_n_translations, sym_ops_rotation [B,max_ops], sym_ops_translation
 [B,max_ops,3], sym_ops_residual [B,max_ops], sym_residual, sym_point_group, sym_flags and sym_symprec; a reader gets them back with
-`lattice` filled in from the file's cells."""
+`lattice` filled in from the file's cells.  A result that carries the cell reduction's arrays (SampleResult.reduced,
+diffusion/cell_reduction.py) gets reduced_multiplicity, reduced_n_translations, reduced_lattice [B,3,3], reduced_transform [B,3,3],
+reduced_num_atoms, reduced_flags, reduced_selling_steps, reduced_symprec, and the reduced crystals' atoms reduced_frac_x [sum
+reduced_num_atoms, 3], reduced_atomic_numbers and reduced_keep."""
 import os
 
 import numpy as np
@@ -31,6 +34,9 @@ UNIQUE_PREFIX = "unique_"
 SYM_KEYS = ("n_lattice", "n_ops", "n_translations", "ops_rotation", "ops_translation", "ops_residual", "residual", "point_group",
             "flags", "symprec")
 SYM_PREFIX = "sym_"
+REDUCED_KEYS = ("multiplicity", "n_translations", "lattice", "transform", "num_atoms", "flags", "selling_steps", "symprec", "frac_x",
+                "atomic_numbers", "keep")  # cell_reduction.REDUCED_KEYS
+REDUCED_PREFIX = "reduced_"
 _DTYPES = dict(frac_x=np.float64, atomic_numbers=np.float64, lattice=np.float64, idx_start=np.int64,
                num_atoms=np.int64)
 
@@ -74,6 +80,16 @@ def _fields(crystals: SampleResult):
             if v.shape[:1] != (B,) or v.ndim != {"ops_rotation": 2, "ops_translation": 3, "ops_residual": 2}.get(k, 1):
                 raise ValueError(f"SampleResult.symmetry[{k!r}] does not hold one row per crystal")
             out[SYM_PREFIX + k] = v
+    reduced = getattr(crystals, "reduced", None)
+    if reduced is not None:
+        n_red = int(np.asarray(reduced["num_atoms"]).sum()) if "num_atoms" in reduced else -1
+        for k in REDUCED_KEYS:
+            if k not in reduced:
+                raise ValueError(f"SampleResult.reduced[{k!r}] is missing")
+            v = np.asarray(reduced[k])
+            if v.shape[:1] != ((n_red,) if k in ("frac_x", "atomic_numbers", "keep") else (B,)):
+                raise ValueError(f"SampleResult.reduced[{k!r}] does not hold one row per crystal (or per reduced atom)")
+            out[REDUCED_PREFIX + k] = v
     return out
 
 
@@ -113,15 +129,17 @@ def load_sample_results_from_hdf5(filename: str) -> SampleResult:
             metrics = _metrics_from(lambda k: k in fh["crystals"], lambda k: fh["crystals"][k][:])
             uniqueness = _metrics_from(lambda k: k in fh["crystals"], lambda k: fh["crystals"][k][:], UNIQUE_PREFIX, UNIQUE_KEYS)
             symmetry = _metrics_from(lambda k: k in fh["crystals"], lambda k: fh["crystals"][k][:], SYM_PREFIX, SYM_KEYS)
+            reduced = _metrics_from(lambda k: k in fh["crystals"], lambda k: fh["crystals"][k][:], REDUCED_PREFIX, REDUCED_KEYS)
     else:
         with np.load(filename) as z:
             data = {k: z[k] for k in KEYS}
             metrics = _metrics_from(lambda k: k in z.files, lambda k: z[k])
             uniqueness = _metrics_from(lambda k: k in z.files, lambda k: z[k], UNIQUE_PREFIX, UNIQUE_KEYS)
             symmetry = _metrics_from(lambda k: k in z.files, lambda k: z[k], SYM_PREFIX, SYM_KEYS)
+            reduced = _metrics_from(lambda k: k in z.files, lambda k: z[k], REDUCED_PREFIX, REDUCED_KEYS)
     if symmetry is not None:  # (the search saw the float32 cells)
         symmetry["lattice"] = np.asarray(data["lattice"], dtype=np.float32).reshape(-1, 3, 3)
-    return SampleResult(**data, metrics=metrics, uniqueness=uniqueness, symmetry=symmetry)
+    return SampleResult(**data, metrics=metrics, uniqueness=uniqueness, symmetry=symmetry, reduced=reduced)
 
 
 def get_crystal_indexes(sample_result: SampleResult, sample_idx: int):

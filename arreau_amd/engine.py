@@ -27,6 +27,12 @@ def screen(frac, lattice, offsets, types=None, criteria=None):
     return screening.screen(frac, lattice, offsets, types, criteria)
 
 
+def reduce_cells(frac, lattice, offsets, types, params=None):
+    """The cell reduction without an engine (arreau_crystal_reduce needs no model): diffusion.cell_reduction.reduce_cells."""
+    from .diffusion import cell_reduction
+    return cell_reduction.reduce_cells(frac, lattice, offsets, types, params)
+
+
 def find_symmetry(frac, lattice, offsets, types, params=None):
     """The symmetry search without an engine (arreau_crystal_symmetry needs no model): diffusion.symmetry_search.find_symmetry."""
     from .diffusion import symmetry_search
@@ -647,6 +653,15 @@ class HipEngine:
         if frac.device != self.device:
             raise ValueError(f"screen: the state must be on {self.device}")
         return screening.screen(frac, lattice, offsets, types, criteria)
+
+    def reduce_cells(self, frac, lattice, offsets, types, params=None):
+        """The cell reduction of a batch on this engine's device (arreau_crystal_reduce; diffusion/cell_reduction.py:
+        `reduce_cells`, which needs no engine): frac [N,3] f32, lattice [B,3,3] f32, offsets [B+1] i32, types [N] i32, params a
+        CellReductionParams or None (the defaults).  Returns its dict of device tensors; does not synchronise."""
+        from .diffusion import cell_reduction
+        if frac.device != self.device:
+            raise ValueError(f"reduce_cells: the state must be on {self.device}")
+        return cell_reduction.reduce_cells(frac, lattice, offsets, types, params)
 
     def find_symmetry(self, frac, lattice, offsets, types, params=None):
         """The symmetry search of a batch on this engine's device (arreau_crystal_symmetry; diffusion/symmetry_search.py:

@@ -59,7 +59,7 @@ def _screen_stats(parts):
     """The per-rank screen and uniqueness statistics the parts carry (SampleResult.info["screen_stats"] / ["unique_stats"]), each
     in one list; None when no part has any."""
     out = {}
-    for key in ("screen_stats", "unique_stats", "symmetry_stats"):
+    for key in ("screen_stats", "unique_stats", "symmetry_stats", "reduce_stats"):
         stats = [st for p in parts if p is not None and p.info for st in p.info.get(key, [])]
         if stats:
             out[key] = stats
@@ -81,10 +81,14 @@ def concat_results(parts) -> SampleResult:
     symmetry = None
     if all(p.symmetry is not None for p in parts):  # (one --symprec and max_ops for the run: the rows have one width)
         symmetry = {k: np.concatenate([np.asarray(p.symmetry[k]) for p in parts]) for k in parts[0].symmetry}
+    reduced = None
+    if all(p.reduced is not None for p in parts):
+        from .diffusion import cell_reduction
+        reduced = cell_reduction.concat_reduced([p.reduced for p in parts])
     return SampleResult(
         frac_x=np.concatenate([p.frac_x for p in parts]), atomic_numbers=np.concatenate([p.atomic_numbers for p in parts]),
         lattice=np.concatenate([p.lattice for p in parts]), num_atoms=num_atoms,
-        idx_start=np.cumsum(num_atoms) - num_atoms, info=info, metrics=metrics, symmetry=symmetry)
+        idx_start=np.cumsum(num_atoms) - num_atoms, info=info, metrics=metrics, symmetry=symmetry, reduced=reduced)
 
 
 def select_crystals(res: SampleResult, keep) -> SampleResult:
@@ -95,9 +99,13 @@ def select_crystals(res: SampleResult, keep) -> SampleResult:
     kept = num_atoms[keep]
     metrics = None if res.metrics is None else {k: np.asarray(v)[keep] for k, v in res.metrics.items()}
     symmetry = None if res.symmetry is None else {k: np.asarray(v)[keep] for k, v in res.symmetry.items()}
+    reduced = None
+    if res.reduced is not None:
+        from .diffusion import cell_reduction
+        reduced = cell_reduction.select_reduced(res.reduced, np.arange(len(res.num_atoms))[keep])
     return SampleResult(frac_x=np.asarray(res.frac_x)[atoms], atomic_numbers=np.asarray(res.atomic_numbers)[atoms],
                         lattice=np.asarray(res.lattice)[keep], num_atoms=kept, idx_start=np.cumsum(kept) - kept, metrics=metrics,
-                        symmetry=symmetry)
+                        symmetry=symmetry, reduced=reduced)
 
 
 FIX_KINDS = ("positions", "species", "lattice")
@@ -146,6 +154,9 @@ def _gather_results(local: SampleResult, rank: int, world_size: int, gather: Opt
     if local.symmetry is not None and not (local.info or {}).get("symmetry_stats"):  # a searched run: this rank's histogram
         from .diffusion import symmetry_search
         local.info = dict(local.info or {}, symmetry_stats=[symmetry_search.stats_of(local.symmetry, rank)])
+    if local.reduced is not None and not (local.info or {}).get("reduce_stats"):  # a reduced run: this rank's histogram
+        from .diffusion import cell_reduction
+        local.info = dict(local.info or {}, reduce_stats=[cell_reduction.stats_of(local.reduced, rank)])
     if unique is not None:  # duplicates within this rank's crystals, on its own device
         from .diffusion import uniqueness
         local.info = dict(local.info or {}, unique_stats=[uniqueness.stats_of(uniqueness.unique_sample_result(local, unique), rank)])
@@ -303,13 +314,32 @@ def build_parser() -> argparse.ArgumentParser:
                     help="find every generated crystal's symmetry operations and point group on the device: histogram per rank and "
                          "in total + sym_* arrays in the output file; with --symops, how many crystals contain that group")
     add_symmetry_search_arguments(ap)
+    ap.add_argument("--reduce_cell", action="store_true",
+                    help="reduce every generated crystal to its primitive, Delaunay-reduced cell on the device (tolerance --symprec): "
+                         "histogram of multiplicities and flags per rank and in total + reduced_* arrays in the output file")
     return ap
 
 
 def add_symmetry_search_arguments(ap):
-    """The symmetry-search flag shared with `python -m arreau_amd.screen`."""
+    """The tolerance flag of the symmetry search and the cell reduction, shared with `python -m arreau_amd.screen`."""
     ap.add_argument("--symprec", type=float, default=0.1,
-                    help="find_symmetry: tolerance in A on cell lengths and atom distances (0.1: a starting value, not a claim)")
+                    help="find_symmetry / reduce_cell: tolerance in A on cell lengths and atom distances (0.1: a starting value, not a claim)")
+
+
+def cell_reduction_params(args, error):
+    """The CellReductionParams of the tolerance flag; `error(message)` reports a bad value."""
+    from .diffusion.cell_reduction import CellReductionParams
+    try:
+        return CellReductionParams(symprec=args.symprec)
+    except ValueError as e:
+        error(f"cell reduction: {e}")
+
+
+def reduce_lines(res, parts=None):
+    """The lines `--reduce_cell` prints for a result that holds the reduction's arrays: the histogram of multiplicities and flags
+    per rank (`parts`: the statistics the ranks carried; None: the result as one set) and in total."""
+    from .diffusion import cell_reduction
+    return cell_reduction.summary_lines(parts if parts else [cell_reduction.stats_of(res.reduced)])
 
 
 def symmetry_search_params(args, error):
@@ -428,6 +458,7 @@ def main():
     criteria = check_screen_arguments(args, ap.error)
     unique = fingerprint_params(args, ap.error) if args.unique else None
     find_sym = symmetry_search_params(args, ap.error) if args.find_symmetry else None
+    reduce_cell = cell_reduction_params(args, ap.error) if args.reduce_cell else None
     condition = load_template(args.template, parse_fix(args.fix)).tile(args.samples_per_template) if args.template else None
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -464,7 +495,7 @@ def main():
                                 corrector_steps=args.corrector_steps, corrector_snr=args.corrector_snr,
                                 resample_passes=args.resample_passes, jump_length=args.jump_length,
                                 lattice_system=args.lattice_system, symmetry=spec, screen=criteria,
-                                find_symmetry=find_sym)
+                                find_symmetry=find_sym, reduce_cell=reduce_cell)
         import fcntl
         with open(lock_path, "a") as lock:
             fcntl.flock(lock, fcntl.LOCK_EX)
@@ -473,7 +504,7 @@ def main():
                                 corrector_steps=args.corrector_steps, corrector_snr=args.corrector_snr,
                                 resample_passes=args.resample_passes, jump_length=args.jump_length,
                                 lattice_system=args.lattice_system, symmetry=spec, screen=criteria,
-                                find_symmetry=find_sym)
+                                find_symmetry=find_sym, reduce_cell=reduce_cell)
                 torch.cuda.synchronize()
                 return out
             finally:
@@ -496,6 +527,9 @@ def main():
                 print(line)
         if find_sym is not None:
             for line in symmetry_lines(res, (res.info or {}).get("symmetry_stats"), spec):
+                print(line)
+        if reduce_cell is not None:
+            for line in reduce_lines(res, (res.info or {}).get("reduce_stats")):
                 print(line)
         print("wrote", save_sample_results(res, args.out))
     if world > 1:

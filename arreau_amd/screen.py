@@ -2,6 +2,7 @@
 
     python -m arreau_amd.screen out/crystals.npz [--min_distance 0.5] [--min_volume 0.1] [--search_radius 3.0] [--out screened.npz]
     python -m arreau_amd.screen out/crystals.npz --find_symmetry [--symprec 0.1]
+    python -m arreau_amd.screen out/crystals.npz --reduce_cell [--symprec 0.1] [--out reduced.npz]
     python -m arreau_amd.screen out/crystals.npz --unique [--against train.npz] [--fp_r_max 6] [--fp_sigma 0.1] [--fp_tolerance 0.01]
 
 Prints the summary `python -m arreau_amd.generate --screen` prints (accepted / attempted and the count per flag) and, with
@@ -11,6 +12,9 @@ check looks for the mask state's atomic number (2001).  The rules are in include
 and with `--against FILE` the novelty -- the share of crystals with no match in that other set.
 `--find_symmetry [--symprec 0.1]` adds the symmetry search (diffusion/symmetry_search.py): the count per crystal system, point
 group and flag, and the sym_* arrays with `--out`.  No space-group number, no standardised cell.
+`--reduce_cell [--symprec 0.1]` adds the cell reduction (diffusion/cell_reduction.py): the count per multiplicity and flag; `--out`
+then writes a crystals file of the REDUCED crystals (primitive, Delaunay-reduced cells; the screen_* / unique_* / sym_* arrays of
+this run describe the cells as given and are not written to it), on which the other options can be run in turn.
 """
 import argparse
 
@@ -27,13 +31,16 @@ def build_parser() -> argparse.ArgumentParser:
     add_fingerprint_arguments(ap)
     ap.add_argument("--find_symmetry", action="store_true", help="also find every crystal's symmetry operations and point group")
     add_symmetry_search_arguments(ap)
+    ap.add_argument("--reduce_cell", action="store_true",
+                    help="also reduce every crystal to its primitive, Delaunay-reduced cell; --out then writes the reduced crystals")
     return ap
 
 
 def main(argv=None):
     from .diffusion import screening
     from .diffusion.inference.process_generated_crystals import load_sample_results_from_hdf5, save_sample_results_to_hdf5
-    from .generate import fingerprint_params, screen_criteria, symmetry_lines, symmetry_search_params, unique_lines
+    from .generate import (cell_reduction_params, fingerprint_params, reduce_lines, screen_criteria, symmetry_lines,
+                           symmetry_search_params, unique_lines)
     ap = build_parser()
     args = ap.parse_args(argv)
     criteria = screen_criteria(args, ap.error)
@@ -41,6 +48,7 @@ def main(argv=None):
         ap.error("--against needs --unique")
     unique = fingerprint_params(args, ap.error) if args.unique else None
     find_sym = symmetry_search_params(args, ap.error) if args.find_symmetry else None
+    reduce_cell = cell_reduction_params(args, ap.error) if args.reduce_cell else None
 
     def load(name):
         try:
@@ -62,6 +70,16 @@ def main(argv=None):
         res.symmetry = symmetry_search.symmetry_sample_result(res, find_sym, args.device)
         for line in symmetry_lines(res):
             print(line)
+    if reduce_cell is not None:
+        from .diffusion import cell_reduction
+        from .diffusion.diffusion_loss import SampleResult
+        res.reduced = cell_reduction.sample_arrays(cell_reduction.reduce_sample_result(res, reduce_cell, args.device))
+        for line in reduce_lines(res):
+            print(line)
+        if args.out:
+            reduced = SampleResult(**cell_reduction.reduced_crystals(res.reduced), reduced=res.reduced)
+            print("wrote", save_sample_results_to_hdf5(reduced, args.out))
+        return res
     if args.out:
         print("wrote", save_sample_results_to_hdf5(res, args.out))
     return res

@@ -431,6 +431,76 @@ typedef struct arreau_symmetry_result { /* DEVICE arrays, one row per crystal */
 int arreau_crystal_symmetry(const float* d_frac, const int32_t* d_types, const float* d_lattice, const int32_t* d_crystal_offsets,
                             int32_t B, int32_t N, const arreau_symmetry_params* params, arreau_symmetry_result* out, void* stream);
 
+/* ---- cell reduction: the primitive, Delaunay-reduced cell of a crystal and its atoms in it ----------------------------------
+ * The fourth instrument beside the screen, the fingerprint and the symmetry search: the pure translations a crystal has in the
+ * cell it is given, the primitive cell they imply, a Delaunay-reduced (Selling) basis of that cell made of its shortest vectors,
+ * and one atom per translation class expressed in it.  One launch, one workgroup of four waves per crystal, no atomics, no
+ * arreau_model; deterministic.  NOT computed: a Niggli form, a conventional or standardised setting, a space-group number.
+ * Conventions as in the symmetry search: cell rows a_0, a_1, a_2, r_d = sum_k x_k L_kd, positions wrapped w = f - floor(f) (a
+ * result >= 1 becomes 0).  dist(delta) of a fractional difference: each component minus its nearest integer (rintf) gives e; the
+ * minimum over the 27 images s in {-1, 0, 1}^3, s_0 slowest, of |c|, c_d = ((e_0 + s_0) L_0d + (e_1 + s_1) L_1d) + (e_2 + s_2) L_2d.
+ *   1. flags.  NONFINITE, CELL, EMPTY as in arreau_crystal_symmetry's rule 1.  A crystal flagged NONFINITE, CELL, EMPTY or
+ *      AMBIGUOUS is copied through unchanged, bit for bit (positions not wrapped): lattice_out = lattice, transform = identity,
+ *      multiplicity 1, n_out = n, keep = 0..n-1, selling_steps 0; n_translations is 0 for the first three and the number of
+ *      accepted translations for AMBIGUOUS.
+ *   2. pure translations.  The species with the fewest atoms (the smallest id on ties), its first atom p0; for every atom q of
+ *      that species, ascending, t = wrap(w_q - w_p0).  t is a translation when max over the atoms i of min over the atoms j of
+ *      the species of i of dist((w_i + t) - w_j) is <= symprec.  n_translations counts them (q = p0 gives the identity); m =
+ *      n_translations.  AMBIGUOUS when m > ARREAU_RED_MAX_TRANSLATIONS, when m does not divide n, or when for some accepted t_a,
+ *      t_b no accepted t_c has dist((t_a + t_b) - t_c) <= symprec (the set is not closed).
+ *   3. primitive basis.  Every vector is held as integer numerators over m in the input basis; its Cartesian form is c_k =
+ *      num_k / m (one division), v_d = (c_0 L_0d + c_1 L_1d) + c_2 L_2d.  The set: m e_0, m e_1, m e_2 (a, b, c), then per
+ *      non-trivial translation, in q order, num = rint(m (t - rint(t))) + m s with the image s in {-1, 0, 1}^3 of the shortest
+ *      |v|^2 (the first in lexicographic order on ties).  The set is sorted by |v|^2, ties to the lower index; the first triple
+ *      i < j < k of the sorted list, in lexicographic order, with | |det| - V / m | <= V / (4 m) (det = v_i . (v_j x v_k), V the
+ *      cell volume) is the primitive basis; all three vectors are negated when det < 0.  No such triple: AMBIGUOUS.
+ *   4. Delaunay reduction.  Integer coefficients in the primitive basis: v_0, v_1, v_2 the basis, v_3 = -(v_0 + v_1 + v_2); each
+ *      vector's Cartesian form is formed from its numerators as in 3 at every step (nothing accumulates).  tol = 1e-5 x the
+ *      largest |v|^2 of the primitive basis.  While some v_i . v_j > tol: the first such pair in the order 01, 02, 03, 12, 13, 23
+ *      takes the Selling step v_k += v_i, v_l += v_i (k, l the other two), v_i = -v_i.  At most ARREAU_RED_MAX_STEPS steps;
+ *      selling_steps counts them, NOT_CONVERGED when the limit is reached.  Of the seven vectors v_0, v_1, v_2, v_3, v_0 + v_1,
+ *      v_1 + v_2, v_2 + v_0, sorted by |v|^2 (ties to the lower index): the shortest, the next not parallel to it, the next
+ *      independent of both (decided on the integers); all three negated when their integer determinant is negative.  Their
+ *      numerators R give transform = R / m (rows: the reduced basis in the input basis, det = 1 / m) and lattice_out row r =
+ *      (T_r0 L_0d + T_r1 L_1d) + T_r2 L_2d.  AMBIGUOUS when det R != m^2 or adj(R) / m is not an integer matrix.
+ *   5. atoms.  Atom a is kept when for no non-trivial translation t_k the atom of its species nearest to w_a + t_k (dist; ties to
+ *      the lower index) has an index below a: the lowest index of every translation class.  AMBIGUOUS when their number is not
+ *      n / m.  The kept atoms, ascending, fill the crystal's first n_out = n / m output slots (the outputs use the input's
+ *      offsets): keep = the atom's index local to the crystal, types_out its species, frac_out = wrap(w Q), Q = adj(R) / m the
+ *      integer inverse of transform, (w_0 Q_0c + w_1 Q_1c) + w_2 Q_2c.  The slots n_out..n-1 hold keep -1, species -1, zeros.
+ *   6. arithmetic: one float32 operation per step, rounded to nearest, in the order written, never contracted; square roots
+ *      correctly rounded.  The float64 restatement (arreau_amd/diffusion/cell_reduction.py) reports the margin of every decision;
+ *      on guarded inputs the discrete outputs agree and the reals are held to the bounds derived there.
+ * Cost: n_rarest x n^2 x 27 distance evaluations for the translations, (m - 1) x n^2 x 27 for the atoms.  Offsets outside [0, N] or
+ * descending are clamped as in the screen.  Does not synchronise.
+ * Argument errors (ARREAU_EINVAL, nothing launched): NULL params / result / arrays, negative sizes, symprec not finite or not
+ * positive. */
+#define ARREAU_RED_NONFINITE 1
+#define ARREAU_RED_CELL 2
+#define ARREAU_RED_EMPTY 4
+#define ARREAU_RED_AMBIGUOUS 8
+#define ARREAU_RED_NOT_CONVERGED 16
+#define ARREAU_RED_MAX_TRANSLATIONS 64
+#define ARREAU_RED_MAX_STEPS 64
+typedef struct arreau_reduce_params {
+    float symprec; /* A; default 0.1, the symmetry search's */
+} arreau_reduce_params;
+typedef struct arreau_reduce_result { /* DEVICE arrays: one row per crystal, then one row per input atom */
+    int32_t* multiplicity;   /* [B] m: input cell volume / reduced cell volume */
+    int32_t* n_translations; /* [B] accepted pure translations, the identity included */
+    float* lattice_out;      /* [B,3,3] rows of the reduced cell */
+    float* transform;        /* [B,3,3] rows: the reduced basis in the input basis, multiples of 1 / m */
+    int32_t* n_out;          /* [B] n / m */
+    int32_t* flags;          /* [B] ARREAU_RED_* */
+    int32_t* selling_steps;  /* [B] */
+    float* frac_out;         /* [N,3] crystal b's atoms at offsets[b] .. offsets[b] + n_out[b] */
+    int32_t* types_out;      /* [N] */
+    int32_t* keep;           /* [N] the input atom (local to the crystal) of every output atom, -1 beyond n_out */
+} arreau_reduce_result;
+/* d_frac[N,3], d_types[N] species ids (required), d_lattice[B,3,3] rows a, b, c.  `params` and `out` are HOST pointers. */
+int arreau_crystal_reduce(const float* d_frac, const int32_t* d_types, const float* d_lattice, const int32_t* d_crystal_offsets,
+                          int32_t B, int32_t N, const arreau_reduce_params* params, arreau_reduce_result* out, void* stream);
+
 /* ---- the score network ---------------------------------------------------------------------- */
 
 /* One evaluation of DiffusionLoss.predict_scores (diffusion/diffusion_loss.py:112-197):
