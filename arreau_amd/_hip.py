@@ -31,6 +31,7 @@ EXPORTS = [
     "arreau_sample_loop_tied", "arreau_reverse_step_tied", "arreau_resample_jump_tied",
     "arreau_sample_loop_sym", "arreau_reverse_step_sym", "arreau_crystal_screen",
     "arreau_crystal_fingerprint", "arreau_fingerprint_match", "arreau_crystal_symmetry", "arreau_crystal_reduce",
+    "arreau_crystal_symmetrize",
 ]
 
 STATUS_NONFINITE, STATUS_BAD_TIMESTEP, STATUS_BAD_TYPE, STATUS_BAD_TIE, STATUS_BAD_SYMMETRY = 1, 2, 4, 8, 16
@@ -129,6 +130,12 @@ class ReduceResultC(Structure):
                                                 "selling_steps", "frac_out", "types_out", "keep")]
 
 
+class SymmetrizeResultC(Structure):
+    """arreau_symmetrize_result: the device arrays the symmetrization writes (per crystal, per atom, per operation)."""
+    _fields_ = [(name, c_void_p) for name in ("frac_out", "lattice", "lengths", "angles", "orbit", "orbit_size", "site_order", "n_orbits",
+                                                "max_displacement", "rms_displacement", "ops_translation", "ops_shift", "partner", "flags")]
+
+
 class Config(Structure):
     _fields_ = [
         ("num_atomic_states", c_int32), ("hidden_dim", c_int32), ("basis_dim", c_int32),
@@ -204,6 +211,7 @@ def _prototypes():
         "arreau_fingerprint_match": [POINTER(FingerprintResultC), i32, POINTER(FingerprintResultC), i32, f32, POINTER(MatchResultC), vp],
         "arreau_crystal_symmetry": [vp] * 4 + [i32, i32, POINTER(SymmetryParamsC), POINTER(SymmetryResultC), vp],
         "arreau_crystal_reduce": [vp] * 4 + [i32, i32, POINTER(ReduceParamsC), POINTER(ReduceResultC), vp],
+        "arreau_crystal_symmetrize": [vp] * 4 + [i32, i32, POINTER(SymmetryResultC), i32, POINTER(SymmetrizeResultC), vp],
         "arreau_train_forward": [vp] * 7 + [i32, i32] + [vp] * 4,
         "arreau_train_backward": [vp] * 4 + [POINTER(StateDict), vp],
         "arreau_train_conv_stats": [vp, vp, vp],

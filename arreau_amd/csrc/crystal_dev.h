@@ -1,13 +1,14 @@
-// Device helpers shared by the per-crystal kernels (screen.hip, fingerprint.hip, symfind.hip, reduce.hip; one workgroup of CRYSTAL_WAVES waves
+// Device helpers shared by the per-crystal kernels (screen.hip, fingerprint.hip, symfind.hip, reduce.hip, symmetrize.hip; one workgroup of CRYSTAL_WAVES waves
 // per crystal): the launch shape, the prologue, the cell and its image range, the wrap of a fractional coordinate and the Cartesian
-// position, one periodic contact, the compaction of a workgroup's hits in thread order, the rarest species and the squared
-// length of a fractional difference.  One float32 rounding per operation.
+// position, one periodic contact, the compaction of a workgroup's hits in thread order, the rarest species, the squared
+// length of a fractional difference and the matrix of a rotation code.  One float32 rounding per operation.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #define CRYSTAL_WAVES 4
 #define CRYSTAL_THREADS (64 * CRYSTAL_WAVES)
 #define CRYSTAL_LDS_ATOMS 256  // crystals of up to this many atoms keep their per-atom data in LDS
+#define SYM_CODES 19683        // 3^9 rotation codes (the symmetry search's; symmetrize.hip reads them)
 
 // every fp32 operation below is spelled out (__fmul_rn / __fadd_rn / __fsub_rn / __fdiv_rn): one rounding each, no contraction
 // to an FMA, so that the float32 host restatement (arreau_amd/diffusion/crystal_batch.py, screening.py) matches bit for bit
@@ -172,4 +173,19 @@ __device__ __forceinline__ int crystal_rarest_species(int n, int lane, int wave,
 __device__ __forceinline__ float crystal_frac_d2(float e0, float e1, float e2, const float* Lm) {
     const float cx = rows_rn(Lm, 0, e0, e1, e2), cy = rows_rn(Lm, 1, e0, e1, e2), cz = rows_rn(Lm, 2, e0, e1, e2);
     return dot3_rn(cx, cy, cz, cx, cy, cz);
+}
+
+// the matrix of a rotation code, W[3 r + c] = digit (3 r + c) - 1, and its determinant
+__device__ __forceinline__ int decode_rotation(int code, int* W) {
+#pragma unroll
+    for (int p = 0; p < 9; ++p) {
+        W[p] = code % 3 - 1;
+        code /= 3;
+    }
+    return W[0] * (W[4] * W[8] - W[5] * W[7]) - W[1] * (W[3] * W[8] - W[5] * W[6]) + W[2] * (W[3] * W[7] - W[4] * W[6]);
+}
+
+// (W v)_r = (W_r0 v_0 + W_r1 v_1) + W_r2 v_2: the products by -1, 0, 1 are exact, two rounded sums
+__device__ __forceinline__ float rot_row(const float* W, int r, float v0, float v1, float v2) {
+    return __fadd_rn(__fadd_rn(__fmul_rn(W[3 * r], v0), __fmul_rn(W[3 * r + 1], v1)), __fmul_rn(W[3 * r + 2], v2));
 }

@@ -13,7 +13,6 @@
 #include <cmath>
 
 #define SYM_ROUND CRYSTAL_THREADS  // candidate translations per round: one compaction pass of the workgroup
-#define SYM_CODES 19683        // 3^9
 #define SYM_IDENTITY 16484
 #define SYM_MAX_LATTICE 48
 
@@ -24,21 +23,6 @@ struct sym_out {
     float *ops_translation, *ops_residual, *residual;
     int32_t *point_group, *flags;
 };
-
-// the matrix of a rotation code, W[3 r + c] = digit (3 r + c) - 1, and its determinant
-__device__ __forceinline__ int decode_rotation(int code, int* W) {
-#pragma unroll
-    for (int p = 0; p < 9; ++p) {
-        W[p] = code % 3 - 1;
-        code /= 3;
-    }
-    return W[0] * (W[4] * W[8] - W[5] * W[7]) - W[1] * (W[3] * W[8] - W[5] * W[6]) + W[2] * (W[3] * W[7] - W[4] * W[6]);
-}
-
-// (W v)_r = (W_r0 v_0 + W_r1 v_1) + W_r2 v_2: the products by -1, 0, 1 are exact, two rounded sums
-__device__ __forceinline__ float rot_row(const float* W, int r, float v0, float v1, float v2) {
-    return __fadd_rn(__fadd_rn(__fmul_rn(W[3 * r], v0), __fmul_rn(W[3 * r + 1], v1)), __fmul_rn(W[3 * r + 2], v2));
-}
 
 // rule 2: is the code a lattice isometry within symprec?  G = (G_01, G_02, G_12), len = |a_i|
 __device__ bool lattice_candidate(int code, const float* Lm, const float* G, const float* len, float symprec) {

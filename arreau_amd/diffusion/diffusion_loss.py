@@ -18,6 +18,7 @@ from . import screening
 from . import uniqueness as uniqueness_mod
 from . import cell_reduction
 from . import symmetry_search
+from . import symmetrize as symmetrize_mod
 from .d3pm import D3PM
 from . import lattice_systems
 from . import symmetry as sym_mod
@@ -58,6 +59,10 @@ class SampleResult:
     # multiplicity, n_translations, lattice, transform, num_atoms, flags, selling_steps and symprec, one row per crystal, and the
     # reduced crystals' frac_x, atomic_numbers and keep as a dense ragged batch; None when it was not asked for
     reduced: Optional[dict] = None
+    # extension: the symmetrization of the final state (sample(symmetrize=...); diffusion/symmetrize.py) -- numpy arrays frac_x,
+    # orbit, orbit_size and site_order, one row per atom of the crystals as sampled, and lattice, lengths, angles, n_orbits,
+    # max_displacement, rms_displacement, ops_translation and flags, one row per crystal; None when it was not asked for
+    symmetrized: Optional[dict] = None
 
 
 class _PinnedRing:
@@ -282,7 +287,8 @@ class DiffusionLoss(nn.Module):
                fixed_cell: bool = False, condition=None, num_steps: Optional[int] = None,
                timesteps: Optional[Sequence[int]] = None, corrector_steps: int = 0,
                corrector_snr: float = pc.DEFAULT_SNR, resample_passes: int = 1, jump_length: int = 10,
-               lattice_system=None, symmetry=None, screen=None, unique=None, find_symmetry=None, reduce_cell=None) -> SampleResult:
+               lattice_system=None, symmetry=None, screen=None, unique=None, find_symmetry=None, reduce_cell=None,
+               symmetrize=None) -> SampleResult:
         """diffusion_loss.py:276-377.  The initial state is drawn on the host exactly like the reference (numpy
         uniforms for the angles, then randn lengths, randn fractional coordinates from torch's global CPU generator).
         Per-step noise:
@@ -364,8 +370,18 @@ class DiffusionLoss(nn.Module):
         translations, its primitive cell, a Delaunay-reduced basis of it and the atoms in that basis.  SampleResult.reduced then
         holds the arrays (cell_reduction.REDUCED_KEYS); frac_x, lattice and every other field stay in the cell as sampled, and
         screen, unique and find_symmetry still read that cell.  No Niggli form, no standardised setting.  None: no launch is added,
-        reduced is None and the results are what they were, bit for bit."""
+        reduced is None and the results are what they were, bit for bit.
+        `symmetrize` (extension, every noise mode and option): a symmetrize.SymmetrizeParams (the symmetry search's symprec and
+        max_ops), or True for its defaults -- the search's launch (shared with `find_symmetry` when both are given: their
+        parameters must then agree) and one more on the final device state (arreau_crystal_symmetrize; rules in
+        include/arreau_hip.h) move every crystal's atoms onto sites its found operations map onto each other exactly, average
+        its metric over their rotations and report its orbits.  SampleResult.symmetrized then holds the arrays
+        (symmetrize.SYMMETRIZED_KEYS); frac_x, lattice and every other field stay as sampled, and screen, unique, find_symmetry and
+        reduce_cell still read that state.  No space-group number, no origin search, no standard setting.  None: no launch is
+        added, symmetrized is None and the results are what they were, bit for bit."""
         reduce_cell = cell_reduction.resolve(reduce_cell)
+        symmetrize = symmetrize_mod.resolve(symmetrize)
+        symmetrize_mod.check_shared_search(symmetrize, symmetry_search.resolve(find_symmetry))
         screen = screening.resolve(screen)
         unique = uniqueness_mod.resolve(unique)
         find_symmetry = symmetry_search.resolve(find_symmetry)
@@ -613,9 +629,14 @@ class DiffusionLoss(nn.Module):
         uniqueness = None
         if unique is not None:
             uniqueness = uniqueness_mod.uniqueness_to_numpy(uniqueness_mod.unique_batch(frac_d, lattice_d, off_d, types_d, unique))
-        found = None
+        found = found_d = None
         if find_symmetry is not None:
-            found = symmetry_search.result_to_numpy(eng.find_symmetry(frac_d, lattice_d, off_d, types_d, find_symmetry))
+            found_d = eng.find_symmetry(frac_d, lattice_d, off_d, types_d, find_symmetry)
+            found = symmetry_search.result_to_numpy(found_d)
+        symmetrized = None
+        if symmetrize is not None:  # (found_d: the search's launch is shared)
+            symmetrized = symmetrize_mod.sample_arrays(symmetrize_mod.result_to_numpy(
+                eng.symmetrize(frac_d, lattice_d, off_d, types_d, symmetrize, found_d)))
         reduced = None
         if reduce_cell is not None:
             reduced = cell_reduction.result_to_numpy(eng.reduce_cells(frac_d, lattice_d, off_d, types_d, reduce_cell))
@@ -623,4 +644,5 @@ class DiffusionLoss(nn.Module):
         atomic_numbers = atomic_number_indexes_to_atomic_numbers(z_table, types_d.cpu().numpy())
         return SampleResult(num_atoms=num_atoms.numpy(), frac_x=frac_d.cpu().numpy().astype(np.float64),
                             atomic_numbers=atomic_numbers, lattice=lattice_d.cpu().numpy().astype(np.float64), info=info,
-                            metrics=metrics, uniqueness=uniqueness, symmetry=found, reduced=reduced)
+                            metrics=metrics, uniqueness=uniqueness, symmetry=found, reduced=reduced,
+                            symmetrized=symmetrized)

@@ -19,7 +19,11 @@ diffusion/symmetry_search.py) gets sym_n_lattice, sym_n_ops, sym_n_translations,
 `lattice` filled in from the file's cells.  A result that carries the cell reduction's arrays (SampleResult.reduced,
 diffusion/cell_reduction.py) gets reduced_multiplicity, reduced_n_translations, reduced_lattice [B,3,3], reduced_transform [B,3,3],
 reduced_num_atoms, reduced_flags, reduced_selling_steps, reduced_symprec, and the reduced crystals' atoms reduced_frac_x [sum
-reduced_num_atoms, 3], reduced_atomic_numbers and reduced_keep."""
+reduced_num_atoms, 3], reduced_atomic_numbers and reduced_keep.  A result that carries the symmetrization's arrays
+(SampleResult.symmetrized, diffusion/symmetrize.py) gets symmetrized_frac_x [sum n, 3], symmetrized_orbit, symmetrized_orbit_size and
+symmetrized_site_order [sum n], and per crystal symmetrized_lattice [B,3,3], symmetrized_lengths, symmetrized_angles [B,3],
+symmetrized_n_orbits, symmetrized_max_displacement, symmetrized_rms_displacement, symmetrized_ops_translation [B,max_ops,3] and
+symmetrized_flags."""
 import os
 
 import numpy as np
@@ -37,6 +41,9 @@ SYM_PREFIX = "sym_"
 REDUCED_KEYS = ("multiplicity", "n_translations", "lattice", "transform", "num_atoms", "flags", "selling_steps", "symprec", "frac_x",
                 "atomic_numbers", "keep")  # cell_reduction.REDUCED_KEYS
 REDUCED_PREFIX = "reduced_"
+SYMMETRIZED_KEYS = ("frac_x", "lattice", "lengths", "angles", "orbit", "orbit_size", "site_order", "n_orbits", "max_displacement",
+                    "rms_displacement", "ops_translation", "flags")  # symmetrize.SYMMETRIZED_KEYS
+SYMMETRIZED_PREFIX = "symmetrized_"
 _DTYPES = dict(frac_x=np.float64, atomic_numbers=np.float64, lattice=np.float64, idx_start=np.int64,
                num_atoms=np.int64)
 
@@ -90,6 +97,15 @@ def _fields(crystals: SampleResult):
             if v.shape[:1] != ((n_red,) if k in ("frac_x", "atomic_numbers", "keep") else (B,)):
                 raise ValueError(f"SampleResult.reduced[{k!r}] does not hold one row per crystal (or per reduced atom)")
             out[REDUCED_PREFIX + k] = v
+    symmetrized = getattr(crystals, "symmetrized", None)
+    if symmetrized is not None:
+        for k in SYMMETRIZED_KEYS:
+            if k not in symmetrized:
+                raise ValueError(f"SampleResult.symmetrized[{k!r}] is missing")
+            v = np.asarray(symmetrized[k])
+            if v.shape[:1] != ((n_tot,) if k in ("frac_x", "orbit", "orbit_size", "site_order") else (B,)):
+                raise ValueError(f"SampleResult.symmetrized[{k!r}] does not hold one row per crystal (or per atom)")
+            out[SYMMETRIZED_PREFIX + k] = v
     return out
 
 
@@ -130,6 +146,7 @@ def load_sample_results_from_hdf5(filename: str) -> SampleResult:
             uniqueness = _metrics_from(lambda k: k in fh["crystals"], lambda k: fh["crystals"][k][:], UNIQUE_PREFIX, UNIQUE_KEYS)
             symmetry = _metrics_from(lambda k: k in fh["crystals"], lambda k: fh["crystals"][k][:], SYM_PREFIX, SYM_KEYS)
             reduced = _metrics_from(lambda k: k in fh["crystals"], lambda k: fh["crystals"][k][:], REDUCED_PREFIX, REDUCED_KEYS)
+            symmetrized = _metrics_from(lambda k: k in fh["crystals"], lambda k: fh["crystals"][k][:], SYMMETRIZED_PREFIX, SYMMETRIZED_KEYS)
     else:
         with np.load(filename) as z:
             data = {k: z[k] for k in KEYS}
@@ -137,9 +154,11 @@ def load_sample_results_from_hdf5(filename: str) -> SampleResult:
             uniqueness = _metrics_from(lambda k: k in z.files, lambda k: z[k], UNIQUE_PREFIX, UNIQUE_KEYS)
             symmetry = _metrics_from(lambda k: k in z.files, lambda k: z[k], SYM_PREFIX, SYM_KEYS)
             reduced = _metrics_from(lambda k: k in z.files, lambda k: z[k], REDUCED_PREFIX, REDUCED_KEYS)
+            symmetrized = _metrics_from(lambda k: k in z.files, lambda k: z[k], SYMMETRIZED_PREFIX, SYMMETRIZED_KEYS)
     if symmetry is not None:  # (the search saw the float32 cells)
         symmetry["lattice"] = np.asarray(data["lattice"], dtype=np.float32).reshape(-1, 3, 3)
-    return SampleResult(**data, metrics=metrics, uniqueness=uniqueness, symmetry=symmetry, reduced=reduced)
+    return SampleResult(**data, metrics=metrics, uniqueness=uniqueness, symmetry=symmetry, reduced=reduced,
+                        symmetrized=symmetrized)
 
 
 def get_crystal_indexes(sample_result: SampleResult, sample_idx: int):

@@ -33,6 +33,12 @@ def reduce_cells(frac, lattice, offsets, types, params=None):
     return cell_reduction.reduce_cells(frac, lattice, offsets, types, params)
 
 
+def symmetrize(frac, lattice, offsets, types, params=None, found=None):
+    """The symmetrization without an engine (arreau_crystal_symmetrize needs no model): diffusion.symmetrize.symmetrize."""
+    from .diffusion import symmetrize as symmetrize_mod
+    return symmetrize_mod.symmetrize(frac, lattice, offsets, types, params, found)
+
+
 def find_symmetry(frac, lattice, offsets, types, params=None):
     """The symmetry search without an engine (arreau_crystal_symmetry needs no model): diffusion.symmetry_search.find_symmetry."""
     from .diffusion import symmetry_search
@@ -662,6 +668,16 @@ class HipEngine:
         if frac.device != self.device:
             raise ValueError(f"reduce_cells: the state must be on {self.device}")
         return cell_reduction.reduce_cells(frac, lattice, offsets, types, params)
+
+    def symmetrize(self, frac, lattice, offsets, types, params=None, found=None):
+        """The symmetrization of a batch on this engine's device (arreau_crystal_symmetrize; diffusion/symmetrize.py: `symmetrize`,
+        which needs no engine): the batch as for `find_symmetry`, params a SymmetrizeParams or None (the defaults), found the dict
+        of `find_symmetry` on the same tensors or None (the search is then launched here).  Returns its dict of device tensors;
+        does not synchronise."""
+        from .diffusion import symmetrize as symmetrize_mod
+        if frac.device != self.device:
+            raise ValueError(f"symmetrize: the state must be on {self.device}")
+        return symmetrize_mod.symmetrize(frac, lattice, offsets, types, params, found)
 
     def find_symmetry(self, frac, lattice, offsets, types, params=None):
         """The symmetry search of a batch on this engine's device (arreau_crystal_symmetry; diffusion/symmetry_search.py:

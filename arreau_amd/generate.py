@@ -59,7 +59,7 @@ def _screen_stats(parts):
     """The per-rank screen and uniqueness statistics the parts carry (SampleResult.info["screen_stats"] / ["unique_stats"]), each
     in one list; None when no part has any."""
     out = {}
-    for key in ("screen_stats", "unique_stats", "symmetry_stats", "reduce_stats"):
+    for key in ("screen_stats", "unique_stats", "symmetry_stats", "reduce_stats", "symmetrize_stats"):
         stats = [st for p in parts if p is not None and p.info for st in p.info.get(key, [])]
         if stats:
             out[key] = stats
@@ -85,10 +85,15 @@ def concat_results(parts) -> SampleResult:
     if all(p.reduced is not None for p in parts):
         from .diffusion import cell_reduction
         reduced = cell_reduction.concat_reduced([p.reduced for p in parts])
+    symmetrized = None
+    if all(p.symmetrized is not None for p in parts):  # (one max_ops for the run: the rows have one width)
+        from .diffusion import symmetrize
+        symmetrized = symmetrize.concat_symmetrized([p.symmetrized for p in parts])
     return SampleResult(
         frac_x=np.concatenate([p.frac_x for p in parts]), atomic_numbers=np.concatenate([p.atomic_numbers for p in parts]),
         lattice=np.concatenate([p.lattice for p in parts]), num_atoms=num_atoms,
-        idx_start=np.cumsum(num_atoms) - num_atoms, info=info, metrics=metrics, symmetry=symmetry, reduced=reduced)
+        idx_start=np.cumsum(num_atoms) - num_atoms, info=info, metrics=metrics, symmetry=symmetry, reduced=reduced,
+        symmetrized=symmetrized)
 
 
 def select_crystals(res: SampleResult, keep) -> SampleResult:
@@ -103,9 +108,13 @@ def select_crystals(res: SampleResult, keep) -> SampleResult:
     if res.reduced is not None:
         from .diffusion import cell_reduction
         reduced = cell_reduction.select_reduced(res.reduced, np.arange(len(res.num_atoms))[keep])
+    symmetrized = None
+    if res.symmetrized is not None:
+        from .diffusion import symmetrize
+        symmetrized = symmetrize.select_symmetrized(res.symmetrized, keep, atoms)
     return SampleResult(frac_x=np.asarray(res.frac_x)[atoms], atomic_numbers=np.asarray(res.atomic_numbers)[atoms],
                         lattice=np.asarray(res.lattice)[keep], num_atoms=kept, idx_start=np.cumsum(kept) - kept, metrics=metrics,
-                        symmetry=symmetry, reduced=reduced)
+                        symmetry=symmetry, reduced=reduced, symmetrized=symmetrized)
 
 
 FIX_KINDS = ("positions", "species", "lattice")
@@ -157,6 +166,9 @@ def _gather_results(local: SampleResult, rank: int, world_size: int, gather: Opt
     if local.reduced is not None and not (local.info or {}).get("reduce_stats"):  # a reduced run: this rank's histogram
         from .diffusion import cell_reduction
         local.info = dict(local.info or {}, reduce_stats=[cell_reduction.stats_of(local.reduced, rank)])
+    if local.symmetrized is not None and not (local.info or {}).get("symmetrize_stats"):  # a symmetrized run: this rank's histogram
+        from .diffusion import symmetrize
+        local.info = dict(local.info or {}, symmetrize_stats=[symmetrize.stats_of(local.symmetrized, rank)])
     if unique is not None:  # duplicates within this rank's crystals, on its own device
         from .diffusion import uniqueness
         local.info = dict(local.info or {}, unique_stats=[uniqueness.stats_of(uniqueness.unique_sample_result(local, unique), rank)])
@@ -317,13 +329,17 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--reduce_cell", action="store_true",
                     help="reduce every generated crystal to its primitive, Delaunay-reduced cell on the device (tolerance --symprec): "
                          "histogram of multiplicities and flags per rank and in total + reduced_* arrays in the output file")
+    ap.add_argument("--symmetrize", action="store_true",
+                    help="symmetrize every generated crystal on the device with the operations found within --symprec: exact "
+                         "orbits, averaged positions and cell; histogram of orbit counts and flags and the largest displacement "
+                         "per rank and in total + symmetrized_* arrays in the output file")
     return ap
 
 
 def add_symmetry_search_arguments(ap):
-    """The tolerance flag of the symmetry search and the cell reduction, shared with `python -m arreau_amd.screen`."""
+    """The tolerance flag of the symmetry search, the cell reduction and the symmetrization, shared with `python -m arreau_amd.screen`."""
     ap.add_argument("--symprec", type=float, default=0.1,
-                    help="find_symmetry / reduce_cell: tolerance in A on cell lengths and atom distances (0.1: a starting value, not a claim)")
+                    help="find_symmetry / reduce_cell / symmetrize: tolerance in A on cell lengths and atom distances (0.1: a starting value, not a claim)")
 
 
 def cell_reduction_params(args, error):
@@ -333,6 +349,23 @@ def cell_reduction_params(args, error):
         return CellReductionParams(symprec=args.symprec)
     except ValueError as e:
         error(f"cell reduction: {e}")
+
+
+def symmetrize_params(args, error):
+    """The SymmetrizeParams of the tolerance flag (max_ops the default); `error(message)` reports a bad value."""
+    from .diffusion.symmetrize import SymmetrizeParams
+    try:
+        return SymmetrizeParams(symprec=args.symprec)
+    except ValueError as e:
+        error(f"symmetrize: {e}")
+
+
+def symmetrize_lines(res, parts=None):
+    """The lines `--symmetrize` prints for a result that holds the symmetrization's arrays: the histogram of orbit counts and
+    flags and the largest displacement per rank (`parts`: the statistics the ranks carried; None: the result as one set) and in
+    total."""
+    from .diffusion import symmetrize
+    return symmetrize.summary_lines(parts if parts else [symmetrize.stats_of(res.symmetrized)])
 
 
 def reduce_lines(res, parts=None):
@@ -459,6 +492,7 @@ def main():
     unique = fingerprint_params(args, ap.error) if args.unique else None
     find_sym = symmetry_search_params(args, ap.error) if args.find_symmetry else None
     reduce_cell = cell_reduction_params(args, ap.error) if args.reduce_cell else None
+    symmetrize = symmetrize_params(args, ap.error) if args.symmetrize else None
     condition = load_template(args.template, parse_fix(args.fix)).tile(args.samples_per_template) if args.template else None
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -495,7 +529,7 @@ def main():
                                 corrector_steps=args.corrector_steps, corrector_snr=args.corrector_snr,
                                 resample_passes=args.resample_passes, jump_length=args.jump_length,
                                 lattice_system=args.lattice_system, symmetry=spec, screen=criteria,
-                                find_symmetry=find_sym, reduce_cell=reduce_cell)
+                                find_symmetry=find_sym, reduce_cell=reduce_cell, symmetrize=symmetrize)
         import fcntl
         with open(lock_path, "a") as lock:
             fcntl.flock(lock, fcntl.LOCK_EX)
@@ -504,7 +538,7 @@ def main():
                                 corrector_steps=args.corrector_steps, corrector_snr=args.corrector_snr,
                                 resample_passes=args.resample_passes, jump_length=args.jump_length,
                                 lattice_system=args.lattice_system, symmetry=spec, screen=criteria,
-                                find_symmetry=find_sym, reduce_cell=reduce_cell)
+                                find_symmetry=find_sym, reduce_cell=reduce_cell, symmetrize=symmetrize)
                 torch.cuda.synchronize()
                 return out
             finally:
@@ -530,6 +564,9 @@ def main():
                 print(line)
         if reduce_cell is not None:
             for line in reduce_lines(res, (res.info or {}).get("reduce_stats")):
+                print(line)
+        if symmetrize is not None:
+            for line in symmetrize_lines(res, (res.info or {}).get("symmetrize_stats")):
                 print(line)
         print("wrote", save_sample_results(res, args.out))
     if world > 1:

@@ -328,7 +328,8 @@ class PONITA_DIFFUSION(nn.Module):
                seed: Optional[int] = None, fixed_cell: bool = False, vis_name: Optional[str] = None,
                condition=None, num_steps: Optional[int] = None, timesteps=None, corrector_steps: int = 0,
                corrector_snr: float = 0.16, resample_passes: int = 1, jump_length: int = 10,
-               lattice_system=None, symmetry=None, screen=None, unique=None, find_symmetry=None, reduce_cell=None) -> SampleResult:
+               lattice_system=None, symmetry=None, screen=None, unique=None, find_symmetry=None, reduce_cell=None,
+               symmetrize=None) -> SampleResult:
         """lightning_wrappers/diffusion.py:220-253.  `num_atoms_per_sample` may also be a sequence with one atom count
         per crystal of the batch (extension; the reference supports a single int).  Frames of a visualization_setting
         other than NONE go to `<DIFFUSION_DIR>/step_<timestep>.cif` like the reference's PNGs (`vis_name` overrides the
@@ -373,4 +374,4 @@ class PONITA_DIFFUSION(nn.Module):
             noise=noise, max_steps=max_steps, use_graph=use_graph, seed=seed, fixed_cell=fixed_cell, condition=condition,
             num_steps=num_steps, timesteps=timesteps, corrector_steps=corrector_steps, corrector_snr=corrector_snr,
             resample_passes=resample_passes, jump_length=jump_length, lattice_system=lattice_system, symmetry=symmetry,
-            screen=screen, unique=unique, find_symmetry=find_symmetry, reduce_cell=reduce_cell)
+            screen=screen, unique=unique, find_symmetry=find_symmetry, reduce_cell=reduce_cell, symmetrize=symmetrize)

@@ -3,6 +3,7 @@
     python -m arreau_amd.screen out/crystals.npz [--min_distance 0.5] [--min_volume 0.1] [--search_radius 3.0] [--out screened.npz]
     python -m arreau_amd.screen out/crystals.npz --find_symmetry [--symprec 0.1]
     python -m arreau_amd.screen out/crystals.npz --reduce_cell [--symprec 0.1] [--out reduced.npz]
+    python -m arreau_amd.screen out/crystals.npz --symmetrize [--symprec 0.1] [--out symmetrized.npz]
     python -m arreau_amd.screen out/crystals.npz --unique [--against train.npz] [--fp_r_max 6] [--fp_sigma 0.1] [--fp_tolerance 0.01]
 
 Prints the summary `python -m arreau_amd.generate --screen` prints (accepted / attempted and the count per flag) and, with
@@ -15,6 +16,9 @@ group and flag, and the sym_* arrays with `--out`.  No space-group number, no st
 `--reduce_cell [--symprec 0.1]` adds the cell reduction (diffusion/cell_reduction.py): the count per multiplicity and flag; `--out`
 then writes a crystals file of the REDUCED crystals (primitive, Delaunay-reduced cells; the screen_* / unique_* / sym_* arrays of
 this run describe the cells as given and are not written to it), on which the other options can be run in turn.
+`--symmetrize [--symprec 0.1]` adds the symmetrization (diffusion/symmetrize.py): the count per number of orbits and flag and the
+largest displacement; `--out` then writes a crystals file of the SYMMETRIZED crystals (averaged positions, rebuilt cells, and the
+symmetrized_* arrays) in the same way.  With `--reduce_cell` too the reduction runs first and its crystals are symmetrized.
 """
 import argparse
 
@@ -33,14 +37,17 @@ def build_parser() -> argparse.ArgumentParser:
     add_symmetry_search_arguments(ap)
     ap.add_argument("--reduce_cell", action="store_true",
                     help="also reduce every crystal to its primitive, Delaunay-reduced cell; --out then writes the reduced crystals")
+    ap.add_argument("--symmetrize", action="store_true",
+                    help="also symmetrize every crystal with the operations found within --symprec; --out then writes the "
+                         "symmetrized crystals (after --reduce_cell: of the reduced crystals)")
     return ap
 
 
 def main(argv=None):
     from .diffusion import screening
     from .diffusion.inference.process_generated_crystals import load_sample_results_from_hdf5, save_sample_results_to_hdf5
-    from .generate import (cell_reduction_params, fingerprint_params, reduce_lines, screen_criteria, symmetry_lines,
-                           symmetry_search_params, unique_lines)
+    from .generate import (cell_reduction_params, fingerprint_params, reduce_lines, screen_criteria, symmetrize_lines,
+                           symmetrize_params, symmetry_lines, symmetry_search_params, unique_lines)
     ap = build_parser()
     args = ap.parse_args(argv)
     criteria = screen_criteria(args, ap.error)
@@ -49,6 +56,7 @@ def main(argv=None):
     unique = fingerprint_params(args, ap.error) if args.unique else None
     find_sym = symmetry_search_params(args, ap.error) if args.find_symmetry else None
     reduce_cell = cell_reduction_params(args, ap.error) if args.reduce_cell else None
+    symmetrize = symmetrize_params(args, ap.error) if args.symmetrize else None
 
     def load(name):
         try:
@@ -76,13 +84,30 @@ def main(argv=None):
         res.reduced = cell_reduction.sample_arrays(cell_reduction.reduce_sample_result(res, reduce_cell, args.device))
         for line in reduce_lines(res):
             print(line)
-        if args.out:
-            reduced = SampleResult(**cell_reduction.reduced_crystals(res.reduced), reduced=res.reduced)
+        reduced = SampleResult(**cell_reduction.reduced_crystals(res.reduced), reduced=res.reduced)
+        if symmetrize is not None:
+            _symmetrize(reduced, symmetrize, args, symmetrize_lines, save_sample_results_to_hdf5)
+        elif args.out:
             print("wrote", save_sample_results_to_hdf5(reduced, args.out))
+        return res
+    if symmetrize is not None:
+        _symmetrize(res, symmetrize, args, symmetrize_lines, save_sample_results_to_hdf5)
         return res
     if args.out:
         print("wrote", save_sample_results_to_hdf5(res, args.out))
     return res
+
+
+def _symmetrize(crystals, params, args, lines, save):
+    """Symmetrize `crystals` (the file's, or its reduced ones), print the summary and, with --out, write the symmetrized crystals."""
+    from .diffusion import symmetrize
+    from .diffusion.diffusion_loss import SampleResult
+    crystals.symmetrized = symmetrize.sample_arrays(symmetrize.symmetrize_sample_result(crystals, params, args.device))
+    for line in lines(crystals):
+        print(line)
+    if args.out:
+        arrays = symmetrize.symmetrized_crystals(crystals.symmetrized, crystals.atomic_numbers, crystals.num_atoms)
+        print("wrote", save(SampleResult(**arrays, reduced=crystals.reduced, symmetrized=crystals.symmetrized), args.out))
 
 
 if __name__ == "__main__":

@@ -501,6 +501,78 @@ typedef struct arreau_reduce_result { /* DEVICE arrays: one row per crystal, the
 int arreau_crystal_reduce(const float* d_frac, const int32_t* d_types, const float* d_lattice, const int32_t* d_crystal_offsets,
                           int32_t B, int32_t N, const arreau_reduce_params* params, arreau_reduce_result* out, void* stream);
 
+/* ---- symmetrization: exact orbits, positions and cell under the operations the symmetry search found ---------------------
+ * The fifth instrument: arreau_crystal_symmetry says which operations a crystal has within symprec; this entry point moves the
+ * atoms onto sites those operations map onto each other exactly, gives the cell the metric they leave invariant and reports
+ * the orbits (which atoms are equivalent, with which multiplicity and site-symmetry order).  One launch, one workgroup of four
+ * waves per crystal, no atomics on floats, no second stream, no arreau_model; deterministic.  NOT computed: a space-group
+ * number, an origin, a standard setting; the cell keeps the basis it came in.
+ * `found` is the result of arreau_crystal_symmetry on the same arrays (a HOST struct of device pointers; n_ops, ops_rotation,
+ * ops_translation and flags are read), max_ops its row width.  Conventions as in the symmetry search.  Per crystal, with the
+ * stored operations (W_m, t_m), m < n_ops, n atoms, wrapped positions w_i (the screen's rule 5):
+ *   1. flags.  NONFINITE, CELL and EMPTY as in arreau_crystal_symmetry's rule 1.  NO_GROUP: the search flagged the crystal
+ *      AMBIGUOUS, OVERFLOW or NOT_A_GROUP (the stored operations are then not a whole group), or n_ops lies outside 1..max_ops, or a
+ *      stored code is no matrix of determinant +-1.  NOT_A_PERMUTATION: a partner map of rule 2 is not one-to-one, or an orbit
+ *      size of rule 6 does not divide n_ops.  A crystal with any flag is copied through unchanged: frac_out = w bit for bit, its
+ *      lengths, angles and lattice come from its own metric G by rule 5, orbit[i] = i, orbit_size = site_order = 1, n_orbits =
+ *      n, both displacements 0, ops_translation and ops_shift 0, partner -1.
+ *   2. partners.  For every operation m and atom i: delta = (W_m w_i + t_m) - w_j, each component minus its nearest integer, and
+ *      |c|^2 of its Cartesian image, exactly the float32 operations of the search's rule 4; p_m(i) is the atom j of i's species
+ *      with the smallest |c|^2, the smallest j on ties, and delta_{m,i} the delta of that pair.  partner[m, a] = p_m(i) for the
+ *      atom a = offsets[b] + i ([max_ops, N]; -1 for m >= n_ops).
+ *   3. refined translations.  mean_m = (sum_i delta_{m,i}) / n, summed in atom order from 0; ops_shift_m = -mean_m and
+ *      ops_translation_m = t'_m = t_m - mean_m (not wrapped): the least-squares translation for the permutation p_m.  The
+ *      refined operations close under composition; unused slots hold zeros.
+ *   4. positions.  frac_out_i = wrap(w_i + (sum_m V_m (mean_m - delta_{m,i})) / n_ops), V_m the integer inverse of W_m
+ *      (adjugate x determinant), the sum in operation order from 0, each term (V_r0 g_0 + V_r1 g_1) + V_r2 g_2: the mean over the
+ *      group of the partners carried back, V_m (w_{p_m(i)} - t'_m).  The result is invariant under every (W_m, t'_m) up to
+ *      rounding.  A crystal whose only operation is the identity returns w bit for bit.
+ *   5. metric.  G' = (sum of W^T G W over the distinct rotations) / their number, summed in code order (the stored operations
+ *      are sorted by code: a rotation is distinct when its code differs from the one before); W^T G W is formed as the search's
+ *      rule 2 forms it, a'_j = (W_0j a_0 + W_1j a_1) + W_2j a_2 and G'_ij = a'_i . a'_j.  lengths_i = sqrt(G'_ii); angles_i =
+ *      acos(G'_jk / (lengths_j lengths_k)) in radians, j, k the other two axes, the quotient clamped to [-1, 1]; lattice is rebuilt
+ *      from them as the sampler builds its cells (arreau_lattice_from_params' orientation), so (lengths, angles, lattice) is the
+ *      representation the sampler uses.  frac_out is fractional and holds in either orientation.
+ *   6. orbits.  orbit[i] = the smallest p_m(i) over m (local to the crystal), orbit_size[i] = the number of distinct p_m(i),
+ *      site_order[i] = n_ops / orbit_size[i]; n_orbits = the number of atoms with orbit[i] = i.
+ *   7. displacements.  u_i = frac_out_i before the wrap minus w_i, |u_i| in the INPUT cell; max_displacement = sqrt(max |u|^2),
+ *      rms_displacement = sqrt((sum |u|^2) / n), in A.
+ *   8. arithmetic: as the symmetry search's rule 7 -- one float32 operation at a time, rounded to nearest, in the order written,
+ *      never contracted; divisions correctly rounded.  Only acos and the rebuilt lattice use the device's elementary functions.
+ *      The float64 restatement (arreau_amd/diffusion/symmetrize.py) is compared on guarded inputs (every decision quantity of
+ *      the search and the nearest against the second-nearest partner at most symprec / 2 or at least 2 symprec); the bounds on the
+ *      reals are derived there.
+ * The partner maps are held in global memory (out->partner), for crystals of any size.  Cost: n_ops x n^2 distance evaluations
+ * per crystal and as many integer comparisons.  Offsets outside [0, N] or descending are clamped as in the screen.  Does not
+ * synchronise.
+ * Argument errors (ARREAU_EINVAL, nothing launched): NULL found / result / arrays, negative sizes, max_ops outside
+ * 1..ARREAU_SYM_MAX_OPS_CAP. */
+#define ARREAU_SYMZ_NONFINITE 1
+#define ARREAU_SYMZ_CELL 2
+#define ARREAU_SYMZ_EMPTY 4
+#define ARREAU_SYMZ_NO_GROUP 8
+#define ARREAU_SYMZ_NOT_A_PERMUTATION 16
+typedef struct arreau_symmetrize_result { /* DEVICE arrays */
+    float* frac_out;         /* [N,3] at the input's offsets */
+    float* lattice;          /* [B,3,3] rows a, b, c rebuilt from lengths and angles */
+    float* lengths;          /* [B,3] A */
+    float* angles;           /* [B,3] radians */
+    int32_t* orbit;          /* [N] the orbit's first atom, local to the crystal */
+    int32_t* orbit_size;     /* [N] */
+    int32_t* site_order;     /* [N] n_ops / orbit_size */
+    int32_t* n_orbits;       /* [B] */
+    float* max_displacement; /* [B] A */
+    float* rms_displacement; /* [B] A */
+    float* ops_translation;  /* [B, max_ops, 3] the refined t'_m, zeros in unused slots */
+    float* ops_shift;        /* [B, max_ops, 3] t'_m - t_m: the mean difference of operation m */
+    int32_t* partner;        /* [max_ops, N] p_m(i), local to the crystal; -1 in unused rows */
+    int32_t* flags;          /* [B] ARREAU_SYMZ_* */
+} arreau_symmetrize_result;
+/* d_frac[N,3], d_types[N] species ids (required), d_lattice[B,3,3] rows a, b, c.  `found` and `out` are HOST pointers. */
+int arreau_crystal_symmetrize(const float* d_frac, const int32_t* d_types, const float* d_lattice, const int32_t* d_crystal_offsets,
+                              int32_t B, int32_t N, const arreau_symmetry_result* found, int32_t max_ops,
+                              arreau_symmetrize_result* out, void* stream);
+
 /* ---- the score network ---------------------------------------------------------------------- */
 
 /* One evaluation of DiffusionLoss.predict_scores (diffusion/diffusion_loss.py:112-197):
