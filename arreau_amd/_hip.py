@@ -31,7 +31,7 @@ EXPORTS = [
     "arreau_sample_loop_tied", "arreau_reverse_step_tied", "arreau_resample_jump_tied",
     "arreau_sample_loop_sym", "arreau_reverse_step_sym", "arreau_crystal_screen",
     "arreau_crystal_fingerprint", "arreau_fingerprint_match", "arreau_crystal_symmetry", "arreau_crystal_reduce",
-    "arreau_crystal_symmetrize",
+    "arreau_crystal_symmetrize", "arreau_structure_match",
 ]
 
 STATUS_NONFINITE, STATUS_BAD_TIMESTEP, STATUS_BAD_TYPE, STATUS_BAD_TIE, STATUS_BAD_SYMMETRY = 1, 2, 4, 8, 16
@@ -136,6 +136,17 @@ class SymmetrizeResultC(Structure):
                                                 "max_displacement", "rms_displacement", "ops_translation", "ops_shift", "partner", "flags")]
 
 
+class StructureMatchParamsC(Structure):
+    """arreau_structure_match_params: the tolerances of the structure match and the lattice mappings tried per pair."""
+    _fields_ = [("ltol", c_float), ("angle_tol", c_float), ("stol", c_float), ("max_mappings", c_int32)]
+
+
+class StructureMatchResultC(Structure):
+    """arreau_structure_match_result: the device arrays the structure match writes, one row per pair, and the row width of partner."""
+    _fields_ = [(name, c_void_p) for name in ("rms", "rms_norm", "max_dist", "mapping", "translation", "partner", "n_mappings",
+                                                "n_candidates", "n_permutations", "matched", "flags", "scratch")] + [("partner_stride", c_int32)]
+
+
 class Config(Structure):
     _fields_ = [
         ("num_atomic_states", c_int32), ("hidden_dim", c_int32), ("basis_dim", c_int32),
@@ -212,6 +223,7 @@ def _prototypes():
         "arreau_crystal_symmetry": [vp] * 4 + [i32, i32, POINTER(SymmetryParamsC), POINTER(SymmetryResultC), vp],
         "arreau_crystal_reduce": [vp] * 4 + [i32, i32, POINTER(ReduceParamsC), POINTER(ReduceResultC), vp],
         "arreau_crystal_symmetrize": [vp] * 4 + [i32, i32, POINTER(SymmetryResultC), i32, POINTER(SymmetrizeResultC), vp],
+        "arreau_structure_match": ([vp] * 4 + [i32, i32]) * 2 + [vp, i32, POINTER(StructureMatchParamsC), POINTER(StructureMatchResultC), vp],
         "arreau_train_forward": [vp] * 7 + [i32, i32] + [vp] * 4,
         "arreau_train_backward": [vp] * 4 + [POINTER(StateDict), vp],
         "arreau_train_conv_stats": [vp, vp, vp],

@@ -1,7 +1,8 @@
-// Device helpers shared by the per-crystal kernels (screen.hip, fingerprint.hip, symfind.hip, reduce.hip, symmetrize.hip; one workgroup of CRYSTAL_WAVES waves
+// Device helpers shared by the per-crystal kernels (screen.hip, fingerprint.hip, symfind.hip, reduce.hip, symmetrize.hip, match.hip; one workgroup of CRYSTAL_WAVES waves
 // per crystal): the launch shape, the prologue, the cell and its image range, the wrap of a fractional coordinate and the Cartesian
 // position, one periodic contact, the compaction of a workgroup's hits in thread order, the rarest species, the squared
-// length of a fractional difference and the matrix of a rotation code.  One float32 rounding per operation.
+// length of a fractional difference, the matrix of a rotation code, its integer inverse and the metric of a cell's image under
+// it.  One float32 rounding per operation.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -188,4 +189,24 @@ __device__ __forceinline__ int decode_rotation(int code, int* W) {
 // (W v)_r = (W_r0 v_0 + W_r1 v_1) + W_r2 v_2: the products by -1, 0, 1 are exact, two rounded sums
 __device__ __forceinline__ float rot_row(const float* W, int r, float v0, float v1, float v2) {
     return __fadd_rn(__fadd_rn(__fmul_rn(W[3 * r], v0), __fmul_rn(W[3 * r + 1], v1)), __fmul_rn(W[3 * r + 2], v2));
+}
+
+// a'_j = (W_0j a_0 + W_1j a_1) + W_2j a_2 (the search's rule 2) and the six scalar products 00, 11, 22, 01, 02, 12 of the images
+__device__ __forceinline__ void image_metric(const int* W, const float* Lm, float* g) {
+    float img[9];
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+#pragma unroll
+        for (int d = 0; d < 3; ++d) img[3 * j + d] = rows_rn(Lm, d, (float)W[j], (float)W[3 + j], (float)W[6 + j]);
+    const int pi[6] = {0, 1, 2, 0, 0, 1}, pj[6] = {0, 1, 2, 1, 2, 2};
+#pragma unroll
+    for (int e = 0; e < 6; ++e)
+        g[e] = dot3_rn(img[3 * pi[e]], img[3 * pi[e] + 1], img[3 * pi[e] + 2], img[3 * pj[e]], img[3 * pj[e] + 1], img[3 * pj[e] + 2]);
+}
+
+// the integer inverse of a matrix of determinant det = +-1: its adjugate times det
+__device__ __forceinline__ void inverse_rotation(const int* W, int det, float* V) {
+    V[0] = (float)(det * (W[4] * W[8] - W[5] * W[7])); V[1] = (float)(det * (W[2] * W[7] - W[1] * W[8])); V[2] = (float)(det * (W[1] * W[5] - W[2] * W[4]));
+    V[3] = (float)(det * (W[5] * W[6] - W[3] * W[8])); V[4] = (float)(det * (W[0] * W[8] - W[2] * W[6])); V[5] = (float)(det * (W[2] * W[3] - W[0] * W[5]));
+    V[6] = (float)(det * (W[3] * W[7] - W[4] * W[6])); V[7] = (float)(det * (W[1] * W[6] - W[0] * W[7])); V[8] = (float)(det * (W[0] * W[4] - W[1] * W[3]));
 }

@@ -29,26 +29,6 @@ struct symz_out {
     int32_t *partner, *flags;
 };
 
-// a'_j = (W_0j a_0 + W_1j a_1) + W_2j a_2 (the search's rule 2) and the six scalar products 00, 11, 22, 01, 02, 12 of the images
-__device__ __forceinline__ void image_metric(const int* W, const float* Lm, float* g) {
-    float img[9];
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-#pragma unroll
-        for (int d = 0; d < 3; ++d) img[3 * j + d] = rows_rn(Lm, d, (float)W[j], (float)W[3 + j], (float)W[6 + j]);
-    const int pi[6] = {0, 1, 2, 0, 0, 1}, pj[6] = {0, 1, 2, 1, 2, 2};
-#pragma unroll
-    for (int e = 0; e < 6; ++e)
-        g[e] = dot3_rn(img[3 * pi[e]], img[3 * pi[e] + 1], img[3 * pi[e] + 2], img[3 * pj[e]], img[3 * pj[e] + 1], img[3 * pj[e] + 2]);
-}
-
-// the integer inverse of a matrix of determinant det = +-1: its adjugate times det
-__device__ __forceinline__ void inverse_rotation(const int* W, int det, float* V) {
-    V[0] = (float)(det * (W[4] * W[8] - W[5] * W[7])); V[1] = (float)(det * (W[2] * W[7] - W[1] * W[8])); V[2] = (float)(det * (W[1] * W[5] - W[2] * W[4]));
-    V[3] = (float)(det * (W[5] * W[6] - W[3] * W[8])); V[4] = (float)(det * (W[0] * W[8] - W[2] * W[6])); V[5] = (float)(det * (W[2] * W[3] - W[0] * W[5]));
-    V[6] = (float)(det * (W[3] * W[7] - W[4] * W[6])); V[7] = (float)(det * (W[1] * W[6] - W[0] * W[7])); V[8] = (float)(det * (W[0] * W[4] - W[1] * W[3]));
-}
-
 __global__ __launch_bounds__(CRYSTAL_THREADS) void crystal_symmetrize_kernel(
     const float* __restrict__ frac, const int32_t* __restrict__ types, const float* __restrict__ lattice,
     const int32_t* __restrict__ offsets, int B, int N, int max_ops, symz_in f, symz_out o) {

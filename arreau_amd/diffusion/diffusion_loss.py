@@ -19,6 +19,7 @@ from . import uniqueness as uniqueness_mod
 from . import cell_reduction
 from . import symmetry_search
 from . import symmetrize as symmetrize_mod
+from . import structure_match
 from .d3pm import D3PM
 from . import lattice_systems
 from . import symmetry as sym_mod
@@ -63,6 +64,10 @@ class SampleResult:
     # orbit, orbit_size and site_order, one row per atom of the crystals as sampled, and lattice, lengths, angles, n_orbits,
     # max_displacement, rms_displacement, ops_translation and flags, one row per crystal; None when it was not asked for
     symmetrized: Optional[dict] = None
+    # extension: the structure match of the final state against targets (sample(match_to=...); diffusion/structure_match.py) -- numpy
+    # arrays target, n_comparable, rms, rms_norm, max_dist, mapping, translation, n_mappings, n_candidates, n_permutations, matched
+    # and flags, one row per crystal, and partner, one row per atom; None when it was not asked for
+    match: Optional[dict] = None
 
 
 class _PinnedRing:
@@ -288,7 +293,7 @@ class DiffusionLoss(nn.Module):
                timesteps: Optional[Sequence[int]] = None, corrector_steps: int = 0,
                corrector_snr: float = pc.DEFAULT_SNR, resample_passes: int = 1, jump_length: int = 10,
                lattice_system=None, symmetry=None, screen=None, unique=None, find_symmetry=None, reduce_cell=None,
-               symmetrize=None) -> SampleResult:
+               symmetrize=None, match_to=None) -> SampleResult:
         """diffusion_loss.py:276-377.  The initial state is drawn on the host exactly like the reference (numpy
         uniforms for the angles, then randn lengths, randn fractional coordinates from torch's global CPU generator).
         Per-step noise:
@@ -378,7 +383,16 @@ class DiffusionLoss(nn.Module):
         its metric over their rotations and report its orbits.  SampleResult.symmetrized then holds the arrays
         (symmetrize.SYMMETRIZED_KEYS); frac_x, lattice and every other field stay as sampled, and screen, unique, find_symmetry and
         reduce_cell still read that state.  No space-group number, no origin search, no standard setting.  None: no launch is
-        added, symmetrized is None and the results are what they were, bit for bit."""
+        added, symmetrized is None and the results are what they were, bit for bit.
+        `match_to` (extension, every noise mode and option): targets to match the final state against -- a SampleResult, a loaded
+        crystals file, or (targets, structure_match.StructureMatchParams) -- in one more launch (arreau_structure_match; rules in
+        include/arreau_hip.h): per crystal the change of basis, the translation and the atom-to-atom map under which a target
+        falls onto it, the rms displacement in A and normalised, and `matched` (rms_norm <= stol).  As many targets as crystals:
+        crystal b is matched against target b; otherwise against every target of its composition, the best one reported.  The
+        atomic numbers are the species ids.  SampleResult.match then holds the arrays (structure_match.MATCH_KEYS).  It reads the
+        state as sampled, like the other instruments.  No Hungarian assignment, no supercells, no volume scaling.  None: no launch
+        is added, match is None and the results are what they were, bit for bit."""
+        match_to = structure_match.resolve(match_to)
         reduce_cell = cell_reduction.resolve(reduce_cell)
         symmetrize = symmetrize_mod.resolve(symmetrize)
         symmetrize_mod.check_shared_search(symmetrize, symmetry_search.resolve(find_symmetry))
@@ -642,7 +656,12 @@ class DiffusionLoss(nn.Module):
             reduced = cell_reduction.result_to_numpy(eng.reduce_cells(frac_d, lattice_d, off_d, types_d, reduce_cell))
             reduced = cell_reduction.sample_arrays(reduced, atomic_number_indexes_to_atomic_numbers(z_table, reduced["types"]))
         atomic_numbers = atomic_number_indexes_to_atomic_numbers(z_table, types_d.cpu().numpy())
+        match = None
+        if match_to is not None:  # (the atomic numbers are the species ids the targets carry: one small upload)
+            species = np.rint(np.asarray(atomic_numbers).reshape(-1)).astype(np.int32)
+            match = structure_match.sample_arrays(structure_match.match_batches(
+                (frac_d, lattice_d, off_d, torch.as_tensor(species, device=frac_d.device)), num_atoms.numpy(), species, *match_to))
         return SampleResult(num_atoms=num_atoms.numpy(), frac_x=frac_d.cpu().numpy().astype(np.float64),
                             atomic_numbers=atomic_numbers, lattice=lattice_d.cpu().numpy().astype(np.float64), info=info,
                             metrics=metrics, uniqueness=uniqueness, symmetry=found, reduced=reduced,
-                            symmetrized=symmetrized)
+                            symmetrized=symmetrized, match=match)

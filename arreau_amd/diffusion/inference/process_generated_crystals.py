@@ -23,7 +23,10 @@ reduced_num_atoms, 3], reduced_atomic_numbers and reduced_keep.  A result that c
 (SampleResult.symmetrized, diffusion/symmetrize.py) gets symmetrized_frac_x [sum n, 3], symmetrized_orbit, symmetrized_orbit_size and
 symmetrized_site_order [sum n], and per crystal symmetrized_lattice [B,3,3], symmetrized_lengths, symmetrized_angles [B,3],
 symmetrized_n_orbits, symmetrized_max_displacement, symmetrized_rms_displacement, symmetrized_ops_translation [B,max_ops,3] and
-symmetrized_flags."""
+symmetrized_flags.  A result that carries a structure match against targets (SampleResult.match,
+diffusion/structure_match.py) gets match_partner [sum n] and per crystal match_target, match_n_comparable, match_rms, match_rms_norm,
+match_max_dist, match_mapping, match_translation [B,3], match_n_mappings, match_n_candidates, match_n_permutations, match_matched and
+match_flags."""
 import os
 
 import numpy as np
@@ -44,6 +47,9 @@ REDUCED_PREFIX = "reduced_"
 SYMMETRIZED_KEYS = ("frac_x", "lattice", "lengths", "angles", "orbit", "orbit_size", "site_order", "n_orbits", "max_displacement",
                     "rms_displacement", "ops_translation", "flags")  # symmetrize.SYMMETRIZED_KEYS
 SYMMETRIZED_PREFIX = "symmetrized_"
+MATCH_KEYS = ("target", "n_comparable", "rms", "rms_norm", "max_dist", "mapping", "translation", "partner", "n_mappings", "n_candidates",
+              "n_permutations", "matched", "flags")  # structure_match.MATCH_KEYS
+MATCH_PREFIX = "match_"
 _DTYPES = dict(frac_x=np.float64, atomic_numbers=np.float64, lattice=np.float64, idx_start=np.int64,
                num_atoms=np.int64)
 
@@ -106,6 +112,15 @@ def _fields(crystals: SampleResult):
             if v.shape[:1] != ((n_tot,) if k in ("frac_x", "orbit", "orbit_size", "site_order") else (B,)):
                 raise ValueError(f"SampleResult.symmetrized[{k!r}] does not hold one row per crystal (or per atom)")
             out[SYMMETRIZED_PREFIX + k] = v
+    match = getattr(crystals, "match", None)
+    if match is not None:
+        for k in MATCH_KEYS:
+            if k not in match:
+                raise ValueError(f"SampleResult.match[{k!r}] is missing")
+            v = np.asarray(match[k])
+            if v.shape[:1] != ((n_tot,) if k == "partner" else (B,)):
+                raise ValueError(f"SampleResult.match[{k!r}] does not hold one row per crystal (or per atom)")
+            out[MATCH_PREFIX + k] = v
     return out
 
 
@@ -147,6 +162,7 @@ def load_sample_results_from_hdf5(filename: str) -> SampleResult:
             symmetry = _metrics_from(lambda k: k in fh["crystals"], lambda k: fh["crystals"][k][:], SYM_PREFIX, SYM_KEYS)
             reduced = _metrics_from(lambda k: k in fh["crystals"], lambda k: fh["crystals"][k][:], REDUCED_PREFIX, REDUCED_KEYS)
             symmetrized = _metrics_from(lambda k: k in fh["crystals"], lambda k: fh["crystals"][k][:], SYMMETRIZED_PREFIX, SYMMETRIZED_KEYS)
+            match = _metrics_from(lambda k: k in fh["crystals"], lambda k: fh["crystals"][k][:], MATCH_PREFIX, MATCH_KEYS)
     else:
         with np.load(filename) as z:
             data = {k: z[k] for k in KEYS}
@@ -155,10 +171,11 @@ def load_sample_results_from_hdf5(filename: str) -> SampleResult:
             symmetry = _metrics_from(lambda k: k in z.files, lambda k: z[k], SYM_PREFIX, SYM_KEYS)
             reduced = _metrics_from(lambda k: k in z.files, lambda k: z[k], REDUCED_PREFIX, REDUCED_KEYS)
             symmetrized = _metrics_from(lambda k: k in z.files, lambda k: z[k], SYMMETRIZED_PREFIX, SYMMETRIZED_KEYS)
+            match = _metrics_from(lambda k: k in z.files, lambda k: z[k], MATCH_PREFIX, MATCH_KEYS)
     if symmetry is not None:  # (the search saw the float32 cells)
         symmetry["lattice"] = np.asarray(data["lattice"], dtype=np.float32).reshape(-1, 3, 3)
     return SampleResult(**data, metrics=metrics, uniqueness=uniqueness, symmetry=symmetry, reduced=reduced,
-                        symmetrized=symmetrized)
+                        symmetrized=symmetrized, match=match)
 
 
 def get_crystal_indexes(sample_result: SampleResult, sample_idx: int):

@@ -38,6 +38,11 @@ Duplicate detection: `--unique` (`--fp_r_max`, `--fp_sigma`, `--fp_tolerance`) f
 (diffusion/uniqueness.py).  Every rank reports unique / attempted within its own crystals; rank 0, after the gather of host arrays,
 matches the whole set once on its own GPU, prints the total and stores those arrays as unique_* in the output file.  May be
 combined with --screen / --require_valid; the two do not interact.
+
+Structure match: `--match_to FILE` (`--ltol`, `--angle_tol`, `--stol`) matches every generated crystal on the device, at the end of
+its sampling call, against every target of its composition in that crystals file (diffusion/structure_match.py) and keeps the best:
+match rate (matched / attempted) and mean rms_norm and rms over the matched, per rank and in total, and match_* arrays in the
+output file.  No Hungarian assignment, no supercells (combine with a reduced target file), no volume scaling.
 """
 import argparse
 import os
@@ -59,7 +64,7 @@ def _screen_stats(parts):
     """The per-rank screen and uniqueness statistics the parts carry (SampleResult.info["screen_stats"] / ["unique_stats"]), each
     in one list; None when no part has any."""
     out = {}
-    for key in ("screen_stats", "unique_stats", "symmetry_stats", "reduce_stats", "symmetrize_stats"):
+    for key in ("screen_stats", "unique_stats", "symmetry_stats", "reduce_stats", "symmetrize_stats", "match_stats"):
         stats = [st for p in parts if p is not None and p.info for st in p.info.get(key, [])]
         if stats:
             out[key] = stats
@@ -89,11 +94,15 @@ def concat_results(parts) -> SampleResult:
     if all(p.symmetrized is not None for p in parts):  # (one max_ops for the run: the rows have one width)
         from .diffusion import symmetrize
         symmetrized = symmetrize.concat_symmetrized([p.symmetrized for p in parts])
+    match = None
+    if all(p.match is not None for p in parts):
+        from .diffusion import structure_match
+        match = structure_match.concat_matches([p.match for p in parts])
     return SampleResult(
         frac_x=np.concatenate([p.frac_x for p in parts]), atomic_numbers=np.concatenate([p.atomic_numbers for p in parts]),
         lattice=np.concatenate([p.lattice for p in parts]), num_atoms=num_atoms,
         idx_start=np.cumsum(num_atoms) - num_atoms, info=info, metrics=metrics, symmetry=symmetry, reduced=reduced,
-        symmetrized=symmetrized)
+        symmetrized=symmetrized, match=match)
 
 
 def select_crystals(res: SampleResult, keep) -> SampleResult:
@@ -112,9 +121,13 @@ def select_crystals(res: SampleResult, keep) -> SampleResult:
     if res.symmetrized is not None:
         from .diffusion import symmetrize
         symmetrized = symmetrize.select_symmetrized(res.symmetrized, keep, atoms)
+    match = None
+    if res.match is not None:
+        from .diffusion import structure_match
+        match = structure_match.select_matches(res.match, keep, atoms)
     return SampleResult(frac_x=np.asarray(res.frac_x)[atoms], atomic_numbers=np.asarray(res.atomic_numbers)[atoms],
                         lattice=np.asarray(res.lattice)[keep], num_atoms=kept, idx_start=np.cumsum(kept) - kept, metrics=metrics,
-                        symmetry=symmetry, reduced=reduced, symmetrized=symmetrized)
+                        symmetry=symmetry, reduced=reduced, symmetrized=symmetrized, match=match)
 
 
 FIX_KINDS = ("positions", "species", "lattice")
@@ -169,6 +182,9 @@ def _gather_results(local: SampleResult, rank: int, world_size: int, gather: Opt
     if local.symmetrized is not None and not (local.info or {}).get("symmetrize_stats"):  # a symmetrized run: this rank's histogram
         from .diffusion import symmetrize
         local.info = dict(local.info or {}, symmetrize_stats=[symmetrize.stats_of(local.symmetrized, rank)])
+    if local.match is not None and not (local.info or {}).get("match_stats"):  # a matched run: this rank's rate
+        from .diffusion import structure_match
+        local.info = dict(local.info or {}, match_stats=[structure_match.stats_of(local.match, rank)])
     if unique is not None:  # duplicates within this rank's crystals, on its own device
         from .diffusion import uniqueness
         local.info = dict(local.info or {}, unique_stats=[uniqueness.stats_of(uniqueness.unique_sample_result(local, unique), rank)])
@@ -333,7 +349,43 @@ def build_parser() -> argparse.ArgumentParser:
                     help="symmetrize every generated crystal on the device with the operations found within --symprec: exact "
                          "orbits, averaged positions and cell; histogram of orbit counts and flags and the largest displacement "
                          "per rank and in total + symmetrized_* arrays in the output file")
+    ap.add_argument("--match_to", default=None, metavar="FILE",
+                    help="match every generated crystal against the targets of a crystals file on the device (the best target of its "
+                         "composition): match rate and mean RMSD per rank and in total + match_* arrays in the output file")
+    add_structure_match_arguments(ap)
     return ap
+
+
+def add_structure_match_arguments(ap):
+    """The tolerance flags of the structure match, shared with `python -m arreau_amd.screen`."""
+    ap.add_argument("--ltol", type=float, default=0.2, help="match_to: relative tolerance on the cell lengths (StructureMatcher's default)")
+    ap.add_argument("--angle_tol", type=float, default=5.0, help="match_to: tolerance on the cell angles, degrees")
+    ap.add_argument("--stol", type=float, default=0.3, help="match_to: a pair matches when rms / (V / n)^(1/3) is at most this")
+
+
+def structure_match_params(args, error):
+    """The StructureMatchParams of the tolerance flags (max_mappings the default); `error(message)` reports a bad value."""
+    from .diffusion.structure_match import StructureMatchParams
+    try:
+        return StructureMatchParams(ltol=args.ltol, angle_tol=args.angle_tol, stol=args.stol)
+    except ValueError as e:
+        error(f"structure match: {e}")
+
+
+def load_targets(filename, error):
+    """The crystals file of --match_to; `error(message)` reports a file that cannot be read."""
+    from .diffusion.inference.process_generated_crystals import load_sample_results_from_hdf5
+    try:
+        return load_sample_results_from_hdf5(filename)
+    except (OSError, KeyError, ValueError) as e:
+        error(f"--match_to: {e}")
+
+
+def match_lines(res, parts=None):
+    """The lines `--match_to` prints for a result that holds the match's arrays: match rate, mean rms_norm and rms over the matched
+    and the flags, per rank (`parts`: the statistics the ranks carried; None: the result as one set) and in total."""
+    from .diffusion import structure_match
+    return structure_match.summary_lines(parts if parts else [structure_match.stats_of(res.match)])
 
 
 def add_symmetry_search_arguments(ap):
@@ -493,6 +545,7 @@ def main():
     find_sym = symmetry_search_params(args, ap.error) if args.find_symmetry else None
     reduce_cell = cell_reduction_params(args, ap.error) if args.reduce_cell else None
     symmetrize = symmetrize_params(args, ap.error) if args.symmetrize else None
+    match_to = (load_targets(args.match_to, ap.error), structure_match_params(args, ap.error), "any") if args.match_to else None
     condition = load_template(args.template, parse_fix(args.fix)).tile(args.samples_per_template) if args.template else None
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -529,7 +582,7 @@ def main():
                                 corrector_steps=args.corrector_steps, corrector_snr=args.corrector_snr,
                                 resample_passes=args.resample_passes, jump_length=args.jump_length,
                                 lattice_system=args.lattice_system, symmetry=spec, screen=criteria,
-                                find_symmetry=find_sym, reduce_cell=reduce_cell, symmetrize=symmetrize)
+                                find_symmetry=find_sym, reduce_cell=reduce_cell, symmetrize=symmetrize, match_to=match_to)
         import fcntl
         with open(lock_path, "a") as lock:
             fcntl.flock(lock, fcntl.LOCK_EX)
@@ -538,7 +591,7 @@ def main():
                                 corrector_steps=args.corrector_steps, corrector_snr=args.corrector_snr,
                                 resample_passes=args.resample_passes, jump_length=args.jump_length,
                                 lattice_system=args.lattice_system, symmetry=spec, screen=criteria,
-                                find_symmetry=find_sym, reduce_cell=reduce_cell, symmetrize=symmetrize)
+                                find_symmetry=find_sym, reduce_cell=reduce_cell, symmetrize=symmetrize, match_to=match_to)
                 torch.cuda.synchronize()
                 return out
             finally:
@@ -567,6 +620,9 @@ def main():
                 print(line)
         if symmetrize is not None:
             for line in symmetrize_lines(res, (res.info or {}).get("symmetrize_stats")):
+                print(line)
+        if match_to is not None:
+            for line in match_lines(res, (res.info or {}).get("match_stats")):
                 print(line)
         print("wrote", save_sample_results(res, args.out))
     if world > 1:

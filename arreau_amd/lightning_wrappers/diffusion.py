@@ -329,7 +329,7 @@ class PONITA_DIFFUSION(nn.Module):
                condition=None, num_steps: Optional[int] = None, timesteps=None, corrector_steps: int = 0,
                corrector_snr: float = 0.16, resample_passes: int = 1, jump_length: int = 10,
                lattice_system=None, symmetry=None, screen=None, unique=None, find_symmetry=None, reduce_cell=None,
-               symmetrize=None) -> SampleResult:
+               symmetrize=None, match_to=None) -> SampleResult:
         """lightning_wrappers/diffusion.py:220-253.  `num_atoms_per_sample` may also be a sequence with one atom count
         per crystal of the batch (extension; the reference supports a single int).  Frames of a visualization_setting
         other than NONE go to `<DIFFUSION_DIR>/step_<timestep>.cif` like the reference's PNGs (`vis_name` overrides the
@@ -349,7 +349,9 @@ class PONITA_DIFFUSION(nn.Module):
         `unique` (extension): a diffusion.uniqueness.FingerprintParams or True -- duplicate detection on the final device state;
         SampleResult.uniqueness holds the result (DiffusionLoss.sample).  `find_symmetry` (extension): a
         diffusion.symmetry_search.SymmetrySearchParams or True -- the symmetry operations and point group of every final crystal;
-        SampleResult.symmetry holds the arrays (DiffusionLoss.sample)."""
+        SampleResult.symmetry holds the arrays (DiffusionLoss.sample).  `match_to` (extension): targets (a SampleResult, a loaded
+        crystals file, or (targets, diffusion.structure_match.StructureMatchParams)) the final crystals are matched against on the
+        device; SampleResult.match holds the arrays (DiffusionLoss.sample)."""
         from ..diffusion import resampling
         resampling.check_resampling(resample_passes, jump_length)  # (raises before any work)
         if num_steps is not None or timesteps is not None:
@@ -374,4 +376,5 @@ class PONITA_DIFFUSION(nn.Module):
             noise=noise, max_steps=max_steps, use_graph=use_graph, seed=seed, fixed_cell=fixed_cell, condition=condition,
             num_steps=num_steps, timesteps=timesteps, corrector_steps=corrector_steps, corrector_snr=corrector_snr,
             resample_passes=resample_passes, jump_length=jump_length, lattice_system=lattice_system, symmetry=symmetry,
-            screen=screen, unique=unique, find_symmetry=find_symmetry, reduce_cell=reduce_cell, symmetrize=symmetrize)
+            screen=screen, unique=unique, find_symmetry=find_symmetry, reduce_cell=reduce_cell, symmetrize=symmetrize,
+            match_to=match_to)

@@ -4,6 +4,7 @@
     python -m arreau_amd.screen out/crystals.npz --find_symmetry [--symprec 0.1]
     python -m arreau_amd.screen out/crystals.npz --reduce_cell [--symprec 0.1] [--out reduced.npz]
     python -m arreau_amd.screen out/crystals.npz --symmetrize [--symprec 0.1] [--out symmetrized.npz]
+    python -m arreau_amd.screen out/crystals.npz --match_to targets.npz [--match_mode paired|any] [--ltol 0.2] [--angle_tol 5] [--stol 0.3]
     python -m arreau_amd.screen out/crystals.npz --unique [--against train.npz] [--fp_r_max 6] [--fp_sigma 0.1] [--fp_tolerance 0.01]
 
 Prints the summary `python -m arreau_amd.generate --screen` prints (accepted / attempted and the count per flag) and, with
@@ -19,12 +20,19 @@ this run describe the cells as given and are not written to it), on which the ot
 `--symmetrize [--symprec 0.1]` adds the symmetrization (diffusion/symmetrize.py): the count per number of orbits and flag and the
 largest displacement; `--out` then writes a crystals file of the SYMMETRIZED crystals (averaged positions, rebuilt cells, and the
 symmetrized_* arrays) in the same way.  With `--reduce_cell` too the reduction runs first and its crystals are symmetrized.
+`--match_to TARGETS` adds the structure match (diffusion/structure_match.py) against the crystals of a second file: match rate, mean
+rms_norm and rms over the matched, and the count per flag; `--match_mode paired` matches crystal b against target b, `any` against
+every target of its composition (the best one counts); without the flag the match is paired when the two files hold equally many
+crystals.  It runs after `--reduce_cell` and `--symmetrize` when those are given, on their crystals, and the targets are then put
+through the same reduction and symmetrization; `--out` gets the match_* arrays.  No Hungarian assignment, no supercells, no
+volume scaling.
 """
 import argparse
 
 
 def build_parser() -> argparse.ArgumentParser:
-    from .generate import add_fingerprint_arguments, add_screen_arguments, add_symmetry_search_arguments
+    from .generate import (add_fingerprint_arguments, add_screen_arguments, add_structure_match_arguments,
+                           add_symmetry_search_arguments)
     ap = argparse.ArgumentParser(prog="python -m arreau_amd.screen", description="structural screen of a crystals file")
     ap.add_argument("file", type=str, help="crystals.npz / .h5")
     add_screen_arguments(ap)
@@ -40,23 +48,34 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--symmetrize", action="store_true",
                     help="also symmetrize every crystal with the operations found within --symprec; --out then writes the "
                          "symmetrized crystals (after --reduce_cell: of the reduced crystals)")
+    ap.add_argument("--match_to", type=str, default=None, metavar="TARGETS",
+                    help="also match every crystal against the crystals of this file (after --reduce_cell / --symmetrize, which the "
+                         "targets then go through too): match rate and mean RMSD")
+    ap.add_argument("--match_mode", choices=("paired", "any"), default=None,
+                    help="--match_to: crystal b against target b, or against every target of its composition (default: paired when "
+                         "the files hold equally many crystals)")
+    add_structure_match_arguments(ap)
     return ap
 
 
 def main(argv=None):
     from .diffusion import screening
     from .diffusion.inference.process_generated_crystals import load_sample_results_from_hdf5, save_sample_results_to_hdf5
-    from .generate import (cell_reduction_params, fingerprint_params, reduce_lines, screen_criteria, symmetrize_lines,
-                           symmetrize_params, symmetry_lines, symmetry_search_params, unique_lines)
+    from .diffusion.diffusion_loss import SampleResult
+    from .generate import (cell_reduction_params, fingerprint_params, match_lines, reduce_lines, screen_criteria, structure_match_params,
+                           symmetrize_lines, symmetrize_params, symmetry_lines, symmetry_search_params, unique_lines)
     ap = build_parser()
     args = ap.parse_args(argv)
     criteria = screen_criteria(args, ap.error)
     if args.against is not None and not args.unique:
         ap.error("--against needs --unique")
+    if args.match_mode is not None and args.match_to is None:
+        ap.error("--match_mode needs --match_to")
     unique = fingerprint_params(args, ap.error) if args.unique else None
     find_sym = symmetry_search_params(args, ap.error) if args.find_symmetry else None
     reduce_cell = cell_reduction_params(args, ap.error) if args.reduce_cell else None
     symmetrize = symmetrize_params(args, ap.error) if args.symmetrize else None
+    match_params = structure_match_params(args, ap.error) if args.match_to is not None else None
 
     def load(name):
         try:
@@ -66,6 +85,7 @@ def main(argv=None):
 
     res = load(args.file)
     against = load(args.against) if args.against is not None else None
+    targets = load(args.match_to) if args.match_to is not None else None
     res.metrics = screening.screen_sample_result(res, criteria, args.device)
     for line in screening.summary_lines([screening.stats_of(res.metrics["flags"])]):
         print(line)
@@ -78,36 +98,44 @@ def main(argv=None):
         res.symmetry = symmetry_search.symmetry_sample_result(res, find_sym, args.device)
         for line in symmetry_lines(res):
             print(line)
+    current = res  # the crystals the next step reads and --out writes: the file's, its reduced ones, their symmetrized ones
     if reduce_cell is not None:
         from .diffusion import cell_reduction
-        from .diffusion.diffusion_loss import SampleResult
         res.reduced = cell_reduction.sample_arrays(cell_reduction.reduce_sample_result(res, reduce_cell, args.device))
         for line in reduce_lines(res):
             print(line)
-        reduced = SampleResult(**cell_reduction.reduced_crystals(res.reduced), reduced=res.reduced)
-        if symmetrize is not None:
-            _symmetrize(reduced, symmetrize, args, symmetrize_lines, save_sample_results_to_hdf5)
-        elif args.out:
-            print("wrote", save_sample_results_to_hdf5(reduced, args.out))
-        return res
+        current = SampleResult(**cell_reduction.reduced_crystals(res.reduced), reduced=res.reduced)
+        if targets is not None:
+            targets = SampleResult(**cell_reduction.reduced_crystals(
+                cell_reduction.sample_arrays(cell_reduction.reduce_sample_result(targets, reduce_cell, args.device))))
     if symmetrize is not None:
-        _symmetrize(res, symmetrize, args, symmetrize_lines, save_sample_results_to_hdf5)
-        return res
+        current = _symmetrize(current, symmetrize, args, symmetrize_lines)
+        if targets is not None:
+            targets = _symmetrize(targets, symmetrize, args, None)
+    if targets is not None:
+        from .diffusion import structure_match
+        try:
+            matched = structure_match.match_crystals(current, targets, match_params, args.match_mode, args.device)
+        except ValueError as e:
+            ap.error(f"--match_to: {e}")
+        current.match = res.match = structure_match.sample_arrays(matched)
+        for line in match_lines(current):
+            print(line)
     if args.out:
-        print("wrote", save_sample_results_to_hdf5(res, args.out))
+        print("wrote", save_sample_results_to_hdf5(current, args.out))
     return res
 
 
-def _symmetrize(crystals, params, args, lines, save):
-    """Symmetrize `crystals` (the file's, or its reduced ones), print the summary and, with --out, write the symmetrized crystals."""
+def _symmetrize(crystals, params, args, lines):
+    """Symmetrize `crystals` (the file's, its reduced ones, or the targets of a match), print the summary (`lines`; None: nothing)
+    and return the symmetrized crystals as the SampleResult that --out writes."""
     from .diffusion import symmetrize
     from .diffusion.diffusion_loss import SampleResult
     crystals.symmetrized = symmetrize.sample_arrays(symmetrize.symmetrize_sample_result(crystals, params, args.device))
-    for line in lines(crystals):
+    for line in (lines(crystals) if lines is not None else []):
         print(line)
-    if args.out:
-        arrays = symmetrize.symmetrized_crystals(crystals.symmetrized, crystals.atomic_numbers, crystals.num_atoms)
-        print("wrote", save(SampleResult(**arrays, reduced=crystals.reduced, symmetrized=crystals.symmetrized), args.out))
+    arrays = symmetrize.symmetrized_crystals(crystals.symmetrized, crystals.atomic_numbers, crystals.num_atoms)
+    return SampleResult(**arrays, reduced=crystals.reduced, symmetrized=crystals.symmetrized)
 
 
 if __name__ == "__main__":

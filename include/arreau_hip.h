@@ -573,6 +573,92 @@ int arreau_crystal_symmetrize(const float* d_frac, const int32_t* d_types, const
                               int32_t B, int32_t N, const arreau_symmetry_result* found, int32_t max_ops,
                               arreau_symmetrize_result* out, void* stream);
 
+/* ---- structure match: is crystal x that crystal y, under which map, and how far off in A ------------------------------------
+ * The sixth instrument: for every pair (x, y) of a pair list, x a crystal of batch X and y one of batch Y (Y may be X), the
+ * change of basis W and the translation under which y's atoms fall next to x's, the atom-to-atom map and the root-mean-square
+ * displacement, in A and normalised as pymatgen's StructureMatcher normalises it.  One launch, one workgroup of four waves per
+ * pair, no atomics, no arreau_model, no synchronisation; deterministic.  NOT computed: an optimal assignment where the
+ * nearest-partner map is no permutation (no Hungarian step: such a candidate is skipped, rule 6); supercells, formula reduction
+ * or anonymous species (the species multisets are compared exactly: run arreau_crystal_reduce first); a rescaling of the cells
+ * to one volume; a mapping W with an entry outside {-1, 0, 1} (complete for two Delaunay-reduced cells, rule 2).
+ * Conventions as in the symmetry search: cell rows a_0, a_1, a_2, fractional columns, the metric G = L L^T, column j of W the
+ * image of basis vector j, the code of W sum (W_rc + 1) 3^(3r + c).  w_i: x's wrapped positions, v_j: y's (the screen's rule 5).
+ *   1. flags per pair.  BAD_PAIR (alone, nothing is read through the indices): an index outside its batch, or x has more atoms
+ *      than partner_stride.  NONFINITE (alone): a non-finite cell entry or coordinate in either crystal.  Else any of CELL
+ *      (either volume not positive or not finite), EMPTY (either crystal has no atoms), DIFFERENT (the atom counts differ, or
+ *      some species has another number of atoms in y than in x).  A pair with one of these five reports rms = rms_norm =
+ *      max_dist = +inf, mapping = -1, translation 0, matched = 0, partner -1 and the three counts 0.
+ *   2. lattice mappings.  Every W with entries in {-1, 0, 1} and det +-1 (det -1 included: the match is blind to handedness, as
+ *      StructureMatcher is), in code order; G' = W^T G_y W is formed as the search's rule 2 forms it, a'_j = (W_0j a_0 + W_1j a_1)
+ *      + W_2j a_2 of y's rows and G'_ij = a'_i . a'_j.  W is accepted when |sqrt(G'_ii) - sqrt(Gx_ii)| <= ltol sqrt(Gx_ii) for every
+ *      i and |angle'_i - angle^x_i| <= angle_tol for every i, angle_i = acos(G_jk / (len_j len_k)), j, k the other two axes, the
+ *      quotient clamped to [-1, 1] (the symmetrization's rule 5).  n_mappings counts every accepted W; the first max_mappings are
+ *      used, OVERFLOW when there are more; NO_MAPPING when there are none (the outputs of rule 1, n_mappings 0).
+ *   3. y in the mapped basis: v'_j = wrap(V v_j), V = W^-1 = det x adj(W), an exact integer matrix (entries up to +-2), each row
+ *      (V_r0 v_0 + V_r1 v_1) + V_r2 v_2.
+ *   4. metric of the comparison.  G_m = (G_x + G') / 2, entry by entry.  dist^2 of a fractional difference: each component minus
+ *      its nearest integer (rintf), then the smallest e G_m e^T over the 27 images e + s, s in {-1, 0, 1}^3, s_0 slowest, the first
+ *      on ties; g_r = (G_r0 e_0 + G_r1 e_1) + G_r2 e_2, e G e^T = (e_0 g_0 + e_1 g_1) + e_2 g_2, a rounded result below 0 becomes 0.
+ *      The normalisation length is l = cbrt(sqrt(det G_m) / n), det G_m expanded along its first row.
+ *   5. candidate translations.  The species of x with the fewest atoms (the smallest id on ties), its first atom p0; for every
+ *      atom q of y of that species, ascending: t = wrap(w_p0 - v'_q).  n_candidates = used mappings x atoms of that species.
+ *   6. test of (W, q).  For every atom i of x, p(i) is the atom j of y of i's species with the smallest dist^2 of (v'_j + t) - w_i,
+ *      the smallest j on ties, and e_i the difference of the image that attains it.  A candidate whose p is not one-to-one is
+ *      dropped; n_permutations counts the others.  For those t' = t - (sum_i e_i) / n, summed in atom order from 0: the
+ *      least-squares translation of that map (not wrapped); d_i^2 = dist^2 of (v'_p(i) + t') - w_i, rms = sqrt((sum_i d_i^2) / n),
+ *      max_dist = sqrt(max_i d_i^2).  Where the nearest-partner map is a permutation it is the optimal assignment.
+ *   7. result.  The candidate of the smallest rms, ties to the smaller code, then the smaller q: rms and max_dist in A, rms_norm =
+ *      rms / l, mapping = the code of W, translation = t', partner[p, i] = p(i) (local to y; -1 from x's atom count to
+ *      partner_stride), matched = (rms_norm <= stol).  NO_PERMUTATION when mappings exist and no candidate survived (the outputs
+ *      of rule 1 with n_mappings and n_candidates as counted).
+ *   8. arithmetic: as the symmetry search's rule 7 -- one float32 operation at a time, rounded to nearest, in the order written,
+ *      never contracted; divisions and square roots correctly rounded.  Only acos and cbrt come from the device library.  The
+ *      float64 restatement (arreau_amd/diffusion/structure_match.py) is compared on guarded inputs; the bounds on the reals are
+ *      derived there.
+ *   9. argument errors (ARREAU_EINVAL, nothing launched): NULL params / result / arrays, negative sizes, ltol, angle_tol or stol
+ *      not finite or not positive, max_mappings outside 1..ARREAU_SM_MAX_MAPPINGS_CAP, a partner_stride above 256 without scratch.
+ *      P = 0 is a no-op.
+ * Crystals of up to 256 atoms keep their coordinates, species and the four partner maps under test in LDS; larger ones read global
+ * memory and keep the maps in out->scratch (the same values).  Cost: n_mappings x n_rarest x n^2 x 27 metric evaluations per pair.
+ * Offsets outside [0, N] or descending are clamped as in the screen. */
+#define ARREAU_SM_NONFINITE 1
+#define ARREAU_SM_CELL 2
+#define ARREAU_SM_EMPTY 4
+#define ARREAU_SM_DIFFERENT 8
+#define ARREAU_SM_BAD_PAIR 16
+#define ARREAU_SM_NO_MAPPING 32
+#define ARREAU_SM_OVERFLOW 64
+#define ARREAU_SM_NO_PERMUTATION 128
+#define ARREAU_SM_MAX_MAPPINGS_CAP 4096
+typedef struct arreau_structure_match_params {
+    float ltol;           /* relative tolerance on the cell lengths; default 0.2 (StructureMatcher's) */
+    float angle_tol;      /* radians; default 5 degrees */
+    float stol;           /* on rms_norm; default 0.3 */
+    int32_t max_mappings; /* lattice mappings tried per pair, 1..ARREAU_SM_MAX_MAPPINGS_CAP; default 192 */
+} arreau_structure_match_params;
+typedef struct arreau_structure_match_result { /* DEVICE arrays, one row per pair */
+    float* rms;              /* [P] A */
+    float* rms_norm;         /* [P] rms / l */
+    float* max_dist;         /* [P] A */
+    int32_t* mapping;        /* [P] the code of W, -1: none */
+    float* translation;      /* [P,3] t' */
+    int32_t* partner;        /* [P, partner_stride] p(i), local to y */
+    int32_t* n_mappings;     /* [P] every accepted W, also beyond max_mappings */
+    int32_t* n_candidates;   /* [P] */
+    int32_t* n_permutations; /* [P] */
+    int32_t* matched;        /* [P] 0 / 1 */
+    int32_t* flags;          /* [P] ARREAU_SM_* */
+    int32_t* scratch;        /* [P, 4, partner_stride] the maps under test of crystals above 256 atoms; may be NULL when
+                                partner_stride <= 256 */
+    int32_t partner_stride;  /* the row width of partner: at least the atom count of every x in the pair list */
+} arreau_structure_match_result;
+/* x_* / y_*: a batch each, frac[N,3], types[N] species ids, lattice[B,3,3] rows a, b, c, offsets[B+1]; d_pairs[P,2] (x, y) indices
+ * (device).  `params` and `out` are HOST pointers. */
+int arreau_structure_match(const float* x_frac, const int32_t* x_types, const float* x_lattice, const int32_t* x_offsets, int32_t Bx,
+                           int32_t Nx, const float* y_frac, const int32_t* y_types, const float* y_lattice, const int32_t* y_offsets,
+                           int32_t By, int32_t Ny, const int32_t* d_pairs, int32_t P, const arreau_structure_match_params* params,
+                           arreau_structure_match_result* out, void* stream);
+
 /* ---- the score network ---------------------------------------------------------------------- */
 
 /* One evaluation of DiffusionLoss.predict_scores (diffusion/diffusion_loss.py:112-197):
