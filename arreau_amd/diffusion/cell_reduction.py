@@ -67,8 +67,7 @@ _SHIFTS = np.stack(np.meshgrid(*[np.arange(-1, 2)] * 3, indexing="ij"), -1).resh
 
 
 def describe(flags) -> str:
-    names = [name for bit, name in FLAG_NAMES if int(flags) & bit]
-    return "|".join(names) if names else "ok"
+    return cb.describe(flags, FLAG_NAMES)
 
 
 @dataclass(frozen=True)
@@ -123,7 +122,7 @@ def reduce_cells(frac, lattice, offsets, types, params=None):
 def result_to_numpy(result):
     """The dict of `reduce_cells` as host numpy arrays (synchronises), with the reduced crystals beside them as a ragged batch
     (crystal_batch.compact_ragged): num_atoms [B] = n_out, frac_x [sum n_out, 3], types [sum n_out], lattice [B,3,3] = lattice_out."""
-    out = {k: (v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)) for k, v in result.items()}
+    out = cb.to_numpy(result)
     _, (out["frac_x"], out["types"]) = cb.compact_ragged(out["offsets"], out["n_out"], out["frac_out"], out["types_out"])
     out["num_atoms"], out["lattice"] = out["n_out"].astype(np.int64), out["lattice_out"]
     return out
@@ -151,26 +150,11 @@ def sample_arrays(reduced, atomic_numbers=None):
     return out
 
 
-def concat_reduced(parts):
-    return {k: np.concatenate([np.asarray(p[k]) for p in parts]) for k in REDUCED_KEYS}
-
-
-def select_reduced(reduced, keep):
-    """The rows of the crystals `keep` (indices) of a REDUCED_KEYS dict."""
-    keep = np.asarray(keep, dtype=np.int64).reshape(-1)
-    num = np.asarray(reduced["num_atoms"], dtype=np.int64)
-    first = np.concatenate([[0], np.cumsum(num)])
-    atoms = np.concatenate([np.arange(first[b], first[b + 1]) for b in keep] + [np.empty(0, dtype=np.int64)]).astype(np.int64)
-    return {k: np.asarray(v)[atoms if k in PER_ATOM_KEYS else keep] for k, v in reduced.items()}
-
-
 def reduced_crystals(reduced, atomic_numbers=None):
     """The reduced crystals of a `result_to_numpy` dict as the arrays of a crystals file: frac_x and lattice float64, atomic_numbers
     (the species ids unless given), num_atoms, idx_start."""
-    num_atoms = np.asarray(reduced["num_atoms"], dtype=np.int64)
     z = (reduced["atomic_numbers"] if "atomic_numbers" in reduced else reduced["types"]) if atomic_numbers is None else atomic_numbers
-    return {"frac_x": np.asarray(reduced["frac_x"], dtype=np.float64), "lattice": np.asarray(reduced["lattice"], dtype=np.float64),
-            "atomic_numbers": np.asarray(z), "num_atoms": num_atoms, "idx_start": np.concatenate([[0], np.cumsum(num_atoms)[:-1]])}
+    return cb.crystal_arrays(reduced["frac_x"], reduced["lattice"], z, reduced["num_atoms"])
 
 
 # ------------------------------------------------------------------------------------------------------------ statistics
@@ -178,9 +162,9 @@ def stats_of(result, rank=0):
     """What the summary lines need, of one rank's (or the whole set's) arrays: the count per multiplicity and per flag."""
     m = np.asarray(result["multiplicity"], dtype=np.int64).reshape(-1)
     flags = np.asarray(result["flags"], dtype=np.int64).reshape(-1)
-    return {"rank": rank if rank == "total" else int(rank), "attempted": int(m.size), "reduced": int(((flags & COPIED_MASK) == 0).sum()),
+    return {"rank": cb.rank_of(rank), "attempted": int(m.size), "reduced": int(((flags & COPIED_MASK) == 0).sum()),
             "multiplicity": {int(k): int((m == k).sum()) for k in np.unique(m)},
-            "flags": {name: int(((flags & bit) != 0).sum()) for bit, name in FLAG_NAMES}}
+            "flags": cb.flag_counts(flags, FLAG_NAMES)}
 
 
 def total_stats(parts):
@@ -194,16 +178,13 @@ def total_stats(parts):
 
 def format_stats(st) -> str:
     """'cell reduction rank 0: reduced 16 / attempted 16; multiplicity 1: 14, 2: 2; flags none'."""
-    who = "total" if st["rank"] == "total" else f"rank {st['rank']}"
-    mult = ", ".join(f"{k}: {v}" for k, v in sorted((int(k), v) for k, v in st["multiplicity"].items()) if v) or "none"
-    flags = ", ".join(f"{k} {v}" for k, v in st["flags"].items() if v) or "none"
-    return f"cell reduction {who}: reduced {st['reduced']} / attempted {st['attempted']}; multiplicity {mult}; flags {flags}"
+    mult = cb.some(dict(sorted((int(k), v) for k, v in st["multiplicity"].items())), ": ")
+    return f"cell reduction {cb.who(st)}: reduced {st['reduced']} / attempted {st['attempted']}; multiplicity {mult}; flags {cb.some(st['flags'])}"
 
 
 def summary_lines(parts):
     """The per-rank lines and the total line of a list of stats_of dicts."""
-    parts = sorted(parts, key=lambda p: p["rank"])
-    return [format_stats(p) for p in parts] + [format_stats(total_stats(parts))]
+    return cb.summary_lines(parts, format_stats, total_stats)
 
 
 # -------------------------------------------------------------------------------------------------- the numpy restatement

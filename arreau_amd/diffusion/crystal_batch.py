@@ -1,6 +1,7 @@
-"""What the per-crystal analysis modules share (screening.py, uniqueness.py, symmetry_search.py, cell_reduction.py; their kernels share
-arreau_amd/csrc/crystal_dev.h in the same way): the check and the upload of a device batch, `resolve`, and the numpy pieces of the
-restatements.  Needs numpy alone at import; torch is imported where a device is used."""
+"""What the per-crystal analysis modules share (screening.py, uniqueness.py, symmetry_search.py, cell_reduction.py, symmetrize.py,
+structure_match.py; their kernels share arreau_amd/csrc/crystal_dev.h in the same way): the check and the upload of a device batch,
+`resolve`, the pieces of their statistics and summary lines, and the numpy pieces of the restatements.  Needs numpy alone at import;
+torch is imported where a device is used."""
 import numpy as np
 
 STAGED_ATOMS = 256  # crystals of up to this many atoms keep their per-atom data in LDS (crystal_dev.h: CRYSTAL_LDS_ATOMS)
@@ -50,6 +51,51 @@ def resolve(value, cls, name):
     if isinstance(value, cls):
         return value
     raise ValueError(f"{name} must be None, True or a {cls.__name__}, got {value!r}")
+
+
+def to_numpy(result):
+    """A dict of device tensors (and whatever else it holds) as host numpy arrays (synchronises)."""
+    return {k: (v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)) for k, v in result.items()}
+
+
+def crystal_arrays(frac_x, lattice, atomic_numbers, num_atoms):
+    """The five arrays of a crystals file: frac_x and lattice float64, atomic_numbers, num_atoms, idx_start."""
+    num_atoms = np.asarray(num_atoms, dtype=np.int64)
+    return {"frac_x": np.asarray(frac_x, dtype=np.float64), "lattice": np.asarray(lattice, dtype=np.float64),
+            "atomic_numbers": np.asarray(atomic_numbers), "num_atoms": num_atoms, "idx_start": np.concatenate([[0], np.cumsum(num_atoms)[:-1]])}
+
+
+# ---------------------------------------------------------------------------------- statistics and summary lines: the shared pieces
+def describe(flags, names) -> str:
+    """'CELL|EMPTY' for the set bits of `flags` among names ((bit, name), ...); 'ok' for none."""
+    names = [name for bit, name in names if int(flags) & bit]
+    return "|".join(names) if names else "ok"
+
+
+def rank_of(rank):
+    """The `rank` entry of a statistics dict: an int, or "total"."""
+    return rank if rank == "total" else int(rank)
+
+
+def flag_counts(flags, names):
+    """{name: crystals with that bit set} of flags [B] int64."""
+    return {name: int(((flags & bit) != 0).sum()) for bit, name in names}
+
+
+def who(st) -> str:
+    """'total' or 'rank 3': whose statistics a summary line reports."""
+    return "total" if st["rank"] == "total" else f"rank {st['rank']}"
+
+
+def some(counts, sep=" ") -> str:
+    """'CELL 2, EMPTY 1' of the non-zero entries of a {name: count} dict ('none' without any)."""
+    return ", ".join(f"{k}{sep}{v}" for k, v in counts.items() if v) or "none"
+
+
+def summary_lines(parts, format_stats, total_stats):
+    """The per-rank lines and the total line of a list of stats_of dicts."""
+    parts = sorted(parts, key=lambda p: p["rank"])
+    return [format_stats(p) for p in parts] + [format_stats(total_stats(parts))]
 
 
 def inputs(frac, lattice, counts, types):

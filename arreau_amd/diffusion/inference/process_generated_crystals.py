@@ -8,48 +8,22 @@ reference fills an `np.empty` float array), lattice [B, 3, 3] float64, idx_start
 each crystal), num_atoms [B] int64.  HDF5 when h5py is importable (it is not in this image); `.npz`
 with the same five keys otherwise.
 
-A result that carries the structural screen's metrics (SampleResult.metrics, diffusion/screening.py) gets seven more arrays,
-one entry per crystal: screen_min_distance, screen_pair [B,5], screen_n_close, screen_volume, screen_number_density,
-screen_flags, screen_valid.  Readers of the five keys above are not affected; a result without metrics is written with
-exactly those five.  A result that carries duplicate detection's arrays (SampleResult.uniqueness, diffusion/uniqueness.py) gets
-six more in the same way: unique_duplicate_of, unique_distance, unique_nearest, unique_nearest_distance, unique_flags,
-unique_unique; without them none is written.  A result that carries the symmetry search's arrays (SampleResult.symmetry,
-diffusion/symmetry_search.py) gets sym_n_lattice, sym_n_ops, sym_n_translations, sym_ops_rotation [B,max_ops], sym_ops_translation
-[B,max_ops,3], sym_ops_residual [B,max_ops], sym_residual, sym_point_group, sym_flags and sym_symprec; a reader gets them back with
-`lattice` filled in from the file's cells.  A result that carries the cell reduction's arrays (SampleResult.reduced,
-diffusion/cell_reduction.py) gets reduced_multiplicity, reduced_n_translations, reduced_lattice [B,3,3], reduced_transform [B,3,3],
-reduced_num_atoms, reduced_flags, reduced_selling_steps, reduced_symprec, and the reduced crystals' atoms reduced_frac_x [sum
-reduced_num_atoms, 3], reduced_atomic_numbers and reduced_keep.  A result that carries the symmetrization's arrays
-(SampleResult.symmetrized, diffusion/symmetrize.py) gets symmetrized_frac_x [sum n, 3], symmetrized_orbit, symmetrized_orbit_size and
-symmetrized_site_order [sum n], and per crystal symmetrized_lattice [B,3,3], symmetrized_lengths, symmetrized_angles [B,3],
-symmetrized_n_orbits, symmetrized_max_displacement, symmetrized_rms_displacement, symmetrized_ops_translation [B,max_ops,3] and
-symmetrized_flags.  A result that carries a structure match against targets (SampleResult.match,
-diffusion/structure_match.py) gets match_partner [sum n] and per crystal match_target, match_n_comparable, match_rms, match_rms_norm,
-match_max_dist, match_mapping, match_translation [B,3], match_n_mappings, match_n_candidates, match_n_permutations, match_matched and
-match_flags."""
+A result that carries an instrument's arrays (diffusion/instruments.py: SampleResult.metrics, .uniqueness, .symmetry, .reduced,
+.symmetrized, .match) gets one more array per stored key, <prefix><key>: screen_*, unique_*, sym_*, reduced_*, symmetrized_*, match_*,
+in that order, each instrument's keys in the order of its module's tuple (screening.STORED_KEYS, uniqueness.UNIQUE_KEYS,
+symmetry_search.SYM_KEYS, cell_reduction.REDUCED_KEYS, symmetrize.SYMMETRIZED_KEYS, structure_match.MATCH_KEYS; the modules say what
+each holds).  One row per crystal, except the per-atom keys: of the result's atoms [sum n] for symmetrized_* and match_*, of the
+reduced crystals' [sum reduced_num_atoms] for reduced_*.  Readers of the five keys above are not affected; a result without an
+instrument's arrays is written without them, and a reader gets back None.  A reader gets the symmetry search's arrays back with
+`lattice` filled in from the file's cells."""
 import os
 
 import numpy as np
 
 from ..diffusion_loss import SampleResult
+from ..instruments import INSTRUMENTS, file_fields
 
 KEYS = ("frac_x", "atomic_numbers", "lattice", "idx_start", "num_atoms")
-METRIC_KEYS = ("min_distance", "pair", "n_close", "volume", "number_density", "flags", "valid")
-METRIC_PREFIX = "screen_"
-UNIQUE_KEYS = ("duplicate_of", "distance", "nearest", "nearest_distance", "flags", "unique")
-UNIQUE_PREFIX = "unique_"
-SYM_KEYS = ("n_lattice", "n_ops", "n_translations", "ops_rotation", "ops_translation", "ops_residual", "residual", "point_group",
-            "flags", "symprec")
-SYM_PREFIX = "sym_"
-REDUCED_KEYS = ("multiplicity", "n_translations", "lattice", "transform", "num_atoms", "flags", "selling_steps", "symprec", "frac_x",
-                "atomic_numbers", "keep")  # cell_reduction.REDUCED_KEYS
-REDUCED_PREFIX = "reduced_"
-SYMMETRIZED_KEYS = ("frac_x", "lattice", "lengths", "angles", "orbit", "orbit_size", "site_order", "n_orbits", "max_displacement",
-                    "rms_displacement", "ops_translation", "flags")  # symmetrize.SYMMETRIZED_KEYS
-SYMMETRIZED_PREFIX = "symmetrized_"
-MATCH_KEYS = ("target", "n_comparable", "rms", "rms_norm", "max_dist", "mapping", "translation", "partner", "n_mappings", "n_candidates",
-              "n_permutations", "matched", "flags")  # structure_match.MATCH_KEYS
-MATCH_PREFIX = "match_"
 _DTYPES = dict(frac_x=np.float64, atomic_numbers=np.float64, lattice=np.float64, idx_start=np.int64,
                num_atoms=np.int64)
 
@@ -66,69 +40,21 @@ def _fields(crystals: SampleResult):
     if out["frac_x"].shape != (n_tot, 3) or out["atomic_numbers"].shape != (n_tot,) or \
             out["lattice"].shape != (B, 3, 3) or out["idx_start"].shape != (B,):
         raise ValueError("SampleResult arrays do not have the crystals.h5 layout")
-    metrics = getattr(crystals, "metrics", None)
-    if metrics is not None:
-        for k in METRIC_KEYS:
-            if k not in metrics:
-                raise ValueError(f"SampleResult.metrics[{k!r}] is missing")
-            v = np.asarray(metrics[k])
-            if v.shape != ((B, 5) if k == "pair" else (B,)):
-                raise ValueError(f"SampleResult.metrics[{k!r}] does not hold one entry per crystal")
-            out[METRIC_PREFIX + k] = v
-    uniqueness = getattr(crystals, "uniqueness", None)
-    if uniqueness is not None:
-        for k in UNIQUE_KEYS:
-            if k not in uniqueness:
-                raise ValueError(f"SampleResult.uniqueness[{k!r}] is missing")
-            v = np.asarray(uniqueness[k])
-            if v.shape != (B,):
-                raise ValueError(f"SampleResult.uniqueness[{k!r}] does not hold one entry per crystal")
-            out[UNIQUE_PREFIX + k] = v
-    symmetry = getattr(crystals, "symmetry", None)
-    if symmetry is not None:
-        for k in SYM_KEYS:
-            if k not in symmetry:
-                raise ValueError(f"SampleResult.symmetry[{k!r}] is missing")
-            v = np.asarray(symmetry[k])
-            if v.shape[:1] != (B,) or v.ndim != {"ops_rotation": 2, "ops_translation": 3, "ops_residual": 2}.get(k, 1):
-                raise ValueError(f"SampleResult.symmetry[{k!r}] does not hold one row per crystal")
-            out[SYM_PREFIX + k] = v
-    reduced = getattr(crystals, "reduced", None)
-    if reduced is not None:
-        n_red = int(np.asarray(reduced["num_atoms"]).sum()) if "num_atoms" in reduced else -1
-        for k in REDUCED_KEYS:
-            if k not in reduced:
-                raise ValueError(f"SampleResult.reduced[{k!r}] is missing")
-            v = np.asarray(reduced[k])
-            if v.shape[:1] != ((n_red,) if k in ("frac_x", "atomic_numbers", "keep") else (B,)):
-                raise ValueError(f"SampleResult.reduced[{k!r}] does not hold one row per crystal (or per reduced atom)")
-            out[REDUCED_PREFIX + k] = v
-    symmetrized = getattr(crystals, "symmetrized", None)
-    if symmetrized is not None:
-        for k in SYMMETRIZED_KEYS:
-            if k not in symmetrized:
-                raise ValueError(f"SampleResult.symmetrized[{k!r}] is missing")
-            v = np.asarray(symmetrized[k])
-            if v.shape[:1] != ((n_tot,) if k in ("frac_x", "orbit", "orbit_size", "site_order") else (B,)):
-                raise ValueError(f"SampleResult.symmetrized[{k!r}] does not hold one row per crystal (or per atom)")
-            out[SYMMETRIZED_PREFIX + k] = v
-    match = getattr(crystals, "match", None)
-    if match is not None:
-        for k in MATCH_KEYS:
-            if k not in match:
-                raise ValueError(f"SampleResult.match[{k!r}] is missing")
-            v = np.asarray(match[k])
-            if v.shape[:1] != ((n_tot,) if k == "partner" else (B,)):
-                raise ValueError(f"SampleResult.match[{k!r}] does not hold one row per crystal (or per atom)")
-            out[MATCH_PREFIX + k] = v
+    for e in INSTRUMENTS:
+        arrays = getattr(crystals, e.field, None)
+        if arrays is not None:
+            out.update(file_fields(e, arrays, B, n_tot))
     return out
 
 
-def _metrics_from(has, get, prefix=METRIC_PREFIX, keys=METRIC_KEYS):
-    """The metrics dict of a file's screen_* arrays (or the uniqueness dict of its unique_* arrays), or None when the file has none."""
-    if not all(has(prefix + k) for k in keys):
-        return None
-    return {k: get(prefix + k) for k in keys}
+def _read(has, get):
+    """The SampleResult of a file's arrays: the five keys, and every instrument's dict (None when the file lacks one of its keys)."""
+    data = {k: get(k) for k in KEYS}
+    for e in INSTRUMENTS:
+        data[e.field] = {k: get(e.prefix + k) for k in e.keys} if all(has(e.prefix + k) for k in e.keys) else None
+    if data["symmetry"] is not None:  # (the search saw the float32 cells)
+        data["symmetry"]["lattice"] = np.asarray(data["lattice"], dtype=np.float32).reshape(-1, 3, 3)
+    return SampleResult(**data)
 
 
 def _is_h5(filename):
@@ -156,26 +82,9 @@ def load_sample_results_from_hdf5(filename: str) -> SampleResult:
     if _is_h5(filename):
         import h5py
         with h5py.File(filename, "r") as fh:
-            data = {k: fh["crystals"][k][:] for k in KEYS}
-            metrics = _metrics_from(lambda k: k in fh["crystals"], lambda k: fh["crystals"][k][:])
-            uniqueness = _metrics_from(lambda k: k in fh["crystals"], lambda k: fh["crystals"][k][:], UNIQUE_PREFIX, UNIQUE_KEYS)
-            symmetry = _metrics_from(lambda k: k in fh["crystals"], lambda k: fh["crystals"][k][:], SYM_PREFIX, SYM_KEYS)
-            reduced = _metrics_from(lambda k: k in fh["crystals"], lambda k: fh["crystals"][k][:], REDUCED_PREFIX, REDUCED_KEYS)
-            symmetrized = _metrics_from(lambda k: k in fh["crystals"], lambda k: fh["crystals"][k][:], SYMMETRIZED_PREFIX, SYMMETRIZED_KEYS)
-            match = _metrics_from(lambda k: k in fh["crystals"], lambda k: fh["crystals"][k][:], MATCH_PREFIX, MATCH_KEYS)
-    else:
-        with np.load(filename) as z:
-            data = {k: z[k] for k in KEYS}
-            metrics = _metrics_from(lambda k: k in z.files, lambda k: z[k])
-            uniqueness = _metrics_from(lambda k: k in z.files, lambda k: z[k], UNIQUE_PREFIX, UNIQUE_KEYS)
-            symmetry = _metrics_from(lambda k: k in z.files, lambda k: z[k], SYM_PREFIX, SYM_KEYS)
-            reduced = _metrics_from(lambda k: k in z.files, lambda k: z[k], REDUCED_PREFIX, REDUCED_KEYS)
-            symmetrized = _metrics_from(lambda k: k in z.files, lambda k: z[k], SYMMETRIZED_PREFIX, SYMMETRIZED_KEYS)
-            match = _metrics_from(lambda k: k in z.files, lambda k: z[k], MATCH_PREFIX, MATCH_KEYS)
-    if symmetry is not None:  # (the search saw the float32 cells)
-        symmetry["lattice"] = np.asarray(data["lattice"], dtype=np.float32).reshape(-1, 3, 3)
-    return SampleResult(**data, metrics=metrics, uniqueness=uniqueness, symmetry=symmetry, reduced=reduced,
-                        symmetrized=symmetrized, match=match)
+            return _read(lambda k: k in fh["crystals"], lambda k: fh["crystals"][k][:])
+    with np.load(filename) as z:
+        return _read(lambda k: k in z.files, lambda k: z[k])
 
 
 def get_crystal_indexes(sample_result: SampleResult, sample_idx: int):

@@ -1,0 +1,98 @@
+"""The per-crystal instruments that run on the final sampled state -- screen, duplicate detection, symmetry search, cell reduction,
+symmetrization, structure match -- as one table, in the order their arrays appear in a crystals file.  An entry holds what the
+instruments differ in for the host-side plumbing: the file layer (inference/process_generated_crystals.py), the batch driver
+(generate.py) and `python -m arreau_amd.screen` loop over it.  The stored keys are the owning modules' own tuples.  Needs numpy
+alone at import, as the six modules do."""
+from dataclasses import dataclass
+from types import ModuleType
+from typing import Optional
+
+import numpy as np
+
+from . import cell_reduction, screening, structure_match, symmetrize, symmetry_search, uniqueness
+
+
+@dataclass(frozen=True)
+class Instrument:
+    keyword: str       # sample(<keyword>=...), and the command-line flag of that name
+    field: str         # SampleResult.<field>: the dict of its arrays
+    prefix: str        # its arrays in a crystals file: <prefix><key>
+    stats_key: str     # SampleResult.info[<stats_key>]: one statistics dict per rank
+    module: ModuleType  # the owner: stats_of, summary_lines, the parameter class
+    keys: tuple        # the stored keys, in file order
+    params: str        # the module's parameter class ...
+    flags: tuple       # ... and its (field, command-line flag) pairs
+    label: str         # what a bad flag value is reported under
+    atom_keys: tuple = ()  # the keys with one row per atom (the others: one row per crystal) ...
+    atoms_from: Optional[str] = None  # ... of the result's crystals, or of the instrument's own crystals with these atom counts
+    shape: object = None  # beyond the leading dimension: a trailing shape (exact), an ndim, or None for no requirement ...
+    shapes: tuple = ()    # ... and the (key, requirement) pairs that differ from it
+    carried: bool = True  # concat_results / select_crystals carry it (uniqueness indexes into the whole set: they do not)
+    stats_from: Optional[str] = None  # stats_of reads this one array (None: the dict)
+
+    def stats_of(self, arrays, rank=0):
+        return self.module.stats_of(arrays if self.stats_from is None else arrays[self.stats_from], rank)
+
+
+_SYMPREC = (("symprec", "symprec"),)
+INSTRUMENTS = (
+    Instrument("screen", "metrics", "screen_", "screen_stats", screening, screening.STORED_KEYS, "ScreenCriteria",
+               (("min_distance", "min_distance"), ("min_volume", "min_volume"), ("search_radius", "search_radius")), "screen criteria",
+               shape=(), shapes=(("pair", (5,)),), stats_from="flags"),
+    Instrument("unique", "uniqueness", "unique_", "unique_stats", uniqueness, uniqueness.UNIQUE_KEYS, "FingerprintParams",
+               (("r_max", "fp_r_max"), ("sigma", "fp_sigma"), ("tolerance", "fp_tolerance")), "fingerprint parameters",
+               shape=(), carried=False),
+    Instrument("find_symmetry", "symmetry", "sym_", "symmetry_stats", symmetry_search, symmetry_search.SYM_KEYS, "SymmetrySearchParams",
+               _SYMPREC, "symmetry search", shape=1, shapes=(("ops_rotation", 2), ("ops_translation", 3), ("ops_residual", 2))),
+    Instrument("reduce_cell", "reduced", "reduced_", "reduce_stats", cell_reduction, cell_reduction.REDUCED_KEYS, "CellReductionParams",
+               _SYMPREC, "cell reduction", atom_keys=cell_reduction.PER_ATOM_KEYS, atoms_from="num_atoms"),
+    Instrument("symmetrize", "symmetrized", "symmetrized_", "symmetrize_stats", symmetrize, symmetrize.SYMMETRIZED_KEYS,
+               "SymmetrizeParams", _SYMPREC, "symmetrize", atom_keys=symmetrize.ATOM_KEYS),
+    Instrument("match_to", "match", "match_", "match_stats", structure_match, structure_match.MATCH_KEYS, "StructureMatchParams",
+               (("ltol", "ltol"), ("angle_tol", "angle_tol"), ("stol", "stol")), "structure match", atom_keys=structure_match.ATOM_KEYS),
+)
+BY_KEYWORD = {e.keyword: e for e in INSTRUMENTS}
+
+
+def concat(entry, parts):
+    """The arrays of `parts` (one dict per piece, in crystal order) as one dict; None when a piece has none or the entry is not
+    carried.  Pieces of one run share their row widths (one max_ops)."""
+    if not entry.carried or not parts or any(p is None for p in parts):
+        return None
+    return {k: np.concatenate([np.asarray(p[k]) for p in parts]) for k in parts[0]}
+
+
+def select(entry, arrays, keep, atoms):
+    """The rows of the crystals `keep` of an entry's dict, and of their atoms: `atoms` for the result's own (both a mask or
+    indices), worked out here from the dict's own atom counts where the entry has its own crystals.  None as in `concat`."""
+    if not entry.carried or arrays is None:
+        return None
+    if entry.atoms_from is not None:
+        first = np.concatenate([[0], np.cumsum(np.asarray(arrays[entry.atoms_from], dtype=np.int64))])
+        crystals = np.arange(len(first) - 1)[np.asarray(keep)]
+        atoms = np.concatenate([np.arange(first[b], first[b + 1]) for b in crystals] + [np.empty(0, dtype=np.int64)]).astype(np.int64)
+    return {k: np.asarray(v)[atoms if k in entry.atom_keys else keep] for k, v in arrays.items()}
+
+
+def file_fields(entry, arrays, B, n_atoms):
+    """{<prefix><key>: array} of an entry's dict for a file of B crystals with n_atoms atoms; a ValueError names the key that is
+    missing or does not have its rows (one per crystal, or per atom) and its shape."""
+    if entry.atoms_from is not None:
+        n_atoms = int(np.asarray(arrays[entry.atoms_from]).sum()) if entry.atoms_from in arrays else -1
+    rules, out = dict(entry.shapes), {}
+    for k in entry.keys:
+        if k not in arrays:
+            raise ValueError(f"SampleResult.{entry.field}[{k!r}] is missing")
+        v, rule = np.asarray(arrays[k]), rules.get(k, entry.shape)
+        fits = v.shape[1:] == rule if isinstance(rule, tuple) else rule is None or v.ndim == rule
+        if v.shape[:1] != ((n_atoms if k in entry.atom_keys else B),) or not fits:
+            raise ValueError(f"SampleResult.{entry.field}[{k!r}] does not hold one entry per crystal"
+                             + (" (or per atom)" if entry.atom_keys else ""))
+        out[entry.prefix + k] = v
+    return out
+
+
+def summary_lines(entry, arrays, parts=None):
+    """The lines an instrument's flag prints: one per rank (`parts`: the statistics the ranks carried; none: `arrays` as one set)
+    and the total."""
+    return entry.module.summary_lines(parts if parts else [entry.stats_of(arrays)] if arrays is not None else [])

@@ -26,8 +26,6 @@ from typing import Optional, Sequence, Union
 
 import numpy as np
 
-from .diffusion_helpers import sample_bravais_angles
-
 # tie code per system: 0 none, 1 a = b, 2 a = b = c
 TIE_CODES = {"cubic": 2, "tetragonal": 1, "orthorhombic": 0, "hexagonal": 1, "rhombohedral": 2, "monoclinic": 0,
              "triclinic": 0}
@@ -68,6 +66,7 @@ def resolve(lattice_system: LatticeSystemArg, B: int, lattice_known=None):
     """(angles [B,3] float64, tie codes int32 [B] or None).  Validates first (`check`), then draws the angles per crystal in
     order from `sample_bravais_angles` on numpy's global generator: radians for a named system, and for None (the whole
     argument, or one crystal's entry) today's monoclinic draw in degrees, unconverted, with code 0."""
+    from .diffusion_helpers import sample_bravais_angles  # (needs torch; the names and tie codes above do not)
     names = check(lattice_system, B, lattice_known)
     if names is None:
         return np.array([sample_bravais_angles("monoclinic") for _ in range(B)]), None

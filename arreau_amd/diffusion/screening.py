@@ -47,7 +47,8 @@ FLAG_NAMES = ((NONFINITE, "NONFINITE"), (CELL, "CELL"), (CLOSE, "CLOSE"), (MASKE
 INVALID_MASK = NONFINITE | CELL | CLOSE | MASKED  # BEYOND is informational
 MAX_SHELLS = 8
 STAGED_ATOMS = cb.STAGED_ATOMS
-METRIC_KEYS = ("min_distance", "pair", "n_close", "volume", "number_density", "flags")
+METRIC_KEYS = ("min_distance", "pair", "n_close", "volume", "number_density", "flags")  # arreau_screen_result, in its order
+STORED_KEYS = METRIC_KEYS + ("valid",)  # what SampleResult.metrics and a crystals file hold
 DISTANCE_BOUND_FACTOR = 32.0
 F32 = np.float32
 
@@ -160,7 +161,7 @@ def stats_of(flags, rank=0, requested=None, rounds=None):
     """What a summary line needs: attempted, accepted and the count per flag, of one rank's attempts."""
     flags = np.asarray(flags, dtype=np.int64).reshape(-1)
     out = {"rank": int(rank), "attempted": int(flags.size), "accepted": int(is_valid(flags).sum()),
-           "flags": {name: int(((flags & bit) != 0).sum()) for bit, name in FLAG_NAMES}}
+           "flags": cb.flag_counts(flags, FLAG_NAMES)}
     if requested is not None:
         out["requested"] = int(requested)
     if rounds is not None:
@@ -177,8 +178,7 @@ def total_stats(parts):
 
 
 def format_stats(st) -> str:
-    who = "total" if st["rank"] == "total" else f"rank {st['rank']}"
-    line = f"screen {who}: accepted {st['accepted']} / attempted {st['attempted']}; " + \
+    line = f"screen {cb.who(st)}: accepted {st['accepted']} / attempted {st['attempted']}; " + \
         ", ".join(f"{name} {st['flags'][name]}" for _, name in FLAG_NAMES)
     if "requested" in st:
         line += f"; requested {st['requested']}"
@@ -191,8 +191,7 @@ def format_stats(st) -> str:
 
 def summary_lines(parts):
     """The per-rank lines and the total line of a list of stats_of dicts."""
-    parts = sorted(parts, key=lambda p: p["rank"])
-    return [format_stats(p) for p in parts] + [format_stats(total_stats(parts))]
+    return cb.summary_lines(parts, format_stats, total_stats)
 
 
 # ------------------------------------------------------------------------------------------------- the numpy restatements

@@ -65,8 +65,7 @@ F32 = np.float32
 
 
 def describe(flags) -> str:
-    names = [name for bit, name in FLAG_NAMES if int(flags) & bit]
-    return "|".join(names) if names else "ok"
+    return cb.describe(flags, FLAG_NAMES)
 
 
 @dataclass(frozen=True)
@@ -216,7 +215,7 @@ def match(x_batch, y_batch, pairs, params=None, stride=None):
 
 def result_to_numpy(result):
     """The dict of `match` as host numpy arrays (synchronises)."""
-    return {k: (v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)) for k, v in result.items()}
+    return cb.to_numpy(result)
 
 
 def per_crystal(result, pairs, counts, mode):
@@ -282,15 +281,6 @@ def sample_arrays(matched):
     return {k: np.asarray(matched[k]) for k in MATCH_KEYS}
 
 
-def concat_matches(parts):
-    return {k: np.concatenate([np.asarray(p[k]) for p in parts]) for k in MATCH_KEYS}
-
-
-def select_matches(matched, keep, atoms):
-    """The rows of the crystals `keep` and of their atoms `atoms` (indices) of a MATCH_KEYS dict."""
-    return {k: np.asarray(v)[atoms if k in ATOM_KEYS else keep] for k, v in matched.items()}
-
-
 # ------------------------------------------------------------------------------------------------------------ statistics
 def stats_of(result, rank=0):
     """What the summary lines need, of one rank's (or the whole set's) per-crystal arrays: attempted, matched, the sum of rms_norm
@@ -298,9 +288,9 @@ def stats_of(result, rank=0):
     flags = np.asarray(result["flags"], dtype=np.int64).reshape(-1)
     ok = np.asarray(result["matched"], dtype=np.int64).reshape(-1) != 0
     norm, rms = np.asarray(result["rms_norm"], dtype=np.float64).reshape(-1), np.asarray(result["rms"], dtype=np.float64).reshape(-1)
-    return {"rank": rank if rank == "total" else int(rank), "attempted": int(flags.size), "matched": int(ok.sum()),
+    return {"rank": cb.rank_of(rank), "attempted": int(flags.size), "matched": int(ok.sum()),
             "sum_rms_norm": float(norm[ok].sum()), "sum_rms": float(rms[ok].sum()),
-            "flags": {name: int(((flags & bit) != 0).sum()) for bit, name in FLAG_NAMES}}
+            "flags": cb.flag_counts(flags, FLAG_NAMES)}
 
 
 def total_stats(parts):
@@ -315,17 +305,14 @@ def match_rate(st) -> float:
 
 def format_stats(st) -> str:
     """'match rank 0: matched 14 / attempted 16 (rate 0.875); mean rms_norm 0.0412, mean rms 0.103 A; flags DIFFERENT 2'."""
-    who = "total" if st["rank"] == "total" else f"rank {st['rank']}"
-    flags = ", ".join(f"{k} {v}" for k, v in st["flags"].items() if v) or "none"
     mean = f"mean rms_norm {st['sum_rms_norm'] / st['matched']:.4g}, mean rms {st['sum_rms'] / st['matched']:.4g} A" if st["matched"] \
         else "mean rms_norm n/a"
-    return f"match {who}: matched {st['matched']} / attempted {st['attempted']} (rate {match_rate(st):.4g}); {mean}; flags {flags}"
+    return f"match {cb.who(st)}: matched {st['matched']} / attempted {st['attempted']} (rate {match_rate(st):.4g}); {mean}; flags {cb.some(st['flags'])}"
 
 
 def summary_lines(parts):
     """The per-rank lines and the total line of a list of stats_of dicts."""
-    parts = sorted(parts, key=lambda p: p["rank"])
-    return [format_stats(p) for p in parts] + [format_stats(total_stats(parts))]
+    return cb.summary_lines(parts, format_stats, total_stats)
 
 
 # ------------------------------------------------------------------------------------------------------ the derived bounds

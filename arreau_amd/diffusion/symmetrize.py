@@ -64,8 +64,7 @@ U = 2.0 ** -24
 
 
 def describe(flags) -> str:
-    names = [name for bit, name in FLAG_NAMES if int(flags) & bit]
-    return "|".join(names) if names else "ok"
+    return cb.describe(flags, FLAG_NAMES)
 
 
 @dataclass(frozen=True)
@@ -132,7 +131,7 @@ def symmetrize(frac, lattice, offsets, types, params=None, found=None):
 def result_to_numpy(result):
     """The dict of `symmetrize` as host numpy arrays (synchronises); `found` becomes the numpy dict of the search, and frac_x is
     frac_out under the name a crystals file uses."""
-    out = {k: (v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)) for k, v in result.items() if k != "found"}
+    out = cb.to_numpy({k: v for k, v in result.items() if k != "found"})
     if result.get("found") is not None:
         out["found"] = ss.result_to_numpy(result["found"])
     out["frac_x"] = out["frac_out"]
@@ -150,21 +149,10 @@ def sample_arrays(symmetrized):
     return {k: np.asarray(symmetrized[k]) for k in SYMMETRIZED_KEYS}
 
 
-def concat_symmetrized(parts):
-    return {k: np.concatenate([np.asarray(p[k]) for p in parts]) for k in SYMMETRIZED_KEYS}
-
-
-def select_symmetrized(symmetrized, keep, atoms):
-    """The rows of the crystals `keep` and of their atoms `atoms` (indices) of a SYMMETRIZED_KEYS dict."""
-    return {k: np.asarray(v)[atoms if k in ATOM_KEYS else keep] for k, v in symmetrized.items()}
-
-
 def symmetrized_crystals(symmetrized, atomic_numbers, num_atoms):
     """The symmetrized crystals as the arrays of a crystals file: frac_x and lattice float64 (the rebuilt cells), the input's
     atomic_numbers and num_atoms, idx_start."""
-    num_atoms = np.asarray(num_atoms, dtype=np.int64)
-    return {"frac_x": np.asarray(symmetrized["frac_x"], dtype=np.float64), "lattice": np.asarray(symmetrized["lattice"], dtype=np.float64),
-            "atomic_numbers": np.asarray(atomic_numbers), "num_atoms": num_atoms, "idx_start": np.concatenate([[0], np.cumsum(num_atoms)[:-1]])}
+    return cb.crystal_arrays(symmetrized["frac_x"], symmetrized["lattice"], atomic_numbers, num_atoms)
 
 
 # ------------------------------------------------------------------------------------------------------------ statistics
@@ -175,10 +163,10 @@ def stats_of(result, rank=0):
     flags = np.asarray(result["flags"], dtype=np.int64).reshape(-1)
     moved = np.asarray(result["max_displacement"], dtype=np.float64).reshape(-1)
     ok = flags == 0
-    return {"rank": rank if rank == "total" else int(rank), "attempted": int(k.size), "symmetrized": int(ok.sum()),
+    return {"rank": cb.rank_of(rank), "attempted": int(k.size), "symmetrized": int(ok.sum()),
             "n_orbits": {int(v): int((k[ok] == v).sum()) for v in np.unique(k[ok])},
             "max_displacement": float(moved[ok].max()) if ok.any() else 0.0,
-            "flags": {name: int(((flags & bit) != 0).sum()) for bit, name in FLAG_NAMES}}
+            "flags": cb.flag_counts(flags, FLAG_NAMES)}
 
 
 def total_stats(parts):
@@ -193,17 +181,14 @@ def total_stats(parts):
 
 def format_stats(st) -> str:
     """'symmetrize rank 0: symmetrized 15 / attempted 16; orbits 2: 3, 20: 12; max displacement 0.031 A; flags NO_GROUP 1'."""
-    who = "total" if st["rank"] == "total" else f"rank {st['rank']}"
-    orbits = ", ".join(f"{k}: {v}" for k, v in sorted((int(k), v) for k, v in st["n_orbits"].items()) if v) or "none"
-    flags = ", ".join(f"{k} {v}" for k, v in st["flags"].items() if v) or "none"
-    return f"symmetrize {who}: symmetrized {st['symmetrized']} / attempted {st['attempted']}; orbits {orbits}; " \
-           f"max displacement {st['max_displacement']:.3g} A; flags {flags}"
+    orbits = cb.some(dict(sorted((int(k), v) for k, v in st["n_orbits"].items())), ": ")
+    return f"symmetrize {cb.who(st)}: symmetrized {st['symmetrized']} / attempted {st['attempted']}; orbits {orbits}; " \
+           f"max displacement {st['max_displacement']:.3g} A; flags {cb.some(st['flags'])}"
 
 
 def summary_lines(parts):
     """The per-rank lines and the total line of a list of stats_of dicts."""
-    parts = sorted(parts, key=lambda p: p["rank"])
-    return [format_stats(p) for p in parts] + [format_stats(total_stats(parts))]
+    return cb.summary_lines(parts, format_stats, total_stats)
 
 
 # ------------------------------------------------------------------------------------------------------ the derived bounds

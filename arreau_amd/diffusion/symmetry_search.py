@@ -170,8 +170,7 @@ def decode_rotation(code) -> np.ndarray:
 
 
 def describe(flags) -> str:
-    names = [name for bit, name in FLAG_NAMES if int(flags) & bit]
-    return "|".join(names) if names else "ok"
+    return cb.describe(flags, FLAG_NAMES)
 
 
 @dataclass(frozen=True)
@@ -232,7 +231,7 @@ def find_symmetry(frac, lattice, offsets, types, params=None):
 
 def result_to_numpy(result):
     """The dict of `find_symmetry` as host numpy arrays (synchronises)."""
-    return {k: (v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)) for k, v in result.items()}
+    return cb.to_numpy(result)
 
 
 def symmetry_sample_result(result, params=None, device="cuda"):
@@ -301,8 +300,8 @@ def stats_of(result, rank=0):
     systems = {s: 0 for s in CRYSTAL_SYSTEMS}
     for k, name in enumerate(POINT_GROUP_NAMES):
         systems[POINT_GROUP_SYSTEMS[k]] += groups[name]
-    return {"rank": rank if rank == "total" else int(rank), "attempted": int(pg.size), "classified": int((pg >= 0).sum()),
-            "systems": systems, "point_groups": groups, "flags": {name: int(((flags & bit) != 0).sum()) for bit, name in FLAG_NAMES}}
+    return {"rank": cb.rank_of(rank), "attempted": int(pg.size), "classified": int((pg >= 0).sum()),
+            "systems": systems, "point_groups": groups, "flags": cb.flag_counts(flags, FLAG_NAMES)}
 
 
 def total_stats(parts):
@@ -314,17 +313,13 @@ def total_stats(parts):
 
 def format_stats(st) -> str:
     """'symmetry rank 0: classified 16 / attempted 16; triclinic 14, cubic 2; point groups 1: 13, -1: 1, m-3m: 2; flags none'."""
-    who = "total" if st["rank"] == "total" else f"rank {st['rank']}"
-    some = lambda d: ", ".join(f"{k} {v}" for k, v in d.items() if v) or "none"
-    groups = ", ".join(f"{k}: {v}" for k, v in st["point_groups"].items() if v) or "none"
-    return f"symmetry {who}: classified {st['classified']} / attempted {st['attempted']}; {some(st['systems'])}; " \
-           f"point groups {groups}; flags {some(st['flags'])}"
+    return f"symmetry {cb.who(st)}: classified {st['classified']} / attempted {st['attempted']}; {cb.some(st['systems'])}; " \
+           f"point groups {cb.some(st['point_groups'], ': ')}; flags {cb.some(st['flags'])}"
 
 
 def summary_lines(parts):
     """The per-rank lines and the total line of a list of stats_of dicts."""
-    parts = sorted(parts, key=lambda p: p["rank"])
-    return [format_stats(p) for p in parts] + [format_stats(total_stats(parts))]
+    return cb.summary_lines(parts, format_stats, total_stats)
 
 
 def contains_line(result, spec_or_ops) -> str:

@@ -86,8 +86,7 @@ def resolve(unique):
 
 
 def describe(flags) -> str:
-    names = [name for bit, name in FLAG_NAMES if int(flags) & bit]
-    return "|".join(names) if names else "ok"
+    return cb.describe(flags, FLAG_NAMES)
 
 
 # ------------------------------------------------------------------------------------------------------- the device calls
@@ -184,15 +183,14 @@ def stats_of(u, rank=0):
     flags, unique = np.asarray(u["flags"]).reshape(-1), np.asarray(u["unique"]).reshape(-1).astype(bool)
     nd = np.asarray(u["nearest_distance"], dtype=np.float64).reshape(-1)
     nd = nd[np.isfinite(nd)]
-    return {"rank": rank if rank == "total" else int(rank), "attempted": int(flags.size), "unique": int(unique.sum()),
+    return {"rank": cb.rank_of(rank), "attempted": int(flags.size), "unique": int(unique.sum()),
             "duplicates": int((np.asarray(u["duplicate_of"]).reshape(-1) >= 0).sum()), "flagged": int((flags != 0).sum()),
             "nearest_min": float(nd.min()) if nd.size else None, "nearest_median": float(np.median(nd)) if nd.size else None}
 
 
 def format_stats(st, word="unique") -> str:
     """'unique rank 0: unique 14 / attempted 16; duplicates 1, flagged 1; nearest_distance min 0.0012 median 0.21'."""
-    who = "total" if st["rank"] == "total" else f"rank {st['rank']}"
-    line = f"{word} {who}: {word} {st['unique']} / attempted {st['attempted']}; " \
+    line = f"{word} {cb.who(st)}: {word} {st['unique']} / attempted {st['attempted']}; " \
            f"{'duplicates' if word == 'unique' else 'matched'} {st['duplicates']}, flagged {st['flagged']}"
     if st["nearest_min"] is not None:
         line += f"; nearest_distance min {st['nearest_min']:.4g} median {st['nearest_median']:.4g}"

@@ -45,12 +45,15 @@ match rate (matched / attempted) and mean rms_norm and rms over the matched, per
 output file.  No Hungarian assignment, no supercells (combine with a reduced target file), no volume scaling.
 """
 import argparse
+import contextlib
 import os
 from typing import Callable, Optional
 
 import numpy as np
 
+from .diffusion import instruments
 from .diffusion.diffusion_loss import SampleResult
+from .diffusion.instruments import INSTRUMENTS
 
 
 def shard_range(num_items: int, world_size: int, rank: int):
@@ -61,73 +64,40 @@ def shard_range(num_items: int, world_size: int, rank: int):
 
 
 def _screen_stats(parts):
-    """The per-rank screen and uniqueness statistics the parts carry (SampleResult.info["screen_stats"] / ["unique_stats"]), each
-    in one list; None when no part has any."""
+    """The per-rank statistics the parts carry (SampleResult.info[<an instrument's stats_key>]), each in one list; None when no
+    part has any."""
     out = {}
-    for key in ("screen_stats", "unique_stats", "symmetry_stats", "reduce_stats", "symmetrize_stats", "match_stats"):
-        stats = [st for p in parts if p is not None and p.info for st in p.info.get(key, [])]
+    for e in INSTRUMENTS:
+        stats = [st for p in parts if p is not None and p.info for st in p.info.get(e.stats_key, [])]
         if stats:
-            out[key] = stats
+            out[e.stats_key] = stats
     return out or None
 
 
 def concat_results(parts) -> SampleResult:
-    """Crystal-order concatenation with the reference's index arrays (main_diffusion_generate.py:67-92).  The screen's metrics
-    are concatenated when every part has them, and the parts' screen statistics are collected."""
+    """Crystal-order concatenation with the reference's index arrays (main_diffusion_generate.py:67-92).  An instrument's arrays
+    are concatenated when every part has them (instruments.concat), and the parts' statistics are collected."""
     info = _screen_stats(parts)
     parts = [p for p in parts if p is not None and p.num_atoms is not None and len(p.num_atoms)]
     if not parts:
         return SampleResult(frac_x=np.empty((0, 3)), atomic_numbers=np.empty((0,)), lattice=np.empty((0, 3, 3)),
                             idx_start=np.empty((0,), dtype=np.int64), num_atoms=np.empty((0,), dtype=np.int64), info=info)
     num_atoms = np.concatenate([np.asarray(p.num_atoms) for p in parts])
-    metrics = None
-    if all(p.metrics is not None for p in parts):
-        metrics = {k: np.concatenate([np.asarray(p.metrics[k]) for p in parts]) for k in parts[0].metrics}
-    symmetry = None
-    if all(p.symmetry is not None for p in parts):  # (one --symprec and max_ops for the run: the rows have one width)
-        symmetry = {k: np.concatenate([np.asarray(p.symmetry[k]) for p in parts]) for k in parts[0].symmetry}
-    reduced = None
-    if all(p.reduced is not None for p in parts):
-        from .diffusion import cell_reduction
-        reduced = cell_reduction.concat_reduced([p.reduced for p in parts])
-    symmetrized = None
-    if all(p.symmetrized is not None for p in parts):  # (one max_ops for the run: the rows have one width)
-        from .diffusion import symmetrize
-        symmetrized = symmetrize.concat_symmetrized([p.symmetrized for p in parts])
-    match = None
-    if all(p.match is not None for p in parts):
-        from .diffusion import structure_match
-        match = structure_match.concat_matches([p.match for p in parts])
     return SampleResult(
         frac_x=np.concatenate([p.frac_x for p in parts]), atomic_numbers=np.concatenate([p.atomic_numbers for p in parts]),
-        lattice=np.concatenate([p.lattice for p in parts]), num_atoms=num_atoms,
-        idx_start=np.cumsum(num_atoms) - num_atoms, info=info, metrics=metrics, symmetry=symmetry, reduced=reduced,
-        symmetrized=symmetrized, match=match)
+        lattice=np.concatenate([p.lattice for p in parts]), num_atoms=num_atoms, idx_start=np.cumsum(num_atoms) - num_atoms, info=info,
+        **{e.field: instruments.concat(e, [getattr(p, e.field) for p in parts]) for e in INSTRUMENTS})
 
 
 def select_crystals(res: SampleResult, keep) -> SampleResult:
-    """The crystals of `res` where keep [B] is true, in their order (atoms, cells, metrics; idx_start rebuilt)."""
+    """The crystals of `res` where keep [B] is true, in their order (atoms, cells, the instruments' arrays; idx_start rebuilt)."""
     keep = np.asarray(keep, dtype=bool).reshape(-1)
     num_atoms = np.asarray(res.num_atoms, dtype=np.int64)
     atoms = np.repeat(keep, num_atoms)
     kept = num_atoms[keep]
-    metrics = None if res.metrics is None else {k: np.asarray(v)[keep] for k, v in res.metrics.items()}
-    symmetry = None if res.symmetry is None else {k: np.asarray(v)[keep] for k, v in res.symmetry.items()}
-    reduced = None
-    if res.reduced is not None:
-        from .diffusion import cell_reduction
-        reduced = cell_reduction.select_reduced(res.reduced, np.arange(len(res.num_atoms))[keep])
-    symmetrized = None
-    if res.symmetrized is not None:
-        from .diffusion import symmetrize
-        symmetrized = symmetrize.select_symmetrized(res.symmetrized, keep, atoms)
-    match = None
-    if res.match is not None:
-        from .diffusion import structure_match
-        match = structure_match.select_matches(res.match, keep, atoms)
     return SampleResult(frac_x=np.asarray(res.frac_x)[atoms], atomic_numbers=np.asarray(res.atomic_numbers)[atoms],
-                        lattice=np.asarray(res.lattice)[keep], num_atoms=kept, idx_start=np.cumsum(kept) - kept, metrics=metrics,
-                        symmetry=symmetry, reduced=reduced, symmetrized=symmetrized, match=match)
+                        lattice=np.asarray(res.lattice)[keep], num_atoms=kept, idx_start=np.cumsum(kept) - kept,
+                        **{e.field: instruments.select(e, getattr(res, e.field), keep, atoms) for e in INSTRUMENTS})
 
 
 FIX_KINDS = ("positions", "species", "lattice")
@@ -170,21 +140,10 @@ def template_batches(num_crystals: int, batch: int, rank: int = 0, world_size: i
 
 
 def _gather_results(local: SampleResult, rank: int, world_size: int, gather: Optional[Callable], unique=None):
-    if local.metrics is not None and not (local.info or {}).get("screen_stats"):  # a screened run: this rank's statistics
-        from .diffusion.screening import stats_of
-        local.info = dict(local.info or {}, screen_stats=[stats_of(local.metrics["flags"], rank)])
-    if local.symmetry is not None and not (local.info or {}).get("symmetry_stats"):  # a searched run: this rank's histogram
-        from .diffusion import symmetry_search
-        local.info = dict(local.info or {}, symmetry_stats=[symmetry_search.stats_of(local.symmetry, rank)])
-    if local.reduced is not None and not (local.info or {}).get("reduce_stats"):  # a reduced run: this rank's histogram
-        from .diffusion import cell_reduction
-        local.info = dict(local.info or {}, reduce_stats=[cell_reduction.stats_of(local.reduced, rank)])
-    if local.symmetrized is not None and not (local.info or {}).get("symmetrize_stats"):  # a symmetrized run: this rank's histogram
-        from .diffusion import symmetrize
-        local.info = dict(local.info or {}, symmetrize_stats=[symmetrize.stats_of(local.symmetrized, rank)])
-    if local.match is not None and not (local.info or {}).get("match_stats"):  # a matched run: this rank's rate
-        from .diffusion import structure_match
-        local.info = dict(local.info or {}, match_stats=[structure_match.stats_of(local.match, rank)])
+    for e in INSTRUMENTS:  # an instrument that ran: this rank's statistics, unless the caller has set them
+        arrays = getattr(local, e.field)
+        if e.carried and arrays is not None and not (local.info or {}).get(e.stats_key):
+            local.info = dict(local.info or {}, **{e.stats_key: [e.stats_of(arrays, rank)]})
     if unique is not None:  # duplicates within this rank's crystals, on its own device
         from .diffusion import uniqueness
         local.info = dict(local.info or {}, unique_stats=[uniqueness.stats_of(uniqueness.unique_sample_result(local, unique), rank)])
@@ -363,13 +322,22 @@ def add_structure_match_arguments(ap):
     ap.add_argument("--stol", type=float, default=0.3, help="match_to: a pair matches when rms / (V / n)^(1/3) is at most this")
 
 
-def structure_match_params(args, error):
-    """The StructureMatchParams of the tolerance flags (max_mappings the default); `error(message)` reports a bad value."""
-    from .diffusion.structure_match import StructureMatchParams
+def instrument_params(keyword, args, error):
+    """The parameters of one instrument (its sample() keyword: instruments.BY_KEYWORD) from its flags -- screen: a ScreenCriteria,
+    unique: a FingerprintParams, find_symmetry: a SymmetrySearchParams, reduce_cell: a CellReductionParams, symmetrize: a
+    SymmetrizeParams, match_to: a StructureMatchParams; what has no flag keeps its default.  `error(message)` reports a bad value."""
+    e = instruments.BY_KEYWORD[keyword]
     try:
-        return StructureMatchParams(ltol=args.ltol, angle_tol=args.angle_tol, stol=args.stol)
-    except ValueError as e:
-        error(f"structure match: {e}")
+        return getattr(e.module, e.params)(**{name: getattr(args, flag) for name, flag in e.flags})
+    except ValueError as err:
+        error(f"{e.label}: {err}")
+
+
+def instrument_lines(keyword, res, parts=None):
+    """The lines one instrument's flag prints for a result that holds its arrays: its statistics per rank (`parts`: what the ranks
+    carried; None: the result as one set) and in total."""
+    e = instruments.BY_KEYWORD[keyword]
+    return instruments.summary_lines(e, getattr(res, e.field), parts)
 
 
 def load_targets(filename, error):
@@ -381,66 +349,16 @@ def load_targets(filename, error):
         error(f"--match_to: {e}")
 
 
-def match_lines(res, parts=None):
-    """The lines `--match_to` prints for a result that holds the match's arrays: match rate, mean rms_norm and rms over the matched
-    and the flags, per rank (`parts`: the statistics the ranks carried; None: the result as one set) and in total."""
-    from .diffusion import structure_match
-    return structure_match.summary_lines(parts if parts else [structure_match.stats_of(res.match)])
-
-
 def add_symmetry_search_arguments(ap):
     """The tolerance flag of the symmetry search, the cell reduction and the symmetrization, shared with `python -m arreau_amd.screen`."""
     ap.add_argument("--symprec", type=float, default=0.1,
                     help="find_symmetry / reduce_cell / symmetrize: tolerance in A on cell lengths and atom distances (0.1: a starting value, not a claim)")
 
 
-def cell_reduction_params(args, error):
-    """The CellReductionParams of the tolerance flag; `error(message)` reports a bad value."""
-    from .diffusion.cell_reduction import CellReductionParams
-    try:
-        return CellReductionParams(symprec=args.symprec)
-    except ValueError as e:
-        error(f"cell reduction: {e}")
-
-
-def symmetrize_params(args, error):
-    """The SymmetrizeParams of the tolerance flag (max_ops the default); `error(message)` reports a bad value."""
-    from .diffusion.symmetrize import SymmetrizeParams
-    try:
-        return SymmetrizeParams(symprec=args.symprec)
-    except ValueError as e:
-        error(f"symmetrize: {e}")
-
-
-def symmetrize_lines(res, parts=None):
-    """The lines `--symmetrize` prints for a result that holds the symmetrization's arrays: the histogram of orbit counts and
-    flags and the largest displacement per rank (`parts`: the statistics the ranks carried; None: the result as one set) and in
-    total."""
-    from .diffusion import symmetrize
-    return symmetrize.summary_lines(parts if parts else [symmetrize.stats_of(res.symmetrized)])
-
-
-def reduce_lines(res, parts=None):
-    """The lines `--reduce_cell` prints for a result that holds the reduction's arrays: the histogram of multiplicities and flags
-    per rank (`parts`: the statistics the ranks carried; None: the result as one set) and in total."""
-    from .diffusion import cell_reduction
-    return cell_reduction.summary_lines(parts if parts else [cell_reduction.stats_of(res.reduced)])
-
-
-def symmetry_search_params(args, error):
-    """The SymmetrySearchParams of the symmetry-search flag; `error(message)` reports a bad value."""
-    from .diffusion.symmetry_search import SymmetrySearchParams
-    try:
-        return SymmetrySearchParams(symprec=args.symprec)
-    except ValueError as e:
-        error(f"symmetry search: {e}")
-
-
 def symmetry_lines(res, parts=None, spec=None):
-    """The lines `--find_symmetry` prints for a result that holds the search's arrays: the histogram per rank (`parts`: the
-    statistics the ranks carried; None: the result as one set) and in total, and with `spec` the crystals that contain its group."""
+    """`instrument_lines` of the symmetry search and, with `spec`, the crystals that contain its group."""
     from .diffusion import symmetry_search
-    lines = symmetry_search.summary_lines(parts if parts else [symmetry_search.stats_of(res.symmetry)])
+    lines = instrument_lines("find_symmetry", res, parts)
     if spec is not None:
         lines.append(symmetry_search.contains_line(res.symmetry, spec))
     return lines
@@ -451,15 +369,6 @@ def add_fingerprint_arguments(ap):
     ap.add_argument("--fp_r_max", type=float, default=6.0, help="unique: the fingerprint covers distances up to this many A")
     ap.add_argument("--fp_sigma", type=float, default=0.1, help="unique: Gaussian smearing of a contact, A")
     ap.add_argument("--fp_tolerance", type=float, default=0.01, help="unique: crystals of one formula within this distance (1 - cos) / 2 are duplicates")
-
-
-def fingerprint_params(args, error):
-    """The FingerprintParams of the fingerprint flags; `error(message)` reports a bad value."""
-    from .diffusion.uniqueness import FingerprintParams
-    try:
-        return FingerprintParams(r_max=args.fp_r_max, sigma=args.fp_sigma, tolerance=args.fp_tolerance)
-    except ValueError as e:
-        error(f"fingerprint parameters: {e}")
 
 
 def unique_lines(res, params, against=None, device="cuda"):
@@ -482,15 +391,6 @@ def add_screen_arguments(ap):
     ap.add_argument("--search_radius", type=float, default=3.0, help="screen: periodic images are searched out to this many A")
 
 
-def screen_criteria(args, error):
-    """The ScreenCriteria of the criteria flags; `error(message)` reports a bad value."""
-    from .diffusion.screening import ScreenCriteria
-    try:
-        return ScreenCriteria(min_distance=args.min_distance, min_volume=args.min_volume, search_radius=args.search_radius)
-    except ValueError as e:
-        error(f"screen criteria: {e}")
-
-
 def check_screen_arguments(args, error):
     """The ScreenCriteria --screen / --require_valid ask for, or None; `error(message)` reports a bad combination."""
     if args.require_valid and args.template is not None:
@@ -499,7 +399,7 @@ def check_screen_arguments(args, error):
         error("--max_rounds must be >= 1")
     if not (args.screen or args.require_valid):
         return None
-    return screen_criteria(args, error)
+    return instrument_params("screen", args, error)
 
 
 def load_symmetry(args, error):
@@ -530,6 +430,22 @@ def load_symmetry(args, error):
         error(f"--symops: {e}")
 
 
+@contextlib.contextmanager
+def _device_turn(lock_path):
+    """Ranks that SHARE one device take turns on it: the file lock is held around a sampler call and released once the device
+    has finished it."""
+    import fcntl
+
+    import torch
+    with open(lock_path, "a") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        try:
+            yield
+            torch.cuda.synchronize()
+        finally:
+            fcntl.flock(lock, fcntl.LOCK_UN)
+
+
 def _lattice_system_choices():
     from .diffusion.lattice_systems import SYSTEMS
     return SYSTEMS
@@ -540,12 +456,13 @@ def main():
     ap = build_parser()
     args = ap.parse_args()
     spec = load_symmetry(args, ap.error)
-    criteria = check_screen_arguments(args, ap.error)
-    unique = fingerprint_params(args, ap.error) if args.unique else None
-    find_sym = symmetry_search_params(args, ap.error) if args.find_symmetry else None
-    reduce_cell = cell_reduction_params(args, ap.error) if args.reduce_cell else None
-    symmetrize = symmetrize_params(args, ap.error) if args.symmetrize else None
-    match_to = (load_targets(args.match_to, ap.error), structure_match_params(args, ap.error), "any") if args.match_to else None
+    asked = {"screen": check_screen_arguments(args, ap.error)}  # per instrument, by its sample() keyword: its parameters, or None
+    for e in INSTRUMENTS[1:]:
+        asked[e.keyword] = instrument_params(e.keyword, args, ap.error) if getattr(args, e.keyword) else None
+    if args.match_to:
+        asked["match_to"] = (load_targets(args.match_to, ap.error), asked["match_to"], "any")
+    unique = asked["unique"]  # (no sample() keyword here: every rank matches its own crystals, rank 0 the whole set)
+    keywords = {k: v for k, v in asked.items() if k != "unique"}
     condition = load_template(args.template, parse_fix(args.fix)).tile(args.samples_per_template) if args.template else None
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -577,25 +494,11 @@ def main():
     lock_path = os.environ.get("ARREAU_GENERATE_GPU_LOCK")
 
     def fn(n, b, cond=None):
-        if not lock_path:
+        with _device_turn(lock_path) if lock_path else contextlib.nullcontext():
             return model.sample(n, b, VisualizationSetting.NONE, False, condition=cond, num_steps=args.num_steps,
                                 corrector_steps=args.corrector_steps, corrector_snr=args.corrector_snr,
                                 resample_passes=args.resample_passes, jump_length=args.jump_length,
-                                lattice_system=args.lattice_system, symmetry=spec, screen=criteria,
-                                find_symmetry=find_sym, reduce_cell=reduce_cell, symmetrize=symmetrize, match_to=match_to)
-        import fcntl
-        with open(lock_path, "a") as lock:
-            fcntl.flock(lock, fcntl.LOCK_EX)
-            try:
-                out = model.sample(n, b, VisualizationSetting.NONE, False, condition=cond, num_steps=args.num_steps,
-                                corrector_steps=args.corrector_steps, corrector_snr=args.corrector_snr,
-                                resample_passes=args.resample_passes, jump_length=args.jump_length,
-                                lattice_system=args.lattice_system, symmetry=spec, screen=criteria,
-                                find_symmetry=find_sym, reduce_cell=reduce_cell, symmetrize=symmetrize, match_to=match_to)
-                torch.cuda.synchronize()
-                return out
-            finally:
-                fcntl.flock(lock, fcntl.LOCK_UN)
+                                lattice_system=args.lattice_system, symmetry=spec, **keywords)
     if condition is not None:
         res = generate_from_template(lambda c: fn(None, None, c), condition, args.batch, rank, world, unique=unique)
     elif args.require_valid:
@@ -605,25 +508,13 @@ def main():
         res = generate_n_crystals(fn, args.num_crystals, spec.n_atoms if spec is not None else args.num_atoms, args.batch, rank,
                                   world, unique=unique)
     if rank == 0:
-        if criteria is not None:
-            from .diffusion.screening import summary_lines
-            for line in summary_lines((res.info or {}).get("screen_stats", [])):
-                print(line)
-        if unique is not None:
-            for line in unique_lines(res, unique, device=f"cuda:{local_rank}"):
-                print(line)
-        if find_sym is not None:
-            for line in symmetry_lines(res, (res.info or {}).get("symmetry_stats"), spec):
-                print(line)
-        if reduce_cell is not None:
-            for line in reduce_lines(res, (res.info or {}).get("reduce_stats")):
-                print(line)
-        if symmetrize is not None:
-            for line in symmetrize_lines(res, (res.info or {}).get("symmetrize_stats")):
-                print(line)
-        if match_to is not None:
-            for line in match_lines(res, (res.info or {}).get("match_stats")):
-                print(line)
+        special = {"unique": lambda parts: unique_lines(res, unique, device=f"cuda:{local_rank}"),
+                   "find_symmetry": lambda parts: symmetry_lines(res, parts, spec)}
+        for e in INSTRUMENTS:
+            if asked[e.keyword] is not None:
+                lines = special.get(e.keyword, lambda parts: instrument_lines(e.keyword, res, parts))
+                for line in lines((res.info or {}).get(e.stats_key)):
+                    print(line)
         print("wrote", save_sample_results(res, args.out))
     if world > 1:
         dist.destroy_process_group()

@@ -59,23 +59,19 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 def main(argv=None):
-    from .diffusion import screening
+    from .diffusion import cell_reduction, screening, structure_match, symmetry_search
     from .diffusion.inference.process_generated_crystals import load_sample_results_from_hdf5, save_sample_results_to_hdf5
     from .diffusion.diffusion_loss import SampleResult
-    from .generate import (cell_reduction_params, fingerprint_params, match_lines, reduce_lines, screen_criteria, structure_match_params,
-                           symmetrize_lines, symmetrize_params, symmetry_lines, symmetry_search_params, unique_lines)
+    from .diffusion.instruments import INSTRUMENTS
+    from .generate import instrument_lines, instrument_params, unique_lines
     ap = build_parser()
     args = ap.parse_args(argv)
-    criteria = screen_criteria(args, ap.error)
     if args.against is not None and not args.unique:
         ap.error("--against needs --unique")
     if args.match_mode is not None and args.match_to is None:
         ap.error("--match_mode needs --match_to")
-    unique = fingerprint_params(args, ap.error) if args.unique else None
-    find_sym = symmetry_search_params(args, ap.error) if args.find_symmetry else None
-    reduce_cell = cell_reduction_params(args, ap.error) if args.reduce_cell else None
-    symmetrize = symmetrize_params(args, ap.error) if args.symmetrize else None
-    match_params = structure_match_params(args, ap.error) if args.match_to is not None else None
+    asked = {e.keyword: instrument_params(e.keyword, args, ap.error) if getattr(args, e.keyword, True) else None
+             for e in INSTRUMENTS}  # (by sample() keyword; None: not asked for.  The screen has no flag here: it always runs)
 
     def load(name):
         try:
@@ -83,57 +79,53 @@ def main(argv=None):
         except (OSError, KeyError) as e:
             ap.error(f"{name}: {e}")
 
+    def report(keyword, crystals):
+        for line in instrument_lines(keyword, crystals):
+            print(line)
+
     res = load(args.file)
     against = load(args.against) if args.against is not None else None
     targets = load(args.match_to) if args.match_to is not None else None
-    res.metrics = screening.screen_sample_result(res, criteria, args.device)
-    for line in screening.summary_lines([screening.stats_of(res.metrics["flags"])]):
-        print(line)
-    if unique is not None:
+    res.metrics = screening.screen_sample_result(res, asked["screen"], args.device)
+    report("screen", res)
+    if asked["unique"] is not None:
         res.info = None  # (no per-rank parts: the file is one set)
-        for line in unique_lines(res, unique, against, args.device):
+        for line in unique_lines(res, asked["unique"], against, args.device):
             print(line)
-    if find_sym is not None:
-        from .diffusion import symmetry_search
-        res.symmetry = symmetry_search.symmetry_sample_result(res, find_sym, args.device)
-        for line in symmetry_lines(res):
-            print(line)
+    if asked["find_symmetry"] is not None:
+        res.symmetry = symmetry_search.symmetry_sample_result(res, asked["find_symmetry"], args.device)
+        report("find_symmetry", res)
     current = res  # the crystals the next step reads and --out writes: the file's, its reduced ones, their symmetrized ones
-    if reduce_cell is not None:
-        from .diffusion import cell_reduction
-        res.reduced = cell_reduction.sample_arrays(cell_reduction.reduce_sample_result(res, reduce_cell, args.device))
-        for line in reduce_lines(res):
-            print(line)
+    if asked["reduce_cell"] is not None:
+        reduce = lambda crystals: cell_reduction.sample_arrays(cell_reduction.reduce_sample_result(crystals, asked["reduce_cell"], args.device))
+        res.reduced = reduce(res)
+        report("reduce_cell", res)
         current = SampleResult(**cell_reduction.reduced_crystals(res.reduced), reduced=res.reduced)
         if targets is not None:
-            targets = SampleResult(**cell_reduction.reduced_crystals(
-                cell_reduction.sample_arrays(cell_reduction.reduce_sample_result(targets, reduce_cell, args.device))))
-    if symmetrize is not None:
-        current = _symmetrize(current, symmetrize, args, symmetrize_lines)
+            targets = SampleResult(**cell_reduction.reduced_crystals(reduce(targets)))
+    if asked["symmetrize"] is not None:
+        current = _symmetrize(current, asked["symmetrize"], args)
+        report("symmetrize", current)
         if targets is not None:
-            targets = _symmetrize(targets, symmetrize, args, None)
+            targets = _symmetrize(targets, asked["symmetrize"], args)
     if targets is not None:
-        from .diffusion import structure_match
         try:
-            matched = structure_match.match_crystals(current, targets, match_params, args.match_mode, args.device)
+            matched = structure_match.match_crystals(current, targets, asked["match_to"], args.match_mode, args.device)
         except ValueError as e:
             ap.error(f"--match_to: {e}")
         current.match = res.match = structure_match.sample_arrays(matched)
-        for line in match_lines(current):
-            print(line)
+        report("match_to", current)
     if args.out:
         print("wrote", save_sample_results_to_hdf5(current, args.out))
     return res
 
 
-def _symmetrize(crystals, params, args, lines):
-    """Symmetrize `crystals` (the file's, its reduced ones, or the targets of a match), print the summary (`lines`; None: nothing)
-    and return the symmetrized crystals as the SampleResult that --out writes."""
+def _symmetrize(crystals, params, args):
+    """Symmetrize `crystals` (the file's, its reduced ones, or the targets of a match; they get the arrays too) and return the
+    symmetrized crystals as the SampleResult that --out writes."""
     from .diffusion import symmetrize
     from .diffusion.diffusion_loss import SampleResult
     crystals.symmetrized = symmetrize.sample_arrays(symmetrize.symmetrize_sample_result(crystals, params, args.device))
-    for line in (lines(crystals) if lines is not None else []):
-        print(line)
     arrays = symmetrize.symmetrized_crystals(crystals.symmetrized, crystals.atomic_numbers, crystals.num_atoms)
     return SampleResult(**arrays, reduced=crystals.reduced, symmetrized=crystals.symmetrized)
 

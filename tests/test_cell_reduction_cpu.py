@@ -140,11 +140,11 @@ def test_command_line_parsers():
         flags = {s for a in parser._actions for s in a.option_strings}
         assert {"--reduce_cell", "--symprec"} <= flags
     args = screen.build_parser().parse_args(["f.npz", "--reduce_cell", "--symprec", "0.05"])
-    assert args.reduce_cell and generate.cell_reduction_params(args, None) == cr.CellReductionParams(symprec=0.05)
+    assert args.reduce_cell and generate.instrument_params("reduce_cell", args, None) == cr.CellReductionParams(symprec=0.05)
     args = generate.build_parser().parse_args(["--model_path", "m.ckpt", "--reduce_cell"]) if False else args
     errors = []
     args.symprec = -1.0
-    generate.cell_reduction_params(args, errors.append)
+    generate.instrument_params("reduce_cell", args, errors.append)
     assert errors and "cell reduction" in errors[0]
 
 

@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+from arreau_amd.diffusion import instruments
 from arreau_amd.diffusion import structure_match as sm
 from arreau_amd.diffusion.diffusion_loss import SampleResult
 from tests import structure_match_cases as cases
@@ -153,9 +154,9 @@ def test_per_crystal_reduction():
     assert out["flags"].tolist() == [0, sm.DIFFERENT, sm.NO_PERMUTATION] and out["matched"].tolist() == [1, 0, 0]
     assert out["rms"][0] == 1 and np.isinf(out["rms"][1]) and np.isinf(out["rms"][2]) and out["mapping"].tolist() == [16484, -1, 16484]
     assert out["partner"].tolist() == [0, 1, -1, -1, -1, 0] and out["translation"].shape == (3, 3) and not out["translation"][1].any()
-    kept = sm.select_matches(sm.sample_arrays(out), [0, 2], [0, 1, 5])
+    kept = instruments.select(instruments.BY_KEYWORD["match_to"], sm.sample_arrays(out), [0, 2], [0, 1, 5])
     assert kept["target"].tolist() == [2, -1] and kept["partner"].tolist() == [0, 1, 0]
-    both = sm.concat_matches([sm.sample_arrays(out), sm.sample_arrays(out)])
+    both = instruments.concat(instruments.BY_KEYWORD["match_to"], [sm.sample_arrays(out), sm.sample_arrays(out)])
     assert both["flags"].shape == (6,) and both["partner"].shape == (12,)
 
 

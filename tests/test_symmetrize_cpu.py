@@ -190,11 +190,11 @@ def test_command_line_parsers():
         flags = {s for a in parser._actions for s in a.option_strings}
         assert {"--symmetrize", "--symprec"} <= flags
     args = screen.build_parser().parse_args(["f.npz", "--symmetrize", "--reduce_cell", "--symprec", "0.05", "--out", "s.npz"])
-    assert args.symmetrize and args.reduce_cell and generate.symmetrize_params(args, None) == sz.SymmetrizeParams(symprec=0.05)
+    assert args.symmetrize and args.reduce_cell and generate.instrument_params("symmetrize", args, None) == sz.SymmetrizeParams(symprec=0.05)
     assert not screen.build_parser().parse_args(["f.npz"]).symmetrize
     errors = []
     args.symprec = -1.0
-    generate.symmetrize_params(args, errors.append)
+    generate.instrument_params("symmetrize", args, errors.append)
     assert errors and "symmetrize" in errors[0]
 
 

@@ -213,8 +213,8 @@ def test_command_line_flags():
         flags = {a for action in parser._actions for a in action.option_strings}
         assert {"--find_symmetry", "--symprec"} <= flags
     args = screen.build_parser().parse_args(["f.npz", "--find_symmetry", "--symprec", "0.05"])
-    assert generate.symmetry_search_params(args, None) == ss.SymmetrySearchParams(symprec=0.05)
+    assert generate.instrument_params("find_symmetry", args, None) == ss.SymmetrySearchParams(symprec=0.05)
     errors = []
     args.symprec = -1.0
-    generate.symmetry_search_params(args, errors.append)
+    generate.instrument_params("find_symmetry", args, errors.append)
     assert errors and "symprec" in errors[0]
