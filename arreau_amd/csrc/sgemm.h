@@ -191,7 +191,7 @@ struct SgemmEpilogue {
 // Derivative Phi(x) + x phi(x): Phi from the branch-free erf of internal.h (< 1 ulp + the 2e-7 of v_exp_f32), phi from one
 // v_exp_f32.  libm's erff / expf -- branches on |x|, about fifty instructions per element -- made a GELU epilogue cost more than
 // the launch it replaced on the 128 x 128 tiles.
-__device__ __forceinline__ float sg_gelu_exact(float x) { return gelu_fast(x); }
+__device__ __forceinline__ float sg_gelu(float x) { return gelu_fast(x); }
 __device__ __forceinline__ float sg_gelu_grad(float x) {
     return 0.5f * (1.0f + arreau_erf(x * 0.70710678118654752440f)) +
            x * 0.39894228040143267794f * __builtin_amdgcn_exp2f(-0.72134752044448170368f * x * x);
@@ -476,7 +476,7 @@ __global__ __launch_bounds__(256, 2) void sgemm_split_kernel(int M, int N, int K
                     }
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        if (epi.kind == 1) { v[r] += cv; mv[r] = sg_gelu_exact(v[r]) * rv[r]; }
+                        if (epi.kind == 1) { v[r] += cv; mv[r] = sg_gelu(v[r]) * rv[r]; }
                         else if (epi.kind == 2) v[r] = v[r] * sg_gelu_grad(mv[r]) * rv[r];
                         else { v[r] += cv; mv[r] = v[r] * c2 + mv[r]; }
                     }

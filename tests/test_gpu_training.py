@@ -18,23 +18,24 @@ TOL = 1e-5
 GRAD_TOL = 1e-4
 
 
-def make_setup(**model_args):
+def make_setup(num_atoms=(3, 5, 2, 1, 6), **model_args):
     """(model, float32 oracle, batch, lattice0, timestep, noise): a synthetic S = 12, T = 100 model (`model_args`: further
-    make_synthetic_model arguments) and a 17-atom training batch of five crystals with every random draw injected"""
+    make_synthetic_model arguments) and a training batch (17 atoms in five crystals unless `num_atoms` says otherwise, at most
+    five crystals) with every random draw injected"""
     from arreau_amd.checkpoint import make_synthetic_model
     from oracle import geometry as OG
     dev = torch.device("cuda", 0)
     m = make_synthetic_model(S=12, seed=1234, num_timesteps=100, **model_args).to(dev)
     om = oracle_from_module(m, torch.float32)
     rng = np.random.RandomState(8)
-    num_atoms = [3, 5, 2, 1, 6]
+    num_atoms = list(num_atoms)
     B, N, S = len(num_atoms), sum(num_atoms), 12
     lengths = torch.tensor(rng.uniform(3.5, 7.0, size=(B, 3)), dtype=torch.float32)
     angles = torch.tensor(np.deg2rad(rng.uniform(75, 105, size=(B, 3))), dtype=torch.float32)
     lattice0 = OG.lattice_from_params(lengths, angles)
     frac0 = torch.tensor(rng.uniform(0, 1, size=(N, 3)), dtype=torch.float32)
     types0 = torch.tensor(rng.randint(0, S - 1, size=N))
-    timestep = torch.tensor([1, 50, 100, 2, 77])
+    timestep = torch.tensor([1, 50, 100, 2, 77])[:B]
     g = torch.Generator().manual_seed(4)
     noise = (torch.randn(N, 3, generator=g), torch.rand(N, S, generator=g), torch.randn(B, 3, generator=g))
     batch = SimpleNamespace(X0=frac0, A0=types0, L0=lattice0.reshape(-1, 3), num_atoms=torch.tensor(num_atoms))
@@ -281,13 +282,21 @@ def test_merged_launches_of_the_training_step_are_bitwise_the_one_kernel_per_ope
             assert torch.equal(ga[n], gb[n]), ("merged launches changed a gradient", n, float((ga[n] - gb[n]).abs().max()))
 
 
-def test_first_training_forward_callibrates_conv_weights(setup):
+@pytest.fixture(scope="module")
+def narrow_setup():
+    """hidden 12, basis 20, widening 3, two layers; crystals of 3 and 5 atoms: three float4 columns per row"""
+    return make_setup(num_atoms=(3, 5), hidden_dim=12, basis_dim=20, widening_factor=3, layers=2)
+
+
+@pytest.mark.parametrize("which", ["setup", "narrow_setup"])
+def test_first_training_forward_callibrates_conv_weights(which, request):
     """FiberBundleConv.callibrate (conv.py:121-123,140-146): after the first training forward kernel.weight is scaled by
-    std(x) / std(x_1) and fiber_kernel.weight by std(x_1) / std(x_2) (per layer, unbiased std), once."""
+    std(x) / std(x_1) and fiber_kernel.weight by std(x_1) / std(x_2) (per layer, unbiased std), once.  The narrow model runs
+    the statistics' spherical mix at C / 4 = 3."""
     import copy
     from oracle import ponita as OP
     from oracle import sampler as OS
-    m, om, batch, lattice0, timestep, noise = setup
+    m, om, batch, lattice0, timestep, noise = request.getfixturevalue(which)
     mm = copy.deepcopy(m)
     w0 = [(l.conv.kernel.weight.detach().clone(), l.conv.fiber_kernel.weight.detach().clone()) for l in mm.model.interaction_layers]
     assert not any(bool(l.conv.callibrated) for l in mm.model.interaction_layers)
