@@ -1,7 +1,5 @@
 // arreau_predict_scores: one evaluation of the score network on the current sampler state, plus the
 // workspace carve-up and the hipEvent timing hook for the dominant (edge) kernel.
-#include <stdlib.h>
-
 #include <bit>
 #include <mutex>
 #include <vector>
@@ -146,7 +144,7 @@ extern "C" int arreau_edge_kernel_time_ms(double* mean_ms, int64_t* launches) {
 
 namespace {
 // the edge kernel, bracketed by hipEvents on its own stream when bench.py asked for its launch time
-int run_edge_kernel(const arreau_model* m, const float* dir, const float* dist, const int32_t* deg, const Workspace& w,
+int run_edge_kernel(const arreau_model* m, const ScorePlan& plan, const float* dir, const float* dist, const int32_t* deg, const Workspace& w,
                     int N, hipStream_t s) {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     bool prof = false;
@@ -159,7 +157,7 @@ int run_edge_kernel(const arreau_model* m, const float* dir, const float* dist, 
         ARREAU_CHECK_HIP(hipEventCreate(&e1));
         ARREAU_CHECK_HIP(hipEventRecord(e0, s));
     }
-    const int rc = arreau_launch_edge(m, dir, dist, deg, w.batch, w.lattice, N, w.kbuf, s);
+    const int rc = arreau_launch_edge(m, plan, dir, dist, deg, w.batch, w.lattice, N, w.kbuf, s);
     if (prof) {
         ARREAU_CHECK_HIP(hipEventRecord(e1, s));
         std::lock_guard<std::mutex> lock(g_prof.mu);
@@ -168,27 +166,29 @@ int run_edge_kernel(const arreau_model* m, const float* dir, const float* dist, 
     return rc;
 }
 
-// interaction layers (conv.py:105-129 + convnext.py:20-33) on the embedded features in w.xa, then the read-outs
-int run_layers_and_readout(const arreau_model* m, const Workspace& w, const int32_t* deg, const int32_t* src,
+// interaction layers (conv.py:105-129 + convnext.py:20-33) on the embedded features in w.xa, then the read-outs.  Every evaluation
+// on the fused kernels ends here: the one place that records its plan.
+int run_layers_and_readout(const arreau_model* m, const ScorePlan& plan, const Workspace& w, const int32_t* deg, const int32_t* src,
                            const int32_t* d_off, int B, int N, float* d_eps, float* d_logits, float* d_len0,
                            hipStream_t s) {
     int rc;
+    if (N > 0) m->ran = plan;
     float* xin = w.xa;
     float* xout = w.xb;
     for (int l = 0; l < m->L; ++l) {
-        if ((rc = arreau_launch_node_layer(m, l, w.kbuf, deg, src, xin, w.xc, xout, w.xbar, w.vsum, N, s))) return rc;
+        if ((rc = arreau_launch_node_layer(m, plan, l, w.kbuf, deg, src, xin, w.xc, xout, w.xbar, w.vsum, N, s))) return rc;
         float* tmp = xin; xin = xout; xout = tmp;
     }
-    return arreau_launch_readout(m, w.xbar, w.vsum, d_off, B, N, w.gs, d_eps, d_logits, d_len0, s);
+    return arreau_launch_readout(m, plan.readout, w.xbar, w.vsum, d_off, B, N, w.gs, d_eps, d_logits, d_len0, s);
 }
 
 // The score network after prep_kernel: neighbour list (unless given), edge kernel, embedding, interaction layers,
 // read-outs, for the whole batch on `s`.
-int run_network(const arreau_model* m, const Workspace& w, bool given, int32_t* deg, int32_t* src, float* dir, float* dist,
+int run_network(const arreau_model* m, const ScorePlan& plan, const Workspace& w, bool given, int32_t* deg, int32_t* src, float* dir, float* dist,
                 const float* d_frac, const int32_t* d_types, const int32_t* d_off, int B, int N, float* d_eps,
                 float* d_logits, float* d_len0, hipStream_t s) {
     int rc;
-    if (arreau_general_path(m)) {
+    if (plan.general) {
         // shape-general fp32 kernels (train_net.hip): any hidden_dim / basis_dim / widening, plain weights (never stale)
         arreau_model* mm = const_cast<arreau_model*>(m);  // the activation buffers are a cache owned by the model
         if (!given && (rc = arreau_launch_neighbor(w.cart, w.lattice, d_off, w.batch, B, N, m->cfg.radius, m->k, deg, src, w.cell, dir, dist, s)))
@@ -204,12 +204,12 @@ int run_network(const arreau_model* m, const Workspace& w, bool given, int32_t* 
         if ((rc = arreau_launch_neighbor_embed(m, w.cart, w.lattice, d_off, w.batch, B, N, deg, src, w.cell, dir, dist, d_frac, d_types,
                                                w.cvec, w.xa, s)))
             return rc;
-        if ((rc = run_edge_kernel(m, dir, dist, deg, w, N, s))) return rc;
+        if ((rc = run_edge_kernel(m, plan, dir, dist, deg, w, N, s))) return rc;
     } else {
-        if ((rc = run_edge_kernel(m, dir, dist, deg, w, N, s))) return rc;
+        if ((rc = run_edge_kernel(m, plan, dir, dist, deg, w, N, s))) return rc;
         if ((rc = arreau_launch_embed(m, d_frac, d_types, w.lattice, w.batch, w.cvec, N, w.xa, s))) return rc;
     }
-    return run_layers_and_readout(m, w, deg, src, d_off, B, N, d_eps, d_logits, d_len0, s);
+    return run_layers_and_readout(m, plan, w, deg, src, d_off, B, N, d_eps, d_logits, d_len0, s);
 }
 }  // namespace
 
@@ -222,7 +222,8 @@ extern "C" int arreau_predict_scores(const arreau_model* m, const float* d_frac,
     ARREAU_REQUIRE(m && d_frac && d_types && d_lengths && d_angles && d_t && d_off && d_eps && d_logits && d_len0,
                    "arreau_predict_scores: null pointer");
     ARREAU_REQUIRE(B >= 1 && N >= 0, "arreau_predict_scores: bad size");
-    ARREAU_REQUIRE(!m->packed_stale || arreau_general_path(m),
+    const ScorePlan plan = arreau_score_plan(m, N);
+    ARREAU_REQUIRE(!m->packed_stale || plan.general,
                    "arreau_predict_scores: weights were updated for training only (arreau_model_update_train_weights); "
                    "re-create the model before sampling, or select the general path (arreau_model_set_variant(model, 5, -1))");
     ARREAU_REQUIRE(d_workspace != nullptr, "arreau_predict_scores: null workspace");
@@ -242,7 +243,7 @@ extern "C" int arreau_predict_scores(const arreau_model* m, const float* d_frac,
     int rc;
     if ((rc = arreau_launch_prep(m, d_frac, d_lengths, d_angles, d_t, d_off, B, N, w.lattice, w.cart, w.batch, w.cvec, s)))
         return rc;
-    return run_network(m, w, use_given_edges != 0, deg, src, dir, dist, d_frac, d_types, d_off, B, N, d_eps, d_logits, d_len0, s);
+    return run_network(m, plan, w, use_given_edges != 0, deg, src, dir, dist, d_frac, d_types, d_off, B, N, d_eps, d_logits, d_len0, s);
 }
 
 // PonitaFiberBundle.forward on the reference's own batch attributes (the inner operator seam).
@@ -254,7 +255,8 @@ extern "C" int arreau_ponita_forward(const arreau_model* m, const float* d_x, co
     ARREAU_REQUIRE(m && d_x && d_vec && d_lattice && d_off && d_deg && d_src && d_dir && d_dist && d_logits && d_vec_out &&
                        d_global_scalar, "arreau_ponita_forward: null pointer");
     ARREAU_REQUIRE(B >= 1 && N >= 0, "arreau_ponita_forward: bad size");
-    ARREAU_REQUIRE(!m->packed_stale || arreau_general_path(m),
+    const ScorePlan plan = arreau_score_plan(m, N);
+    ARREAU_REQUIRE(!m->packed_stale || plan.general,
                    "arreau_ponita_forward: weights were updated for training only; re-create the model or select the general path");
     ARREAU_REQUIRE(d_workspace != nullptr, "arreau_ponita_forward: null workspace");
     Workspace w = carve(&m->cfg, N, B, d_workspace, workspace_bytes);
@@ -266,7 +268,7 @@ extern "C" int arreau_ponita_forward(const arreau_model* m, const float* d_x, co
     int rc;
     if ((rc = arreau_launch_batch_index(d_off, B, N, w.batch, s))) return rc;
     w.lattice = const_cast<float*>(d_lattice);  // the edge kernel reads the caller's cells (cos features, invariants.py:82-85)
-    if (arreau_general_path(m)) {
+    if (plan.general) {
         arreau_model* mm = const_cast<arreau_model*>(m);
         float* x0 = arreau_general_x0(mm, N, B, s);
         if (!x0) return ARREAU_EHIP;
@@ -274,9 +276,9 @@ extern "C" int arreau_ponita_forward(const arreau_model* m, const float* d_x, co
         return arreau_general_network(mm, arreau_graph_view{w.batch, d_deg, d_src, d_lattice, d_dir, d_dist}, d_off, B, N,
                                       d_vec_out, d_logits, d_global_scalar, s);
     }
-    if ((rc = run_edge_kernel(m, d_dir, d_dist, d_deg, w, N, s))) return rc;
+    if ((rc = run_edge_kernel(m, plan, d_dir, d_dist, d_deg, w, N, s))) return rc;
     if ((rc = arreau_launch_embed_general(m, d_x, d_vec, N, w.xa, s))) return rc;
-    return run_layers_and_readout(m, w, d_deg, d_src, d_off, B, N, d_vec_out, d_logits, d_global_scalar, s);
+    return run_layers_and_readout(m, plan, w, d_deg, d_src, d_off, B, N, d_vec_out, d_logits, d_global_scalar, s);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -288,32 +290,28 @@ __global__ void fill_i32_kernel(int32_t* __restrict__ p, int32_t v, int n) {
     if (i < n) p[i] = v;
 }
 
-// The single-stream product loop runs WITHOUT a prep launch per step (round 3) when it can: the update launch of step i
-// leaves the lattice and the per-crystal embedding of step i + 1 behind (reverse_crystal_block), the neighbour-list waves form
-// the Cartesian positions themselves and advance the device-side timestep (neighbor_embed_kernel<LOOP>), and ONE prep launch
-// in front of the loop (arreau_sample_loop) supplies the first step.  ARREAU_LOOP_PREP=1 keeps the prep launch in every step
-// (A/B, tests: the two loops are bit-identical).
-bool loop_without_prep(const arreau_model* m) {
-    const char* e = getenv("ARREAU_LOOP_PREP");
-    return !(e && atoi(e) != 0) && !arreau_general_path(m);
-}
-
+// The single-stream product loop runs WITHOUT a prep launch per step (plan.no_prep; round 3) when it can: the update launch of
+// step i leaves the lattice and the per-crystal embedding of step i + 1 behind (reverse_crystal_block), the neighbour-list waves
+// form the Cartesian positions themselves and advance the device-side timestep (neighbor_embed_kernel<LOOP>), and ONE prep launch
+// in front of the loop (arreau_sample_loop) supplies the first step.  With a prep launch in every step (A/B, tests) the loop is
+// bit-identical.
+//
 // Predictor-corrector sampling (arreau_sample_loop_corrected, opt.corr): only the first evaluation of a step advances the device
 // timestep; the later ones rebuild the neighbour list and the per-atom embedding from the moved positions at the same timestep.
 // The lattice and the per-crystal embedding stay valid: a corrector moves fractional coordinates only.
-int enqueue_sample_step(const arreau_model* m, const SampleState& st, const Workspace& w, hipStream_t s, bool no_prep, uint64_t seed,
-                        const StepOptions& opt) {
+int enqueue_sample_step(const arreau_model* m, const ScorePlan& plan, const SampleState& st, const Workspace& w, hipStream_t s,
+                        uint64_t seed, const StepOptions& opt) {
     int rc;
     const int32_t* next_t = opt.sched ? opt.sched->next : nullptr;  // respaced loop: the device timestep follows the table
     // fused kernels: the per-crystal pooling of the lattice read-out happens inside the lattice update (no launch of its own)
-    const bool pool_in_update = !arreau_general_path(m);
+    const bool pool_in_update = !plan.general;
     for (int j = 0; j <= opt.corr.steps; ++j) {
-        if (no_prep) {
+        if (plan.no_prep) {
             if ((rc = arreau_launch_neighbor_embed(m, nullptr, w.lattice, st.offsets, w.batch, st.B, st.N, w.deg, w.src, w.cell, w.dir, w.dist,
                                                    st.frac, st.types, w.cvec, w.xa, s, w.t_cur, next_t, /*advance=*/j == 0)))
                 return rc;
-            if ((rc = run_edge_kernel(m, w.dir, w.dist, w.deg, w, st.N, s))) return rc;
-            if ((rc = run_layers_and_readout(m, w, w.deg, w.src, st.offsets, st.B, st.N, w.eps, w.logits, nullptr, s))) return rc;
+            if ((rc = run_edge_kernel(m, plan, w.dir, w.dist, w.deg, w, st.N, s))) return rc;
+            if ((rc = run_layers_and_readout(m, plan, w, w.deg, w.src, st.offsets, st.B, st.N, w.eps, w.logits, nullptr, s))) return rc;
         } else {
             // the first set-up of the step advances the device timestep; a corrector's re-evaluation reads it (t_cur)
             if ((rc = j == 0 ? arreau_launch_prep(m, st.frac, st.lengths, st.angles, nullptr, st.offsets, st.B, st.N, w.lattice, w.cart, w.batch,
@@ -321,7 +319,7 @@ int enqueue_sample_step(const arreau_model* m, const SampleState& st, const Work
                              : arreau_launch_prep(m, st.frac, st.lengths, st.angles, w.t_cur, st.offsets, st.B, st.N, w.lattice, w.cart, w.batch,
                                                   w.cvec, s)))
                 return rc;
-            if ((rc = run_network(m, w, false, w.deg, w.src, w.dir, w.dist, st.frac, st.types, st.offsets, st.B, st.N, w.eps, w.logits,
+            if ((rc = run_network(m, plan, w, false, w.deg, w.src, w.dir, w.dist, st.frac, st.types, st.offsets, st.B, st.N, w.eps, w.logits,
                                   pool_in_update ? nullptr : w.len0, s)))
                 return rc;
         }
@@ -329,7 +327,7 @@ int enqueue_sample_step(const arreau_model* m, const SampleState& st, const Work
     }
     // without a prep launch per step (fused kernels only) the update also leaves the next step's lattice and embedding behind
     ReverseInputs in{w.t_cur, w.eps, w.logits, w.len0, StepNoiseSrc{.seed = seed}, pool_in_update ? w.gs : nullptr, w.batch};
-    if (no_prep) {
+    if (plan.no_prep) {
         in.lattice_ws = w.lattice;
         in.cvec_next = w.cvec;
     }
@@ -347,21 +345,17 @@ struct ResamplePlan {
     std::vector<ResampleBlock> blocks;
 };
 
-// The key of a captured step: besides the buffers, sizes and seed, which kernels it holds depends on switches read per call
-// (ARREAU_BASIS_MIN_RECEIVERS, ARREAU_FUSE_SMALL) and on the variants, and the condition's pointers, the schedule's table and
-// clip, the corrector's step count and snr, the resampling's R and J (a resampled step reads the pass word) and the lattice
-// systems' tie array and the symmetry tables are kernel arguments or launch choices of the capture: a change of any of them must
-// not replay the stale graph.
-SampleGraphKey sample_graph_key(const arreau_model* m, const SampleState& st, const void* d_workspace, uint64_t seed, bool no_prep,
+// The key of a captured step: the buffers, sizes and seed, the plan (every kernel choice of the evaluation), and the condition's
+// pointers, the schedule's table and clip, the corrector's step count and snr, the resampling's R and J (a resampled step reads
+// the pass word), the lattice systems' tie array and the symmetry tables, which are kernel arguments or launch choices of the
+// capture: a change of any of them must not replay the stale graph.
+SampleGraphKey sample_graph_key(const ScorePlan& score, const SampleState& st, const void* d_workspace, uint64_t seed,
                                 const StepOptions& opt, const ResamplePlan* plan) {
     SampleGraphKey k{};
-    k.state = st; k.workspace = d_workspace; k.seed = seed;
+    k.state = st; k.workspace = d_workspace; k.seed = seed; k.plan = score;
     if (opt.cond) k.cond = *opt.cond;
     if (opt.sym) k.sym = *opt.sym;
     k.length_tie = opt.length_tie;
-    k.edge_variant = m->edge_variant; k.mlp_variant = m->mlp_variant; k.conv_variant = m->conv_variant; k.no_prep = no_prep;
-    k.basis_form = arreau_basis_form(m, st.N); k.basis_fp8 = arreau_basis_fp8(m); k.cross_fp8 = arreau_cross_fp8(m);
-    k.small_layer_fusion = arreau_small_layer_fusable(m, st.N);
     k.scheduled = opt.sched != nullptr;
     if (opt.sched) {
         k.sched_next = opt.sched->next;
@@ -388,7 +382,8 @@ int sample_loop_impl(arreau_model* m, const SampleState& st, int32_t t_start, in
     const int B = st.B, N = st.N;
     ARREAU_REQUIRE(m && st.frac && st.types && st.lengths && st.angles && st.offsets && st.lattice, "arreau_sample_loop: null pointer");
     ARREAU_REQUIRE(B >= 1 && N >= 0 && n_steps >= 0, "arreau_sample_loop: bad size");
-    ARREAU_REQUIRE(!m->packed_stale || arreau_general_path(m),
+    const ScorePlan score = arreau_score_plan(m, N);  // of every evaluation of this call
+    ARREAU_REQUIRE(!m->packed_stale || score.general,
                    "arreau_sample_loop: weights were updated for training only; re-create the model or select the general path");
     if (schedule) {
         ARREAU_REQUIRE(schedule->d_next != nullptr, "arreau_sample_loop_scheduled: null next-timestep table");
@@ -422,8 +417,7 @@ int sample_loop_impl(arreau_model* m, const SampleState& st, int32_t t_start, in
     ARREAU_REQUIRE(!sym || (opt.cond == nullptr && opt.corr.steps == 0 && plan == nullptr),
                    "arreau_sample_loop_sym: space-group symmetry is not combined with a condition, corrector steps or resampling");
     opt.pass = plan ? w.pass : nullptr;
-    const bool no_prep = loop_without_prep(m);
-    if (no_prep) {
+    if (score.no_prep) {
         // t_cur holds the timestep of the step in progress; every step's first launch advances it, so it starts one above (in a
         // respaced loop at the table entry t_start + 1, whose successor is t_start)
         ARREAU_LAUNCH(fill_i32_kernel, dim3((B + 255) / 256), dim3(256), 0, s, w.t_cur, t_start + 1, B);
@@ -468,7 +462,7 @@ int sample_loop_impl(arreau_model* m, const SampleState& st, int32_t t_start, in
         // The executable graph is kept with the model and reused while the next call names the same buffers, sizes and seed
         // (a sampler drawing sub-batch after sub-batch through the caching allocator does): capture + instantiation, about
         // 2 ms, are then paid once.  The timestep is not part of the graph (it lives in t_next / t_cur, set above).
-        key = sample_graph_key(m, st, d_workspace, seed, no_prep, opt, plan);
+        key = sample_graph_key(score, st, d_workspace, seed, opt, plan);
         exec = (hipGraphExec_t)m->retired_graph;
         have_exec = exec && key == m->graph_key;
     }
@@ -477,11 +471,11 @@ int sample_loop_impl(arreau_model* m, const SampleState& st, int32_t t_start, in
         int r;
         if (!graph_mode || !have_exec) {
             // (eager: the first step of a capture also forces lazy module loading, which must not happen inside a capture)
-            if ((r = enqueue_sample_step(m, st, w, s, no_prep, seed, opt))) return r;
+            if ((r = enqueue_sample_step(m, score, st, w, s, seed, opt))) return r;
             if (!graph_mode) return ARREAU_OK;
             hipGraph_t graph = nullptr;
             ARREAU_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-            r = enqueue_sample_step(m, st, w, s, no_prep, seed, opt);
+            r = enqueue_sample_step(m, score, st, w, s, seed, opt);
             hipError_t e = hipStreamEndCapture(s, &graph);
             if (r) {
                 if (graph) (void)hipGraphDestroy(graph);

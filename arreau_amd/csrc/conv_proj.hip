@@ -28,7 +28,6 @@
 //   waves have drained their share of slot q+1 (hand-counted vmcnt: copies and stores retire in issue order).
 //
 // Per layer at 256 x 20: 671 MB of basis streamed under 129 GFLOP of fp16 MFMA work.
-#include <stdlib.h>
 
 #include "f16x3.h"
 
@@ -586,8 +585,8 @@ __global__ __launch_bounds__(64 * (PW + 4), (PW + 4) / 4) void conv_proj_kernel(
 }
 
 // the launcher: one persistent workgroup per CU (a multiple of 8 workgroups keeps the XCD-aware order)
-int arreau_launch_conv_proj(const arreau_model* m, int layer, const float* basis, const int32_t* deg, const int32_t* src,
-                            const float* x_in, float* x_conv, int N, hipStream_t s) {
+int arreau_launch_conv_proj(const arreau_model* m, const ScorePlan& plan, int layer, const float* basis, const int32_t* deg,
+                            const int32_t* src, const float* x_in, float* x_conv, int N, hipStream_t s) {
     if (N <= 0) return ARREAU_OK;
     if (!(m->C == 128 && m->D == 256 && m->k == 8 && m->f16_ok)) {
         arreau_set_error("conv_proj kernel: unsupported (hidden_dim, basis_dim, max_neighbors) or weights beyond the fp16 range");
@@ -602,21 +601,18 @@ int arreau_launch_conv_proj(const arreau_model* m, int layer, const float* basis
     // that starts where the previous one started finds nothing of it on the die; a pass that starts where the previous one ENDED
     // finds the last ~100-250 MB (MI355X_MICROARCH.md: a line stays while the bytes touched since its last use fit the cache).
     // The edge kernel wrote the stash front to back, so layer 0 reads it back to front, layer 1 front to back, ...  Each receiver
-    // is computed exactly as before: bit-identical.  ARREAU_CONV_PROJ_BOUSTROPHEDON=0: every pass front to back (A/B).
-    static const int bous_env = [] { const char* e = getenv("ARREAU_CONV_PROJ_BOUSTROPHEDON"); return e ? atoi(e) : 1; }();
-    const int reverse = bous_env != 0 && (layer & 1) == 0 ? 1 : 0;
+    // is computed exactly as before: bit-identical.  (!plan.boustrophedon: every pass front to back, A/B.)
+    const int reverse = plan.boustrophedon && (layer & 1) == 0 ? 1 : 0;
     const u32x4* x8w = reinterpret_cast<const u32x4*>(m->conv_x8) + (size_t)layer * (m->C / 16) * (m->D / 64) * 2 * 64;
     auto launch = [&](auto kernel, int threads) {
         ARREAU_LAUNCH(kernel, dim3(blocks), dim3(threads), 0, s, reinterpret_cast<const u32x4*>(basis), wchunks, x8w, deg, src, x_in,
                       m->fk + (size_t)layer * 16 * 16 * m->C, m->conv_bias + (size_t)layer * m->C, 0, N, x_conv, reverse);
     };
-    const bool fp8 = arreau_basis_fp8(m);
     arreau_prof_conv(0, s);
     // (round 5: the twelve-wave geometry -- eight projection waves of one tile each, ARREAU_CONV_PROJ_WAVES=8 -- is gone: it never
     // ran faster than this one)
-    m->ran_x8 = fp8 && arreau_cross_fp8(m) ? 1 : 0;
-    if (m->ran_x8) launch(conv_proj_kernel<128, 256, 4, true, true>, 512);
-    else if (fp8) launch(conv_proj_kernel<128, 256, 4, true>, 512);
+    if (plan.cross_fp8) launch(conv_proj_kernel<128, 256, 4, true, true>, 512);  // (the plan: only with the fp8 residual plane)
+    else if (plan.basis_fp8) launch(conv_proj_kernel<128, 256, 4, true>, 512);
     else launch(conv_proj_kernel<128, 256, 4, false>, 512);
     arreau_prof_conv(1, s);
     ARREAU_CHECK_HIP(hipGetLastError());

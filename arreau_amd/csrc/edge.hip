@@ -154,26 +154,16 @@ static void launch_variant(const arreau_model* m, const float* dir, const float*
                        dist, deg, batch, lattice, m->ori, m->w1p, m->b1, m->b2, m->cfg.radius, N, m->k, m->L, kbuf);
 }
 
-int arreau_launch_edge(const arreau_model* m, const float* dir, const float* dist, const int32_t* deg,
+int arreau_launch_edge(const arreau_model* m, const ScorePlan& plan, const float* dir, const float* dist, const int32_t* deg,
                        const int32_t* batch, const float* lattice, int N, float* kbuf, hipStream_t s) {
     if (N == 0) return ARREAU_OK;
     if (!(m->C == 128 && m->D == 256)) {
         arreau_set_error("edge kernel: unsupported (hidden_dim, basis_dim)");
         return ARREAU_EINVAL;
     }
-    // variant switch (default 4; the fp32-MFMA kernels stay for A/B runs and as the numerical cross-check):
-    // 0 (also 1, 2) = fp32 MFMA, 32 rows/wave, 2 waves/SIMD; 3 = bf16x6 split-precision kernel (edge_bf16.hip);
-    // 4 = fp16x3 split-precision kernel (edge_f16.hip; falls back to 3 when a weight does not fit fp16)
-    const int variant = m->edge_variant;
-    if (variant == 4 && m->f16_ok) {
-        m->ran_edge = 4;
-        return arreau_launch_edge_f16x3(m, dir, dist, deg, batch, lattice, N, kbuf, s);
-    }
-    if (variant >= 3) {
-        m->ran_edge = 3;
-        return arreau_launch_edge_bf16x6(m, dir, dist, deg, batch, lattice, N, kbuf, s);
-    }
-    m->ran_edge = 0;  // (variants 1 and 2, other wave geometries of the same fp32-MFMA kernel, were removed in round 5)
+    // (the fp32-MFMA kernel, 32 rows per wave and 2 waves per SIMD, stays for A/B runs and as the numerical cross-check)
+    if (plan.edge == ScorePlan::EDGE_F16X3) return arreau_launch_edge_f16x3(m, plan, dir, dist, deg, batch, lattice, N, kbuf, s);
+    if (plan.edge == ScorePlan::EDGE_BF16X6) return arreau_launch_edge_bf16x6(m, dir, dist, deg, batch, lattice, N, kbuf, s);
     launch_variant<1, 2>(m, dir, dist, deg, batch, lattice, N, kbuf, s);
     ARREAU_CHECK_HIP(hipGetLastError());
     return ARREAU_OK;

@@ -10,7 +10,6 @@
 // output tile: 12 / 16 / 32 KiB) are shared through a three-slot LDS ring filled by LDS-DMA
 // (global_load_lds_dwordx4): no staging registers, no ds_write, one barrier per chunk in the MIDDLE of the chunk's
 // MFMA stream ("ring protocol" below), the copy's latency covered by a whole chunk of matrix work.
-#include <stdlib.h>
 #include <utility>
 
 #include "f16x3.h"
@@ -473,8 +472,7 @@ __global__ __launch_bounds__(64 * EH_WAVES, 2) void edge_kernel_f16x3(
 // epilogues -- so the K tiles are BIT-IDENTICAL: the launcher picks the form by batch size.
 // ---------------------------------------------------------------------------------------------------------------------
 // measured on MI355X (tools/gpu_edge_split_sweep.sh): 60 / 120 / 200 / 260 / 380 receivers: 19.8 / 31.8 / 56.9 / 71.0 / 88.1 us
-// against 65.9 / 67.0 / 69.0 / 71.8 / 74.0 us of the persistent form
-#define ARREAU_EDGE_SPLIT_MAX_NODES 240
+// against 65.9 / 67.0 / 69.0 / 71.8 / 74.0 us of the persistent form: the plan takes this form up to 240 receivers (score_plan.h)
 template <int C, int D, bool BFP8>
 __global__ __launch_bounds__(512) void edge_kernel_f16x3_split(
     const float* __restrict__ nbr_dir, const float* __restrict__ nbr_dist, const int32_t* __restrict__ deg,
@@ -685,56 +683,32 @@ __global__ __launch_bounds__(512) void edge_kernel_f16x3_split(
     }
 }
 
-int arreau_launch_edge_f16x3(const arreau_model* m, const float* dir, const float* dist, const int32_t* deg,
+int arreau_launch_edge_f16x3(const arreau_model* m, const ScorePlan& plan, const float* dir, const float* dist, const int32_t* deg,
                              const int32_t* batch, const float* lattice, int N, float* kbuf, hipStream_t s) {
     if (N <= 0) return ARREAU_OK;
     if (!(m->C == 128 && m->D == 256 && m->k <= 8)) {
         arreau_set_error("edge kernel (fp16x3): unsupported (hidden_dim, basis_dim, max_neighbors)");
         return ARREAU_EINVAL;
     }
-    // 8 waves = two receivers per workgroup, one workgroup per CU (2 waves per SIMD from the same workgroup).
-    // A 4-wave / two-workgroups-per-CU geometry was tried and dropped: it was not run-to-run reproducible.
-    // Persistent: one workgroup per CU walks the receiver pairs with stride gridDim (ARREAU_EDGE_WGS overrides the
-    // workgroup count, e.g. to (N+1)/2 for one pair per workgroup).
-    static const int wgs_env = [] { const char* e = getenv("ARREAU_EDGE_WGS"); return e ? atoi(e) : 0; }();
-    // Small launches: one tile per workgroup, output chunks split over its waves (bit-identical K tiles): while the tiles
-    // are fewer than the chip's wave slots the persistent form above is one wave's latency (62 us at 1 x 8 atoms).
-    static const int split_env = [] { const char* e = getenv("ARREAU_EDGE_SPLIT"); return e ? atoi(e) : -1; }();
-    const bool split_ok = m->L * 4 >= 8 && m->L * 4 <= 24;
-    // The K tiles are bit-identical to the persistent form's on one stream.  Beside another stream's neighbour-list kernel
-    // (the withdrawn batch-slicing experiment) about one evaluation in ten came out different at the 1e-5 level, never with
-    // the persistent form; the cause is not found.  The library runs one stream.
-    const bool use_split = split_ok && !arreau_basis_form(m, N) &&
-                           (split_env >= 0 ? split_env != 0 : N <= ARREAU_EDGE_SPLIT_MAX_NODES);
-    if (use_split) {
-        auto launch = [&](auto kernel) {
-            ARREAU_LAUNCH(kernel, dim3((unsigned)N * 4), dim3(512), 0, s, dir, dist, deg, batch, lattice, m->ori,
-                               reinterpret_cast<const u32x4*>(m->edge_f16), m->b1, m->b2, m->cfg.radius, N, m->k, m->L, kbuf, 0);
-        };
-        if (arreau_basis_fp8(m)) launch(edge_kernel_f16x3_split<128, 256, true>);
-        else launch(edge_kernel_f16x3_split<128, 256, false>);
-        ARREAU_CHECK_HIP(hipGetLastError());
-        return ARREAU_OK;
-    }
-    const int npairs = (N + 1) / 2;
-    const int n_cu = arreau_cu_count();
-    const int wgs = wgs_env > 0 ? (wgs_env < npairs ? wgs_env : npairs) : (npairs < n_cu ? npairs : n_cu);
-    if (arreau_basis_form(m, N)) {  // stop after layer 2, store the basis planes (the node-layer launcher projects them)
-        if (arreau_basis_fp8(m))
-            ARREAU_LAUNCH((edge_kernel_f16x3<128, 256, 8, false, true>), dim3(wgs), dim3(512), 0, s, dir, dist, deg, batch, lattice, m->ori,
-                          reinterpret_cast<const u32x4*>(m->edge_f16), m->b1, m->b2, m->cfg.radius, N, m->k, m->L, kbuf, 0, N);
-        else
-            ARREAU_LAUNCH((edge_kernel_f16x3<128, 256, 8, false, false>), dim3(wgs), dim3(512), 0, s, dir, dist, deg, batch, lattice, m->ori,
-                          reinterpret_cast<const u32x4*>(m->edge_f16), m->b1, m->b2, m->cfg.radius, N, m->k, m->L, kbuf, 0, N);
-        ARREAU_CHECK_HIP(hipGetLastError());
-        return ARREAU_OK;
-    }
-    auto launch = [&](auto kernel) {
-        ARREAU_LAUNCH(kernel, dim3(wgs), dim3(512), 0, s, dir, dist, deg, batch, lattice, m->ori,
-                           reinterpret_cast<const u32x4*>(m->edge_f16), m->b1, m->b2, m->cfg.radius, N, m->k, m->L, kbuf, 0, N);
+    // every form takes the same arguments, the persistent ones the receiver count once more (`tail`)
+    auto launch = [&](auto kernel, unsigned workgroups, auto... tail) {
+        ARREAU_LAUNCH(kernel, dim3(workgroups), dim3(512), 0, s, dir, dist, deg, batch, lattice, m->ori,
+                      reinterpret_cast<const u32x4*>(m->edge_f16), m->b1, m->b2, m->cfg.radius, N, m->k, m->L, kbuf, 0, tail...);
     };
-    if (arreau_basis_fp8(m)) launch(edge_kernel_f16x3<128, 256, 8, true, true>);
-    else launch(edge_kernel_f16x3<128, 256, 8, true, false>);
+    const bool fp8 = plan.basis_fp8;
+    if (plan.edge_form == ScorePlan::EDGE_SPLIT) {
+        // One tile per workgroup.  The K tiles are bit-identical to the persistent form's on one stream.  Beside another stream's
+        // neighbour-list kernel (the withdrawn batch-slicing experiment) about one evaluation in ten came out different at the 1e-5
+        // level, never with the persistent form; the cause is not found.  The library runs one stream.
+        launch(fp8 ? edge_kernel_f16x3_split<128, 256, true> : edge_kernel_f16x3_split<128, 256, false>, (unsigned)N * 4);
+    } else if (plan.basis_form) {
+        // stop after layer 2, store the basis planes (the node-layer launcher projects them)
+        launch(fp8 ? edge_kernel_f16x3<128, 256, 8, false, true> : edge_kernel_f16x3<128, 256, 8, false, false>, plan.edge_wgs, N);
+    } else {
+        // 8 waves = two receivers per workgroup, one workgroup per CU (2 waves per SIMD from the same workgroup).
+        // A 4-wave / two-workgroups-per-CU geometry was tried and dropped: it was not run-to-run reproducible.
+        launch(fp8 ? edge_kernel_f16x3<128, 256, 8, true, true> : edge_kernel_f16x3<128, 256, 8, true, false>, plan.edge_wgs, N);
+    }
     ARREAU_CHECK_HIP(hipGetLastError());
     return ARREAU_OK;
 }

@@ -7,6 +7,7 @@
 #include <tuple>
 
 #include "../../include/arreau_hip.h"
+#include "score_plan.h"
 
 #define ARREAU_NUM_ATTR 6      // inv1, inv2, dist, cos a, cos b, cos c   (transforms/invariants.py:85-88)
 #define ARREAU_NUM_MONO 83     // distinct monomials of degree 1..3 in 6 variables (6 + 21 + 56)
@@ -94,8 +95,7 @@ struct SampleGraphKey {
     const int32_t* sched_next;  // respaced sampling: the next-timestep table
     const int32_t* length_tie;  // lattice systems: the per-crystal tie codes (null: untied)
     arreau_symmetry sym;      // space-group symmetry: the ten table pointers and their sizes (all zero: no symmetry)
-    // kernel choices: the variants, and the switches read per call (ARREAU_BASIS_MIN_RECEIVERS, ARREAU_FUSE_SMALL)
-    int32_t edge_variant, mlp_variant, conv_variant, no_prep, basis_form, basis_fp8, cross_fp8, small_layer_fusion;
+    ScorePlan plan;           // every kernel choice of the captured evaluation
     int32_t scheduled;
     uint32_t clip_bits;        // the schedule's lattice_clipmax
     int32_t corrector_steps;
@@ -128,9 +128,9 @@ struct arreau_model {
     int calibrating;         // 1 while that calibration runs: basis form at any launch size, formats from fp8_ok / x8_ok alone
     float edge_act_bound, node_act_bound;  // weight-derived bounds of the fp16 operands of the edge / ConvNext chains (model.hip)
     // Arithmetic / geometry variants requested for this model (defaults from ARREAU_*_VARIANT at create,
-    // arreau_model_set_variant overrides) and what the last arreau_predict_scores actually launched.
+    // arreau_model_set_variant overrides) and the plan the last evaluation of the score network executed (all zero: none yet).
     int edge_variant, mlp_variant, conv_variant, readout_variant;
-    mutable int ran_edge, ran_mlp, ran_conv, ran_x8, ran_readout;
+    mutable ScorePlan ran;
     // training (train_net.hip): plain row-major fp32 copies of the weights the sampling kernels hold only in packed
     // form, and the step's activation buffers (created on first use)
     const float *t_w1f, *t_w2, *t_wk, *t_lin1, *t_lin2, *t_ro_w;
@@ -342,12 +342,10 @@ int arreau_launch_resample_jump(const arreau_model* m, const SampleState& st, co
                                 hipStream_t stream);
 
 void arreau_train_ctx_destroy(struct arreau_train_ctx* t);
-// edge_variant value that selects the shape-general fp32 network (train_net.hip) for the whole evaluation
-#define ARREAU_VARIANT_GENERAL 5
-inline bool arreau_general_path(const arreau_model* m) { return !m->fused || m->edge_variant == ARREAU_VARIANT_GENERAL; }
 // The score network on the shape-general fp32 kernels (the training forward without its own graph construction): graph
 // arrays and the embedded features x0 [N*16][C] (null: t.x already holds them) are the caller's; outputs as
-// arreau_predict_scores.  Keeps every activation (a following arreau_train_backward is valid when keep_graph copies).
+// arreau_predict_scores.  Keeps every activation (a following arreau_train_backward is valid when keep_graph copies).  Records a
+// general plan in m->ran.
 struct arreau_graph_view {
     const int32_t *batch, *deg, *src;
     const float *lattice, *dir, *dist;
@@ -368,6 +366,13 @@ inline int arreau_cu_count() {
         return 256;
     }();
     return n_cu;
+}
+
+// The plan of one evaluation of N atoms on this model (score_plan.h); reads the environment, so once per library call.
+inline ScorePlan arreau_score_plan(const arreau_model* m, int N) {
+    return score_plan(ScorePlanInputs{m->fused, m->C, m->D, m->H, m->L, m->k, m->S, m->f16_ok, m->fp8_ok, m->x8_ok, m->calibrating,
+                                      m->edge_variant, m->mlp_variant, m->conv_variant, m->readout_variant, arreau_cu_count()},
+                      score_switches(), N);
 }
 
 // Debug aid (api.hip, "uninitialised-state probe"): when a pollution pattern is set (arreau_debug_set_pollution), every
@@ -413,40 +418,27 @@ struct ReverseInputs {
     float* cvec_next = nullptr;
 };
 int arreau_launch_reverse(const arreau_model* m, const SampleState& st, const ReverseInputs& in, const StepOptions& opt, hipStream_t s);
-int arreau_launch_edge(const arreau_model* m, const float* dir, const float* dist, const int32_t* deg,
+// The launchers below execute the plan they are given (score_plan.h); they refuse shapes their kernels do not take and launch.
+int arreau_launch_edge(const arreau_model* m, const ScorePlan& plan, const float* dir, const float* dist, const int32_t* deg,
                        const int32_t* batch, const float* lattice, int N, float* kbuf, hipStream_t s);
 int arreau_launch_edge_bf16x6(const arreau_model* m, const float* dir, const float* dist, const int32_t* deg,
                               const int32_t* batch, const float* lattice, int N, float* kbuf, hipStream_t s);
-int arreau_launch_edge_f16x3(const arreau_model* m, const float* dir, const float* dist, const int32_t* deg,
+int arreau_launch_edge_f16x3(const arreau_model* m, const ScorePlan& plan, const float* dir, const float* dist, const int32_t* deg,
                              const int32_t* batch, const float* lattice, int N, float* kbuf, hipStream_t s);
 int arreau_launch_embed(const arreau_model* m, const float* frac, const int32_t* types, const float* lattice,
                         const int32_t* batch, const float* cvec, int N, float* x0, hipStream_t s);
 int arreau_launch_embed_general(const arreau_model* m, const float* x, const float* vec, int N, float* x0, hipStream_t s);
 int arreau_launch_batch_index(const int32_t* offsets, int B, int N, int32_t* batch, hipStream_t s);
-int arreau_launch_node_layer(const arreau_model* m, int layer, const float* kbuf, const int32_t* deg,
+// kbuf: the per-layer edge kernels K [L][N*k*16][C] as fp32 -- the K pair: an edge kernel that projects in place + the streamed conv
+// kernel or the small-layer kernel, for launches too small for the basis form -- or (plan.basis_form) the stash of windowed basis
+// planes, which each layer's message kernel projects itself (conv_proj.hip).  All forms evaluate the same numbers: the basis form
+// with three fp16 cross products (!plan.cross_fp8) is bit-identical to the K pair, with the fp8 cross products close to it, not equal.
+int arreau_launch_node_layer(const arreau_model* m, const ScorePlan& plan, int layer, const float* kbuf, const int32_t* deg,
                              const int32_t* src, const float* x_in, float* x_conv, float* x_out, float* xbar,
                              float* vsum, int N, hipStream_t s);
-// ---- K stash format ------------------------------------------------------------------------------------------------
-// The per-layer edge kernels K [L][N*k*16][C] are held as fp32.  Only the K pair (an edge kernel that projects in place + the
-// streamed conv kernel or the small-layer kernel) writes and reads them, and it serves only launches too small for the basis
-// form below.  (A 3-byte float format once held this stash when the K pair ran at every size: DESIGN_HISTORY.md.)
-// Basis form (round 3, the default for launches above the small-launch sizes): the edge kernel stores the windowed basis
-// planes instead of the L projected kernels, and each layer's message kernel projects them itself (conv_proj.hip) -- no K
-// stash.  The edge launcher and the node-layer launcher take the decision from the same fields and the same receiver count.
-bool arreau_basis_form(const arreau_model* m, int receivers);
-// Numerics switch of the split-precision edge path: the residual plane of the windowed basis is rounded to fp8 e4m3 (11 + 4
-// significand bits; default) -- what the basis form stores (3 bytes per value), applied by every fp16x3 edge kernel so that all
-// launch sizes evaluate the same numbers.  Round 5: per MODEL -- arreau_model_create keeps it only if its calibration batch says the
-// outputs hardly move (model.hip: calibrate_message_formats); ARREAU_BASIS_FP8=0 / 1 in the environment overrides either way
-// (0: both planes fp16 everywhere, the round-2 arithmetic).
-bool arreau_basis_fp8(const arreau_model* m);
-// Round 4: the two cross products of the per-layer kernel projection (conv_proj.hip) on the fp8 matrix instruction (twice the fp16
-// rate; operands e4m3: model.hip, pack_conv_cross_fp8).  Applies to the basis form with the fp8 residual plane; ARREAU_CROSS_FP8=0
-// keeps three fp16 products (bit-identical to the K pair of the small launches).  Read per call (tests toggle it).
-bool arreau_cross_fp8(const arreau_model* m);
 void arreau_prof_conv(int end, hipStream_t s);  // api.hip: hipEvents around the message kernel while bench.py profiles
-int arreau_launch_conv_proj(const arreau_model* m, int layer, const float* basis, const int32_t* deg, const int32_t* src,
-                            const float* x_in, float* x_conv, int N, hipStream_t s);
+int arreau_launch_conv_proj(const arreau_model* m, const ScorePlan& plan, int layer, const float* basis, const int32_t* deg,
+                            const int32_t* src, const float* x_in, float* x_conv, int N, hipStream_t s);
 
 int arreau_launch_mlp_bf16x6(const arreau_model* m, int layer, const float* x_conv, const float* x_in, float* x_out,
                              float* xbar, float* vsum, int N, hipStream_t s);
@@ -458,13 +450,13 @@ int arreau_launch_mlp_train_forward(const arreau_model* m, int layer, const floa
                                     const float* kl = nullptr, int kl_pitch = 0, const int32_t* deg = nullptr, const int32_t* src = nullptr,
                                     const float* fk = nullptr, float* x1 = nullptr);
 int arreau_repack_mlp_f16x3_m16(arreau_model* m, hipStream_t s);
-int arreau_launch_mlp_f16x3_m16(const arreau_model* m, int layer, const float* x_conv, const float* x_in, float* x_out,
-                                float* xbar, float* vsum, int N, hipStream_t s);
+// the tile form: nb nodes per wave, a weight ring of `slots` chunks (plan.mlp_nb, plan.mlp_slots)
+int arreau_launch_mlp_f16x3_m16(const arreau_model* m, int nb, int slots, int layer, const float* x_conv, const float* x_in,
+                                float* x_out, float* xbar, float* vsum, int N, hipStream_t s);
 // one launch per layer for small launches (node_f16m.hip): conv_kernel_streamed<128> + the split MLP form
-bool arreau_small_layer_fusable(const arreau_model* m, int N);
 int arreau_launch_small_layer(const arreau_model* m, int layer, const float* kbuf, const int32_t* deg, const int32_t* src,
                               const float* x_in, float* x_out, float* xbar, float* vsum, int Ntot, hipStream_t s);
 int arreau_launch_mlp_f16x3_m16_split(const arreau_model* m, int layer, const float* x_conv, const float* x_in, float* x_out,
                                       float* xbar, float* vsum, int N, hipStream_t s);
-int arreau_launch_readout(const arreau_model* m, const float* xbar, const float* vsum, const int32_t* offsets,
-                          int B, int N, float* gs, float* eps, float* logits, float* len0, hipStream_t s);
+int arreau_launch_readout(const arreau_model* m, ScorePlan::Readout kernel, const float* xbar, const float* vsum,
+                          const int32_t* offsets, int B, int N, float* gs, float* eps, float* logits, float* len0, hipStream_t s);

@@ -372,8 +372,7 @@ static int calibrate_message_formats(arreau_model* m, hipStream_t s) {
     }
     (void)hipStreamSynchronize(s);
     (void)hipFree(dev);
-    m->ran_edge = m->ran_mlp = m->ran_conv = m->ran_readout = -1;
-    m->ran_x8 = 0;
+    m->ran = ScorePlan{};
     if (rc != ARREAU_OK) { arreau_set_error(std::string("format calibration: ") + arreau_last_error()); return rc; }
     (void)flags;
     auto finite = [&](int v) {
@@ -695,8 +694,7 @@ extern "C" int arreau_model_create(const arreau_config* cfg, const arreau_state_
     m->train_full_range = edge_bound > f16_slack || node_bound > f16_slack ? 1 : 0;
     m->conv_variant = env_int("ARREAU_CONV_VARIANT", 2);  // 2: basis form + conv_proj.hip; 1: K stash + streamed conv; 0: register conv
     m->readout_variant = env_int("ARREAU_READOUT_VARIANT", 1);
-    m->ran_edge = m->ran_mlp = m->ran_conv = m->ran_readout = -1;
-    m->ran_x8 = 0;
+    m->ran = ScorePlan{};
     m->fused = fused ? 1 : 0;
     // ARREAU_GENERAL_PATH=1 (or edge variant 5): run the shape-general fp32 kernels also for the fused shape (cross-check)
     if (!fused || getenv("ARREAU_GENERAL_PATH")) m->edge_variant = ARREAU_VARIANT_GENERAL;
@@ -782,12 +780,13 @@ extern "C" int arreau_model_status(const arreau_model* model, arreau_status* out
     if (reset) ARREAU_CHECK_HIP(hipMemsetAsync(model->status, 0, sizeof(int32_t), s));
     ARREAU_CHECK_HIP(hipStreamSynchronize(s));
     out->flags = flags;
-    out->edge_kernel = model->ran_edge;
-    out->mlp_kernel = model->ran_mlp;
-    out->conv_kernel = model->ran_conv;
-    out->readout_kernel = model->ran_readout;
-    out->basis_row_bytes = model->ran_conv == 2 ? (arreau_basis_fp8(model) ? 768 : 1024) : 0;
-    out->conv_cross_fp8 = model->ran_conv == 2 ? model->ran_x8 : 0;
+    const ScorePlanCodes ran = score_plan_codes(model->ran);  // what the last evaluation executed
+    out->edge_kernel = ran.edge_kernel;
+    out->mlp_kernel = ran.mlp_kernel;
+    out->conv_kernel = ran.conv_kernel;
+    out->readout_kernel = ran.readout_kernel;
+    out->basis_row_bytes = ran.basis_row_bytes;
+    out->conv_cross_fp8 = ran.conv_cross_fp8;
     out->edge_activation_bound = model->edge_act_bound;
     out->node_activation_bound = model->node_act_bound;
     out->basis_fp8_share = model->calib_fp8;

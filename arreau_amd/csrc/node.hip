@@ -1,6 +1,5 @@
 // Node-side kernels of the score network: feature assembly + embedding, the per-layer
 // message/spherical-conv/ConvNext update, and the read-outs.
-#include <stdlib.h>
 
 #include "internal.h"
 #include "readout_dev.h"
@@ -616,7 +615,7 @@ __global__ __launch_bounds__(256, 2) void mlp_kernel(
     }
 }
 
-int arreau_launch_node_layer(const arreau_model* m, int layer, const float* kbuf, const int32_t* deg,
+int arreau_launch_node_layer(const arreau_model* m, const ScorePlan& plan, int layer, const float* kbuf, const int32_t* deg,
                              const int32_t* src, const float* x_in, float* x_conv, float* x_out, float* xbar,
                              float* vsum, int N, hipStream_t s) {
     if (N <= 0) return ARREAU_OK;
@@ -628,42 +627,31 @@ int arreau_launch_node_layer(const arreau_model* m, int layer, const float* kbuf
     const size_t layer_stride = (size_t)N * m->k * 16 * C;
     const size_t mlp_layer = (size_t)2 * H * C;  // floats of W1 + W2, packed
     const int conv_blocks = N < 512 ? N : 512;   // persistent: 2 workgroups of 512 threads per CU (a multiple of 8: XCD-aware order)
-    // conv variant: 1 (default, k = 8 only) = streamed form (K blocks by LDS-DMA, one workgroup per CU); 0 = register form
-    const bool basis_form = arreau_basis_form(m, N);
-    const int conv_variant = m->conv_variant == 2 ? 1 : m->conv_variant;  // (2 without the basis form = the streamed K pair)
-    m->ran_conv = basis_form ? 2 : (conv_variant == 1 && m->k == 8) ? 1 : 0;
-    if (arreau_small_layer_fusable(m, N)) {  // small launch: both halves of the layer in one kernel (bit-identical)
-        m->ran_mlp = 3;
+    switch (plan.message) {
+    case ScorePlan::MSG_IN_SMALL_LAYER:  // small launch: both halves of the layer in one kernel (bit-identical)
         return arreau_launch_small_layer(m, layer, kbuf, deg, src, x_in, x_out, xbar, vsum, N, s);
-    }
-    if (basis_form) {
-        const int rc = arreau_launch_conv_proj(m, layer, kbuf, deg, src, x_in, x_conv, N, s);
+    case ScorePlan::MSG_BASIS_PROJ: {
+        const int rc = arreau_launch_conv_proj(m, plan, layer, kbuf, deg, src, x_in, x_conv, N, s);
         if (rc) return rc;
-    } else if (conv_variant == 1 && m->k == 8) {
+        break;
+    }
+    case ScorePlan::MSG_STREAMED:  // K blocks by LDS-DMA, one workgroup per CU (k = 8 only)
         ARREAU_LAUNCH((conv_kernel_streamed<128>), dim3(N < 256 ? N : 256), dim3(512), 0, s, kbuf + (size_t)layer * layer_stride, deg,
                                src, x_in, m->fk + (size_t)layer * 16 * 16 * C, m->conv_bias + (size_t)layer * C, 0, N, x_conv);
-    } else {
+        break;
+    case ScorePlan::MSG_REGISTER:
         ARREAU_LAUNCH((conv_kernel<128>), dim3(conv_blocks), dim3(512), 0, s, kbuf + (size_t)layer * layer_stride,
                            deg, src, x_in, m->fk + (size_t)layer * 16 * 16 * C, m->conv_bias + (size_t)layer * C, 0, N, m->k, x_conv);
+        break;
     }
     ARREAU_CHECK_HIP(hipGetLastError());
-    // variant switch: 3 (default) = fp16x3 on 16x16x32 MFMAs (node_f16m.hip; needs weights that fit fp16); 1 = bf16x6 split-precision
-    // MLP kernel (node_bf16.hip); 0 = fp32-MFMA kernel below  (2, the same arithmetic on 32x32x16 MFMAs, was removed in round 5)
-    // 4 = always the small-launch form of 3 (one node per workgroup, node_f16m.hip: bit-identical; 3 picks it by size)
-    const int mlp_variant = m->mlp_variant;
-    if (mlp_variant == 4 && m->f16_ok) {
-        m->ran_mlp = 3;
-        return arreau_launch_mlp_f16x3_m16_split(m, layer, x_conv, x_in, x_out, xbar, vsum, N, s);
+    switch (plan.mlp) {
+    case ScorePlan::MLP_F16X3_SPLIT: return arreau_launch_mlp_f16x3_m16_split(m, layer, x_conv, x_in, x_out, xbar, vsum, N, s);
+    case ScorePlan::MLP_F16X3_TILE:
+        return arreau_launch_mlp_f16x3_m16(m, plan.mlp_nb, plan.mlp_slots, layer, x_conv, x_in, x_out, xbar, vsum, N, s);
+    case ScorePlan::MLP_BF16X6: return arreau_launch_mlp_bf16x6(m, layer, x_conv, x_in, x_out, xbar, vsum, N, s);
+    default: break;  // MLP_FP32: mlp_kernel of this file
     }
-    if (mlp_variant == 3 && m->f16_ok) {
-        m->ran_mlp = 3;
-        return arreau_launch_mlp_f16x3_m16(m, layer, x_conv, x_in, x_out, xbar, vsum, N, s);
-    }
-    if (mlp_variant >= 1) {
-        m->ran_mlp = 1;
-        return arreau_launch_mlp_bf16x6(m, layer, x_conv, x_in, x_out, xbar, vsum, N, s);
-    }
-    m->ran_mlp = 0;
     ARREAU_LAUNCH((mlp_kernel<128, 512>), dim3((N + 3) / 4), dim3(256), 0, s, x_conv, x_in, x_out,
                        m->ln_w + (size_t)layer * C, m->ln_b + (size_t)layer * C, m->mlp + (size_t)layer * mlp_layer,
                        m->mb1 + (size_t)layer * H, m->mb2 + (size_t)layer * C, m->ls + (size_t)layer * C,
@@ -795,33 +783,8 @@ __global__ void readout_crystals_kernel(const float* __restrict__ gs, const int3
     len0[idx] = acc;
 }
 
-// conv_variant 2 (default): basis form wherever it applies -- the fused shape, k = 8, fp16-representable weights, the
-// split-precision edge kernel -- and a launch large enough for it to pay: measured at n = 20 (graph replay, one box), the
-// basis form against the K pair on fp32 K: 960 receivers 0.436 / 0.421 ms per step, 1920: 0.655 / 0.656, 2560: 0.852 /
-// 0.870, 3520: 1.059 / 1.078, 5120: 1.35 / 1.48 -- so it takes over from 2,000 receivers (ARREAU_BASIS_MIN_RECEIVERS
-// moves the switch: the tests set 240 to run the basis form on small batches).  Below that the K pair runs on an fp32 K
-// buffer (and at most 240 receivers: the tile-per-workgroup kernels); all of them evaluate the same numbers.
-bool arreau_basis_form(const arreau_model* m, int receivers) {
-    const char* e = getenv("ARREAU_BASIS_MIN_RECEIVERS");
-    const int min_receivers = e ? atoi(e) : 2000;
-    // (L >= 2: the stash -- 96 or 128 KiB per atom -- lives in the workspace region sized for L per-layer K buffers of 64 KiB per atom)
-    return m->conv_variant == 2 && m->edge_variant == 4 && m->f16_ok && m->k == 8 && m->C == 128 && m->D == 256 && m->L >= 2 &&
-           receivers > (min_receivers > 240 && !m->calibrating ? min_receivers : 240);
-}
-
-bool arreau_basis_fp8(const arreau_model* m) {
-    static const int env = [] { const char* e = getenv("ARREAU_BASIS_FP8"); return e ? atoi(e) : -1; }();
-    // (the environment overrides the model's calibration either way -- A/B, tests -- except while that calibration runs)
-    return env >= 0 && !m->calibrating ? env != 0 : m->fp8_ok != 0;
-}
-
-bool arreau_cross_fp8(const arreau_model* m) {
-    const char* e = getenv("ARREAU_CROSS_FP8");
-    return (e == nullptr || atoi(e) != 0 || m->calibrating) && m->x8_ok && arreau_basis_fp8(m);
-}
-
-int arreau_launch_readout(const arreau_model* m, const float* xbar, const float* vsum, const int32_t* offsets, int B,
-                          int N, float* gs, float* eps, float* logits, float* len0, hipStream_t s) {
+int arreau_launch_readout(const arreau_model* m, ScorePlan::Readout kernel, const float* xbar, const float* vsum,
+                          const int32_t* offsets, int B, int N, float* gs, float* eps, float* logits, float* len0, hipStream_t s) {
     if (B == 0) return ARREAU_OK;
     if (N > 0) {
         const size_t smem = ((size_t)RO_ATOMS * m->L * m->C + (size_t)m->L * RO_ATOMS * RO_COLS) * sizeof(float);
@@ -829,9 +792,10 @@ int arreau_launch_readout(const arreau_model* m, const float* xbar, const float*
             arreau_set_error("readout kernel: num_layers * 128 threads must fit one workgroup");
             return ARREAU_EINVAL;
         }
-        // read-out variant: 1 (default) = fp32-MFMA kernel (needs S + 4 <= 96, L <= 8); 0 = vector kernel
-        const int ro_variant = m->readout_variant;
-        if (ro_variant == 1 && m->S + 4 <= 96 && m->L <= 8 && m->C == 128) {
+        if (kernel == ScorePlan::RO_VECTOR) {
+            ARREAU_LAUNCH(readout_nodes_kernel, dim3((N + RO_ATOMS - 1) / RO_ATOMS), dim3(RO_COLS * m->L), smem, s, xbar, vsum,
+                               m->ro_wT, m->ro_b, m->ori, m->S, m->C, m->L, N, eps, logits, gs, m->status);
+        } else {  // fp32-MFMA kernel (S + 4 <= 96, L <= 8)
             const size_t smem_m = (size_t)m->L * 3 * 64 * 16 * sizeof(float);
             static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&readout_mfma_kernel<128, 3>),
                                                                hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 3 * 64 * 16 * 4);
@@ -840,20 +804,12 @@ int arreau_launch_readout(const arreau_model* m, const float* xbar, const float*
                                                                  hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 3 * 64 * 16 * 4);
             ARREAU_CHECK_HIP(attr_s);
             const unsigned blocks32 = (unsigned)((N + 31) / 32);
-            static const int split_env = [] { const char* e = getenv("ARREAU_READOUT_SPLIT"); return e ? atoi(e) : -1; }();
-            // launch of fewer workgroups than the chip has CUs: one workgroup per output tile (measured, round 3: 160
-            // workgroups -- 256 x 20 -- 18.7 us split against 21.6; 640 -- 1024 x 20 -- 75 against 65; 2048: 220 against 169)
-            if (split_env >= 0 ? split_env != 0 : blocks32 < 256)
+            if (kernel == ScorePlan::RO_MFMA_SPLIT)  // one workgroup per output tile
                 ARREAU_LAUNCH((readout_mfma_kernel<128, 3, 1>), dim3(blocks32, 3), dim3(64 * m->L), smem_m, s, xbar, vsum,
                                    m->ro_pack, m->ro_b, m->ori, m->S, m->L, N, 0, N, eps, logits, gs, m->status);
             else
                 ARREAU_LAUNCH((readout_mfma_kernel<128, 3>), dim3(blocks32), dim3(64 * m->L), smem_m, s, xbar, vsum,
                                    m->ro_pack, m->ro_b, m->ori, m->S, m->L, N, 0, N, eps, logits, gs, m->status);
-            m->ran_readout = 1;
-        } else {
-            ARREAU_LAUNCH(readout_nodes_kernel, dim3((N + RO_ATOMS - 1) / RO_ATOMS), dim3(RO_COLS * m->L), smem, s, xbar, vsum,
-                               m->ro_wT, m->ro_b, m->ori, m->S, m->C, m->L, N, eps, logits, gs, m->status);
-            m->ran_readout = 0;
         }
         ARREAU_CHECK_HIP(hipGetLastError());
     }

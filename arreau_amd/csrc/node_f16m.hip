@@ -588,7 +588,6 @@ __global__ __launch_bounds__(512) void mlp_kernel_f16x3_m16_split(
     }
 }
 
-#define ARREAU_MLP_SPLIT_MAX_NODES 512
 int arreau_launch_mlp_f16x3_m16_split(const arreau_model* m, int layer, const float* x_conv, const float* x_in, float* x_out,
                                       float* xbar, float* vsum, int N, hipStream_t s) {
     if (N <= 0) return ARREAU_OK;
@@ -610,13 +609,6 @@ int arreau_launch_mlp_f16x3_m16_split(const arreau_model* m, int layer, const fl
 
 // Message passing + spherical convolution + ConvNext block of one layer in ONE launch (small launches on an fp32 K
 // buffer with k = 8; see the kernel): what conv_kernel_streamed<128> followed by the launch above computes, bit for bit.
-bool arreau_small_layer_fusable(const arreau_model* m, int N) {
-    const char* e = getenv("ARREAU_FUSE_SMALL");  // 0: two launches per layer (A/B, tests); read per call
-    static const int split_env = [] { const char* v = getenv("ARREAU_MLP_SPLIT"); return v ? atoi(v) : -1; }();
-    return (e == nullptr || atoi(e) != 0) && split_env < 0 && N <= ARREAU_MLP_SPLIT_MAX_NODES && m->mlp_variant == 3 &&
-           m->f16_ok && m->k == 8 && m->C == 128 && m->H == 512 && (m->conv_variant == 1 || m->conv_variant == 2) &&
-           !arreau_basis_form(m, N);
-}
 int arreau_launch_small_layer(const arreau_model* m, int layer, const float* kbuf, const int32_t* deg, const int32_t* src,
                               const float* x_in, float* x_out, float* xbar, float* vsum, int Ntot, hipStream_t s) {
     if (Ntot <= 0) return ARREAU_OK;
@@ -699,8 +691,8 @@ int arreau_repack_mlp_f16x3_m16(arreau_model* m, hipStream_t s) {
     return ARREAU_OK;
 }
 
-int arreau_launch_mlp_f16x3_m16(const arreau_model* m, int layer, const float* x_conv, const float* x_in, float* x_out,
-                                float* xbar, float* vsum, int N, hipStream_t s) {
+int arreau_launch_mlp_f16x3_m16(const arreau_model* m, int nb, int slots, int layer, const float* x_conv, const float* x_in,
+                                float* x_out, float* xbar, float* vsum, int N, hipStream_t s) {
     if (N <= 0) return ARREAU_OK;
     const int C = m->C, H = m->H;
     if (!(C == 128 && H == 512)) {
@@ -709,31 +701,12 @@ int arreau_launch_mlp_f16x3_m16(const arreau_model* m, int layer, const float* x
     }
     constexpr int NW = 4;
     const size_t layer_u32x4 = (size_t)2 * H * C * 2 * 2 / 16;  // bytes of W1 + W2 as 2 fp16 planes, in 16-byte units
-    // Tile geometry: one wave = 2 nodes (32 rows, each weight fragment read from LDS serves six MFMAs) or 1 node (16 rows:
-    // twice the tiles, a little more than half the time each -- 0.6 measured) -- bit-identical rows either way.  The launch
-    // takes whole rounds of tiles over the chip's wave slots (2 workgroups x 4 waves per CU), so pick the geometry whose
-    // rounds cost less: 16-row tiles while a batch leaves slots idle (1 x 8: -20 % step time) or has an expensive tail
-    // (256 x 20: 2.5 rounds of 0.6 against 1.25 rounds -> 2 of 1.0: 1.70 vs 1.73 ms per step), 32-row tiles for large
-    // batches (1024 x 20: 5 full rounds).  ARREAU_MLP_NB = 1 / 2 forces a geometry (tests).
-    // Small launches: one node per workgroup, the layer's work dealt to eight waves (bit-identical; see below).  Measured on
-    // MI355X: 10.7 us per layer at 8 nodes against 22.5 us; the forms cross where the node-per-workgroup form needs more
-    // than about two rounds of the chip.  ARREAU_MLP_SPLIT = 0 / 1 forces a form (tests).
-    static const int split_env = [] { const char* e = getenv("ARREAU_MLP_SPLIT"); return e ? atoi(e) : -1; }();
-    if (split_env >= 0 ? split_env != 0 : N <= ARREAU_MLP_SPLIT_MAX_NODES)
-        return arreau_launch_mlp_f16x3_m16_split(m, layer, x_conv, x_in, x_out, xbar, vsum, N, s);
-    static const int nb_env = [] { const char* e = getenv("ARREAU_MLP_NB"); return e ? atoi(e) : 0; }();
-    const int wave_slots = 8 * arreau_cu_count();
-    const long long rounds1 = ((long long)N + wave_slots - 1) / wave_slots;
-    const long long rounds2 = (((long long)N + 1) / 2 + wave_slots - 1) / wave_slots;
-    const int nb = nb_env == 1 || nb_env == 2 ? nb_env : (6 * rounds1 < 10 * rounds2 ? 1 : 2);
+    // one wave = nb nodes (2: 32 rows, each weight fragment read from LDS serves six MFMAs; 1: 16 rows), bit-identical rows either way
     const long long tiles = ((long long)N + nb - 1) / nb;
     const dim3 grid((unsigned)((tiles + NW - 1) / NW)), block(64 * NW);
     const float* lnw = m->ln_w + (size_t)layer * C;
     const float* lnb = m->ln_b + (size_t)layer * C;
     const u32x4* stream = reinterpret_cast<const u32x4*>(m->mlp_f16m) + (size_t)layer * layer_u32x4;
-    // ring depth: 3 slots; ARREAU_MLP_SLOTS=4 selects the four-slot ring (measured on MI355X at 256 x 20: 1.77 vs 1.77 ms
-    // per step, no gain -- the L2 -> LDS latency is already covered by one chunk of matrix work -- so the smaller one stays)
-    static const int slots = [] { const char* e = getenv("ARREAU_MLP_SLOTS"); return e && atoi(e) == 4 ? 4 : 3; }();
     auto launch = [&](auto kernel) {
         ARREAU_LAUNCH(kernel, grid, block, 0, s, x_conv, x_in, x_out, lnw, lnb, stream, m->mb1 + (size_t)layer * H,
                            m->mb2 + (size_t)layer * C, m->ls + (size_t)layer * C, m->ro_wv + (size_t)layer * C,

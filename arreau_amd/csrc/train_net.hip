@@ -537,9 +537,7 @@ int arreau_general_network(arreau_model* m, const arreau_graph_view& g, const in
         LAUNCH(train_outputs_kernel, dim3(N), dim3(128), t.rbar, m->ro_b, m->ori, S, L, N, d_eps, d_logits, t.gs, 0);
     }
     LAUNCH(pool_crystals_kernel, dim3(blocks(3 * B, 128)), dim3(128), t.gs, d_off, B, d_len0);
-    m->ran_edge = m->ran_mlp = ARREAU_VARIANT_GENERAL;
-    m->ran_conv = ARREAU_VARIANT_GENERAL;
-    m->ran_readout = ARREAU_VARIANT_GENERAL;  // train_outputs_kernel
+    m->ran = ScorePlan{.general = true};
     return ARREAU_OK;
 }
 

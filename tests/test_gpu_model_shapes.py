@@ -208,7 +208,7 @@ def _assert_scores_close_to_float64(got, want64, want32, tag, atoms_per_crystal=
 def _expected_families(sm, basis_form=False):
     if not sm.fused:
         return dict(edge_kernel="general-fp32-gemm", mlp_kernel="general-fp32-gemm", conv_variant=5, readout_kernel=5)
-    if sm.full_range:  # no basis form without the fp16x3 edge kernel (node.hip: arreau_basis_form): K pair at k = 8, else register
+    if sm.full_range:  # no basis form without the fp16x3 edge kernel (score_plan.h: basis_form): K pair at k = 8, else register
         return dict(edge_kernel="bf16x6", mlp_kernel="bf16x6", conv_variant=1 if sm.k == 8 else 0,
                     readout_kernel=1 if sm.S + 4 <= 96 else 0)
     # conv: 2 basis form (k = 8, L >= 2, enough receivers), 1 streamed K pair (k = 8), 0 register form (any k)
