@@ -31,7 +31,7 @@ EXPORTS = [
     "arreau_sample_loop_tied", "arreau_reverse_step_tied", "arreau_resample_jump_tied",
     "arreau_sample_loop_sym", "arreau_reverse_step_sym", "arreau_crystal_screen",
     "arreau_crystal_fingerprint", "arreau_fingerprint_match", "arreau_crystal_symmetry", "arreau_crystal_reduce",
-    "arreau_crystal_symmetrize", "arreau_structure_match",
+    "arreau_crystal_symmetrize", "arreau_structure_match", "arreau_structure_match_assigned",
 ]
 
 STATUS_NONFINITE, STATUS_BAD_TIMESTEP, STATUS_BAD_TYPE, STATUS_BAD_TIE, STATUS_BAD_SYMMETRY = 1, 2, 4, 8, 16
@@ -224,6 +224,8 @@ def _prototypes():
         "arreau_crystal_reduce": [vp] * 4 + [i32, i32, POINTER(ReduceParamsC), POINTER(ReduceResultC), vp],
         "arreau_crystal_symmetrize": [vp] * 4 + [i32, i32, POINTER(SymmetryResultC), i32, POINTER(SymmetrizeResultC), vp],
         "arreau_structure_match": ([vp] * 4 + [i32, i32]) * 2 + [vp, i32, POINTER(StructureMatchParamsC), POINTER(StructureMatchResultC), vp],
+        "arreau_structure_match_assigned": ([vp] * 4 + [i32, i32]) * 2 + [vp, i32, POINTER(StructureMatchParamsC), POINTER(StructureMatchResultC),
+                                            i32, vp, vp],
         "arreau_train_forward": [vp] * 7 + [i32, i32] + [vp] * 4,
         "arreau_train_backward": [vp] * 4 + [POINTER(StateDict), vp],
         "arreau_train_conv_stats": [vp, vp, vp],

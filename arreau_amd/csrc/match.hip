@@ -11,6 +11,10 @@
 //            forms the rms again from the stored partners; lane 0 keeps the wave's best (rms, code, q);
 //   phase 3  the best of the four waves; wave 0 evaluates that candidate once more (the same float32 operations, the same bits)
 //            and writes partner, translation, rms, max_dist, rms_norm.
+// The kernel is a template on the assignment mode (rule 6b).  The assigning instance keeps every same-species dist^2 of part A as
+// the candidate's cost matrix (LDS up to ARREAU_SM_ASSIGN_LDS_ATOMS atoms, d_cost above) and, where the nearest-partner map is not
+// one-to-one, the wave that owns the candidate solves the linear assignment by shortest augmenting paths, columns on lanes in
+// blocks of 64, in exact 64-bit integer arithmetic on the costs rounded to multiples of 2^-24 A^2; phase 3 repeats it.
 #include "internal.h"
 #include "crystal_dev.h"
 #include <cmath>
@@ -88,8 +92,20 @@ __device__ __forceinline__ float nearest_image_d2(float* e, const float* G) {
     return best;
 }
 
+// the solver's writes of one lane are read by the other lanes of its wave (LDS or global memory)
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+}
+
+constexpr int SM_ROW_V = 0, SM_ROW_D = 2, SM_ROW_Y = 4, SM_ROW_PRED = 5;  // the solver's state rows (v and d: low word, high word)
+constexpr int SM_EXCLUDED = -2147483647 - 1;                              // pred of a column of another species
+static_assert(ARREAU_SM_ASSIGN_STATE_ROWS == 6, "v (2), d (2), y, pred");
+
+template <bool ASSIGN>
 __global__ __launch_bounds__(CRYSTAL_THREADS) void structure_match_kernel(sm_side X, sm_side Y, const int32_t* __restrict__ pairs, int P,
-                                                                          float ltol, float angle_tol, float stol, int max_mappings, sm_out o) {
+                                                                          float ltol, float angle_tol, float stol, int max_mappings, sm_out o,
+                                                                          float* d_cost) {
     const int p = blockIdx.x;
     if (p >= P) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -102,6 +118,9 @@ __global__ __launch_bounds__(CRYSTAL_THREADS) void structure_match_kernel(sm_sid
     __shared__ unsigned s_ka[CRYSTAL_WAVES], s_kb[CRYSTAL_WAVES];
     __shared__ float s_best[CRYSTAL_WAVES];
     __shared__ int s_bcode[CRYSTAL_WAVES], s_bq[CRYSTAL_WAVES], s_surv[CRYSTAL_WAVES];
+    constexpr int A = ARREAU_SM_ASSIGN_LDS_ATOMS, ROWS = ARREAU_SM_ASSIGN_STATE_ROWS;
+    __shared__ float s_cost[ASSIGN ? CRYSTAL_WAVES * A * (A + 1) : 1];  // (rows of A + 1: the lanes of part A write one column at a time)
+    __shared__ int s_state[ASSIGN ? CRYSTAL_WAVES * ROWS * CRYSTAL_LDS_ATOMS : 1];
 
     const float inf = __int_as_float(0x7f800000);
     int32_t* o_partner = o.partner + (size_t)p * o.stride;
@@ -223,6 +242,16 @@ __global__ __launch_bounds__(CRYSTAL_THREADS) void structure_match_kernel(sm_sid
     // barrier: the map one-to-one?  then the refined translation and the distances once more.
     int* pm = n <= CRYSTAL_LDS_ATOMS ? s_pm + wave * CRYSTAL_LDS_ATOMS : o.scratch + ((size_t)p * CRYSTAL_WAVES + wave) * o.stride;
     float V[9], Gm[6], t[3], sum[3];  // the state of the wave's candidate between part A and part B
+    // rule 6b: the wave's cost matrix cm (row stride cs) and solver state st (row stride ss), each in LDS or in d_cost
+    float* cm = nullptr;
+    int* st = nullptr;
+    int cs = 0, ss = 0;
+    if constexpr (ASSIGN) {
+        float* home = d_cost ? d_cost + ((size_t)p * CRYSTAL_WAVES + wave) * ((size_t)o.stride + ROWS) * o.stride : nullptr;
+        if (n <= A) { cm = s_cost + wave * A * (A + 1); cs = A + 1; } else { cm = home; cs = o.stride; }
+        if (n <= CRYSTAL_LDS_ATOMS) { st = s_state + wave * ROWS * CRYSTAL_LDS_ATOMS; ss = CRYSTAL_LDS_ATOMS; }
+        else { st = reinterpret_cast<int*>(home + (size_t)o.stride * o.stride); ss = o.stride; }
+    }
     auto mapped = [&](int j, float* y) {  // rule 3: v' = wrap(W^-1 v)
         const float v0 = vpos(j, 0), v1 = vpos(j, 1), v2 = vpos(j, 2);
 #pragma unroll
@@ -262,6 +291,7 @@ __global__ __launch_bounds__(CRYSTAL_THREADS) void structure_match_kernel(sm_sid
                     mapped(j, y);
                     e[0] = __fsub_rn(__fadd_rn(y[0], t[0]), x0); e[1] = __fsub_rn(__fadd_rn(y[1], t[1]), x1); e[2] = __fsub_rn(__fadd_rn(y[2], t[2]), x2);
                     const float d2 = nearest_image_d2(e, Gm);
+                    if constexpr (ASSIGN) cm[(size_t)i * cs + j] = d2;
                     if (d2 < best2) { best2 = d2; best = j; b0 = e[0]; b1 = e[1]; b2 = e[2]; }
                 }
                 pm[i] = best;
@@ -269,15 +299,121 @@ __global__ __launch_bounds__(CRYSTAL_THREADS) void structure_match_kernel(sm_sid
             lane_sum(b0, b1, b2, min(64, n - i0), sum[0], sum[1], sum[2]);
         }
     };
-    // part B: returns whether the map is a permutation; then rms2 = (sum of d^2) / n and max2 = max d^2 with the refined translation
-    auto part_b = [&](float& rms2, float& max2, float* refined) -> bool {
+    // rule 6b: the one-to-one, species-preserving map of the smallest sum of the wave's cost matrix, into pm.  Shortest augmenting
+    // paths (Jonker-Volgenant) from part A's start: column duals 0, a row keeps its nearest partner when it is the smallest row
+    // that claims the column (its dual is that minimum, implicitly); the other rows are augmented in ascending order.  Columns
+    // live on lanes (j = lane, lane + 64, ...), each lane owns the state of its columns; costs are round(d^2 x 2^24) as 64-bit
+    // integers, so every sum and difference is exact.  Called by the whole wave.
+    auto ld64 = [&](int row, int j) -> long long {
+        return (long long)(((unsigned long long)(unsigned)st[(size_t)(row + 1) * ss + j] << 32) | (unsigned)st[(size_t)row * ss + j]);
+    };
+    auto st64 = [&](int row, int j, long long v) {
+        st[(size_t)row * ss + j] = (int)(unsigned)(unsigned long long)v;
+        st[(size_t)(row + 1) * ss + j] = (int)(v >> 32);
+    };
+    auto cost = [&](int i, int j) -> long long { return __float2ll_rn(__fmul_rn(cm[(size_t)i * cs + j], 16777216.f)); };
+    auto solve = [&]() {
+        int* y = st + (size_t)SM_ROW_Y * ss;
+        int* pred = st + (size_t)SM_ROW_PRED * ss;
+        for (int j = lane; j < n; j += 64) { y[j] = -1; st64(SM_ROW_V, j, 0); }
+        wave_sync();
+        for (int i = lane; i < n; i += 64) {
+            const int pi = pm[i];
+            bool first = pi >= 0;
+            for (int k = 0; k < i; ++k) first = first && pm[k] != pi;
+            if (first) y[pi] = i;
+        }
+        wave_sync();
+        for (int i = lane; i < n; i += 64) {
+            const int pi = pm[i];
+            if (pi >= 0 && y[pi] != i) pm[i] = -1;
+        }
+        wave_sync();
+        for (int f = 0; f < n; ++f) {
+            if (pm[f] >= 0) continue;  // (uniform)
+            const int tf = spx(f);
+            for (int j = lane; j < n; j += 64) {
+                const bool same = spy(j) == tf;  // another species is excluded, not made expensive
+                pred[j] = same ? f : SM_EXCLUDED;
+                if (same) st64(SM_ROW_D, j, cost(f, j) - ld64(SM_ROW_V, j));
+            }
+            int j1 = -1;
+            long long mind = 0;
+            for (int step = 0; step < n; ++step) {  // (every step scans one column)
+                long long bd = 0x7fffffffffffffffLL;
+                int bj = 0x7fffffff;
+                for (int j = lane; j < n; j += 64) {  // ascending j and a strict comparison: ties go to the smallest j
+                    if (pred[j] < 0) continue;
+                    const long long d = ld64(SM_ROW_D, j);
+                    if (d < bd) { bd = d; bj = j; }
+                }
+#pragma unroll
+                for (int off = 32; off >= 1; off >>= 1) {
+                    const long long od = __shfl_xor(bd, off);
+                    const int oj = __shfl_xor(bj, off);
+                    if (od < bd || (od == bd && oj < bj)) { bd = od; bj = oj; }
+                }
+                if (bj >= n) break;  // (not reached: the species multisets agree, a free column of the species exists)
+                mind = bd;
+                if (lane == (bj & 63)) pred[bj] = ~pred[bj];  // scanned
+                const int i = y[bj];
+                if (i < 0) { j1 = bj; break; }
+                const long long h = cost(i, bj) - ld64(SM_ROW_V, bj) - mind;
+                for (int j = lane; j < n; j += 64) {
+                    if (pred[j] < 0) continue;
+                    const long long nd = cost(i, j) - ld64(SM_ROW_V, j) - h;
+                    if (nd < ld64(SM_ROW_D, j)) { st64(SM_ROW_D, j, nd); pred[j] = i; }
+                }
+            }
+            if (j1 >= 0) {
+                for (int j = lane; j < n; j += 64)
+                    if (pred[j] < 0 && pred[j] != SM_EXCLUDED) st64(SM_ROW_V, j, ld64(SM_ROW_V, j) + ld64(SM_ROW_D, j) - mind);
+                wave_sync();
+                int j = j1;
+                for (int hop = 0; hop < n; ++hop) {  // the path back to f: every row on it moves to the column it was reached from
+                    const int i = ~pred[j];
+                    if (i < 0 || i >= n) break;  // (not reached)
+                    const int before = pm[i];
+                    if (lane == 0) { y[j] = i; pm[i] = j; }
+                    if (i == f || before < 0) break;
+                    j = before;
+                }
+            }
+            wave_sync();
+        }
+    };
+    // part B: returns whether the map is a permutation (or was made one-to-one by the assignment step: `solved`); then rms2 = (sum
+    // of d^2) / n and max2 = max d^2 with the refined translation
+    auto part_b = [&](float& rms2, float& max2, float* refined, bool& solved) -> bool {
         int twice = 0;
         for (int i = lane; i < n; i += 64) {
             const int pi = pm[i];
             if (pi < 0) { twice = 1; continue; }
             for (int k = 0; k < i; ++k) twice |= pm[k] == pi;
         }
-        if (__any(twice)) return false;
+        solved = false;
+        if (__any(twice)) {
+            if constexpr (!ASSIGN) return false;
+            wave_sync();  // (every lane has read the map before the solver writes it)
+            solve();
+            int hole = 0;
+            for (int i = lane; i < n; i += 64) hole |= pm[i] < 0;
+            if (__any(hole)) return false;  // (not reached)
+            solved = true;
+            sum[0] = sum[1] = sum[2] = 0.f;  // the differences of the chosen partners under the unrefined t: part A's operations
+            for (int i0 = 0; i0 < n; i0 += 64) {
+                const int i = i0 + lane;
+                float e[3] = {0.f, 0.f, 0.f};
+                if (i < n) {
+                    float y[3];
+                    mapped(pm[i], y);
+                    e[0] = __fsub_rn(__fadd_rn(y[0], t[0]), wpos(i, 0)); e[1] = __fsub_rn(__fadd_rn(y[1], t[1]), wpos(i, 1));
+                    e[2] = __fsub_rn(__fadd_rn(y[2], t[2]), wpos(i, 2));
+                    nearest_image_d2(e, Gm);
+                }
+                lane_sum(e[0], e[1], e[2], min(64, n - i0), sum[0], sum[1], sum[2]);
+            }
+        }
 #pragma unroll
         for (int r = 0; r < 3; ++r) refined[r] = __fsub_rn(t[r], __fdiv_rn(sum[r], (float)n));
         float total = 0.f, dummy1 = 0.f, dummy2 = 0.f;
@@ -323,8 +459,9 @@ __global__ __launch_bounds__(CRYSTAL_THREADS) void structure_match_kernel(sm_sid
         __syncthreads();  // (the partner map: written by the lanes of part A, read across lanes in part B)
         if (have) {
             float rms2, max2, refined[3];
-            if (part_b(rms2, max2, refined)) {
-                ++survivors;
+            bool solved;
+            if (part_b(rms2, max2, refined, solved)) {
+                survivors += solved ? 0 : 1;  // n_permutations: the candidates whose nearest-partner map was one-to-one
                 const float rms = sqrtf(rms2);
                 if (rms < best_rms) { best_rms = rms; best_code = code; best_q = q; }  // (ascending (code, q) on a wave: ties keep the first)
             }
@@ -354,7 +491,8 @@ __global__ __launch_bounds__(CRYSTAL_THREADS) void structure_match_kernel(sm_sid
     __syncthreads();
     if (wave == 0) {
         float rms2, max2, refined[3];
-        part_b(rms2, max2, refined);  // (a permutation: it was one in phase 2)
+        bool solved;
+        part_b(rms2, max2, refined, solved);  // (a permutation, or solved again: as in phase 2)
         for (int i = lane; i < o.stride; i += 64) o_partner[i] = i < n ? pm[i] : -1;
         if (lane == 0) {
             const float rms = sqrtf(rms2);
@@ -369,9 +507,48 @@ __global__ __launch_bounds__(CRYSTAL_THREADS) void structure_match_kernel(sm_sid
             o.translation[3 * (size_t)p] = refined[0]; o.translation[3 * (size_t)p + 1] = refined[1]; o.translation[3 * (size_t)p + 2] = refined[2];
             o.n_mappings[p] = n_mappings; o.n_candidates[p] = (int)n_candidates; o.n_permutations[p] = survivors;
             o.matched[p] = norm <= stol ? 1 : 0;  // (a NaN does not match)
-            o.flags[p] = more;
+            o.flags[p] = more | (solved ? ARREAU_SM_ASSIGNED : 0);
         }
     }
+}
+
+// the argument checks and the launch of both entry points; `who` names the caller in the error text
+int launch_structure_match(const char* who, const float* x_frac, const int32_t* x_types, const float* x_lattice, const int32_t* x_offsets, int32_t Bx,
+                           int32_t Nx, const float* y_frac, const int32_t* y_types, const float* y_lattice, const int32_t* y_offsets, int32_t By,
+                           int32_t Ny, const int32_t* d_pairs, int32_t P, const arreau_structure_match_params* params,
+                           arreau_structure_match_result* out, int32_t assignment, float* d_cost, void* stream) {
+#define SM_REQUIRE(cond, text) ARREAU_REQUIRE(cond, std::string(who) + text)
+    SM_REQUIRE(params != nullptr && out != nullptr, ": null params or result");
+    SM_REQUIRE(Bx >= 0 && Nx >= 0 && By >= 0 && Ny >= 0 && P >= 0, ": bad size");
+    SM_REQUIRE(std::isfinite(params->ltol) && params->ltol > 0.f, ": ltol must be finite and > 0");
+    SM_REQUIRE(std::isfinite(params->angle_tol) && params->angle_tol > 0.f, ": angle_tol must be finite and > 0");
+    SM_REQUIRE(std::isfinite(params->stol) && params->stol > 0.f, ": stol must be finite and > 0");
+    SM_REQUIRE(params->max_mappings >= 1 && params->max_mappings <= ARREAU_SM_MAX_MAPPINGS_CAP, ": max_mappings must lie in 1..4096");
+    SM_REQUIRE(assignment == ARREAU_SM_ASSIGN_NEAREST || assignment == ARREAU_SM_ASSIGN_OPTIMAL, ": assignment must be 0 (nearest) or 1 (optimal)");
+    if (P == 0) return ARREAU_OK;
+    SM_REQUIRE(d_pairs != nullptr, ": null pair list");
+    SM_REQUIRE((x_lattice && x_offsets) || Bx == 0, ": null pointer (x)");
+    SM_REQUIRE((y_lattice && y_offsets) || By == 0, ": null pointer (y)");
+    SM_REQUIRE(((x_frac && x_types) || Nx == 0) && ((y_frac && y_types) || Ny == 0), ": null per-atom pointer");
+    SM_REQUIRE(out->rms && out->rms_norm && out->max_dist && out->mapping && out->translation && out->n_mappings && out->n_candidates &&
+                   out->n_permutations && out->matched && out->flags,
+               ": null result array");
+    SM_REQUIRE(out->partner_stride >= 0 && (out->partner || out->partner_stride == 0), ": null partner array or bad stride");
+    SM_REQUIRE(out->scratch || out->partner_stride <= CRYSTAL_LDS_ATOMS, ": a partner_stride above 256 needs the scratch array");
+    SM_REQUIRE(assignment == ARREAU_SM_ASSIGN_NEAREST || d_cost || out->partner_stride <= ARREAU_SM_ASSIGN_LDS_ATOMS,
+               ": the optimal assignment with a partner_stride above ARREAU_SM_ASSIGN_LDS_ATOMS needs d_cost");
+#undef SM_REQUIRE
+    sm_side X{x_frac, x_types, x_lattice, x_offsets, (int)Bx, (int)Nx}, Y{y_frac, y_types, y_lattice, y_offsets, (int)By, (int)Ny};
+    sm_out o{out->rms, out->rms_norm, out->max_dist, out->mapping, out->translation, out->partner, out->n_mappings, out->n_candidates,
+             out->n_permutations, out->matched, out->flags, out->scratch, (int)out->partner_stride};
+    if (assignment == ARREAU_SM_ASSIGN_OPTIMAL)
+        ARREAU_LAUNCH(structure_match_kernel<true>, dim3((unsigned)P), dim3(CRYSTAL_THREADS), 0, (hipStream_t)stream, X, Y, d_pairs, (int)P,
+                      params->ltol, params->angle_tol, params->stol, (int)params->max_mappings, o, d_cost);
+    else
+        ARREAU_LAUNCH(structure_match_kernel<false>, dim3((unsigned)P), dim3(CRYSTAL_THREADS), 0, (hipStream_t)stream, X, Y, d_pairs, (int)P,
+                      params->ltol, params->angle_tol, params->stol, (int)params->max_mappings, o, (float*)nullptr);
+    ARREAU_CHECK_HIP(hipGetLastError());
+    return ARREAU_OK;
 }
 
 }  // namespace
@@ -380,29 +557,15 @@ extern "C" int arreau_structure_match(const float* x_frac, const int32_t* x_type
                                       int32_t Nx, const float* y_frac, const int32_t* y_types, const float* y_lattice, const int32_t* y_offsets,
                                       int32_t By, int32_t Ny, const int32_t* d_pairs, int32_t P, const arreau_structure_match_params* params,
                                       arreau_structure_match_result* out, void* stream) {
-    ARREAU_REQUIRE(params != nullptr && out != nullptr, "arreau_structure_match: null params or result");
-    ARREAU_REQUIRE(Bx >= 0 && Nx >= 0 && By >= 0 && Ny >= 0 && P >= 0, "arreau_structure_match: bad size");
-    ARREAU_REQUIRE(std::isfinite(params->ltol) && params->ltol > 0.f, "arreau_structure_match: ltol must be finite and > 0");
-    ARREAU_REQUIRE(std::isfinite(params->angle_tol) && params->angle_tol > 0.f, "arreau_structure_match: angle_tol must be finite and > 0");
-    ARREAU_REQUIRE(std::isfinite(params->stol) && params->stol > 0.f, "arreau_structure_match: stol must be finite and > 0");
-    ARREAU_REQUIRE(params->max_mappings >= 1 && params->max_mappings <= ARREAU_SM_MAX_MAPPINGS_CAP,
-                   "arreau_structure_match: max_mappings must lie in 1..4096");
-    if (P == 0) return ARREAU_OK;
-    ARREAU_REQUIRE(d_pairs != nullptr, "arreau_structure_match: null pair list");
-    ARREAU_REQUIRE((x_lattice && x_offsets) || Bx == 0, "arreau_structure_match: null pointer (x)");
-    ARREAU_REQUIRE((y_lattice && y_offsets) || By == 0, "arreau_structure_match: null pointer (y)");
-    ARREAU_REQUIRE(((x_frac && x_types) || Nx == 0) && ((y_frac && y_types) || Ny == 0), "arreau_structure_match: null per-atom pointer");
-    ARREAU_REQUIRE(out->rms && out->rms_norm && out->max_dist && out->mapping && out->translation && out->n_mappings && out->n_candidates &&
-                       out->n_permutations && out->matched && out->flags,
-                   "arreau_structure_match: null result array");
-    ARREAU_REQUIRE(out->partner_stride >= 0 && (out->partner || out->partner_stride == 0), "arreau_structure_match: null partner array or bad stride");
-    ARREAU_REQUIRE(out->scratch || out->partner_stride <= CRYSTAL_LDS_ATOMS,
-                   "arreau_structure_match: a partner_stride above 256 needs the scratch array");
-    sm_side X{x_frac, x_types, x_lattice, x_offsets, (int)Bx, (int)Nx}, Y{y_frac, y_types, y_lattice, y_offsets, (int)By, (int)Ny};
-    sm_out o{out->rms, out->rms_norm, out->max_dist, out->mapping, out->translation, out->partner, out->n_mappings, out->n_candidates,
-             out->n_permutations, out->matched, out->flags, out->scratch, (int)out->partner_stride};
-    ARREAU_LAUNCH(structure_match_kernel, dim3((unsigned)P), dim3(CRYSTAL_THREADS), 0, (hipStream_t)stream, X, Y, d_pairs, (int)P, params->ltol,
-                  params->angle_tol, params->stol, (int)params->max_mappings, o);
-    ARREAU_CHECK_HIP(hipGetLastError());
-    return ARREAU_OK;
+    return launch_structure_match("arreau_structure_match", x_frac, x_types, x_lattice, x_offsets, Bx, Nx, y_frac, y_types, y_lattice, y_offsets,
+                                  By, Ny, d_pairs, P, params, out, ARREAU_SM_ASSIGN_NEAREST, nullptr, stream);
+}
+
+extern "C" int arreau_structure_match_assigned(const float* x_frac, const int32_t* x_types, const float* x_lattice, const int32_t* x_offsets,
+                                               int32_t Bx, int32_t Nx, const float* y_frac, const int32_t* y_types, const float* y_lattice,
+                                               const int32_t* y_offsets, int32_t By, int32_t Ny, const int32_t* d_pairs, int32_t P,
+                                               const arreau_structure_match_params* params, arreau_structure_match_result* out, int32_t assignment,
+                                               float* d_cost, void* stream) {
+    return launch_structure_match("arreau_structure_match_assigned", x_frac, x_types, x_lattice, x_offsets, Bx, Nx, y_frac, y_types, y_lattice,
+                                  y_offsets, By, Ny, d_pairs, P, params, out, assignment, d_cost, stream);
 }

@@ -390,7 +390,7 @@ class DiffusionLoss(nn.Module):
         falls onto it, the rms displacement in A and normalised, and `matched` (rms_norm <= stol).  As many targets as crystals:
         crystal b is matched against target b; otherwise against every target of its composition, the best one reported.  The
         atomic numbers are the species ids.  SampleResult.match then holds the arrays (structure_match.MATCH_KEYS).  It reads the
-        state as sampled, like the other instruments.  No Hungarian assignment, no supercells, no volume scaling.  None: no launch
+        state as sampled, like the other instruments.  The optimal assignment only with StructureMatchParams(assignment="optimal"), no supercells, no volume scaling.  None: no launch
         is added, match is None and the results are what they were, bit for bit."""
         match_to = structure_match.resolve(match_to)
         reduce_cell = cell_reduction.resolve(reduce_cell)

@@ -49,7 +49,7 @@ INSTRUMENTS = (
     Instrument("symmetrize", "symmetrized", "symmetrized_", "symmetrize_stats", symmetrize, symmetrize.SYMMETRIZED_KEYS,
                "SymmetrizeParams", _SYMPREC, "symmetrize", atom_keys=symmetrize.ATOM_KEYS),
     Instrument("match_to", "match", "match_", "match_stats", structure_match, structure_match.MATCH_KEYS, "StructureMatchParams",
-               (("ltol", "ltol"), ("angle_tol", "angle_tol"), ("stol", "stol")), "structure match", atom_keys=structure_match.ATOM_KEYS),
+               (("ltol", "ltol"), ("angle_tol", "angle_tol"), ("stol", "stol"), ("assignment", "assignment")), "structure match", atom_keys=structure_match.ATOM_KEYS),
 )
 BY_KEYWORD = {e.keyword: e for e in INSTRUMENTS}
 

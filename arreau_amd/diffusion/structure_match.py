@@ -6,8 +6,12 @@ needs no engine (`match`), the host pairing helpers (`paired`, `same_composition
 SampleResults or loaded files, the statistics lines and a float64 numpy restatement of rules 1-7 (`structure_match_reference_f64`).
 The restatement and the helpers need numpy alone.
 
-What this is not.  No Hungarian assignment: a candidate whose nearest-partner map is not one-to-one is skipped (where the map is a
-permutation it is the optimal assignment).  No supercell, formula-reduced or anonymous-species matching: the species multisets are
+The assignment.  By default (`assignment="nearest"`) a candidate whose nearest-partner map is not one-to-one is skipped (where
+the map is a permutation it is the optimal assignment).  With `assignment="optimal"` such a candidate gets the one-to-one,
+species-preserving map of the smallest sum of squared distances at its unrefined translation (the header's rule 6b; the linear
+assignment StructureMatcher solves), so no pair ends NO_PERMUTATION; the flag ASSIGNED says the winner's map came from that step.
+
+What this is not.  No supercell, formula-reduced or anonymous-species matching: the species multisets are
 compared exactly, run cell_reduction first.  No rescaling of the two cells to one volume.  A mapping W with an entry outside
 {-1, 0, 1} is not found (complete for two Delaunay-reduced cells).  And nothing is said about a trained model.
 
@@ -36,7 +40,20 @@ an edge of the mean metric G_m: every entry of G_m lies within l_1^2, its larges
   * l = cbrt(sqrt(det G_m) / n): det's six triple products below l_1^6, each within (3 x 32 + 2) u l_1^6, five roundings of partial
     sums below 6 l_1^6: |det_f32 - det| <= (6 x 98 + 30) u l_1^6 = 618 u rho det; the square root and cube root divide that by 6
     and add u, the division u, the device's cbrt 4 u: l within (103 rho + 8) u l.  rms_norm = rms / l: DISTANCE_BOUND(rms) / l +
-    rms_norm ((103 rho + 8) u + u) (`norm_bound`)."""
+    rms_norm ((103 rho + 8) u + u) (`norm_bound`).
+  * the assignment step (rule 6b).  A cost entry c = d^2 of e = (v'_j + t) - w_i at the unrefined t.  Given the float32 e, d^2
+    carries the 54 + 288 = 342 u l_1^2 |e|^2 of the bullet above (no sum over atoms), and |e|^2 <= c / lambda, lambda the smallest
+    eigenvalue of G_m: a c with a = 342 u l_1^2 / lambda.  e itself carries 36 u per component, which moves d by at most 3 l_1 x
+    36 u = 108 u l_1 and d^2 by 2 d x that plus its square: b sqrt(c) + (108 u l_1)^2 with b = 216 u l_1.  The kernel rounds c to
+    a multiple of 2^-24 A^2 (2^-25) and from there adds and compares 64-bit integers exactly: its solver returns a true optimum
+    of the rounded matrix, whatever the order of its operations.  |c_f32 - c| <= a c + b sqrt(c) + c_0, c_0 = (108 u l_1)^2 +
+    2^-25 (`cost_bound`).  Over a map of n rows with exact sum S: f(S) = a S + b sqrt(n S) + n c_0 (Cauchy-Schwarz).  If the
+    kernel's map has the exact sum S* + x, S* the true optimum, then its rounded sum is no larger than the optimum's rounded
+    sum: x <= f(S* + x) + f(S*) <= 2 f(S*) + a x + b sqrt(n x), so sqrt(x) <= (b sqrt(n) + sqrt(b^2 n + 8 (1 - a) f(S*))) /
+    (2 (1 - a)): SOLVER_BOUND(S*) is the square of that (`solver_bound`), the most by which the kernel's map can miss the true
+    optimum sum.  A test case is decided where the GAP to the runner-up assignment (the smallest optimum with one edge of the
+    optimal map forbidden, minus the optimum) is at least four times SOLVER_BOUND and at least 1e-3 A^2; then the kernel's map
+    is the restatement's.  For a given map the bounds on rms, max_dist, rms_norm and translation above hold as they stand."""
 import math
 from dataclasses import dataclass
 from numbers import Integral, Real
@@ -50,6 +67,14 @@ from . import symmetry_search as ss
 NONFINITE, CELL, EMPTY, DIFFERENT, BAD_PAIR, NO_MAPPING, OVERFLOW, NO_PERMUTATION = 1, 2, 4, 8, 16, 32, 64, 128
 FLAG_NAMES = ((NONFINITE, "NONFINITE"), (CELL, "CELL"), (EMPTY, "EMPTY"), (DIFFERENT, "DIFFERENT"), (BAD_PAIR, "BAD_PAIR"),
               (NO_MAPPING, "NO_MAPPING"), (OVERFLOW, "OVERFLOW"), (NO_PERMUTATION, "NO_PERMUTATION"))
+ASSIGNED = 256  # informational (rule 6b): the winner's map came from the assignment step; not in NO_RESULT_MASK, nor in `matched`
+# FLAG_NAMES: the flags of rules 1-7; ALL_FLAG_NAMES: those and ASSIGNED, what `describe` and the statistics count
+ALL_FLAG_NAMES = FLAG_NAMES + ((ASSIGNED, "ASSIGNED"),)
+ASSIGNMENTS = {"nearest": 0, "optimal": 1}  # arreau_hip.h: ARREAU_SM_ASSIGN_NEAREST / ARREAU_SM_ASSIGN_OPTIMAL
+ASSIGN_LDS_ATOMS, ASSIGN_STATE_ROWS = 24, 6  # arreau_hip.h: ARREAU_SM_ASSIGN_LDS_ATOMS / ARREAU_SM_ASSIGN_STATE_ROWS
+# `match` with assignment "optimal": the cost scratch of one launch stays below this many bytes (4 x (stride + 6) x stride floats
+# per pair); a longer pair list is split into consecutive launches
+COST_BUDGET_BYTES = 256 << 20
 NO_RESULT_MASK = NONFINITE | CELL | EMPTY | DIFFERENT | BAD_PAIR | NO_MAPPING | NO_PERMUTATION  # rms = +inf, mapping = -1
 MAX_MAPPINGS_CAP = 4096  # match.hip / arreau_hip.h: ARREAU_SM_MAX_MAPPINGS_CAP
 DEFAULT_LTOL, DEFAULT_ANGLE_TOL, DEFAULT_STOL, DEFAULT_MAX_MAPPINGS = 0.2, 5.0, 0.3, 192
@@ -65,18 +90,20 @@ F32 = np.float32
 
 
 def describe(flags) -> str:
-    return cb.describe(flags, FLAG_NAMES)
+    return cb.describe(flags, ALL_FLAG_NAMES)
 
 
 @dataclass(frozen=True)
 class StructureMatchParams:
     """ltol: the relative tolerance on the cell lengths; angle_tol: on the cell angles, in DEGREES (the C struct takes radians);
     stol: on rms_norm = rms / (V / n)^(1/3) -- the three of pymatgen's StructureMatcher, with its defaults (starting values, not a
-    claim).  max_mappings: the lattice mappings tried per pair (1..4096); n_mappings counts them all."""
+    claim).  max_mappings: the lattice mappings tried per pair (1..4096); n_mappings counts them all.  assignment: "nearest" -- a
+    candidate whose nearest-partner map is not one-to-one is dropped; "optimal" -- it gets the optimal assignment (rule 6b)."""
     ltol: float = DEFAULT_LTOL
     angle_tol: float = DEFAULT_ANGLE_TOL
     stol: float = DEFAULT_STOL
     max_mappings: int = DEFAULT_MAX_MAPPINGS
+    assignment: str = "nearest"
 
     def __post_init__(self):
         for name in ("ltol", "angle_tol", "stol"):
@@ -88,6 +115,8 @@ class StructureMatchParams:
         if not isinstance(v, Integral) or isinstance(v, bool) or not 1 <= int(v) <= MAX_MAPPINGS_CAP:
             raise ValueError(f"max_mappings must lie in 1..{MAX_MAPPINGS_CAP}, got {v!r}")
         object.__setattr__(self, "max_mappings", int(v))
+        if not isinstance(self.assignment, str) or self.assignment not in ASSIGNMENTS:
+            raise ValueError(f"assignment must be 'nearest' or 'optimal', got {self.assignment!r}")
 
     @property
     def angle_tol_rad(self) -> float:
@@ -170,8 +199,11 @@ def best_per_x(pairs, result, Bx):
 
 
 # ------------------------------------------------------------------------------------------------------- the device call
-def match(x_batch, y_batch, pairs, params=None, stride=None):
-    """Match pairs of crystals on the GPU without an engine (arreau_structure_match, one launch).  x_batch, y_batch: (frac [N,3]
+def match(x_batch, y_batch, pairs, params=None, stride=None, cost_budget=None):
+    """Match pairs of crystals on the GPU without an engine (arreau_structure_match, one launch; with assignment "optimal"
+    arreau_structure_match_assigned, whose cost scratch above ASSIGN_LDS_ATOMS atoms is kept below `cost_budget` bytes --
+    COST_BUDGET_BYTES by default -- by consecutive launches over slices of the pair list: pairs are independent, the result is one
+    launch's bit for bit).  x_batch, y_batch: (frac [N,3]
     float32, lattice [B,3,3] float32, offsets [B+1] int32, types [N] int32) contiguous tensors on one cuda device (crystal_batch's
     `upload` makes them; y_batch may be x_batch); pairs [P,2] int32 (x, y) indices, a tensor on that device or a host array.
     Returns a dict of device tensors: rms, rms_norm, max_dist, mapping, n_mappings, n_candidates, n_permutations, matched, flags
@@ -207,8 +239,21 @@ def match(x_batch, y_batch, pairs, params=None, stride=None):
                                    _hip.ptr(scratch).value if scratch is not None and P else None, stride)
     side = lambda b, B, N: [_hip.ptr(b[0]) if N else None, _hip.ptr(b[3]) if N else None, _hip.ptr(b[1]) if B else None, _hip.ptr(b[2]), B, N]
     with torch.cuda.device(dev):
-        _hip.check(_hip.lib().arreau_structure_match(*side(x_batch, Bx, Nx), *side(y_batch, By, Ny), _hip.ptr(pairs) if P else None, P,
-                                                     ctypes.byref(c), ctypes.byref(r), _hip.stream_ptr(dev)), "arreau_structure_match")
+        if p.assignment == "nearest":
+            _hip.check(_hip.lib().arreau_structure_match(*side(x_batch, Bx, Nx), *side(y_batch, By, Ny), _hip.ptr(pairs) if P else None, P,
+                                                         ctypes.byref(c), ctypes.byref(r), _hip.stream_ptr(dev)), "arreau_structure_match")
+        else:
+            per_pair = WAVES * (stride + ASSIGN_STATE_ROWS) * stride * 4 if stride > ASSIGN_LDS_ATOMS else 0
+            budget = COST_BUDGET_BYTES if cost_budget is None else int(cost_budget)
+            chunk = max(1, min(P, budget // per_pair)) if per_pair else max(P, 1)
+            cost = torch.empty(chunk * per_pair // 4, **f32) if per_pair and P else None  # (one buffer: the launches run in stream order)
+            for a in range(0, max(P, 1), chunk):
+                b = min(a + chunk, P)
+                r = _hip.StructureMatchResultC(*[_hip.ptr(out[k][a:b]).value if P else None for k in PAIR_KEYS],
+                                               _hip.ptr(scratch[a:b]).value if scratch is not None and P else None, stride)
+                _hip.check(_hip.lib().arreau_structure_match_assigned(
+                    *side(x_batch, Bx, Nx), *side(y_batch, By, Ny), _hip.ptr(pairs[a:b]) if P else None, b - a, ctypes.byref(c), ctypes.byref(r),
+                    ASSIGNMENTS[p.assignment], _hip.ptr(cost), _hip.stream_ptr(dev)), "arreau_structure_match_assigned")
     out["pairs"] = pairs
     return out
 
@@ -290,13 +335,13 @@ def stats_of(result, rank=0):
     norm, rms = np.asarray(result["rms_norm"], dtype=np.float64).reshape(-1), np.asarray(result["rms"], dtype=np.float64).reshape(-1)
     return {"rank": cb.rank_of(rank), "attempted": int(flags.size), "matched": int(ok.sum()),
             "sum_rms_norm": float(norm[ok].sum()), "sum_rms": float(rms[ok].sum()),
-            "flags": cb.flag_counts(flags, FLAG_NAMES)}
+            "flags": cb.flag_counts(flags, ALL_FLAG_NAMES)}
 
 
 def total_stats(parts):
     return {"rank": "total", "attempted": sum(p["attempted"] for p in parts), "matched": sum(p["matched"] for p in parts),
             "sum_rms_norm": sum(p["sum_rms_norm"] for p in parts), "sum_rms": sum(p["sum_rms"] for p in parts),
-            "flags": {n: sum(p["flags"][n] for p in parts) for _, n in FLAG_NAMES}}
+            "flags": {n: sum(p["flags"].get(n, 0) for p in parts) for _, n in ALL_FLAG_NAMES}}
 
 
 def match_rate(st) -> float:
@@ -352,6 +397,86 @@ def norm_bound(n, l1, D, rms, ell, det_gm):
     return distance_bound(n, l1, D, rms) / ell + (rms / ell) * (103.0 * rho + 9.0) * U
 
 
+def cost_bound(l1, lam, c):
+    """|float32 - exact| of one entry c (A^2) of a candidate's cost matrix, lam the smallest eigenvalue of its mean metric."""
+    return 342.0 * U * l1 * l1 / lam * c + 216.0 * U * l1 * math.sqrt(c) + (108.0 * U * l1) ** 2 + 2.0 ** -25
+
+
+def solver_bound(n, l1, lam, optimum):
+    """SOLVER_BOUND: the most by which the exact sum of the kernel's assignment can exceed the true optimum sum (module docstring)."""
+    a, b, c0 = 342.0 * U * l1 * l1 / lam, 216.0 * U * l1, (108.0 * U * l1) ** 2 + 2.0 ** -25
+    f = a * optimum + b * math.sqrt(n * optimum) + n * c0
+    root = (b * math.sqrt(n) + math.sqrt(b * b * n + 8.0 * (1.0 - a) * f)) / (2.0 * (1.0 - a))
+    return root * root
+
+
+# ------------------------------------------------------------------------------------------------- the assignment (numpy)
+def linear_assignment(cost):
+    """The one-to-one map rows -> columns of the smallest sum of a square cost matrix (+inf: the pair is excluded), by shortest
+    augmenting paths as rule 6b states them: column duals 0, a row keeps the column of its row minimum (the smallest j on
+    ties: the nearest partner) when it is the smallest row that claims it, the free rows are augmented in ascending order, the
+    unscanned column of the smallest reduced distance is scanned next, ties to the smallest j.  Returns (columns [n], column duals
+    [n]); a ValueError where no one-to-one map avoids the excluded pairs."""
+    C = np.asarray(cost, dtype=np.float64)
+    n = C.shape[0]
+    assert C.shape == (n, n)
+    start = C.argmin(axis=1)  # (the row duals are the row minima, implicitly: what makes the start dual feasible)
+    x, y, v = np.full(n, -1, np.int64), np.full(n, -1, np.int64), np.zeros(n)
+    for i in range(n):
+        if np.isfinite(C[i, start[i]]) and y[start[i]] < 0:
+            x[i], y[start[i]] = start[i], i
+    for f in np.nonzero(x < 0)[0]:
+        with np.errstate(invalid="ignore"):
+            d = C[f] - v
+        pred, open_ = np.full(n, f, np.int64), np.isfinite(d)
+        while True:
+            if not open_.any():
+                raise ValueError("linear_assignment: no one-to-one map avoids the excluded pairs")
+            j1 = int(np.where(open_, d, np.inf).argmin())
+            lowest, open_[j1] = d[j1], False
+            if not np.isfinite(lowest):
+                raise ValueError("linear_assignment: no one-to-one map avoids the excluded pairs")
+            i = int(y[j1])
+            if i < 0:
+                break
+            with np.errstate(invalid="ignore"):
+                nd = C[i] - v - (C[i, j1] - v[j1] - lowest)
+            better = open_ & (nd < d)
+            d[better], pred[better] = nd[better], i
+        scanned = ~open_ & np.isfinite(d)
+        v[scanned] += d[scanned] - lowest
+        j = j1
+        while True:
+            i = int(pred[j])
+            y[j], x[i], j = i, j, int(x[i])
+            if i == f:
+                break
+    return x, v
+
+
+def assignment_gap(cost, columns, duals):
+    """The gap of an optimal assignment to the runner-up: the smallest optimum with one edge (i, columns[i]) forbidden, minus the
+    optimum (+inf where there is no other map).  With the optimal duals the reduced costs R >= 0 vanish on the map; forbidding
+    (i, columns[i]) costs the shortest path from row i back to its column through the other rows: R[i, j] + dist(j -> columns[i]),
+    dist the shortest paths between columns under R[row of j, j'] (Floyd-Warshall)."""
+    C = np.asarray(cost, dtype=np.float64)
+    n = C.shape[0]
+    if n < 2:
+        return float("inf")
+    x = np.asarray(columns, dtype=np.int64)
+    rows = np.empty(n, np.int64)
+    rows[x] = np.arange(n)
+    u = C[np.arange(n), x] - duals[x]
+    R = np.maximum(C - u[:, None] - duals[None, :], 0.0)
+    D = R[rows].copy()  # [j, j']: leave column j through its row
+    np.fill_diagonal(D, 0.0)
+    for k in range(n):
+        D = np.minimum(D, D[:, k, None] + D[None, k, :])
+    R = R.copy()
+    R[np.arange(n), x] = np.inf  # the forbidden edge itself
+    return float((R + D[:, x].T).min())
+
+
 # -------------------------------------------------------------------------------------------------- the numpy restatement
 _IMAGES = np.stack(np.meshgrid([-1, 0, 1], [-1, 0, 1], [-1, 0, 1], indexing="ij"), -1).reshape(27, 3).astype(np.float64)  # s_0 slowest
 
@@ -386,16 +511,18 @@ def mapping_deviations(Lx, Ly):
         return codes, W, (np.abs(lp - lx) / lx).max(axis=1), np.abs(ap - ax).max(axis=1), Gp
 
 
-def evaluate_candidate(w, v, tx, ty, Gx, Gp, W, t=None, q=None, p0=None, partner=None):
+def evaluate_candidate(w, v, tx, ty, Gx, Gp, W, t=None, q=None, p0=None, partner=None, assignment="nearest"):
     """Rules 3, 4, 6 in float64 for one mapping W (G' = Gp) and either a start atom q (the search: t = wrap(w_p0 - v'_q), nearest
-    partners) or a given translation t' and partner map (the check of a device's choice).  Returns a namespace: partner [n],
-    permutation (bool), nearest / second [n] (A; the search only), translation t' [3], e [n,3] (the differences under t'), rms,
-    max_dist, ell, det_gm."""
+    partners; with assignment "optimal" the optimal assignment where those are not one-to-one, rule 6b) or a given translation t'
+    and partner map (the check of a device's choice).  Returns a namespace: partner [n], permutation (bool: the nearest-partner
+    map is one-to-one), nearest / second [n] (A; the search only), translation t' [3], e [n,3] (the differences under t'), rms,
+    max_dist, ell, det_gm, lam (the smallest eigenvalue of G_m); solved (bool) and, where it is, optimum (the smallest sum, A^2)
+    and gap (to the runner-up assignment, A^2)."""
     n = len(w)
     V = np.rint(np.linalg.inv(W.astype(np.float64)))
     vp = ss._wrap01(v @ V.T)
     Gm = (Gx + Gp) / 2.0
-    out = SimpleNamespace(nearest=None, second=None, permutation=True)
+    out = SimpleNamespace(nearest=None, second=None, permutation=True, solved=False, optimum=None, gap=None)
     if partner is None:
         t0 = ss._wrap01(w[p0] - vp[q])
         d2, e = _nearest_image((vp[None, :, :] + t0[None, None, :]) - w[:, None, :], Gm)  # [i, j]
@@ -404,11 +531,15 @@ def evaluate_candidate(w, v, tx, ty, Gx, Gp, W, t=None, q=None, p0=None, partner
         srt = np.sqrt(np.sort(d2, axis=1))
         out.nearest, out.second = srt[:, 0], (srt[:, 1] if n > 1 else np.full(n, np.inf))
         out.permutation = len(set(partner.tolist())) == n
+        if not out.permutation and assignment == "optimal":
+            partner, duals = linear_assignment(d2)
+            out.solved, out.optimum = True, float(d2[np.arange(n), partner].sum())
+            out.gap = assignment_gap(d2, partner, duals)
         t = t0 - e[np.arange(n), partner].mean(axis=0)
     out.partner, out.translation = np.asarray(partner, dtype=np.int64), np.asarray(t, dtype=np.float64)
     d2, out.e = _nearest_image((vp[out.partner] + out.translation[None, :]) - w, Gm)
     out.rms, out.max_dist = math.sqrt(float(d2.mean())), math.sqrt(float(d2.max()))
-    out.det_gm = float(np.linalg.det(Gm))
+    out.det_gm, out.lam = float(np.linalg.det(Gm)), float(np.linalg.eigvalsh(Gm)[0])
     out.ell = (math.sqrt(out.det_gm) / n) ** (1.0 / 3.0) if out.det_gm > 0 else float("nan")
     return out
 
@@ -419,7 +550,9 @@ def structure_match_reference_f64(x, y, pairs, params=None, details=False):
     x) and per pair `D` (the largest |component| of a difference under the best candidate's t'), `ell`, `det_gm`, `l1`.
     details=True adds, per pair (None where the decision is not reached): `length_dev` and `angle_dev` (of every candidate of det
     +-1), `nearest` and `second` ([candidates, n], A: the nearest and second-nearest partner distance of every candidate and atom)
-    and `survivors`, the list of (rms, code, q) of every candidate whose map is a permutation, sorted."""
+    and `survivors`, the list of (rms, code, q) of every candidate whose map is a permutation, sorted; and, what params.assignment
+    "optimal" adds, `contenders` (the sorted (rms, code, q) of every candidate that stands for the minimum: the survivors and the
+    solved ones) and `solved`, one dict per candidate the assignment step solved: code, q, n, optimum, gap, lam, rms."""
     p = params if params is not None else StructureMatchParams()
     fx, Lx, cx, tx, firstx = cb.inputs(*x)
     fy, Ly, cy, ty, firsty = cb.inputs(*y)
@@ -430,7 +563,8 @@ def structure_match_reference_f64(x, y, pairs, params=None, details=False):
                           translation=np.zeros((P, 3)), partner=np.full((P, stride), -1, np.int32), n_mappings=np.zeros(P, np.int32),
                           n_candidates=np.zeros(P, np.int32), n_permutations=np.zeros(P, np.int32), matched=np.zeros(P, np.int32),
                           flags=np.zeros(P, np.int32), D=np.zeros(P), ell=np.full(P, np.nan), det_gm=np.full(P, np.nan), l1=np.zeros(P),
-                          length_dev=[None] * P, angle_dev=[None] * P, nearest=[None] * P, second=[None] * P, survivors=[None] * P)
+                          length_dev=[None] * P, angle_dev=[None] * P, nearest=[None] * P, second=[None] * P, survivors=[None] * P,
+                          contenders=[None] * P, solved=[None] * P)
     for k, (bx, by) in enumerate(pairs):
         if not (0 <= bx < len(cx) and 0 <= by < len(cy)):
             out.flags[k] = BAD_PAIR
@@ -467,18 +601,23 @@ def structure_match_reference_f64(x, y, pairs, params=None, details=False):
         rare = species[int(np.argmin(cnt))]  # the fewest atoms, the smallest id on ties
         p0, qs = int(np.nonzero(sx == rare)[0][0]), np.nonzero(sy == rare)[0]
         out.n_candidates[k] = len(keep) * len(qs)
-        nearest, second, survivors, best = [], [], [], None
+        nearest, second, survivors, contenders, solved, best = [], [], [], [], [], None
         for m in keep:
             for q in qs:
-                c = evaluate_candidate(w, v, sx, sy, Gx, Gp[m], W[m], q=int(q), p0=p0)
+                c = evaluate_candidate(w, v, sx, sy, Gx, Gp[m], W[m], q=int(q), p0=p0, assignment=p.assignment)
                 nearest.append(c.nearest)
                 second.append(c.second)
+                key = (c.rms, int(codes[m]), int(q))
                 if c.permutation:
-                    key = (c.rms, int(codes[m]), int(q))
                     survivors.append(key)
+                if c.solved:
+                    solved.append({"code": int(codes[m]), "q": int(q), "n": n, "optimum": c.optimum, "gap": c.gap, "lam": c.lam, "rms": c.rms})
+                if c.permutation or c.solved:
+                    contenders.append(key)
                     if best is None or key < best[0]:
                         best = (key, c)
         out.nearest[k], out.second[k], out.survivors[k] = np.array(nearest), np.array(second), sorted(survivors)
+        out.contenders[k], out.solved[k] = sorted(contenders), solved
         out.n_permutations[k] = len(survivors)
         if best is None:
             out.flags[k] |= NO_PERMUTATION
@@ -488,6 +627,8 @@ def structure_match_reference_f64(x, y, pairs, params=None, details=False):
         out.partner[k, :n] = c.partner
         out.rms_norm[k], out.ell[k], out.det_gm[k], out.D[k] = rms / c.ell, c.ell, c.det_gm, float(np.abs(c.e).max())
         out.matched[k] = int(out.rms_norm[k] <= stol)
+        if c.solved:
+            out.flags[k] |= ASSIGNED
     if not details:
-        del out.length_dev, out.angle_dev, out.nearest, out.second, out.survivors
+        del out.length_dev, out.angle_dev, out.nearest, out.second, out.survivors, out.contenders, out.solved
     return out

@@ -42,7 +42,7 @@ combined with --screen / --require_valid; the two do not interact.
 Structure match: `--match_to FILE` (`--ltol`, `--angle_tol`, `--stol`) matches every generated crystal on the device, at the end of
 its sampling call, against every target of its composition in that crystals file (diffusion/structure_match.py) and keeps the best:
 match rate (matched / attempted) and mean rms_norm and rms over the matched, per rank and in total, and match_* arrays in the
-output file.  No Hungarian assignment, no supercells (combine with a reduced target file), no volume scaling.
+output file.  The optimal assignment only with `--assignment optimal`, no supercells (combine with a reduced target file), no volume scaling.
 """
 import argparse
 import contextlib
@@ -320,6 +320,9 @@ def add_structure_match_arguments(ap):
     ap.add_argument("--ltol", type=float, default=0.2, help="match_to: relative tolerance on the cell lengths (StructureMatcher's default)")
     ap.add_argument("--angle_tol", type=float, default=5.0, help="match_to: tolerance on the cell angles, degrees")
     ap.add_argument("--stol", type=float, default=0.3, help="match_to: a pair matches when rms / (V / n)^(1/3) is at most this")
+    ap.add_argument("--assignment", choices=("nearest", "optimal"), default="nearest",
+                    help="match_to: what becomes of a candidate whose nearest-partner map is not one-to-one -- nearest: it is dropped; "
+                         "optimal: it gets the optimal assignment (StructureMatcher's)")
 
 
 def instrument_params(keyword, args, error):

@@ -24,7 +24,7 @@ symmetrized_* arrays) in the same way.  With `--reduce_cell` too the reduction r
 rms_norm and rms over the matched, and the count per flag; `--match_mode paired` matches crystal b against target b, `any` against
 every target of its composition (the best one counts); without the flag the match is paired when the two files hold equally many
 crystals.  It runs after `--reduce_cell` and `--symmetrize` when those are given, on their crystals, and the targets are then put
-through the same reduction and symmetrization; `--out` gets the match_* arrays.  No Hungarian assignment, no supercells, no
+through the same reduction and symmetrization; `--out` gets the match_* arrays.  The optimal assignment only with `--assignment optimal`, no supercells, no
 volume scaling.
 """
 import argparse

@@ -577,8 +577,9 @@ int arreau_crystal_symmetrize(const float* d_frac, const int32_t* d_types, const
  * The sixth instrument: for every pair (x, y) of a pair list, x a crystal of batch X and y one of batch Y (Y may be X), the
  * change of basis W and the translation under which y's atoms fall next to x's, the atom-to-atom map and the root-mean-square
  * displacement, in A and normalised as pymatgen's StructureMatcher normalises it.  One launch, one workgroup of four waves per
- * pair, no atomics, no arreau_model, no synchronisation; deterministic.  NOT computed: an optimal assignment where the
- * nearest-partner map is no permutation (no Hungarian step: such a candidate is skipped, rule 6); supercells, formula reduction
+ * pair, no atomics, no arreau_model, no synchronisation; deterministic.  Where the nearest-partner map of a candidate is no
+ * permutation the candidate is skipped (rule 6) unless the assignment mode OPTIMAL is asked for (arreau_structure_match_assigned):
+ * then the optimal (Hungarian-type) assignment is solved for it, rule 6b.  NOT computed: supercells, formula reduction
  * or anonymous species (the species multisets are compared exactly: run arreau_crystal_reduce first); a rescaling of the cells
  * to one volume; a mapping W with an entry outside {-1, 0, 1} (complete for two Delaunay-reduced cells, rule 2).
  * Conventions as in the symmetry search: cell rows a_0, a_1, a_2, fractional columns, the metric G = L L^T, column j of W the
@@ -607,6 +608,20 @@ int arreau_crystal_symmetrize(const float* d_frac, const int32_t* d_types, const
  *      dropped; n_permutations counts the others.  For those t' = t - (sum_i e_i) / n, summed in atom order from 0: the
  *      least-squares translation of that map (not wrapped); d_i^2 = dist^2 of (v'_p(i) + t') - w_i, rms = sqrt((sum_i d_i^2) / n),
  *      max_dist = sqrt(max_i d_i^2).  Where the nearest-partner map is a permutation it is the optimal assignment.
+ *  6b. assignment OPTIMAL (arreau_structure_match_assigned; NEAREST is rule 6 as it stands).  A candidate whose p is not one-to-one
+ *      is not dropped: its map becomes the one-to-one, species-preserving map that minimises sum_i c(i, p(i)), c(i, j) = dist^2 of
+ *      (v'_j + t) - w_i exactly as rule 4 forms it in float32, at the UNREFINED t of rule 5, each c rounded to the nearest multiple
+ *      of 2^-24 A^2 and the sums formed exactly (64-bit integers), so the minimum does not depend on an order of operations; pairs
+ *      of different species are excluded.  Rule 1 makes such a map exist, so every candidate survives and NO_PERMUTATION is not
+ *      set.  e_i is the difference of the image that attains dist^2 for the chosen partner; from there rule 6 goes on unchanged:
+ *      t' = t - (sum_i e_i) / n in atom order, the distances once more under t', rms and max_dist -- one pass, as
+ *      StructureMatcher._cart_dists does it.  The solver is a shortest-augmenting-path one (Jonker-Volgenant): column duals start
+ *      at 0, a row keeps its nearest partner when it is the smallest row that claims that column, the remaining (free) rows are
+ *      augmented in ascending i, and the unscanned column of the smallest reduced distance is taken next, ties to the smallest j.
+ *      Where several maps attain the minimum, this order decides; it depends on the inputs alone, not on the launch.
+ *      n_permutations keeps its meaning (the candidates whose nearest-partner map was one-to-one; n_candidates - n_permutations
+ *      were solved), and the flag ASSIGNED (informational: it does not make a pair unmatched) says that the winning candidate's
+ *      map came from this step.
  *   7. result.  The candidate of the smallest rms, ties to the smaller code, then the smaller q: rms and max_dist in A, rms_norm =
  *      rms / l, mapping = the code of W, translation = t', partner[p, i] = p(i) (local to y; -1 from x's atom count to
  *      partner_stride), matched = (rms_norm <= stol).  NO_PERMUTATION when mappings exist and no candidate survived (the outputs
@@ -617,7 +632,8 @@ int arreau_crystal_symmetrize(const float* d_frac, const int32_t* d_types, const
  *      derived there.
  *   9. argument errors (ARREAU_EINVAL, nothing launched): NULL params / result / arrays, negative sizes, ltol, angle_tol or stol
  *      not finite or not positive, max_mappings outside 1..ARREAU_SM_MAX_MAPPINGS_CAP, a partner_stride above 256 without scratch.
- *      P = 0 is a no-op.
+ *      P = 0 is a no-op.  arreau_structure_match_assigned also: an assignment outside {0, 1}; OPTIMAL with a partner_stride above
+ *      ARREAU_SM_ASSIGN_LDS_ATOMS and d_cost NULL.
  * Crystals of up to 256 atoms keep their coordinates, species and the four partner maps under test in LDS; larger ones read global
  * memory and keep the maps in out->scratch (the same values).  Cost: n_mappings x n_rarest x n^2 x 27 metric evaluations per pair.
  * Offsets outside [0, N] or descending are clamped as in the screen. */
@@ -629,7 +645,12 @@ int arreau_crystal_symmetrize(const float* d_frac, const int32_t* d_types, const
 #define ARREAU_SM_NO_MAPPING 32
 #define ARREAU_SM_OVERFLOW 64
 #define ARREAU_SM_NO_PERMUTATION 128
+#define ARREAU_SM_ASSIGNED 256 /* informational: the winning candidate's map came from the assignment step (rule 6b) */
 #define ARREAU_SM_MAX_MAPPINGS_CAP 4096
+#define ARREAU_SM_ASSIGN_NEAREST 0
+#define ARREAU_SM_ASSIGN_OPTIMAL 1
+#define ARREAU_SM_ASSIGN_LDS_ATOMS 24  /* crystals of up to this many atoms keep the four cost matrices under test in LDS */
+#define ARREAU_SM_ASSIGN_STATE_ROWS 6  /* rows of solver state behind every cost matrix of d_cost */
 typedef struct arreau_structure_match_params {
     float ltol;           /* relative tolerance on the cell lengths; default 0.2 (StructureMatcher's) */
     float angle_tol;      /* radians; default 5 degrees */
@@ -658,6 +679,16 @@ int arreau_structure_match(const float* x_frac, const int32_t* x_types, const fl
                            int32_t Nx, const float* y_frac, const int32_t* y_types, const float* y_lattice, const int32_t* y_offsets,
                            int32_t By, int32_t Ny, const int32_t* d_pairs, int32_t P, const arreau_structure_match_params* params,
                            arreau_structure_match_result* out, void* stream);
+/* The same with the assignment mode of rule 6b: ARREAU_SM_ASSIGN_NEAREST is arreau_structure_match bit for bit, ARREAU_SM_ASSIGN_OPTIMAL
+ * solves the assignment of every candidate whose nearest-partner map is not one-to-one.  d_cost: device scratch of
+ * P x 4 x (partner_stride + ARREAU_SM_ASSIGN_STATE_ROWS) x partner_stride floats -- per pair and wave a cost matrix
+ * [partner_stride, partner_stride] and the rows of solver state (used by crystals above 256 atoms; smaller ones keep it in LDS);
+ * may be NULL when partner_stride <= ARREAU_SM_ASSIGN_LDS_ATOMS or assignment is NEAREST.  Its contents are not an output. */
+int arreau_structure_match_assigned(const float* x_frac, const int32_t* x_types, const float* x_lattice, const int32_t* x_offsets, int32_t Bx,
+                                    int32_t Nx, const float* y_frac, const int32_t* y_types, const float* y_lattice,
+                                    const int32_t* y_offsets, int32_t By, int32_t Ny, const int32_t* d_pairs, int32_t P,
+                                    const arreau_structure_match_params* params, arreau_structure_match_result* out, int32_t assignment,
+                                    float* d_cost, void* stream);
 
 /* ---- the score network ---------------------------------------------------------------------- */
 
