@@ -30,6 +30,7 @@ EXPORTS = [
     "arreau_sample_loop_resampled", "arreau_resample_jump", "arreau_optimizer_step_ema",
     "arreau_sample_loop_tied", "arreau_reverse_step_tied", "arreau_resample_jump_tied",
     "arreau_sample_loop_sym", "arreau_reverse_step_sym", "arreau_crystal_screen",
+    "arreau_sample_loop_eta", "arreau_reverse_step_eta",
     "arreau_crystal_fingerprint", "arreau_fingerprint_match", "arreau_crystal_symmetry", "arreau_crystal_reduce",
     "arreau_crystal_symmetrize", "arreau_structure_match", "arreau_structure_match_assigned",
 ]
@@ -208,10 +209,12 @@ def _prototypes():
         "arreau_sample_loop_resampled": loop + [cond, sched, corr, res, vp],
         "arreau_sample_loop_tied": loop + [cond, sched, corr, res, vp, vp],
         "arreau_sample_loop_sym": loop + [cond, sched, corr, res, vp, sym, vp],
+        "arreau_sample_loop_eta": loop + [cond, sched, corr, res, vp, f32, vp],
         "arreau_condition_initial_state": [vp] * 4 + [i32, i32, i32, u64, cond, vp],
         "arreau_reverse_step_to": step_to + [vp],
         "arreau_reverse_step_tied": step_to + [vp, vp],
         "arreau_reverse_step_sym": step_to + [vp, sym, vp],
+        "arreau_reverse_step_eta": step_to + [vp, f32, vp],
         "arreau_corrector_step": [vp] * 4 + [i32, i32, vp, vp, f32, cond, vp],
         "arreau_resample_jump": jump + [vp],
         "arreau_resample_jump_tied": jump + [vp, vp],

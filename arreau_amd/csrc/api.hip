@@ -347,8 +347,8 @@ struct ResamplePlan {
 
 // The key of a captured step: the buffers, sizes and seed, the plan (every kernel choice of the evaluation), and the condition's
 // pointers, the schedule's table and clip, the corrector's step count and snr, the resampling's R and J (a resampled step reads
-// the pass word), the lattice systems' tie array and the symmetry tables, which are kernel arguments or launch choices of the
-// capture: a change of any of them must not replay the stale graph.
+// the pass word), the lattice systems' tie array, the symmetry tables and the eta of a DDIM-style step, which are kernel arguments
+// or launch choices of the capture: a change of any of them must not replay the stale graph.
 SampleGraphKey sample_graph_key(const ScorePlan& score, const SampleState& st, const void* d_workspace, uint64_t seed,
                                 const StepOptions& opt, const ResamplePlan* plan) {
     SampleGraphKey k{};
@@ -367,6 +367,10 @@ SampleGraphKey sample_graph_key(const ScorePlan& score, const SampleState& st, c
         k.resample_passes = plan->passes;
         k.resample_jump = plan->jump;
     }
+    if (opt.eta >= 0.0f) {
+        k.eta_step = 1;
+        k.eta_bits = std::bit_cast<uint32_t>(opt.eta);
+    }
     return k;
 }
 
@@ -374,7 +378,7 @@ int sample_loop_impl(arreau_model* m, const SampleState& st, int32_t t_start, in
                      size_t workspace_bytes, int32_t use_graph, const arreau_sample_condition* condition,
                      const arreau_sample_schedule* schedule, const arreau_corrector* corrector,
                      const ResamplePlan* plan /* null: no resampling */, const int32_t* d_length_tie /* null: untied */,
-                     const arreau_symmetry* sym /* null: no symmetry */, void* stream) {
+                     const arreau_symmetry* sym /* null: no symmetry */, float eta /* negative: the ancestral step */, void* stream) {
     if (corrector) {
         const int rc = arreau_corrector_check(corrector->steps, corrector->snr, "arreau_sample_loop_corrected");
         if (rc) return rc;
@@ -412,6 +416,7 @@ int sample_loop_impl(arreau_model* m, const SampleState& st, int32_t t_start, in
     if (corrector && corrector->steps > 0) opt.corr = CorrectorDev{corrector->steps, corrector->snr};
     opt.length_tie = d_length_tie;
     opt.sym = sym;
+    opt.eta = eta;
     if (n_steps == 0) return ARREAU_OK;
     hipStream_t s = (hipStream_t)stream;
     ARREAU_REQUIRE(!sym || (opt.cond == nullptr && opt.corr.steps == 0 && plan == nullptr),
@@ -526,7 +531,7 @@ int sample_loop(const char* who, arreau_model* m, const SampleState& st, int32_t
                 void* d_workspace, size_t workspace_bytes, int32_t use_graph, void* stream,
                 const arreau_sample_condition* condition = nullptr, const arreau_sample_schedule* schedule = nullptr,
                 const arreau_corrector* corrector = nullptr, const arreau_resampling* resampling = nullptr,
-                const int32_t* d_length_tie = nullptr, const arreau_symmetry* sym = nullptr) {
+                const int32_t* d_length_tie = nullptr, const arreau_symmetry* sym = nullptr, float eta = -1.0f) {
     ResamplePlan plan{1, 1, {}};
     if (resampling) {
         int rc;
@@ -560,12 +565,12 @@ int sample_loop(const char* who, arreau_model* m, const SampleState& st, int32_t
         }
     }
     return sample_loop_impl(m, st, t_start, n_steps, seed, d_workspace, workspace_bytes, use_graph, condition, schedule, corrector,
-                            plan.passes > 1 ? &plan : nullptr, d_length_tie, sym, stream);
+                            plan.passes > 1 ? &plan : nullptr, d_length_tie, sym, eta, stream);
 }
 }  // namespace
 
-// The seven exports: each is the one before it plus one option (NULL: the loop without it), a thin adapter onto sample_loop.  The
-// rules of the options are stated in include/arreau_hip.h.
+// The exports: each of the first seven is the one before it plus one option (NULL: the loop without it), a thin adapter onto
+// sample_loop; arreau_sample_loop_eta is the tied one plus an eta.  The rules of the options are stated in include/arreau_hip.h.
 extern "C" int arreau_sample_loop(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
                                   const int32_t* d_off, int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed,
                                   const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice, void* d_workspace,
@@ -625,6 +630,19 @@ extern "C" int arreau_sample_loop_tied(arreau_model* m, float* d_frac, int32_t* 
     const SampleState st{d_frac, d_types, d_lengths, d_angles, d_off, B, N, d_const_types, d_fixed_lengths, d_lattice};
     return sample_loop("arreau_sample_loop_tied", m, st, t_start, n_steps, seed, d_workspace, workspace_bytes, use_graph, stream,
                        condition, schedule, corrector, resampling, d_length_tie);
+}
+
+extern "C" int arreau_sample_loop_eta(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                                      const int32_t* d_off, int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed,
+                                      const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice, void* d_workspace,
+                                      size_t workspace_bytes, int32_t use_graph, const arreau_sample_condition* condition,
+                                      const arreau_sample_schedule* schedule, const arreau_corrector* corrector,
+                                      const arreau_resampling* resampling, const int32_t* d_length_tie, float eta, void* stream) {
+    int rc;
+    if ((rc = arreau_eta_check(eta, "arreau_sample_loop_eta"))) return rc;
+    const SampleState st{d_frac, d_types, d_lengths, d_angles, d_off, B, N, d_const_types, d_fixed_lengths, d_lattice};
+    return sample_loop("arreau_sample_loop_eta", m, st, t_start, n_steps, seed, d_workspace, workspace_bytes, use_graph, stream,
+                       condition, schedule, corrector, resampling, d_length_tie, /*sym=*/nullptr, eta + 0.0f /* -0 -> +0 */);
 }
 
 extern "C" int arreau_sample_loop_sym(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,

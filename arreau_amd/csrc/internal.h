@@ -101,6 +101,8 @@ struct SampleGraphKey {
     int32_t corrector_steps;
     uint32_t snr_bits;         // the corrector's snr
     int32_t resample_passes, resample_jump;  // 0, 0: no resampling
+    int32_t eta_step;          // DDIM-style sampling: 1 when the steps are eta steps
+    uint32_t eta_bits;         // their eta
     bool operator==(const SampleGraphKey&) const = default;
 };
 
@@ -313,7 +315,11 @@ struct StepOptions {
     const int32_t* pass = nullptr;        // resampled loop: the device word of the pass index, word3 = 256 pass[0] (RESAMPLE)
     const int32_t* length_tie = nullptr;  // lattice systems: the tie code per crystal (TIE)
     const arreau_symmetry* sym = nullptr; // space-group symmetry: the orbit tables (SYM); not with a condition or a resampled loop
+    float eta = -1.0f;                    // DDIM-style step (ETA): the noise scale in [0, 1]; negative: the ancestral step.  Not with sym
 };
+// DDIM-style sampling (arreau_sample_loop_eta, arreau_reverse_step_eta; the rules are stated in include/arreau_hip.h):
+// ARREAU_EINVAL unless eta is finite and lies in [0, 1].
+int arreau_eta_check(float eta, const char* who);  // update.hip
 
 // One corrector move per crystal at timestep d_t[b]: z from the caller's d_z_frac [N,3], or (d_z_frac null) the Philox draw
 // (seed, t, ARREAU_DRAW_Z_CORRECTOR, element, iter; 256 pass[0] + iter with opt.pass).  Reads st.frac / offsets / B / N, opt.corr.snr,

@@ -5,7 +5,8 @@
 // VP_lattice.reverse_given_x0 (diffusion_helpers.py:185-199) on lengths, then lattice_from_params.
 // Note the reference adds `variance * z` (not sqrt(variance)) and zeroes z when t <= 1.
 // TIE: the lattice-system tie of the lengths (length_tie[b]); the three x0 and current lengths are exchanged by shuffles.
-template <bool TIE>
+// ETA: the eta move of the lengths (update_dev.h).
+template <bool TIE, bool ETA>
 __device__ __forceinline__ void reverse_lattice_body(int gt /* global thread of the lattice part */, float* __restrict__ lengths, const float* __restrict__ angles,
                                        const int32_t* __restrict__ tstep, const int32_t* __restrict__ offsets,
                                        const float* __restrict__ len0, StepNoiseSrc noise,
@@ -15,7 +16,8 @@ __device__ __forceinline__ void reverse_lattice_body(int gt /* global thread of 
                                        // sampling loop: pool the per-atom read-out here (same ordered sum as
                                        // readout_crystals_kernel) instead of a launch of its own; len0_out receives it
                                        const float* __restrict__ gs_atoms, float* __restrict__ len0_out, const SampleConditionDev* cond,
-                                       const StepScheduleDev* sched, uint32_t word3, const int32_t* __restrict__ length_tie) {
+                                       const StepScheduleDev* sched, uint32_t word3, const int32_t* __restrict__ length_tie,
+                                       float eta) {
     // four lanes per crystal: lane i < 3 owns length component i (pooling, update), lane 0 then writes the cell
     const int b = b0 + (gt >> 2), i = gt & 3;
     const bool live = b < B;  // (whole groups of four are live or not; the shuffles below need every lane)
@@ -41,11 +43,12 @@ __device__ __forceinline__ void reverse_lattice_body(int gt /* global thread of 
             xts[q] = __shfl(xt, lead + q, 64);
         }
         if (live && i < 3)
-            mylen = tied_length_component(b, i, code, x0s, xts, t, s_to, sched, lengths, noise, alpha_bars, betas, fixed_lengths, cond, word3);
+            mylen = tied_length_component<ETA>(b, i, code, x0s, xts, t, s_to, sched, lengths, noise, alpha_bars, betas, fixed_lengths, cond,
+                                               word3, eta);
     } else {
         if (live && i < 3)
-            mylen = reverse_length_component(b, i, t, s_to, sched, first, last, lengths, len0, noise, alpha_bars, betas, fixed_lengths,
-                                             gs_atoms, len0_out, cond, word3);
+            mylen = reverse_length_component<ETA>(b, i, t, s_to, sched, first, last, lengths, len0, noise, alpha_bars, betas, fixed_lengths,
+                                                  gs_atoms, len0_out, cond, word3, eta);
     }
     const int base = (threadIdx.x & 63) & ~3;
     float newlen[3];
@@ -78,7 +81,9 @@ __device__ __forceinline__ void reverse_lattice_body(int gt /* global thread of 
 // 2 a = b = c; rules in include/arreau_hip.h).  Without TIE `length_tie` is not read.
 // SYM: space-group symmetry (arreau_sample_loop_sym): the atom part runs reverse_atoms_body_sym on the orbit tables `sym_arg`
 // (a leader's wave updates its whole orbit, members leave).  Only without COND and RESAMPLE.  Without SYM `sym_arg` is not read.
-template <bool COND, bool SCHED, bool RESAMPLE, bool TIE, bool SYM>
+// ETA: DDIM-style sampling (arreau_sample_loop_eta): positions and lengths make the eta moves of update_dev.h, the noise scaled
+// by `eta` in [0, 1] and not read at 0; the species step is unchanged.  Not with SYM.  Without ETA `eta` is not read.
+template <bool COND, bool SCHED, bool RESAMPLE, bool TIE, bool SYM, bool ETA>
 __global__ __launch_bounds__(256) void reverse_kernel(
     int lat_blocks, float* __restrict__ lengths, const float* __restrict__ angles, const int32_t* __restrict__ tstep,
     const int32_t* __restrict__ offsets, const float* __restrict__ len0, StepNoiseSrc noise, const float* __restrict__ alpha_bars,
@@ -91,45 +96,51 @@ __global__ __launch_bounds__(256) void reverse_kernel(
     // sampling loop: the lattice part is one workgroup per crystal, which also prepares the next step (reverse_crystal_block)
     float* __restrict__ lattice_ws, float* __restrict__ cvec_next, const float* __restrict__ t_emb_w, const float* __restrict__ embT, int C,
     SampleConditionDev cond_arg, StepScheduleDev sched_arg, const int32_t* __restrict__ pass, const int32_t* __restrict__ length_tie,
-    arreau_symmetry sym_arg) {
+    arreau_symmetry sym_arg, float eta) {
     const uint32_t word3 = RESAMPLE ? 256u * (uint32_t)pass[0] : 0u;  // the counter word of pass r
     const SampleConditionDev* cond = COND ? &cond_arg : nullptr;
     const StepScheduleDev* sched = SCHED ? &sched_arg : nullptr;
     if ((int)blockIdx.x < lat_blocks && cvec_next != nullptr) {  // (kernel argument: uniform)
-        reverse_crystal_block<TIE>(b0 + (int)blockIdx.x, lengths, angles, tstep, offsets, len0, noise, alpha_bars, betas, T, lattice,
-                                   fixed_lengths, status, gs_atoms, len0_out, lattice_ws, cvec_next, t_emb_w, embT, S, C, cond, sched, word3,
-                                   length_tie);
+        reverse_crystal_block<TIE, ETA>(b0 + (int)blockIdx.x, lengths, angles, tstep, offsets, len0, noise, alpha_bars, betas, T, lattice,
+                                        fixed_lengths, status, gs_atoms, len0_out, lattice_ws, cvec_next, t_emb_w, embT, S, C, cond, sched,
+                                        word3, length_tie, eta);
         return;
     }
     if ((int)blockIdx.x < lat_blocks) {
-        reverse_lattice_body<TIE>(blockIdx.x * blockDim.x + threadIdx.x, lengths, angles, tstep, offsets, len0, noise, alpha_bars, betas, B_lat,
-                                  T, lattice, fixed_lengths, status, b0, gs_atoms, len0_out, cond, sched, word3, length_tie);
+        reverse_lattice_body<TIE, ETA>(blockIdx.x * blockDim.x + threadIdx.x, lengths, angles, tstep, offsets, len0, noise, alpha_bars, betas,
+                                       B_lat, T, lattice, fixed_lengths, status, b0, gs_atoms, len0_out, cond, sched, word3, length_tie, eta);
         return;
     }
     if constexpr (SYM) {
-        static_assert(!COND && !RESAMPLE, "the SYM instances are unconditioned and not resampled");
+        static_assert(!COND && !RESAMPLE && !ETA, "the SYM instances are unconditioned, not resampled and take no eta");
         reverse_atoms_body_sym((int)blockIdx.x - lat_blocks, frac, types, tstep, offsets, B, N, eps, logits, noise, ve_sigmas, q1t, qmats, S,
                                T, const_types, absorbing, status, n0, batch, sched, sym_arg);
     } else {
-        reverse_atoms_body((int)blockIdx.x - lat_blocks, frac, types, tstep, offsets, B, N, eps, logits, noise, ve_sigmas, q1t, qmats, S, T,
-                           const_types, absorbing, status, n0, batch, cond, sched, word3);
+        reverse_atoms_body<ETA>((int)blockIdx.x - lat_blocks, frac, types, tstep, offsets, B, N, eps, logits, noise, ve_sigmas, q1t, qmats, S, T,
+                                const_types, absorbing, status, n0, batch, cond, sched, word3, eta);
     }
 }
 
 namespace {
+// the instance of one step: TIE and RESAMPLE from the options' pointers
+template <bool COND, bool SCHED, bool ETA>
+auto reverse_kernel_of(const StepOptions& opt) {
+    return opt.length_tie ? (opt.pass ? reverse_kernel<COND, SCHED, true, true, false, ETA> : reverse_kernel<COND, SCHED, false, true, false, ETA>)
+                          : (opt.pass ? reverse_kernel<COND, SCHED, true, false, false, ETA> : reverse_kernel<COND, SCHED, false, false, false, ETA>);
+}
 template <bool COND, bool SCHED>
 void enqueue_reverse_kernel(const arreau_model* m, int lat_blocks, int atom_blocks, const SampleState& st, const ReverseInputs& in,
                             const SampleConditionDev& cond, const StepScheduleDev& sched, const StepOptions& opt, hipStream_t s) {
-    auto kernel = opt.length_tie ? (opt.pass ? reverse_kernel<COND, SCHED, true, true, false> : reverse_kernel<COND, SCHED, false, true, false>)
-                                 : (opt.pass ? reverse_kernel<COND, SCHED, true, false, false> : reverse_kernel<COND, SCHED, false, false, false>);
+    auto kernel = opt.eta >= 0.0f ? reverse_kernel_of<COND, SCHED, true>(opt) : reverse_kernel_of<COND, SCHED, false>(opt);
     if constexpr (!COND) {
-        if (opt.sym) kernel = opt.length_tie ? reverse_kernel<false, SCHED, false, true, true> : reverse_kernel<false, SCHED, false, false, true>;
+        if (opt.sym)
+            kernel = opt.length_tie ? reverse_kernel<false, SCHED, false, true, true, false> : reverse_kernel<false, SCHED, false, false, true, false>;
     }
     ARREAU_LAUNCH(kernel, dim3(lat_blocks + atom_blocks), dim3(256), 0, s, lat_blocks, st.lengths, st.angles, in.t, st.offsets, in.len0, in.noise,
                   m->vp_alpha_bars, m->vp_betas, st.B, m->T, st.lattice, st.fixed_lengths, m->status, 0, in.gs_atoms,
                   in.gs_atoms ? const_cast<float*>(in.len0) : nullptr, st.frac, st.types, st.B, st.N, in.eps, in.logits, m->ve_sigmas, m->q1t,
                   m->qmats, m->S, st.const_types, m->qmats_absorbing, 0, in.batch, in.lattice_ws, in.cvec_next, m->t_emb_w, m->embT, m->C,
-                  cond, sched, opt.pass, opt.length_tie, opt.sym ? *opt.sym : arreau_symmetry{});
+                  cond, sched, opt.pass, opt.length_tie, opt.sym ? *opt.sym : arreau_symmetry{}, opt.eta);
 }
 }  // namespace
 
@@ -146,6 +157,7 @@ int arreau_launch_reverse(const arreau_model* m, const SampleState& st, const Re
                    "reverse update: a respaced step takes either the next-timestep table or the per-crystal targets");
     ARREAU_REQUIRE(!opt.sym || (!conditioned && opt.pass == nullptr),
                    "reverse update: space-group symmetry is not combined with a condition or a resampled loop");
+    ARREAU_REQUIRE(!opt.sym || opt.eta < 0.0f, "reverse update: space-group symmetry is not combined with an eta");
     if (lat_blocks + atom_blocks == 0) return ARREAU_OK;
     const SampleConditionDev c = conditioned ? *opt.cond : SampleConditionDev{};
     const StepScheduleDev sc = scheduled ? *opt.sched : StepScheduleDev{};
@@ -175,16 +187,18 @@ static int reverse_step_to(const arreau_model* m, float* d_frac, int32_t* d_type
                            const int32_t* d_t, const int32_t* d_s, const int32_t* d_off, int32_t B, int32_t N, const float* d_eps,
                            const float* d_logits, const float* d_len0, const float* d_z_lattice, const float* d_z_frac,
                            const float* d_u_types, float* d_lattice, float lattice_clipmax, const int32_t* d_length_tie,
-                           const arreau_symmetry* sym, void* stream, const char* who) {
+                           const arreau_symmetry* sym, void* stream, const char* who, float eta = -1.0f /* negative: none */) {
+    // (at eta = 0 the draws of the lengths and positions are not read: their arrays may be null)
     ARREAU_REQUIRE(m && d_frac && d_types && d_lengths && d_angles && d_t && d_s && d_off && d_eps && d_logits && d_len0 &&
-                       d_z_lattice && d_z_frac && d_u_types && d_lattice, std::string(who) + ": null pointer");
+                       ((d_z_lattice && d_z_frac) || eta == 0.0f) && d_u_types && d_lattice, std::string(who) + ": null pointer");
     ARREAU_REQUIRE(B >= 1 && N >= 0, std::string(who) + ": bad size");
     ARREAU_REQUIRE(lattice_clipmax > 0.0f && lattice_clipmax <= 1.0f, std::string(who) + ": lattice_clipmax must lie in (0, 1]");
     const SampleState st{.frac = d_frac, .types = d_types, .lengths = d_lengths, .angles = d_angles, .offsets = d_off, .B = B, .N = N,
                          .lattice = d_lattice};
     const ReverseInputs in{d_t, d_eps, d_logits, d_len0, StepNoiseSrc{d_z_lattice, d_z_frac, d_u_types, 0}};
     const StepScheduleDev sched{nullptr, d_s, lattice_clipmax};
-    return arreau_launch_reverse(m, st, in, StepOptions{.sched = &sched, .length_tie = d_length_tie, .sym = sym}, (hipStream_t)stream);
+    return arreau_launch_reverse(m, st, in, StepOptions{.sched = &sched, .length_tie = d_length_tie, .sym = sym, .eta = eta},
+                                 (hipStream_t)stream);
 }
 
 extern "C" int arreau_reverse_step_to(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths,
@@ -204,6 +218,25 @@ extern "C" int arreau_reverse_step_tied(const arreau_model* m, float* d_frac, in
                                         float lattice_clipmax, const int32_t* d_length_tie, void* stream) {
     return reverse_step_to(m, d_frac, d_types, d_lengths, d_angles, d_t, d_s, d_off, B, N, d_eps, d_logits, d_len0, d_z_lattice, d_z_frac,
                            d_u_types, d_lattice, lattice_clipmax, d_length_tie, /*sym=*/nullptr, stream, "arreau_reverse_step_tied");
+}
+
+// DDIM-style sampling: an eta that is finite and lies in [0, 1], or ARREAU_EINVAL.
+int arreau_eta_check(float eta, const char* who) {
+    ARREAU_REQUIRE(std::isfinite(eta) && eta >= 0.0f && eta <= 1.0f, std::string(who) + ": eta must be finite and lie in [0, 1]");
+    return ARREAU_OK;
+}
+
+// arreau_reverse_step_tied as the eta step (rules in include/arreau_hip.h); the tie pointer may be NULL.
+extern "C" int arreau_reverse_step_eta(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths,
+                                       const float* d_angles, const int32_t* d_t, const int32_t* d_s, const int32_t* d_off, int32_t B,
+                                       int32_t N, const float* d_eps, const float* d_logits, const float* d_len0,
+                                       const float* d_z_lattice, const float* d_z_frac, const float* d_u_types, float* d_lattice,
+                                       float lattice_clipmax, const int32_t* d_length_tie, float eta, void* stream) {
+    int rc;
+    if ((rc = arreau_eta_check(eta, "arreau_reverse_step_eta"))) return rc;
+    return reverse_step_to(m, d_frac, d_types, d_lengths, d_angles, d_t, d_s, d_off, B, N, d_eps, d_logits, d_len0, d_z_lattice, d_z_frac,
+                           d_u_types, d_lattice, lattice_clipmax, d_length_tie, /*sym=*/nullptr, stream, "arreau_reverse_step_eta",
+                           eta + 0.0f /* -0 -> +0 */);
 }
 
 // arreau_reverse_step_tied with space-group symmetry (rules in include/arreau_hip.h); NULL = arreau_reverse_step_tied.

@@ -53,15 +53,36 @@ __device__ __forceinline__ float known_length_component(const SampleConditionDev
     return sqrtf(ab) * l0 + sqrtf(1.0f - ab) * z;
 }
 
+// DDIM-style sampling (arreau_sample_loop_eta / arreau_reverse_step_eta; the rules are stated in include/arreau_hip.h): the ETA
+// instances of the length and position updates.  eta in [0, 1] scales the step's injected noise; at eta = 0 the draws (kinds 0
+// and 1, or the caller's arrays, which may then be null) are not read.  The non-ETA instances do not see this code.
+// The length move from t to s, float32 in the order of the rule: zz is the draw (0 for t <= 1), read only when eta > 0.
+__device__ __forceinline__ float eta_length_move(float x0, float xt, float ab_t, float ab_s, float beta, float eta, float zz) {
+    const float den = 1.0f - ab_t;
+    const float var = (1.0f - ab_s) * beta / den;
+    const float k = sqrtf(fmaxf((1.0f - ab_s) * (1.0f - eta * eta * beta / den), 0.0f) / den);
+    float l = (sqrtf(ab_s) - k * sqrtf(ab_t)) * x0 + k * xt;
+    if (eta > 0.0f) l += eta * var * zz;
+    return l;
+}
+// The draw of length element e of the step at t for the eta move: none at eta = 0 (the array may be null) or for t <= 1.
+__device__ __forceinline__ float eta_length_draw(StepNoiseSrc noise, uint32_t e, int t, float eta, uint32_t word3) {
+    if (!(eta > 0.0f) || t <= 1) return 0.0f;
+    return noise.z_lattice ? noise.z_lattice[e] : philox_normal(noise.seed, (uint32_t)t, ARREAU_DRAW_Z_LATTICE, e, word3);
+}
+
 // One component of the length update of crystal b from timestep t to s (VP_lattice.reverse_given_x0 with t - 1 replaced by s;
 // the per-atom read-out is pooled here when gs_atoms is given: the ordered sum of readout_crystals_kernel).  Writes
 // lengths[3 b + i] and returns it.  A stride-1 step (always, without a schedule) takes beta from the model's betas table.
+// ETA: the move is eta_length_move's (the same beta, x0 and x_t); everything around it is as without.
+template <bool ETA = false>
 __device__ __forceinline__ float reverse_length_component(int b, int i, int t, int s, const StepScheduleDev* sched, int first, int last, float* __restrict__ lengths,
                                                           const float* __restrict__ len0, StepNoiseSrc noise,
                                                           const float* __restrict__ alpha_bars, const float* __restrict__ betas,
                                                           const float* __restrict__ fixed_lengths, const float* __restrict__ gs_atoms,
                                                           float* __restrict__ len0_out, const SampleConditionDev* cond,
-                                                          uint32_t word3 /* resampled loop: 256 r in pass r; else 0 */) {
+                                                          uint32_t word3 /* resampled loop: 256 r in pass r; else 0 */,
+                                                          float eta = 0.0f /* ETA only */) {
     const float* __restrict__ z = noise.z_lattice;
     const float n = (float)(last - first);
     const float ab_t = alpha_bars[t], ab_p = alpha_bars[s];
@@ -87,11 +108,17 @@ __device__ __forceinline__ float reverse_length_component(int b, int i, int t, i
     }
     const float x0 = pooled * n;  // pred_lengths_0 * num_atoms (diffusion_loss.py:338)
     const float xt = lengths[3 * b + i];
-    const float mean = (c0 * x0 + c1 * xt) / denom;
-    const float zdraw = z ? z[3 * b + i] : philox_normal(noise.seed, (uint32_t)t, ARREAU_DRAW_Z_LATTICE, 3u * b + i, word3);
-    const float zz = t > 1 ? zdraw : 0.0f;
+    float moved;
+    if constexpr (ETA) {
+        moved = eta_length_move(x0, xt, ab_t, ab_p, beta, eta, eta_length_draw(noise, 3u * b + i, t, eta, word3));
+    } else {
+        const float mean = (c0 * x0 + c1 * xt) / denom;
+        const float zdraw = z ? z[3 * b + i] : philox_normal(noise.seed, (uint32_t)t, ARREAU_DRAW_Z_LATTICE, 3u * b + i, word3);
+        const float zz = t > 1 ? zdraw : 0.0f;
+        moved = mean + variance * zz;
+    }
     // fixed-cell sampling (arreau_sample_loop, d_fixed_lengths): the given lengths are re-imposed after the update
-    float mylen = fixed_lengths ? fixed_lengths[3 * b + i] : mean + variance * zz;
+    float mylen = fixed_lengths ? fixed_lengths[3 * b + i] : moved;
     // conditioned sampling, rule 2: a known length is replaced before the cell is formed from it
     if (cond && cond->len_mask && cond->len_mask[b]) mylen = known_length_component(cond, b, i, t, s, noise.seed, alpha_bars, word3);
     lengths[3 * b + i] = mylen;
@@ -138,12 +165,13 @@ __device__ __forceinline__ float length_x0_component(int b, int i, int first, in
 }
 // Component i of the tied update (rule 1): an axis of the tied group G takes the leader's x_t and draw (element 3 b) and the group's
 // mean x0 (summed in axis order, divided by |G|), so every axis of G computes the same bits; the others their own.  x0s / xts: the
-// crystal's three x0 and current lengths.  Writes lengths[3 b + i] and returns it.
+// crystal's three x0 and current lengths.  Writes lengths[3 b + i] and returns it.  ETA: as in reverse_length_component.
+template <bool ETA = false>
 __device__ __forceinline__ float tied_length_component(int b, int i, int code, const float* x0s, const float* xts, int t, int s,
                                                        const StepScheduleDev* sched, float* __restrict__ lengths, StepNoiseSrc noise,
                                                        const float* __restrict__ alpha_bars, const float* __restrict__ betas,
                                                        const float* __restrict__ fixed_lengths, const SampleConditionDev* cond,
-                                                       uint32_t word3) {
+                                                       uint32_t word3, float eta = 0.0f /* ETA only */) {
     const bool tied = length_tied(code, i);
     const float* __restrict__ z = noise.z_lattice;
     const float ab_t = alpha_bars[t], ab_p = alpha_bars[s];
@@ -155,11 +183,17 @@ __device__ __forceinline__ float tied_length_component(int b, int i, int code, c
     const float variance = (1.0f - ab_p) * beta / denom;
     const float x0 = !tied ? x0s[i] : (code == 1 ? (x0s[0] + x0s[1]) / 2.0f : ((x0s[0] + x0s[1]) + x0s[2]) / 3.0f);
     const float xt = tied ? xts[0] : xts[i];
-    const float mean = (c0 * x0 + c1 * xt) / denom;
     const uint32_t e = 3u * b + (tied ? 0u : (uint32_t)i);
-    const float zdraw = z ? z[e] : philox_normal(noise.seed, (uint32_t)t, ARREAU_DRAW_Z_LATTICE, e, word3);
-    const float zz = t > 1 ? zdraw : 0.0f;
-    float mylen = fixed_lengths ? fixed_lengths[3 * b + i] : mean + variance * zz;  // a fixed cell: the (host-tied) given lengths
+    float moved;
+    if constexpr (ETA) {
+        moved = eta_length_move(x0, xt, ab_t, ab_p, beta, eta, eta_length_draw(noise, e, t, eta, word3));
+    } else {
+        const float mean = (c0 * x0 + c1 * xt) / denom;
+        const float zdraw = z ? z[e] : philox_normal(noise.seed, (uint32_t)t, ARREAU_DRAW_Z_LATTICE, e, word3);
+        const float zz = t > 1 ? zdraw : 0.0f;
+        moved = mean + variance * zz;
+    }
+    float mylen = fixed_lengths ? fixed_lengths[3 * b + i] : moved;  // a fixed cell: the (host-tied) given lengths
     if (cond && cond->len_mask && cond->len_mask[b]) mylen = known_length_component(cond, b, i, t, s, noise.seed, alpha_bars, word3);
     lengths[3 * b + i] = mylen;
     return mylen;
@@ -167,7 +201,8 @@ __device__ __forceinline__ float tied_length_component(int b, int i, int code, c
 
 // One wave per atom: VE_pbc.reverse on the fractional coordinates (diffusion_helpers.py:65-81) and
 // D3PM.reverse on the atom type (d3pm.py:74-110, 198-215), from timestep t to s (t - 1 without a schedule).  Lanes span the S
-// classes (2 per lane).
+// classes (2 per lane).  ETA: the position update is the eta move (rules in include/arreau_hip.h); the species half is unchanged.
+template <bool ETA = false>
 __device__ __forceinline__ void reverse_one_atom(
     int i /* atom (wave-uniform) */, int lane, float* __restrict__ frac, int32_t* __restrict__ types, const int32_t* __restrict__ tstep,
     const int32_t* __restrict__ offsets, int B, const float* __restrict__ eps,
@@ -176,7 +211,7 @@ __device__ __forceinline__ void reverse_one_atom(
     int T, const int32_t* __restrict__ const_types, int absorbing, int32_t* __restrict__ status,
     const int32_t* __restrict__ batch /* crystal of each atom, or null: searched in `offsets` */,
     const SampleConditionDev* cond /* conditioned sampling, or null */, const StepScheduleDev* sched /* respaced, or null */,
-    uint32_t word3 /* resampled loop: 256 r in pass r; else 0 */) {
+    uint32_t word3 /* resampled loop: 256 r in pass r; else 0 */, float eta = 0.0f /* ETA only */) {
     const float* __restrict__ z_frac = noise.z_frac;
     const float* __restrict__ u_types = noise.u_types;
     // crystal of this atom = largest b with offsets[b] <= i: a 64-ary search by the whole wave (each level one
@@ -202,10 +237,23 @@ __device__ __forceinline__ void reverse_one_atom(
         const float sp = ve_sigmas[s_to];  // t >= 1 here; the reference's t == 0 branch is unreachable in sampling
         const float s2 = s * s, sp2 = sp * sp;
         const size_t g = 3 * (size_t)i + lane;
-        const float mean = frac[g] - eps[g] * (s2 - sp2);
-        const float stdv = sqrtf((sp2 * (s2 - sp2)) / s2);
-        const float zf = z_frac ? z_frac[g] : philox_normal(noise.seed, (uint32_t)t, ARREAU_DRAW_Z_FRAC, (uint32_t)g, word3);
-        float fv = remainder_one(mean + stdv * zf);
+        float fv;
+        if constexpr (ETA) {
+            // x0 = x_t - sig_t^2 eps in the predictor's convention; the direction term keeps what the noise does not take
+            const float r = sp / s;
+            const float dir = sp * sqrtf((1.0f - eta * eta) + eta * eta * r * r);
+            float v = frac[g] - eps[g] * s * (s - dir);
+            if (eta > 0.0f) {  // (at eta = 0 the draw is not read: z_frac may be null)
+                const float zf = z_frac ? z_frac[g] : philox_normal(noise.seed, (uint32_t)t, ARREAU_DRAW_Z_FRAC, (uint32_t)g, word3);
+                v += eta * sp * sqrtf(1.0f - r * r) * zf;
+            }
+            fv = remainder_one(v);
+        } else {
+            const float mean = frac[g] - eps[g] * (s2 - sp2);
+            const float stdv = sqrtf((sp2 * (s2 - sp2)) / s2);
+            const float zf = z_frac ? z_frac[g] : philox_normal(noise.seed, (uint32_t)t, ARREAU_DRAW_Z_FRAC, (uint32_t)g, word3);
+            fv = remainder_one(mean + stdv * zf);
+        }
         if (cond && cond->pos_mask && cond->pos_mask[i]) fv = known_frac_component(cond, g, t, s_to, noise.seed, ve_sigmas, word3);  // rule 1
         frac[g] = fv;
     }
@@ -441,17 +489,18 @@ __device__ __forceinline__ int d3pm_reverse_class(int i, int lane, float l0, flo
 }
 
 // the form the stand-alone kernel uses: workgroup `blk` of four waves, one atom each
+template <bool ETA>
 __device__ __forceinline__ void reverse_atoms_body(
     int blk /* block of the atom part */, float* __restrict__ frac, int32_t* __restrict__ types, const int32_t* __restrict__ tstep,
     const int32_t* __restrict__ offsets, int B, int N, const float* __restrict__ eps,
     const float* __restrict__ logits, StepNoiseSrc noise,
     const float* __restrict__ ve_sigmas, const float* __restrict__ q1t, const float* __restrict__ qmats, int S,
     int T, const int32_t* __restrict__ const_types, int absorbing, int32_t* __restrict__ status, int n0,
-    const int32_t* __restrict__ batch, const SampleConditionDev* cond, const StepScheduleDev* sched, uint32_t word3) {
+    const int32_t* __restrict__ batch, const SampleConditionDev* cond, const StepScheduleDev* sched, uint32_t word3, float eta) {
     const int i = n0 + blk * 4 + (int)(threadIdx.x >> 6);  // atoms n0 .. N-1
     if (i >= N) return;  // wave-uniform; no block-level barrier below
-    reverse_one_atom(i, threadIdx.x & 63, frac, types, tstep, offsets, B, eps, logits, noise, ve_sigmas, q1t, qmats, S, T, const_types, absorbing,
-                     status, batch, cond, sched, word3);
+    reverse_one_atom<ETA>(i, threadIdx.x & 63, frac, types, tstep, offsets, B, eps, logits, noise, ve_sigmas, q1t, qmats, S, T, const_types,
+                          absorbing, status, batch, cond, sched, word3, eta);
 }
 
 // ---- space-group symmetry (arreau_sample_loop_sym / arreau_reverse_step_sym; rules in include/arreau_hip.h) -----------------
@@ -614,7 +663,8 @@ __device__ __forceinline__ void reverse_atoms_body_sym(
 // The step then needs no prep launch (the Cartesian positions, prep's other product, are formed by the neighbour-list waves
 // from the fractional coordinates).  Same arithmetic as reverse_lattice_body + prep_kernel, thread for thread.
 // TIE: the lattice-system tie of the lengths (length_tie[b]); the three x0 and current lengths are exchanged through LDS.
-template <bool TIE>
+// ETA: the eta move of the lengths.
+template <bool TIE, bool ETA>
 __device__ __forceinline__ void reverse_crystal_block(int b, float* __restrict__ lengths, const float* __restrict__ angles,
                                                       const int32_t* __restrict__ tstep, const int32_t* __restrict__ offsets,
                                                       const float* __restrict__ len0, StepNoiseSrc noise,
@@ -624,7 +674,8 @@ __device__ __forceinline__ void reverse_crystal_block(int b, float* __restrict__
                                                       float* __restrict__ len0_out, float* __restrict__ lattice_ws,
                                                       float* __restrict__ cvec_next, const float* __restrict__ t_emb_w,
                                                       const float* __restrict__ embT, int S, int C, const SampleConditionDev* cond,
-                                                      const StepScheduleDev* sched, uint32_t word3, const int32_t* __restrict__ length_tie) {
+                                                      const StepScheduleDev* sched, uint32_t word3, const int32_t* __restrict__ length_tie,
+                                                      float eta) {
     __shared__ float newlen[3];
     __shared__ float feat[ARREAU_T_EMB_DIM + ARREAU_N_CRYSTAL_FEATS];
     const int t_raw = tstep[b];
@@ -641,12 +692,12 @@ __device__ __forceinline__ void reverse_crystal_block(int b, float* __restrict__
         }
         __syncthreads();
         if (threadIdx.x < 3)
-            newlen[threadIdx.x] = tied_length_component(b, threadIdx.x, code, x0s, xts, t, s, sched, lengths, noise, alpha_bars, betas,
-                                                        fixed_lengths, cond, word3);
+            newlen[threadIdx.x] = tied_length_component<ETA>(b, threadIdx.x, code, x0s, xts, t, s, sched, lengths, noise, alpha_bars, betas,
+                                                             fixed_lengths, cond, word3, eta);
     } else {
         if (threadIdx.x < 3)
-            newlen[threadIdx.x] = reverse_length_component(b, threadIdx.x, t, s, sched, first, last, lengths, len0, noise, alpha_bars, betas,
-                                                           fixed_lengths, gs_atoms, len0_out, cond, word3);
+            newlen[threadIdx.x] = reverse_length_component<ETA>(b, threadIdx.x, t, s, sched, first, last, lengths, len0, noise, alpha_bars,
+                                                                betas, fixed_lengths, gs_atoms, len0_out, cond, word3, eta);
     }
     __syncthreads();
     const float* ang = angles + 3 * b;

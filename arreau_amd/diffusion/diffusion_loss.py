@@ -12,6 +12,7 @@ import torch
 import torch.nn as nn
 
 from . import corrector as pc
+from . import ddim
 from . import resampling as rs
 from . import respacing
 from . import screening
@@ -293,7 +294,7 @@ class DiffusionLoss(nn.Module):
                timesteps: Optional[Sequence[int]] = None, corrector_steps: int = 0,
                corrector_snr: float = pc.DEFAULT_SNR, resample_passes: int = 1, jump_length: int = 10,
                lattice_system=None, symmetry=None, screen=None, unique=None, find_symmetry=None, reduce_cell=None,
-               symmetrize=None, match_to=None) -> SampleResult:
+               symmetrize=None, match_to=None, eta: Optional[float] = None) -> SampleResult:
         """diffusion_loss.py:276-377.  The initial state is drawn on the host exactly like the reference (numpy
         uniforms for the angles, then randn lengths, randn fractional coordinates from torch's global CPU generator).
         Per-step noise:
@@ -355,6 +356,15 @@ class DiffusionLoss(nn.Module):
         per orbit.  Works with graph replay, respaced schedules, fixed cells, max_steps and frames; a condition, corrector steps,
         resampling and the host-noise modes are rejected.  None, or a sequence of None only, is the sampler as it was.  No
         sample-quality claim is made.
+        `eta` (extension, every noise mode): DDIM-style sampling (Song, Meng & Ermon 2021) -- a float in [0, 1] that scales the
+        noise every step injects into positions and lengths (ddim.py; rules in include/arreau_hip.h; arreau_sample_loop_eta /
+        arreau_reverse_step_eta): 1 is the ancestral step (up to rounding, and to the clip of the lengths' beta), 0 injects none,
+        so positions and lengths become a function of the initial state alone, whatever the seed.  The species keep the D3PM
+        step with its Gumbel draw: they are deterministic only where they are held (constant_atoms, a condition's known
+        species).  The draws keep their keys; at eta = 0 those of positions and lengths are not read (the host-noise modes
+        still draw them, so their generators advance as always).  Works with schedules, conditions, corrector steps, resampling
+        (its jumps are unchanged), fixed cells, lattice systems, graph replay and frames; with `symmetry` it is rejected.  None
+        is the sampler as it was, bit for bit.  No sample-quality claim is made.
         `screen` (extension, every noise mode and option): a screening.ScreenCriteria, or True for its defaults -- the final
         device state is screened in one launch before it is copied back (arreau_crystal_screen; rules in include/arreau_hip.h):
         shortest contact over all periodic images, cell volume, number density, mask state.  SampleResult.metrics then holds the
@@ -407,6 +417,7 @@ class DiffusionLoss(nn.Module):
         schedule = respacing.resolve_schedule(self.T, num_steps=num_steps, timesteps=timesteps)  # None: every timestep
         corrector_steps, corrector_snr = pc.check_corrector(corrector_steps, corrector_snr)
         resample_passes, jump_length = rs.check_resampling(resample_passes, jump_length)
+        eta = ddim.check_eta(eta) if eta is not None else None
         if resample_passes > 1 and visualization_setting in (VisualizationSetting.ALL, VisualizationSetting.ALL_DETAILED):
             raise ValueError("resampling (resample_passes > 1) takes visualization_setting NONE or LAST: a frame inside a block "
                              "would be overwritten by the block's next pass")
@@ -423,6 +434,8 @@ class DiffusionLoss(nn.Module):
             if unsupported:
                 raise ValueError("symmetry= is not supported with " + ", ".join(unsupported) + " yet (a follow-up); it runs in the "
                                  "Philox loop without a condition, correctors or resampling")
+            if eta is not None:
+                raise ValueError("symmetry= is not supported with eta= (the symmetric step has no DDIM-style form)")
             num_atoms_per_sample, lattice_system = sym_mod.batch_layout(specs, num_atoms_per_sample, lattice_system)
             num_samples_in_batch = len(specs)
             if constant_atoms is not None:
@@ -539,7 +552,7 @@ class DiffusionLoss(nn.Module):
                         eng.sample_loop(frac_d, types_d, len_d, ang_d, off_d, steps[start], end - start, seed, const_d, lattice_d,
                                         use_graph=bool(use_graph), fixed_lengths=fixed, condition=cond_d, next_table=next_d,
                                         lattice_clipmax=clipmax, corrector=corrector, resampling=resampling, length_tie=tie_d,
-                                        symmetry=sym_d)
+                                        symmetry=sym_d, eta=eta)
                         start = end
                     if j is not None:
                         vis_crystal_during_sampling(z_table, types_d.cpu().numpy(), lattice_d.cpu().numpy(),
@@ -574,7 +587,11 @@ class DiffusionLoss(nn.Module):
                         eng.corrector_step(frac_d, t_d, off_d, eps, gauss(N, 3), corrector_snr)
                         eps, logits, len0 = eng.predict_scores(frac_d, types_d, len_d, ang_d, t_d, off_d)
                     z_l, z_f, u_t = gauss(B, 3), gauss(N, 3), unif(N, S)
-                    if tie_d is not None:  # lattice systems: the tied step (s = t - 1 without a schedule is the plain step)
+                    if eta is not None:  # DDIM-style sampling: the eta step (tied or not; s = t - 1 without a schedule)
+                        s_d.fill_(timestep - 1 if schedule is None else successor[timestep])
+                        eng.reverse_step_eta(frac_d, types_d, len_d, ang_d, t_d, s_d, off_d, eps, logits, len0, z_l, z_f, u_t,
+                                             lattice_d, eta, tie_d, clipmax)
+                    elif tie_d is not None:  # lattice systems: the tied step (s = t - 1 without a schedule is the plain step)
                         s_d.fill_(timestep - 1 if schedule is None else successor[timestep])
                         eng.reverse_step_tied(frac_d, types_d, len_d, ang_d, t_d, s_d, off_d, eps, logits, len0, z_l, z_f, u_t,
                                               lattice_d, tie_d, clipmax)

@@ -226,7 +226,7 @@ class HipEngine:
 
     def sample_loop(self, frac, types, lengths, angles, offsets, t_start, n_steps, seed, const_types, lattice_out,
                     use_graph=False, fixed_lengths=None, condition=None, next_table=None, lattice_clipmax=0.999, corrector=None,
-                    resampling=None, length_tie=None, symmetry=None):
+                    resampling=None, length_tie=None, symmetry=None, eta=None):
         """n_steps iterations of the sampling loop in one library call (arreau_sample_loop; with any of the options below
         arreau_sample_loop_resampled, whose NULL options are the loop without them): in-place update of
         (frac, types, lengths); Philox noise keyed by (seed, timestep, draw, element).  `condition`: the device arrays of a
@@ -242,7 +242,14 @@ class HipEngine:
         `length_tie`: lattice systems (arreau_sample_loop_tied): a contiguous int32 [B] tensor on the device, the tie code of every
         crystal's lengths (0 none, 1 a = b, 2 a = b = c; lattice_systems.py); None is the loop without it.
         `symmetry`: space-group symmetry (arreau_sample_loop_sym): the dict of device tables of symmetry.device_arrays; None is
-        the loop without it.  Not with `condition`, corrector steps or resampling passes > 1 (the library rejects them)."""
+        the loop without it.  Not with `condition`, corrector steps or resampling passes > 1 (the library rejects them).
+        `eta`: DDIM-style sampling (arreau_sample_loop_eta): a float in [0, 1] that scales the noise every step injects into
+        positions and lengths (0: none, and the draws are not read); None is the loop without it.  Not with `symmetry`."""
+        if eta is not None:
+            from .diffusion.ddim import check_eta
+            eta = check_eta(eta)
+            if symmetry is not None:
+                raise ValueError("eta is not combined with symmetry tables")
         res = None
         if resampling is not None:
             from .diffusion.resampling import check_resampling
@@ -276,6 +283,8 @@ class HipEngine:
         opts = (_byref(cond), _byref(sched), _byref(corr), _byref(res))
         if symmetry is not None:
             name, opts = "arreau_sample_loop_sym", opts + (_hip.ptr(length_tie), _byref(self._symmetry_struct(symmetry, N)))
+        elif eta is not None:
+            name, opts = "arreau_sample_loop_eta", opts + (_hip.ptr(length_tie), ctypes.c_float(eta))
         elif length_tie is not None:
             name, opts = "arreau_sample_loop_tied", opts + (_hip.ptr(length_tie),)
         elif any(o is not None for o in opts):
@@ -631,6 +640,17 @@ class HipEngine:
         sym = self._symmetry_struct(symmetry, frac.shape[0]) if symmetry is not None else None
         self._reverse_step_to("arreau_reverse_step_sym", frac, types, lengths, angles, t_crystal, s_crystal, offsets, eps, logits, len0,
                               z_lattice, z_frac, u_types, lattice_out, lattice_clipmax, _hip.ptr(length_tie), _byref(sym))
+
+    def reverse_step_eta(self, frac, types, lengths, angles, t_crystal, s_crystal, offsets, eps, logits, len0, z_lattice, z_frac,
+                         u_types, lattice_out, eta, length_tie=None, lattice_clipmax=0.999):
+        """reverse_step_tied as the DDIM-style step (arreau_reverse_step_eta): `eta` in [0, 1] scales the noise of positions and
+        lengths; length_tie may be None; at eta = 0 z_lattice and z_frac are not read and may be None."""
+        from .diffusion.ddim import check_eta
+        eta = check_eta(eta)
+        if length_tie is not None:
+            self._check_tie(length_tie, lengths.shape[0])
+        self._reverse_step_to("arreau_reverse_step_eta", frac, types, lengths, angles, t_crystal, s_crystal, offsets, eps, logits, len0,
+                              z_lattice, z_frac, u_types, lattice_out, lattice_clipmax, _hip.ptr(length_tie), ctypes.c_float(eta))
 
     def resample_jump(self, frac, types, lengths, angles, s_crystal, t_crystal, offsets, z_frac, z_lengths, u_types, lattice_out,
                       const_types=None, fixed_lengths=None, condition=None, length_tie=None):

@@ -14,6 +14,10 @@ fixes those components wherever the file has no mask for them; `--samples_per_te
 
 Respaced sampling: `--num_steps K` runs K evenly spaced denoising steps instead of every timestep (DiffusionLoss.sample).
 
+DDIM-style sampling: `--eta X` (0..1) scales the noise every step injects into positions and lengths; 0 makes them a function
+of the initial state alone, 1 is the ancestral step; the usual companion of `--num_steps` (DiffusionLoss.sample).  Not with
+`--symops`.
+
 Predictor-corrector sampling: `--corrector_steps M` runs M Langevin corrector moves on the positions before every denoising
 step, with the step-size rule's `--corrector_snr` (default 0.16; DiffusionLoss.sample).
 
@@ -240,6 +244,14 @@ def _corrector_snr_arg(text: str) -> float:
         raise argparse.ArgumentTypeError(str(e)) from None
 
 
+def _eta_arg(text: str) -> float:
+    from .diffusion.ddim import check_eta
+    try:
+        return check_eta(float(text))
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
 def _resample_passes_arg(text: str) -> int:
     from .diffusion.resampling import check_resampling
     try:
@@ -271,6 +283,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--samples_per_template", type=int, default=1, help="the templates are tiled this many times")
     ap.add_argument("--num_steps", type=int, default=None,
                     help="respaced sampling: this many evenly spaced denoising steps (2..T-1; default: every timestep)")
+    ap.add_argument("--eta", type=_eta_arg, default=None,
+                    help="DDIM-style sampling: scale of the noise every step injects into positions and lengths (0..1; 0 = "
+                         "deterministic, 1 = ancestral; default: the sampler without it)")
     ap.add_argument("--corrector_steps", type=_corrector_steps_arg, default=0,
                     help="predictor-corrector sampling: Langevin corrector moves on the positions per denoising step (0..16)")
     ap.add_argument("--corrector_snr", type=_corrector_snr_arg, default=0.16,
@@ -459,6 +474,8 @@ def main():
     ap = build_parser()
     args = ap.parse_args()
     spec = load_symmetry(args, ap.error)
+    if spec is not None and args.eta is not None:
+        ap.error("--eta is not supported with --symops")
     asked = {"screen": check_screen_arguments(args, ap.error)}  # per instrument, by its sample() keyword: its parameters, or None
     for e in INSTRUMENTS[1:]:
         asked[e.keyword] = instrument_params(e.keyword, args, ap.error) if getattr(args, e.keyword) else None
@@ -501,7 +518,7 @@ def main():
             return model.sample(n, b, VisualizationSetting.NONE, False, condition=cond, num_steps=args.num_steps,
                                 corrector_steps=args.corrector_steps, corrector_snr=args.corrector_snr,
                                 resample_passes=args.resample_passes, jump_length=args.jump_length,
-                                lattice_system=args.lattice_system, symmetry=spec, **keywords)
+                                lattice_system=args.lattice_system, symmetry=spec, eta=args.eta, **keywords)
     if condition is not None:
         res = generate_from_template(lambda c: fn(None, None, c), condition, args.batch, rank, world, unique=unique)
     elif args.require_valid:

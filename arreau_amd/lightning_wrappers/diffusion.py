@@ -329,7 +329,7 @@ class PONITA_DIFFUSION(nn.Module):
                condition=None, num_steps: Optional[int] = None, timesteps=None, corrector_steps: int = 0,
                corrector_snr: float = 0.16, resample_passes: int = 1, jump_length: int = 10,
                lattice_system=None, symmetry=None, screen=None, unique=None, find_symmetry=None, reduce_cell=None,
-               symmetrize=None, match_to=None) -> SampleResult:
+               symmetrize=None, match_to=None, eta: Optional[float] = None) -> SampleResult:
         """lightning_wrappers/diffusion.py:220-253.  `num_atoms_per_sample` may also be a sequence with one atom count
         per crystal of the batch (extension; the reference supports a single int).  Frames of a visualization_setting
         other than NONE go to `<DIFFUSION_DIR>/step_<timestep>.cif` like the reference's PNGs (`vis_name` overrides the
@@ -351,9 +351,14 @@ class PONITA_DIFFUSION(nn.Module):
         diffusion.symmetry_search.SymmetrySearchParams or True -- the symmetry operations and point group of every final crystal;
         SampleResult.symmetry holds the arrays (DiffusionLoss.sample).  `match_to` (extension): targets (a SampleResult, a loaded
         crystals file, or (targets, diffusion.structure_match.StructureMatchParams)) the final crystals are matched against on the
-        device; SampleResult.match holds the arrays (DiffusionLoss.sample)."""
+        device; SampleResult.match holds the arrays (DiffusionLoss.sample).  `eta` (extension): DDIM-style sampling -- a float
+        in [0, 1] that scales the noise every step injects into positions and lengths; 0 makes them a function of the initial
+        state alone, whatever the seed; None is the sampler as it was; not with `symmetry` (DiffusionLoss.sample)."""
         from ..diffusion import resampling
         resampling.check_resampling(resample_passes, jump_length)  # (raises before any work)
+        if eta is not None:
+            from ..diffusion import ddim
+            eta = ddim.check_eta(eta)  # (raises before any work)
         if num_steps is not None or timesteps is not None:
             from ..diffusion import respacing
             respacing.resolve_schedule(self.diffusion_loss.T, num_steps=num_steps, timesteps=timesteps)  # (raises before any work)
@@ -377,4 +382,4 @@ class PONITA_DIFFUSION(nn.Module):
             num_steps=num_steps, timesteps=timesteps, corrector_steps=corrector_steps, corrector_snr=corrector_snr,
             resample_passes=resample_passes, jump_length=jump_length, lattice_system=lattice_system, symmetry=symmetry,
             screen=screen, unique=unique, find_symmetry=find_symmetry, reduce_cell=reduce_cell, symmetrize=symmetrize,
-            match_to=match_to)
+            match_to=match_to, eta=eta)

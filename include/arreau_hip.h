@@ -1062,6 +1062,54 @@ int arreau_reverse_step_sym(const arreau_model* model,
                             float* d_lattice, float lattice_clipmax, const int32_t* d_length_tie, const arreau_symmetry* symmetry,
                             void* stream);
 
+/* ---- DDIM-style sampling (an eta that scales the reverse step's noise) -----------------------------------------------
+ * Song, Meng & Ermon 2021 ("Denoising Diffusion Implicit Models"): the same trained network and the same schedule, with a
+ * parameter eta in [0, 1] that scales the noise a step injects -- eta = 1 the ancestral step of the sections above, eta = 0 a
+ * deterministic map.  On a respaced schedule the ancestral step injects the full posterior noise of every jump; this is the
+ * usual remedy.  The reference has no such option; the rules are the library's own.  The step that leaves t produces s (t - 1,
+ * or the scheduled successor).  Float32 on the model's tables, evaluated in the order written:
+ *   1. VE positions.  The predictor moves against eps with weight sig_t^2 - sig_s^2, so its x0 estimate is x_t - sig_t^2 eps.
+ *      With r = sig_s / sig_t:  dir = sig_s sqrt((1 - eta^2) + eta^2 r^2),
+ *      x_s = remainder(x_t - eps sig_t (sig_t - dir) + eta sig_s sqrt(1 - r^2) z, 1).
+ *      eta = 1: rule 1 of the respaced section (sig_t (sig_t - dir) = sig_t^2 - sig_s^2, the same std).  eta = 0:
+ *      x_s = remainder(x_t - eps sig_t (sig_t - sig_s), 1).
+ *   2. VP lengths (x0 prediction).  beta as in rule 2 of the respaced section (betas[t] at stride 1, otherwise
+ *      min(1 - abar_t / abar_s, lattice_clipmax)); den = 1 - abar_t, var = (1 - abar_s) beta / den,
+ *      k = sqrt(max((1 - abar_s) (1 - eta^2 beta / den), 0) / den),
+ *      l_s = (sqrt(abar_s) - k sqrt(abar_t)) x0 + k x_t + eta var z,  z = 0 for t <= 1.
+ *      The direction term uses the true posterior variance; the noise keeps the ancestral step's amplitude (var, not its
+ *      root).  eta = 1 is that step wherever beta is not clipped, up to the rounding of the float32 betas table against
+ *      1 - abar_t / abar_s.  At (t, s) = (1, 0): l_s = x0.
+ *   3. species: unchanged -- the D3PM step with its Gumbel draw.  eta = 0 makes positions and lengths a function of the
+ *      state alone; species are deterministic only where they are held (d_const_types, a condition's known species).
+ *   4. fixed cells, the known components of a condition (their rules and draws, kinds 3 and 4), corrector steps, resampling
+ *      jumps and the lattice-system tie apply as without an eta.  Tied axes take the leader's x_t and draw and the group's
+ *      mean x0, and stay bitwise equal.
+ *   5. noise keys do not change: kinds 0 and 1 draw what they draw in the ancestral step.  The noise terms are added only
+ *      when eta > 0: at eta = 0 the draws are not read (not generated, and a caller's d_z_lattice / d_z_frac may be NULL).
+ *   6. eta not finite or outside [0, 1]: ARREAU_EINVAL before any work.  Not combined with space-group symmetry.
+ * No claim on sample quality is made: there is no trained checkpoint here. */
+
+/* arreau_sample_loop_tied with the eta step above in every step (d_length_tie and the other options may be NULL as there): both
+ * loop forms, the shape-general path, graph replay, schedules, segments, conditions, correctors, resampling, fixed cells and
+ * constant species.  eta is part of what a cached hipGraph was captured for: another eta is captured anew. */
+int arreau_sample_loop_eta(arreau_model* model, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                           const int32_t* d_crystal_offsets, int32_t B, int32_t N, int32_t t_start, int32_t n_steps,
+                           uint64_t seed, const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice,
+                           void* d_workspace, size_t workspace_bytes, int32_t use_graph,
+                           const arreau_sample_condition* cond, const arreau_sample_schedule* schedule,
+                           const arreau_corrector* corrector, const arreau_resampling* resampling, const int32_t* d_length_tie,
+                           float eta, void* stream);
+
+/* arreau_reverse_step_tied as the eta step (the caller's noise; d_length_tie may be NULL; at eta = 0 d_z_lattice and d_z_frac
+ * may be NULL).  Fed arreau_philox_fill's draws it is the step of arreau_sample_loop_eta bit for bit. */
+int arreau_reverse_step_eta(const arreau_model* model,
+                            float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                            const int32_t* d_t, const int32_t* d_s, const int32_t* d_crystal_offsets, int32_t B, int32_t N,
+                            const float* d_eps, const float* d_logits, const float* d_len0,
+                            const float* d_z_lattice, const float* d_z_frac, const float* d_u_types,
+                            float* d_lattice, float lattice_clipmax, const int32_t* d_length_tie, float eta, void* stream);
+
 /* The sampler's in-kernel noise written out: d_out[i] = draw (seed, timestep, kind, element i) -- standard normal for
  * kind 0 (z_lattice), 1 (z_frac), 3 (known positions) and 4 (known lengths), uniform [0,1) for kind 2 (u_types); d_raw[4 i .. 4 i + 3] (may be NULL) = the raw
  * Philox4x32-10 words of counter (i, timestep, kind, 0), key = seed.  Feeding these arrays to arreau_reverse_step
