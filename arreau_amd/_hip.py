@@ -33,6 +33,7 @@ EXPORTS = [
     "arreau_sample_loop_eta", "arreau_reverse_step_eta",
     "arreau_crystal_fingerprint", "arreau_fingerprint_match", "arreau_crystal_symmetry", "arreau_crystal_reduce",
     "arreau_crystal_symmetrize", "arreau_structure_match", "arreau_structure_match_assigned",
+    "arreau_noise_state", "arreau_invert_step", "arreau_invert_loop",
 ]
 
 STATUS_NONFINITE, STATUS_BAD_TIMESTEP, STATUS_BAD_TYPE, STATUS_BAD_TIE, STATUS_BAD_SYMMETRY = 1, 2, 4, 8, 16
@@ -218,6 +219,9 @@ def _prototypes():
         "arreau_corrector_step": [vp] * 4 + [i32, i32, vp, vp, f32, cond, vp],
         "arreau_resample_jump": jump + [vp],
         "arreau_resample_jump_tied": jump + [vp, vp],
+        "arreau_noise_state": [vp] * 6 + [i32, i32, i32, u64] + [vp] * 5,
+        "arreau_invert_step": [vp] * 8 + [i32, i32] + [vp] * 5,
+        "arreau_invert_loop": [vp] * 6 + [i32] * 4 + [vp] * 4 + [c_size_t, i32, vp],
         "arreau_philox_fill": [u64, i32, i32, i64, vp, vp, vp],
         "arreau_philox_fill_word": [u64, i32, i32, u32, i64, vp, vp, vp],
         "arreau_crystal_screen": [vp] * 4 + [i32, i32, POINTER(ScreenCriteriaC), POINTER(ScreenResultC), vp],

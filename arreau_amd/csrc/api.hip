@@ -348,7 +348,8 @@ struct ResamplePlan {
 // The key of a captured step: the buffers, sizes and seed, the plan (every kernel choice of the evaluation), and the condition's
 // pointers, the schedule's table and clip, the corrector's step count and snr, the resampling's R and J (a resampled step reads
 // the pass word), the lattice systems' tie array, the symmetry tables and the eta of a DDIM-style step, which are kernel arguments
-// or launch choices of the capture: a change of any of them must not replay the stale graph.
+// or launch choices of the capture: a change of any of them must not replay the stale graph.  So is the direction: an inversion
+// loop (arreau_invert_loop) on the same buffers, table pointer included, captures other kernels than a sampling loop.
 SampleGraphKey sample_graph_key(const ScorePlan& score, const SampleState& st, const void* d_workspace, uint64_t seed,
                                 const StepOptions& opt, const ResamplePlan* plan) {
     SampleGraphKey k{};
@@ -371,6 +372,7 @@ SampleGraphKey sample_graph_key(const ScorePlan& score, const SampleState& st, c
         k.eta_step = 1;
         k.eta_bits = std::bit_cast<uint32_t>(opt.eta);
     }
+    k.invert = opt.invert ? 1 : 0;
     return k;
 }
 
@@ -378,7 +380,8 @@ int sample_loop_impl(arreau_model* m, const SampleState& st, int32_t t_start, in
                      size_t workspace_bytes, int32_t use_graph, const arreau_sample_condition* condition,
                      const arreau_sample_schedule* schedule, const arreau_corrector* corrector,
                      const ResamplePlan* plan /* null: no resampling */, const int32_t* d_length_tie /* null: untied */,
-                     const arreau_symmetry* sym /* null: no symmetry */, float eta /* negative: the ancestral step */, void* stream) {
+                     const arreau_symmetry* sym /* null: no symmetry */, float eta /* negative: the ancestral step */, void* stream,
+                     bool invert = false /* DDIM inversion: t_start is the first level, `schedule` the ascending table; no other option */) {
     if (corrector) {
         const int rc = arreau_corrector_check(corrector->steps, corrector->snr, "arreau_sample_loop_corrected");
         if (rc) return rc;
@@ -417,6 +420,9 @@ int sample_loop_impl(arreau_model* m, const SampleState& st, int32_t t_start, in
     opt.length_tie = d_length_tie;
     opt.sym = sym;
     opt.eta = eta;
+    opt.invert = invert;
+    ARREAU_REQUIRE(!invert || (schedule && !opt.cond && opt.corr.steps == 0 && !plan && !d_length_tie && !sym && eta < 0.0f),
+                   "arreau_invert_loop: an inversion loop takes its ascending table and no sampling option");
     if (n_steps == 0) return ARREAU_OK;
     hipStream_t s = (hipStream_t)stream;
     ARREAU_REQUIRE(!sym || (opt.cond == nullptr && opt.corr.steps == 0 && plan == nullptr),
@@ -424,11 +430,13 @@ int sample_loop_impl(arreau_model* m, const SampleState& st, int32_t t_start, in
     opt.pass = plan ? w.pass : nullptr;
     if (score.no_prep) {
         // t_cur holds the timestep of the step in progress; every step's first launch advances it, so it starts one above (in a
-        // respaced loop at the table entry t_start + 1, whose successor is t_start)
-        ARREAU_LAUNCH(fill_i32_kernel, dim3((B + 255) / 256), dim3(256), 0, s, w.t_cur, t_start + 1, B);
+        // respaced loop at the table entry t_start + 1, whose successor is t_start) -- an inversion loop, which climbs, one below
+        // (the ascending table's entry t_start - 1, whose successor is t_start)
+        const int before = invert ? -1 : 1;
+        ARREAU_LAUNCH(fill_i32_kernel, dim3((B + 255) / 256), dim3(256), 0, s, w.t_cur, t_start + before, B);
         ARREAU_CHECK_HIP(hipGetLastError());
         if ((rc = arreau_launch_prep(m, st.frac, st.lengths, st.angles, w.t_cur, st.offsets, B, N, w.lattice, w.cart, w.batch, w.cvec, s,
-                                     nullptr, nullptr, -1)))
+                                     nullptr, nullptr, -before)))
             return rc;
     } else {
         ARREAU_LAUNCH(fill_i32_kernel, dim3((B + 255) / 256), dim3(256), 0, s, w.t_next, t_start, B);
@@ -643,6 +651,23 @@ extern "C" int arreau_sample_loop_eta(arreau_model* m, float* d_frac, int32_t* d
     const SampleState st{d_frac, d_types, d_lengths, d_angles, d_off, B, N, d_const_types, d_fixed_lengths, d_lattice};
     return sample_loop("arreau_sample_loop_eta", m, st, t_start, n_steps, seed, d_workspace, workspace_bytes, use_graph, stream,
                        condition, schedule, corrector, resampling, d_length_tie, /*sym=*/nullptr, eta + 0.0f /* -0 -> +0 */);
+}
+
+// DDIM inversion (rules in include/arreau_hip.h): the sampling loop climbing the levels of an ascending table, every step the
+// network evaluation at the crystals' level and the INVERT update to the next one.  The same loop code in both forms, with graph
+// replay and on the shape-general path; no seed, no corrector, no jump.
+extern "C" int arreau_invert_loop(arreau_model* m, float* d_frac, const int32_t* d_types, float* d_lengths, const float* d_angles,
+                                  const int32_t* d_off, int32_t B, int32_t N, int32_t t_first, int32_t n_steps, const int32_t* d_up,
+                                  const float* d_fixed_lengths, float* d_lattice, void* d_workspace, size_t workspace_bytes,
+                                  int32_t use_graph, void* stream) {
+    ARREAU_REQUIRE(m && d_up, "arreau_invert_loop: null pointer");
+    ARREAU_REQUIRE(n_steps >= 0 && t_first >= 1 && (int64_t)t_first + n_steps <= m->T,
+                   "arreau_invert_loop: the levels t_first < ... (n_steps climbs) must lie in 1..T");
+    // (the species are read by the network and never written: the pointer only completes the state)
+    const SampleState st{d_frac, const_cast<int32_t*>(d_types), d_lengths, d_angles, d_off, B, N, nullptr, d_fixed_lengths, d_lattice};
+    const arreau_sample_schedule up{d_up, 1.0f /* not read by an inversion step */};
+    return sample_loop_impl(m, st, t_first, n_steps, /*seed=*/0, d_workspace, workspace_bytes, use_graph, nullptr, &up, nullptr, nullptr,
+                            nullptr, nullptr, -1.0f, stream, /*invert=*/true);
 }
 
 extern "C" int arreau_sample_loop_sym(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,

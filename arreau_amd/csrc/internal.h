@@ -103,6 +103,7 @@ struct SampleGraphKey {
     int32_t resample_passes, resample_jump;  // 0, 0: no resampling
     int32_t eta_step;          // DDIM-style sampling: 1 when the steps are eta steps
     uint32_t eta_bits;         // their eta
+    int32_t invert;            // DDIM inversion: 1 when the steps are inversion steps (arreau_invert_loop)
     bool operator==(const SampleGraphKey&) const = default;
 };
 
@@ -316,6 +317,7 @@ struct StepOptions {
     const int32_t* length_tie = nullptr;  // lattice systems: the tie code per crystal (TIE)
     const arreau_symmetry* sym = nullptr; // space-group symmetry: the orbit tables (SYM); not with a condition or a resampled loop
     float eta = -1.0f;                    // DDIM-style step (ETA): the noise scale in [0, 1]; negative: the ancestral step.  Not with sym
+    bool invert = false;                  // DDIM inversion (INVERT): `sched` names the HIGHER level every crystal climbs to; no other option
 };
 // DDIM-style sampling (arreau_sample_loop_eta, arreau_reverse_step_eta; the rules are stated in include/arreau_hip.h):
 // ARREAU_EINVAL unless eta is finite and lies in [0, 1].

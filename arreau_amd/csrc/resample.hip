@@ -224,6 +224,20 @@ extern "C" int arreau_resample_jump(const arreau_model* m, float* d_frac, int32_
                          d_fixed_lengths, cond, d_lattice, nullptr, stream, "arreau_resample_jump");
 }
 
+// Forward noising of a clean state to level t (rules in include/arreau_hip.h, section "Starting the sampler from given crystals"):
+// the jump (0, t) of every crystal with the kernel's own Philox draws, pass word 0 -- a word the resampled loop never uses for the
+// jump kinds.  Outside a loop: no device timestep, no next step's set-up.
+extern "C" int arreau_noise_state(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                                  const int32_t* d_off, int32_t B, int32_t N, int32_t t, uint64_t seed, const int32_t* d_const_types,
+                                  const float* d_fixed_lengths, float* d_lattice, const int32_t* d_length_tie, void* stream) {
+    ARREAU_REQUIRE(m && d_frac && d_types && d_lengths && d_angles && d_off && d_lattice, "arreau_noise_state: null pointer");
+    ARREAU_REQUIRE(B >= 1 && N >= 0, "arreau_noise_state: bad size");
+    ARREAU_REQUIRE(t >= 1 && t <= m->T, "arreau_noise_state: t must lie in 1..T");
+    const SampleState st{d_frac, d_types, d_lengths, d_angles, d_off, B, N, d_const_types, d_fixed_lengths, d_lattice};
+    return arreau_launch_resample_jump(m, st, /*d_s=*/nullptr, /*d_t=*/nullptr, 0, t, /*d_batch=*/nullptr, StepNoiseSrc{.seed = seed},
+                                       /*pass=*/0u, /*cond=*/nullptr, /*loop=*/nullptr, d_length_tie, (hipStream_t)stream);
+}
+
 // arreau_resample_jump with the lattice-system tie of the lengths (rules in include/arreau_hip.h); NULL = arreau_resample_jump.
 extern "C" int arreau_resample_jump_tied(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
                                          const int32_t* d_s, const int32_t* d_t, const int32_t* d_off, int32_t B, int32_t N,

@@ -6,7 +6,8 @@
 // Note the reference adds `variance * z` (not sqrt(variance)) and zeroes z when t <= 1.
 // TIE: the lattice-system tie of the lengths (length_tie[b]); the three x0 and current lengths are exchanged by shuffles.
 // ETA: the eta move of the lengths (update_dev.h).
-template <bool TIE, bool ETA>
+// INVERT: the inversion move of the lengths, from the crystal's level up to its target (update_dev.h; not with TIE or ETA).
+template <bool TIE, bool ETA, bool INVERT = false>
 __device__ __forceinline__ void reverse_lattice_body(int gt /* global thread of the lattice part */, float* __restrict__ lengths, const float* __restrict__ angles,
                                        const int32_t* __restrict__ tstep, const int32_t* __restrict__ offsets,
                                        const float* __restrict__ len0, StepNoiseSrc noise,
@@ -22,10 +23,16 @@ __device__ __forceinline__ void reverse_lattice_body(int gt /* global thread of 
     const int b = b0 + (gt >> 2), i = gt & 3;
     const bool live = b < B;  // (whole groups of four are live or not; the shuffles below need every lane)
     const int bc = live ? b : B - 1;
-    int t = tstep[bc];
-    if (live && i == 0 && (t < 1 || t > T)) atomicOr(status, ARREAU_STATUS_BAD_TIMESTEP);  // clamped, but flagged
-    t = t < 1 ? 1 : (t > T ? T : t);
-    const int s_to = step_target(sched, bc, t, status, live && i == 0);
+    int t = tstep[bc], s_to;
+    if constexpr (INVERT) {
+        static_assert(!TIE && !ETA, "the INVERT instances are untied and take no eta");
+        t = invert_level(t, T, status, live && i == 0);
+        s_to = invert_target(sched, bc, t, T, status, live && i == 0);
+    } else {
+        if (live && i == 0 && (t < 1 || t > T)) atomicOr(status, ARREAU_STATUS_BAD_TIMESTEP);  // clamped, but flagged
+        t = t < 1 ? 1 : (t > T ? T : t);
+        s_to = step_target(sched, bc, t, status, live && i == 0);
+    }
     const int first = offsets[bc], last = offsets[bc + 1];
     float mylen = 0.f;
     if constexpr (TIE) {
@@ -47,8 +54,8 @@ __device__ __forceinline__ void reverse_lattice_body(int gt /* global thread of 
                                                word3, eta);
     } else {
         if (live && i < 3)
-            mylen = reverse_length_component<ETA>(b, i, t, s_to, sched, first, last, lengths, len0, noise, alpha_bars, betas, fixed_lengths,
-                                                  gs_atoms, len0_out, cond, word3, eta);
+            mylen = reverse_length_component<ETA, INVERT>(b, i, t, s_to, sched, first, last, lengths, len0, noise, alpha_bars, betas,
+                                                          fixed_lengths, gs_atoms, len0_out, cond, word3, eta);
     }
     const int base = (threadIdx.x & 63) & ~3;
     float newlen[3];
@@ -83,7 +90,11 @@ __device__ __forceinline__ void reverse_lattice_body(int gt /* global thread of 
 // (a leader's wave updates its whole orbit, members leave).  Only without COND and RESAMPLE.  Without SYM `sym_arg` is not read.
 // ETA: DDIM-style sampling (arreau_sample_loop_eta): positions and lengths make the eta moves of update_dev.h, the noise scaled
 // by `eta` in [0, 1] and not read at 0; the species step is unchanged.  Not with SYM.  Without ETA `eta` is not read.
-template <bool COND, bool SCHED, bool RESAMPLE, bool TIE, bool SYM, bool ETA>
+// INVERT: DDIM inversion (arreau_invert_loop / arreau_invert_step): every crystal climbs from its level `tstep` up to the target the
+// schedule argument names (the ascending table or the per-crystal array), lengths and positions by the inversion moves of
+// update_dev.h; the atom part is the position move alone (invert_atoms_body), so `types`, `logits` and the noise are not read.
+// Only with SCHED and none of the others.
+template <bool COND, bool SCHED, bool RESAMPLE, bool TIE, bool SYM, bool ETA, bool INVERT = false>
 __global__ __launch_bounds__(256) void reverse_kernel(
     int lat_blocks, float* __restrict__ lengths, const float* __restrict__ angles, const int32_t* __restrict__ tstep,
     const int32_t* __restrict__ offsets, const float* __restrict__ len0, StepNoiseSrc noise, const float* __restrict__ alpha_bars,
@@ -101,17 +112,21 @@ __global__ __launch_bounds__(256) void reverse_kernel(
     const SampleConditionDev* cond = COND ? &cond_arg : nullptr;
     const StepScheduleDev* sched = SCHED ? &sched_arg : nullptr;
     if ((int)blockIdx.x < lat_blocks && cvec_next != nullptr) {  // (kernel argument: uniform)
-        reverse_crystal_block<TIE, ETA>(b0 + (int)blockIdx.x, lengths, angles, tstep, offsets, len0, noise, alpha_bars, betas, T, lattice,
-                                        fixed_lengths, status, gs_atoms, len0_out, lattice_ws, cvec_next, t_emb_w, embT, S, C, cond, sched,
-                                        word3, length_tie, eta);
+        reverse_crystal_block<TIE, ETA, INVERT>(b0 + (int)blockIdx.x, lengths, angles, tstep, offsets, len0, noise, alpha_bars, betas, T,
+                                                lattice, fixed_lengths, status, gs_atoms, len0_out, lattice_ws, cvec_next, t_emb_w, embT, S, C,
+                                                cond, sched, word3, length_tie, eta);
         return;
     }
     if ((int)blockIdx.x < lat_blocks) {
-        reverse_lattice_body<TIE, ETA>(blockIdx.x * blockDim.x + threadIdx.x, lengths, angles, tstep, offsets, len0, noise, alpha_bars, betas,
-                                       B_lat, T, lattice, fixed_lengths, status, b0, gs_atoms, len0_out, cond, sched, word3, length_tie, eta);
+        reverse_lattice_body<TIE, ETA, INVERT>(blockIdx.x * blockDim.x + threadIdx.x, lengths, angles, tstep, offsets, len0, noise, alpha_bars,
+                                               betas, B_lat, T, lattice, fixed_lengths, status, b0, gs_atoms, len0_out, cond, sched, word3,
+                                               length_tie, eta);
         return;
     }
-    if constexpr (SYM) {
+    if constexpr (INVERT) {
+        static_assert(!COND && SCHED && !RESAMPLE && !TIE && !SYM && !ETA, "the INVERT instance takes a schedule and no other option");
+        invert_atoms_body((int)blockIdx.x - lat_blocks, frac, tstep, offsets, B, N, eps, ve_sigmas, T, status, n0, batch, sched);
+    } else if constexpr (SYM) {
         static_assert(!COND && !RESAMPLE && !ETA, "the SYM instances are unconditioned, not resampled and take no eta");
         reverse_atoms_body_sym((int)blockIdx.x - lat_blocks, frac, types, tstep, offsets, B, N, eps, logits, noise, ve_sigmas, q1t, qmats, S,
                                T, const_types, absorbing, status, n0, batch, sched, sym_arg);
@@ -132,6 +147,9 @@ template <bool COND, bool SCHED>
 void enqueue_reverse_kernel(const arreau_model* m, int lat_blocks, int atom_blocks, const SampleState& st, const ReverseInputs& in,
                             const SampleConditionDev& cond, const StepScheduleDev& sched, const StepOptions& opt, hipStream_t s) {
     auto kernel = opt.eta >= 0.0f ? reverse_kernel_of<COND, SCHED, true>(opt) : reverse_kernel_of<COND, SCHED, false>(opt);
+    if constexpr (!COND && SCHED) {
+        if (opt.invert) kernel = reverse_kernel<false, true, false, false, false, false, true>;
+    }
     if constexpr (!COND) {
         if (opt.sym)
             kernel = opt.length_tie ? reverse_kernel<false, SCHED, false, true, true, false> : reverse_kernel<false, SCHED, false, false, true, false>;
@@ -158,6 +176,8 @@ int arreau_launch_reverse(const arreau_model* m, const SampleState& st, const Re
     ARREAU_REQUIRE(!opt.sym || (!conditioned && opt.pass == nullptr),
                    "reverse update: space-group symmetry is not combined with a condition or a resampled loop");
     ARREAU_REQUIRE(!opt.sym || opt.eta < 0.0f, "reverse update: space-group symmetry is not combined with an eta");
+    ARREAU_REQUIRE(!opt.invert || (scheduled && !conditioned && !opt.pass && !opt.length_tie && !opt.sym && opt.eta < 0.0f && opt.corr.steps == 0),
+                   "reverse update: an inversion step takes its targets and no other option");
     if (lat_blocks + atom_blocks == 0) return ARREAU_OK;
     const SampleConditionDev c = conditioned ? *opt.cond : SampleConditionDev{};
     const StepScheduleDev sc = scheduled ? *opt.sched : StepScheduleDev{};
@@ -237,6 +257,21 @@ extern "C" int arreau_reverse_step_eta(const arreau_model* m, float* d_frac, int
     return reverse_step_to(m, d_frac, d_types, d_lengths, d_angles, d_t, d_s, d_off, B, N, d_eps, d_logits, d_len0, d_z_lattice, d_z_frac,
                            d_u_types, d_lattice, lattice_clipmax, d_length_tie, /*sym=*/nullptr, stream, "arreau_reverse_step_eta",
                            eta + 0.0f /* -0 -> +0 */);
+}
+
+// DDIM inversion: one step from level d_s[b] up to level d_t[b] on the caller's network outputs (rules in include/arreau_hip.h).
+extern "C" int arreau_invert_step(const arreau_model* m, float* d_frac, const int32_t* d_types, float* d_lengths, const float* d_angles,
+                                  const int32_t* d_s, const int32_t* d_t, const int32_t* d_off, int32_t B, int32_t N,
+                                  const float* d_eps, const float* d_len0, const float* d_fixed_lengths, float* d_lattice, void* stream) {
+    ARREAU_REQUIRE(m && d_frac && d_types && d_lengths && d_angles && d_s && d_t && d_off && d_eps && d_len0 && d_lattice,
+                   "arreau_invert_step: null pointer");
+    ARREAU_REQUIRE(B >= 1 && N >= 0, "arreau_invert_step: bad size");
+    // (the species are not read by the update and never written: the pointer only completes the state)
+    const SampleState st{.frac = d_frac, .types = const_cast<int32_t*>(d_types), .lengths = d_lengths, .angles = d_angles, .offsets = d_off,
+                         .B = B, .N = N, .fixed_lengths = d_fixed_lengths, .lattice = d_lattice};
+    const ReverseInputs in{d_s, d_eps, /*logits=*/nullptr, d_len0, StepNoiseSrc{}};
+    const StepScheduleDev sched{nullptr, d_t, 0.0f};
+    return arreau_launch_reverse(m, st, in, StepOptions{.sched = &sched, .invert = true}, (hipStream_t)stream);
 }
 
 // arreau_reverse_step_tied with space-group symmetry (rules in include/arreau_hip.h); NULL = arreau_reverse_step_tied.

@@ -71,11 +71,42 @@ __device__ __forceinline__ float eta_length_draw(StepNoiseSrc noise, uint32_t e,
     return noise.z_lattice ? noise.z_lattice[e] : philox_normal(noise.seed, (uint32_t)t, ARREAU_DRAW_Z_LATTICE, e, word3);
 }
 
+// DDIM inversion (arreau_invert_loop / arreau_invert_step; the rules are stated in include/arreau_hip.h): the INVERT instances of
+// the length and position updates climb from the level s a crystal is at to a higher level t, the inverse of the eta = 0 move.  In
+// these instances the helpers' `t` is the level the step leaves (the lower one) and their `s` the level it produces (the higher
+// one); no draw, no beta and no clip enters.  The other instances do not see this code.
+// The level a crystal leaves, clamped to 1..T-1 (flagged by the caller's one thread per crystal: `flag`).
+__device__ __forceinline__ int invert_level(int raw, int T, int32_t* __restrict__ status, bool flag) {
+    int s = raw > T - 1 ? T - 1 : raw;
+    s = s < 1 ? 1 : s;
+    if (flag && s != raw) atomicOr(status, ARREAU_STATUS_BAD_TIMESTEP);  // clamped, but flagged
+    return s;
+}
+// The level the step that leaves s (clamped) produces: the caller's per-crystal target or the loop's ascending table.  Valid
+// targets are s + 1 .. T; anything else is clamped into that range and flagged.  (T caps last, so every table index stays in range.)
+__device__ __forceinline__ int invert_target(const StepScheduleDev* sc, int b, int s, int T, int32_t* __restrict__ status, bool flag) {
+    const int raw = sc->s_of ? sc->s_of[b] : sc->next[s];
+    int t = raw < s + 1 ? s + 1 : raw;
+    t = t > T ? T : t;
+    if (flag && t != raw) atomicOr(status, ARREAU_STATUS_BAD_TIMESTEP);  // clamped, but flagged
+    return t;
+}
+// The length move from level s up to t, float32 in the order of the rule.
+__device__ __forceinline__ float invert_length_move(float x0, float ls, float ab_s, float ab_t) {
+    const float rho = sqrtf((1.0f - ab_t) / (1.0f - ab_s));
+    return sqrtf(ab_t) * x0 + rho * (ls - sqrtf(ab_s) * x0);
+}
+// One component of the position move from level s up to t: the unit-variance direction sig_s eps is kept and rescaled to sig_t.
+__device__ __forceinline__ float invert_frac_move(float xs, float eps, float sig_s, float sig_t) {
+    return remainder_one(xs + eps * sig_s * (sig_t - sig_s));
+}
+
 // One component of the length update of crystal b from timestep t to s (VP_lattice.reverse_given_x0 with t - 1 replaced by s;
 // the per-atom read-out is pooled here when gs_atoms is given: the ordered sum of readout_crystals_kernel).  Writes
 // lengths[3 b + i] and returns it.  A stride-1 step (always, without a schedule) takes beta from the model's betas table.
 // ETA: the move is eta_length_move's (the same beta, x0 and x_t); everything around it is as without.
-template <bool ETA = false>
+// INVERT: the move is invert_length_move's, from level t up to level s (same x0, same pooling; beta and the draw are not formed).
+template <bool ETA = false, bool INVERT = false>
 __device__ __forceinline__ float reverse_length_component(int b, int i, int t, int s, const StepScheduleDev* sched, int first, int last, float* __restrict__ lengths,
                                                           const float* __restrict__ len0, StepNoiseSrc noise,
                                                           const float* __restrict__ alpha_bars, const float* __restrict__ betas,
@@ -109,7 +140,9 @@ __device__ __forceinline__ float reverse_length_component(int b, int i, int t, i
     const float x0 = pooled * n;  // pred_lengths_0 * num_atoms (diffusion_loss.py:338)
     const float xt = lengths[3 * b + i];
     float moved;
-    if constexpr (ETA) {
+    if constexpr (INVERT) {
+        moved = invert_length_move(x0, xt, ab_t, ab_p);
+    } else if constexpr (ETA) {
         moved = eta_length_move(x0, xt, ab_t, ab_p, beta, eta, eta_length_draw(noise, 3u * b + i, t, eta, word3));
     } else {
         const float mean = (c0 * x0 + c1 * xt) / denom;
@@ -504,7 +537,7 @@ __device__ __forceinline__ void reverse_atoms_body(
 }
 
 // ---- space-group symmetry (arreau_sample_loop_sym / arreau_reverse_step_sym; rules in include/arreau_hip.h) -----------------
-// Crystal of atom i: the caller's index, or the 64-ary search of reverse_one_atom.
+// Crystal of atom i: the caller's index, or the 64-ary search of reverse_one_atom.  (Also the INVERT atom part's.)
 __device__ __forceinline__ int sym_atom_crystal(int i, int lane, const int32_t* __restrict__ offsets, int B, const int32_t* __restrict__ batch) {
     if (batch != nullptr) return batch[i];
     int lo = 0, hi = B;
@@ -656,6 +689,25 @@ __device__ __forceinline__ void reverse_atoms_body_sym(
     }
 }
 
+// The INVERT form of reverse_atoms_body: one wave per atom, the position move from the crystal's level up to its target and
+// nothing else -- the species are the caller's at every level, so neither `types` nor the logits are touched and the D3PM half
+// is not instantiated.  (The clamps are flagged by the crystal's lattice thread.)
+__device__ __forceinline__ void invert_atoms_body(int blk, float* __restrict__ frac, const int32_t* __restrict__ tstep,
+                                                  const int32_t* __restrict__ offsets, int B, int N, const float* __restrict__ eps,
+                                                  const float* __restrict__ ve_sigmas, int T, int32_t* __restrict__ status, int n0,
+                                                  const int32_t* __restrict__ batch, const StepScheduleDev* sched) {
+    const int i = n0 + blk * 4 + (int)(threadIdx.x >> 6);  // atoms n0 .. N-1
+    if (i >= N) return;  // wave-uniform; no block-level barrier below
+    const int lane = threadIdx.x & 63;
+    const int b = sym_atom_crystal(i, lane, offsets, B, batch);
+    const int s = invert_level(tstep[b], T, status, false);
+    const int t = invert_target(sched, b, s, T, status, false);
+    if (lane < 3) {
+        const size_t g = 3 * (size_t)i + lane;
+        frac[g] = invert_frac_move(frac[g], eps[g], ve_sigmas[s], ve_sigmas[t]);
+    }
+}
+
 // Sampling loop (round 3): the lattice update of a crystal by ONE workgroup that then also prepares the crystal's NEXT step --
 // what prep_kernel (node.hip) would compute at the top of that step from the lengths just written: the cell (into the
 // caller's lattice AND the workspace copy the network reads) and the per-crystal part of the embedding for timestep t - 1 (the
@@ -664,7 +716,9 @@ __device__ __forceinline__ void reverse_atoms_body_sym(
 // from the fractional coordinates).  Same arithmetic as reverse_lattice_body + prep_kernel, thread for thread.
 // TIE: the lattice-system tie of the lengths (length_tie[b]); the three x0 and current lengths are exchanged through LDS.
 // ETA: the eta move of the lengths.
-template <bool TIE, bool ETA>
+// INVERT: the inversion move of the lengths, from the crystal's level up to its target (not with TIE or ETA); the step prepared
+// is the one at the target, the HIGHER level.
+template <bool TIE, bool ETA, bool INVERT = false>
 __device__ __forceinline__ void reverse_crystal_block(int b, float* __restrict__ lengths, const float* __restrict__ angles,
                                                       const int32_t* __restrict__ tstep, const int32_t* __restrict__ offsets,
                                                       const float* __restrict__ len0, StepNoiseSrc noise,
@@ -679,9 +733,16 @@ __device__ __forceinline__ void reverse_crystal_block(int b, float* __restrict__
     __shared__ float newlen[3];
     __shared__ float feat[ARREAU_T_EMB_DIM + ARREAU_N_CRYSTAL_FEATS];
     const int t_raw = tstep[b];
-    if (threadIdx.x == 0 && (t_raw < 1 || t_raw > T)) atomicOr(status, ARREAU_STATUS_BAD_TIMESTEP);  // clamped, but flagged
-    const int t = t_raw < 1 ? 1 : (t_raw > T ? T : t_raw);
-    const int s = step_target(sched, b, t, status, threadIdx.x == 0);
+    int t, s;
+    if constexpr (INVERT) {
+        static_assert(!TIE && !ETA, "the INVERT instances are untied and take no eta");
+        t = invert_level(t_raw, T, status, threadIdx.x == 0);
+        s = invert_target(sched, b, t, T, status, threadIdx.x == 0);
+    } else {
+        if (threadIdx.x == 0 && (t_raw < 1 || t_raw > T)) atomicOr(status, ARREAU_STATUS_BAD_TIMESTEP);  // clamped, but flagged
+        t = t_raw < 1 ? 1 : (t_raw > T ? T : t_raw);
+        s = step_target(sched, b, t, status, threadIdx.x == 0);
+    }
     const int first = offsets[b], last = offsets[b + 1];
     if constexpr (TIE) {
         __shared__ float x0s[3], xts[3];
@@ -696,8 +757,8 @@ __device__ __forceinline__ void reverse_crystal_block(int b, float* __restrict__
                                                              fixed_lengths, cond, word3, eta);
     } else {
         if (threadIdx.x < 3)
-            newlen[threadIdx.x] = reverse_length_component<ETA>(b, threadIdx.x, t, s, sched, first, last, lengths, len0, noise, alpha_bars,
-                                                                betas, fixed_lengths, gs_atoms, len0_out, cond, word3, eta);
+            newlen[threadIdx.x] = reverse_length_component<ETA, INVERT>(b, threadIdx.x, t, s, sched, first, last, lengths, len0, noise,
+                                                                        alpha_bars, betas, fixed_lengths, gs_atoms, len0_out, cond, word3, eta);
     }
     __syncthreads();
     const float* ang = angles + 3 * b;

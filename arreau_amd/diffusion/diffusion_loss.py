@@ -13,6 +13,7 @@ import torch.nn as nn
 
 from . import corrector as pc
 from . import ddim
+from . import inversion
 from . import resampling as rs
 from . import respacing
 from . import screening
@@ -285,6 +286,58 @@ class DiffusionLoss(nn.Module):
         t_c = t_c.to(device=dev, dtype=torch.int32).contiguous()
         return eng.predict_scores(frac, ty, lengths, ang, t_c, off, edges=edges)
 
+    @staticmethod
+    def _atom_counts(num_atoms_per_sample, B):
+        """The atom count of every crystal, int64 [B].  Extension over the reference (uniform n only, diffusion_loss.py:308): a
+        sequence gives each crystal of the batch its own atom count (the HIP path works on CSR offsets, so ragged batches cost
+        nothing extra)."""
+        if isinstance(num_atoms_per_sample, (int, np.integer)):
+            return torch.full((B,), int(num_atoms_per_sample))
+        num_atoms = torch.as_tensor([int(v) for v in num_atoms_per_sample], dtype=torch.long)
+        if num_atoms.numel() != B or int(num_atoms.min()) < 1:
+            raise ValueError("num_atoms_per_sample must be an int or hold one positive count per crystal of the batch")
+        return num_atoms
+
+    def draw_initial_state(self, num_atoms_per_sample, num_samples_in_batch, num_atomic_states=None, constant_atoms=None,
+                           lattice_system=None, condition=None, specs=None) -> inversion.SamplerState:
+        """The host draw of sample(): the state at level T-1 a run starts from, as an inversion.SamplerState.  The reference's
+        generators in the reference's order: numpy's global generator for the angles (lattice_systems.resolve), then torch's
+        global CPU generator for randn lengths [B,3] and randn fractional coordinates [N,3] * pos_sigma_max.  Species: the mask
+        class S - 1, or constant_atoms.  lattice_system ties the lengths (the codes travel in the state); a condition's known
+        cells give their angles (its other known components are imposed on the device, by sample()); `specs` (the resolved
+        symmetry specs of sample()) project the leaders onto their sites.  Handing the result to sample(initial_state=...) under
+        the generator states this call left is the plain sample() call bit for bit."""
+        B = int(num_samples_in_batch)
+        S = int(self.num_atomic_states if num_atomic_states is None else num_atomic_states)
+        num_atoms = self._atom_counts(num_atoms_per_sample, B)
+        N = int(num_atoms.sum())
+        dt = torch.get_default_dtype()
+        # the angles per crystal (numpy's generator; lattice_system=None: the monoclinic draw in degrees, as the reference)
+        angles_np, tie = lattice_systems.resolve(lattice_system, B, condition.lattice_known() if condition is not None else None)
+        angles = torch.tensor(angles_np)
+        if condition is not None and condition.lattice_known().any():  # rule 3: the template's angles (radians)
+            known = torch.as_tensor(condition.lattice_known())
+            angles[known] = torch.as_tensor(condition.known_angles(), dtype=angles.dtype)[known]
+        lengths = torch.randn([B, 3])
+        if tie is not None:
+            lattice_systems.tie_lengths(lengths, tie)  # the initial state's tie; the device keeps it at every step
+        frac_x = torch.randn([N, 3], dtype=dt) * pos_sigma_max
+        if specs is not None:  # leaders onto their sites, members their images (unwrapped, as the draw)
+            fx = frac_x.double().numpy()
+            first = np.concatenate([[0], np.cumsum(num_atoms.numpy())])
+            for b, s_b in enumerate(specs):
+                if s_b is not None:
+                    fx[first[b]:first[b + 1]] = s_b.initial_positions(fx[first[b]:first[b + 1]])
+            frac_x = torch.as_tensor(fx).to(dt)
+        if constant_atoms is not None:
+            atom_types = torch.as_tensor(constant_atoms).reshape(-1).long()
+            if atom_types.numel() != N:
+                raise ValueError("constant_atoms must hold one class index per atom")
+        else:
+            atom_types = torch.full((N,), S - 1)
+        return inversion.SamplerState(frac_x=frac_x.numpy(), species=atom_types.numpy(), lengths=lengths.numpy(),
+                                      angles=angles.numpy(), num_atoms=num_atoms.numpy(), t=self.T - 1, length_tie=tie)
+
     @torch.no_grad()
     def sample(self, *, model, z_table: AtomicNumberTable, t_emb_weights=None, num_atoms_per_sample=None,
                num_samples_in_batch: Optional[int] = None, vis_name: str = "", visualization_setting=VisualizationSetting.NONE,
@@ -294,9 +347,10 @@ class DiffusionLoss(nn.Module):
                timesteps: Optional[Sequence[int]] = None, corrector_steps: int = 0,
                corrector_snr: float = pc.DEFAULT_SNR, resample_passes: int = 1, jump_length: int = 10,
                lattice_system=None, symmetry=None, screen=None, unique=None, find_symmetry=None, reduce_cell=None,
-               symmetrize=None, match_to=None, eta: Optional[float] = None) -> SampleResult:
+               symmetrize=None, match_to=None, eta: Optional[float] = None, initial_state=None) -> SampleResult:
         """diffusion_loss.py:276-377.  The initial state is drawn on the host exactly like the reference (numpy
-        uniforms for the angles, then randn lengths, randn fractional coordinates from torch's global CPU generator).
+        uniforms for the angles, then randn lengths, randn fractional coordinates from torch's global CPU generator):
+        draw_initial_state, which a caller may also use on its own.
         Per-step noise:
           noise="philox" (default): the whole loop is ONE library call (arreau_sample_loop): the three draws of a step are
               generated inside the update kernels from Philox4x32-10 keyed by (seed, timestep, draw, element), the
@@ -365,6 +419,18 @@ class DiffusionLoss(nn.Module):
         still draw them, so their generators advance as always).  Works with schedules, conditions, corrector steps, resampling
         (its jumps are unchanged), fixed cells, lattice systems, graph replay and frames; with `symmetry` it is rejected.  None
         is the sampler as it was, bit for bit.  No sample-quality claim is made.
+        `initial_state` (extension, every noise mode): an inversion.SamplerState -- what PONITA_DIFFUSION.noise_to (known crystals
+        forward-noised to a level), PONITA_DIFFUSION.encode (DDIM inversion) and draw_initial_state (the draw this method makes
+        itself) return.  Positions, species, lengths, angles, atom counts and the lattice-system tie come from the state and
+        nothing is drawn for them; the loop enters at the state's level t (1..T-1) instead of T-1: num_steps is resolved with
+        top = t (respacing), an explicit `timesteps` must start at t, and without either every timestep t, t-1, ..., 1 is
+        visited.  Everything after that is the sampler as it is, in every noise mode: eta, correctors, resampling, fixed_cell
+        (the state's lengths are held), max_steps, frames and the instruments.  constant_atoms: True holds the state's species; a
+        tensor of class indices replaces and holds them.  The state defines the batch: num_atoms_per_sample /
+        num_samples_in_batch may be omitted or must agree with it.  Rejected before any work: a state together with `condition`,
+        `symmetry` or `lattice_system`, a level outside 1..T-1, a batch that disagrees.  With the state draw_initial_state returns
+        under the same generator states the run is the plain one bit for bit; None is the sampler as it was.  No claim on
+        reconstruction or sample quality is made.
         `screen` (extension, every noise mode and option): a screening.ScreenCriteria, or True for its defaults -- the final
         device state is screened in one launch before it is copied back (arreau_crystal_screen; rules in include/arreau_hip.h):
         shortest contact over all periodic images, cell volume, number density, mask state.  SampleResult.metrics then holds the
@@ -414,7 +480,16 @@ class DiffusionLoss(nn.Module):
             raise ValueError("visualization_setting other than NONE needs vis_name (prefix of the frame files)")
         if noise not in ("philox", "device", "reference"):
             raise ValueError("noise must be 'philox', 'device' or 'reference'")
-        schedule = respacing.resolve_schedule(self.T, num_steps=num_steps, timesteps=timesteps)  # None: every timestep
+        if initial_state is not None:  # validated before any work; the state defines the batch and the level the loop enters at
+            inversion.check_initial_state(initial_state, self.T, condition=condition, symmetry=symmetry, lattice_system=lattice_system,
+                                          num_atoms_per_sample=num_atoms_per_sample, num_samples_in_batch=num_samples_in_batch,
+                                          num_atomic_states=len(z_table) if z_table is not None else None)
+            num_atoms_per_sample = [int(v) for v in np.asarray(initial_state.num_atoms).reshape(-1)]
+            num_samples_in_batch = len(num_atoms_per_sample)
+            schedule = inversion.schedule_from(self.T, initial_state.t, num_steps=num_steps, timesteps=timesteps)
+        else:
+            schedule = respacing.resolve_schedule(self.T, num_steps=num_steps, timesteps=timesteps)  # None: every timestep
+        top = self.T - 1 if initial_state is None else int(initial_state.t)  # the level the loop enters at
         corrector_steps, corrector_snr = pc.check_corrector(corrector_steps, corrector_snr)
         resample_passes, jump_length = rs.check_resampling(resample_passes, jump_length)
         eta = ddim.check_eta(eta) if eta is not None else None
@@ -455,39 +530,25 @@ class DiffusionLoss(nn.Module):
         eng = model.engine()
         dev = eng.device
         S = len(z_table)
-        # Extension over the reference (uniform n only, diffusion_loss.py:308): a sequence gives each crystal of
-        # the batch its own atom count (the HIP path works on CSR offsets, so ragged batches cost nothing extra).
-        if isinstance(num_atoms_per_sample, (int, np.integer)):
-            num_atoms = torch.full((B,), int(num_atoms_per_sample))
-        else:
-            num_atoms = torch.as_tensor([int(v) for v in num_atoms_per_sample], dtype=torch.long)
-            if num_atoms.numel() != B or int(num_atoms.min()) < 1:
-                raise ValueError("num_atoms_per_sample must be an int or hold one positive count per crystal of the batch")
+        num_atoms = self._atom_counts(num_atoms_per_sample, B)
         N = int(num_atoms.sum())
         dt = torch.get_default_dtype()
-        # the angles per crystal (numpy's generator; lattice_system=None: the monoclinic draw in degrees, as the reference)
-        angles_np, tie = lattice_systems.resolve(lattice_system, B, condition.lattice_known() if condition is not None else None)
-        angles = torch.tensor(angles_np)
-        if condition is not None and condition.lattice_known().any():  # rule 3: the template's angles (radians)
-            known = torch.as_tensor(condition.lattice_known())
-            angles[known] = torch.as_tensor(condition.known_angles(), dtype=angles.dtype)[known]
-        lengths = torch.randn([B, 3])
-        if tie is not None:
-            lattice_systems.tie_lengths(lengths, tie)  # the initial state's tie; the device keeps it at every step
-        frac_x = torch.randn([N, 3], dtype=dt) * pos_sigma_max
-        if specs is not None:  # leaders onto their sites, members their images (unwrapped, as the draw)
-            fx = frac_x.double().numpy()
-            first = np.concatenate([[0], np.cumsum(num_atoms.numpy())])
-            for b, s_b in enumerate(specs):
-                if s_b is not None:
-                    fx[first[b]:first[b + 1]] = s_b.initial_positions(fx[first[b]:first[b + 1]])
-            frac_x = torch.as_tensor(fx).to(dt)
-        if constant_atoms is not None:
-            atom_types = torch.as_tensor(constant_atoms).reshape(-1).long()
-            if atom_types.numel() != N:
-                raise ValueError("constant_atoms must hold one class index per atom")
-        else:
-            atom_types = torch.full((N,), S - 1)
+        if initial_state is None:
+            state = self.draw_initial_state(num_atoms_per_sample, B, num_atomic_states=S, constant_atoms=constant_atoms,
+                                            lattice_system=lattice_system, condition=condition, specs=specs)
+        else:  # nothing is drawn: the state as given, its species replaced by the ones to hold when those are given
+            state = initial_state
+            if constant_atoms is False:
+                constant_atoms = None
+            if constant_atoms is not None and constant_atoms is not True:
+                held = torch.as_tensor(constant_atoms).reshape(-1).long()
+                if held.numel() != N:
+                    raise ValueError("constant_atoms must hold one class index per atom")
+                state = inversion.SamplerState(state.frac_x, held.numpy(), state.lengths, state.angles, state.num_atoms, state.t,
+                                               state.length_tie)
+        tie = state.length_tie
+        angles, lengths = torch.as_tensor(state.angles), torch.as_tensor(state.lengths)
+        frac_x, atom_types = torch.as_tensor(state.frac_x), torch.as_tensor(state.species).long()
 
         f32 = dict(device=dev, dtype=torch.float32)
         frac_d = frac_x.to(**f32).contiguous()
@@ -500,10 +561,10 @@ class DiffusionLoss(nn.Module):
         tie_d = torch.as_tensor(tie, device=dev, dtype=torch.int32).contiguous() if tie is not None else None
         sym_d = sym_mod.device_arrays(specs, off_d, dev) if specs is not None else None
         # the timesteps this run visits, in order: every one (T-1 .. 1) or the schedule's, cut to max_steps
-        steps = list(range(self.T - 1, 0, -1)) if schedule is None else schedule
+        steps = list(range(top, 0, -1)) if schedule is None else schedule
         steps = steps if max_steps is None else steps[:max(0, int(max_steps))]
         n_steps = len(steps)
-        t_first = self.T - 1 if schedule is None else schedule[0]
+        t_first = top if schedule is None else schedule[0]
         successor = None if schedule is None else dict(zip(schedule, schedule[1:] + [0]))
         clipmax = float(getattr(self.lattice_diffusion, "clipmax", lattice_clipmax))
         next_d = respacing.next_table(self.T, schedule).to(dev) if schedule is not None and noise == "philox" else None
@@ -616,10 +677,6 @@ class DiffusionLoss(nn.Module):
         # (SampleResult.info).  Before that, when fp8 operand planes were in use (basis stash residual, cross products of the layer
         # projections): a basis value beyond e4m3's range turns into NaN there (the hardware conversion does not saturate), so the
         # batch is first re-run with two fp16 planes and three fp16 products, which the engine then keeps.
-        info = None
-        from .. import _hip as _h
-        import warnings
-
         def rerun():
             eng.status(reset=True)
             frac_d.copy_(init_state[0]); types_d.copy_(init_state[1]); len_d.copy_(init_state[2])
@@ -628,27 +685,7 @@ class DiffusionLoss(nn.Module):
                 torch.cuda.set_rng_state(cuda_rng_state, dev)
             run_loop(False)
 
-        st = eng.status(reset=False)
-        if st["flags"] == _h.STATUS_NONFINITE and eng.fp8_formats_in_use(st):
-            warnings.warn("arreau_amd: non-finite outputs with fp8 operand planes in use (a basis value beyond e4m3's range?); "
-                          "re-running the batch with two fp16 planes and three fp16 products, which this engine keeps from now on")
-            eng.set_formats(0, 0)
-            rerun()
-            info = {"fp16_planes_rerun": True}
-            st = eng.status(reset=False)
-        overflow = (st["flags"] == _h.STATUS_NONFINITE) and eng.fused_shape \
-            and (st["edge_kernel"] == "fp16x3" or st["mlp_kernel"].startswith("fp16x3"))
-        if overflow:
-            warnings.warn("arreau_amd: an activation left the fp16 range of the split-precision kernels (weights with activation "
-                          f"bounds edge {st['edge_activation_bound']:.3g} / node {st['node_activation_bound']:.3g}); re-running the "
-                          "batch on the full-range bf16x6 kernels, which this engine keeps if they come out finite")
-            previous = (st["edge_variant"], st["mlp_variant"])
-            eng.set_variant(3, 1)
-            rerun()
-            if eng.status(reset=False)["flags"] & _h.STATUS_NONFINITE:
-                eng.set_variant(*previous)  # not a range problem (e.g. a degenerate cell): keep the faster kernels, raise below
-            info = dict(info or {}, full_range_rerun=True, kernels="bf16x6", edge_activation_bound=st["edge_activation_bound"],
-                        node_activation_bound=st["node_activation_bound"])
+        info = eng.rerun_if_out_of_range(rerun)  # (shared with PONITA_DIFFUSION.encode)
         eng.check_status()  # sticky device flags (non-finite outputs, clamped indices): raise instead of returning them
         if frames:
             vis_crystal_during_sampling(z_table, types_d.cpu().numpy(), lattice_d.cpu().numpy(), frac_d.cpu().numpy(),

@@ -189,6 +189,37 @@ class HipEngine:
         self.check_status()
         return out
 
+    def rerun_if_out_of_range(self, rerun):
+        """After a loop of evaluations on a batch (sample(), encode()): the range fallback both share.  `rerun()` resets the status
+        word, restores the batch's saved initial state (and generator states) and runs the loop again, eagerly.  A NONFINITE flag
+        with fp8 operand planes in use: the planes are switched to fp16 for good and the batch is re-run.  A NONFINITE flag on the
+        default fp16x3 kernels of the fused shape: the batch is re-run on the full-range bf16x6 kernels, which the engine keeps if
+        that run came out finite.  Returns what was done (SampleResult.info), or None; the caller reads the flags afterwards."""
+        import warnings
+        info = None
+        st = self.status(reset=False)
+        if st["flags"] == _hip.STATUS_NONFINITE and self.fp8_formats_in_use(st):
+            warnings.warn("arreau_amd: non-finite outputs with fp8 operand planes in use (a basis value beyond e4m3's range?); "
+                          "re-running the batch with two fp16 planes and three fp16 products, which this engine keeps from now on")
+            self.set_formats(0, 0)
+            rerun()
+            info = {"fp16_planes_rerun": True}
+            st = self.status(reset=False)
+        overflow = (st["flags"] == _hip.STATUS_NONFINITE) and self.fused_shape \
+            and (st["edge_kernel"] == "fp16x3" or st["mlp_kernel"].startswith("fp16x3"))
+        if overflow:
+            warnings.warn("arreau_amd: an activation left the fp16 range of the split-precision kernels (weights with activation "
+                          f"bounds edge {st['edge_activation_bound']:.3g} / node {st['node_activation_bound']:.3g}); re-running the "
+                          "batch on the full-range bf16x6 kernels, which this engine keeps if they come out finite")
+            previous = (st["edge_variant"], st["mlp_variant"])
+            self.set_variant(3, 1)
+            rerun()
+            if self.status(reset=False)["flags"] & _hip.STATUS_NONFINITE:
+                self.set_variant(*previous)  # not a range problem (e.g. a degenerate cell): keep the faster kernels; the caller raises
+            info = dict(info or {}, full_range_rerun=True, kernels="bf16x6", edge_activation_bound=st["edge_activation_bound"],
+                        node_activation_bound=st["node_activation_bound"])
+        return info
+
     def set_batch_layout(self, num_atoms, groups=0):
         """Kept for callers of the former batch-slicing experiment: the library runs the score network as one stream
         over the whole batch, so `groups` 0 and 1 change nothing and larger values raise ValueError.  (Slices on
@@ -669,6 +700,46 @@ class HipEngine:
             _hip.ptr(t_crystal), _hip.ptr(offsets), B, N, _hip.ptr(z_frac), _hip.ptr(z_lengths), _hip.ptr(u_types),
             _hip.ptr(const_types), _hip.ptr(fixed_lengths), _byref(cond), _hip.ptr(lattice_out), *tie,
             _hip.stream_ptr(self.device)), name)
+
+    def noise_state(self, frac, types, lengths, angles, offsets, t, seed, lattice_out, const_types=None, fixed_lengths=None,
+                    length_tie=None):
+        """Forward noising of a clean state to level t in place (arreau_noise_state; rules in include/arreau_hip.h): the jump
+        (0, t) of every crystal with Philox draws (seed, t, kinds 6 / 7 / 8, element, word3 = 0).  Held: const_types,
+        fixed_lengths; `length_tie` ties the lengths (int32 [B] codes)."""
+        B, N = lengths.shape[0], frac.shape[0]
+        if length_tie is not None:
+            self._check_tie(length_tie, B)
+        _hip.check(_hip.lib().arreau_noise_state(
+            self._handle, _hip.ptr(frac), _hip.ptr(types), _hip.ptr(lengths), _hip.ptr(angles), _hip.ptr(offsets), B, N, int(t),
+            int(seed) & (2 ** 64 - 1), _hip.ptr(const_types), _hip.ptr(fixed_lengths), _hip.ptr(lattice_out), _hip.ptr(length_tie),
+            _hip.stream_ptr(self.device)), "arreau_noise_state")
+
+    def invert_step(self, frac, types, lengths, angles, s_crystal, t_crystal, offsets, eps, len0, lattice_out, fixed_lengths=None):
+        """One DDIM inversion step in place on (frac, lengths), per crystal from level s_crystal[b] up to t_crystal[b], on the
+        network outputs eps [N,3] and len0 [B,3] at s (arreau_invert_step); `types` is neither read nor written."""
+        B, N = lengths.shape[0], frac.shape[0]
+        _hip.check(_hip.lib().arreau_invert_step(
+            self._handle, _hip.ptr(frac), _hip.ptr(types), _hip.ptr(lengths), _hip.ptr(angles), _hip.ptr(s_crystal),
+            _hip.ptr(t_crystal), _hip.ptr(offsets), B, N, _hip.ptr(eps), _hip.ptr(len0), _hip.ptr(fixed_lengths),
+            _hip.ptr(lattice_out), _hip.stream_ptr(self.device)), "arreau_invert_step")
+
+    def invert_loop(self, frac, types, lengths, angles, offsets, t_first, n_steps, up_table, lattice_out, use_graph=False,
+                    fixed_lengths=None):
+        """n_steps DDIM inversion steps in one library call (arreau_invert_loop): the state at level t_first climbs along
+        `up_table`, the device int32 [T+1] table of inversion.ascending_table; in-place update of (frac, lengths), `types` is
+        read only.  One network evaluation per step.  t_first must be a level whose "one below" entry the table holds
+        (up_table[t_first - 1] == t_first): ascending_table writes it for every level it is given, so a climb may be cut into
+        calls at any of them; another entry is clamped and flagged on the device."""
+        T = int(self.cfg.num_timesteps)
+        if (tuple(up_table.shape) != (T + 1,) or up_table.dtype != torch.int32 or up_table.device != self.device
+                or not up_table.is_contiguous()):
+            raise ValueError(f"up_table must be a contiguous int32 tensor of shape ({T + 1},) on {self.device}")
+        N, B = frac.shape[0], lengths.shape[0]
+        ws = self.workspace(N, B)
+        _hip.check(_hip.lib().arreau_invert_loop(
+            self._handle, _hip.ptr(frac), _hip.ptr(types), _hip.ptr(lengths), _hip.ptr(angles), _hip.ptr(offsets), B, N,
+            int(t_first), int(n_steps), _hip.ptr(up_table), _hip.ptr(fixed_lengths), _hip.ptr(lattice_out), _hip.ptr(ws), ws.numel(),
+            int(bool(use_graph)), _hip.stream_ptr(self.device)), "arreau_invert_loop")
 
     def screen(self, frac, lattice, offsets, types=None, criteria=None):
         """The structural screen of a batch on this engine's device (arreau_crystal_screen; diffusion/screening.py: `screen`,

@@ -18,6 +18,13 @@ DDIM-style sampling: `--eta X` (0..1) scales the noise every step injects into p
 of the initial state alone, 1 is the ancestral step; the usual companion of `--num_steps` (DiffusionLoss.sample).  Not with
 `--symops`.
 
+Starting from given crystals: `--start_from crystals.npz --start_t K` forward-noises the file's crystals to level K (1..T-1) and
+denoises from there -- variants in the neighbourhood of the given structures; with `--invert` they are instead encoded up to
+level K by DDIM inversion, species held, and then decoded (PONITA_DIFFUSION.noise_to / encode; sample(initial_state=...)).  The
+file defines the batch (`--num_crystals` / `--num_atoms` are not used); every rank takes its contiguous share of it.
+`--num_steps` then counts the steps from K down.  `--invert` is a deterministic round trip only with `--eta 0`.  Not with
+`--template`, `--symops`, `--lattice_system`.
+
 Predictor-corrector sampling: `--corrector_steps M` runs M Langevin corrector moves on the positions before every denoising
 step, with the step-size rule's `--corrector_snr` (default 0.16; DiffusionLoss.sample).
 
@@ -286,6 +293,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--eta", type=_eta_arg, default=None,
                     help="DDIM-style sampling: scale of the noise every step injects into positions and lengths (0..1; 0 = "
                          "deterministic, 1 = ancestral; default: the sampler without it)")
+    ap.add_argument("--start_from", type=str, default=None, metavar="FILE",
+                    help="start from the crystals of this crystals.npz / .h5 instead of the prior: noised to --start_t (or, with "
+                         "--invert, encoded up to it), then sampled; the file defines the batch")
+    ap.add_argument("--start_t", type=int, default=None, metavar="K", help="--start_from: the level the sampler enters at (1..T-1)")
+    ap.add_argument("--invert", action="store_true",
+                    help="--start_from: reach --start_t by DDIM inversion (species held) instead of forward noising")
     ap.add_argument("--corrector_steps", type=_corrector_steps_arg, default=0,
                     help="predictor-corrector sampling: Langevin corrector moves on the positions per denoising step (0..16)")
     ap.add_argument("--corrector_snr", type=_corrector_snr_arg, default=0.16,
@@ -358,13 +371,13 @@ def instrument_lines(keyword, res, parts=None):
     return instruments.summary_lines(e, getattr(res, e.field), parts)
 
 
-def load_targets(filename, error):
-    """The crystals file of --match_to; `error(message)` reports a file that cannot be read."""
+def load_targets(filename, error, flag="--match_to"):
+    """The crystals file of `flag` (--match_to, --start_from); `error(message)` reports a file that cannot be read."""
     from .diffusion.inference.process_generated_crystals import load_sample_results_from_hdf5
     try:
         return load_sample_results_from_hdf5(filename)
     except (OSError, KeyError, ValueError) as e:
-        error(f"--match_to: {e}")
+        error(f"{flag}: {e}")
 
 
 def add_symmetry_search_arguments(ap):
@@ -420,6 +433,35 @@ def check_screen_arguments(args, error):
     return instrument_params("screen", args, error)
 
 
+def check_start_arguments(args, error):
+    """The combinations of --start_from / --start_t / --invert; `error(message)` reports a bad one.  True when a start file is given."""
+    if args.start_from is None:
+        if args.start_t is not None or args.invert:
+            error("--start_t / --invert need --start_from")
+        return False
+    for flag in ("template", "symops", "lattice_system"):
+        if getattr(args, flag) is not None:
+            error(f"--start_from cannot be combined with --{flag}")
+    if args.require_valid:
+        error("--start_from cannot be combined with --require_valid")
+    if args.start_t is None or args.start_t < 1:
+        error("--start_from needs --start_t K with K >= 1 (the level the sampler enters at)")
+    return True
+
+
+def generate_from_crystals(start_fn: Callable, crystals: SampleResult, num_crystals_per_batch: int = 256, rank: int = 0,
+                           world_size: int = 1, gather: Optional[Callable] = None, unique=None) -> Optional[SampleResult]:
+    """start_fn(crystals) -> SampleResult (e.g. noise_to or encode, then sample(initial_state=...)) over this rank's contiguous
+    share of the given crystals, in sub-batches.  Returns the concatenated result on rank 0 (None elsewhere when world_size > 1)."""
+    n = len(np.asarray(crystals.num_atoms))
+    mine = []
+    for a, b in template_batches(n, num_crystals_per_batch, rank, world_size):
+        keep = np.zeros(n, dtype=bool)
+        keep[a:b] = True
+        mine.append(start_fn(select_crystals(crystals, keep)))
+    return _gather_results(concat_results(mine), rank, world_size, gather, unique)
+
+
 def load_symmetry(args, error):
     """The SymmetrySpec of the --symops options (None without them); `error(message)` reports a bad combination."""
     if args.symops is None:
@@ -473,6 +515,7 @@ def main():
     import torch
     ap = build_parser()
     args = ap.parse_args()
+    start = check_start_arguments(args, ap.error)
     spec = load_symmetry(args, ap.error)
     if spec is not None and args.eta is not None:
         ap.error("--eta is not supported with --symops")
@@ -484,8 +527,11 @@ def main():
     unique = asked["unique"]  # (no sample() keyword here: every rank matches its own crystals, rank 0 the whole set)
     keywords = {k: v for k, v in asked.items() if k != "unique"}
     condition = load_template(args.template, parse_fix(args.fix)).tile(args.samples_per_template) if args.template else None
+    start_crystals = load_targets(args.start_from, ap.error, "--start_from") if start else None
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    if start and args.invert and args.eta != 0.0 and rank == 0:
+        print("note: --invert without --eta 0 decodes stochastically (positions and lengths are then no function of the encoded state)")
     # ARREAU_GENERATE_BACKEND=gloo + ARREAU_GENERATE_ONE_DEVICE=1 rehearse several ranks on a one-GPU box (the only
     # communication is the final gather of host arrays, so the backend is not on the data path)
     if os.environ.get("ARREAU_GENERATE_ONE_DEVICE", "0") == "1":
@@ -502,7 +548,14 @@ def main():
     from .diffusion.inference.visualize_crystal import VisualizationSetting
     from .lightning_wrappers.diffusion import PONITA_DIFFUSION
     model = PONITA_DIFFUSION.load_from_checkpoint(args.model_path, map_location=f"cuda:{local_rank}", strict=False)
-    if args.num_steps is not None:
+    if start:
+        from .diffusion import inversion
+        try:  # (a bad --start_t / --num_steps fails before sampling)
+            inversion.check_level(model.diffusion_loss.T, args.start_t, "--start_t")
+            inversion.schedule_from(model.diffusion_loss.T, args.start_t, num_steps=args.num_steps)
+        except ValueError as e:
+            ap.error(str(e))
+    elif args.num_steps is not None:
         from .diffusion import respacing
         respacing.resolve_schedule(model.diffusion_loss.T, num_steps=args.num_steps)  # (a bad --num_steps fails before sampling)
     if args.seed is not None:
@@ -519,7 +572,17 @@ def main():
                                 corrector_steps=args.corrector_steps, corrector_snr=args.corrector_snr,
                                 resample_passes=args.resample_passes, jump_length=args.jump_length,
                                 lattice_system=args.lattice_system, symmetry=spec, eta=args.eta, **keywords)
-    if condition is not None:
+    def start_fn(crystals):
+        with _device_turn(lock_path) if lock_path else contextlib.nullcontext():
+            state = (model.encode(crystals, t=args.start_t, num_steps=args.num_steps) if args.invert
+                     else model.noise_to(crystals, args.start_t))
+            return model.sample(visualization_setting=VisualizationSetting.NONE, initial_state=state, num_steps=args.num_steps,
+                                use_constant_atomic_symbols=True if args.invert else None, corrector_steps=args.corrector_steps,
+                                corrector_snr=args.corrector_snr, resample_passes=args.resample_passes, jump_length=args.jump_length,
+                                eta=args.eta, **keywords)
+    if start:
+        res = generate_from_crystals(start_fn, start_crystals, args.batch, rank, world, unique=unique)
+    elif condition is not None:
         res = generate_from_template(lambda c: fn(None, None, c), condition, args.batch, rank, world, unique=unique)
     elif args.require_valid:
         res = generate_valid_crystals(fn, args.num_crystals, spec.n_atoms if spec is not None else args.num_atoms, args.batch, rank,

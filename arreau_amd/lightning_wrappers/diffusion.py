@@ -329,7 +329,7 @@ class PONITA_DIFFUSION(nn.Module):
                condition=None, num_steps: Optional[int] = None, timesteps=None, corrector_steps: int = 0,
                corrector_snr: float = 0.16, resample_passes: int = 1, jump_length: int = 10,
                lattice_system=None, symmetry=None, screen=None, unique=None, find_symmetry=None, reduce_cell=None,
-               symmetrize=None, match_to=None, eta: Optional[float] = None) -> SampleResult:
+               symmetrize=None, match_to=None, eta: Optional[float] = None, initial_state=None) -> SampleResult:
         """lightning_wrappers/diffusion.py:220-253.  `num_atoms_per_sample` may also be a sequence with one atom count
         per crystal of the batch (extension; the reference supports a single int).  Frames of a visualization_setting
         other than NONE go to `<DIFFUSION_DIR>/step_<timestep>.cif` like the reference's PNGs (`vis_name` overrides the
@@ -353,19 +353,32 @@ class PONITA_DIFFUSION(nn.Module):
         crystals file, or (targets, diffusion.structure_match.StructureMatchParams)) the final crystals are matched against on the
         device; SampleResult.match holds the arrays (DiffusionLoss.sample).  `eta` (extension): DDIM-style sampling -- a float
         in [0, 1] that scales the noise every step injects into positions and lengths; 0 makes them a function of the initial
-        state alone, whatever the seed; None is the sampler as it was; not with `symmetry` (DiffusionLoss.sample)."""
+        state alone, whatever the seed; None is the sampler as it was; not with `symmetry` (DiffusionLoss.sample).
+        `initial_state` (extension): a diffusion.inversion.SamplerState -- from `noise_to` (known crystals forward-noised to a
+        level), `encode` (DDIM inversion) or DiffusionLoss.draw_initial_state: the run starts from that state at its level instead
+        of a prior draw at T-1; it defines the batch, so the two counts may be omitted; use_constant_atomic_symbols=True holds
+        the state's species; not with `condition`, `symmetry` or `lattice_system` (DiffusionLoss.sample)."""
         from ..diffusion import resampling
         resampling.check_resampling(resample_passes, jump_length)  # (raises before any work)
         if eta is not None:
             from ..diffusion import ddim
             eta = ddim.check_eta(eta)  # (raises before any work)
-        if num_steps is not None or timesteps is not None:
+        if initial_state is not None:
+            from ..diffusion import inversion
+            inversion.check_initial_state(initial_state, self.diffusion_loss.T, condition=condition, symmetry=symmetry,
+                                          lattice_system=lattice_system, num_atoms_per_sample=num_atoms_per_sample,
+                                          num_samples_in_batch=num_samples_in_batch,
+                                          num_atomic_states=self.num_atomic_states)  # (raises before any work)
+            inversion.schedule_from(self.diffusion_loss.T, initial_state.t, num_steps=num_steps, timesteps=timesteps)
+        elif num_steps is not None or timesteps is not None:
             from ..diffusion import respacing
             respacing.resolve_schedule(self.diffusion_loss.T, num_steps=num_steps, timesteps=timesteps)  # (raises before any work)
         if condition is not None and use_constant_atomic_symbols is not None and condition.species_known().any():
             raise ValueError("use_constant_atomic_symbols and a species mask both fix the species; give one of them")
         z_table = AtomicNumberTable(self.z_table_zs.tolist())
-        if use_constant_atomic_symbols is not None:
+        if initial_state is not None and isinstance(use_constant_atomic_symbols, bool):
+            constant_atoms = True if use_constant_atomic_symbols else None  # the state's own species, held
+        elif use_constant_atomic_symbols is not None:
             if not isinstance(num_atoms_per_sample, (int, np.integer)):
                 raise ValueError("use_constant_atomic_symbols needs a uniform num_atoms_per_sample")
             # one index per atom of a crystal, tiled over the batch (the reference's np.repeat at :236
@@ -382,4 +395,114 @@ class PONITA_DIFFUSION(nn.Module):
             num_steps=num_steps, timesteps=timesteps, corrector_steps=corrector_steps, corrector_snr=corrector_snr,
             resample_passes=resample_passes, jump_length=jump_length, lattice_system=lattice_system, symmetry=symmetry,
             screen=screen, unique=unique, find_symmetry=find_symmetry, reduce_cell=reduce_cell, symmetrize=symmetrize,
-            match_to=match_to, eta=eta)
+            match_to=match_to, eta=eta, initial_state=initial_state)
+
+    # ---- starting the sampler from given crystals (extension; rules in include/arreau_hip.h) -------------------------------------
+    def _crystal_state(self, crystals, t, what):
+        """(SamplerState at level t of the crystals as they are, device tensors frac, types, lengths, angles, offsets, cell): the
+        crystals of a SampleResult or a loaded crystals file -- species as class indices of this model's table, lengths and
+        angles of the cells by matrix_to_params."""
+        from ..diffusion import inversion
+        from ..diffusion.lattice_helpers import matrix_to_params
+        from ..diffusion.tools.atomic_number_table import atomic_numbers_to_indices
+        t = inversion.check_level(self.diffusion_loss.T, t, f"{what}: t")
+        num_atoms = np.asarray(crystals.num_atoms, dtype=np.int64).reshape(-1)
+        if num_atoms.size < 1 or int(num_atoms.min()) < 1:
+            raise ValueError(f"{what}: the crystals must hold at least one crystal, each with at least one atom")
+        N, B = int(num_atoms.sum()), int(num_atoms.size)
+        frac = np.asarray(crystals.frac_x, dtype=np.float64)
+        cells = np.asarray(crystals.lattice, dtype=np.float64).reshape(-1, 3, 3)
+        if frac.shape != (N, 3) or cells.shape != (B, 3, 3):
+            raise ValueError(f"{what}: frac_x must be [sum(num_atoms), 3] and lattice [len(num_atoms), 3, 3]")
+        z_table = AtomicNumberTable(self.z_table_zs.tolist())
+        try:
+            species = atomic_numbers_to_indices(z_table, np.rint(np.asarray(crystals.atomic_numbers).reshape(-1)).astype(np.int64))
+        except ValueError:
+            raise ValueError(f"{what}: an atomic number of the crystals is not in this model's table") from None
+        if species.shape != (N,):
+            raise ValueError(f"{what}: atomic_numbers must hold one entry per atom")
+        lengths, angles = matrix_to_params(cells)
+        state = inversion.SamplerState(frac_x=frac, species=species, lengths=np.asarray(lengths, dtype=np.float64),
+                                       angles=np.asarray(angles, dtype=np.float64), num_atoms=num_atoms, t=t)
+        inversion.check_state(state, self.diffusion_loss.T, self.num_atomic_states)
+        return state
+
+    def _state_to_device(self, state, dev):
+        f32 = dict(device=dev, dtype=torch.float32)
+        frac = torch.as_tensor(state.frac_x).to(**f32).contiguous()
+        types = torch.as_tensor(state.species).to(device=dev, dtype=torch.int32).contiguous()
+        lengths = torch.as_tensor(state.lengths).to(**f32).contiguous()
+        angles = torch.as_tensor(state.angles).to(**f32).contiguous()
+        off = crystal_offsets(torch.as_tensor(state.num_atoms), dev)
+        return frac, types, lengths, angles, off, torch.zeros((state.B, 3, 3), **f32)
+
+    @staticmethod
+    def _state_from_device(state, frac, types, lengths, t, length_tie=None):
+        from ..diffusion import inversion
+        return inversion.SamplerState(frac_x=frac.cpu().numpy(), species=types.cpu().numpy().astype(np.int64),
+                                      lengths=lengths.cpu().numpy(), angles=np.asarray(state.angles), num_atoms=np.asarray(state.num_atoms),
+                                      t=int(t), length_tie=length_tie)
+
+    @torch.no_grad()
+    def noise_to(self, crystals, t: int, seed: Optional[int] = None, constant_atoms: bool = False, fixed_cell: bool = False,
+                 lattice_system=None):
+        """Known crystals forward-noised to level t (1..T-1): the state a `sample(initial_state=...)` call denoises from, for
+        variants in the neighbourhood of the crystals (SDEdit; "start from existing materials").  `crystals`: a SampleResult or a
+        loaded crystals file; lengths and angles come from its cells (matrix_to_params).  One launch of the forward process in
+        closed form (arreau_noise_state; rules in include/arreau_hip.h) with Philox draws keyed by (seed, t); `seed` defaults to a
+        draw from torch's global CPU generator.  constant_atoms: the species are not noised; fixed_cell: the lengths are not
+        noised; lattice_system (one name or one per crystal, None entries allowed): the tied lengths jump together and the tie
+        travels in the state (the angles stay the crystals' own).  Returns a diffusion.inversion.SamplerState at level t."""
+        from ..diffusion import lattice_systems
+        state = self._crystal_state(crystals, t, "noise_to")
+        names = lattice_systems.check(lattice_system, state.B)
+        tie = None if names is None else np.array([0 if n is None else lattice_systems.TIE_CODES[n] for n in names], dtype=np.int32)
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        eng = self.engine()
+        dev = eng.device
+        frac, types, lengths, angles, off, cell = self._state_to_device(state, dev)
+        tie_d = torch.as_tensor(tie, device=dev, dtype=torch.int32).contiguous() if tie is not None else None
+        eng.noise_state(frac, types, lengths, angles, off, state.t, seed, cell, const_types=types.clone() if constant_atoms else None,
+                        fixed_lengths=lengths.clone() if fixed_cell else None, length_tie=tie_d)
+        eng.check_status()
+        return self._state_from_device(state, frac, types, lengths, state.t, tie)
+
+    @torch.no_grad()
+    def encode(self, crystals, t: Optional[int] = None, num_steps: Optional[int] = None, timesteps=None, fixed_cell: bool = False,
+               use_graph: Optional[bool] = None):
+        """DDIM inversion (Song, Meng & Ermon 2021, section 4.3): crystal -> latent, the inverse map of `sample(eta=0)` on
+        positions and lengths.  The crystals are taken as the state at the lowest level visited (1 by default) and climb to level
+        t (default T-1), one network evaluation per visited level below the top (arreau_invert_loop; rules in
+        include/arreau_hip.h).  The levels are those a `sample(initial_state=..., num_steps=..., timesteps=...)` call from level t
+        visits with the same keywords, ascending (inversion.encode_levels): every level without them.  The species are never
+        written: the network sees the crystals' species at every level, so the matching decode holds them
+        (use_constant_atomic_symbols=True).  fixed_cell: the lengths are held.  use_graph: replay one captured step (default: from
+        200 steps).  No exact inverse of the final 1 -> 0 denoise step, no ties, symmetry or conditions, no likelihood; no claim
+        on reconstruction quality is made.  Returns a diffusion.inversion.SamplerState at level t."""
+        from ..diffusion import inversion
+        T = self.diffusion_loss.T
+        levels = inversion.encode_levels(T, t=t, num_steps=num_steps, timesteps=timesteps)  # (raises before any work)
+        state = self._crystal_state(crystals, levels[-1], "encode")
+        n_steps = len(levels) - 1
+        eng = self.engine()
+        dev = eng.device
+        frac, types, lengths, angles, off, cell = self._state_to_device(state, dev)
+        init = (frac.clone(), lengths.clone())
+        up = torch.as_tensor(inversion.ascending_table(T, levels)).to(dev)
+        fixed = lengths.clone() if fixed_cell else None
+        if use_graph is None:
+            use_graph = n_steps >= 200
+
+        def run(use_graph):
+            eng.invert_loop(frac, types, lengths, angles, off, levels[0], n_steps, up, cell, use_graph=bool(use_graph), fixed_lengths=fixed)
+
+        def rerun():
+            eng.status(reset=True)
+            frac.copy_(init[0]); lengths.copy_(init[1])
+            run(False)
+
+        run(use_graph)
+        eng.rerun_if_out_of_range(rerun)  # the range fallback of sample(): the climb again from the saved state, full-range kernels
+        eng.check_status()
+        return self._state_from_device(state, frac, types, lengths, levels[-1])

@@ -1110,6 +1110,70 @@ int arreau_reverse_step_eta(const arreau_model* model,
                             const float* d_z_lattice, const float* d_z_frac, const float* d_u_types,
                             float* d_lattice, float lattice_clipmax, const int32_t* d_length_tie, float eta, void* stream);
 
+/* ---- Starting the sampler from given crystals (forward noising, DDIM inversion) ---------------------------------------
+ * Every loop export takes t_start, so a run may enter the schedule anywhere; what follows produces the states to enter with.
+ * Level convention: "a state at level t" is one whose first network evaluation is at timestep t.  The prior draw of a full
+ * run is a state at level T-1.  The reference has neither operation; the rules are the library's own.
+ *   1. forward noising to level t (arreau_noise_state, 1 <= t <= T): the jump (s, t) = (0, t) of the RePaint section, rule 2,
+ *      computed by the same kernel:
+ *      positions  x <- remainder(x + sqrt((sig_t - sig_0)(sig_t + sig_0)) z, 1);
+ *      lengths    l <- sqrt(abar_t) l + sqrt(1 - abar_t) z, then the cell into d_lattice;
+ *      species    q_sample with q_mats[t-1] and that kernel's Gumbel arg-max.
+ *      Held as there (rule 3): species given by d_const_types, the lengths of d_fixed_lengths; d_length_tie ties the lengths
+ *      as in the lattice-systems section (rule 2 there).  The draws are Philox (seed, t, kind 6 / 7 / 8, element, word3 = 0).
+ *      A resampled loop draws these kinds only with pass words r >= 1 (its pass 0 starts without a jump), so the keys with
+ *      word3 = 0 are free and no loop draw is ever repeated.  Fed arreau_philox_fill_word(seed, t, 6 / 7 / 8, 0, ...),
+ *      arreau_resample_jump with d_s = 0, d_t = t reproduces it bit for bit.
+ *   2. inversion step from level s up to level t (1 <= s < t <= T): the inverse of the eta = 0 step of the DDIM section
+ *      (Song, Meng & Ermon 2021, section 4.3), with the network evaluated on the state at s with timestep s.  Float32 on the
+ *      model's tables, evaluated in the order written:
+ *      positions  x_t = remainder(x_s + eps sig_s (sig_t - sig_s), 1).  The predictor's x0 estimate is x_s - sig_s^2 eps; the
+ *                 unit-variance direction sig_s eps is kept and rescaled to sig_t.
+ *      lengths    x0 = the predicted clean lengths exactly as the eta move takes them (pooled read-out times the atom count);
+ *                 rho = sqrt((1 - abar_t) / (1 - abar_s)),  l_t = sqrt(abar_t) x0 + rho (l_s - sqrt(abar_s) x0).
+ *                 No beta, no clip and no draw enters.  With d_fixed_lengths the lengths are held.
+ *      species    never written: the species the network sees at every level are the caller's (the situation of
+ *                 d_const_types in a sampling loop).  D3PM has no inverse.
+ *   3. a pair outside 1 <= s < t <= T is clamped into it (s into 1..T-1, then t into s+1..T) and sets
+ *      ARREAU_STATUS_BAD_TIMESTEP, as the descending step does for its target; crystals with valid pairs in the same batch are
+ *      not affected.
+ *   4. no noise is read and no seed enters.  Lattice-system ties, symmetry tables and conditions are not part of these rules:
+ *      the exports below do not take them.
+ *   5. identity: let x_t, l_t be the step's output for (eps, x0).  The eta = 0 step t -> s fed eps sig_s / sig_t and the same x0
+ *      returns x_s, l_s up to rounding: x_t - (eps sig_s / sig_t) sig_t (sig_t - sig_s) = x_s, and with k = 1 / rho,
+ *      (sqrt(abar_s) - k sqrt(abar_t)) x0 + k l_t = l_s.  rho reaches 63 at T = 100 and 579 at T = 1000 from level 1: the
+ *      rounding of the length move scales with rho (|l_s| + |x0|), not with |l_t|.
+ * The final step 1 -> 0 of a sampling run has no inverse here: a crystal is taken as the state at the lowest level visited.
+ * No claim on reconstruction quality is made: there is no trained checkpoint here. */
+
+/* Rule 1 in place on (d_frac, d_types, d_lengths); d_lattice[B,3,3] receives the cells.  d_const_types, d_fixed_lengths and
+ * d_length_tie may be NULL.  t outside 1..T: ARREAU_EINVAL before any work. */
+int arreau_noise_state(const arreau_model* model, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                       const int32_t* d_crystal_offsets, int32_t B, int32_t N, int32_t t, uint64_t seed,
+                       const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice,
+                       const int32_t* d_length_tie, void* stream);
+
+/* One inversion step (rules 2-3) per crystal from level d_s[b] up to d_t[b] on the caller's network outputs d_eps[N,3] and
+ * d_len0[B,3], in place on (d_frac, d_lengths); d_lattice receives the cells.  d_types is not read or written;
+ * d_fixed_lengths may be NULL.  For tests and host-driven loops: fed arreau_predict_scores' outputs at d_s it is the step of
+ * arreau_invert_loop bit for bit. */
+int arreau_invert_step(const arreau_model* model, float* d_frac, const int32_t* d_types, float* d_lengths,
+                       const float* d_angles, const int32_t* d_s, const int32_t* d_t, const int32_t* d_crystal_offsets,
+                       int32_t B, int32_t N, const float* d_eps, const float* d_len0, const float* d_fixed_lengths,
+                       float* d_lattice, void* stream);
+
+/* n_steps inversion steps in one call: the state (a state at level t_first) climbs t_first = u_0 < u_1 < ... < u_n along the
+ * device table d_up (int32 [T+1]): d_up[u_i] = u_{i+1}, and d_up[t_first - 1] = t_first -- the "one below" entry the loop's
+ * first launch advances from, mirroring the "one above" entry of a descending schedule; also at stride 1 the table is the
+ * caller's.  A climb cut into calls needs that entry for the first level of every call.  One network evaluation per step, at the level left.  Both loop forms, the shape-general path and graph replay
+ * (use_graph, from 3 steps) as in arreau_sample_loop; that the loop climbs is part of what a cached hipGraph was captured for,
+ * so a sampling graph of the same buffers is never replayed for it, or the other way round.  t_first < 1 or
+ * t_first + n_steps > T: ARREAU_EINVAL before any work; a table entry that does not climb is clamped and flagged (rule 3). */
+int arreau_invert_loop(arreau_model* model, float* d_frac, const int32_t* d_types, float* d_lengths, const float* d_angles,
+                       const int32_t* d_crystal_offsets, int32_t B, int32_t N, int32_t t_first, int32_t n_steps,
+                       const int32_t* d_up, const float* d_fixed_lengths, float* d_lattice, void* d_workspace,
+                       size_t workspace_bytes, int32_t use_graph, void* stream);
+
 /* The sampler's in-kernel noise written out: d_out[i] = draw (seed, timestep, kind, element i) -- standard normal for
  * kind 0 (z_lattice), 1 (z_frac), 3 (known positions) and 4 (known lengths), uniform [0,1) for kind 2 (u_types); d_raw[4 i .. 4 i + 3] (may be NULL) = the raw
  * Philox4x32-10 words of counter (i, timestep, kind, 0), key = seed.  Feeding these arrays to arreau_reverse_step
