@@ -34,6 +34,7 @@ EXPORTS = [
     "arreau_crystal_fingerprint", "arreau_fingerprint_match", "arreau_crystal_symmetry", "arreau_crystal_reduce",
     "arreau_crystal_symmetrize", "arreau_structure_match", "arreau_structure_match_assigned",
     "arreau_noise_state", "arreau_invert_step", "arreau_invert_loop",
+    "arreau_sample_loop_multistep", "arreau_reverse_step_multistep",
 ]
 
 STATUS_NONFINITE, STATUS_BAD_TIMESTEP, STATUS_BAD_TYPE, STATUS_BAD_TIE, STATUS_BAD_SYMMETRY = 1, 2, 4, 8, 16
@@ -82,6 +83,11 @@ class SymmetryC(Structure):
     _fields_ = [(name, c_void_p) for name in ("leader", "op", "orbit", "orbit_ptr", "orbit_atoms", "stab_ptr", "stab_ops", "rot",
                                                 "rot_inv", "trans")] + [(name, c_int32) for name in ("n_orbits", "n_orbit_atoms",
                                                                                                      "n_stab_ops", "n_ops")]
+
+
+class MultistepC(Structure):
+    """arreau_multistep: the four history buffers of second-order multistep sampling (device pointers)."""
+    _fields_ = [(name, c_void_p) for name in ("hist_eps", "hist_x0", "hist_t_atom", "hist_t_len")]
 
 
 class ScreenCriteriaC(Structure):
@@ -180,6 +186,7 @@ def _prototypes():
     """{symbol: argtypes} of every export.  Each sampling entry point is the one before it plus one option in front of the stream."""
     vp, i32, i64, u32, u64, f32, f64 = c_void_p, c_int32, c_int64, ctypes.c_uint32, ctypes.c_uint64, c_float, c_double
     cond, sched, corr, res, sym = (POINTER(t) for t in (SampleConditionC, SampleScheduleC, CorrectorC, ResamplingC, SymmetryC))
+    ms = POINTER(MultistepC)
     loop = [vp] * 6 + [i32] * 4 + [u64] + [vp] * 4 + [c_size_t, i32]
     step_to = [vp] * 8 + [i32, i32] + [vp] * 7 + [f32]
     jump = [vp] * 8 + [i32, i32] + [vp] * 5 + [cond, vp]
@@ -211,6 +218,8 @@ def _prototypes():
         "arreau_sample_loop_tied": loop + [cond, sched, corr, res, vp, vp],
         "arreau_sample_loop_sym": loop + [cond, sched, corr, res, vp, sym, vp],
         "arreau_sample_loop_eta": loop + [cond, sched, corr, res, vp, f32, vp],
+        "arreau_sample_loop_multistep": loop + [cond, sched, corr, res, vp, ms, vp],
+        "arreau_reverse_step_multistep": step_to + [vp, ms, vp],
         "arreau_condition_initial_state": [vp] * 4 + [i32, i32, i32, u64, cond, vp],
         "arreau_reverse_step_to": step_to + [vp],
         "arreau_reverse_step_tied": step_to + [vp, vp],

@@ -347,7 +347,8 @@ struct ResamplePlan {
 
 // The key of a captured step: the buffers, sizes and seed, the plan (every kernel choice of the evaluation), and the condition's
 // pointers, the schedule's table and clip, the corrector's step count and snr, the resampling's R and J (a resampled step reads
-// the pass word), the lattice systems' tie array, the symmetry tables and the eta of a DDIM-style step, which are kernel arguments
+// the pass word), the lattice systems' tie array, the symmetry tables, the eta of a DDIM-style step and the history buffers of a
+// multistep step, which are kernel arguments
 // or launch choices of the capture: a change of any of them must not replay the stale graph.  So is the direction: an inversion
 // loop (arreau_invert_loop) on the same buffers, table pointer included, captures other kernels than a sampling loop.
 SampleGraphKey sample_graph_key(const ScorePlan& score, const SampleState& st, const void* d_workspace, uint64_t seed,
@@ -373,6 +374,7 @@ SampleGraphKey sample_graph_key(const ScorePlan& score, const SampleState& st, c
         k.eta_bits = std::bit_cast<uint32_t>(opt.eta);
     }
     k.invert = opt.invert ? 1 : 0;
+    if (opt.ms) k.ms = *opt.ms;
     return k;
 }
 
@@ -381,7 +383,8 @@ int sample_loop_impl(arreau_model* m, const SampleState& st, int32_t t_start, in
                      const arreau_sample_schedule* schedule, const arreau_corrector* corrector,
                      const ResamplePlan* plan /* null: no resampling */, const int32_t* d_length_tie /* null: untied */,
                      const arreau_symmetry* sym /* null: no symmetry */, float eta /* negative: the ancestral step */, void* stream,
-                     bool invert = false /* DDIM inversion: t_start is the first level, `schedule` the ascending table; no other option */) {
+                     bool invert = false /* DDIM inversion: t_start is the first level, `schedule` the ascending table; no other option */,
+                     const arreau_multistep* ms = nullptr /* second-order multistep: the history buffers; eta is then 0 */) {
     if (corrector) {
         const int rc = arreau_corrector_check(corrector->steps, corrector->snr, "arreau_sample_loop_corrected");
         if (rc) return rc;
@@ -421,6 +424,9 @@ int sample_loop_impl(arreau_model* m, const SampleState& st, int32_t t_start, in
     opt.sym = sym;
     opt.eta = eta;
     opt.invert = invert;
+    opt.ms = ms;
+    ARREAU_REQUIRE(!ms || (!opt.cond && opt.corr.steps == 0 && !plan && !sym && !invert && eta == 0.0f),
+                   "arreau_sample_loop_multistep: a multistep loop takes no condition, corrector steps, resampling or symmetry");
     ARREAU_REQUIRE(!invert || (schedule && !opt.cond && opt.corr.steps == 0 && !plan && !d_length_tie && !sym && eta < 0.0f),
                    "arreau_invert_loop: an inversion loop takes its ascending table and no sampling option");
     if (n_steps == 0) return ARREAU_OK;
@@ -539,7 +545,8 @@ int sample_loop(const char* who, arreau_model* m, const SampleState& st, int32_t
                 void* d_workspace, size_t workspace_bytes, int32_t use_graph, void* stream,
                 const arreau_sample_condition* condition = nullptr, const arreau_sample_schedule* schedule = nullptr,
                 const arreau_corrector* corrector = nullptr, const arreau_resampling* resampling = nullptr,
-                const int32_t* d_length_tie = nullptr, const arreau_symmetry* sym = nullptr, float eta = -1.0f) {
+                const int32_t* d_length_tie = nullptr, const arreau_symmetry* sym = nullptr, float eta = -1.0f,
+                const arreau_multistep* ms = nullptr) {
     ResamplePlan plan{1, 1, {}};
     if (resampling) {
         int rc;
@@ -573,12 +580,13 @@ int sample_loop(const char* who, arreau_model* m, const SampleState& st, int32_t
         }
     }
     return sample_loop_impl(m, st, t_start, n_steps, seed, d_workspace, workspace_bytes, use_graph, condition, schedule, corrector,
-                            plan.passes > 1 ? &plan : nullptr, d_length_tie, sym, eta, stream);
+                            plan.passes > 1 ? &plan : nullptr, d_length_tie, sym, eta, stream, /*invert=*/false, ms);
 }
 }  // namespace
 
 // The exports: each of the first seven is the one before it plus one option (NULL: the loop without it), a thin adapter onto
-// sample_loop; arreau_sample_loop_eta is the tied one plus an eta.  The rules of the options are stated in include/arreau_hip.h.
+// sample_loop; arreau_sample_loop_eta is the tied one plus an eta, arreau_sample_loop_multistep the tied one plus the history buffers.
+// The rules of the options are stated in include/arreau_hip.h.
 extern "C" int arreau_sample_loop(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
                                   const int32_t* d_off, int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed,
                                   const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice, void* d_workspace,
@@ -651,6 +659,28 @@ extern "C" int arreau_sample_loop_eta(arreau_model* m, float* d_frac, int32_t* d
     const SampleState st{d_frac, d_types, d_lengths, d_angles, d_off, B, N, d_const_types, d_fixed_lengths, d_lattice};
     return sample_loop("arreau_sample_loop_eta", m, st, t_start, n_steps, seed, d_workspace, workspace_bytes, use_graph, stream,
                        condition, schedule, corrector, resampling, d_length_tie, /*sym=*/nullptr, eta + 0.0f /* -0 -> +0 */);
+}
+
+// Second-order multistep sampling (rules in include/arreau_hip.h): the eta = 0 loop whose steps extrapolate with the previous step's
+// prediction, kept in the caller's history buffers.  What the rules do not combine it with is rejected before any work.
+extern "C" int arreau_sample_loop_multistep(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                                            const int32_t* d_off, int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed,
+                                            const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice,
+                                            void* d_workspace, size_t workspace_bytes, int32_t use_graph,
+                                            const arreau_sample_condition* condition, const arreau_sample_schedule* schedule,
+                                            const arreau_corrector* corrector, const arreau_resampling* resampling,
+                                            const int32_t* d_length_tie, const arreau_multistep* multistep, void* stream) {
+    const char* who = "arreau_sample_loop_multistep";
+    int rc;
+    if ((rc = arreau_multistep_check(multistep, who))) return rc;
+    SampleConditionDev c;
+    if ((rc = arreau_condition_to_dev(condition, &c))) return rc;
+    ARREAU_REQUIRE(arreau_condition_empty(&c), std::string(who) + ": not combined with a condition");
+    ARREAU_REQUIRE(!corrector || corrector->steps == 0, std::string(who) + ": not combined with corrector steps");
+    ARREAU_REQUIRE(!resampling || resampling->passes == 1, std::string(who) + ": not combined with resampling (passes > 1)");
+    const SampleState st{d_frac, d_types, d_lengths, d_angles, d_off, B, N, d_const_types, d_fixed_lengths, d_lattice};
+    return sample_loop(who, m, st, t_start, n_steps, seed, d_workspace, workspace_bytes, use_graph, stream, nullptr, schedule, nullptr,
+                       nullptr, d_length_tie, /*sym=*/nullptr, /*eta=*/0.0f, multistep);
 }
 
 // DDIM inversion (rules in include/arreau_hip.h): the sampling loop climbing the levels of an ascending table, every step the

@@ -84,6 +84,14 @@ inline bool operator==(const arreau_symmetry& a, const arreau_symmetry& b) {
     return members(a) == members(b);
 }
 
+inline bool operator==(const arreau_multistep& a, const arreau_multistep& b) {
+    auto members = [](const arreau_multistep& h) {
+        const auto& [hist_eps, hist_x0, hist_t_atom, hist_t_len] = h;
+        return std::tie(hist_eps, hist_x0, hist_t_atom, hist_t_len);
+    };
+    return members(a) == members(b);
+}
+
 // What the cached executable graph of arreau_sample_loop was captured for (api.hip: sample_graph_key): every input that decides
 // the kernels of a captured step or their arguments.  Compared member by member; the two floats by their bits.  No member
 // initialisers: arreau_model_create zero-fills the model, and SampleGraphKey{} is the key no call has.
@@ -104,6 +112,7 @@ struct SampleGraphKey {
     int32_t eta_step;          // DDIM-style sampling: 1 when the steps are eta steps
     uint32_t eta_bits;         // their eta
     int32_t invert;            // DDIM inversion: 1 when the steps are inversion steps (arreau_invert_loop)
+    arreau_multistep ms;       // second-order multistep: the four history pointers (all null: none)
     bool operator==(const SampleGraphKey&) const = default;
 };
 
@@ -317,11 +326,15 @@ struct StepOptions {
     const int32_t* length_tie = nullptr;  // lattice systems: the tie code per crystal (TIE)
     const arreau_symmetry* sym = nullptr; // space-group symmetry: the orbit tables (SYM); not with a condition or a resampled loop
     float eta = -1.0f;                    // DDIM-style step (ETA): the noise scale in [0, 1]; negative: the ancestral step.  Not with sym
+    const arreau_multistep* ms = nullptr; // second-order multistep (MS): the history buffers; eta is then 0; a schedule and a tie only
     bool invert = false;                  // DDIM inversion (INVERT): `sched` names the HIGHER level every crystal climbs to; no other option
 };
 // DDIM-style sampling (arreau_sample_loop_eta, arreau_reverse_step_eta; the rules are stated in include/arreau_hip.h):
 // ARREAU_EINVAL unless eta is finite and lies in [0, 1].
 int arreau_eta_check(float eta, const char* who);  // update.hip
+// Second-order multistep sampling (arreau_sample_loop_multistep, arreau_reverse_step_multistep): ARREAU_EINVAL unless the struct and
+// its four history pointers are given.
+int arreau_multistep_check(const arreau_multistep* ms, const char* who);  // update.hip
 
 // One corrector move per crystal at timestep d_t[b]: z from the caller's d_z_frac [N,3], or (d_z_frac null) the Philox draw
 // (seed, t, ARREAU_DRAW_Z_CORRECTOR, element, iter; 256 pass[0] + iter with opt.pass).  Reads st.frac / offsets / B / N, opt.corr.snr,

@@ -7,7 +7,9 @@
 // TIE: the lattice-system tie of the lengths (length_tie[b]); the three x0 and current lengths are exchanged by shuffles.
 // ETA: the eta move of the lengths (update_dev.h).
 // INVERT: the inversion move of the lengths, from the crystal's level up to its target (update_dev.h; not with TIE or ETA).
-template <bool TIE, bool ETA, bool INVERT = false>
+// MS: the multistep move of the lengths (update_dev.h; with ETA, eta = 0); lane 0 of the crystal's four reads its history level,
+// hands it on by a shuffle and overwrites it.
+template <bool TIE, bool ETA, bool INVERT = false, bool MS = false>
 __device__ __forceinline__ void reverse_lattice_body(int gt /* global thread of the lattice part */, float* __restrict__ lengths, const float* __restrict__ angles,
                                        const int32_t* __restrict__ tstep, const int32_t* __restrict__ offsets,
                                        const float* __restrict__ len0, StepNoiseSrc noise,
@@ -18,7 +20,7 @@ __device__ __forceinline__ void reverse_lattice_body(int gt /* global thread of 
                                        // readout_crystals_kernel) instead of a launch of its own; len0_out receives it
                                        const float* __restrict__ gs_atoms, float* __restrict__ len0_out, const SampleConditionDev* cond,
                                        const StepScheduleDev* sched, uint32_t word3, const int32_t* __restrict__ length_tie,
-                                       float eta) {
+                                       float eta, const arreau_multistep& ms = {} /* MS only */) {
     // four lanes per crystal: lane i < 3 owns length component i (pooling, update), lane 0 then writes the cell
     const int b = b0 + (gt >> 2), i = gt & 3;
     const bool live = b < B;  // (whole groups of four are live or not; the shuffles below need every lane)
@@ -35,12 +37,19 @@ __device__ __forceinline__ void reverse_lattice_body(int gt /* global thread of 
     }
     const int first = offsets[bc], last = offsets[bc + 1];
     float mylen = 0.f;
+    int hist_p = 0;
+    if constexpr (MS) {
+        static_assert(ETA && !INVERT, "the MS instances are ETA instances (at eta = 0)");
+        if (live && i == 0) hist_p = ms.hist_t_len[b];
+        hist_p = __shfl(hist_p, (threadIdx.x & 63) & ~3, 64);
+    }
     if constexpr (TIE) {
         const int code = length_tie_code(length_tie, cond ? cond->len_mask : nullptr, bc, status, live && i == 0);
-        float x0 = 0.f, xt = 0.f;
+        float x0 = 0.f, xt = 0.f, x0p = 0.f;
         if (live && i < 3) {
             x0 = length_x0_component(b, i, first, last, len0, gs_atoms, len0_out);
             xt = lengths[3 * b + i];
+            if constexpr (MS) x0p = ms.hist_x0[3 * b + i];
         }
         const int lead = (threadIdx.x & 63) & ~3;
         float x0s[3], xts[3];
@@ -49,13 +58,29 @@ __device__ __forceinline__ void reverse_lattice_body(int gt /* global thread of 
             x0s[q] = __shfl(x0, lead + q, 64);
             xts[q] = __shfl(xt, lead + q, 64);
         }
+        if constexpr (MS) {
+            float x0ps[3];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) x0ps[q] = __shfl(x0p, lead + q, 64);
+            if (live && i < 3)
+                mylen = tied_length_component<ETA, true>(b, i, code, x0s, xts, t, s_to, sched, lengths, noise, alpha_bars, betas, fixed_lengths,
+                                                         cond, word3, eta, ms, x0ps, hist_p, T);
+        } else {
+            if (live && i < 3)
+                mylen = tied_length_component<ETA>(b, i, code, x0s, xts, t, s_to, sched, lengths, noise, alpha_bars, betas, fixed_lengths, cond,
+                                                   word3, eta);
+        }
+    } else if constexpr (MS) {
         if (live && i < 3)
-            mylen = tied_length_component<ETA>(b, i, code, x0s, xts, t, s_to, sched, lengths, noise, alpha_bars, betas, fixed_lengths, cond,
-                                               word3, eta);
+            mylen = reverse_length_component<ETA, false, true>(b, i, t, s_to, sched, first, last, lengths, len0, noise, alpha_bars, betas,
+                                                               fixed_lengths, gs_atoms, len0_out, cond, word3, eta, ms, hist_p, T);
     } else {
         if (live && i < 3)
             mylen = reverse_length_component<ETA, INVERT>(b, i, t, s_to, sched, first, last, lengths, len0, noise, alpha_bars, betas,
                                                           fixed_lengths, gs_atoms, len0_out, cond, word3, eta);
+    }
+    if constexpr (MS) {
+        if (live && i == 0) ms.hist_t_len[b] = t;
     }
     const int base = (threadIdx.x & 63) & ~3;
     float newlen[3];
@@ -94,7 +119,10 @@ __device__ __forceinline__ void reverse_lattice_body(int gt /* global thread of 
 // schedule argument names (the ascending table or the per-crystal array), lengths and positions by the inversion moves of
 // update_dev.h; the atom part is the position move alone (invert_atoms_body), so `types`, `logits` and the noise are not read.
 // Only with SCHED and none of the others.
-template <bool COND, bool SCHED, bool RESAMPLE, bool TIE, bool SYM, bool ETA, bool INVERT = false>
+// MS: second-order multistep sampling (arreau_sample_loop_multistep): an ETA instance, launched with eta = 0, whose position and
+// length moves extrapolate with the previous step's prediction kept in the history buffers `ms_arg` (update_dev.h; rules in
+// include/arreau_hip.h).  Only SCHED and TIE vary.  Without MS `ms_arg` is not read.
+template <bool COND, bool SCHED, bool RESAMPLE, bool TIE, bool SYM, bool ETA, bool INVERT = false, bool MS = false>
 __global__ __launch_bounds__(256) void reverse_kernel(
     int lat_blocks, float* __restrict__ lengths, const float* __restrict__ angles, const int32_t* __restrict__ tstep,
     const int32_t* __restrict__ offsets, const float* __restrict__ len0, StepNoiseSrc noise, const float* __restrict__ alpha_bars,
@@ -107,23 +135,37 @@ __global__ __launch_bounds__(256) void reverse_kernel(
     // sampling loop: the lattice part is one workgroup per crystal, which also prepares the next step (reverse_crystal_block)
     float* __restrict__ lattice_ws, float* __restrict__ cvec_next, const float* __restrict__ t_emb_w, const float* __restrict__ embT, int C,
     SampleConditionDev cond_arg, StepScheduleDev sched_arg, const int32_t* __restrict__ pass, const int32_t* __restrict__ length_tie,
-    arreau_symmetry sym_arg, float eta) {
+    arreau_symmetry sym_arg, float eta, arreau_multistep ms_arg) {
     const uint32_t word3 = RESAMPLE ? 256u * (uint32_t)pass[0] : 0u;  // the counter word of pass r
     const SampleConditionDev* cond = COND ? &cond_arg : nullptr;
     const StepScheduleDev* sched = SCHED ? &sched_arg : nullptr;
     if ((int)blockIdx.x < lat_blocks && cvec_next != nullptr) {  // (kernel argument: uniform)
-        reverse_crystal_block<TIE, ETA, INVERT>(b0 + (int)blockIdx.x, lengths, angles, tstep, offsets, len0, noise, alpha_bars, betas, T,
-                                                lattice, fixed_lengths, status, gs_atoms, len0_out, lattice_ws, cvec_next, t_emb_w, embT, S, C,
-                                                cond, sched, word3, length_tie, eta);
+        if constexpr (MS)
+            reverse_crystal_block<TIE, ETA, false, true>(b0 + (int)blockIdx.x, lengths, angles, tstep, offsets, len0, noise, alpha_bars, betas,
+                                                         T, lattice, fixed_lengths, status, gs_atoms, len0_out, lattice_ws, cvec_next, t_emb_w,
+                                                         embT, S, C, cond, sched, word3, length_tie, eta, ms_arg);
+        else
+            reverse_crystal_block<TIE, ETA, INVERT>(b0 + (int)blockIdx.x, lengths, angles, tstep, offsets, len0, noise, alpha_bars, betas, T,
+                                                    lattice, fixed_lengths, status, gs_atoms, len0_out, lattice_ws, cvec_next, t_emb_w, embT, S,
+                                                    C, cond, sched, word3, length_tie, eta);
         return;
     }
     if ((int)blockIdx.x < lat_blocks) {
-        reverse_lattice_body<TIE, ETA, INVERT>(blockIdx.x * blockDim.x + threadIdx.x, lengths, angles, tstep, offsets, len0, noise, alpha_bars,
-                                               betas, B_lat, T, lattice, fixed_lengths, status, b0, gs_atoms, len0_out, cond, sched, word3,
-                                               length_tie, eta);
+        if constexpr (MS)
+            reverse_lattice_body<TIE, ETA, false, true>(blockIdx.x * blockDim.x + threadIdx.x, lengths, angles, tstep, offsets, len0, noise,
+                                                        alpha_bars, betas, B_lat, T, lattice, fixed_lengths, status, b0, gs_atoms, len0_out, cond,
+                                                        sched, word3, length_tie, eta, ms_arg);
+        else
+            reverse_lattice_body<TIE, ETA, INVERT>(blockIdx.x * blockDim.x + threadIdx.x, lengths, angles, tstep, offsets, len0, noise,
+                                                   alpha_bars, betas, B_lat, T, lattice, fixed_lengths, status, b0, gs_atoms, len0_out, cond,
+                                                   sched, word3, length_tie, eta);
         return;
     }
-    if constexpr (INVERT) {
+    if constexpr (MS) {
+        static_assert(!COND && !RESAMPLE && !SYM && ETA && !INVERT, "the MS instances vary in SCHED and TIE only");
+        reverse_atoms_body<true, true>((int)blockIdx.x - lat_blocks, frac, types, tstep, offsets, B, N, eps, logits, noise, ve_sigmas, q1t, qmats,
+                                       S, T, const_types, absorbing, status, n0, batch, cond, sched, word3, eta, ms_arg);
+    } else if constexpr (INVERT) {
         static_assert(!COND && SCHED && !RESAMPLE && !TIE && !SYM && !ETA, "the INVERT instance takes a schedule and no other option");
         invert_atoms_body((int)blockIdx.x - lat_blocks, frac, tstep, offsets, B, N, eps, ve_sigmas, T, status, n0, batch, sched);
     } else if constexpr (SYM) {
@@ -151,6 +193,11 @@ void enqueue_reverse_kernel(const arreau_model* m, int lat_blocks, int atom_bloc
         if (opt.invert) kernel = reverse_kernel<false, true, false, false, false, false, true>;
     }
     if constexpr (!COND) {
+        if (opt.ms)
+            kernel = opt.length_tie ? reverse_kernel<false, SCHED, false, true, false, true, false, true>
+                                    : reverse_kernel<false, SCHED, false, false, false, true, false, true>;
+    }
+    if constexpr (!COND) {
         if (opt.sym)
             kernel = opt.length_tie ? reverse_kernel<false, SCHED, false, true, true, false> : reverse_kernel<false, SCHED, false, false, true, false>;
     }
@@ -158,7 +205,8 @@ void enqueue_reverse_kernel(const arreau_model* m, int lat_blocks, int atom_bloc
                   m->vp_alpha_bars, m->vp_betas, st.B, m->T, st.lattice, st.fixed_lengths, m->status, 0, in.gs_atoms,
                   in.gs_atoms ? const_cast<float*>(in.len0) : nullptr, st.frac, st.types, st.B, st.N, in.eps, in.logits, m->ve_sigmas, m->q1t,
                   m->qmats, m->S, st.const_types, m->qmats_absorbing, 0, in.batch, in.lattice_ws, in.cvec_next, m->t_emb_w, m->embT, m->C,
-                  cond, sched, opt.pass, opt.length_tie, opt.sym ? *opt.sym : arreau_symmetry{}, opt.eta);
+                  cond, sched, opt.pass, opt.length_tie, opt.sym ? *opt.sym : arreau_symmetry{}, opt.eta,
+                  opt.ms ? *opt.ms : arreau_multistep{});
 }
 }  // namespace
 
@@ -178,6 +226,10 @@ int arreau_launch_reverse(const arreau_model* m, const SampleState& st, const Re
     ARREAU_REQUIRE(!opt.sym || opt.eta < 0.0f, "reverse update: space-group symmetry is not combined with an eta");
     ARREAU_REQUIRE(!opt.invert || (scheduled && !conditioned && !opt.pass && !opt.length_tie && !opt.sym && opt.eta < 0.0f && opt.corr.steps == 0),
                    "reverse update: an inversion step takes its targets and no other option");
+    ARREAU_REQUIRE(!opt.ms || (!conditioned && !opt.pass && !opt.sym && !opt.invert && opt.corr.steps == 0 && opt.eta == 0.0f),
+                   "reverse update: a multistep step is the eta = 0 step and takes a schedule and a tie only");
+    ARREAU_REQUIRE(!opt.ms || (opt.ms->hist_eps && opt.ms->hist_x0 && opt.ms->hist_t_atom && opt.ms->hist_t_len),
+                   "reverse update: a multistep history pointer is null");
     if (lat_blocks + atom_blocks == 0) return ARREAU_OK;
     const SampleConditionDev c = conditioned ? *opt.cond : SampleConditionDev{};
     const StepScheduleDev sc = scheduled ? *opt.sched : StepScheduleDev{};
@@ -207,7 +259,8 @@ static int reverse_step_to(const arreau_model* m, float* d_frac, int32_t* d_type
                            const int32_t* d_t, const int32_t* d_s, const int32_t* d_off, int32_t B, int32_t N, const float* d_eps,
                            const float* d_logits, const float* d_len0, const float* d_z_lattice, const float* d_z_frac,
                            const float* d_u_types, float* d_lattice, float lattice_clipmax, const int32_t* d_length_tie,
-                           const arreau_symmetry* sym, void* stream, const char* who, float eta = -1.0f /* negative: none */) {
+                           const arreau_symmetry* sym, void* stream, const char* who, float eta = -1.0f /* negative: none */,
+                           const arreau_multistep* ms = nullptr /* the multistep history (then eta = 0) */) {
     // (at eta = 0 the draws of the lengths and positions are not read: their arrays may be null)
     ARREAU_REQUIRE(m && d_frac && d_types && d_lengths && d_angles && d_t && d_s && d_off && d_eps && d_logits && d_len0 &&
                        ((d_z_lattice && d_z_frac) || eta == 0.0f) && d_u_types && d_lattice, std::string(who) + ": null pointer");
@@ -217,7 +270,7 @@ static int reverse_step_to(const arreau_model* m, float* d_frac, int32_t* d_type
                          .lattice = d_lattice};
     const ReverseInputs in{d_t, d_eps, d_logits, d_len0, StepNoiseSrc{d_z_lattice, d_z_frac, d_u_types, 0}};
     const StepScheduleDev sched{nullptr, d_s, lattice_clipmax};
-    return arreau_launch_reverse(m, st, in, StepOptions{.sched = &sched, .length_tie = d_length_tie, .sym = sym, .eta = eta},
+    return arreau_launch_reverse(m, st, in, StepOptions{.sched = &sched, .length_tie = d_length_tie, .sym = sym, .eta = eta, .ms = ms},
                                  (hipStream_t)stream);
 }
 
@@ -257,6 +310,27 @@ extern "C" int arreau_reverse_step_eta(const arreau_model* m, float* d_frac, int
     return reverse_step_to(m, d_frac, d_types, d_lengths, d_angles, d_t, d_s, d_off, B, N, d_eps, d_logits, d_len0, d_z_lattice, d_z_frac,
                            d_u_types, d_lattice, lattice_clipmax, d_length_tie, /*sym=*/nullptr, stream, "arreau_reverse_step_eta",
                            eta + 0.0f /* -0 -> +0 */);
+}
+
+// Second-order multistep sampling: every history pointer given, or ARREAU_EINVAL.
+int arreau_multistep_check(const arreau_multistep* ms, const char* who) {
+    ARREAU_REQUIRE(ms && ms->hist_eps && ms->hist_x0 && ms->hist_t_atom && ms->hist_t_len,
+                   std::string(who) + ": a multistep history pointer is null");
+    return ARREAU_OK;
+}
+
+// arreau_reverse_step_eta at eta = 0 as the multistep step on the caller's history (rules in include/arreau_hip.h).
+extern "C" int arreau_reverse_step_multistep(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths,
+                                             const float* d_angles, const int32_t* d_t, const int32_t* d_s, const int32_t* d_off, int32_t B,
+                                             int32_t N, const float* d_eps, const float* d_logits, const float* d_len0,
+                                             const float* d_z_lattice, const float* d_z_frac, const float* d_u_types, float* d_lattice,
+                                             float lattice_clipmax, const int32_t* d_length_tie, const arreau_multistep* multistep,
+                                             void* stream) {
+    int rc;
+    if ((rc = arreau_multistep_check(multistep, "arreau_reverse_step_multistep"))) return rc;
+    return reverse_step_to(m, d_frac, d_types, d_lengths, d_angles, d_t, d_s, d_off, B, N, d_eps, d_logits, d_len0, d_z_lattice, d_z_frac,
+                           d_u_types, d_lattice, lattice_clipmax, d_length_tie, /*sym=*/nullptr, stream, "arreau_reverse_step_multistep",
+                           0.0f, multistep);
 }
 
 // DDIM inversion: one step from level d_s[b] up to level d_t[b] on the caller's network outputs (rules in include/arreau_hip.h).

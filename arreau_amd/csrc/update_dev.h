@@ -71,6 +71,36 @@ __device__ __forceinline__ float eta_length_draw(StepNoiseSrc noise, uint32_t e,
     return noise.z_lattice ? noise.z_lattice[e] : philox_normal(noise.seed, (uint32_t)t, ARREAU_DRAW_Z_LATTICE, e, word3);
 }
 
+// Second-order multistep sampling (arreau_sample_loop_multistep / arreau_reverse_step_multistep; the rules are stated in
+// include/arreau_hip.h): the MS instances are ETA instances at eta = 0 whose position and length moves extrapolate with the previous
+// step's prediction, kept per element in the caller's history buffers with the level it was made at.  Every element's history is
+// read and then overwritten by the thread that owns it; a level is read by one thread of its atom / crystal, handed to the others
+// in registers or LDS, and overwritten by that thread.  The other instances do not see this code.
+// A history level p is usable for the step that leaves t when t < p <= T (0: empty); only a usable p indexes a table.
+__device__ __forceinline__ bool ms_usable(int p, int t, int T) { return p > t && p <= T; }
+// The move is second order when p is usable, the target is not level 0 and the step-size ratio lies in [1/3, 3] (a NaN fails).
+__device__ __forceinline__ bool ms_second_order(bool usable, int s, float r) { return usable && s >= 1 && r >= 1.0f / 3.0f && r <= 3.0f; }
+// One component of the position move (rule 1), float32 in the order of the rule: e = sig_t eps, ep the history, `first` the
+// eta = 0 move (before the wrap), which a first-order step keeps.
+__device__ __forceinline__ float ms_frac_move(float first, float x, float e, float ep, float sig_t, float sig_s, float sig_p, bool usable, int s) {
+    const float r = logf(sig_p / sig_t) / logf(sig_t / sig_s);
+    if (!ms_second_order(usable, s, r)) return first;
+    const float d = e + (e - ep) / (2.0f * r);
+    return x - (sig_t - sig_s) * d;
+}
+// Half the log-SNR of a VP level.
+__device__ __forceinline__ float ms_lambda(float ab) { return 0.5f * (logf(ab) - logf(1.0f - ab)); }
+// The length move (rule 2), float32 in the order of the rule: x0p the history, ab_p the history level's abar (any value when not
+// usable), `first` the eta = 0 move, which a first-order step keeps.
+__device__ __forceinline__ float ms_length_move(float first, float x0, float x0p, float xt, float ab_t, float ab_s, float ab_p, bool usable, int s) {
+    const float lam_t = ms_lambda(ab_t);
+    const float r = (lam_t - ms_lambda(ab_p)) / (ms_lambda(ab_s) - lam_t);
+    if (!ms_second_order(usable, s, r)) return first;
+    const float k = sqrtf(fmaxf(1.0f - ab_s, 0.0f) / (1.0f - ab_t));  // eta_length_move's k at eta = 0
+    const float D = x0 + (x0 - x0p) / (2.0f * r);
+    return (sqrtf(ab_s) - k * sqrtf(ab_t)) * D + k * xt;
+}
+
 // DDIM inversion (arreau_invert_loop / arreau_invert_step; the rules are stated in include/arreau_hip.h): the INVERT instances of
 // the length and position updates climb from the level s a crystal is at to a higher level t, the inverse of the eta = 0 move.  In
 // these instances the helpers' `t` is the level the step leaves (the lower one) and their `s` the level it produces (the higher
@@ -106,14 +136,16 @@ __device__ __forceinline__ float invert_frac_move(float xs, float eps, float sig
 // lengths[3 b + i] and returns it.  A stride-1 step (always, without a schedule) takes beta from the model's betas table.
 // ETA: the move is eta_length_move's (the same beta, x0 and x_t); everything around it is as without.
 // INVERT: the move is invert_length_move's, from level t up to level s (same x0, same pooling; beta and the draw are not formed).
-template <bool ETA = false, bool INVERT = false>
+// MS (with ETA, eta = 0): the multistep move on the history `ms` with the crystal's history level hist_p; the history takes x0.
+template <bool ETA = false, bool INVERT = false, bool MS = false>
 __device__ __forceinline__ float reverse_length_component(int b, int i, int t, int s, const StepScheduleDev* sched, int first, int last, float* __restrict__ lengths,
                                                           const float* __restrict__ len0, StepNoiseSrc noise,
                                                           const float* __restrict__ alpha_bars, const float* __restrict__ betas,
                                                           const float* __restrict__ fixed_lengths, const float* __restrict__ gs_atoms,
                                                           float* __restrict__ len0_out, const SampleConditionDev* cond,
                                                           uint32_t word3 /* resampled loop: 256 r in pass r; else 0 */,
-                                                          float eta = 0.0f /* ETA only */) {
+                                                          float eta = 0.0f /* ETA only */, const arreau_multistep& ms = {} /* MS only */,
+                                                          int hist_p = 0 /* MS only */, int T = 0 /* MS only */) {
     const float* __restrict__ z = noise.z_lattice;
     const float n = (float)(last - first);
     const float ab_t = alpha_bars[t], ab_p = alpha_bars[s];
@@ -144,6 +176,11 @@ __device__ __forceinline__ float reverse_length_component(int b, int i, int t, i
         moved = invert_length_move(x0, xt, ab_t, ab_p);
     } else if constexpr (ETA) {
         moved = eta_length_move(x0, xt, ab_t, ab_p, beta, eta, eta_length_draw(noise, 3u * b + i, t, eta, word3));
+        if constexpr (MS) {
+            const bool usable = ms_usable(hist_p, t, T);
+            moved = ms_length_move(moved, x0, ms.hist_x0[3 * b + i], xt, ab_t, ab_p, alpha_bars[usable ? hist_p : t], usable, s);
+            ms.hist_x0[3 * b + i] = x0;
+        }
     } else {
         const float mean = (c0 * x0 + c1 * xt) / denom;
         const float zdraw = z ? z[3 * b + i] : philox_normal(noise.seed, (uint32_t)t, ARREAU_DRAW_Z_LATTICE, 3u * b + i, word3);
@@ -199,12 +236,15 @@ __device__ __forceinline__ float length_x0_component(int b, int i, int first, in
 // Component i of the tied update (rule 1): an axis of the tied group G takes the leader's x_t and draw (element 3 b) and the group's
 // mean x0 (summed in axis order, divided by |G|), so every axis of G computes the same bits; the others their own.  x0s / xts: the
 // crystal's three x0 and current lengths.  Writes lengths[3 b + i] and returns it.  ETA: as in reverse_length_component.
-template <bool ETA = false>
+// MS: as there; x0ps the crystal's three history values (an axis of G takes the leader's), and the history takes the x0 used.
+template <bool ETA = false, bool MS = false>
 __device__ __forceinline__ float tied_length_component(int b, int i, int code, const float* x0s, const float* xts, int t, int s,
                                                        const StepScheduleDev* sched, float* __restrict__ lengths, StepNoiseSrc noise,
                                                        const float* __restrict__ alpha_bars, const float* __restrict__ betas,
                                                        const float* __restrict__ fixed_lengths, const SampleConditionDev* cond,
-                                                       uint32_t word3, float eta = 0.0f /* ETA only */) {
+                                                       uint32_t word3, float eta = 0.0f /* ETA only */,
+                                                       const arreau_multistep& ms = {} /* MS only */, const float* x0ps = nullptr /* MS only */,
+                                                       int hist_p = 0 /* MS only */, int T = 0 /* MS only */) {
     const bool tied = length_tied(code, i);
     const float* __restrict__ z = noise.z_lattice;
     const float ab_t = alpha_bars[t], ab_p = alpha_bars[s];
@@ -220,6 +260,11 @@ __device__ __forceinline__ float tied_length_component(int b, int i, int code, c
     float moved;
     if constexpr (ETA) {
         moved = eta_length_move(x0, xt, ab_t, ab_p, beta, eta, eta_length_draw(noise, e, t, eta, word3));
+        if constexpr (MS) {
+            const bool usable = ms_usable(hist_p, t, T);
+            moved = ms_length_move(moved, x0, tied ? x0ps[0] : x0ps[i], xt, ab_t, ab_p, alpha_bars[usable ? hist_p : t], usable, s);
+            ms.hist_x0[3 * b + i] = x0;
+        }
     } else {
         const float mean = (c0 * x0 + c1 * xt) / denom;
         const float zdraw = z ? z[e] : philox_normal(noise.seed, (uint32_t)t, ARREAU_DRAW_Z_LATTICE, e, word3);
@@ -235,7 +280,8 @@ __device__ __forceinline__ float tied_length_component(int b, int i, int code, c
 // One wave per atom: VE_pbc.reverse on the fractional coordinates (diffusion_helpers.py:65-81) and
 // D3PM.reverse on the atom type (d3pm.py:74-110, 198-215), from timestep t to s (t - 1 without a schedule).  Lanes span the S
 // classes (2 per lane).  ETA: the position update is the eta move (rules in include/arreau_hip.h); the species half is unchanged.
-template <bool ETA = false>
+// MS (with ETA, eta = 0): the multistep position move on the history `ms`; lane 0 reads and then overwrites the atom's level.
+template <bool ETA = false, bool MS = false>
 __device__ __forceinline__ void reverse_one_atom(
     int i /* atom (wave-uniform) */, int lane, float* __restrict__ frac, int32_t* __restrict__ types, const int32_t* __restrict__ tstep,
     const int32_t* __restrict__ offsets, int B, const float* __restrict__ eps,
@@ -244,7 +290,9 @@ __device__ __forceinline__ void reverse_one_atom(
     int T, const int32_t* __restrict__ const_types, int absorbing, int32_t* __restrict__ status,
     const int32_t* __restrict__ batch /* crystal of each atom, or null: searched in `offsets` */,
     const SampleConditionDev* cond /* conditioned sampling, or null */, const StepScheduleDev* sched /* respaced, or null */,
-    uint32_t word3 /* resampled loop: 256 r in pass r; else 0 */, float eta = 0.0f /* ETA only */) {
+    uint32_t word3 /* resampled loop: 256 r in pass r; else 0 */, float eta = 0.0f /* ETA only */,
+    const arreau_multistep& ms = {} /* MS only */) {
+    static_assert(!MS || ETA, "the MS instances are ETA instances (at eta = 0)");
     const float* __restrict__ z_frac = noise.z_frac;
     const float* __restrict__ u_types = noise.u_types;
     // crystal of this atom = largest b with offsets[b] <= i: a 64-ary search by the whole wave (each level one
@@ -264,6 +312,11 @@ __device__ __forceinline__ void reverse_one_atom(
     int t = tstep[lo];
     t = t < 1 ? 1 : (t > T ? T : t);
     const int s_to = step_target(sched, lo, t, status, false);  // (flagged by the crystal's lattice thread)
+    int hist_p = 0;
+    if constexpr (MS) {
+        if (lane == 0) hist_p = ms.hist_t_atom[i];
+        hist_p = __builtin_amdgcn_readfirstlane(hist_p);  // (the whole wave is active here)
+    }
 
     if (lane < 3) {
         const float s = ve_sigmas[t];
@@ -280,6 +333,12 @@ __device__ __forceinline__ void reverse_one_atom(
                 const float zf = z_frac ? z_frac[g] : philox_normal(noise.seed, (uint32_t)t, ARREAU_DRAW_Z_FRAC, (uint32_t)g, word3);
                 v += eta * sp * sqrtf(1.0f - r * r) * zf;
             }
+            if constexpr (MS) {
+                const bool usable = ms_usable(hist_p, t, T);
+                const float e = eps[g] * s;
+                v = ms_frac_move(v, frac[g], e, ms.hist_eps[g], s, sp, ve_sigmas[usable ? hist_p : t], usable, s_to);
+                ms.hist_eps[g] = e;
+            }
             fv = remainder_one(v);
         } else {
             const float mean = frac[g] - eps[g] * (s2 - sp2);
@@ -289,6 +348,9 @@ __device__ __forceinline__ void reverse_one_atom(
         }
         if (cond && cond->pos_mask && cond->pos_mask[i]) fv = known_frac_component(cond, g, t, s_to, noise.seed, ve_sigmas, word3);  // rule 1
         frac[g] = fv;
+    }
+    if constexpr (MS) {
+        if (lane == 0) ms.hist_t_atom[i] = t;
     }
 
     // ---- D3PM posterior logits ------------------------------------------------------------------
@@ -522,18 +584,19 @@ __device__ __forceinline__ int d3pm_reverse_class(int i, int lane, float l0, flo
 }
 
 // the form the stand-alone kernel uses: workgroup `blk` of four waves, one atom each
-template <bool ETA>
+template <bool ETA, bool MS = false>
 __device__ __forceinline__ void reverse_atoms_body(
     int blk /* block of the atom part */, float* __restrict__ frac, int32_t* __restrict__ types, const int32_t* __restrict__ tstep,
     const int32_t* __restrict__ offsets, int B, int N, const float* __restrict__ eps,
     const float* __restrict__ logits, StepNoiseSrc noise,
     const float* __restrict__ ve_sigmas, const float* __restrict__ q1t, const float* __restrict__ qmats, int S,
     int T, const int32_t* __restrict__ const_types, int absorbing, int32_t* __restrict__ status, int n0,
-    const int32_t* __restrict__ batch, const SampleConditionDev* cond, const StepScheduleDev* sched, uint32_t word3, float eta) {
+    const int32_t* __restrict__ batch, const SampleConditionDev* cond, const StepScheduleDev* sched, uint32_t word3, float eta,
+    const arreau_multistep& ms = {} /* MS only */) {
     const int i = n0 + blk * 4 + (int)(threadIdx.x >> 6);  // atoms n0 .. N-1
     if (i >= N) return;  // wave-uniform; no block-level barrier below
-    reverse_one_atom<ETA>(i, threadIdx.x & 63, frac, types, tstep, offsets, B, eps, logits, noise, ve_sigmas, q1t, qmats, S, T, const_types,
-                          absorbing, status, batch, cond, sched, word3, eta);
+    reverse_one_atom<ETA, MS>(i, threadIdx.x & 63, frac, types, tstep, offsets, B, eps, logits, noise, ve_sigmas, q1t, qmats, S, T, const_types,
+                              absorbing, status, batch, cond, sched, word3, eta, ms);
 }
 
 // ---- space-group symmetry (arreau_sample_loop_sym / arreau_reverse_step_sym; rules in include/arreau_hip.h) -----------------
@@ -708,6 +771,17 @@ __device__ __forceinline__ void invert_atoms_body(int blk, float* __restrict__ f
     }
 }
 
+// The LDS of an MS crystal block: the crystal's three history values and, as bits, its history level.
+template <bool MS>
+__device__ __forceinline__ float* ms_block_lds() {
+    if constexpr (MS) {
+        __shared__ float v[4];
+        return v;
+    } else {
+        return nullptr;
+    }
+}
+
 // Sampling loop (round 3): the lattice update of a crystal by ONE workgroup that then also prepares the crystal's NEXT step --
 // what prep_kernel (node.hip) would compute at the top of that step from the lengths just written: the cell (into the
 // caller's lattice AND the workspace copy the network reads) and the per-crystal part of the embedding for timestep t - 1 (the
@@ -718,7 +792,9 @@ __device__ __forceinline__ void invert_atoms_body(int blk, float* __restrict__ f
 // ETA: the eta move of the lengths.
 // INVERT: the inversion move of the lengths, from the crystal's level up to its target (not with TIE or ETA); the step prepared
 // is the one at the target, the HIGHER level.
-template <bool TIE, bool ETA, bool INVERT = false>
+// MS: the multistep move of the lengths (with ETA, eta = 0); thread 0 reads the crystal's history level, hands it on through LDS
+// and overwrites it.
+template <bool TIE, bool ETA, bool INVERT = false, bool MS = false>
 __device__ __forceinline__ void reverse_crystal_block(int b, float* __restrict__ lengths, const float* __restrict__ angles,
                                                       const int32_t* __restrict__ tstep, const int32_t* __restrict__ offsets,
                                                       const float* __restrict__ len0, StepNoiseSrc noise,
@@ -729,7 +805,7 @@ __device__ __forceinline__ void reverse_crystal_block(int b, float* __restrict__
                                                       float* __restrict__ cvec_next, const float* __restrict__ t_emb_w,
                                                       const float* __restrict__ embT, int S, int C, const SampleConditionDev* cond,
                                                       const StepScheduleDev* sched, uint32_t word3, const int32_t* __restrict__ length_tie,
-                                                      float eta) {
+                                                      float eta, const arreau_multistep& ms = {} /* MS only */) {
     __shared__ float newlen[3];
     __shared__ float feat[ARREAU_T_EMB_DIM + ARREAU_N_CRYSTAL_FEATS];
     const int t_raw = tstep[b];
@@ -744,6 +820,15 @@ __device__ __forceinline__ void reverse_crystal_block(int b, float* __restrict__
         s = step_target(sched, b, t, status, threadIdx.x == 0);
     }
     const int first = offsets[b], last = offsets[b + 1];
+    float* const x0ps = ms_block_lds<MS>();  // (the other instances allocate nothing)
+    int hist_level = 0;
+    if constexpr (MS) {
+        static_assert(ETA && !INVERT, "the MS instances are ETA instances (at eta = 0)");
+        if (threadIdx.x < 3) x0ps[threadIdx.x] = ms.hist_x0[3 * b + threadIdx.x];
+        if (threadIdx.x == 0) x0ps[3] = __int_as_float(ms.hist_t_len[b]);
+        __syncthreads();
+        hist_level = __float_as_int(x0ps[3]);
+    }
     if constexpr (TIE) {
         __shared__ float x0s[3], xts[3];
         const int code = length_tie_code(length_tie, cond ? cond->len_mask : nullptr, b, status, threadIdx.x == 0);
@@ -752,15 +837,29 @@ __device__ __forceinline__ void reverse_crystal_block(int b, float* __restrict__
             xts[threadIdx.x] = lengths[3 * b + threadIdx.x];
         }
         __syncthreads();
-        if (threadIdx.x < 3)
-            newlen[threadIdx.x] = tied_length_component<ETA>(b, threadIdx.x, code, x0s, xts, t, s, sched, lengths, noise, alpha_bars, betas,
-                                                             fixed_lengths, cond, word3, eta);
+        if (threadIdx.x < 3) {
+            if constexpr (MS)
+                newlen[threadIdx.x] = tied_length_component<ETA, true>(b, threadIdx.x, code, x0s, xts, t, s, sched, lengths, noise, alpha_bars,
+                                                                       betas, fixed_lengths, cond, word3, eta, ms, x0ps, hist_level, T);
+            else
+                newlen[threadIdx.x] = tied_length_component<ETA>(b, threadIdx.x, code, x0s, xts, t, s, sched, lengths, noise, alpha_bars, betas,
+                                                                 fixed_lengths, cond, word3, eta);
+        }
     } else {
-        if (threadIdx.x < 3)
-            newlen[threadIdx.x] = reverse_length_component<ETA, INVERT>(b, threadIdx.x, t, s, sched, first, last, lengths, len0, noise,
-                                                                        alpha_bars, betas, fixed_lengths, gs_atoms, len0_out, cond, word3, eta);
+        if (threadIdx.x < 3) {
+            if constexpr (MS)
+                newlen[threadIdx.x] = reverse_length_component<ETA, false, true>(b, threadIdx.x, t, s, sched, first, last, lengths, len0, noise,
+                                                                                 alpha_bars, betas, fixed_lengths, gs_atoms, len0_out, cond, word3,
+                                                                                 eta, ms, hist_level, T);
+            else
+                newlen[threadIdx.x] = reverse_length_component<ETA, INVERT>(b, threadIdx.x, t, s, sched, first, last, lengths, len0, noise,
+                                                                            alpha_bars, betas, fixed_lengths, gs_atoms, len0_out, cond, word3, eta);
+        }
     }
     __syncthreads();
+    if constexpr (MS) {
+        if (threadIdx.x == 0) ms.hist_t_len[b] = t;
+    }
     const float* ang = angles + 3 * b;
     if (threadIdx.x == 0) {
         float Lm[9];

@@ -14,6 +14,7 @@ import torch.nn as nn
 from . import corrector as pc
 from . import ddim
 from . import inversion
+from . import multistep as multistep_mod
 from . import resampling as rs
 from . import respacing
 from . import screening
@@ -347,7 +348,8 @@ class DiffusionLoss(nn.Module):
                timesteps: Optional[Sequence[int]] = None, corrector_steps: int = 0,
                corrector_snr: float = pc.DEFAULT_SNR, resample_passes: int = 1, jump_length: int = 10,
                lattice_system=None, symmetry=None, screen=None, unique=None, find_symmetry=None, reduce_cell=None,
-               symmetrize=None, match_to=None, eta: Optional[float] = None, initial_state=None) -> SampleResult:
+               symmetrize=None, match_to=None, eta: Optional[float] = None, initial_state=None,
+               multistep: bool = False) -> SampleResult:
         """diffusion_loss.py:276-377.  The initial state is drawn on the host exactly like the reference (numpy
         uniforms for the angles, then randn lengths, randn fractional coordinates from torch's global CPU generator):
         draw_initial_state, which a caller may also use on its own.
@@ -431,6 +433,15 @@ class DiffusionLoss(nn.Module):
         `symmetry` or `lattice_system`, a level outside 1..T-1, a batch that disagrees.  With the state draw_initial_state returns
         under the same generator states the run is the plain one bit for bit; None is the sampler as it was.  No claim on
         reconstruction or sample quality is made.
+        `multistep` (extension, every noise mode): second-order multistep sampling (DPM-Solver++ 2M, Lu et al. 2022; multistep.py;
+        rules in include/arreau_hip.h; arreau_sample_loop_multistep / arreau_reverse_step_multistep) -- the deterministic eta = 0
+        step of positions and lengths, extrapolated with the previous step's prediction (in log sigma and in log-SNR time), at the
+        same one network evaluation per step; a move whose step-size ratio leaves [1/3, 3], the first move and the last are first
+        order.  The species keep the D3PM step with its draw.  The history lives in four device buffers this call allocates and
+        holds through segments (frames) and a re-run.  Works with schedules, lattice systems, fixed cells, constant_atoms,
+        initial_state, max_steps, frames, graph replay and the instruments; rejected before any work with `condition`, corrector
+        steps, resampling passes > 1, `symmetry` and an eta other than None or 0.  False is the sampler as it was, bit for bit.
+        No sample-quality claim is made.
         `screen` (extension, every noise mode and option): a screening.ScreenCriteria, or True for its defaults -- the final
         device state is screened in one launch before it is copied back (arreau_crystal_screen; rules in include/arreau_hip.h):
         shortest contact over all periodic images, cell volume, number density, mask state.  SampleResult.metrics then holds the
@@ -493,6 +504,8 @@ class DiffusionLoss(nn.Module):
         corrector_steps, corrector_snr = pc.check_corrector(corrector_steps, corrector_snr)
         resample_passes, jump_length = rs.check_resampling(resample_passes, jump_length)
         eta = ddim.check_eta(eta) if eta is not None else None
+        multistep = multistep_mod.check_multistep(multistep, eta=eta, condition=condition, corrector_steps=corrector_steps,
+                                                  resample_passes=resample_passes, symmetry=symmetry)
         if resample_passes > 1 and visualization_setting in (VisualizationSetting.ALL, VisualizationSetting.ALL_DETAILED):
             raise ValueError("resampling (resample_passes > 1) takes visualization_setting NONE or LAST: a frame inside a block "
                              "would be overwritten by the block's next pass")
@@ -589,6 +602,7 @@ class DiffusionLoss(nn.Module):
 
         corrector = (corrector_steps, corrector_snr) if corrector_steps > 0 else None
         resampling = (resample_passes, jump_length, schedule) if resample_passes > 1 else None
+        history = multistep_mod.allocate_history(N, B, dev) if multistep else None  # empty; held through every call of the run
         # the events of the host-noise modes: the visited steps, with jumps when resampling (the successor of the last step is
         # the timestep it produces)
         last_succ = (steps[-1] - 1 if schedule is None else successor[steps[-1]]) if steps else 0
@@ -613,7 +627,7 @@ class DiffusionLoss(nn.Module):
                         eng.sample_loop(frac_d, types_d, len_d, ang_d, off_d, steps[start], end - start, seed, const_d, lattice_d,
                                         use_graph=bool(use_graph), fixed_lengths=fixed, condition=cond_d, next_table=next_d,
                                         lattice_clipmax=clipmax, corrector=corrector, resampling=resampling, length_tie=tie_d,
-                                        symmetry=sym_d, eta=eta)
+                                        symmetry=sym_d, eta=eta, multistep=history)
                         start = end
                     if j is not None:
                         vis_crystal_during_sampling(z_table, types_d.cpu().numpy(), lattice_d.cpu().numpy(),
@@ -648,7 +662,11 @@ class DiffusionLoss(nn.Module):
                         eng.corrector_step(frac_d, t_d, off_d, eps, gauss(N, 3), corrector_snr)
                         eps, logits, len0 = eng.predict_scores(frac_d, types_d, len_d, ang_d, t_d, off_d)
                     z_l, z_f, u_t = gauss(B, 3), gauss(N, 3), unif(N, S)
-                    if eta is not None:  # DDIM-style sampling: the eta step (tied or not; s = t - 1 without a schedule)
+                    if history is not None:  # multistep: the eta = 0 step extrapolated with the history (no z is read)
+                        s_d.fill_(timestep - 1 if schedule is None else successor[timestep])
+                        eng.reverse_step_multistep(frac_d, types_d, len_d, ang_d, t_d, s_d, off_d, eps, logits, len0, u_t, lattice_d,
+                                                   history, tie_d, clipmax)
+                    elif eta is not None:  # DDIM-style sampling: the eta step (tied or not; s = t - 1 without a schedule)
                         s_d.fill_(timestep - 1 if schedule is None else successor[timestep])
                         eng.reverse_step_eta(frac_d, types_d, len_d, ang_d, t_d, s_d, off_d, eps, logits, len0, z_l, z_f, u_t,
                                              lattice_d, eta, tie_d, clipmax)
@@ -680,6 +698,8 @@ class DiffusionLoss(nn.Module):
         def rerun():
             eng.status(reset=True)
             frac_d.copy_(init_state[0]); types_d.copy_(init_state[1]); len_d.copy_(init_state[2])
+            if history is not None:
+                multistep_mod.empty_history(history)  # the state changed outside a step
             torch.random.set_rng_state(rng_state)
             if cuda_rng_state is not None:
                 torch.cuda.set_rng_state(cuda_rng_state, dev)

@@ -257,7 +257,7 @@ class HipEngine:
 
     def sample_loop(self, frac, types, lengths, angles, offsets, t_start, n_steps, seed, const_types, lattice_out,
                     use_graph=False, fixed_lengths=None, condition=None, next_table=None, lattice_clipmax=0.999, corrector=None,
-                    resampling=None, length_tie=None, symmetry=None, eta=None):
+                    resampling=None, length_tie=None, symmetry=None, eta=None, multistep=None):
         """n_steps iterations of the sampling loop in one library call (arreau_sample_loop; with any of the options below
         arreau_sample_loop_resampled, whose NULL options are the loop without them): in-place update of
         (frac, types, lengths); Philox noise keyed by (seed, timestep, draw, element).  `condition`: the device arrays of a
@@ -275,7 +275,15 @@ class HipEngine:
         `symmetry`: space-group symmetry (arreau_sample_loop_sym): the dict of device tables of symmetry.device_arrays; None is
         the loop without it.  Not with `condition`, corrector steps or resampling passes > 1 (the library rejects them).
         `eta`: DDIM-style sampling (arreau_sample_loop_eta): a float in [0, 1] that scales the noise every step injects into
-        positions and lengths (0: none, and the draws are not read); None is the loop without it.  Not with `symmetry`."""
+        positions and lengths (0: none, and the draws are not read); None is the loop without it.  Not with `symmetry`.
+        `multistep`: second-order multistep sampling (arreau_sample_loop_multistep): the dict of history tensors of
+        multistep.allocate_history, read and overwritten by every step and never emptied by a call; None is the loop without it.
+        Not with `condition`, corrector steps, resampling passes > 1, `symmetry` or an eta other than 0."""
+        if multistep is not None:
+            from .diffusion.multistep import check_multistep
+            check_multistep(True, eta=eta, condition=condition, corrector_steps=corrector[0] if corrector is not None else 0,
+                            resample_passes=resampling[0] if resampling is not None else 1, symmetry=symmetry)
+            eta = None  # (the multistep export takes none: its steps are the eta = 0 steps)
         if eta is not None:
             from .diffusion.ddim import check_eta
             eta = check_eta(eta)
@@ -312,7 +320,9 @@ class HipEngine:
         if length_tie is not None:
             self._check_tie(length_tie, B)
         opts = (_byref(cond), _byref(sched), _byref(corr), _byref(res))
-        if symmetry is not None:
+        if multistep is not None:
+            name, opts = "arreau_sample_loop_multistep", opts + (_hip.ptr(length_tie), _byref(self._multistep_struct(multistep, N, B)))
+        elif symmetry is not None:
             name, opts = "arreau_sample_loop_sym", opts + (_hip.ptr(length_tie), _byref(self._symmetry_struct(symmetry, N)))
         elif eta is not None:
             name, opts = "arreau_sample_loop_eta", opts + (_hip.ptr(length_tie), ctypes.c_float(eta))
@@ -323,6 +333,20 @@ class HipEngine:
         else:  # (the plain entry point: A/B runs against an older library through ARREAU_HIP_LIB call it)
             name, opts = "arreau_sample_loop", ()
         _hip.check(getattr(_hip.lib(), name)(*args, *opts, _hip.stream_ptr(self.device)), name)
+
+    def _multistep_struct(self, history, N, B):
+        """arreau_multistep of the dict of history tensors of multistep.allocate_history, with shapes, dtypes and device checked."""
+        from .diffusion.multistep import HISTORY_KEYS
+        if not isinstance(history, dict) or set(history) != set(HISTORY_KEYS):
+            raise ValueError(f"multistep history: expected a dict with exactly the keys {HISTORY_KEYS}")
+        want = {"hist_eps": ((N, 3), torch.float32), "hist_x0": ((B, 3), torch.float32), "hist_t_atom": ((N,), torch.int32),
+                "hist_t_len": ((B,), torch.int32)}
+        for n in HISTORY_KEYS:
+            t, (shape, dtype) = history[n], want[n]
+            if (not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device
+                    or not t.is_contiguous()):
+                raise ValueError(f"multistep history: {n} must be a contiguous {dtype} tensor of shape {shape} on {self.device}")
+        return _hip.MultistepC(*[_hip.ptr(history[n]).value for n in HISTORY_KEYS])
 
     def _check_tie(self, length_tie, B):
         if (tuple(length_tie.shape) != (B,) or length_tie.dtype != torch.int32 or length_tie.device != self.device
@@ -682,6 +706,16 @@ class HipEngine:
             self._check_tie(length_tie, lengths.shape[0])
         self._reverse_step_to("arreau_reverse_step_eta", frac, types, lengths, angles, t_crystal, s_crystal, offsets, eps, logits, len0,
                               z_lattice, z_frac, u_types, lattice_out, lattice_clipmax, _hip.ptr(length_tie), ctypes.c_float(eta))
+
+    def reverse_step_multistep(self, frac, types, lengths, angles, t_crystal, s_crystal, offsets, eps, logits, len0, u_types, lattice_out,
+                               history, length_tie=None, lattice_clipmax=0.999):
+        """reverse_step_eta at eta = 0 as the second-order multistep step (arreau_reverse_step_multistep): `history` the dict of
+        multistep.allocate_history, read and overwritten; no position or length draw is read; length_tie may be None."""
+        if length_tie is not None:
+            self._check_tie(length_tie, lengths.shape[0])
+        ms = self._multistep_struct(history, frac.shape[0], lengths.shape[0])
+        self._reverse_step_to("arreau_reverse_step_multistep", frac, types, lengths, angles, t_crystal, s_crystal, offsets, eps, logits,
+                              len0, None, None, u_types, lattice_out, lattice_clipmax, _hip.ptr(length_tie), _byref(ms))
 
     def resample_jump(self, frac, types, lengths, angles, s_crystal, t_crystal, offsets, z_frac, z_lengths, u_types, lattice_out,
                       const_types=None, fixed_lengths=None, condition=None, length_tie=None):

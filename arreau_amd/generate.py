@@ -18,6 +18,10 @@ DDIM-style sampling: `--eta X` (0..1) scales the noise every step injects into p
 of the initial state alone, 1 is the ancestral step; the usual companion of `--num_steps` (DiffusionLoss.sample).  Not with
 `--symops`.
 
+Second-order multistep sampling: `--multistep` extrapolates the deterministic `--eta 0` step with the previous step's prediction
+(DPM-Solver++ 2M): the same one network evaluation per step, fewer `--num_steps` for the same solver error
+(DiffusionLoss.sample).  Not with `--template`, `--symops`, corrector steps, resampling or an `--eta` other than 0.
+
 Starting from given crystals: `--start_from crystals.npz --start_t K` forward-noises the file's crystals to level K (1..T-1) and
 denoises from there -- variants in the neighbourhood of the given structures; with `--invert` they are instead encoded up to
 level K by DDIM inversion, species held, and then decoded (PONITA_DIFFUSION.noise_to / encode; sample(initial_state=...)).  The
@@ -293,6 +297,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--eta", type=_eta_arg, default=None,
                     help="DDIM-style sampling: scale of the noise every step injects into positions and lengths (0..1; 0 = "
                          "deterministic, 1 = ancestral; default: the sampler without it)")
+    ap.add_argument("--multistep", action="store_true",
+                    help="second-order multistep sampling: the deterministic --eta 0 step extrapolated with the previous step's "
+                         "prediction (fewer --num_steps for the same solver error); not with --template, --symops, corrector steps, "
+                         "resampling or an --eta other than 0")
     ap.add_argument("--start_from", type=str, default=None, metavar="FILE",
                     help="start from the crystals of this crystals.npz / .h5 instead of the prior: noised to --start_t (or, with "
                          "--invert, encoded up to it), then sampled; the file defines the batch")
@@ -519,6 +527,13 @@ def main():
     spec = load_symmetry(args, ap.error)
     if spec is not None and args.eta is not None:
         ap.error("--eta is not supported with --symops")
+    if args.multistep:
+        from .diffusion.multistep import check_multistep
+        try:
+            check_multistep(True, eta=args.eta, condition=args.template, corrector_steps=args.corrector_steps,
+                            resample_passes=args.resample_passes, symmetry=spec)
+        except ValueError as e:
+            ap.error(str(e).replace("condition=", "--template").replace("symmetry=", "--symops"))
     asked = {"screen": check_screen_arguments(args, ap.error)}  # per instrument, by its sample() keyword: its parameters, or None
     for e in INSTRUMENTS[1:]:
         asked[e.keyword] = instrument_params(e.keyword, args, ap.error) if getattr(args, e.keyword) else None
@@ -571,7 +586,8 @@ def main():
             return model.sample(n, b, VisualizationSetting.NONE, False, condition=cond, num_steps=args.num_steps,
                                 corrector_steps=args.corrector_steps, corrector_snr=args.corrector_snr,
                                 resample_passes=args.resample_passes, jump_length=args.jump_length,
-                                lattice_system=args.lattice_system, symmetry=spec, eta=args.eta, **keywords)
+                                lattice_system=args.lattice_system, symmetry=spec, eta=args.eta, multistep=args.multistep,
+                                **keywords)
     def start_fn(crystals):
         with _device_turn(lock_path) if lock_path else contextlib.nullcontext():
             state = (model.encode(crystals, t=args.start_t, num_steps=args.num_steps) if args.invert
@@ -579,7 +595,7 @@ def main():
             return model.sample(visualization_setting=VisualizationSetting.NONE, initial_state=state, num_steps=args.num_steps,
                                 use_constant_atomic_symbols=True if args.invert else None, corrector_steps=args.corrector_steps,
                                 corrector_snr=args.corrector_snr, resample_passes=args.resample_passes, jump_length=args.jump_length,
-                                eta=args.eta, **keywords)
+                                eta=args.eta, multistep=args.multistep, **keywords)
     if start:
         res = generate_from_crystals(start_fn, start_crystals, args.batch, rank, world, unique=unique)
     elif condition is not None:

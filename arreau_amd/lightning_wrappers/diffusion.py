@@ -329,7 +329,8 @@ class PONITA_DIFFUSION(nn.Module):
                condition=None, num_steps: Optional[int] = None, timesteps=None, corrector_steps: int = 0,
                corrector_snr: float = 0.16, resample_passes: int = 1, jump_length: int = 10,
                lattice_system=None, symmetry=None, screen=None, unique=None, find_symmetry=None, reduce_cell=None,
-               symmetrize=None, match_to=None, eta: Optional[float] = None, initial_state=None) -> SampleResult:
+               symmetrize=None, match_to=None, eta: Optional[float] = None, initial_state=None,
+               multistep: bool = False) -> SampleResult:
         """lightning_wrappers/diffusion.py:220-253.  `num_atoms_per_sample` may also be a sequence with one atom count
         per crystal of the batch (extension; the reference supports a single int).  Frames of a visualization_setting
         other than NONE go to `<DIFFUSION_DIR>/step_<timestep>.cif` like the reference's PNGs (`vis_name` overrides the
@@ -357,8 +358,13 @@ class PONITA_DIFFUSION(nn.Module):
         `initial_state` (extension): a diffusion.inversion.SamplerState -- from `noise_to` (known crystals forward-noised to a
         level), `encode` (DDIM inversion) or DiffusionLoss.draw_initial_state: the run starts from that state at its level instead
         of a prior draw at T-1; it defines the batch, so the two counts may be omitted; use_constant_atomic_symbols=True holds
-        the state's species; not with `condition`, `symmetry` or `lattice_system` (DiffusionLoss.sample)."""
-        from ..diffusion import resampling
+        the state's species; not with `condition`, `symmetry` or `lattice_system` (DiffusionLoss.sample).  `multistep` (extension):
+        second-order multistep sampling -- the deterministic eta = 0 step extrapolated with the previous step's prediction, for
+        fewer steps at the same solver error; not with `condition`, corrector steps, resampling, `symmetry` or an eta other than
+        None or 0 (DiffusionLoss.sample)."""
+        from ..diffusion import multistep as multistep_mod, resampling
+        multistep = multistep_mod.check_multistep(multistep, eta=eta, condition=condition, corrector_steps=corrector_steps,
+                                                  resample_passes=resample_passes, symmetry=symmetry)  # (raises before any work)
         resampling.check_resampling(resample_passes, jump_length)  # (raises before any work)
         if eta is not None:
             from ..diffusion import ddim
@@ -395,7 +401,7 @@ class PONITA_DIFFUSION(nn.Module):
             num_steps=num_steps, timesteps=timesteps, corrector_steps=corrector_steps, corrector_snr=corrector_snr,
             resample_passes=resample_passes, jump_length=jump_length, lattice_system=lattice_system, symmetry=symmetry,
             screen=screen, unique=unique, find_symmetry=find_symmetry, reduce_cell=reduce_cell, symmetrize=symmetrize,
-            match_to=match_to, eta=eta, initial_state=initial_state)
+            match_to=match_to, eta=eta, initial_state=initial_state, multistep=multistep)
 
     # ---- starting the sampler from given crystals (extension; rules in include/arreau_hip.h) -------------------------------------
     def _crystal_state(self, crystals, t, what):

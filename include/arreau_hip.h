@@ -1110,6 +1110,68 @@ int arreau_reverse_step_eta(const arreau_model* model,
                             const float* d_z_lattice, const float* d_z_frac, const float* d_u_types,
                             float* d_lattice, float lattice_clipmax, const int32_t* d_length_tie, float eta, void* stream);
 
+/* ---- Second-order multistep sampling (the previous step's prediction extrapolates the move) ------------------------------
+ * Lu et al. 2022 ("DPM-Solver++", the 2M rule): the eta = 0 step of the section above is a first-order solver of the
+ * probability-flow ODE, so its error falls as 1/K on K steps.  Keeping the previous step's prediction and extrapolating with it
+ * makes the move second order at the same one network evaluation per step.  The reference has no such option; the rules are the
+ * library's own.  The step leaves level t for level s (t - 1, or the scheduled successor).  Float32 on the model's tables,
+ * evaluated in the order written.
+ *   History: the caller provides hist_eps[N,3] and hist_x0[B,3] (float32), hist_t_atom[N] and hist_t_len[B] (int32): per element
+ *   the previous prediction, per atom / crystal the level p it was made at; a level of 0 means empty.  Every element's history and
+ *   level are read and then overwritten by the thread that owns them: no cross-thread ordering and no second buffer, so one captured
+ *   graph step serves every replay.  A history level p is usable when t < p <= T (only a usable p indexes a table).
+ *   1. VE positions (noise prediction, log-sigma time).  e = sig_t eps;  r = logf(sig_p / sig_t) / logf(sig_t / sig_s).  The move is
+ *      second order when p is usable, s >= 1 and 1/3 <= r <= 3 (float32 compares with 1.0f / 3.0f and 3.0f: a NaN or an infinite r
+ *      fails).  Then d = e + (e - e_p) / (2 r) and x_s = remainder(x_t - (sig_t - sig_s) d, 1).  Otherwise the move is the eta = 0
+ *      move of the DDIM section, bit for bit.  Then hist_eps <- e and the atom's level <- t.
+ *   2. VP lengths (x0 prediction, log-SNR time).  x0 as in the step (pooled read-out times the atom count, or the tied group's
+ *      mean);  lam_u = 0.5 (logf(abar_u) - logf(1 - abar_u));  r = (lam_t - lam_p) / (lam_s - lam_t);  k as in rule 2 of the DDIM
+ *      section at eta = 0, k = sqrt(max(1 - abar_s, 0) / (1 - abar_t)).  Second order under the same three conditions:
+ *      D = x0 + (x0 - x0_p) / (2 r) and l_s = (sqrt(abar_s) - k sqrt(abar_t)) D + k x_t.  Otherwise the eta = 0 length move, bit for
+ *      bit (at s = 0: l = x0).  Then hist_x0 <- x0 (per axis, the value used) and the crystal's level <- t.  Tied axes take the
+ *      leader's x_t and history value and the group's mean x0, and stay bitwise equal.  A fixed cell holds its lengths as without
+ *      (its history is still kept).
+ *   3. species: unchanged -- the D3PM step with its draw, kind 2, the same keys.  No position or length draw is read (a caller's
+ *      d_z_lattice / d_z_frac may be NULL).
+ *   4. the caller empties the levels (zero-fills hist_t_atom and hist_t_len) whenever the state changes outside a step.  A loop call
+ *      never empties them, so a run cut into calls (frames, segments) is the run in one call.  The four pointers are part of what a
+ *      cached hipGraph was captured for.
+ *   5. combines with schedules, the lattice-system tie, fixed cells, constant species, any t_start, graph replay, both loop forms,
+ *      the shape-general path and, on the step export, per-crystal timesteps.
+ *   6. rejected with ARREAU_EINVAL before any work: a condition, corrector steps > 0, resampling passes > 1, a NULL struct or
+ *      history pointer.  The exports take no symmetry tables and no eta.
+ * The step-size guard: a second-order move across very unequal steps (the cosine schedule's first respaced step has r above 4 in
+ * log-SNR units at T = 1000: 5.4 at K = 24) extrapolates further than the history supports; such a move is first order.
+ * No claim on sample quality is made: there is no trained checkpoint here. */
+typedef struct arreau_multistep {
+    float* hist_eps;       /* [N,3] sig_p eps of the previous step */
+    float* hist_x0;        /* [B,3] its predicted clean lengths */
+    int32_t* hist_t_atom;  /* [N]   the level the atom's hist_eps was made at (0: empty) */
+    int32_t* hist_t_len;   /* [B]   the level the crystal's hist_x0 was made at (0: empty) */
+} arreau_multistep;
+
+/* arreau_sample_loop_tied with the multistep step above in every step (`multistep` is a host pointer to the struct of device
+ * pointers; d_length_tie, schedule and the fixed / constant arrays may be NULL as there; condition, corrector and resampling must be
+ * NULL or empty, rule 6): both loop forms, the shape-general path and graph replay. */
+int arreau_sample_loop_multistep(arreau_model* model, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                                 const int32_t* d_crystal_offsets, int32_t B, int32_t N, int32_t t_start, int32_t n_steps,
+                                 uint64_t seed, const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice,
+                                 void* d_workspace, size_t workspace_bytes, int32_t use_graph,
+                                 const arreau_sample_condition* cond, const arreau_sample_schedule* schedule,
+                                 const arreau_corrector* corrector, const arreau_resampling* resampling, const int32_t* d_length_tie,
+                                 const arreau_multistep* multistep, void* stream);
+
+/* arreau_reverse_step_eta at eta = 0 as the multistep step (the caller's uniforms for the species; d_z_lattice and d_z_frac are not
+ * read and may be NULL; d_length_tie may be NULL).  With empty levels it is arreau_reverse_step_eta at eta = 0 bit for bit; fed
+ * arreau_philox_fill's draws it is the step of arreau_sample_loop_multistep bit for bit. */
+int arreau_reverse_step_multistep(const arreau_model* model,
+                                  float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                                  const int32_t* d_t, const int32_t* d_s, const int32_t* d_crystal_offsets, int32_t B, int32_t N,
+                                  const float* d_eps, const float* d_logits, const float* d_len0,
+                                  const float* d_z_lattice, const float* d_z_frac, const float* d_u_types,
+                                  float* d_lattice, float lattice_clipmax, const int32_t* d_length_tie,
+                                  const arreau_multistep* multistep, void* stream);
+
 /* ---- Starting the sampler from given crystals (forward noising, DDIM inversion) ---------------------------------------
  * Every loop export takes t_start, so a run may enter the schedule anywhere; what follows produces the states to enter with.
  * Level convention: "a state at level t" is one whose first network evaluation is at timestep t.  The prior draw of a full
