@@ -35,6 +35,7 @@ EXPORTS = [
     "arreau_crystal_symmetrize", "arreau_structure_match", "arreau_structure_match_assigned",
     "arreau_noise_state", "arreau_invert_step", "arreau_invert_loop",
     "arreau_sample_loop_multistep", "arreau_reverse_step_multistep",
+    "arreau_sample_loop_species", "arreau_reverse_step_species",
 ]
 
 STATUS_NONFINITE, STATUS_BAD_TIMESTEP, STATUS_BAD_TYPE, STATUS_BAD_TIE, STATUS_BAD_SYMMETRY = 1, 2, 4, 8, 16
@@ -88,6 +89,11 @@ class SymmetryC(Structure):
 class MultistepC(Structure):
     """arreau_multistep: the four history buffers of second-order multistep sampling (device pointers)."""
     _fields_ = [(name, c_void_p) for name in ("hist_eps", "hist_x0", "hist_t_atom", "hist_t_len")]
+
+
+class SpeciesControlC(Structure):
+    """arreau_species_control: the admission rows [B,4] uint32 (device pointer; NULL: every class) and the species temperature."""
+    _fields_ = [("d_allow", c_void_p), ("temperature", c_float)]
 
 
 class ScreenCriteriaC(Structure):
@@ -187,6 +193,7 @@ def _prototypes():
     vp, i32, i64, u32, u64, f32, f64 = c_void_p, c_int32, c_int64, ctypes.c_uint32, ctypes.c_uint64, c_float, c_double
     cond, sched, corr, res, sym = (POINTER(t) for t in (SampleConditionC, SampleScheduleC, CorrectorC, ResamplingC, SymmetryC))
     ms = POINTER(MultistepC)
+    spec, f32p = POINTER(SpeciesControlC), POINTER(c_float)
     loop = [vp] * 6 + [i32] * 4 + [u64] + [vp] * 4 + [c_size_t, i32]
     step_to = [vp] * 8 + [i32, i32] + [vp] * 7 + [f32]
     jump = [vp] * 8 + [i32, i32] + [vp] * 5 + [cond, vp]
@@ -220,6 +227,8 @@ def _prototypes():
         "arreau_sample_loop_eta": loop + [cond, sched, corr, res, vp, f32, vp],
         "arreau_sample_loop_multistep": loop + [cond, sched, corr, res, vp, ms, vp],
         "arreau_reverse_step_multistep": step_to + [vp, ms, vp],
+        "arreau_sample_loop_species": loop + [cond, sched, corr, res, vp, sym, f32p, ms, spec, vp],
+        "arreau_reverse_step_species": step_to + [vp, sym, f32p, ms, spec, vp],
         "arreau_condition_initial_state": [vp] * 4 + [i32, i32, i32, u64, cond, vp],
         "arreau_reverse_step_to": step_to + [vp],
         "arreau_reverse_step_tied": step_to + [vp, vp],

@@ -347,8 +347,8 @@ struct ResamplePlan {
 
 // The key of a captured step: the buffers, sizes and seed, the plan (every kernel choice of the evaluation), and the condition's
 // pointers, the schedule's table and clip, the corrector's step count and snr, the resampling's R and J (a resampled step reads
-// the pass word), the lattice systems' tie array, the symmetry tables, the eta of a DDIM-style step and the history buffers of a
-// multistep step, which are kernel arguments
+// the pass word), the lattice systems' tie array, the symmetry tables, the eta of a DDIM-style step, the history buffers of a
+// multistep step and the admission rows and temperature of species control, which are kernel arguments
 // or launch choices of the capture: a change of any of them must not replay the stale graph.  So is the direction: an inversion
 // loop (arreau_invert_loop) on the same buffers, table pointer included, captures other kernels than a sampling loop.
 SampleGraphKey sample_graph_key(const ScorePlan& score, const SampleState& st, const void* d_workspace, uint64_t seed,
@@ -375,6 +375,11 @@ SampleGraphKey sample_graph_key(const ScorePlan& score, const SampleState& st, c
     }
     k.invert = opt.invert ? 1 : 0;
     if (opt.ms) k.ms = *opt.ms;
+    if (opt.species) {
+        k.species = 1;
+        k.species_allow = opt.species->d_allow;
+        k.species_tau_bits = std::bit_cast<uint32_t>(opt.species->temperature);
+    }
     return k;
 }
 
@@ -384,7 +389,8 @@ int sample_loop_impl(arreau_model* m, const SampleState& st, int32_t t_start, in
                      const ResamplePlan* plan /* null: no resampling */, const int32_t* d_length_tie /* null: untied */,
                      const arreau_symmetry* sym /* null: no symmetry */, float eta /* negative: the ancestral step */, void* stream,
                      bool invert = false /* DDIM inversion: t_start is the first level, `schedule` the ascending table; no other option */,
-                     const arreau_multistep* ms = nullptr /* second-order multistep: the history buffers; eta is then 0 */) {
+                     const arreau_multistep* ms = nullptr /* second-order multistep: the history buffers; eta is then 0 */,
+                     const arreau_species_control* species = nullptr /* species control (checked by the export) */) {
     if (corrector) {
         const int rc = arreau_corrector_check(corrector->steps, corrector->snr, "arreau_sample_loop_corrected");
         if (rc) return rc;
@@ -425,6 +431,7 @@ int sample_loop_impl(arreau_model* m, const SampleState& st, int32_t t_start, in
     opt.eta = eta;
     opt.invert = invert;
     opt.ms = ms;
+    opt.species = species;
     ARREAU_REQUIRE(!ms || (!opt.cond && opt.corr.steps == 0 && !plan && !sym && !invert && eta == 0.0f),
                    "arreau_sample_loop_multistep: a multistep loop takes no condition, corrector steps, resampling or symmetry");
     ARREAU_REQUIRE(!invert || (schedule && !opt.cond && opt.corr.steps == 0 && !plan && !d_length_tie && !sym && eta < 0.0f),
@@ -546,7 +553,7 @@ int sample_loop(const char* who, arreau_model* m, const SampleState& st, int32_t
                 const arreau_sample_condition* condition = nullptr, const arreau_sample_schedule* schedule = nullptr,
                 const arreau_corrector* corrector = nullptr, const arreau_resampling* resampling = nullptr,
                 const int32_t* d_length_tie = nullptr, const arreau_symmetry* sym = nullptr, float eta = -1.0f,
-                const arreau_multistep* ms = nullptr) {
+                const arreau_multistep* ms = nullptr, const arreau_species_control* species = nullptr) {
     ResamplePlan plan{1, 1, {}};
     if (resampling) {
         int rc;
@@ -580,7 +587,7 @@ int sample_loop(const char* who, arreau_model* m, const SampleState& st, int32_t
         }
     }
     return sample_loop_impl(m, st, t_start, n_steps, seed, d_workspace, workspace_bytes, use_graph, condition, schedule, corrector,
-                            plan.passes > 1 ? &plan : nullptr, d_length_tie, sym, eta, stream, /*invert=*/false, ms);
+                            plan.passes > 1 ? &plan : nullptr, d_length_tie, sym, eta, stream, /*invert=*/false, ms, species);
 }
 }  // namespace
 
@@ -681,6 +688,44 @@ extern "C" int arreau_sample_loop_multistep(arreau_model* m, float* d_frac, int3
     const SampleState st{d_frac, d_types, d_lengths, d_angles, d_off, B, N, d_const_types, d_fixed_lengths, d_lattice};
     return sample_loop(who, m, st, t_start, n_steps, seed, d_workspace, workspace_bytes, use_graph, stream, nullptr, schedule, nullptr,
                        nullptr, d_length_tie, /*sym=*/nullptr, /*eta=*/0.0f, multistep);
+}
+
+// Species control (rules in include/arreau_hip.h): whichever of the loops above the options name, its steps the SPEC instances.
+// The checks of arreau_sample_loop_sym / _eta / _multistep run first, under this export's name; what the loops do not combine is
+// rejected by them as before.
+extern "C" int arreau_sample_loop_species(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                                          const int32_t* d_off, int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed,
+                                          const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice,
+                                          void* d_workspace, size_t workspace_bytes, int32_t use_graph,
+                                          const arreau_sample_condition* condition, const arreau_sample_schedule* schedule,
+                                          const arreau_corrector* corrector, const arreau_resampling* resampling,
+                                          const int32_t* d_length_tie, const arreau_symmetry* symmetry, const float* eta,
+                                          const arreau_multistep* multistep, const arreau_species_control* species, void* stream) {
+    const char* who = "arreau_sample_loop_species";
+    int rc;
+    arreau_species_control sp;
+    if ((rc = arreau_species_check(species, who, &sp))) return rc;
+    if (eta && (rc = arreau_eta_check(*eta, who))) return rc;
+    ARREAU_REQUIRE(!symmetry || !eta, std::string(who) + ": space-group symmetry is not combined with an eta");
+    if (symmetry) {
+        if ((rc = arreau_symmetry_check(symmetry, who))) return rc;
+        ARREAU_REQUIRE(!resampling || resampling->passes <= 1, std::string(who) + ": space-group symmetry is not combined with resampling (passes > 1)");
+    }
+    if (multistep) {
+        if ((rc = arreau_multistep_check(multistep, who))) return rc;
+        SampleConditionDev c;
+        if ((rc = arreau_condition_to_dev(condition, &c))) return rc;
+        ARREAU_REQUIRE(arreau_condition_empty(&c), std::string(who) + ": multistep is not combined with a condition");
+        ARREAU_REQUIRE(!corrector || corrector->steps == 0, std::string(who) + ": multistep is not combined with corrector steps");
+        ARREAU_REQUIRE(!resampling || resampling->passes == 1, std::string(who) + ": multistep is not combined with resampling (passes > 1)");
+        ARREAU_REQUIRE(!symmetry, std::string(who) + ": multistep is not combined with space-group symmetry");
+        ARREAU_REQUIRE(!eta || *eta == 0.0f, std::string(who) + ": a multistep loop is the eta = 0 loop");
+        condition = nullptr; corrector = nullptr; resampling = nullptr;
+    }
+    const float e = multistep ? 0.0f : (eta ? *eta + 0.0f /* -0 -> +0 */ : -1.0f);
+    const SampleState st{d_frac, d_types, d_lengths, d_angles, d_off, B, N, d_const_types, d_fixed_lengths, d_lattice};
+    return sample_loop(who, m, st, t_start, n_steps, seed, d_workspace, workspace_bytes, use_graph, stream, condition, schedule, corrector,
+                       resampling, d_length_tie, symmetry, e, multistep, &sp);
 }
 
 // DDIM inversion (rules in include/arreau_hip.h): the sampling loop climbing the levels of an ascending table, every step the

@@ -113,6 +113,9 @@ struct SampleGraphKey {
     uint32_t eta_bits;         // their eta
     int32_t invert;            // DDIM inversion: 1 when the steps are inversion steps (arreau_invert_loop)
     arreau_multistep ms;       // second-order multistep: the four history pointers (all null: none)
+    int32_t species;           // species control: 1 when the steps take it
+    const uint32_t* species_allow;  // its admission rows (null: every class)
+    uint32_t species_tau_bits;      // its temperature
     bool operator==(const SampleGraphKey&) const = default;
 };
 
@@ -328,6 +331,7 @@ struct StepOptions {
     float eta = -1.0f;                    // DDIM-style step (ETA): the noise scale in [0, 1]; negative: the ancestral step.  Not with sym
     const arreau_multistep* ms = nullptr; // second-order multistep (MS): the history buffers; eta is then 0; a schedule and a tie only
     bool invert = false;                  // DDIM inversion (INVERT): `sched` names the HIGHER level every crystal climbs to; no other option
+    const arreau_species_control* species = nullptr;  // species control (SPEC): the admission rows and the temperature; not with invert
 };
 // DDIM-style sampling (arreau_sample_loop_eta, arreau_reverse_step_eta; the rules are stated in include/arreau_hip.h):
 // ARREAU_EINVAL unless eta is finite and lies in [0, 1].
@@ -335,6 +339,9 @@ int arreau_eta_check(float eta, const char* who);  // update.hip
 // Second-order multistep sampling (arreau_sample_loop_multistep, arreau_reverse_step_multistep): ARREAU_EINVAL unless the struct and
 // its four history pointers are given.
 int arreau_multistep_check(const arreau_multistep* ms, const char* who);  // update.hip
+// Species control (arreau_sample_loop_species, arreau_reverse_step_species): ARREAU_EINVAL unless the struct is given and its
+// temperature is finite and not negative; *out receives the struct the kernels take.
+int arreau_species_check(const arreau_species_control* species, const char* who, arreau_species_control* out);  // update.hip
 
 // One corrector move per crystal at timestep d_t[b]: z from the caller's d_z_frac [N,3], or (d_z_frac null) the Philox draw
 // (seed, t, ARREAU_DRAW_Z_CORRECTOR, element, iter; 256 pass[0] + iter with opt.pass).  Reads st.frac / offsets / B / N, opt.corr.snr,

@@ -122,7 +122,11 @@ __device__ __forceinline__ void reverse_lattice_body(int gt /* global thread of 
 // MS: second-order multistep sampling (arreau_sample_loop_multistep): an ETA instance, launched with eta = 0, whose position and
 // length moves extrapolate with the previous step's prediction kept in the history buffers `ms_arg` (update_dev.h; rules in
 // include/arreau_hip.h).  Only SCHED and TIE vary.  Without MS `ms_arg` is not read.
-template <bool COND, bool SCHED, bool RESAMPLE, bool TIE, bool SYM, bool ETA, bool INVERT = false, bool MS = false>
+// SPEC: species control (arreau_sample_loop_species): the species half of the atom part admits, per crystal, the classes of the
+// row spec_arg.d_allow[b] only and scales its Gumbel term by spec_arg.temperature (update_dev.h: d3pm_reverse_class<true>; rules
+// in include/arreau_hip.h).  Positions and lengths do not see it, so it goes with every instance but INVERT, which has no species
+// half.  Without SPEC `spec_arg` is not read.
+template <bool COND, bool SCHED, bool RESAMPLE, bool TIE, bool SYM, bool ETA, bool INVERT = false, bool MS = false, bool SPEC = false>
 __global__ __launch_bounds__(256) void reverse_kernel(
     int lat_blocks, float* __restrict__ lengths, const float* __restrict__ angles, const int32_t* __restrict__ tstep,
     const int32_t* __restrict__ offsets, const float* __restrict__ len0, StepNoiseSrc noise, const float* __restrict__ alpha_bars,
@@ -135,7 +139,7 @@ __global__ __launch_bounds__(256) void reverse_kernel(
     // sampling loop: the lattice part is one workgroup per crystal, which also prepares the next step (reverse_crystal_block)
     float* __restrict__ lattice_ws, float* __restrict__ cvec_next, const float* __restrict__ t_emb_w, const float* __restrict__ embT, int C,
     SampleConditionDev cond_arg, StepScheduleDev sched_arg, const int32_t* __restrict__ pass, const int32_t* __restrict__ length_tie,
-    arreau_symmetry sym_arg, float eta, arreau_multistep ms_arg) {
+    arreau_symmetry sym_arg, float eta, arreau_multistep ms_arg, arreau_species_control spec_arg) {
     const uint32_t word3 = RESAMPLE ? 256u * (uint32_t)pass[0] : 0u;  // the counter word of pass r
     const SampleConditionDev* cond = COND ? &cond_arg : nullptr;
     const StepScheduleDev* sched = SCHED ? &sched_arg : nullptr;
@@ -163,50 +167,54 @@ __global__ __launch_bounds__(256) void reverse_kernel(
     }
     if constexpr (MS) {
         static_assert(!COND && !RESAMPLE && !SYM && ETA && !INVERT, "the MS instances vary in SCHED and TIE only");
-        reverse_atoms_body<true, true>((int)blockIdx.x - lat_blocks, frac, types, tstep, offsets, B, N, eps, logits, noise, ve_sigmas, q1t, qmats,
-                                       S, T, const_types, absorbing, status, n0, batch, cond, sched, word3, eta, ms_arg);
+        reverse_atoms_body<true, true, SPEC>((int)blockIdx.x - lat_blocks, frac, types, tstep, offsets, B, N, eps, logits, noise, ve_sigmas, q1t,
+                                             qmats, S, T, const_types, absorbing, status, n0, batch, cond, sched, word3, eta, ms_arg, spec_arg);
     } else if constexpr (INVERT) {
-        static_assert(!COND && SCHED && !RESAMPLE && !TIE && !SYM && !ETA, "the INVERT instance takes a schedule and no other option");
+        static_assert(!COND && SCHED && !RESAMPLE && !TIE && !SYM && !ETA && !SPEC, "the INVERT instance takes a schedule and no other option");
         invert_atoms_body((int)blockIdx.x - lat_blocks, frac, tstep, offsets, B, N, eps, ve_sigmas, T, status, n0, batch, sched);
     } else if constexpr (SYM) {
         static_assert(!COND && !RESAMPLE && !ETA, "the SYM instances are unconditioned, not resampled and take no eta");
-        reverse_atoms_body_sym((int)blockIdx.x - lat_blocks, frac, types, tstep, offsets, B, N, eps, logits, noise, ve_sigmas, q1t, qmats, S,
-                               T, const_types, absorbing, status, n0, batch, sched, sym_arg);
+        reverse_atoms_body_sym<SPEC>((int)blockIdx.x - lat_blocks, frac, types, tstep, offsets, B, N, eps, logits, noise, ve_sigmas, q1t, qmats,
+                                     S, T, const_types, absorbing, status, n0, batch, sched, sym_arg, spec_arg);
     } else {
-        reverse_atoms_body<ETA>((int)blockIdx.x - lat_blocks, frac, types, tstep, offsets, B, N, eps, logits, noise, ve_sigmas, q1t, qmats, S, T,
-                                const_types, absorbing, status, n0, batch, cond, sched, word3, eta);
+        reverse_atoms_body<ETA, false, SPEC>((int)blockIdx.x - lat_blocks, frac, types, tstep, offsets, B, N, eps, logits, noise, ve_sigmas, q1t,
+                                             qmats, S, T, const_types, absorbing, status, n0, batch, cond, sched, word3, eta, {}, spec_arg);
     }
 }
 
 namespace {
 // the instance of one step: TIE and RESAMPLE from the options' pointers
-template <bool COND, bool SCHED, bool ETA>
+template <bool COND, bool SCHED, bool ETA, bool SPEC>
 auto reverse_kernel_of(const StepOptions& opt) {
-    return opt.length_tie ? (opt.pass ? reverse_kernel<COND, SCHED, true, true, false, ETA> : reverse_kernel<COND, SCHED, false, true, false, ETA>)
-                          : (opt.pass ? reverse_kernel<COND, SCHED, true, false, false, ETA> : reverse_kernel<COND, SCHED, false, false, false, ETA>);
+    return opt.length_tie ? (opt.pass ? reverse_kernel<COND, SCHED, true, true, false, ETA, false, false, SPEC>
+                                      : reverse_kernel<COND, SCHED, false, true, false, ETA, false, false, SPEC>)
+                          : (opt.pass ? reverse_kernel<COND, SCHED, true, false, false, ETA, false, false, SPEC>
+                                      : reverse_kernel<COND, SCHED, false, false, false, ETA, false, false, SPEC>);
 }
-template <bool COND, bool SCHED>
+// SPEC: species control; every instance below has its SPEC twin, the inversion step excepted
+template <bool COND, bool SCHED, bool SPEC>
 void enqueue_reverse_kernel(const arreau_model* m, int lat_blocks, int atom_blocks, const SampleState& st, const ReverseInputs& in,
                             const SampleConditionDev& cond, const StepScheduleDev& sched, const StepOptions& opt, hipStream_t s) {
-    auto kernel = opt.eta >= 0.0f ? reverse_kernel_of<COND, SCHED, true>(opt) : reverse_kernel_of<COND, SCHED, false>(opt);
-    if constexpr (!COND && SCHED) {
+    auto kernel = opt.eta >= 0.0f ? reverse_kernel_of<COND, SCHED, true, SPEC>(opt) : reverse_kernel_of<COND, SCHED, false, SPEC>(opt);
+    if constexpr (!COND && SCHED && !SPEC) {
         if (opt.invert) kernel = reverse_kernel<false, true, false, false, false, false, true>;
     }
     if constexpr (!COND) {
         if (opt.ms)
-            kernel = opt.length_tie ? reverse_kernel<false, SCHED, false, true, false, true, false, true>
-                                    : reverse_kernel<false, SCHED, false, false, false, true, false, true>;
+            kernel = opt.length_tie ? reverse_kernel<false, SCHED, false, true, false, true, false, true, SPEC>
+                                    : reverse_kernel<false, SCHED, false, false, false, true, false, true, SPEC>;
     }
     if constexpr (!COND) {
         if (opt.sym)
-            kernel = opt.length_tie ? reverse_kernel<false, SCHED, false, true, true, false> : reverse_kernel<false, SCHED, false, false, true, false>;
+            kernel = opt.length_tie ? reverse_kernel<false, SCHED, false, true, true, false, false, false, SPEC>
+                                    : reverse_kernel<false, SCHED, false, false, true, false, false, false, SPEC>;
     }
     ARREAU_LAUNCH(kernel, dim3(lat_blocks + atom_blocks), dim3(256), 0, s, lat_blocks, st.lengths, st.angles, in.t, st.offsets, in.len0, in.noise,
                   m->vp_alpha_bars, m->vp_betas, st.B, m->T, st.lattice, st.fixed_lengths, m->status, 0, in.gs_atoms,
                   in.gs_atoms ? const_cast<float*>(in.len0) : nullptr, st.frac, st.types, st.B, st.N, in.eps, in.logits, m->ve_sigmas, m->q1t,
                   m->qmats, m->S, st.const_types, m->qmats_absorbing, 0, in.batch, in.lattice_ws, in.cvec_next, m->t_emb_w, m->embT, m->C,
                   cond, sched, opt.pass, opt.length_tie, opt.sym ? *opt.sym : arreau_symmetry{}, opt.eta,
-                  opt.ms ? *opt.ms : arreau_multistep{});
+                  opt.ms ? *opt.ms : arreau_multistep{}, opt.species ? *opt.species : arreau_species_control{});
 }
 }  // namespace
 
@@ -230,11 +238,16 @@ int arreau_launch_reverse(const arreau_model* m, const SampleState& st, const Re
                    "reverse update: a multistep step is the eta = 0 step and takes a schedule and a tie only");
     ARREAU_REQUIRE(!opt.ms || (opt.ms->hist_eps && opt.ms->hist_x0 && opt.ms->hist_t_atom && opt.ms->hist_t_len),
                    "reverse update: a multistep history pointer is null");
+    ARREAU_REQUIRE(!opt.species || !opt.invert, "reverse update: an inversion step has no species half to control");
+    ARREAU_REQUIRE(!opt.species || (std::isfinite(opt.species->temperature) && opt.species->temperature >= 0.0f),
+                   "reverse update: the species temperature must be finite and not negative");
     if (lat_blocks + atom_blocks == 0) return ARREAU_OK;
     const SampleConditionDev c = conditioned ? *opt.cond : SampleConditionDev{};
     const StepScheduleDev sc = scheduled ? *opt.sched : StepScheduleDev{};
-    auto enqueue = conditioned ? (scheduled ? enqueue_reverse_kernel<true, true> : enqueue_reverse_kernel<true, false>)
-                               : (scheduled ? enqueue_reverse_kernel<false, true> : enqueue_reverse_kernel<false, false>);
+    auto enqueue = opt.species ? (conditioned ? (scheduled ? enqueue_reverse_kernel<true, true, true> : enqueue_reverse_kernel<true, false, true>)
+                                              : (scheduled ? enqueue_reverse_kernel<false, true, true> : enqueue_reverse_kernel<false, false, true>))
+                               : (conditioned ? (scheduled ? enqueue_reverse_kernel<true, true, false> : enqueue_reverse_kernel<true, false, false>)
+                                              : (scheduled ? enqueue_reverse_kernel<false, true, false> : enqueue_reverse_kernel<false, false, false>));
     enqueue(m, lat_blocks, atom_blocks, st, in, c, sc, opt, s);
     ARREAU_CHECK_HIP(hipGetLastError());
     return ARREAU_OK;
@@ -260,17 +273,21 @@ static int reverse_step_to(const arreau_model* m, float* d_frac, int32_t* d_type
                            const float* d_logits, const float* d_len0, const float* d_z_lattice, const float* d_z_frac,
                            const float* d_u_types, float* d_lattice, float lattice_clipmax, const int32_t* d_length_tie,
                            const arreau_symmetry* sym, void* stream, const char* who, float eta = -1.0f /* negative: none */,
-                           const arreau_multistep* ms = nullptr /* the multistep history (then eta = 0) */) {
-    // (at eta = 0 the draws of the lengths and positions are not read: their arrays may be null)
+                           const arreau_multistep* ms = nullptr /* the multistep history (then eta = 0) */,
+                           const arreau_species_control* species = nullptr /* species control (checked by the caller) */) {
+    // (at eta = 0 the draws of the lengths and positions are not read: their arrays may be null; so may the species' uniforms at a
+    // species temperature of 0)
     ARREAU_REQUIRE(m && d_frac && d_types && d_lengths && d_angles && d_t && d_s && d_off && d_eps && d_logits && d_len0 &&
-                       ((d_z_lattice && d_z_frac) || eta == 0.0f) && d_u_types && d_lattice, std::string(who) + ": null pointer");
+                       ((d_z_lattice && d_z_frac) || eta == 0.0f) && (d_u_types || (species && species->temperature == 0.0f)) && d_lattice,
+                   std::string(who) + ": null pointer");
     ARREAU_REQUIRE(B >= 1 && N >= 0, std::string(who) + ": bad size");
     ARREAU_REQUIRE(lattice_clipmax > 0.0f && lattice_clipmax <= 1.0f, std::string(who) + ": lattice_clipmax must lie in (0, 1]");
     const SampleState st{.frac = d_frac, .types = d_types, .lengths = d_lengths, .angles = d_angles, .offsets = d_off, .B = B, .N = N,
                          .lattice = d_lattice};
     const ReverseInputs in{d_t, d_eps, d_logits, d_len0, StepNoiseSrc{d_z_lattice, d_z_frac, d_u_types, 0}};
     const StepScheduleDev sched{nullptr, d_s, lattice_clipmax};
-    return arreau_launch_reverse(m, st, in, StepOptions{.sched = &sched, .length_tie = d_length_tie, .sym = sym, .eta = eta, .ms = ms},
+    return arreau_launch_reverse(m, st, in,
+                                 StepOptions{.sched = &sched, .length_tie = d_length_tie, .sym = sym, .eta = eta, .ms = ms, .species = species},
                                  (hipStream_t)stream);
 }
 
@@ -331,6 +348,39 @@ extern "C" int arreau_reverse_step_multistep(const arreau_model* m, float* d_fra
     return reverse_step_to(m, d_frac, d_types, d_lengths, d_angles, d_t, d_s, d_off, B, N, d_eps, d_logits, d_len0, d_z_lattice, d_z_frac,
                            d_u_types, d_lattice, lattice_clipmax, d_length_tie, /*sym=*/nullptr, stream, "arreau_reverse_step_multistep",
                            0.0f, multistep);
+}
+
+// Species control: a temperature that is finite and not negative, or ARREAU_EINVAL; *out the struct the kernels take (-0 -> +0).
+int arreau_species_check(const arreau_species_control* species, const char* who, arreau_species_control* out) {
+    ARREAU_REQUIRE(species != nullptr, std::string(who) + ": null species control");
+    ARREAU_REQUIRE(std::isfinite(species->temperature) && species->temperature >= 0.0f,
+                   std::string(who) + ": the species temperature must be finite and not negative");
+    *out = arreau_species_control{species->d_allow, species->temperature + 0.0f};
+    return ARREAU_OK;
+}
+
+// The step of whichever of arreau_reverse_step_to / _tied / _sym / _eta / _multistep the options name, under species control (rules in
+// include/arreau_hip.h).  What those do not combine is rejected as there (arreau_launch_reverse).
+extern "C" int arreau_reverse_step_species(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths,
+                                           const float* d_angles, const int32_t* d_t, const int32_t* d_s, const int32_t* d_off, int32_t B,
+                                           int32_t N, const float* d_eps, const float* d_logits, const float* d_len0,
+                                           const float* d_z_lattice, const float* d_z_frac, const float* d_u_types, float* d_lattice,
+                                           float lattice_clipmax, const int32_t* d_length_tie, const arreau_symmetry* symmetry,
+                                           const float* eta, const arreau_multistep* multistep, const arreau_species_control* species,
+                                           void* stream) {
+    const char* who = "arreau_reverse_step_species";
+    int rc;
+    arreau_species_control sp;
+    if ((rc = arreau_species_check(species, who, &sp))) return rc;
+    if (eta && (rc = arreau_eta_check(*eta, who))) return rc;
+    if (symmetry && (rc = arreau_symmetry_check(symmetry, who))) return rc;
+    if (multistep) {
+        if ((rc = arreau_multistep_check(multistep, who))) return rc;
+        ARREAU_REQUIRE(!eta || *eta == 0.0f, std::string(who) + ": a multistep step is the eta = 0 step");
+    }
+    const float e = multistep ? 0.0f : (eta ? *eta + 0.0f /* -0 -> +0 */ : -1.0f);
+    return reverse_step_to(m, d_frac, d_types, d_lengths, d_angles, d_t, d_s, d_off, B, N, d_eps, d_logits, d_len0, d_z_lattice, d_z_frac,
+                           d_u_types, d_lattice, lattice_clipmax, d_length_tie, symmetry, stream, who, e, multistep, &sp);
 }
 
 // DDIM inversion: one step from level d_s[b] up to level d_t[b] on the caller's network outputs (rules in include/arreau_hip.h).

@@ -277,11 +277,188 @@ __device__ __forceinline__ float tied_length_component(int b, int i, int code, c
     return mylen;
 }
 
+// Species control (arreau_sample_loop_species / arreau_reverse_step_species; the rules are stated in include/arreau_hip.h): whether
+// the classes `lane` and `lane + 64` of crystal b are admitted by the step that leaves t.  The crystal's row of four words is
+// wave-uniform (a null table admits every class); an ordinary class is admitted by its bit, the mask class S - 1 by its bit or,
+// above t = 1, always.
+__device__ __forceinline__ void species_admitted(const arreau_species_control& sp, int b, int lane, int S, int t, bool& a0, bool& a1) {
+    uint32_t w0 = ~0u, w1 = ~0u, w2 = ~0u, w3 = ~0u;
+    if (sp.d_allow != nullptr) {  // (kernel argument: uniform)
+        const uint32_t* __restrict__ row = sp.d_allow + 4 * (size_t)b;
+        w0 = row[0]; w1 = row[1]; w2 = row[2]; w3 = row[3];
+    }
+    const bool bit0 = (((lane < 32 ? w0 : w1) >> (lane & 31)) & 1u) != 0u;  // class lane: word lane >> 5
+    const bool bit1 = (((lane < 32 ? w2 : w3) >> (lane & 31)) & 1u) != 0u;  // class lane + 64: word 2 + (lane >> 5)
+    const int mask = S - 1;
+    a0 = lane < S && (bit0 || (lane == mask && t > 1));
+    a1 = lane + 64 < S && (bit1 || (lane + 64 == mask && t > 1));
+}
+
+// Space-group symmetry: D3PM.reverse on the class of atom i (d3pm.py:74-110, 198-215) from given x0 logits l0 / l1 of classes
+// lane / lane + 64 (-inf beyond S), from timestep t to s_to: the new class (wave-uniform), drawn with atom i's uniforms (elements
+// i S + s).  The arithmetic of reverse_one_atom's species half, operation for operation; it is kept apart so that the existing
+// kernel instances keep their instructions.
+// SPEC: species control -- the one place its rules are written, for a single atom (reverse_one_atom's SPEC instances) and for an
+// orbit alike: the x0 logits and the posterior logits of a class outside the admitted set of crystal b become -inf, the Gumbel
+// term is scaled by sp.temperature (0: no uniform is read or generated), and the arg-max runs over the admitted classes.  Without
+// SPEC none of this is compiled: a0 / a1 are v0 / v1 and `b` and `sp` are not read.
+template <bool SPEC = false>
+__device__ __forceinline__ int d3pm_reverse_class(int i, int lane, float l0, float l1, int t, int s_to, const int32_t* __restrict__ types,
+                                                  StepNoiseSrc noise, const float* __restrict__ q1t, const float* __restrict__ qmats, int S,
+                                                  int absorbing, int32_t* __restrict__ status, const StepScheduleDev* sched, uint32_t word3,
+                                                  int b = 0 /* SPEC only */, const arreau_species_control& sp = {} /* SPEC only */) {
+    const float* __restrict__ u_types = noise.u_types;
+    // ---- D3PM posterior logits ------------------------------------------------------------------
+    const int s0 = lane, s1 = lane + 64;
+    const bool v0 = s0 < S, v1 = s1 < S;
+    bool a0 = v0, a1 = v1;
+    if constexpr (SPEC) {
+        species_admitted(sp, b, lane, S, t, a0, a1);
+        l0 = a0 ? l0 : -INFINITY;  // rule 1: the softmax gives an excluded class an exact 0
+        l1 = a1 ? l1 : -INFINITY;
+    }
+    float post0, post1;
+    if (t == 1) {
+        post0 = l0; post1 = l1;  // raw x0 logits at the last step (d3pm.py:106-108)
+    } else {
+        float mx = fmaxf(l0, l1);
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+        const float e0 = a0 ? expf(l0 - mx) : 0.f, e1 = a1 ? expf(l1 - mx) : 0.f;  // (a0 / a1: v0 / v1 without SPEC)
+        float sum = e0 + e1;
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off, 64);
+        const float p0 = e0 / sum, p1 = e1 / sum;  // softmax of the x0 logits; lane holds classes s0, s1
+        int xt = types[i];
+        if ((xt < 0 || xt >= S) && lane == 0) atomicOr(status, ARREAU_STATUS_BAD_TYPE);  // clamped, but flagged
+        xt = xt < 0 ? 0 : (xt >= S ? S - 1 : xt);
+        const bool unit = sched == nullptr || s_to == t - 1;
+        const float* q1row = q1t + ((size_t)(t - 1) * S + xt) * S;  // fact1 = Q_t^T[x_t, :] (stride 1)
+        const float* qm = qmats + (size_t)(s_to - 1) * S * S;  // Qbar_s (reference index t-2 at stride 1)
+        float f2a = 0.f, f2b = 0.f;
+        if (absorbing) {
+            // Absorbing ("mask") chain: Qbar_t is diagonal plus the mask column (checked on the host for every t at model
+            // creation).  The dense loop below adds exact zeros everywhere else, so these are bit for bit its sums: for an
+            // ordinary class s only the term c = s, for the mask class the whole column in class order -- without the
+            // S x S read per atom.
+            const int mask = S - 1;
+            const float d0 = v0 ? qm[(size_t)s0 * S + s0] : 0.f, d1 = v1 ? qm[(size_t)s1 * S + s1] : 0.f;
+            const float c0 = v0 ? qm[(size_t)s0 * S + mask] : 0.f, c1 = v1 ? qm[(size_t)s1 * S + mask] : 0.f;
+            f2a = fmaf(p0, d0, 0.f);
+            f2b = fmaf(p1, d1, 0.f);
+            float fm = 0.f;
+            // (c is wave-uniform: the broadcasts are v_readlane, not LDS-crossbar permutes -- round 3: the 2 S permutes per atom
+            // were most of this kernel's time)
+            auto lane_value = [](float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); };
+            for (int c = 0; c < S; ++c) {
+                const float pc = c < 64 ? lane_value(p0, c) : lane_value(p1, c - 64);
+                const float qc = c < 64 ? lane_value(c0, c) : lane_value(c1, c - 64);
+                fm = fmaf(pc, qc, fm);
+            }
+            if (s0 == mask) f2a = fm;
+            if (s1 == mask) f2b = fm;
+        } else
+        // fact2 = softmax . Qbar: rows of Qbar are fetched 16 at a time (independent loads in flight), then the
+        // softmax entries are broadcast from the lanes that hold them
+        for (int c0 = 0; c0 < S; c0 += 16) {
+            float qa[16], qb[16];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int c = min(c0 + i, S - 1);
+                qa[i] = v0 ? qm[(size_t)c * S + s0] : 0.f;
+                qb[i] = v1 ? qm[(size_t)c * S + s1] : 0.f;
+            }
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const int c = c0 + i;  // wave-uniform
+                float sc = c < 64 ? __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p0), c))
+                                  : __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p1), c - 64));
+                sc = c < S ? sc : 0.f;
+                f2a = fmaf(sc, qa[i], f2a);
+                f2b = fmaf(sc, qb[i], f2b);
+            }
+        }
+        if (unit) {
+            post0 = v0 ? logf(q1row[s0] + D3PM_EPS) + logf(f2a + D3PM_EPS) : -INFINITY;
+            post1 = v1 ? logf(q1row[s1] + D3PM_EPS) + logf(f2b + D3PM_EPS) : -INFINITY;
+        } else {
+            // respaced: fact1 = Qbar_{t-s}[:, x_t], the column x_t of q_mats[t-s-1] (the mask chain is time-homogeneous, so the
+            // (t-s)-step transition is the (t-s)-step product).  Absorbing chain: that column is zero off the diagonal unless
+            // x_t is the mask class -- the entries skipped are exact zeros, as in the shortcut above.
+            const float* qcol = qmats + (size_t)(t - s_to - 1) * S * S + xt;
+            const bool all = !absorbing || xt == S - 1;
+            const float fa = (v0 && (all || s0 == xt)) ? qcol[(size_t)s0 * S] : 0.f;
+            const float fb = (v1 && (all || s1 == xt)) ? qcol[(size_t)s1 * S] : 0.f;
+            post0 = v0 ? logf(fa + D3PM_EPS) + logf(f2a + D3PM_EPS) : -INFINITY;
+            post1 = v1 ? logf(fb + D3PM_EPS) + logf(f2b + D3PM_EPS) : -INFINITY;
+        }
+    }
+    if constexpr (SPEC) {  // rule 3: without it an excluded class keeps 2 log(1e-6) and can win a draw
+        post0 = a0 ? post0 : -INFINITY;
+        post1 = a1 ? post1 : -INFINITY;
+    }
+    // ---- Gumbel arg-max (d3pm.py:206-214) ----------------------------------------------------------
+    const float scale = (t != 1) ? 1.0f : 0.2f;
+    // (the array-or-generator choice is made on the kernel argument itself -- a scalar compare -- not on a per-lane pointer:
+    // no per-lane 64-bit integer compares on this path, DESIGN.md section 8)
+    const bool have_u = u_types != nullptr;
+    const float* un = u_types + (have_u ? (size_t)i * S : 0);
+    auto draw_u = [&](int s_) {
+        return have_u ? un[s_] : philox_uniform(noise.seed, (uint32_t)t, ARREAU_DRAW_U_TYPES, (uint32_t)((size_t)i * S + s_), word3);
+    };
+    float best = -INFINITY;
+    int besti = 0x7fffffff;
+    if constexpr (SPEC) {
+        // rules 4-5: value = post + (tau scale) g over the admitted classes; only a value above -inf competes (a NaN does not)
+        const float ts = sp.temperature * scale;
+        float val0 = post0, val1 = post1;
+        if (sp.temperature > 0.0f) {  // (kernel argument: uniform; at 0 the uniforms are not touched and u_types may be null)
+            if (a0) {
+                const float u = fminf(fmaxf(draw_u(s0), D3PM_EPS), 1.0f);
+                val0 = post0 + (-logf(-logf(u))) * ts;
+            }
+            if (a1) {
+                const float u = fminf(fmaxf(draw_u(s1), D3PM_EPS), 1.0f);
+                val1 = post1 + (-logf(-logf(u))) * ts;
+            }
+        }
+        if (a0 && val0 > -INFINITY) { best = val0; besti = s0; }
+        if (a1 && val1 > best) { best = val1; besti = s1; }
+    } else {
+        if (v0) {
+            const float u = fminf(fmaxf(draw_u(s0), D3PM_EPS), 1.0f);
+            best = post0 + (-logf(-logf(u))) * scale;
+            besti = s0;
+        }
+        if (v1) {
+            const float u = fminf(fmaxf(draw_u(s1), D3PM_EPS), 1.0f);
+            const float val = post1 + (-logf(-logf(u))) * scale;
+            if (val > best) { best = val; besti = s1; }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const float ob = __shfl_xor(best, off, 64);
+        const int oi = __shfl_xor(besti, off, 64);
+        if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }  // first index wins ties
+    }
+    if constexpr (SPEC) {
+        if (besti == 0x7fffffff) {  // (wave-uniform) no admitted value above -inf: the lowest admitted class
+            const unsigned long long m0 = __ballot(a0), m1 = __ballot(a1);
+            // (a row that admits nothing at t = 1 is rejected by the caller; the mask class keeps the index in range)
+            besti = m0 ? __builtin_ctzll(m0) : (m1 ? 64 + __builtin_ctzll(m1) : S - 1);
+        }
+    }
+    return besti;
+}
+
 // One wave per atom: VE_pbc.reverse on the fractional coordinates (diffusion_helpers.py:65-81) and
 // D3PM.reverse on the atom type (d3pm.py:74-110, 198-215), from timestep t to s (t - 1 without a schedule).  Lanes span the S
 // classes (2 per lane).  ETA: the position update is the eta move (rules in include/arreau_hip.h); the species half is unchanged.
 // MS (with ETA, eta = 0): the multistep position move on the history `ms`; lane 0 reads and then overwrites the atom's level.
-template <bool ETA = false, bool MS = false>
+// SPEC: species control -- the species half is d3pm_reverse_class<true> on the atom's own logits and its crystal's row; the
+// position half is unchanged.  The other instances do not see that call.
+template <bool ETA = false, bool MS = false, bool SPEC = false>
 __device__ __forceinline__ void reverse_one_atom(
     int i /* atom (wave-uniform) */, int lane, float* __restrict__ frac, int32_t* __restrict__ types, const int32_t* __restrict__ tstep,
     const int32_t* __restrict__ offsets, int B, const float* __restrict__ eps,
@@ -291,7 +468,7 @@ __device__ __forceinline__ void reverse_one_atom(
     const int32_t* __restrict__ batch /* crystal of each atom, or null: searched in `offsets` */,
     const SampleConditionDev* cond /* conditioned sampling, or null */, const StepScheduleDev* sched /* respaced, or null */,
     uint32_t word3 /* resampled loop: 256 r in pass r; else 0 */, float eta = 0.0f /* ETA only */,
-    const arreau_multistep& ms = {} /* MS only */) {
+    const arreau_multistep& ms = {} /* MS only */, const arreau_species_control& sp = {} /* SPEC only */) {
     static_assert(!MS || ETA, "the MS instances are ETA instances (at eta = 0)");
     const float* __restrict__ z_frac = noise.z_frac;
     const float* __restrict__ u_types = noise.u_types;
@@ -358,6 +535,12 @@ __device__ __forceinline__ void reverse_one_atom(
     const bool v0 = s0 < S, v1 = s1 < S;
     const float* lg = logits + (size_t)i * S;
     const float l0 = v0 ? lg[s0] : -INFINITY, l1 = v1 ? lg[s1] : -INFINITY;
+    if constexpr (SPEC) {
+        const int cls = d3pm_reverse_class<true>(i, lane, l0, l1, t, s_to, types, noise, q1t, qmats, S, absorbing, status, sched, word3, lo, sp);
+        // rule 6: held species are imposed after the draw, as below
+        if (lane == 0) types[i] = (cond && cond->type_mask && cond->type_mask[i]) ? cond->a0[i] : (const_types ? const_types[i] : cls);
+        return;
+    }
     float post0, post1;
     if (t == 1) {
         post0 = l0; post1 = l1;  // raw x0 logits at the last step (d3pm.py:106-108)
@@ -466,125 +649,8 @@ __device__ __forceinline__ void reverse_one_atom(
     if (lane == 0) types[i] = (cond && cond->type_mask && cond->type_mask[i]) ? cond->a0[i] : (const_types ? const_types[i] : besti);
 }
 
-// Space-group symmetry: D3PM.reverse on the class of atom i (d3pm.py:74-110, 198-215) from given x0 logits l0 / l1 of classes
-// lane / lane + 64 (-inf beyond S), from timestep t to s_to: the new class (wave-uniform), drawn with atom i's uniforms (elements
-// i S + s).  The arithmetic of reverse_one_atom's species half, operation for operation; it is kept apart so that the existing
-// kernel instances keep their instructions.
-__device__ __forceinline__ int d3pm_reverse_class(int i, int lane, float l0, float l1, int t, int s_to, const int32_t* __restrict__ types,
-                                                  StepNoiseSrc noise, const float* __restrict__ q1t, const float* __restrict__ qmats, int S,
-                                                  int absorbing, int32_t* __restrict__ status, const StepScheduleDev* sched, uint32_t word3) {
-    const float* __restrict__ u_types = noise.u_types;
-    // ---- D3PM posterior logits ------------------------------------------------------------------
-    const int s0 = lane, s1 = lane + 64;
-    const bool v0 = s0 < S, v1 = s1 < S;
-    float post0, post1;
-    if (t == 1) {
-        post0 = l0; post1 = l1;  // raw x0 logits at the last step (d3pm.py:106-108)
-    } else {
-        float mx = fmaxf(l0, l1);
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-        const float e0 = v0 ? expf(l0 - mx) : 0.f, e1 = v1 ? expf(l1 - mx) : 0.f;
-        float sum = e0 + e1;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off, 64);
-        const float p0 = e0 / sum, p1 = e1 / sum;  // softmax of the x0 logits; lane holds classes s0, s1
-        int xt = types[i];
-        if ((xt < 0 || xt >= S) && lane == 0) atomicOr(status, ARREAU_STATUS_BAD_TYPE);  // clamped, but flagged
-        xt = xt < 0 ? 0 : (xt >= S ? S - 1 : xt);
-        const bool unit = sched == nullptr || s_to == t - 1;
-        const float* q1row = q1t + ((size_t)(t - 1) * S + xt) * S;  // fact1 = Q_t^T[x_t, :] (stride 1)
-        const float* qm = qmats + (size_t)(s_to - 1) * S * S;  // Qbar_s (reference index t-2 at stride 1)
-        float f2a = 0.f, f2b = 0.f;
-        if (absorbing) {
-            // Absorbing ("mask") chain: Qbar_t is diagonal plus the mask column (checked on the host for every t at model
-            // creation).  The dense loop below adds exact zeros everywhere else, so these are bit for bit its sums: for an
-            // ordinary class s only the term c = s, for the mask class the whole column in class order -- without the
-            // S x S read per atom.
-            const int mask = S - 1;
-            const float d0 = v0 ? qm[(size_t)s0 * S + s0] : 0.f, d1 = v1 ? qm[(size_t)s1 * S + s1] : 0.f;
-            const float c0 = v0 ? qm[(size_t)s0 * S + mask] : 0.f, c1 = v1 ? qm[(size_t)s1 * S + mask] : 0.f;
-            f2a = fmaf(p0, d0, 0.f);
-            f2b = fmaf(p1, d1, 0.f);
-            float fm = 0.f;
-            // (c is wave-uniform: the broadcasts are v_readlane, not LDS-crossbar permutes -- round 3: the 2 S permutes per atom
-            // were most of this kernel's time)
-            auto lane_value = [](float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); };
-            for (int c = 0; c < S; ++c) {
-                const float pc = c < 64 ? lane_value(p0, c) : lane_value(p1, c - 64);
-                const float qc = c < 64 ? lane_value(c0, c) : lane_value(c1, c - 64);
-                fm = fmaf(pc, qc, fm);
-            }
-            if (s0 == mask) f2a = fm;
-            if (s1 == mask) f2b = fm;
-        } else
-        // fact2 = softmax . Qbar: rows of Qbar are fetched 16 at a time (independent loads in flight), then the
-        // softmax entries are broadcast from the lanes that hold them
-        for (int c0 = 0; c0 < S; c0 += 16) {
-            float qa[16], qb[16];
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int c = min(c0 + i, S - 1);
-                qa[i] = v0 ? qm[(size_t)c * S + s0] : 0.f;
-                qb[i] = v1 ? qm[(size_t)c * S + s1] : 0.f;
-            }
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int c = c0 + i;  // wave-uniform
-                float sc = c < 64 ? __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p0), c))
-                                  : __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p1), c - 64));
-                sc = c < S ? sc : 0.f;
-                f2a = fmaf(sc, qa[i], f2a);
-                f2b = fmaf(sc, qb[i], f2b);
-            }
-        }
-        if (unit) {
-            post0 = v0 ? logf(q1row[s0] + D3PM_EPS) + logf(f2a + D3PM_EPS) : -INFINITY;
-            post1 = v1 ? logf(q1row[s1] + D3PM_EPS) + logf(f2b + D3PM_EPS) : -INFINITY;
-        } else {
-            // respaced: fact1 = Qbar_{t-s}[:, x_t], the column x_t of q_mats[t-s-1] (the mask chain is time-homogeneous, so the
-            // (t-s)-step transition is the (t-s)-step product).  Absorbing chain: that column is zero off the diagonal unless
-            // x_t is the mask class -- the entries skipped are exact zeros, as in the shortcut above.
-            const float* qcol = qmats + (size_t)(t - s_to - 1) * S * S + xt;
-            const bool all = !absorbing || xt == S - 1;
-            const float fa = (v0 && (all || s0 == xt)) ? qcol[(size_t)s0 * S] : 0.f;
-            const float fb = (v1 && (all || s1 == xt)) ? qcol[(size_t)s1 * S] : 0.f;
-            post0 = v0 ? logf(fa + D3PM_EPS) + logf(f2a + D3PM_EPS) : -INFINITY;
-            post1 = v1 ? logf(fb + D3PM_EPS) + logf(f2b + D3PM_EPS) : -INFINITY;
-        }
-    }
-    // ---- Gumbel arg-max (d3pm.py:206-214) ----------------------------------------------------------
-    const float scale = (t != 1) ? 1.0f : 0.2f;
-    // (the array-or-generator choice is made on the kernel argument itself -- a scalar compare -- not on a per-lane pointer:
-    // no per-lane 64-bit integer compares on this path, DESIGN.md section 8)
-    const bool have_u = u_types != nullptr;
-    const float* un = u_types + (have_u ? (size_t)i * S : 0);
-    auto draw_u = [&](int s_) {
-        return have_u ? un[s_] : philox_uniform(noise.seed, (uint32_t)t, ARREAU_DRAW_U_TYPES, (uint32_t)((size_t)i * S + s_), word3);
-    };
-    float best = -INFINITY;
-    int besti = 0x7fffffff;
-    if (v0) {
-        const float u = fminf(fmaxf(draw_u(s0), D3PM_EPS), 1.0f);
-        best = post0 + (-logf(-logf(u))) * scale;
-        besti = s0;
-    }
-    if (v1) {
-        const float u = fminf(fmaxf(draw_u(s1), D3PM_EPS), 1.0f);
-        const float val = post1 + (-logf(-logf(u))) * scale;
-        if (val > best) { best = val; besti = s1; }
-    }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const float ob = __shfl_xor(best, off, 64);
-        const int oi = __shfl_xor(besti, off, 64);
-        if (ob > best || (ob == best && oi < besti)) { best = ob; besti = oi; }  // first index wins ties
-    }
-    return besti;
-}
-
 // the form the stand-alone kernel uses: workgroup `blk` of four waves, one atom each
-template <bool ETA, bool MS = false>
+template <bool ETA, bool MS = false, bool SPEC = false>
 __device__ __forceinline__ void reverse_atoms_body(
     int blk /* block of the atom part */, float* __restrict__ frac, int32_t* __restrict__ types, const int32_t* __restrict__ tstep,
     const int32_t* __restrict__ offsets, int B, int N, const float* __restrict__ eps,
@@ -592,11 +658,11 @@ __device__ __forceinline__ void reverse_atoms_body(
     const float* __restrict__ ve_sigmas, const float* __restrict__ q1t, const float* __restrict__ qmats, int S,
     int T, const int32_t* __restrict__ const_types, int absorbing, int32_t* __restrict__ status, int n0,
     const int32_t* __restrict__ batch, const SampleConditionDev* cond, const StepScheduleDev* sched, uint32_t word3, float eta,
-    const arreau_multistep& ms = {} /* MS only */) {
+    const arreau_multistep& ms = {} /* MS only */, const arreau_species_control& sp = {} /* SPEC only */) {
     const int i = n0 + blk * 4 + (int)(threadIdx.x >> 6);  // atoms n0 .. N-1
     if (i >= N) return;  // wave-uniform; no block-level barrier below
-    reverse_one_atom<ETA, MS>(i, threadIdx.x & 63, frac, types, tstep, offsets, B, eps, logits, noise, ve_sigmas, q1t, qmats, S, T, const_types,
-                              absorbing, status, batch, cond, sched, word3, eta, ms);
+    reverse_one_atom<ETA, MS, SPEC>(i, threadIdx.x & 63, frac, types, tstep, offsets, B, eps, logits, noise, ve_sigmas, q1t, qmats, S, T,
+                                    const_types, absorbing, status, batch, cond, sched, word3, eta, ms, sp);
 }
 
 // ---- space-group symmetry (arreau_sample_loop_sym / arreau_reverse_step_sym; rules in include/arreau_hip.h) -----------------
@@ -650,11 +716,15 @@ __device__ __forceinline__ float sym_lane_value(float v, int l) { return __int_a
 
 // The SYM form of reverse_atoms_body: one wave per atom.  An unconstrained atom (leader -1) runs reverse_one_atom as the plain
 // kernel does; a member leaves (its leader's wave writes it); a leader updates its whole orbit (rules 1-5).
+// SPEC: species control -- the orbit's one class is drawn by d3pm_reverse_class<true> on the orbit's mean logits, the leader's
+// draw and its crystal's row; an unconstrained atom runs reverse_one_atom's SPEC instance.
+template <bool SPEC = false>
 __device__ __forceinline__ void reverse_atoms_body_sym(
     int blk, float* __restrict__ frac, int32_t* __restrict__ types, const int32_t* __restrict__ tstep, const int32_t* __restrict__ offsets,
     int B, int N, const float* __restrict__ eps, const float* __restrict__ logits, StepNoiseSrc noise, const float* __restrict__ ve_sigmas,
     const float* __restrict__ q1t, const float* __restrict__ qmats, int S, int T, const int32_t* __restrict__ const_types, int absorbing,
-    int32_t* __restrict__ status, int n0, const int32_t* __restrict__ batch, const StepScheduleDev* sched, const arreau_symmetry& sy) {
+    int32_t* __restrict__ status, int n0, const int32_t* __restrict__ batch, const StepScheduleDev* sched, const arreau_symmetry& sy,
+    const arreau_species_control& sp = {} /* SPEC only */) {
     const int i = n0 + blk * 4 + (int)(threadIdx.x >> 6);
     if (i >= N) return;  // wave-uniform; no block-level barrier below
     const int lane = threadIdx.x & 63;
@@ -673,8 +743,12 @@ __device__ __forceinline__ void reverse_atoms_body_sym(
         if (!orbit_ok && lane == 0) atomicOr(status, ARREAU_STATUS_BAD_SYMMETRY);
     }
     if (!orbit_ok) {  // rule 7: unconstrained (or a rejected orbit's leader alone)
-        reverse_one_atom(i, lane, frac, types, tstep, offsets, B, eps, logits, noise, ve_sigmas, q1t, qmats, S, T, const_types, absorbing,
-                         status, batch, nullptr, sched, 0u);
+        if constexpr (SPEC)
+            reverse_one_atom<false, false, true>(i, lane, frac, types, tstep, offsets, B, eps, logits, noise, ve_sigmas, q1t, qmats, S, T,
+                                                 const_types, absorbing, status, batch, nullptr, sched, 0u, 0.0f, {}, sp);
+        else
+            reverse_one_atom(i, lane, frac, types, tstep, offsets, B, eps, logits, noise, ve_sigmas, q1t, qmats, S, T, const_types, absorbing,
+                             status, batch, nullptr, sched, 0u);
         return;
     }
     int t = tstep[b];
@@ -733,7 +807,7 @@ __device__ __forceinline__ void reverse_atoms_body_sym(
     }
     l0 = v0 ? l0 * inv_o : -INFINITY;
     l1 = v1 ? l1 * inv_o : -INFINITY;
-    const int cls = d3pm_reverse_class(i, lane, l0, l1, t, s_to, types, noise, q1t, qmats, S, absorbing, status, sched, 0u);
+    const int cls = d3pm_reverse_class<SPEC>(i, lane, l0, l1, t, s_to, types, noise, q1t, qmats, S, absorbing, status, sched, 0u, b, sp);
     const int newt = const_types ? const_types[i] : cls;
     // rule 4 and the members' species: lanes over the members
     for (int a = a0 + lane; a < a1; a += 64) {

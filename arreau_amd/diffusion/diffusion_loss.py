@@ -18,6 +18,7 @@ from . import multistep as multistep_mod
 from . import resampling as rs
 from . import respacing
 from . import screening
+from . import species as species_mod
 from . import uniqueness as uniqueness_mod
 from . import cell_reduction
 from . import symmetry_search
@@ -349,7 +350,7 @@ class DiffusionLoss(nn.Module):
                corrector_snr: float = pc.DEFAULT_SNR, resample_passes: int = 1, jump_length: int = 10,
                lattice_system=None, symmetry=None, screen=None, unique=None, find_symmetry=None, reduce_cell=None,
                symmetrize=None, match_to=None, eta: Optional[float] = None, initial_state=None,
-               multistep: bool = False) -> SampleResult:
+               multistep: bool = False, elements=None, species_temperature: float = 1.0) -> SampleResult:
         """diffusion_loss.py:276-377.  The initial state is drawn on the host exactly like the reference (numpy
         uniforms for the angles, then randn lengths, randn fractional coordinates from torch's global CPU generator):
         draw_initial_state, which a caller may also use on its own.
@@ -417,7 +418,7 @@ class DiffusionLoss(nn.Module):
         arreau_reverse_step_eta): 1 is the ancestral step (up to rounding, and to the clip of the lengths' beta), 0 injects none,
         so positions and lengths become a function of the initial state alone, whatever the seed.  The species keep the D3PM
         step with its Gumbel draw: they are deterministic only where they are held (constant_atoms, a condition's known
-        species).  The draws keep their keys; at eta = 0 those of positions and lengths are not read (the host-noise modes
+        species) or with species_temperature=0, which removes the draw.  The draws keep their keys; at eta = 0 those of positions and lengths are not read (the host-noise modes
         still draw them, so their generators advance as always).  Works with schedules, conditions, corrector steps, resampling
         (its jumps are unchanged), fixed cells, lattice systems, graph replay and frames; with `symmetry` it is rejected.  None
         is the sampler as it was, bit for bit.  No sample-quality claim is made.
@@ -437,11 +438,24 @@ class DiffusionLoss(nn.Module):
         rules in include/arreau_hip.h; arreau_sample_loop_multistep / arreau_reverse_step_multistep) -- the deterministic eta = 0
         step of positions and lengths, extrapolated with the previous step's prediction (in log sigma and in log-SNR time), at the
         same one network evaluation per step; a move whose step-size ratio leaves [1/3, 3], the first move and the last are first
-        order.  The species keep the D3PM step with its draw.  The history lives in four device buffers this call allocates and
+        order.  The species keep the D3PM step with its draw (species_temperature=0 removes it).  The history lives in four device buffers this call allocates and
         holds through segments (frames) and a re-run.  Works with schedules, lattice systems, fixed cells, constant_atoms,
         initial_state, max_steps, frames, graph replay and the instruments; rejected before any work with `condition`, corrector
         steps, resampling passes > 1, `symmetry` and an eta other than None or 0.  False is the sampler as it was, bit for bit.
         No sample-quality claim is made.
+        `elements`, `species_temperature` (extension, every noise mode): species control (species.py; rules in
+        include/arreau_hip.h; arreau_sample_loop_species / arreau_reverse_step_species).  `elements` restricts the classes the D3PM
+        species step may choose: one collection of element symbols and / or atomic numbers for the whole batch, or a list with one
+        entry per crystal, an entry being such a collection or None (unrestricted).  A restricted crystal ends with elements of its
+        set only and never with the mask state; an excluded class has probability exactly 0 in every step.
+        `species_temperature` >= 0 scales the Gumbel term of the species draw: 1 is the step as it is, 0 takes the arg-max of the
+        posterior and draws nothing, so sample(eta=0, species_temperature=0) and multistep runs are functions of the initial state
+        in positions, lengths and species.  Both combine with every option above, space-group symmetry included (an orbit draws
+        one admitted class).  Rejected before any work: an unknown symbol, an element the table does not hold, an empty set, a list
+        of the wrong length, a temperature that is negative or not finite, a held species (constant_atoms, a condition's known
+        species) outside its crystal's set.  A given initial_state whose species lie outside is accepted: every sampled atom
+        leaves its first step inside.  None and 1.0 are the sampler as it was, bit for bit, through the exports it used.  No
+        sample-quality claim is made.
         `screen` (extension, every noise mode and option): a screening.ScreenCriteria, or True for its defaults -- the final
         device state is screened in one launch before it is copied back (arreau_crystal_screen; rules in include/arreau_hip.h):
         shortest contact over all periodic images, cell volume, number density, mask state.  SampleResult.metrics then holds the
@@ -506,6 +520,7 @@ class DiffusionLoss(nn.Module):
         eta = ddim.check_eta(eta) if eta is not None else None
         multistep = multistep_mod.check_multistep(multistep, eta=eta, condition=condition, corrector_steps=corrector_steps,
                                                   resample_passes=resample_passes, symmetry=symmetry)
+        species_temperature = species_mod.validate_temperature(species_temperature)
         if resample_passes > 1 and visualization_setting in (VisualizationSetting.ALL, VisualizationSetting.ALL_DETAILED):
             raise ValueError("resampling (resample_passes > 1) takes visualization_setting NONE or LAST: a frame inside a block "
                              "would be overwritten by the block's next pass")
@@ -540,6 +555,20 @@ class DiffusionLoss(nn.Module):
             raise ValueError("num_atoms_per_sample and num_samples_in_batch are needed without a condition")
         B = int(num_samples_in_batch)
         lattice_systems.check(lattice_system, B, condition.lattice_known() if condition is not None else None)
+        # species control: the admission rows (None: no set is given), validated with the held species before the engine is touched
+        allow_rows = species_mod.resolve_elements(elements, z_table, B) if elements is not None else None
+        if allow_rows is not None:
+            species_mod.check_rows(allow_rows)
+            crystal_of = np.repeat(np.arange(B), self._atom_counts(num_atoms_per_sample, B).numpy())
+            if condition is not None and condition.species_known().any():
+                known = condition.species_known()
+                lut = {int(z): c for c, z in enumerate(z_table.zs)}
+                cls = np.array([lut.get(int(z), -1) if k else 0 for z, k in zip(np.asarray(condition.atomic_numbers), known)])
+                species_mod.check_held(allow_rows, crystal_of, cls, known, "condition")
+            if constant_atoms is not None and constant_atoms is not True and constant_atoms is not False:
+                held = np.asarray(torch.as_tensor(constant_atoms).reshape(-1))
+                if held.size == crystal_of.size:  # (a wrong size is rejected where the species are read)
+                    species_mod.check_held(allow_rows, crystal_of, held, np.ones(held.size, bool), "constant_atoms")
         eng = model.engine()
         dev = eng.device
         S = len(z_table)
@@ -559,6 +588,8 @@ class DiffusionLoss(nn.Module):
                     raise ValueError("constant_atoms must hold one class index per atom")
                 state = inversion.SamplerState(state.frac_x, held.numpy(), state.lengths, state.angles, state.num_atoms, state.t,
                                                state.length_tie)
+        if allow_rows is not None and constant_atoms is True:  # the state's own species are held
+            species_mod.check_held(allow_rows, crystal_of, np.asarray(state.species), np.ones(N, bool), "constant_atoms=True")
         tie = state.length_tie
         angles, lengths = torch.as_tensor(state.angles), torch.as_tensor(state.lengths)
         frac_x, atom_types = torch.as_tensor(state.frac_x), torch.as_tensor(state.species).long()
@@ -603,6 +634,10 @@ class DiffusionLoss(nn.Module):
         corrector = (corrector_steps, corrector_snr) if corrector_steps > 0 else None
         resampling = (resample_passes, jump_length, schedule) if resample_passes > 1 else None
         history = multistep_mod.allocate_history(N, B, dev) if multistep else None  # empty; held through every call of the run
+        # species control: (rows, temperature) for the species exports; None (no set, temperature 1) keeps the exports used so far
+        species_ctl = None
+        if allow_rows is not None or species_temperature != 1.0:
+            species_ctl = (species_mod.device_rows(allow_rows, dev) if allow_rows is not None else None, species_temperature)
         # the events of the host-noise modes: the visited steps, with jumps when resampling (the successor of the last step is
         # the timestep it produces)
         last_succ = (steps[-1] - 1 if schedule is None else successor[steps[-1]]) if steps else 0
@@ -627,7 +662,7 @@ class DiffusionLoss(nn.Module):
                         eng.sample_loop(frac_d, types_d, len_d, ang_d, off_d, steps[start], end - start, seed, const_d, lattice_d,
                                         use_graph=bool(use_graph), fixed_lengths=fixed, condition=cond_d, next_table=next_d,
                                         lattice_clipmax=clipmax, corrector=corrector, resampling=resampling, length_tie=tie_d,
-                                        symmetry=sym_d, eta=eta, multistep=history)
+                                        symmetry=sym_d, eta=eta, multistep=history, species=species_ctl)
                         start = end
                     if j is not None:
                         vis_crystal_during_sampling(z_table, types_d.cpu().numpy(), lattice_d.cpu().numpy(),
@@ -662,7 +697,12 @@ class DiffusionLoss(nn.Module):
                         eng.corrector_step(frac_d, t_d, off_d, eps, gauss(N, 3), corrector_snr)
                         eps, logits, len0 = eng.predict_scores(frac_d, types_d, len_d, ang_d, t_d, off_d)
                     z_l, z_f, u_t = gauss(B, 3), gauss(N, 3), unif(N, S)
-                    if history is not None:  # multistep: the eta = 0 step extrapolated with the history (no z is read)
+                    if species_ctl is not None:  # species control: whichever step below the options name, under it
+                        s_d.fill_(timestep - 1 if schedule is None else successor[timestep])
+                        eng.reverse_step_species(frac_d, types_d, len_d, ang_d, t_d, s_d, off_d, eps, logits, len0, z_l, z_f, u_t,
+                                                 lattice_d, species_ctl, length_tie=tie_d, eta=eta if history is None else None,
+                                                 multistep=history, lattice_clipmax=clipmax)
+                    elif history is not None:  # multistep: the eta = 0 step extrapolated with the history (no z is read)
                         s_d.fill_(timestep - 1 if schedule is None else successor[timestep])
                         eng.reverse_step_multistep(frac_d, types_d, len_d, ang_d, t_d, s_d, off_d, eps, logits, len0, u_t, lattice_d,
                                                    history, tie_d, clipmax)

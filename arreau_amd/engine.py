@@ -257,7 +257,7 @@ class HipEngine:
 
     def sample_loop(self, frac, types, lengths, angles, offsets, t_start, n_steps, seed, const_types, lattice_out,
                     use_graph=False, fixed_lengths=None, condition=None, next_table=None, lattice_clipmax=0.999, corrector=None,
-                    resampling=None, length_tie=None, symmetry=None, eta=None, multistep=None):
+                    resampling=None, length_tie=None, symmetry=None, eta=None, multistep=None, species=None):
         """n_steps iterations of the sampling loop in one library call (arreau_sample_loop; with any of the options below
         arreau_sample_loop_resampled, whose NULL options are the loop without them): in-place update of
         (frac, types, lengths); Philox noise keyed by (seed, timestep, draw, element).  `condition`: the device arrays of a
@@ -278,7 +278,8 @@ class HipEngine:
         positions and lengths (0: none, and the draws are not read); None is the loop without it.  Not with `symmetry`.
         `multistep`: second-order multistep sampling (arreau_sample_loop_multistep): the dict of history tensors of
         multistep.allocate_history, read and overwritten by every step and never emptied by a call; None is the loop without it.
-        Not with `condition`, corrector steps, resampling passes > 1, `symmetry` or an eta other than 0."""
+        Not with `condition`, corrector steps, resampling passes > 1, `symmetry` or an eta other than 0.
+        `species`: species control (arreau_sample_loop_species; see sample_loop_species); None is the loop without it."""
         if multistep is not None:
             from .diffusion.multistep import check_multistep
             check_multistep(True, eta=eta, condition=condition, corrector_steps=corrector[0] if corrector is not None else 0,
@@ -320,7 +321,13 @@ class HipEngine:
         if length_tie is not None:
             self._check_tie(length_tie, B)
         opts = (_byref(cond), _byref(sched), _byref(corr), _byref(res))
-        if multistep is not None:
+        if species is not None:  # whichever loop the options name, under species control
+            eta_c = ctypes.c_float(eta) if eta is not None else None
+            name = "arreau_sample_loop_species"
+            opts += (_hip.ptr(length_tie), _byref(self._symmetry_struct(symmetry, N) if symmetry is not None else None), _byref(eta_c),
+                     _byref(self._multistep_struct(multistep, N, B) if multistep is not None else None),
+                     _byref(self._species_struct(species, B)))
+        elif multistep is not None:
             name, opts = "arreau_sample_loop_multistep", opts + (_hip.ptr(length_tie), _byref(self._multistep_struct(multistep, N, B)))
         elif symmetry is not None:
             name, opts = "arreau_sample_loop_sym", opts + (_hip.ptr(length_tie), _byref(self._symmetry_struct(symmetry, N)))
@@ -333,6 +340,27 @@ class HipEngine:
         else:  # (the plain entry point: A/B runs against an older library through ARREAU_HIP_LIB call it)
             name, opts = "arreau_sample_loop", ()
         _hip.check(getattr(_hip.lib(), name)(*args, *opts, _hip.stream_ptr(self.device)), name)
+
+    def sample_loop_species(self, frac, types, lengths, angles, offsets, t_start, n_steps, seed, const_types, lattice_out, species,
+                            **options):
+        """sample_loop under species control (arreau_sample_loop_species; rules in include/arreau_hip.h): `species` is the pair
+        (allow, temperature) -- allow the admission rows, a contiguous int32 tensor [B, 4] holding the uint32 words of
+        species.pack_rows (None: every class for every crystal), temperature the scale of the species' Gumbel term (>= 0; at 0
+        no uniform is drawn).  `options`: every keyword of sample_loop, combined and rejected as there."""
+        if species is None:
+            raise ValueError("sample_loop_species: species must be the pair (allow, temperature)")
+        self.sample_loop(frac, types, lengths, angles, offsets, t_start, n_steps, seed, const_types, lattice_out, species=species,
+                         **options)
+
+    def _species_struct(self, species, B):
+        """arreau_species_control of the pair (allow, temperature), with the rows' shape, dtype and device checked."""
+        from .diffusion.species import validate_temperature
+        allow, tau = species
+        tau = validate_temperature(tau)
+        if allow is not None and (not torch.is_tensor(allow) or tuple(allow.shape) != (B, 4) or allow.dtype != torch.int32
+                                  or allow.device != self.device or not allow.is_contiguous()):
+            raise ValueError(f"species control: allow must be a contiguous int32 tensor of shape ({B}, 4) on {self.device}")
+        return _hip.SpeciesControlC(_hip.ptr(allow).value if allow is not None else None, tau)
 
     def _multistep_struct(self, history, N, B):
         """arreau_multistep of the dict of history tensors of multistep.allocate_history, with shapes, dtypes and device checked."""
@@ -716,6 +744,22 @@ class HipEngine:
         ms = self._multistep_struct(history, frac.shape[0], lengths.shape[0])
         self._reverse_step_to("arreau_reverse_step_multistep", frac, types, lengths, angles, t_crystal, s_crystal, offsets, eps, logits,
                               len0, None, None, u_types, lattice_out, lattice_clipmax, _hip.ptr(length_tie), _byref(ms))
+
+    def reverse_step_species(self, frac, types, lengths, angles, t_crystal, s_crystal, offsets, eps, logits, len0, z_lattice, z_frac,
+                             u_types, lattice_out, species, length_tie=None, symmetry=None, eta=None, multistep=None,
+                             lattice_clipmax=0.999):
+        """The step of reverse_step_tied / _sym / _eta / _multistep (whichever `symmetry`, `eta`, `multistep` name) under species
+        control (arreau_reverse_step_species): `species` the pair (allow, temperature) of sample_loop_species.  u_types may be
+        None at a temperature of 0; z_lattice and z_frac at eta = 0 or with multistep."""
+        B, N = lengths.shape[0], frac.shape[0]
+        if length_tie is not None:
+            self._check_tie(length_tie, B)
+        sym = self._symmetry_struct(symmetry, N) if symmetry is not None else None
+        ms = self._multistep_struct(multistep, N, B) if multistep is not None else None
+        eta_c = ctypes.c_float(float(eta)) if eta is not None else None
+        self._reverse_step_to("arreau_reverse_step_species", frac, types, lengths, angles, t_crystal, s_crystal, offsets, eps, logits,
+                              len0, z_lattice, z_frac, u_types, lattice_out, lattice_clipmax, _hip.ptr(length_tie), _byref(sym),
+                              _byref(eta_c), _byref(ms), _byref(self._species_struct(species, B)))
 
     def resample_jump(self, frac, types, lengths, angles, s_crystal, t_crystal, offsets, z_frac, z_lengths, u_types, lattice_out,
                       const_types=None, fixed_lengths=None, condition=None, length_tie=None):

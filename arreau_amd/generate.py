@@ -22,6 +22,11 @@ Second-order multistep sampling: `--multistep` extrapolates the deterministic `-
 (DPM-Solver++ 2M): the same one network evaluation per step, fewer `--num_steps` for the same solver error
 (DiffusionLoss.sample).  Not with `--template`, `--symops`, corrector steps, resampling or an `--eta` other than 0.
 
+Species control: `--elements Li,Fe,O` restricts the elements the sampler may choose to that set (symbols or atomic numbers; one
+set for every crystal of every rank): no atom ends outside it or as the mask state.  `--species_temperature X` (>= 0) scales the
+Gumbel draw of the species step; 0 draws nothing, which with `--eta 0` or `--multistep` makes the run a function of its initial
+state in species too (DiffusionLoss.sample).  With every other option.
+
 Starting from given crystals: `--start_from crystals.npz --start_t K` forward-noises the file's crystals to level K (1..T-1) and
 denoises from there -- variants in the neighbourhood of the given structures; with `--invert` they are instead encoded up to
 level K by DDIM inversion, species held, and then decoded (PONITA_DIFFUSION.noise_to / encode; sample(initial_state=...)).  The
@@ -263,6 +268,21 @@ def _eta_arg(text: str) -> float:
         raise argparse.ArgumentTypeError(str(e)) from None
 
 
+def _elements_arg(text: str):
+    out = [int(e) if e.isdigit() else e for e in (part.strip() for part in text.split(",")) if e]
+    if not out:
+        raise argparse.ArgumentTypeError("--elements needs at least one element symbol or atomic number")
+    return out
+
+
+def _species_temperature_arg(text: str) -> float:
+    from .diffusion.species import validate_temperature
+    try:
+        return validate_temperature(float(text))
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
 def _resample_passes_arg(text: str) -> int:
     from .diffusion.resampling import check_resampling
     try:
@@ -301,6 +321,12 @@ def build_parser() -> argparse.ArgumentParser:
                     help="second-order multistep sampling: the deterministic --eta 0 step extrapolated with the previous step's "
                          "prediction (fewer --num_steps for the same solver error); not with --template, --symops, corrector steps, "
                          "resampling or an --eta other than 0")
+    ap.add_argument("--elements", type=_elements_arg, default=None, metavar="LIST",
+                    help="species control: comma-separated element symbols and / or atomic numbers the sampler may choose from "
+                         "(e.g. Li,Fe,O); one set for every crystal; no atom ends outside it or as the mask state")
+    ap.add_argument("--species_temperature", type=_species_temperature_arg, default=1.0, metavar="X",
+                    help="species control: scale of the Gumbel draw of the species step (>= 0; 1 = the sampler as it is, 0 = no "
+                         "draw: deterministic species)")
     ap.add_argument("--start_from", type=str, default=None, metavar="FILE",
                     help="start from the crystals of this crystals.npz / .h5 instead of the prior: noised to --start_t (or, with "
                          "--invert, encoded up to it), then sampled; the file defines the batch")
@@ -573,6 +599,16 @@ def main():
     elif args.num_steps is not None:
         from .diffusion import respacing
         respacing.resolve_schedule(model.diffusion_loss.T, num_steps=args.num_steps)  # (a bad --num_steps fails before sampling)
+    species_kw = dict(elements=args.elements, species_temperature=args.species_temperature)
+    if args.elements is not None or args.species_temperature != 1.0:
+        from .diffusion import species as species_mod
+        try:  # (a bad --elements fails before sampling)
+            row = species_mod.resolve_elements(args.elements, model.hparams.z_table, 1)[0]
+        except ValueError as e:
+            ap.error(str(e).replace("elements:", "--elements:"))
+        if rank == 0:
+            print(f"species control: elements {'any' if args.elements is None else 'Z in {' + species_mod.describe(row, model.hparams.z_table) + '}'}"
+                  f", species temperature {args.species_temperature:g}")
     if args.seed is not None:
         import numpy as np
         torch.manual_seed(args.seed + rank)
@@ -587,7 +623,7 @@ def main():
                                 corrector_steps=args.corrector_steps, corrector_snr=args.corrector_snr,
                                 resample_passes=args.resample_passes, jump_length=args.jump_length,
                                 lattice_system=args.lattice_system, symmetry=spec, eta=args.eta, multistep=args.multistep,
-                                **keywords)
+                                **species_kw, **keywords)
     def start_fn(crystals):
         with _device_turn(lock_path) if lock_path else contextlib.nullcontext():
             state = (model.encode(crystals, t=args.start_t, num_steps=args.num_steps) if args.invert
@@ -595,7 +631,7 @@ def main():
             return model.sample(visualization_setting=VisualizationSetting.NONE, initial_state=state, num_steps=args.num_steps,
                                 use_constant_atomic_symbols=True if args.invert else None, corrector_steps=args.corrector_steps,
                                 corrector_snr=args.corrector_snr, resample_passes=args.resample_passes, jump_length=args.jump_length,
-                                eta=args.eta, multistep=args.multistep, **keywords)
+                                eta=args.eta, multistep=args.multistep, **species_kw, **keywords)
     if start:
         res = generate_from_crystals(start_fn, start_crystals, args.batch, rank, world, unique=unique)
     elif condition is not None:

@@ -330,7 +330,7 @@ class PONITA_DIFFUSION(nn.Module):
                corrector_snr: float = 0.16, resample_passes: int = 1, jump_length: int = 10,
                lattice_system=None, symmetry=None, screen=None, unique=None, find_symmetry=None, reduce_cell=None,
                symmetrize=None, match_to=None, eta: Optional[float] = None, initial_state=None,
-               multistep: bool = False) -> SampleResult:
+               multistep: bool = False, elements=None, species_temperature: float = 1.0) -> SampleResult:
         """lightning_wrappers/diffusion.py:220-253.  `num_atoms_per_sample` may also be a sequence with one atom count
         per crystal of the batch (extension; the reference supports a single int).  Frames of a visualization_setting
         other than NONE go to `<DIFFUSION_DIR>/step_<timestep>.cif` like the reference's PNGs (`vis_name` overrides the
@@ -361,8 +361,12 @@ class PONITA_DIFFUSION(nn.Module):
         the state's species; not with `condition`, `symmetry` or `lattice_system` (DiffusionLoss.sample).  `multistep` (extension):
         second-order multistep sampling -- the deterministic eta = 0 step extrapolated with the previous step's prediction, for
         fewer steps at the same solver error; not with `condition`, corrector steps, resampling, `symmetry` or an eta other than
-        None or 0 (DiffusionLoss.sample)."""
-        from ..diffusion import multistep as multistep_mod, resampling
+        None or 0 (DiffusionLoss.sample).  `elements`, `species_temperature` (extension): species control -- per-crystal element
+        sets the species step may choose from (one collection for the batch, or a list with one collection or None per crystal)
+        and a temperature >= 0 on its Gumbel draw (0: no draw, so eta = 0 and multistep runs are deterministic in all three
+        components); with every option above (DiffusionLoss.sample)."""
+        from ..diffusion import multistep as multistep_mod, resampling, species as species_mod
+        species_temperature = species_mod.validate_temperature(species_temperature)  # (raises before any work)
         multistep = multistep_mod.check_multistep(multistep, eta=eta, condition=condition, corrector_steps=corrector_steps,
                                                   resample_passes=resample_passes, symmetry=symmetry)  # (raises before any work)
         resampling.check_resampling(resample_passes, jump_length)  # (raises before any work)
@@ -401,7 +405,8 @@ class PONITA_DIFFUSION(nn.Module):
             num_steps=num_steps, timesteps=timesteps, corrector_steps=corrector_steps, corrector_snr=corrector_snr,
             resample_passes=resample_passes, jump_length=jump_length, lattice_system=lattice_system, symmetry=symmetry,
             screen=screen, unique=unique, find_symmetry=find_symmetry, reduce_cell=reduce_cell, symmetrize=symmetrize,
-            match_to=match_to, eta=eta, initial_state=initial_state, multistep=multistep)
+            match_to=match_to, eta=eta, initial_state=initial_state, multistep=multistep, elements=elements,
+            species_temperature=species_temperature)
 
     # ---- starting the sampler from given crystals (extension; rules in include/arreau_hip.h) -------------------------------------
     def _crystal_state(self, crystals, t, what):

@@ -1081,7 +1081,8 @@ int arreau_reverse_step_sym(const arreau_model* model,
  *      root).  eta = 1 is that step wherever beta is not clipped, up to the rounding of the float32 betas table against
  *      1 - abar_t / abar_s.  At (t, s) = (1, 0): l_s = x0.
  *   3. species: unchanged -- the D3PM step with its Gumbel draw.  eta = 0 makes positions and lengths a function of the
- *      state alone; species are deterministic only where they are held (d_const_types, a condition's known species).
+ *      state alone; species are deterministic only where they are held (d_const_types, a condition's known species) or at a
+ *      species temperature of 0 (the section "Species control" below), which removes the draw.
  *   4. fixed cells, the known components of a condition (their rules and draws, kinds 3 and 4), corrector steps, resampling
  *      jumps and the lattice-system tie apply as without an eta.  Tied axes take the leader's x_t and draw and the group's
  *      mean x0, and stay bitwise equal.
@@ -1131,7 +1132,8 @@ int arreau_reverse_step_eta(const arreau_model* model,
  *      bit (at s = 0: l = x0).  Then hist_x0 <- x0 (per axis, the value used) and the crystal's level <- t.  Tied axes take the
  *      leader's x_t and history value and the group's mean x0, and stay bitwise equal.  A fixed cell holds its lengths as without
  *      (its history is still kept).
- *   3. species: unchanged -- the D3PM step with its draw, kind 2, the same keys.  No position or length draw is read (a caller's
+ *   3. species: unchanged -- the D3PM step with its draw, kind 2, the same keys (a species temperature of 0, the section "Species
+ *      control" below, removes it).  No position or length draw is read (a caller's
  *      d_z_lattice / d_z_frac may be NULL).
  *   4. the caller empties the levels (zero-fills hist_t_atom and hist_t_len) whenever the state changes outside a step.  A loop call
  *      never empties them, so a run cut into calls (frames, segments) is the run in one call.  The four pointers are part of what a
@@ -1171,6 +1173,70 @@ int arreau_reverse_step_multistep(const arreau_model* model,
                                   const float* d_z_lattice, const float* d_z_frac, const float* d_u_types,
                                   float* d_lattice, float lattice_clipmax, const int32_t* d_length_tie,
                                   const arreau_multistep* multistep, void* stream);
+
+/* ---- Species control (per-crystal element sets, a species temperature) -------------------------------------------------
+ * The D3PM species step restricted to a set of classes per crystal ("generate in a chemical system") and its Gumbel term scaled
+ * by a temperature that can be turned down to 0, which makes the eta = 0 and multistep samplers functions of the initial state in
+ * all three components.  The reference has no such option; the rules are the library's own.  They touch the species half of the
+ * step alone: positions, lengths and the cell are those of the step without the option, bit for bit.
+ *   Inputs: per crystal b an admission row allow[b] of four uint32 words -- class c is bit c & 31 of word c >> 5 (S <= 124; bits at
+ *   or above S are ignored) -- and one scalar temperature tau >= 0.
+ *   The admitted set: the step leaves level t for level s.  E(b, t) is every ordinary class c < S - 1 whose bit is set, plus the
+ *   mask class S - 1: when t > 1 always (the chain passes through it), when t == 1 only if its own bit is set.
+ *   Float32, in this order:
+ *   1. x0 logits: l_c stays for c in E and becomes -inf otherwise, so the softmax gives an excluded class an exact 0 and its
+ *      maximum and sum run over what is left.
+ *   2. posterior: computed as without the option (unit stride, respaced, absorbing shortcut, dense chain) from that softmax.
+ *   3. posterior logits: post_c stays for c in E and becomes -inf otherwise (at t == 1 post is the masked logits of 1).  This makes
+ *      the exclusion exact: without it an excluded class keeps 2 log(1e-6) and can win a Gumbel draw.
+ *   4. value_c = post_c + (tau scale_t) g_c, scale_t = 1 for t != 1 and 0.2 at t == 1, g_c = -log(-log(clip(u_c, 1e-6, 1))) from the
+ *      keys of the step without the option (kind 2, element i S + c).  At tau == 0 nothing is added: the uniforms are neither read
+ *      nor generated and d_u_types may be NULL.
+ *   5. arg-max over the admitted classes only, lowest index first on ties.  Only a value above -inf competes (a NaN does not); if
+ *      no admitted class has one (non-finite logits) the result is the lowest admitted class.  So after a step a sampled atom of
+ *      crystal b holds a class of E(b, t), unconditionally.  (A row that admits nothing at t == 1 -- the callers reject a row
+ *      without an ordinary class -- gives the mask class.)
+ *   6. held species (d_const_types, a condition's known species) are imposed after the draw, as without the option; they are not
+ *      checked on the device.
+ *   7. an atom that enters the step outside its set (a given initial state, a RePaint jump on a non-absorbing chain) leaves it inside.
+ *   8. a symmetric orbit draws one class by the same steps: the orbit's mean logits, the leader's draw, its crystal's row.
+ *   9. a row of all ones (or a NULL table) with tau == 1 is the step without the option bit for bit: no value is masked, and
+ *      1.0f * scale is scale.
+ * A temperature that is negative or not finite is rejected with ARREAU_EINVAL before any work.  The table pointer and the
+ * temperature are part of what a cached hipGraph was captured for.  No claim on sample quality is made. */
+typedef struct arreau_species_control {
+    const uint32_t* d_allow; /* [B,4] admission rows (device); NULL: every class for every crystal */
+    float temperature;       /* tau >= 0: the scale of the Gumbel term (1: the step's own; 0: no draw) */
+} arreau_species_control;
+
+/* Whichever loop of arreau_sample_loop_sym / _eta / _multistep the options name, under species control: `symmetry` and `multistep`
+ * as there (NULL: without), `eta` a host pointer to the eta of arreau_sample_loop_eta (NULL: the ancestral step, whose kernels
+ * differ from the eta = 1 kernels in rounding), `species` a host pointer to the struct above (required).  Every other argument as
+ * in arreau_sample_loop_tied: schedule, condition, corrector, resampling, tie, fixed cell, constant species, t_start, segments, graph
+ * replay, both loop forms and the shape-general path.  What those loops do not combine stays rejected with ARREAU_EINVAL: symmetry
+ * with an eta, a condition, corrector steps or resampling; multistep with a condition, corrector steps, resampling, symmetry or an
+ * eta other than 0. */
+int arreau_sample_loop_species(arreau_model* model, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                               const int32_t* d_crystal_offsets, int32_t B, int32_t N, int32_t t_start, int32_t n_steps,
+                               uint64_t seed, const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice,
+                               void* d_workspace, size_t workspace_bytes, int32_t use_graph,
+                               const arreau_sample_condition* cond, const arreau_sample_schedule* schedule,
+                               const arreau_corrector* corrector, const arreau_resampling* resampling, const int32_t* d_length_tie,
+                               const arreau_symmetry* symmetry, const float* eta, const arreau_multistep* multistep,
+                               const arreau_species_control* species, void* stream);
+
+/* The step of arreau_reverse_step_sym / _eta / _multistep (whichever `symmetry`, `eta`, `multistep` name; all NULL:
+ * arreau_reverse_step_tied) under species control, on the caller's noise and per-crystal d_t / d_s.  d_u_types may be NULL at a
+ * temperature of 0; d_z_lattice and d_z_frac at eta = 0 or with multistep.  Fed arreau_philox_fill's draws it is the step of
+ * arreau_sample_loop_species bit for bit. */
+int arreau_reverse_step_species(const arreau_model* model,
+                                float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                                const int32_t* d_t, const int32_t* d_s, const int32_t* d_crystal_offsets, int32_t B, int32_t N,
+                                const float* d_eps, const float* d_logits, const float* d_len0,
+                                const float* d_z_lattice, const float* d_z_frac, const float* d_u_types,
+                                float* d_lattice, float lattice_clipmax, const int32_t* d_length_tie,
+                                const arreau_symmetry* symmetry, const float* eta, const arreau_multistep* multistep,
+                                const arreau_species_control* species, void* stream);
 
 /* ---- Starting the sampler from given crystals (forward noising, DDIM inversion) ---------------------------------------
  * Every loop export takes t_start, so a run may enter the schedule anywhere; what follows produces the states to enter with.
