@@ -36,6 +36,8 @@ EXPORTS = [
     "arreau_noise_state", "arreau_invert_step", "arreau_invert_loop",
     "arreau_sample_loop_multistep", "arreau_reverse_step_multistep",
     "arreau_sample_loop_species", "arreau_reverse_step_species",
+    "arreau_diffusion_noise_keyed", "arreau_philox_fill_keyed", "arreau_keyed_timestep", "arreau_diffusion_loss_rows",
+    "arreau_loss_rows_reduce",
 ]
 
 STATUS_NONFINITE, STATUS_BAD_TIMESTEP, STATUS_BAD_TYPE, STATUS_BAD_TIE, STATUS_BAD_SYMMETRY = 1, 2, 4, 8, 16
@@ -217,6 +219,11 @@ def _prototypes():
         "arreau_ponita_forward": [vp] * 5 + [i32, i32] + [vp] * 7 + [vp, c_size_t, vp],
         "arreau_diffusion_noise": [vp] * 6 + [i32, i32] + [vp] * 11,
         "arreau_diffusion_losses": [vp] * 10 + [i32, i32] + [vp] * 6,
+        "arreau_diffusion_noise_keyed": [vp] * 5 + [i32, i32, u64, vp, i32, vp, i32] + [vp] * 9,
+        "arreau_philox_fill_keyed": [u64, i32, i32, u32, i64, vp, vp, vp],
+        "arreau_keyed_timestep": [u32, i32, i32, i32, POINTER(i32)],
+        "arreau_diffusion_loss_rows": [vp] * 10 + [i32, i32] + [vp] * 5 + [vp, vp, i64, vp],
+        "arreau_loss_rows_reduce": [vp, i64, i32, i32, vp, vp, vp],
         "arreau_sample_loop": loop + [vp],
         "arreau_sample_loop_conditioned": loop + [cond, vp],
         "arreau_sample_loop_scheduled": loop + [cond, sched, vp],

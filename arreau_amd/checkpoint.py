@@ -82,9 +82,10 @@ def _reference_class_paths():
                 sys.modules[name] = mod
 
 
-def save_lightning_checkpoint(path, module, include_ori_grid=True, weights=None):
+def save_lightning_checkpoint(path, module, include_ori_grid=True, weights=None, trainer_state=None):
     """Write `module` (a PONITA_DIFFUSION) as a Lightning-format checkpoint.  `weights` {state_dict key: tensor}: values written in
-    place of the module's own (save_ema_checkpoint)."""
+    place of the module's own (save_ema_checkpoint).  `trainer_state`: entries that replace the empty trainer bookkeeping (epoch,
+    global_step, loops, optimizer_states, lr_schedulers: save_training_checkpoint)."""
     from .lightning_wrappers.diffusion import ORI_GRID_KEY
     sd = {k: v.detach().cpu() for k, v in module.state_dict().items()}
     for k, v in (weights or {}).items():
@@ -99,9 +100,69 @@ def save_lightning_checkpoint(path, module, include_ori_grid=True, weights=None)
         "hparams_name": "kwargs",
         "hyper_parameters": {"args": module.hparams.args, "z_table": module.hparams.z_table},
     }
+    ckpt.update(trainer_state or {})
     with _reference_class_paths():
         torch.save(ckpt, path)
     return path
+
+
+TRAINING_LOOP_KEY = "arreau_amd.training"  # the entry of `loops` that holds what arreau_amd.train needs to continue a run
+
+
+def _to_cpu(obj):
+    """Tensors of a nested state_dict as CPU copies with storage of their own (an optimizer's moments are views of flat buffers)."""
+    if torch.is_tensor(obj):
+        return obj.detach().to("cpu", copy=True)
+    if isinstance(obj, dict):
+        return {k: _to_cpu(v) for k, v in obj.items()}
+    if isinstance(obj, (list, tuple)):
+        return type(obj)(_to_cpu(v) for v in obj)
+    return obj
+
+
+def save_training_checkpoint(path, module, optimizer, scheduler, epoch, global_step, batch_position=0, run_args=None,
+                             best_val_loss=None, rng_states=None, epochs_completed=None):
+    """save_lightning_checkpoint's file with the trainer slots filled, so that a run can continue from it bit for bit:
+    `epoch`, `global_step`; `optimizer_states` = [optimizer.state_dict()] (a torch optimizer's, or an EMAOptimizer's with the
+    average inside); `lr_schedulers` = [scheduler.state_dict()]; and under loops[TRAINING_LOOP_KEY] what the driver itself needs:
+    the epochs completed and the batch position inside the epoch in progress, torch's CPU generator state (`rng_states`: one per
+    rank; default this process's), the run's arguments that must agree on resume (`run_args`, a dict), the engine's full-range
+    switch and status cadence (module._train_full_range, module._train_steps) and the best validation loss so far.
+    PONITA_DIFFUSION.load_from_checkpoint reads the file as it reads any checkpoint."""
+    loop = {"epochs_completed": int(epoch if epochs_completed is None else epochs_completed), "batch_position": int(batch_position),
+            "cpu_rng_states": [s.clone() for s in (rng_states if rng_states is not None else [torch.random.get_rng_state()])],
+            "run_args": dict(run_args or {}), "train_full_range": bool(getattr(module, "_train_full_range", False)),
+            "train_steps": int(getattr(module, "_train_steps", 0)),
+            "best_val_loss": None if best_val_loss is None else float(best_val_loss)}
+    state = {"epoch": int(epoch), "global_step": int(global_step), "optimizer_states": [_to_cpu(optimizer.state_dict())],
+             "lr_schedulers": [_to_cpu(scheduler.state_dict())] if scheduler is not None else [], "loops": {TRAINING_LOOP_KEY: loop}}
+    return save_lightning_checkpoint(path, module, trainer_state=state)
+
+
+def load_training_state(checkpoint, module=None, optimizer=None, scheduler=None, rank=0, restore_rng=True):
+    """The training state of a file save_training_checkpoint wrote (a path, or the dict load_lightning_checkpoint returned).
+    Raises ValueError for a checkpoint without one.  Given `module` / `optimizer` / `scheduler`, their state is restored from it
+    (weights and buffers strictly; moments, step counts, the average, LRs; the full-range switch), and with restore_rng torch's
+    CPU generator is set to the state saved for `rank`.  Returns the loops[TRAINING_LOOP_KEY] dict plus epoch and global_step."""
+    ckpt = load_lightning_checkpoint(checkpoint) if not isinstance(checkpoint, dict) else checkpoint
+    loop = (ckpt.get("loops") or {}).get(TRAINING_LOOP_KEY)
+    if loop is None or not ckpt.get("optimizer_states"):
+        raise ValueError("the checkpoint holds no training state (it was not written by save_training_checkpoint)")
+    state = dict(loop, epoch=int(ckpt["epoch"]), global_step=int(ckpt["global_step"]))
+    if module is not None:
+        module.load_state_dict(ckpt["state_dict"], strict=True)
+        module._train_full_range = bool(loop["train_full_range"])
+        module._train_steps = int(loop["train_steps"])
+    if optimizer is not None:
+        optimizer.load_state_dict(ckpt["optimizer_states"][0])
+    if scheduler is not None and ckpt.get("lr_schedulers"):
+        scheduler.load_state_dict(ckpt["lr_schedulers"][0])
+    if restore_rng:
+        states = loop["cpu_rng_states"]
+        if rank >= len(states):
+            raise ValueError(f"the checkpoint holds the generator states of {len(states)} rank(s), not of rank {rank}")
+        torch.random.set_rng_state(states[rank])
+    return state
 
 
 def ema_checkpoint_path(path):

@@ -22,6 +22,12 @@
 #define ARREAU_DRAW_Z_JUMP_FRAC 6u      // randn [N,3]  VE_pbc.forward s -> t of the positions
 #define ARREAU_DRAW_Z_JUMP_LENGTHS 7u   // randn [B,3]  VP_lattice.forward s -> t of the lengths
 #define ARREAU_DRAW_U_JUMP_TYPES 8u     // rand  [N,S]  D3PM.q_sample s -> t of the species
+// keyed forward noising of the training / validation loss (arreau_diffusion_noise_keyed): word3 = the crystal's id, the element
+// is counted within the crystal, so a crystal's draws do not depend on the batch around it
+#define ARREAU_DRAW_U_TIMESTEP 9u        // rand  [1]    the timestep uniform: element 0 at counter timestep 0
+#define ARREAU_DRAW_Z_TRAIN_FRAC 10u     // randn [n,3]  element 3 a + d, a the atom's index within its crystal
+#define ARREAU_DRAW_U_TRAIN_TYPES 11u    // rand  [n,S]  element a S + s
+#define ARREAU_DRAW_Z_TRAIN_LENGTHS 12u  // randn [3]    element d
 
 struct Philox4 { uint32_t x[4]; };
 

@@ -3,6 +3,7 @@
 // arreau_predict_scores on the noised state -- the three losses and their gradients with respect to the network
 // outputs (the seeds of the backward pass).  Latency-bound per-atom / per-crystal work; no MFMA.
 #include "internal.h"
+#include "philox.h"
 
 #define D3PM_EPS 1e-6f        // d3pm.py:23
 #define D3PM_HYBRID 0.001f    // d3pm.py:15 hybrid_loss_coeff
@@ -25,18 +26,42 @@ __device__ __forceinline__ float remainder_one_t(float x) {
     return m;
 }
 
+// The keyed draws of arreau_diffusion_noise_keyed (rules in include/arreau_hip.h): counter (element, t, kind, crystal id).
+struct NoiseKey {
+    uint64_t seed;
+    const int64_t* ids;   // [B] crystal ids (low 32 bits are the counter word)
+    const int32_t* copy;  // [B] or null (0)
+    int32_t copies;       // R
+    int32_t draw_t;       // 1: the timestep is drawn (kind 9) and written to tstep
+};
+// t = 1 + ((copy 2^24 + u24) T) / (R 2^24) in 64-bit integers
+__host__ __device__ inline int keyed_timestep(uint32_t u24, int64_t copy, int64_t R, int64_t T) {
+    return (int)(1 + ((copy * 16777216 + (int64_t)u24) * T) / (R * 16777216));
+}
+
 // ---------------------------------------------------------------------------------------------
 // Per crystal: matrix_to_params (lattice_helpers.py:16-35), VP_lattice.forward on the lengths
 // (diffusion_helpers.py:156-163), and the inverse cell for cart_to_frac_coords (:233-251; the reference
 // uses pinv, which equals the inverse for the full-rank cells of a dataset).
 // ---------------------------------------------------------------------------------------------
-__global__ void noise_crystals_kernel(const float* __restrict__ lattice0, const int32_t* __restrict__ tstep,
+// KEYED: the draws come from Philox under `key` instead of the caller's arrays (and the timestep, unless it is given).
+template <bool KEYED>
+__global__ void noise_crystals_kernel(const float* __restrict__ lattice0, int32_t* __restrict__ tstep,
                                       const float* __restrict__ z_len, const float* __restrict__ alpha_bars, int B,
                                       int T, float* __restrict__ lengths, float* __restrict__ angles,
                                       float* __restrict__ noisy_lengths, float* __restrict__ inv_lattice,
-                                      int32_t* __restrict__ status) {
+                                      int32_t* __restrict__ status, NoiseKey key) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
+    if (KEYED && key.draw_t) {
+        int c = key.copy ? key.copy[b] : 0;
+        if (c < 0 || c >= key.copies) {
+            atomicOr(status, ARREAU_STATUS_BAD_TIMESTEP);
+            c = c < 0 ? 0 : key.copies - 1;
+        }
+        const Philox4 r = philox4x32_10(0u, 0u, ARREAU_DRAW_U_TIMESTEP, (uint32_t)key.ids[b], (uint32_t)key.seed, (uint32_t)(key.seed >> 32));
+        tstep[b] = keyed_timestep(r.x[0] >> 8, c, key.copies, T);
+    }
     const float* m = lattice0 + 9 * (size_t)b;
     float len[3];
 #pragma unroll
@@ -53,7 +78,8 @@ __global__ void noise_crystals_kernel(const float* __restrict__ lattice0, const 
         const float c = fminf(fmaxf(dot / (len[j] * len[k]), -1.0f), 1.0f);
         angles[3 * b + i] = acosf(c);
         lengths[3 * b + i] = len[i];
-        noisy_lengths[3 * b + i] = sa * len[i] + sb * z_len[3 * b + i];
+        const float z = KEYED ? philox_normal(key.seed, (uint32_t)t, ARREAU_DRAW_Z_TRAIN_LENGTHS, (uint32_t)i, (uint32_t)key.ids[b]) : z_len[3 * b + i];
+        noisy_lengths[3 * b + i] = sa * len[i] + sb * z;
     }
     // inverse by the adjugate (double: the cell is data, conditioning is not ours to assume)
     const double a = m[0], bb = m[1], c = m[2], d = m[3], e = m[4], f = m[5], g = m[6], h = m[7], i9 = m[8];
@@ -69,12 +95,13 @@ __global__ void noise_crystals_kernel(const float* __restrict__ lattice0, const 
 // Per atom (one wave): VE_pbc.forward (diffusion_helpers.py:43-63) incl. min_distance_sqr_pbc over the 27
 // images (:254-325, first minimum wins) and cart_to_frac_coords % 1; D3PM.q_sample (d3pm.py:119-127).
 // ---------------------------------------------------------------------------------------------
+template <bool KEYED>
 __global__ __launch_bounds__(256) void noise_atoms_kernel(
     const float* __restrict__ frac0, const int32_t* __restrict__ types0, const float* __restrict__ lattice0,
     const float* __restrict__ inv_lattice, const int32_t* __restrict__ tstep, const int32_t* __restrict__ offsets, int B,
     int N, const float* __restrict__ z_frac, const float* __restrict__ u_types, const float* __restrict__ ve_sigmas,
     const float* __restrict__ qmats, int S, int T, float* __restrict__ noisy_frac, float* __restrict__ target_eps,
-    int32_t* __restrict__ noisy_types, int32_t* __restrict__ status) {
+    int32_t* __restrict__ noisy_types, int32_t* __restrict__ status, NoiseKey key) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int i = blockIdx.x * 4 + wave;
     if (i >= N) return;
@@ -90,6 +117,8 @@ __global__ __launch_bounds__(256) void noise_atoms_kernel(
     int t = tstep[lo];
     t = t < 1 ? 1 : (t > T ? T : t);
     const float* Lm = lattice0 + 9 * (size_t)lo;
+    // keyed: the atom's index within its crystal and the crystal's id name the draws
+    const uint32_t a_in = KEYED ? (uint32_t)(i - offsets[lo]) : 0u, cid = KEYED ? (uint32_t)key.ids[lo] : 0u;
     // ---- coordinates: lanes 0..26 take one image each -----------------------------------------------------
     {
         const float sigma = ve_sigmas[t];
@@ -97,7 +126,8 @@ __global__ __launch_bounds__(256) void noise_atoms_kernel(
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
             f0[d] = frac0[3 * (size_t)i + d];
-            fn[d] = remainder_one_t(f0[d] + z_frac[3 * (size_t)i + d] * sigma);
+            const float z = KEYED ? philox_normal(key.seed, (uint32_t)t, ARREAU_DRAW_Z_TRAIN_FRAC, 3u * a_in + (uint32_t)d, cid) : z_frac[3 * (size_t)i + d];
+            fn[d] = remainder_one_t(f0[d] + z * sigma);
         }
         float cn[3], cp[3];
 #pragma unroll
@@ -142,7 +172,8 @@ __global__ __launch_bounds__(256) void noise_atoms_kernel(
     float best = -INFINITY;
     int besti = 0x7fffffff;
     for (int s = lane; s < S; s += 64) {
-        const float u = fminf(fmaxf(un[s], D3PM_EPS), 1.0f);
+        const float ur = KEYED ? philox_uniform(key.seed, (uint32_t)t, ARREAU_DRAW_U_TRAIN_TYPES, a_in * (uint32_t)S + (uint32_t)s, cid) : un[s];
+        const float u = fminf(fmaxf(ur, D3PM_EPS), 1.0f);
         const float val = logf(qrow[s] + D3PM_EPS) + (-logf(-logf(u)));
         if (val > best) { best = val; besti = s; }
     }
@@ -349,7 +380,171 @@ __global__ __launch_bounds__(256) void loss_reduce_kernel(const float* __restric
         losses[5] = ce;
     }
 }
+// ---------------------------------------------------------------------------------------------
+// Per crystal (one wave): the row of arreau_diffusion_loss_rows.  The fixed order of the in-crystal sums: lane l adds the atoms
+// l, l + 64, l + 128, ... of the crystal in ascending order, then the 64 lane sums meet in the xor butterfly 32, 16, ..., 1
+// (wave_sum).  One crystal is always one wave of 64 lanes, so the order depends on the crystal's atom count alone.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void loss_rows_kernel(const float* __restrict__ terms, const float* __restrict__ pred_len,
+                                                        const float* __restrict__ lengths, const int32_t* __restrict__ tstep,
+                                                        const int32_t* __restrict__ offsets, int B, int T,
+                                                        const int64_t* __restrict__ row_index, int64_t n_rows,
+                                                        arreau_loss_row* __restrict__ rows, int32_t* __restrict__ status) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 4 + wave;
+    if (b >= B) return;
+    const int lo = offsets[b], hi = offsets[b + 1];
+    float ef = 0.f, vb = 0.f, ce = 0.f;
+    for (int i = lo + lane; i < hi; i += 64) {
+        ef += terms[3 * (size_t)i];
+        vb += terms[3 * (size_t)i + 1];
+        ce += terms[3 * (size_t)i + 2];
+    }
+    ef = wave_sum(ef);
+    vb = wave_sum(vb);
+    ce = wave_sum(ce);
+    if (lane != 0) return;
+    const int64_t r = row_index[b];
+    if (r < 0 || r >= n_rows) {
+        atomicOr(status, ARREAU_STATUS_BAD_TIMESTEP);
+        return;
+    }
+    const float n = (float)(hi - lo);
+    float e[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        const float dl = pred_len[3 * b + d] - lengths[3 * b + d] / n;  // loss_reduce_kernel's d
+        e[d] = dl * dl;  // (a statement of its own: rounded once, not fused into the sum)
+    }
+    const float e01 = e[0] + e[1];
+    int t = tstep[b];
+    t = t < 1 ? 1 : (t > T ? T : t);
+    arreau_loss_row row;
+    row.coord = ef;
+    row.vb = vb;
+    row.ce = ce;
+    row.lattice = e01 + e[2];
+    row.num_atoms = hi - lo;
+    row.timestep = t;
+    rows[r] = row;
+}
+
+// One workgroup per record: record q < n_bins takes the rows of timestep bin q, record n_bins every written row.  Thread k adds
+// its rows k, k + 256, ... in row order in float64, then the 256 partials meet in the tree 128, 64, ..., 1.
+__global__ __launch_bounds__(256) void loss_rows_reduce_kernel(const arreau_loss_row* __restrict__ rows, int64_t n, int n_bins,
+                                                               int T, double* __restrict__ sums, int64_t* __restrict__ counts) {
+    __shared__ double part[4][256];
+    __shared__ long long cnt[3][256];
+    const int q = blockIdx.x;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    long long atoms = 0, crystals = 0, unwritten = 0;
+    for (int64_t r = threadIdx.x; r < n; r += 256) {
+        const arreau_loss_row row = rows[r];
+        if (row.num_atoms <= 0) {
+            ++unwritten;
+            continue;
+        }
+        int t = row.timestep;
+        t = t < 1 ? 1 : (t > T ? T : t);
+        const int bin = (int)(((int64_t)(t - 1) * n_bins) / T);
+        if (q != n_bins && bin != q) continue;
+        acc[0] += (double)row.coord;
+        acc[1] += (double)row.vb;
+        acc[2] += (double)row.ce;
+        acc[3] += (double)row.lattice;
+        atoms += row.num_atoms;
+        ++crystals;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) part[j][threadIdx.x] = acc[j];
+    cnt[0][threadIdx.x] = atoms;
+    cnt[1][threadIdx.x] = crystals;
+    cnt[2][threadIdx.x] = unwritten;
+    __syncthreads();
+    for (int stride = 128; stride >= 1; stride >>= 1) {
+        if ((int)threadIdx.x < stride) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) part[j][threadIdx.x] += part[j][threadIdx.x + stride];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) cnt[j][threadIdx.x] += cnt[j][threadIdx.x + stride];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) sums[4 * q + j] = part[j][0];
+        counts[2 * q] = cnt[0][0];
+        counts[2 * q + 1] = cnt[1][0];
+        if (q == n_bins) counts[2 * (n_bins + 1)] = cnt[2][0];
+    }
+}
+
+// the keyed draws written out, for parity tests: counter (i, timestep, kind, crystal id)
+__global__ void philox_fill_keyed_kernel(uint64_t seed, uint32_t timestep, uint32_t kind, uint32_t id, int64_t n,
+                                         float* __restrict__ out, uint32_t* __restrict__ raw) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (raw) {
+        const Philox4 r = philox4x32_10((uint32_t)i, timestep, kind, id, (uint32_t)seed, (uint32_t)(seed >> 32));
+        for (int j = 0; j < 4; ++j) raw[4 * i + j] = r.x[j];
+    }
+    if (out) out[i] = (kind == ARREAU_DRAW_U_TIMESTEP || kind == ARREAU_DRAW_U_TRAIN_TYPES) ? philox_uniform(seed, timestep, kind, (uint32_t)i, id)
+                                                                                             : philox_normal(seed, timestep, kind, (uint32_t)i, id);
+}
 }  // namespace
+
+extern "C" int arreau_philox_fill_keyed(uint64_t seed, int32_t timestep, int32_t kind, uint32_t crystal_id, int64_t n,
+                                        float* d_out, uint32_t* d_raw, void* stream) {
+    ARREAU_REQUIRE((d_out || d_raw) && n >= 0 && timestep >= 0 && kind >= (int32_t)ARREAU_DRAW_U_TIMESTEP &&
+                       kind <= (int32_t)ARREAU_DRAW_Z_TRAIN_LENGTHS, "arreau_philox_fill_keyed: bad argument");
+    if (n == 0) return ARREAU_OK;
+    hipLaunchKernelGGL(philox_fill_keyed_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, seed,
+                       (uint32_t)timestep, (uint32_t)kind, crystal_id, n, d_out, d_raw);
+    ARREAU_CHECK_HIP(hipGetLastError());
+    return ARREAU_OK;
+}
+
+extern "C" int arreau_keyed_timestep(uint32_t u24, int32_t copy, int32_t copies, int32_t T, int32_t* t_out) {
+    ARREAU_REQUIRE(t_out && T >= 1 && copies >= 1 && copies <= T && copy >= 0 && copy < copies && u24 < (1u << 24),
+                   "arreau_keyed_timestep: needs 1 <= copies <= T, 0 <= copy < copies and u24 < 2^24");
+    *t_out = keyed_timestep(u24, copy, copies, T);
+    return ARREAU_OK;
+}
+
+extern "C" int arreau_diffusion_noise_keyed(const arreau_model* m, const float* d_frac0, const int32_t* d_types0,
+                                            const float* d_lattice0, const int32_t* d_off, int32_t B, int32_t N, uint64_t seed,
+                                            const int64_t* d_crystal_ids, int32_t copies, const int32_t* d_copy,
+                                            int32_t given_timesteps, int32_t* d_t, float* d_noisy_frac, float* d_target_eps,
+                                            int32_t* d_noisy_types, float* d_noisy_lengths, float* d_lengths, float* d_angles,
+                                            float* d_inv_lattice, void* stream) {
+    ARREAU_REQUIRE(m && d_frac0 && d_types0 && d_lattice0 && d_t && d_off && d_crystal_ids && d_noisy_frac && d_target_eps &&
+                       d_noisy_types && d_noisy_lengths && d_lengths && d_angles && d_inv_lattice,
+                   "arreau_diffusion_noise_keyed: null pointer");
+    ARREAU_REQUIRE(B >= 1 && N >= 0, "arreau_diffusion_noise_keyed: bad size");
+    ARREAU_REQUIRE(copies >= 1 && copies <= m->T, "arreau_diffusion_noise_keyed: the copy count must lie in 1..num_timesteps");
+    hipStream_t s = (hipStream_t)stream;
+    const NoiseKey key{seed, d_crystal_ids, d_copy, copies, given_timesteps ? 0 : 1};
+    hipLaunchKernelGGL(noise_crystals_kernel<true>, dim3((B + 127) / 128), dim3(128), 0, s, d_lattice0, d_t, (const float*)nullptr,
+                       m->vp_alpha_bars, B, m->T, d_lengths, d_angles, d_noisy_lengths, d_inv_lattice, m->status, key);
+    ARREAU_CHECK_HIP(hipGetLastError());
+    if (N > 0) {
+        hipLaunchKernelGGL(noise_atoms_kernel<true>, dim3((N + 3) / 4), dim3(256), 0, s, d_frac0, d_types0, d_lattice0,
+                           d_inv_lattice, d_t, d_off, B, N, (const float*)nullptr, (const float*)nullptr, m->ve_sigmas, m->qmats,
+                           m->S, m->T, d_noisy_frac, d_target_eps, d_noisy_types, m->status, key);
+        ARREAU_CHECK_HIP(hipGetLastError());
+    }
+    return ARREAU_OK;
+}
+
+extern "C" int arreau_loss_rows_reduce(const arreau_loss_row* d_rows, int64_t n_rows, int32_t n_bins, int32_t T, double* d_sums,
+                                       int64_t* d_counts, void* stream) {
+    ARREAU_REQUIRE(d_rows && d_sums && d_counts, "arreau_loss_rows_reduce: null pointer");
+    ARREAU_REQUIRE(n_rows >= 0 && n_bins >= 1 && n_bins <= 1024 && T >= 1, "arreau_loss_rows_reduce: needs n_rows >= 0, 1 <= n_bins <= 1024, T >= 1");
+    hipLaunchKernelGGL(loss_rows_reduce_kernel, dim3(n_bins + 1), dim3(256), 0, (hipStream_t)stream, d_rows, n_rows, n_bins, T,
+                       d_sums, d_counts);
+    ARREAU_CHECK_HIP(hipGetLastError());
+    return ARREAU_OK;
+}
 
 extern "C" int arreau_diffusion_noise(const arreau_model* m, const float* d_frac0, const int32_t* d_types0,
                                       const float* d_lattice0, const int32_t* d_t, const int32_t* d_off, int32_t B,
@@ -362,13 +557,14 @@ extern "C" int arreau_diffusion_noise(const arreau_model* m, const float* d_frac
                        d_inv_lattice, "arreau_diffusion_noise: null pointer");
     ARREAU_REQUIRE(B >= 1 && N >= 0, "arreau_diffusion_noise: bad size");
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(noise_crystals_kernel, dim3((B + 127) / 128), dim3(128), 0, s, d_lattice0, d_t, d_z_lengths,
-                       m->vp_alpha_bars, B, m->T, d_lengths, d_angles, d_noisy_lengths, d_inv_lattice, m->status);
+    hipLaunchKernelGGL(noise_crystals_kernel<false>, dim3((B + 127) / 128), dim3(128), 0, s, d_lattice0, const_cast<int32_t*>(d_t),
+                       d_z_lengths, m->vp_alpha_bars, B, m->T, d_lengths, d_angles, d_noisy_lengths, d_inv_lattice, m->status,
+                       NoiseKey{});  // (the timesteps are only read)
     ARREAU_CHECK_HIP(hipGetLastError());
     if (N > 0) {
-        hipLaunchKernelGGL(noise_atoms_kernel, dim3((N + 3) / 4), dim3(256), 0, s, d_frac0, d_types0, d_lattice0,
+        hipLaunchKernelGGL(noise_atoms_kernel<false>, dim3((N + 3) / 4), dim3(256), 0, s, d_frac0, d_types0, d_lattice0,
                            d_inv_lattice, d_t, d_off, B, N, d_z_frac, d_u_types, m->ve_sigmas, m->qmats, m->S, m->T,
-                           d_noisy_frac, d_target_eps, d_noisy_types, m->status);
+                           d_noisy_frac, d_target_eps, d_noisy_types, m->status, NoiseKey{});
         ARREAU_CHECK_HIP(hipGetLastError());
     }
     return ARREAU_OK;
@@ -390,6 +586,23 @@ extern "C" int arreau_diffusion_losses(const arreau_model* m, const float* d_pre
     ARREAU_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(loss_reduce_kernel, dim3(1), dim3(256), 0, s, d_terms, N, d_pred_lengths, d_lengths, d_off, B,
                        d_losses, d_grad_lengths);
+    ARREAU_CHECK_HIP(hipGetLastError());
+    return ARREAU_OK;
+}
+
+extern "C" int arreau_diffusion_loss_rows(const arreau_model* m, const float* d_pred_eps, const float* d_target_eps,
+                                          const float* d_logits, const int32_t* d_types0, const int32_t* d_noisy_types,
+                                          const int32_t* d_t, const float* d_pred_lengths, const float* d_lengths,
+                                          const int32_t* d_off, int32_t B, int32_t N, float* d_terms, float* d_losses,
+                                          float* d_grad_eps, float* d_grad_logits, float* d_grad_lengths,
+                                          const int64_t* d_row_index, arreau_loss_row* d_rows, int64_t n_rows, void* stream) {
+    ARREAU_REQUIRE(d_row_index && d_rows && n_rows >= 1, "arreau_diffusion_loss_rows: needs a row table and the row of every crystal");
+    const int rc = arreau_diffusion_losses(m, d_pred_eps, d_target_eps, d_logits, d_types0, d_noisy_types, d_t, d_pred_lengths,
+                                           d_lengths, d_off, B, N, d_terms, d_losses, d_grad_eps, d_grad_logits, d_grad_lengths,
+                                           stream);
+    if (rc != ARREAU_OK) return rc;
+    hipLaunchKernelGGL(loss_rows_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, d_terms, d_pred_lengths, d_lengths,
+                       d_t, d_off, B, m->T, d_row_index, n_rows, d_rows, m->status);
     ARREAU_CHECK_HIP(hipGetLastError());
     return ARREAU_OK;
 }

@@ -200,7 +200,7 @@ class DiffusionLoss(nn.Module):
         self.num_atomic_states = num_atomic_states
 
     def __call__(self, model, batch, t_emb_weights=None, timestep=None, noise=None, return_parts=False,
-                 training=False):
+                 training=False, seed=None, crystal_ids=None, copies=1, copy=None, rows=None, row_index=None):
         """diffusion_loss.py:204-274: sample a timestep per crystal, noise (coordinates, atom types, cell lengths),
         evaluate the score network on the noised batch and return `coord + atom-type + lattice` error (weights 1).
 
@@ -210,6 +210,14 @@ class DiffusionLoss(nn.Module):
         rand(N,S) (D3PM.get_xt), randn_like(lengths) (VP_lattice.forward), from torch's global CPU generator;
         `noise=(z_frac, u_types, z_lengths)` injects them instead (parity tests).  Everything else runs in
         libarreau_hip.so (arreau_diffusion_noise -> arreau_predict_scores -> arreau_diffusion_losses).
+
+        `noise="philox"` is the keyed path (arreau_diffusion_noise_keyed; rules in include/arreau_hip.h): nothing is drawn on the
+        host and nothing but the clean batch and the ids is staged.  The timestep and the three draws of crystal b come from
+        Philox keyed by (`seed`, crystal_ids[b]) -- `crystal_ids` [B] integers below 2^32, default batch.index (collate's dataset
+        indices) -- so a crystal is noised the same way wherever it lands in a batch.  `copies` = R and `copy` [B] (default 0): R
+        noisings of every crystal at stratified timesteps.  A given `timestep` replaces the drawn one.
+        `rows` / `row_index` (any noise mode): also write every crystal's loss row into the caller's table
+        (HipEngine.loss_row_table; arreau_diffusion_loss_rows) at row_index[b].
 
         `training=True` evaluates the network with arreau_train_forward (fp32, activations kept) instead of the fused
         sampling kernels, so that HipEngine.train_backward can follow.
@@ -224,15 +232,36 @@ class DiffusionLoss(nn.Module):
         frac0 = torch.as_tensor(batch.X0)
         if frac0.shape != (N, 3):
             raise ValueError("batch.X0 must be [sum(num_atoms), 3]")
+        keyed = isinstance(noise, str)
+        if keyed:
+            if noise != "philox":
+                raise ValueError("noise must be None (host draws), a tuple of draws or 'philox' (keyed draws in the kernels)")
+            if seed is None:
+                raise ValueError("noise='philox' needs a seed")
+            ids = torch.as_tensor(batch.index if crystal_ids is None else crystal_ids).to("cpu", torch.int64).reshape(-1)
+            if ids.numel() != B or (B and (int(ids.min()) < 0 or int(ids.max()) >= 2 ** 32)):
+                raise ValueError("crystal_ids must hold one id in 0..2^32-1 per crystal")
+            copies = int(copies)
+            if not 1 <= copies <= self.T:
+                raise ValueError(f"copies must lie in 1..{self.T}")
+            copy_h = None
+            if copy is not None:
+                copy_h = torch.as_tensor(copy).to("cpu", torch.int64).reshape(-1)
+                if copy_h.numel() != B or int(copy_h.min()) < 0 or int(copy_h.max()) >= copies:
+                    raise ValueError("copy must hold one value in 0..copies-1 per crystal")
+        elif seed is not None or crystal_ids is not None or copy is not None or copies != 1:
+            raise ValueError("seed, crystal_ids, copies and copy belong to noise='philox'")
         if timestep is None:
-            t = torch.randint(1, self.T + 1, size=(B, 1)).long()
+            t = None if keyed else torch.randint(1, self.T + 1, size=(B, 1)).long()
         elif torch.is_tensor(timestep) and timestep.numel() == B:
             t = timestep.reshape(B, 1).long().cpu()
         else:
             t = torch.ones((B, 1)).long() * int(timestep)
-        if int(t.min()) < 1 or int(t.max()) > self.T:
+        if t is not None and (int(t.min()) < 1 or int(t.max()) > self.T):
             raise ValueError(f"timestep must be in 1..{self.T}")
-        if noise is None:
+        if keyed:
+            z_frac = u_types = z_len = None  # drawn in the kernels
+        elif noise is None:
             dt = torch.get_default_dtype()
             z_frac = torch.randn((N, 3), dtype=dt)
             u_types = torch.rand((N, S))
@@ -244,18 +273,36 @@ class DiffusionLoss(nn.Module):
         # enqueued the next step (round 4, rocprofv3 kernel trace of the training step: 0.25 ms of 3.2 without the profiler).
         off_host = torch.zeros(B + 1, dtype=torch.int64)
         off_host[1:] = torch.cumsum(n_cpu, 0)
-        frac_d, cell_d, z_frac_d, u_types_d, z_len_d = stage_to_device(
-            dev, torch.float32, [frac0, torch.as_tensor(batch.L0).reshape(-1, 3, 3), z_frac, u_types, z_len])
-        t_d, types0, off = stage_to_device(dev, torch.int32, [t.reshape(B), batch.A0, off_host])
-        nz = eng.diffusion_noise(frac_d, types0, cell_d, t_d, off, z_frac_d, u_types_d, z_len_d)
+        row_d = None
+        if keyed:
+            frac_d, cell_d = stage_to_device(dev, torch.float32, [frac0, torch.as_tensor(batch.L0).reshape(-1, 3, 3)])
+            ints = [batch.A0, off_host] + ([t.reshape(B)] if t is not None else []) + ([copy_h] if copy_h is not None else [])
+            ints = stage_to_device(dev, torch.int32, ints)
+            types0, off = ints[0], ints[1]
+            longs = stage_to_device(dev, torch.int64, [ids] + ([torch.as_tensor(row_index).reshape(B)] if rows is not None else []))
+            nz = eng.diffusion_noise_keyed(frac_d, types0, cell_d, off, seed, longs[0], copies,
+                                           ints[-1] if copy_h is not None else None, ints[2] if t is not None else None)
+            t_d = nz.pop("t")
+            row_d = longs[1] if rows is not None else None
+        else:
+            frac_d, cell_d, z_frac_d, u_types_d, z_len_d = stage_to_device(
+                dev, torch.float32, [frac0, torch.as_tensor(batch.L0).reshape(-1, 3, 3), z_frac, u_types, z_len])
+            t_d, types0, off = stage_to_device(dev, torch.int32, [t.reshape(B), batch.A0, off_host])
+            nz = eng.diffusion_noise(frac_d, types0, cell_d, t_d, off, z_frac_d, u_types_d, z_len_d)
+            if rows is not None:
+                row_d, = stage_to_device(dev, torch.int64, [torch.as_tensor(row_index).reshape(B)])
         evaluate = eng.train_forward if training else eng.predict_scores
         run = lambda: evaluate(nz["noisy_frac"], nz["noisy_types"], nz["noisy_lengths"], nz["angles"], t_d, off)
         # (validation: sticky device flags -> raise; non-finite outputs with fp8 operand planes in use -> repeated on fp16 planes: HipEngine.checked.
         # Reading the flags synchronises the stream, so the training step -- whose host work overlaps the device's, and whose
         # forward runs no fp8 product -- leaves that to PONITA_DIFFUSION.training_step, every STATUS_CHECK_EVERY steps.)
         eps, logits, len0 = run() if training else eng.checked(run)
-        losses, grads = eng.diffusion_losses(eps, nz["target_eps"], logits, types0, nz["noisy_types"], t_d, len0,
-                                             nz["lengths"], off, with_grads=True)
+        if rows is not None:
+            losses, grads, _ = eng.diffusion_loss_rows(eps, nz["target_eps"], logits, types0, nz["noisy_types"], t_d, len0,
+                                                       nz["lengths"], off, row_d, rows, with_grads=True)
+        else:
+            losses, grads = eng.diffusion_losses(eps, nz["target_eps"], logits, types0, nz["noisy_types"], t_d, len0,
+                                                 nz["lengths"], off, with_grads=True)
         if return_parts:
             return losses[0], dict(error_frac_x=losses[1], error_atomic_type=losses[2], error_lattice=losses[3],
                                    vb=losses[4], ce=losses[5], pred_eps=eps, logits=logits, pred_lengths=len0,

@@ -117,35 +117,63 @@ class CrystalDataset(torch.utils.data.Dataset):
                                L0=torch.tensor(np.asarray(c.L0), dtype=dt), num_atoms=len(c.atomic_numbers))
 
 
-def collate(items):
+def collate(items, index=None):
     """What torch_geometric's DataLoader makes of a list of those `Data` objects: tensors concatenated along dim 0,
-    python ints stacked, plus `batch` (crystal of each atom) and `ptr`."""
+    python ints stacked, plus `batch` (crystal of each atom) and `ptr`.  `index` (extension): the dataset indices of the items, kept
+    as the int64 field `index` -- the crystal ids of the keyed noise (DiffusionLoss.__call__(noise="philox"))."""
     n = torch.tensor([int(it.num_atoms) for it in items], dtype=torch.long)
     B = len(items)
-    return SimpleNamespace(pos=torch.cat([it.pos for it in items]), X0=torch.cat([it.X0 for it in items]),
+    extra = {} if index is None else {"index": torch.as_tensor(np.asarray(index), dtype=torch.long).reshape(B)}
+    return SimpleNamespace(**extra, pos=torch.cat([it.pos for it in items]), X0=torch.cat([it.X0 for it in items]),
                            A0=torch.cat([it.A0 for it in items]), L0=torch.cat([it.L0 for it in items]), num_atoms=n,
                            batch=torch.arange(B).repeat_interleave(n), ptr=torch.cat([n.new_zeros(1), n.cumsum(0)]),
                            num_graphs=B)
 
 
 def iterate_batches(dataset, batch_size: int, shuffle: bool = True, seed: int = 0, rank: int = 0, world_size: int = 1,
-                    drop_last: bool = False):
+                    drop_last: bool = False, start: int = 0):
     """One epoch of batches for data-parallel rank `rank` of `world_size`: every rank uses the same permutation (seeded)
     and takes every world_size-th crystal, like DistributedSampler under Lightning's DDP (main_diffusion.py:293-303).
     With several ranks the permutation is first cut to a multiple of world_size (DistributedSampler's drop_last), so every
     rank sees the same number of crystals and therefore of batches: a rank with one batch more than its peers would wait
-    for ever in that step's all-reduce."""
+    for ever in that step's all-reduce.  `start`: skip that many batches, by index arithmetic (none of them is built): the tail of the
+    full iteration, for a run resumed inside an epoch."""
     order = np.arange(len(dataset))
     if shuffle:
         np.random.RandomState(seed).shuffle(order)
     if world_size > 1:
         order = order[:len(order) - len(order) % world_size]
     mine = order[rank::world_size]
-    for s in range(0, len(mine), batch_size):
+    for s in range(int(start) * batch_size, len(mine), batch_size):
         idx = mine[s:s + batch_size]
         if drop_last and len(idx) < batch_size:
             break
-        yield collate([dataset[int(i)] for i in idx])
+        yield collate([dataset[int(i)] for i in idx], index=idx)
+
+
+def split_indices(n: int, val_fraction: float, seed: int = 0):
+    """(train indices, validation indices) of a seeded split of range(n) by index: a permutation under `seed`, its first
+    round(val_fraction * n) entries (at least one, at most n - 1) the validation set; both sorted.  A function of (n, val_fraction,
+    seed) alone: the same on every rank and in every run."""
+    if not 0.0 < val_fraction < 1.0 or n < 2:
+        raise ValueError("val_fraction must lie strictly between 0 and 1 and the dataset must hold at least two crystals")
+    order = np.random.RandomState(seed).permutation(n)
+    k = min(max(int(round(val_fraction * n)), 1), n - 1)
+    return np.sort(order[k:]), np.sort(order[:k])
+
+
+class Subset(torch.utils.data.Dataset):
+    """The crystals `indices` of a CrystalDataset, with its class table (a --val_fraction split)."""
+
+    def __init__(self, dataset, indices):
+        self.dataset, self.indices = dataset, np.asarray(indices, dtype=np.int64)
+        self.z_table = dataset.z_table
+
+    def __len__(self):
+        return len(self.indices)
+
+    def __getitem__(self, idx: int):
+        return self.dataset[int(self.indices[idx])]
 
 
 def synthetic_alexandria_like(num_crystals: int, seed: int = 0, num_species: int = 89, max_atoms: int = 64,

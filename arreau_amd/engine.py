@@ -498,6 +498,85 @@ class HipEngine:
             "arreau_diffusion_losses")
         return (losses, g) if with_grads else losses
 
+    # ---- training runs: keyed noise, per-crystal loss rows, their binned reduction (rules in include/arreau_hip.h) ----
+    ROW_WORDS = 6  # arreau_loss_row: four float32 sums, int32 atom count, int32 timestep
+
+    def diffusion_noise_keyed(self, frac0, types0, lattice0, offsets, seed, crystal_ids, copies=1, copy=None, t_crystal=None):
+        """Forward noising with the draws made in the kernels, keyed by (seed, crystal id) (arreau_diffusion_noise_keyed).
+        crystal_ids [B] int64 on the device; copy [B] int32 or None; t_crystal [B] int32: the caller's timesteps instead of the
+        drawn ones.  Returns diffusion_noise's dict plus `t` (int32 [B], the timesteps used)."""
+        dev = self.device
+        N, B = frac0.shape[0], lattice0.shape[0]
+        if crystal_ids.dtype != torch.int64 or crystal_ids.shape != (B,) or crystal_ids.device != dev:
+            raise ValueError("crystal_ids must be an int64 tensor [B] on the engine's device")
+        if copy is not None and (copy.dtype != torch.int32 or copy.shape != (B,) or copy.device != dev):
+            raise ValueError("copy must be an int32 tensor [B] on the engine's device")
+        f32 = dict(device=dev, dtype=torch.float32)
+        t = torch.empty(B, device=dev, dtype=torch.int32) if t_crystal is None else t_crystal
+        out = dict(noisy_frac=torch.empty((N, 3), **f32), target_eps=torch.empty((N, 3), **f32),
+                   noisy_types=torch.empty(N, device=dev, dtype=torch.int32), noisy_lengths=torch.empty((B, 3), **f32),
+                   lengths=torch.empty((B, 3), **f32), angles=torch.empty((B, 3), **f32), t=t)
+        inv = torch.empty((B, 3, 3), **f32)
+        _hip.check(_hip.lib().arreau_diffusion_noise_keyed(
+            self._handle, _hip.ptr(frac0), _hip.ptr(types0), _hip.ptr(lattice0), _hip.ptr(offsets), B, N,
+            int(seed) & (2 ** 64 - 1), _hip.ptr(crystal_ids), int(copies), _hip.ptr(copy), int(t_crystal is not None), _hip.ptr(t),
+            _hip.ptr(out["noisy_frac"]), _hip.ptr(out["target_eps"]), _hip.ptr(out["noisy_types"]), _hip.ptr(out["noisy_lengths"]),
+            _hip.ptr(out["lengths"]), _hip.ptr(out["angles"]), _hip.ptr(inv), _hip.stream_ptr(dev)),
+            "arreau_diffusion_noise_keyed")
+        return out
+
+    def philox_fill_keyed(self, seed, timestep, kind, crystal_id, n, raw=False):
+        """The keyed draws written out (arreau_philox_fill_keyed): kinds 10 / 12 standard normal, 9 / 11 uniform [0,1)."""
+        out = torch.empty(n, device=self.device, dtype=torch.float32)
+        words = torch.empty((n, 4), device=self.device, dtype=torch.int32) if raw else None
+        _hip.check(_hip.lib().arreau_philox_fill_keyed(int(seed) & (2 ** 64 - 1), int(timestep), int(kind), int(crystal_id) & (2 ** 32 - 1),
+                                                       int(n), _hip.ptr(out), _hip.ptr(words), _hip.stream_ptr(self.device)),
+                   "arreau_philox_fill_keyed")
+        return (out, words) if raw else out
+
+    def loss_row_table(self, n_rows):
+        """A zeroed table of n_rows arreau_loss_row (int32 [n_rows, 6]; rows_to_fields views it)."""
+        return torch.zeros((int(n_rows), self.ROW_WORDS), device=self.device, dtype=torch.int32)
+
+    @staticmethod
+    def rows_to_fields(rows):
+        """(float32 [n, 4] coord / vb / ce / lattice sums, int32 [n] atom counts, int32 [n] timesteps) of a row table (copies)."""
+        return rows[:, :4].contiguous().view(torch.float32), rows[:, 4].contiguous(), rows[:, 5].contiguous()
+
+    def diffusion_loss_rows(self, pred_eps, target_eps, logits, types0, noisy_types, t_crystal, pred_lengths, lengths, offsets,
+                            row_index, rows, with_grads=False):
+        """diffusion_losses plus one row per crystal in the caller's table (arreau_diffusion_loss_rows): crystal b goes to
+        rows[row_index[b]] (row_index int64 [B] on the device, rows from loss_row_table).  Returns (losses[6], (grad_eps,
+        grad_logits, grad_lengths) or Nones, terms [N,3])."""
+        dev = self.device
+        N, B = pred_eps.shape[0], pred_lengths.shape[0]
+        if row_index.dtype != torch.int64 or row_index.shape != (B,) or row_index.device != dev:
+            raise ValueError("row_index must be an int64 tensor [B] on the engine's device")
+        if rows.dtype != torch.int32 or rows.dim() != 2 or rows.shape[1] != self.ROW_WORDS or rows.device != dev:
+            raise ValueError("rows must come from loss_row_table")
+        f32 = dict(device=dev, dtype=torch.float32)
+        terms = torch.empty((N, 3), **f32)
+        losses = torch.empty(6, **f32)
+        g = (torch.empty((N, 3), **f32), torch.empty((N, self.S), **f32), torch.empty((B, 3), **f32)) if with_grads \
+            else (None, None, None)
+        _hip.check(_hip.lib().arreau_diffusion_loss_rows(
+            self._handle, _hip.ptr(pred_eps), _hip.ptr(target_eps), _hip.ptr(logits), _hip.ptr(types0),
+            _hip.ptr(noisy_types), _hip.ptr(t_crystal), _hip.ptr(pred_lengths), _hip.ptr(lengths), _hip.ptr(offsets), B, N,
+            _hip.ptr(terms), _hip.ptr(losses), _hip.ptr(g[0]), _hip.ptr(g[1]), _hip.ptr(g[2]), _hip.ptr(row_index), _hip.ptr(rows),
+            int(rows.shape[0]), _hip.stream_ptr(dev)), "arreau_diffusion_loss_rows")
+        return losses, g, terms
+
+    def loss_rows_reduce(self, rows, n_bins, T=None):
+        """The binned fixed-order float64 reduction of a row table (arreau_loss_rows_reduce).  Returns device tensors
+        (sums float64 [n_bins + 1, 4], counts int64 [n_bins + 1, 2], unwritten int64 [1]); the last record is the total."""
+        dev = self.device
+        T = int(self.cfg.num_timesteps if T is None else T)
+        sums = torch.empty((n_bins + 1, 4), device=dev, dtype=torch.float64)
+        counts = torch.empty(2 * (n_bins + 1) + 1, device=dev, dtype=torch.int64)
+        _hip.check(_hip.lib().arreau_loss_rows_reduce(_hip.ptr(rows), int(rows.shape[0]), int(n_bins), T, _hip.ptr(sums),
+                                                      _hip.ptr(counts), _hip.stream_ptr(dev)), "arreau_loss_rows_reduce")
+        return sums, counts[:-1].view(n_bins + 1, 2), counts[-1:]
+
     # ---- training (BASELINE config 5) ---------------------------------------------------------------
     def train_forward(self, frac, types, lengths, angles, t_crystal, offsets):
         """Training-mode network evaluation (arreau_train_forward): fp32, activations kept for train_backward.

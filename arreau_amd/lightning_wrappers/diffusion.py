@@ -135,10 +135,11 @@ class PONITA_DIFFUSION(nn.Module):
         return model
 
     # ---- training (BASELINE config 5) --------------------------------------------------------------
-    def training_step(self, graph, timestep=None, noise=None):
+    def training_step(self, graph, timestep=None, noise=None, **keyed):
         """lightning_wrappers/diffusion.py:108-118: one forward + backward of the score-matching loss on a collated batch
         (fields X0, A0, L0, num_atoms).  Leaves d(loss)/d(parameter) in `.grad` of every trainable parameter of
         `self.model` (what loss.backward() does in the reference) and returns the loss as a 0-d CUDA tensor.
+        `noise="philox"` with `seed=` (and crystal_ids, copies, copy: DiffusionLoss.__call__): the keyed draws, made in the kernels.
         On the first training forward the conv weights are rescaled by the activation std ratios
         (FiberBundleConv.callibrate, ponita/nn/conv.py:121-123,140-146) -- after this step's gradients were taken."""
         # The step never waits for the device (inputs cross in asynchronous copies), so the host could run many steps ahead:
@@ -148,7 +149,7 @@ class PONITA_DIFFUSION(nn.Module):
         if len(inflight) >= 2:
             inflight.popleft().synchronize()
         loss, parts = self.diffusion_loss(self, graph, self.t_emb, timestep=timestep, noise=noise, return_parts=True,
-                                          training=True)
+                                          training=True, **keyed)
         eng = self.engine(for_training=True)
         grads = eng.train_backward(parts["grad_eps"], parts["grad_logits"], parts["grad_lengths"])
         params = self.__dict__.get("_named_parameter_cache")
@@ -197,9 +198,78 @@ class PONITA_DIFFUSION(nn.Module):
         return loss
 
     @torch.no_grad()
-    def validation_step(self, graph, timestep=None, noise=None):
-        """lightning_wrappers/diffusion.py:126-137: the same loss without a backward pass (fused sampling kernels)."""
-        return self.diffusion_loss(self, graph, self.t_emb, timestep=timestep, noise=noise)
+    def validation_step(self, graph, timestep=None, noise=None, **keyed):
+        """lightning_wrappers/diffusion.py:126-137: the same loss without a backward pass (fused sampling kernels).  `keyed`: the
+        arguments of the keyed noise (noise="philox", seed=..., crystal_ids, copies, copy: DiffusionLoss.__call__)."""
+        return self.diffusion_loss(self, graph, self.t_emb, timestep=timestep, noise=noise, **keyed)
+
+    @torch.no_grad()
+    def evaluate(self, dataset, batch_size, seed, copies=4, n_bins=10, kernels="train", rank=0, world_size=1):
+        """The held-out loss of `dataset` AS ONE BATCH: the reference's formula
+            (sum coord + 0.001 sum vb + sum ce) / N + sum lattice / (3 B)
+        over all crystals and all `copies` noisings of the set (N atoms and B crystals counted with their copies), so it does not
+        depend on how the set was cut into batches.  Every (crystal, copy) is noised by the keyed draws of (seed, dataset index,
+        copy, copies) -- the same way every time it is looked at, wherever it lands -- at timesteps stratified over 1..T by copy.
+        Its loss row goes to row copies * index + copy of ONE device table (arreau_diffusion_loss_rows); nothing is read back until
+        the table has been reduced in one launch (arreau_loss_rows_reduce: fixed order, float64), so two calls give the same bits.
+        Several ranks: rank r evaluates the pairs r, r + world_size, ... into its zero-initialised table, the tables are summed
+        over the ranks (adding zeros is exact) and every rank runs the one reduction: all ranks hold the same bits.
+        kernels="train": the network is evaluated with arreau_train_forward -- the choice inside a training run, where the sampling
+        kernels' packed planes are stale between optimizer steps; "sampling": through predict_scores, for a loaded checkpoint.
+        Returns dict(loss, error_frac_x, error_atomic_type, error_lattice, vb, ce, num_crystals, num_atoms, copies, seed, bins):
+        `bins` lists the same errors per timestep bin (bin = (t - 1) * n_bins / T), each normalised by the bin's own counts."""
+        if kernels not in ("train", "sampling"):
+            raise ValueError("kernels must be 'train' or 'sampling'")
+        T = self.diffusion_loss.T
+        n, R = len(dataset), int(copies)
+        if not 1 <= R <= T:
+            raise ValueError(f"copies must lie in 1..{T}")
+        if n < 1 or batch_size < 1 or n_bins < 1:
+            raise ValueError("evaluate needs a non-empty dataset, batch_size >= 1 and n_bins >= 1")
+        from ..diffusion.lattice_dataset import collate
+        training = kernels == "train"
+        stale = self._engine is not None and self._engine.stale_for_sampling
+        # (the sampling kernels on a module in training: a fresh engine inside the block, the training engine back afterwards)
+        guard = self.parameters_swapped() if (not training and stale) else contextlib.nullcontext()
+        with guard:
+            eng = self.engine(for_training=training)
+            rows = eng.loss_row_table(n * R)
+            pairs = np.arange(rank, n * R, world_size, dtype=np.int64)
+            for s in range(0, len(pairs), batch_size):
+                k = pairs[s:s + batch_size]
+                idx, cp = k // R, k % R
+                batch = collate([dataset[int(i)] for i in idx], index=idx)
+                self.diffusion_loss(self, batch, self.t_emb, noise="philox", seed=seed, copies=R, copy=cp, rows=rows, row_index=k,
+                                    training=training)
+            if world_size > 1:
+                import torch.distributed as dist
+                # (int32 words, all but one rank's zero: the integer sum is the written word, bit for bit)
+                if dist.get_backend() == "nccl":
+                    dist.all_reduce(rows, op=dist.ReduceOp.SUM)
+                else:
+                    host = rows.cpu()
+                    dist.all_reduce(host, op=dist.ReduceOp.SUM)
+                    rows.copy_(host)
+            sums, counts, unwritten = eng.loss_rows_reduce(rows, int(n_bins), T)
+            sums, counts, unwritten = sums.cpu().numpy(), counts.cpu().numpy(), int(unwritten)  # the one host read
+            eng.check_status()
+        if unwritten:
+            raise RuntimeError(f"evaluate: {unwritten} of {n * R} rows were never written (a rank's partial table?)")
+
+        def record(s, c):
+            atoms, crystals = int(c[0]), int(c[1])
+            if crystals == 0:
+                return dict(num_crystals=0, num_atoms=0, loss=None, error_frac_x=None, error_atomic_type=None, error_lattice=None,
+                            vb=None, ce=None)
+            ef, vb, ce, el = s[0] / atoms, s[1] / atoms, s[2] / atoms, s[3] / (3 * crystals)
+            et = 0.001 * vb + ce
+            return dict(num_crystals=crystals, num_atoms=atoms, loss=float(ef + et + el), error_frac_x=float(ef),
+                        error_atomic_type=float(et), error_lattice=float(el), vb=float(vb), ce=float(ce))
+
+        out = record(sums[-1], counts[-1])
+        out.update(copies=R, seed=int(seed), n_bins=int(n_bins), num_timesteps=int(T), kernels=kernels,
+                   bins=[record(sums[q], counts[q]) for q in range(int(n_bins))])
+        return out
 
     test_step = validation_step  # :139-150
 

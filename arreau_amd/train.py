@@ -10,6 +10,12 @@ of a flat fp32 bucket (1.17 M parameters = 4.7 MB; RCCL when the process group i
 
 `--ema_decay D` keeps an exponential moving average of the weights (arreau_amd.optim.EMAOptimizer, updated inside the optimizer's
 launch); with `--out X.ckpt` rank 0 then also writes the averaged weights to `X-EMA.ckpt`, the checkpoint to sample from.
+
+Training runs: `--val_data FILES` or `--val_fraction F` holds crystals out and `--val_interval E` logs their loss every E epochs
+(PONITA_DIFFUSION.evaluate: keyed noise, the loss of the set as one batch, the same on every rank); `--checkpoint_dir D` with
+`--checkpoint_every_n_epochs` / `--checkpoint_every_n_steps` writes training checkpoints (checkpoint.save_training_checkpoint),
+`--keep_best` keeps the one with the lowest validation loss, and `--resume CKPT` continues a run from one bit for bit.
+`--noise philox` draws the training noise in the kernels, keyed by (seed, epoch, crystal), instead of on the host.
 """
 import argparse
 import os
@@ -107,24 +113,44 @@ def configure_training(model, epochs: int, ema_decay: Optional[float] = None, em
     return optimizer, scheduler
 
 
+PHILOX_EPOCH_STRIDE = 0x9E3779B97F4A7C15  # the keyed training noise of epoch e runs under seed + e * this, mod 2^64
+
+
+def epoch_noise_seed(seed: int, epoch: int) -> int:
+    return (int(seed) + int(epoch) * PHILOX_EPOCH_STRIDE) % 2 ** 64
+
+
 def train_epochs(model, dataset, epochs: int, batch_size: int, rank: int = 0, world_size: int = 1, seed: int = 0,
-                 log=print, optimizer=None, scheduler=None):
+                 log=print, optimizer=None, scheduler=None, noise: str = "host", start_epoch: int = 0, start_batch: int = 0,
+                 global_step: int = 0, on_step=None, on_epoch=None):
     """`batch_size` is per rank (global batch = batch_size * world_size).  Returns the list of per-step losses.
-    `optimizer` / `scheduler`: from configure_training (default: configure_optimizers' own, no EMA)."""
+    `optimizer` / `scheduler`: from configure_training (default: configure_optimizers' own, no EMA).
+    `noise`: "host" draws the step's noise from torch's CPU generator (the reference's order); "philox" draws it in the kernels,
+    keyed by (epoch_noise_seed(seed, epoch), the crystal's dataset index).  `start_epoch` / `start_batch` / `global_step`: where a
+    resumed run continues (the batches before start_batch of its first epoch are skipped by index arithmetic).
+    `on_step(epoch, batches_done, global_step)` after every optimizer step and `on_epoch(epoch, global_step)` after every epoch's
+    scheduler step: the driver's checkpoints and validation."""
     from .diffusion.lattice_dataset import iterate_batches
     from .diffusion.diffusion_loss import DiffusionLossMetric
+    if noise not in ("host", "philox"):
+        raise ValueError("noise must be 'host' or 'philox'")
     if optimizer is None:
         optimizer, scheduler = configure_training(model, epochs)
     losses = []
-    for epoch in range(epochs):
+    for epoch in range(start_epoch, epochs):
         metric = DiffusionLossMetric()  # (diffusion_loss.py:52-65; the reference logs it per epoch with sync_dist)
         step_losses = []                # device scalars: read back once per epoch, not per step (no host sync in the loop)
+        first = start_batch if epoch == start_epoch else 0
+        keyed = dict(noise="philox", seed=epoch_noise_seed(seed, epoch)) if noise == "philox" else {}
         for step, batch in enumerate(iterate_batches(dataset, batch_size, shuffle=True, seed=seed + epoch, rank=rank,
-                                                     world_size=world_size, drop_last=True)):
-            loss = model.training_step(batch)
+                                                     world_size=world_size, drop_last=True, start=first), first):
+            loss = model.training_step(batch, **keyed)
             optimizer_step(model, optimizer, world_size)
+            global_step += 1
             step_losses.append(loss.detach())
             metric.update(loss, batch)
+            if on_step is not None:
+                on_step(epoch, step + 1, global_step)
         scheduler.step()
         if step_losses:
             losses += [float(v) for v in torch.stack(step_losses).cpu()]
@@ -134,7 +160,132 @@ def train_epochs(model, dataset, epochs: int, batch_size: int, rank: int = 0, wo
         if rank == 0:
             log(f"epoch {epoch}: {len(step_losses)} steps, loss per crystal {mean:.5f} (all ranks), last loss "
                 f"{losses[-1] if losses else float('nan'):.5f}, lr {scheduler.get_last_lr()[0]:.3e}")
+        if on_epoch is not None:
+            on_epoch(epoch, global_step)
     return losses
+
+
+# the arguments of a run that must agree when it is resumed (checkpoint.save_training_checkpoint's run_args)
+MODEL_ARGS = ("hidden_dim", "basis_dim", "layers", "widening_factor", "num_timesteps", "radius", "max_neighbors", "lr", "warmup",
+              "weight_decay", "seed", "ema_decay", "ema_every_n_steps")
+
+
+def run_arguments(args, world_size, train_len, val_len):
+    """What a training checkpoint records of the run, and check_resume compares."""
+    return {"world_size": int(world_size), "batch_size": int(args.batch_size), "noise": str(args.noise),
+            "dataset_lengths": [int(train_len), int(val_len)], "model": {k: getattr(args, k) for k in MODEL_ARGS}}
+
+
+def check_resume(state, run_args):
+    """Reject, before any work, a resume the checkpoint's run does not continue: `state` is load_training_state's dict (ValueError
+    there for a file without training state), `run_args` the present run's run_arguments."""
+    saved = state.get("run_args") or {}
+    for key, what in (("world_size", "world size"), ("batch_size", "batch size"), ("noise", "noise mode"),
+                      ("dataset_lengths", "dataset lengths (training, validation)"), ("model", "model arguments")):
+        if saved.get(key) != run_args[key]:
+            raise ValueError(f"--resume: the checkpoint was written by a run with another {what}: {saved.get(key)!r}, now "
+                             f"{run_args[key]!r}")
+
+
+def rebuild_engine(model):
+    """Drop the module's HIP engine and pack a fresh one from the parameters as they are -- what a run resumed from a checkpoint
+    written now starts with.  An engine that has lived through optimizer steps is not that engine bit for bit (it chose its operand
+    bounds when it was created, from the weights of that time), so the driver calls this on every rank wherever a training checkpoint
+    is written: the run that goes on and the run that is resumed from the file are then the same computation."""
+    model._engine = None
+    model._drop_transient()
+    eng = model.engine(for_training=True)
+    if getattr(model, "_train_full_range", False):  # the run had left the fp16x3 forward products for the full-range ones
+        eng.set_variant(3 if eng.fused_shape else -1, 1)
+    return eng
+
+
+class TrainingRun:
+    """The driver's validation, checkpoints and best-so-far bookkeeping, as the two callbacks of train_epochs."""
+
+    def __init__(self, model, optimizer, scheduler, args, run_args, rank, world_size, val_set=None, best_val_loss=None, log=print):
+        self.model, self.optimizer, self.scheduler, self.args, self.run_args = model, optimizer, scheduler, args, run_args
+        self.rank, self.world_size, self.val_set, self.best, self.log = rank, world_size, val_set, best_val_loss, log
+        self.written = []
+        if args.checkpoint_dir and rank == 0:
+            os.makedirs(args.checkpoint_dir, exist_ok=True)
+
+    def _rng_states(self):
+        mine = torch.random.get_rng_state()
+        if self.world_size <= 1:
+            return [mine]
+        import torch.distributed as dist
+        states = [None] * self.world_size
+        dist.all_gather_object(states, mine)
+        return states
+
+    def checkpoint(self, name, epoch, global_step, epochs_completed, batch_position):
+        """every rank takes part (the generator states are gathered); rank 0 writes"""
+        from .checkpoint import save_training_checkpoint
+        states = self._rng_states()
+        path = None
+        if self.rank == 0:
+            path = os.path.join(self.args.checkpoint_dir, name)
+            save_training_checkpoint(path, self.model, self.optimizer, self.scheduler, epoch, global_step, batch_position,
+                                     self.run_args, self.best, states, epochs_completed)
+            self.written.append(path)
+            self.log("wrote", path)
+        rebuild_engine(self.model)  # every rank: what a resumed run starts with
+        return path
+
+    def on_step(self, epoch, batches_done, global_step):
+        n = self.args.checkpoint_every_n_steps
+        if self.args.checkpoint_dir and n and global_step % n == 0:
+            self.checkpoint(f"epoch={epoch}-step={global_step}.ckpt", epoch, global_step, epoch, batches_done)
+
+    def validate(self, epoch):
+        a = self.args
+        ev = dict(batch_size=a.batch_size, seed=a.val_seed, copies=a.val_copies, rank=self.rank, world_size=self.world_size)
+        res = {"epoch": epoch, "weights": self.model.evaluate(self.val_set, **ev)}
+        decides = res["weights"]
+        if a.ema_decay is not None and len(self.optimizer.ema_params):
+            with self.optimizer.swap_ema_weights():
+                res["ema"] = decides = self.model.evaluate(self.val_set, **ev)
+        if self.world_size > 1:  # every rank ran the one reduction on the summed table: the totals are the same bits
+            import torch.distributed as dist
+            totals = [None] * self.world_size
+            dist.all_gather_object(totals, [res[k]["loss"] for k in sorted(res) if k != "epoch"])
+            if any(t != totals[0] for t in totals):
+                raise SystemExit(f"rank {self.rank}: the ranks hold different validation totals: {totals}")
+        if self.rank == 0:
+            for name in ("weights", "ema"):
+                if name in res:
+                    r = res[name]
+                    self.log(f"epoch {epoch}: valid loss{' (EMA)' if name == 'ema' else ''} {r['loss']:.9g} (coordinates "
+                             f"{r['error_frac_x']:.6g}, species {r['error_atomic_type']:.6g}, lattice {r['error_lattice']:.6g}; "
+                             f"{r['num_crystals']} crystal-copies" + (f", the same on all {self.world_size} ranks)" if self.world_size > 1 else ")"))
+        return res, decides["loss"]
+
+    def on_epoch(self, epoch, global_step):
+        import json
+        a = self.args
+        improved, res = False, None
+        if self.val_set is not None and (epoch + 1) % a.val_interval == 0:
+            res, loss = self.validate(epoch)
+            improved = self.best is None or loss < self.best
+            if improved:
+                self.best = loss
+        n = a.checkpoint_every_n_epochs
+        path = None
+        if a.checkpoint_dir and n and (epoch + 1) % n == 0:
+            path = self.checkpoint(f"epoch={epoch}.ckpt", epoch, global_step, epoch + 1, 0)
+        if a.checkpoint_dir and res is not None and self.rank == 0:
+            table = os.path.splitext(path)[0] + ".json" if path else os.path.join(a.checkpoint_dir, f"epoch={epoch}.json")
+            with open(table, "w") as fh:
+                json.dump(res, fh, indent=1)
+        if a.checkpoint_dir and a.keep_best and improved:
+            best = self.checkpoint("best.ckpt", epoch, global_step, epoch + 1, 0)
+            if self.rank == 0:
+                with open(os.path.join(a.checkpoint_dir, "best.json"), "w") as fh:
+                    json.dump(res, fh, indent=1)
+                if a.ema_decay is not None:
+                    from .checkpoint import save_ema_checkpoint
+                    self.log("wrote", save_ema_checkpoint(best, self.model, self.optimizer))
 
 
 def main():
@@ -159,7 +310,39 @@ def main():
     ap.add_argument("--ema_decay", type=float, default=None,
                     help="keep an exponential moving average of the weights with this decay; --out then also writes X-EMA.ckpt")
     ap.add_argument("--ema_every_n_steps", type=int, default=1, help="update the average every N optimizer steps")
+    # training runs: validation, checkpoints, resume
+    ap.add_argument("--val_data", nargs="*", default=None, help="validation set files (lattice_dataset layout)")
+    ap.add_argument("--val_fraction", type=float, default=None,
+                    help="hold this fraction of the data out for validation (a split by index seeded with --seed: the same on every "
+                         "rank and in every run)")
+    ap.add_argument("--val_interval", type=int, default=5, help="validate every E epochs (the reference's default)")
+    ap.add_argument("--val_copies", type=int, default=4, help="noisings per validation crystal, at stratified timesteps")
+    ap.add_argument("--val_seed", type=int, default=0, help="seed of the validation noise")
+    ap.add_argument("--noise", choices=("host", "philox"), default="host",
+                    help="training-step draws: torch's CPU generator, or keyed Philox draws in the kernels under the seed "
+                         "seed + epoch * 0x9E3779B97F4A7C15 mod 2^64")
+    ap.add_argument("--checkpoint_dir", type=str, default=None, help="where training checkpoints go")
+    ap.add_argument("--checkpoint_every_n_epochs", type=int, default=1, help="with --checkpoint_dir: a checkpoint every N epochs (0: none)")
+    ap.add_argument("--checkpoint_every_n_steps", type=int, default=0, help="with --checkpoint_dir: a checkpoint every N optimizer steps (0: none)")
+    ap.add_argument("--keep_best", action="store_true",
+                    help="with --checkpoint_dir and a validation set: best.ckpt (and best-EMA.ckpt with --ema_decay) whenever the "
+                         "validation loss improves; with --ema_decay the average decides")
+    ap.add_argument("--resume", type=str, default=None, help="continue from this training checkpoint")
     args = ap.parse_args()
+    if args.val_data and args.val_fraction is not None:
+        ap.error("give --val_data or --val_fraction, not both")
+    if args.val_interval < 1 or args.val_copies < 1 or args.checkpoint_every_n_epochs < 0 or args.checkpoint_every_n_steps < 0:
+        ap.error("--val_interval and --val_copies must be at least 1, the checkpoint cadences at least 0")
+    if args.keep_best and not (args.checkpoint_dir and (args.val_data or args.val_fraction is not None)):
+        ap.error("--keep_best needs --checkpoint_dir and a validation set")
+    resumed = None
+    if args.resume:  # rejected before any work: a file without training state
+        from .checkpoint import load_lightning_checkpoint, load_training_state
+        resumed = load_lightning_checkpoint(args.resume)
+        try:
+            load_training_state(resumed, restore_rng=False)
+        except ValueError as e:
+            ap.error(f"--resume {args.resume}: {e}")
     if args.ema_decay is not None and not 0.0 <= args.ema_decay <= 1.0:
         ap.error("--ema_decay must lie in [0, 1]")
     if args.ema_every_n_steps < 1:
@@ -168,6 +351,28 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if os.environ.get("ARREAU_TRAIN_ONE_DEVICE", "0") == "1":
         local_rank = 0
+    from .checkpoint import default_args, save_ema_checkpoint, save_lightning_checkpoint
+    from .diffusion.lattice_dataset import CrystalDataset, synthetic_alexandria_like
+    from .lightning_wrappers.diffusion import PONITA_DIFFUSION
+    ds = CrystalDataset(args.data) if args.data else CrystalDataset(configs=synthetic_alexandria_like(args.num_synthetic, args.seed))
+    train_set, val_set = ds, None
+    if args.val_fraction is not None:
+        from .diffusion.lattice_dataset import Subset, split_indices
+        train_idx, val_idx = split_indices(len(ds), args.val_fraction, args.seed)
+        train_set, val_set = Subset(ds, train_idx), Subset(ds, val_idx)
+    elif args.val_data:
+        val_set = CrystalDataset(args.val_data)
+        if not val_set.unique_atomic_numbers <= ds.unique_atomic_numbers:
+            raise SystemExit("--val_data holds elements the training data does not")
+        val_set.z_table = ds.z_table  # one class table: the model's
+    run_args = run_arguments(args, world, len(train_set), len(val_set) if val_set is not None else 0)
+    state = None
+    if resumed is not None:  # rejected before any work: a run the checkpoint does not continue
+        state = load_training_state(resumed, restore_rng=False)
+        try:
+            check_resume(state, run_args)
+        except ValueError as e:
+            raise SystemExit(str(e))
     torch.cuda.set_device(local_rank)
     if world > 1:
         import torch.distributed as dist
@@ -177,10 +382,6 @@ def main():
             dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
         else:
             dist.init_process_group(backend)
-    from .checkpoint import default_args, save_ema_checkpoint, save_lightning_checkpoint
-    from .diffusion.lattice_dataset import CrystalDataset, synthetic_alexandria_like
-    from .lightning_wrappers.diffusion import PONITA_DIFFUSION
-    ds = CrystalDataset(args.data) if args.data else CrystalDataset(configs=synthetic_alexandria_like(args.num_synthetic, args.seed))
     torch.manual_seed(args.seed)  # same initial weights on every rank
     net_args = default_args(lr=args.lr, epochs=args.epochs, hidden_dim=args.hidden_dim, basis_dim=args.basis_dim,
                             layers=args.layers, widening_factor=args.widening_factor, num_timesteps=args.num_timesteps,
@@ -189,7 +390,22 @@ def main():
     model = PONITA_DIFFUSION(net_args, ds.z_table).to(f"cuda:{local_rank}")
     torch.manual_seed(args.seed + 1000 + rank)  # different noise per rank
     optimizer, scheduler = configure_training(model, args.epochs, args.ema_decay, args.ema_every_n_steps)
-    train_epochs(model, ds, args.epochs, args.batch_size, rank, world, args.seed, optimizer=optimizer, scheduler=scheduler)
+    run = None
+    if resumed is not None or val_set is not None or args.checkpoint_dir:
+        where = dict(start_epoch=0, start_batch=0, global_step=0)
+        if resumed is not None:
+            state = load_training_state(resumed, model, optimizer, scheduler, rank=rank)
+            where = dict(start_epoch=state["epochs_completed"], start_batch=state["batch_position"], global_step=state["global_step"])
+            rebuild_engine(model)
+            if rank == 0:
+                print(f"resumed {args.resume}: epoch {where['start_epoch']}, batch {where['start_batch']}, step {where['global_step']}")
+        run = TrainingRun(model, optimizer, scheduler, args, run_args, rank, world, val_set,
+                          state["best_val_loss"] if state is not None else None)
+        train_epochs(model, train_set, args.epochs, args.batch_size, rank, world, args.seed, optimizer=optimizer, scheduler=scheduler,
+                     noise=args.noise, on_step=run.on_step, on_epoch=run.on_epoch, **where)
+    else:
+        train_epochs(model, ds, args.epochs, args.batch_size, rank, world, args.seed, optimizer=optimizer, scheduler=scheduler,
+                     noise=args.noise)
     # data-parallel invariant: the replicas hold the same weights (same initial weights, same averaged gradients, ONE set
     # of calibration ratios); a drift here means a rank applied something its peers did not.  Each rank keeps its own average
     # of the weights (no collective): the averages of identical weights agree too.
@@ -211,6 +427,8 @@ def main():
                 print(f"replica {what} checksums:", " ".join(f"{v:.12e}" for v in vals))
             if max(vals) - min(vals) > 1e-9 * max(1.0, abs(vals[0])):
                 raise SystemExit(f"rank {rank}: data-parallel replicas diverged ({what}): {vals}")
+        elif run is not None:  # a training run: the line two runs that should agree are compared by
+            print(f"final {what} checksum: {float(check):.17e}")
     if rank == 0 and args.out:
         print("wrote", save_lightning_checkpoint(args.out, model))
         if args.ema_decay is not None:

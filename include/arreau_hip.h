@@ -1346,6 +1346,74 @@ int arreau_diffusion_losses(const arreau_model* model, const float* d_pred_eps, 
                             float* d_losses, float* d_grad_eps, float* d_grad_logits, float* d_grad_lengths,
                             void* stream);
 
+/* ---- training runs: keyed forward noising, per-crystal loss rows, their binned reduction ------------------------ */
+
+/* arreau_diffusion_noise with its draws made inside the kernels, keyed by the CRYSTAL and not by its place in the batch:
+ * Philox4x32-10, counter = (element, t, kind, crystal id), key = the 64-bit seed.  Draw kinds (after the sampler's 0..8):
+ *    9  the timestep uniform   element 0, counter timestep 0
+ *   10  z_frac    (normal)     element 3 a + d, a the atom's index WITHIN its crystal
+ *   11  u_types   (uniform)    element a S + s
+ *   12  z_lengths (normal)     element d
+ * normals and uniforms formed from the words as the sampler forms them (Box-Muller of words 0 and 1; 24 bits of word 0).
+ *   1. d_crystal_ids[B]: int64, each below 2^32 (the low 32 bits are the counter word; a caller that holds the ids on the host
+ *      rejects larger ones).  copies = R >= 1 copies of every crystal may be noised; d_copy[B] (NULL: all 0) says which copy a
+ *      row is.  R > T: ARREAU_EINVAL before any work.  A copy outside 0..R-1 is clamped and sets ARREAU_STATUS_BAD_TIMESTEP.
+ *   2. the timestep of a row, in integers so that it can be restated exactly: with u24 the top 24 bits of word 0 of the kind-9
+ *      draw,   t = 1 + ((copy * 2^24 + u24) * T) / (R * 2^24)   (64-bit integer division).
+ *      R = 1 is a uniform draw over 1..T; R > 1 gives each copy of a crystal its own stratum of 1..T, so its copies never
+ *      share a timestep.  The kernel writes d_t[B].  given_timesteps != 0: d_t is the caller's and kind 9 is not drawn.
+ *      arreau_keyed_timestep is the rule on the host (u24 < 2^24, 0 <= copy < R <= T, else ARREAU_EINVAL).
+ *   3. everything after the draws is arreau_diffusion_noise's arithmetic, order and status flags (the same kernels, the draw
+ *      source a template argument).  Hence: fed the same numbers as arrays -- arreau_philox_fill_keyed(seed, t_b, kind, id_b)
+ *      per crystal -- arreau_diffusion_noise gives the same bits; and a crystal's noised state is a function of
+ *      (seed, id, copy, R) alone, whatever the batch around it, its place in it, or the launch geometry.
+ * arreau_philox_fill_keyed: d_out[i] = the draw (i, timestep, kind, crystal id) of kinds 9..12 (other kinds: ARREAU_EINVAL;
+ * arreau_philox_fill_word keeps its kinds 0..8); d_raw as in arreau_philox_fill. */
+int arreau_diffusion_noise_keyed(const arreau_model* model, const float* d_frac0, const int32_t* d_types0,
+                                 const float* d_lattice0, const int32_t* d_crystal_offsets, int32_t B, int32_t N,
+                                 uint64_t seed, const int64_t* d_crystal_ids, int32_t copies, const int32_t* d_copy,
+                                 int32_t given_timesteps, int32_t* d_t, float* d_noisy_frac, float* d_target_eps,
+                                 int32_t* d_noisy_types, float* d_noisy_lengths, float* d_lengths, float* d_angles,
+                                 float* d_inv_lattice, void* stream);
+int arreau_philox_fill_keyed(uint64_t seed, int32_t timestep, int32_t kind, uint32_t crystal_id, int64_t n, float* d_out,
+                             uint32_t* d_raw, void* stream);
+int arreau_keyed_timestep(uint32_t u24, int32_t copy, int32_t copies, int32_t T, int32_t* t_out);
+
+/* One crystal's share of the loss, as SUMS (not means), so that any aggregate can be formed from rows: the reference's batch
+ * loss is (sum coord + 0.001 sum vb + sum ce) / N + sum lattice / (3 B) over the rows of a batch. */
+typedef struct {
+    float coord;        /* sum over the crystal's atoms of d_terms[.][0] (wrapped coordinate error) */
+    float vb;           /* ... of d_terms[.][1] */
+    float ce;           /* ... of d_terms[.][2] */
+    float lattice;      /* sum over the three axes of (pred_length - length / num_atoms)^2 */
+    int32_t num_atoms;  /* > 0 in a written row: 0 marks a row no crystal was written to */
+    int32_t timestep;
+} arreau_loss_row;
+
+/* arreau_diffusion_losses on the same inputs, writing everything it writes (the same two launches: the same bits in d_losses,
+ * d_terms and the gradients), plus, in a third launch, for every crystal b the row d_rows[d_row_index[b]] of a caller-owned table
+ * of n_rows rows (int64 indices; one outside 0..n_rows-1 writes nothing and sets ARREAU_STATUS_BAD_TIMESTEP).
+ * The in-crystal sums have ONE order, which depends on the crystal's atom count alone, not on the batch or the launch geometry:
+ * one wave of 64 lanes per crystal; lane l adds the terms of atoms l, l + 64, l + 128, ... of the crystal in ascending order
+ * (starting from 0.0f), then the 64 lane sums are combined by the xor butterfly with partner distances 32, 16, 8, 4, 2, 1.  The
+ * lattice sum is (e_0 + e_1) + e_2 with e_d = d * d rounded to fp32 on its own.  No float atomics. */
+int arreau_diffusion_loss_rows(const arreau_model* model, const float* d_pred_eps, const float* d_target_eps,
+                               const float* d_logits, const int32_t* d_types0, const int32_t* d_noisy_types,
+                               const int32_t* d_t, const float* d_pred_lengths, const float* d_lengths,
+                               const int32_t* d_crystal_offsets, int32_t B, int32_t N, float* d_terms, float* d_losses,
+                               float* d_grad_eps, float* d_grad_logits, float* d_grad_lengths, const int64_t* d_row_index,
+                               arreau_loss_row* d_rows, int64_t n_rows, void* stream);
+
+/* One launch sums the n_rows rows of a table into n_bins + 1 records: record q < n_bins takes the rows of timestep bin
+ * q = (t - 1) * n_bins / T (integer division; t clamped to 1..T), record n_bins every written row.
+ *   d_sums[n_bins + 1][4]     float64 sums of coord, vb, ce, lattice;
+ *   d_counts[n_bins + 1][2]   int64 atom count and crystal count, followed by ONE more int64, d_counts[2 (n_bins + 1)]: the number
+ *                             of unwritten rows (num_atoms <= 0), which are skipped -- how a rank's partial table is recognised.
+ * Fixed order, float64: one workgroup of 256 threads per record; thread k adds its rows k, k + 256, ... in row order, then the 256
+ * partials meet in the tree with strides 128, 64, ..., 1.  Two launches on one table give the same bits.  1 <= n_bins <= 1024. */
+int arreau_loss_rows_reduce(const arreau_loss_row* d_rows, int64_t n_rows, int32_t n_bins, int32_t T, double* d_sums,
+                            int64_t* d_counts, void* stream);
+
 /* Training-mode evaluation of the score network on a (noised) batch -- same inputs and outputs as
  * arreau_predict_scores, fp32 throughout, every layer's activations kept for the backward pass (the sampling kernels
  * keep none).  PonitaFiberBundle.forward in train mode (ponita/models/ponita.py:88-123). */
