@@ -38,6 +38,7 @@ EXPORTS = [
     "arreau_sample_loop_species", "arreau_reverse_step_species",
     "arreau_diffusion_noise_keyed", "arreau_philox_fill_keyed", "arreau_keyed_timestep", "arreau_diffusion_loss_rows",
     "arreau_loss_rows_reduce",
+    "arreau_sample_loop_keyed", "arreau_noise_state_keyed", "arreau_condition_initial_state_keyed", "arreau_philox_fill_crystals",
 ]
 
 STATUS_NONFINITE, STATUS_BAD_TIMESTEP, STATUS_BAD_TYPE, STATUS_BAD_TIE, STATUS_BAD_SYMMETRY = 1, 2, 4, 8, 16
@@ -235,6 +236,10 @@ def _prototypes():
         "arreau_sample_loop_multistep": loop + [cond, sched, corr, res, vp, ms, vp],
         "arreau_reverse_step_multistep": step_to + [vp, ms, vp],
         "arreau_sample_loop_species": loop + [cond, sched, corr, res, vp, sym, f32p, ms, spec, vp],
+        "arreau_sample_loop_keyed": loop + [cond, sched, corr, res, vp, sym, f32p, ms, spec, vp, vp],
+        "arreau_noise_state_keyed": [vp] * 6 + [i32, i32, i32, u64] + [vp] * 6,
+        "arreau_condition_initial_state_keyed": [vp] * 5 + [i32, i32, i32, u64, cond, vp, vp],
+        "arreau_philox_fill_crystals": [vp, vp, i32, i32, i32, u32, i32, i32, vp, vp, vp],
         "arreau_reverse_step_species": step_to + [vp, sym, f32p, ms, spec, vp],
         "arreau_condition_initial_state": [vp] * 4 + [i32, i32, i32, u64, cond, vp],
         "arreau_reverse_step_to": step_to + [vp],

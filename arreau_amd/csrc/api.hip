@@ -326,7 +326,8 @@ int enqueue_sample_step(const arreau_model* m, const ScorePlan& plan, const Samp
         if (j < opt.corr.steps && (rc = arreau_launch_corrector(m, st, w.t_cur, w.eps, nullptr, seed, (uint32_t)j, opt, s))) return rc;
     }
     // without a prep launch per step (fused kernels only) the update also leaves the next step's lattice and embedding behind
-    ReverseInputs in{w.t_cur, w.eps, w.logits, w.len0, StepNoiseSrc{.seed = seed}, pool_in_update ? w.gs : nullptr, w.batch};
+    ReverseInputs in{w.t_cur, w.eps, w.logits, w.len0, StepNoiseSrc{.seed = seed, .seeds = opt.crystal_seeds}, pool_in_update ? w.gs : nullptr,
+                     w.batch};
     if (plan.no_prep) {
         in.lattice_ws = w.lattice;
         in.cvec_next = w.cvec;
@@ -348,7 +349,7 @@ struct ResamplePlan {
 // The key of a captured step: the buffers, sizes and seed, the plan (every kernel choice of the evaluation), and the condition's
 // pointers, the schedule's table and clip, the corrector's step count and snr, the resampling's R and J (a resampled step reads
 // the pass word), the lattice systems' tie array, the symmetry tables, the eta of a DDIM-style step, the history buffers of a
-// multistep step and the admission rows and temperature of species control, which are kernel arguments
+// multistep step, the admission rows and temperature of species control and the table of stream seeds of a keyed loop, which are kernel arguments
 // or launch choices of the capture: a change of any of them must not replay the stale graph.  So is the direction: an inversion
 // loop (arreau_invert_loop) on the same buffers, table pointer included, captures other kernels than a sampling loop.
 SampleGraphKey sample_graph_key(const ScorePlan& score, const SampleState& st, const void* d_workspace, uint64_t seed,
@@ -380,6 +381,7 @@ SampleGraphKey sample_graph_key(const ScorePlan& score, const SampleState& st, c
         k.species_allow = opt.species->d_allow;
         k.species_tau_bits = std::bit_cast<uint32_t>(opt.species->temperature);
     }
+    k.crystal_seeds = opt.crystal_seeds;
     return k;
 }
 
@@ -390,7 +392,8 @@ int sample_loop_impl(arreau_model* m, const SampleState& st, int32_t t_start, in
                      const arreau_symmetry* sym /* null: no symmetry */, float eta /* negative: the ancestral step */, void* stream,
                      bool invert = false /* DDIM inversion: t_start is the first level, `schedule` the ascending table; no other option */,
                      const arreau_multistep* ms = nullptr /* second-order multistep: the history buffers; eta is then 0 */,
-                     const arreau_species_control* species = nullptr /* species control (checked by the export) */) {
+                     const arreau_species_control* species = nullptr /* species control (checked by the export) */,
+                     const uint64_t* crystal_seeds = nullptr /* keyed sampling: the stream seed of every crystal */) {
     if (corrector) {
         const int rc = arreau_corrector_check(corrector->steps, corrector->snr, "arreau_sample_loop_corrected");
         if (rc) return rc;
@@ -432,6 +435,7 @@ int sample_loop_impl(arreau_model* m, const SampleState& st, int32_t t_start, in
     opt.invert = invert;
     opt.ms = ms;
     opt.species = species;
+    opt.crystal_seeds = crystal_seeds;
     ARREAU_REQUIRE(!ms || (!opt.cond && opt.corr.steps == 0 && !plan && !sym && !invert && eta == 0.0f),
                    "arreau_sample_loop_multistep: a multistep loop takes no condition, corrector steps, resampling or symmetry");
     ARREAU_REQUIRE(!invert || (schedule && !opt.cond && opt.corr.steps == 0 && !plan && !d_length_tie && !sym && eta < 0.0f),
@@ -532,7 +536,8 @@ int sample_loop_impl(arreau_model* m, const SampleState& st, int32_t t_start, in
         for (const ResampleBlock& bl : plan->blocks) {
             for (int r = 0; r < plan->passes; ++r) {
                 if (r > 0 && (rc = arreau_launch_resample_jump(m, st, /*d_s=*/nullptr, /*d_t=*/nullptr, bl.bottom, bl.top, w.batch,
-                                                               StepNoiseSrc{.seed = seed}, (uint32_t)r, opt.cond, &loop, d_length_tie, s)))
+                                                               StepNoiseSrc{.seed = seed, .seeds = crystal_seeds}, (uint32_t)r, opt.cond, &loop,
+                                                               d_length_tie, s)))
                     return rc;
                 for (int i = 0; i < bl.count; ++i)
                     if ((rc = run_step())) return rc;
@@ -553,7 +558,8 @@ int sample_loop(const char* who, arreau_model* m, const SampleState& st, int32_t
                 const arreau_sample_condition* condition = nullptr, const arreau_sample_schedule* schedule = nullptr,
                 const arreau_corrector* corrector = nullptr, const arreau_resampling* resampling = nullptr,
                 const int32_t* d_length_tie = nullptr, const arreau_symmetry* sym = nullptr, float eta = -1.0f,
-                const arreau_multistep* ms = nullptr, const arreau_species_control* species = nullptr) {
+                const arreau_multistep* ms = nullptr, const arreau_species_control* species = nullptr,
+                const uint64_t* crystal_seeds = nullptr) {
     ResamplePlan plan{1, 1, {}};
     if (resampling) {
         int rc;
@@ -587,7 +593,7 @@ int sample_loop(const char* who, arreau_model* m, const SampleState& st, int32_t
         }
     }
     return sample_loop_impl(m, st, t_start, n_steps, seed, d_workspace, workspace_bytes, use_graph, condition, schedule, corrector,
-                            plan.passes > 1 ? &plan : nullptr, d_length_tie, sym, eta, stream, /*invert=*/false, ms, species);
+                            plan.passes > 1 ? &plan : nullptr, d_length_tie, sym, eta, stream, /*invert=*/false, ms, species, crystal_seeds);
 }
 }  // namespace
 
@@ -693,15 +699,14 @@ extern "C" int arreau_sample_loop_multistep(arreau_model* m, float* d_frac, int3
 // Species control (rules in include/arreau_hip.h): whichever of the loops above the options name, its steps the SPEC instances.
 // The checks of arreau_sample_loop_sym / _eta / _multistep run first, under this export's name; what the loops do not combine is
 // rejected by them as before.
-extern "C" int arreau_sample_loop_species(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
-                                          const int32_t* d_off, int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed,
-                                          const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice,
-                                          void* d_workspace, size_t workspace_bytes, int32_t use_graph,
-                                          const arreau_sample_condition* condition, const arreau_sample_schedule* schedule,
-                                          const arreau_corrector* corrector, const arreau_resampling* resampling,
-                                          const int32_t* d_length_tie, const arreau_symmetry* symmetry, const float* eta,
-                                          const arreau_multistep* multistep, const arreau_species_control* species, void* stream) {
-    const char* who = "arreau_sample_loop_species";
+static int sample_loop_species(const char* who, arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                               const int32_t* d_off, int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed,
+                               const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice, void* d_workspace,
+                               size_t workspace_bytes, int32_t use_graph, const arreau_sample_condition* condition,
+                               const arreau_sample_schedule* schedule, const arreau_corrector* corrector,
+                               const arreau_resampling* resampling, const int32_t* d_length_tie, const arreau_symmetry* symmetry,
+                               const float* eta, const arreau_multistep* multistep, const arreau_species_control* species,
+                               const uint64_t* d_crystal_seeds, void* stream) {
     int rc;
     arreau_species_control sp;
     if ((rc = arreau_species_check(species, who, &sp))) return rc;
@@ -725,7 +730,36 @@ extern "C" int arreau_sample_loop_species(arreau_model* m, float* d_frac, int32_
     const float e = multistep ? 0.0f : (eta ? *eta + 0.0f /* -0 -> +0 */ : -1.0f);
     const SampleState st{d_frac, d_types, d_lengths, d_angles, d_off, B, N, d_const_types, d_fixed_lengths, d_lattice};
     return sample_loop(who, m, st, t_start, n_steps, seed, d_workspace, workspace_bytes, use_graph, stream, condition, schedule, corrector,
-                       resampling, d_length_tie, symmetry, e, multistep, &sp);
+                       resampling, d_length_tie, symmetry, e, multistep, &sp, d_crystal_seeds);
+}
+
+extern "C" int arreau_sample_loop_species(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                                          const int32_t* d_off, int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed,
+                                          const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice,
+                                          void* d_workspace, size_t workspace_bytes, int32_t use_graph,
+                                          const arreau_sample_condition* condition, const arreau_sample_schedule* schedule,
+                                          const arreau_corrector* corrector, const arreau_resampling* resampling,
+                                          const int32_t* d_length_tie, const arreau_symmetry* symmetry, const float* eta,
+                                          const arreau_multistep* multistep, const arreau_species_control* species, void* stream) {
+    return sample_loop_species("arreau_sample_loop_species", m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, t_start, n_steps, seed,
+                               d_const_types, d_fixed_lengths, d_lattice, d_workspace, workspace_bytes, use_graph, condition, schedule,
+                               corrector, resampling, d_length_tie, symmetry, eta, multistep, species, nullptr, stream);
+}
+
+// Keyed sampling (rules in include/arreau_hip.h): arreau_sample_loop_species with the table of stream seeds, which every draw of
+// the loop -- steps, corrector moves, jumps -- is keyed by; a NULL table is arreau_sample_loop_species bit for bit.  The same
+// checks under this export's name; what that loop rejects stays rejected.
+extern "C" int arreau_sample_loop_keyed(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                                        const int32_t* d_off, int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed,
+                                        const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice, void* d_workspace,
+                                        size_t workspace_bytes, int32_t use_graph, const arreau_sample_condition* condition,
+                                        const arreau_sample_schedule* schedule, const arreau_corrector* corrector,
+                                        const arreau_resampling* resampling, const int32_t* d_length_tie, const arreau_symmetry* symmetry,
+                                        const float* eta, const arreau_multistep* multistep, const arreau_species_control* species,
+                                        const uint64_t* d_crystal_seeds, void* stream) {
+    return sample_loop_species("arreau_sample_loop_keyed", m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, t_start, n_steps, seed,
+                               d_const_types, d_fixed_lengths, d_lattice, d_workspace, workspace_bytes, use_graph, condition, schedule,
+                               corrector, resampling, d_length_tie, symmetry, eta, multistep, species, d_crystal_seeds, stream);
 }
 
 // DDIM inversion (rules in include/arreau_hip.h): the sampling loop climbing the levels of an ascending table, every step the

@@ -23,7 +23,8 @@ __global__ __launch_bounds__(CORR_THREADS) void corrector_kernel(float* __restri
                                                                  uint64_t seed, uint32_t iter, float snr,
                                                                  const float* __restrict__ ve_sigmas,
                                                                  const uint8_t* __restrict__ pos_mask, int32_t* __restrict__ status,
-                                                                 const int32_t* __restrict__ pass) {
+                                                                 const int32_t* __restrict__ pass,
+                                                                 const uint64_t* __restrict__ seeds /* keyed sampling, or null */) {
     if constexpr (RESAMPLE) iter += 256u * (uint32_t)pass[0];  // the counter word of pass r
     __shared__ float part[2][CORR_THREADS / 64];
     const int b = blockIdx.x;
@@ -35,8 +36,12 @@ __global__ __launch_bounds__(CORR_THREADS) void corrector_kernel(float* __restri
     const int n3 = 3 * (last - first);
     // (the array-or-generator choice is made on the kernel argument itself, as in reverse_one_atom)
     const bool have_z = z_frac != nullptr;
+    // keyed sampling (rules in include/arreau_hip.h): the crystal's stream seed, elements counted from its first component
+    const bool keyed = seeds != nullptr;  // (kernel argument: uniform)
+    const uint64_t dseed = keyed ? seeds[b] : seed;
+    const uint32_t e0 = keyed ? 0u : (uint32_t)g0;
     auto draw_z = [&](size_t g) {
-        return have_z ? z_frac[g] : philox_normal(seed, (uint32_t)t, ARREAU_DRAW_Z_CORRECTOR, (uint32_t)g, iter);
+        return have_z ? z_frac[g] : philox_normal(dseed, (uint32_t)t, ARREAU_DRAW_Z_CORRECTOR, e0 + (uint32_t)(g - g0), iter);
     };
     float ee = 0.0f, zz = 0.0f;
     for (int c = threadIdx.x; c < n3; c += CORR_THREADS) {
@@ -95,7 +100,7 @@ int arreau_launch_corrector(const arreau_model* m, const SampleState& st, const 
     auto kernel = mask ? (opt.pass ? corrector_kernel<true, true> : corrector_kernel<true, false>)
                        : (opt.pass ? corrector_kernel<false, true> : corrector_kernel<false, false>);
     ARREAU_LAUNCH(kernel, dim3(st.B), dim3(CORR_THREADS), 0, s, st.frac, d_t, st.offsets, m->T, d_eps, d_z_frac, seed, iter, opt.corr.snr,
-                  m->ve_sigmas, mask, m->status, opt.pass);
+                  m->ve_sigmas, mask, m->status, opt.pass, opt.crystal_seeds);
     ARREAU_CHECK_HIP(hipGetLastError());
     return ARREAU_OK;
 }

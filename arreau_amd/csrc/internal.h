@@ -116,6 +116,7 @@ struct SampleGraphKey {
     int32_t species;           // species control: 1 when the steps take it
     const uint32_t* species_allow;  // its admission rows (null: every class)
     uint32_t species_tau_bits;      // its temperature
+    const uint64_t* crystal_seeds;  // keyed sampling: the table of stream seeds (null: not keyed)
     bool operator==(const SampleGraphKey&) const = default;
 };
 
@@ -290,6 +291,9 @@ struct StepNoiseSrc {
     const float* z_frac;     // [N,3]  or null
     const float* u_types;    // [N,S]  or null
     uint64_t seed;           // used when the arrays are null
+    // keyed sampling (arreau_sample_loop_keyed; rules in include/arreau_hip.h): the stream seed of every crystal [B], or null.  With
+    // it a draw of crystal b takes seeds[b] for `seed` and counts its element within the crystal; without it nothing changes.
+    const uint64_t* seeds;
 };
 
 inline bool arreau_condition_empty(const SampleConditionDev* c) {
@@ -332,6 +336,7 @@ struct StepOptions {
     const arreau_multistep* ms = nullptr; // second-order multistep (MS): the history buffers; eta is then 0; a schedule and a tie only
     bool invert = false;                  // DDIM inversion (INVERT): `sched` names the HIGHER level every crystal climbs to; no other option
     const arreau_species_control* species = nullptr;  // species control (SPEC): the admission rows and the temperature; not with invert
+    const uint64_t* crystal_seeds = nullptr;  // keyed sampling: the stream seed of every crystal (StepNoiseSrc::seeds of every draw)
 };
 // DDIM-style sampling (arreau_sample_loop_eta, arreau_reverse_step_eta; the rules are stated in include/arreau_hip.h):
 // ARREAU_EINVAL unless eta is finite and lies in [0, 1].
@@ -344,8 +349,8 @@ int arreau_multistep_check(const arreau_multistep* ms, const char* who);  // upd
 int arreau_species_check(const arreau_species_control* species, const char* who, arreau_species_control* out);  // update.hip
 
 // One corrector move per crystal at timestep d_t[b]: z from the caller's d_z_frac [N,3], or (d_z_frac null) the Philox draw
-// (seed, t, ARREAU_DRAW_Z_CORRECTOR, element, iter; 256 pass[0] + iter with opt.pass).  Reads st.frac / offsets / B / N, opt.corr.snr,
-// opt.pass and of opt.cond the position mask (null / no mask: every atom moves).
+// (seed, t, ARREAU_DRAW_Z_CORRECTOR, element, iter; 256 pass[0] + iter with opt.pass; keyed by opt.crystal_seeds when given).  Reads
+// st.frac / offsets / B / N, opt.corr.snr, opt.pass, opt.crystal_seeds and of opt.cond the position mask (null / no mask: every atom moves).
 int arreau_launch_corrector(const arreau_model* m, const SampleState& st, const int32_t* d_t, const float* d_eps, const float* d_z_frac,
                             uint64_t seed, uint32_t iter, const StepOptions& opt, hipStream_t s);
 

@@ -28,6 +28,13 @@
 #define ARREAU_DRAW_Z_TRAIN_FRAC 10u     // randn [n,3]  element 3 a + d, a the atom's index within its crystal
 #define ARREAU_DRAW_U_TRAIN_TYPES 11u    // rand  [n,S]  element a S + s
 #define ARREAU_DRAW_Z_TRAIN_LENGTHS 12u  // randn [3]    element d
+// keyed sampling (arreau_sample_loop_keyed; rules in include/arreau_hip.h): the initial state of a crystal, at counter timestep 0
+// under the crystal's stream seed, elements counted within the crystal
+#define ARREAU_DRAW_Z_INIT_LENGTHS 13u   // randn [3]    element d
+#define ARREAU_DRAW_Z_INIT_FRAC 14u      // randn [n,3]  element 3 a + d
+#define ARREAU_DRAW_U_INIT_ANGLES 15u    // rand  [k]    element j: the j-th uniform the crystal's angle draw consumes
+// the counter tag of the stream seed itself: words 0 and 1 of philox4x32_10((key lo, key hi, TAG, 0), seed) (host, exact integers)
+#define ARREAU_STREAM_SEED_TAG 0x4B455953u  // "KEYS"
 
 struct Philox4 { uint32_t x[4]; };
 
@@ -50,6 +57,12 @@ __host__ __device__ inline Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint3
 __host__ __device__ inline float philox_uniform(uint64_t seed, uint32_t timestep, uint32_t kind, uint32_t element, uint32_t word3 = 0u) {
     const Philox4 r = philox4x32_10(element, timestep, kind, word3, (uint32_t)seed, (uint32_t)(seed >> 32));
     return (float)(r.x[0] >> 8) * (1.0f / 16777216.0f);
+}
+
+// keyed sampling, rule 1: the stream seed of (seed, key), 0 <= key < 2^63
+__host__ __device__ inline uint64_t arreau_stream_seed(uint64_t seed, uint64_t key) {
+    const Philox4 r = philox4x32_10((uint32_t)key, (uint32_t)(key >> 32), ARREAU_STREAM_SEED_TAG, 0u, (uint32_t)seed, (uint32_t)(seed >> 32));
+    return (uint64_t)r.x[0] | ((uint64_t)r.x[1] << 32);
 }
 
 #ifdef __HIPCC__

@@ -33,7 +33,10 @@ struct JumpNoise {
     const float* u_types;    // [N,S] or null
     uint64_t seed;
     uint32_t pass;           // counter word3 of the Philox draws
+    const uint64_t* seeds;   // keyed sampling: the stream seed of every crystal [B] (StepNoiseSrc::seeds), or null
 };
+// the keys of the jump's Philox draws (update_dev.h: atom_draw_key / length_draw_key)
+__device__ __forceinline__ StepNoiseSrc jump_key_src(const JumpNoise& n) { return StepNoiseSrc{nullptr, nullptr, nullptr, n.seed, n.seeds}; }
 
 // TIE: lattice systems (arreau_resample_jump_tied, the tied loop): the axes tied by length_tie[b] jump together from the leader's
 // length with the leader's draw (rule 2 of the section in include/arreau_hip.h); a crystal whose lengths len_mask knows is not tied.
@@ -69,8 +72,10 @@ __global__ __launch_bounds__(JUMP_THREADS) void resample_jump_kernel(
                 if (fixed_lengths == nullptr) {  // a fixed cell is held (kernel argument: uniform)
                     const float ratio = s > 0 ? alpha_bars[t] / alpha_bars[s] : alpha_bars[t];
                     const int e = tied ? 3 * b : g;
+                    const DrawKey dk = length_draw_key(jump_key_src(noise), b);
                     const float z = noise.z_lengths ? noise.z_lengths[e]
-                                                    : philox_normal(noise.seed, (uint32_t)t, ARREAU_DRAW_Z_JUMP_LENGTHS, (uint32_t)e, noise.pass);
+                                                    : philox_normal(dk.seed, (uint32_t)t, ARREAU_DRAW_Z_JUMP_LENGTHS,
+                                                                    dk.atom + (tied ? 0u : threadIdx.x), noise.pass);
                     l = sqrtf(ratio) * (tied ? oldlen[0] : l) + sqrtf(1.0f - ratio) * z;
                     lengths[g] = l;
                 }
@@ -83,8 +88,9 @@ __global__ __launch_bounds__(JUMP_THREADS) void resample_jump_kernel(
             if (fixed_lengths == nullptr) {  // a fixed cell is held (kernel argument: uniform)
                 // VP_lattice.forward composed (diffusion_helpers.py:156-163): abar_{t|s} = abar_t / abar_s, abar_0 = 1
                 const float ratio = s > 0 ? alpha_bars[t] / alpha_bars[s] : alpha_bars[t];
+                const DrawKey dk = length_draw_key(jump_key_src(noise), b);
                 const float z = noise.z_lengths ? noise.z_lengths[g]
-                                                : philox_normal(noise.seed, (uint32_t)t, ARREAU_DRAW_Z_JUMP_LENGTHS, (uint32_t)g, noise.pass);
+                                                : philox_normal(dk.seed, (uint32_t)t, ARREAU_DRAW_Z_JUMP_LENGTHS, dk.atom + threadIdx.x, noise.pass);
                 l = sqrtf(ratio) * l + sqrtf(1.0f - ratio) * z;
                 lengths[g] = l;
             }
@@ -131,12 +137,13 @@ __global__ __launch_bounds__(JUMP_THREADS) void resample_jump_kernel(
     int s, t;
     bool bad;
     jump_pair(jt, lo, T, s, t, bad);  // (flagged by the crystal's workgroup)
+    const DrawKey dk = atom_draw_key(jump_key_src(noise), offsets, lo, i);  // (keyed sampling: the crystal's seed, the atom's index in it)
     if (lane < 3) {
         // VE_pbc.forward composed (diffusion_helpers.py:43-47): std sqrt(sig_t^2 - sig_s^2), formed without cancellation
         const float st = ve_sigmas[t], ss = ve_sigmas[s];
         const float sd = sqrtf((st - ss) * (st + ss));
         const size_t g = 3 * (size_t)i + lane;
-        const float z = noise.z_frac ? noise.z_frac[g] : philox_normal(noise.seed, (uint32_t)t, ARREAU_DRAW_Z_JUMP_FRAC, (uint32_t)g, noise.pass);
+        const float z = noise.z_frac ? noise.z_frac[g] : philox_normal(dk.seed, (uint32_t)t, ARREAU_DRAW_Z_JUMP_FRAC, 3u * dk.atom + (uint32_t)lane, noise.pass);
         frac[g] = remainder_one(frac[g] + sd * z);
     }
     // species held by the loop: constant species, known species of a condition (wave-uniform)
@@ -154,8 +161,8 @@ __global__ __launch_bounds__(JUMP_THREADS) void resample_jump_kernel(
         // absorbing chain: row xs is zero off the diagonal and the mask column (checked at model creation), so those entries are
         // the exact zeros the dense read would give
         const float q = (!absorbing || c == xs || c == mask) ? qrow[c] : 0.0f;
-        const uint32_t e = (uint32_t)((size_t)i * S + c);
-        const float uu = have_u ? noise.u_types[(size_t)i * S + c] : philox_uniform(noise.seed, (uint32_t)t, ARREAU_DRAW_U_JUMP_TYPES, e, noise.pass);
+        const uint32_t e = dk.atom * (uint32_t)S + (uint32_t)c;
+        const float uu = have_u ? noise.u_types[(size_t)i * S + c] : philox_uniform(dk.seed, (uint32_t)t, ARREAU_DRAW_U_JUMP_TYPES, e, noise.pass);
         const float u = fminf(fmaxf(uu, D3PM_EPS), 1.0f);
         const float val = logf(q + D3PM_EPS) + (-logf(-logf(u)));
         if (val > best) { best = val; besti = c; }
@@ -192,7 +199,7 @@ int arreau_launch_resample_jump(const arreau_model* m, const SampleState& st, co
     const unsigned blocks = (unsigned)st.B + (unsigned)((st.N + 3) / 4);
     auto kernel = d_length_tie ? resample_jump_kernel<true> : resample_jump_kernel<false>;
     ARREAU_LAUNCH(kernel, dim3(blocks), dim3(JUMP_THREADS), 0, stream, st.B, st.N, st.frac, st.types, st.lengths, st.angles,
-                  JumpTimes{d_s, d_t, s, t}, st.offsets, d_batch, JumpNoise{noise.z_frac, noise.z_lattice, noise.u_types, noise.seed, pass},
+                  JumpTimes{d_s, d_t, s, t}, st.offsets, d_batch, JumpNoise{noise.z_frac, noise.z_lattice, noise.u_types, noise.seed, pass, noise.seeds},
                   m->ve_sigmas, m->vp_alpha_bars, m->qmats, m->S, m->T, m->qmats_absorbing, st.const_types, st.fixed_lengths, type_mask,
                   st.lattice, lp, m->vp_betas, m->t_emb_w, m->embT, m->C, m->status, d_length_tie, len_mask);
     ARREAU_CHECK_HIP(hipGetLastError());
@@ -227,15 +234,33 @@ extern "C" int arreau_resample_jump(const arreau_model* m, float* d_frac, int32_
 // Forward noising of a clean state to level t (rules in include/arreau_hip.h, section "Starting the sampler from given crystals"):
 // the jump (0, t) of every crystal with the kernel's own Philox draws, pass word 0 -- a word the resampled loop never uses for the
 // jump kinds.  Outside a loop: no device timestep, no next step's set-up.
+static int noise_state(const char* who, const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                       const int32_t* d_off, int32_t B, int32_t N, int32_t t, uint64_t seed, const int32_t* d_const_types,
+                       const float* d_fixed_lengths, float* d_lattice, const int32_t* d_length_tie, const uint64_t* d_crystal_seeds,
+                       void* stream) {
+    ARREAU_REQUIRE(m && d_frac && d_types && d_lengths && d_angles && d_off && d_lattice, std::string(who) + ": null pointer");
+    ARREAU_REQUIRE(B >= 1 && N >= 0, std::string(who) + ": bad size");
+    ARREAU_REQUIRE(t >= 1 && t <= m->T, std::string(who) + ": t must lie in 1..T");
+    const SampleState st{d_frac, d_types, d_lengths, d_angles, d_off, B, N, d_const_types, d_fixed_lengths, d_lattice};
+    return arreau_launch_resample_jump(m, st, /*d_s=*/nullptr, /*d_t=*/nullptr, 0, t, /*d_batch=*/nullptr,
+                                       StepNoiseSrc{.seed = seed, .seeds = d_crystal_seeds}, /*pass=*/0u, /*cond=*/nullptr, /*loop=*/nullptr,
+                                       d_length_tie, (hipStream_t)stream);
+}
+
 extern "C" int arreau_noise_state(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
                                   const int32_t* d_off, int32_t B, int32_t N, int32_t t, uint64_t seed, const int32_t* d_const_types,
                                   const float* d_fixed_lengths, float* d_lattice, const int32_t* d_length_tie, void* stream) {
-    ARREAU_REQUIRE(m && d_frac && d_types && d_lengths && d_angles && d_off && d_lattice, "arreau_noise_state: null pointer");
-    ARREAU_REQUIRE(B >= 1 && N >= 0, "arreau_noise_state: bad size");
-    ARREAU_REQUIRE(t >= 1 && t <= m->T, "arreau_noise_state: t must lie in 1..T");
-    const SampleState st{d_frac, d_types, d_lengths, d_angles, d_off, B, N, d_const_types, d_fixed_lengths, d_lattice};
-    return arreau_launch_resample_jump(m, st, /*d_s=*/nullptr, /*d_t=*/nullptr, 0, t, /*d_batch=*/nullptr, StepNoiseSrc{.seed = seed},
-                                       /*pass=*/0u, /*cond=*/nullptr, /*loop=*/nullptr, d_length_tie, (hipStream_t)stream);
+    return noise_state("arreau_noise_state", m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, t, seed, d_const_types, d_fixed_lengths,
+                       d_lattice, d_length_tie, nullptr, stream);
+}
+
+// Keyed sampling (rules in include/arreau_hip.h): arreau_noise_state with the table of stream seeds; NULL = arreau_noise_state.
+extern "C" int arreau_noise_state_keyed(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                                        const int32_t* d_off, int32_t B, int32_t N, int32_t t, uint64_t seed,
+                                        const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice,
+                                        const int32_t* d_length_tie, const uint64_t* d_crystal_seeds, void* stream) {
+    return noise_state("arreau_noise_state_keyed", m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, t, seed, d_const_types,
+                       d_fixed_lengths, d_lattice, d_length_tie, d_crystal_seeds, stream);
 }
 
 // arreau_resample_jump with the lattice-system tie of the lengths (rules in include/arreau_hip.h); NULL = arreau_resample_jump.

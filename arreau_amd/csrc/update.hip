@@ -451,18 +451,72 @@ extern "C" int arreau_philox_fill(uint64_t seed, int32_t timestep, int32_t kind,
     return arreau_philox_fill_word(seed, timestep, kind, 0u, n, d_out, d_raw, stream);
 }
 
+// Keyed sampling (rules in include/arreau_hip.h): the draws of the keyed loop written out in batch layout.  One workgroup per
+// crystal b strides over its n_b * width (per atom) or width (per crystal) elements e: the draw (seeds[b], timestep, kind, e, word3)
+// goes to row offsets[b] * width + e (per atom) or b * width + e (per crystal) -- what the caller's-noise exports read at that row.
+__global__ __launch_bounds__(256) void philox_fill_crystals_kernel(const uint64_t* __restrict__ seeds, const int32_t* __restrict__ offsets,
+                                                                   uint32_t timestep, uint32_t kind, uint32_t word3, int width, int per_atom,
+                                                                   int uniform, float* __restrict__ out, uint32_t* __restrict__ raw) {
+    const int b = blockIdx.x;
+    const uint64_t seed = seeds[b];
+    const int first = offsets[b], last = offsets[b + 1];
+    const int64_t n = per_atom ? (int64_t)(last - first) * width : width;
+    const int64_t row0 = per_atom ? (int64_t)first * width : (int64_t)b * width;
+    for (int64_t e = threadIdx.x; e < n; e += blockDim.x) {
+        if (raw) {
+            const Philox4 r = philox4x32_10((uint32_t)e, timestep, kind, word3, (uint32_t)seed, (uint32_t)(seed >> 32));
+            for (int j = 0; j < 4; ++j) raw[4 * (row0 + e) + j] = r.x[j];
+        }
+        if (out) out[row0 + e] = uniform ? philox_uniform(seed, timestep, kind, (uint32_t)e, word3) : philox_normal(seed, timestep, kind, (uint32_t)e, word3);
+    }
+}
+
+extern "C" int arreau_philox_fill_crystals(const uint64_t* d_seeds, const int32_t* d_offsets, int32_t B, int32_t timestep, int32_t kind,
+                                           uint32_t word3, int32_t per_atom_width, int32_t per_crystal_width, float* d_out, uint32_t* d_raw,
+                                           void* stream) {
+    ARREAU_REQUIRE(d_seeds && d_offsets && (d_out || d_raw) && B >= 0 && timestep >= 0, "arreau_philox_fill_crystals: bad argument");
+    ARREAU_REQUIRE(kind >= 0 && kind <= (int32_t)ARREAU_DRAW_U_INIT_ANGLES && !(kind >= (int32_t)ARREAU_DRAW_U_TIMESTEP && kind <= (int32_t)ARREAU_DRAW_Z_TRAIN_LENGTHS),
+                   "arreau_philox_fill_crystals: not a draw kind of the sampler");
+    ARREAU_REQUIRE((per_atom_width > 0) != (per_crystal_width > 0) && per_atom_width >= 0 && per_crystal_width >= 0,
+                   "arreau_philox_fill_crystals: give either a per-atom or a per-crystal width");
+    if (B == 0) return ARREAU_OK;
+    const int uniform = kind == (int32_t)ARREAU_DRAW_U_TYPES || kind == (int32_t)ARREAU_DRAW_U_JUMP_TYPES || kind == (int32_t)ARREAU_DRAW_U_INIT_ANGLES;
+    ARREAU_LAUNCH(philox_fill_crystals_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, d_seeds, d_offsets, (uint32_t)timestep,
+                  (uint32_t)kind, word3, per_atom_width > 0 ? per_atom_width : per_crystal_width, per_atom_width > 0 ? 1 : 0, uniform, d_out,
+                  d_raw);
+    ARREAU_CHECK_HIP(hipGetLastError());
+    return ARREAU_OK;
+}
+
 // Conditioned sampling, rule 5 (include/arreau_hip.h): the known components of the initial state at tau = t_start, i.e. the
 // helpers of the in-loop replacement with Philox timestep key t_start + 1.  One thread per known-position component (3 N),
 // per known-length component (3 B) and per known species (N).
+// Keyed sampling (arreau_condition_initial_state_keyed): with the table `seeds` (then `offsets` is read) a crystal's draws take its
+// stream seed and elements counted within it; a thread finds its atom's crystal by bisection of `offsets`.
 __global__ void condition_initial_state_kernel(float* __restrict__ frac, int32_t* __restrict__ types, float* __restrict__ lengths,
                                                int B, int N, int t_key, uint64_t seed, SampleConditionDev cond,
-                                               const float* __restrict__ ve_sigmas, const float* __restrict__ alpha_bars) {
+                                               const float* __restrict__ ve_sigmas, const float* __restrict__ alpha_bars,
+                                               const int32_t* __restrict__ offsets, const uint64_t* __restrict__ seeds) {
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const StepNoiseSrc src{nullptr, nullptr, nullptr, seed, seeds};
     if (g < 3 * (int64_t)N) {
-        if (cond.pos_mask && cond.pos_mask[g / 3]) frac[g] = known_frac_component(&cond, (size_t)g, t_key, t_key - 1, seed, ve_sigmas, 0u);
+        if (cond.pos_mask && cond.pos_mask[g / 3]) {
+            const int i = (int)(g / 3);
+            int lo = 0;
+            if (seeds != nullptr) {  // largest b with offsets[b] <= i
+                int hi = B;
+                while (hi - lo > 1) {
+                    const int mid = (lo + hi) >> 1;
+                    if (offsets[mid] <= i) lo = mid; else hi = mid;
+                }
+            }
+            const DrawKey dk = atom_draw_key(src, offsets, lo, i);
+            frac[g] = known_frac_component(&cond, (size_t)g, 3u * dk.atom + (uint32_t)(g - 3 * (int64_t)i), t_key, t_key - 1, dk.seed, ve_sigmas, 0u);
+        }
     } else if (g < 3 * (int64_t)N + 3 * (int64_t)B) {
         const int c = (int)(g - 3 * (int64_t)N), b = c / 3;
-        if (cond.len_mask && cond.len_mask[b]) lengths[c] = known_length_component(&cond, b, c - 3 * b, t_key, t_key - 1, seed, alpha_bars, 0u);
+        if (cond.len_mask && cond.len_mask[b])
+            lengths[c] = known_length_component(&cond, b, c - 3 * b, t_key, t_key - 1, length_draw_key(src, b), alpha_bars, 0u);
     } else if (g < 4 * (int64_t)N + 3 * (int64_t)B) {
         const int i = (int)(g - 3 * (int64_t)N - 3 * (int64_t)B);
         if (cond.type_mask && cond.type_mask[i]) types[i] = cond.a0[i];
@@ -480,19 +534,36 @@ int arreau_condition_to_dev(const arreau_sample_condition* c, SampleConditionDev
     return ARREAU_OK;
 }
 
-extern "C" int arreau_condition_initial_state(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, int32_t B,
-                                              int32_t N, int32_t t_start, uint64_t seed, const arreau_sample_condition* cond,
-                                              void* stream) {
-    ARREAU_REQUIRE(m && d_frac && d_types && d_lengths, "arreau_condition_initial_state: null pointer");
-    ARREAU_REQUIRE(B >= 1 && N >= 0, "arreau_condition_initial_state: bad size");
-    ARREAU_REQUIRE(t_start >= 1 && t_start <= m->T, "arreau_condition_initial_state: t_start must lie in 1..T");
+static int condition_initial_state(const char* who, const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, int32_t B,
+                                   int32_t N, int32_t t_start, uint64_t seed, const arreau_sample_condition* cond, const int32_t* d_off,
+                                   const uint64_t* d_crystal_seeds, void* stream) {
+    ARREAU_REQUIRE(m && d_frac && d_types && d_lengths, std::string(who) + ": null pointer");
+    ARREAU_REQUIRE(B >= 1 && N >= 0, std::string(who) + ": bad size");
+    ARREAU_REQUIRE(t_start >= 1 && t_start <= m->T, std::string(who) + ": t_start must lie in 1..T");
+    ARREAU_REQUIRE(!d_crystal_seeds || d_off, std::string(who) + ": the table of stream seeds needs the crystal offsets");
     SampleConditionDev c;
     int rc;
     if ((rc = arreau_condition_to_dev(cond, &c))) return rc;
     if (arreau_condition_empty(&c)) return ARREAU_OK;
     const int64_t n = 4 * (int64_t)N + 3 * (int64_t)B;
     ARREAU_LAUNCH(condition_initial_state_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_frac, d_types,
-                  d_lengths, B, N, t_start + 1, seed, c, m->ve_sigmas, m->vp_alpha_bars);
+                  d_lengths, B, N, t_start + 1, seed, c, m->ve_sigmas, m->vp_alpha_bars, d_off, d_crystal_seeds);
     ARREAU_CHECK_HIP(hipGetLastError());
     return ARREAU_OK;
+}
+
+extern "C" int arreau_condition_initial_state(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, int32_t B,
+                                              int32_t N, int32_t t_start, uint64_t seed, const arreau_sample_condition* cond,
+                                              void* stream) {
+    return condition_initial_state("arreau_condition_initial_state", m, d_frac, d_types, d_lengths, B, N, t_start, seed, cond, nullptr,
+                                   nullptr, stream);
+}
+
+// Keyed sampling (rules in include/arreau_hip.h): arreau_condition_initial_state with the crystal offsets and the table of stream
+// seeds; a NULL table = arreau_condition_initial_state.
+extern "C" int arreau_condition_initial_state_keyed(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths,
+                                                    const int32_t* d_off, int32_t B, int32_t N, int32_t t_start, uint64_t seed,
+                                                    const arreau_sample_condition* cond, const uint64_t* d_crystal_seeds, void* stream) {
+    return condition_initial_state("arreau_condition_initial_state_keyed", m, d_frac, d_types, d_lengths, B, N, t_start, seed, cond, d_off,
+                                   d_crystal_seeds, stream);
 }

@@ -15,6 +15,24 @@ __device__ __forceinline__ float remainder_one(float x) {
     return m;
 }
 
+// Keyed sampling (arreau_sample_loop_keyed; the rules are stated in include/arreau_hip.h): what a Philox draw of crystal b is keyed
+// by.  Without the table (noise.seeds null -- a kernel argument, so the choice is a scalar one) it is the call's seed and the global
+// index, exactly as before the table existed; with it the crystal's stream seed and the index counted within the crystal.
+// The draws of an atom: `seed` and the atom index `atom` its elements are formed from (3 atom + d, atom S + c).
+struct DrawKey {
+    uint64_t seed;
+    uint32_t atom;
+};
+__device__ __forceinline__ DrawKey atom_draw_key(const StepNoiseSrc& noise, const int32_t* __restrict__ offsets, int b, int i) {
+    if (noise.seeds != nullptr) return DrawKey{noise.seeds[b], (uint32_t)(i - offsets[b])};
+    return DrawKey{noise.seed, (uint32_t)i};
+}
+// The draws of crystal b's lengths: `seed` and the element `atom` of its first component (0 keyed, 3 b without).
+__device__ __forceinline__ DrawKey length_draw_key(const StepNoiseSrc& noise, int b) {
+    if (noise.seeds != nullptr) return DrawKey{noise.seeds[b], 0u};
+    return DrawKey{noise.seed, 3u * (uint32_t)b};
+}
+
 // Respaced sampling (arreau_sample_loop_scheduled / arreau_reverse_step_to; rules in include/arreau_hip.h): the timestep s that
 // the step leaving t (crystal b, t already clamped to 1..T) produces.  Without a schedule s = t - 1.  Valid targets are s = 0 at
 // t = 1 and 1 <= s <= t - 1 above it; anything else is clamped into that range and flagged (by the caller's one thread per
@@ -35,21 +53,23 @@ __device__ __forceinline__ int step_target(const StepScheduleDev* sc, int b, int
 // draw of (seed, t), and the template itself at tau = 0.  The initial state uses the same helpers with t = t_start + 1,
 // tau = t_start.  word3: the counter word of the draw (0; 256 r in pass r of a resampled loop) -- no default, so that every
 // call site says which.
-// Rule 1, VE_pbc.forward (diffusion_helpers.py:43-47): component g = 3 i + d of a known position.
-__device__ __forceinline__ float known_frac_component(const SampleConditionDev* c, size_t g, int t, int tau, uint64_t seed,
+// Rule 1, VE_pbc.forward (diffusion_helpers.py:43-47): component g = 3 i + d of a known position, drawn as element e under `seed`
+// (e = g and the call's seed; keyed sampling: the component's index within its crystal and the crystal's stream seed).
+__device__ __forceinline__ float known_frac_component(const SampleConditionDev* c, size_t g, uint32_t e, int t, int tau, uint64_t seed,
                                                       const float* __restrict__ ve_sigmas, uint32_t word3) {
     const float x0 = c->x0[g];
     if (tau == 0) return remainder_one(x0);
-    const float z = philox_normal(seed, (uint32_t)t, ARREAU_DRAW_Z_KNOWN_FRAC, (uint32_t)g, word3);
+    const float z = philox_normal(seed, (uint32_t)t, ARREAU_DRAW_Z_KNOWN_FRAC, e, word3);
     return remainder_one(x0 + ve_sigmas[tau] * z);
 }
-// Rule 2, VP_lattice.forward (diffusion_helpers.py:156-163): component i of crystal b's known lengths.
-__device__ __forceinline__ float known_length_component(const SampleConditionDev* c, int b, int i, int t, int tau, uint64_t seed,
+// Rule 2, VP_lattice.forward (diffusion_helpers.py:156-163): component i of crystal b's known lengths, drawn as element
+// key.atom + i under key.seed (length_draw_key).
+__device__ __forceinline__ float known_length_component(const SampleConditionDev* c, int b, int i, int t, int tau, DrawKey key,
                                                         const float* __restrict__ alpha_bars, uint32_t word3) {
     const float l0 = c->l0[3 * b + i];
     if (tau == 0) return l0;
     const float ab = alpha_bars[tau];
-    const float z = philox_normal(seed, (uint32_t)t, ARREAU_DRAW_Z_KNOWN_LENGTHS, 3u * b + i, word3);
+    const float z = philox_normal(key.seed, (uint32_t)t, ARREAU_DRAW_Z_KNOWN_LENGTHS, key.atom + i, word3);
     return sqrtf(ab) * l0 + sqrtf(1.0f - ab) * z;
 }
 
@@ -65,10 +85,11 @@ __device__ __forceinline__ float eta_length_move(float x0, float xt, float ab_t,
     if (eta > 0.0f) l += eta * var * zz;
     return l;
 }
-// The draw of length element e of the step at t for the eta move: none at eta = 0 (the array may be null) or for t <= 1.
-__device__ __forceinline__ float eta_length_draw(StepNoiseSrc noise, uint32_t e, int t, float eta, uint32_t word3) {
+// The draw of length element e of the step at t for the eta move: none at eta = 0 (the array may be null) or for t <= 1.  The
+// generator's element is pe under pseed (e and the call's seed; keyed sampling: the crystal's own).
+__device__ __forceinline__ float eta_length_draw(StepNoiseSrc noise, uint32_t e, uint64_t pseed, uint32_t pe, int t, float eta, uint32_t word3) {
     if (!(eta > 0.0f) || t <= 1) return 0.0f;
-    return noise.z_lattice ? noise.z_lattice[e] : philox_normal(noise.seed, (uint32_t)t, ARREAU_DRAW_Z_LATTICE, e, word3);
+    return noise.z_lattice ? noise.z_lattice[e] : philox_normal(pseed, (uint32_t)t, ARREAU_DRAW_Z_LATTICE, pe, word3);
 }
 
 // Second-order multistep sampling (arreau_sample_loop_multistep / arreau_reverse_step_multistep; the rules are stated in
@@ -147,6 +168,7 @@ __device__ __forceinline__ float reverse_length_component(int b, int i, int t, i
                                                           float eta = 0.0f /* ETA only */, const arreau_multistep& ms = {} /* MS only */,
                                                           int hist_p = 0 /* MS only */, int T = 0 /* MS only */) {
     const float* __restrict__ z = noise.z_lattice;
+    const DrawKey dk = length_draw_key(noise, b);  // (keyed sampling: the crystal's stream seed, element i)
     const float n = (float)(last - first);
     const float ab_t = alpha_bars[t], ab_p = alpha_bars[s];
     const float beta = (sched == nullptr || s == t - 1) ? betas[t] : fminf(1.0f - ab_t / ab_p, sched->clipmax);
@@ -175,7 +197,7 @@ __device__ __forceinline__ float reverse_length_component(int b, int i, int t, i
     if constexpr (INVERT) {
         moved = invert_length_move(x0, xt, ab_t, ab_p);
     } else if constexpr (ETA) {
-        moved = eta_length_move(x0, xt, ab_t, ab_p, beta, eta, eta_length_draw(noise, 3u * b + i, t, eta, word3));
+        moved = eta_length_move(x0, xt, ab_t, ab_p, beta, eta, eta_length_draw(noise, 3u * b + i, dk.seed, dk.atom + i, t, eta, word3));
         if constexpr (MS) {
             const bool usable = ms_usable(hist_p, t, T);
             moved = ms_length_move(moved, x0, ms.hist_x0[3 * b + i], xt, ab_t, ab_p, alpha_bars[usable ? hist_p : t], usable, s);
@@ -183,14 +205,14 @@ __device__ __forceinline__ float reverse_length_component(int b, int i, int t, i
         }
     } else {
         const float mean = (c0 * x0 + c1 * xt) / denom;
-        const float zdraw = z ? z[3 * b + i] : philox_normal(noise.seed, (uint32_t)t, ARREAU_DRAW_Z_LATTICE, 3u * b + i, word3);
+        const float zdraw = z ? z[3 * b + i] : philox_normal(dk.seed, (uint32_t)t, ARREAU_DRAW_Z_LATTICE, dk.atom + i, word3);
         const float zz = t > 1 ? zdraw : 0.0f;
         moved = mean + variance * zz;
     }
     // fixed-cell sampling (arreau_sample_loop, d_fixed_lengths): the given lengths are re-imposed after the update
     float mylen = fixed_lengths ? fixed_lengths[3 * b + i] : moved;
     // conditioned sampling, rule 2: a known length is replaced before the cell is formed from it
-    if (cond && cond->len_mask && cond->len_mask[b]) mylen = known_length_component(cond, b, i, t, s, noise.seed, alpha_bars, word3);
+    if (cond && cond->len_mask && cond->len_mask[b]) mylen = known_length_component(cond, b, i, t, s, dk, alpha_bars, word3);
     lengths[3 * b + i] = mylen;
     return mylen;
 }
@@ -257,9 +279,11 @@ __device__ __forceinline__ float tied_length_component(int b, int i, int code, c
     const float x0 = !tied ? x0s[i] : (code == 1 ? (x0s[0] + x0s[1]) / 2.0f : ((x0s[0] + x0s[1]) + x0s[2]) / 3.0f);
     const float xt = tied ? xts[0] : xts[i];
     const uint32_t e = 3u * b + (tied ? 0u : (uint32_t)i);
+    const DrawKey dk = length_draw_key(noise, b);  // (keyed sampling: the crystal's stream seed, the leader's element 0)
+    const uint32_t pe = dk.atom + (tied ? 0u : (uint32_t)i);
     float moved;
     if constexpr (ETA) {
-        moved = eta_length_move(x0, xt, ab_t, ab_p, beta, eta, eta_length_draw(noise, e, t, eta, word3));
+        moved = eta_length_move(x0, xt, ab_t, ab_p, beta, eta, eta_length_draw(noise, e, dk.seed, pe, t, eta, word3));
         if constexpr (MS) {
             const bool usable = ms_usable(hist_p, t, T);
             moved = ms_length_move(moved, x0, tied ? x0ps[0] : x0ps[i], xt, ab_t, ab_p, alpha_bars[usable ? hist_p : t], usable, s);
@@ -267,12 +291,12 @@ __device__ __forceinline__ float tied_length_component(int b, int i, int code, c
         }
     } else {
         const float mean = (c0 * x0 + c1 * xt) / denom;
-        const float zdraw = z ? z[e] : philox_normal(noise.seed, (uint32_t)t, ARREAU_DRAW_Z_LATTICE, e, word3);
+        const float zdraw = z ? z[e] : philox_normal(dk.seed, (uint32_t)t, ARREAU_DRAW_Z_LATTICE, pe, word3);
         const float zz = t > 1 ? zdraw : 0.0f;
         moved = mean + variance * zz;
     }
     float mylen = fixed_lengths ? fixed_lengths[3 * b + i] : moved;  // a fixed cell: the (host-tied) given lengths
-    if (cond && cond->len_mask && cond->len_mask[b]) mylen = known_length_component(cond, b, i, t, s, noise.seed, alpha_bars, word3);
+    if (cond && cond->len_mask && cond->len_mask[b]) mylen = known_length_component(cond, b, i, t, s, dk, alpha_bars, word3);
     lengths[3 * b + i] = mylen;
     return mylen;
 }
@@ -306,6 +330,7 @@ template <bool SPEC = false>
 __device__ __forceinline__ int d3pm_reverse_class(int i, int lane, float l0, float l1, int t, int s_to, const int32_t* __restrict__ types,
                                                   StepNoiseSrc noise, const float* __restrict__ q1t, const float* __restrict__ qmats, int S,
                                                   int absorbing, int32_t* __restrict__ status, const StepScheduleDev* sched, uint32_t word3,
+                                                  DrawKey dk /* atom_draw_key of atom i */,
                                                   int b = 0 /* SPEC only */, const arreau_species_control& sp = {} /* SPEC only */) {
     const float* __restrict__ u_types = noise.u_types;
     // ---- D3PM posterior logits ------------------------------------------------------------------
@@ -404,7 +429,7 @@ __device__ __forceinline__ int d3pm_reverse_class(int i, int lane, float l0, flo
     const bool have_u = u_types != nullptr;
     const float* un = u_types + (have_u ? (size_t)i * S : 0);
     auto draw_u = [&](int s_) {
-        return have_u ? un[s_] : philox_uniform(noise.seed, (uint32_t)t, ARREAU_DRAW_U_TYPES, (uint32_t)((size_t)i * S + s_), word3);
+        return have_u ? un[s_] : philox_uniform(dk.seed, (uint32_t)t, ARREAU_DRAW_U_TYPES, dk.atom * (uint32_t)S + (uint32_t)s_, word3);
     };
     float best = -INFINITY;
     int besti = 0x7fffffff;
@@ -489,6 +514,7 @@ __device__ __forceinline__ void reverse_one_atom(
     int t = tstep[lo];
     t = t < 1 ? 1 : (t > T ? T : t);
     const int s_to = step_target(sched, lo, t, status, false);  // (flagged by the crystal's lattice thread)
+    const DrawKey dk = atom_draw_key(noise, offsets, lo, i);  // (keyed sampling: the crystal's stream seed, the atom's index in it)
     int hist_p = 0;
     if constexpr (MS) {
         if (lane == 0) hist_p = ms.hist_t_atom[i];
@@ -507,7 +533,7 @@ __device__ __forceinline__ void reverse_one_atom(
             const float dir = sp * sqrtf((1.0f - eta * eta) + eta * eta * r * r);
             float v = frac[g] - eps[g] * s * (s - dir);
             if (eta > 0.0f) {  // (at eta = 0 the draw is not read: z_frac may be null)
-                const float zf = z_frac ? z_frac[g] : philox_normal(noise.seed, (uint32_t)t, ARREAU_DRAW_Z_FRAC, (uint32_t)g, word3);
+                const float zf = z_frac ? z_frac[g] : philox_normal(dk.seed, (uint32_t)t, ARREAU_DRAW_Z_FRAC, 3u * dk.atom + (uint32_t)lane, word3);
                 v += eta * sp * sqrtf(1.0f - r * r) * zf;
             }
             if constexpr (MS) {
@@ -520,10 +546,10 @@ __device__ __forceinline__ void reverse_one_atom(
         } else {
             const float mean = frac[g] - eps[g] * (s2 - sp2);
             const float stdv = sqrtf((sp2 * (s2 - sp2)) / s2);
-            const float zf = z_frac ? z_frac[g] : philox_normal(noise.seed, (uint32_t)t, ARREAU_DRAW_Z_FRAC, (uint32_t)g, word3);
+            const float zf = z_frac ? z_frac[g] : philox_normal(dk.seed, (uint32_t)t, ARREAU_DRAW_Z_FRAC, 3u * dk.atom + (uint32_t)lane, word3);
             fv = remainder_one(mean + stdv * zf);
         }
-        if (cond && cond->pos_mask && cond->pos_mask[i]) fv = known_frac_component(cond, g, t, s_to, noise.seed, ve_sigmas, word3);  // rule 1
+        if (cond && cond->pos_mask && cond->pos_mask[i]) fv = known_frac_component(cond, g, 3u * dk.atom + (uint32_t)lane, t, s_to, dk.seed, ve_sigmas, word3);  // rule 1
         frac[g] = fv;
     }
     if constexpr (MS) {
@@ -536,7 +562,7 @@ __device__ __forceinline__ void reverse_one_atom(
     const float* lg = logits + (size_t)i * S;
     const float l0 = v0 ? lg[s0] : -INFINITY, l1 = v1 ? lg[s1] : -INFINITY;
     if constexpr (SPEC) {
-        const int cls = d3pm_reverse_class<true>(i, lane, l0, l1, t, s_to, types, noise, q1t, qmats, S, absorbing, status, sched, word3, lo, sp);
+        const int cls = d3pm_reverse_class<true>(i, lane, l0, l1, t, s_to, types, noise, q1t, qmats, S, absorbing, status, sched, word3, dk, lo, sp);
         // rule 6: held species are imposed after the draw, as below
         if (lane == 0) types[i] = (cond && cond->type_mask && cond->type_mask[i]) ? cond->a0[i] : (const_types ? const_types[i] : cls);
         return;
@@ -624,7 +650,7 @@ __device__ __forceinline__ void reverse_one_atom(
     const bool have_u = u_types != nullptr;
     const float* un = u_types + (have_u ? (size_t)i * S : 0);
     auto draw_u = [&](int s_) {
-        return have_u ? un[s_] : philox_uniform(noise.seed, (uint32_t)t, ARREAU_DRAW_U_TYPES, (uint32_t)((size_t)i * S + s_), word3);
+        return have_u ? un[s_] : philox_uniform(dk.seed, (uint32_t)t, ARREAU_DRAW_U_TYPES, dk.atom * (uint32_t)S + (uint32_t)s_, word3);
     };
     float best = -INFINITY;
     int besti = 0x7fffffff;
@@ -736,8 +762,10 @@ __device__ __forceinline__ void reverse_atoms_body_sym(
     if (lead >= 0 && lead != i) return;  // a member: written by its leader's wave
     int b = 0, o = -1;
     bool orbit_ok = false;
+    DrawKey dk{noise.seed, (uint32_t)i};
     if (lead == i) {
         b = sym_atom_crystal(i, lane, offsets, B, batch);
+        dk = atom_draw_key(noise, offsets, b, i);  // (keyed sampling: the leader's draws, keyed within its crystal)
         o = sy.orbit[i];
         orbit_ok = sym_orbit_ok(sy, i, o, offsets[b], offsets[b + 1], lane);
         if (!orbit_ok && lane == 0) atomicOr(status, ARREAU_STATUS_BAD_SYMMETRY);
@@ -773,7 +801,7 @@ __device__ __forceinline__ void reverse_atoms_body_sym(
         xc = frac[g];
         const float mean = xc - ebar * (s2 - sp2);
         const float stdv = sqrtf((sp2 * (s2 - sp2)) / s2);
-        const float zf = noise.z_frac ? noise.z_frac[g] : sym_philox_normal(noise.seed, (uint32_t)t, ARREAU_DRAW_Z_FRAC, (uint32_t)g);
+        const float zf = noise.z_frac ? noise.z_frac[g] : sym_philox_normal(dk.seed, (uint32_t)t, ARREAU_DRAW_Z_FRAC, 3u * dk.atom + (uint32_t)lane);
         y = mean + stdv * zf;
     }
     const float ys[3] = {sym_lane_value(y, 0), sym_lane_value(y, 1), sym_lane_value(y, 2)};
@@ -807,7 +835,7 @@ __device__ __forceinline__ void reverse_atoms_body_sym(
     }
     l0 = v0 ? l0 * inv_o : -INFINITY;
     l1 = v1 ? l1 * inv_o : -INFINITY;
-    const int cls = d3pm_reverse_class<SPEC>(i, lane, l0, l1, t, s_to, types, noise, q1t, qmats, S, absorbing, status, sched, 0u, b, sp);
+    const int cls = d3pm_reverse_class<SPEC>(i, lane, l0, l1, t, s_to, types, noise, q1t, qmats, S, absorbing, status, sched, 0u, dk, b, sp);
     const int newt = const_types ? const_types[i] : cls;
     // rule 4 and the members' species: lanes over the members
     for (int a = a0 + lane; a < a1; a += 64) {

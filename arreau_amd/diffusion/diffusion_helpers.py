@@ -114,17 +114,19 @@ def radius_graph_pbc(cart_coords, lattice, num_atoms, radius, max_num_neighbors_
     return edge_index[:, :E], cell_off[:E], per_crystal, odist[:E], odir[:E]
 
 
-def sample_bravais_angles(lattice_type: str):
-    """diffusion_helpers.py:739-774: angles in DEGREES (the sampler consumes them as radians)."""
+def sample_bravais_angles(lattice_type: str, uniform=None):
+    """diffusion_helpers.py:739-774: angles in DEGREES (the sampler consumes them as radians).  `uniform(low, high)`: the source
+    of the draws (keyed sampling: keyed.angle_uniforms); None is numpy's global generator, as the reference."""
+    uniform = np.random.uniform if uniform is None else uniform  # (one call, one draw: the default path's draws are unchanged)
     if lattice_type in ("cubic", "tetragonal", "orthorhombic"):
         return np.array([90, 90, 90])
     if lattice_type == "monoclinic":
-        return np.array([90, np.random.uniform(90, 180), 90])
+        return np.array([90, uniform(90, 180), 90])
     if lattice_type == "triclinic":
-        return np.array([np.random.uniform(60, 120) for _ in range(3)])
+        return np.array([uniform(60, 120) for _ in range(3)])
     if lattice_type == "hexagonal":
         return np.array([90, 90, 120])
     if lattice_type == "rhombohedral":
-        angle = np.random.uniform(60, 120)
+        angle = uniform(60, 120)
         return np.array([angle, angle, angle])
     raise ValueError(f"Invalid lattice type: {lattice_type}")

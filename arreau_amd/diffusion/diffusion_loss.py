@@ -14,6 +14,7 @@ import torch.nn as nn
 from . import corrector as pc
 from . import ddim
 from . import inversion
+from . import keyed as keyed_mod
 from . import multistep as multistep_mod
 from . import resampling as rs
 from . import respacing
@@ -68,6 +69,9 @@ class SampleResult:
     # orbit, orbit_size and site_order, one row per atom of the crystals as sampled, and lattice, lengths, angles, n_orbits,
     # max_displacement, rms_displacement, ops_translation and flags, one row per crystal; None when it was not asked for
     symmetrized: Optional[dict] = None
+    # extension: keyed sampling (sample(crystal_keys=...); diffusion/keyed.py) -- the int64 key of every crystal; None when the run
+    # was not keyed
+    crystal_keys: Optional[np.ndarray] = None
     # extension: the structure match of the final state against targets (sample(match_to=...); diffusion/structure_match.py) -- numpy
     # arrays target, n_comparable, rms, rms_norm, max_dist, mapping, translation, n_mappings, n_candidates, n_permutations, matched
     # and flags, one row per crystal, and partner, one row per atom; None when it was not asked for
@@ -348,29 +352,46 @@ class DiffusionLoss(nn.Module):
         return num_atoms
 
     def draw_initial_state(self, num_atoms_per_sample, num_samples_in_batch, num_atomic_states=None, constant_atoms=None,
-                           lattice_system=None, condition=None, specs=None) -> inversion.SamplerState:
+                           lattice_system=None, condition=None, specs=None, seed=None, crystal_keys=None,
+                           model=None) -> inversion.SamplerState:
         """The host draw of sample(): the state at level T-1 a run starts from, as an inversion.SamplerState.  The reference's
         generators in the reference's order: numpy's global generator for the angles (lattice_systems.resolve), then torch's
         global CPU generator for randn lengths [B,3] and randn fractional coordinates [N,3] * pos_sigma_max.  Species: the mask
         class S - 1, or constant_atoms.  lattice_system ties the lengths (the codes travel in the state); a condition's known
         cells give their angles (its other known components are imposed on the device, by sample()); `specs` (the resolved
         symmetry specs of sample()) project the leaders onto their sites.  Handing the result to sample(initial_state=...) under
-        the generator states this call left is the plain sample() call bit for bit."""
+        the generator states this call left is the plain sample() call bit for bit.
+        `seed`, `crystal_keys` (keyed sampling; rules in keyed.py): the draws of crystal b come from its own stream instead -- the
+        uniforms of its angle draw restated on the host (kind 15), the normals of its lengths and positions written out by the
+        device (kinds 13 and 14; `model` gives the engine) -- and the formulas below are applied to them as to the generators'
+        values.  The global generators are neither read nor advanced."""
         B = int(num_samples_in_batch)
+        streams = None
+        if crystal_keys is not None:
+            streams = keyed_mod.stream_seeds(seed, keyed_mod.validate_keys(crystal_keys, B, seed))
+            if model is None:
+                raise ValueError("draw_initial_state: keyed draws need model= (the normals are drawn on the device)")
         S = int(self.num_atomic_states if num_atomic_states is None else num_atomic_states)
         num_atoms = self._atom_counts(num_atoms_per_sample, B)
         N = int(num_atoms.sum())
         dt = torch.get_default_dtype()
         # the angles per crystal (numpy's generator; lattice_system=None: the monoclinic draw in degrees, as the reference)
-        angles_np, tie = lattice_systems.resolve(lattice_system, B, condition.lattice_known() if condition is not None else None)
+        angles_np, tie = lattice_systems.resolve(lattice_system, B, condition.lattice_known() if condition is not None else None,
+                                                 uniforms=[keyed_mod.angle_uniforms(int(s)) for s in streams] if streams is not None else None)
         angles = torch.tensor(angles_np)
         if condition is not None and condition.lattice_known().any():  # rule 3: the template's angles (radians)
             known = torch.as_tensor(condition.lattice_known())
             angles[known] = torch.as_tensor(condition.known_angles(), dtype=angles.dtype)[known]
-        lengths = torch.randn([B, 3])
+        if streams is not None:
+            eng = model.engine()
+            z_len, z_frac = eng.keyed_initial_draws(torch.as_tensor(streams.view(np.int64), device=eng.device),
+                                                    crystal_offsets(num_atoms, eng.device))
+            lengths = z_len.cpu().to(dt)
+        else:
+            lengths = torch.randn([B, 3])
         if tie is not None:
             lattice_systems.tie_lengths(lengths, tie)  # the initial state's tie; the device keeps it at every step
-        frac_x = torch.randn([N, 3], dtype=dt) * pos_sigma_max
+        frac_x = (z_frac.cpu().to(dt) if streams is not None else torch.randn([N, 3], dtype=dt)) * pos_sigma_max
         if specs is not None:  # leaders onto their sites, members their images (unwrapped, as the draw)
             fx = frac_x.double().numpy()
             first = np.concatenate([[0], np.cumsum(num_atoms.numpy())])
@@ -397,7 +418,7 @@ class DiffusionLoss(nn.Module):
                corrector_snr: float = pc.DEFAULT_SNR, resample_passes: int = 1, jump_length: int = 10,
                lattice_system=None, symmetry=None, screen=None, unique=None, find_symmetry=None, reduce_cell=None,
                symmetrize=None, match_to=None, eta: Optional[float] = None, initial_state=None,
-               multistep: bool = False, elements=None, species_temperature: float = 1.0) -> SampleResult:
+               multistep: bool = False, elements=None, species_temperature: float = 1.0, crystal_keys=None) -> SampleResult:
         """diffusion_loss.py:276-377.  The initial state is drawn on the host exactly like the reference (numpy
         uniforms for the angles, then randn lengths, randn fractional coordinates from torch's global CPU generator):
         draw_initial_state, which a caller may also use on its own.
@@ -539,7 +560,20 @@ class DiffusionLoss(nn.Module):
         crystal b is matched against target b; otherwise against every target of its composition, the best one reported.  The
         atomic numbers are the species ids.  SampleResult.match then holds the arrays (structure_match.MATCH_KEYS).  It reads the
         state as sampled, like the other instruments.  The optimal assignment only with StructureMatchParams(assignment="optimal"), no supercells, no volume scaling.  None: no launch
-        is added, match is None and the results are what they were, bit for bit."""
+        is added, match is None and the results are what they were, bit for bit.
+        `crystal_keys` (extension, noise="philox" with a `seed`): keyed sampling (keyed.py; rules in include/arreau_hip.h;
+        arreau_sample_loop_keyed) -- one integer key in 0..2^63-1 per crystal, no key twice.  Every random number crystal b consumes
+        -- its initial angles, lengths and positions, every draw of every step, corrector move and jump, the known components of a
+        condition -- comes from a stream of its own derived from (seed, crystal_keys[b]), with elements counted inside the
+        crystal.  Its final state is then a function of (model, options, seed, key, its atom count, its own inputs): within one
+        score arithmetic bitwise the same alone, in any batch, at any index, eager or replayed, in one call or in segments.
+        Limits: batches on different sides of the score network's basis-form threshold, or with and without ARREAU_CROSS_FP8, agree
+        only to the bound of the network's batch-independence test; the re-run after an fp16x3 overflow is decided per batch.  The
+        host's global generators are neither read nor advanced.  With every option above.  Rejected before any work: keys without
+        a seed, with a host-noise mode, out of range, of the wrong count, a key twice.  SampleResult.crystal_keys carries the keys.
+        None is the sampler as it was, bit for bit, through the exports it used."""
+        if crystal_keys is not None:  # validated before any work and before any generator is touched (the count: below)
+            crystal_keys = keyed_mod.validate_keys(crystal_keys, None, seed, noise if noise in ("philox", "device", "reference") else "philox")
         match_to = structure_match.resolve(match_to)
         reduce_cell = cell_reduction.resolve(reduce_cell)
         symmetrize = symmetrize_mod.resolve(symmetrize)
@@ -601,6 +635,8 @@ class DiffusionLoss(nn.Module):
         elif num_atoms_per_sample is None or num_samples_in_batch is None:
             raise ValueError("num_atoms_per_sample and num_samples_in_batch are needed without a condition")
         B = int(num_samples_in_batch)
+        if crystal_keys is not None:
+            keyed_mod.validate_keys(crystal_keys, B, seed)
         lattice_systems.check(lattice_system, B, condition.lattice_known() if condition is not None else None)
         # species control: the admission rows (None: no set is given), validated with the held species before the engine is touched
         allow_rows = species_mod.resolve_elements(elements, z_table, B) if elements is not None else None
@@ -624,7 +660,8 @@ class DiffusionLoss(nn.Module):
         dt = torch.get_default_dtype()
         if initial_state is None:
             state = self.draw_initial_state(num_atoms_per_sample, B, num_atomic_states=S, constant_atoms=constant_atoms,
-                                            lattice_system=lattice_system, condition=condition, specs=specs)
+                                            lattice_system=lattice_system, condition=condition, specs=specs, seed=seed,
+                                            crystal_keys=crystal_keys, model=model)
         else:  # nothing is drawn: the state as given, its species replaced by the ones to hold when those are given
             state = initial_state
             if constant_atoms is False:
@@ -670,12 +707,16 @@ class DiffusionLoss(nn.Module):
         if noise == "philox" and seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
             rng_state = torch.random.get_rng_state()
+        # keyed sampling: the table of stream seeds (uint64 bits in an int64 tensor), held through every call of the run
+        seeds_d = None
+        if crystal_keys is not None:
+            seeds_d = torch.as_tensor(keyed_mod.stream_seeds(seed, crystal_keys).view(np.int64), device=dev).contiguous()
         cond_d = None
         if condition is not None:
             # rule 5: the known components of the drawn initial state, at the first timestep t_1 (T - 1 without a schedule;
             # Philox key t_1 + 1); the saved initial state of a re-run below includes them
             cond_d = condition.device_arrays(z_table, dev)
-            eng.condition_initial_state(frac_d, types_d, len_d, t_first, seed, cond_d)
+            eng.condition_initial_state(frac_d, types_d, len_d, t_first, seed, cond_d, offsets=off_d, crystal_seeds=seeds_d)
             init_state = (frac_d.clone(), types_d.clone(), len_d.clone())
 
         corrector = (corrector_steps, corrector_snr) if corrector_steps > 0 else None
@@ -709,7 +750,7 @@ class DiffusionLoss(nn.Module):
                         eng.sample_loop(frac_d, types_d, len_d, ang_d, off_d, steps[start], end - start, seed, const_d, lattice_d,
                                         use_graph=bool(use_graph), fixed_lengths=fixed, condition=cond_d, next_table=next_d,
                                         lattice_clipmax=clipmax, corrector=corrector, resampling=resampling, length_tie=tie_d,
-                                        symmetry=sym_d, eta=eta, multistep=history, species=species_ctl)
+                                        symmetry=sym_d, eta=eta, multistep=history, species=species_ctl, crystal_seeds=seeds_d)
                         start = end
                     if j is not None:
                         vis_crystal_during_sampling(z_table, types_d.cpu().numpy(), lattice_d.cpu().numpy(),
@@ -825,4 +866,5 @@ class DiffusionLoss(nn.Module):
         return SampleResult(num_atoms=num_atoms.numpy(), frac_x=frac_d.cpu().numpy().astype(np.float64),
                             atomic_numbers=atomic_numbers, lattice=lattice_d.cpu().numpy().astype(np.float64), info=info,
                             metrics=metrics, uniqueness=uniqueness, symmetry=found, reduced=reduced,
-                            symmetrized=symmetrized, match=match)
+                            symmetrized=symmetrized, match=match,
+                            crystal_keys=np.array(crystal_keys, dtype=np.int64) if crystal_keys is not None else None)

@@ -15,7 +15,10 @@ symmetry_search.SYM_KEYS, cell_reduction.REDUCED_KEYS, symmetrize.SYMMETRIZED_KE
 each holds).  One row per crystal, except the per-atom keys: of the result's atoms [sum n] for symmetrized_* and match_*, of the
 reduced crystals' [sum reduced_num_atoms] for reduced_*.  Readers of the five keys above are not affected; a result without an
 instrument's arrays is written without them, and a reader gets back None.  A reader gets the symmetry search's arrays back with
-`lattice` filled in from the file's cells."""
+`lattice` filled in from the file's cells.
+
+A keyed result (SampleResult.crystal_keys; diffusion/keyed.py) gets one more array, `crystal_keys` [B] int64, after all of those; a
+result without keys is written exactly as before, and a reader of a file without the array gets back None."""
 import os
 
 import numpy as np
@@ -44,6 +47,12 @@ def _fields(crystals: SampleResult):
         arrays = getattr(crystals, e.field, None)
         if arrays is not None:
             out.update(file_fields(e, arrays, B, n_tot))
+    keys = getattr(crystals, "crystal_keys", None)
+    if keys is not None:
+        keys = np.asarray(keys).astype(np.int64, copy=False)
+        if keys.shape != (B,):
+            raise ValueError("SampleResult.crystal_keys must hold one key per crystal")
+        out["crystal_keys"] = keys
     return out
 
 
@@ -54,6 +63,8 @@ def _read(has, get):
         data[e.field] = {k: get(e.prefix + k) for k in e.keys} if all(has(e.prefix + k) for k in e.keys) else None
     if data["symmetry"] is not None:  # (the search saw the float32 cells)
         data["symmetry"]["lattice"] = np.asarray(data["lattice"], dtype=np.float32).reshape(-1, 3, 3)
+    if has("crystal_keys"):
+        data["crystal_keys"] = np.asarray(get("crystal_keys"), dtype=np.int64)
     return SampleResult(**data)
 
 

@@ -62,17 +62,20 @@ def check(lattice_system: LatticeSystemArg, B: int, lattice_known=None) -> Optio
     return names
 
 
-def resolve(lattice_system: LatticeSystemArg, B: int, lattice_known=None):
+def resolve(lattice_system: LatticeSystemArg, B: int, lattice_known=None, uniforms=None):
     """(angles [B,3] float64, tie codes int32 [B] or None).  Validates first (`check`), then draws the angles per crystal in
     order from `sample_bravais_angles` on numpy's global generator: radians for a named system, and for None (the whole
-    argument, or one crystal's entry) today's monoclinic draw in degrees, unconverted, with code 0."""
+    argument, or one crystal's entry) today's monoclinic draw in degrees, unconverted, with code 0.
+    `uniforms` (keyed sampling): one uniform(low, high) source per crystal (keyed.angle_uniforms), used instead of numpy's
+    generator, which is then not touched."""
     from .diffusion_helpers import sample_bravais_angles  # (needs torch; the names and tie codes above do not)
     names = check(lattice_system, B, lattice_known)
+    src = (lambda b: None) if uniforms is None else (lambda b: uniforms[b])
     if names is None:
-        return np.array([sample_bravais_angles("monoclinic") for _ in range(B)]), None
+        return np.array([sample_bravais_angles("monoclinic", src(b)) for b in range(B)]), None
     angles = np.empty((B, 3), dtype=np.float64)
     for b, name in enumerate(names):
-        angles[b] = sample_bravais_angles("monoclinic") if name is None else np.deg2rad(sample_bravais_angles(name))
+        angles[b] = sample_bravais_angles("monoclinic", src(b)) if name is None else np.deg2rad(sample_bravais_angles(name, src(b)))
     codes = np.array([0 if name is None else TIE_CODES[name] for name in names], dtype=np.int32)
     return angles, codes
 

@@ -257,7 +257,7 @@ class HipEngine:
 
     def sample_loop(self, frac, types, lengths, angles, offsets, t_start, n_steps, seed, const_types, lattice_out,
                     use_graph=False, fixed_lengths=None, condition=None, next_table=None, lattice_clipmax=0.999, corrector=None,
-                    resampling=None, length_tie=None, symmetry=None, eta=None, multistep=None, species=None):
+                    resampling=None, length_tie=None, symmetry=None, eta=None, multistep=None, species=None, crystal_seeds=None):
         """n_steps iterations of the sampling loop in one library call (arreau_sample_loop; with any of the options below
         arreau_sample_loop_resampled, whose NULL options are the loop without them): in-place update of
         (frac, types, lengths); Philox noise keyed by (seed, timestep, draw, element).  `condition`: the device arrays of a
@@ -279,7 +279,15 @@ class HipEngine:
         `multistep`: second-order multistep sampling (arreau_sample_loop_multistep): the dict of history tensors of
         multistep.allocate_history, read and overwritten by every step and never emptied by a call; None is the loop without it.
         Not with `condition`, corrector steps, resampling passes > 1, `symmetry` or an eta other than 0.
-        `species`: species control (arreau_sample_loop_species; see sample_loop_species); None is the loop without it."""
+        `species`: species control (arreau_sample_loop_species; see sample_loop_species); None is the loop without it.
+        `crystal_seeds`: keyed sampling (arreau_sample_loop_keyed; rules in include/arreau_hip.h): a contiguous int64 [B] tensor on
+        the device holding the uint64 stream seeds of keyed.stream_seeds -- every draw of crystal b is then keyed by its seed and
+        counted within the crystal.  The export is the species one plus the table, so without `species` the steps run under
+        (every class, temperature 1).  None is the loop without it, through the export it used."""
+        if crystal_seeds is not None:
+            self._check_seeds(crystal_seeds, lengths.shape[0])
+            if species is None:
+                species = (None, 1.0)
         if multistep is not None:
             from .diffusion.multistep import check_multistep
             check_multistep(True, eta=eta, condition=condition, corrector_steps=corrector[0] if corrector is not None else 0,
@@ -327,6 +335,8 @@ class HipEngine:
             opts += (_hip.ptr(length_tie), _byref(self._symmetry_struct(symmetry, N) if symmetry is not None else None), _byref(eta_c),
                      _byref(self._multistep_struct(multistep, N, B) if multistep is not None else None),
                      _byref(self._species_struct(species, B)))
+            if crystal_seeds is not None:  # keyed sampling: the same loop with the table of stream seeds
+                name, opts = "arreau_sample_loop_keyed", opts + (_hip.ptr(crystal_seeds),)
         elif multistep is not None:
             name, opts = "arreau_sample_loop_multistep", opts + (_hip.ptr(length_tie), _byref(self._multistep_struct(multistep, N, B)))
         elif symmetry is not None:
@@ -376,6 +386,34 @@ class HipEngine:
                 raise ValueError(f"multistep history: {n} must be a contiguous {dtype} tensor of shape {shape} on {self.device}")
         return _hip.MultistepC(*[_hip.ptr(history[n]).value for n in HISTORY_KEYS])
 
+    def _check_seeds(self, crystal_seeds, B):
+        if (not torch.is_tensor(crystal_seeds) or tuple(crystal_seeds.shape) != (B,) or crystal_seeds.dtype != torch.int64
+                or crystal_seeds.device != self.device or not crystal_seeds.is_contiguous()):
+            raise ValueError(f"crystal_seeds must be a contiguous int64 tensor of shape ({B},) on {self.device} (the uint64 stream seeds)")
+
+    def philox_fill_crystals(self, crystal_seeds, offsets, timestep, kind, word3=0, per_atom_width=0, per_crystal_width=0, raw=False):
+        """The keyed draws written out in batch layout (arreau_philox_fill_crystals): per_atom_width = w gives [N, w] (row of atom a
+        of crystal b: elements a w .. a w + w - 1 of its stream), per_crystal_width = w gives [B, w]; normal or uniform by kind.
+        raw=True: also the raw words, int32 [.., w, 4]."""
+        B = int(crystal_seeds.shape[0])
+        self._check_seeds(crystal_seeds, B)
+        if (per_atom_width > 0) == (per_crystal_width > 0):
+            raise ValueError("philox_fill_crystals: give either per_atom_width or per_crystal_width")
+        w = int(per_atom_width or per_crystal_width)
+        rows = int(offsets[-1].item()) if per_atom_width > 0 else B
+        out = torch.empty((rows, w), device=self.device, dtype=torch.float32)
+        words = torch.empty((rows, w, 4), device=self.device, dtype=torch.int32) if raw else None
+        _hip.check(_hip.lib().arreau_philox_fill_crystals(
+            _hip.ptr(crystal_seeds), _hip.ptr(offsets), B, int(timestep), int(kind), int(word3) & (2 ** 32 - 1), int(per_atom_width),
+            int(per_crystal_width), _hip.ptr(out), _hip.ptr(words), _hip.stream_ptr(self.device)), "arreau_philox_fill_crystals")
+        return (out, words) if raw else out
+
+    def keyed_initial_draws(self, crystal_seeds, offsets):
+        """Rule 3 of keyed sampling: the standard normals of the initial lengths [B,3] (kind 13) and positions [N,3] (kind 14)."""
+        from .diffusion.keyed import KIND_INIT_FRAC, KIND_INIT_LENGTHS
+        return (self.philox_fill_crystals(crystal_seeds, offsets, 0, KIND_INIT_LENGTHS, per_crystal_width=3),
+                self.philox_fill_crystals(crystal_seeds, offsets, 0, KIND_INIT_FRAC, per_atom_width=3))
+
     def _check_tie(self, length_tie, B):
         if (tuple(length_tie.shape) != (B,) or length_tie.dtype != torch.int32 or length_tie.device != self.device
                 or not length_tie.is_contiguous()):
@@ -405,11 +443,20 @@ class HipEngine:
         return _hip.SymmetryC(*[_hip.ptr(tables[n]).value for n in names], n_orb, tables["orbit_atoms"].numel(),
                               tables["stab_ops"].numel(), n_ops)
 
-    def condition_initial_state(self, frac, types, lengths, t_start, seed, condition):
+    def condition_initial_state(self, frac, types, lengths, t_start, seed, condition, offsets=None, crystal_seeds=None):
         """Rule 5 of conditioned sampling (arreau_condition_initial_state): the known components of an initial state drawn
-        for timestep t_start, in place."""
+        for timestep t_start, in place.  `crystal_seeds` (with `offsets`): keyed sampling (arreau_condition_initial_state_keyed)."""
         N, B = frac.shape[0], lengths.shape[0]
         cond = self._condition_struct(condition, N, B)
+        if crystal_seeds is not None:
+            self._check_seeds(crystal_seeds, B)
+            if offsets is None:
+                raise ValueError("condition_initial_state: crystal_seeds need the crystal offsets")
+            _hip.check(_hip.lib().arreau_condition_initial_state_keyed(
+                self._handle, _hip.ptr(frac), _hip.ptr(types), _hip.ptr(lengths), _hip.ptr(offsets), B, N, int(t_start),
+                int(seed) & (2 ** 64 - 1), ctypes.byref(cond), _hip.ptr(crystal_seeds), _hip.stream_ptr(self.device)),
+                "arreau_condition_initial_state_keyed")
+            return
         _hip.check(_hip.lib().arreau_condition_initial_state(
             self._handle, _hip.ptr(frac), _hip.ptr(types), _hip.ptr(lengths), B, N, int(t_start), int(seed) & (2 ** 64 - 1),
             ctypes.byref(cond), _hip.stream_ptr(self.device)), "arreau_condition_initial_state")
@@ -859,13 +906,21 @@ class HipEngine:
             _hip.stream_ptr(self.device)), name)
 
     def noise_state(self, frac, types, lengths, angles, offsets, t, seed, lattice_out, const_types=None, fixed_lengths=None,
-                    length_tie=None):
+                    length_tie=None, crystal_seeds=None):
         """Forward noising of a clean state to level t in place (arreau_noise_state; rules in include/arreau_hip.h): the jump
         (0, t) of every crystal with Philox draws (seed, t, kinds 6 / 7 / 8, element, word3 = 0).  Held: const_types,
-        fixed_lengths; `length_tie` ties the lengths (int32 [B] codes)."""
+        fixed_lengths; `length_tie` ties the lengths (int32 [B] codes).  `crystal_seeds`: keyed sampling
+        (arreau_noise_state_keyed): the draws keyed by every crystal's stream seed, elements counted within it."""
         B, N = lengths.shape[0], frac.shape[0]
         if length_tie is not None:
             self._check_tie(length_tie, B)
+        if crystal_seeds is not None:
+            self._check_seeds(crystal_seeds, B)
+            _hip.check(_hip.lib().arreau_noise_state_keyed(
+                self._handle, _hip.ptr(frac), _hip.ptr(types), _hip.ptr(lengths), _hip.ptr(angles), _hip.ptr(offsets), B, N, int(t),
+                int(seed) & (2 ** 64 - 1), _hip.ptr(const_types), _hip.ptr(fixed_lengths), _hip.ptr(lattice_out), _hip.ptr(length_tie),
+                _hip.ptr(crystal_seeds), _hip.stream_ptr(self.device)), "arreau_noise_state_keyed")
+            return
         _hip.check(_hip.lib().arreau_noise_state(
             self._handle, _hip.ptr(frac), _hip.ptr(types), _hip.ptr(lengths), _hip.ptr(angles), _hip.ptr(offsets), B, N, int(t),
             int(seed) & (2 ** 64 - 1), _hip.ptr(const_types), _hip.ptr(fixed_lengths), _hip.ptr(lattice_out), _hip.ptr(length_tie),

@@ -63,6 +63,14 @@ Structure match: `--match_to FILE` (`--ltol`, `--angle_tol`, `--stol`) matches e
 its sampling call, against every target of its composition in that crystals file (diffusion/structure_match.py) and keeps the best:
 match rate (matched / attempted) and mean rms_norm and rms over the matched, per rank and in total, and match_* arrays in the
 output file.  The optimal assignment only with `--assignment optimal`, no supercells (combine with a reduced target file), no volume scaling.
+
+Keyed sampling: `--keyed` (needs `--seed`) makes every crystal a function of (seed, key) alone (diffusion/keyed.py).  Every rank
+uses the same seed; output slot k of `--num_crystals` has key k on its first attempt.  With `--require_valid`, attempt a of slot k
+has key a * num_crystals + k and the slot keeps its first valid attempt; every rank retries only the slots of its slice that are
+still open, up to `--max_rounds`, and a shortfall is reported, not padded.  The file (which then also holds `crystal_keys`) is the
+same for every world size and every `--batch` -- up to where the score network changes its kernels with the size of a launch
+(keyed.py, rule 5).  `--keys 17,4711` regenerates those slots alone.  `--template` and `--start_from` runs key a crystal by its
+index in the file times `--samples_per_template` plus the copy.  Without `--keyed` nothing changes, `seed + rank` included.
 """
 import argparse
 import contextlib
@@ -103,7 +111,11 @@ def concat_results(parts) -> SampleResult:
         return SampleResult(frac_x=np.empty((0, 3)), atomic_numbers=np.empty((0,)), lattice=np.empty((0, 3, 3)),
                             idx_start=np.empty((0,), dtype=np.int64), num_atoms=np.empty((0,), dtype=np.int64), info=info)
     num_atoms = np.concatenate([np.asarray(p.num_atoms) for p in parts])
+    keys = None  # keyed sampling: carried when every part has them
+    if all(getattr(p, "crystal_keys", None) is not None for p in parts):
+        keys = np.concatenate([np.asarray(p.crystal_keys, dtype=np.int64) for p in parts])
     return SampleResult(
+        crystal_keys=keys,
         frac_x=np.concatenate([p.frac_x for p in parts]), atomic_numbers=np.concatenate([p.atomic_numbers for p in parts]),
         lattice=np.concatenate([p.lattice for p in parts]), num_atoms=num_atoms, idx_start=np.cumsum(num_atoms) - num_atoms, info=info,
         **{e.field: instruments.concat(e, [getattr(p, e.field) for p in parts]) for e in INSTRUMENTS})
@@ -117,6 +129,7 @@ def select_crystals(res: SampleResult, keep) -> SampleResult:
     kept = num_atoms[keep]
     return SampleResult(frac_x=np.asarray(res.frac_x)[atoms], atomic_numbers=np.asarray(res.atomic_numbers)[atoms],
                         lattice=np.asarray(res.lattice)[keep], num_atoms=kept, idx_start=np.cumsum(kept) - kept,
+                        crystal_keys=np.asarray(res.crystal_keys)[keep] if getattr(res, "crystal_keys", None) is not None else None,
                         **{e.field: instruments.select(e, getattr(res, e.field), keep, atoms) for e in INSTRUMENTS})
 
 
@@ -238,6 +251,66 @@ def generate_valid_crystals(sample_fn: Callable[[int, int], SampleResult], num_c
     return _gather_results(local, rank, world_size, gather, unique)
 
 
+def generate_keyed(sample_keys: Callable, slots, num_crystals: int, num_crystals_per_batch: int = 256, rank: int = 0,
+                   world_size: int = 1, gather: Optional[Callable] = None, require_valid: bool = False, max_rounds: int = 10,
+                   unique=None) -> Optional[SampleResult]:
+    """The keyed driver (diffusion/keyed.py: fill_slots): sample_keys(keys) -> SampleResult of the crystals with those keys (e.g.
+    PONITA_DIFFUSION.sample(n, len(keys), seed=s, crystal_keys=keys); with require_valid: WITH metrics).  This rank's contiguous
+    share of `slots` (slots of a run of num_crystals) is sampled under slot_key(slot, attempt, num_crystals); with require_valid
+    a slot keeps its first valid attempt and only open slots are retried, up to max_rounds.  The crystals come back in slot
+    order with their keys (SampleResult.crystal_keys; slot = key % num_crystals), so the gathered result does not depend on
+    world_size or the batch size.  A shortfall is warned about and left in the statistics; nothing is padded."""
+    import warnings
+
+    from .diffusion import keyed
+    valid_of = None
+    if require_valid:
+        def valid_of(res):
+            if res.metrics is None:
+                raise ValueError("generate_keyed: sample_keys must return the screen's metrics (sample(..., screen=...))")
+            return res.metrics["valid"]
+    start, stop = shard_range(len(slots), world_size, rank)
+    mine = list(slots)[start:stop]
+    accepted, attempts = keyed.fill_slots(sample_keys, mine, num_crystals, num_crystals_per_batch, valid_of, max_rounds)
+    kept = []
+    for slot, key, res, i in accepted:
+        keep = np.zeros(len(np.asarray(res.num_atoms)), dtype=bool)
+        keep[i] = True
+        one = select_crystals(res, keep)
+        one.crystal_keys = np.array([key], dtype=np.int64)
+        kept.append(one)
+    local = concat_results(kept)
+    if require_valid:
+        from .diffusion.screening import stats_of
+        flags = [np.asarray(res.metrics["flags"]) for res, _, _ in attempts]
+        rounds = 0 if not attempts else max(k // int(num_crystals) for _, _, keys in attempts for k in keys) + 1
+        local.info = {"screen_stats": [stats_of(np.concatenate(flags) if flags else np.empty(0, np.int64), rank, requested=len(mine),
+                                                rounds=rounds)]}
+        if len(accepted) < len(mine):
+            warnings.warn(f"generate_keyed: rank {rank} has {len(accepted)} valid crystals of the {len(mine)} requested after "
+                          f"{rounds} round(s); the result is {len(mine) - len(accepted)} short")
+    return _gather_results(local, rank, world_size, gather, unique)
+
+
+def check_keyed_arguments(args, error):
+    """The combinations of --keyed / --keys; `error(message)` reports a bad one.  Returns the slots to generate (None: not keyed)."""
+    if not args.keyed:
+        if args.keys is not None:
+            error("--keys needs --keyed")
+        return None
+    if args.seed is None:
+        error("--keyed needs --seed: a crystal is a function of (seed, key)")
+    if args.keys is None:
+        return list(range(args.num_crystals))
+    if args.template is not None or args.start_from is not None:
+        error("--keys names output slots of --num_crystals; not with --template / --start_from")
+    from .diffusion import keyed
+    try:
+        return keyed.parse_keys(args.keys, args.num_crystals)
+    except ValueError as e:
+        error(str(e))
+
+
 def save_sample_results(crystals: SampleResult, filename: str):
     """The reference's crystals.h5 layout (diffusion/inference/process_generated_crystals.py:8-15)."""
     from .diffusion.inference.process_generated_crystals import save_sample_results_to_hdf5
@@ -306,7 +379,13 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--num_atoms", type=int, default=4)
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--out", type=str, default="out/crystals.npz")
-    ap.add_argument("--seed", type=int, default=None, help="seed of the host/device generators (rank is added)")
+    ap.add_argument("--seed", type=int, default=None, help="seed of the host/device generators (rank is added; with --keyed: the "
+                    "seed of every crystal's stream, the same on every rank)")
+    ap.add_argument("--keyed", action="store_true",
+                    help="keyed sampling: every crystal is a function of (--seed, its key) alone, so the output does not depend on "
+                         "the number of ranks or --batch; slot k has key k (needs --seed)")
+    ap.add_argument("--keys", type=str, default=None, metavar="LIST",
+                    help="--keyed: regenerate only these comma-separated output slots of --num_crystals (e.g. 17,4711)")
     ap.add_argument("--template", type=str, default=None,
                     help="crystals.npz / .h5 of templates (optional position_mask / species_mask / lattice_mask arrays)")
     ap.add_argument("--fix", type=str, default="", help="components fixed where the template has no mask: "
@@ -550,6 +629,7 @@ def main():
     ap = build_parser()
     args = ap.parse_args()
     start = check_start_arguments(args, ap.error)
+    slots = check_keyed_arguments(args, ap.error)
     spec = load_symmetry(args, ap.error)
     if spec is not None and args.eta is not None:
         ap.error("--eta is not supported with --symops")
@@ -609,39 +689,52 @@ def main():
         if rank == 0:
             print(f"species control: elements {'any' if args.elements is None else 'Z in {' + species_mod.describe(row, model.hparams.z_table) + '}'}"
                   f", species temperature {args.species_temperature:g}")
-    if args.seed is not None:
-        import numpy as np
+    if args.seed is not None and not args.keyed:  # (a keyed run reads no generator)
         torch.manual_seed(args.seed + rank)
         np.random.seed(args.seed + rank)
+    keyed_kw = lambda keys: dict(seed=args.seed, crystal_keys=[int(k) for k in keys]) if args.keyed else {}
     # ARREAU_GENERATE_GPU_LOCK=<file>: ranks that SHARE one device (the one-GPU rehearsal above) take turns on it -- a file
     # lock held around each sampler call.  On a node every rank owns its GPU and the variable is not set.
     lock_path = os.environ.get("ARREAU_GENERATE_GPU_LOCK")
 
-    def fn(n, b, cond=None):
+    def fn(n, b, cond=None, keys=None):
         with _device_turn(lock_path) if lock_path else contextlib.nullcontext():
-            return model.sample(n, b, VisualizationSetting.NONE, False, condition=cond, num_steps=args.num_steps,
+            return model.sample(n, b, VisualizationSetting.NONE, False, condition=cond, num_steps=args.num_steps, **keyed_kw(keys),
                                 corrector_steps=args.corrector_steps, corrector_snr=args.corrector_snr,
                                 resample_passes=args.resample_passes, jump_length=args.jump_length,
                                 lattice_system=args.lattice_system, symmetry=spec, eta=args.eta, multistep=args.multistep,
                                 **species_kw, **keywords)
     def start_fn(crystals):
         with _device_turn(lock_path) if lock_path else contextlib.nullcontext():
+            keys = crystals.crystal_keys if args.keyed else None  # (the crystal's index in the file: set below)
             state = (model.encode(crystals, t=args.start_t, num_steps=args.num_steps) if args.invert
-                     else model.noise_to(crystals, args.start_t))
+                     else model.noise_to(crystals, args.start_t, **keyed_kw(keys)))
             return model.sample(visualization_setting=VisualizationSetting.NONE, initial_state=state, num_steps=args.num_steps,
+                                **keyed_kw(keys),
                                 use_constant_atomic_symbols=True if args.invert else None, corrector_steps=args.corrector_steps,
                                 corrector_snr=args.corrector_snr, resample_passes=args.resample_passes, jump_length=args.jump_length,
                                 eta=args.eta, multistep=args.multistep, **species_kw, **keywords)
+    n_atoms = spec.n_atoms if spec is not None else args.num_atoms
     if start:
+        if args.keyed:  # the key of a crystal: its index in the file
+            start_crystals.crystal_keys = np.arange(len(np.asarray(start_crystals.num_atoms)), dtype=np.int64)
         res = generate_from_crystals(start_fn, start_crystals, args.batch, rank, world, unique=unique)
+    elif condition is not None and args.keyed:
+        # the key of tiled template j (order t0, t1, ..., t0, t1, ...): its index in the file times samples_per_template plus the copy
+        from .diffusion.keyed import template_key
+        n_file, K = condition.B // args.samples_per_template, args.samples_per_template
+        mine = [fn(None, None, condition.slice(a, b), keys=[template_key(j, n_file, K) for j in range(a, b)])
+                for a, b in template_batches(condition.B, args.batch, rank, world)]
+        res = _gather_results(concat_results(mine), rank, world, None, unique)
     elif condition is not None:
         res = generate_from_template(lambda c: fn(None, None, c), condition, args.batch, rank, world, unique=unique)
+    elif args.keyed:
+        res = generate_keyed(lambda keys: fn(n_atoms, len(keys), keys=keys), slots, args.num_crystals, args.batch, rank, world,
+                             require_valid=args.require_valid, max_rounds=args.max_rounds, unique=unique)
     elif args.require_valid:
-        res = generate_valid_crystals(fn, args.num_crystals, spec.n_atoms if spec is not None else args.num_atoms, args.batch, rank,
-                                      world, max_rounds=args.max_rounds, unique=unique)
+        res = generate_valid_crystals(fn, args.num_crystals, n_atoms, args.batch, rank, world, max_rounds=args.max_rounds, unique=unique)
     else:
-        res = generate_n_crystals(fn, args.num_crystals, spec.n_atoms if spec is not None else args.num_atoms, args.batch, rank,
-                                  world, unique=unique)
+        res = generate_n_crystals(fn, args.num_crystals, n_atoms, args.batch, rank, world, unique=unique)
     if rank == 0:
         special = {"unique": lambda parts: unique_lines(res, unique, device=f"cuda:{local_rank}"),
                    "find_symmetry": lambda parts: symmetry_lines(res, parts, spec)}

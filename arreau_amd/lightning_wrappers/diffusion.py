@@ -400,7 +400,7 @@ class PONITA_DIFFUSION(nn.Module):
                corrector_snr: float = 0.16, resample_passes: int = 1, jump_length: int = 10,
                lattice_system=None, symmetry=None, screen=None, unique=None, find_symmetry=None, reduce_cell=None,
                symmetrize=None, match_to=None, eta: Optional[float] = None, initial_state=None,
-               multistep: bool = False, elements=None, species_temperature: float = 1.0) -> SampleResult:
+               multistep: bool = False, elements=None, species_temperature: float = 1.0, crystal_keys=None) -> SampleResult:
         """lightning_wrappers/diffusion.py:220-253.  `num_atoms_per_sample` may also be a sequence with one atom count
         per crystal of the batch (extension; the reference supports a single int).  Frames of a visualization_setting
         other than NONE go to `<DIFFUSION_DIR>/step_<timestep>.cif` like the reference's PNGs (`vis_name` overrides the
@@ -434,8 +434,13 @@ class PONITA_DIFFUSION(nn.Module):
         None or 0 (DiffusionLoss.sample).  `elements`, `species_temperature` (extension): species control -- per-crystal element
         sets the species step may choose from (one collection for the batch, or a list with one collection or None per crystal)
         and a temperature >= 0 on its Gumbel draw (0: no draw, so eta = 0 and multistep runs are deterministic in all three
-        components); with every option above (DiffusionLoss.sample)."""
-        from ..diffusion import multistep as multistep_mod, resampling, species as species_mod
+        components); with every option above (DiffusionLoss.sample).  `crystal_keys` (extension; needs `seed`, noise="philox"):
+        keyed sampling -- one integer key per crystal; every random number a crystal consumes comes from a stream of its own
+        derived from (seed, key), so the crystal is the same alone, in any batch, at any rank count (diffusion/keyed.py;
+        DiffusionLoss.sample, which states where the guarantee stops)."""
+        from ..diffusion import keyed as keyed_mod, multistep as multistep_mod, resampling, species as species_mod
+        if crystal_keys is not None:  # (raises before any work)
+            crystal_keys = keyed_mod.validate_keys(crystal_keys, None, seed, noise if noise in ("philox", "device", "reference") else "philox")
         species_temperature = species_mod.validate_temperature(species_temperature)  # (raises before any work)
         multistep = multistep_mod.check_multistep(multistep, eta=eta, condition=condition, corrector_steps=corrector_steps,
                                                   resample_passes=resample_passes, symmetry=symmetry)  # (raises before any work)
@@ -476,7 +481,7 @@ class PONITA_DIFFUSION(nn.Module):
             resample_passes=resample_passes, jump_length=jump_length, lattice_system=lattice_system, symmetry=symmetry,
             screen=screen, unique=unique, find_symmetry=find_symmetry, reduce_cell=reduce_cell, symmetrize=symmetrize,
             match_to=match_to, eta=eta, initial_state=initial_state, multistep=multistep, elements=elements,
-            species_temperature=species_temperature)
+            species_temperature=species_temperature, crystal_keys=crystal_keys)
 
     # ---- starting the sampler from given crystals (extension; rules in include/arreau_hip.h) -------------------------------------
     def _crystal_state(self, crystals, t, what):
@@ -526,15 +531,20 @@ class PONITA_DIFFUSION(nn.Module):
 
     @torch.no_grad()
     def noise_to(self, crystals, t: int, seed: Optional[int] = None, constant_atoms: bool = False, fixed_cell: bool = False,
-                 lattice_system=None):
+                 lattice_system=None, crystal_keys=None):
         """Known crystals forward-noised to level t (1..T-1): the state a `sample(initial_state=...)` call denoises from, for
         variants in the neighbourhood of the crystals (SDEdit; "start from existing materials").  `crystals`: a SampleResult or a
         loaded crystals file; lengths and angles come from its cells (matrix_to_params).  One launch of the forward process in
         closed form (arreau_noise_state; rules in include/arreau_hip.h) with Philox draws keyed by (seed, t); `seed` defaults to a
         draw from torch's global CPU generator.  constant_atoms: the species are not noised; fixed_cell: the lengths are not
         noised; lattice_system (one name or one per crystal, None entries allowed): the tied lengths jump together and the tie
-        travels in the state (the angles stay the crystals' own).  Returns a diffusion.inversion.SamplerState at level t."""
-        from ..diffusion import lattice_systems
+        travels in the state (the angles stay the crystals' own).  `crystal_keys` (needs `seed`): keyed sampling -- crystal b is
+        noised with the stream of (seed, crystal_keys[b]), elements counted within it, so its noised state does not depend on
+        the batch (diffusion/keyed.py; arreau_noise_state_keyed); no generator is touched.  Returns a
+        diffusion.inversion.SamplerState at level t."""
+        from ..diffusion import keyed as keyed_mod, lattice_systems
+        if crystal_keys is not None:  # (raises before any work)
+            crystal_keys = keyed_mod.validate_keys(crystal_keys, len(np.asarray(crystals.num_atoms).reshape(-1)), seed)
         state = self._crystal_state(crystals, t, "noise_to")
         names = lattice_systems.check(lattice_system, state.B)
         tie = None if names is None else np.array([0 if n is None else lattice_systems.TIE_CODES[n] for n in names], dtype=np.int32)
@@ -544,8 +554,11 @@ class PONITA_DIFFUSION(nn.Module):
         dev = eng.device
         frac, types, lengths, angles, off, cell = self._state_to_device(state, dev)
         tie_d = torch.as_tensor(tie, device=dev, dtype=torch.int32).contiguous() if tie is not None else None
+        seeds_d = None
+        if crystal_keys is not None:
+            seeds_d = torch.as_tensor(keyed_mod.stream_seeds(seed, crystal_keys).view(np.int64), device=dev).contiguous()
         eng.noise_state(frac, types, lengths, angles, off, state.t, seed, cell, const_types=types.clone() if constant_atoms else None,
-                        fixed_lengths=lengths.clone() if fixed_cell else None, length_tie=tie_d)
+                        fixed_lengths=lengths.clone() if fixed_cell else None, length_tie=tie_d, crystal_seeds=seeds_d)
         eng.check_status()
         return self._state_from_device(state, frac, types, lengths, state.t, tie)
 

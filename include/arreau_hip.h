@@ -1314,6 +1314,66 @@ int arreau_philox_fill(uint64_t seed, int32_t timestep, int32_t kind, int64_t n,
 int arreau_philox_fill_word(uint64_t seed, int32_t timestep, int32_t kind, uint32_t word3, int64_t n, float* d_out,
                             uint32_t* d_raw, void* stream);
 
+/* ---- keyed sampling (a crystal is a function of (seed, key), not of its batch) -------------------------------------------
+ * The loops above key a draw by (seed, timestep, kind, GLOBAL element, word3): element 3 i + d with i the atom's index in the
+ * batch, so a crystal's draws depend on where it sits in the batch.  The keyed loop gives every crystal b a stream of its own,
+ * derived from (seed, key_b), and counts elements inside the crystal.  The reference has no such mode; the rules are the
+ * library's own (restated in arreau_amd/diffusion/keyed.py).
+ *   1. stream seed: for a key 0 <= key < 2^63,
+ *          s_b = stream_seed(seed, key_b) = w0 | w1 << 32,
+ *      w0, w1 words 0 and 1 of philox4x32_10(counter = (key lo, key hi, 0x4B455953, 0), key = (seed lo, seed hi)).  The caller
+ *      computes it on the host in exact integer arithmetic and hands the library the table d_crystal_seeds [B] (uint64, device).
+ *      (seed 5, key 1) and (seed 6, key 0) are different streams, unlike seed + key.
+ *   2. draws of the loop: wherever the Philox loop draws (seed, t, kind, element, word3), the keyed loop draws
+ *      (s_b, t, kind, element', word3), b the crystal of the element and element' counted within it:
+ *          3 a + d   positions (kinds 1, 3, 5, 6),   d   lengths (kinds 0, 4, 7; a tied axis the leader's d = 0),
+ *          a S + c   species (kinds 2, 8),           a the atom's index in its crystal.
+ *      Kinds and word3 keep their meaning (corrector iteration, 256 r in pass r, r for the jump).  Every draw site: the position and
+ *      species halves of the step (plain, eta, multistep, species control), the length components (plain and tied), the symmetric
+ *      step's leaders, the known components of a condition in the step and in the initial state, the corrector, the jump, the
+ *      forward noising of arreau_noise_state.
+ *   3. initial state: kinds 13 (normal [3], the lengths), 14 (normal [n,3], the positions) and 15 (uniform, the j-th uniform the
+ *      crystal's angle draw consumes), at counter timestep 0, word3 0, under s_b.  The host applies its formulas to them exactly
+ *      as to its generators' values.  arreau_philox_fill_crystals writes them out.
+ *   4. hence the state of crystal b after any number of steps is a function of (model, options, seed, key_b, its atom count, its
+ *      own inputs).  Within one score arithmetic it is bitwise independent of the other crystals of the batch, of its index in it
+ *      and of how the run is cut into calls.
+ *   5. limits.  (a) The score network picks its kernels by the size of the launch: batches on different sides of the basis-form
+ *      threshold, or run with and without ARREAU_CROSS_FP8, agree to the bound of the network's batch-independence test, not
+ *      bitwise.  (b) The re-run of a batch after an fp16x3 overflow is a decision about the whole batch: a crystal that shares a
+ *      batch with an overflowing one is re-run with it on other kernels.
+ * Without the table every kernel draws exactly what it drew before the table existed.
+ *
+ * arreau_sample_loop_keyed: arreau_sample_loop_species plus d_crystal_seeds; NULL is arreau_sample_loop_species bit for bit.  Every
+ * combination that loop accepts, both loop forms, the shape-general path, eager and graph replay (the table pointer is part of
+ * what a cached graph was captured for); what it rejects stays rejected. */
+int arreau_sample_loop_keyed(arreau_model* model, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                             const int32_t* d_crystal_offsets, int32_t B, int32_t N, int32_t t_start, int32_t n_steps,
+                             uint64_t seed, const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice,
+                             void* d_workspace, size_t workspace_bytes, int32_t use_graph,
+                             const arreau_sample_condition* cond, const arreau_sample_schedule* schedule,
+                             const arreau_corrector* corrector, const arreau_resampling* resampling, const int32_t* d_length_tie,
+                             const arreau_symmetry* symmetry, const float* eta, const arreau_multistep* multistep,
+                             const arreau_species_control* species, const uint64_t* d_crystal_seeds, void* stream);
+/* arreau_noise_state / arreau_condition_initial_state with the table (the latter also takes the crystal offsets, which it needs
+ * to count within a crystal); a NULL table is the export without it. */
+int arreau_noise_state_keyed(const arreau_model* model, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                             const int32_t* d_crystal_offsets, int32_t B, int32_t N, int32_t t, uint64_t seed,
+                             const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice,
+                             const int32_t* d_length_tie, const uint64_t* d_crystal_seeds, void* stream);
+int arreau_condition_initial_state_keyed(const arreau_model* model, float* d_frac, int32_t* d_types, float* d_lengths,
+                                         const int32_t* d_crystal_offsets, int32_t B, int32_t N, int32_t t_start, uint64_t seed,
+                                         const arreau_sample_condition* cond, const uint64_t* d_crystal_seeds, void* stream);
+/* The keyed draws written out in batch layout: exactly one of per_atom_width / per_crystal_width is positive.  per_atom_width = w:
+ * d_out [N,w], row of atom a of crystal b = the draws (d_seeds[b], timestep, kind, a w + c, word3), c < w (w = 3 for positions,
+ * S for species).  per_crystal_width = w: d_out [B,w], row b = the draws of elements 0..w-1.  Normal for kinds 0, 1, 3..7, 13, 14,
+ * uniform [0,1) for kinds 2, 8, 15; kinds 9..12 are rejected.  d_raw (may be NULL; d_out may be NULL with it): the four raw words
+ * per element.  Fed to arreau_reverse_step*, arreau_corrector_step and arreau_resample_jump*, these arrays reproduce the keyed
+ * loop bit for bit (a tied axis reads the leader's entry of the [B,3] array, as in the loop). */
+int arreau_philox_fill_crystals(const uint64_t* d_seeds, const int32_t* d_crystal_offsets, int32_t B, int32_t timestep,
+                                int32_t kind, uint32_t word3, int32_t per_atom_width, int32_t per_crystal_width, float* d_out,
+                                uint32_t* d_raw, void* stream);
+
 /* ---- score-matching training loss, forward part (BASELINE config 5) ------------------------------------------ */
 
 /* The forward-noising half of DiffusionLoss.__call__ (diffusion/diffusion_loss.py:222-234), random draws supplied by
