@@ -33,6 +33,7 @@ EXPORTS = [
     "arreau_sample_loop_eta", "arreau_reverse_step_eta",
     "arreau_crystal_fingerprint", "arreau_fingerprint_match", "arreau_crystal_symmetry", "arreau_crystal_reduce",
     "arreau_crystal_symmetrize", "arreau_structure_match", "arreau_structure_match_assigned",
+    "arreau_crystal_conventional",
     "arreau_noise_state", "arreau_invert_step", "arreau_invert_loop",
     "arreau_sample_loop_multistep", "arreau_reverse_step_multistep",
     "arreau_sample_loop_species", "arreau_reverse_step_species",
@@ -153,6 +154,12 @@ class SymmetrizeResultC(Structure):
                                                 "max_displacement", "rms_displacement", "ops_translation", "ops_shift", "partner", "flags")]
 
 
+class ConventionalResultC(Structure):
+    """arreau_conventional_result: the nine per-crystal and three per-atom device arrays the conventional-cell launch writes."""
+    _fields_ = [(name, c_void_p) for name in ("lattice", "lengths", "angles", "transform", "centring", "bravais", "n_points", "num_atoms",
+                                                "flags", "frac_out", "types_out", "source")]
+
+
 class StructureMatchParamsC(Structure):
     """arreau_structure_match_params: the tolerances of the structure match and the lattice mappings tried per pair."""
     _fields_ = [("ltol", c_float), ("angle_tol", c_float), ("stol", c_float), ("max_mappings", c_int32)]
@@ -260,6 +267,7 @@ def _prototypes():
         "arreau_crystal_symmetry": [vp] * 4 + [i32, i32, POINTER(SymmetryParamsC), POINTER(SymmetryResultC), vp],
         "arreau_crystal_reduce": [vp] * 4 + [i32, i32, POINTER(ReduceParamsC), POINTER(ReduceResultC), vp],
         "arreau_crystal_symmetrize": [vp] * 4 + [i32, i32, POINTER(SymmetryResultC), i32, POINTER(SymmetrizeResultC), vp],
+        "arreau_crystal_conventional": [vp] * 4 + [i32, i32, POINTER(SymmetryResultC), i32, POINTER(ConventionalResultC), vp],
         "arreau_structure_match": ([vp] * 4 + [i32, i32]) * 2 + [vp, i32, POINTER(StructureMatchParamsC), POINTER(StructureMatchResultC), vp],
         "arreau_structure_match_assigned": ([vp] * 4 + [i32, i32]) * 2 + [vp, i32, POINTER(StructureMatchParamsC), POINTER(StructureMatchResultC),
                                             i32, vp, vp],

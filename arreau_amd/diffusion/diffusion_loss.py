@@ -24,6 +24,7 @@ from . import uniqueness as uniqueness_mod
 from . import cell_reduction
 from . import symmetry_search
 from . import symmetrize as symmetrize_mod
+from . import conventional_cell as conventional_mod
 from . import structure_match
 from .d3pm import D3PM
 from . import lattice_systems
@@ -76,6 +77,10 @@ class SampleResult:
     # arrays target, n_comparable, rms, rms_norm, max_dist, mapping, translation, n_mappings, n_candidates, n_permutations, matched
     # and flags, one row per crystal, and partner, one row per atom; None when it was not asked for
     match: Optional[dict] = None
+    # extension: the conventional cells of the final state (sample(conventional_cell=...); diffusion/conventional_cell.py) -- numpy
+    # arrays lattice, lengths, angles, transform, centring, bravais, n_points, num_atoms and flags, one row per crystal, and the
+    # conventional crystals' frac_x, atomic_numbers and source as a dense ragged batch; None when it was not asked for
+    conventional: Optional[dict] = None
 
 
 class _PinnedRing:
@@ -418,7 +423,8 @@ class DiffusionLoss(nn.Module):
                corrector_snr: float = pc.DEFAULT_SNR, resample_passes: int = 1, jump_length: int = 10,
                lattice_system=None, symmetry=None, screen=None, unique=None, find_symmetry=None, reduce_cell=None,
                symmetrize=None, match_to=None, eta: Optional[float] = None, initial_state=None,
-               multistep: bool = False, elements=None, species_temperature: float = 1.0, crystal_keys=None) -> SampleResult:
+               multistep: bool = False, elements=None, species_temperature: float = 1.0, crystal_keys=None,
+               conventional_cell=None) -> SampleResult:
         """diffusion_loss.py:276-377.  The initial state is drawn on the host exactly like the reference (numpy
         uniforms for the angles, then randn lengths, randn fractional coordinates from torch's global CPU generator):
         draw_initial_state, which a caller may also use on its own.
@@ -561,6 +567,15 @@ class DiffusionLoss(nn.Module):
         atomic numbers are the species ids.  SampleResult.match then holds the arrays (structure_match.MATCH_KEYS).  It reads the
         state as sampled, like the other instruments.  The optimal assignment only with StructureMatchParams(assignment="optimal"), no supercells, no volume scaling.  None: no launch
         is added, match is None and the results are what they were, bit for bit.
+        `conventional_cell` (extension, every noise mode and option): a conventional_cell.ConventionalCellParams (the symmetry
+        search's symprec and max_ops), or True for its defaults -- on the final device state the reduction's launch (shared with
+        `reduce_cell` when both are given: their symprec must then agree, as must find_symmetry's and symmetrize's parameters), the
+        symmetry search on the REDUCED batch and one more launch (arreau_crystal_conventional; rules in include/arreau_hip.h) give
+        every crystal its conventional cell with the atoms in it, the centring, the Bravais lattice (aP .. cF) and, through
+        conventional_cell.pearson_symbol, the Pearson symbol.  SampleResult.conventional then holds the arrays
+        (conventional_cell.CONVENTIONAL_KEYS); frac_x, lattice and every other field stay as sampled, and the other instruments still
+        read that state.  No space-group number, no origin shift, no idealised metric.  None: no launch is added, conventional is
+        None and the results are what they were, bit for bit.
         `crystal_keys` (extension, noise="philox" with a `seed`): keyed sampling (keyed.py; rules in include/arreau_hip.h;
         arreau_sample_loop_keyed) -- one integer key in 0..2^63-1 per crystal, no key twice.  Every random number crystal b consumes
         -- its initial angles, lengths and positions, every draw of every step, corrector move and jump, the known components of a
@@ -578,6 +593,8 @@ class DiffusionLoss(nn.Module):
         reduce_cell = cell_reduction.resolve(reduce_cell)
         symmetrize = symmetrize_mod.resolve(symmetrize)
         symmetrize_mod.check_shared_search(symmetrize, symmetry_search.resolve(find_symmetry))
+        conventional_cell = conventional_mod.resolve(conventional_cell)
+        conventional_mod.check_shared(conventional_cell, reduce_cell, symmetry_search.resolve(find_symmetry), symmetrize)
         screen = screening.resolve(screen)
         unique = uniqueness_mod.resolve(unique)
         find_symmetry = symmetry_search.resolve(find_symmetry)
@@ -853,10 +870,15 @@ class DiffusionLoss(nn.Module):
         if symmetrize is not None:  # (found_d: the search's launch is shared)
             symmetrized = symmetrize_mod.sample_arrays(symmetrize_mod.result_to_numpy(
                 eng.symmetrize(frac_d, lattice_d, off_d, types_d, symmetrize, found_d)))
-        reduced = None
+        reduced = reduced_d = None
         if reduce_cell is not None:
-            reduced = cell_reduction.result_to_numpy(eng.reduce_cells(frac_d, lattice_d, off_d, types_d, reduce_cell))
+            reduced_d = eng.reduce_cells(frac_d, lattice_d, off_d, types_d, reduce_cell)
+            reduced = cell_reduction.result_to_numpy(reduced_d)
             reduced = cell_reduction.sample_arrays(reduced, atomic_number_indexes_to_atomic_numbers(z_table, reduced["types"]))
+        conventional = None
+        if conventional_cell is not None:  # (reduced_d: the reduction's launch is shared)
+            conventional = conventional_mod.result_to_numpy(eng.conventional_cell(frac_d, lattice_d, off_d, types_d, conventional_cell, reduced_d))
+            conventional = conventional_mod.sample_arrays(conventional, atomic_number_indexes_to_atomic_numbers(z_table, conventional["types"]))
         atomic_numbers = atomic_number_indexes_to_atomic_numbers(z_table, types_d.cpu().numpy())
         match = None
         if match_to is not None:  # (the atomic numbers are the species ids the targets carry: one small upload)
@@ -866,5 +888,5 @@ class DiffusionLoss(nn.Module):
         return SampleResult(num_atoms=num_atoms.numpy(), frac_x=frac_d.cpu().numpy().astype(np.float64),
                             atomic_numbers=atomic_numbers, lattice=lattice_d.cpu().numpy().astype(np.float64), info=info,
                             metrics=metrics, uniqueness=uniqueness, symmetry=found, reduced=reduced,
-                            symmetrized=symmetrized, match=match,
+                            symmetrized=symmetrized, match=match, conventional=conventional,
                             crystal_keys=np.array(crystal_keys, dtype=np.int64) if crystal_keys is not None else None)

@@ -1,15 +1,16 @@
 """The per-crystal instruments that run on the final sampled state -- screen, duplicate detection, symmetry search, cell reduction,
-symmetrization, structure match -- as one table, in the order their arrays appear in a crystals file.  An entry holds what the
+symmetrization, structure match -- as one table, in the order their arrays appear in a crystals file, and after them the DERIVED
+ones, which chain those launches (the conventional cell: reduction, search on the reduced cell, conventional basis).  An entry holds what the
 instruments differ in for the host-side plumbing: the file layer (inference/process_generated_crystals.py), the batch driver
 (generate.py) and `python -m arreau_amd.screen` loop over it.  The stored keys are the owning modules' own tuples.  Needs numpy
-alone at import, as the six modules do."""
+alone at import, as the modules do."""
 from dataclasses import dataclass
 from types import ModuleType
 from typing import Optional
 
 import numpy as np
 
-from . import cell_reduction, screening, structure_match, symmetrize, symmetry_search, uniqueness
+from . import cell_reduction, conventional_cell, screening, structure_match, symmetrize, symmetry_search, uniqueness
 
 
 @dataclass(frozen=True)
@@ -51,7 +52,14 @@ INSTRUMENTS = (
     Instrument("match_to", "match", "match_", "match_stats", structure_match, structure_match.MATCH_KEYS, "StructureMatchParams",
                (("ltol", "ltol"), ("angle_tol", "angle_tol"), ("stol", "stol"), ("assignment", "assignment")), "structure match", atom_keys=structure_match.ATOM_KEYS),
 )
-BY_KEYWORD = {e.keyword: e for e in INSTRUMENTS}
+# what is built on the six above: in a crystals file, in the summaries and on the command lines after them
+DERIVED = (
+    Instrument("conventional_cell", "conventional", "conventional_", "conventional_stats", conventional_cell,
+               conventional_cell.CONVENTIONAL_KEYS, "ConventionalCellParams", _SYMPREC, "conventional cell",
+               atom_keys=conventional_cell.ATOM_KEYS, atoms_from="num_atoms"),
+)
+ALL = INSTRUMENTS + DERIVED
+BY_KEYWORD = {e.keyword: e for e in ALL}
 
 
 def concat(entry, parts):

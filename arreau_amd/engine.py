@@ -33,6 +33,12 @@ def reduce_cells(frac, lattice, offsets, types, params=None):
     return cell_reduction.reduce_cells(frac, lattice, offsets, types, params)
 
 
+def conventional_cell(frac, lattice, offsets, types, params=None, reduced=None):
+    """The conventional cells without an engine (arreau_crystal_conventional needs no model): diffusion.conventional_cell.conventional_cell."""
+    from .diffusion import conventional_cell as conventional_mod
+    return conventional_mod.conventional_cell(frac, lattice, offsets, types, params, reduced)
+
+
 def symmetrize(frac, lattice, offsets, types, params=None, found=None):
     """The symmetrization without an engine (arreau_crystal_symmetrize needs no model): diffusion.symmetrize.symmetrize."""
     from .diffusion import symmetrize as symmetrize_mod
@@ -981,6 +987,16 @@ class HipEngine:
         if frac.device != self.device:
             raise ValueError(f"symmetrize: the state must be on {self.device}")
         return symmetrize_mod.symmetrize(frac, lattice, offsets, types, params, found)
+
+    def conventional_cell(self, frac, lattice, offsets, types, params=None, reduced=None):
+        """The conventional cells of a batch on this engine's device (arreau_crystal_reduce, arreau_crystal_symmetry on the reduced
+        batch, arreau_crystal_conventional; diffusion/conventional_cell.py: `conventional_cell`, which needs no engine): the batch as
+        for `reduce_cells`, params a ConventionalCellParams or None (the defaults), reduced the dict of `reduce_cells` on the same
+        tensors with the same symprec or None (the reduction is then launched here).  Returns its dict of device tensors."""
+        from .diffusion import conventional_cell as conventional_mod
+        if frac.device != self.device:
+            raise ValueError(f"conventional_cell: the state must be on {self.device}")
+        return conventional_mod.conventional_cell(frac, lattice, offsets, types, params, reduced)
 
     def find_symmetry(self, frac, lattice, offsets, types, params=None):
         """The symmetry search of a batch on this engine's device (arreau_crystal_symmetry; diffusion/symmetry_search.py:

@@ -81,7 +81,7 @@ import numpy as np
 
 from .diffusion import instruments
 from .diffusion.diffusion_loss import SampleResult
-from .diffusion.instruments import INSTRUMENTS
+from .diffusion.instruments import ALL as INSTRUMENTS
 
 
 def shard_range(num_items: int, world_size: int, rank: int):
@@ -449,6 +449,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="symmetrize every generated crystal on the device with the operations found within --symprec: exact "
                          "orbits, averaged positions and cell; histogram of orbit counts and flags and the largest displacement "
                          "per rank and in total + symmetrized_* arrays in the output file")
+    ap.add_argument("--conventional_cell", action="store_true",
+                    help="give every generated crystal its conventional cell on the device (reduction, symmetry search on the reduced "
+                         "cell, conventional basis; tolerance --symprec): centring, Bravais lattice and Pearson symbol; histogram of "
+                         "Bravais lattices and flags per rank and in total + conventional_* arrays in the output file")
     ap.add_argument("--match_to", default=None, metavar="FILE",
                     help="match every generated crystal against the targets of a crystals file on the device (the best target of its "
                          "composition): match rate and mean RMSD per rank and in total + match_* arrays in the output file")
@@ -469,7 +473,7 @@ def add_structure_match_arguments(ap):
 def instrument_params(keyword, args, error):
     """The parameters of one instrument (its sample() keyword: instruments.BY_KEYWORD) from its flags -- screen: a ScreenCriteria,
     unique: a FingerprintParams, find_symmetry: a SymmetrySearchParams, reduce_cell: a CellReductionParams, symmetrize: a
-    SymmetrizeParams, match_to: a StructureMatchParams; what has no flag keeps its default.  `error(message)` reports a bad value."""
+    SymmetrizeParams, match_to: a StructureMatchParams, conventional_cell: a ConventionalCellParams; what has no flag keeps its default.  `error(message)` reports a bad value."""
     e = instruments.BY_KEYWORD[keyword]
     try:
         return getattr(e.module, e.params)(**{name: getattr(args, flag) for name, flag in e.flags})
@@ -496,7 +500,7 @@ def load_targets(filename, error, flag="--match_to"):
 def add_symmetry_search_arguments(ap):
     """The tolerance flag of the symmetry search, the cell reduction and the symmetrization, shared with `python -m arreau_amd.screen`."""
     ap.add_argument("--symprec", type=float, default=0.1,
-                    help="find_symmetry / reduce_cell / symmetrize: tolerance in A on cell lengths and atom distances (0.1: a starting value, not a claim)")
+                    help="find_symmetry / reduce_cell / symmetrize / conventional_cell: tolerance in A on cell lengths and atom distances (0.1: a starting value, not a claim)")
 
 
 def symmetry_lines(res, parts=None, spec=None):

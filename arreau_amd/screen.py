@@ -4,6 +4,7 @@
     python -m arreau_amd.screen out/crystals.npz --find_symmetry [--symprec 0.1]
     python -m arreau_amd.screen out/crystals.npz --reduce_cell [--symprec 0.1] [--out reduced.npz]
     python -m arreau_amd.screen out/crystals.npz --symmetrize [--symprec 0.1] [--out symmetrized.npz]
+    python -m arreau_amd.screen out/crystals.npz --conventional_cell [--symprec 0.1] [--out conventional.npz]
     python -m arreau_amd.screen out/crystals.npz --match_to targets.npz [--match_mode paired|any] [--ltol 0.2] [--angle_tol 5] [--stol 0.3]
     python -m arreau_amd.screen out/crystals.npz --unique [--against train.npz] [--fp_r_max 6] [--fp_sigma 0.1] [--fp_tolerance 0.01]
 
@@ -20,6 +21,10 @@ this run describe the cells as given and are not written to it), on which the ot
 `--symmetrize [--symprec 0.1]` adds the symmetrization (diffusion/symmetrize.py): the count per number of orbits and flag and the
 largest displacement; `--out` then writes a crystals file of the SYMMETRIZED crystals (averaged positions, rebuilt cells, and the
 symmetrized_* arrays) in the same way.  With `--reduce_cell` too the reduction runs first and its crystals are symmetrized.
+`--conventional_cell [--symprec 0.1]` adds the conventional cells (diffusion/conventional_cell.py: the reduction, the symmetry search
+on the reduced cells, the conventional basis): the count per Bravais lattice and flag; `--out` then writes a crystals file of the
+CONVENTIONAL crystals (with the conventional_* arrays alone: the other arrays of this run describe the crystals as given).  It reads the crystals as given; `--out` together with `--reduce_cell` or
+`--symmetrize` is rejected: run them in turn, each on the file the one before wrote.  No space-group number, no idealised metric.
 `--match_to TARGETS` adds the structure match (diffusion/structure_match.py) against the crystals of a second file: match rate, mean
 rms_norm and rms over the matched, and the count per flag; `--match_mode paired` matches crystal b against target b, `any` against
 every target of its composition (the best one counts); without the flag the match is paired when the two files hold equally many
@@ -48,6 +53,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--symmetrize", action="store_true",
                     help="also symmetrize every crystal with the operations found within --symprec; --out then writes the "
                          "symmetrized crystals (after --reduce_cell: of the reduced crystals)")
+    ap.add_argument("--conventional_cell", action="store_true",
+                    help="also give every crystal its conventional cell, centring and Bravais lattice; --out then writes the "
+                         "conventional crystals (not together with --reduce_cell or --symmetrize: run them in turn)")
     ap.add_argument("--match_to", type=str, default=None, metavar="TARGETS",
                     help="also match every crystal against the crystals of this file (after --reduce_cell / --symmetrize, which the "
                          "targets then go through too): match rate and mean RMSD")
@@ -62,7 +70,7 @@ def main(argv=None):
     from .diffusion import cell_reduction, screening, structure_match, symmetry_search
     from .diffusion.inference.process_generated_crystals import load_sample_results_from_hdf5, save_sample_results_to_hdf5
     from .diffusion.diffusion_loss import SampleResult
-    from .diffusion.instruments import INSTRUMENTS
+    from .diffusion.instruments import ALL as INSTRUMENTS
     from .generate import instrument_lines, instrument_params, unique_lines
     ap = build_parser()
     args = ap.parse_args(argv)
@@ -70,6 +78,9 @@ def main(argv=None):
         ap.error("--against needs --unique")
     if args.match_mode is not None and args.match_to is None:
         ap.error("--match_mode needs --match_to")
+    if args.conventional_cell and args.out and (args.reduce_cell or args.symmetrize):
+        ap.error("--conventional_cell with --out writes the conventional crystals and --reduce_cell / --symmetrize theirs: run them in "
+                 "turn, each on the file the one before wrote")
     asked = {e.keyword: instrument_params(e.keyword, args, ap.error) if getattr(args, e.keyword, True) else None
              for e in INSTRUMENTS}  # (by sample() keyword; None: not asked for.  The screen has no flag here: it always runs)
 
@@ -115,6 +126,12 @@ def main(argv=None):
             ap.error(f"--match_to: {e}")
         current.match = res.match = structure_match.sample_arrays(matched)
         report("match_to", current)
+    if asked["conventional_cell"] is not None:  # (of the crystals as given: the chain reduces them itself)
+        from .diffusion import conventional_cell
+        res.conventional = conventional_cell.sample_arrays(conventional_cell.conventional_sample_result(res, asked["conventional_cell"], args.device))
+        report("conventional_cell", res)
+        if args.out:
+            current = SampleResult(**conventional_cell.conventional_crystals(res.conventional), conventional=res.conventional)
     if args.out:
         print("wrote", save_sample_results_to_hdf5(current, args.out))
     return res

@@ -365,7 +365,8 @@ int arreau_fingerprint_match(const arreau_fingerprint_result* x, int32_t Bx, con
  * The third instrument beside the screen and the fingerprint: which operations x' = W x + t (on fractional columns, modulo
  * lattice translations) map the crystal onto itself within a tolerance symprec (A), and which of the 32 point groups their
  * rotations form.  One launch, one workgroup of four waves per crystal, no atomics, no second stream, no arreau_model;
- * deterministic.  NOT computed: a space-group number, a standardised or primitive cell.
+ * deterministic.  NOT computed: a space-group number, a primitive cell (arreau_crystal_reduce) or a conventional one
+ * (arreau_crystal_conventional, which reads this search run on the reduced cell).
  * Conventions: the cell rows are a_0, a_1, a_2 (d_lattice); the Cartesian position of x is r_d = sum_k x_k L_kd.  Column j of W
  * holds the image of basis vector j, a'_j = sum_k W_kj a_k; with G_ij = a_i . a_j the image basis has the metric G' = W^T G W.
  * The rotation code of W is sum_{r,c} (W_rc + 1) 3^(3r + c) (W_00 the least significant base-3 digit; identity: 16484).
@@ -435,7 +436,8 @@ int arreau_crystal_symmetry(const float* d_frac, const int32_t* d_types, const f
  * The fourth instrument beside the screen, the fingerprint and the symmetry search: the pure translations a crystal has in the
  * cell it is given, the primitive cell they imply, a Delaunay-reduced (Selling) basis of that cell made of its shortest vectors,
  * and one atom per translation class expressed in it.  One launch, one workgroup of four waves per crystal, no atomics, no
- * arreau_model; deterministic.  NOT computed: a Niggli form, a conventional or standardised setting, a space-group number.
+ * arreau_model; deterministic.  NOT computed: a Niggli form, a space-group number; the conventional setting is a launch of its
+ * own on this one's output (arreau_crystal_conventional).
  * Conventions as in the symmetry search: cell rows a_0, a_1, a_2, r_d = sum_k x_k L_kd, positions wrapped w = f - floor(f) (a
  * result >= 1 becomes 0).  dist(delta) of a fractional difference: each component minus its nearest integer (rintf) gives e; the
  * minimum over the 27 images s in {-1, 0, 1}^3, s_0 slowest, of |c|, c_d = ((e_0 + s_0) L_0d + (e_1 + s_1) L_1d) + (e_2 + s_2) L_2d.
@@ -572,6 +574,94 @@ typedef struct arreau_symmetrize_result { /* DEVICE arrays */
 int arreau_crystal_symmetrize(const float* d_frac, const int32_t* d_types, const float* d_lattice, const int32_t* d_crystal_offsets,
                               int32_t B, int32_t N, const arreau_symmetry_result* found, int32_t max_ops,
                               arreau_symmetrize_result* out, void* stream);
+
+/* ---- conventional cell: the conventional basis, centring, Bravais lattice and atoms of a reduced crystal ----------------------
+ * The seventh per-crystal instrument: arreau_crystal_reduce gives a crystal's primitive, Delaunay-reduced cell and
+ * arreau_crystal_symmetry, run on THAT cell, its rotations; this entry point turns them into the cell a crystallographer reads:
+ * the conventional basis of the crystal family, the centring (P, A, B, C, I, F, R), the Bravais lattice (aP, mP, mS, oP, oS, oI,
+ * oF, tP, tI, hR, hP, cP, cI, cF) and the atoms of the conventional cell.  It neither reduces nor searches: the caller runs the
+ * three launches in order (reduce, search on the reduced batch, this one).  One launch, one workgroup of four waves per crystal,
+ * no atomics, no second stream, no arreau_model; deterministic.  NOT computed: a space-group number, an origin shift, the ITA
+ * standard choice among the monoclinic centrings (A, C and I all count as mS), an idealised metric (the cell keeps its noise; to
+ * idealise, symmetrize the conventional crystal afterwards).
+ * The batch (d_frac, d_types, d_lattice, d_crystal_offsets) is primitive and Delaunay-reduced; `found` is the result of
+ * arreau_crystal_symmetry on the same arrays (a HOST struct of device pointers; n_ops, ops_rotation, point_group and flags are
+ * read), max_ops its row width.  Conventions as in the symmetry search: a lattice vector is an integer row v (v L in space), a
+ * rotation W acts on columns, v' = W v; the rotations of a Delaunay-reduced cell have entries in {-1, 0, 1}, so every step below
+ * but the comparison of lengths is exact integer arithmetic.  |v|^2 of an integer row: c_d = (v_0 L_0d + v_1 L_1d) + v_2 L_2d,
+ * (c_x c_x + c_y c_y) + c_z c_z, as the cell reduction forms it.  Per crystal, with the distinct stored rotations in code order:
+ *   1. flags.  NONFINITE, CELL and EMPTY as in arreau_crystal_symmetry's rule 1.  NO_GROUP: the search flagged the crystal
+ *      AMBIGUOUS, OVERFLOW or NOT_A_GROUP, or n_ops lies outside 1..max_ops, or point_group outside 0..31, or a stored code is no
+ *      matrix of determinant +-1, or there are more than 48 distinct rotations.  NO_BASIS: rules 2-5 give no basis or a check of
+ *      rule 5 fails.  A crystal with any flag is copied through unchanged, bit for bit (positions not wrapped): lattice = the
+ *      input's, transform = identity, centring 0, bravais = -1, n_points = 1, num_atoms = n, source = 0..n-1.
+ *   2. proper parts and axes.  W' = det(W) W; its order from its trace: 3 -> 1, -1 -> 2, 0 -> 3, 1 -> 4, 2 -> 6 (anything else:
+ *      NO_BASIS).  S = sum_{j < order} W'^j has rank 1: the axis is its first non-zero column and the normal of the perpendicular
+ *      lattice plane {v : S v = 0} its first non-zero row, each divided by the gcd of its entries and given a positive first
+ *      non-zero entry.  "The first part of order k" is the first in code order.
+ *   3. shortest plane vectors.  The integer rows v != 0 with entries in -3..3 and normal . v = 0, enumerated in lexicographic
+ *      order from (-3, -3, -3), v_0 slowest; the shortest is the first of the smallest |v|^2 (a strict float32 comparison).
+ *   4. basis by family (point_group 0-1 triclinic, 2-4 monoclinic, 5-7 orthorhombic, 8-14 tetragonal, 15-26 trigonal and
+ *      hexagonal, 27-31 cubic).  Every rule yields a set of integer candidates P (rows a, b, c); the right-handed ones (det P >
+ *      0) are kept and the lexicographically smallest P, read row by row, wins: vectors the group maps onto each other are
+ *      equally long, and integers, not floats, choose among them.
+ *        triclinic     the cell as given, P = identity.
+ *        monoclinic    b = +- the axis of the first part of order 2; a the shortest vector of its plane, c the shortest not
+ *                      parallel to a, negated when a . c > 0 (float32, (x x' + y y') + z z'); candidates (s a, t b, s c), s, t = +-1.
+ *        orthorhombic  the three distinct axes of the parts of order 2, sorted by |v|^2 (ties to the first found); when that
+ *                      order makes the lattice A-centred the axes are taken as (second, third, first), when B-centred as (first,
+ *                      third, second): the centred face becomes C with |a| <= |b|; candidates: every sign of the three.
+ *        tetragonal    c = the axis of the first part R of order 4; a0 the shortest vector of its plane; candidates (a, R a, c) and
+ *                      (a, R^-1 a, c) for a = +- R^j a0.
+ *        trig., hex.   c = the axis of the first part of order 6, of order 3 when there is none; R the first part of order 3;
+ *                      candidates as for tetragonal; with det P = 3 only those in the obverse setting (rule 5's R set) are kept.
+ *        cubic         the three distinct axes of the parts of order 4, of order 2 when there is none; candidates: every order
+ *                      and every sign of the three.
+ *   5. transform, centring and checks, all exact.  n_points = det P must lie in 1..4.  The centring translations are the integer
+ *      combinations of the rows of adj(P) modulo n_points (numerators over n_points), sorted lexicographically: exactly
+ *      n_points of them, and one of the sets P {0}; A {0, (0,1,1)/2}; B {0, (1,0,1)/2}; C {0, (1,1,0)/2}; I {0, (1,1,1)/2}; F {0,
+ *      (0,1,1)/2, (1,0,1)/2, (1,1,0)/2}; R {0, (1,2,2)/3, (2,1,1)/3} (obverse).  The family admits: triclinic P; monoclinic P, A,
+ *      C, I; orthorhombic P, C, I, F; tetragonal P, I; trigonal and hexagonal P, R; cubic P, I, F.  Every distinct rotation in
+ *      the conventional basis, adj(P)^T W P^T / n_points, must be an integer matrix.  Any failure: NO_BASIS.
+ *   6. cell.  lattice row r = (P_r0 L_0d + P_r1 L_1d) + P_r2 L_2d; lengths_r = sqrt of its squared length; angles_i = acos of
+ *      (row_j . row_k) / (lengths_j lengths_k), j, k the other two, clamped to [-1, 1], in radians: the sampler's representation,
+ *      as the symmetrization reports it.  bravais = 0..13 in the order above; centring = 0..6 for P, A, B, C, I, F, R.
+ *   7. atoms.  num_atoms = n x n_points.  Output atom k n + i is atom i under the k-th centring translation, in their sorted
+ *      order: frac_out_c = wrap((((w_0 A_0c + w_1 A_1c) + w_2 A_2c) + num_kc) / n_points), A = adj(P), w the wrapped input
+ *      position; types_out its species and source = i.  Crystal b's atoms start at 4 x offsets[b] (the per-atom arrays hold 4 N
+ *      rows); the slots beyond num_atoms hold zeros, species -1 and source -1.
+ *   8. arithmetic: one float32 operation per step, rounded to nearest, in the order written, never contracted; the division and
+ *      the square roots correctly rounded; only acos is the device's.  The float64 restatement
+ *      (arreau_amd/diffusion/conventional_cell.py) reports the relative gap of every float comparison that decided; on guarded
+ *      inputs (every gap at least 1e-3) the integer outputs agree and the reals are held to the bounds derived there.
+ * Cost: the basis is found by one thread per crystal (a few thousand integer operations and at most 2 x 342 squared lengths);
+ * the atoms are written by the workgroup.  Offsets outside [0, N] or descending are clamped as in the screen.  Does not
+ * synchronise.
+ * Argument errors (ARREAU_EINVAL, nothing launched): NULL found / result / arrays, negative sizes, max_ops outside
+ * 1..ARREAU_SYM_MAX_OPS_CAP. */
+#define ARREAU_CONV_NONFINITE 1
+#define ARREAU_CONV_CELL 2
+#define ARREAU_CONV_EMPTY 4
+#define ARREAU_CONV_NO_GROUP 8
+#define ARREAU_CONV_NO_BASIS 16
+typedef struct arreau_conventional_result { /* DEVICE arrays: one row per crystal, then 4 N rows of atoms */
+    float* lattice;      /* [B,3,3] rows a, b, c of the conventional cell, P L */
+    float* lengths;      /* [B,3] A */
+    float* angles;       /* [B,3] radians */
+    int32_t* transform;  /* [B,3,3] P: rows, the conventional vectors in the reduced basis */
+    int32_t* centring;   /* [B] 0..6: P, A, B, C, I, F, R */
+    int32_t* bravais;    /* [B] 0..13: aP, mP, mS, oP, oS, oI, oF, tP, tI, hR, hP, cP, cI, cF; -1: none */
+    int32_t* n_points;   /* [B] det P: lattice points per conventional cell */
+    int32_t* num_atoms;  /* [B] n x n_points */
+    int32_t* flags;      /* [B] ARREAU_CONV_* */
+    float* frac_out;     /* [4N,3] crystal b's atoms at 4 offsets[b] .. 4 offsets[b] + num_atoms[b] */
+    int32_t* types_out;  /* [4N] */
+    int32_t* source;     /* [4N] the reduced-cell atom (local to the crystal) of every output atom, -1 beyond num_atoms */
+} arreau_conventional_result;
+/* d_frac[N,3], d_types[N] species ids (required), d_lattice[B,3,3] rows a, b, c.  `found` and `out` are HOST pointers. */
+int arreau_crystal_conventional(const float* d_frac, const int32_t* d_types, const float* d_lattice, const int32_t* d_crystal_offsets,
+                                int32_t B, int32_t N, const arreau_symmetry_result* found, int32_t max_ops,
+                                arreau_conventional_result* out, void* stream);
 
 /* ---- structure match: is crystal x that crystal y, under which map, and how far off in A ------------------------------------
  * The sixth instrument: for every pair (x, y) of a pair list, x a crystal of batch X and y one of batch Y (Y may be X), the
