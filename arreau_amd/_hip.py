@@ -33,7 +33,7 @@ EXPORTS = [
     "arreau_sample_loop_eta", "arreau_reverse_step_eta",
     "arreau_crystal_fingerprint", "arreau_fingerprint_match", "arreau_crystal_symmetry", "arreau_crystal_reduce",
     "arreau_crystal_symmetrize", "arreau_structure_match", "arreau_structure_match_assigned",
-    "arreau_crystal_conventional",
+    "arreau_crystal_conventional", "arreau_crystal_coordination",
     "arreau_noise_state", "arreau_invert_step", "arreau_invert_loop",
     "arreau_sample_loop_multistep", "arreau_reverse_step_multistep",
     "arreau_sample_loop_species", "arreau_reverse_step_species",
@@ -109,6 +109,17 @@ class ScreenCriteriaC(Structure):
 class ScreenResultC(Structure):
     """arreau_screen_result: the six device arrays the screen writes, one entry per crystal."""
     _fields_ = [(name, c_void_p) for name in ("min_distance", "pair", "n_close", "volume", "number_density", "flags")]
+
+
+class CoordinationParamsC(Structure):
+    """arreau_coordination_params: the tolerance, cutoff and list width of the coordination search."""
+    _fields_ = [("tol", c_float), ("cutoff", c_float), ("max_neighbors", c_int32), ("max_shells", c_int32)]
+
+
+class CoordinationResultC(Structure):
+    """arreau_coordination_result: the six per-crystal and six per-atom device arrays the coordination search writes."""
+    _fields_ = [(name, c_void_p) for name in ("n_bonds", "n_mutual", "min_cn", "max_cn", "mean_cn", "flags",
+                                                "cn", "neighbors", "nearest", "farthest", "mutual", "nearest_d2")]
 
 
 class FingerprintParamsC(Structure):
@@ -262,6 +273,7 @@ def _prototypes():
         "arreau_philox_fill": [u64, i32, i32, i64, vp, vp, vp],
         "arreau_philox_fill_word": [u64, i32, i32, u32, i64, vp, vp, vp],
         "arreau_crystal_screen": [vp] * 4 + [i32, i32, POINTER(ScreenCriteriaC), POINTER(ScreenResultC), vp],
+        "arreau_crystal_coordination": [vp] * 3 + [i32, i32, POINTER(CoordinationParamsC), POINTER(CoordinationResultC), vp],
         "arreau_crystal_fingerprint": [vp] * 4 + [i32, i32, POINTER(FingerprintParamsC), POINTER(FingerprintResultC), vp],
         "arreau_fingerprint_match": [POINTER(FingerprintResultC), i32, POINTER(FingerprintResultC), i32, f32, POINTER(MatchResultC), vp],
         "arreau_crystal_symmetry": [vp] * 4 + [i32, i32, POINTER(SymmetryParamsC), POINTER(SymmetryResultC), vp],

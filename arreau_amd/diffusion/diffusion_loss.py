@@ -25,6 +25,7 @@ from . import cell_reduction
 from . import symmetry_search
 from . import symmetrize as symmetrize_mod
 from . import conventional_cell as conventional_mod
+from . import coordination as coordination_mod
 from . import structure_match
 from .d3pm import D3PM
 from . import lattice_systems
@@ -81,6 +82,10 @@ class SampleResult:
     # arrays lattice, lengths, angles, transform, centring, bravais, n_points, num_atoms and flags, one row per crystal, and the
     # conventional crystals' frac_x, atomic_numbers and source as a dense ragged batch; None when it was not asked for
     conventional: Optional[dict] = None
+    # extension: the coordination environments of the final state (sample(coordination=...); diffusion/coordination.py) -- numpy
+    # arrays n_bonds, n_mutual, min_cn, max_cn, mean_cn and flags, one row per crystal, and cn, neighbors [.., max_neighbors, 4],
+    # nearest, farthest, mutual and species, one row per atom; None when it was not asked for
+    coordination: Optional[dict] = None
 
 
 class _PinnedRing:
@@ -424,7 +429,7 @@ class DiffusionLoss(nn.Module):
                lattice_system=None, symmetry=None, screen=None, unique=None, find_symmetry=None, reduce_cell=None,
                symmetrize=None, match_to=None, eta: Optional[float] = None, initial_state=None,
                multistep: bool = False, elements=None, species_temperature: float = 1.0, crystal_keys=None,
-               conventional_cell=None) -> SampleResult:
+               conventional_cell=None, coordination=None) -> SampleResult:
         """diffusion_loss.py:276-377.  The initial state is drawn on the host exactly like the reference (numpy
         uniforms for the angles, then randn lengths, randn fractional coordinates from torch's global CPU generator):
         draw_initial_state, which a caller may also use on its own.
@@ -586,7 +591,15 @@ class DiffusionLoss(nn.Module):
         only to the bound of the network's batch-independence test; the re-run after an fp16x3 overflow is decided per batch.  The
         host's global generators are neither read nor advanced.  With every option above.  Rejected before any work: keys without
         a seed, with a host-noise mode, out of range, of the wrong count, a key twice.  SampleResult.crystal_keys carries the keys.
-        None is the sampler as it was, bit for bit, through the exports it used."""
+        None is the sampler as it was, bit for bit, through the exports it used.
+        `coordination` (extension, every noise mode and option): a coordination.CoordinationParams (tol, cutoff, max_neighbors,
+        max_shells), or True for its defaults -- one more launch on the final device state (arreau_crystal_coordination; rules in
+        include/arreau_hip.h) gives every atom its neighbours -- all atoms and images within (1 + tol) times its nearest distance
+        and within the cutoff --, its coordination number and nearest distance, and every crystal their sums and extremes.
+        SampleResult.coordination then holds the arrays (coordination.STORED_KEYS).  It reads the state as sampled.  No Voronoi
+        weighting (not the reference's CrystalNN), no radii, no chemistry.  A bad value is rejected before any work.  None: no
+        launch is added, coordination is None and the results are what they were, bit for bit."""
+        coordination = coordination_mod.resolve(coordination)
         if crystal_keys is not None:  # validated before any work and before any generator is touched (the count: below)
             crystal_keys = keyed_mod.validate_keys(crystal_keys, None, seed, noise if noise in ("philox", "device", "reference") else "philox")
         match_to = structure_match.resolve(match_to)
@@ -885,8 +898,12 @@ class DiffusionLoss(nn.Module):
             species = np.rint(np.asarray(atomic_numbers).reshape(-1)).astype(np.int32)
             match = structure_match.sample_arrays(structure_match.match_batches(
                 (frac_d, lattice_d, off_d, torch.as_tensor(species, device=frac_d.device)), num_atoms.numpy(), species, *match_to))
+        coordinated = None
+        if coordination is not None:
+            coordinated = coordination_mod.sample_arrays(coordination_mod.result_to_numpy(
+                eng.coordination(frac_d, lattice_d, off_d, coordination)), atomic_numbers)
         return SampleResult(num_atoms=num_atoms.numpy(), frac_x=frac_d.cpu().numpy().astype(np.float64),
                             atomic_numbers=atomic_numbers, lattice=lattice_d.cpu().numpy().astype(np.float64), info=info,
                             metrics=metrics, uniqueness=uniqueness, symmetry=found, reduced=reduced,
-                            symmetrized=symmetrized, match=match, conventional=conventional,
+                            symmetrized=symmetrized, match=match, conventional=conventional, coordination=coordinated,
                             crystal_keys=np.array(crystal_keys, dtype=np.int64) if crystal_keys is not None else None)

@@ -1,6 +1,7 @@
 """The per-crystal instruments that run on the final sampled state -- screen, duplicate detection, symmetry search, cell reduction,
-symmetrization, structure match -- as one table, in the order their arrays appear in a crystals file, and after them the DERIVED
-ones, which chain those launches (the conventional cell: reduction, search on the reduced cell, conventional basis).  An entry holds what the
+symmetrization, structure match -- as one table, in the order their arrays appear in a crystals file, after them the DERIVED
+ones, which chain those launches (the conventional cell: reduction, search on the reduced cell, conventional basis), and last the
+LOCAL ones, which describe each atom's surroundings (the coordination environments); EVERY is all of them.  An entry holds what the
 instruments differ in for the host-side plumbing: the file layer (inference/process_generated_crystals.py), the batch driver
 (generate.py) and `python -m arreau_amd.screen` loop over it.  The stored keys are the owning modules' own tuples.  Needs numpy
 alone at import, as the modules do."""
@@ -10,7 +11,7 @@ from typing import Optional
 
 import numpy as np
 
-from . import cell_reduction, conventional_cell, screening, structure_match, symmetrize, symmetry_search, uniqueness
+from . import cell_reduction, conventional_cell, coordination, screening, structure_match, symmetrize, symmetry_search, uniqueness
 
 
 @dataclass(frozen=True)
@@ -59,7 +60,14 @@ DERIVED = (
                atom_keys=conventional_cell.ATOM_KEYS, atoms_from="num_atoms"),
 )
 ALL = INSTRUMENTS + DERIVED
-BY_KEYWORD = {e.keyword: e for e in ALL}
+# what looks at each atom's surroundings, not at the crystal as a whole: after every other instrument's arrays
+LOCAL = (
+    Instrument("coordination", "coordination", "coord_", "coordination_stats", coordination, coordination.STORED_KEYS,
+               "CoordinationParams", (("tol", "cn_tol"), ("cutoff", "cn_cutoff")), "coordination", atom_keys=coordination.ATOM_KEYS,
+               shape=(), shapes=(("neighbors", 3),)),
+)
+EVERY = ALL + LOCAL
+BY_KEYWORD = {e.keyword: e for e in EVERY}
 
 
 def concat(entry, parts):

@@ -39,6 +39,12 @@ def conventional_cell(frac, lattice, offsets, types, params=None, reduced=None):
     return conventional_mod.conventional_cell(frac, lattice, offsets, types, params, reduced)
 
 
+def coordination(frac, lattice, offsets, params=None):
+    """The coordination environments without an engine (arreau_crystal_coordination needs no model): diffusion.coordination.coordination."""
+    from .diffusion import coordination as coordination_mod
+    return coordination_mod.coordination(frac, lattice, offsets, params)
+
+
 def symmetrize(frac, lattice, offsets, types, params=None, found=None):
     """The symmetrization without an engine (arreau_crystal_symmetrize needs no model): diffusion.symmetrize.symmetrize."""
     from .diffusion import symmetrize as symmetrize_mod
@@ -997,6 +1003,15 @@ class HipEngine:
         if frac.device != self.device:
             raise ValueError(f"conventional_cell: the state must be on {self.device}")
         return conventional_mod.conventional_cell(frac, lattice, offsets, types, params, reduced)
+
+    def coordination(self, frac, lattice, offsets, params=None):
+        """The coordination environments of a batch on this engine's device (arreau_crystal_coordination;
+        diffusion/coordination.py: `coordination`, which needs no engine): frac [N,3] f32, lattice [B,3,3] f32, offsets [B+1] i32,
+        params a CoordinationParams or None (the defaults).  Returns its dict of device tensors."""
+        from .diffusion import coordination as coordination_mod
+        if frac.device != self.device:
+            raise ValueError(f"coordination: the state must be on {self.device}")
+        return coordination_mod.coordination(frac, lattice, offsets, params)
 
     def find_symmetry(self, frac, lattice, offsets, types, params=None):
         """The symmetry search of a batch on this engine's device (arreau_crystal_symmetry; diffusion/symmetry_search.py:

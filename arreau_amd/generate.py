@@ -81,7 +81,7 @@ import numpy as np
 
 from .diffusion import instruments
 from .diffusion.diffusion_loss import SampleResult
-from .diffusion.instruments import ALL as INSTRUMENTS
+from .diffusion.instruments import EVERY as INSTRUMENTS
 
 
 def shard_range(num_items: int, world_size: int, rank: int):
@@ -457,7 +457,19 @@ def build_parser() -> argparse.ArgumentParser:
                     help="match every generated crystal against the targets of a crystals file on the device (the best target of its "
                          "composition): match rate and mean RMSD per rank and in total + match_* arrays in the output file")
     add_structure_match_arguments(ap)
+    ap.add_argument("--coordination", action="store_true",
+                    help="find every atom's neighbours on the device (all atoms and images within (1 + cn_tol) times its nearest "
+                         "distance and within cn_cutoff): histogram of coordination numbers, mean per element, share of mutual bonds "
+                         "and flags per rank and in total + coord_* arrays in the output file")
+    add_coordination_arguments(ap)
     return ap
+
+
+def add_coordination_arguments(ap):
+    """The flags of the coordination search, shared with `python -m arreau_amd.screen`."""
+    ap.add_argument("--cn_tol", type=float, default=0.1,
+                    help="coordination: a neighbour lies within (1 + cn_tol) times the atom's nearest distance (0.1: a starting value, not a claim)")
+    ap.add_argument("--cn_cutoff", type=float, default=6.0, help="coordination: nothing beyond this distance in A is a neighbour")
 
 
 def add_structure_match_arguments(ap):
@@ -473,7 +485,7 @@ def add_structure_match_arguments(ap):
 def instrument_params(keyword, args, error):
     """The parameters of one instrument (its sample() keyword: instruments.BY_KEYWORD) from its flags -- screen: a ScreenCriteria,
     unique: a FingerprintParams, find_symmetry: a SymmetrySearchParams, reduce_cell: a CellReductionParams, symmetrize: a
-    SymmetrizeParams, match_to: a StructureMatchParams, conventional_cell: a ConventionalCellParams; what has no flag keeps its default.  `error(message)` reports a bad value."""
+    SymmetrizeParams, match_to: a StructureMatchParams, conventional_cell: a ConventionalCellParams, coordination: a CoordinationParams; what has no flag keeps its default.  `error(message)` reports a bad value."""
     e = instruments.BY_KEYWORD[keyword]
     try:
         return getattr(e.module, e.params)(**{name: getattr(args, flag) for name, flag in e.flags})

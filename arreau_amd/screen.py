@@ -6,6 +6,7 @@
     python -m arreau_amd.screen out/crystals.npz --symmetrize [--symprec 0.1] [--out symmetrized.npz]
     python -m arreau_amd.screen out/crystals.npz --conventional_cell [--symprec 0.1] [--out conventional.npz]
     python -m arreau_amd.screen out/crystals.npz --match_to targets.npz [--match_mode paired|any] [--ltol 0.2] [--angle_tol 5] [--stol 0.3]
+    python -m arreau_amd.screen out/crystals.npz --coordination [--cn_tol 0.1] [--cn_cutoff 6.0]
     python -m arreau_amd.screen out/crystals.npz --unique [--against train.npz] [--fp_r_max 6] [--fp_sigma 0.1] [--fp_tolerance 0.01]
 
 Prints the summary `python -m arreau_amd.generate --screen` prints (accepted / attempted and the count per flag) and, with
@@ -31,12 +32,17 @@ every target of its composition (the best one counts); without the flag the matc
 crystals.  It runs after `--reduce_cell` and `--symmetrize` when those are given, on their crystals, and the targets are then put
 through the same reduction and symmetrization; `--out` gets the match_* arrays.  The optimal assignment only with `--assignment optimal`, no supercells, no
 volume scaling.
+`--coordination [--cn_tol 0.1] [--cn_cutoff 6.0]` adds the coordination environments (diffusion/coordination.py: every atom's
+neighbours within (1 + cn_tol) times its nearest distance and within cn_cutoff): the histogram of coordination numbers, the mean per
+element, the share of bonds both ends agree on and the count per flag, and the coord_* arrays with `--out`.  It runs last, on the
+crystals `--out` writes: the file's, or those of `--reduce_cell` / `--symmetrize` / `--conventional_cell --out`.  No Voronoi
+weighting (not CrystalNN), no radii, no chemistry.
 """
 import argparse
 
 
 def build_parser() -> argparse.ArgumentParser:
-    from .generate import (add_fingerprint_arguments, add_screen_arguments, add_structure_match_arguments,
+    from .generate import (add_coordination_arguments, add_fingerprint_arguments, add_screen_arguments, add_structure_match_arguments,
                            add_symmetry_search_arguments)
     ap = argparse.ArgumentParser(prog="python -m arreau_amd.screen", description="structural screen of a crystals file")
     ap.add_argument("file", type=str, help="crystals.npz / .h5")
@@ -63,6 +69,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="--match_to: crystal b against target b, or against every target of its composition (default: paired when "
                          "the files hold equally many crystals)")
     add_structure_match_arguments(ap)
+    ap.add_argument("--coordination", action="store_true",
+                    help="also find every atom's neighbours and coordination number (last: on the crystals --out writes)")
+    add_coordination_arguments(ap)
     return ap
 
 
@@ -70,7 +79,7 @@ def main(argv=None):
     from .diffusion import cell_reduction, screening, structure_match, symmetry_search
     from .diffusion.inference.process_generated_crystals import load_sample_results_from_hdf5, save_sample_results_to_hdf5
     from .diffusion.diffusion_loss import SampleResult
-    from .diffusion.instruments import ALL as INSTRUMENTS
+    from .diffusion.instruments import EVERY as INSTRUMENTS
     from .generate import instrument_lines, instrument_params, unique_lines
     ap = build_parser()
     args = ap.parse_args(argv)
@@ -132,6 +141,10 @@ def main(argv=None):
         report("conventional_cell", res)
         if args.out:
             current = SampleResult(**conventional_cell.conventional_crystals(res.conventional), conventional=res.conventional)
+    if asked["coordination"] is not None:  # (of the crystals --out writes)
+        from .diffusion import coordination
+        current.coordination = coordination.coordination_sample_result(current, asked["coordination"], args.device)
+        report("coordination", current)
     if args.out:
         print("wrote", save_sample_results_to_hdf5(current, args.out))
     return res

@@ -291,6 +291,69 @@ int arreau_crystal_screen(const float* d_frac, const int32_t* d_types /* may be 
                           const int32_t* d_crystal_offsets, int32_t B, int32_t N, const arreau_screen_criteria* crit,
                           arreau_screen_result* out /* device arrays, each [B] (pair: [B,5]) */, void* stream);
 
+/* ---- coordination environments of generated crystals -----------------------------------------------------------------
+ * Per atom: its nearest distance over every periodic image, its neighbours -- every atom and image within (1 + tol) times that
+ * distance and within a cutoff (the table-free rule pymatgen ships as MinimumDistanceNN; the reference's predict_bonds uses
+ * CrystalNN, which weights Voronoi faces and needs radii: not this) --, their number, the first max_neighbors of them and how
+ * many of them the other end agrees on; per crystal the sums and extremes.  The screen's exact image search, run per atom over
+ * all j.  One launch, one workgroup of four waves per crystal, one wave per atom, no atomics (every reduction is an integer
+ * sum or a minimum / maximum of the bits of a non-negative float: no order matters), no arreau_model.  Every arithmetic step is
+ * ONE float32 operation rounded to nearest, in the order written, never contracted to a fused multiply-add, so a float32 host
+ * restatement (arreau_amd/diffusion/coordination.py) matches bit for bit.
+ *   1. cell, NONFINITE, images and positions: the screen's rules 1, 2, 4 and 5 with search_radius = cutoff.  CELL: volume not
+ *      finite or not (q_k <= max_shells) for an axis (no volume threshold here).  For NONFINITE and CELL nothing else is
+ *      computed: the reals are NaN, neighbors -1, the counts 0, min_cn and max_cn -1, no other flag.
+ *   2. distance of receiver i, atom j, image m = (n_1, n_2, n_3): s_d = (n_1 L_0d + n_2 L_1d) + n_3 L_2d, disp = (p_j + s) - p_i,
+ *      d2 = (dx dx + dy dy) + dz dz -- the screen's rule 6, for EVERY j (not j >= i) and every m; the pair (j = i, m = (0, 0, 0)) is
+ *      the atom itself and is skipped, every other image of i counts.  The search range is e = j M + m, 0 <= e < n M.
+ *   3. phase A: d2min(i) = the minimum of the bits of d2 over the range (+inf where it holds no finite d2); written to
+ *      nearest_d2; a workgroup barrier follows.
+ *   4. phase B: thr2(i) = f2 * d2min(i), f2 = (float)((1 + (double)tol)^2); r2 = (float)((double)cutoff * cutoff).  (j, m) is a
+ *      NEIGHBOUR of i iff d2 <= thr2(i) and d2 <= r2.  cn(i) is their exact number.  One wave owns an atom and walks e in
+ *      ascending chunks of 64; a ballot and a prefix population count give each hit its slot, so neighbors holds the first
+ *      max_neighbors neighbours in ascending (j, m), (j, n_1, n_2, n_3) each with j local to the crystal, the rest -1.
+ *   5. nearest = sqrt(d2min) (correctly rounded); farthest = sqrt of the largest neighbour d2, 0 at cn = 0; mutual(i) = the
+ *      neighbours (j, m) of i with d2 <= thr2(j), d2 the one computed from i's side: the bonds both ends agree on.
+ *   6. per crystal: n_bonds = sum cn, n_mutual = sum mutual, min_cn, max_cn (-1 without atoms), mean_cn = (float)n_bonds /
+ *      (float)n (NaN without atoms).  flags: EMPTY n = 0; OVERLAP some d2min == 0; ISOLATED some cn = 0 (nothing within the
+ *      cutoff; nearest is still the minimum over the range); OVERFLOW some cn > max_neighbors (the list is cut, cn is exact).
+ * Limits: counts are int32 (a neighbour lies within the cutoff, so they stay far below 2^31 for any physical density); 32-bit
+ * index arithmetic where n M fits, a 64-bit loop otherwise.  Offsets are clamped as in the screen.
+ * Argument errors (ARREAU_EINVAL, nothing launched): NULL params / result / arrays, negative sizes, tol not finite or < 0, cutoff
+ * not finite or <= 0, max_neighbors outside 1..ARREAU_COORD_MAX_NEIGHBORS, max_shells outside 1..ARREAU_SCREEN_MAX_SHELLS,
+ * neighbors not 16-byte aligned.  B == 0 returns ARREAU_OK. */
+#define ARREAU_COORD_NONFINITE 1
+#define ARREAU_COORD_CELL 2
+#define ARREAU_COORD_EMPTY 4
+#define ARREAU_COORD_OVERLAP 8
+#define ARREAU_COORD_ISOLATED 16
+#define ARREAU_COORD_OVERFLOW 32
+#define ARREAU_COORD_MAX_NEIGHBORS 64
+typedef struct arreau_coordination_params {
+    float tol;              /* a neighbour lies within (1 + tol) nearest; default 0.1 (a starting value, not a claim) */
+    float cutoff;           /* A; default 6.0 */
+    int32_t max_neighbors;  /* stored per atom, 1..ARREAU_COORD_MAX_NEIGHBORS; default 24 */
+    int32_t max_shells;     /* cap on the images per axis, 1..ARREAU_SCREEN_MAX_SHELLS; default 8 */
+} arreau_coordination_params;
+typedef struct arreau_coordination_result { /* DEVICE arrays */
+    int32_t* n_bonds;    /* [B] */
+    int32_t* n_mutual;   /* [B] */
+    int32_t* min_cn;     /* [B] */
+    int32_t* max_cn;     /* [B] */
+    float* mean_cn;      /* [B] */
+    int32_t* flags;      /* [B] ARREAU_COORD_* */
+    int32_t* cn;         /* [N] */
+    int32_t* neighbors;  /* [N, max_neighbors, 4] j, n_1, n_2, n_3; 16-byte aligned */
+    float* nearest;      /* [N] */
+    float* farthest;     /* [N] */
+    int32_t* mutual;     /* [N] */
+    float* nearest_d2;   /* [N] d2min */
+} arreau_coordination_result;
+/* d_frac[N,3], d_lattice[B,3,3] rows a, b, c as for the screen (no species: the rule is table-free).  `params` and `out` are HOST
+ * pointers to the structs; the arrays `out` names are device arrays. */
+int arreau_crystal_coordination(const float* d_frac, const float* d_lattice, const int32_t* d_crystal_offsets, int32_t B, int32_t N,
+                                const arreau_coordination_params* params, arreau_coordination_result* out, void* stream);
+
 /* ---- duplicate detection: structure fingerprints and their all-pairs match ------------------------------------------
  * The screen's sibling: per crystal a reduced formula and a fingerprint of its pair distribution (Oganov & Valle, J. Chem.
  * Phys. 130, 104504 (2009), with the normalisation taken at the bin centre so that it is finite for every input), and for
