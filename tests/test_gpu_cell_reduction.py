@@ -1,7 +1,12 @@
 """Cell reduction on the device (arreau_crystal_reduce, csrc/reduce.hip) against the float64 restatement on every guarded case of
 tests/cell_reduction_cases.py in one ragged batch: flags, multiplicity, n_out, keep and selling_steps equal, lattice and positions
-within twice the bounds derived in diffusion/cell_reduction.py (never from the kernel's output).  Then the other instruments,
-unchanged, on its results: the fingerprint of a crystal and of its reduced form, the symmetry search on a skewed rock salt and on
+within twice the bounds derived in diffusion/cell_reduction.py (never from the kernel's output).  The same assertions on
+`size_cases()` and `size_flag_cases()` in a second ragged launch of 18 crystals and 2,264 atoms: 63 / 64 / 65 atoms (a second
+block of 64 lanes in the candidate loop), 80 atoms of which only the first 64, or only the last 16, reject a candidate, 257 to
+264 atoms (the unstaged path, two rounds of 256, counters carried between them, a class representative at 256, copy_through past
+256), 27 and 64 translations (the closure and triple loops past 256 threads, K = 66), 65 translations, face and rhombohedral
+centring, an open closure; their bits alone in a launch and in a repeated launch; the fingerprint of each against its reduced
+form.  Then the other instruments, unchanged, on its results: the fingerprint of a crystal and of its reduced form, the symmetry search on a skewed rock salt and on
 its reduced cell; the flags; sample(reduce_cell=...); the export.  Needs an MI355X: `-m gpu`."""
 import ctypes
 import os
@@ -159,6 +164,110 @@ def test_flags(dev):
             assert np.array_equal(got["transform"][b], np.eye(3, dtype=np.float32)) and int(got["n_out"][b]) == len(f), name
         else:
             assert int(got["n_out"][b]) == len(f) and int(got["flags"][b]) == 0, name
+
+
+# ------------------------------------------------------------- past 16 atoms: rounds, 64 translations, closure (size_cases)
+# the 257-, 260-, 261- and 264-atom crystals between small ones, the flagged crystals among the reduced ones
+SIZE_ORDER = ("face-centred", "rounds 260 permuted", "P1 n63", "261 atoms", "R-centred", "P1 n257", "open closure", "2-atom 4x4x4",
+              "rounds 264 permuted", "P1 n64", "first block decides", "65 translations", "last block decides", "2-atom 3x2x1", "nan in atom 258", "P1 n65", "rounds 260", "2-atom 3x3x3")
+
+
+def size_group():
+    """[(Case, FlagCase or None)] in SIZE_ORDER: every size case and every flagged one."""
+    assert sorted(SIZE_ORDER) == sorted(cases.SIZE_NAMES + cases.SIZE_FLAG_NAMES)
+    flagged = cases.size_flag_cases()
+    return [(flagged[k].case, flagged[k]) if k in flagged else (cases.size_cases()[k], None) for k in SIZE_ORDER]
+
+
+def size_run(dev):
+    """Every size case and flagged size case in ONE ragged launch (cached): (group, batch, first atom of each crystal, result)."""
+    if "size" not in _RUN:
+        group = size_group()
+        batch = cases.batch_of([c for c, _ in group])
+        _RUN["size"] = (group, batch, np.concatenate([[0], np.cumsum(batch[2])]), launch(dev, batch))
+    return _RUN["size"]
+
+
+def test_size_cases_match_the_f64_restatement(dev):
+    """test_kernel_matches_the_f64_restatement's assertions on the cases whose loops make a second trip."""
+    group, batch, first, got = size_run(dev)
+    worst = {"lattice": 0.0, "position": 0.0}
+    for b, (case, flagged) in enumerate(group):
+        if flagged is not None:
+            continue
+        ref = cases.reference(case)
+        for k in INT_KEYS:
+            assert int(got[k][b]) == int(getattr(ref, k)[0]), (case.name, k)
+        assert int(got["multiplicity"][b]) == case.multiplicity and int(got["flags"][b]) == 0, case.name
+        sl = slice(first[b], first[b + 1])
+        assert np.array_equal(got["keep"][sl], ref.keep), case.name
+        assert np.array_equal(got["types_out"][sl], ref.types_out), case.name
+        L = case.lattice.astype(np.float64)
+        lat_bound, pos_bound = 2.0 * cr.lattice_bound(ref.transform[0], L), 2.0 * cr.position_bound(ref.inverse[0])
+        assert np.array_equal(got["transform"][b].astype(np.float64), (ref.transform[0]).astype(np.float32).astype(np.float64)), case.name
+        d_lat = float(np.abs(got["lattice_out"][b].astype(np.float64) - ref.lattice_out[0]).max())
+        n_out = int(ref.n_out[0])
+        d = got["frac_out"][sl][:n_out].astype(np.float64) - ref.frac_out[:n_out]
+        d_pos = float(np.abs(d - np.rint(d)).max())
+        print(f"{case.name}: n {case.n} m {case.multiplicity} steps {int(got['selling_steps'][b])} |lattice - f64| {d_lat:.3e} "
+              f"(bound {lat_bound:.3e}, {d_lat / lat_bound:.3f} of it) |x - f64| {d_pos:.3e} (bound {pos_bound:.3e}, {d_pos / pos_bound:.3f} of it)")
+        worst["lattice"], worst["position"] = max(worst["lattice"], d_lat / lat_bound), max(worst["position"], d_pos / pos_bound)
+        assert d_lat <= lat_bound and d_pos <= pos_bound, case.name
+        assert (got["frac_out"][sl][n_out:] == 0).all() and (got["keep"][sl][n_out:] == -1).all() and (got["types_out"][sl][n_out:] == -1).all()
+    print("largest deviation / tolerance:", worst)
+
+
+def test_size_flag_cases_are_copied_through(dev):
+    """65 translations, the open closure, 261 atoms (copy_through strides twice) and the NaN in the second round of 256."""
+    group, batch, first, got = size_run(dev)
+    seen = 0
+    for b, (case, flagged) in enumerate(group):
+        if flagged is None:
+            continue
+        seen += 1
+        ref, name = cases.reference(case), case.name
+        assert int(got["flags"][b]) == flagged.flags == int(ref.flags[0]), (name, cr.describe(got["flags"][b]))
+        assert int(got["n_translations"][b]) == flagged.n_translations == int(ref.n_translations[0]), name
+        assert int(got["multiplicity"][b]) == 1 and int(got["n_out"][b]) == case.n and int(got["selling_steps"][b]) == 0, name
+        sl = slice(first[b], first[b + 1])
+        assert np.array_equal(got["frac_out"][sl].view(np.int32), case.frac.view(np.int32)), name
+        assert np.array_equal(got["lattice_out"][b].view(np.int32), case.lattice.view(np.int32)), name
+        assert np.array_equal(got["types_out"][sl], case.types) and np.array_equal(got["keep"][sl], np.arange(case.n)), name
+        assert np.array_equal(got["transform"][b], np.eye(3, dtype=np.float32)), name
+    assert seen == len(cases.SIZE_FLAG_NAMES) == 4
+
+
+def test_size_cases_do_not_depend_on_their_place_or_the_launch(dev):
+    group, batch, first, got = size_run(dev)
+    bits = lambda a: a.view(np.int32) if a.dtype == np.float32 else a  # (a NaN that was copied through equals itself)
+    again = launch(dev, batch)
+    for k in cr.RED_KEYS:
+        assert np.array_equal(bits(got[k]), bits(again[k])), k
+    for name in ("2-atom 4x4x4", "rounds 260 permuted"):
+        b = SIZE_ORDER.index(name)
+        alone = launch(dev, cases.batch_of([group[b][0]]))
+        for k in cr.CRYSTAL_KEYS:
+            assert np.array_equal(bits(alone[k][0]), bits(got[k][b])), (name, k)
+        for k in cr.ATOM_KEYS:
+            assert np.array_equal(bits(alone[k]), bits(got[k][first[b]:first[b + 1]])), (name, k)
+
+
+def test_fingerprint_of_the_reduced_size_cases_matches_the_input(dev):
+    """test_fingerprint_of_the_reduced_form_matches_the_input on every unflagged size case, none left out."""
+    group, batch, first, got = size_run(dev)
+    rows = [b for b, (_, flagged) in enumerate(group) if flagged is None]
+    assert len(rows) == len(cases.SIZE_NAMES)
+    fx = uq.fingerprint(*device_batch(dev, cases.batch_of([group[b][0] for b in rows])), FP_PARAMS)
+    red = (np.concatenate([got["frac_out"][first[b]:first[b] + int(got["n_out"][b])] for b in rows]), got["lattice_out"][rows],
+           [int(got["n_out"][b]) for b in rows], np.concatenate([got["types_out"][first[b]:first[b] + int(got["n_out"][b])] for b in rows]))
+    fy = uq.fingerprint(*device_batch(dev, red), FP_PARAMS)
+    assert not fx["flags"].any().item() and not fy["flags"].any().item(), (fx["flags"], fy["flags"])
+    row = lambda f, r: {k: v[r:r + 1].contiguous() for k, v in f.items()}
+    for r, b in enumerate(rows):
+        m = uq.match(row(fx, r), row(fy, r), 0.01)
+        d = float(m["nearest_distance"].cpu()[0])
+        print(f"{group[b][0].name}: fingerprint distance input / reduced {d:.3e} (bound {uq.D_BOUND:.3e})")
+        assert int(m["nearest"].cpu()[0]) == 0 and abs(d) <= uq.D_BOUND, group[b][0].name
 
 
 def test_argument_errors_touch_nothing(dev):
