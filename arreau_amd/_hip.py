@@ -33,7 +33,7 @@ EXPORTS = [
     "arreau_sample_loop_eta", "arreau_reverse_step_eta",
     "arreau_crystal_fingerprint", "arreau_fingerprint_match", "arreau_crystal_symmetry", "arreau_crystal_reduce",
     "arreau_crystal_symmetrize", "arreau_structure_match", "arreau_structure_match_assigned",
-    "arreau_crystal_conventional", "arreau_crystal_coordination",
+    "arreau_crystal_conventional", "arreau_crystal_coordination", "arreau_crystal_bond_order",
     "arreau_noise_state", "arreau_invert_step", "arreau_invert_loop",
     "arreau_sample_loop_multistep", "arreau_reverse_step_multistep",
     "arreau_sample_loop_species", "arreau_reverse_step_species",
@@ -120,6 +120,17 @@ class CoordinationResultC(Structure):
     """arreau_coordination_result: the six per-crystal and six per-atom device arrays the coordination search writes."""
     _fields_ = [(name, c_void_p) for name in ("n_bonds", "n_mutual", "min_cn", "max_cn", "mean_cn", "flags",
                                                 "cn", "neighbors", "nearest", "farthest", "mutual", "nearest_d2")]
+
+
+class BondOrderParamsC(Structure):
+    """arreau_bond_order_params: the row width of the neighbour list and the 36 cosine edges of the angle histogram."""
+    _fields_ = [("max_neighbors", c_int32), ("cos_edges", c_float * 36)]
+
+
+class BondOrderResultC(Structure):
+    """arreau_bond_order_result: the four per-crystal and six per-atom device arrays the bond-order launch writes."""
+    _fields_ = [(name, c_void_p) for name in ("mean_q", "n_angles", "angle_hist", "flags",
+                                                "n_used", "q", "q2", "cos_min", "cos_max", "angles")]
 
 
 class FingerprintParamsC(Structure):
@@ -274,6 +285,7 @@ def _prototypes():
         "arreau_philox_fill_word": [u64, i32, i32, u32, i64, vp, vp, vp],
         "arreau_crystal_screen": [vp] * 4 + [i32, i32, POINTER(ScreenCriteriaC), POINTER(ScreenResultC), vp],
         "arreau_crystal_coordination": [vp] * 3 + [i32, i32, POINTER(CoordinationParamsC), POINTER(CoordinationResultC), vp],
+        "arreau_crystal_bond_order": [vp] * 3 + [i32, i32, vp, vp, POINTER(BondOrderParamsC), POINTER(BondOrderResultC), vp],
         "arreau_crystal_fingerprint": [vp] * 4 + [i32, i32, POINTER(FingerprintParamsC), POINTER(FingerprintResultC), vp],
         "arreau_fingerprint_match": [POINTER(FingerprintResultC), i32, POINTER(FingerprintResultC), i32, f32, POINTER(MatchResultC), vp],
         "arreau_crystal_symmetry": [vp] * 4 + [i32, i32, POINTER(SymmetryParamsC), POINTER(SymmetryResultC), vp],

@@ -25,6 +25,7 @@ from . import cell_reduction
 from . import symmetry_search
 from . import symmetrize as symmetrize_mod
 from . import conventional_cell as conventional_mod
+from . import bond_order as bond_order_mod
 from . import coordination as coordination_mod
 from . import structure_match
 from .d3pm import D3PM
@@ -86,6 +87,11 @@ class SampleResult:
     # arrays n_bonds, n_mutual, min_cn, max_cn, mean_cn and flags, one row per crystal, and cn, neighbors [.., max_neighbors, 4],
     # nearest, farthest, mutual and species, one row per atom; None when it was not asked for
     coordination: Optional[dict] = None
+    # extension: the bond angles and Steinhardt order parameters of the final state (sample(bond_order=...);
+    # diffusion/bond_order.py) -- numpy arrays mean_q [.., 4], n_angles, angle_hist [.., 37], flags and coord_flags, one row per
+    # crystal, and n_used, q and q2 [.., 4], cos_min, cos_max, angles [.., 37] and species, one row per atom; None when it was not
+    # asked for
+    bond_order: Optional[dict] = None
 
 
 class _PinnedRing:
@@ -429,7 +435,7 @@ class DiffusionLoss(nn.Module):
                lattice_system=None, symmetry=None, screen=None, unique=None, find_symmetry=None, reduce_cell=None,
                symmetrize=None, match_to=None, eta: Optional[float] = None, initial_state=None,
                multistep: bool = False, elements=None, species_temperature: float = 1.0, crystal_keys=None,
-               conventional_cell=None, coordination=None) -> SampleResult:
+               conventional_cell=None, coordination=None, bond_order=None) -> SampleResult:
         """diffusion_loss.py:276-377.  The initial state is drawn on the host exactly like the reference (numpy
         uniforms for the angles, then randn lengths, randn fractional coordinates from torch's global CPU generator):
         draw_initial_state, which a caller may also use on its own.
@@ -598,8 +604,18 @@ class DiffusionLoss(nn.Module):
         and within the cutoff --, its coordination number and nearest distance, and every crystal their sums and extremes.
         SampleResult.coordination then holds the arrays (coordination.STORED_KEYS).  It reads the state as sampled.  No Voronoi
         weighting (not the reference's CrystalNN), no radii, no chemistry.  A bad value is rejected before any work.  None: no
-        launch is added, coordination is None and the results are what they were, bit for bit."""
+        launch is added, coordination is None and the results are what they were, bit for bit.
+        `bond_order` (extension, every noise mode and option): a bond_order.BondOrderParams (the coordination search's tol, cutoff,
+        max_neighbors, max_shells), or True for its defaults -- the coordination launch and one more on its neighbour lists
+        (arreau_crystal_bond_order; rules in include/arreau_hip.h) give every atom the histogram of the angles between its bonds
+        (37 bins centred on 0, 5, ..., 180 degrees) and the Steinhardt order parameters q_2, q_4, q_6, q_8 of its shell, and every
+        crystal the summed histogram and the mean q_l.  SampleResult.bond_order then holds the arrays (bond_order.STORED_KEYS).
+        With `coordination` too the coordination launch is shared: their parameters must then agree (ValueError before any work).
+        It reads the state as sampled.  No w_l, no neighbour-averaged parameters, no classification of environments, no Voronoi
+        weights.  None: no launch is added, bond_order is None and the results are what they were, bit for bit."""
         coordination = coordination_mod.resolve(coordination)
+        bond_order = bond_order_mod.resolve(bond_order)
+        bond_order_mod.check_shared(bond_order, coordination)
         if crystal_keys is not None:  # validated before any work and before any generator is touched (the count: below)
             crystal_keys = keyed_mod.validate_keys(crystal_keys, None, seed, noise if noise in ("philox", "device", "reference") else "philox")
         match_to = structure_match.resolve(match_to)
@@ -898,12 +914,16 @@ class DiffusionLoss(nn.Module):
             species = np.rint(np.asarray(atomic_numbers).reshape(-1)).astype(np.int32)
             match = structure_match.sample_arrays(structure_match.match_batches(
                 (frac_d, lattice_d, off_d, torch.as_tensor(species, device=frac_d.device)), num_atoms.numpy(), species, *match_to))
-        coordinated = None
+        coordinated = coordinated_d = None
         if coordination is not None:
-            coordinated = coordination_mod.sample_arrays(coordination_mod.result_to_numpy(
-                eng.coordination(frac_d, lattice_d, off_d, coordination)), atomic_numbers)
+            coordinated_d = eng.coordination(frac_d, lattice_d, off_d, coordination)
+            coordinated = coordination_mod.sample_arrays(coordination_mod.result_to_numpy(coordinated_d), atomic_numbers)
+        ordered = None
+        if bond_order is not None:  # (coordinated_d: the search's launch is shared)
+            ordered = bond_order_mod.sample_arrays(bond_order_mod.result_to_numpy(
+                eng.bond_order(frac_d, lattice_d, off_d, bond_order, coordinated_d)), atomic_numbers)
         return SampleResult(num_atoms=num_atoms.numpy(), frac_x=frac_d.cpu().numpy().astype(np.float64),
                             atomic_numbers=atomic_numbers, lattice=lattice_d.cpu().numpy().astype(np.float64), info=info,
                             metrics=metrics, uniqueness=uniqueness, symmetry=found, reduced=reduced,
-                            symmetrized=symmetrized, match=match, conventional=conventional, coordination=coordinated,
+                            symmetrized=symmetrized, match=match, conventional=conventional, coordination=coordinated, bond_order=ordered,
                             crystal_keys=np.array(crystal_keys, dtype=np.int64) if crystal_keys is not None else None)

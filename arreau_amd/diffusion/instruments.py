@@ -1,7 +1,9 @@
 """The per-crystal instruments that run on the final sampled state -- screen, duplicate detection, symmetry search, cell reduction,
 symmetrization, structure match -- as one table, in the order their arrays appear in a crystals file, after them the DERIVED
 ones, which chain those launches (the conventional cell: reduction, search on the reduced cell, conventional basis), and last the
-LOCAL ones, which describe each atom's surroundings (the coordination environments); EVERY is all of them.  An entry holds what the
+LOCAL ones, which describe each atom's surroundings (the coordination environments); EVERY is all of them.  SHELL holds what
+is built on a LOCAL one's neighbour lists (the bond angles and order parameters); TABLE is EVERY and SHELL, the whole table, and
+KEYWORDS maps a sample() keyword to its entry.  An entry holds what the
 instruments differ in for the host-side plumbing: the file layer (inference/process_generated_crystals.py), the batch driver
 (generate.py) and `python -m arreau_amd.screen` loop over it.  The stored keys are the owning modules' own tuples.  Needs numpy
 alone at import, as the modules do."""
@@ -11,7 +13,8 @@ from typing import Optional
 
 import numpy as np
 
-from . import cell_reduction, conventional_cell, coordination, screening, structure_match, symmetrize, symmetry_search, uniqueness
+from . import (bond_order, cell_reduction, conventional_cell, coordination, screening, structure_match, symmetrize, symmetry_search,
+               uniqueness)
 
 
 @dataclass(frozen=True)
@@ -68,6 +71,15 @@ LOCAL = (
 )
 EVERY = ALL + LOCAL
 BY_KEYWORD = {e.keyword: e for e in EVERY}
+# what chains on the coordination launch and reads its neighbour lists: after the coordination arrays
+SHELL = (
+    Instrument("bond_order", "bond_order", "order_", "bond_order_stats", bond_order, bond_order.STORED_KEYS, "BondOrderParams",
+               (("tol", "cn_tol"), ("cutoff", "cn_cutoff")), "bond order", atom_keys=bond_order.ATOM_KEYS, shape=(),
+               shapes=(("q", (len(bond_order.L_VALUES),)), ("q2", (len(bond_order.L_VALUES),)), ("mean_q", (len(bond_order.L_VALUES),)),
+                       ("angles", (bond_order.ANGLE_BINS,)), ("angle_hist", (bond_order.ANGLE_BINS,)))),
+)
+TABLE = EVERY + SHELL  # the whole table: what the file layer, the batch driver and the screen loop over
+KEYWORDS = {e.keyword: e for e in TABLE}
 
 
 def concat(entry, parts):

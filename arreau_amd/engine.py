@@ -45,6 +45,12 @@ def coordination(frac, lattice, offsets, params=None):
     return coordination_mod.coordination(frac, lattice, offsets, params)
 
 
+def bond_order(frac, lattice, offsets, params=None):
+    """The bond angles and Steinhardt order parameters without an engine (arreau_crystal_bond_order needs no model): diffusion.bond_order.bond_order."""
+    from .diffusion import bond_order as bond_order_mod
+    return bond_order_mod.bond_order(frac, lattice, offsets, params)
+
+
 def symmetrize(frac, lattice, offsets, types, params=None, found=None):
     """The symmetrization without an engine (arreau_crystal_symmetrize needs no model): diffusion.symmetrize.symmetrize."""
     from .diffusion import symmetrize as symmetrize_mod
@@ -1012,6 +1018,19 @@ class HipEngine:
         if frac.device != self.device:
             raise ValueError(f"coordination: the state must be on {self.device}")
         return coordination_mod.coordination(frac, lattice, offsets, params)
+
+    def bond_order(self, frac, lattice, offsets, params=None, coordination_result=None):
+        """The bond angles and Steinhardt order parameters of a batch on this engine's device (arreau_crystal_bond_order;
+        diffusion/bond_order.py: `bond_order`, which needs no engine): the coordination launch with `params`, or the given device
+        `coordination_result` of a search with those parameters, then the new launch.  Returns the dict of device tensors
+        `bond_order` returns.  Does not synchronise."""
+        from .diffusion import bond_order as bond_order_mod
+        if frac.device != self.device:
+            raise ValueError(f"bond_order: the state must be on {self.device}")
+        p = params if params is not None else bond_order_mod.BondOrderParams()
+        if coordination_result is None:
+            coordination_result = self.coordination(frac, lattice, offsets, p.coordination())
+        return bond_order_mod.from_coordination(frac, lattice, offsets, coordination_result, p.max_neighbors)
 
     def find_symmetry(self, frac, lattice, offsets, types, params=None):
         """The symmetry search of a batch on this engine's device (arreau_crystal_symmetry; diffusion/symmetry_search.py:

@@ -64,6 +64,11 @@ its sampling call, against every target of its composition in that crystals file
 match rate (matched / attempted) and mean rms_norm and rms over the matched, per rank and in total, and match_* arrays in the
 output file.  The optimal assignment only with `--assignment optimal`, no supercells (combine with a reduced target file), no volume scaling.
 
+Coordination environments: `--coordination` (`--cn_tol`, `--cn_cutoff`) finds every atom's neighbours on the device
+(diffusion/coordination.py) and stores coord_* arrays.  Bond order: `--bond_order` (the same two flags; with `--coordination` the
+search is shared) adds the bond-angle histogram and the Steinhardt order parameters q_2 .. q_8 of every atom's shell
+(diffusion/bond_order.py): the summed histogram, mean q4 and q6 overall and per element, the count per flag, and order_* arrays.
+
 Keyed sampling: `--keyed` (needs `--seed`) makes every crystal a function of (seed, key) alone (diffusion/keyed.py).  Every rank
 uses the same seed; output slot k of `--num_crystals` has key k on its first attempt.  With `--require_valid`, attempt a of slot k
 has key a * num_crystals + k and the slot keeps its first valid attempt; every rank retries only the slots of its slice that are
@@ -81,7 +86,7 @@ import numpy as np
 
 from .diffusion import instruments
 from .diffusion.diffusion_loss import SampleResult
-from .diffusion.instruments import EVERY as INSTRUMENTS
+from .diffusion.instruments import TABLE as INSTRUMENTS
 
 
 def shard_range(num_items: int, world_size: int, rank: int):
@@ -461,12 +466,16 @@ def build_parser() -> argparse.ArgumentParser:
                     help="find every atom's neighbours on the device (all atoms and images within (1 + cn_tol) times its nearest "
                          "distance and within cn_cutoff): histogram of coordination numbers, mean per element, share of mutual bonds "
                          "and flags per rank and in total + coord_* arrays in the output file")
+    ap.add_argument("--bond_order", action="store_true",
+                    help="bond angles and Steinhardt order parameters on the device, of every atom's coordination shell (--cn_tol, "
+                         "--cn_cutoff): summed angle histogram, mean q4 and q6 overall and per element and flags per rank and in "
+                         "total + order_* arrays in the output file")
     add_coordination_arguments(ap)
     return ap
 
 
 def add_coordination_arguments(ap):
-    """The flags of the coordination search, shared with `python -m arreau_amd.screen`."""
+    """The flags of the coordination search, shared with `python -m arreau_amd.screen`; --bond_order reads them too."""
     ap.add_argument("--cn_tol", type=float, default=0.1,
                     help="coordination: a neighbour lies within (1 + cn_tol) times the atom's nearest distance (0.1: a starting value, not a claim)")
     ap.add_argument("--cn_cutoff", type=float, default=6.0, help="coordination: nothing beyond this distance in A is a neighbour")
@@ -483,10 +492,10 @@ def add_structure_match_arguments(ap):
 
 
 def instrument_params(keyword, args, error):
-    """The parameters of one instrument (its sample() keyword: instruments.BY_KEYWORD) from its flags -- screen: a ScreenCriteria,
+    """The parameters of one instrument (its sample() keyword: instruments.KEYWORDS) from its flags -- screen: a ScreenCriteria,
     unique: a FingerprintParams, find_symmetry: a SymmetrySearchParams, reduce_cell: a CellReductionParams, symmetrize: a
-    SymmetrizeParams, match_to: a StructureMatchParams, conventional_cell: a ConventionalCellParams, coordination: a CoordinationParams; what has no flag keeps its default.  `error(message)` reports a bad value."""
-    e = instruments.BY_KEYWORD[keyword]
+    SymmetrizeParams, match_to: a StructureMatchParams, conventional_cell: a ConventionalCellParams, coordination: a CoordinationParams, bond_order: a BondOrderParams; what has no flag keeps its default.  `error(message)` reports a bad value."""
+    e = instruments.KEYWORDS[keyword]
     try:
         return getattr(e.module, e.params)(**{name: getattr(args, flag) for name, flag in e.flags})
     except ValueError as err:
@@ -496,7 +505,7 @@ def instrument_params(keyword, args, error):
 def instrument_lines(keyword, res, parts=None):
     """The lines one instrument's flag prints for a result that holds its arrays: its statistics per rank (`parts`: what the ranks
     carried; None: the result as one set) and in total."""
-    e = instruments.BY_KEYWORD[keyword]
+    e = instruments.KEYWORDS[keyword]
     return instruments.summary_lines(e, getattr(res, e.field), parts)
 
 

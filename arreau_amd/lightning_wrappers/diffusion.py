@@ -401,7 +401,7 @@ class PONITA_DIFFUSION(nn.Module):
                lattice_system=None, symmetry=None, screen=None, unique=None, find_symmetry=None, reduce_cell=None,
                symmetrize=None, match_to=None, eta: Optional[float] = None, initial_state=None,
                multistep: bool = False, elements=None, species_temperature: float = 1.0, crystal_keys=None,
-               conventional_cell=None, coordination=None) -> SampleResult:
+               conventional_cell=None, coordination=None, bond_order=None) -> SampleResult:
         """lightning_wrappers/diffusion.py:220-253.  `num_atoms_per_sample` may also be a sequence with one atom count
         per crystal of the batch (extension; the reference supports a single int).  Frames of a visualization_setting
         other than NONE go to `<DIFFUSION_DIR>/step_<timestep>.cif` like the reference's PNGs (`vis_name` overrides the
@@ -442,7 +442,9 @@ class PONITA_DIFFUSION(nn.Module):
         diffusion.conventional_cell.ConventionalCellParams or True -- the conventional cell, centring and Bravais lattice of every
         final crystal; SampleResult.conventional holds the arrays (DiffusionLoss.sample).  `coordination` (extension): a
         diffusion.coordination.CoordinationParams or True -- every atom's neighbours, coordination number and nearest distance
-        in the final crystals; SampleResult.coordination holds the arrays (DiffusionLoss.sample)."""
+        in the final crystals; SampleResult.coordination holds the arrays (DiffusionLoss.sample).  `bond_order` (extension): a
+        diffusion.bond_order.BondOrderParams or True -- every atom's bond-angle histogram and Steinhardt order parameters
+        q_2 .. q_8 in the final crystals; SampleResult.bond_order holds the arrays (DiffusionLoss.sample)."""
         from ..diffusion import keyed as keyed_mod, multistep as multistep_mod, resampling, species as species_mod
         if crystal_keys is not None:  # (raises before any work)
             crystal_keys = keyed_mod.validate_keys(crystal_keys, None, seed, noise if noise in ("philox", "device", "reference") else "philox")
@@ -487,7 +489,7 @@ class PONITA_DIFFUSION(nn.Module):
             screen=screen, unique=unique, find_symmetry=find_symmetry, reduce_cell=reduce_cell, symmetrize=symmetrize,
             match_to=match_to, eta=eta, initial_state=initial_state, multistep=multistep, elements=elements,
             species_temperature=species_temperature, crystal_keys=crystal_keys, conventional_cell=conventional_cell,
-            coordination=coordination)
+            coordination=coordination, bond_order=bond_order)
 
     # ---- starting the sampler from given crystals (extension; rules in include/arreau_hip.h) -------------------------------------
     def _crystal_state(self, crystals, t, what):

@@ -7,6 +7,7 @@
     python -m arreau_amd.screen out/crystals.npz --conventional_cell [--symprec 0.1] [--out conventional.npz]
     python -m arreau_amd.screen out/crystals.npz --match_to targets.npz [--match_mode paired|any] [--ltol 0.2] [--angle_tol 5] [--stol 0.3]
     python -m arreau_amd.screen out/crystals.npz --coordination [--cn_tol 0.1] [--cn_cutoff 6.0]
+    python -m arreau_amd.screen out/crystals.npz --bond_order [--cn_tol 0.1] [--cn_cutoff 6.0]
     python -m arreau_amd.screen out/crystals.npz --unique [--against train.npz] [--fp_r_max 6] [--fp_sigma 0.1] [--fp_tolerance 0.01]
 
 Prints the summary `python -m arreau_amd.generate --screen` prints (accepted / attempted and the count per flag) and, with
@@ -37,6 +38,10 @@ neighbours within (1 + cn_tol) times its nearest distance and within cn_cutoff):
 element, the share of bonds both ends agree on and the count per flag, and the coord_* arrays with `--out`.  It runs last, on the
 crystals `--out` writes: the file's, or those of `--reduce_cell` / `--symmetrize` / `--conventional_cell --out`.  No Voronoi
 weighting (not CrystalNN), no radii, no chemistry.
+`--bond_order [--cn_tol 0.1] [--cn_cutoff 6.0]` adds the bond angles and Steinhardt order parameters of every atom's coordination
+shell (diffusion/bond_order.py): the summed angle histogram, the mean q4 and q6 overall and per element and the count per flag, and
+the order_* arrays with `--out`.  It runs last too, beside `--coordination`, on the same crystals.  No w_l, no neighbour-averaged
+parameters, no classification of environments.
 """
 import argparse
 
@@ -71,6 +76,8 @@ def build_parser() -> argparse.ArgumentParser:
     add_structure_match_arguments(ap)
     ap.add_argument("--coordination", action="store_true",
                     help="also find every atom's neighbours and coordination number (last: on the crystals --out writes)")
+    ap.add_argument("--bond_order", action="store_true",
+                    help="also find every atom's bond-angle histogram and Steinhardt order parameters (last: on the crystals --out writes)")
     add_coordination_arguments(ap)
     return ap
 
@@ -79,7 +86,7 @@ def main(argv=None):
     from .diffusion import cell_reduction, screening, structure_match, symmetry_search
     from .diffusion.inference.process_generated_crystals import load_sample_results_from_hdf5, save_sample_results_to_hdf5
     from .diffusion.diffusion_loss import SampleResult
-    from .diffusion.instruments import EVERY as INSTRUMENTS
+    from .diffusion.instruments import TABLE as INSTRUMENTS
     from .generate import instrument_lines, instrument_params, unique_lines
     ap = build_parser()
     args = ap.parse_args(argv)
@@ -145,6 +152,10 @@ def main(argv=None):
         from .diffusion import coordination
         current.coordination = coordination.coordination_sample_result(current, asked["coordination"], args.device)
         report("coordination", current)
+    if asked["bond_order"] is not None:  # (of the same crystals)
+        from .diffusion import bond_order
+        current.bond_order = bond_order.bond_order_sample_result(current, asked["bond_order"], args.device)
+        report("bond_order", current)
     if args.out:
         print("wrote", save_sample_results_to_hdf5(current, args.out))
     return res

@@ -354,6 +354,80 @@ typedef struct arreau_coordination_result { /* DEVICE arrays */
 int arreau_crystal_coordination(const float* d_frac, const float* d_lattice, const int32_t* d_crystal_offsets, int32_t B, int32_t N,
                                 const arreau_coordination_params* params, arreau_coordination_result* out, void* stream);
 
+/* ---- bond angles and Steinhardt order parameters of generated crystals -----------------------------------------------
+ * What a coordination number cannot tell: per atom the distribution of the angles between its bonds and the bond-orientational
+ * order parameters q_l, l = 2, 4, 6, 8 (Steinhardt, Nelson & Ronchetti, Phys. Rev. B 28, 784 (1983)) of the neighbour shell a
+ * coordination result stores; per crystal the summed angle histogram and the mean q_l.  By the addition theorem of the
+ * spherical harmonics, for a shell of m unit bond vectors u_e,
+ *     q_l^2 = (4 pi / (2l+1)) sum_mm |mean_e Y_lmm(u_e)|^2 = (1 / m^2) sum_{e,f} P_l(u_e . u_f) = (m + 2 sum_{e<f} P_l(c_ef)) / m^2,
+ * so one loop over the pairs of an atom's neighbours gives the histogram and every q_l from Legendre polynomials alone: no
+ * spherical harmonics, no Wigner symbols, no tables.  No w_l, no neighbour-averaged parameters, no classification.
+ * One launch after arreau_crystal_coordination, whose cn and neighbors arrays it reads: one workgroup of four waves per crystal,
+ * one wave per atom (i = wave, wave + 4, ...), lane f owns bond f; no global atomics, no arreau_model.  Every float step is ONE
+ * float32 operation rounded to nearest, in the order written, never contracted to a fused multiply-add, so a float32 host
+ * restatement (arreau_amd/diffusion/bond_order.py) matches bit for bit.  "x < y ? x : y" below means that comparison: a NaN
+ * never replaces a number, the first of two zeros stays.
+ *   1. cell, positions and NONFINITE: the coordination rule 1 (wrapped positions p, cell rows L).  No image search is made, so
+ *      there is no CELL flag.  For NONFINITE nothing else is computed: the reals are NaN, the counts 0, no other flag.
+ *   2. the list: m(i) = min(cn(i), max_neighbors); entry e < m(i) of atom i is (j, n_1, n_2, n_3).  A crystal with some cn(i) < 0
+ *      or with a j outside 0..n-1 among the first m(i) entries of an atom is BAD_LIST and blanked as for NONFINITE; this is
+ *      decided for the whole crystal before anything is indexed with a j, and nothing is read out of range.
+ *   3. bond e of atom i (lane e < m): s_d = (n_1 L_0d + n_2 L_1d) + n_3 L_2d, disp = (p_j + s) - p_i, d2 = (dx dx + dy dy) + dz dz
+ *      (the coordination rule 2, the same operations); d = sqrt(d2) correctly rounded; u = disp / d componentwise.  An atom
+ *      with a bond of d2 == 0 is DEGENERATE: its reals are NaN, its histogram 0, the crystal gets OVERLAP.
+ *   4. pairs e < f: c_ef = (ux ux' + uy uy') + uz uz' (u of e first), then c = c < -1 ? -1 : c, c = c > 1 ? 1 : c.  Lane f
+ *      (0 <= f < m) walks e = 0 .. f-1 in ascending order.
+ *   5. Legendre polynomials: P_0 = 1, P_1 = c, P_{k+1} = a_k (c P_k) - b_k P_{k-1} for k = 1..7, a_k = (float)((2k+1)/(k+1)),
+ *      b_k = (float)(k/(k+1)) formed in double; in the order t = c P_k; t = a_k t; s = b_k P_{k-1}; P_{k+1} = t - s.
+ *   6. sums: lane f holds s_f = (((+0 + P_l(c_0f)) + P_l(c_1f)) + ...); lanes f >= m and lane 0 hold +0.  The LANE SUM folds the
+ *      64 lane values by the butterfly v <- v + shuffle_xor(v, w), w = 32, 16, 8, 4, 2, 1: S_l(i).  It depends on the list alone.
+ *   7. q2_l(i) = ((float)m + 2 S_l) / ((float)m (float)m), then q2 = q2 < 0 ? 0 : q2; q_l = sqrt(q2_l).  m = 0: NaN for both,
+ *      the crystal gets ISOLATED.  m = 1: q2_l = 1 for every l.
+ *   8. angle histogram, ARREAU_BOND_ANGLE_BINS = 37 bins centred on 0, 5, ..., 180 degrees: bin(c) = #{k in 0..35 : c <= E_k},
+ *      E = cos_edges, which the caller computes as E_k = (float)cos((k + 1/2) 5 degrees) in double (centres on multiples of 5
+ *      degrees keep 60, 90, 120 and 180 off the edges).  angles[i] counts the pairs of atom i per bin.  cos_min(i) and
+ *      cos_max(i) are the extremes of c_ef (the largest and the smallest angle): lane f folds its pairs in walking order from
+ *      +inf / -inf by lo = c < lo ? c : lo, hi = c > hi ? c : hi; the lanes are folded by the butterfly of rule 6 with
+ *      lo = other < lo ? other : lo (hi alike), and lane 0's value is stored.  NaN for m < 2.
+ *   9. per crystal: angle_hist = the sum of its atoms' histograms, n_angles their total; mean_q[l] = the lane sum of rule 6 of
+ *      q_l over the atoms with m >= 1 and all four q finite, lane = i mod 64, ascending i within a lane, divided by (float) of
+ *      their number; NaN without any.  n_used(i) = m(i).  flags: NONFINITE; EMPTY n = 0; BAD_LIST; OVERLAP; ISOLATED;
+ *      TRUNCATED some cn > max_neighbors (the shell is cut, n_used says where).
+ * A crystal alone gives the bits it gives inside any batch.  Offsets are clamped as in the screen.
+ * Argument errors (ARREAU_EINVAL, nothing launched): NULL params / result / arrays, negative sizes, max_neighbors outside
+ * 1..ARREAU_COORD_MAX_NEIGHBORS, d_neighbors not 16-byte aligned, cos_edges not strictly descending inside (-1, 1).  B == 0
+ * returns ARREAU_OK. */
+#define ARREAU_BOND_NONFINITE 1
+#define ARREAU_BOND_EMPTY 2
+#define ARREAU_BOND_BAD_LIST 4
+#define ARREAU_BOND_OVERLAP 8
+#define ARREAU_BOND_ISOLATED 16
+#define ARREAU_BOND_TRUNCATED 32
+#define ARREAU_BOND_ANGLE_BINS 37
+#define ARREAU_BOND_ORDER_L 4 /* l = 2, 4, 6, 8 */
+typedef struct arreau_bond_order_params {
+    int32_t max_neighbors;                        /* the row width of d_neighbors, 1..ARREAU_COORD_MAX_NEIGHBORS */
+    float cos_edges[ARREAU_BOND_ANGLE_BINS - 1];  /* E_k, strictly descending inside (-1, 1) */
+} arreau_bond_order_params;
+typedef struct arreau_bond_order_result { /* DEVICE arrays */
+    float* mean_q;        /* [B, 4] */
+    int32_t* n_angles;    /* [B] */
+    int32_t* angle_hist;  /* [B, 37] */
+    int32_t* flags;       /* [B] ARREAU_BOND_* */
+    int32_t* n_used;      /* [N] m */
+    float* q;             /* [N, 4] q_2, q_4, q_6, q_8 */
+    float* q2;            /* [N, 4] their squares */
+    float* cos_min;       /* [N] */
+    float* cos_max;       /* [N] */
+    int32_t* angles;      /* [N, 37] */
+} arreau_bond_order_result;
+/* d_frac, d_lattice, d_crystal_offsets as for the coordination search; d_cn [N] and d_neighbors [N, max_neighbors, 4] are a
+ * coordination result's cn and neighbors arrays (or a list in their layout).  `params` and `out` are HOST pointers to the structs;
+ * the arrays `out` names are device arrays. */
+int arreau_crystal_bond_order(const float* d_frac, const float* d_lattice, const int32_t* d_crystal_offsets, int32_t B, int32_t N,
+                              const int32_t* d_cn, const int32_t* d_neighbors, const arreau_bond_order_params* params,
+                              arreau_bond_order_result* out, void* stream);
+
 /* ---- duplicate detection: structure fingerprints and their all-pairs match ------------------------------------------
  * The screen's sibling: per crystal a reduced formula and a fingerprint of its pair distribution (Oganov & Valle, J. Chem.
  * Phys. 130, 104504 (2009), with the normalisation taken at the bin centre so that it is finite for every input), and for
