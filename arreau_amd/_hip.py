@@ -40,6 +40,7 @@ EXPORTS = [
     "arreau_diffusion_noise_keyed", "arreau_philox_fill_keyed", "arreau_keyed_timestep", "arreau_diffusion_loss_rows",
     "arreau_loss_rows_reduce",
     "arreau_sample_loop_keyed", "arreau_noise_state_keyed", "arreau_condition_initial_state_keyed", "arreau_philox_fill_crystals",
+    "arreau_sample_loop_guided", "arreau_contact_guidance_step",
 ]
 
 STATUS_NONFINITE, STATUS_BAD_TIMESTEP, STATUS_BAD_TYPE, STATUS_BAD_TIE, STATUS_BAD_SYMMETRY = 1, 2, 4, 8, 16
@@ -98,6 +99,13 @@ class MultistepC(Structure):
 class SpeciesControlC(Structure):
     """arreau_species_control: the admission rows [B,4] uint32 (device pointer; NULL: every class) and the species temperature."""
     _fields_ = [("d_allow", c_void_p), ("temperature", c_float)]
+
+
+class ContactGuidanceC(Structure):
+    """arreau_contact_guidance: min_distance, weight and max_shells of contact guidance and its three device diagnostic arrays (each
+    may be NULL)."""
+    _fields_ = [("min_distance", c_float), ("weight", c_float), ("max_shells", c_int32), ("d_energy", c_void_p),
+                ("d_contacts", c_void_p), ("d_flags", c_void_p)]
 
 
 class ScreenCriteriaC(Structure):
@@ -225,7 +233,7 @@ def _prototypes():
     vp, i32, i64, u32, u64, f32, f64 = c_void_p, c_int32, c_int64, ctypes.c_uint32, ctypes.c_uint64, c_float, c_double
     cond, sched, corr, res, sym = (POINTER(t) for t in (SampleConditionC, SampleScheduleC, CorrectorC, ResamplingC, SymmetryC))
     ms = POINTER(MultistepC)
-    spec, f32p = POINTER(SpeciesControlC), POINTER(c_float)
+    spec, f32p, guide = POINTER(SpeciesControlC), POINTER(c_float), POINTER(ContactGuidanceC)
     loop = [vp] * 6 + [i32] * 4 + [u64] + [vp] * 4 + [c_size_t, i32]
     step_to = [vp] * 8 + [i32, i32] + [vp] * 7 + [f32]
     jump = [vp] * 8 + [i32, i32] + [vp] * 5 + [cond, vp]
@@ -266,6 +274,8 @@ def _prototypes():
         "arreau_reverse_step_multistep": step_to + [vp, ms, vp],
         "arreau_sample_loop_species": loop + [cond, sched, corr, res, vp, sym, f32p, ms, spec, vp],
         "arreau_sample_loop_keyed": loop + [cond, sched, corr, res, vp, sym, f32p, ms, spec, vp, vp],
+        "arreau_sample_loop_guided": loop + [cond, sched, corr, res, vp, sym, f32p, ms, spec, vp, guide, vp],
+        "arreau_contact_guidance_step": [vp] * 5 + [i32, i32, vp, guide, vp],
         "arreau_noise_state_keyed": [vp] * 6 + [i32, i32, i32, u64] + [vp] * 6,
         "arreau_condition_initial_state_keyed": [vp] * 5 + [i32, i32, i32, u64, cond, vp, vp],
         "arreau_philox_fill_crystals": [vp, vp, i32, i32, i32, u32, i32, i32, vp, vp, vp],

@@ -323,6 +323,8 @@ int enqueue_sample_step(const arreau_model* m, const ScorePlan& plan, const Samp
                                   pool_in_update ? nullptr : w.len0, s)))
                 return rc;
         }
+        // contact guidance: the eps of this evaluation, guided in place, is what the corrector and the predictor below read
+        if (opt.guide && (rc = arreau_launch_contact_guide(m, st, w.t_cur, w.lattice, w.eps, *opt.guide, s))) return rc;
         if (j < opt.corr.steps && (rc = arreau_launch_corrector(m, st, w.t_cur, w.eps, nullptr, seed, (uint32_t)j, opt, s))) return rc;
     }
     // without a prep launch per step (fused kernels only) the update also leaves the next step's lattice and embedding behind
@@ -349,7 +351,8 @@ struct ResamplePlan {
 // The key of a captured step: the buffers, sizes and seed, the plan (every kernel choice of the evaluation), and the condition's
 // pointers, the schedule's table and clip, the corrector's step count and snr, the resampling's R and J (a resampled step reads
 // the pass word), the lattice systems' tie array, the symmetry tables, the eta of a DDIM-style step, the history buffers of a
-// multistep step, the admission rows and temperature of species control and the table of stream seeds of a keyed loop, which are kernel arguments
+// multistep step, the admission rows and temperature of species control, the table of stream seeds of a keyed loop and the parameters
+// and diagnostic pointers of contact guidance, which are kernel arguments
 // or launch choices of the capture: a change of any of them must not replay the stale graph.  So is the direction: an inversion
 // loop (arreau_invert_loop) on the same buffers, table pointer included, captures other kernels than a sampling loop.
 SampleGraphKey sample_graph_key(const ScorePlan& score, const SampleState& st, const void* d_workspace, uint64_t seed,
@@ -382,6 +385,13 @@ SampleGraphKey sample_graph_key(const ScorePlan& score, const SampleState& st, c
         k.species_tau_bits = std::bit_cast<uint32_t>(opt.species->temperature);
     }
     k.crystal_seeds = opt.crystal_seeds;
+    if (opt.guide) {
+        k.guide = 1;
+        k.guide_d0_bits = std::bit_cast<uint32_t>(opt.guide->min_distance);
+        k.guide_weight_bits = std::bit_cast<uint32_t>(opt.guide->weight);
+        k.guide_max_shells = opt.guide->max_shells;
+        k.guide_energy = opt.guide->d_energy; k.guide_contacts = opt.guide->d_contacts; k.guide_flags = opt.guide->d_flags;
+    }
     return k;
 }
 
@@ -393,7 +403,9 @@ int sample_loop_impl(arreau_model* m, const SampleState& st, int32_t t_start, in
                      bool invert = false /* DDIM inversion: t_start is the first level, `schedule` the ascending table; no other option */,
                      const arreau_multistep* ms = nullptr /* second-order multistep: the history buffers; eta is then 0 */,
                      const arreau_species_control* species = nullptr /* species control (checked by the export) */,
-                     const uint64_t* crystal_seeds = nullptr /* keyed sampling: the stream seed of every crystal */) {
+                     const uint64_t* crystal_seeds = nullptr /* keyed sampling: the stream seed of every crystal */,
+                     const arreau_contact_guidance* guide = nullptr /* contact guidance (checked by the export); weight 0: none */) {
+    ARREAU_REQUIRE(!invert || !guide, "arreau_invert_loop: an inversion loop takes no contact guidance");
     if (corrector) {
         const int rc = arreau_corrector_check(corrector->steps, corrector->snr, "arreau_sample_loop_corrected");
         if (rc) return rc;
@@ -436,6 +448,7 @@ int sample_loop_impl(arreau_model* m, const SampleState& st, int32_t t_start, in
     opt.ms = ms;
     opt.species = species;
     opt.crystal_seeds = crystal_seeds;
+    opt.guide = guide && guide->weight > 0.0f ? guide : nullptr;  // weight 0: the loop without the option (and its graph key)
     ARREAU_REQUIRE(!ms || (!opt.cond && opt.corr.steps == 0 && !plan && !sym && !invert && eta == 0.0f),
                    "arreau_sample_loop_multistep: a multistep loop takes no condition, corrector steps, resampling or symmetry");
     ARREAU_REQUIRE(!invert || (schedule && !opt.cond && opt.corr.steps == 0 && !plan && !d_length_tie && !sym && eta < 0.0f),
@@ -559,7 +572,7 @@ int sample_loop(const char* who, arreau_model* m, const SampleState& st, int32_t
                 const arreau_corrector* corrector = nullptr, const arreau_resampling* resampling = nullptr,
                 const int32_t* d_length_tie = nullptr, const arreau_symmetry* sym = nullptr, float eta = -1.0f,
                 const arreau_multistep* ms = nullptr, const arreau_species_control* species = nullptr,
-                const uint64_t* crystal_seeds = nullptr) {
+                const uint64_t* crystal_seeds = nullptr, const arreau_contact_guidance* guide = nullptr) {
     ResamplePlan plan{1, 1, {}};
     if (resampling) {
         int rc;
@@ -593,7 +606,8 @@ int sample_loop(const char* who, arreau_model* m, const SampleState& st, int32_t
         }
     }
     return sample_loop_impl(m, st, t_start, n_steps, seed, d_workspace, workspace_bytes, use_graph, condition, schedule, corrector,
-                            plan.passes > 1 ? &plan : nullptr, d_length_tie, sym, eta, stream, /*invert=*/false, ms, species, crystal_seeds);
+                            plan.passes > 1 ? &plan : nullptr, d_length_tie, sym, eta, stream, /*invert=*/false, ms, species, crystal_seeds,
+                            guide);
 }
 }  // namespace
 
@@ -706,8 +720,9 @@ static int sample_loop_species(const char* who, arreau_model* m, float* d_frac, 
                                const arreau_sample_schedule* schedule, const arreau_corrector* corrector,
                                const arreau_resampling* resampling, const int32_t* d_length_tie, const arreau_symmetry* symmetry,
                                const float* eta, const arreau_multistep* multistep, const arreau_species_control* species,
-                               const uint64_t* d_crystal_seeds, void* stream) {
+                               const uint64_t* d_crystal_seeds, void* stream, const arreau_contact_guidance* guide = nullptr) {
     int rc;
+    if (guide && (rc = arreau_contact_guidance_check(guide, who))) return rc;
     arreau_species_control sp;
     if ((rc = arreau_species_check(species, who, &sp))) return rc;
     if (eta && (rc = arreau_eta_check(*eta, who))) return rc;
@@ -730,7 +745,7 @@ static int sample_loop_species(const char* who, arreau_model* m, float* d_frac, 
     const float e = multistep ? 0.0f : (eta ? *eta + 0.0f /* -0 -> +0 */ : -1.0f);
     const SampleState st{d_frac, d_types, d_lengths, d_angles, d_off, B, N, d_const_types, d_fixed_lengths, d_lattice};
     return sample_loop(who, m, st, t_start, n_steps, seed, d_workspace, workspace_bytes, use_graph, stream, condition, schedule, corrector,
-                       resampling, d_length_tie, symmetry, e, multistep, &sp, d_crystal_seeds);
+                       resampling, d_length_tie, symmetry, e, multistep, &sp, d_crystal_seeds, guide);
 }
 
 extern "C" int arreau_sample_loop_species(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
@@ -760,6 +775,21 @@ extern "C" int arreau_sample_loop_keyed(arreau_model* m, float* d_frac, int32_t*
     return sample_loop_species("arreau_sample_loop_keyed", m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, t_start, n_steps, seed,
                                d_const_types, d_fixed_lengths, d_lattice, d_workspace, workspace_bytes, use_graph, condition, schedule,
                                corrector, resampling, d_length_tie, symmetry, eta, multistep, species, d_crystal_seeds, stream);
+}
+
+// Contact guidance (rules in include/arreau_hip.h): arreau_sample_loop_keyed whose every network evaluation is followed by the
+// guidance launch on its eps; a NULL struct or weight == 0 is arreau_sample_loop_keyed bit for bit.  The parameters are checked first.
+extern "C" int arreau_sample_loop_guided(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                                         const int32_t* d_off, int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed,
+                                         const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice, void* d_workspace,
+                                         size_t workspace_bytes, int32_t use_graph, const arreau_sample_condition* condition,
+                                         const arreau_sample_schedule* schedule, const arreau_corrector* corrector,
+                                         const arreau_resampling* resampling, const int32_t* d_length_tie, const arreau_symmetry* symmetry,
+                                         const float* eta, const arreau_multistep* multistep, const arreau_species_control* species,
+                                         const uint64_t* d_crystal_seeds, const arreau_contact_guidance* guidance, void* stream) {
+    return sample_loop_species("arreau_sample_loop_guided", m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, t_start, n_steps, seed,
+                               d_const_types, d_fixed_lengths, d_lattice, d_workspace, workspace_bytes, use_graph, condition, schedule,
+                               corrector, resampling, d_length_tie, symmetry, eta, multistep, species, d_crystal_seeds, stream, guidance);
 }
 
 // DDIM inversion (rules in include/arreau_hip.h): the sampling loop climbing the levels of an ascending table, every step the

@@ -117,6 +117,10 @@ struct SampleGraphKey {
     const uint32_t* species_allow;  // its admission rows (null: every class)
     uint32_t species_tau_bits;      // its temperature
     const uint64_t* crystal_seeds;  // keyed sampling: the table of stream seeds (null: not keyed)
+    int32_t guide;                  // contact guidance: 1 when every evaluation is followed by its launch
+    uint32_t guide_d0_bits, guide_weight_bits;  // its min_distance and weight
+    int32_t guide_max_shells;
+    const void *guide_energy, *guide_contacts, *guide_flags;  // its diagnostic arrays (each may be null)
     bool operator==(const SampleGraphKey&) const = default;
 };
 
@@ -337,6 +341,7 @@ struct StepOptions {
     bool invert = false;                  // DDIM inversion (INVERT): `sched` names the HIGHER level every crystal climbs to; no other option
     const arreau_species_control* species = nullptr;  // species control (SPEC): the admission rows and the temperature; not with invert
     const uint64_t* crystal_seeds = nullptr;  // keyed sampling: the stream seed of every crystal (StepNoiseSrc::seeds of every draw)
+    const arreau_contact_guidance* guide = nullptr;  // contact guidance: one launch on the eps of every evaluation; null (also for weight 0): none; not with invert
 };
 // DDIM-style sampling (arreau_sample_loop_eta, arreau_reverse_step_eta; the rules are stated in include/arreau_hip.h):
 // ARREAU_EINVAL unless eta is finite and lies in [0, 1].
@@ -347,6 +352,14 @@ int arreau_multistep_check(const arreau_multistep* ms, const char* who);  // upd
 // Species control (arreau_sample_loop_species, arreau_reverse_step_species): ARREAU_EINVAL unless the struct is given and its
 // temperature is finite and not negative; *out receives the struct the kernels take.
 int arreau_species_check(const arreau_species_control* species, const char* who, arreau_species_control* out);  // update.hip
+
+// Contact guidance (arreau_sample_loop_guided, arreau_contact_guidance_step; the rules are stated in include/arreau_hip.h).
+// arreau_contact_guidance_check: ARREAU_EINVAL unless the struct is given, min_distance is finite and > 0, weight finite and >= 0 and
+// max_shells in 1..ARREAU_SCREEN_MAX_SHELLS.  The launch reads st.frac / offsets / B / N, the per-crystal timesteps d_t and the cells
+// d_lattice [B,9] the evaluation saw, and rewrites d_eps [N,3] in place (contact_guide.hip).
+int arreau_contact_guidance_check(const arreau_contact_guidance* g, const char* who);
+int arreau_launch_contact_guide(const arreau_model* m, const SampleState& st, const int32_t* d_t, const float* d_lattice, float* d_eps,
+                                const arreau_contact_guidance& opt, hipStream_t s);
 
 // One corrector move per crystal at timestep d_t[b]: z from the caller's d_z_frac [N,3], or (d_z_frac null) the Philox draw
 // (seed, t, ARREAU_DRAW_Z_CORRECTOR, element, iter; 256 pass[0] + iter with opt.pass; keyed by opt.crystal_seeds when given).  Reads

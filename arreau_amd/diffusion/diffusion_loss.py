@@ -27,6 +27,7 @@ from . import symmetrize as symmetrize_mod
 from . import conventional_cell as conventional_mod
 from . import bond_order as bond_order_mod
 from . import coordination as coordination_mod
+from . import contact_guidance as guidance_mod
 from . import structure_match
 from .d3pm import D3PM
 from . import lattice_systems
@@ -435,7 +436,7 @@ class DiffusionLoss(nn.Module):
                lattice_system=None, symmetry=None, screen=None, unique=None, find_symmetry=None, reduce_cell=None,
                symmetrize=None, match_to=None, eta: Optional[float] = None, initial_state=None,
                multistep: bool = False, elements=None, species_temperature: float = 1.0, crystal_keys=None,
-               conventional_cell=None, coordination=None, bond_order=None) -> SampleResult:
+               conventional_cell=None, coordination=None, bond_order=None, contact_guidance=None) -> SampleResult:
         """diffusion_loss.py:276-377.  The initial state is drawn on the host exactly like the reference (numpy
         uniforms for the angles, then randn lengths, randn fractional coordinates from torch's global CPU generator):
         draw_initial_state, which a caller may also use on its own.
@@ -612,7 +613,20 @@ class DiffusionLoss(nn.Module):
         crystal the summed histogram and the mean q_l.  SampleResult.bond_order then holds the arrays (bond_order.STORED_KEYS).
         With `coordination` too the coordination launch is shared: their parameters must then agree (ValueError before any work).
         It reads the state as sampled.  No w_l, no neighbour-averaged parameters, no classification of environments, no Voronoi
-        weights.  None: no launch is added, bond_order is None and the results are what they were, bit for bit."""
+        weights.  None: no launch is added, bond_order is None and the results are what they were, bit for bit.
+        `contact_guidance` (extension, every noise mode and option): a contact_guidance.ContactGuidance (min_distance, weight,
+        max_shells), or True for its defaults -- training-free guidance away from short contacts (rules in include/arreau_hip.h,
+        "contact guidance"; arreau_sample_loop_guided).  Every network evaluation of every step, a corrector's included, is followed
+        by one launch that finds every pair of atoms and periodic image closer than min_distance (the screen's exact search) and
+        adds the gradient of U = 1/2 sum 1/2 (min_distance - d)^2, preconditioned by the cell and scaled by weight / sigma_t^2, to
+        the predicted eps: the step's clean-structure estimate moves `weight` times the overlap apart (0.5 resolves an isolated
+        contact).  noise="philox" runs it inside the loop, graph replay included; noise="device" and "reference" run the same
+        launch between the evaluation and the step (arreau_contact_guidance_step).  SampleResult.info["contact_guidance"] holds
+        the last evaluation's energy, contacts and flags per crystal (contact_guidance.INFO_KEYS).  Positions only: no cell-strain
+        term, no radii or species dependence, no weight schedule other than 1 / sigma_t^2; no claim on sample quality.  A bad
+        value is rejected before any work.  weight = 0 and None: no launch is added and the results are what they were, bit for
+        bit (None also through the exports it used)."""
+        contact_guidance = guidance_mod.resolve(contact_guidance)
         coordination = coordination_mod.resolve(coordination)
         bond_order = bond_order_mod.resolve(bond_order)
         bond_order_mod.check_shared(bond_order, coordination)
@@ -767,6 +781,8 @@ class DiffusionLoss(nn.Module):
 
         corrector = (corrector_steps, corrector_snr) if corrector_steps > 0 else None
         resampling = (resample_passes, jump_length, schedule) if resample_passes > 1 else None
+        # contact guidance: the parameters and the device arrays of its last evaluation, held through every call of the run
+        guide = (contact_guidance, guidance_mod.allocate_info(B, dev)) if contact_guidance is not None else None
         history = multistep_mod.allocate_history(N, B, dev) if multistep else None  # empty; held through every call of the run
         # species control: (rows, temperature) for the species exports; None (no set, temperature 1) keeps the exports used so far
         species_ctl = None
@@ -796,7 +812,8 @@ class DiffusionLoss(nn.Module):
                         eng.sample_loop(frac_d, types_d, len_d, ang_d, off_d, steps[start], end - start, seed, const_d, lattice_d,
                                         use_graph=bool(use_graph), fixed_lengths=fixed, condition=cond_d, next_table=next_d,
                                         lattice_clipmax=clipmax, corrector=corrector, resampling=resampling, length_tie=tie_d,
-                                        symmetry=sym_d, eta=eta, multistep=history, species=species_ctl, crystal_seeds=seeds_d)
+                                        symmetry=sym_d, eta=eta, multistep=history, species=species_ctl, crystal_seeds=seeds_d,
+                                        guidance=guide)
                         start = end
                     if j is not None:
                         vis_crystal_during_sampling(z_table, types_d.cpu().numpy(), lattice_d.cpu().numpy(),
@@ -816,6 +833,13 @@ class DiffusionLoss(nn.Module):
                         return torch.rand(shape, dtype=dt).to(**f32)
                 t_d = torch.empty(B, device=dev, dtype=torch.int32)
                 s_d = torch.empty(B, device=dev, dtype=torch.int32)
+
+                def evaluate():  # the network at t_d on the current state; with contact guidance its eps is guided in place
+                    eps, logits, len0 = eng.predict_scores(frac_d, types_d, len_d, ang_d, t_d, off_d)
+                    if guide is not None and contact_guidance.weight > 0:
+                        from .lattice_helpers import lattice_from_params
+                        eng.contact_guidance_step(frac_d, lattice_from_params(len_d, ang_d), t_d, off_d, eps, guide)
+                    return eps, logits, len0
                 for ev in events:
                     timestep = ev.t
                     if ev.kind == "jump":  # resampling: the state back up to the block's top, in front of pass ev.r
@@ -826,10 +850,10 @@ class DiffusionLoss(nn.Module):
                                           length_tie=tie_d)
                         continue
                     t_d.fill_(timestep)
-                    eps, logits, len0 = eng.predict_scores(frac_d, types_d, len_d, ang_d, t_d, off_d)
+                    eps, logits, len0 = evaluate()
                     for _ in range(corrector_steps):  # predictor-corrector: the moves at t, each followed by a new evaluation
                         eng.corrector_step(frac_d, t_d, off_d, eps, gauss(N, 3), corrector_snr)
-                        eps, logits, len0 = eng.predict_scores(frac_d, types_d, len_d, ang_d, t_d, off_d)
+                        eps, logits, len0 = evaluate()
                     z_l, z_f, u_t = gauss(B, 3), gauss(N, 3), unif(N, S)
                     if species_ctl is not None:  # species control: whichever step below the options name, under it
                         s_d.fill_(timestep - 1 if schedule is None else successor[timestep])
@@ -881,6 +905,8 @@ class DiffusionLoss(nn.Module):
 
         info = eng.rerun_if_out_of_range(rerun)  # (shared with PONITA_DIFFUSION.encode)
         eng.check_status()  # sticky device flags (non-finite outputs, clamped indices): raise instead of returning them
+        if guide is not None:
+            info = dict(info or {}, contact_guidance=guidance_mod.info_to_numpy(guide[1]))
         if frames:
             vis_crystal_during_sampling(z_table, types_d.cpu().numpy(), lattice_d.cpu().numpy(), frac_d.cpu().numpy(),
                                         vis_name + "_final", show_bonds, num_atoms.numpy())

@@ -275,7 +275,8 @@ class HipEngine:
 
     def sample_loop(self, frac, types, lengths, angles, offsets, t_start, n_steps, seed, const_types, lattice_out,
                     use_graph=False, fixed_lengths=None, condition=None, next_table=None, lattice_clipmax=0.999, corrector=None,
-                    resampling=None, length_tie=None, symmetry=None, eta=None, multistep=None, species=None, crystal_seeds=None):
+                    resampling=None, length_tie=None, symmetry=None, eta=None, multistep=None, species=None, crystal_seeds=None,
+                    guidance=None):
         """n_steps iterations of the sampling loop in one library call (arreau_sample_loop; with any of the options below
         arreau_sample_loop_resampled, whose NULL options are the loop without them): in-place update of
         (frac, types, lengths); Philox noise keyed by (seed, timestep, draw, element).  `condition`: the device arrays of a
@@ -301,7 +302,15 @@ class HipEngine:
         `crystal_seeds`: keyed sampling (arreau_sample_loop_keyed; rules in include/arreau_hip.h): a contiguous int64 [B] tensor on
         the device holding the uint64 stream seeds of keyed.stream_seeds -- every draw of crystal b is then keyed by its seed and
         counted within the crystal.  The export is the species one plus the table, so without `species` the steps run under
-        (every class, temperature 1).  None is the loop without it, through the export it used."""
+        (every class, temperature 1).  None is the loop without it, through the export it used.
+        `guidance`: contact guidance (arreau_sample_loop_guided; rules in include/arreau_hip.h): a contact_guidance.ContactGuidance,
+        or the pair (ContactGuidance, info) with info the dict of device arrays of contact_guidance.allocate_info, which then hold
+        the last evaluation's energy, contacts and flags per crystal.  Every network evaluation of every step is followed by one
+        launch that adds the gradient of the contact penalty to its eps.  The export is the keyed one plus the struct, so without
+        `species` the steps run under (every class, temperature 1).  None is the loop without it, through the export it used."""
+        guide = self._guidance_struct(guidance, lengths.shape[0]) if guidance is not None else None
+        if guide is not None and species is None:
+            species = (None, 1.0)
         if crystal_seeds is not None:
             self._check_seeds(crystal_seeds, lengths.shape[0])
             if species is None:
@@ -353,7 +362,9 @@ class HipEngine:
             opts += (_hip.ptr(length_tie), _byref(self._symmetry_struct(symmetry, N) if symmetry is not None else None), _byref(eta_c),
                      _byref(self._multistep_struct(multistep, N, B) if multistep is not None else None),
                      _byref(self._species_struct(species, B)))
-            if crystal_seeds is not None:  # keyed sampling: the same loop with the table of stream seeds
+            if guide is not None:  # contact guidance: the keyed loop (its table may be NULL) with the guidance struct
+                name, opts = "arreau_sample_loop_guided", opts + (_hip.ptr(crystal_seeds), ctypes.byref(guide))
+            elif crystal_seeds is not None:  # keyed sampling: the same loop with the table of stream seeds
                 name, opts = "arreau_sample_loop_keyed", opts + (_hip.ptr(crystal_seeds),)
         elif multistep is not None:
             name, opts = "arreau_sample_loop_multistep", opts + (_hip.ptr(length_tie), _byref(self._multistep_struct(multistep, N, B)))
@@ -368,6 +379,41 @@ class HipEngine:
         else:  # (the plain entry point: A/B runs against an older library through ARREAU_HIP_LIB call it)
             name, opts = "arreau_sample_loop", ()
         _hip.check(getattr(_hip.lib(), name)(*args, *opts, _hip.stream_ptr(self.device)), name)
+
+    def _guidance_struct(self, guidance, B):
+        """arreau_contact_guidance of a ContactGuidance or of the pair (ContactGuidance, info), with the info arrays' shape, dtype
+        and device checked."""
+        from .diffusion.contact_guidance import INFO_KEYS, ContactGuidance
+        params, info = guidance if isinstance(guidance, tuple) else (guidance, None)
+        if not isinstance(params, ContactGuidance):
+            raise ValueError(f"guidance must be a ContactGuidance or the pair (ContactGuidance, info), got {guidance!r}")
+        ptrs = [None, None, None]
+        if info is not None:
+            if not isinstance(info, dict) or set(info) != set(INFO_KEYS):
+                raise ValueError(f"guidance info: expected a dict with exactly the keys {INFO_KEYS}")
+            for q, name in enumerate(INFO_KEYS):
+                t, dtype = info[name], torch.float32 if name == "energy" else torch.int32
+                if (not torch.is_tensor(t) or tuple(t.shape) != (B,) or t.dtype != dtype or t.device != self.device
+                        or not t.is_contiguous()):
+                    raise ValueError(f"guidance info: {name} must be a contiguous {dtype} tensor of shape ({B},) on {self.device}")
+                ptrs[q] = _hip.ptr(t).value
+        return _hip.ContactGuidanceC(params.min_distance, params.weight, params.max_shells, *ptrs)
+
+    def contact_guidance_step(self, frac, lattice, t_crystal, offsets, eps, guidance):
+        """Contact guidance on eps [N,3] in place (arreau_contact_guidance_step; rules in include/arreau_hip.h): frac [N,3] f32,
+        lattice [B,3,3] f32 (the cells the evaluation saw, rows a, b, c), t_crystal [B] i32, offsets [B+1] i32, `guidance` as in
+        sample_loop.  Between predict_scores and a step export it is the guided loop's step bit for bit.  Returns eps."""
+        B, N = int(t_crystal.shape[0]), int(frac.shape[0])
+        guide = self._guidance_struct(guidance, B)
+        for name, t, shape, dtype in (("frac", frac, (N, 3), torch.float32), ("lattice", lattice, (B, 3, 3), torch.float32),
+                                      ("t_crystal", t_crystal, (B,), torch.int32), ("offsets", offsets, (B + 1,), torch.int32),
+                                      ("eps", eps, (N, 3), torch.float32)):
+            if tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"contact_guidance_step: {name} must be a contiguous {dtype} tensor of shape {shape} on {self.device}")
+        _hip.check(_hip.lib().arreau_contact_guidance_step(
+            self._handle, _hip.ptr(frac), _hip.ptr(lattice), _hip.ptr(t_crystal), _hip.ptr(offsets), B, N, _hip.ptr(eps),
+            ctypes.byref(guide), _hip.stream_ptr(self.device)), "arreau_contact_guidance_step")
+        return eps
 
     def sample_loop_species(self, frac, types, lengths, angles, offsets, t_start, n_steps, seed, const_types, lattice_out, species,
                             **options):

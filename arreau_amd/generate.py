@@ -76,6 +76,12 @@ still open, up to `--max_rounds`, and a shortfall is reported, not padded.  The 
 same for every world size and every `--batch` -- up to where the score network changes its kernels with the size of a launch
 (keyed.py, rule 5).  `--keys 17,4711` regenerates those slots alone.  `--template` and `--start_from` runs key a crystal by its
 index in the file times `--samples_per_template` plus the copy.  Without `--keyed` nothing changes, `seed + rank` included.
+
+Contact guidance: `--guide_contacts [--guide_min_distance D --guide_weight W]` steers every step away from contacts shorter than D
+(diffusion/contact_guidance.py): where `--require_valid` throws a crystal with a short contact away and samples again, this pushes
+the contact apart while the crystal is sampled.  With every other option (an `--invert` run guides the decode, not the encode).
+It prints, per rank and in total, the contacts below D, the penalty and the flags of the last network evaluation; `--screen`
+still judges the final state.
 """
 import argparse
 import contextlib
@@ -471,7 +477,25 @@ def build_parser() -> argparse.ArgumentParser:
                          "--cn_cutoff): summed angle histogram, mean q4 and q6 overall and per element and flags per rank and in "
                          "total + order_* arrays in the output file")
     add_coordination_arguments(ap)
+    ap.add_argument("--guide_contacts", action="store_true",
+                    help="contact guidance: steer every sampling step away from contacts shorter than --guide_min_distance (the "
+                         "gradient of a contact penalty added to the predicted eps on the device); prints the contacts and flags of "
+                         "the last network evaluation per rank and in total")
+    ap.add_argument("--guide_min_distance", type=float, default=0.5, help="guide_contacts: contacts below this many A are pushed apart")
+    ap.add_argument("--guide_weight", type=float, default=0.5,
+                    help="guide_contacts: the descent step on the predicted clean structure (0.5 resolves an isolated contact)")
     return ap
+
+
+def check_guidance_arguments(args, error):
+    """The ContactGuidance --guide_contacts asks for, or None; `error(message)` reports a bad value."""
+    if not args.guide_contacts:
+        return None
+    from .diffusion.contact_guidance import ContactGuidance
+    try:
+        return ContactGuidance(min_distance=args.guide_min_distance, weight=args.guide_weight)
+    except ValueError as e:
+        error(f"--guide_contacts: {e}")
 
 
 def add_coordination_arguments(ap):
@@ -655,6 +679,8 @@ def main():
     args = ap.parse_args()
     start = check_start_arguments(args, ap.error)
     slots = check_keyed_arguments(args, ap.error)
+    guide = check_guidance_arguments(args, ap.error)
+    guide_parts = []  # contact guidance: the last-evaluation statistics of every batch this rank sampled
     spec = load_symmetry(args, ap.error)
     if spec is not None and args.eta is not None:
         ap.error("--eta is not supported with --symops")
@@ -722,23 +748,30 @@ def main():
     # lock held around each sampler call.  On a node every rank owns its GPU and the variable is not set.
     lock_path = os.environ.get("ARREAU_GENERATE_GPU_LOCK")
 
+    def guided(res):  # keeps the batch's guidance statistics (the drivers carry the instruments' alone)
+        if guide is not None:
+            from .diffusion import contact_guidance as guidance_mod
+            guide_parts.append(guidance_mod.stats_of(res.info["contact_guidance"], rank))
+        return res
+
     def fn(n, b, cond=None, keys=None):
         with _device_turn(lock_path) if lock_path else contextlib.nullcontext():
-            return model.sample(n, b, VisualizationSetting.NONE, False, condition=cond, num_steps=args.num_steps, **keyed_kw(keys),
-                                corrector_steps=args.corrector_steps, corrector_snr=args.corrector_snr,
-                                resample_passes=args.resample_passes, jump_length=args.jump_length,
-                                lattice_system=args.lattice_system, symmetry=spec, eta=args.eta, multistep=args.multistep,
-                                **species_kw, **keywords)
+            return guided(model.sample(n, b, VisualizationSetting.NONE, False, condition=cond, num_steps=args.num_steps, **keyed_kw(keys),
+                                       corrector_steps=args.corrector_steps, corrector_snr=args.corrector_snr,
+                                       resample_passes=args.resample_passes, jump_length=args.jump_length,
+                                       lattice_system=args.lattice_system, symmetry=spec, eta=args.eta, multistep=args.multistep,
+                                       contact_guidance=guide, **species_kw, **keywords))
     def start_fn(crystals):
         with _device_turn(lock_path) if lock_path else contextlib.nullcontext():
             keys = crystals.crystal_keys if args.keyed else None  # (the crystal's index in the file: set below)
             state = (model.encode(crystals, t=args.start_t, num_steps=args.num_steps) if args.invert
                      else model.noise_to(crystals, args.start_t, **keyed_kw(keys)))
-            return model.sample(visualization_setting=VisualizationSetting.NONE, initial_state=state, num_steps=args.num_steps,
-                                **keyed_kw(keys),
-                                use_constant_atomic_symbols=True if args.invert else None, corrector_steps=args.corrector_steps,
-                                corrector_snr=args.corrector_snr, resample_passes=args.resample_passes, jump_length=args.jump_length,
-                                eta=args.eta, multistep=args.multistep, **species_kw, **keywords)
+            return guided(model.sample(visualization_setting=VisualizationSetting.NONE, initial_state=state, num_steps=args.num_steps,
+                                       **keyed_kw(keys),
+                                       use_constant_atomic_symbols=True if args.invert else None, corrector_steps=args.corrector_steps,
+                                       corrector_snr=args.corrector_snr, resample_passes=args.resample_passes,
+                                       jump_length=args.jump_length, eta=args.eta, multistep=args.multistep, contact_guidance=guide,
+                                       **species_kw, **keywords))
     n_atoms = spec.n_atoms if spec is not None else args.num_atoms
     if start:
         if args.keyed:  # the key of a crystal: its index in the file
@@ -760,6 +793,16 @@ def main():
         res = generate_valid_crystals(fn, args.num_crystals, n_atoms, args.batch, rank, world, max_rounds=args.max_rounds, unique=unique)
     else:
         res = generate_n_crystals(fn, args.num_crystals, n_atoms, args.batch, rank, world, unique=unique)
+    if guide is not None:  # every rank's batches summed, gathered like the results; rank 0 prints
+        from .diffusion import contact_guidance as guidance_mod
+        mine = guidance_mod.total_stats(guide_parts, rank)
+        ranks = [mine]
+        if world > 1:
+            ranks = [None] * world if rank == 0 else None
+            dist.gather_object(mine, ranks, dst=0)
+        if rank == 0:
+            for line in guidance_mod.summary_lines(ranks):
+                print(line)
     if rank == 0:
         special = {"unique": lambda parts: unique_lines(res, unique, device=f"cuda:{local_rank}"),
                    "find_symmetry": lambda parts: symmetry_lines(res, parts, spec)}

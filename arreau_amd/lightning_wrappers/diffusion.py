@@ -401,7 +401,7 @@ class PONITA_DIFFUSION(nn.Module):
                lattice_system=None, symmetry=None, screen=None, unique=None, find_symmetry=None, reduce_cell=None,
                symmetrize=None, match_to=None, eta: Optional[float] = None, initial_state=None,
                multistep: bool = False, elements=None, species_temperature: float = 1.0, crystal_keys=None,
-               conventional_cell=None, coordination=None, bond_order=None) -> SampleResult:
+               conventional_cell=None, coordination=None, bond_order=None, contact_guidance=None) -> SampleResult:
         """lightning_wrappers/diffusion.py:220-253.  `num_atoms_per_sample` may also be a sequence with one atom count
         per crystal of the batch (extension; the reference supports a single int).  Frames of a visualization_setting
         other than NONE go to `<DIFFUSION_DIR>/step_<timestep>.cif` like the reference's PNGs (`vis_name` overrides the
@@ -444,7 +444,12 @@ class PONITA_DIFFUSION(nn.Module):
         diffusion.coordination.CoordinationParams or True -- every atom's neighbours, coordination number and nearest distance
         in the final crystals; SampleResult.coordination holds the arrays (DiffusionLoss.sample).  `bond_order` (extension): a
         diffusion.bond_order.BondOrderParams or True -- every atom's bond-angle histogram and Steinhardt order parameters
-        q_2 .. q_8 in the final crystals; SampleResult.bond_order holds the arrays (DiffusionLoss.sample)."""
+        q_2 .. q_8 in the final crystals; SampleResult.bond_order holds the arrays (DiffusionLoss.sample).  `contact_guidance`
+        (extension): a diffusion.contact_guidance.ContactGuidance or True -- every network evaluation's eps is steered down the
+        gradient of a penalty on contacts shorter than min_distance, so the sampler avoids them instead of being screened for
+        them; SampleResult.info["contact_guidance"] holds the last evaluation's energy, contacts and flags (DiffusionLoss.sample)."""
+        from ..diffusion import contact_guidance as guidance_mod
+        contact_guidance = guidance_mod.resolve(contact_guidance)  # (raises before any work)
         from ..diffusion import keyed as keyed_mod, multistep as multistep_mod, resampling, species as species_mod
         if crystal_keys is not None:  # (raises before any work)
             crystal_keys = keyed_mod.validate_keys(crystal_keys, None, seed, noise if noise in ("philox", "device", "reference") else "philox")
@@ -489,7 +494,7 @@ class PONITA_DIFFUSION(nn.Module):
             screen=screen, unique=unique, find_symmetry=find_symmetry, reduce_cell=reduce_cell, symmetrize=symmetrize,
             match_to=match_to, eta=eta, initial_state=initial_state, multistep=multistep, elements=elements,
             species_temperature=species_temperature, crystal_keys=crystal_keys, conventional_cell=conventional_cell,
-            coordination=coordination, bond_order=bond_order)
+            coordination=coordination, bond_order=bond_order, contact_guidance=contact_guidance)
 
     # ---- starting the sampler from given crystals (extension; rules in include/arreau_hip.h) -------------------------------------
     def _crystal_state(self, crystals, t, what):
@@ -572,7 +577,7 @@ class PONITA_DIFFUSION(nn.Module):
 
     @torch.no_grad()
     def encode(self, crystals, t: Optional[int] = None, num_steps: Optional[int] = None, timesteps=None, fixed_cell: bool = False,
-               use_graph: Optional[bool] = None):
+               use_graph: Optional[bool] = None, contact_guidance=None):
         """DDIM inversion (Song, Meng & Ermon 2021, section 4.3): crystal -> latent, the inverse map of `sample(eta=0)` on
         positions and lengths.  The crystals are taken as the state at the lowest level visited (1 by default) and climb to level
         t (default T-1), one network evaluation per visited level below the top (arreau_invert_loop; rules in
@@ -581,8 +586,11 @@ class PONITA_DIFFUSION(nn.Module):
         written: the network sees the crystals' species at every level, so the matching decode holds them
         (use_constant_atomic_symbols=True).  fixed_cell: the lengths are held.  use_graph: replay one captured step (default: from
         200 steps).  No exact inverse of the final 1 -> 0 denoise step, no ties, symmetry or conditions, no likelihood; no claim
-        on reconstruction quality is made.  Returns a diffusion.inversion.SamplerState at level t."""
-        from ..diffusion import inversion
+        on reconstruction quality is made.  `contact_guidance` other than None is rejected before any work: an inversion has no
+        clean-structure prediction to guide (the library's inversion loop rejects the option too).  Returns a
+        diffusion.inversion.SamplerState at level t."""
+        from ..diffusion import contact_guidance as guidance_mod, inversion
+        guidance_mod.check_sampling(guidance_mod.resolve(contact_guidance), inversion=True)
         T = self.diffusion_loss.T
         levels = inversion.encode_levels(T, t=t, num_steps=num_steps, timesteps=timesteps)  # (raises before any work)
         state = self._crystal_state(crystals, levels[-1], "encode")

@@ -1601,6 +1601,80 @@ int arreau_philox_fill_crystals(const uint64_t* d_seeds, const int32_t* d_crysta
                                 int32_t kind, uint32_t word3, int32_t per_atom_width, int32_t per_crystal_width, float* d_out,
                                 uint32_t* d_raw, void* stream);
 
+/* ---- contact guidance (steer the sampler away from short contacts) -------------------------------------------------------
+ * Training-free, energy-based guidance of the positions: every network evaluation of a step is followed by one launch that adds
+ * the gradient of a contact penalty to the predicted eps, so that what the step predicts as the clean structure has its short
+ * contacts pushed apart.  The reference has no such option; the rules are the library's own (restated in float64 in
+ * arreau_amd/diffusion/contact_guidance.py).  Parameters: min_distance d0 in A (finite, > 0), weight w (finite, >= 0), max_shells
+ * in 1..ARREAU_SCREEN_MAX_SHELLS (the screen's cap, with the screen's meaning).  For crystal b: the wrapped fractional positions
+ * (w = f - floor(f), a result of 1 becomes 0), the Cartesian positions r = (w_0 L_0 + w_1 L_1) + w_2 L_2 and the cell rows a, b, c
+ * = L_0, L_1, L_2 that the step's network evaluation saw (the screen's rules 4 and 5).  Float32, one rounding per operation, in the
+ * order written, never contracted.
+ *   1. contacts: every (i, j, n) with j != i and n = (n_1, n_2, n_3) in the screen's image range for the radius d0
+ *      (q_k = d0 / spacing of the planes across axis k, N_k = max(1, ceil(q_k)), |n_k| <= N_k), s = (n_1 L_0 + n_2 L_1) + n_3 L_2,
+ *      disp = (r_j + s) - r_i, d2 = (dx dx + dy dy) + dz dz, d = sqrt(d2), for which 0 < d2 < (float)((double)d0 * d0) -- the
+ *      comparison of squares the screen's CLOSE count makes, that is 0 < d < d0.  Self images (j = i) are left out: they exert no
+ *      force on positions.  A pair with d2 == 0 is skipped and sets OVERLAP.
+ *   2. penalty: U_b = 1/2 sum_i sum_(j,n) 1/2 (d0 - d)^2, in A^2 (every unordered contact once).
+ *   3. Cartesian gradient on atom i: D_i = sum_(j,n) ((d0 - d) / d) disp.  It points towards the neighbours (dU/dr_i = D_i).
+ *   4. metric-preconditioned fractional gradient: g_i = D_i L^-1, g_i,k = (D_i . c_k) / V with c_0 = b x c, c_1 = c x a,
+ *      c_2 = a x b and V = a . (b x c), signed.  A fractional move -w g_i is then the Cartesian move -w D_i, whatever the cell.
+ *   5. guided prediction: eps'_i = eps_i + (w / sigma_t^2) g_i, sigma = ve_sigmas, t the crystal's timestep (clamped into 1..T and
+ *      flagged in the model's status word like every step).  Every consumer of the step's eps reads eps' in place of eps: the
+ *      predictor in all its instances (ancestral, respaced, eta, multistep and its history, tied, symmetric, species control,
+ *      keyed) and the corrector.  Reading: the predictor's clean-position estimate x - sigma_t^2 eps becomes
+ *      x - sigma_t^2 eps - w g: the predicted clean structure is moved one descent step of size w down U.  For an isolated
+ *      contact each atom moves w (d0 - d) away from the other, so w = 0.5 resolves it exactly.  Under the predictor's reading of
+ *      eps as -score this is guidance by p_t(y | x) ~ exp(-w U / sigma_t^2).  The corrector reads -eps' / sigma_t^2 as its score (its rule
+ *      1) and normalises its step by |eps'| (its rule 2): guidance turns a corrector move, it does not lengthen it.
+ *   6. order within a step: after every network evaluation of the step, a corrector's re-evaluations included, and before
+ *      whatever reads that evaluation's eps (evaluate, guide, correct, evaluate, guide, predict).
+ *   7. atoms with known positions under a condition get a guided eps like any other atom, which the conditioning rule then
+ *      overwrites; they still push their neighbours.
+ *   8. flags (per crystal, int32): NONFINITE a cell entry or coordinate is not finite; CELL the volume is not finite or an axis
+ *      needs more than max_shells images (not (q_k <= max_shells)); EMPTY n = 0; OVERLAP a pair with d2 == 0 was skipped.
+ *      NONFINITE stands alone (nothing else is computed); CELL and EMPTY may be set together.  A crystal flagged NONFINITE, CELL or EMPTY keeps its eps bit for bit, with U = 0 and contacts = 0.
+ *   9. weight == 0 or a NULL struct is the loop without the option: no launch is added, bit identical.  An inversion loop
+ *      rejects the option, bad parameters are rejected, with ARREAU_EINVAL before any work.
+ *  10. the three parameters and the three diagnostic pointers are part of what a cached hipGraph was captured for.
+ * Summation order (fixed, so eager runs, graph replay and a crystal's place in the batch give the same bits): one workgroup of four
+ * waves per crystal, wave v owns atoms v, v + 4, ...; for atom i lane l adds the contacts it meets at e = l, l + 64, ... of the
+ * range e = j M + m (j ascending, images m in lexicographic order), the 64 partial sums are folded by the butterfly
+ * xor 32, 16, ..., 1, a wave adds the energies of its atoms in ascending i, and the four waves are added in wave order.  No
+ * float atomics.  energy = 0.25 * that sum; contacts = the ordered contacts / 2.
+ * What this is not: the penalty acts on positions only -- no cell-strain term (lengths and angles are not guided), no radii or
+ * species dependence (one d0 for every pair), no weight schedule other than 1 / sigma_t^2, no claim on sample quality. */
+#define ARREAU_GUIDE_NONFINITE 1
+#define ARREAU_GUIDE_CELL 2
+#define ARREAU_GUIDE_EMPTY 4
+#define ARREAU_GUIDE_OVERLAP 8
+typedef struct arreau_contact_guidance {
+    float min_distance;  /* d0 in A: finite, > 0 */
+    float weight;        /* w: finite, >= 0; 0 is the loop without the option */
+    int32_t max_shells;  /* 1..ARREAU_SCREEN_MAX_SHELLS */
+    float* d_energy;     /* [B] U_b of the last evaluation (device), or NULL */
+    int32_t* d_contacts; /* [B] its unordered contacts (device), or NULL */
+    int32_t* d_flags;    /* [B] ARREAU_GUIDE_* (device), or NULL */
+} arreau_contact_guidance;
+
+/* arreau_sample_loop_keyed plus `guidance`, a HOST pointer to the struct above; NULL (or weight == 0) is that loop bit for bit.
+ * Every combination that loop accepts, both loop forms, the shape-general path, eager and graph replay. */
+int arreau_sample_loop_guided(arreau_model* model, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                              const int32_t* d_crystal_offsets, int32_t B, int32_t N, int32_t t_start, int32_t n_steps,
+                              uint64_t seed, const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice,
+                              void* d_workspace, size_t workspace_bytes, int32_t use_graph,
+                              const arreau_sample_condition* cond, const arreau_sample_schedule* schedule,
+                              const arreau_corrector* corrector, const arreau_resampling* resampling, const int32_t* d_length_tie,
+                              const arreau_symmetry* symmetry, const float* eta, const arreau_multistep* multistep,
+                              const arreau_species_control* species, const uint64_t* d_crystal_seeds,
+                              const arreau_contact_guidance* guidance, void* stream);
+/* Rules 1-5 and 8 on the caller's arrays: d_eps [N,3] in place, at the per-crystal timesteps d_t [B], with the cells d_lattice
+ * [B,3,3] (rows a, b, c).  `guidance` is required; weight == 0 launches too (eps + 0 g, and the diagnostics).  For tests and
+ * host-driven loops: between arreau_predict_scores and a step export it is the guided loop's step bit for bit. */
+int arreau_contact_guidance_step(const arreau_model* model, const float* d_frac, const float* d_lattice, const int32_t* d_t,
+                                 const int32_t* d_crystal_offsets, int32_t B, int32_t N, float* d_eps /* in place */,
+                                 const arreau_contact_guidance* guidance, void* stream);
+
 /* ---- score-matching training loss, forward part (BASELINE config 5) ------------------------------------------ */
 
 /* The forward-noising half of DiffusionLoss.__call__ (diffusion/diffusion_loss.py:222-234), random draws supplied by
