@@ -1,6 +1,5 @@
 // arreau_predict_scores: one evaluation of the score network on the current sampler state, plus the
 // workspace carve-up and the hipEvent timing hook for the dominant (edge) kernel.
-#include <bit>
 #include <mutex>
 #include <vector>
 
@@ -166,11 +165,14 @@ int run_edge_kernel(const arreau_model* m, const ScorePlan& plan, const float* d
     return rc;
 }
 
+// The neighbour list an evaluation builds or is given, and where its three outputs go.
+struct EdgeList { int32_t *deg, *src; float *dir, *dist; };
+struct ScoreOutputs { float *eps, *logits, *len0; };
+
 // interaction layers (conv.py:105-129 + convnext.py:20-33) on the embedded features in w.xa, then the read-outs.  Every evaluation
 // on the fused kernels ends here: the one place that records its plan.
 int run_layers_and_readout(const arreau_model* m, const ScorePlan& plan, const Workspace& w, const int32_t* deg, const int32_t* src,
-                           const int32_t* d_off, int B, int N, float* d_eps, float* d_logits, float* d_len0,
-                           hipStream_t s) {
+                           const int32_t* d_off, int B, int N, const ScoreOutputs& out, hipStream_t s) {
     int rc;
     if (N > 0) m->ran = plan;
     float* xin = w.xa;
@@ -179,14 +181,14 @@ int run_layers_and_readout(const arreau_model* m, const ScorePlan& plan, const W
         if ((rc = arreau_launch_node_layer(m, plan, l, w.kbuf, deg, src, xin, w.xc, xout, w.xbar, w.vsum, N, s))) return rc;
         float* tmp = xin; xin = xout; xout = tmp;
     }
-    return arreau_launch_readout(m, plan.readout, w.xbar, w.vsum, d_off, B, N, w.gs, d_eps, d_logits, d_len0, s);
+    return arreau_launch_readout(m, plan.readout, w.xbar, w.vsum, d_off, B, N, w.gs, out.eps, out.logits, out.len0, s);
 }
 
 // The score network after prep_kernel: neighbour list (unless given), edge kernel, embedding, interaction layers,
 // read-outs, for the whole batch on `s`.
-int run_network(const arreau_model* m, const ScorePlan& plan, const Workspace& w, bool given, int32_t* deg, int32_t* src, float* dir, float* dist,
-                const float* d_frac, const int32_t* d_types, const int32_t* d_off, int B, int N, float* d_eps,
-                float* d_logits, float* d_len0, hipStream_t s) {
+int run_network(const arreau_model* m, const ScorePlan& plan, const Workspace& w, bool given, const EdgeList& e, const float* d_frac,
+                const int32_t* d_types, const int32_t* d_off, int B, int N, const ScoreOutputs& out, hipStream_t s) {
+    const auto [deg, src, dir, dist] = e;
     int rc;
     if (plan.general) {
         // shape-general fp32 kernels (train_net.hip): any hidden_dim / basis_dim / widening, plain weights (never stale)
@@ -196,8 +198,8 @@ int run_network(const arreau_model* m, const ScorePlan& plan, const Workspace& w
         float* x0 = arreau_general_x0(mm, N, B, s);
         if (!x0) return ARREAU_EHIP;
         if ((rc = arreau_launch_embed(m, d_frac, d_types, w.lattice, w.batch, w.cvec, N, x0, s))) return rc;
-        return arreau_general_network(mm, arreau_graph_view{w.batch, deg, src, w.lattice, dir, dist}, d_off, B, N, d_eps, d_logits,
-                                      d_len0, s);
+        return arreau_general_network(mm, arreau_graph_view{w.batch, deg, src, w.lattice, dir, dist}, d_off, B, N, out.eps, out.logits,
+                                      out.len0, s);
     }
     if (!given) {
         // neighbour list and embedding side by side in one launch (both need prep_kernel's outputs only)
@@ -209,7 +211,7 @@ int run_network(const arreau_model* m, const ScorePlan& plan, const Workspace& w
         if ((rc = run_edge_kernel(m, plan, dir, dist, deg, w, N, s))) return rc;
         if ((rc = arreau_launch_embed(m, d_frac, d_types, w.lattice, w.batch, w.cvec, N, w.xa, s))) return rc;
     }
-    return run_layers_and_readout(m, plan, w, deg, src, d_off, B, N, d_eps, d_logits, d_len0, s);
+    return run_layers_and_readout(m, plan, w, deg, src, d_off, B, N, out, s);
 }
 }  // namespace
 
@@ -235,15 +237,12 @@ extern "C" int arreau_predict_scores(const arreau_model* m, const float* d_frac,
     if (use_given_edges) {
         ARREAU_REQUIRE(d_deg && d_src && d_dir && d_dist, "arreau_predict_scores: teacher-forced edges missing");
     }
-    int32_t* deg = d_deg ? d_deg : w.deg;
-    int32_t* src = d_src ? d_src : w.src;
-    float* dir = d_dir ? d_dir : w.dir;
-    float* dist = d_dist ? d_dist : w.dist;
+    const EdgeList e{d_deg ? d_deg : w.deg, d_src ? d_src : w.src, d_dir ? d_dir : w.dir, d_dist ? d_dist : w.dist};
     hipStream_t s = (hipStream_t)stream;
     int rc;
     if ((rc = arreau_launch_prep(m, d_frac, d_lengths, d_angles, d_t, d_off, B, N, w.lattice, w.cart, w.batch, w.cvec, s)))
         return rc;
-    return run_network(m, plan, w, use_given_edges != 0, deg, src, dir, dist, d_frac, d_types, d_off, B, N, d_eps, d_logits, d_len0, s);
+    return run_network(m, plan, w, use_given_edges != 0, e, d_frac, d_types, d_off, B, N, {d_eps, d_logits, d_len0}, s);
 }
 
 // PonitaFiberBundle.forward on the reference's own batch attributes (the inner operator seam).
@@ -278,7 +277,7 @@ extern "C" int arreau_ponita_forward(const arreau_model* m, const float* d_x, co
     }
     if ((rc = run_edge_kernel(m, plan, d_dir, d_dist, d_deg, w, N, s))) return rc;
     if ((rc = arreau_launch_embed_general(m, d_x, d_vec, N, w.xa, s))) return rc;
-    return run_layers_and_readout(m, plan, w, d_deg, d_src, d_off, B, N, d_vec_out, d_logits, d_global_scalar, s);
+    return run_layers_and_readout(m, plan, w, d_deg, d_src, d_off, B, N, {d_vec_out, d_logits, d_global_scalar}, s);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -311,7 +310,7 @@ int enqueue_sample_step(const arreau_model* m, const ScorePlan& plan, const Samp
                                                    st.frac, st.types, w.cvec, w.xa, s, w.t_cur, next_t, /*advance=*/j == 0)))
                 return rc;
             if ((rc = run_edge_kernel(m, plan, w.dir, w.dist, w.deg, w, st.N, s))) return rc;
-            if ((rc = run_layers_and_readout(m, plan, w, w.deg, w.src, st.offsets, st.B, st.N, w.eps, w.logits, nullptr, s))) return rc;
+            if ((rc = run_layers_and_readout(m, plan, w, w.deg, w.src, st.offsets, st.B, st.N, {w.eps, w.logits, nullptr}, s))) return rc;
         } else {
             // the first set-up of the step advances the device timestep; a corrector's re-evaluation reads it (t_cur)
             if ((rc = j == 0 ? arreau_launch_prep(m, st.frac, st.lengths, st.angles, nullptr, st.offsets, st.B, st.N, w.lattice, w.cart, w.batch,
@@ -319,8 +318,8 @@ int enqueue_sample_step(const arreau_model* m, const ScorePlan& plan, const Samp
                              : arreau_launch_prep(m, st.frac, st.lengths, st.angles, w.t_cur, st.offsets, st.B, st.N, w.lattice, w.cart, w.batch,
                                                   w.cvec, s)))
                 return rc;
-            if ((rc = run_network(m, plan, w, false, w.deg, w.src, w.dir, w.dist, st.frac, st.types, st.offsets, st.B, st.N, w.eps, w.logits,
-                                  pool_in_update ? nullptr : w.len0, s)))
+            if ((rc = run_network(m, plan, w, false, {w.deg, w.src, w.dir, w.dist}, st.frac, st.types, st.offsets, st.B, st.N,
+                                  {w.eps, w.logits, pool_in_update ? nullptr : w.len0}, s)))
                 return rc;
         }
         // contact guidance: the eps of this evaluation, guided in place, is what the corrector and the predictor below read
@@ -340,129 +339,176 @@ int enqueue_sample_step(const arreau_model* m, const ScorePlan& plan, const Samp
 // RePaint resampling (arreau_sample_loop_resampled): the blocks of one loop call, from the host's list of the steps it visits.
 // Block k runs steps first .. first + count - 1 (indices into the visited list), R times; passes 1..R-1 start with the jump
 // bottom -> top.
-struct ResampleBlock {
-    int first, count, top, bottom;
-};
-struct ResamplePlan {
-    int passes, jump;
-    std::vector<ResampleBlock> blocks;
+struct ResampleBlock { int first, count, top, bottom; };
+
+// What an arreau_sample_loop* export (or arreau_invert_loop) was called with besides the model and the state.  The export fills it
+// with designated initialisers: an option it does not take stays null.
+struct LoopRequest {
+    int32_t t_start = 0, n_steps = 0;
+    uint64_t seed = 0;
+    void* workspace = nullptr;
+    size_t workspace_bytes = 0;
+    int32_t use_graph = 0;
+    void* stream = nullptr;
+    const arreau_sample_condition* condition = nullptr;
+    const arreau_sample_schedule* schedule = nullptr;  // of an inversion loop: the ascending table
+    const arreau_corrector* corrector = nullptr;
+    const arreau_resampling* resampling = nullptr;
+    const int32_t* d_length_tie = nullptr;
+    const arreau_symmetry* symmetry = nullptr;
+    const float* eta = nullptr;
+    const arreau_multistep* multistep = nullptr;
+    const arreau_species_control* species = nullptr;
+    bool species_required = false;  // arreau_sample_loop_species and the exports built on it (their multistep rules have their own wording)
+    const uint64_t* d_crystal_seeds = nullptr;
+    const arreau_contact_guidance* guidance = nullptr;
+    bool invert = false;  // arreau_invert_loop: t_start is the first level
 };
 
-// The key of a captured step: the buffers, sizes and seed, the plan (every kernel choice of the evaluation), and the condition's
-// pointers, the schedule's table and clip, the corrector's step count and snr, the resampling's R and J (a resampled step reads
-// the pass word), the lattice systems' tie array, the symmetry tables, the eta of a DDIM-style step, the history buffers of a
-// multistep step, the admission rows and temperature of species control, the table of stream seeds of a keyed loop and the parameters
-// and diagnostic pointers of contact guidance, which are kernel arguments
-// or launch choices of the capture: a change of any of them must not replay the stale graph.  So is the direction: an inversion
-// loop (arreau_invert_loop) on the same buffers, table pointer included, captures other kernels than a sampling loop.
-SampleGraphKey sample_graph_key(const ScorePlan& score, const SampleState& st, const void* d_workspace, uint64_t seed,
-                                const StepOptions& opt, const ResamplePlan* plan) {
-    SampleGraphKey k{};
-    k.state = st; k.workspace = d_workspace; k.seed = seed; k.plan = score;
-    if (opt.cond) k.cond = *opt.cond;
-    if (opt.sym) k.sym = *opt.sym;
-    k.length_tie = opt.length_tie;
-    k.scheduled = opt.sched != nullptr;
-    if (opt.sched) {
-        k.sched_next = opt.sched->next;
-        k.clip_bits = std::bit_cast<uint32_t>(opt.sched->clipmax);
+// A request that passed resolve_loop_request: what the loop runs on.
+struct LoopCall {
+    ScorePlan score;  // of every evaluation of the call
+    Workspace w;
+    SampleOptions opt;
+    std::vector<ResampleBlock> blocks;  // of a resampled loop (opt.resample_passes > 1)
+};
+
+// The blocks of a resampled loop: the visited steps t_1 .. t_n and the successor of t_n, from the host copy of the schedule (or
+// t - 1 without one), cut every `jump` steps.
+int resample_blocks(const char* who, const LoopRequest& req, const arreau_resampling* resampling, int jump,
+                    std::vector<ResampleBlock>* blocks) {
+    const int n_steps = req.n_steps, t_start = req.t_start;
+    std::vector<int> steps;
+    int last_succ = 0;
+    if (req.schedule) {
+        ARREAU_REQUIRE(resampling->timesteps != nullptr && resampling->n_timesteps >= 1,
+                       std::string(who) + ": a respaced loop needs the host copy of its schedule (timesteps)");
+        const int32_t* ts = resampling->timesteps;
+        const int K = resampling->n_timesteps;
+        int i0 = -1;
+        for (int i = 0; i < K; ++i)
+            if (ts[i] == t_start) { i0 = i; break; }
+        ARREAU_REQUIRE(i0 >= 0 && (int64_t)i0 + n_steps <= K,
+                       std::string(who) + ": the host schedule does not hold t_start followed by n_steps - 1 timesteps");
+        steps.assign(ts + i0, ts + i0 + n_steps);
+        last_succ = i0 + n_steps < K ? ts[i0 + n_steps] : 0;
+    } else {
+        for (int i = 0; i < n_steps; ++i) steps.push_back(t_start - i);
+        last_succ = t_start - n_steps;
     }
-    k.corrector_steps = opt.corr.steps;
-    k.snr_bits = std::bit_cast<uint32_t>(opt.corr.snr);
-    if (plan) {
-        k.resample_passes = plan->passes;
-        k.resample_jump = plan->jump;
+    for (int a = 0; a < n_steps; a += jump) {
+        const int cnt = n_steps - a < jump ? n_steps - a : jump;
+        blocks->push_back(ResampleBlock{a, cnt, steps[a], a + cnt < n_steps ? steps[a + cnt] : last_succ});
     }
-    if (opt.eta >= 0.0f) {
-        k.eta_step = 1;
-        k.eta_bits = std::bit_cast<uint32_t>(opt.eta);
-    }
-    k.invert = opt.invert ? 1 : 0;
-    if (opt.ms) k.ms = *opt.ms;
-    if (opt.species) {
-        k.species = 1;
-        k.species_allow = opt.species->d_allow;
-        k.species_tau_bits = std::bit_cast<uint32_t>(opt.species->temperature);
-    }
-    k.crystal_seeds = opt.crystal_seeds;
-    if (opt.guide) {
-        k.guide = 1;
-        k.guide_d0_bits = std::bit_cast<uint32_t>(opt.guide->min_distance);
-        k.guide_weight_bits = std::bit_cast<uint32_t>(opt.guide->weight);
-        k.guide_max_shells = opt.guide->max_shells;
-        k.guide_energy = opt.guide->d_energy; k.guide_contacts = opt.guide->d_contacts; k.guide_flags = opt.guide->d_flags;
-    }
-    return k;
+    return ARREAU_OK;
 }
 
-int sample_loop_impl(arreau_model* m, const SampleState& st, int32_t t_start, int32_t n_steps, uint64_t seed, void* d_workspace,
-                     size_t workspace_bytes, int32_t use_graph, const arreau_sample_condition* condition,
-                     const arreau_sample_schedule* schedule, const arreau_corrector* corrector,
-                     const ResamplePlan* plan /* null: no resampling */, const int32_t* d_length_tie /* null: untied */,
-                     const arreau_symmetry* sym /* null: no symmetry */, float eta /* negative: the ancestral step */, void* stream,
-                     bool invert = false /* DDIM inversion: t_start is the first level, `schedule` the ascending table; no other option */,
-                     const arreau_multistep* ms = nullptr /* second-order multistep: the history buffers; eta is then 0 */,
-                     const arreau_species_control* species = nullptr /* species control (checked by the export) */,
-                     const uint64_t* crystal_seeds = nullptr /* keyed sampling: the stream seed of every crystal */,
-                     const arreau_contact_guidance* guide = nullptr /* contact guidance (checked by the export); weight 0: none */) {
-    ARREAU_REQUIRE(!invert || !guide, "arreau_invert_loop: an inversion loop takes no contact guidance");
-    if (corrector) {
-        const int rc = arreau_corrector_check(corrector->steps, corrector->snr, "arreau_sample_loop_corrected");
-        if (rc) return rc;
+// The one place the rules of the options are applied (they are stated in include/arreau_hip.h): every check of a loop call, and
+// what the accepted call runs on in *c.  The order is part of the interface -- the first failing check is the one reported
+// (DESIGN.md lists it) --, and so are the messages, also where one names another export than `who`.  arreau_launch_reverse guards
+// the combinations once more for the step exports, which reach it directly.
+int resolve_loop_request(const char* who, const arreau_model* m, const SampleState& st, const LoopRequest& req, LoopCall* c) {
+    const std::string name(who);
+    SampleOptions& o = c->opt = SampleOptions{};
+    const arreau_sample_condition* condition = req.condition;
+    const arreau_corrector* corrector = req.corrector;
+    const arreau_resampling* resampling = req.resampling;
+    int rc;
+    if (req.guidance && (rc = arreau_contact_guidance_check(req.guidance, who))) return rc;
+    if (req.species_required && (rc = arreau_species_check(req.species, who, &o.species))) return rc;  // (-0 -> +0)
+    o.species_on = req.species_required;
+    if (req.eta && (rc = arreau_eta_check(*req.eta, who))) return rc;
+    ARREAU_REQUIRE(!req.symmetry || !req.eta, name + ": space-group symmetry is not combined with an eta");
+    if (req.symmetry) {
+        if ((rc = arreau_symmetry_check(req.symmetry, who))) return rc;
+        ARREAU_REQUIRE(!resampling || resampling->passes <= 1, name + ": space-group symmetry is not combined with resampling (passes > 1)");
     }
-    const int B = st.B, N = st.N;
+    if (req.multistep) {
+        // a multistep loop is the eta = 0 loop on the caller's history buffers; a schedule, a tie, species control, keys and guidance only
+        const std::string ms = name + (req.species_required ? ": multistep is not combined with " : ": not combined with ");
+        if ((rc = arreau_multistep_check(req.multistep, who))) return rc;
+        if ((rc = arreau_condition_to_dev(condition, &o.cond))) return rc;
+        ARREAU_REQUIRE(arreau_condition_empty(&o.cond), ms + "a condition");
+        ARREAU_REQUIRE(!corrector || corrector->steps == 0, ms + "corrector steps");
+        ARREAU_REQUIRE(!resampling || resampling->passes == 1, ms + "resampling (passes > 1)");
+        ARREAU_REQUIRE(!req.symmetry, ms + "space-group symmetry");
+        ARREAU_REQUIRE(!req.eta || *req.eta == 0.0f, name + ": a multistep loop is the eta = 0 loop");
+        condition = nullptr; corrector = nullptr; resampling = nullptr;  // what they still hold is the loop without them: not read
+    }
+    o.eta = req.multistep ? 0.0f : (req.eta ? *req.eta + 0.0f /* -0 -> +0 */ : -1.0f);
+    if (resampling) {
+        if ((rc = arreau_resampling_check(resampling->passes, resampling->jump_length, who))) return rc;
+        if (resampling->passes > 1) {
+            o.resample_passes = resampling->passes;
+            o.resample_jump = resampling->jump_length;
+            if (req.n_steps > 0 && (rc = resample_blocks(who, req, resampling, o.resample_jump, &c->blocks))) return rc;
+        }
+    }
+    ARREAU_REQUIRE(!req.invert || !req.guidance, "arreau_invert_loop: an inversion loop takes no contact guidance");
+    if (corrector) {
+        if ((rc = arreau_corrector_check(corrector->steps, corrector->snr, "arreau_sample_loop_corrected"))) return rc;
+        // a NULL corrector and steps == 0 are the same loop (and the same graph key): the snr is then not read
+        if (corrector->steps > 0) o.corr = CorrectorDev{corrector->steps, corrector->snr};
+    }
     ARREAU_REQUIRE(m && st.frac && st.types && st.lengths && st.angles && st.offsets && st.lattice, "arreau_sample_loop: null pointer");
-    ARREAU_REQUIRE(B >= 1 && N >= 0 && n_steps >= 0, "arreau_sample_loop: bad size");
-    const ScorePlan score = arreau_score_plan(m, N);  // of every evaluation of this call
-    ARREAU_REQUIRE(!m->packed_stale || score.general,
+    ARREAU_REQUIRE(st.B >= 1 && st.N >= 0 && req.n_steps >= 0, "arreau_sample_loop: bad size");
+    c->score = arreau_score_plan(m, st.N);
+    ARREAU_REQUIRE(!m->packed_stale || c->score.general,
                    "arreau_sample_loop: weights were updated for training only; re-create the model or select the general path");
-    if (schedule) {
-        ARREAU_REQUIRE(schedule->d_next != nullptr, "arreau_sample_loop_scheduled: null next-timestep table");
-        ARREAU_REQUIRE(schedule->lattice_clipmax > 0.0f && schedule->lattice_clipmax <= 1.0f,
+    if (req.schedule) {
+        ARREAU_REQUIRE(req.schedule->d_next != nullptr, "arreau_sample_loop_scheduled: null next-timestep table");
+        ARREAU_REQUIRE(req.schedule->lattice_clipmax > 0.0f && req.schedule->lattice_clipmax <= 1.0f,
                        "arreau_sample_loop_scheduled: lattice_clipmax must lie in (0, 1]");
         // the loop starts one above t_start (d_next[t_start + 1] == t_start, include/arreau_hip.h), so t_start + 1 <= T
-        ARREAU_REQUIRE(n_steps == 0 || (t_start >= 1 && t_start <= m->T - 1), "arreau_sample_loop_scheduled: t_start must lie in 1..T-1");
+        ARREAU_REQUIRE(req.n_steps == 0 || (req.t_start >= 1 && req.t_start <= m->T - 1), "arreau_sample_loop_scheduled: t_start must lie in 1..T-1");
+        o.sched = StepScheduleDev{req.schedule->d_next, nullptr, req.schedule->lattice_clipmax};
     } else {
-        ARREAU_REQUIRE(t_start <= m->T && t_start - n_steps >= 0, "arreau_sample_loop: timesteps t_start .. t_start-n_steps+1 must lie in 1..T");
+        ARREAU_REQUIRE(req.t_start <= m->T && req.t_start - req.n_steps >= 0,
+                       "arreau_sample_loop: timesteps t_start .. t_start-n_steps+1 must lie in 1..T");
     }
-    ARREAU_REQUIRE(d_workspace != nullptr, "arreau_sample_loop: null workspace");
-    Workspace w = carve(&m->cfg, N, B, d_workspace, workspace_bytes);
-    if (w.bytes > workspace_bytes) {
+    ARREAU_REQUIRE(req.workspace != nullptr, "arreau_sample_loop: null workspace");
+    c->w = carve(&m->cfg, st.N, st.B, req.workspace, req.workspace_bytes);
+    if (c->w.bytes > req.workspace_bytes) {
         arreau_set_error("arreau_sample_loop: workspace too small");
         return ARREAU_ECAPACITY;
     }
-    SampleConditionDev cond_dev;
-    int rc;
-    if ((rc = arreau_condition_to_dev(condition, &cond_dev))) return rc;
-    const StepScheduleDev sched_dev{schedule ? schedule->d_next : nullptr, nullptr, schedule ? schedule->lattice_clipmax : 0.0f};
-    // the options of every step of this call, built once
-    StepOptions opt;
-    opt.cond = arreau_condition_empty(&cond_dev) ? nullptr : &cond_dev;  // empty: the unconditioned loop
-    opt.sched = schedule ? &sched_dev : nullptr;                         // null: every timestep, t_start down
-    // a NULL corrector and steps == 0 are the same loop (and the same graph key): the snr is then not read
-    if (corrector && corrector->steps > 0) opt.corr = CorrectorDev{corrector->steps, corrector->snr};
-    opt.length_tie = d_length_tie;
-    opt.sym = sym;
-    opt.eta = eta;
-    opt.invert = invert;
-    opt.ms = ms;
-    opt.species = species;
-    opt.crystal_seeds = crystal_seeds;
-    opt.guide = guide && guide->weight > 0.0f ? guide : nullptr;  // weight 0: the loop without the option (and its graph key)
-    ARREAU_REQUIRE(!ms || (!opt.cond && opt.corr.steps == 0 && !plan && !sym && !invert && eta == 0.0f),
+    if ((rc = arreau_condition_to_dev(condition, &o.cond))) return rc;  // (without a mask: all null, the unconditioned loop)
+    o.pass = o.resample_passes > 1 ? c->w.pass : nullptr;
+    o.length_tie = req.d_length_tie;
+    if (req.symmetry) o.sym = *req.symmetry;
+    if (req.multistep) o.ms = *req.multistep;
+    o.invert = req.invert;
+    o.crystal_seeds = req.d_crystal_seeds;
+    if (req.guidance && req.guidance->weight > 0.0f) o.guide = *req.guidance;  // weight 0: the loop without the option (and its graph key)
+    const bool plain = arreau_condition_empty(&o.cond) && o.corr.steps == 0 && o.resample_passes == 0;
+    ARREAU_REQUIRE(!req.multistep || (plain && !req.symmetry && !req.invert && o.eta == 0.0f),
                    "arreau_sample_loop_multistep: a multistep loop takes no condition, corrector steps, resampling or symmetry");
-    ARREAU_REQUIRE(!invert || (schedule && !opt.cond && opt.corr.steps == 0 && !plan && !d_length_tie && !sym && eta < 0.0f),
+    ARREAU_REQUIRE(!req.invert || (plain && req.schedule && !req.d_length_tie && !req.symmetry && o.eta < 0.0f),
                    "arreau_invert_loop: an inversion loop takes its ascending table and no sampling option");
-    if (n_steps == 0) return ARREAU_OK;
-    hipStream_t s = (hipStream_t)stream;
-    ARREAU_REQUIRE(!sym || (opt.cond == nullptr && opt.corr.steps == 0 && plan == nullptr),
+    // (read for n_steps > 0 only: an empty loop with these options is accepted)
+    ARREAU_REQUIRE(req.n_steps == 0 || !req.symmetry || plain,
                    "arreau_sample_loop_sym: space-group symmetry is not combined with a condition, corrector steps or resampling");
-    opt.pass = plan ? w.pass : nullptr;
+    return ARREAU_OK;
+}
+
+// What every arreau_sample_loop* export and arreau_invert_loop run, `who` being the export: the checks, then the loop.
+int run_sample_loop(const char* who, arreau_model* m, const SampleState& st, const LoopRequest& req) {
+    LoopCall c;
+    int rc;
+    if ((rc = resolve_loop_request(who, m, st, req, &c))) return rc;
+    if (req.n_steps == 0) return ARREAU_OK;
+    const int B = st.B, N = st.N, t_start = req.t_start, n_steps = req.n_steps;
+    const uint64_t seed = req.seed;
+    const ScorePlan& score = c.score;  // of every evaluation of this call
+    const Workspace& w = c.w;
+    const StepOptions opt = c.opt.view();  // the options of every step of this call
+    const bool resampled = c.opt.resample_passes > 1;
+    hipStream_t s = (hipStream_t)req.stream;
     if (score.no_prep) {
         // t_cur holds the timestep of the step in progress; every step's first launch advances it, so it starts one above (in a
         // respaced loop at the table entry t_start + 1, whose successor is t_start) -- an inversion loop, which climbs, one below
         // (the ascending table's entry t_start - 1, whose successor is t_start)
-        const int before = invert ? -1 : 1;
+        const int before = opt.invert ? -1 : 1;
         ARREAU_LAUNCH(fill_i32_kernel, dim3((B + 255) / 256), dim3(256), 0, s, w.t_cur, t_start + before, B);
         ARREAU_CHECK_HIP(hipGetLastError());
         if ((rc = arreau_launch_prep(m, st.frac, st.lengths, st.angles, w.t_cur, st.offsets, B, N, w.lattice, w.cart, w.batch, w.cvec, s,
@@ -474,11 +520,11 @@ int sample_loop_impl(arreau_model* m, const SampleState& st, int32_t t_start, in
     }
     // steps run (every pass of every block counts)
     int64_t n_runs = n_steps;
-    if (plan) {
+    if (resampled) {
         n_runs = 0;
-        for (const ResampleBlock& bl : plan->blocks) n_runs += (int64_t)plan->passes * bl.count;
+        for (const ResampleBlock& bl : c.blocks) n_runs += (int64_t)c.opt.resample_passes * bl.count;
     }
-    const bool graph_mode = use_graph && n_runs >= 3;
+    const bool graph_mode = req.use_graph && n_runs >= 3;
     hipStream_t user = s;
     hipEvent_t ev = nullptr;
     SampleGraphKey key{};
@@ -502,10 +548,10 @@ int sample_loop_impl(arreau_model* m, const SampleState& st, int32_t t_start, in
         s = (hipStream_t)m->loop_stream;
         ARREAU_CHECK_HIP(hipEventRecord(ev, user));
         ARREAU_CHECK_HIP(hipStreamWaitEvent(s, ev, 0));
-        // The executable graph is kept with the model and reused while the next call names the same buffers, sizes and seed
-        // (a sampler drawing sub-batch after sub-batch through the caching allocator does): capture + instantiation, about
+        // The executable graph is kept with the model and reused while the next call names the same buffers, sizes, seed, plan and
+        // options (a sampler drawing sub-batch after sub-batch through the caching allocator does): capture + instantiation, about
         // 2 ms, are then paid once.  The timestep is not part of the graph (it lives in t_next / t_cur, set above).
-        key = sample_graph_key(score, st, d_workspace, seed, opt, plan);
+        key = SampleGraphKey{st, req.workspace, seed, score, c.opt};
         exec = (hipGraphExec_t)m->retired_graph;
         have_exec = exec && key == m->graph_key;
     }
@@ -537,7 +583,7 @@ int sample_loop_impl(arreau_model* m, const SampleState& st, int32_t t_start, in
         ARREAU_CHECK_HIP(hipGraphLaunch(exec, s));
         return ARREAU_OK;
     };
-    if (!plan) {
+    if (!resampled) {
         for (int i = 0; i < n_steps; ++i)
             if ((rc = run_step())) return rc;
     } else {
@@ -546,11 +592,11 @@ int sample_loop_impl(arreau_model* m, const SampleState& st, int32_t t_start, in
         const JumpLoopDev loop{w.lattice, w.cvec, w.t_next, w.t_cur, w.pass};
         ARREAU_LAUNCH(fill_i32_kernel, dim3(1), dim3(256), 0, s, w.pass, 0, 1);
         ARREAU_CHECK_HIP(hipGetLastError());
-        for (const ResampleBlock& bl : plan->blocks) {
-            for (int r = 0; r < plan->passes; ++r) {
+        for (const ResampleBlock& bl : c.blocks) {
+            for (int r = 0; r < c.opt.resample_passes; ++r) {
                 if (r > 0 && (rc = arreau_launch_resample_jump(m, st, /*d_s=*/nullptr, /*d_t=*/nullptr, bl.bottom, bl.top, w.batch,
-                                                               StepNoiseSrc{.seed = seed, .seeds = crystal_seeds}, (uint32_t)r, opt.cond, &loop,
-                                                               d_length_tie, s)))
+                                                               StepNoiseSrc{.seed = seed, .seeds = opt.crystal_seeds}, (uint32_t)r, opt.cond, &loop,
+                                                               opt.length_tie, s)))
                     return rc;
                 for (int i = 0; i < bl.count; ++i)
                     if ((rc = run_step())) return rc;
@@ -564,62 +610,20 @@ int sample_loop_impl(arreau_model* m, const SampleState& st, int32_t t_start, in
     ARREAU_CHECK_HIP(hipStreamWaitEvent(user, ev, 0));  // the caller's stream continues after the loop
     return ARREAU_OK;
 }
-
-// What every arreau_sample_loop* export runs, `who` being the export: the resampling plan (none without `resampling`), then the loop.
-int sample_loop(const char* who, arreau_model* m, const SampleState& st, int32_t t_start, int32_t n_steps, uint64_t seed,
-                void* d_workspace, size_t workspace_bytes, int32_t use_graph, void* stream,
-                const arreau_sample_condition* condition = nullptr, const arreau_sample_schedule* schedule = nullptr,
-                const arreau_corrector* corrector = nullptr, const arreau_resampling* resampling = nullptr,
-                const int32_t* d_length_tie = nullptr, const arreau_symmetry* sym = nullptr, float eta = -1.0f,
-                const arreau_multistep* ms = nullptr, const arreau_species_control* species = nullptr,
-                const uint64_t* crystal_seeds = nullptr, const arreau_contact_guidance* guide = nullptr) {
-    ResamplePlan plan{1, 1, {}};
-    if (resampling) {
-        int rc;
-        if ((rc = arreau_resampling_check(resampling->passes, resampling->jump_length, who))) return rc;
-        plan.passes = resampling->passes;
-        plan.jump = resampling->jump_length;
-    }
-    if (plan.passes > 1 && n_steps > 0) {
-        // the visited steps t_1 .. t_n and the successor of t_n, from the host copy of the schedule (or t - 1 without one)
-        std::vector<int> steps;
-        int last_succ = 0;
-        if (schedule) {
-            ARREAU_REQUIRE(resampling->timesteps != nullptr && resampling->n_timesteps >= 1,
-                           std::string(who) + ": a respaced loop needs the host copy of its schedule (timesteps)");
-            const int32_t* ts = resampling->timesteps;
-            const int K = resampling->n_timesteps;
-            int i0 = -1;
-            for (int i = 0; i < K; ++i)
-                if (ts[i] == t_start) { i0 = i; break; }
-            ARREAU_REQUIRE(i0 >= 0 && (int64_t)i0 + n_steps <= K,
-                           std::string(who) + ": the host schedule does not hold t_start followed by n_steps - 1 timesteps");
-            steps.assign(ts + i0, ts + i0 + n_steps);
-            last_succ = i0 + n_steps < K ? ts[i0 + n_steps] : 0;
-        } else {
-            for (int i = 0; i < n_steps; ++i) steps.push_back(t_start - i);
-            last_succ = t_start - n_steps;
-        }
-        for (int a = 0; a < n_steps; a += plan.jump) {
-            const int cnt = n_steps - a < plan.jump ? n_steps - a : plan.jump;
-            plan.blocks.push_back(ResampleBlock{a, cnt, steps[a], a + cnt < n_steps ? steps[a + cnt] : last_succ});
-        }
-    }
-    return sample_loop_impl(m, st, t_start, n_steps, seed, d_workspace, workspace_bytes, use_graph, condition, schedule, corrector,
-                            plan.passes > 1 ? &plan : nullptr, d_length_tie, sym, eta, stream, /*invert=*/false, ms, species, crystal_seeds,
-                            guide);
-}
 }  // namespace
 
-// The exports: each of the first seven is the one before it plus one option (NULL: the loop without it), a thin adapter onto
-// sample_loop; arreau_sample_loop_eta is the tied one plus an eta, arreau_sample_loop_multistep the tied one plus the history buffers.
-// The rules of the options are stated in include/arreau_hip.h.
+// The exports: each is a fill of the state and of a LoopRequest with what it takes, and one call of run_sample_loop under its own
+// name.  The first six are each the one before plus one option (NULL: the loop without it); _eta, _multistep and _sym are the tied
+// one plus theirs; _species takes all of those, _keyed and _guided one more each.  The rules of the options are stated in
+// include/arreau_hip.h and applied by resolve_loop_request.
 extern "C" int arreau_sample_loop(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
                                   const int32_t* d_off, int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed,
                                   const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice, void* d_workspace,
                                   size_t workspace_bytes, int32_t use_graph, void* stream) {
     const SampleState st{d_frac, d_types, d_lengths, d_angles, d_off, B, N, d_const_types, d_fixed_lengths, d_lattice};
-    return sample_loop("arreau_sample_loop", m, st, t_start, n_steps, seed, d_workspace, workspace_bytes, use_graph, stream);
+    return run_sample_loop("arreau_sample_loop", m, st,
+                           {.t_start = t_start, .n_steps = n_steps, .seed = seed, .workspace = d_workspace, .workspace_bytes = workspace_bytes,
+                            .use_graph = use_graph, .stream = stream});
 }
 
 extern "C" int arreau_sample_loop_conditioned(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
@@ -628,8 +632,9 @@ extern "C" int arreau_sample_loop_conditioned(arreau_model* m, float* d_frac, in
                                               void* d_workspace, size_t workspace_bytes, int32_t use_graph,
                                               const arreau_sample_condition* condition, void* stream) {
     const SampleState st{d_frac, d_types, d_lengths, d_angles, d_off, B, N, d_const_types, d_fixed_lengths, d_lattice};
-    return sample_loop("arreau_sample_loop_conditioned", m, st, t_start, n_steps, seed, d_workspace, workspace_bytes, use_graph, stream,
-                       condition);
+    return run_sample_loop("arreau_sample_loop_conditioned", m, st,
+                           {.t_start = t_start, .n_steps = n_steps, .seed = seed, .workspace = d_workspace, .workspace_bytes = workspace_bytes,
+                            .use_graph = use_graph, .stream = stream, .condition = condition});
 }
 
 extern "C" int arreau_sample_loop_scheduled(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
@@ -638,8 +643,9 @@ extern "C" int arreau_sample_loop_scheduled(arreau_model* m, float* d_frac, int3
                                             void* d_workspace, size_t workspace_bytes, int32_t use_graph,
                                             const arreau_sample_condition* condition, const arreau_sample_schedule* schedule, void* stream) {
     const SampleState st{d_frac, d_types, d_lengths, d_angles, d_off, B, N, d_const_types, d_fixed_lengths, d_lattice};
-    return sample_loop("arreau_sample_loop_scheduled", m, st, t_start, n_steps, seed, d_workspace, workspace_bytes, use_graph, stream,
-                       condition, schedule);
+    return run_sample_loop("arreau_sample_loop_scheduled", m, st,
+                           {.t_start = t_start, .n_steps = n_steps, .seed = seed, .workspace = d_workspace, .workspace_bytes = workspace_bytes,
+                            .use_graph = use_graph, .stream = stream, .condition = condition, .schedule = schedule});
 }
 
 extern "C" int arreau_sample_loop_corrected(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
@@ -649,8 +655,9 @@ extern "C" int arreau_sample_loop_corrected(arreau_model* m, float* d_frac, int3
                                             const arreau_sample_condition* condition, const arreau_sample_schedule* schedule,
                                             const arreau_corrector* corrector, void* stream) {
     const SampleState st{d_frac, d_types, d_lengths, d_angles, d_off, B, N, d_const_types, d_fixed_lengths, d_lattice};
-    return sample_loop("arreau_sample_loop_corrected", m, st, t_start, n_steps, seed, d_workspace, workspace_bytes, use_graph, stream,
-                       condition, schedule, corrector);
+    return run_sample_loop("arreau_sample_loop_corrected", m, st,
+                           {.t_start = t_start, .n_steps = n_steps, .seed = seed, .workspace = d_workspace, .workspace_bytes = workspace_bytes,
+                            .use_graph = use_graph, .stream = stream, .condition = condition, .schedule = schedule, .corrector = corrector});
 }
 
 extern "C" int arreau_sample_loop_resampled(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
@@ -660,8 +667,10 @@ extern "C" int arreau_sample_loop_resampled(arreau_model* m, float* d_frac, int3
                                             const arreau_sample_condition* condition, const arreau_sample_schedule* schedule,
                                             const arreau_corrector* corrector, const arreau_resampling* resampling, void* stream) {
     const SampleState st{d_frac, d_types, d_lengths, d_angles, d_off, B, N, d_const_types, d_fixed_lengths, d_lattice};
-    return sample_loop("arreau_sample_loop_resampled", m, st, t_start, n_steps, seed, d_workspace, workspace_bytes, use_graph, stream,
-                       condition, schedule, corrector, resampling);
+    return run_sample_loop("arreau_sample_loop_resampled", m, st,
+                           {.t_start = t_start, .n_steps = n_steps, .seed = seed, .workspace = d_workspace, .workspace_bytes = workspace_bytes,
+                            .use_graph = use_graph, .stream = stream, .condition = condition, .schedule = schedule, .corrector = corrector,
+                            .resampling = resampling});
 }
 
 extern "C" int arreau_sample_loop_tied(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
@@ -671,8 +680,10 @@ extern "C" int arreau_sample_loop_tied(arreau_model* m, float* d_frac, int32_t* 
                                        const arreau_sample_schedule* schedule, const arreau_corrector* corrector,
                                        const arreau_resampling* resampling, const int32_t* d_length_tie, void* stream) {
     const SampleState st{d_frac, d_types, d_lengths, d_angles, d_off, B, N, d_const_types, d_fixed_lengths, d_lattice};
-    return sample_loop("arreau_sample_loop_tied", m, st, t_start, n_steps, seed, d_workspace, workspace_bytes, use_graph, stream,
-                       condition, schedule, corrector, resampling, d_length_tie);
+    return run_sample_loop("arreau_sample_loop_tied", m, st,
+                           {.t_start = t_start, .n_steps = n_steps, .seed = seed, .workspace = d_workspace, .workspace_bytes = workspace_bytes,
+                            .use_graph = use_graph, .stream = stream, .condition = condition, .schedule = schedule, .corrector = corrector,
+                            .resampling = resampling, .d_length_tie = d_length_tie});
 }
 
 extern "C" int arreau_sample_loop_eta(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
@@ -681,15 +692,15 @@ extern "C" int arreau_sample_loop_eta(arreau_model* m, float* d_frac, int32_t* d
                                       size_t workspace_bytes, int32_t use_graph, const arreau_sample_condition* condition,
                                       const arreau_sample_schedule* schedule, const arreau_corrector* corrector,
                                       const arreau_resampling* resampling, const int32_t* d_length_tie, float eta, void* stream) {
-    int rc;
-    if ((rc = arreau_eta_check(eta, "arreau_sample_loop_eta"))) return rc;
     const SampleState st{d_frac, d_types, d_lengths, d_angles, d_off, B, N, d_const_types, d_fixed_lengths, d_lattice};
-    return sample_loop("arreau_sample_loop_eta", m, st, t_start, n_steps, seed, d_workspace, workspace_bytes, use_graph, stream,
-                       condition, schedule, corrector, resampling, d_length_tie, /*sym=*/nullptr, eta + 0.0f /* -0 -> +0 */);
+    return run_sample_loop("arreau_sample_loop_eta", m, st,
+                           {.t_start = t_start, .n_steps = n_steps, .seed = seed, .workspace = d_workspace, .workspace_bytes = workspace_bytes,
+                            .use_graph = use_graph, .stream = stream, .condition = condition, .schedule = schedule, .corrector = corrector,
+                            .resampling = resampling, .d_length_tie = d_length_tie, .eta = &eta});
 }
 
-// Second-order multistep sampling (rules in include/arreau_hip.h): the eta = 0 loop whose steps extrapolate with the previous step's
-// prediction, kept in the caller's history buffers.  What the rules do not combine it with is rejected before any work.
+// Second-order multistep sampling: the eta = 0 loop whose steps extrapolate with the previous step's prediction, kept in the
+// caller's history buffers (required).
 extern "C" int arreau_sample_loop_multistep(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
                                             const int32_t* d_off, int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed,
                                             const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice,
@@ -697,57 +708,30 @@ extern "C" int arreau_sample_loop_multistep(arreau_model* m, float* d_frac, int3
                                             const arreau_sample_condition* condition, const arreau_sample_schedule* schedule,
                                             const arreau_corrector* corrector, const arreau_resampling* resampling,
                                             const int32_t* d_length_tie, const arreau_multistep* multistep, void* stream) {
-    const char* who = "arreau_sample_loop_multistep";
     int rc;
-    if ((rc = arreau_multistep_check(multistep, who))) return rc;
-    SampleConditionDev c;
-    if ((rc = arreau_condition_to_dev(condition, &c))) return rc;
-    ARREAU_REQUIRE(arreau_condition_empty(&c), std::string(who) + ": not combined with a condition");
-    ARREAU_REQUIRE(!corrector || corrector->steps == 0, std::string(who) + ": not combined with corrector steps");
-    ARREAU_REQUIRE(!resampling || resampling->passes == 1, std::string(who) + ": not combined with resampling (passes > 1)");
+    if ((rc = arreau_multistep_check(multistep, "arreau_sample_loop_multistep"))) return rc;  // (required here: NULL is an error)
     const SampleState st{d_frac, d_types, d_lengths, d_angles, d_off, B, N, d_const_types, d_fixed_lengths, d_lattice};
-    return sample_loop(who, m, st, t_start, n_steps, seed, d_workspace, workspace_bytes, use_graph, stream, nullptr, schedule, nullptr,
-                       nullptr, d_length_tie, /*sym=*/nullptr, /*eta=*/0.0f, multistep);
+    return run_sample_loop("arreau_sample_loop_multistep", m, st,
+                           {.t_start = t_start, .n_steps = n_steps, .seed = seed, .workspace = d_workspace, .workspace_bytes = workspace_bytes,
+                            .use_graph = use_graph, .stream = stream, .condition = condition, .schedule = schedule, .corrector = corrector,
+                            .resampling = resampling, .d_length_tie = d_length_tie, .multistep = multistep});
 }
 
-// Species control (rules in include/arreau_hip.h): whichever of the loops above the options name, its steps the SPEC instances.
-// The checks of arreau_sample_loop_sym / _eta / _multistep run first, under this export's name; what the loops do not combine is
-// rejected by them as before.
-static int sample_loop_species(const char* who, arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
-                               const int32_t* d_off, int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed,
-                               const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice, void* d_workspace,
-                               size_t workspace_bytes, int32_t use_graph, const arreau_sample_condition* condition,
-                               const arreau_sample_schedule* schedule, const arreau_corrector* corrector,
-                               const arreau_resampling* resampling, const int32_t* d_length_tie, const arreau_symmetry* symmetry,
-                               const float* eta, const arreau_multistep* multistep, const arreau_species_control* species,
-                               const uint64_t* d_crystal_seeds, void* stream, const arreau_contact_guidance* guide = nullptr) {
-    int rc;
-    if (guide && (rc = arreau_contact_guidance_check(guide, who))) return rc;
-    arreau_species_control sp;
-    if ((rc = arreau_species_check(species, who, &sp))) return rc;
-    if (eta && (rc = arreau_eta_check(*eta, who))) return rc;
-    ARREAU_REQUIRE(!symmetry || !eta, std::string(who) + ": space-group symmetry is not combined with an eta");
-    if (symmetry) {
-        if ((rc = arreau_symmetry_check(symmetry, who))) return rc;
-        ARREAU_REQUIRE(!resampling || resampling->passes <= 1, std::string(who) + ": space-group symmetry is not combined with resampling (passes > 1)");
-    }
-    if (multistep) {
-        if ((rc = arreau_multistep_check(multistep, who))) return rc;
-        SampleConditionDev c;
-        if ((rc = arreau_condition_to_dev(condition, &c))) return rc;
-        ARREAU_REQUIRE(arreau_condition_empty(&c), std::string(who) + ": multistep is not combined with a condition");
-        ARREAU_REQUIRE(!corrector || corrector->steps == 0, std::string(who) + ": multistep is not combined with corrector steps");
-        ARREAU_REQUIRE(!resampling || resampling->passes == 1, std::string(who) + ": multistep is not combined with resampling (passes > 1)");
-        ARREAU_REQUIRE(!symmetry, std::string(who) + ": multistep is not combined with space-group symmetry");
-        ARREAU_REQUIRE(!eta || *eta == 0.0f, std::string(who) + ": a multistep loop is the eta = 0 loop");
-        condition = nullptr; corrector = nullptr; resampling = nullptr;
-    }
-    const float e = multistep ? 0.0f : (eta ? *eta + 0.0f /* -0 -> +0 */ : -1.0f);
+extern "C" int arreau_sample_loop_sym(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                                      const int32_t* d_off, int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed,
+                                      const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice, void* d_workspace,
+                                      size_t workspace_bytes, int32_t use_graph, const arreau_sample_condition* condition,
+                                      const arreau_sample_schedule* schedule, const arreau_corrector* corrector,
+                                      const arreau_resampling* resampling, const int32_t* d_length_tie, const arreau_symmetry* symmetry,
+                                      void* stream) {
     const SampleState st{d_frac, d_types, d_lengths, d_angles, d_off, B, N, d_const_types, d_fixed_lengths, d_lattice};
-    return sample_loop(who, m, st, t_start, n_steps, seed, d_workspace, workspace_bytes, use_graph, stream, condition, schedule, corrector,
-                       resampling, d_length_tie, symmetry, e, multistep, &sp, d_crystal_seeds, guide);
+    return run_sample_loop("arreau_sample_loop_sym", m, st,
+                           {.t_start = t_start, .n_steps = n_steps, .seed = seed, .workspace = d_workspace, .workspace_bytes = workspace_bytes,
+                            .use_graph = use_graph, .stream = stream, .condition = condition, .schedule = schedule, .corrector = corrector,
+                            .resampling = resampling, .d_length_tie = d_length_tie, .symmetry = symmetry});
 }
 
+// Species control: whichever of the loops above the options name, its steps the SPEC instances; `species` is required.
 extern "C" int arreau_sample_loop_species(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
                                           const int32_t* d_off, int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed,
                                           const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice,
@@ -756,14 +740,16 @@ extern "C" int arreau_sample_loop_species(arreau_model* m, float* d_frac, int32_
                                           const arreau_corrector* corrector, const arreau_resampling* resampling,
                                           const int32_t* d_length_tie, const arreau_symmetry* symmetry, const float* eta,
                                           const arreau_multistep* multistep, const arreau_species_control* species, void* stream) {
-    return sample_loop_species("arreau_sample_loop_species", m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, t_start, n_steps, seed,
-                               d_const_types, d_fixed_lengths, d_lattice, d_workspace, workspace_bytes, use_graph, condition, schedule,
-                               corrector, resampling, d_length_tie, symmetry, eta, multistep, species, nullptr, stream);
+    const SampleState st{d_frac, d_types, d_lengths, d_angles, d_off, B, N, d_const_types, d_fixed_lengths, d_lattice};
+    return run_sample_loop("arreau_sample_loop_species", m, st,
+                           {.t_start = t_start, .n_steps = n_steps, .seed = seed, .workspace = d_workspace, .workspace_bytes = workspace_bytes,
+                            .use_graph = use_graph, .stream = stream, .condition = condition, .schedule = schedule, .corrector = corrector,
+                            .resampling = resampling, .d_length_tie = d_length_tie, .symmetry = symmetry, .eta = eta, .multistep = multistep,
+                            .species = species, .species_required = true});
 }
 
-// Keyed sampling (rules in include/arreau_hip.h): arreau_sample_loop_species with the table of stream seeds, which every draw of
-// the loop -- steps, corrector moves, jumps -- is keyed by; a NULL table is arreau_sample_loop_species bit for bit.  The same
-// checks under this export's name; what that loop rejects stays rejected.
+// Keyed sampling: arreau_sample_loop_species with the table of stream seeds, which every draw of the loop -- steps, corrector
+// moves, jumps -- is keyed by; a NULL table is arreau_sample_loop_species bit for bit.
 extern "C" int arreau_sample_loop_keyed(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
                                         const int32_t* d_off, int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed,
                                         const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice, void* d_workspace,
@@ -772,13 +758,16 @@ extern "C" int arreau_sample_loop_keyed(arreau_model* m, float* d_frac, int32_t*
                                         const arreau_resampling* resampling, const int32_t* d_length_tie, const arreau_symmetry* symmetry,
                                         const float* eta, const arreau_multistep* multistep, const arreau_species_control* species,
                                         const uint64_t* d_crystal_seeds, void* stream) {
-    return sample_loop_species("arreau_sample_loop_keyed", m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, t_start, n_steps, seed,
-                               d_const_types, d_fixed_lengths, d_lattice, d_workspace, workspace_bytes, use_graph, condition, schedule,
-                               corrector, resampling, d_length_tie, symmetry, eta, multistep, species, d_crystal_seeds, stream);
+    const SampleState st{d_frac, d_types, d_lengths, d_angles, d_off, B, N, d_const_types, d_fixed_lengths, d_lattice};
+    return run_sample_loop("arreau_sample_loop_keyed", m, st,
+                           {.t_start = t_start, .n_steps = n_steps, .seed = seed, .workspace = d_workspace, .workspace_bytes = workspace_bytes,
+                            .use_graph = use_graph, .stream = stream, .condition = condition, .schedule = schedule, .corrector = corrector,
+                            .resampling = resampling, .d_length_tie = d_length_tie, .symmetry = symmetry, .eta = eta, .multistep = multistep,
+                            .species = species, .species_required = true, .d_crystal_seeds = d_crystal_seeds});
 }
 
-// Contact guidance (rules in include/arreau_hip.h): arreau_sample_loop_keyed whose every network evaluation is followed by the
-// guidance launch on its eps; a NULL struct or weight == 0 is arreau_sample_loop_keyed bit for bit.  The parameters are checked first.
+// Contact guidance: arreau_sample_loop_keyed whose every network evaluation is followed by the guidance launch on its eps; a NULL
+// struct or weight == 0 is arreau_sample_loop_keyed bit for bit.
 extern "C" int arreau_sample_loop_guided(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
                                          const int32_t* d_off, int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed,
                                          const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice, void* d_workspace,
@@ -787,14 +776,17 @@ extern "C" int arreau_sample_loop_guided(arreau_model* m, float* d_frac, int32_t
                                          const arreau_resampling* resampling, const int32_t* d_length_tie, const arreau_symmetry* symmetry,
                                          const float* eta, const arreau_multistep* multistep, const arreau_species_control* species,
                                          const uint64_t* d_crystal_seeds, const arreau_contact_guidance* guidance, void* stream) {
-    return sample_loop_species("arreau_sample_loop_guided", m, d_frac, d_types, d_lengths, d_angles, d_off, B, N, t_start, n_steps, seed,
-                               d_const_types, d_fixed_lengths, d_lattice, d_workspace, workspace_bytes, use_graph, condition, schedule,
-                               corrector, resampling, d_length_tie, symmetry, eta, multistep, species, d_crystal_seeds, stream, guidance);
+    const SampleState st{d_frac, d_types, d_lengths, d_angles, d_off, B, N, d_const_types, d_fixed_lengths, d_lattice};
+    return run_sample_loop("arreau_sample_loop_guided", m, st,
+                           {.t_start = t_start, .n_steps = n_steps, .seed = seed, .workspace = d_workspace, .workspace_bytes = workspace_bytes,
+                            .use_graph = use_graph, .stream = stream, .condition = condition, .schedule = schedule, .corrector = corrector,
+                            .resampling = resampling, .d_length_tie = d_length_tie, .symmetry = symmetry, .eta = eta, .multistep = multistep,
+                            .species = species, .species_required = true, .d_crystal_seeds = d_crystal_seeds, .guidance = guidance});
 }
 
-// DDIM inversion (rules in include/arreau_hip.h): the sampling loop climbing the levels of an ascending table, every step the
-// network evaluation at the crystals' level and the INVERT update to the next one.  The same loop code in both forms, with graph
-// replay and on the shape-general path; no seed, no corrector, no jump.
+// DDIM inversion: the sampling loop climbing the levels of an ascending table, every step the network evaluation at the crystals'
+// level and the INVERT update to the next one.  The same loop code in both forms, with graph replay and on the shape-general
+// path; no seed, no corrector, no jump.
 extern "C" int arreau_invert_loop(arreau_model* m, float* d_frac, const int32_t* d_types, float* d_lengths, const float* d_angles,
                                   const int32_t* d_off, int32_t B, int32_t N, int32_t t_first, int32_t n_steps, const int32_t* d_up,
                                   const float* d_fixed_lengths, float* d_lattice, void* d_workspace, size_t workspace_bytes,
@@ -805,26 +797,9 @@ extern "C" int arreau_invert_loop(arreau_model* m, float* d_frac, const int32_t*
     // (the species are read by the network and never written: the pointer only completes the state)
     const SampleState st{d_frac, const_cast<int32_t*>(d_types), d_lengths, d_angles, d_off, B, N, nullptr, d_fixed_lengths, d_lattice};
     const arreau_sample_schedule up{d_up, 1.0f /* not read by an inversion step */};
-    return sample_loop_impl(m, st, t_first, n_steps, /*seed=*/0, d_workspace, workspace_bytes, use_graph, nullptr, &up, nullptr, nullptr,
-                            nullptr, nullptr, -1.0f, stream, /*invert=*/true);
-}
-
-extern "C" int arreau_sample_loop_sym(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
-                                      const int32_t* d_off, int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed,
-                                      const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice, void* d_workspace,
-                                      size_t workspace_bytes, int32_t use_graph, const arreau_sample_condition* condition,
-                                      const arreau_sample_schedule* schedule, const arreau_corrector* corrector,
-                                      const arreau_resampling* resampling, const int32_t* d_length_tie, const arreau_symmetry* symmetry,
-                                      void* stream) {
-    if (symmetry) {
-        int rc;
-        if ((rc = arreau_symmetry_check(symmetry, "arreau_sample_loop_sym"))) return rc;
-        ARREAU_REQUIRE(!resampling || resampling->passes <= 1,
-                       "arreau_sample_loop_sym: space-group symmetry is not combined with resampling (passes > 1)");
-    }
-    const SampleState st{d_frac, d_types, d_lengths, d_angles, d_off, B, N, d_const_types, d_fixed_lengths, d_lattice};
-    return sample_loop("arreau_sample_loop_sym", m, st, t_start, n_steps, seed, d_workspace, workspace_bytes, use_graph, stream, condition,
-                       schedule, corrector, resampling, d_length_tie, symmetry);
+    return run_sample_loop("arreau_invert_loop", m, st,
+                           {.t_start = t_first, .n_steps = n_steps, .workspace = d_workspace, .workspace_bytes = workspace_bytes,
+                            .use_graph = use_graph, .stream = stream, .schedule = &up, .invert = true});
 }
 
 // ---------------------------------------------------------------------------------------------

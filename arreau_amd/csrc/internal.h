@@ -48,6 +48,7 @@ struct SampleConditionDev {
     const uint8_t* type_mask; // [N]
     const float* l0;          // [B,3] known cell lengths
     const uint8_t* len_mask;  // [B]
+    bool operator==(const SampleConditionDev&) const = default;
 };
 
 // The sampler state a loop call or a single update works on: device pointers and sizes, the caller's.  Host side only: launchers
@@ -65,62 +66,98 @@ struct SampleState {
     bool operator==(const SampleState&) const = default;
 };
 
-// Member-wise equality of the two plain structs SampleGraphKey holds that are not ours to extend (a kernel argument, a struct of
-// the public header).  The structured bindings stop compiling when a member is added, so none can be left out of the comparison.
-inline bool operator==(const SampleConditionDev& a, const SampleConditionDev& b) {
-    auto members = [](const SampleConditionDev& c) {
-        const auto& [x0, pos_mask, a0, type_mask, l0, len_mask] = c;
-        return std::tie(x0, pos_mask, a0, type_mask, l0, len_mask);
-    };
-    return members(a) == members(b);
-}
-inline bool operator==(const arreau_symmetry& a, const arreau_symmetry& b) {
-    auto members = [](const arreau_symmetry& y) {
-        const auto& [leader, op, orbit, orbit_ptr, orbit_atoms, stab_ptr, stab_ops, rot, rot_inv, trans, n_orbits, n_orbit_atoms,
-                     n_stab_ops, n_ops] = y;
-        return std::tie(leader, op, orbit, orbit_ptr, orbit_atoms, stab_ptr, stab_ops, rot, rot_inv, trans, n_orbits, n_orbit_atoms,
-                        n_stab_ops, n_ops);
-    };
-    return members(a) == members(b);
-}
+// Member-wise equality of the public header's structs that SampleOptions holds (not ours to extend).  The structured binding stops
+// compiling when a member is added, so none can be left out of the comparison.
+#define ARREAU_MEMBERWISE_EQ(T, ...)                     \
+    inline bool operator==(const T& a, const T& b) {     \
+        auto members = [](const T& v) {                  \
+            const auto& [__VA_ARGS__] = v;               \
+            return std::tie(__VA_ARGS__);                \
+        };                                               \
+        return members(a) == members(b);                 \
+    }
+ARREAU_MEMBERWISE_EQ(arreau_symmetry, leader, op, orbit, orbit_ptr, orbit_atoms, stab_ptr, stab_ops, rot, rot_inv, trans, n_orbits, n_orbit_atoms,
+                     n_stab_ops, n_ops)
+ARREAU_MEMBERWISE_EQ(arreau_multistep, hist_eps, hist_x0, hist_t_atom, hist_t_len)
+ARREAU_MEMBERWISE_EQ(arreau_species_control, d_allow, temperature)
+ARREAU_MEMBERWISE_EQ(arreau_contact_guidance, min_distance, weight, max_shells, d_energy, d_contacts, d_flags)
+#undef ARREAU_MEMBERWISE_EQ
 
-inline bool operator==(const arreau_multistep& a, const arreau_multistep& b) {
-    auto members = [](const arreau_multistep& h) {
-        const auto& [hist_eps, hist_x0, hist_t_atom, hist_t_len] = h;
-        return std::tie(hist_eps, hist_x0, hist_t_atom, hist_t_len);
-    };
-    return members(a) == members(b);
-}
+// Respaced sampling (arreau_sample_loop_scheduled, arreau_reverse_step_to; the rules are stated in include/arreau_hip.h): the step
+// that leaves timestep t of crystal b produces the state at s = s_of[b] when s_of is given, else s = next[t] (the device-side
+// next-timestep table [T+1] of the loop).  Kernels take it by value and hand their helpers a pointer to it, or null when the
+// launch has no schedule (then s = t - 1 and the helpers compile to the schedule-less code).
+struct StepScheduleDev {
+    const int32_t* next;  // [T+1] or null
+    const int32_t* s_of;  // [B]   or null
+    float clipmax;        // the VP schedule's beta clip (VP_lattice clipmax)
+    bool operator==(const StepScheduleDev&) const = default;
+};
 
-// What the cached executable graph of arreau_sample_loop was captured for (api.hip: sample_graph_key): every input that decides
-// the kernels of a captured step or their arguments.  Compared member by member; the two floats by their bits.  No member
-// initialisers: arreau_model_create zero-fills the model, and SampleGraphKey{} is the key no call has.
+// Predictor-corrector sampling (arreau_sample_loop_corrected, arreau_corrector_step; the rule is stated in include/arreau_hip.h):
+// M corrector moves at the step's timestep come before the predictor, each after a full network evaluation on the current state.
+struct CorrectorDev {
+    int steps;  // M (0: the plain step)
+    float snr;
+    bool operator==(const CorrectorDev&) const = default;
+};
+
+// What modifies a step of the sampler, on the host side, as the launchers read it: pointers, null / zero for the plain step.  A loop
+// call's is a view of its SampleOptions (below); a step export fills its own.  The launchers pick the kernel instance from it.
+struct StepOptions {
+    const SampleConditionDev* cond = nullptr;  // conditioned sampling (the COND instances); needs Philox noise
+    const StepScheduleDev* sched = nullptr;    // respaced step: s from a table or per crystal; null: s = t - 1
+    CorrectorDev corr{};                       // corrector moves before the predictor
+    const int32_t* pass = nullptr;        // resampled loop: the device word of the pass index, word3 = 256 pass[0] (RESAMPLE)
+    const int32_t* length_tie = nullptr;  // lattice systems: the tie code per crystal (TIE)
+    const arreau_symmetry* sym = nullptr; // space-group symmetry: the orbit tables (SYM); not with a condition or a resampled loop
+    float eta = -1.0f;                    // DDIM-style step (ETA): the noise scale in [0, 1]; negative: the ancestral step.  Not with sym
+    const arreau_multistep* ms = nullptr; // second-order multistep (MS): the history buffers; eta is then 0; a schedule and a tie only
+    bool invert = false;                  // DDIM inversion (INVERT): `sched` names the HIGHER level every crystal climbs to; no other option
+    const arreau_species_control* species = nullptr;  // species control (SPEC): the admission rows and the temperature; not with invert
+    const uint64_t* crystal_seeds = nullptr;  // keyed sampling: the stream seed of every crystal (StepNoiseSrc::seeds of every draw)
+    const arreau_contact_guidance* guide = nullptr;  // contact guidance: one launch on the eps of every evaluation; null (also for weight 0): none; not with invert
+};
+
+// The options of one loop call, checked, normalised and held by value (api.hip: resolve_loop_request is the one place that fills
+// it): what every step of the call reads, and -- being all of it -- the options' part of the key of a captured step.  An absent
+// option is its value-initialised member whatever the caller's struct held (a NULL corrector and steps == 0, a NULL guidance and
+// weight == 0 are the same options); eta is -1 without one.  The floats compare with ==, which for these values is equality of
+// their bits: every accepted one is finite and never -0 (the checks reject the rest, x + 0.0f turns -0 into +0).  No member
+// initialisers: it lives in the zero-filled model.
+struct SampleOptions {
+    SampleConditionDev cond;       // conditioned sampling: the six pointers (all null: none)
+    StepScheduleDev sched;         // respaced sampling: the table and the clip (next null: every timestep)
+    CorrectorDev corr;             // corrector moves (steps 0, snr 0: none)
+    int32_t resample_passes, resample_jump;  // RePaint resampling: R and J (0, 0: none)
+    const int32_t* pass;           // ... and the workspace word of the pass index its steps read
+    const int32_t* length_tie;     // lattice systems: the tie codes (null: untied)
+    arreau_symmetry sym;           // space-group symmetry: the tables (leader null: none)
+    float eta;                     // DDIM-style steps: their eta (negative: ancestral steps)
+    arreau_multistep ms;           // second-order multistep: the history buffers (hist_eps null: none)
+    bool invert;                   // DDIM inversion (arreau_invert_loop): other kernels on the same buffers and table
+    bool species_on;               // species control: whether the steps are the SPEC instances ...
+    arreau_species_control species;  // ... and their admission rows and temperature
+    const uint64_t* crystal_seeds; // keyed sampling: the table of stream seeds (null: not keyed)
+    arreau_contact_guidance guide; // contact guidance: parameters and diagnostic arrays (weight 0: none)
+    bool operator==(const SampleOptions&) const = default;
+    StepOptions view() const {     // valid while *this is
+        return StepOptions{.cond = cond.pos_mask || cond.type_mask || cond.len_mask ? &cond : nullptr, .sched = sched.next ? &sched : nullptr,
+                           .corr = corr, .pass = pass, .length_tie = length_tie, .sym = sym.leader ? &sym : nullptr, .eta = eta,
+                           .ms = ms.hist_eps ? &ms : nullptr, .invert = invert, .species = species_on ? &species : nullptr,
+                           .crystal_seeds = crystal_seeds, .guide = guide.weight > 0.0f ? &guide : nullptr};
+    }
+};
+
+// What the cached executable graph of arreau_sample_loop was captured for: the buffers, the seed, every kernel choice of the
+// evaluation and all the options, which are kernel arguments or launch choices of the capture.  A new option is a member of
+// SampleOptions and so part of the key.  SampleGraphKey{} (the zero-filled model's) is the key no call has.
 struct SampleGraphKey {
-    SampleState state;        // buffers and sizes
+    SampleState state;      // buffers and sizes
     const void* workspace;
-    uint64_t seed;            // the Philox seed
-    SampleConditionDev cond;  // conditioned sampling: the six pointers of the condition (all null: none)
-    const int32_t* sched_next;  // respaced sampling: the next-timestep table
-    const int32_t* length_tie;  // lattice systems: the per-crystal tie codes (null: untied)
-    arreau_symmetry sym;      // space-group symmetry: the ten table pointers and their sizes (all zero: no symmetry)
-    ScorePlan plan;           // every kernel choice of the captured evaluation
-    int32_t scheduled;
-    uint32_t clip_bits;        // the schedule's lattice_clipmax
-    int32_t corrector_steps;
-    uint32_t snr_bits;         // the corrector's snr
-    int32_t resample_passes, resample_jump;  // 0, 0: no resampling
-    int32_t eta_step;          // DDIM-style sampling: 1 when the steps are eta steps
-    uint32_t eta_bits;         // their eta
-    int32_t invert;            // DDIM inversion: 1 when the steps are inversion steps (arreau_invert_loop)
-    arreau_multistep ms;       // second-order multistep: the four history pointers (all null: none)
-    int32_t species;           // species control: 1 when the steps take it
-    const uint32_t* species_allow;  // its admission rows (null: every class)
-    uint32_t species_tau_bits;      // its temperature
-    const uint64_t* crystal_seeds;  // keyed sampling: the table of stream seeds (null: not keyed)
-    int32_t guide;                  // contact guidance: 1 when every evaluation is followed by its launch
-    uint32_t guide_d0_bits, guide_weight_bits;  // its min_distance and weight
-    int32_t guide_max_shells;
-    const void *guide_energy, *guide_contacts, *guide_flags;  // its diagnostic arrays (each may be null)
+    uint64_t seed;          // the Philox seed
+    ScorePlan plan;
+    SampleOptions opt;
     bool operator==(const SampleGraphKey&) const = default;
 };
 
@@ -308,41 +345,8 @@ int arreau_condition_to_dev(const arreau_sample_condition* c, SampleConditionDev
 // every size is positive.  The kernels take the table struct by value and check every index before they follow it.
 int arreau_symmetry_check(const arreau_symmetry* y, const char* who);  // update.hip
 
-// Respaced sampling (arreau_sample_loop_scheduled, arreau_reverse_step_to; the rules are stated in include/arreau_hip.h): the step
-// that leaves timestep t of crystal b produces the state at s = s_of[b] when s_of is given, else s = next[t] (the device-side
-// next-timestep table [T+1] of the loop).  Kernels take it by value and hand their helpers a pointer to it, or null when the
-// launch has no schedule (then s = t - 1 and the helpers compile to the schedule-less code).
-struct StepScheduleDev {
-    const int32_t* next;  // [T+1] or null
-    const int32_t* s_of;  // [B]   or null
-    float clipmax;        // the VP schedule's beta clip (VP_lattice clipmax)
-};
-
-// Predictor-corrector sampling (arreau_sample_loop_corrected, arreau_corrector_step; the rule is stated in include/arreau_hip.h).
-// arreau_corrector_check: ARREAU_EINVAL unless 0 <= steps <= ARREAU_MAX_CORRECTOR_STEPS and (steps == 0 or snr finite and > 0).
+// Predictor-corrector sampling: ARREAU_EINVAL unless 0 <= steps <= ARREAU_MAX_CORRECTOR_STEPS and (steps == 0 or snr finite and > 0).
 int arreau_corrector_check(int32_t steps, float snr, const char* who);
-// M corrector moves at the step's timestep come before the predictor, each after a full network evaluation on the current state.
-struct CorrectorDev {
-    int steps;  // M (0: the plain step)
-    float snr;
-};
-
-// What modifies a step of the sampler, on the host side; all null / zero is the plain step.  Built once per library call and handed
-// down by const reference; the launchers pick the kernel instance from it.
-struct StepOptions {
-    const SampleConditionDev* cond = nullptr;  // conditioned sampling (the COND instances); needs Philox noise
-    const StepScheduleDev* sched = nullptr;    // respaced step: s from a table or per crystal; null: s = t - 1
-    CorrectorDev corr{};                       // corrector moves before the predictor
-    const int32_t* pass = nullptr;        // resampled loop: the device word of the pass index, word3 = 256 pass[0] (RESAMPLE)
-    const int32_t* length_tie = nullptr;  // lattice systems: the tie code per crystal (TIE)
-    const arreau_symmetry* sym = nullptr; // space-group symmetry: the orbit tables (SYM); not with a condition or a resampled loop
-    float eta = -1.0f;                    // DDIM-style step (ETA): the noise scale in [0, 1]; negative: the ancestral step.  Not with sym
-    const arreau_multistep* ms = nullptr; // second-order multistep (MS): the history buffers; eta is then 0; a schedule and a tie only
-    bool invert = false;                  // DDIM inversion (INVERT): `sched` names the HIGHER level every crystal climbs to; no other option
-    const arreau_species_control* species = nullptr;  // species control (SPEC): the admission rows and the temperature; not with invert
-    const uint64_t* crystal_seeds = nullptr;  // keyed sampling: the stream seed of every crystal (StepNoiseSrc::seeds of every draw)
-    const arreau_contact_guidance* guide = nullptr;  // contact guidance: one launch on the eps of every evaluation; null (also for weight 0): none; not with invert
-};
 // DDIM-style sampling (arreau_sample_loop_eta, arreau_reverse_step_eta; the rules are stated in include/arreau_hip.h):
 // ARREAU_EINVAL unless eta is finite and lies in [0, 1].
 int arreau_eta_check(float eta, const char* who);  // update.hip

@@ -267,28 +267,35 @@ extern "C" int arreau_reverse_step(const arreau_model* m, float* d_frac, int32_t
     return arreau_launch_reverse(m, st, in, StepOptions{}, (hipStream_t)stream);
 }
 
-// arreau_reverse_step from timestep t to a per-crystal target s (respaced sampling; rules in include/arreau_hip.h).
-static int reverse_step_to(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
-                           const int32_t* d_t, const int32_t* d_s, const int32_t* d_off, int32_t B, int32_t N, const float* d_eps,
-                           const float* d_logits, const float* d_len0, const float* d_z_lattice, const float* d_z_frac,
-                           const float* d_u_types, float* d_lattice, float lattice_clipmax, const int32_t* d_length_tie,
-                           const arreau_symmetry* sym, void* stream, const char* who, float eta = -1.0f /* negative: none */,
-                           const arreau_multistep* ms = nullptr /* the multistep history (then eta = 0) */,
-                           const arreau_species_control* species = nullptr /* species control (checked by the caller) */) {
+// What the arreau_reverse_step_to family of exports share, as the caller gave it: arreau_reverse_step's arguments, the per-crystal
+// targets s and the clip.  Each export fills it, names its options in a StepOptions and calls reverse_step_to.
+struct StepToArgs {
+    const arreau_model* m;
+    float *frac, *lengths, *lattice;
+    int32_t* types;
+    const float *angles, *eps, *logits, *len0, *z_lattice, *z_frac, *u_types;
+    const int32_t *t, *s, *offsets;
+    int32_t B, N;
+    float clipmax;
+    void* stream;
+};
+
+// arreau_reverse_step from timestep t to a per-crystal target s (respaced sampling; rules in include/arreau_hip.h), with the
+// options of `opt` (its schedule is set here).
+static int reverse_step_to(const char* who, const StepToArgs& a, StepOptions opt) {
     // (at eta = 0 the draws of the lengths and positions are not read: their arrays may be null; so may the species' uniforms at a
     // species temperature of 0)
-    ARREAU_REQUIRE(m && d_frac && d_types && d_lengths && d_angles && d_t && d_s && d_off && d_eps && d_logits && d_len0 &&
-                       ((d_z_lattice && d_z_frac) || eta == 0.0f) && (d_u_types || (species && species->temperature == 0.0f)) && d_lattice,
-                   std::string(who) + ": null pointer");
-    ARREAU_REQUIRE(B >= 1 && N >= 0, std::string(who) + ": bad size");
-    ARREAU_REQUIRE(lattice_clipmax > 0.0f && lattice_clipmax <= 1.0f, std::string(who) + ": lattice_clipmax must lie in (0, 1]");
-    const SampleState st{.frac = d_frac, .types = d_types, .lengths = d_lengths, .angles = d_angles, .offsets = d_off, .B = B, .N = N,
-                         .lattice = d_lattice};
-    const ReverseInputs in{d_t, d_eps, d_logits, d_len0, StepNoiseSrc{d_z_lattice, d_z_frac, d_u_types, 0}};
-    const StepScheduleDev sched{nullptr, d_s, lattice_clipmax};
-    return arreau_launch_reverse(m, st, in,
-                                 StepOptions{.sched = &sched, .length_tie = d_length_tie, .sym = sym, .eta = eta, .ms = ms, .species = species},
-                                 (hipStream_t)stream);
+    ARREAU_REQUIRE(a.m && a.frac && a.types && a.lengths && a.angles && a.t && a.s && a.offsets && a.eps && a.logits && a.len0 &&
+                       ((a.z_lattice && a.z_frac) || opt.eta == 0.0f) && (a.u_types || (opt.species && opt.species->temperature == 0.0f)) &&
+                       a.lattice, std::string(who) + ": null pointer");
+    ARREAU_REQUIRE(a.B >= 1 && a.N >= 0, std::string(who) + ": bad size");
+    ARREAU_REQUIRE(a.clipmax > 0.0f && a.clipmax <= 1.0f, std::string(who) + ": lattice_clipmax must lie in (0, 1]");
+    const SampleState st{.frac = a.frac, .types = a.types, .lengths = a.lengths, .angles = a.angles, .offsets = a.offsets, .B = a.B, .N = a.N,
+                         .lattice = a.lattice};
+    const ReverseInputs in{a.t, a.eps, a.logits, a.len0, StepNoiseSrc{a.z_lattice, a.z_frac, a.u_types, 0}};
+    const StepScheduleDev sched{nullptr, a.s, a.clipmax};
+    opt.sched = &sched;
+    return arreau_launch_reverse(a.m, st, in, opt, (hipStream_t)a.stream);
 }
 
 extern "C" int arreau_reverse_step_to(const arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths,
@@ -296,8 +303,10 @@ extern "C" int arreau_reverse_step_to(const arreau_model* m, float* d_frac, int3
                                       int32_t N, const float* d_eps, const float* d_logits, const float* d_len0,
                                       const float* d_z_lattice, const float* d_z_frac, const float* d_u_types, float* d_lattice,
                                       float lattice_clipmax, void* stream) {
-    return reverse_step_to(m, d_frac, d_types, d_lengths, d_angles, d_t, d_s, d_off, B, N, d_eps, d_logits, d_len0, d_z_lattice, d_z_frac,
-                           d_u_types, d_lattice, lattice_clipmax, /*d_length_tie=*/nullptr, /*sym=*/nullptr, stream, "arreau_reverse_step_to");
+    const StepToArgs a{.m = m, .frac = d_frac, .lengths = d_lengths, .lattice = d_lattice, .types = d_types, .angles = d_angles, .eps = d_eps,
+                       .logits = d_logits, .len0 = d_len0, .z_lattice = d_z_lattice, .z_frac = d_z_frac, .u_types = d_u_types, .t = d_t,
+                       .s = d_s, .offsets = d_off, .B = B, .N = N, .clipmax = lattice_clipmax, .stream = stream};
+    return reverse_step_to("arreau_reverse_step_to", a, StepOptions{});
 }
 
 // arreau_reverse_step_to with the lattice-system tie of the lengths (rules in include/arreau_hip.h); NULL = arreau_reverse_step_to.
@@ -306,8 +315,10 @@ extern "C" int arreau_reverse_step_tied(const arreau_model* m, float* d_frac, in
                                         int32_t N, const float* d_eps, const float* d_logits, const float* d_len0,
                                         const float* d_z_lattice, const float* d_z_frac, const float* d_u_types, float* d_lattice,
                                         float lattice_clipmax, const int32_t* d_length_tie, void* stream) {
-    return reverse_step_to(m, d_frac, d_types, d_lengths, d_angles, d_t, d_s, d_off, B, N, d_eps, d_logits, d_len0, d_z_lattice, d_z_frac,
-                           d_u_types, d_lattice, lattice_clipmax, d_length_tie, /*sym=*/nullptr, stream, "arreau_reverse_step_tied");
+    const StepToArgs a{.m = m, .frac = d_frac, .lengths = d_lengths, .lattice = d_lattice, .types = d_types, .angles = d_angles, .eps = d_eps,
+                       .logits = d_logits, .len0 = d_len0, .z_lattice = d_z_lattice, .z_frac = d_z_frac, .u_types = d_u_types, .t = d_t,
+                       .s = d_s, .offsets = d_off, .B = B, .N = N, .clipmax = lattice_clipmax, .stream = stream};
+    return reverse_step_to("arreau_reverse_step_tied", a, StepOptions{.length_tie = d_length_tie});
 }
 
 // DDIM-style sampling: an eta that is finite and lies in [0, 1], or ARREAU_EINVAL.
@@ -324,9 +335,10 @@ extern "C" int arreau_reverse_step_eta(const arreau_model* m, float* d_frac, int
                                        float lattice_clipmax, const int32_t* d_length_tie, float eta, void* stream) {
     int rc;
     if ((rc = arreau_eta_check(eta, "arreau_reverse_step_eta"))) return rc;
-    return reverse_step_to(m, d_frac, d_types, d_lengths, d_angles, d_t, d_s, d_off, B, N, d_eps, d_logits, d_len0, d_z_lattice, d_z_frac,
-                           d_u_types, d_lattice, lattice_clipmax, d_length_tie, /*sym=*/nullptr, stream, "arreau_reverse_step_eta",
-                           eta + 0.0f /* -0 -> +0 */);
+    const StepToArgs a{.m = m, .frac = d_frac, .lengths = d_lengths, .lattice = d_lattice, .types = d_types, .angles = d_angles, .eps = d_eps,
+                       .logits = d_logits, .len0 = d_len0, .z_lattice = d_z_lattice, .z_frac = d_z_frac, .u_types = d_u_types, .t = d_t,
+                       .s = d_s, .offsets = d_off, .B = B, .N = N, .clipmax = lattice_clipmax, .stream = stream};
+    return reverse_step_to("arreau_reverse_step_eta", a, StepOptions{.length_tie = d_length_tie, .eta = eta + 0.0f /* -0 -> +0 */});
 }
 
 // Second-order multistep sampling: every history pointer given, or ARREAU_EINVAL.
@@ -345,9 +357,10 @@ extern "C" int arreau_reverse_step_multistep(const arreau_model* m, float* d_fra
                                              void* stream) {
     int rc;
     if ((rc = arreau_multistep_check(multistep, "arreau_reverse_step_multistep"))) return rc;
-    return reverse_step_to(m, d_frac, d_types, d_lengths, d_angles, d_t, d_s, d_off, B, N, d_eps, d_logits, d_len0, d_z_lattice, d_z_frac,
-                           d_u_types, d_lattice, lattice_clipmax, d_length_tie, /*sym=*/nullptr, stream, "arreau_reverse_step_multistep",
-                           0.0f, multistep);
+    const StepToArgs a{.m = m, .frac = d_frac, .lengths = d_lengths, .lattice = d_lattice, .types = d_types, .angles = d_angles, .eps = d_eps,
+                       .logits = d_logits, .len0 = d_len0, .z_lattice = d_z_lattice, .z_frac = d_z_frac, .u_types = d_u_types, .t = d_t,
+                       .s = d_s, .offsets = d_off, .B = B, .N = N, .clipmax = lattice_clipmax, .stream = stream};
+    return reverse_step_to("arreau_reverse_step_multistep", a, StepOptions{.length_tie = d_length_tie, .eta = 0.0f, .ms = multistep});
 }
 
 // Species control: a temperature that is finite and not negative, or ARREAU_EINVAL; *out the struct the kernels take (-0 -> +0).
@@ -379,8 +392,10 @@ extern "C" int arreau_reverse_step_species(const arreau_model* m, float* d_frac,
         ARREAU_REQUIRE(!eta || *eta == 0.0f, std::string(who) + ": a multistep step is the eta = 0 step");
     }
     const float e = multistep ? 0.0f : (eta ? *eta + 0.0f /* -0 -> +0 */ : -1.0f);
-    return reverse_step_to(m, d_frac, d_types, d_lengths, d_angles, d_t, d_s, d_off, B, N, d_eps, d_logits, d_len0, d_z_lattice, d_z_frac,
-                           d_u_types, d_lattice, lattice_clipmax, d_length_tie, symmetry, stream, who, e, multistep, &sp);
+    const StepToArgs a{.m = m, .frac = d_frac, .lengths = d_lengths, .lattice = d_lattice, .types = d_types, .angles = d_angles, .eps = d_eps,
+                       .logits = d_logits, .len0 = d_len0, .z_lattice = d_z_lattice, .z_frac = d_z_frac, .u_types = d_u_types, .t = d_t,
+                       .s = d_s, .offsets = d_off, .B = B, .N = N, .clipmax = lattice_clipmax, .stream = stream};
+    return reverse_step_to(who, a, StepOptions{.length_tie = d_length_tie, .sym = symmetry, .eta = e, .ms = multistep, .species = &sp});
 }
 
 // DDIM inversion: one step from level d_s[b] up to level d_t[b] on the caller's network outputs (rules in include/arreau_hip.h).
@@ -406,8 +421,10 @@ extern "C" int arreau_reverse_step_sym(const arreau_model* m, float* d_frac, int
                                        float lattice_clipmax, const int32_t* d_length_tie, const arreau_symmetry* symmetry, void* stream) {
     int rc;
     if (symmetry && (rc = arreau_symmetry_check(symmetry, "arreau_reverse_step_sym"))) return rc;
-    return reverse_step_to(m, d_frac, d_types, d_lengths, d_angles, d_t, d_s, d_off, B, N, d_eps, d_logits, d_len0, d_z_lattice, d_z_frac,
-                           d_u_types, d_lattice, lattice_clipmax, d_length_tie, symmetry, stream, "arreau_reverse_step_sym");
+    const StepToArgs a{.m = m, .frac = d_frac, .lengths = d_lengths, .lattice = d_lattice, .types = d_types, .angles = d_angles, .eps = d_eps,
+                       .logits = d_logits, .len0 = d_len0, .z_lattice = d_z_lattice, .z_frac = d_z_frac, .u_types = d_u_types, .t = d_t,
+                       .s = d_s, .offsets = d_off, .B = B, .N = N, .clipmax = lattice_clipmax, .stream = stream};
+    return reverse_step_to("arreau_reverse_step_sym", a, StepOptions{.length_tie = d_length_tie, .sym = symmetry});
 }
 
 // the host checks of a symmetry table set: every pointer given, sizes positive (the kernel checks every index it follows)

@@ -3,7 +3,8 @@ tests/sampling_corner_cases.py; guards: test_sampling_corners_cpu.py): 67 ragged
 timesteps, S = 124 / 2 / 12 classes and T = 2.  One launch per case against the float64 restatements gathered per crystal, with
 the bounds of each entry point's own restatement test and every class equal; bitwise against the constant-pair launches, the
 untied step and the P1 symmetric step; the eta, inversion and conditioned resampled loops on the same batch bitwise against
-their steps and events in both loop forms, and one conditioned step in value.  Needs an MI355X: `-m gpu`.
+their steps and events in both loop forms, and one conditioned step in value.  Last, the contract of the loop's graph key on the
+same batch (section 6: 7 tests of three-step loops, 2.8 s together on an MI355X).  Needs an MI355X: `-m gpu`.
 
 Measured on an MI355X (74 tests in 5.1 s; the slowest 0.5 s, the first loop of the module; every other at most 0.2 s).  Largest
 error, positions wrapped / lengths / cell, per model; the bounds are 1e-5 for positions and 1e-5 max(1, magnitude) for lengths and
@@ -566,4 +567,109 @@ def test_one_conditioned_step_in_value(dev, loop_model):
     assert float(dd[pm].max()) <= 1e-6
     assert torch.equal(ty.cpu().long()[tm], ty_o[tm])
     assert wrong <= 1  # the network's own logits: a Gumbel arg-max within rounding of a tie may go either way
+    eng.check_status()
+
+
+# -------------------------------------------------------------------------------------------------------------- 6
+def _key_rows(case, dev):
+    """name -> (options A, options B, poison, check): a replay call with A, then poison() (what a stale replay would read or write
+    is changed under it), then a replay call with B on the same buffers; check() after it.  Only the named option differs."""
+    from arreau_amd.diffusion import contact_guidance as cg
+    from arreau_amd.diffusion import keyed
+    from arreau_amd.diffusion import species as sp
+    nothing = lambda: None
+    allowed = np.ones((B, case.S), dtype=bool)
+    allowed[::2, 5:] = False  # the even crystals: classes 0..4 only
+    rows_a, rows_b = sp.device_rows(allowed, dev), sp.device_rows(allowed, dev)
+    seeds = torch.from_numpy(keyed.stream_seeds(99, np.arange(B)).view(np.int64).copy())
+    seeds_a, seeds_b = seeds.to(dev).contiguous(), seeds.to(dev).contiguous()
+    tie_a, tie_b = _i32(C.CODES, dev), _i32(C.CODES, dev)
+    guide, info = cg.ContactGuidance(min_distance=2.0, weight=0.3), cg.allocate_info(B, dev)
+    sched = dict(t_start=99, next_table=respacing.next_table(C.T, [99, 80, 61, 40]).to(dev))
+
+    def clear_info():
+        assert any(bool(info[q].any()) for q in cg.INFO_KEYS), "the guided run wrote no diagnostics: the row would see nothing"
+        for q in cg.INFO_KEYS:
+            info[q].zero_()
+
+    def info_untouched():
+        assert not any(bool(info[q].any()) for q in cg.INFO_KEYS), "a replay wrote the diagnostics of a call that named none"
+
+    return {
+        "lattice_clipmax": (dict(sched, lattice_clipmax=0.999), dict(sched, lattice_clipmax=0.05), nothing, nothing),
+        "species-rows-pointer": (dict(species=(rows_a, 1.0)), dict(species=(rows_b, 1.0)), lambda: rows_a.fill_(-1), nothing),
+        "crystal-seeds-pointer": (dict(crystal_seeds=seeds_a), dict(crystal_seeds=seeds_b), lambda: seeds_a.add_(1), nothing),
+        "tie-pointer": (dict(length_tie=tie_a), dict(length_tie=tie_b), lambda: tie_a.zero_(), nothing),
+        "guidance-info-absent": (dict(guidance=(guide, info)), dict(guidance=guide), clear_info, info_untouched),
+    }
+
+
+KEY_ROWS = ["lattice_clipmax", "species-rows-pointer", "crystal-seeds-pointer", "tie-pointer", "guidance-info-absent"]
+
+
+@pytest.mark.parametrize("row", KEY_ROWS)
+def test_graph_key_holds_every_option(dev, row):
+    """The contract of the graph key (internal.h: SampleGraphKey holds the call's SampleOptions whole): a replay loop with option
+    value A, the state restored into the same buffers, a replay loop with value B -- the result is the eager loop's with B bit for
+    bit, so the graph captured for A was not replayed.  Three steps per call (the fewest that replay), the 67-crystal batch, S12.
+    A value row also shows that A and B give different states; a pointer row (two tables of the same contents) overwrites table A
+    before the second call, so a stale replay would read other values, and shows that the overwritten table gives another state;
+    the info row shows the first call wrote the diagnostics and the second, which names none, left them alone.
+    The rows other tests hold already, in the same form: eta 0.0 -> 0.5 and none (test_gpu_ddim_sampling.py::
+    test_eta_loop_without_a_schedule_and_another_eta_is_captured_anew), the corrector's snr and its steps 1 -> 2
+    (test_gpu_corrector_sampling.py::test_changed_corrector_never_replays_a_stale_graph), the species temperature
+    (test_gpu_species_sampling.py, "another temperature, other rows on the same buffers"), the guidance's weight, its min_distance
+    and another set of info arrays (test_gpu_contact_guidance.py::test_another_weight_on_the_same_buffers_is_not_a_stale_replay),
+    the resampling's passes and jump length (test_gpu_resampled_sampling.py::test_changed_resampling_never_replays_a_stale_graph),
+    the multistep history pointers (test_gpu_multistep_sampling.py::test_loop_without_a_schedule_and_the_graph_key) and the
+    direction (test_gpu_inversion.py, the invert loop on a sampling loop's buffers)."""
+    _, S, m, _ = _model(dev, "S12")
+    eng = m.engine()
+    case, seed, n = LoopCase(dev, S, 53), 24681357, 3
+    opt_a, opt_b, poison, check = _key_rows(case, dev)[row]
+
+    def run(bufs, use_graph, t_start=60, **opt):
+        eng.sample_loop(*bufs[:3], case.an, case.off, t_start, n, seed, None, bufs[3], use_graph=use_graph, **opt)
+        return bufs
+
+    eng.status(reset=True)
+    bufs = run(case.fresh(), True, **opt_a)
+    first = tuple(x.clone() for x in bufs)
+    assert_same_bits(first, run(case.fresh(), False, **opt_a), (row, "A: replay against eager"))
+    poison()
+    for x, x0 in zip(bufs, case.fresh()):
+        x.copy_(x0)
+    run(bufs, True, **opt_b)
+    check()
+    assert_same_bits(bufs, run(case.fresh(), False, **opt_b), (row, "B on A's buffers: replay against eager"))
+    if row == "lattice_clipmax":
+        assert not torch.equal(bufs[2], first[2]), "the two clips give the same lengths: the row would see nothing"
+    elif row.endswith("pointer"):
+        assert_same_bits(bufs, first, (row, "the same contents give the same state"))
+        spoiled = run(case.fresh(), False, **opt_a)
+        assert any(not torch.equal(a, b) for a, b in zip(spoiled, first)), "the overwritten table gives the same state: the row would see nothing"
+    eng.check_status()
+
+
+@pytest.mark.parametrize("pair", ["corrector", "guidance"])
+def test_graph_key_does_not_split_an_absent_option(dev, pair):
+    """What the key must not split: corrector None and (0, snr), guidance None and weight 0 are the same options (internal.h:
+    SampleOptions), so on the same buffers the second call of each pair replays the graph the first one left.  The library has
+    no way to observe a replay, so the assertion is equality only: both calls, and the eager loop, give the same bits."""
+    from arreau_amd.diffusion import contact_guidance as cg
+    _, S, m, _ = _model(dev, "S12")
+    eng = m.engine()
+    case, seed, n = LoopCase(dev, S, 59), 97531, 3
+    absent, present = {"corrector": (dict(corrector=None), dict(corrector=(0, SNR))),
+                       "guidance": (dict(species=(None, 1.0), guidance=None), dict(species=(None, 1.0), guidance=cg.ContactGuidance(2.0, 0.0)))}[pair]
+    eng.status(reset=True)
+    want = case.fresh()
+    eng.sample_loop(*want[:3], case.an, case.off, 60, n, seed, None, want[3], use_graph=False, **absent)
+    bufs = case.fresh()
+    for opt in (absent, present, absent):
+        for x, x0 in zip(bufs, case.fresh()):
+            x.copy_(x0)
+        eng.sample_loop(*bufs[:3], case.an, case.off, 60, n, seed, None, bufs[3], use_graph=True, **opt)
+        assert_same_bits(bufs, want, (pair, opt))
+    assert not torch.equal(want[0], case.fresh()[0])
     eng.check_status()
