@@ -12,28 +12,20 @@ import torch
 import torch.nn as nn
 
 from . import corrector as pc
-from . import ddim
+from . import instruments
 from . import inversion
 from . import keyed as keyed_mod
 from . import multistep as multistep_mod
-from . import resampling as rs
 from . import respacing
-from . import screening
+from . import sample_plan
 from . import species as species_mod
-from . import uniqueness as uniqueness_mod
-from . import cell_reduction
-from . import symmetry_search
-from . import symmetrize as symmetrize_mod
-from . import conventional_cell as conventional_mod
-from . import bond_order as bond_order_mod
-from . import coordination as coordination_mod
 from . import contact_guidance as guidance_mod
-from . import structure_match
 from .d3pm import D3PM
 from . import lattice_systems
 from . import symmetry as sym_mod
 from .diffusion_helpers import VE_pbc, VP_lattice, crystal_offsets
 from .inference.visualize_crystal import VisualizationSetting, vis_crystal_during_sampling
+from .lattice_helpers import lattice_from_params
 from .tools.atomic_number_table import AtomicNumberTable, atomic_number_indexes_to_atomic_numbers
 
 pos_sigma_min = 0.001
@@ -209,6 +201,124 @@ class DiffusionLossMetric:
         return self.total_loss / self.total_samples
 
 
+def state_to_device(state, dev):
+    """(frac [N,3], types [N] i32, lengths [B,3], angles [B,3], offsets [B+1] i32, a zeroed cell buffer [B,3,3]) of an
+    inversion.SamplerState as contiguous tensors on `dev`, float32 unless noted."""
+    f32 = dict(device=dev, dtype=torch.float32)
+    frac, lengths, angles = (torch.as_tensor(v).to(**f32).contiguous() for v in (state.frac_x, state.lengths, state.angles))
+    types = torch.as_tensor(state.species).to(device=dev, dtype=torch.int32).contiguous()
+    return frac, types, lengths, angles, crystal_offsets(torch.as_tensor(state.num_atoms), dev), torch.zeros((state.B, 3, 3), **f32)
+
+
+@dataclass
+class _RunBuffers:
+    """The device buffers of one sample() call: the state the steps update in place, what holds parts of it, and the option
+    tables and structs every call of the run takes."""
+    frac_d: torch.Tensor
+    types_d: torch.Tensor
+    len_d: torch.Tensor
+    ang_d: torch.Tensor
+    off_d: torch.Tensor
+    lattice_d: torch.Tensor
+    clipmax: float
+    const_d: Optional[torch.Tensor] = None
+    tie_d: Optional[torch.Tensor] = None
+    sym_d: Optional[dict] = None
+    next_d: Optional[torch.Tensor] = None   # the Philox loop's next-timestep table of a schedule
+    cond_d: Optional[dict] = None
+    seeds_d: Optional[torch.Tensor] = None
+    history: Optional[dict] = None          # multistep: empty at first, held through segments and a re-run
+    guide: Optional[tuple] = None           # contact guidance: (parameters, the device arrays of its last evaluation)
+    species_ctl: Optional[tuple] = None     # (rows, temperature); None (no set, temperature 1) keeps the exports used so far
+
+    @classmethod
+    def upload(cls, dev, plan, state, held, T, clipmax):
+        frac_d, types_d, len_d, ang_d, off_d, lattice_d = state_to_device(state, dev)
+        species_ctl = None
+        if plan.allow_rows is not None or plan.species_temperature != 1.0:
+            species_ctl = (species_mod.device_rows(plan.allow_rows, dev) if plan.allow_rows is not None else None,
+                           plan.species_temperature)
+        return cls(
+            frac_d, types_d, len_d, ang_d, off_d, lattice_d, clipmax, const_d=types_d.clone() if held else None,
+            tie_d=(torch.as_tensor(state.length_tie, device=dev, dtype=torch.int32).contiguous()
+                   if state.length_tie is not None else None),
+            sym_d=sym_mod.device_arrays(plan.specs, off_d, dev) if plan.specs is not None else None,
+            next_d=respacing.next_table(T, plan.schedule).to(dev) if plan.schedule is not None and plan.noise == "philox" else None,
+            history=multistep_mod.allocate_history(plan.N, plan.B, dev) if plan.multistep else None,
+            guide=(plan.guidance, guidance_mod.allocate_info(plan.B, dev)) if plan.guidance is not None else None,
+            species_ctl=species_ctl)
+
+    def snapshot(self):
+        return self.frac_d.clone(), self.types_d.clone(), self.len_d.clone()
+
+    def restore(self, saved):
+        self.frac_d.copy_(saved[0]); self.types_d.copy_(saved[1]); self.len_d.copy_(saved[2])
+        if self.history is not None:
+            multistep_mod.empty_history(self.history)  # the state changed outside a step
+
+
+def _philox_driver(eng, plan, buf, seed, use_graph, frame):
+    """The run as library loops (eng.sample_loop), cut after the steps whose state is a frame (plan.stops).  The noise is a
+    function of (seed, timestep), so a run in segments is the same trajectory as a run in one call; a respaced segment starts at
+    any scheduled timestep (respacing.next_table)."""
+    fixed = buf.len_d.clone() if plan.fixed_cell else None
+    start = 0
+    for j in plan.stops + [None]:
+        end = j + 1 if j is not None else len(plan.steps)
+        if end > start:
+            eng.sample_loop(buf.frac_d, buf.types_d, buf.len_d, buf.ang_d, buf.off_d, plan.steps[start], end - start, seed, buf.const_d,
+                            buf.lattice_d, use_graph=bool(use_graph), fixed_lengths=fixed, condition=buf.cond_d, next_table=buf.next_d,
+                            lattice_clipmax=buf.clipmax, corrector=plan.corrector, resampling=plan.resampling, length_tie=buf.tie_d,
+                            symmetry=buf.sym_d, eta=plan.eta, multistep=buf.history, species=buf.species_ctl,
+                            crystal_seeds=buf.seeds_d, guidance=buf.guide)
+            start = end
+        if j is not None:
+            frame(f"_{plan.steps[j]}")
+
+
+def _host_noise_driver(eng, plan, buf, seed, use_graph, frame):
+    """The run as the events of resampling.plan on the host (noise 'device' and 'reference'; `seed` and `use_graph` belong to the
+    Philox driver): per step the network evaluation, the corrector moves, each followed by a new evaluation, the three draws --
+    lengths, positions, species -- and one predictor step; per jump its three draws and the jump."""
+    B, N, S = plan.B, plan.N, plan.S
+    f32 = dict(device=buf.frac_d.device, dtype=torch.float32)
+    if plan.noise == "device":  # torch's device generator, in float32
+        gauss, unif = (lambda *shape: torch.randn(shape, **f32)), (lambda *shape: torch.rand(shape, **f32))
+    else:  # the global CPU generator in the default dtype, as the reference draws
+        dt = torch.get_default_dtype()
+        gauss, unif = (lambda *shape: torch.randn(shape, dtype=dt).to(**f32)), (lambda *shape: torch.rand(shape, dtype=dt).to(**f32))
+    t_d = torch.empty(B, device=f32["device"], dtype=torch.int32)
+    s_d = torch.empty(B, device=f32["device"], dtype=torch.int32)
+    state = (buf.frac_d, buf.types_d, buf.len_d, buf.ang_d)
+    corrector_steps, corrector_snr = plan.corrector or (0, None)
+
+    def evaluate():  # the network at t_d on the current state; with contact guidance its eps is guided in place
+        eps, logits, len0 = eng.predict_scores(*state, t_d, buf.off_d)
+        if buf.guide is not None and buf.guide[0].weight > 0:
+            eng.contact_guidance_step(buf.frac_d, lattice_from_params(buf.len_d, buf.ang_d), t_d, buf.off_d, eps, buf.guide)
+        return eps, logits, len0
+    for ev in plan.events:
+        if ev.kind == "jump":  # resampling: the state back up to the block's top, in front of pass ev.r
+            z_f, z_l, u_t = gauss(N, 3), gauss(B, 3), unif(N, S)
+            s_d.fill_(ev.s)
+            t_d.fill_(ev.t)
+            eng.resample_jump(*state, s_d, t_d, buf.off_d, z_f, z_l, u_t, buf.lattice_d, const_types=buf.const_d, length_tie=buf.tie_d)
+            continue
+        t_d.fill_(ev.t)
+        eps, logits, len0 = evaluate()
+        for _ in range(corrector_steps):  # predictor-corrector: the moves at t, each followed by a new evaluation
+            eng.corrector_step(buf.frac_d, t_d, buf.off_d, eps, gauss(N, 3), corrector_snr)
+            eps, logits, len0 = evaluate()
+        z_l, z_f, u_t = gauss(B, 3), gauss(N, 3), unif(N, S)
+        eng.predictor_step(*state, t_d, s_d, buf.off_d, eps, logits, len0, z_l, z_f, u_t, buf.lattice_d, ev.s,
+                           scheduled=plan.schedule is not None, length_tie=buf.tie_d, eta=plan.eta, multistep=buf.history,
+                           species=buf.species_ctl, lattice_clipmax=buf.clipmax)
+        if buf.const_d is not None:
+            buf.types_d.copy_(buf.const_d)
+        if ev.t != plan.t_first and sample_plan.frame_after(plan.visualization_setting, ev.t):
+            frame(f"_{ev.t}")
+
+
 class DiffusionLoss(nn.Module):
     def __init__(self, args, num_atomic_states: int):
         super().__init__()
@@ -356,17 +466,7 @@ class DiffusionLoss(nn.Module):
         t_c = t_c.to(device=dev, dtype=torch.int32).contiguous()
         return eng.predict_scores(frac, ty, lengths, ang, t_c, off, edges=edges)
 
-    @staticmethod
-    def _atom_counts(num_atoms_per_sample, B):
-        """The atom count of every crystal, int64 [B].  Extension over the reference (uniform n only, diffusion_loss.py:308): a
-        sequence gives each crystal of the batch its own atom count (the HIP path works on CSR offsets, so ragged batches cost
-        nothing extra)."""
-        if isinstance(num_atoms_per_sample, (int, np.integer)):
-            return torch.full((B,), int(num_atoms_per_sample))
-        num_atoms = torch.as_tensor([int(v) for v in num_atoms_per_sample], dtype=torch.long)
-        if num_atoms.numel() != B or int(num_atoms.min()) < 1:
-            raise ValueError("num_atoms_per_sample must be an int or hold one positive count per crystal of the batch")
-        return num_atoms
+    _atom_counts = staticmethod(sample_plan.atom_counts)
 
     def draw_initial_state(self, num_atoms_per_sample, num_samples_in_batch, num_atomic_states=None, constant_atoms=None,
                            lattice_system=None, condition=None, specs=None, seed=None, crystal_keys=None,
@@ -401,8 +501,7 @@ class DiffusionLoss(nn.Module):
             angles[known] = torch.as_tensor(condition.known_angles(), dtype=angles.dtype)[known]
         if streams is not None:
             eng = model.engine()
-            z_len, z_frac = eng.keyed_initial_draws(torch.as_tensor(streams.view(np.int64), device=eng.device),
-                                                    crystal_offsets(num_atoms, eng.device))
+            z_len, z_frac = eng.keyed_initial_draws(keyed_mod.device_seeds(streams, eng.device), crystal_offsets(num_atoms, eng.device))
             lengths = z_len.cpu().to(dt)
         else:
             lengths = torch.randn([B, 3])
@@ -626,266 +725,35 @@ class DiffusionLoss(nn.Module):
         term, no radii or species dependence, no weight schedule other than 1 / sigma_t^2; no claim on sample quality.  A bad
         value is rejected before any work.  weight = 0 and None: no launch is added and the results are what they were, bit for
         bit (None also through the exports it used)."""
-        contact_guidance = guidance_mod.resolve(contact_guidance)
-        coordination = coordination_mod.resolve(coordination)
-        bond_order = bond_order_mod.resolve(bond_order)
-        bond_order_mod.check_shared(bond_order, coordination)
-        if crystal_keys is not None:  # validated before any work and before any generator is touched (the count: below)
-            crystal_keys = keyed_mod.validate_keys(crystal_keys, None, seed, noise if noise in ("philox", "device", "reference") else "philox")
-        match_to = structure_match.resolve(match_to)
-        reduce_cell = cell_reduction.resolve(reduce_cell)
-        symmetrize = symmetrize_mod.resolve(symmetrize)
-        symmetrize_mod.check_shared_search(symmetrize, symmetry_search.resolve(find_symmetry))
-        conventional_cell = conventional_mod.resolve(conventional_cell)
-        conventional_mod.check_shared(conventional_cell, reduce_cell, symmetry_search.resolve(find_symmetry), symmetrize)
-        screen = screening.resolve(screen)
-        unique = uniqueness_mod.resolve(unique)
-        find_symmetry = symmetry_search.resolve(find_symmetry)
-        frames = visualization_setting != VisualizationSetting.NONE
-        if frames and not vis_name:
-            raise ValueError("visualization_setting other than NONE needs vis_name (prefix of the frame files)")
-        if noise not in ("philox", "device", "reference"):
-            raise ValueError("noise must be 'philox', 'device' or 'reference'")
-        if initial_state is not None:  # validated before any work; the state defines the batch and the level the loop enters at
-            inversion.check_initial_state(initial_state, self.T, condition=condition, symmetry=symmetry, lattice_system=lattice_system,
-                                          num_atoms_per_sample=num_atoms_per_sample, num_samples_in_batch=num_samples_in_batch,
-                                          num_atomic_states=len(z_table) if z_table is not None else None)
-            num_atoms_per_sample = [int(v) for v in np.asarray(initial_state.num_atoms).reshape(-1)]
-            num_samples_in_batch = len(num_atoms_per_sample)
-            schedule = inversion.schedule_from(self.T, initial_state.t, num_steps=num_steps, timesteps=timesteps)
-        else:
-            schedule = respacing.resolve_schedule(self.T, num_steps=num_steps, timesteps=timesteps)  # None: every timestep
-        top = self.T - 1 if initial_state is None else int(initial_state.t)  # the level the loop enters at
-        corrector_steps, corrector_snr = pc.check_corrector(corrector_steps, corrector_snr)
-        resample_passes, jump_length = rs.check_resampling(resample_passes, jump_length)
-        eta = ddim.check_eta(eta) if eta is not None else None
-        multistep = multistep_mod.check_multistep(multistep, eta=eta, condition=condition, corrector_steps=corrector_steps,
-                                                  resample_passes=resample_passes, symmetry=symmetry)
-        species_temperature = species_mod.validate_temperature(species_temperature)
-        if resample_passes > 1 and visualization_setting in (VisualizationSetting.ALL, VisualizationSetting.ALL_DETAILED):
-            raise ValueError("resampling (resample_passes > 1) takes visualization_setting NONE or LAST: a frame inside a block "
-                             "would be overwritten by the block's next pass")
-        if symmetry is not None and not isinstance(symmetry, sym_mod.SymmetrySpec) and num_samples_in_batch is None:
-            try:
-                num_samples_in_batch = len(symmetry)
-            except TypeError:
-                pass
-        specs = sym_mod.resolve(symmetry, num_samples_in_batch)  # None: no crystal is constrained (validated before any work)
-        if specs is not None:
-            unsupported = [name for name, on in (("condition", condition is not None), ("corrector_steps > 0", corrector_steps > 0),
-                                                 ("resample_passes > 1", resample_passes > 1), (f"noise={noise!r}", noise != "philox"))
-                           if on]
-            if unsupported:
-                raise ValueError("symmetry= is not supported with " + ", ".join(unsupported) + " yet (a follow-up); it runs in the "
-                                 "Philox loop without a condition, correctors or resampling")
-            if eta is not None:
-                raise ValueError("symmetry= is not supported with eta= (the symmetric step has no DDIM-style form)")
-            num_atoms_per_sample, lattice_system = sym_mod.batch_layout(specs, num_atoms_per_sample, lattice_system)
-            num_samples_in_batch = len(specs)
-            if constant_atoms is not None:
-                ca = np.asarray(torch.as_tensor(constant_atoms).reshape(-1))
-                if ca.size == sum(num_atoms_per_sample):
-                    first = np.concatenate([[0], np.cumsum(num_atoms_per_sample)])
-                    for b, s_b in enumerate(specs):
-                        if s_b is not None:
-                            s_b.check_species(ca[first[b]:first[b + 1]], f"constant species of crystal {b}")
-        if condition is not None:  # validated before the engine is touched
-            num_atoms_per_sample, num_samples_in_batch = condition.resolve_batch(num_atoms_per_sample, num_samples_in_batch)
-            condition.check_sampling(z_table, noise=noise, fixed_cell=fixed_cell, constant_species=constant_atoms is not None)
-        elif num_atoms_per_sample is None or num_samples_in_batch is None:
-            raise ValueError("num_atoms_per_sample and num_samples_in_batch are needed without a condition")
-        B = int(num_samples_in_batch)
-        if crystal_keys is not None:
-            keyed_mod.validate_keys(crystal_keys, B, seed)
-        lattice_systems.check(lattice_system, B, condition.lattice_known() if condition is not None else None)
-        # species control: the admission rows (None: no set is given), validated with the held species before the engine is touched
-        allow_rows = species_mod.resolve_elements(elements, z_table, B) if elements is not None else None
-        if allow_rows is not None:
-            species_mod.check_rows(allow_rows)
-            crystal_of = np.repeat(np.arange(B), self._atom_counts(num_atoms_per_sample, B).numpy())
-            if condition is not None and condition.species_known().any():
-                known = condition.species_known()
-                lut = {int(z): c for c, z in enumerate(z_table.zs)}
-                cls = np.array([lut.get(int(z), -1) if k else 0 for z, k in zip(np.asarray(condition.atomic_numbers), known)])
-                species_mod.check_held(allow_rows, crystal_of, cls, known, "condition")
-            if constant_atoms is not None and constant_atoms is not True and constant_atoms is not False:
-                held = np.asarray(torch.as_tensor(constant_atoms).reshape(-1))
-                if held.size == crystal_of.size:  # (a wrong size is rejected where the species are read)
-                    species_mod.check_held(allow_rows, crystal_of, held, np.ones(held.size, bool), "constant_atoms")
+        options = {k: v for k, v in locals().items() if k != "self"}  # (first statement: the keywords as given, nothing else)
+        sample_plan.check_options(**options)  # (what needs nothing of self, first)
+        plan = sample_plan.resolve(self.T, **options)
         eng = model.engine()
         dev = eng.device
-        S = len(z_table)
-        num_atoms = self._atom_counts(num_atoms_per_sample, B)
-        N = int(num_atoms.sum())
-        dt = torch.get_default_dtype()
-        if initial_state is None:
-            state = self.draw_initial_state(num_atoms_per_sample, B, num_atomic_states=S, constant_atoms=constant_atoms,
-                                            lattice_system=lattice_system, condition=condition, specs=specs, seed=seed,
-                                            crystal_keys=crystal_keys, model=model)
-        else:  # nothing is drawn: the state as given, its species replaced by the ones to hold when those are given
-            state = initial_state
-            if constant_atoms is False:
-                constant_atoms = None
-            if constant_atoms is not None and constant_atoms is not True:
-                held = torch.as_tensor(constant_atoms).reshape(-1).long()
-                if held.numel() != N:
-                    raise ValueError("constant_atoms must hold one class index per atom")
-                state = inversion.SamplerState(state.frac_x, held.numpy(), state.lengths, state.angles, state.num_atoms, state.t,
-                                               state.length_tie)
-        if allow_rows is not None and constant_atoms is True:  # the state's own species are held
-            species_mod.check_held(allow_rows, crystal_of, np.asarray(state.species), np.ones(N, bool), "constant_atoms=True")
-        tie = state.length_tie
-        angles, lengths = torch.as_tensor(state.angles), torch.as_tensor(state.lengths)
-        frac_x, atom_types = torch.as_tensor(state.frac_x), torch.as_tensor(state.species).long()
-
-        f32 = dict(device=dev, dtype=torch.float32)
-        frac_d = frac_x.to(**f32).contiguous()
-        len_d = lengths.to(**f32).contiguous()
-        ang_d = angles.to(**f32).contiguous()
-        types_d = atom_types.to(device=dev, dtype=torch.int32).contiguous()
-        const_d = types_d.clone() if constant_atoms is not None else None
-        off_d = crystal_offsets(num_atoms, dev)
-        lattice_d = torch.zeros((B, 3, 3), **f32)
-        tie_d = torch.as_tensor(tie, device=dev, dtype=torch.int32).contiguous() if tie is not None else None
-        sym_d = sym_mod.device_arrays(specs, off_d, dev) if specs is not None else None
-        # the timesteps this run visits, in order: every one (T-1 .. 1) or the schedule's, cut to max_steps
-        steps = list(range(top, 0, -1)) if schedule is None else schedule
-        steps = steps if max_steps is None else steps[:max(0, int(max_steps))]
-        n_steps = len(steps)
-        t_first = top if schedule is None else schedule[0]
-        successor = None if schedule is None else dict(zip(schedule, schedule[1:] + [0]))
-        clipmax = float(getattr(self.lattice_diffusion, "clipmax", lattice_clipmax))
-        next_d = respacing.next_table(self.T, schedule).to(dev) if schedule is not None and noise == "philox" else None
-        if (use_graph or fixed_cell) and noise != "philox":
-            raise ValueError("graph replay and fixed-cell sampling need noise='philox' (the in-kernel generator)")
-
-        # The loop as a function of the state buffers: it runs a second time, from the saved initial state, when the default
-        # fp16x3 kernels flag an overflow (see below).
-        init_state = (frac_d.clone(), types_d.clone(), len_d.clone())
-        rng_state = torch.random.get_rng_state()
-        cuda_rng_state = torch.cuda.get_rng_state(dev) if noise == "device" else None  # (the draws of noise='device')
+        state, constant_atoms = self._starting_state(plan, model, initial_state, constant_atoms, condition, seed)
         if noise == "philox" and seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-            rng_state = torch.random.get_rng_state()
-        # keyed sampling: the table of stream seeds (uint64 bits in an int64 tensor), held through every call of the run
-        seeds_d = None
-        if crystal_keys is not None:
-            seeds_d = torch.as_tensor(keyed_mod.stream_seeds(seed, crystal_keys).view(np.int64), device=dev).contiguous()
-        cond_d = None
+        buf = _RunBuffers.upload(dev, plan, state, constant_atoms is not None, self.T,
+                                 float(getattr(self.lattice_diffusion, "clipmax", lattice_clipmax)))
+        # the generator states a re-run below starts from (the draws of noise='reference' and of noise='device')
+        rng_state = torch.random.get_rng_state()
+        cuda_rng_state = torch.cuda.get_rng_state(dev) if noise == "device" else None
+        if plan.crystal_keys is not None:  # keyed sampling: the table of stream seeds, held through every call of the run
+            buf.seeds_d = keyed_mod.device_seeds(keyed_mod.stream_seeds(seed, plan.crystal_keys), dev)
         if condition is not None:
             # rule 5: the known components of the drawn initial state, at the first timestep t_1 (T - 1 without a schedule;
             # Philox key t_1 + 1); the saved initial state of a re-run below includes them
-            cond_d = condition.device_arrays(z_table, dev)
-            eng.condition_initial_state(frac_d, types_d, len_d, t_first, seed, cond_d, offsets=off_d, crystal_seeds=seeds_d)
-            init_state = (frac_d.clone(), types_d.clone(), len_d.clone())
+            buf.cond_d = condition.device_arrays(z_table, dev)
+            eng.condition_initial_state(buf.frac_d, buf.types_d, buf.len_d, plan.t_first, seed, buf.cond_d, offsets=buf.off_d,
+                                        crystal_seeds=buf.seeds_d)
+        saved = buf.snapshot()
 
-        corrector = (corrector_steps, corrector_snr) if corrector_steps > 0 else None
-        resampling = (resample_passes, jump_length, schedule) if resample_passes > 1 else None
-        # contact guidance: the parameters and the device arrays of its last evaluation, held through every call of the run
-        guide = (contact_guidance, guidance_mod.allocate_info(B, dev)) if contact_guidance is not None else None
-        history = multistep_mod.allocate_history(N, B, dev) if multistep else None  # empty; held through every call of the run
-        # species control: (rows, temperature) for the species exports; None (no set, temperature 1) keeps the exports used so far
-        species_ctl = None
-        if allow_rows is not None or species_temperature != 1.0:
-            species_ctl = (species_mod.device_rows(allow_rows, dev) if allow_rows is not None else None, species_temperature)
-        # the events of the host-noise modes: the visited steps, with jumps when resampling (the successor of the last step is
-        # the timestep it produces)
-        last_succ = (steps[-1] - 1 if schedule is None else successor[steps[-1]]) if steps else 0
-        events = rs.plan(steps, last_succ, resample_passes, jump_length)
+        def frame(suffix):  # the current state as a frame file
+            vis_crystal_during_sampling(z_table, buf.types_d.cpu().numpy(), buf.lattice_d.cpu().numpy(), buf.frac_d.cpu().numpy(),
+                                        vis_name + suffix, show_bonds, plan.num_atoms.numpy())
+        driver = _philox_driver if noise == "philox" else _host_noise_driver
+        driver(eng, plan, buf, seed, plan.use_graph, frame)
 
-        def run_loop(use_graph):
-            if noise == "philox":
-                if use_graph is None:
-                    use_graph = n_steps * resample_passes >= 200  # capture + instantiation (about 2 ms) against ~4 us saved per kernel boundary
-                fixed = len_d.clone() if fixed_cell else None
-                # Frames (diffusion_loss.py:351-370): the loop is cut after the steps at the timesteps the reference
-                # visualises -- every 10th for ALL, every one for ALL_DETAILED, never the first -- of those this run visits.
-                # The noise is a function of (seed, timestep), so a run in segments is the same trajectory as a run in one
-                # call; a respaced segment starts at any scheduled timestep (respacing.next_table).
-                stops = [j for j in range(1, n_steps)
-                         if (visualization_setting == VisualizationSetting.ALL and steps[j] % 10 == 0)
-                         or visualization_setting == VisualizationSetting.ALL_DETAILED]
-                start = 0
-                for j in stops + [None]:
-                    end = j + 1 if j is not None else n_steps
-                    if end > start:
-                        eng.sample_loop(frac_d, types_d, len_d, ang_d, off_d, steps[start], end - start, seed, const_d, lattice_d,
-                                        use_graph=bool(use_graph), fixed_lengths=fixed, condition=cond_d, next_table=next_d,
-                                        lattice_clipmax=clipmax, corrector=corrector, resampling=resampling, length_tie=tie_d,
-                                        symmetry=sym_d, eta=eta, multistep=history, species=species_ctl, crystal_seeds=seeds_d,
-                                        guidance=guide)
-                        start = end
-                    if j is not None:
-                        vis_crystal_during_sampling(z_table, types_d.cpu().numpy(), lattice_d.cpu().numpy(),
-                                                    frac_d.cpu().numpy(), vis_name + f"_{steps[j]}", show_bonds, num_atoms.numpy())
-            else:
-                if noise == "device":  # torch's device generator, in float32
-                    def gauss(*shape):
-                        return torch.randn(shape, **f32)
-
-                    def unif(*shape):
-                        return torch.rand(shape, **f32)
-                else:  # the global CPU generator in the default dtype, as the reference draws
-                    def gauss(*shape):
-                        return torch.randn(shape, dtype=dt).to(**f32)
-
-                    def unif(*shape):
-                        return torch.rand(shape, dtype=dt).to(**f32)
-                t_d = torch.empty(B, device=dev, dtype=torch.int32)
-                s_d = torch.empty(B, device=dev, dtype=torch.int32)
-
-                def evaluate():  # the network at t_d on the current state; with contact guidance its eps is guided in place
-                    eps, logits, len0 = eng.predict_scores(frac_d, types_d, len_d, ang_d, t_d, off_d)
-                    if guide is not None and contact_guidance.weight > 0:
-                        from .lattice_helpers import lattice_from_params
-                        eng.contact_guidance_step(frac_d, lattice_from_params(len_d, ang_d), t_d, off_d, eps, guide)
-                    return eps, logits, len0
-                for ev in events:
-                    timestep = ev.t
-                    if ev.kind == "jump":  # resampling: the state back up to the block's top, in front of pass ev.r
-                        z_f, z_l, u_t = gauss(N, 3), gauss(B, 3), unif(N, S)
-                        s_d.fill_(ev.s)
-                        t_d.fill_(ev.t)
-                        eng.resample_jump(frac_d, types_d, len_d, ang_d, s_d, t_d, off_d, z_f, z_l, u_t, lattice_d, const_types=const_d,
-                                          length_tie=tie_d)
-                        continue
-                    t_d.fill_(timestep)
-                    eps, logits, len0 = evaluate()
-                    for _ in range(corrector_steps):  # predictor-corrector: the moves at t, each followed by a new evaluation
-                        eng.corrector_step(frac_d, t_d, off_d, eps, gauss(N, 3), corrector_snr)
-                        eps, logits, len0 = evaluate()
-                    z_l, z_f, u_t = gauss(B, 3), gauss(N, 3), unif(N, S)
-                    if species_ctl is not None:  # species control: whichever step below the options name, under it
-                        s_d.fill_(timestep - 1 if schedule is None else successor[timestep])
-                        eng.reverse_step_species(frac_d, types_d, len_d, ang_d, t_d, s_d, off_d, eps, logits, len0, z_l, z_f, u_t,
-                                                 lattice_d, species_ctl, length_tie=tie_d, eta=eta if history is None else None,
-                                                 multistep=history, lattice_clipmax=clipmax)
-                    elif history is not None:  # multistep: the eta = 0 step extrapolated with the history (no z is read)
-                        s_d.fill_(timestep - 1 if schedule is None else successor[timestep])
-                        eng.reverse_step_multistep(frac_d, types_d, len_d, ang_d, t_d, s_d, off_d, eps, logits, len0, u_t, lattice_d,
-                                                   history, tie_d, clipmax)
-                    elif eta is not None:  # DDIM-style sampling: the eta step (tied or not; s = t - 1 without a schedule)
-                        s_d.fill_(timestep - 1 if schedule is None else successor[timestep])
-                        eng.reverse_step_eta(frac_d, types_d, len_d, ang_d, t_d, s_d, off_d, eps, logits, len0, z_l, z_f, u_t,
-                                             lattice_d, eta, tie_d, clipmax)
-                    elif tie_d is not None:  # lattice systems: the tied step (s = t - 1 without a schedule is the plain step)
-                        s_d.fill_(timestep - 1 if schedule is None else successor[timestep])
-                        eng.reverse_step_tied(frac_d, types_d, len_d, ang_d, t_d, s_d, off_d, eps, logits, len0, z_l, z_f, u_t,
-                                              lattice_d, tie_d, clipmax)
-                    elif schedule is None:
-                        eng.reverse_step(frac_d, types_d, len_d, ang_d, t_d, off_d, eps, logits, len0, z_l, z_f, u_t, lattice_d)
-                    else:
-                        s_d.fill_(successor[timestep])
-                        eng.reverse_step_to(frac_d, types_d, len_d, ang_d, t_d, s_d, off_d, eps, logits, len0, z_l, z_f, u_t,
-                                            lattice_d, clipmax)
-                    if const_d is not None:
-                        types_d.copy_(const_d)
-                    if timestep != t_first and ((visualization_setting == VisualizationSetting.ALL and timestep % 10 == 0)
-                                                   or visualization_setting == VisualizationSetting.ALL_DETAILED):
-                        vis_crystal_during_sampling(z_table, types_d.cpu().numpy(), lattice_d.cpu().numpy(),
-                                                    frac_d.cpu().numpy(), vis_name + f"_{timestep}", show_bonds, num_atoms.numpy())
-
-        run_loop(use_graph)
         # Range safety without an environment variable: the fp16x3 kernels never clamp -- an activation beyond 65504 reaches the
         # outputs as NaN and sets the sticky NONFINITE flag.  When that happens on the default kernels the batch is re-run HERE,
         # from its saved initial state and with the same draws (same Philox seed / same host and device generator states), on
@@ -895,61 +763,45 @@ class DiffusionLoss(nn.Module):
         # batch is first re-run with two fp16 planes and three fp16 products, which the engine then keeps.
         def rerun():
             eng.status(reset=True)
-            frac_d.copy_(init_state[0]); types_d.copy_(init_state[1]); len_d.copy_(init_state[2])
-            if history is not None:
-                multistep_mod.empty_history(history)  # the state changed outside a step
+            buf.restore(saved)
             torch.random.set_rng_state(rng_state)
             if cuda_rng_state is not None:
                 torch.cuda.set_rng_state(cuda_rng_state, dev)
-            run_loop(False)
+            driver(eng, plan, buf, seed, False, frame)
 
         info = eng.rerun_if_out_of_range(rerun)  # (shared with PONITA_DIFFUSION.encode)
         eng.check_status()  # sticky device flags (non-finite outputs, clamped indices): raise instead of returning them
-        if guide is not None:
-            info = dict(info or {}, contact_guidance=guidance_mod.info_to_numpy(guide[1]))
-        if frames:
-            vis_crystal_during_sampling(z_table, types_d.cpu().numpy(), lattice_d.cpu().numpy(), frac_d.cpu().numpy(),
-                                        vis_name + "_final", show_bonds, num_atoms.numpy())
-        metrics = None
-        if screen is not None:  # the final state, where it is: one launch, then the host copies below
-            crit = screen.with_mask_type(-1 if constant_atoms is not None else S - 1)
-            metrics = screening.metrics_to_numpy(eng.screen(frac_d, lattice_d, off_d, types_d, crit))
-        uniqueness = None
-        if unique is not None:
-            uniqueness = uniqueness_mod.uniqueness_to_numpy(uniqueness_mod.unique_batch(frac_d, lattice_d, off_d, types_d, unique))
-        found = found_d = None
-        if find_symmetry is not None:
-            found_d = eng.find_symmetry(frac_d, lattice_d, off_d, types_d, find_symmetry)
-            found = symmetry_search.result_to_numpy(found_d)
-        symmetrized = None
-        if symmetrize is not None:  # (found_d: the search's launch is shared)
-            symmetrized = symmetrize_mod.sample_arrays(symmetrize_mod.result_to_numpy(
-                eng.symmetrize(frac_d, lattice_d, off_d, types_d, symmetrize, found_d)))
-        reduced = reduced_d = None
-        if reduce_cell is not None:
-            reduced_d = eng.reduce_cells(frac_d, lattice_d, off_d, types_d, reduce_cell)
-            reduced = cell_reduction.result_to_numpy(reduced_d)
-            reduced = cell_reduction.sample_arrays(reduced, atomic_number_indexes_to_atomic_numbers(z_table, reduced["types"]))
-        conventional = None
-        if conventional_cell is not None:  # (reduced_d: the reduction's launch is shared)
-            conventional = conventional_mod.result_to_numpy(eng.conventional_cell(frac_d, lattice_d, off_d, types_d, conventional_cell, reduced_d))
-            conventional = conventional_mod.sample_arrays(conventional, atomic_number_indexes_to_atomic_numbers(z_table, conventional["types"]))
-        atomic_numbers = atomic_number_indexes_to_atomic_numbers(z_table, types_d.cpu().numpy())
-        match = None
-        if match_to is not None:  # (the atomic numbers are the species ids the targets carry: one small upload)
-            species = np.rint(np.asarray(atomic_numbers).reshape(-1)).astype(np.int32)
-            match = structure_match.sample_arrays(structure_match.match_batches(
-                (frac_d, lattice_d, off_d, torch.as_tensor(species, device=frac_d.device)), num_atoms.numpy(), species, *match_to))
-        coordinated = coordinated_d = None
-        if coordination is not None:
-            coordinated_d = eng.coordination(frac_d, lattice_d, off_d, coordination)
-            coordinated = coordination_mod.sample_arrays(coordination_mod.result_to_numpy(coordinated_d), atomic_numbers)
-        ordered = None
-        if bond_order is not None:  # (coordinated_d: the search's launch is shared)
-            ordered = bond_order_mod.sample_arrays(bond_order_mod.result_to_numpy(
-                eng.bond_order(frac_d, lattice_d, off_d, bond_order, coordinated_d)), atomic_numbers)
-        return SampleResult(num_atoms=num_atoms.numpy(), frac_x=frac_d.cpu().numpy().astype(np.float64),
-                            atomic_numbers=atomic_numbers, lattice=lattice_d.cpu().numpy().astype(np.float64), info=info,
-                            metrics=metrics, uniqueness=uniqueness, symmetry=found, reduced=reduced,
-                            symmetrized=symmetrized, match=match, conventional=conventional, coordination=coordinated, bond_order=ordered,
-                            crystal_keys=np.array(crystal_keys, dtype=np.int64) if crystal_keys is not None else None)
+        if buf.guide is not None:
+            info = dict(info or {}, contact_guidance=guidance_mod.info_to_numpy(buf.guide[1]))
+        if visualization_setting != VisualizationSetting.NONE:
+            frame("_final")
+        # the instruments, by table: each reads the final state where it is and fills its own field
+        atomic_numbers = atomic_number_indexes_to_atomic_numbers(z_table, buf.types_d.cpu().numpy())
+        final = instruments.DeviceState(eng, buf.frac_d, buf.lattice_d, buf.off_d, buf.types_d, z_table, plan.num_atoms.numpy(),
+                                        atomic_numbers, mask_type=-1 if constant_atoms is not None else plan.S - 1)
+        fields = {e.field: e.run(final, plan.instruments[e.keyword]) if plan.instruments[e.keyword] is not None else None
+                  for e in instruments.TABLE}
+        return SampleResult(num_atoms=plan.num_atoms.numpy(), frac_x=buf.frac_d.cpu().numpy().astype(np.float64),
+                            atomic_numbers=atomic_numbers, lattice=buf.lattice_d.cpu().numpy().astype(np.float64), info=info,
+                            crystal_keys=np.array(plan.crystal_keys, dtype=np.int64) if plan.crystal_keys is not None else None,
+                            **fields)
+
+    def _starting_state(self, plan, model, initial_state, constant_atoms, condition, seed):
+        """(the SamplerState the run starts from, constant_atoms as the run reads it): the draw of draw_initial_state, or the
+        given state with its species replaced by the ones to hold when those are given (nothing is drawn)."""
+        if initial_state is None:
+            state = self.draw_initial_state(plan.num_atoms_per_sample, plan.B, num_atomic_states=plan.S, constant_atoms=constant_atoms,
+                                            lattice_system=plan.lattice_system, condition=condition, specs=plan.specs, seed=seed,
+                                            crystal_keys=plan.crystal_keys, model=model)
+        else:
+            state = initial_state
+            if constant_atoms is False:
+                constant_atoms = None
+            if constant_atoms is not None and constant_atoms is not True:  # (its size: sample_plan.resolve)
+                held = torch.as_tensor(constant_atoms).reshape(-1).long()
+                state = inversion.SamplerState(state.frac_x, held.numpy(), state.lengths, state.angles, state.num_atoms, state.t,
+                                               state.length_tie)
+        if plan.allow_rows is not None and constant_atoms is True:  # the state's own species are held
+            species_mod.check_held(plan.allow_rows, plan.crystal_of, np.asarray(state.species), np.ones(plan.N, bool),
+                                   "constant_atoms=True")
+        return state, constant_atoms

@@ -5,16 +5,83 @@ LOCAL ones, which describe each atom's surroundings (the coordination environmen
 is built on a LOCAL one's neighbour lists (the bond angles and order parameters); TABLE is EVERY and SHELL, the whole table, and
 KEYWORDS maps a sample() keyword to its entry.  An entry holds what the
 instruments differ in for the host-side plumbing: the file layer (inference/process_generated_crystals.py), the batch driver
-(generate.py) and `python -m arreau_amd.screen` loop over it.  The stored keys are the owning modules' own tuples.  Needs numpy
-alone at import, as the modules do."""
-from dataclasses import dataclass
+(generate.py) and `python -m arreau_amd.screen` loop over it, and so does DiffusionLoss.sample, which calls every asked-for
+entry's `run` on the final device state (DeviceState) in table order: an entry that shares a launch comes after the entry that
+makes it.  The stored keys are the owning modules' own tuples.  Needs numpy alone at import, as the modules do."""
+from dataclasses import dataclass, field
 from types import ModuleType
-from typing import Optional
+from typing import Callable, Optional
 
 import numpy as np
 
 from . import (bond_order, cell_reduction, conventional_cell, coordination, screening, structure_match, symmetrize, symmetry_search,
                uniqueness)
+from .tools.atomic_number_table import atomic_number_indexes_to_atomic_numbers
+
+
+@dataclass
+class DeviceState:
+    """What an entry's `run` reads: the final state of a sample() call where it lies on the device, and `launched`, the device
+    results of this run's launches that a later entry shares (keyed by the keyword of the entry that made them)."""
+    eng: object
+    frac: object          # [N,3] f32
+    lattice: object       # [B,3,3] f32
+    offsets: object       # [B+1] i32
+    types: object         # [N] i32 class indices
+    z_table: object
+    num_atoms: np.ndarray
+    atomic_numbers: np.ndarray  # of `types`
+    mask_type: int        # what the screen takes for the mask state: S - 1, or -1 when the species were held constant
+    launched: dict = field(default_factory=dict)
+
+    @property
+    def batch(self):
+        return self.frac, self.lattice, self.offsets, self.types
+
+
+def _run_screen(s, params):
+    return screening.metrics_to_numpy(s.eng.screen(*s.batch, params.with_mask_type(s.mask_type)))
+
+
+def _run_unique(s, params):
+    return uniqueness.uniqueness_to_numpy(uniqueness.unique_batch(*s.batch, params))
+
+
+def _run_find_symmetry(s, params):
+    s.launched["find_symmetry"] = s.eng.find_symmetry(*s.batch, params)
+    return symmetry_search.result_to_numpy(s.launched["find_symmetry"])
+
+
+def _run_reduce_cell(s, params):
+    s.launched["reduce_cell"] = s.eng.reduce_cells(*s.batch, params)
+    reduced = cell_reduction.result_to_numpy(s.launched["reduce_cell"])
+    return cell_reduction.sample_arrays(reduced, atomic_number_indexes_to_atomic_numbers(s.z_table, reduced["types"]))
+
+
+def _run_symmetrize(s, params):  # (the search's launch is shared)
+    return symmetrize.sample_arrays(symmetrize.result_to_numpy(s.eng.symmetrize(*s.batch, params, s.launched.get("find_symmetry"))))
+
+
+def _run_match(s, params):  # (the atomic numbers are the species ids the targets carry: one small upload)
+    import torch
+    species = np.rint(np.asarray(s.atomic_numbers).reshape(-1)).astype(np.int32)
+    return structure_match.sample_arrays(structure_match.match_batches(
+        (s.frac, s.lattice, s.offsets, torch.as_tensor(species, device=s.frac.device)), s.num_atoms, species, *params))
+
+
+def _run_conventional_cell(s, params):  # (the reduction's launch is shared)
+    found = conventional_cell.result_to_numpy(s.eng.conventional_cell(*s.batch, params, s.launched.get("reduce_cell")))
+    return conventional_cell.sample_arrays(found, atomic_number_indexes_to_atomic_numbers(s.z_table, found["types"]))
+
+
+def _run_coordination(s, params):
+    s.launched["coordination"] = s.eng.coordination(s.frac, s.lattice, s.offsets, params)
+    return coordination.sample_arrays(coordination.result_to_numpy(s.launched["coordination"]), s.atomic_numbers)
+
+
+def _run_bond_order(s, params):  # (the coordination launch is shared)
+    return bond_order.sample_arrays(bond_order.result_to_numpy(
+        s.eng.bond_order(s.frac, s.lattice, s.offsets, params, s.launched.get("coordination"))), s.atomic_numbers)
 
 
 @dataclass(frozen=True)
@@ -34,6 +101,7 @@ class Instrument:
     shapes: tuple = ()    # ... and the (key, requirement) pairs that differ from it
     carried: bool = True  # concat_results / select_crystals carry it (uniqueness indexes into the whole set: they do not)
     stats_from: Optional[str] = None  # stats_of reads this one array (None: the dict)
+    run: Optional[Callable] = None    # run(DeviceState, resolved parameters) -> the dict of SampleResult.<field>: sample()'s launch
 
     def stats_of(self, arrays, rank=0):
         return self.module.stats_of(arrays if self.stats_from is None else arrays[self.stats_from], rank)
@@ -43,31 +111,31 @@ _SYMPREC = (("symprec", "symprec"),)
 INSTRUMENTS = (
     Instrument("screen", "metrics", "screen_", "screen_stats", screening, screening.STORED_KEYS, "ScreenCriteria",
                (("min_distance", "min_distance"), ("min_volume", "min_volume"), ("search_radius", "search_radius")), "screen criteria",
-               shape=(), shapes=(("pair", (5,)),), stats_from="flags"),
+               shape=(), shapes=(("pair", (5,)),), stats_from="flags", run=_run_screen),
     Instrument("unique", "uniqueness", "unique_", "unique_stats", uniqueness, uniqueness.UNIQUE_KEYS, "FingerprintParams",
                (("r_max", "fp_r_max"), ("sigma", "fp_sigma"), ("tolerance", "fp_tolerance")), "fingerprint parameters",
-               shape=(), carried=False),
+               shape=(), carried=False, run=_run_unique),
     Instrument("find_symmetry", "symmetry", "sym_", "symmetry_stats", symmetry_search, symmetry_search.SYM_KEYS, "SymmetrySearchParams",
-               _SYMPREC, "symmetry search", shape=1, shapes=(("ops_rotation", 2), ("ops_translation", 3), ("ops_residual", 2))),
+               _SYMPREC, "symmetry search", shape=1, shapes=(("ops_rotation", 2), ("ops_translation", 3), ("ops_residual", 2)), run=_run_find_symmetry),
     Instrument("reduce_cell", "reduced", "reduced_", "reduce_stats", cell_reduction, cell_reduction.REDUCED_KEYS, "CellReductionParams",
-               _SYMPREC, "cell reduction", atom_keys=cell_reduction.PER_ATOM_KEYS, atoms_from="num_atoms"),
+               _SYMPREC, "cell reduction", atom_keys=cell_reduction.PER_ATOM_KEYS, atoms_from="num_atoms", run=_run_reduce_cell),
     Instrument("symmetrize", "symmetrized", "symmetrized_", "symmetrize_stats", symmetrize, symmetrize.SYMMETRIZED_KEYS,
-               "SymmetrizeParams", _SYMPREC, "symmetrize", atom_keys=symmetrize.ATOM_KEYS),
+               "SymmetrizeParams", _SYMPREC, "symmetrize", atom_keys=symmetrize.ATOM_KEYS, run=_run_symmetrize),
     Instrument("match_to", "match", "match_", "match_stats", structure_match, structure_match.MATCH_KEYS, "StructureMatchParams",
-               (("ltol", "ltol"), ("angle_tol", "angle_tol"), ("stol", "stol"), ("assignment", "assignment")), "structure match", atom_keys=structure_match.ATOM_KEYS),
+               (("ltol", "ltol"), ("angle_tol", "angle_tol"), ("stol", "stol"), ("assignment", "assignment")), "structure match", atom_keys=structure_match.ATOM_KEYS, run=_run_match),
 )
 # what is built on the six above: in a crystals file, in the summaries and on the command lines after them
 DERIVED = (
     Instrument("conventional_cell", "conventional", "conventional_", "conventional_stats", conventional_cell,
                conventional_cell.CONVENTIONAL_KEYS, "ConventionalCellParams", _SYMPREC, "conventional cell",
-               atom_keys=conventional_cell.ATOM_KEYS, atoms_from="num_atoms"),
+               atom_keys=conventional_cell.ATOM_KEYS, atoms_from="num_atoms", run=_run_conventional_cell),
 )
 ALL = INSTRUMENTS + DERIVED
 # what looks at each atom's surroundings, not at the crystal as a whole: after every other instrument's arrays
 LOCAL = (
     Instrument("coordination", "coordination", "coord_", "coordination_stats", coordination, coordination.STORED_KEYS,
                "CoordinationParams", (("tol", "cn_tol"), ("cutoff", "cn_cutoff")), "coordination", atom_keys=coordination.ATOM_KEYS,
-               shape=(), shapes=(("neighbors", 3),)),
+               shape=(), shapes=(("neighbors", 3),), run=_run_coordination),
 )
 EVERY = ALL + LOCAL
 BY_KEYWORD = {e.keyword: e for e in EVERY}
@@ -76,7 +144,7 @@ SHELL = (
     Instrument("bond_order", "bond_order", "order_", "bond_order_stats", bond_order, bond_order.STORED_KEYS, "BondOrderParams",
                (("tol", "cn_tol"), ("cutoff", "cn_cutoff")), "bond order", atom_keys=bond_order.ATOM_KEYS, shape=(),
                shapes=(("q", (len(bond_order.L_VALUES),)), ("q2", (len(bond_order.L_VALUES),)), ("mean_q", (len(bond_order.L_VALUES),)),
-                       ("angles", (bond_order.ANGLE_BINS,)), ("angle_hist", (bond_order.ANGLE_BINS,)))),
+                       ("angles", (bond_order.ANGLE_BINS,)), ("angle_hist", (bond_order.ANGLE_BINS,))), run=_run_bond_order),
 )
 TABLE = EVERY + SHELL  # the whole table: what the file layer, the batch driver and the screen loop over
 KEYWORDS = {e.keyword: e for e in TABLE}

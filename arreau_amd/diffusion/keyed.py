@@ -56,6 +56,12 @@ def stream_seeds(seed: int, keys) -> np.ndarray:
     return np.array([stream_seed(seed, int(k)) for k in np.asarray(keys).reshape(-1)], dtype=np.uint64)
 
 
+def device_seeds(streams: np.ndarray, device):
+    """The table the keyed exports take: the uint64 stream seeds as the bits of a contiguous int64 tensor [B] on `device`."""
+    import torch
+    return torch.as_tensor(np.asarray(streams, dtype=np.uint64).view(np.int64), device=device).contiguous()
+
+
 def raw_words(stream: int, timestep: int, kind: int, element: int, word3: int = 0):
     """Rule 2: the four raw words of the draw (stream seed, timestep, kind, element, word3)."""
     stream = int(stream)

@@ -10,6 +10,15 @@ import os
 import torch
 
 from . import _hip
+from .diffusion import (bond_order as bond_order_mod, cell_reduction, conventional_cell as conventional_mod,
+                        coordination as coordination_mod, screening, symmetrize as symmetrize_mod, symmetry_search)
+from .diffusion.contact_guidance import INFO_KEYS, ContactGuidance
+from .diffusion.corrector import check_corrector
+from .diffusion.ddim import check_eta
+from .diffusion.keyed import KIND_INIT_FRAC, KIND_INIT_LENGTHS
+from .diffusion.multistep import HISTORY_KEYS, check_multistep
+from .diffusion.resampling import check_resampling
+from .diffusion.species import validate_temperature
 
 
 def _f32(t):
@@ -21,45 +30,71 @@ def _byref(struct):
     return ctypes.byref(struct) if struct is not None else None
 
 
+def _require(label, name, t, shape, dtype, device, message=None):
+    """The tensor contract of the entry points: `t` is a contiguous `dtype` tensor of `shape` (None: any, not empty) on `device`,
+    else ValueError.  Under a label the text names the dtype as torch prints it ("condition: x0 must be a contiguous torch.float32
+    tensor ..."), without one bare ("length_tie must be a contiguous int32 tensor ..."); `message` replaces the text."""
+    if (torch.is_tensor(t) and t.dtype == dtype and t.device == device and t.is_contiguous()
+            and (tuple(t.shape) == tuple(shape) if shape is not None else t.numel() > 0)):
+        return
+    if message is None:
+        who, kind = (f"{label}: {name}", dtype) if label else (name, str(dtype).replace("torch.", ""))
+        message = (f"{who} must be a contiguous {kind} tensor of shape {tuple(shape)} on {device}" if shape is not None
+                   else f"{who} must be a non-empty contiguous {kind} tensor on {device}")
+    raise ValueError(message)
+
+
+# Which export serves an option set of sample_loop: (export, the option that selects it, the option columns it takes after the
+# four common ones -- condition, schedule, corrector, resampling), read top to bottom; the first row whose option is given wins.
+# "common": any of the four common options; the last row is the plain export, which takes none of them (A/B runs against an
+# older library through ARREAU_HIP_LIB call it).  Two irregularities: _eta takes its float by value ("eta") while the species
+# family takes it by pointer ("eta_ref", NULL: none), and _multistep skips the symmetry and eta columns.
+_SPECIES_COLUMNS = ("tie", "sym", "eta_ref", "multistep", "species")
+_LOOP_EXPORTS = (
+    ("arreau_sample_loop_guided", "guidance", _SPECIES_COLUMNS + ("seeds", "guidance")),
+    ("arreau_sample_loop_keyed", "seeds", _SPECIES_COLUMNS + ("seeds",)),
+    ("arreau_sample_loop_species", "species", _SPECIES_COLUMNS),
+    ("arreau_sample_loop_multistep", "multistep", ("tie", "multistep")),
+    ("arreau_sample_loop_sym", "sym", ("tie", "sym")),
+    ("arreau_sample_loop_eta", "eta", ("tie", "eta")),
+    ("arreau_sample_loop_tied", "tie", ("tie",)),
+    ("arreau_sample_loop_resampled", "common", ()),
+    ("arreau_sample_loop", None, None),
+)
+
+
 def screen(frac, lattice, offsets, types=None, criteria=None):
     """The structural screen without an engine (arreau_crystal_screen needs no model): diffusion.screening.screen."""
-    from .diffusion import screening
     return screening.screen(frac, lattice, offsets, types, criteria)
 
 
 def reduce_cells(frac, lattice, offsets, types, params=None):
     """The cell reduction without an engine (arreau_crystal_reduce needs no model): diffusion.cell_reduction.reduce_cells."""
-    from .diffusion import cell_reduction
     return cell_reduction.reduce_cells(frac, lattice, offsets, types, params)
 
 
 def conventional_cell(frac, lattice, offsets, types, params=None, reduced=None):
     """The conventional cells without an engine (arreau_crystal_conventional needs no model): diffusion.conventional_cell.conventional_cell."""
-    from .diffusion import conventional_cell as conventional_mod
     return conventional_mod.conventional_cell(frac, lattice, offsets, types, params, reduced)
 
 
 def coordination(frac, lattice, offsets, params=None):
     """The coordination environments without an engine (arreau_crystal_coordination needs no model): diffusion.coordination.coordination."""
-    from .diffusion import coordination as coordination_mod
     return coordination_mod.coordination(frac, lattice, offsets, params)
 
 
 def bond_order(frac, lattice, offsets, params=None):
     """The bond angles and Steinhardt order parameters without an engine (arreau_crystal_bond_order needs no model): diffusion.bond_order.bond_order."""
-    from .diffusion import bond_order as bond_order_mod
     return bond_order_mod.bond_order(frac, lattice, offsets, params)
 
 
 def symmetrize(frac, lattice, offsets, types, params=None, found=None):
     """The symmetrization without an engine (arreau_crystal_symmetrize needs no model): diffusion.symmetrize.symmetrize."""
-    from .diffusion import symmetrize as symmetrize_mod
     return symmetrize_mod.symmetrize(frac, lattice, offsets, types, params, found)
 
 
 def find_symmetry(frac, lattice, offsets, types, params=None):
     """The symmetry search without an engine (arreau_crystal_symmetry needs no model): diffusion.symmetry_search.find_symmetry."""
-    from .diffusion import symmetry_search
     return symmetry_search.find_symmetry(frac, lattice, offsets, types, params)
 
 
@@ -308,26 +343,22 @@ class HipEngine:
         the last evaluation's energy, contacts and flags per crystal.  Every network evaluation of every step is followed by one
         launch that adds the gradient of the contact penalty to its eps.  The export is the keyed one plus the struct, so without
         `species` the steps run under (every class, temperature 1).  None is the loop without it, through the export it used."""
-        guide = self._guidance_struct(guidance, lengths.shape[0]) if guidance is not None else None
-        if guide is not None and species is None:
-            species = (None, 1.0)
+        N, B = frac.shape[0], lengths.shape[0]
+        guide = self._guidance_struct(guidance, B) if guidance is not None else None
         if crystal_seeds is not None:
-            self._check_seeds(crystal_seeds, lengths.shape[0])
-            if species is None:
-                species = (None, 1.0)
+            self._check_seeds(crystal_seeds, B)
+        if (guide is not None or crystal_seeds is not None) and species is None:
+            species = (None, 1.0)
         if multistep is not None:
-            from .diffusion.multistep import check_multistep
             check_multistep(True, eta=eta, condition=condition, corrector_steps=corrector[0] if corrector is not None else 0,
                             resample_passes=resampling[0] if resampling is not None else 1, symmetry=symmetry)
             eta = None  # (the multistep export takes none: its steps are the eta = 0 steps)
         if eta is not None:
-            from .diffusion.ddim import check_eta
             eta = check_eta(eta)
             if symmetry is not None:
                 raise ValueError("eta is not combined with symmetry tables")
-        res = None
+        res = ts_arr = None
         if resampling is not None:
-            from .diffusion.resampling import check_resampling
             passes, jump = check_resampling(*resampling[:2])
             ts = list(resampling[2]) if len(resampling) > 2 and resampling[2] is not None else None
             if passes > 1:
@@ -337,53 +368,33 @@ class HipEngine:
                 res = _hip.ResamplingC(passes, jump, ctypes.cast(ts_arr, ctypes.POINTER(ctypes.c_int32)) if ts else None,
                                        len(ts) if ts else 0)
         if corrector is not None:
-            from .diffusion.corrector import check_corrector
             corrector = check_corrector(*corrector)
-        N, B = frac.shape[0], lengths.shape[0]
         ws = self.workspace(N, B)
         args = (self._handle, _hip.ptr(frac), _hip.ptr(types), _hip.ptr(lengths), _hip.ptr(angles), _hip.ptr(offsets), B, N,
                 int(t_start), int(n_steps), int(seed) & (2 ** 64 - 1), _hip.ptr(const_types), _hip.ptr(fixed_lengths),
                 _hip.ptr(lattice_out), _hip.ptr(ws), ws.numel(), int(bool(use_graph)))
         sched = None
         if next_table is not None:
-            T = int(self.cfg.num_timesteps)
-            if (tuple(next_table.shape) != (T + 1,) or next_table.dtype != torch.int32 or next_table.device != self.device
-                    or not next_table.is_contiguous()):
-                raise ValueError(f"next_table must be a contiguous int32 tensor of shape ({T + 1},) on {self.device}")
+            _require("", "next_table", next_table, (int(self.cfg.num_timesteps) + 1,), torch.int32, self.device)
             sched = _hip.SampleScheduleC(_hip.ptr(next_table).value, float(lattice_clipmax))
         cond = self._condition_struct(condition, N, B) if condition is not None else None
         corr = _hip.CorrectorC(corrector[0], corrector[1]) if corrector is not None else None
-        if length_tie is not None:
-            self._check_tie(length_tie, B)
-        opts = (_byref(cond), _byref(sched), _byref(corr), _byref(res))
-        if species is not None:  # whichever loop the options name, under species control
-            eta_c = ctypes.c_float(eta) if eta is not None else None
-            name = "arreau_sample_loop_species"
-            opts += (_hip.ptr(length_tie), _byref(self._symmetry_struct(symmetry, N) if symmetry is not None else None), _byref(eta_c),
-                     _byref(self._multistep_struct(multistep, N, B) if multistep is not None else None),
-                     _byref(self._species_struct(species, B)))
-            if guide is not None:  # contact guidance: the keyed loop (its table may be NULL) with the guidance struct
-                name, opts = "arreau_sample_loop_guided", opts + (_hip.ptr(crystal_seeds), ctypes.byref(guide))
-            elif crystal_seeds is not None:  # keyed sampling: the same loop with the table of stream seeds
-                name, opts = "arreau_sample_loop_keyed", opts + (_hip.ptr(crystal_seeds),)
-        elif multistep is not None:
-            name, opts = "arreau_sample_loop_multistep", opts + (_hip.ptr(length_tie), _byref(self._multistep_struct(multistep, N, B)))
-        elif symmetry is not None:
-            name, opts = "arreau_sample_loop_sym", opts + (_hip.ptr(length_tie), _byref(self._symmetry_struct(symmetry, N)))
-        elif eta is not None:
-            name, opts = "arreau_sample_loop_eta", opts + (_hip.ptr(length_tie), ctypes.c_float(eta))
-        elif length_tie is not None:
-            name, opts = "arreau_sample_loop_tied", opts + (_hip.ptr(length_tie),)
-        elif any(o is not None for o in opts):
-            name = "arreau_sample_loop_resampled"
-        else:  # (the plain entry point: A/B runs against an older library through ARREAU_HIP_LIB call it)
-            name, opts = "arreau_sample_loop", ()
+        self._check_tie(length_tie, B)
+        common = (_byref(cond), _byref(sched), _byref(corr), _byref(res))
+        eta_c = ctypes.c_float(eta) if eta is not None else None
+        columns = {"tie": _hip.ptr(length_tie), "eta": eta_c, "eta_ref": _byref(eta_c), "seeds": _hip.ptr(crystal_seeds),
+                   "sym": _byref(self._symmetry_struct(symmetry, N) if symmetry is not None else None),
+                   "multistep": _byref(self._multistep_struct(multistep, N, B) if multistep is not None else None),
+                   "species": _byref(self._species_struct(species, B) if species is not None else None), "guidance": _byref(guide)}
+        given = {"guidance": guide, "seeds": crystal_seeds, "species": species, "multistep": multistep, "sym": symmetry, "eta": eta,
+                 "tie": length_tie, "common": next((o for o in common if o is not None), None)}
+        name, _, takes = next(row for row in _LOOP_EXPORTS if row[1] is None or given[row[1]] is not None)
+        opts = common + tuple(columns[c] for c in takes) if takes is not None else ()
         _hip.check(getattr(_hip.lib(), name)(*args, *opts, _hip.stream_ptr(self.device)), name)
 
     def _guidance_struct(self, guidance, B):
         """arreau_contact_guidance of a ContactGuidance or of the pair (ContactGuidance, info), with the info arrays' shape, dtype
         and device checked."""
-        from .diffusion.contact_guidance import INFO_KEYS, ContactGuidance
         params, info = guidance if isinstance(guidance, tuple) else (guidance, None)
         if not isinstance(params, ContactGuidance):
             raise ValueError(f"guidance must be a ContactGuidance or the pair (ContactGuidance, info), got {guidance!r}")
@@ -392,11 +403,8 @@ class HipEngine:
             if not isinstance(info, dict) or set(info) != set(INFO_KEYS):
                 raise ValueError(f"guidance info: expected a dict with exactly the keys {INFO_KEYS}")
             for q, name in enumerate(INFO_KEYS):
-                t, dtype = info[name], torch.float32 if name == "energy" else torch.int32
-                if (not torch.is_tensor(t) or tuple(t.shape) != (B,) or t.dtype != dtype or t.device != self.device
-                        or not t.is_contiguous()):
-                    raise ValueError(f"guidance info: {name} must be a contiguous {dtype} tensor of shape ({B},) on {self.device}")
-                ptrs[q] = _hip.ptr(t).value
+                _require("guidance info", name, info[name], (B,), torch.float32 if name == "energy" else torch.int32, self.device)
+                ptrs[q] = _hip.ptr(info[name]).value
         return _hip.ContactGuidanceC(params.min_distance, params.weight, params.max_shells, *ptrs)
 
     def contact_guidance_step(self, frac, lattice, t_crystal, offsets, eps, guidance):
@@ -408,8 +416,7 @@ class HipEngine:
         for name, t, shape, dtype in (("frac", frac, (N, 3), torch.float32), ("lattice", lattice, (B, 3, 3), torch.float32),
                                       ("t_crystal", t_crystal, (B,), torch.int32), ("offsets", offsets, (B + 1,), torch.int32),
                                       ("eps", eps, (N, 3), torch.float32)):
-            if tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device or not t.is_contiguous():
-                raise ValueError(f"contact_guidance_step: {name} must be a contiguous {dtype} tensor of shape {shape} on {self.device}")
+            _require("contact_guidance_step", name, t, shape, dtype, self.device)
         _hip.check(_hip.lib().arreau_contact_guidance_step(
             self._handle, _hip.ptr(frac), _hip.ptr(lattice), _hip.ptr(t_crystal), _hip.ptr(offsets), B, N, _hip.ptr(eps),
             ctypes.byref(guide), _hip.stream_ptr(self.device)), "arreau_contact_guidance_step")
@@ -428,32 +435,25 @@ class HipEngine:
 
     def _species_struct(self, species, B):
         """arreau_species_control of the pair (allow, temperature), with the rows' shape, dtype and device checked."""
-        from .diffusion.species import validate_temperature
         allow, tau = species
         tau = validate_temperature(tau)
-        if allow is not None and (not torch.is_tensor(allow) or tuple(allow.shape) != (B, 4) or allow.dtype != torch.int32
-                                  or allow.device != self.device or not allow.is_contiguous()):
-            raise ValueError(f"species control: allow must be a contiguous int32 tensor of shape ({B}, 4) on {self.device}")
+        if allow is not None:
+            _require("", "species control: allow", allow, (B, 4), torch.int32, self.device)
         return _hip.SpeciesControlC(_hip.ptr(allow).value if allow is not None else None, tau)
 
     def _multistep_struct(self, history, N, B):
         """arreau_multistep of the dict of history tensors of multistep.allocate_history, with shapes, dtypes and device checked."""
-        from .diffusion.multistep import HISTORY_KEYS
         if not isinstance(history, dict) or set(history) != set(HISTORY_KEYS):
             raise ValueError(f"multistep history: expected a dict with exactly the keys {HISTORY_KEYS}")
         want = {"hist_eps": ((N, 3), torch.float32), "hist_x0": ((B, 3), torch.float32), "hist_t_atom": ((N,), torch.int32),
                 "hist_t_len": ((B,), torch.int32)}
         for n in HISTORY_KEYS:
-            t, (shape, dtype) = history[n], want[n]
-            if (not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device
-                    or not t.is_contiguous()):
-                raise ValueError(f"multistep history: {n} must be a contiguous {dtype} tensor of shape {shape} on {self.device}")
+            _require("multistep history", n, history[n], *want[n], self.device)
         return _hip.MultistepC(*[_hip.ptr(history[n]).value for n in HISTORY_KEYS])
 
     def _check_seeds(self, crystal_seeds, B):
-        if (not torch.is_tensor(crystal_seeds) or tuple(crystal_seeds.shape) != (B,) or crystal_seeds.dtype != torch.int64
-                or crystal_seeds.device != self.device or not crystal_seeds.is_contiguous()):
-            raise ValueError(f"crystal_seeds must be a contiguous int64 tensor of shape ({B},) on {self.device} (the uint64 stream seeds)")
+        _require("", "crystal_seeds", crystal_seeds, (B,), torch.int64, self.device,
+                 f"crystal_seeds must be a contiguous int64 tensor of shape ({B},) on {self.device} (the uint64 stream seeds)")
 
     def philox_fill_crystals(self, crystal_seeds, offsets, timestep, kind, word3=0, per_atom_width=0, per_crystal_width=0, raw=False):
         """The keyed draws written out in batch layout (arreau_philox_fill_crystals): per_atom_width = w gives [N, w] (row of atom a
@@ -474,14 +474,12 @@ class HipEngine:
 
     def keyed_initial_draws(self, crystal_seeds, offsets):
         """Rule 3 of keyed sampling: the standard normals of the initial lengths [B,3] (kind 13) and positions [N,3] (kind 14)."""
-        from .diffusion.keyed import KIND_INIT_FRAC, KIND_INIT_LENGTHS
         return (self.philox_fill_crystals(crystal_seeds, offsets, 0, KIND_INIT_LENGTHS, per_crystal_width=3),
                 self.philox_fill_crystals(crystal_seeds, offsets, 0, KIND_INIT_FRAC, per_atom_width=3))
 
     def _check_tie(self, length_tie, B):
-        if (tuple(length_tie.shape) != (B,) or length_tie.dtype != torch.int32 or length_tie.device != self.device
-                or not length_tie.is_contiguous()):
-            raise ValueError(f"length_tie must be a contiguous int32 tensor of shape ({B},) on {self.device}")
+        if length_tie is not None:
+            _require("", "length_tie", length_tie, (B,), torch.int32, self.device)
 
     def _symmetry_struct(self, tables, N):
         """arreau_symmetry of the dict of device tables of symmetry.device_arrays, with shapes, dtypes and device checked."""
@@ -490,10 +488,8 @@ class HipEngine:
         if missing or set(tables) - set(names):
             raise ValueError(f"symmetry tables: expected exactly {names}")
         for n in names:
-            t = tables[n]
-            want = torch.float32 if n in ("rot", "rot_inv", "trans") else torch.int32
-            if t.dtype != want or t.device != self.device or not t.is_contiguous() or t.numel() == 0:
-                raise ValueError(f"symmetry tables: {n} must be a non-empty contiguous {want} tensor on {self.device}")
+            _require("symmetry tables", n, tables[n], None, torch.float32 if n in ("rot", "rot_inv", "trans") else torch.int32,
+                     self.device)
         for n in ("leader", "op", "orbit"):
             if tuple(tables[n].shape) != (N,):
                 raise ValueError(f"symmetry tables: {n} must have shape ({N},)")
@@ -512,18 +508,15 @@ class HipEngine:
         for timestep t_start, in place.  `crystal_seeds` (with `offsets`): keyed sampling (arreau_condition_initial_state_keyed)."""
         N, B = frac.shape[0], lengths.shape[0]
         cond = self._condition_struct(condition, N, B)
+        name, offs, keyed = "arreau_condition_initial_state", (), ()
         if crystal_seeds is not None:
             self._check_seeds(crystal_seeds, B)
             if offsets is None:
                 raise ValueError("condition_initial_state: crystal_seeds need the crystal offsets")
-            _hip.check(_hip.lib().arreau_condition_initial_state_keyed(
-                self._handle, _hip.ptr(frac), _hip.ptr(types), _hip.ptr(lengths), _hip.ptr(offsets), B, N, int(t_start),
-                int(seed) & (2 ** 64 - 1), ctypes.byref(cond), _hip.ptr(crystal_seeds), _hip.stream_ptr(self.device)),
-                "arreau_condition_initial_state_keyed")
-            return
-        _hip.check(_hip.lib().arreau_condition_initial_state(
-            self._handle, _hip.ptr(frac), _hip.ptr(types), _hip.ptr(lengths), B, N, int(t_start), int(seed) & (2 ** 64 - 1),
-            ctypes.byref(cond), _hip.stream_ptr(self.device)), "arreau_condition_initial_state")
+            name, offs, keyed = name + "_keyed", (_hip.ptr(offsets),), (_hip.ptr(crystal_seeds),)
+        _hip.check(getattr(_hip.lib(), name)(
+            self._handle, _hip.ptr(frac), _hip.ptr(types), _hip.ptr(lengths), *offs, B, N, int(t_start), int(seed) & (2 ** 64 - 1),
+            ctypes.byref(cond), *keyed, _hip.stream_ptr(self.device)), name)
 
     def _condition_struct(self, condition, N, B):
         """arreau_sample_condition of a dict of device tensors, with their shapes, dtypes and device checked."""
@@ -537,35 +530,31 @@ class HipEngine:
             t = condition.get(name)
             if t is None:
                 continue
-            if tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device or not t.is_contiguous():
-                raise ValueError(f"condition: {name} must be a contiguous {dtype} tensor of shape {shape} on {self.device}")
+            _require("condition", name, t, shape, dtype, self.device)
             setattr(c, name, _hip.ptr(t))
         return c
+
+    def _philox_fill(self, name, n, raw, *key):
+        """One of the philox_fill exports: `key`, then n, the normals or uniforms out [n] and, with raw, the words [n, 4]."""
+        out = torch.empty(n, device=self.device, dtype=torch.float32)
+        words = torch.empty((n, 4), device=self.device, dtype=torch.int32) if raw else None
+        _hip.check(getattr(_hip.lib(), name)(*key, int(n), _hip.ptr(out), _hip.ptr(words), _hip.stream_ptr(self.device)), name)
+        return (out, words) if raw else out
 
     def philox_fill(self, seed, timestep, kind, n, raw=False):
         """The sampler's in-kernel noise written out (arreau_philox_fill): kinds 0/1 (and 3/4, the draws of conditioned
         sampling) standard normal, 2 uniform [0,1)."""
-        out = torch.empty(n, device=self.device, dtype=torch.float32)
-        words = torch.empty((n, 4), device=self.device, dtype=torch.int32) if raw else None
-        _hip.check(_hip.lib().arreau_philox_fill(int(seed) & (2 ** 64 - 1), int(timestep), int(kind), int(n), _hip.ptr(out),
-                                                 _hip.ptr(words), _hip.stream_ptr(self.device)), "arreau_philox_fill")
-        return (out, words) if raw else out
+        return self._philox_fill("arreau_philox_fill", n, raw, int(seed) & (2 ** 64 - 1), int(timestep), int(kind))
 
     def philox_fill_word(self, seed, timestep, kind, word3, n, raw=False):
         """arreau_philox_fill with the counter's fourth word (arreau_philox_fill_word): kind 5 with word3 = j is the Langevin
         noise of the loop's j-th corrector move at `timestep`."""
-        out = torch.empty(n, device=self.device, dtype=torch.float32)
-        words = torch.empty((n, 4), device=self.device, dtype=torch.int32) if raw else None
-        _hip.check(_hip.lib().arreau_philox_fill_word(int(seed) & (2 ** 64 - 1), int(timestep), int(kind), int(word3) & (2 ** 32 - 1),
-                                                      int(n), _hip.ptr(out), _hip.ptr(words), _hip.stream_ptr(self.device)),
-                   "arreau_philox_fill_word")
-        return (out, words) if raw else out
+        return self._philox_fill("arreau_philox_fill_word", n, raw, int(seed) & (2 ** 64 - 1), int(timestep), int(kind), int(word3) & (2 ** 32 - 1))
 
     def corrector_step(self, frac, t_crystal, offsets, eps, z_frac, snr, condition=None):
         """One Langevin corrector move on frac [N,3] in place (arreau_corrector_step): per crystal at timestep t_crystal[b],
         from the network's eps [N,3] and the caller's standard-normal z_frac [N,3].  `condition`: as in sample_loop; its
         position mask keeps those atoms fixed and out of the norms."""
-        from .diffusion.corrector import check_corrector
         _, snr = check_corrector(1, snr)
         N, B = frac.shape[0], t_crystal.shape[0]
         cond = self._condition_struct(condition, N, B) if condition is not None else None
@@ -618,10 +607,9 @@ class HipEngine:
         drawn ones.  Returns diffusion_noise's dict plus `t` (int32 [B], the timesteps used)."""
         dev = self.device
         N, B = frac0.shape[0], lattice0.shape[0]
-        if crystal_ids.dtype != torch.int64 or crystal_ids.shape != (B,) or crystal_ids.device != dev:
-            raise ValueError("crystal_ids must be an int64 tensor [B] on the engine's device")
-        if copy is not None and (copy.dtype != torch.int32 or copy.shape != (B,) or copy.device != dev):
-            raise ValueError("copy must be an int32 tensor [B] on the engine's device")
+        _require("", "crystal_ids", crystal_ids, (B,), torch.int64, dev, "crystal_ids must be an int64 tensor [B] on the engine's device")
+        if copy is not None:
+            _require("", "copy", copy, (B,), torch.int32, dev, "copy must be an int32 tensor [B] on the engine's device")
         f32 = dict(device=dev, dtype=torch.float32)
         t = torch.empty(B, device=dev, dtype=torch.int32) if t_crystal is None else t_crystal
         out = dict(noisy_frac=torch.empty((N, 3), **f32), target_eps=torch.empty((N, 3), **f32),
@@ -638,12 +626,7 @@ class HipEngine:
 
     def philox_fill_keyed(self, seed, timestep, kind, crystal_id, n, raw=False):
         """The keyed draws written out (arreau_philox_fill_keyed): kinds 10 / 12 standard normal, 9 / 11 uniform [0,1)."""
-        out = torch.empty(n, device=self.device, dtype=torch.float32)
-        words = torch.empty((n, 4), device=self.device, dtype=torch.int32) if raw else None
-        _hip.check(_hip.lib().arreau_philox_fill_keyed(int(seed) & (2 ** 64 - 1), int(timestep), int(kind), int(crystal_id) & (2 ** 32 - 1),
-                                                       int(n), _hip.ptr(out), _hip.ptr(words), _hip.stream_ptr(self.device)),
-                   "arreau_philox_fill_keyed")
-        return (out, words) if raw else out
+        return self._philox_fill("arreau_philox_fill_keyed", n, raw, int(seed) & (2 ** 64 - 1), int(timestep), int(kind), int(crystal_id) & (2 ** 32 - 1))
 
     def loss_row_table(self, n_rows):
         """A zeroed table of n_rows arreau_loss_row (int32 [n_rows, 6]; rows_to_fields views it)."""
@@ -661,8 +644,7 @@ class HipEngine:
         grad_logits, grad_lengths) or Nones, terms [N,3])."""
         dev = self.device
         N, B = pred_eps.shape[0], pred_lengths.shape[0]
-        if row_index.dtype != torch.int64 or row_index.shape != (B,) or row_index.device != dev:
-            raise ValueError("row_index must be an int64 tensor [B] on the engine's device")
+        _require("", "row_index", row_index, (B,), torch.int64, dev, "row_index must be an int64 tensor [B] on the engine's device")
         if rows.dtype != torch.int32 or rows.dim() != 2 or rows.shape[1] != self.ROW_WORDS or rows.device != dev:
             raise ValueError("rows must come from loss_row_table")
         f32 = dict(device=dev, dtype=torch.float32)
@@ -908,8 +890,7 @@ class HipEngine:
                          u_types, lattice_out, length_tie, symmetry, lattice_clipmax=0.999):
         """reverse_step_tied with space-group symmetry (arreau_reverse_step_sym): `symmetry` the dict of symmetry.device_arrays
         (None: the tied step); length_tie may be None."""
-        if length_tie is not None:
-            self._check_tie(length_tie, lengths.shape[0])
+        self._check_tie(length_tie, lengths.shape[0])
         sym = self._symmetry_struct(symmetry, frac.shape[0]) if symmetry is not None else None
         self._reverse_step_to("arreau_reverse_step_sym", frac, types, lengths, angles, t_crystal, s_crystal, offsets, eps, logits, len0,
                               z_lattice, z_frac, u_types, lattice_out, lattice_clipmax, _hip.ptr(length_tie), _byref(sym))
@@ -918,10 +899,8 @@ class HipEngine:
                          u_types, lattice_out, eta, length_tie=None, lattice_clipmax=0.999):
         """reverse_step_tied as the DDIM-style step (arreau_reverse_step_eta): `eta` in [0, 1] scales the noise of positions and
         lengths; length_tie may be None; at eta = 0 z_lattice and z_frac are not read and may be None."""
-        from .diffusion.ddim import check_eta
         eta = check_eta(eta)
-        if length_tie is not None:
-            self._check_tie(length_tie, lengths.shape[0])
+        self._check_tie(length_tie, lengths.shape[0])
         self._reverse_step_to("arreau_reverse_step_eta", frac, types, lengths, angles, t_crystal, s_crystal, offsets, eps, logits, len0,
                               z_lattice, z_frac, u_types, lattice_out, lattice_clipmax, _hip.ptr(length_tie), ctypes.c_float(eta))
 
@@ -929,8 +908,7 @@ class HipEngine:
                                history, length_tie=None, lattice_clipmax=0.999):
         """reverse_step_eta at eta = 0 as the second-order multistep step (arreau_reverse_step_multistep): `history` the dict of
         multistep.allocate_history, read and overwritten; no position or length draw is read; length_tie may be None."""
-        if length_tie is not None:
-            self._check_tie(length_tie, lengths.shape[0])
+        self._check_tie(length_tie, lengths.shape[0])
         ms = self._multistep_struct(history, frac.shape[0], lengths.shape[0])
         self._reverse_step_to("arreau_reverse_step_multistep", frac, types, lengths, angles, t_crystal, s_crystal, offsets, eps, logits,
                               len0, None, None, u_types, lattice_out, lattice_clipmax, _hip.ptr(length_tie), _byref(ms))
@@ -942,14 +920,36 @@ class HipEngine:
         control (arreau_reverse_step_species): `species` the pair (allow, temperature) of sample_loop_species.  u_types may be
         None at a temperature of 0; z_lattice and z_frac at eta = 0 or with multistep."""
         B, N = lengths.shape[0], frac.shape[0]
-        if length_tie is not None:
-            self._check_tie(length_tie, B)
+        self._check_tie(length_tie, B)
         sym = self._symmetry_struct(symmetry, N) if symmetry is not None else None
         ms = self._multistep_struct(multistep, N, B) if multistep is not None else None
         eta_c = ctypes.c_float(float(eta)) if eta is not None else None
         self._reverse_step_to("arreau_reverse_step_species", frac, types, lengths, angles, t_crystal, s_crystal, offsets, eps, logits,
                               len0, z_lattice, z_frac, u_types, lattice_out, lattice_clipmax, _hip.ptr(length_tie), _byref(sym),
                               _byref(eta_c), _byref(ms), _byref(self._species_struct(species, B)))
+
+    def predictor_step(self, frac, types, lengths, angles, t_crystal, s_crystal, offsets, eps, logits, len0, z_lattice, z_frac,
+                       u_types, lattice_out, successor, scheduled=True, length_tie=None, eta=None, multistep=None, species=None,
+                       lattice_clipmax=0.999):
+        """The predictor step of the host-noise loop through the step export its options name, first match: `species` (whichever
+        step the other options name, under it), `multistep`, `eta`, `length_tie`, else reverse_step when the run has no schedule
+        (scheduled=False), else reverse_step_to.  `successor`: the level every crystal lands on (t - 1 without a schedule), written
+        to the caller's buffer s_crystal [B] i32 for every export but the plain reverse_step, which takes none."""
+        state, outputs, draws = (frac, types, lengths, angles, t_crystal), (offsets, eps, logits, len0), (z_lattice, z_frac, u_types)
+        if species is None and multistep is None and eta is None and length_tie is None and not scheduled:
+            return self.reverse_step(*state, *outputs, *draws, lattice_out)
+        s_crystal.fill_(successor)
+        if species is not None:
+            self.reverse_step_species(*state, s_crystal, *outputs, *draws, lattice_out, species, length_tie=length_tie,
+                                      eta=eta if multistep is None else None, multistep=multistep, lattice_clipmax=lattice_clipmax)
+        elif multistep is not None:  # (the eta = 0 step extrapolated with the history: no z is read)
+            self.reverse_step_multistep(*state, s_crystal, *outputs, u_types, lattice_out, multistep, length_tie, lattice_clipmax)
+        elif eta is not None:
+            self.reverse_step_eta(*state, s_crystal, *outputs, *draws, lattice_out, eta, length_tie, lattice_clipmax)
+        elif length_tie is not None:
+            self.reverse_step_tied(*state, s_crystal, *outputs, *draws, lattice_out, length_tie, lattice_clipmax)
+        else:
+            self.reverse_step_to(*state, s_crystal, *outputs, *draws, lattice_out, lattice_clipmax)
 
     def resample_jump(self, frac, types, lengths, angles, s_crystal, t_crystal, offsets, z_frac, z_lengths, u_types, lattice_out,
                       const_types=None, fixed_lengths=None, condition=None, length_tie=None):
@@ -959,9 +959,9 @@ class HipEngine:
         tie codes [B] int32 (arreau_resample_jump_tied); None is the jump without them."""
         B, N = lengths.shape[0], frac.shape[0]
         cond = self._condition_struct(condition, N, B) if condition is not None else None
+        self._check_tie(length_tie, B)
         name, tie = "arreau_resample_jump", ()
         if length_tie is not None:
-            self._check_tie(length_tie, B)
             name, tie = "arreau_resample_jump_tied", (_hip.ptr(length_tie),)
         _hip.check(getattr(_hip.lib(), name)(
             self._handle, _hip.ptr(frac), _hip.ptr(types), _hip.ptr(lengths), _hip.ptr(angles), _hip.ptr(s_crystal),
@@ -976,19 +976,15 @@ class HipEngine:
         fixed_lengths; `length_tie` ties the lengths (int32 [B] codes).  `crystal_seeds`: keyed sampling
         (arreau_noise_state_keyed): the draws keyed by every crystal's stream seed, elements counted within it."""
         B, N = lengths.shape[0], frac.shape[0]
-        if length_tie is not None:
-            self._check_tie(length_tie, B)
+        self._check_tie(length_tie, B)
+        name, keyed = "arreau_noise_state", ()
         if crystal_seeds is not None:
             self._check_seeds(crystal_seeds, B)
-            _hip.check(_hip.lib().arreau_noise_state_keyed(
-                self._handle, _hip.ptr(frac), _hip.ptr(types), _hip.ptr(lengths), _hip.ptr(angles), _hip.ptr(offsets), B, N, int(t),
-                int(seed) & (2 ** 64 - 1), _hip.ptr(const_types), _hip.ptr(fixed_lengths), _hip.ptr(lattice_out), _hip.ptr(length_tie),
-                _hip.ptr(crystal_seeds), _hip.stream_ptr(self.device)), "arreau_noise_state_keyed")
-            return
-        _hip.check(_hip.lib().arreau_noise_state(
+            name, keyed = "arreau_noise_state_keyed", (_hip.ptr(crystal_seeds),)
+        _hip.check(getattr(_hip.lib(), name)(
             self._handle, _hip.ptr(frac), _hip.ptr(types), _hip.ptr(lengths), _hip.ptr(angles), _hip.ptr(offsets), B, N, int(t),
             int(seed) & (2 ** 64 - 1), _hip.ptr(const_types), _hip.ptr(fixed_lengths), _hip.ptr(lattice_out), _hip.ptr(length_tie),
-            _hip.stream_ptr(self.device)), "arreau_noise_state")
+            *keyed, _hip.stream_ptr(self.device)), name)
 
     def invert_step(self, frac, types, lengths, angles, s_crystal, t_crystal, offsets, eps, len0, lattice_out, fixed_lengths=None):
         """One DDIM inversion step in place on (frac, lengths), per crystal from level s_crystal[b] up to t_crystal[b], on the
@@ -1006,10 +1002,7 @@ class HipEngine:
         read only.  One network evaluation per step.  t_first must be a level whose "one below" entry the table holds
         (up_table[t_first - 1] == t_first): ascending_table writes it for every level it is given, so a climb may be cut into
         calls at any of them; another entry is clamped and flagged on the device."""
-        T = int(self.cfg.num_timesteps)
-        if (tuple(up_table.shape) != (T + 1,) or up_table.dtype != torch.int32 or up_table.device != self.device
-                or not up_table.is_contiguous()):
-            raise ValueError(f"up_table must be a contiguous int32 tensor of shape ({T + 1},) on {self.device}")
+        _require("", "up_table", up_table, (int(self.cfg.num_timesteps) + 1,), torch.int32, self.device)
         N, B = frac.shape[0], lengths.shape[0]
         ws = self.workspace(N, B)
         _hip.check(_hip.lib().arreau_invert_loop(
@@ -1017,23 +1010,23 @@ class HipEngine:
             int(t_first), int(n_steps), _hip.ptr(up_table), _hip.ptr(fixed_lengths), _hip.ptr(lattice_out), _hip.ptr(ws), ws.numel(),
             int(bool(use_graph)), _hip.stream_ptr(self.device)), "arreau_invert_loop")
 
+    def _on_device(self, what, frac):
+        if frac.device != self.device:
+            raise ValueError(f"{what}: the state must be on {self.device}")
+
     def screen(self, frac, lattice, offsets, types=None, criteria=None):
         """The structural screen of a batch on this engine's device (arreau_crystal_screen; diffusion/screening.py: `screen`,
         which needs no engine): frac [N,3] f32, lattice [B,3,3] f32, offsets [B+1] i32, types [N] i32 or None, criteria a
         ScreenCriteria (None: the defaults; mask_type None: no species check).  One launch on the current stream; returns the
         dict of device tensors min_distance, pair, n_close, volume, number_density, flags, valid."""
-        from .diffusion import screening
-        if frac.device != self.device:
-            raise ValueError(f"screen: the state must be on {self.device}")
+        self._on_device("screen", frac)
         return screening.screen(frac, lattice, offsets, types, criteria)
 
     def reduce_cells(self, frac, lattice, offsets, types, params=None):
         """The cell reduction of a batch on this engine's device (arreau_crystal_reduce; diffusion/cell_reduction.py:
         `reduce_cells`, which needs no engine): frac [N,3] f32, lattice [B,3,3] f32, offsets [B+1] i32, types [N] i32, params a
         CellReductionParams or None (the defaults).  Returns its dict of device tensors; does not synchronise."""
-        from .diffusion import cell_reduction
-        if frac.device != self.device:
-            raise ValueError(f"reduce_cells: the state must be on {self.device}")
+        self._on_device("reduce_cells", frac)
         return cell_reduction.reduce_cells(frac, lattice, offsets, types, params)
 
     def symmetrize(self, frac, lattice, offsets, types, params=None, found=None):
@@ -1041,9 +1034,7 @@ class HipEngine:
         which needs no engine): the batch as for `find_symmetry`, params a SymmetrizeParams or None (the defaults), found the dict
         of `find_symmetry` on the same tensors or None (the search is then launched here).  Returns its dict of device tensors;
         does not synchronise."""
-        from .diffusion import symmetrize as symmetrize_mod
-        if frac.device != self.device:
-            raise ValueError(f"symmetrize: the state must be on {self.device}")
+        self._on_device("symmetrize", frac)
         return symmetrize_mod.symmetrize(frac, lattice, offsets, types, params, found)
 
     def conventional_cell(self, frac, lattice, offsets, types, params=None, reduced=None):
@@ -1051,18 +1042,14 @@ class HipEngine:
         batch, arreau_crystal_conventional; diffusion/conventional_cell.py: `conventional_cell`, which needs no engine): the batch as
         for `reduce_cells`, params a ConventionalCellParams or None (the defaults), reduced the dict of `reduce_cells` on the same
         tensors with the same symprec or None (the reduction is then launched here).  Returns its dict of device tensors."""
-        from .diffusion import conventional_cell as conventional_mod
-        if frac.device != self.device:
-            raise ValueError(f"conventional_cell: the state must be on {self.device}")
+        self._on_device("conventional_cell", frac)
         return conventional_mod.conventional_cell(frac, lattice, offsets, types, params, reduced)
 
     def coordination(self, frac, lattice, offsets, params=None):
         """The coordination environments of a batch on this engine's device (arreau_crystal_coordination;
         diffusion/coordination.py: `coordination`, which needs no engine): frac [N,3] f32, lattice [B,3,3] f32, offsets [B+1] i32,
         params a CoordinationParams or None (the defaults).  Returns its dict of device tensors."""
-        from .diffusion import coordination as coordination_mod
-        if frac.device != self.device:
-            raise ValueError(f"coordination: the state must be on {self.device}")
+        self._on_device("coordination", frac)
         return coordination_mod.coordination(frac, lattice, offsets, params)
 
     def bond_order(self, frac, lattice, offsets, params=None, coordination_result=None):
@@ -1070,9 +1057,7 @@ class HipEngine:
         diffusion/bond_order.py: `bond_order`, which needs no engine): the coordination launch with `params`, or the given device
         `coordination_result` of a search with those parameters, then the new launch.  Returns the dict of device tensors
         `bond_order` returns.  Does not synchronise."""
-        from .diffusion import bond_order as bond_order_mod
-        if frac.device != self.device:
-            raise ValueError(f"bond_order: the state must be on {self.device}")
+        self._on_device("bond_order", frac)
         p = params if params is not None else bond_order_mod.BondOrderParams()
         if coordination_result is None:
             coordination_result = self.coordination(frac, lattice, offsets, p.coordination())
@@ -1082,9 +1067,7 @@ class HipEngine:
         """The symmetry search of a batch on this engine's device (arreau_crystal_symmetry; diffusion/symmetry_search.py:
         `find_symmetry`, which needs no engine): frac [N,3] f32, lattice [B,3,3] f32, offsets [B+1] i32, types [N] i32, params
         a SymmetrySearchParams (None: the defaults).  One launch on the current stream; returns the dict of device tensors."""
-        from .diffusion import symmetry_search
-        if frac.device != self.device:
-            raise ValueError(f"find_symmetry: the state must be on {self.device}")
+        self._on_device("find_symmetry", frac)
         return symmetry_search.find_symmetry(frac, lattice, offsets, types, params)
 
     def edges_to_slots(self, edge_index, dists, direction, N):

@@ -13,8 +13,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from ..diffusion import sample_plan
 from ..diffusion.diffusion_helpers import GaussianFourierProjection, crystal_offsets
-from ..diffusion.diffusion_loss import DiffusionLoss, SampleResult
+from ..diffusion.diffusion_loss import DiffusionLoss, SampleResult, state_to_device
 from ..diffusion.inference.visualize_crystal import VisualizationSetting
 from ..diffusion.tools.atomic_number_table import AtomicNumberTable, atomic_symbols_to_indices
 from ..ponita.models.ponita import PonitaFiberBundle
@@ -308,16 +309,11 @@ class PONITA_DIFFUSION(nn.Module):
 
     @staticmethod
     def _frame_prefix(vis_name, visualization_setting):
-        if visualization_setting == VisualizationSetting.NONE:
-            return vis_name or ""
-        import os
-        if vis_name is None:
-            os.makedirs(DIFFUSION_DIR, exist_ok=True)  # (:239-240)
+        """The prefix of the frame files: vis_name, or the reference's `<DIFFUSION_DIR>/step` (:239-240) when frames are asked
+        for without one ("" stays: DiffusionLoss.sample rejects it)."""
+        if vis_name is None and visualization_setting != VisualizationSetting.NONE:
             return f"{DIFFUSION_DIR}/step"
-        if not vis_name:
-            return ""  # DiffusionLoss.sample rejects it
-        os.makedirs(os.path.dirname(os.path.abspath(vis_name)), exist_ok=True)
-        return vis_name
+        return vis_name or ""
 
     def notify_parameters_changed(self):
         """Call after an optimizer step: the HIP engine holds copies of the weights.  An engine that exists is refreshed
@@ -405,71 +401,15 @@ class PONITA_DIFFUSION(nn.Module):
         """lightning_wrappers/diffusion.py:220-253.  `num_atoms_per_sample` may also be a sequence with one atom count
         per crystal of the batch (extension; the reference supports a single int).  Frames of a visualization_setting
         other than NONE go to `<DIFFUSION_DIR>/step_<timestep>.cif` like the reference's PNGs (`vis_name` overrides the
-        prefix).  `condition` (extension): a diffusion.conditioning.SampleCondition -- structure completion from a
-        template (DiffusionLoss.sample); it defines the batch, so the two counts may be omitted.  `num_steps` / `timesteps`
-        (extension): respaced sampling on fewer timesteps (DiffusionLoss.sample).  `corrector_steps` / `corrector_snr`
-        (extension): predictor-corrector sampling, Langevin moves on the positions before each step (DiffusionLoss.sample).
-        `resample_passes` / `jump_length` (extension): RePaint resampling, blocks of steps re-denoised after a forward jump back
-        to their top (DiffusionLoss.sample).  `lattice_system` (extension): crystals of a chosen lattice system -- one name
-        (lattice_systems.SYSTEMS) for the batch or one per crystal: the system's angles, in radians, and tied lengths kept equal at
-        every step (DiffusionLoss.sample).  None is the sampler as it was: monoclinic angles in degrees read as radians, the
-        reference's behaviour, which is not "monoclinic".  `symmetry` (extension): space-group symmetry -- a
-        diffusion.symmetry.SymmetrySpec for every crystal of the batch, or one (or None) per crystal: atoms tied in the orbits of
-        the spec's group at every step, species shared within an orbit; the specs decide the atom counts and lattice systems
-        (DiffusionLoss.sample).  `screen` (extension): a diffusion.screening.ScreenCriteria or True -- the final state is screened
-        on the device (shortest contact, cell volume, mask state) and SampleResult.metrics holds the result (DiffusionLoss.sample).
-        `unique` (extension): a diffusion.uniqueness.FingerprintParams or True -- duplicate detection on the final device state;
-        SampleResult.uniqueness holds the result (DiffusionLoss.sample).  `find_symmetry` (extension): a
-        diffusion.symmetry_search.SymmetrySearchParams or True -- the symmetry operations and point group of every final crystal;
-        SampleResult.symmetry holds the arrays (DiffusionLoss.sample).  `match_to` (extension): targets (a SampleResult, a loaded
-        crystals file, or (targets, diffusion.structure_match.StructureMatchParams)) the final crystals are matched against on the
-        device; SampleResult.match holds the arrays (DiffusionLoss.sample).  `eta` (extension): DDIM-style sampling -- a float
-        in [0, 1] that scales the noise every step injects into positions and lengths; 0 makes them a function of the initial
-        state alone, whatever the seed; None is the sampler as it was; not with `symmetry` (DiffusionLoss.sample).
-        `initial_state` (extension): a diffusion.inversion.SamplerState -- from `noise_to` (known crystals forward-noised to a
-        level), `encode` (DDIM inversion) or DiffusionLoss.draw_initial_state: the run starts from that state at its level instead
-        of a prior draw at T-1; it defines the batch, so the two counts may be omitted; use_constant_atomic_symbols=True holds
-        the state's species; not with `condition`, `symmetry` or `lattice_system` (DiffusionLoss.sample).  `multistep` (extension):
-        second-order multistep sampling -- the deterministic eta = 0 step extrapolated with the previous step's prediction, for
-        fewer steps at the same solver error; not with `condition`, corrector steps, resampling, `symmetry` or an eta other than
-        None or 0 (DiffusionLoss.sample).  `elements`, `species_temperature` (extension): species control -- per-crystal element
-        sets the species step may choose from (one collection for the batch, or a list with one collection or None per crystal)
-        and a temperature >= 0 on its Gumbel draw (0: no draw, so eta = 0 and multistep runs are deterministic in all three
-        components); with every option above (DiffusionLoss.sample).  `crystal_keys` (extension; needs `seed`, noise="philox"):
-        keyed sampling -- one integer key per crystal; every random number a crystal consumes comes from a stream of its own
-        derived from (seed, key), so the crystal is the same alone, in any batch, at any rank count (diffusion/keyed.py;
-        DiffusionLoss.sample, which states where the guarantee stops).  `conventional_cell` (extension): a
-        diffusion.conventional_cell.ConventionalCellParams or True -- the conventional cell, centring and Bravais lattice of every
-        final crystal; SampleResult.conventional holds the arrays (DiffusionLoss.sample).  `coordination` (extension): a
-        diffusion.coordination.CoordinationParams or True -- every atom's neighbours, coordination number and nearest distance
-        in the final crystals; SampleResult.coordination holds the arrays (DiffusionLoss.sample).  `bond_order` (extension): a
-        diffusion.bond_order.BondOrderParams or True -- every atom's bond-angle histogram and Steinhardt order parameters
-        q_2 .. q_8 in the final crystals; SampleResult.bond_order holds the arrays (DiffusionLoss.sample).  `contact_guidance`
-        (extension): a diffusion.contact_guidance.ContactGuidance or True -- every network evaluation's eps is steered down the
-        gradient of a penalty on contacts shorter than min_distance, so the sampler avoids them instead of being screened for
-        them; SampleResult.info["contact_guidance"] holds the last evaluation's energy, contacts and flags (DiffusionLoss.sample)."""
-        from ..diffusion import contact_guidance as guidance_mod
-        contact_guidance = guidance_mod.resolve(contact_guidance)  # (raises before any work)
-        from ..diffusion import keyed as keyed_mod, multistep as multistep_mod, resampling, species as species_mod
-        if crystal_keys is not None:  # (raises before any work)
-            crystal_keys = keyed_mod.validate_keys(crystal_keys, None, seed, noise if noise in ("philox", "device", "reference") else "philox")
-        species_temperature = species_mod.validate_temperature(species_temperature)  # (raises before any work)
-        multistep = multistep_mod.check_multistep(multistep, eta=eta, condition=condition, corrector_steps=corrector_steps,
-                                                  resample_passes=resample_passes, symmetry=symmetry)  # (raises before any work)
-        resampling.check_resampling(resample_passes, jump_length)  # (raises before any work)
-        if eta is not None:
-            from ..diffusion import ddim
-            eta = ddim.check_eta(eta)  # (raises before any work)
-        if initial_state is not None:
-            from ..diffusion import inversion
-            inversion.check_initial_state(initial_state, self.diffusion_loss.T, condition=condition, symmetry=symmetry,
-                                          lattice_system=lattice_system, num_atoms_per_sample=num_atoms_per_sample,
-                                          num_samples_in_batch=num_samples_in_batch,
-                                          num_atomic_states=self.num_atomic_states)  # (raises before any work)
-            inversion.schedule_from(self.diffusion_loss.T, initial_state.t, num_steps=num_steps, timesteps=timesteps)
-        elif num_steps is not None or timesteps is not None:
-            from ..diffusion import respacing
-            respacing.resolve_schedule(self.diffusion_loss.T, num_steps=num_steps, timesteps=timesteps)  # (raises before any work)
+        prefix; its directory is made).  `use_constant_atomic_symbols`: the symbols of one crystal's atoms, held for every
+        crystal of the batch (needs a uniform num_atoms_per_sample; not together with a condition's species mask); with an
+        `initial_state`, True holds the state's own species.  Every other keyword is DiffusionLoss.sample's, documented there,
+        and is checked -- with the two above -- before any work: a rejected call has made no directory, built no engine and read
+        no generator (diffusion/sample_plan.py)."""
+        # (first statement: DiffusionLoss.sample's keywords as given, under their own names)
+        options = {k: v for k, v in locals().items() if k not in ("self", "use_constant_atomic_symbols")}
+        options.update(model=self, vis_name=self._frame_prefix(vis_name, visualization_setting))
+        sample_plan.check_options(**options)  # (the rules that need nothing of this module, before it is read)
         if condition is not None and use_constant_atomic_symbols is not None and condition.species_known().any():
             raise ValueError("use_constant_atomic_symbols and a species mask both fix the species; give one of them")
         z_table = AtomicNumberTable(self.z_table_zs.tolist())
@@ -484,17 +424,11 @@ class PONITA_DIFFUSION(nn.Module):
             constant_atoms = torch.as_tensor(np.tile(idx, num_samples_in_batch))
         else:
             constant_atoms = None
-        return self.diffusion_loss.sample(
-            model=self, z_table=z_table, t_emb_weights=self.t_emb, num_atoms_per_sample=num_atoms_per_sample,
-            num_samples_in_batch=num_samples_in_batch, vis_name=self._frame_prefix(vis_name, visualization_setting),
-            visualization_setting=visualization_setting, show_bonds=show_bonds, constant_atoms=constant_atoms,
-            noise=noise, max_steps=max_steps, use_graph=use_graph, seed=seed, fixed_cell=fixed_cell, condition=condition,
-            num_steps=num_steps, timesteps=timesteps, corrector_steps=corrector_steps, corrector_snr=corrector_snr,
-            resample_passes=resample_passes, jump_length=jump_length, lattice_system=lattice_system, symmetry=symmetry,
-            screen=screen, unique=unique, find_symmetry=find_symmetry, reduce_cell=reduce_cell, symmetrize=symmetrize,
-            match_to=match_to, eta=eta, initial_state=initial_state, multistep=multistep, elements=elements,
-            species_temperature=species_temperature, crystal_keys=crystal_keys, conventional_cell=conventional_cell,
-            coordination=coordination, bond_order=bond_order, contact_guidance=contact_guidance)
+        options.update(z_table=z_table, t_emb_weights=self.t_emb, constant_atoms=constant_atoms)
+        sample_plan.resolve(self.diffusion_loss.T, **options)  # (every other rule, before a directory is made)
+        if options["vis_name"] and visualization_setting != VisualizationSetting.NONE:
+            os.makedirs(os.path.dirname(os.path.abspath(options["vis_name"])), exist_ok=True)
+        return self.diffusion_loss.sample(**options)
 
     # ---- starting the sampler from given crystals (extension; rules in include/arreau_hip.h) -------------------------------------
     def _crystal_state(self, crystals, t, what):
@@ -526,15 +460,6 @@ class PONITA_DIFFUSION(nn.Module):
         inversion.check_state(state, self.diffusion_loss.T, self.num_atomic_states)
         return state
 
-    def _state_to_device(self, state, dev):
-        f32 = dict(device=dev, dtype=torch.float32)
-        frac = torch.as_tensor(state.frac_x).to(**f32).contiguous()
-        types = torch.as_tensor(state.species).to(device=dev, dtype=torch.int32).contiguous()
-        lengths = torch.as_tensor(state.lengths).to(**f32).contiguous()
-        angles = torch.as_tensor(state.angles).to(**f32).contiguous()
-        off = crystal_offsets(torch.as_tensor(state.num_atoms), dev)
-        return frac, types, lengths, angles, off, torch.zeros((state.B, 3, 3), **f32)
-
     @staticmethod
     def _state_from_device(state, frac, types, lengths, t, length_tie=None):
         from ..diffusion import inversion
@@ -565,11 +490,11 @@ class PONITA_DIFFUSION(nn.Module):
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         eng = self.engine()
         dev = eng.device
-        frac, types, lengths, angles, off, cell = self._state_to_device(state, dev)
+        frac, types, lengths, angles, off, cell = state_to_device(state, dev)
         tie_d = torch.as_tensor(tie, device=dev, dtype=torch.int32).contiguous() if tie is not None else None
         seeds_d = None
         if crystal_keys is not None:
-            seeds_d = torch.as_tensor(keyed_mod.stream_seeds(seed, crystal_keys).view(np.int64), device=dev).contiguous()
+            seeds_d = keyed_mod.device_seeds(keyed_mod.stream_seeds(seed, crystal_keys), dev)
         eng.noise_state(frac, types, lengths, angles, off, state.t, seed, cell, const_types=types.clone() if constant_atoms else None,
                         fixed_lengths=lengths.clone() if fixed_cell else None, length_tie=tie_d, crystal_seeds=seeds_d)
         eng.check_status()
@@ -597,7 +522,7 @@ class PONITA_DIFFUSION(nn.Module):
         n_steps = len(levels) - 1
         eng = self.engine()
         dev = eng.device
-        frac, types, lengths, angles, off, cell = self._state_to_device(state, dev)
+        frac, types, lengths, angles, off, cell = state_to_device(state, dev)
         init = (frac.clone(), lengths.clone())
         up = torch.as_tensor(inversion.ascending_table(T, levels)).to(dev)
         fixed = lengths.clone() if fixed_cell else None
