@@ -33,7 +33,7 @@ EXPORTS = [
     "arreau_sample_loop_eta", "arreau_reverse_step_eta",
     "arreau_crystal_fingerprint", "arreau_fingerprint_match", "arreau_crystal_symmetry", "arreau_crystal_reduce",
     "arreau_crystal_symmetrize", "arreau_structure_match", "arreau_structure_match_assigned",
-    "arreau_crystal_conventional", "arreau_crystal_coordination", "arreau_crystal_bond_order",
+    "arreau_crystal_conventional", "arreau_crystal_coordination", "arreau_crystal_bond_order", "arreau_crystal_voronoi",
     "arreau_noise_state", "arreau_invert_step", "arreau_invert_loop",
     "arreau_sample_loop_multistep", "arreau_reverse_step_multistep",
     "arreau_sample_loop_species", "arreau_reverse_step_species",
@@ -139,6 +139,18 @@ class BondOrderResultC(Structure):
     """arreau_bond_order_result: the four per-crystal and six per-atom device arrays the bond-order launch writes."""
     _fields_ = [(name, c_void_p) for name in ("mean_q", "n_angles", "angle_hist", "flags",
                                                 "n_used", "q", "q2", "cos_min", "cos_max", "angles")]
+
+
+class VoronoiParamsC(Structure):
+    """arreau_voronoi_params: the weight threshold, cutoff and caps of the Voronoi construction."""
+    _fields_ = [("tol", c_float), ("cutoff", c_float), ("max_faces", c_int32), ("max_candidates", c_int32), ("max_shells", c_int32)]
+
+
+class VoronoiResultC(Structure):
+    """arreau_voronoi_result: the seven per-crystal and eleven per-atom device arrays the Voronoi launch writes."""
+    _fields_ = [(name, c_void_p) for name in ("n_faces", "min_cn", "max_cn", "mean_cn", "mean_cn_eff", "volume_sum", "flags",
+                                                "cn", "neighbors", "face_weight", "face_solid_angle", "face_area", "face_distance",
+                                                "volume", "omega_sum", "max_radius", "cn_eff", "atom_flags")]
 
 
 class FingerprintParamsC(Structure):
@@ -296,6 +308,7 @@ def _prototypes():
         "arreau_crystal_screen": [vp] * 4 + [i32, i32, POINTER(ScreenCriteriaC), POINTER(ScreenResultC), vp],
         "arreau_crystal_coordination": [vp] * 3 + [i32, i32, POINTER(CoordinationParamsC), POINTER(CoordinationResultC), vp],
         "arreau_crystal_bond_order": [vp] * 3 + [i32, i32, vp, vp, POINTER(BondOrderParamsC), POINTER(BondOrderResultC), vp],
+        "arreau_crystal_voronoi": [vp] * 3 + [i32, i32, POINTER(VoronoiParamsC), POINTER(VoronoiResultC), vp],
         "arreau_crystal_fingerprint": [vp] * 4 + [i32, i32, POINTER(FingerprintParamsC), POINTER(FingerprintResultC), vp],
         "arreau_fingerprint_match": [POINTER(FingerprintResultC), i32, POINTER(FingerprintResultC), i32, f32, POINTER(MatchResultC), vp],
         "arreau_crystal_symmetry": [vp] * 4 + [i32, i32, POINTER(SymmetryParamsC), POINTER(SymmetryResultC), vp],

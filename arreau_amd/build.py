@@ -12,7 +12,7 @@ import sys
 import time
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-SOURCES = ["model.hip", "graph.hip", "screen.hip", "coordination.hip", "bond_order.hip", "fingerprint.hip", "symfind.hip", "reduce.hip", "symmetrize.hip", "conventional.hip", "match.hip", "edge.hip", "edge_bf16.hip", "edge_f16.hip", "node.hip", "node_bf16.hip", "node_f16m.hip", "conv_proj.hip", "update.hip", "corrector.hip", "contact_guide.hip", "resample.hip", "train.hip", "train_net.hip", "optim.hip", "api.hip"]
+SOURCES = ["model.hip", "graph.hip", "screen.hip", "coordination.hip", "bond_order.hip", "voronoi.hip", "fingerprint.hip", "symfind.hip", "reduce.hip", "symmetrize.hip", "conventional.hip", "match.hip", "edge.hip", "edge_bf16.hip", "edge_f16.hip", "node.hip", "node_bf16.hip", "node_f16m.hip", "conv_proj.hip", "update.hip", "corrector.hip", "contact_guide.hip", "resample.hip", "train.hip", "train_net.hip", "optim.hip", "api.hip"]
 HEADERS = ["internal.h", "score_plan.h", "edge_rows.h", "bf16x6.h", "f16x3.h", os.path.join("..", "..", "include", "arreau_hip.h"), "sgemm.h", "train_kernels.h", "philox.h", "embed_dev.h", "prep_dev.h", "graph_dev.h", "crystal_dev.h", "symfind_table.h", "update_dev.h", "readout_dev.h"]
 LIB = os.path.join(CSRC, "libarreau_hip.so")
 # Debug twin: the same sources with -DARREAU_DEBUG_WAIT_ALL (every hand-counted `s_waitcnt vmcnt(N)` becomes vmcnt(0)).

@@ -3,7 +3,8 @@ the bond-orientational order parameters q_2, q_4, q_6, q_8 of its neighbour shel
 q_l (arreau_crystal_bond_order, arreau_amd/csrc/bond_order.hip; the rules are written out in include/arreau_hip.h).  What a
 coordination number cannot tell: an octahedron from a trigonal prism, fcc from hcp from an icosahedral shell (all 12), a
 tetrahedral 4 from a square-planar 4.  Here: the parameters, the constants, the entry points that need no engine (`bond_order`:
-the coordination launch, then the new one; `from_coordination`: the new one on a coordination result), the statistics and two numpy
+the coordination launch, then the new one; `from_coordination`: the new one on a coordination result; `from_voronoi`: on a
+Voronoi result's faces), the statistics and two numpy
 restatements for the tests -- `bond_order_reference_f32`, one float32 operation at a time in the kernel's order, sums and butterfly
 included (the bit-for-bit yardstick), and `bond_order_reference_f64`, the same lists in float64, which also returns the margin of
 every pair's cosine to the nearest histogram edge.  Needs numpy alone at import.
@@ -131,6 +132,14 @@ def from_coordination(frac, lattice, offsets, coordination_result, max_neighbors
                                                         ctypes.byref(r), _hip.stream_ptr(dev)), "arreau_crystal_bond_order")
     out["coord_flags"] = coordination_result.get("flags")
     return out
+
+
+def from_voronoi(frac, lattice, offsets, voronoi_result, max_faces=None):
+    """The same on Voronoi shells: the twin of `from_coordination` for a device Voronoi result (the dict of voronoi.voronoi), whose
+    cn [N] and neighbors [N, max_faces, 4] have the coordination result's layout -- the shell of an atom is then the faces of
+    weight >= tol of its Voronoi cell, of them the first max_faces.  The existing launch, no new kernel.  coord_flags is None:
+    the Voronoi flags have their own bits (voronoi.FLAG_NAMES) and stay in the Voronoi result."""
+    return from_coordination(frac, lattice, offsets, {"cn": voronoi_result["cn"], "neighbors": voronoi_result["neighbors"]}, max_faces)
 
 
 def bond_order(frac, lattice, offsets, params=None):

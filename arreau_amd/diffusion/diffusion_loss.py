@@ -85,6 +85,11 @@ class SampleResult:
     # crystal, and n_used, q and q2 [.., 4], cos_min, cos_max, angles [.., 37] and species, one row per atom; None when it was not
     # asked for
     bond_order: Optional[dict] = None
+    # extension: the Voronoi cells of the final state (sample(voronoi=...); diffusion/voronoi.py) -- numpy arrays n_faces, min_cn,
+    # max_cn, mean_cn, mean_cn_eff, volume_sum and flags, one row per crystal, and cn, neighbors [.., max_faces, 4], face_weight,
+    # face_solid_angle, face_area, face_distance [.., max_faces], volume, omega_sum, max_radius, cn_eff, atom_flags and species,
+    # one row per atom; None when it was not asked for
+    voronoi: Optional[dict] = None
 
 
 class _PinnedRing:
@@ -535,7 +540,7 @@ class DiffusionLoss(nn.Module):
                lattice_system=None, symmetry=None, screen=None, unique=None, find_symmetry=None, reduce_cell=None,
                symmetrize=None, match_to=None, eta: Optional[float] = None, initial_state=None,
                multistep: bool = False, elements=None, species_temperature: float = 1.0, crystal_keys=None,
-               conventional_cell=None, coordination=None, bond_order=None, contact_guidance=None) -> SampleResult:
+               conventional_cell=None, coordination=None, bond_order=None, contact_guidance=None, voronoi=None) -> SampleResult:
         """diffusion_loss.py:276-377.  The initial state is drawn on the host exactly like the reference (numpy
         uniforms for the angles, then randn lengths, randn fractional coordinates from torch's global CPU generator):
         draw_initial_state, which a caller may also use on its own.
@@ -713,6 +718,14 @@ class DiffusionLoss(nn.Module):
         With `coordination` too the coordination launch is shared: their parameters must then agree (ValueError before any work).
         It reads the state as sampled.  No w_l, no neighbour-averaged parameters, no classification of environments, no Voronoi
         weights.  None: no launch is added, bond_order is None and the results are what they were, bit for bit.
+        `voronoi` (extension, every noise mode and option): a voronoi.VoronoiParams (tol, cutoff, max_faces, max_candidates,
+        max_shells), or True for its defaults -- one more launch on the final device state (arreau_crystal_voronoi; rules in
+        include/arreau_hip.h) builds every atom's Voronoi cell over every periodic image: the neighbours behind its faces, each
+        with its solid angle, area and distance and its weight (solid angle over the atom's largest), the number of faces of
+        weight >= tol, the cell's volume, and the OPEN flag where the cutoff does not close the cell.  SampleResult.voronoi then
+        holds the arrays (voronoi.STORED_KEYS).  It reads the state as sampled.  Not CrystalNN: no radii, no electronegativities,
+        no distance weighting, no probabilities.  None: no launch is added, voronoi is None and the results are what they were,
+        bit for bit.
         `contact_guidance` (extension, every noise mode and option): a contact_guidance.ContactGuidance (min_distance, weight,
         max_shells), or True for its defaults -- training-free guidance away from short contacts (rules in include/arreau_hip.h,
         "contact guidance"; arreau_sample_loop_guided).  Every network evaluation of every step, a corrector's included, is followed
@@ -780,7 +793,7 @@ class DiffusionLoss(nn.Module):
         final = instruments.DeviceState(eng, buf.frac_d, buf.lattice_d, buf.off_d, buf.types_d, z_table, plan.num_atoms.numpy(),
                                         atomic_numbers, mask_type=-1 if constant_atoms is not None else plan.S - 1)
         fields = {e.field: e.run(final, plan.instruments[e.keyword]) if plan.instruments[e.keyword] is not None else None
-                  for e in instruments.TABLE}
+                  for e in instruments.WHOLE}
         return SampleResult(num_atoms=plan.num_atoms.numpy(), frac_x=buf.frac_d.cpu().numpy().astype(np.float64),
                             atomic_numbers=atomic_numbers, lattice=buf.lattice_d.cpu().numpy().astype(np.float64), info=info,
                             crystal_keys=np.array(plan.crystal_keys, dtype=np.int64) if plan.crystal_keys is not None else None,

@@ -3,7 +3,9 @@ symmetrization, structure match -- as one table, in the order their arrays appea
 ones, which chain those launches (the conventional cell: reduction, search on the reduced cell, conventional basis), and last the
 LOCAL ones, which describe each atom's surroundings (the coordination environments); EVERY is all of them.  SHELL holds what
 is built on a LOCAL one's neighbour lists (the bond angles and order parameters); TABLE is EVERY and SHELL, the whole table, and
-KEYWORDS maps a sample() keyword to its entry.  An entry holds what the
+KEYWORDS maps a sample() keyword to its entry.  CELLS holds what builds each atom's Voronoi cell (its own launch, after the
+bond order); WHOLE is TABLE and CELLS -- what the file layer, the batch driver, the screen and sample() loop over -- and
+WHOLE_KEYWORDS its keyword map.  An entry holds what the
 instruments differ in for the host-side plumbing: the file layer (inference/process_generated_crystals.py), the batch driver
 (generate.py) and `python -m arreau_amd.screen` loop over it, and so does DiffusionLoss.sample, which calls every asked-for
 entry's `run` on the final device state (DeviceState) in table order: an entry that shares a launch comes after the entry that
@@ -15,7 +17,7 @@ from typing import Callable, Optional
 import numpy as np
 
 from . import (bond_order, cell_reduction, conventional_cell, coordination, screening, structure_match, symmetrize, symmetry_search,
-               uniqueness)
+               uniqueness, voronoi)
 from .tools.atomic_number_table import atomic_number_indexes_to_atomic_numbers
 
 
@@ -84,6 +86,11 @@ def _run_bond_order(s, params):  # (the coordination launch is shared)
         s.eng.bond_order(s.frac, s.lattice, s.offsets, params, s.launched.get("coordination"))), s.atomic_numbers)
 
 
+def _run_voronoi(s, params):
+    s.launched["voronoi"] = s.eng.voronoi(s.frac, s.lattice, s.offsets, params)
+    return voronoi.sample_arrays(voronoi.result_to_numpy(s.launched["voronoi"]), s.atomic_numbers)
+
+
 @dataclass(frozen=True)
 class Instrument:
     keyword: str       # sample(<keyword>=...), and the command-line flag of that name
@@ -148,6 +155,14 @@ SHELL = (
 )
 TABLE = EVERY + SHELL  # the whole table: what the file layer, the batch driver and the screen loop over
 KEYWORDS = {e.keyword: e for e in TABLE}
+# what builds each atom's Voronoi cell: a launch of its own, after the bond order; its arrays after order_*
+CELLS = (
+    Instrument("voronoi", "voronoi", "voronoi_", "voronoi_stats", voronoi, voronoi.STORED_KEYS, "VoronoiParams",
+               (("tol", "vor_tol"), ("cutoff", "vor_cutoff")), "voronoi", atom_keys=voronoi.ATOM_KEYS, shape=(),
+               shapes=(("neighbors", 3),) + tuple((k, 2) for k in voronoi.FACE_KEYS), run=_run_voronoi),
+)
+WHOLE = TABLE + CELLS  # the whole table with the cells: what the file layer, the batch driver, the screen and sample() loop over
+WHOLE_KEYWORDS = {e.keyword: e for e in WHOLE}
 
 
 def concat(entry, parts):

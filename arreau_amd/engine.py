@@ -11,7 +11,8 @@ import torch
 
 from . import _hip
 from .diffusion import (bond_order as bond_order_mod, cell_reduction, conventional_cell as conventional_mod,
-                        coordination as coordination_mod, screening, symmetrize as symmetrize_mod, symmetry_search)
+                        coordination as coordination_mod, screening, symmetrize as symmetrize_mod, symmetry_search,
+                        voronoi as voronoi_mod)
 from .diffusion.contact_guidance import INFO_KEYS, ContactGuidance
 from .diffusion.corrector import check_corrector
 from .diffusion.ddim import check_eta
@@ -81,6 +82,11 @@ def conventional_cell(frac, lattice, offsets, types, params=None, reduced=None):
 def coordination(frac, lattice, offsets, params=None):
     """The coordination environments without an engine (arreau_crystal_coordination needs no model): diffusion.coordination.coordination."""
     return coordination_mod.coordination(frac, lattice, offsets, params)
+
+
+def voronoi(frac, lattice, offsets, params=None):
+    """The Voronoi cells without an engine (arreau_crystal_voronoi needs no model): diffusion.voronoi.voronoi."""
+    return voronoi_mod.voronoi(frac, lattice, offsets, params)
 
 
 def bond_order(frac, lattice, offsets, params=None):
@@ -1062,6 +1068,13 @@ class HipEngine:
         if coordination_result is None:
             coordination_result = self.coordination(frac, lattice, offsets, p.coordination())
         return bond_order_mod.from_coordination(frac, lattice, offsets, coordination_result, p.max_neighbors)
+
+    def voronoi(self, frac, lattice, offsets, params=None):
+        """The Voronoi cells of a batch on this engine's device (arreau_crystal_voronoi; diffusion/voronoi.py: `voronoi`, which
+        needs no engine): frac [N,3] f32, lattice [B,3,3] f32, offsets [B+1] i32, params a VoronoiParams or None (the defaults).
+        Returns its dict of device tensors.  Does not synchronise."""
+        self._on_device("voronoi", frac)
+        return voronoi_mod.voronoi(frac, lattice, offsets, params)
 
     def find_symmetry(self, frac, lattice, offsets, types, params=None):
         """The symmetry search of a batch on this engine's device (arreau_crystal_symmetry; diffusion/symmetry_search.py:

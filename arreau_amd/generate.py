@@ -68,6 +68,9 @@ Coordination environments: `--coordination` (`--cn_tol`, `--cn_cutoff`) finds ev
 (diffusion/coordination.py) and stores coord_* arrays.  Bond order: `--bond_order` (the same two flags; with `--coordination` the
 search is shared) adds the bond-angle histogram and the Steinhardt order parameters q_2 .. q_8 of every atom's shell
 (diffusion/bond_order.py): the summed histogram, mean q4 and q6 overall and per element, the count per flag, and order_* arrays.
+Voronoi cells: `--voronoi` (`--vor_tol`, `--vor_cutoff`) builds every atom's Voronoi cell on the device (diffusion/voronoi.py): the
+histogram of cn (faces of weight >= vor_tol), mean cn and cn_eff overall and per element, the share of OPEN atoms, the count per flag,
+and voronoi_* arrays.  Not CrystalNN: no radii, no electronegativities, no distance weighting, no probabilities.
 
 Keyed sampling: `--keyed` (needs `--seed`) makes every crystal a function of (seed, key) alone (diffusion/keyed.py).  Every rank
 uses the same seed; output slot k of `--num_crystals` has key k on its first attempt.  With `--require_valid`, attempt a of slot k
@@ -92,7 +95,7 @@ import numpy as np
 
 from .diffusion import instruments
 from .diffusion.diffusion_loss import SampleResult
-from .diffusion.instruments import TABLE as INSTRUMENTS
+from .diffusion.instruments import WHOLE as INSTRUMENTS
 
 
 def shard_range(num_items: int, world_size: int, rank: int):
@@ -477,6 +480,11 @@ def build_parser() -> argparse.ArgumentParser:
                          "--cn_cutoff): summed angle histogram, mean q4 and q6 overall and per element and flags per rank and in "
                          "total + order_* arrays in the output file")
     add_coordination_arguments(ap)
+    ap.add_argument("--voronoi", action="store_true",
+                    help="build every atom's Voronoi cell on the device (--vor_tol, --vor_cutoff): solid-angle-weighted neighbours and "
+                         "atom volumes; histogram of cn, mean cn and cn_eff overall and per element, share of OPEN atoms and flags "
+                         "per rank and in total + voronoi_* arrays in the output file")
+    add_voronoi_arguments(ap)
     ap.add_argument("--guide_contacts", action="store_true",
                     help="contact guidance: steer every sampling step away from contacts shorter than --guide_min_distance (the "
                          "gradient of a contact penalty added to the predicted eps on the device); prints the contacts and flags of "
@@ -505,6 +513,15 @@ def add_coordination_arguments(ap):
     ap.add_argument("--cn_cutoff", type=float, default=6.0, help="coordination: nothing beyond this distance in A is a neighbour")
 
 
+def add_voronoi_arguments(ap):
+    """The flags of the Voronoi construction, shared with `python -m arreau_amd.screen`."""
+    ap.add_argument("--vor_tol", type=float, default=0.05,
+                    help="voronoi: a face counts as a neighbour when its solid angle is at least vor_tol times the atom's largest "
+                         "(0.05: a starting value, not a claim)")
+    ap.add_argument("--vor_cutoff", type=float, default=6.0,
+                    help="voronoi: the atoms within this distance in A may bound a cell; an atom whose cell they do not close is OPEN")
+
+
 def add_structure_match_arguments(ap):
     """The tolerance flags of the structure match, shared with `python -m arreau_amd.screen`."""
     ap.add_argument("--ltol", type=float, default=0.2, help="match_to: relative tolerance on the cell lengths (StructureMatcher's default)")
@@ -516,10 +533,10 @@ def add_structure_match_arguments(ap):
 
 
 def instrument_params(keyword, args, error):
-    """The parameters of one instrument (its sample() keyword: instruments.KEYWORDS) from its flags -- screen: a ScreenCriteria,
+    """The parameters of one instrument (its sample() keyword: instruments.WHOLE_KEYWORDS) from its flags -- screen: a ScreenCriteria,
     unique: a FingerprintParams, find_symmetry: a SymmetrySearchParams, reduce_cell: a CellReductionParams, symmetrize: a
-    SymmetrizeParams, match_to: a StructureMatchParams, conventional_cell: a ConventionalCellParams, coordination: a CoordinationParams, bond_order: a BondOrderParams; what has no flag keeps its default.  `error(message)` reports a bad value."""
-    e = instruments.KEYWORDS[keyword]
+    SymmetrizeParams, match_to: a StructureMatchParams, conventional_cell: a ConventionalCellParams, coordination: a CoordinationParams, bond_order: a BondOrderParams, voronoi: a VoronoiParams; what has no flag keeps its default.  `error(message)` reports a bad value."""
+    e = instruments.WHOLE_KEYWORDS[keyword]
     try:
         return getattr(e.module, e.params)(**{name: getattr(args, flag) for name, flag in e.flags})
     except ValueError as err:
@@ -529,7 +546,7 @@ def instrument_params(keyword, args, error):
 def instrument_lines(keyword, res, parts=None):
     """The lines one instrument's flag prints for a result that holds its arrays: its statistics per rank (`parts`: what the ranks
     carried; None: the result as one set) and in total."""
-    e = instruments.KEYWORDS[keyword]
+    e = instruments.WHOLE_KEYWORDS[keyword]
     return instruments.summary_lines(e, getattr(res, e.field), parts)
 
 

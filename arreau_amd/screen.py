@@ -8,6 +8,7 @@
     python -m arreau_amd.screen out/crystals.npz --match_to targets.npz [--match_mode paired|any] [--ltol 0.2] [--angle_tol 5] [--stol 0.3]
     python -m arreau_amd.screen out/crystals.npz --coordination [--cn_tol 0.1] [--cn_cutoff 6.0]
     python -m arreau_amd.screen out/crystals.npz --bond_order [--cn_tol 0.1] [--cn_cutoff 6.0]
+    python -m arreau_amd.screen out/crystals.npz --voronoi [--vor_tol 0.05] [--vor_cutoff 6.0]
     python -m arreau_amd.screen out/crystals.npz --unique [--against train.npz] [--fp_r_max 6] [--fp_sigma 0.1] [--fp_tolerance 0.01]
 
 Prints the summary `python -m arreau_amd.generate --screen` prints (accepted / attempted and the count per flag) and, with
@@ -42,12 +43,17 @@ weighting (not CrystalNN), no radii, no chemistry.
 shell (diffusion/bond_order.py): the summed angle histogram, the mean q4 and q6 overall and per element and the count per flag, and
 the order_* arrays with `--out`.  It runs last too, beside `--coordination`, on the same crystals.  No w_l, no neighbour-averaged
 parameters, no classification of environments.
+`--voronoi [--vor_tol 0.05] [--vor_cutoff 6.0]` adds every atom's Voronoi cell (diffusion/voronoi.py: the neighbours behind its faces,
+each weighted by its solid angle over the atom's largest; a face counts at weight >= vor_tol): the histogram of cn, the mean cn and
+cn_eff overall and per element, the share of atoms whose cell vor_cutoff does not close (OPEN) and the count per flag, and the
+voronoi_* arrays with `--out`.  It runs last too, beside `--coordination` / `--bond_order`, on the same crystals.  Not CrystalNN: no
+radii, no electronegativities, no distance weighting, no probabilities.
 """
 import argparse
 
 
 def build_parser() -> argparse.ArgumentParser:
-    from .generate import (add_coordination_arguments, add_fingerprint_arguments, add_screen_arguments, add_structure_match_arguments,
+    from .generate import (add_coordination_arguments, add_fingerprint_arguments, add_voronoi_arguments, add_screen_arguments, add_structure_match_arguments,
                            add_symmetry_search_arguments)
     ap = argparse.ArgumentParser(prog="python -m arreau_amd.screen", description="structural screen of a crystals file")
     ap.add_argument("file", type=str, help="crystals.npz / .h5")
@@ -79,6 +85,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--bond_order", action="store_true",
                     help="also find every atom's bond-angle histogram and Steinhardt order parameters (last: on the crystals --out writes)")
     add_coordination_arguments(ap)
+    ap.add_argument("--voronoi", action="store_true",
+                    help="also build every atom's Voronoi cell: solid-angle-weighted neighbours and atom volumes (last: on the crystals --out writes)")
+    add_voronoi_arguments(ap)
     return ap
 
 
@@ -86,7 +95,7 @@ def main(argv=None):
     from .diffusion import cell_reduction, screening, structure_match, symmetry_search
     from .diffusion.inference.process_generated_crystals import load_sample_results_from_hdf5, save_sample_results_to_hdf5
     from .diffusion.diffusion_loss import SampleResult
-    from .diffusion.instruments import TABLE as INSTRUMENTS
+    from .diffusion.instruments import WHOLE as INSTRUMENTS
     from .generate import instrument_lines, instrument_params, unique_lines
     ap = build_parser()
     args = ap.parse_args(argv)
@@ -156,6 +165,10 @@ def main(argv=None):
         from .diffusion import bond_order
         current.bond_order = bond_order.bond_order_sample_result(current, asked["bond_order"], args.device)
         report("bond_order", current)
+    if asked["voronoi"] is not None:  # (of the same crystals)
+        from .diffusion import voronoi
+        current.voronoi = voronoi.voronoi_sample_result(current, asked["voronoi"], args.device)
+        report("voronoi", current)
     if args.out:
         print("wrote", save_sample_results_to_hdf5(current, args.out))
     return res

@@ -428,6 +428,121 @@ int arreau_crystal_bond_order(const float* d_frac, const float* d_lattice, const
                               const int32_t* d_cn, const int32_t* d_neighbors, const arreau_bond_order_params* params,
                               arreau_bond_order_result* out, void* stream);
 
+/* ---- Voronoi cells of generated crystals: solid-angle-weighted neighbours, atom volumes -------------------------------
+ * Per atom the faces of its Voronoi cell over every periodic image: the neighbours are the atoms whose bisecting planes bound
+ * the cell, each with the solid angle its face subtends, the face's area and the distance; the WEIGHT of a face is its solid
+ * angle over the atom's largest (pymatgen VoronoiNN's weight, where CrystalNN starts); the cell's volume comes with it.  Table
+ * free: no radii, no electronegativities, no distance weighting, no probabilities -- not CrystalNN; plain (not radical, not
+ * weighted) Voronoi cells; no polyhedron names.  One launch, one workgroup of four waves per crystal, one wave per atom
+ * (i = wave, wave + 4, ...), no atomics, no arreau_model.  The distances of rule 1 are one float32 operation at a time; the
+ * planes of rule 2 are solved and tested in float64 from those float32 displacements, taken as exact; the faces of rule 3 are
+ * plain float32 (the compiler may fuse a multiply-add).  The order of every sum is fixed, so a result does not depend on the
+ * launch or the batch, but no float32 host restatement matches it bit for bit: arreau_amd/diffusion/voronoi.py restates the rules
+ * with the same split of precisions, and in float64 throughout.
+ *   0. cell, NONFINITE, CELL, images, positions: the coordination rule 1 with search_radius = cutoff.  For NONFINITE and CELL
+ *      nothing else is computed: the reals are NaN, neighbors -1, the counts 0, min_cn and max_cn -1, no other flag.
+ *   1. CANDIDATES of atom i: every (j, m) but (i, (0, 0, 0)) with d2 <= r2 = (float)((double)cutoff * cutoff), d2 and disp formed
+ *      exactly as in the coordination rule 2, gathered in ascending (j, m) by ballot.  d_e = disp as float64, h_e = |d_e|^2 / 2
+ *      and |d_e| in float64 (the plane bisects the displacement the kernel holds); the stored distance is sqrt(d2) in float32.
+ *      More than max_candidates of them: the atom is OVERFLOW, its reals NaN, its cn 0, its list -1.  No candidate is dropped
+ *      early: the security-radius rule (farther than twice the largest vertex radius of a closed cell of nearer candidates) is
+ *      not used, every candidate within the cutoff takes part.  An atom with a candidate at d2 == 0 shares its site and has no
+ *      cell: it is OVERLAP, its reals NaN, its cn 0, its list -1 (an atom that merely sees such a pair meets each of their
+ *      planes twice and fails the closure test of rule 5).
+ *   2. VERTICES of face a (a = 0 .. K-1 in candidate order): for b = 0 .. K-1, b != a, lanes take c = b+1 .. K-1, c != a; v
+ *      solves d_a.v = h_a, d_b.v = h_b, d_c.v = h_c by Cramer's rule, det = (d_a x d_b).d_c, v = (h_a d_b x d_c + h_b d_c x d_a +
+ *      h_c d_a x d_b) / det.  The triple is SKIPPED when det == 0 or |det| < ARREAU_VORONOI_DET_TOL |d_a||d_b||d_c|.  v is
+ *      ACCEPTED iff d_e.v - h_e <= ARREAU_VORONOI_PLANE_TOL * cutoff * |d_e| for every candidate e other than a, b, c
+ *      (inclusive: v may lie up to PLANE_TOL * cutoff beyond a plane).  The planes are tested in ascending distance and the loop
+ *      ends when no lane's vertex is left, which does not change the answer.  The hits are compacted by ballot in (b, c) order
+ *      into the face's own list, at most ARREAU_VORONOI_FACE_VERTICES; more (only copies of degenerate vertices can make so many)
+ *      make the atom OVERFLOW.  A vertex where q > 3 planes meet appears (q-1 choose 2) times in a face's list; the copies span
+ *      fan triangles of zero area, so nothing is de-duplicated.
+ *      Everything in this rule is float64.  Float32 does not suffice: with u = 2^-24 the bound below demands DET_TOL near
+ *      1e-2, and so coarse a DET_TOL skips real, ill-conditioned vertices of irregular crystals whose loss moves omega_sum by
+ *      less than CLOSURE_TOL (up to 6.5e-4 on random crystals in the float64 restatement), so the certificate would pass cells
+ *      that are wrong in the fourth digit.  In float64, with u = 2^-53 and R = cutoff: Cramer's numerator has three terms of at most h |d||d| each, each with about 8 u relative
+ *      rounding, and |det| >= DET_TOL |d_a||d_b||d_c|, so |dv| <= 8 u (|d_a| + |d_b| + |d_c|) / (2 DET_TOL) <= 12 u R / DET_TOL.
+ *      DET_TOL = 1e-6 (three normals within a few 1e-5 degrees of one plane) makes that 1.4e-9 R; PLANE_TOL = 1e-6 is some 700
+ *      times it, and small enough that what it lets in is harmless: a vertex accepted up to s beyond a plane adds a triangle
+ *      of area about s^2 to a face (the true vertices next to it are accepted too), 4e-11 A^2 at R = 6 A.  Exactly degenerate
+ *      vertices (sc, fcc) are degenerate in the float32 displacements too and fall inside the slack, and so do those the
+ *      rounding of the inputs splits by less than it (ideal hcp given in float32: split by 1e-7 A, rejoined, closed to 4e-7
+ *      sr); vertices split by more are the several true vertices of the cell the kernel was given.
+ *   3. per FACE (a candidate with at least three accepted vertices): g = the mean of its vertices (lane sums, then the
+ *      butterfly v <- v + shuffle_xor(v, w), w = 32 .. 1); n = d_a / |d_a|; t = the coordinate axis with the smallest |n_t| (x
+ *      before y before z on ties); u1 = (n x t) / |n x t|, u2 = n x u1; angle(v) = atan2((v - g).u2, (v - g).u1); the vertices
+ *      sorted by ascending angle, ties in list order: w_0 .. w_{k-1} (the vertices rounded to float32; all of rule 3 is float32).  area = sum_k n.((w_k - g) x (w_{k+1} - g)) / 2 (cyclic);
+ *      solid_angle = sum_k 2 atan2(g.(w_k x w_{k+1}), |g||w_k||w_{k+1}| + (g.w_k)|w_{k+1}| + (g.w_{k+1})|w_k| + (w_k.w_{k+1})|g|)
+ *      (Van Oosterom & Strackee 1983); both sums by lane (k, k + 64) and the butterfly.  distance = |d_a|.
+ *   4. per ATOM: max_solid = the largest solid angle of its faces; weight_f = max(solid_angle_f, 0) / max_solid, and 0 for every
+ *      face when max_solid is not > 0 (a face of zero area -- a second neighbour of sc or fcc that touches the cell in an edge
+ *      or a corner -- has a solid angle that is rounding noise of either sign: it weighs 0); cn = the number of faces with
+ *      weight >= tol (exact); at tol = 0 that is every face, the zero-area ones included, so count neighbours with a tol above
+ *      0; cn_eff = the sum of all faces' weights; omega_sum = the sum of their solid angles;
+ *      volume = sum area * distance / 6; max_radius = the largest |v| of an accepted vertex (sums: lane k holds faces k and
+ *      k + 64, then the butterfly).  neighbors holds the first max_faces faces of weight >= tol in ascending (j, m), (j, n_1,
+ *      n_2, n_3) each with j local to the crystal, -1 beyond: the coordination result's layout, so arreau_crystal_bond_order
+ *      reads cn and neighbors as they are.  face_weight, face_solid_angle, face_area, face_distance [N, max_faces] in the same
+ *      order, NaN beyond.  cn > max_faces sets TRUNCATED.
+ *   5. the CERTIFICATE.  An atom is OPEN when 2 max_radius > cutoff (an atom beyond the cutoff could still cut the cell) or
+ *      not (|omega_sum - 4 pi| <= ARREAU_VORONOI_CLOSURE_TOL) (a vertex was lost to DET_TOL, or the candidates close no cell; an
+ *      atom without candidates is OPEN).  CLOSURE_TOL = 1e-3 sr: a lost vertex or a wrong face moves a solid angle by 1e-3 or
+ *      more, the float32 sum of a closed cell stays within some 1e-5.  An OPEN atom keeps its numbers.  atom_flags [N] holds
+ *      each atom's OVERLAP, OPEN, OVERFLOW and TRUNCATED bits.
+ *   6. per crystal: n_faces = sum cn, min_cn, max_cn (-1 without atoms), mean_cn = (float)n_faces / (float)n, mean_cn_eff = (sum
+ *      cn_eff) / (float)n, volume_sum = sum volume (each wave adds its atoms in order, the four waves are added in order; NaN
+ *      when an atom is OVERFLOW or OVERLAP; NaN without atoms).  flags: the OR of the atoms' bits, EMPTY n = 0, and NONFINITE / CELL.
+ * Offsets are clamped as in the screen.  The defaults (tol 0.05, cutoff 6 A) are starting values, not claims.
+ * Argument errors (ARREAU_EINVAL, nothing launched): NULL params / result / arrays, negative sizes, tol not finite or outside
+ * [0, 1], cutoff not finite or <= 0, max_faces outside 1..ARREAU_VORONOI_MAX_FACES, max_candidates outside
+ * 1..ARREAU_VORONOI_MAX_CANDIDATES, max_shells outside 1..ARREAU_SCREEN_MAX_SHELLS, neighbors not 16-byte aligned.  B == 0
+ * returns ARREAU_OK. */
+#define ARREAU_VORONOI_NONFINITE 1
+#define ARREAU_VORONOI_CELL 2
+#define ARREAU_VORONOI_EMPTY 4
+#define ARREAU_VORONOI_OVERLAP 8
+#define ARREAU_VORONOI_OPEN 16
+#define ARREAU_VORONOI_OVERFLOW 32
+#define ARREAU_VORONOI_TRUNCATED 64
+#define ARREAU_VORONOI_MAX_FACES 64
+#define ARREAU_VORONOI_MAX_CANDIDATES 128
+#define ARREAU_VORONOI_FACE_VERTICES 128
+#define ARREAU_VORONOI_DET_TOL 1e-6   /* float64 */
+#define ARREAU_VORONOI_PLANE_TOL 1e-6 /* float64 */
+#define ARREAU_VORONOI_CLOSURE_TOL 1e-3f
+typedef struct arreau_voronoi_params {
+    float tol;               /* a face counts when its weight >= tol, in [0, 1]; default 0.05 (a starting value, not a claim) */
+    float cutoff;            /* A; default 6.0 */
+    int32_t max_faces;       /* stored per atom, 1..ARREAU_VORONOI_MAX_FACES; default 32 */
+    int32_t max_candidates;  /* 1..ARREAU_VORONOI_MAX_CANDIDATES; default 128 */
+    int32_t max_shells;      /* cap on the images per axis, 1..ARREAU_SCREEN_MAX_SHELLS; default 8 */
+} arreau_voronoi_params;
+typedef struct arreau_voronoi_result { /* DEVICE arrays */
+    int32_t* n_faces;         /* [B] */
+    int32_t* min_cn;          /* [B] */
+    int32_t* max_cn;          /* [B] */
+    float* mean_cn;           /* [B] */
+    float* mean_cn_eff;       /* [B] */
+    float* volume_sum;        /* [B] */
+    int32_t* flags;           /* [B] ARREAU_VORONOI_* */
+    int32_t* cn;              /* [N] */
+    int32_t* neighbors;       /* [N, max_faces, 4] j, n_1, n_2, n_3; 16-byte aligned */
+    float* face_weight;       /* [N, max_faces] */
+    float* face_solid_angle;  /* [N, max_faces] */
+    float* face_area;         /* [N, max_faces] */
+    float* face_distance;     /* [N, max_faces] */
+    float* volume;            /* [N] */
+    float* omega_sum;         /* [N] */
+    float* max_radius;        /* [N] */
+    float* cn_eff;            /* [N] */
+    int32_t* atom_flags;      /* [N] OVERLAP | OPEN | OVERFLOW | TRUNCATED */
+} arreau_voronoi_result;
+/* d_frac, d_lattice, d_crystal_offsets as for the coordination search.  `params` and `out` are HOST pointers to the structs; the
+ * arrays `out` names are device arrays. */
+int arreau_crystal_voronoi(const float* d_frac, const float* d_lattice, const int32_t* d_crystal_offsets, int32_t B, int32_t N,
+                           const arreau_voronoi_params* params, arreau_voronoi_result* out, void* stream);
+
 /* ---- duplicate detection: structure fingerprints and their all-pairs match ------------------------------------------
  * The screen's sibling: per crystal a reduced formula and a fingerprint of its pair distribution (Oganov & Valle, J. Chem.
  * Phys. 130, 104504 (2009), with the normalisation taken at the bin centre so that it is finite for every input), and for
