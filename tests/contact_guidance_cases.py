@@ -2,6 +2,8 @@
 contact of a case has d >= MIN_D and every pair and image a margin |d - d0| >= MIN_MARGIN, except where a case says otherwise
 (`overlap`: the coincident pair); the CPU test checks this, so a case that misses it cannot pass silently.  Inputs are float32: the
 kernel's own; the float64 restatement reads the same values."""
+import functools
+
 import numpy as np
 
 from arreau_amd.diffusion.contact_guidance import CELL, EMPTY, NONFINITE, OVERLAP, ContactGuidance
@@ -108,6 +110,69 @@ def ragged_case(seed=15):
     frac = rng.uniform(0, 1, (sum(counts), 3))
     frac[1:3] = [[0.2, 0.3, 0.4], [0.2, 0.3, 0.5]]  # the two-atom crystal holds a contact
     return GuidanceCase("ragged", frac, cells, counts, ContactGuidance(min_distance=0.9, weight=0.5), t=[1, 2, T // 2, T - 1, T])
+
+
+BIG_CELL = ((11.5, 16.7, 26.0), (76.1, 72.7, 102.0))  # the big cell of the match and reduction cases
+LOOP_PARAMS = ContactGuidance(min_distance=2.0, weight=0.3)  # the loop tests' parameters
+LARGE_N = 257  # one atom more than the kernel stages in LDS (CRYSTAL_LDS_ATOMS = 256)
+
+
+def large_case(seed=257, n=LARGE_N):
+    """257 atoms in the big cell, d0 = 2.0: atoms 0..255 uniform with the third fraction squeezed into [0.05, 0.70], atom 256 alone
+    at (0.5, 0.5, 0.875), farther than d0 from every atom and image.  n = 256 is the same crystal without its last atom: the
+    largest the kernel stages in LDS, with the same cell and so the same image count M."""
+    rng = np.random.RandomState(seed)
+    frac = rng.uniform(0, 1, (LARGE_N - 1, 3))
+    frac[:, 2] = 0.05 + 0.65 * frac[:, 2]
+    frac = np.concatenate([frac, [[0.5, 0.5, 0.875]]])[:n]
+    return GuidanceCase("large" if n == LARGE_N else f"large{n}", frac, cell_from_params(*BIG_CELL), [n], LOOP_PARAMS)
+
+
+def large_between_small():
+    """`large` between two small crystals of the same parameters: the block in front and the block behind must not matter."""
+    frac = [[0.10, 0.20, 0.30], [0.30, 0.30, 0.40], [0.80, 0.15, 0.85]]  # 0.98 A between the first two
+    small = [GuidanceCase(f"small{k}", frac, CUBE4, [3], LOOP_PARAMS) for k in range(2)]
+    return batch_of("large", [small[0], large_case(), small[1]])
+
+
+def eight_shells_case():
+    """Three atoms in diag(4, 4, 0.26) with d0 = 2.0: 2.0 / 0.26 = 7.7, eight images along c, accepted at max_shells = 8.  Its twin in
+    diag(4, 4, 0.24) needs nine and is CELL.  One batch: an accepted 17-image axis next to a rejected one."""
+    frac = [[0.10, 0.20, 0.10], [0.40, 0.30, 0.45], [0.70, 0.62, 0.80]]
+    return GuidanceCase("eight shells", frac + frac, [np.diag([4.0, 4.0, 0.26]), np.diag([4.0, 4.0, 0.24])], [3, 3], LOOP_PARAMS, flags=[0, CELL])
+
+
+SEVENTY_COUNTS = [1, 2, 7, 20, 65] * 14
+
+
+@functools.lru_cache(maxsize=None)
+def seventy_case(seed=70):
+    """70 crystals, counts cycling through 1, 2, 7, 20, 65, at timesteps spread evenly over 1..T (both ends included); cells and
+    parameters as `ragged`.  Among some 10^6 pairs and images a random draw holds one within 1e-3 A of d0, so every crystal is
+    drawn again (from the same generator) until it keeps MIN_D and MIN_MARGIN: a condition on the float64 restatement alone."""
+    from arreau_amd.diffusion.contact_guidance import reference
+    rng = np.random.RandomState(seed)
+    params = ContactGuidance(min_distance=0.9, weight=0.5)
+    crystals = []
+    for b, n in enumerate(SEVENTY_COUNTS):
+        for _ in range(1000):
+            one = GuidanceCase(f"seventy[{b}]", rng.uniform(0, 1, (n, 3)), cell_from_params(rng.uniform(4.5, 6.5, 3), rng.uniform(70, 110, 3)), [n],
+                               params, t=[1 + (b * (T - 1)) // (len(SEVENTY_COUNTS) - 1)])
+            r = reference(one.frac, one.lattice, one.offsets, params)
+            if r.flags[0] == 0 and (r.margin[0].size == 0 or r.margin[0].min() >= 2 * MIN_MARGIN) and (r.d[0].size == 0 or r.d[0].min() >= 2 * MIN_D):
+                break
+        else:
+            raise AssertionError(f"no draw of crystal {b} keeps the margins")
+        crystals.append(one)
+    return batch_of("seventy", crystals)
+
+
+BAD_T = [0, -3, T + 1, 5, T]  # `ragged` at timesteps outside 1..T: clamped to [1, 1, T, 5, T] and flagged
+
+
+def launch_cases():
+    """The cases only the launch tests and the precondition test run (too large for the finite-difference tests)."""
+    return [large_between_small(), eight_shells_case(), seventy_case()]
 
 
 def all_cases():

@@ -14,6 +14,7 @@ from tests import contact_guidance_cases as cases
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = cases.all_cases()
 IDS = [c.name for c in CASES]
+LAUNCH_CASES = cases.launch_cases()  # one restatement each: too large for the finite-difference and invariance tests below
 
 
 def _ref(case, frac=None, lattice=None):
@@ -24,7 +25,7 @@ def _ref(case, frac=None, lattice=None):
 
 
 # ----------------------------------------------------------------------------------------------------- the cases themselves
-@pytest.mark.parametrize("case", CASES, ids=IDS)
+@pytest.mark.parametrize("case", CASES + LAUNCH_CASES, ids=IDS + [c.name for c in LAUNCH_CASES])
 def test_cases_hold_their_own_preconditions(case):
     """Every contact at d >= 0.05 A, every pair and image at least 1e-3 A from d0 (the coincident pair of `overlap` is skipped by
     the rule and so by the margin), flags and contacts as the case states them."""
@@ -60,6 +61,46 @@ def test_cases_cover_what_they_are_for():
     assert by["ragged"].contacts[4] > 10 and by["ragged"].contacts[1] == 1
     mixed = cases.mixed_batch()
     assert list(_ref(mixed).flags) == [0, cg.NONFINITE, 0, cg.EMPTY, cg.OVERLAP, 0]
+
+
+def test_launch_cases_cover_what_they_are_for():
+    """`large`: 257 atoms (one past the staged path) between two small crystals, at least 300 contacts, the last atom without one
+    and farther than d0 from every atom and image, every margin decided; the 256-atom crystal is its first 256 atoms in the same
+    cell with the same shells, so the same image count.  `eight shells`: [1, 1, 8] accepted next to a CELL twin.  `seventy`: 70
+    crystals, the counts of `ragged` cycling, timesteps from 1 to T.  The forces of every unflagged crystal sum to zero."""
+    from arreau_amd.diffusion import crystal_batch as cb
+    by = {c.name: (c, _ref(c)) for c in LAUNCH_CASES}
+    big, r = by["large"]
+    a, e = big.offsets[1], big.offsets[2]
+    assert big.counts == [3, cases.LARGE_N, 3] and cases.LARGE_N == 257 and list(r.flags) == [0, 0, 0]
+    assert r.contacts[0] > 0 and r.contacts[2] == r.contacts[0]  # the neighbours in the batch are guided too
+    assert r.contacts[1] >= 300 and r.atom_contacts[e - 1] == 0 and r.margin[1].min() >= 1e-3
+    L = big.lattice[1].astype(np.float64)
+    p = cg._wrap(big.frac[a:e]).astype(np.float64) @ L
+    s = cb.shift_table(r.shells[1])[0] @ L
+    d0 = float(np.float32(big.params.min_distance))
+    assert np.linalg.norm(p[:-1, None, :] + s[None] - p[-1], axis=-1).min() > d0
+    assert np.linalg.norm(s[np.abs(s).sum(1) > 0], axis=1).min() > d0  # its own images too
+    less = cases.large_case(n=256)
+    r256 = _ref(less)
+    assert np.array_equal(less.frac, big.frac[a:e - 1]) and np.array_equal(less.lattice[0], big.lattice[1])
+    assert list(r256.shells[0]) == list(r.shells[1]) and r256.contacts[0] == r.contacts[1]
+    assert np.array_equal(r256.atom_contacts, r.atom_contacts[a:e - 1])  # the same contacts; the float64 sums in numpy's order
+    assert abs(r256.U[0] - r.U[1]) <= 1e-12 * r.U[1] and np.abs(r256.g - r.g[a:e - 1]).max() <= 1e-12 * np.abs(r256.g).max()
+    eight, r8 = by["eight shells"]
+    assert list(r8.shells[0]) == [1, 1, 8] and list(r8.flags) == [0, cg.CELL] and r8.contacts[0] > 0 and eight.params.max_shells == 8
+    assert r8.margin[0].min() >= 1e-3 and np.array_equal(eight.frac[:3], eight.frac[3:])
+    sev, r70 = by["seventy"]
+    assert sev.B == 70 and sev.counts == [1, 2, 7, 20, 65] * 14 and not r70.flags.any()
+    assert sev.t[0] == 1 and sev.t[-1] == cases.T and (np.diff(sev.t) >= 1).all() and len(set(sev.t.tolist())) == 70
+    assert (r70.contacts[4::5] > 10).all()
+    assert list(np.clip(cases.BAD_T, 1, cases.T)) == [1, 1, cases.T, 5, cases.T] and len(cases.BAD_T) == cases.ragged_case().B
+    for case, ref in list(by.values()) + [(cases.ragged_case(), _ref(cases.ragged_case()))]:
+        for b in range(case.B):
+            if not ref.flags[b] & cg.SKIPPED:
+                x, y = case.offsets[b], case.offsets[b + 1]
+                # sum_i g_i L = sum_i D_i = 0: every contact is seen from both ends with opposite displacements
+                assert np.abs((ref.g[x:y] @ case.lattice[b].astype(np.float64)).sum(0)).max() <= 1e-12, (case.name, b)
 
 
 # ----------------------------------------------------------------------------------------------------- gradient

@@ -1,6 +1,9 @@
 """Contact guidance on the GPU (rules in include/arreau_hip.h, "contact guidance"; diffusion/contact_guidance.py): the guidance
 launch against the float64 restatement within the derived float32 bounds, its reproducibility, the guided loop against its steps
-bit for bit, the step identity, and the paths that must not change."""
+bit for bit, the step identity, and the paths that must not change.  The launch cases reach 257 atoms in one crystal (the path
+that does not stage positions in LDS), eight image shells, 70 crystals and timesteps outside 1..T; the kernel's 64-bit index
+branch (n M above 2^32 - 64: about 900 000 atoms in one crystal at the largest M) stays untested.  The loop under the other
+predictor forms: tests/test_gpu_contact_guidance_forms.py, which imports `chain`, `guided_scores` and `draws` from here."""
 import ctypes
 
 import numpy as np
@@ -20,7 +23,7 @@ SNR = 0.16
 GUIDE = cg.ContactGuidance(min_distance=2.0, weight=0.3)  # the loop tests': wide enough that the random crystals hold contacts
 FLAT_BATCH = cases.batch_of("flat+pair", [cases.flat_case(), cases.GuidanceCase("pair1", cases.pair_case().frac, cases.pair_case().lattice, [2],
                                                                                cases.flat_case().params, contacts=[1])])
-STEP_CASES = cases.all_cases() + [cases.mixed_batch(), FLAT_BATCH]
+STEP_CASES = cases.all_cases() + [cases.mixed_batch(), FLAT_BATCH] + cases.launch_cases()  # (`large`: the unstaged path; `eight shells`)
 
 assert cases.T == T
 
@@ -108,10 +111,25 @@ def test_diagnostics_are_optional_and_weight_zero_adds_nothing(dev, fused_model)
     assert np.array_equal(zero, eps) and all(_same_bytes(info[q], info0[q]) for q in cg.INFO_KEYS)
 
 
-@pytest.mark.parametrize("which", ["mixed", "ragged"])
+@pytest.mark.parametrize("which", ["mixed", "ragged", "seventy"])
 def test_a_crystal_gives_the_same_bits_wherever_it_sits_in_the_batch(dev, fused_model, which):
+    """`mixed` and `ragged`: the batch in another order.  `seventy`: its first crystal, its last and a 65-atom one launched alone
+    (each at its own timestep) against their rows of the 70-crystal launch."""
     m, _ = fused_model
     eng = m.engine()
+    if which == "seventy":
+        base = cases.seventy_case()
+        eps = np.random.RandomState(9).normal(size=base.frac.shape).astype(np.float32)
+        got, info = _guide_step(eng, base, dev, eps)
+        assert base.counts[34] == 65
+        for b in (0, base.B - 1, 34):
+            a, e = base.offsets[b], base.offsets[b + 1]
+            alone, info_1 = _guide_step(eng, base.crystal(b), dev, eps[a:e])
+            assert _same_bytes(alone, got[a:e]), b
+            for q in cg.INFO_KEYS:
+                assert info_1[q].tobytes() == info[q][b:b + 1].tobytes(), (b, q)
+        assert info["contacts"][34] > 10 and not _same_bytes(got, eps)
+        return
     base = cases.mixed_batch() if which == "mixed" else cases.ragged_case()
     order = [3, 5, 0, 4, 2, 1] if which == "mixed" else [4, 2, 0, 3, 1]
     moved = cases.batch_of("moved", [base], order)
@@ -126,39 +144,144 @@ def test_a_crystal_gives_the_same_bits_wherever_it_sits_in_the_batch(dev, fused_
             assert info_m[q][at:at + 1].tobytes() == info[q][b:b + 1].tobytes(), (which, b, q)
 
 
+def test_the_unstaged_path_gives_the_staged_path_s_bits(dev, fused_model):
+    """`large` (257 atoms: positions formed from global memory at every use) against the same crystal without its last atom (256:
+    staged in LDS).  The two share the cell, hence the image count M.  Lane l of atom i's wave walks e = l, l + 64, ... of
+    e = j M + m in both, so it meets the same contacts in the same order; the extra range e in [256 M, 257 M) is atom 256, which is
+    farther than d0 from everything and adds nothing to any sum (the CPU test asserts it).  Atom 256 belongs to wave 0, which adds
+    wave_sum(0) = 0 to its energy after the last of its atoms: x + 0 is x.  So eps' of atoms 0..255, the energy and the contacts
+    must be the same bytes, provided crystal_cart from global memory and from LDS are "the same values" as the kernel says."""
+    m, _ = fused_model
+    eng = m.engine()
+    big, less = cases.large_case(), cases.large_case(n=256)
+    assert big.counts == [257] and less.counts == [256] and np.array_equal(big.frac[:256], less.frac)
+    eps = np.random.RandomState(11).normal(size=big.frac.shape).astype(np.float32)
+    got, info = _guide_step(eng, big, dev, eps)
+    got_less, info_less = _guide_step(eng, less, dev, eps[:256])
+    assert _same_bytes(got[:256], got_less) and _same_bytes(got[256:], eps[256:])  # (the lone atom: eps + k 0)
+    assert all(_same_bytes(info[q], info_less[q]) for q in cg.INFO_KEYS)
+    assert info["contacts"][0] >= 300 and info["flags"][0] == 0 and not _same_bytes(got_less, eps[:256])
+    eng.check_status()
+
+
+def test_timesteps_outside_the_schedule_are_clamped_and_flagged(dev, fused_model):
+    """`ragged` at t = [0, -3, T + 1, 5, T]: eps' is guided_eps at the clamped timesteps [1, 1, T, 5, T] within the bounds of
+    test_step_matches_the_restatement and the same bytes as the launch at the clamped timesteps; STATUS_BAD_TIMESTEP is set by the
+    first launch and not by the second."""
+    from arreau_amd import _hip
+    m, _ = fused_model
+    eng = m.engine()
+    base = cases.ragged_case()
+    bad = cases.GuidanceCase("bad t", base.frac, base.lattice, base.counts, base.params, t=cases.BAD_T)
+    good = cases.GuidanceCase("clamped t", base.frac, base.lattice, base.counts, base.params, t=np.clip(cases.BAD_T, 1, T))
+    ref = cg.reference(base.frac, base.lattice, base.offsets, base.params)
+    sig = _sigmas(m)
+    k = cg.sigma_coefficient(sig, bad.t, base.params.weight)
+    assert np.array_equal(k, cg.sigma_coefficient(sig, good.t, base.params.weight)) and k[0] == k[1] != k[3]
+    eps = np.random.RandomState(12).normal(size=base.frac.shape).astype(np.float32)
+    eng.status(reset=True)
+    got, info = _guide_step(eng, bad, dev, eps)
+    assert eng.status(reset=True)["flags"] & _hip.STATUS_BAD_TIMESTEP
+    clamped, info_c = _guide_step(eng, good, dev, eps)
+    assert eng.status(reset=True)["flags"] == 0
+    assert _same_bytes(got, clamped) and all(_same_bytes(info[q], info_c[q]) for q in cg.INFO_KEYS)
+    want = cg.guided_eps(eps, ref, base.offsets, sig, bad.t, base.params)
+    d0 = float(np.float32(base.params.min_distance))
+    assert list(info["contacts"]) == list(ref.contacts) and not info["flags"].any()
+    for b in range(base.B):
+        a, e = base.offsets[b], base.offsets[b + 1]
+        gb = cg.g_bound(d0, ref.d_min[b], base.lattice[b], ref.shells[b], int(ref.atom_contacts[a:e].max()))
+        assert (np.abs(got[a:e].astype(np.float64) - want[a:e]) <= cg.eps_bound(k[b], gb, ref.g[a:e], want[a:e])).all(), b
+
+
+@pytest.mark.parametrize("name", ["ragged", "large", "seventy"])
+def test_the_device_s_forces_sum_to_zero(dev, fused_model, name):
+    """Every contact pushes its two atoms with opposite forces, so sum_i D_i = sum_i g_i L = 0 in every unflagged crystal.  On the
+    device's own numbers (g from a launch on eps = 0, divided by k = w / sigma_t^2): each g_i is within g_bound + 6 u max|g| of the
+    exact one (g_bound; k in float32 and the product, as in test_step_matches_the_restatement), the exact ones sum to zero, so per
+    Cartesian component d, |sum_i (g_i L)_d| <= n (g_bound + 6 u max|g|) sum_k |L_kd|.  The restatement supplies the bound's
+    arguments alone (d_min, shells, contacts per atom): its pair enumeration is not what the sum is compared with."""
+    m, _ = fused_model
+    eng = m.engine()
+    case = {c.name: c for c in [cases.ragged_case()] + cases.launch_cases()}[name]
+    ref = cg.reference(case.frac, case.lattice, case.offsets, case.params)
+    k = cg.sigma_coefficient(_sigmas(m), case.t, case.params.weight)
+    d0 = float(np.float32(case.params.min_distance))
+    g_dev, info = _guide_step(eng, case, dev, np.zeros_like(case.frac))
+    checked = 0
+    for b in range(case.B):
+        a, e = case.offsets[b], case.offsets[b + 1]
+        if info["flags"][b] & cg.SKIPPED or ref.ordered[b] == 0:
+            assert not g_dev[a:e].any()
+            continue
+        L = case.lattice[b].astype(np.float64)
+        g = g_dev[a:e].astype(np.float64) / k[b]
+        gb = cg.g_bound(d0, ref.d_min[b], L, ref.shells[b], int(ref.atom_contacts[a:e].max()))
+        total = np.abs((g @ L).sum(0))
+        bound = (e - a) * (gb + 6 * cg.U32 * np.abs(g).max()) * np.abs(L).sum(0)
+        print(f"{name}[{b}]: n {e - a}, |sum g L| {total.max():.3g} of bound {bound.min():.3g}, largest |g L| {np.abs(g @ L).max():.3g}")
+        assert (total <= bound).all(), (b, total, bound)
+        checked += 1
+    assert checked >= {"ragged": 3, "large": 3, "seventy": 28}[name]
+    eng.check_status()
+
+
 # ------------------------------------------------------------------------------------------- the loop against its steps
-def _chain(eng, case, form, steps, successors, seeds=None):
-    """predict_scores -> contact_guidance_step -> (corrector_step -> predict_scores -> contact_guidance_step ->) the step export fed
-    the filled draws, for every step; the cell the evaluation saw is lattice_from_params of the state's lengths.  Returns the
-    state and the info of the last evaluation."""
-    B, N, dev = case.B, case.N, eng.device
-    f, ty, le, lat = case.fresh()
+def guided_scores(eng, state, an, off, t_c, info, params=GUIDE):
+    """One evaluation as the guided loop makes it: predict_scores, then contact_guidance_step on the cell the evaluation saw
+    (lattice_from_params of the state's lengths).  Returns (eps', logits, len0)."""
+    f, ty, le = state[:3]
+    eps, logits, len0 = eng.predict_scores(f, ty, le, an, t_c, off)
+    eng.contact_guidance_step(f, lattice_from_params(le, an), t_c, off, eps, (params, info))
+    return eps, logits, len0
+
+
+def draws(eng, seed, t, B, N, word=0):
+    """The loop's draws of timestep t, counter word `word`: z_lattice [B,3], z_frac [N,3], u_types [N,S]."""
+    return (eng.philox_fill_word(seed, t, 0, word, 3 * B).view(B, 3), eng.philox_fill_word(seed, t, 1, word, 3 * N).view(N, 3),
+            eng.philox_fill_word(seed, t, 2, word, N * S).view(N, S))
+
+
+def chain(eng, start, an, off, steps, successors, step, corrector=False, seed=SEED):
+    """predict_scores -> contact_guidance_step -> (corrector_step -> predict_scores -> contact_guidance_step ->) `step`, for every
+    step, from a copy of `start` = (frac, types, lengths, lattice).  `step(state, t, s, t_c, s_c, scores)` calls the form's step
+    export with its options on the state in place, fed the filled draws.  Returns the state and the info of the last evaluation."""
+    state = tuple(x.clone() for x in start)
+    B, N, dev = state[2].shape[0], state[0].shape[0], eng.device
     info = cg.allocate_info(B, dev)
-
-    def evaluate(t_c):
-        eps, logits, len0 = eng.predict_scores(f, ty, le, case.an, t_c, case.off)
-        eng.contact_guidance_step(f, lattice_from_params(le, case.an), t_c, case.off, eps, (GUIDE, info))
-        return eps, logits, len0
-
     for t, s in zip(steps, successors):
         t_c, s_c = full_i32(B, t, dev), full_i32(B, s, dev)
-        eps, logits, len0 = evaluate(t_c)
-        if form == "corrector":
-            eng.corrector_step(f, t_c, case.off, eps, eng.philox_fill_word(SEED, t, 5, 0, 3 * N).view(N, 3), SNR)
-            eps, logits, len0 = evaluate(t_c)
+        scores = guided_scores(eng, state, an, off, t_c, info)
+        if corrector:
+            eng.corrector_step(state[0], t_c, off, scores[0], eng.philox_fill_word(seed, t, 5, 0, 3 * N).view(N, 3), SNR)
+            scores = guided_scores(eng, state, an, off, t_c, info)
+        step(state, t, s, t_c, s_c, scores)
+    return state, info
+
+
+def _step_of(eng, case, form, seeds=None):
+    """The step exports of the forms of test_guided_loop_is_its_steps_bit_for_bit."""
+    B, N = case.B, case.N
+
+    def step(state, t, s, t_c, s_c, scores):
+        f, ty, le, lat = state
         if form == "keyed":
             z_l = eng.philox_fill_crystals(seeds, case.off, t, 0, per_crystal_width=3)
             z_f = eng.philox_fill_crystals(seeds, case.off, t, 1, per_atom_width=3)
             u_t = eng.philox_fill_crystals(seeds, case.off, t, 2, per_atom_width=S)
-            eng.reverse_step_species(f, ty, le, case.an, t_c, s_c, case.off, eps, logits, len0, z_l, z_f, u_t, lat, (None, 1.0), lattice_clipmax=CLIP)
-            continue
+            eng.reverse_step_species(f, ty, le, case.an, t_c, s_c, case.off, *scores, z_l, z_f, u_t, lat, (None, 1.0), lattice_clipmax=CLIP)
+            return
         z_l, z_f, u_t = (eng.philox_fill(SEED, t, 0, 3 * B).view(B, 3), eng.philox_fill(SEED, t, 1, 3 * N).view(N, 3),
                          eng.philox_fill(SEED, t, 2, N * S).view(N, S))
         if form == "respaced-eta0":
-            eng.reverse_step_eta(f, ty, le, case.an, t_c, s_c, case.off, eps, logits, len0, None, None, u_t, lat, 0.0, None, CLIP)
+            eng.reverse_step_eta(f, ty, le, case.an, t_c, s_c, case.off, *scores, None, None, u_t, lat, 0.0, None, CLIP)
         else:
-            eng.reverse_step(f, ty, le, case.an, t_c, case.off, eps, logits, len0, z_l, z_f, u_t, lat)
-    return (f, ty, le, lat), info
+            eng.reverse_step(f, ty, le, case.an, t_c, case.off, *scores, z_l, z_f, u_t, lat)
+    return step
+
+
+def _chain(eng, case, form, steps, successors, seeds=None):
+    return chain(eng, case.fresh(), case.an, case.off, steps, successors, _step_of(eng, case, form, seeds), corrector=form == "corrector")
 
 
 @pytest.mark.parametrize("loop_prep", [None, "1"], ids=["no-prep", "prep-per-step"])
@@ -238,6 +361,30 @@ def test_another_weight_on_the_same_buffers_is_not_a_stale_replay(dev, fused_mod
         seen.append(bufs[0].clone())
     assert not torch.equal(seen[0], seen[1]) and not torch.equal(seen[1], seen[2]) and torch.equal(seen[2], seen[3])
     assert not torch.equal(seen[3], seen[4]) and torch.equal(seen[0], seen[5])
+    # guidance with another option on the same buffers: multistep, a tie, neither, multistep again
+    from arreau_amd.diffusion import multistep as ms
+    steps = [60, 45, 30, 1]
+    tie = torch.as_tensor([0, 1, 2], dtype=torch.int32, device=dev)
+    kw = dict(next_table=respacing.next_table(T, steps).to(dev), lattice_clipmax=CLIP)
+    hist = ms.allocate_history(case.N, case.B, dev)
+    seen = []
+    for option in ("multistep", "tie", None, "multistep"):
+        more = lambda h: {"multistep": dict(multistep=h), "tie": dict(length_tie=tie), None: {}}[option]
+        case.load(bufs)
+        for q in ms.HISTORY_KEYS:
+            hist[q].zero_()
+        eng.sample_loop(*bufs[:3], case.an, case.off, steps[0], len(steps), SEED, None, bufs[3], use_graph=True, guidance=(GUIDE, infos[0]), **kw,
+                        **more(hist))
+        want, want_info, want_hist = case.fresh(), cg.allocate_info(case.B, dev), ms.allocate_history(case.N, case.B, dev)
+        eng.sample_loop(*want[:3], case.an, case.off, steps[0], len(steps), SEED, None, want[3], use_graph=False, guidance=(GUIDE, want_info), **kw,
+                        **more(want_hist))
+        assert_same_bits(bufs, want, option)
+        assert_same_bits([infos[0][q] for q in cg.INFO_KEYS], [want_info[q] for q in cg.INFO_KEYS], (option, "info"))
+        if option == "multistep":
+            assert_same_bits([hist[q] for q in ms.HISTORY_KEYS], [want_hist[q] for q in ms.HISTORY_KEYS], "history")
+        seen.append([x.clone() for x in bufs])
+    assert_same_bits(seen[3], seen[0], "multistep again")
+    assert not torch.equal(seen[0][0], seen[2][0]) and not torch.equal(seen[1][2], seen[2][2]) and not torch.equal(seen[0][2], seen[1][2])
     eng.check_status()
 
 
