@@ -11,12 +11,6 @@
 
 namespace {
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = __fadd_rn(v, __shfl_xor(v, off, 64));
-    return v;
-}
-
 __global__ __launch_bounds__(CRYSTAL_THREADS) void contact_guide_kernel(
     const float* __restrict__ frac, const float* __restrict__ lattice, const int32_t* __restrict__ offsets,
     const int32_t* __restrict__ tstep, int B, int N, int T, const float* __restrict__ ve_sigmas, float d0, float md2 /* d0^2 */,
@@ -60,12 +54,7 @@ __global__ __launch_bounds__(CRYSTAL_THREADS) void contact_guide_kernel(
     const float sig = ve_sigmas[t];
     const float coef = __fdiv_rn(weight, __fmul_rn(sig, sig));
 
-    // ---- positions: staged in LDS when the crystal fits, else formed from global memory where they are used (same values)
-    const bool staged = n <= CRYSTAL_LDS_ATOMS;
-    if (staged)
-        for (int a = tid; a < 3 * n; a += CRYSTAL_THREADS) spos[a] = crystal_cart(frac, Lm, (size_t)first + a / 3, a % 3);
-    __syncthreads();
-    auto position = [&](int atom, int d) -> float { return staged ? spos[3 * atom + d] : crystal_cart(frac, Lm, (size_t)first + atom, d); };
+    const crystal_positions position = crystal_stage_positions(spos, frac, Lm, first, n);
 
     // ---- one wave per atom: i = wave, wave + 4, ...
     float u_wave = 0.0f;  // the wave's energies, ascending i (the same bits in every lane)
@@ -73,39 +62,22 @@ __global__ __launch_bounds__(CRYSTAL_THREADS) void contact_guide_kernel(
     for (int i = wave; i < n; i += CRYSTAL_WAVES) {
         const float pix = position(i, 0), piy = position(i, 1), piz = position(i, 2);
         float Dx = 0.0f, Dy = 0.0f, Dz = 0.0f, u = 0.0f;
-        auto contact = [&](int j, unsigned m) {
-            if (j == i) return;  // self images exert no force on positions
-            const unsigned m12 = m / cell.W3;
-            const float n3 = (float)((int)(m - m12 * cell.W3) - cell.N3), n2 = (float)((int)(m12 % cell.W2) - cell.N2), n1 = (float)((int)(m12 / cell.W2) - cell.N1);
-            const float dx = __fsub_rn(__fadd_rn(position(j, 0), rows_rn(Lm, 0, n1, n2, n3)), pix);
-            const float dy = __fsub_rn(__fadd_rn(position(j, 1), rows_rn(Lm, 1, n1, n2, n3)), piy);
-            const float dz = __fsub_rn(__fadd_rn(position(j, 2), rows_rn(Lm, 2, n1, n2, n3)), piz);
-            const float d2 = dot3_rn(dx, dy, dz, dx, dy, dz);
-            if (!(d2 < md2)) return;
-            if (d2 == 0.0f) { zero = 1; return; }
-            const float d = sqrtf(d2);  // correctly rounded
+        crystal_walk((unsigned long long)n * cell.M, cell.M, (unsigned)lane, 64u, [&](unsigned j, unsigned m) {
+            if ((int)j == i) return;  // self images exert no force on positions
+            const crystal_contact k = crystal_contact_at(cell, Lm, position, (int)j, m, pix, piy, piz);
+            if (!(k.d2 < md2)) return;
+            if (k.d2 == 0.0f) { zero = 1; return; }
+            const float d = sqrtf(k.d2);  // correctly rounded
             const float gap = __fsub_rn(d0, d);
             const float f = __fdiv_rn(gap, d);
-            Dx = __fadd_rn(Dx, __fmul_rn(f, dx));
-            Dy = __fadd_rn(Dy, __fmul_rn(f, dy));
-            Dz = __fadd_rn(Dz, __fmul_rn(f, dz));
+            Dx = __fadd_rn(Dx, __fmul_rn(f, k.dx));
+            Dy = __fadd_rn(Dy, __fmul_rn(f, k.dy));
+            Dz = __fadd_rn(Dz, __fmul_rn(f, k.dz));
             u = __fadd_rn(u, __fmul_rn(gap, gap));
             ++cnt;
-        };
-        const unsigned long long span = (unsigned long long)n * cell.M;
-        if (span <= 0xffffffffull - 64u) {  // (uniform) the usual case: 32-bit index arithmetic
-            for (unsigned e = (unsigned)lane; e < (unsigned)span; e += 64u) {
-                const unsigned j = e / cell.M;
-                contact((int)j, e - j * cell.M);
-            }
-        } else {
-            for (unsigned long long e = (unsigned long long)lane; e < span; e += 64ull) {
-                const unsigned long long j = e / cell.M;
-                contact((int)j, (unsigned)(e - j * cell.M));
-            }
-        }
-        Dx = wave_sum(Dx); Dy = wave_sum(Dy); Dz = wave_sum(Dz);
-        u_wave = __fadd_rn(u_wave, wave_sum(u));
+        });
+        Dx = crystal_wave_sum(Dx); Dy = crystal_wave_sum(Dy); Dz = crystal_wave_sum(Dz);
+        u_wave = __fadd_rn(u_wave, crystal_wave_sum(u));
         if (lane < 3) {  // g_k = (D . c_k) / V, eps' = eps + (w / sig^2) g_k
             const float* ck = lane == 0 ? c0 : (lane == 1 ? c1 : c2);
             const float g = __fdiv_rn(dot3_rn(Dx, Dy, Dz, ck[0], ck[1], ck[2]), vol);

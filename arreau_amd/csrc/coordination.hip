@@ -51,15 +51,13 @@ __global__ __launch_bounds__(CRYSTAL_THREADS) void crystal_coordination_kernel(
     }
     crystal_cell_images(cell);
 
-    // ---- positions: staged in LDS when the crystal fits, else formed from global memory where they are used (same values)
-    const bool staged = n <= CRYSTAL_LDS_ATOMS;
-    if (staged)
-        for (int a = tid; a < 3 * n; a += CRYSTAL_THREADS) spos[a] = crystal_cart(frac, Lm, (size_t)first + a / 3, a % 3);
-    __syncthreads();
-    auto position = [&](int atom, int d) -> float { return staged ? spos[3 * atom + d] : crystal_cart(frac, Lm, (size_t)first + atom, d); };
-
+    const crystal_positions position = crystal_stage_positions(spos, frac, Lm, first, n);
+    const bool staged = position.staged;
     const unsigned long long span = (unsigned long long)n * cell.M;  // receiver i meets e = j * M + m, 0 <= e < span
-    const bool narrow = span <= 0xffffffffull - 64;                  // (uniform) the usual case: 32-bit index arithmetic
+    // This kernel keeps its own copy of crystal_dev.h's walk and contact: it is at the limit of its scalar registers, and through
+    // crystal_walk / crystal_walk_chunks 59 of them go through vector lanes instead of 13.  Medians, MI355X, 1024 random crystals of
+    // 64 atoms: the parent's 546 us became 567 us through the walk helpers, 577 us through them and crystal_contact_at.
+    const bool narrow = crystal_walk_narrow(span, 64);  // (uniform) the usual case: 32-bit index arithmetic
 
     // ---- phase A: d2min(i), the minimum of the bits of d2 (d2 >= +0: the bits order like the values; inf keeps its place above
     // every finite value) over every (j, m) but the atom itself.  One wave per atom; the wave minimum is a min of integers.
@@ -68,7 +66,7 @@ __global__ __launch_bounds__(CRYSTAL_THREADS) void crystal_coordination_kernel(
         unsigned best = 0x7f800000u;
         auto contact = [&](unsigned j, unsigned m) {
             if (j == (unsigned)i && m == cell.centre) return;  // the atom itself; every other image of i counts
-            // the screen's operations, spelled out as there: called through the helper they are packed in pairs and the loop is slower
+            // crystal_contact_at's operations (see above)
             const unsigned m12 = m / cell.W3;
             const float n3 = (float)((int)(m - m12 * cell.W3) - cell.N3), n2 = (float)((int)(m12 % cell.W2) - cell.N2), n1 = (float)((int)(m12 / cell.W2) - cell.N1);
             const float sx = __fadd_rn(__fadd_rn(__fmul_rn(n1, Lm[0]), __fmul_rn(n2, Lm[3])), __fmul_rn(n3, Lm[6]));

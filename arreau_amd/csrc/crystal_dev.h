@@ -1,10 +1,70 @@
-// Device helpers shared by the per-crystal kernels (screen.hip, fingerprint.hip, symfind.hip, reduce.hip, symmetrize.hip, match.hip; one workgroup of CRYSTAL_WAVES waves
-// per crystal): the launch shape, the prologue, the cell and its image range, the wrap of a fractional coordinate and the Cartesian
-// position, one periodic contact, the compaction of a workgroup's hits in thread order, the rarest species, the squared
-// length of a fractional difference, the matrix of a rotation code, its integer inverse and the metric of a cell's image under
-// it.  One float32 rounding per operation.
+// Device helpers shared by the per-crystal kernels (one workgroup of CRYSTAL_WAVES waves per crystal): screen.hip, fingerprint.hip,
+// coordination.hip, bond_order.hip, voronoi.hip, contact_guide.hip, symfind.hip, reduce.hip, symmetrize.hip, conventional.hip and
+// match.hip.  What is here: the image walk (the flattened range e = j M + m dealt to threads by stride or in chunks, with 32-bit
+// index arithmetic where the range allows it); the launch shape; the prologue; the wrap of a fractional coordinate and the
+// Cartesian position; the positions staged in LDS; the cell and its image range; one periodic contact; the wave's butterfly sum and
+// its self-synchronisation; the compaction of a workgroup's hits in thread order; the rarest species; the squared length of a
+// fractional difference; the matrix of a rotation code, its integer inverse and the metric of a cell's image under it.  One
+// float32 rounding per operation.
 #pragma once
+
+// ---- the image walk.  Plain C++: tests/crystal_walk_host.cpp compiles this part with the host compiler alone.
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#define CRYSTAL_HD __host__ __device__ __forceinline__
+#else
+#define CRYSTAL_HD inline
+#endif
+
+// whether a walk of `span` entries by steps of `stride` stays inside 32 bits (the index may pass the span by one stride)
+CRYSTAL_HD bool crystal_walk_narrow(unsigned long long span, unsigned stride) { return span <= 0xffffffffull - stride; }
+
+// e = j M + m -> (j, m), in the arithmetic of E (unsigned, or unsigned long long where j M + m needs it)
+template <class E>
+CRYSTAL_HD void crystal_walk_index(E e, unsigned M, unsigned& j, unsigned& m) {
+    const E q = e / M;
+    j = (unsigned)q; m = (unsigned)(e - q * M);
+}
+
+template <class E, class F>
+CRYSTAL_HD void crystal_walk_as(E span, unsigned M, E start, unsigned stride, F& fn) {
+    for (E e = start; e < span; e += stride) {
+        unsigned j, m;
+        crystal_walk_index(e, M, j, m);
+        fn(j, m);
+    }
+}
+
+template <class E, class F>
+CRYSTAL_HD void crystal_walk_chunks_as(E span, unsigned M, unsigned lane, unsigned width, F& fn) {
+    for (E base = 0; base < span; base += width) {
+        const E e = base + lane;
+        unsigned j, m;
+        crystal_walk_index(e, M, j, m);
+        fn(e < span, j, m);
+    }
+}
+
+// fn(j, m) for e = start, start + stride, ... < span, ascending: a thread's or a lane's share of the range
+template <class F>
+CRYSTAL_HD void crystal_walk(unsigned long long span, unsigned M, unsigned long long start, unsigned stride, F&& fn) {
+    if (crystal_walk_narrow(span, stride) && start <= 0xffffffffull)  // (uniform) the usual case
+        crystal_walk_as<unsigned>((unsigned)span, M, (unsigned)start, stride, fn);
+    else
+        crystal_walk_as<unsigned long long>(span, M, start, stride, fn);
+}
+
+// fn(valid, j, m) for e = lane, lane + width, ... in rounds of `width` entries (lane < width): every thread of the wave or the
+// workgroup calls fn in every round, whether its own entry lies inside the span (valid) or not, so fn may hold ballots and barriers
+template <class F>
+CRYSTAL_HD void crystal_walk_chunks(unsigned long long span, unsigned M, unsigned lane, unsigned width, F&& fn) {
+    if (crystal_walk_narrow(span, width))  // (uniform) the usual case
+        crystal_walk_chunks_as<unsigned>((unsigned)span, M, lane, width, fn);
+    else
+        crystal_walk_chunks_as<unsigned long long>(span, M, lane, width, fn);
+}
+
+#if defined(__HIPCC__)  // ---- everything below is device code
 
 #define CRYSTAL_WAVES 4
 #define CRYSTAL_THREADS (64 * CRYSTAL_WAVES)
@@ -37,6 +97,24 @@ __device__ __forceinline__ float crystal_wrap(float f) {
 
 __device__ __forceinline__ float crystal_cart(const float* __restrict__ frac, const float* Lm, size_t atom, int d) {
     return rows_rn(Lm, d, crystal_wrap(frac[3 * atom]), crystal_wrap(frac[3 * atom + 1]), crystal_wrap(frac[3 * atom + 2]));
+}
+
+// The Cartesian positions of a crystal's atoms: staged in LDS when the crystal fits, else formed from global memory where they
+// are used (the same values).  crystal_stage_positions fills the caller's spos[3 * CRYSTAL_LDS_ATOMS]; one barrier, every thread
+// calls it (what else a caller stages ahead of the call is visible after it too).
+struct crystal_positions {
+    const float *spos, *frac, *Lm;
+    size_t first;
+    bool staged;
+    __device__ __forceinline__ float operator()(int atom, int d) const { return staged ? spos[3 * atom + d] : crystal_cart(frac, Lm, first + atom, d); }
+};
+
+__device__ __forceinline__ crystal_positions crystal_stage_positions(float* spos, const float* __restrict__ frac, const float* Lm, int first, int n) {
+    const bool staged = n <= CRYSTAL_LDS_ATOMS;
+    if (staged)
+        for (int a = threadIdx.x; a < 3 * n; a += CRYSTAL_THREADS) spos[a] = crystal_cart(frac, Lm, (size_t)first + a / 3, a % 3);
+    __syncthreads();
+    return {spos, frac, Lm, (size_t)first, staged};
 }
 
 // Crystal b's atom range (first, n), clamped into [0, N] so that a bad offset table cannot make a kernel read outside frac / types,
@@ -102,15 +180,39 @@ __device__ __forceinline__ void crystal_image(const crystal_cell& c, unsigned m,
     im[0] = (int)(m12 / c.W2) - c.N1; im[1] = (int)(m12 % c.W2) - c.N2; im[2] = (int)(m - m12 * c.W3) - c.N3;
 }
 
-// an atom at pi and image m of an atom at pj: s = (n1 L_0 + n2 L_1) + n3 L_2, disp = (pj + s) - pi, d2 = (dx dx + dy dy) + dz dz.
-// (screen.hip spells these operations out: through a helper they are packed in pairs, which costs its loop moves and wait states)
-__device__ __forceinline__ float contact_d2(const crystal_cell& c, const float* Lm, const float* pi, const float* pj, unsigned m) {
+// Receiver i at (pix, piy, piz) and image m of sender j: the image (n1, n2, n3), the shift s = (n1 L_0 + n2 L_1) + n3 L_2, the
+// displacement (p_j + s) - p_i and d2 = (dx dx + dy dy) + dz dz, in the one operation order every contact search uses.
+struct crystal_contact {
+    int n1, n2, n3;
+    float dx, dy, dz, d2;
+};
+
+template <class Position>
+__device__ __forceinline__ crystal_contact crystal_contact_at(const crystal_cell& c, const float* Lm, const Position& position, int j, unsigned m,
+                                                              float pix, float piy, float piz) {
     int im[3];
     crystal_image(c, m, im);
-    float disp[3];
+    crystal_contact k{im[0], im[1], im[2]};
+    const float n1 = (float)im[0], n2 = (float)im[1], n3 = (float)im[2];
+    const float sx = rows_rn(Lm, 0, n1, n2, n3), sy = rows_rn(Lm, 1, n1, n2, n3), sz = rows_rn(Lm, 2, n1, n2, n3);
+    k.dx = __fsub_rn(__fadd_rn(position(j, 0), sx), pix);
+    k.dy = __fsub_rn(__fadd_rn(position(j, 1), sy), piy);
+    k.dz = __fsub_rn(__fadd_rn(position(j, 2), sz), piz);
+    k.d2 = dot3_rn(k.dx, k.dy, k.dz, k.dx, k.dy, k.dz);
+    return k;
+}
+
+// v <- v + shuffle_xor(v, w), w = 32 .. 1: the wave's sum in a fixed order; every lane ends with the same bits (a + b == b + a)
+__device__ __forceinline__ float crystal_wave_sum(float v) {
 #pragma unroll
-    for (int d = 0; d < 3; ++d) disp[d] = __fsub_rn(__fadd_rn(pj[d], rows_rn(Lm, d, (float)im[0], (float)im[1], (float)im[2])), pi[d]);
-    return dot3_rn(disp[0], disp[1], disp[2], disp[0], disp[1], disp[2]);
+    for (int off = 32; off >= 1; off >>= 1) v = __fadd_rn(v, __shfl_xor(v, off));
+    return v;
+}
+
+// A wave that talks to itself: what one lane wrote (LDS or global memory) is read by the other lanes of its wave after this
+__device__ __forceinline__ void crystal_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __builtin_amdgcn_wave_barrier();
 }
 
 // This thread's rank among the workgroup's hits, in thread order, and their number.  One barrier, every thread calls it; `slots`
@@ -210,3 +312,5 @@ __device__ __forceinline__ void inverse_rotation(const int* W, int det, float* V
     V[3] = (float)(det * (W[5] * W[6] - W[3] * W[8])); V[4] = (float)(det * (W[0] * W[8] - W[2] * W[6])); V[5] = (float)(det * (W[2] * W[3] - W[0] * W[5]));
     V[6] = (float)(det * (W[3] * W[7] - W[4] * W[6])); V[7] = (float)(det * (W[1] * W[6] - W[0] * W[7])); V[8] = (float)(det * (W[0] * W[4] - W[1] * W[3]));
 }
+
+#endif  // __HIPCC__

@@ -1,7 +1,7 @@
 // Duplicate detection (arreau_crystal_fingerprint, arreau_fingerprint_match; the rules are written out in include/arreau_hip.h):
 // a reduced formula and a pair-distribution fingerprint per crystal, then for every crystal the earliest comparable crystal within
-// a tolerance.  Contacts are enumerated as screen.hip enumerates them: the cell and the image decode are crystal_dev.h's in both; the
-// contact's arithmetic is contact_d2 here and the same operations spelled out in screen.hip.  No atomics; no order of
+// a tolerance.  Contacts are enumerated as screen.hip enumerates them: the cell and the image walk are crystal_dev.h's in both, the
+// contact's arithmetic is crystal_contact_at here and the same operations kept in screen.hip's loop.  No atomics; no order of
 // summation depends on where a crystal sits in the batch.  Needs no arreau_model.
 #include "internal.h"
 #include "crystal_dev.h"
@@ -78,14 +78,10 @@ __global__ __launch_bounds__(CRYSTAL_THREADS) void crystal_fingerprint_kernel(
         for (int q = 0; q < K; ++q) r = s_species[q] == t ? q : r;
         return r;
     };
-    const bool staged = n <= CRYSTAL_LDS_ATOMS;
-    if (staged) {
-        for (int a = tid; a < 3 * n; a += CRYSTAL_THREADS) spos[a] = crystal_cart(frac, Lm, (size_t)first + a / 3, a % 3);
+    if (n <= CRYSTAL_LDS_ATOMS)
         for (int a = tid; a < n; a += CRYSTAL_THREADS) srank[a] = (unsigned char)rank_of(types[(size_t)first + a]);
-    }
-    __syncthreads();
-    auto position = [&](int atom, int d) -> float { return staged ? spos[3 * atom + d] : crystal_cart(frac, Lm, (size_t)first + atom, d); };
-    auto species_rank = [&](int atom) -> int { return staged ? (int)srank[atom] : rank_of(types[(size_t)first + atom]); };
+    const crystal_positions position = crystal_stage_positions(spos, frac, Lm, first, n);  // (its barrier covers the ranks)
+    auto species_rank = [&](int atom) -> int { return position.staged ? (int)srank[atom] : rank_of(types[(size_t)first + atom]); };
 
     // ---- the gather.  A thread owns bin `lane` of the components wave, wave + 4, ...; contacts inside r_cut are compacted into
     // the LDS list in enumeration order (i, j, m) and every cell adds the list's entries in that order.
@@ -112,28 +108,20 @@ __global__ __launch_bounds__(CRYSTAL_THREADS) void crystal_fingerprint_kernel(
     };
     int parity = 0;
     for (int i = 0; i < n; ++i) {
-        const float pi[3] = {position(i, 0), position(i, 1), position(i, 2)};
+        const float pix = position(i, 0), piy = position(i, 1), piz = position(i, 2);
         const int ri = species_rank(i);
-        const unsigned long long span = (unsigned long long)(n - i) * cell.M;
-        const bool narrow = span <= 0xffffffffull - CRYSTAL_THREADS;  // (uniform) the usual case: 32-bit index arithmetic
-        for (unsigned long long base = 0; base < span; base += CRYSTAL_THREADS) {
-            const unsigned long long e = base + (unsigned)tid;
+        crystal_walk_chunks((unsigned long long)(n - i) * cell.M, cell.M, (unsigned)tid, CRYSTAL_THREADS, [&](bool valid, unsigned dj, unsigned m) {
             bool hit = false;
             float R = 0.0f;
             int comp = 0;
-            if (e < span) {
-                const unsigned dj = narrow ? (unsigned)e / cell.M : (unsigned)(e / cell.M);
-                const unsigned m = narrow ? (unsigned)e - dj * cell.M : (unsigned)(e - (unsigned long long)dj * cell.M);
-                if (!(dj == 0 && m <= cell.centre)) {  // an atom with itself: only the images after (0, 0, 0)
-                    const int j = i + (int)dj;
-                    const float pj[3] = {position(j, 0), position(j, 1), position(j, 2)};
-                    const float d2 = contact_d2(cell, Lm, pi, pj, m);
-                    if (d2 < rc2) {
-                        hit = true;
-                        R = sqrtf(d2);
-                        const int rj = species_rank(j), A = min(ri, rj), Bq = max(ri, rj);
-                        comp = (Bq * (Bq + 1) / 2 + A) | (A == Bq ? 64 : 0);
-                    }
+            if (valid && !(dj == 0 && m <= cell.centre)) {  // an atom with itself: only the images after (0, 0, 0)
+                const int j = i + (int)dj;
+                const float d2 = crystal_contact_at(cell, Lm, position, j, m, pix, piy, piz).d2;
+                if (d2 < rc2) {
+                    hit = true;
+                    R = sqrtf(d2);
+                    const int rj = species_rank(j), A = min(ri, rj), Bq = max(ri, rj);
+                    comp = (Bq * (Bq + 1) / 2 + A) | (A == Bq ? 64 : 0);
                 }
             }
             // the hits of this round, in thread order: the wave's ballot, then a prefix over the four waves
@@ -147,7 +135,7 @@ __global__ __launch_bounds__(CRYSTAL_THREADS) void crystal_fingerprint_kernel(
             cnt += total;
             parity ^= 1;
             if (cnt > FP_DRAIN) drain();
-        }
+        });
     }
     drain();
 

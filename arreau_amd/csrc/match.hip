@@ -92,12 +92,6 @@ __device__ __forceinline__ float nearest_image_d2(float* e, const float* G) {
     return best;
 }
 
-// the solver's writes of one lane are read by the other lanes of its wave (LDS or global memory)
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
-
 constexpr int SM_ROW_V = 0, SM_ROW_D = 2, SM_ROW_Y = 4, SM_ROW_PRED = 5;  // the solver's state rows (v and d: low word, high word)
 constexpr int SM_EXCLUDED = -2147483647 - 1;                              // pred of a column of another species
 static_assert(ARREAU_SM_ASSIGN_STATE_ROWS == 6, "v (2), d (2), y, pred");
@@ -316,19 +310,19 @@ __global__ __launch_bounds__(CRYSTAL_THREADS) void structure_match_kernel(sm_sid
         int* y = st + (size_t)SM_ROW_Y * ss;
         int* pred = st + (size_t)SM_ROW_PRED * ss;
         for (int j = lane; j < n; j += 64) { y[j] = -1; st64(SM_ROW_V, j, 0); }
-        wave_sync();
+        crystal_wave_sync();
         for (int i = lane; i < n; i += 64) {
             const int pi = pm[i];
             bool first = pi >= 0;
             for (int k = 0; k < i; ++k) first = first && pm[k] != pi;
             if (first) y[pi] = i;
         }
-        wave_sync();
+        crystal_wave_sync();
         for (int i = lane; i < n; i += 64) {
             const int pi = pm[i];
             if (pi >= 0 && y[pi] != i) pm[i] = -1;
         }
-        wave_sync();
+        crystal_wave_sync();
         for (int f = 0; f < n; ++f) {
             if (pm[f] >= 0) continue;  // (uniform)
             const int tf = spx(f);
@@ -368,7 +362,7 @@ __global__ __launch_bounds__(CRYSTAL_THREADS) void structure_match_kernel(sm_sid
             if (j1 >= 0) {
                 for (int j = lane; j < n; j += 64)
                     if (pred[j] < 0 && pred[j] != SM_EXCLUDED) st64(SM_ROW_V, j, ld64(SM_ROW_V, j) + ld64(SM_ROW_D, j) - mind);
-                wave_sync();
+                crystal_wave_sync();
                 int j = j1;
                 for (int hop = 0; hop < n; ++hop) {  // the path back to f: every row on it moves to the column it was reached from
                     const int i = ~pred[j];
@@ -379,7 +373,7 @@ __global__ __launch_bounds__(CRYSTAL_THREADS) void structure_match_kernel(sm_sid
                     j = before;
                 }
             }
-            wave_sync();
+            crystal_wave_sync();
         }
     };
     // part B: returns whether the map is a permutation (or was made one-to-one by the assignment step: `solved`); then rms2 = (sum
@@ -394,7 +388,7 @@ __global__ __launch_bounds__(CRYSTAL_THREADS) void structure_match_kernel(sm_sid
         solved = false;
         if (__any(twice)) {
             if constexpr (!ASSIGN) return false;
-            wave_sync();  // (every lane has read the map before the solver writes it)
+            crystal_wave_sync();  // (every lane has read the map before the solver writes it)
             solve();
             int hole = 0;
             for (int i = lane; i < n; i += 64) hole |= pm[i] < 0;

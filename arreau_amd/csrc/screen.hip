@@ -57,12 +57,7 @@ __global__ __launch_bounds__(CRYSTAL_THREADS) void crystal_screen_kernel(
     }
     crystal_cell_images(cell);
 
-    // ---- positions: staged in LDS when the crystal fits, else formed from global memory where they are used (same values)
-    const bool staged = n <= CRYSTAL_LDS_ATOMS;
-    if (staged)
-        for (int a = tid; a < 3 * n; a += CRYSTAL_THREADS) spos[a] = crystal_cart(frac, Lm, (size_t)first + a / 3, a % 3);
-    __syncthreads();
-    auto position = [&](int atom, int d) -> float { return staged ? spos[3 * atom + d] : crystal_cart(frac, Lm, (size_t)first + atom, d); };
+    const crystal_positions position = crystal_stage_positions(spos, frac, Lm, first, n);
 
     // ---- the search.  Receiver i (uniform), then the flattened (j >= i, image m) range dealt to the 256 threads: every thread
     // meets its contacts in ascending (i, j, m), so a strict "<" on the bits of d2 keeps the first of equal minima.
@@ -74,7 +69,8 @@ __global__ __launch_bounds__(CRYSTAL_THREADS) void crystal_screen_kernel(
         auto contact = [&](unsigned dj, unsigned m) {
             if (dj == 0 && m <= cell.centre) return;  // an atom with itself: only the images after (0, 0, 0)
             const int j = i + (int)dj;
-            // contact_d2's operations, spelled out: called through the helper they are packed in pairs and this loop is slower
+            // crystal_contact_at's operations, kept in the loop: through the helper they are packed in pairs, and 1024 random
+            // crystals of 64 atoms take 153.1 us against 152.2 us (medians, MI355X; 256 x 20 is 0.3 us faster through it)
             const unsigned m12 = m / cell.W3;
             const float n3 = (float)((int)(m - m12 * cell.W3) - cell.N3), n2 = (float)((int)(m12 % cell.W2) - cell.N2), n1 = (float)((int)(m12 / cell.W2) - cell.N1);
             const float sx = __fadd_rn(__fadd_rn(__fmul_rn(n1, Lm[0]), __fmul_rn(n2, Lm[3])), __fmul_rn(n3, Lm[6]));
@@ -92,18 +88,7 @@ __global__ __launch_bounds__(CRYSTAL_THREADS) void crystal_screen_kernel(
                 best_m = m;
             }
         };
-        const unsigned long long span = (unsigned long long)(n - i) * cell.M;
-        if (span <= 0xffffffffull - CRYSTAL_THREADS) {  // (uniform) the usual case: 32-bit index arithmetic
-            for (unsigned e = (unsigned)tid; e < (unsigned)span; e += CRYSTAL_THREADS) {
-                const unsigned dj = e / cell.M;
-                contact(dj, e - dj * cell.M);
-            }
-        } else {
-            for (unsigned long long e = (unsigned long long)tid; e < span; e += CRYSTAL_THREADS) {
-                const unsigned long long dj = e / cell.M;
-                contact((unsigned)dj, (unsigned)(e - dj * cell.M));
-            }
-        }
+        crystal_walk((unsigned long long)(n - i) * cell.M, cell.M, (unsigned)tid, CRYSTAL_THREADS, contact);
     }
 
     // ---- deterministic reduction: the wave minimum of the ordered key (bits of d2; i, j; m), one exact double each

@@ -19,7 +19,7 @@
 //                             face vertices x, y, z, angle 4 * 128 floats        2048 B
 //                             the same vertices in angular order 3 * 128 floats  1536 B     11776 B a wave, 47104 B
 //   per-wave partial results  6 * 4 words                                          96 B     50272 B; the rest is alignment
-// A wave talks to itself through its own slice alone, so the per-atom work needs no workgroup barrier: wave_sync() orders the
+// A wave talks to itself through its own slice alone, so the per-atom work needs no workgroup barrier: crystal_wave_sync() orders the
 // wave's LDS writes before its reads.
 #include "internal.h"
 #include "crystal_dev.h"
@@ -38,19 +38,6 @@ struct vor_wave {
     float vx[VF], vy[VF], vz[VF], va[VF];
     float sx[VF], sy[VF], sz[VF];
 };
-
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// the fixed butterfly: v <- v + shuffle_xor(v, w), w = 32 .. 1; every lane ends with the same bits
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
@@ -105,14 +92,8 @@ __global__ __launch_bounds__(CRYSTAL_THREADS) void crystal_voronoi_kernel(
     }
     crystal_cell_images(cell);
 
-    const bool staged = n <= CRYSTAL_LDS_ATOMS;
-    if (staged)
-        for (int a = tid; a < 3 * n; a += CRYSTAL_THREADS) spos[a] = crystal_cart(frac, Lm, (size_t)first + a / 3, a % 3);
-    __syncthreads();
-    auto position = [&](int atom, int d) -> float { return staged ? spos[3 * atom + d] : crystal_cart(frac, Lm, (size_t)first + atom, d); };
-
+    const crystal_positions position = crystal_stage_positions(spos, frac, Lm, first, n);
     const unsigned long long span = (unsigned long long)n * cell.M;
-    const bool narrow = span <= 0xffffffffull - 64;
     const double ptol = (double)ARREAU_VORONOI_PLANE_TOL * (double)cutoff;  // the plane test's slack as a distance
     const float four_pi = 12.566370614359172f;
     vor_wave& W = s_wave[wave];
@@ -124,52 +105,32 @@ __global__ __launch_bounds__(CRYSTAL_THREADS) void crystal_voronoi_kernel(
         int4* const row = nb_rows + A * max_faces;
         const size_t frow = A * max_faces;
         const float pix = position(i, 0), piy = position(i, 1), piz = position(i, 2);
-        wave_sync();  // (the slice is free: the previous atom's reads are done)
+        crystal_wave_sync();  // (the slice is free: the previous atom's reads are done)
 
         // ---- rule 1: the candidates, every (j, m) but the atom itself with d2 <= r2, in ascending (j, m)
         int nc = 0, overlap = 0;
-        auto chunk = [&](bool valid, unsigned j, unsigned m) {
+        crystal_walk_chunks(span, cell.M, (unsigned)lane, 64u, [&](bool valid, unsigned j, unsigned m) {
             bool hit = false;
-            float dx = 0.f, dy = 0.f, dz = 0.f, d2 = 0.f;
+            crystal_contact k{};
             if (valid && !(j == (unsigned)i && m == cell.centre)) {
-                int im[3];
-                crystal_image(cell, m, im);
-                const float n1 = (float)im[0], n2 = (float)im[1], n3 = (float)im[2];
-                const float sx = __fadd_rn(__fadd_rn(__fmul_rn(n1, Lm[0]), __fmul_rn(n2, Lm[3])), __fmul_rn(n3, Lm[6]));
-                const float sy = __fadd_rn(__fadd_rn(__fmul_rn(n1, Lm[1]), __fmul_rn(n2, Lm[4])), __fmul_rn(n3, Lm[7]));
-                const float sz = __fadd_rn(__fadd_rn(__fmul_rn(n1, Lm[2]), __fmul_rn(n2, Lm[5])), __fmul_rn(n3, Lm[8]));
-                dx = __fsub_rn(__fadd_rn(position((int)j, 0), sx), pix);
-                dy = __fsub_rn(__fadd_rn(position((int)j, 1), sy), piy);
-                dz = __fsub_rn(__fadd_rn(position((int)j, 2), sz), piz);
-                d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-                hit = d2 <= r2;
+                k = crystal_contact_at(cell, Lm, position, (int)j, m, pix, piy, piz);
+                hit = k.d2 <= r2;
             }
             const unsigned long long hits = __ballot(hit);
             const int slot = nc + __popcll(hits & ((1ull << lane) - 1ull));
             if (hit && slot < max_cand) {  // (max_cand <= VC: inside the slice)
-                const double x = (double)dx, y = (double)dy, z = (double)dz, h2 = (x * x + y * y) + z * z, len = sqrt(h2);
+                const double x = (double)k.dx, y = (double)k.dy, z = (double)k.dz, h2 = (x * x + y * y) + z * z, len = sqrt(h2);
                 W.cx[slot] = x; W.cy[slot] = y; W.cz[slot] = z;
-                W.ch[slot] = 0.5 * h2; W.cd[slot] = len; W.cl[slot] = sqrtf(d2);
+                W.ch[slot] = 0.5 * h2; W.cd[slot] = len; W.cl[slot] = sqrtf(k.d2);
                 W.cj[slot] = (int)j; W.cm[slot] = (int)m;
             }
             nc += __popcll(hits);
-            overlap |= __ballot(hit && d2 == 0.f) != 0ull;
-        };
-        if (narrow) {
-            for (unsigned base = 0; base < (unsigned)span; base += 64u) {
-                const unsigned e = base + (unsigned)lane, j = e / cell.M;
-                chunk(e < (unsigned)span, j, e - j * cell.M);
-            }
-        } else {
-            for (unsigned long long base = 0; base < span; base += 64ull) {
-                const unsigned long long e = base + (unsigned long long)lane, j = e / cell.M;
-                chunk(e < span, (unsigned)j, (unsigned)(e - j * cell.M));
-            }
-        }
+            overlap |= __ballot(hit && k.d2 == 0.f) != 0ull;
+        });
         nc = __builtin_amdgcn_readfirstlane(nc);
         int aflags = overlap ? ARREAU_VORONOI_OVERLAP : 0;
         const int K = min(nc, max_cand);
-        wave_sync();
+        crystal_wave_sync();
 
         // ---- the order the planes are tested in: ascending distance (the answer of an AND does not depend on it; a far vertex
         // is thrown out by a near plane early)
@@ -182,7 +143,7 @@ __global__ __launch_bounds__(CRYSTAL_THREADS) void crystal_voronoi_kernel(
             }
             W.ord[r] = k;
         }
-        wave_sync();
+        crystal_wave_sync();
 
         // ---- rules 2 and 3: face by face, the vertices on it from pairs of other planes
         float maxr2 = 0.f;
@@ -234,12 +195,12 @@ __global__ __launch_bounds__(CRYSTAL_THREADS) void crystal_voronoi_kernel(
             float omega = 0.f, area = 0.f;
             if (nv > VF) vover = true;
             if (nv >= 3 && nv <= VF) {
-                wave_sync();
+                crystal_wave_sync();
                 // the centroid, the in-plane axes (u1, u2, n right-handed) and each vertex's angle about the normal
                 float px = 0.f, py = 0.f, pz = 0.f;
                 for (int k = lane; k < nv; k += 64) { px += W.vx[k]; py += W.vy[k]; pz += W.vz[k]; }
                 const float inv_nv = 1.0f / (float)nv;
-                const float gx = wave_sum(px) * inv_nv, gy = wave_sum(py) * inv_nv, gz = wave_sum(pz) * inv_nv;
+                const float gx = crystal_wave_sum(px) * inv_nv, gy = crystal_wave_sum(py) * inv_nv, gz = crystal_wave_sum(pz) * inv_nv;
                 const float il = 1.0f / W.cl[a], nx = (float)ax * il, ny = (float)ay * il, nz = (float)az * il;
                 float tx = 0.f, ty = 0.f, tz = 0.f;  // the axis the normal leans on least
                 if (fabsf(nx) <= fabsf(ny) && fabsf(nx) <= fabsf(nz)) tx = 1.f; else if (fabsf(ny) <= fabsf(nz)) ty = 1.f; else tz = 1.f;
@@ -251,7 +212,7 @@ __global__ __launch_bounds__(CRYSTAL_THREADS) void crystal_voronoi_kernel(
                     const float rx = W.vx[k] - gx, ry = W.vy[k] - gy, rz = W.vz[k] - gz;
                     W.va[k] = atan2f(rx * u2x + ry * u2y + rz * u2z, rx * u1x + ry * u1y + rz * u1z);
                 }
-                wave_sync();
+                crystal_wave_sync();
                 for (int k = lane; k < nv; k += 64) {  // a rank sort: ties (copies of a degenerate vertex) in hit order
                     const float key = W.va[k];
                     int r = 0;
@@ -261,7 +222,7 @@ __global__ __launch_bounds__(CRYSTAL_THREADS) void crystal_voronoi_kernel(
                     }
                     W.sx[r] = W.vx[k]; W.sy[r] = W.vy[k]; W.sz[r] = W.vz[k];
                 }
-                wave_sync();
+                crystal_wave_sync();
                 // the fan about the centroid: triangle k = (g, w_k, w_k+1), cyclic
                 const float gl = sqrtf(gx * gx + gy * gy + gz * gz);
                 float l_area = 0.f, l_omega = 0.f;
@@ -276,12 +237,12 @@ __global__ __launch_bounds__(CRYSTAL_THREADS) void crystal_voronoi_kernel(
                                       (p0 * q0 + p1 * q1 + p2 * q2) * gl;
                     l_omega += 2.0f * atan2f(num, den);
                 }
-                area = wave_sum(l_area);
-                omega = wave_sum(l_omega);
+                area = crystal_wave_sum(l_area);
+                omega = crystal_wave_sum(l_omega);
                 if (a < 64) face_lo |= 1ull << a; else face_hi |= 1ull << (a - 64);
             }
             if (lane == 0) { W.fo[a] = omega; W.fa[a] = area; }
-            wave_sync();
+            crystal_wave_sync();
         }
 
         // ---- rules 4 and 5: weights, the stored faces, the sums, the certificate
@@ -319,9 +280,9 @@ __global__ __launch_bounds__(CRYSTAL_THREADS) void crystal_voronoi_kernel(
         store(is1 && wt1 >= tol, k1, wt1, o1, ar1, ds1);
         cn = __builtin_amdgcn_readfirstlane(cn);
         if (lane >= min(cn, max_faces) && lane < max_faces) blank_slot(frow + lane);  // (max_faces <= 64: one lane per slot)
-        const float cn_eff = wave_sum(wt0 + wt1);
-        const float omega_sum = wave_sum(o0 + o1);
-        const float volume = wave_sum(ar0 * ds0 * (1.0f / 6.0f) + ar1 * ds1 * (1.0f / 6.0f));
+        const float cn_eff = crystal_wave_sum(wt0 + wt1);
+        const float omega_sum = crystal_wave_sum(o0 + o1);
+        const float volume = crystal_wave_sum(ar0 * ds0 * (1.0f / 6.0f) + ar1 * ds1 * (1.0f / 6.0f));
         const float max_radius = sqrtf(wave_max(maxr2));
         if (2.0f * max_radius > cutoff || !(fabsf(omega_sum - four_pi) <= ARREAU_VORONOI_CLOSURE_TOL)) aflags |= ARREAU_VORONOI_OPEN;
         if (cn > max_faces) aflags |= ARREAU_VORONOI_TRUNCATED;
