@@ -67,6 +67,15 @@ F32_DEVIATION = {"face_solid_angle": 3.54e-7, "omega_sum": 2.26e-7, "face_weight
 # solid angles stay as good as a closed cell's.  A closed atom is held to these:
 F32_DEVIATION_CLOSED = {"face_solid_angle": 2.67e-7, "omega_sum": 2.00e-7, "face_weight": 1.54e-6, "cn_eff": 7.91e-6, "volume": 4.18e-7,
                         "face_area": 1.28e-6, "max_radius": 1.55e-7, "face_distance": 4.00e-7}
+# the batches at the caps (tests/voronoi_cases.py: NEW_NAMES; faces of up to 128 vertex copies, atoms of 40 and 70 faces), measured
+# the same way after the tables above were made.  A batch that exceeds a table has a row here, (closed, any): per quantity the
+# larger of the table's number and its own, and only that batch is held to it; "hard cap" exceeds nothing and has none.  The older
+# batches' bounds are the tables above, unchanged.
+_AT_CAPS = {"cages": {"face_solid_angle": 2.72e-7, "omega_sum": 5.34e-7, "volume": 7.03e-7, "face_area": 1.78e-6},
+            "hub40": {"cn_eff": 7.95e-6, "volume": 4.28e-7}, "hub70": {"cn_eff": 1.36e-5},
+            "large wide": {"volume": 7.25e-7, "face_area": 1.71e-6}}  # (what each exceeds F32_DEVIATION_CLOSED by; its OPEN atoms: within F32_DEVIATION)
+F32_DEVIATION_AT_CAPS = {name: ({**F32_DEVIATION_CLOSED, **row}, {k: max(v, row.get(k, 0.0)) for k, v in F32_DEVIATION.items()})
+                         for name, row in _AT_CAPS.items()}
 BOUND_FACTOR = 16.0
 WEIGHT_GUARD, DET_GUARD, CUTOFF_GUARD, GUARD_FACTOR, CLOSURE_F32 = 1e-4, 1e-3, 1e-5, 10.0, 2e-5
 
@@ -254,8 +263,8 @@ def atom_cell(d, d2, cutoff, tol, dt=np.float64, chunk=1 << 15):
     """Rules 2-5 for one atom from its candidates' displacements d [K,3] and squared distances d2 [K] (both of dtype dt, in
     ascending (j, m)): rule 2 (the planes) in float64 from d taken as exact, as the kernel does; the vertices rounded to dt and
     rules 3-5 in dt.  Returns a namespace: is_face [K], omega, area, weight [K] (0 where no face), length [K], volume, omega_sum,
-    max_radius, cn_eff, cn, open, too_many (a face with more than FACE_VERTICES vertex copies), faces (per face the ordered
-    vertices [k,3]), and the margins plane_ratio, det, radius, closure, weight, bound (module docstring)."""
+    max_radius, cn_eff, cn, open, nv [K] (the vertex copies found on each candidate's plane), too_many (a face with more than
+    FACE_VERTICES of them), faces (per face the ordered vertices [k,3]), and the margins plane_ratio, det, radius, closure, weight, bound (module docstring)."""
     K = d.shape[0]
     f8 = np.float64
     D = d.astype(f8)
@@ -304,9 +313,9 @@ def atom_cell(d, d2, cutoff, tol, dt=np.float64, chunk=1 << 15):
                 max_r2 = max(max_r2, _dot(w, w))
                 m.bound = max(m.bound, float(bound[t]) + float(np.spacing(F32(vl[t]))))
     out = SimpleNamespace(is_face=np.zeros(K, bool), omega=np.zeros(K, dt), area=np.zeros(K, dt), weight=np.zeros(K, dt), length=l,
-                          faces=[None] * K, too_many=False)
+                          faces=[None] * K, too_many=False, nv=np.array([len(x) for x in verts], dtype=np.int64))
     for e in range(K):
-        nv = len(verts[e])
+        nv = int(out.nv[e])
         if nv > FACE_VERTICES:
             out.too_many = True
         if nv < 3 or nv > FACE_VERTICES:
@@ -355,8 +364,10 @@ def voronoi_reference(frac, lattice, counts, params=None, dtype=np.float64, keep
     crystal.  float64 is the yardstick; float32 the same arithmetic (the candidates' d2 then one float32 operation at a time, as
     the kernel forms them).  Returns a namespace of the eighteen outputs (RESULT_KEYS, reals of `dtype`) and, per atom, `margins`
     (a list of namespaces plane_ratio, det, radius, closure, weight, bound, cutoff; None where no cell was built), `guarded` [N]
-    (module docstring: float32 decides every comparison of the atom as float64 does), `n_candidates` [N]; with keep_faces, `faces`:
-    per atom a list of (j, (n_1, n_2, n_3), ordered vertices [k,3] relative to the atom, area, solid angle) of every face.
+    (module docstring: float32 decides every comparison of the atom as float64 does), `n_candidates` [N], `max_vertices` [N] (the
+    most vertex copies on one plane of the atom, also where that is too many; -1 where rule 2 was not reached), `selected` (per
+    atom the candidate indices, in (j, m) order, of the faces of weight >= tol: all cn of them; None where no cell was built);
+    with keep_faces, `faces`: per atom a list of (j, (n_1, n_2, n_3), ordered vertices [k,3] relative to the atom, area, solid angle) of every face.
     exact_inputs (float64 only) takes frac and lattice as the float64 numbers they are, not as the float32 the kernel would see:
     an ideal structure whose ratios float32 cannot hold (hcp) stays ideal."""
     if exact_inputs:
@@ -371,6 +382,7 @@ def voronoi_reference(frac, lattice, counts, params=None, dtype=np.float64, keep
     B, N = len(counts), frac.shape[0]
     out = _empty_result(B, N, p_.max_faces, dt)
     out.margins, out.guarded, out.n_candidates, out.faces = [None] * N, np.zeros(N, bool), np.zeros(N, np.int64), [None] * N
+    out.max_vertices, out.selected = np.full(N, -1, np.int64), [None] * N
     R = float(F32(p_.cutoff))
     r2 = dt(F32(np.float64(R) ** 2)) if dt == F32 else np.float64(F32(np.float64(R) ** 2))
     for b, n in enumerate(counts):
@@ -412,13 +424,14 @@ def voronoi_reference(frac, lattice, counts, params=None, dtype=np.float64, keep
                 flags |= aflags
                 continue
             c = atom_cell(disp[e], d2[e], R, float(F32(p_.tol)), dt)
+            out.max_vertices[A] = c.nv.max(initial=0)
             if c.too_many:
                 out.atom_flags[A] = aflags | OVERFLOW
                 flags |= aflags | OVERFLOW
                 continue
             sel = np.flatnonzero(c.is_face & (c.weight >= dt(F32(p_.tol))))
             k = min(sel.size, p_.max_faces)
-            out.cn[A] = sel.size
+            out.cn[A], out.selected[A] = sel.size, sel
             out.neighbors[A, :k, 0], out.neighbors[A, :k, 1:] = e[sel[:k]] // M, g[e[sel[:k]] % M]
             out.face_weight[A, :k], out.face_solid_angle[A, :k] = c.weight[sel[:k]], c.omega[sel[:k]]
             out.face_area[A, :k], out.face_distance[A, :k] = c.area[sel[:k]], c.length[sel[:k]]

@@ -108,6 +108,7 @@ def test_kernel_matches_the_float64_restatement(dev, name):
         assert abs(float(got["mean_cn_eff"][b]) - float(r.mean_cn_eff[b])) <= bound["cn_eff"][b] + 2.0 ** -22 * n * float(r.mean_cn_eff[b]), (name, b)
         assert abs(float(got["volume_sum"][b]) - float(r.volume_sum[b])) <= n * bound["volume"][b] + 2.0 ** -22 * n * float(r.volume_sum[b]), (name, b)
     want_guarded = {"known": 29, "known half": 29, "one atom": 1, "skewed": 1, "flags": 2, "overflow": 0, "truncated": 2, "ragged": 1200, "large": 244}
+    want_guarded.update(cases.WANT_GUARDED)  # (the batches at the caps: 95 % of the atoms a cell is built for, test_voronoi_cpu.py)
     assert r.guarded.sum() >= want_guarded[name]  # (the comparison is not vacuous: at least 95 % of the ragged and large atoms)
 
 
@@ -158,28 +159,34 @@ def test_a_crystal_alone_gives_the_bits_it_gives_in_the_batch(dev):
         assert np.array_equal(bits(again[k]), bits(got[k])), k
 
 
-@pytest.mark.parametrize("name", ["known", "ragged", "large"])
+@pytest.mark.parametrize("name", ["known", "ragged", "large", "cages", "hub40", "hub70"])
 def test_closure_reciprocity_and_volumes_on_the_device(dev, name):
     """The device's own numbers: on every closed atom omega_sum is 4 pi within the bound (the float64 restatement's is 4 pi to
-    1e-10), the volumes of a crystal closed in all its atoms sum to the cell's, and a stored face's partner has its area."""
+    1e-10), the volumes of a crystal closed in all its atoms sum to the cell's, and a stored face's partner has its area.  On the
+    batches at the caps each of the three is allowed what the float64 restatement itself misses it by: the cages' float32
+    coordinates split the vertex at the cage's centre by 1e-7 A, and the restatement closes them to 2e-5 in omega_sum, to 8e-7 of
+    the volume and to 2e-5 A^2 between partners (the hubs: to 1e-14; test_voronoi_cpu.py)."""
+    caps = name in cases.NEW_NAMES
     bt, r = cases.reference(name)
     got = run(dev, name)
     closed_b, _ = cases.bounds(bt)
     first, crystal = first_of(bt.counts), np.repeat(np.arange(len(bt.counts)), bt.counts)
     shut = is_closed(got["atom_flags"], got["omega_sum"]) & r.guarded
-    assert shut.sum() >= {"known": 29, "ragged": 400, "large": 100}[name]
+    assert shut.sum() >= {"known": 29, "ragged": 400, "large": 100, "cages": 77, "hub40": 46, "hub70": 75}[name]
     err = np.abs(got["omega_sum"][shut].astype(np.float64) - FOUR_PI)
     slack = 1e-6 if name == "known" else 0.0  # (ideal hcp in float32: its split vertices close the cell to 4e-7 only, in float64 too)
-    assert (err <= closed_b["omega_sum"][crystal[shut]] + slack).all(), (name, float(err.max()))
+    own = np.abs(r.omega_sum[shut] - FOUR_PI) if caps else 0.0
+    assert (err <= closed_b["omega_sum"][crystal[shut]] + slack + own).all(), (name, float(err.max()))
     whole = 0
     for b, n in enumerate(bt.counts):
         if n and shut[first[b]:first[b + 1]].all():
             vol = abs(np.linalg.det(bt.lattice[b].astype(np.float64)))
             total = got["volume"][first[b]:first[b + 1]].astype(np.float64).sum()
-            assert abs(total - vol) <= n * closed_b["volume"][b] + 1e-6 * vol, (name, b, total, vol)
-            assert abs(float(got["volume_sum"][b]) - vol) <= n * closed_b["volume"][b] + 1e-6 * vol + 2.0 ** -22 * n * vol
+            own = abs(float(r.volume_sum[b]) - vol) if caps else 0.0
+            assert abs(total - vol) <= n * closed_b["volume"][b] + 1e-6 * vol + own, (name, b, total, vol)
+            assert abs(float(got["volume_sum"][b]) - vol) <= n * closed_b["volume"][b] + 1e-6 * vol + 2.0 ** -22 * n * vol + own
             whole += 1
-    assert whole >= {"known": 8, "ragged": 1, "large": 0}[name]
+    assert whole >= {"known": 8, "ragged": 1, "large": 0, "cages": 4, "hub40": 0, "hub70": 1}[name]
     pairs = 0
     for b, n in enumerate(bt.counts):
         for i in range(n):
@@ -192,22 +199,161 @@ def test_closure_reciprocity_and_volumes_on_the_device(dev, name):
                 if not shut[c]:
                     continue
                 back = np.flatnonzero((got["neighbors"][c] == np.array([i, -n1, -n2, -n3])).all(axis=1))
-                if back.size == 0:  # the partner weighs less than tol on its own atom: not stored there (the restatement agrees)
-                    assert not any(jj == i and im == (-n1, -n2, -n3) and w >= bt.params.tol for (jj, im, _, _, _), w in
-                                   zip(r.faces[c], faces_weights(r, c))), (name, b, i, j)
+                if back.size == 0:  # the partner weighs less than tol on its own atom, or lies past that atom's max_faces (hub70's
+                    # centre keeps 64 of 70): not stored there (the restatement agrees)
+                    kept = [(jj, im) for (jj, im, _, _, _), w in zip(r.faces[c], faces_weights(r, c)) if w >= bt.params.tol]
+                    assert (i, (-n1, -n2, -n3)) not in kept[:bt.params.max_faces], (name, b, i, j)
                     continue
                 assert back.size == 1
-                assert abs(float(got["face_area"][a, s]) - float(got["face_area"][c, back[0]])) <= 2.0 * closed_b["face_area"][b] + slack, (name, b, i, j)
+                own = abs(float(r.face_area[a, s]) - float(r.face_area[c, back[0]])) if caps else 0.0  # (both guarded: the same rows there)
+                assert abs(float(got["face_area"][a, s]) - float(got["face_area"][c, back[0]])) <= 2.0 * closed_b["face_area"][b] + slack + own, (name, b, i, j)
                 assert got["face_distance"][a, s] == got["face_distance"][c, back[0]] or \
                     abs(float(got["face_distance"][a, s]) - float(got["face_distance"][c, back[0]])) <= 2.0 * closed_b["face_distance"][b]
                 pairs += 1
-    assert pairs >= {"known": 200, "ragged": 1000, "large": 500}[name]
+    assert pairs >= {"known": 200, "ragged": 1000, "large": 500, "cages": 400, "hub40": 300, "hub70": 400}[name]
 
 
 def faces_weights(r, a):
     """The weights of atom a's kept faces in the float64 restatement, in their order."""
     top = max((om for _, _, _, _, om in r.faces[a]), default=0.0)
     return [om / top if top > 0 else 0.0 for _, _, _, _, om in r.faces[a]]
+
+
+def assert_blank(got, a, flags):
+    """Atom a has no cell: cn 0, its flags, the reals NaN, the list -1."""
+    assert got["cn"][a] == 0 and got["atom_flags"][a] == flags, (a, got["cn"][a], got["atom_flags"][a])
+    assert all(np.isnan(got[k][a]).all() for k in PER_ATOM_REALS + vo.FACE_KEYS) and (got["neighbors"][a] == -1).all(), a
+
+
+def assert_same_atoms(x, y, atoms):
+    for k in vo.RESULT_KEYS[len(vo.CRYSTAL_KEYS):]:
+        assert np.array_equal(bits(x[k][atoms]), bits(y[k][atoms])), k
+
+
+def test_the_caps_on_the_device(dev):
+    """What the batches at the caps are for, read off the device's arrays (the numbers are the float64 restatement's,
+    test_voronoi_cpu.py): a face of more than 64 vertex copies is built, one of more than 128 is OVERFLOW; 40 rows stored and the
+    rest blank; 70 faces counted and 64 stored."""
+    bt, r = cases.reference("cages")
+    got, first = run(dev, "cages"), first_of(bt.counts)
+    assert got["flags"].tolist() == [0, 0, 0, 0, vo.OVERFLOW, 0]
+    c16, c17, c18, c20 = (cases.CAGE_NAMES.index(n) for n in ("cage16", "cage17", "cage18", "cage20"))
+    for b, n_cage in ((c16, 16), (c17, 17), (c18, 18)):
+        sl = slice(first[b], first[b] + n_cage)
+        assert (r.max_vertices[sl] > 64).all() and (got["atom_flags"][sl] == 0).all() and np.array_equal(got["cn"][sl], r.cn[sl])
+    full = first[c18] + np.flatnonzero(r.max_vertices[first[c18]:first[c18 + 1]] == vo.FACE_VERTICES)  # exactly 128 copies: built
+    assert full.size >= 1 and r.guarded[full].all() and (got["atom_flags"][full] == 0).all() and not np.isnan(got["volume"][full]).any()
+    for a in range(first[c20], first[c20] + 20):
+        assert r.max_vertices[a] > vo.FACE_VERTICES and r.n_candidates[a] <= vo.MAX_CANDIDATES
+        assert_blank(got, a, vo.OVERFLOW)
+    fill = slice(first[c20] + 20, first[c20 + 1])
+    assert (got["atom_flags"][fill] == 0).all() and np.array_equal(got["cn"][fill], r.cn[fill]) and not np.isnan(got["volume"][fill]).any()
+    assert np.isnan(got["volume_sum"][c20]) and got["min_cn"][c20] == 0 and got["n_faces"][c20] == r.cn[fill].sum()
+    bt, r = cases.reference("hub40")
+    got = run(dev, "hub40")
+    assert r.cn[0] == 40 and got["cn"][0] == 40 and got["flags"].tolist() == [0] and got["neighbors"].shape == (48, 64, 4)
+    assert np.array_equal(got["neighbors"][0], r.neighbors[0]) and (got["neighbors"][0, :40, 0] > 0).all() and (got["neighbors"][0, 40:] == -1).all()
+    assert all(np.isnan(got[k][0, 40:]).all() and not np.isnan(got[k][0, :40]).any() for k in vo.FACE_KEYS)
+    bt, r = cases.reference("hub70")
+    got = run(dev, "hub70")
+    assert r.cn[0] == 70 and got["cn"][0] == 70 and got["atom_flags"][0] == vo.TRUNCATED and got["flags"].tolist() == [vo.TRUNCATED]
+    assert np.array_equal(got["neighbors"][0], r.neighbors[0]) and (got["neighbors"][0, :, 0] > 0).all() and (got["atom_flags"][1:] == 0).all()
+    assert not any(np.isnan(got[k][0]).any() for k in vo.FACE_KEYS) and got["max_cn"][0] == 70
+    assert abs(float(got["volume_sum"][0]) - 729.0) <= 78 * cases.bounds(bt)[0]["volume"][0] + 2.0 ** -22 * 78 * 729.0
+
+
+def test_max_candidates_at_the_largest_count_and_one_below(dev):
+    """hub70 with room for exactly its largest candidate count (the restatement's: 108) gives the bits it gives with room for 128;
+    with room for one less exactly the atoms that have that many are OVERFLOW and blank, and every other atom keeps its bits."""
+    bt, r = cases.reference("hub70")
+    got, top = run(dev, "hub70"), int(r.n_candidates.max())
+    full = r.n_candidates == top
+    assert 64 < top < vo.MAX_CANDIDATES and 1 <= full.sum() < len(full)
+    exact = launch(dev, cases.with_params(bt, max_candidates=top))
+    for k in vo.RESULT_KEYS:
+        assert np.array_equal(bits(exact[k]), bits(got[k])), k
+    less = launch(dev, cases.with_params(bt, max_candidates=top - 1))
+    for a in np.flatnonzero(full):
+        assert_blank(less, a, vo.OVERFLOW)
+    assert_same_atoms(less, got, ~full)
+    assert less["flags"].tolist() == [int(got["flags"][0]) | vo.OVERFLOW] and less["n_faces"][0] == got["cn"][~full].sum()
+    assert less["min_cn"][0] == 0 and less["max_cn"][0] == got["cn"][~full].max() and np.isnan(less["volume_sum"][0]) and np.isnan(less["mean_cn_eff"][0])
+
+
+def test_the_hard_cap_of_128_candidates(dev):
+    """One crystal at two cutoffs 0.009 A apart: at the first its densest atom has exactly 128 candidates (the last slot of the
+    wave's slice) and is built as the restatement builds it (test_kernel_matches_the_float64_restatement holds its numbers); at
+    the second it has 129 and is OVERFLOW, while the atom that now has exactly 128 is built."""
+    bt, r = cases.reference("hard cap")
+    got, a, nxt = run(dev, "hard cap"), cases.HARD_CAP_ATOM, cases.HARD_CAP_NEXT
+    assert r.n_candidates[a] == r.n_candidates.max() == vo.MAX_CANDIDATES and r.guarded[a] and r.atom_flags[a] == 0
+    assert got["flags"].tolist() == [0] and got["atom_flags"][a] == 0 and got["cn"][a] == r.cn[a] > 0 and np.array_equal(got["neighbors"][a], r.neighbors[a])
+    over = cases.hard_cap_batch(cases.HARD_CAP_OVER)
+    count = cases.candidate_counts(over)
+    assert count[a] == count.max() == vo.MAX_CANDIDATES + 1 and count[nxt] == vo.MAX_CANDIDATES and (np.delete(count, a) <= vo.MAX_CANDIDATES).all()
+    more = launch(dev, over)
+    assert_blank(more, a, vo.OVERFLOW)
+    rest = np.delete(np.arange(len(count)), a)
+    assert more["flags"][0] & vo.OVERFLOW and ((more["atom_flags"][rest] & vo.OVERFLOW) == 0).all() and not np.isnan(more["volume"][rest]).any()
+    assert more["cn"][nxt] >= r.cn[nxt] > 0 and more["atom_flags"][nxt] == r.atom_flags[nxt] == 0  # (a plane more cuts no face open)
+
+
+def sweep(dev, bt, r, got, values):
+    """max_faces alone changes: cn, the flags and the stored rows are the restatement's, cut (cases.cut), on the atoms it decides;
+    the rows past cn are blank; every stored real and per-atom real has the bits of the launch `got` with the longest list."""
+    built = np.array([m is not None for m in r.margins], dtype=bool)
+    decided = r.guarded | ~built
+    for mf in values:
+        one = launch(dev, cases.with_params(bt, max_faces=mf))
+        want = cases.cut(r, mf)
+        assert one["neighbors"].shape == (len(r.cn), mf, 4)
+        for k in ("cn", "atom_flags", "neighbors"):
+            assert np.array_equal(one[k][decided], getattr(want, k)[decided]), (mf, k)
+        assert np.array_equal((one["atom_flags"] & vo.TRUNCATED) != 0, one["cn"] > mf), mf
+        beyond = np.arange(mf)[None, :] >= one["cn"][:, None]
+        assert (one["neighbors"][beyond] == -1).all() and (one["neighbors"][~beyond][:, 0] >= 0).all(), mf
+        for k in vo.FACE_KEYS:
+            assert np.isnan(one[k][beyond]).all() and np.array_equal(bits(one[k]), bits(got[k][:, :mf])), (mf, k)
+        for k in PER_ATOM_REALS + ("cn",):
+            assert np.array_equal(bits(one[k]), bits(got[k])), (mf, k)
+        assert np.array_equal(one["neighbors"], got["neighbors"][:, :mf]) and one["n_faces"][0] == got["n_faces"][0]
+        assert one["flags"][0] == (int(got["flags"][0]) & ~vo.TRUNCATED) | (vo.TRUNCATED if (one["cn"] > mf).any() else 0), mf
+
+
+def test_max_faces_sweeps(dev):
+    """fcc at max_faces 1..13 (12 faces: the cut inside the first 64 candidates, then none), hub40 about the number of faces its
+    centre (40, all among its first 64 candidates) and a filler (18 of 25) have among their first 64 candidates, and hub70 about
+    its centre's (59 of 70): the cut inside the first call of the kernel's store(), exactly between the two and inside the second."""
+    kb, kr = cases.reference("known")
+    b = cases.KNOWN_NAMES.index("fcc_primitive")
+    at = slice(first_of(kb.counts)[b], first_of(kb.counts)[b + 1])
+    fcc = cases.single(kb, b)
+    one_r = cases.atoms(kr, at)
+    assert one_r.cn.tolist() == [12]
+    sweep(dev, fcc, one_r, launch(dev, fcc), range(1, 14))
+    for name in ("hub40", "hub70"):
+        bt, r = cases.reference(name)
+        sweep(dev, bt, r, run(dev, name), cases.SWEEPS[name])
+
+
+def test_a_cage_alone_gives_the_bits_it_gives_in_the_batch(dev):
+    bt = cases.reference("cages")[0]
+    got, first = run(dev, "cages"), first_of(bt.counts)
+    assert first[1] > 0
+    for name in ("cage16", "cage17", "cage18", "cage20"):
+        b = cases.CAGE_NAMES.index(name)
+        alone = launch(dev, cases.single(bt, b))
+        for k in vo.CRYSTAL_KEYS:
+            assert np.array_equal(bits(alone[k][0]), bits(got[k][b])), (name, k)
+        for k in vo.RESULT_KEYS[len(vo.CRYSTAL_KEYS):]:
+            assert np.array_equal(bits(alone[k]), bits(got[k][first[b]:first[b + 1]])), (name, k)
+
+
+def test_two_launches_of_hub70_give_the_same_bits(dev):
+    bt = cases.reference("hub70")[0]
+    got, again = run(dev, "hub70"), launch(dev, bt)
+    for k in vo.RESULT_KEYS:
+        assert np.array_equal(bits(again[k]), bits(got[k])), k
 
 
 def test_sample_with_voronoi(dev, fused_model):

@@ -257,6 +257,142 @@ def test_tol_zero_counts_every_face_and_no_weight_is_negative():
         assert abs(float(r.cn_eff[0]) - 6.0) < 1e-4 and not r.guarded[0]  # (a weight on its threshold: unguarded)
 
 
+# --------------------------------------------------------------------------------- what the batches at the caps reach
+# Every number the device tests of these batches rely on, from the float64 restatement alone: the branches of the kernel they are
+# there for run only if these hold (test_gpu_voronoi.py).
+def built_of(r):
+    return np.array([m is not None for m in r.margins], dtype=bool)
+
+
+@pytest.mark.parametrize("name", cases.NEW_NAMES)
+def test_enough_atoms_of_the_batches_at_the_caps_are_guarded(name):
+    """A condition on the constructions, not a measurement: 95 % of the atoms a cell is built for; and float32 decides the guarded
+    ones as float64 does (the same integers, flags and lists from the float32 restatement)."""
+    bt, r = cases.reference(name)
+    built = built_of(r)
+    assert cases.WANT_GUARDED[name] >= 0.95 * built.sum() and r.guarded.sum() >= cases.WANT_GUARDED[name], (name, r.guarded.sum(), built.sum())
+    assert built.sum() >= len(built) - (20 if name == "cages" else 0)  # (cage20's twenty cage atoms alone have no cell)
+    r32 = vo.voronoi_reference(bt.frac, bt.lattice, bt.counts, bt.params, dtype=np.float32)
+    g = r.guarded
+    for k in ("cn", "atom_flags", "neighbors"):
+        assert np.array_equal(getattr(r32, k)[g], getattr(r, k)[g]), (name, k)
+    assert np.array_equal(r32.n_candidates, r.n_candidates) and np.array_equal(r32.atom_flags[~built], r.atom_flags[~built])
+    if g.all():
+        assert np.array_equal(r32.flags, r.flags) and np.array_equal(r32.n_faces, r.n_faces)
+
+
+def test_what_the_cages_reach():
+    """cage16, cage17: every cage atom has a face of 64 < nv <= 128 vertex copies (the second lane round of the kernel's per-face
+    loops); cage20: every cage atom one of more than 128 with at most 128 candidates (OVERFLOW by vertices alone)."""
+    bt, r = cases.reference("cages")
+    first, ok = first_of(bt.counts), closed(r)
+    assert tuple(cases.CAGE_NAMES) == ("one atom", "cage16", "cage17", "cage18", "cage20", "bcc_primitive") and bt.counts == [1, 23, 24, 25, 27, 1]
+    assert r.flags.tolist() == bt.expect["flags"] == [0, 0, 0, 0, vo.OVERFLOW, 0] and first[1] > 0
+    for b, n_cage, guarded in ((1, 16, 23), (2, 17, 23), (3, 18, 25)):
+        sl, cage = slice(first[b], first[b + 1]), slice(first[b], first[b] + n_cage)
+        assert ((r.max_vertices[cage] > 64) & (r.max_vertices[cage] <= vo.FACE_VERTICES)).all(), r.max_vertices[cage]
+        assert r.max_vertices[first[b] + n_cage:first[b + 1]].max() <= 64 and r.n_candidates[sl].max() <= 64  # (the fillers' faces are ordinary)
+        assert ok[sl].all() and (r.atom_flags[sl] == 0).all() and r.guarded[sl].sum() == guarded and (r.cn[sl] <= bt.params.max_faces).all()
+        # the float32 coordinates split the vertex at the cage's centre by 1e-7 A; the plane test's slack rejoins the copies, and the
+        # cell closes to 2e-5 in omega_sum and 8e-7 of the volume (not to 1e-10 as a generic crystal's)
+        vol = abs(np.linalg.det(bt.lattice[b].astype(np.float64)))
+        assert np.abs(r.omega_sum[sl] - FOUR_PI).max() <= 1e-4 and abs(r.volume_sum[b] - vol) <= 2e-6 * vol, (b, r.volume_sum[b], vol)
+    assert r.max_vertices[first[1]:first[1] + 16].min() >= 92 and r.max_vertices[first[2]:first[2] + 17].min() >= 107
+    # cage18: a face of exactly FACE_VERTICES copies (the cap's last value that builds) on an atom, with the float64 displacements
+    # and with the float32 ones the kernel forms (the count of the centre vertex's copies depends on them: not a guarded comparison)
+    one = cases.single(bt, 3)
+    r32 = vo.voronoi_reference(one.frac, one.lattice, one.counts, one.params, dtype=np.float32)
+    at64, at32 = r.max_vertices[first[3]:first[3] + 18], r32.max_vertices[:18]
+    full = first[3] + np.flatnonzero((at64 == vo.FACE_VERTICES) & (at32 == vo.FACE_VERTICES))
+    assert full.size >= 1 and max(at64.max(), at32.max()) == vo.FACE_VERTICES and (r32.atom_flags == 0).all()
+    assert r.guarded[full].all() and (r.atom_flags[full] == 0).all() and (r.cn[full] > 0).all()
+    cage, fill = slice(first[4], first[4] + 20), slice(first[4] + 20, first[5])
+    assert (r.max_vertices[cage] > vo.FACE_VERTICES).all() and (r.n_candidates[cage] <= 56).all() and (r.atom_flags[cage] == vo.OVERFLOW).all()
+    assert (r.cn[cage] == 0).all() and np.isnan(r.volume[cage]).all() and not built_of(r)[cage].any()
+    assert ok[fill].all() and r.guarded[fill].all() and (r.atom_flags[fill] == 0).all() and (r.cn[fill] >= 7).all() and np.isnan(r.volume_sum[4])
+    assert ok[first[0]] and ok[first[5]] and r.guarded[first[0]] and r.guarded[first[5]] and r.n_candidates[first[5]] > 64
+
+
+def test_what_the_hubs_reach():
+    """hub40: 40 faces on one atom, all stored; every atom uses both halves of the candidate lanes.  hub70: 70 faces, TRUNCATED at
+    the longest list.  The atoms the max_faces sweeps cut at the boundary between the first 64 candidates and the rest."""
+    for name, n_sphere, k_lo, k_hi in (("hub40", 40, 71, 87), ("hub70", 70, 84, 108)):
+        bt, r = cases.reference(name)
+        n = n_sphere + 8
+        assert bt.counts == [n] and bt.params.max_faces == vo.MAX_FACES and closed(r).all() and r.cn[0] == n_sphere
+        assert (r.n_candidates.min(), r.n_candidates.max()) == (k_lo, k_hi) and k_lo > 64
+        assert r.max_vertices.max() <= 64  # (generic faces: the cap here is the list's, not the vertices')
+        assert np.abs(r.omega_sum - FOUR_PI).max() <= 1e-10 * FOUR_PI and abs(r.volume_sum[0] - 729.0) <= 1e-10 * 729.0
+        both = sum(1 for s in r.selected if (s < 64).any() and (s >= 64).any())
+        assert both >= {"hub40": 44, "hub70": 78}[name]  # (stored faces from both calls of the kernel's store())
+        for a, m, cn in cases.SWEEP_ATOMS[name]:
+            assert (int((r.selected[a] < 64).sum()), r.selected[a].size, int(r.cn[a])) == (m, cn, cn) and r.guarded[a], (name, a)
+            assert {m - 1, m, m + 1} <= set(cases.SWEEPS[name])
+    bt, r = cases.reference("hub40")
+    assert r.flags.tolist() == [0] and r.guarded.sum() == 46 and (r.atom_flags == 0).all() and (r.neighbors[0, :40, 0] > 0).all() and (r.neighbors[0, 40:] == -1).all()
+    bt, r = cases.reference("hub70")
+    assert r.flags.tolist() == [vo.TRUNCATED] and r.guarded.all() and r.atom_flags[0] == vo.TRUNCATED and (r.atom_flags[1:] == 0).all()
+    assert (r.neighbors[0, :, 0] > 0).all() and r.cn[1:].max() <= 35
+    # the candidate cap's case: some atoms, not all, have the largest count
+    assert 1 <= (r.n_candidates == 108).sum() < 78
+
+
+def test_cut_is_what_the_restatement_gives_at_a_shorter_list():
+    """cases.cut against real runs: fcc at max_faces 1..13 and hub40 at 18 (its filler atom 41: the 18 faces among its first 64
+    candidates stored, the 7 others not)."""
+    kb, kr = cases.reference("known")
+    b = cases.KNOWN_NAMES.index("fcc_primitive")
+    at = slice(first_of(kb.counts)[b], first_of(kb.counts)[b + 1])
+    fcc, whole = cases.single(kb, b), cases.atoms(kr, at)
+    runs = [(fcc, whole, mf) for mf in range(1, 14)] + [cases.reference("hub40") + (18,)]
+    for bt, r, mf in runs:
+        real = vo.voronoi_reference(bt.frac, bt.lattice, bt.counts, cases.with_params(bt, max_faces=mf).params)
+        want = cases.cut(r, mf)
+        for k in ("cn", "atom_flags", "neighbors") + vo.FACE_KEYS:
+            assert np.array_equal(getattr(real, k), getattr(want, k), equal_nan=True), (bt.name, mf, k)
+        assert np.array_equal((real.atom_flags & vo.TRUNCATED) != 0, real.cn > mf) and np.array_equal(real.volume, r.volume)
+    assert real.atom_flags[41] == vo.TRUNCATED and real.atom_flags[0] == vo.TRUNCATED and (real.selected[41][:18] < 64).all() and (real.selected[41][18:] >= 64).all()
+
+
+def test_what_the_wide_cutoff_reaches_past_the_staging():
+    bt, r = cases.reference("large wide")
+    assert bt.counts == [cb.STAGED_ATOMS + 1] and (r.n_candidates.min(), r.n_candidates.max()) == (39, 75)
+    assert (r.n_candidates > 64).sum() == 87 and r.guarded.sum() == 255 and closed(r).sum() == 169 and built_of(r).all()
+    assert (r.guarded & (r.n_candidates > 64)).sum() >= 80  # (the atoms the case is there for are compared)
+
+
+def test_the_hard_cap_cutoffs():
+    """Exactly 128 candidates at the first cutoff (atom 15 alone, built and guarded), 129 at the second (and atom 10 exactly 128);
+    no candidate of either atom within CUTOFF_GUARD of either cutoff."""
+    bt, r = cases.reference("hard cap")
+    a, nxt = cases.HARD_CAP_ATOM, cases.HARD_CAP_NEXT
+    assert bt.counts == [22] and r.flags.tolist() == [0] and built_of(r).all() and closed(r).all()
+    assert r.n_candidates.max() == vo.MAX_CANDIDATES == 128 and np.flatnonzero(r.n_candidates == 128).tolist() == [a] and r.guarded[a] and r.guarded[nxt]
+    assert all(m.cutoff > vo.CUTOFF_GUARD for m in r.margins) and r.n_candidates.min() > 64
+    over = cases.hard_cap_batch(cases.HARD_CAP_OVER)
+    count = cases.candidate_counts(over)
+    assert count[a] == count.max() == 129 and count[nxt] == 128 and np.flatnonzero(count > 128).tolist() == [a]
+    for batch, counts in ((bt, r.n_candidates), (over, count)):
+        r2 = float(np.float32(float(np.float32(batch.params.cutoff)) ** 2))
+        for i in (a, nxt):
+            d2 = cases.candidate_d2(batch, i).astype(np.float64)
+            assert (d2 <= r2).sum() == counts[i], (batch.params.cutoff, i)  # (the helper counts what the restatement counts)
+            assert np.abs(d2 / r2 - 1.0).min() > vo.CUTOFF_GUARD, (batch.params.cutoff, i)
+
+
+def test_the_rows_of_the_batches_at_the_caps():
+    """F32_DEVIATION_AT_CAPS: a row only for a new batch, never below the tables, and no more than 2.7 times them (the largest measured: 2.67, the cages' omega_sum)."""
+    assert set(vo.F32_DEVIATION_AT_CAPS) <= set(cases.NEW_NAMES) and not set(vo.F32_DEVIATION_AT_CAPS) & set(cases.OLD_NAMES)
+    for name, (shut, any_) in vo.F32_DEVIATION_AT_CAPS.items():
+        assert set(shut) == set(any_) == set(vo.F32_DEVIATION)
+        assert all(vo.F32_DEVIATION_CLOSED[k] <= shut[k] <= 2.7 * vo.F32_DEVIATION_CLOSED[k] for k in shut), name
+        assert all(vo.F32_DEVIATION[k] <= any_[k] <= 2.7 * vo.F32_DEVIATION[k] and shut[k] <= any_[k] * 1.01 for k in shut), name
+    for bt in (cases.known_batch(), cases.hard_cap_batch()):  # a batch without a row: the tables
+        s = vo.scales(bt.lattice, bt.counts, bt.params)
+        shut, any_ = cases.bounds(bt)
+        assert all(np.array_equal(shut[k], 16.0 * vo.F32_DEVIATION_CLOSED[k] * s[k]) and np.array_equal(any_[k], 16.0 * vo.F32_DEVIATION[k] * s[k]) for k in s)
+
+
 # ------------------------------------------------------------------------------------------------------------- plumbing
 def test_parameter_validation():
     assert vo.resolve(None) is None and vo.resolve(False) is None and vo.resolve(True) == vo.VoronoiParams()

@@ -1,7 +1,8 @@
 """The inputs the Voronoi construction's CPU and GPU tests share (test_voronoi_cpu.py, test_gpu_voronoi.py) and the float32
 deviation tool measures on (tools/exp/voronoi_f32_deviation.py): textbook structures at a cutoff that closes every cell, a
-one-atom triclinic cell, the strongly skewed cell, every flag, the 70-crystal ragged batch of random crystals and a crystal past
-the LDS staging.  numpy only; the same bytes for both.
+one-atom triclinic cell, the strongly skewed cell, every flag, the 70-crystal ragged batch of random crystals, a crystal past
+the LDS staging, and the batches that reach the kernel's caps (NEW_NAMES: faces of 65..128 and more vertex copies, atoms of 40 and
+70 faces, exactly 128 and 129 candidates).  numpy only; the same bytes for both.
 
 A batch is a namespace frac [N,3] float32, lattice [B,3,3] float32, counts [B], species [N] (atomic numbers), params (the
 VoronoiParams it is built with) and expect: {"cn": per-atom list or None, "flags": per-crystal list or None}.
@@ -10,6 +11,7 @@ The random crystals are the coordination cases' (8..24 atoms, cell lengths 5..9 
 RANDOM_SEEDS); at RAGGED.cutoff = 5 A the densest of them has about 100 candidates per atom and the sparsest leave cells OPEN:
 both are decided by the float64 restatement, and an atom is GUARDED by it alone (arreau_amd/diffusion/voronoi.py)."""
 from functools import lru_cache
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -124,6 +126,157 @@ def large_batch(seed=5):
     return _batch("large", [(frac, L, np.full(n, 13))], LARGE)
 
 
+LARGE_WIDE = vo.VoronoiParams(cutoff=5.4)
+
+
+def large_wide_batch():
+    """The 257-atom crystal at 5.4 A: a third of its atoms have more than 64 candidates, so positions formed from global memory
+    meet the second half of the candidate lanes."""
+    bt = large_batch()
+    bt.params, bt.key = LARGE_WIDE, "large wide"
+    return bt
+
+
+# ------------------------------------------------------------------------------------------------ the cases at the caps
+# Atoms on a sphere: an atom of the cage sees every other one on a sphere through itself, so their bisecting planes all pass through
+# the cage's centre, and that one vertex is found on a face once per pair of the other planes that bound it there: a face of the
+# cage collects far more vertex copies (64 < nv <= 128, or past the cap) than any face of a generic crystal.  An atom at the centre
+# (a hub) has every atom of the sphere for a face.  What each case reaches is asserted in test_voronoi_cpu.py from the float64
+# restatement alone.
+CAGE_ROTATION = np.linalg.qr(np.random.RandomState(3).normal(size=(3, 3)))[0]  # (no plane along a cell axis)
+FILLERS = [[0, 0, 0], [0.5, 0, 0], [0, 0.5, 0], [0, 0, 0.5], [0.5, 0.5, 0], [0.5, 0, 0.5], [0, 0.5, 0.5]]  # close the cells outward
+CAGE = vo.VoronoiParams(cutoff=6.5, max_faces=32)
+HUB40 = vo.VoronoiParams(cutoff=6.5, max_faces=64)
+HUB70 = vo.VoronoiParams(cutoff=6.0, max_faces=64)
+
+
+def sphere_points(n, seed, min_chord):
+    """n unit vectors drawn uniformly, none closer than min_chord to one accepted before it."""
+    rng, out = np.random.RandomState(seed), []
+    while len(out) < n:
+        v = rng.normal(size=3)
+        v /= np.linalg.norm(v)
+        if all(np.linalg.norm(v - q) > min_chord for q in out):
+            out.append(v)
+    return np.array(out)
+
+
+def dodecahedron():
+    """The 20 vertices of a regular dodecahedron as unit vectors."""
+    g = (1 + np.sqrt(5)) / 2
+    p = [(a, b, c) for a in (1, -1) for b in (1, -1) for c in (1, -1)]
+    for q in [(0, s1 / g, s2 * g) for s1 in (1, -1) for s2 in (1, -1)]:
+        p += [q, (q[1], q[2], q[0]), (q[2], q[0], q[1])]
+    p = np.array(p, dtype=np.float64)
+    return p / np.linalg.norm(p, axis=1)[:, None]
+
+
+def cage_crystal(points, radius, edge, hub=False):
+    """(frac, cell, atomic numbers): the unit vectors scaled to `radius`, rotated and centred in a cubic cell of `edge`, an atom
+    at the centre first (hub), the seven fillers last."""
+    x = (points * radius) @ CAGE_ROTATION.T
+    if hub:
+        x = np.concatenate([np.zeros((1, 3)), x])
+    frac = np.concatenate([x / edge + 0.5, np.array(FILLERS, dtype=np.float64)]).astype(F32)
+    return frac, cc.cube(edge), [8] * hub + [14] * len(points) + [22] * len(FILLERS)
+
+
+CAGE_NAMES = ("one atom", "cage16", "cage17", "cage18", "cage20", "bcc_primitive")  # the crystals of cages_batch, in order
+
+
+def cages_batch():
+    """cage16 and cage17 (every cage atom has a face of 64 < nv <= 128 vertex copies), cage18 (a seed, of 1000 tried, at which an atom
+    has a face of exactly 128 copies and none has more, in the float64 restatement and in the float32 one, whose displacements are
+    the kernel's: the last slot of the vertex arrays; the copies of the centre vertex lie 1e-7 A apart, so their number moves by
+    one or two with the displacements' rounding), cage20 (a dodecahedron: every
+    cage face has more than 128, OVERFLOW by vertices) between the one-atom triclinic cell and bcc: the cages start at non-zero
+    offsets."""
+    by_name = {k[0]: k for k in cc.known_structures()}
+    one, bcc = one_atom_batch(), by_name["bcc_primitive"]
+    crystals = [(one.frac, one.lattice[0], one.species), cage_crystal(sphere_points(16, 16, 0.55), 2.8, 8.6),
+                cage_crystal(sphere_points(17, 17, 0.55), 2.8, 8.6), cage_crystal(sphere_points(18, 313, 0.55), 2.8, 8.6),
+                cage_crystal(dodecahedron(), 2.8, 8.6), bcc[1:4]]
+    return _batch("cages", crystals, CAGE, flags=[0, 0, 0, 0, vo.OVERFLOW, 0])
+
+
+def hub40_batch():
+    """A centre atom with 40 faces, all stored at max_faces = 64; every atom has more than 64 candidates."""
+    return _batch("hub40", [cage_crystal(sphere_points(40, 40, 0.42), 3.0, 9.0, hub=True)], HUB40, flags=[0])
+
+
+def hub70_batch():
+    """A centre atom with 70 faces: TRUNCATED at the longest list there is; 84..108 candidates per atom."""
+    return _batch("hub70", [cage_crystal(sphere_points(70, 70, 0.30), 3.2, 9.0, hub=True)], HUB70, flags=[vo.TRUNCATED])
+
+
+def with_params(bt, **changes):
+    """The batch with some of its parameters changed (a new namespace, the arrays shared)."""
+    p = bt.params
+    kw = dict(tol=p.tol, cutoff=p.cutoff, max_faces=p.max_faces, max_candidates=p.max_candidates, max_shells=p.max_shells)
+    kw.update(changes)
+    out = type(bt)(**vars(bt))
+    out.params, out.expect = vo.VoronoiParams(**kw), {"cn": None, "flags": None}
+    return out
+
+
+def candidate_counts(bt):
+    """The restatement's candidates per atom at the batch's cutoff, cheaply: with room for one candidate it builds no cell."""
+    return vo.voronoi_reference(bt.frac, bt.lattice, bt.counts, with_params(bt, max_candidates=1).params).n_candidates
+
+
+def candidate_d2(bt, i):
+    """The float32 squared distances from atom i of a one-crystal batch to every (j, m) but itself, ascending, formed as rule 1
+    forms them: how far each candidate lies from the cutoff, also for an atom the restatement builds no cell for."""
+    L, f = bt.lattice[0], bt.frac
+    _, q, bad = vo.cb.cell_f32(L, bt.params.cutoff, 0.0, bt.params.max_shells)
+    assert not bad and len(bt.counts) == 1
+    pos, g, centre, s = vo.cb.positions_and_shifts(f.astype(F32), L.astype(F32), [max(1, int(np.ceil(x))) for x in q], F32)
+    disp = ((pos[:, None, :] + s[None, :, :]).astype(F32) - pos[i][None, None, :]).astype(F32).reshape(-1, 3)
+    sq = (disp * disp).astype(F32)
+    d2 = ((sq[:, 0] + sq[:, 1]).astype(F32) + sq[:, 2]).astype(F32)
+    return np.sort(np.delete(d2, i * g.shape[0] + centre))
+
+
+# The hard cap: the densest crystal of the ragged batch (22 atoms) at two cutoffs found by bisection on the CPU.  Its atom 15 has its
+# 128th candidate at 5.83463 A, its 129th at 5.83726 A and its 130th at 5.859 A; atom 10 has its 128th at 5.83797 A and its 129th
+# at 5.8566 A; no other atom reaches 129 below 5.87 A.  At 5.836 A the largest K is 128 (atom 15: the last slot of the wave's
+# slice); at 5.845 A atom 15 has 129 (OVERFLOW) and atom 10 exactly 128.
+HARD_CAP_CRYSTAL, HARD_CAP_ATOM, HARD_CAP_NEXT = 23, 15, 10
+HARD_CAP = vo.VoronoiParams(cutoff=5.836)
+HARD_CAP_OVER = vo.VoronoiParams(cutoff=5.845)
+
+
+def hard_cap_batch(params=HARD_CAP):
+    bt = single(cc.ragged_batch(), HARD_CAP_CRYSTAL)
+    bt.params, bt.name, bt.key = params, "hard cap", "hard cap"
+    return bt
+
+
+def cut(r, max_faces):
+    """What the restatement gives when max_faces alone is lowered (rule 5: the first max_faces faces in (j, m) order, cn counts them
+    all, TRUNCATED exactly where cn > max_faces): the per-atom integers and the stored faces of `r`, cut.  test_voronoi_cpu.py
+    holds it against real runs of the restatement."""
+    assert max_faces <= r.neighbors.shape[1]
+    out = SimpleNamespace(cn=r.cn, neighbors=r.neighbors[:, :max_faces],
+                          atom_flags=(r.atom_flags & ~vo.TRUNCATED) | np.where(r.cn > max_faces, vo.TRUNCATED, 0).astype(np.int32))
+    for k in vo.FACE_KEYS:
+        setattr(out, k, getattr(r, k)[:, :max_faces])
+    return out
+
+
+def atoms(r, sl):
+    """The per-atom part of a restatement's result for a slice of its atoms."""
+    out = SimpleNamespace(**{k: getattr(r, k)[sl] for k in vo.RESULT_KEYS[len(vo.CRYSTAL_KEYS):] + ("guarded", "n_candidates", "max_vertices")})
+    out.margins, out.selected = r.margins[sl], r.selected[sl]
+    return out
+
+
+# max_faces about the number of selected faces an atom has among its first 64 candidates (the kernel stores those first, then the
+# rest): hub40's filler atom 41 has 18 of its 25 there, its centre all 40 of 40; hub70's centre 59 of 70
+SWEEP_ATOMS = {"hub40": ((41, 18, 25), (0, 40, 40)), "hub70": ((0, 59, 70),)}  # (atom, faces among the first 64 candidates, cn)
+SWEEPS = {"hub40": (17, 18, 19, 32, 39, 40, 41), "hub70": (58, 59, 60)}
+
+
 def single(batch, b):
     """Crystal b of a batch as a batch of its own."""
     first = int(np.sum(batch.counts[:b]))
@@ -131,12 +284,15 @@ def single(batch, b):
     return _batch(f"{batch.name}[{b}]", [(batch.frac[first:first + n], batch.lattice[b], batch.species[first:first + n])], batch.params)
 
 
-NAMES = ("known", "known half", "one atom", "skewed", "flags", "overflow", "truncated", "ragged", "large")
+OLD_NAMES = ("known", "known half", "one atom", "skewed", "flags", "overflow", "truncated", "ragged", "large")
+NEW_NAMES = ("cages", "hub40", "hub70", "large wide", "hard cap")
+NAMES = OLD_NAMES + NEW_NAMES
 
 
 def all_batches():
     return [known_batch(), known_batch(KNOWN_HALF, "known half"), one_atom_batch(), skewed_batch(), flag_batch(), overflow_batch(),
-            truncated_batch(), ragged_batch(), large_batch()]
+            truncated_batch(), ragged_batch(), large_batch(), cages_batch(), hub40_batch(), hub70_batch(), large_wide_batch(),
+            hard_cap_batch()]
 
 
 @lru_cache(maxsize=None)
@@ -146,9 +302,16 @@ def reference(name):
     return bt, vo.voronoi_reference(bt.frac, bt.lattice, bt.counts, bt.params, keep_faces=True)
 
 
+# the guarded atoms the device comparison needs of each batch at the caps: 95 % of the atoms a cell is built for (cage20's cage
+# atoms are OVERFLOW: no cell, no margins), rounded up; test_voronoi_cpu.py asserts them from the restatement
+WANT_GUARDED = {"cages": 77, "hub40": 46, "hub70": 75, "large wide": 245, "hard cap": 21}
+
+
 def bounds(bt):
     """(closed, any): per crystal the bounds the device's reals must meet against the float64 restatement, for an atom that is not
     OPEN and for any atom: BOUND_FACTOR times the measured float32 deviation times the crystal's scale
-    (arreau_amd/diffusion/voronoi.py), each a dict of [B] arrays keyed like F32_DEVIATION."""
+    (arreau_amd/diffusion/voronoi.py), each a dict of [B] arrays keyed like F32_DEVIATION.  A batch at the caps whose measured
+    deviation exceeds the tables has its own row (F32_DEVIATION_AT_CAPS); the other batches' bounds are what they were."""
     s = vo.scales(bt.lattice, bt.counts, bt.params)
-    return tuple({k: vo.BOUND_FACTOR * table[k] * s[k] for k in table} for table in (vo.F32_DEVIATION_CLOSED, vo.F32_DEVIATION))
+    tables = vo.F32_DEVIATION_AT_CAPS.get(bt.key, (vo.F32_DEVIATION_CLOSED, vo.F32_DEVIATION))
+    return tuple({k: vo.BOUND_FACTOR * table[k] * s[k] for k in table} for table in tables)
