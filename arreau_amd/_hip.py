@@ -33,7 +33,7 @@ EXPORTS = [
     "arreau_sample_loop_eta", "arreau_reverse_step_eta",
     "arreau_crystal_fingerprint", "arreau_fingerprint_match", "arreau_crystal_symmetry", "arreau_crystal_reduce",
     "arreau_crystal_symmetrize", "arreau_structure_match", "arreau_structure_match_assigned",
-    "arreau_crystal_conventional", "arreau_crystal_coordination", "arreau_crystal_bond_order", "arreau_crystal_voronoi",
+    "arreau_crystal_conventional", "arreau_crystal_coordination", "arreau_crystal_bond_order", "arreau_crystal_voronoi", "arreau_crystal_xrd",
     "arreau_noise_state", "arreau_invert_step", "arreau_invert_loop",
     "arreau_sample_loop_multistep", "arreau_reverse_step_multistep",
     "arreau_sample_loop_species", "arreau_reverse_step_species",
@@ -151,6 +151,17 @@ class VoronoiResultC(Structure):
     _fields_ = [(name, c_void_p) for name in ("n_faces", "min_cn", "max_cn", "mean_cn", "mean_cn_eff", "volume_sum", "flags",
                                                 "cn", "neighbors", "face_weight", "face_solid_angle", "face_area", "face_distance",
                                                 "volume", "omega_sum", "max_radius", "cn_eff", "atom_flags")]
+
+
+class XrdParamsC(Structure):
+    """arreau_xrd_params: the wavelength, the 2 theta grid, the peak width, the Debye-Waller B and the index cap of the powder pattern."""
+    _fields_ = [("wavelength", c_double), ("two_theta_min", c_double), ("two_theta_max", c_double), ("fwhm", c_double), ("b_iso", c_double),
+                ("n_points", c_int32), ("max_index", c_int32)]
+
+
+class XrdResultC(Structure):
+    """arreau_xrd_result: the pattern [B, n_points] and the four per-crystal device arrays the diffraction launch writes."""
+    _fields_ = [(name, c_void_p) for name in ("pattern", "n_reflections", "volume", "weight_sum", "flags")]
 
 
 class FingerprintParamsC(Structure):
@@ -309,6 +320,7 @@ def _prototypes():
         "arreau_crystal_coordination": [vp] * 3 + [i32, i32, POINTER(CoordinationParamsC), POINTER(CoordinationResultC), vp],
         "arreau_crystal_bond_order": [vp] * 3 + [i32, i32, vp, vp, POINTER(BondOrderParamsC), POINTER(BondOrderResultC), vp],
         "arreau_crystal_voronoi": [vp] * 3 + [i32, i32, POINTER(VoronoiParamsC), POINTER(VoronoiResultC), vp],
+        "arreau_crystal_xrd": [vp] * 4 + [i32, i32, POINTER(XrdParamsC), POINTER(XrdResultC), vp],
         "arreau_crystal_fingerprint": [vp] * 4 + [i32, i32, POINTER(FingerprintParamsC), POINTER(FingerprintResultC), vp],
         "arreau_fingerprint_match": [POINTER(FingerprintResultC), i32, POINTER(FingerprintResultC), i32, f32, POINTER(MatchResultC), vp],
         "arreau_crystal_symmetry": [vp] * 4 + [i32, i32, POINTER(SymmetryParamsC), POINTER(SymmetryResultC), vp],

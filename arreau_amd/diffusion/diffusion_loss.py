@@ -90,6 +90,10 @@ class SampleResult:
     # face_solid_angle, face_area, face_distance [.., max_faces], volume, omega_sum, max_radius, cn_eff, atom_flags and species,
     # one row per atom; None when it was not asked for
     voronoi: Optional[dict] = None
+    # extension: the powder diffraction patterns of the final state (sample(xrd=...); diffusion/xrd.py) -- numpy arrays pattern
+    # [.., n_points], n_reflections, volume, weight_sum, flags, max_intensity, two_theta_peak and grid [.., 5] (the grid-defining
+    # parameters: the 2 theta values are xrd.grid(row)), one row per crystal; None when it was not asked for
+    xrd: Optional[dict] = None
 
 
 class _PinnedRing:
@@ -540,7 +544,7 @@ class DiffusionLoss(nn.Module):
                lattice_system=None, symmetry=None, screen=None, unique=None, find_symmetry=None, reduce_cell=None,
                symmetrize=None, match_to=None, eta: Optional[float] = None, initial_state=None,
                multistep: bool = False, elements=None, species_temperature: float = 1.0, crystal_keys=None,
-               conventional_cell=None, coordination=None, bond_order=None, contact_guidance=None, voronoi=None) -> SampleResult:
+               conventional_cell=None, coordination=None, bond_order=None, contact_guidance=None, voronoi=None, xrd=None) -> SampleResult:
         """diffusion_loss.py:276-377.  The initial state is drawn on the host exactly like the reference (numpy
         uniforms for the angles, then randn lengths, randn fractional coordinates from torch's global CPU generator):
         draw_initial_state, which a caller may also use on its own.
@@ -726,6 +730,12 @@ class DiffusionLoss(nn.Module):
         holds the arrays (voronoi.STORED_KEYS).  It reads the state as sampled.  Not CrystalNN: no radii, no electronegativities,
         no distance weighting, no probabilities.  None: no launch is added, voronoi is None and the results are what they were,
         bit for bit.
+        `xrd` (extension, every noise mode and option): an xrd.XrdParams (wavelength, two_theta_min, two_theta_max, n_points, fwhm,
+        b_iso, scattering, max_index), or True for its defaults -- one more launch on the final device state (arreau_crystal_xrd;
+        rules in include/arreau_hip.h) writes every crystal's powder X-ray diffraction pattern on a fixed 2 theta grid: Z-weighted
+        point scatterers, Lorentz-polarisation factor, Gaussians of one width.  SampleResult.xrd then holds the arrays
+        (xrd.STORED_KEYS).  It reads the state as sampled.  No form-factor tables, no anomalous dispersion, no peak list, no K
+        alpha 2.  None: no launch is added, xrd is None and the results are what they were, bit for bit.
         `contact_guidance` (extension, every noise mode and option): a contact_guidance.ContactGuidance (min_distance, weight,
         max_shells), or True for its defaults -- training-free guidance away from short contacts (rules in include/arreau_hip.h,
         "contact guidance"; arreau_sample_loop_guided).  Every network evaluation of every step, a corrector's included, is followed
@@ -793,7 +803,7 @@ class DiffusionLoss(nn.Module):
         final = instruments.DeviceState(eng, buf.frac_d, buf.lattice_d, buf.off_d, buf.types_d, z_table, plan.num_atoms.numpy(),
                                         atomic_numbers, mask_type=-1 if constant_atoms is not None else plan.S - 1)
         fields = {e.field: e.run(final, plan.instruments[e.keyword]) if plan.instruments[e.keyword] is not None else None
-                  for e in instruments.WHOLE}
+                  for e in instruments.FULL}
         return SampleResult(num_atoms=plan.num_atoms.numpy(), frac_x=buf.frac_d.cpu().numpy().astype(np.float64),
                             atomic_numbers=atomic_numbers, lattice=buf.lattice_d.cpu().numpy().astype(np.float64), info=info,
                             crystal_keys=np.array(plan.crystal_keys, dtype=np.int64) if plan.crystal_keys is not None else None,

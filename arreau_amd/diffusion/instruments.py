@@ -5,7 +5,8 @@ LOCAL ones, which describe each atom's surroundings (the coordination environmen
 is built on a LOCAL one's neighbour lists (the bond angles and order parameters); TABLE is EVERY and SHELL, the whole table, and
 KEYWORDS maps a sample() keyword to its entry.  CELLS holds what builds each atom's Voronoi cell (its own launch, after the
 bond order); WHOLE is TABLE and CELLS -- what the file layer, the batch driver, the screen and sample() loop over -- and
-WHOLE_KEYWORDS its keyword map.  An entry holds what the
+WHOLE_KEYWORDS its keyword map.  PATTERNS holds what walks reciprocal space (the powder diffraction pattern: its own launch,
+after the cells); FULL is WHOLE and PATTERNS -- what those four loop over now -- and FULL_KEYWORDS its keyword map.  An entry holds what the
 instruments differ in for the host-side plumbing: the file layer (inference/process_generated_crystals.py), the batch driver
 (generate.py) and `python -m arreau_amd.screen` loop over it, and so does DiffusionLoss.sample, which calls every asked-for
 entry's `run` on the final device state (DeviceState) in table order: an entry that shares a launch comes after the entry that
@@ -17,7 +18,7 @@ from typing import Callable, Optional
 import numpy as np
 
 from . import (bond_order, cell_reduction, conventional_cell, coordination, screening, structure_match, symmetrize, symmetry_search,
-               uniqueness, voronoi)
+               uniqueness, voronoi, xrd)
 from .tools.atomic_number_table import atomic_number_indexes_to_atomic_numbers
 
 
@@ -89,6 +90,12 @@ def _run_bond_order(s, params):  # (the coordination launch is shared)
 def _run_voronoi(s, params):
     s.launched["voronoi"] = s.eng.voronoi(s.frac, s.lattice, s.offsets, params)
     return voronoi.sample_arrays(voronoi.result_to_numpy(s.launched["voronoi"]), s.atomic_numbers)
+
+
+def _run_xrd(s, params):  # (the atomic numbers are the amplitudes: one small upload)
+    import torch
+    weights = torch.as_tensor(xrd.host_weights(s.atomic_numbers, params), device=s.frac.device)
+    return xrd.sample_arrays(xrd.result_to_numpy(s.eng.xrd(s.frac, s.lattice, s.offsets, weights, xrd.for_weights(params))), params)
 
 
 @dataclass(frozen=True)
@@ -163,6 +170,15 @@ CELLS = (
 )
 WHOLE = TABLE + CELLS  # the whole table with the cells: what the file layer, the batch driver, the screen and sample() loop over
 WHOLE_KEYWORDS = {e.keyword: e for e in WHOLE}
+# what walks reciprocal space: a launch of its own, after the cells; its arrays after voronoi_*
+PATTERNS = (
+    Instrument("xrd", "xrd", "xrd_", "xrd_stats", xrd, xrd.STORED_KEYS, "XrdParams",
+               (("wavelength", "xrd_wavelength"), ("fwhm", "xrd_fwhm"), ("two_theta_min", "xrd_two_theta_min"),
+                ("two_theta_max", "xrd_two_theta_max"), ("n_points", "xrd_points"), ("b_iso", "xrd_b_iso"),
+                ("scattering", "xrd_scattering")), "xrd", shape=(), shapes=(("pattern", 2), ("grid", (len(xrd.GRID_KEYS),))), run=_run_xrd),
+)
+FULL = WHOLE + PATTERNS  # every instrument: what the file layer, the batch driver, the screen and sample() loop over
+FULL_KEYWORDS = {e.keyword: e for e in FULL}
 
 
 def concat(entry, parts):

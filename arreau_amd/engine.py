@@ -12,7 +12,7 @@ import torch
 from . import _hip
 from .diffusion import (bond_order as bond_order_mod, cell_reduction, conventional_cell as conventional_mod,
                         coordination as coordination_mod, screening, symmetrize as symmetrize_mod, symmetry_search,
-                        voronoi as voronoi_mod)
+                        voronoi as voronoi_mod, xrd as xrd_mod)
 from .diffusion.contact_guidance import INFO_KEYS, ContactGuidance
 from .diffusion.corrector import check_corrector
 from .diffusion.ddim import check_eta
@@ -87,6 +87,11 @@ def coordination(frac, lattice, offsets, params=None):
 def voronoi(frac, lattice, offsets, params=None):
     """The Voronoi cells without an engine (arreau_crystal_voronoi needs no model): diffusion.voronoi.voronoi."""
     return voronoi_mod.voronoi(frac, lattice, offsets, params)
+
+
+def xrd(frac, lattice, offsets, weights_or_atomic_numbers, params=None):
+    """The powder diffraction patterns without an engine (arreau_crystal_xrd needs no model): diffusion.xrd.xrd."""
+    return xrd_mod.xrd(frac, lattice, offsets, weights_or_atomic_numbers, params)
 
 
 def bond_order(frac, lattice, offsets, params=None):
@@ -1075,6 +1080,14 @@ class HipEngine:
         Returns its dict of device tensors.  Does not synchronise."""
         self._on_device("voronoi", frac)
         return voronoi_mod.voronoi(frac, lattice, offsets, params)
+
+    def xrd(self, frac, lattice, offsets, weights_or_atomic_numbers, params=None):
+        """The powder diffraction patterns of a batch on this engine's device (arreau_crystal_xrd; diffusion/xrd.py: `xrd`, which
+        needs no engine): frac [N,3] f32, lattice [B,3,3] f32, offsets [B+1] i32, the atomic numbers or amplitudes [N] (what
+        params.scattering says), params an XrdParams or None (the defaults).  Returns its dict of device tensors.  Does not
+        synchronise."""
+        self._on_device("xrd", frac)
+        return xrd_mod.xrd(frac, lattice, offsets, weights_or_atomic_numbers, params)
 
     def find_symmetry(self, frac, lattice, offsets, types, params=None):
         """The symmetry search of a batch on this engine's device (arreau_crystal_symmetry; diffusion/symmetry_search.py:

@@ -71,6 +71,10 @@ search is shared) adds the bond-angle histogram and the Steinhardt order paramet
 Voronoi cells: `--voronoi` (`--vor_tol`, `--vor_cutoff`) builds every atom's Voronoi cell on the device (diffusion/voronoi.py): the
 histogram of cn (faces of weight >= vor_tol), mean cn and cn_eff overall and per element, the share of OPEN atoms, the count per flag,
 and voronoi_* arrays.  Not CrystalNN: no radii, no electronegativities, no distance weighting, no probabilities.
+Powder diffraction: `--xrd` (`--xrd_wavelength`, `--xrd_fwhm`, `--xrd_two_theta_min`, `--xrd_two_theta_max`, `--xrd_points`,
+`--xrd_b_iso`, `--xrd_scattering`) writes every crystal's powder X-ray diffraction pattern on a fixed 2 theta grid on the device
+(diffusion/xrd.py): the count per flag, the mean number of lattice points kept and the mean, minimum and maximum 2 theta of the
+strongest peak, and xrd_* arrays.  Z-weighted point scatterers: no form-factor tables, no anomalous dispersion, no K alpha 2.
 
 Keyed sampling: `--keyed` (needs `--seed`) makes every crystal a function of (seed, key) alone (diffusion/keyed.py).  Every rank
 uses the same seed; output slot k of `--num_crystals` has key k on its first attempt.  With `--require_valid`, attempt a of slot k
@@ -95,7 +99,7 @@ import numpy as np
 
 from .diffusion import instruments
 from .diffusion.diffusion_loss import SampleResult
-from .diffusion.instruments import WHOLE as INSTRUMENTS
+from .diffusion.instruments import FULL as INSTRUMENTS
 
 
 def shard_range(num_items: int, world_size: int, rank: int):
@@ -485,6 +489,11 @@ def build_parser() -> argparse.ArgumentParser:
                          "atom volumes; histogram of cn, mean cn and cn_eff overall and per element, share of OPEN atoms and flags "
                          "per rank and in total + voronoi_* arrays in the output file")
     add_voronoi_arguments(ap)
+    ap.add_argument("--xrd", action="store_true",
+                    help="write every crystal's powder X-ray diffraction pattern on a fixed 2 theta grid on the device (--xrd_wavelength, "
+                         "--xrd_fwhm, --xrd_two_theta_min, --xrd_two_theta_max, --xrd_points, --xrd_b_iso, --xrd_scattering): flags, mean "
+                         "lattice points kept and the strongest peak's 2 theta per rank and in total + xrd_* arrays in the output file")
+    add_xrd_arguments(ap)
     ap.add_argument("--guide_contacts", action="store_true",
                     help="contact guidance: steer every sampling step away from contacts shorter than --guide_min_distance (the "
                          "gradient of a contact penalty added to the predicted eps on the device); prints the contacts and flags of "
@@ -522,6 +531,18 @@ def add_voronoi_arguments(ap):
                     help="voronoi: the atoms within this distance in A may bound a cell; an atom whose cell they do not close is OPEN")
 
 
+def add_xrd_arguments(ap):
+    """The flags of the powder diffraction pattern, shared with `python -m arreau_amd.screen` (starting values, not claims)."""
+    ap.add_argument("--xrd_wavelength", type=float, default=1.54184, help="xrd: the wavelength in A (1.54184: Cu K alpha)")
+    ap.add_argument("--xrd_fwhm", type=float, default=0.2, help="xrd: the full width at half maximum of every reflection in degrees")
+    ap.add_argument("--xrd_two_theta_min", type=float, default=5.0, help="xrd: the first grid value in degrees")
+    ap.add_argument("--xrd_two_theta_max", type=float, default=90.0, help="xrd: the last grid value in degrees (at most 160)")
+    ap.add_argument("--xrd_points", type=int, default=1701, help="xrd: the number of grid values, ends included (2..4096)")
+    ap.add_argument("--xrd_b_iso", type=float, default=0.0, help="xrd: one isotropic Debye-Waller B in A^2 for every atom")
+    ap.add_argument("--xrd_scattering", type=str, default="Z", choices=("Z", "unit"),
+                    help="xrd: an atom's amplitude: its atomic number (the forward-scattering limit of the form factor) or 1")
+
+
 def add_structure_match_arguments(ap):
     """The tolerance flags of the structure match, shared with `python -m arreau_amd.screen`."""
     ap.add_argument("--ltol", type=float, default=0.2, help="match_to: relative tolerance on the cell lengths (StructureMatcher's default)")
@@ -533,10 +554,10 @@ def add_structure_match_arguments(ap):
 
 
 def instrument_params(keyword, args, error):
-    """The parameters of one instrument (its sample() keyword: instruments.WHOLE_KEYWORDS) from its flags -- screen: a ScreenCriteria,
+    """The parameters of one instrument (its sample() keyword: instruments.FULL_KEYWORDS) from its flags -- screen: a ScreenCriteria,
     unique: a FingerprintParams, find_symmetry: a SymmetrySearchParams, reduce_cell: a CellReductionParams, symmetrize: a
-    SymmetrizeParams, match_to: a StructureMatchParams, conventional_cell: a ConventionalCellParams, coordination: a CoordinationParams, bond_order: a BondOrderParams, voronoi: a VoronoiParams; what has no flag keeps its default.  `error(message)` reports a bad value."""
-    e = instruments.WHOLE_KEYWORDS[keyword]
+    SymmetrizeParams, match_to: a StructureMatchParams, conventional_cell: a ConventionalCellParams, coordination: a CoordinationParams, bond_order: a BondOrderParams, voronoi: a VoronoiParams, xrd: an XrdParams; what has no flag keeps its default.  `error(message)` reports a bad value."""
+    e = instruments.FULL_KEYWORDS[keyword]
     try:
         return getattr(e.module, e.params)(**{name: getattr(args, flag) for name, flag in e.flags})
     except ValueError as err:
@@ -546,7 +567,7 @@ def instrument_params(keyword, args, error):
 def instrument_lines(keyword, res, parts=None):
     """The lines one instrument's flag prints for a result that holds its arrays: its statistics per rank (`parts`: what the ranks
     carried; None: the result as one set) and in total."""
-    e = instruments.WHOLE_KEYWORDS[keyword]
+    e = instruments.FULL_KEYWORDS[keyword]
     return instruments.summary_lines(e, getattr(res, e.field), parts)
 
 

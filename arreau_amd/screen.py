@@ -9,6 +9,7 @@
     python -m arreau_amd.screen out/crystals.npz --coordination [--cn_tol 0.1] [--cn_cutoff 6.0]
     python -m arreau_amd.screen out/crystals.npz --bond_order [--cn_tol 0.1] [--cn_cutoff 6.0]
     python -m arreau_amd.screen out/crystals.npz --voronoi [--vor_tol 0.05] [--vor_cutoff 6.0]
+    python -m arreau_amd.screen out/crystals.npz --xrd [--xrd_wavelength 1.54184] [--xrd_fwhm 0.2] [--xrd_against targets.npz]
     python -m arreau_amd.screen out/crystals.npz --unique [--against train.npz] [--fp_r_max 6] [--fp_sigma 0.1] [--fp_tolerance 0.01]
 
 Prints the summary `python -m arreau_amd.generate --screen` prints (accepted / attempted and the count per flag) and, with
@@ -48,12 +49,18 @@ each weighted by its solid angle over the atom's largest; a face counts at weigh
 cn_eff overall and per element, the share of atoms whose cell vor_cutoff does not close (OPEN) and the count per flag, and the
 voronoi_* arrays with `--out`.  It runs last too, beside `--coordination` / `--bond_order`, on the same crystals.  Not CrystalNN: no
 radii, no electronegativities, no distance weighting, no probabilities.
+`--xrd [--xrd_wavelength --xrd_fwhm --xrd_two_theta_min --xrd_two_theta_max --xrd_points --xrd_b_iso --xrd_scattering]` adds every
+crystal's powder X-ray diffraction pattern on a fixed 2 theta grid (diffusion/xrd.py): the count per flag, the mean number of lattice
+points kept and the mean, minimum and maximum 2 theta of the strongest peak, and the xrd_* arrays with `--out`.  It runs last, on the
+same crystals.  `--xrd_against TARGETS` gives every crystal of TARGETS a pattern under the same parameters: with as many targets as
+crystals it prints the paired mean and median distance ((1 - cos) / 2 of the two patterns), otherwise each crystal's smallest distance to
+any target.  Z-weighted point scatterers: no form-factor tables, no anomalous dispersion, no peak list, no K alpha 2.
 """
 import argparse
 
 
 def build_parser() -> argparse.ArgumentParser:
-    from .generate import (add_coordination_arguments, add_fingerprint_arguments, add_voronoi_arguments, add_screen_arguments, add_structure_match_arguments,
+    from .generate import (add_coordination_arguments, add_fingerprint_arguments, add_voronoi_arguments, add_xrd_arguments, add_screen_arguments, add_structure_match_arguments,
                            add_symmetry_search_arguments)
     ap = argparse.ArgumentParser(prog="python -m arreau_amd.screen", description="structural screen of a crystals file")
     ap.add_argument("file", type=str, help="crystals.npz / .h5")
@@ -88,6 +95,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--voronoi", action="store_true",
                     help="also build every atom's Voronoi cell: solid-angle-weighted neighbours and atom volumes (last: on the crystals --out writes)")
     add_voronoi_arguments(ap)
+    ap.add_argument("--xrd", action="store_true",
+                    help="also write every crystal's powder X-ray diffraction pattern on a fixed 2 theta grid (last: on the crystals --out writes)")
+    ap.add_argument("--xrd_against", type=str, default=None,
+                    help="with --xrd: a crystals file whose patterns (same parameters) the crystals' are compared with: paired mean and "
+                         "median distance with as many targets as crystals, else each crystal's smallest distance to any target")
+    add_xrd_arguments(ap)
     return ap
 
 
@@ -95,7 +108,7 @@ def main(argv=None):
     from .diffusion import cell_reduction, screening, structure_match, symmetry_search
     from .diffusion.inference.process_generated_crystals import load_sample_results_from_hdf5, save_sample_results_to_hdf5
     from .diffusion.diffusion_loss import SampleResult
-    from .diffusion.instruments import WHOLE as INSTRUMENTS
+    from .diffusion.instruments import FULL as INSTRUMENTS
     from .generate import instrument_lines, instrument_params, unique_lines
     ap = build_parser()
     args = ap.parse_args(argv)
@@ -103,6 +116,8 @@ def main(argv=None):
         ap.error("--against needs --unique")
     if args.match_mode is not None and args.match_to is None:
         ap.error("--match_mode needs --match_to")
+    if args.xrd_against is not None and not args.xrd:
+        ap.error("--xrd_against needs --xrd")
     if args.conventional_cell and args.out and (args.reduce_cell or args.symmetrize):
         ap.error("--conventional_cell with --out writes the conventional crystals and --reduce_cell / --symmetrize theirs: run them in "
                  "turn, each on the file the one before wrote")
@@ -122,6 +137,7 @@ def main(argv=None):
     res = load(args.file)
     against = load(args.against) if args.against is not None else None
     targets = load(args.match_to) if args.match_to is not None else None
+    xrd_targets = load(args.xrd_against) if args.xrd_against is not None else None
     res.metrics = screening.screen_sample_result(res, asked["screen"], args.device)
     report("screen", res)
     if asked["unique"] is not None:
@@ -169,6 +185,13 @@ def main(argv=None):
         from .diffusion import voronoi
         current.voronoi = voronoi.voronoi_sample_result(current, asked["voronoi"], args.device)
         report("voronoi", current)
+    if asked["xrd"] is not None:  # (of the same crystals)
+        from .diffusion import xrd
+        current.xrd = xrd.xrd_sample_result(current, asked["xrd"], args.device)
+        report("xrd", current)
+        if xrd_targets is not None:
+            for line in xrd.against_lines(current.xrd["pattern"], xrd.xrd_sample_result(xrd_targets, asked["xrd"], args.device)["pattern"]):
+                print(line)
     if args.out:
         print("wrote", save_sample_results_to_hdf5(current, args.out))
     return res

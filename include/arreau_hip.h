@@ -543,6 +543,76 @@ typedef struct arreau_voronoi_result { /* DEVICE arrays */
 int arreau_crystal_voronoi(const float* d_frac, const float* d_lattice, const int32_t* d_crystal_offsets, int32_t B, int32_t N,
                            const arreau_voronoi_params* params, arreau_voronoi_result* out, void* stream);
 
+/* ---- powder X-ray diffraction patterns of generated crystals ----------------------------------------------------------
+ * Per crystal its powder pattern on a fixed 2 theta grid: the one observable a generated crystal is compared with in a
+ * laboratory, and a signature that does not depend on the description -- a crystal gives the same pattern in any basis, in its
+ * primitive cell, in its conventional cell and in any supercell.  Table free: the atoms are point scatterers of amplitude w_a
+ * (the caller's [N] floats: the atomic numbers, the forward-scattering limit of the X-ray form factor, or 1, or anything else);
+ * no Cromer-Mann form factors, no anomalous dispersion, no peak list, no merging of equivalent reflections, no preferred
+ * orientation, no K alpha 2.  One launch, one workgroup of four waves per crystal, a thread per reflection of a round of 256
+ * box entries, no atomics, no arreau_model.  The order of every sum is fixed, so a crystal's row is the same bits alone, in any
+ * batch and at any place in it.  arreau_amd/diffusion/xrd.py restates the rules in float64 and with the same split of precisions.
+ *   1. PARAMETERS (float64, on the host, once per launch): sigma = fwhm / (2 sqrt(2 ln 2)) degrees; the grid g_p = two_theta_min
+ *      + p step, step = (two_theta_max - two_theta_min) / (n_points - 1), g_{n_points-1} = two_theta_max; the range lo =
+ *      max(two_theta_min - 6 sigma, 0), hi = two_theta_max + 6 sigma as a cut on d*: d*_lo = 2 sin(lo / 2) / wavelength, d*_hi =
+ *      2 sin(hi / 2) / wavelength.  6 sigma <= ARREAU_XRD_MAX_WINDOW = 10 degrees, so hi <= 170: asin and LP stay well conditioned.
+ *   2. CELL (float64 from the float32 entries, taken as exact): rows a_1, a_2, a_3, det = a_1 . (a_2 x a_3), V = |det|, the
+ *      reciprocal rows b_1 = (a_2 x a_3) / det, b_2 = (a_3 x a_1) / det, b_3 = (a_1 x a_2) / det: a_i . b_j = delta_ij, no 2 pi.
+ *      NONFINITE: a cell entry, a coordinate or an amplitude of the crystal is not finite.  CELL: V or the float32 volume (the
+ *      screen's expression, which `volume` reports) is zero or not finite.  EMPTY: no atoms.  In that order; one flag at most.
+ *   3. BOX: |h_k| <= H_k = floor(d*_hi |a_k|) with |a_k| the DIRECT cell's row lengths.  The bound is exact, h_k = G . a_k <= |G|
+ *      |a_k|; the reciprocal lengths would give a smaller box in a skewed cell and lose reflections.  RANGE: an H_k > max_index.
+ *      A flagged crystal's pattern, volume and weight_sum are NaN and its n_reflections 0; nothing else is computed.
+ *   4. REFLECTIONS: the box entries e = (h W_2 + (k + H_2)) W_3 + (l + H_3), W_k = 2 H_k + 1, h = 0 .. H_1, in ascending e; of them
+ *      the half space h > 0, or h = 0 and k > 0, or h = k = 0 and l > 0 (Friedel: each counts twice).  G = (h b_1 + k b_2) + l b_3,
+ *      d*^2 = |G|^2, float64; KEPT iff d*_lo^2 <= d*^2 <= d*_hi^2.  n_reflections = 2 * the kept: the lattice points of the full
+ *      sphere's shell, which depends on the cell's description (a supercell has more, all but the parent's with F = 0).
+ *   5. STRUCTURE FACTOR (float32, one rounding per operation, atoms in order): x_a the wrapped coordinates (f - floor(f), a result
+ *      of 1 becomes 0); t = (h x + k y) + l z; r = t - rint(t) in revolutions; (s, c) = sincospi(2 r); re += w_a c, im += w_a s.
+ *      The reduced phase carries at most 2 pi (|h| + |k| + |l| + 2) 2^-24 radians of error, which grows with max_index.
+ *   6. INTENSITY (float64): sin theta = wavelength d* / 2, theta = asin, 2 theta in degrees; LP = (1 + cos^2 2 theta) / (sin^2
+ *      theta cos theta) from sin theta alone; DW = exp(-b_iso d*^2 / 2) (exp(-B s^2) per amplitude, s = d* / 2, one B for every
+ *      atom); I = 2 (re^2 + im^2) DW LP / V^2.  The 1 / V^2 makes the pattern a property of the crystal, not of the cell it is
+ *      described in.  amp = (float)(I / (sigma sqrt(2 pi))).
+ *   7. PATTERN: P(g_p) = sum over the kept reflections, in ascending e, of amp * expf(-0.5 z^2), z = (float)((g_p - 2 theta_hkl)
+ *      / sigma), the difference float64, over the grid points with |g_p - 2 theta_hkl| <= 6 sigma; float32 adds, no atomics.  The
+ *      cut at 6 sigma drops terms of relative size e^-18 = 1.5e-8.  The pattern is a smooth function of the inputs: no binning.
+ *   8. weight_sum = sum w_a: thread t adds atoms t, t + 256, ..., then the wave butterfly, then the four waves in order.
+ * Offsets are clamped as in the screen.  The defaults (Cu K alpha 1.54184 A, 5..90 degrees in 1701 points, fwhm 0.2, b_iso 0,
+ * max_index 64) are starting values, not claims.
+ * Argument errors (ARREAU_EINVAL, nothing launched): NULL params / result / arrays, negative sizes, wavelength not finite or
+ * <= 0, not 0 <= two_theta_min < two_theta_max <= ARREAU_XRD_MAX_TWO_THETA, n_points outside 2..ARREAU_XRD_MAX_POINTS, fwhm not
+ * finite or <= 0, 6 sigma > ARREAU_XRD_MAX_WINDOW, b_iso not finite or < 0, max_index outside 1..ARREAU_XRD_MAX_INDEX.  B == 0
+ * returns ARREAU_OK. */
+#define ARREAU_XRD_NONFINITE 1
+#define ARREAU_XRD_CELL 2
+#define ARREAU_XRD_EMPTY 4
+#define ARREAU_XRD_RANGE 8
+#define ARREAU_XRD_MAX_POINTS 4096
+#define ARREAU_XRD_MAX_INDEX 127
+#define ARREAU_XRD_MAX_TWO_THETA 160.0
+#define ARREAU_XRD_MAX_WINDOW 10.0 /* degrees: the largest 6 sigma */
+typedef struct arreau_xrd_params {
+    double wavelength;     /* A; default 1.54184 (Cu K alpha) */
+    double two_theta_min;  /* degrees; default 5 */
+    double two_theta_max;  /* degrees; default 90 */
+    double fwhm;           /* degrees; default 0.2 */
+    double b_iso;          /* A^2; default 0 */
+    int32_t n_points;      /* 2..ARREAU_XRD_MAX_POINTS; default 1701 */
+    int32_t max_index;     /* 1..ARREAU_XRD_MAX_INDEX; default 64 */
+} arreau_xrd_params;
+typedef struct arreau_xrd_result { /* DEVICE arrays */
+    float* pattern;          /* [B, n_points] */
+    int32_t* n_reflections;  /* [B] */
+    float* volume;           /* [B] */
+    float* weight_sum;       /* [B] */
+    int32_t* flags;          /* [B] ARREAU_XRD_* */
+} arreau_xrd_result;
+/* d_frac, d_lattice, d_crystal_offsets as for the coordination search; d_weights [N] float32, the atoms' amplitudes.  `params`
+ * and `out` are HOST pointers to the structs; the arrays `out` names are device arrays. */
+int arreau_crystal_xrd(const float* d_frac, const float* d_lattice, const int32_t* d_crystal_offsets, const float* d_weights,
+                       int32_t B, int32_t N, const arreau_xrd_params* params, arreau_xrd_result* out, void* stream);
+
 /* ---- duplicate detection: structure fingerprints and their all-pairs match ------------------------------------------
  * The screen's sibling: per crystal a reduced formula and a fingerprint of its pair distribution (Oganov & Valle, J. Chem.
  * Phys. 130, 104504 (2009), with the normalisation taken at the bin centre so that it is finite for every input), and for
