@@ -41,6 +41,7 @@ EXPORTS = [
     "arreau_loss_rows_reduce",
     "arreau_sample_loop_keyed", "arreau_noise_state_keyed", "arreau_condition_initial_state_keyed", "arreau_philox_fill_crystals",
     "arreau_sample_loop_guided", "arreau_contact_guidance_step",
+    "arreau_sample_loop_xrd_guided", "arreau_xrd_guidance_step",
 ]
 
 STATUS_NONFINITE, STATUS_BAD_TIMESTEP, STATUS_BAD_TYPE, STATUS_BAD_TIE, STATUS_BAD_SYMMETRY = 1, 2, 4, 8, 16
@@ -164,6 +165,13 @@ class XrdResultC(Structure):
     _fields_ = [(name, c_void_p) for name in ("pattern", "n_reflections", "volume", "weight_sum", "flags")]
 
 
+class XrdGuidanceC(Structure):
+    """arreau_xrd_guidance: the xrd parameters, the weight, the target patterns [B, n_points], the class or atom amplitudes (one of
+    them NULL) and the three device diagnostic arrays (each may be NULL)."""
+    _fields_ = [("params", XrdParamsC), ("weight", c_float), ("d_target", c_void_p), ("d_class_weights", c_void_p),
+                ("d_atom_weights", c_void_p), ("d_distance", c_void_p), ("d_reflections", c_void_p), ("d_flags", c_void_p)]
+
+
 class FingerprintParamsC(Structure):
     """arreau_fingerprint_params: the radial grid and smearing of the structure fingerprint."""
     _fields_ = [("r_max", c_float), ("sigma", c_float), ("n_bins", c_int32), ("max_shells", c_int32)]
@@ -256,7 +264,7 @@ def _prototypes():
     vp, i32, i64, u32, u64, f32, f64 = c_void_p, c_int32, c_int64, ctypes.c_uint32, ctypes.c_uint64, c_float, c_double
     cond, sched, corr, res, sym = (POINTER(t) for t in (SampleConditionC, SampleScheduleC, CorrectorC, ResamplingC, SymmetryC))
     ms = POINTER(MultistepC)
-    spec, f32p, guide = POINTER(SpeciesControlC), POINTER(c_float), POINTER(ContactGuidanceC)
+    spec, f32p, guide, xguide = POINTER(SpeciesControlC), POINTER(c_float), POINTER(ContactGuidanceC), POINTER(XrdGuidanceC)
     loop = [vp] * 6 + [i32] * 4 + [u64] + [vp] * 4 + [c_size_t, i32]
     step_to = [vp] * 8 + [i32, i32] + [vp] * 7 + [f32]
     jump = [vp] * 8 + [i32, i32] + [vp] * 5 + [cond, vp]
@@ -299,6 +307,8 @@ def _prototypes():
         "arreau_sample_loop_keyed": loop + [cond, sched, corr, res, vp, sym, f32p, ms, spec, vp, vp],
         "arreau_sample_loop_guided": loop + [cond, sched, corr, res, vp, sym, f32p, ms, spec, vp, guide, vp],
         "arreau_contact_guidance_step": [vp] * 5 + [i32, i32, vp, guide, vp],
+        "arreau_sample_loop_xrd_guided": loop + [cond, sched, corr, res, vp, sym, f32p, ms, spec, vp, guide, xguide, vp],
+        "arreau_xrd_guidance_step": [vp] * 6 + [i32, i32, vp, xguide, vp, vp],
         "arreau_noise_state_keyed": [vp] * 6 + [i32, i32, i32, u64] + [vp] * 6,
         "arreau_condition_initial_state_keyed": [vp] * 5 + [i32, i32, i32, u64, cond, vp, vp],
         "arreau_philox_fill_crystals": [vp, vp, i32, i32, i32, u32, i32, i32, vp, vp, vp],

@@ -324,6 +324,7 @@ int enqueue_sample_step(const arreau_model* m, const ScorePlan& plan, const Samp
         }
         // contact guidance: the eps of this evaluation, guided in place, is what the corrector and the predictor below read
         if (opt.guide && (rc = arreau_launch_contact_guide(m, st, w.t_cur, w.lattice, w.eps, *opt.guide, s))) return rc;
+        if (opt.xrd_guide && (rc = arreau_launch_xrd_guide(m, st, w.t_cur, w.lattice, w.eps, *opt.xrd_guide, nullptr, s))) return rc;
         if (j < opt.corr.steps && (rc = arreau_launch_corrector(m, st, w.t_cur, w.eps, nullptr, seed, (uint32_t)j, opt, s))) return rc;
     }
     // without a prep launch per step (fused kernels only) the update also leaves the next step's lattice and embedding behind
@@ -362,6 +363,7 @@ struct LoopRequest {
     bool species_required = false;  // arreau_sample_loop_species and the exports built on it (their multistep rules have their own wording)
     const uint64_t* d_crystal_seeds = nullptr;
     const arreau_contact_guidance* guidance = nullptr;
+    const arreau_xrd_guidance* xrd_guidance = nullptr;
     bool invert = false;  // arreau_invert_loop: t_start is the first level
 };
 
@@ -415,6 +417,7 @@ int resolve_loop_request(const char* who, const arreau_model* m, const SampleSta
     const arreau_resampling* resampling = req.resampling;
     int rc;
     if (req.guidance && (rc = arreau_contact_guidance_check(req.guidance, who))) return rc;
+    if (req.xrd_guidance && (rc = arreau_xrd_guidance_check(req.xrd_guidance, who, false))) return rc;
     if (req.species_required && (rc = arreau_species_check(req.species, who, &o.species))) return rc;  // (-0 -> +0)
     o.species_on = req.species_required;
     if (req.eta && (rc = arreau_eta_check(*req.eta, who))) return rc;
@@ -445,6 +448,7 @@ int resolve_loop_request(const char* who, const arreau_model* m, const SampleSta
         }
     }
     ARREAU_REQUIRE(!req.invert || !req.guidance, "arreau_invert_loop: an inversion loop takes no contact guidance");
+    ARREAU_REQUIRE(!req.invert || !req.xrd_guidance, "arreau_invert_loop: an inversion loop takes no xrd guidance");
     if (corrector) {
         if ((rc = arreau_corrector_check(corrector->steps, corrector->snr, "arreau_sample_loop_corrected"))) return rc;
         // a NULL corrector and steps == 0 are the same loop (and the same graph key): the snr is then not read
@@ -480,6 +484,7 @@ int resolve_loop_request(const char* who, const arreau_model* m, const SampleSta
     o.invert = req.invert;
     o.crystal_seeds = req.d_crystal_seeds;
     if (req.guidance && req.guidance->weight > 0.0f) o.guide = *req.guidance;  // weight 0: the loop without the option (and its graph key)
+    if (req.xrd_guidance && req.xrd_guidance->weight > 0.0f) o.xrd_guide = *req.xrd_guidance;  // (the same)
     const bool plain = arreau_condition_empty(&o.cond) && o.corr.steps == 0 && o.resample_passes == 0;
     ARREAU_REQUIRE(!req.multistep || (plain && !req.symmetry && !req.invert && o.eta == 0.0f),
                    "arreau_sample_loop_multistep: a multistep loop takes no condition, corrector steps, resampling or symmetry");
@@ -614,7 +619,7 @@ int run_sample_loop(const char* who, arreau_model* m, const SampleState& st, con
 
 // The exports: each is a fill of the state and of a LoopRequest with what it takes, and one call of run_sample_loop under its own
 // name.  The first six are each the one before plus one option (NULL: the loop without it); _eta, _multistep and _sym are the tied
-// one plus theirs; _species takes all of those, _keyed and _guided one more each.  The rules of the options are stated in
+// one plus theirs; _species takes all of those, _keyed, _guided and _xrd_guided one more each.  The rules of the options are stated in
 // include/arreau_hip.h and applied by resolve_loop_request.
 extern "C" int arreau_sample_loop(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
                                   const int32_t* d_off, int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed,
@@ -782,6 +787,27 @@ extern "C" int arreau_sample_loop_guided(arreau_model* m, float* d_frac, int32_t
                             .use_graph = use_graph, .stream = stream, .condition = condition, .schedule = schedule, .corrector = corrector,
                             .resampling = resampling, .d_length_tie = d_length_tie, .symmetry = symmetry, .eta = eta, .multistep = multistep,
                             .species = species, .species_required = true, .d_crystal_seeds = d_crystal_seeds, .guidance = guidance});
+}
+
+// XRD guidance: arreau_sample_loop_guided whose every network evaluation is also followed by the XRD guidance launch on its eps,
+// after contact guidance's; a NULL struct or weight == 0 is arreau_sample_loop_guided bit for bit.
+extern "C" int arreau_sample_loop_xrd_guided(arreau_model* m, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                                             const int32_t* d_off, int32_t B, int32_t N, int32_t t_start, int32_t n_steps, uint64_t seed,
+                                             const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice,
+                                             void* d_workspace, size_t workspace_bytes, int32_t use_graph,
+                                             const arreau_sample_condition* condition, const arreau_sample_schedule* schedule,
+                                             const arreau_corrector* corrector, const arreau_resampling* resampling,
+                                             const int32_t* d_length_tie, const arreau_symmetry* symmetry, const float* eta,
+                                             const arreau_multistep* multistep, const arreau_species_control* species,
+                                             const uint64_t* d_crystal_seeds, const arreau_contact_guidance* guidance,
+                                             const arreau_xrd_guidance* xrd_guidance, void* stream) {
+    const SampleState st{d_frac, d_types, d_lengths, d_angles, d_off, B, N, d_const_types, d_fixed_lengths, d_lattice};
+    return run_sample_loop("arreau_sample_loop_xrd_guided", m, st,
+                           {.t_start = t_start, .n_steps = n_steps, .seed = seed, .workspace = d_workspace, .workspace_bytes = workspace_bytes,
+                            .use_graph = use_graph, .stream = stream, .condition = condition, .schedule = schedule, .corrector = corrector,
+                            .resampling = resampling, .d_length_tie = d_length_tie, .symmetry = symmetry, .eta = eta, .multistep = multistep,
+                            .species = species, .species_required = true, .d_crystal_seeds = d_crystal_seeds, .guidance = guidance,
+                            .xrd_guidance = xrd_guidance});
 }
 
 // DDIM inversion: the sampling loop climbing the levels of an ascending table, every step the network evaluation at the crystals'

@@ -81,6 +81,8 @@ ARREAU_MEMBERWISE_EQ(arreau_symmetry, leader, op, orbit, orbit_ptr, orbit_atoms,
 ARREAU_MEMBERWISE_EQ(arreau_multistep, hist_eps, hist_x0, hist_t_atom, hist_t_len)
 ARREAU_MEMBERWISE_EQ(arreau_species_control, d_allow, temperature)
 ARREAU_MEMBERWISE_EQ(arreau_contact_guidance, min_distance, weight, max_shells, d_energy, d_contacts, d_flags)
+ARREAU_MEMBERWISE_EQ(arreau_xrd_params, wavelength, two_theta_min, two_theta_max, fwhm, b_iso, n_points, max_index)
+ARREAU_MEMBERWISE_EQ(arreau_xrd_guidance, params, weight, d_target, d_class_weights, d_atom_weights, d_distance, d_reflections, d_flags)
 #undef ARREAU_MEMBERWISE_EQ
 
 // Respaced sampling (arreau_sample_loop_scheduled, arreau_reverse_step_to; the rules are stated in include/arreau_hip.h): the step
@@ -117,6 +119,7 @@ struct StepOptions {
     const arreau_species_control* species = nullptr;  // species control (SPEC): the admission rows and the temperature; not with invert
     const uint64_t* crystal_seeds = nullptr;  // keyed sampling: the stream seed of every crystal (StepNoiseSrc::seeds of every draw)
     const arreau_contact_guidance* guide = nullptr;  // contact guidance: one launch on the eps of every evaluation; null (also for weight 0): none; not with invert
+    const arreau_xrd_guidance* xrd_guide = nullptr;  // XRD guidance: one launch on that eps, after contact guidance's; null (also for weight 0): none; not with invert
 };
 
 // The options of one loop call, checked, normalised and held by value (api.hip: resolve_loop_request is the one place that fills
@@ -140,12 +143,14 @@ struct SampleOptions {
     arreau_species_control species;  // ... and their admission rows and temperature
     const uint64_t* crystal_seeds; // keyed sampling: the table of stream seeds (null: not keyed)
     arreau_contact_guidance guide; // contact guidance: parameters and diagnostic arrays (weight 0: none)
+    arreau_xrd_guidance xrd_guide; // XRD guidance: parameters, target, amplitudes and diagnostic arrays (weight 0: none)
     bool operator==(const SampleOptions&) const = default;
     StepOptions view() const {     // valid while *this is
         return StepOptions{.cond = cond.pos_mask || cond.type_mask || cond.len_mask ? &cond : nullptr, .sched = sched.next ? &sched : nullptr,
                            .corr = corr, .pass = pass, .length_tie = length_tie, .sym = sym.leader ? &sym : nullptr, .eta = eta,
                            .ms = ms.hist_eps ? &ms : nullptr, .invert = invert, .species = species_on ? &species : nullptr,
-                           .crystal_seeds = crystal_seeds, .guide = guide.weight > 0.0f ? &guide : nullptr};
+                           .crystal_seeds = crystal_seeds, .guide = guide.weight > 0.0f ? &guide : nullptr,
+                           .xrd_guide = xrd_guide.weight > 0.0f ? &xrd_guide : nullptr};
     }
 };
 
@@ -364,6 +369,15 @@ int arreau_species_check(const arreau_species_control* species, const char* who,
 int arreau_contact_guidance_check(const arreau_contact_guidance* g, const char* who);
 int arreau_launch_contact_guide(const arreau_model* m, const SampleState& st, const int32_t* d_t, const float* d_lattice, float* d_eps,
                                 const arreau_contact_guidance& opt, hipStream_t s);
+
+// XRD guidance (arreau_sample_loop_xrd_guided, arreau_xrd_guidance_step; the rules are stated in include/arreau_hip.h).
+// arreau_xrd_guidance_check: ARREAU_EINVAL unless the struct is given, its arreau_xrd_params pass the xrd launch's validation, weight
+// is finite and >= 0, the target is given and exactly one of the amplitude arrays is (a loop: the class weights).  The launch reads
+// st.frac / types / offsets / B / N, the per-crystal timesteps d_t and the cells d_lattice [B,9] the evaluation saw, rewrites d_eps
+// [N,3] in place and writes g to d_gradient [N,3] when that is given (xrd_guide.hip).
+int arreau_xrd_guidance_check(const arreau_xrd_guidance* g, const char* who, bool step_export);
+int arreau_launch_xrd_guide(const arreau_model* m, const SampleState& st, const int32_t* d_t, const float* d_lattice, float* d_eps,
+                            const arreau_xrd_guidance& opt, float* d_gradient, hipStream_t s);
 
 // One corrector move per crystal at timestep d_t[b]: z from the caller's d_z_frac [N,3], or (d_z_frac null) the Philox draw
 // (seed, t, ARREAU_DRAW_Z_CORRECTOR, element, iter; 256 pass[0] + iter with opt.pass; keyed by opt.crystal_seeds when given).  Reads

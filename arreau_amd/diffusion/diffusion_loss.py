@@ -20,6 +20,7 @@ from . import respacing
 from . import sample_plan
 from . import species as species_mod
 from . import contact_guidance as guidance_mod
+from . import xrd_guidance as xrd_guidance_mod
 from .d3pm import D3PM
 from . import lattice_systems
 from . import symmetry as sym_mod
@@ -239,6 +240,7 @@ class _RunBuffers:
     history: Optional[dict] = None          # multistep: empty at first, held through segments and a re-run
     guide: Optional[tuple] = None           # contact guidance: (parameters, the device arrays of its last evaluation)
     species_ctl: Optional[tuple] = None     # (rows, temperature); None (no set, temperature 1) keeps the exports used so far
+    xguide: Optional[object] = None         # XRD guidance: the xrd_guidance.DeviceGuidance of the run (target, amplitudes, diagnostics)
 
     @classmethod
     def upload(cls, dev, plan, state, held, T, clipmax):
@@ -279,7 +281,7 @@ def _philox_driver(eng, plan, buf, seed, use_graph, frame):
                             buf.lattice_d, use_graph=bool(use_graph), fixed_lengths=fixed, condition=buf.cond_d, next_table=buf.next_d,
                             lattice_clipmax=buf.clipmax, corrector=plan.corrector, resampling=plan.resampling, length_tie=buf.tie_d,
                             symmetry=buf.sym_d, eta=plan.eta, multistep=buf.history, species=buf.species_ctl,
-                            crystal_seeds=buf.seeds_d, guidance=buf.guide)
+                            crystal_seeds=buf.seeds_d, guidance=buf.guide, **({"xrd_guidance": buf.xguide} if buf.xguide is not None else {}))
             start = end
         if j is not None:
             frame(f"_{plan.steps[j]}")
@@ -301,10 +303,12 @@ def _host_noise_driver(eng, plan, buf, seed, use_graph, frame):
     state = (buf.frac_d, buf.types_d, buf.len_d, buf.ang_d)
     corrector_steps, corrector_snr = plan.corrector or (0, None)
 
-    def evaluate():  # the network at t_d on the current state; with contact guidance its eps is guided in place
+    def evaluate():  # the network at t_d on the current state; with guidance its eps is guided in place: contacts, then the pattern
         eps, logits, len0 = eng.predict_scores(*state, t_d, buf.off_d)
         if buf.guide is not None and buf.guide[0].weight > 0:
             eng.contact_guidance_step(buf.frac_d, lattice_from_params(buf.len_d, buf.ang_d), t_d, buf.off_d, eps, buf.guide)
+        if buf.xguide is not None and buf.xguide.weight > 0:
+            eng.xrd_guidance_step(buf.frac_d, buf.types_d, lattice_from_params(buf.len_d, buf.ang_d), t_d, buf.off_d, eps, buf.xguide)
         return eps, logits, len0
     for ev in plan.events:
         if ev.kind == "jump":  # resampling: the state back up to the block's top, in front of pass ev.r
@@ -544,7 +548,8 @@ class DiffusionLoss(nn.Module):
                lattice_system=None, symmetry=None, screen=None, unique=None, find_symmetry=None, reduce_cell=None,
                symmetrize=None, match_to=None, eta: Optional[float] = None, initial_state=None,
                multistep: bool = False, elements=None, species_temperature: float = 1.0, crystal_keys=None,
-               conventional_cell=None, coordination=None, bond_order=None, contact_guidance=None, voronoi=None, xrd=None) -> SampleResult:
+               conventional_cell=None, coordination=None, bond_order=None, contact_guidance=None, voronoi=None, xrd=None,
+               xrd_guidance=None) -> SampleResult:
         """diffusion_loss.py:276-377.  The initial state is drawn on the host exactly like the reference (numpy
         uniforms for the angles, then randn lengths, randn fractional coordinates from torch's global CPU generator):
         draw_initial_state, which a caller may also use on its own.
@@ -747,7 +752,23 @@ class DiffusionLoss(nn.Module):
         the last evaluation's energy, contacts and flags per crystal (contact_guidance.INFO_KEYS).  Positions only: no cell-strain
         term, no radii or species dependence, no weight schedule other than 1 / sigma_t^2; no claim on sample quality.  A bad
         value is rejected before any work.  weight = 0 and None: no launch is added and the results are what they were, bit for
-        bit (None also through the exports it used)."""
+        bit (None also through the exports it used).
+        `xrd_guidance` (extension, every noise mode and option): an xrd_guidance.XrdGuidance(target, weight=2.0, params=XrdParams())
+        -- training-free guidance of the positions towards a target powder pattern (rules in include/arreau_hip.h, "XRD guidance";
+        arreau_sample_loop_xrd_guided): structure solution from a powder pattern with the cell given (fixed_cell, a condition or
+        a lattice system) and the composition given.  `target`: patterns [n_points] or [B, n_points] on the grid of `params`, or
+        crystals (a SampleResult or a loaded file), whose patterns are computed under the same params before the loop.  Every
+        network evaluation is followed, after contact guidance's launch, by one launch that adds the gradient of the distance
+        (1 - cos(P, Q)) / 2 between the pattern P of the current positions and the target Q, preconditioned by the cell and
+        scaled by weight / sigma_t^2, to the predicted eps.  The amplitude of an atom is that of its current class (Z, or 1 under
+        scattering "unit"; 0 for the mask class: a masked atom neither scatters nor is pushed).  noise="philox" runs it inside the
+        loop, graph replay included; noise="device" and "reference" run the same launch between the evaluation and the step
+        (arreau_xrd_guidance_step).  SampleResult.info["xrd_guidance"] holds the last evaluation's distance, reflections and
+        flags per crystal (xrd_guidance.INFO_KEYS).  Positions only: a wrong cell cannot be repaired; no guidance of species, no
+        intensity scale or background fit, no weight schedule other than 1 / sigma_t^2, crystals of more than 256 atoms are
+        flagged LARGE and not guided; no claim on sample quality.  A bad value, scattering "weights" and a target count other
+        than 1 or the batch's are rejected before any work.  weight = 0 and None: no launch is added and the results are what they
+        were, bit for bit (None also through the exports it used)."""
         options = {k: v for k, v in locals().items() if k != "self"}  # (first statement: the keywords as given, nothing else)
         sample_plan.check_options(**options)  # (what needs nothing of self, first)
         plan = sample_plan.resolve(self.T, **options)
@@ -769,6 +790,8 @@ class DiffusionLoss(nn.Module):
             buf.cond_d = condition.device_arrays(z_table, dev)
             eng.condition_initial_state(buf.frac_d, buf.types_d, buf.len_d, plan.t_first, seed, buf.cond_d, offsets=buf.off_d,
                                         crystal_seeds=buf.seeds_d)
+        if plan.xrd_guidance is not None:  # the target rows (crystals: one xrd launch), the class amplitudes, the diagnostics
+            buf.xguide = xrd_guidance_mod.device_guidance(plan.xrd_guidance, z_table, plan.B, dev)
         saved = buf.snapshot()
 
         def frame(suffix):  # the current state as a frame file
@@ -796,6 +819,8 @@ class DiffusionLoss(nn.Module):
         eng.check_status()  # sticky device flags (non-finite outputs, clamped indices): raise instead of returning them
         if buf.guide is not None:
             info = dict(info or {}, contact_guidance=guidance_mod.info_to_numpy(buf.guide[1]))
+        if buf.xguide is not None:
+            info = dict(info or {}, xrd_guidance=xrd_guidance_mod.info_to_numpy(buf.xguide.info))
         if visualization_setting != VisualizationSetting.NONE:
             frame("_final")
         # the instruments, by table: each reads the final state where it is and fills its own field

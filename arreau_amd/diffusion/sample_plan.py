@@ -21,6 +21,7 @@ from . import resampling as rs
 from . import respacing
 from . import species as species_mod
 from . import symmetry as sym_mod
+from . import xrd_guidance as xrd_guidance_mod
 from .inference.visualize_crystal import VisualizationSetting
 
 NOISE_MODES = ("philox", "device", "reference")
@@ -30,6 +31,7 @@ NOISE_MODES = ("philox", "device", "reference")
 class SamplePlan:
     instruments: dict            # sample() keyword -> resolved parameters (None: not asked for), the shared-launch rules applied
     guidance: object             # the resolved ContactGuidance or None
+    xrd_guidance: object         # the XrdGuidance or None: scattering "Z" or "unit", one target for all crystals or one each
     noise: str
     visualization_setting: object
     num_atoms_per_sample: object  # as draw_initial_state takes it: after the state, the specs or the condition defined the batch
@@ -159,12 +161,14 @@ def _visited(schedule, top, max_steps):
 def check_options(*, vis_name="", visualization_setting=VisualizationSetting.NONE, noise="philox", use_graph=None, seed=None,
                   fixed_cell=False, condition=None, corrector_steps=0, corrector_snr=pc.DEFAULT_SNR, resample_passes=1, jump_length=10,
                   symmetry=None, eta=None, multistep=False, species_temperature=1.0, crystal_keys=None, contact_guidance=None,
-                  **others):
+                  xrd_guidance=None, **others):
     """The rules that need neither the diffusion nor the batch: every option value on its own and the combinations that are
     rejected whatever the batch.  `resolve` starts with them; PONITA_DIFFUSION.sample runs them before it reads anything of
     itself.  Returns (the fields of SamplePlan these rules decide, passes, jump length); `others` holds the instrument keywords
     and whatever of sample()'s keywords has no rule here."""
     guidance = guidance_mod.resolve(contact_guidance)
+    xrd_guidance = xrd_guidance_mod.resolve(xrd_guidance)
+    xrd_guidance_mod.check_sampling(xrd_guidance)
     resolved = _resolve_instruments({k: others.get(k) for k in instruments.FULL_KEYWORDS})
     if crystal_keys is not None:  # (the count: resolve)
         crystal_keys = keyed_mod.validate_keys(crystal_keys, None, seed, noise if noise in NOISE_MODES else "philox")
@@ -183,7 +187,7 @@ def check_options(*, vis_name="", visualization_setting=VisualizationSetting.NON
                          "would be overwritten by the block's next pass")
     if (use_graph or fixed_cell) and noise != "philox":
         raise ValueError("graph replay and fixed-cell sampling need noise='philox' (the in-kernel generator)")
-    return dict(instruments=resolved, guidance=guidance, noise=noise, visualization_setting=visualization_setting,
+    return dict(instruments=resolved, guidance=guidance, xrd_guidance=xrd_guidance, noise=noise, visualization_setting=visualization_setting,
                 corrector=(corrector_steps, corrector_snr) if corrector_steps > 0 else None, eta=eta, multistep=multistep,
                 species_temperature=species_temperature, crystal_keys=crystal_keys, fixed_cell=bool(fixed_cell)), resample_passes, jump_length
 
@@ -209,6 +213,7 @@ def resolve(T, z_table, *, num_atoms_per_sample=None, num_samples_in_batch=None,
     elif num_atoms_per_sample is None or num_samples_in_batch is None:
         raise ValueError("num_atoms_per_sample and num_samples_in_batch are needed without a condition")
     B = int(num_samples_in_batch)
+    xrd_guidance_mod.check_sampling(decided["xrd_guidance"], B=B)
     if decided["crystal_keys"] is not None:
         keyed_mod.validate_keys(decided["crystal_keys"], B, seed)
     lattice_systems.check(lattice_system, B, condition.lattice_known() if condition is not None else None)

@@ -13,6 +13,7 @@ from . import _hip
 from .diffusion import (bond_order as bond_order_mod, cell_reduction, conventional_cell as conventional_mod,
                         coordination as coordination_mod, screening, symmetrize as symmetrize_mod, symmetry_search,
                         voronoi as voronoi_mod, xrd as xrd_mod)
+from .diffusion import xrd_guidance as xrd_guidance_mod
 from .diffusion.contact_guidance import INFO_KEYS, ContactGuidance
 from .diffusion.corrector import check_corrector
 from .diffusion.ddim import check_eta
@@ -62,6 +63,8 @@ _LOOP_EXPORTS = (
     ("arreau_sample_loop_resampled", "common", ()),
     ("arreau_sample_loop", None, None),
 )
+# XRD guidance: the row read ahead of the table's -- the guided export plus the struct
+_XRD_LOOP_EXPORT = ("arreau_sample_loop_xrd_guided", "xrd_guidance", _SPECIES_COLUMNS + ("seeds", "guidance", "xrd_guidance"))
 
 
 def screen(frac, lattice, offsets, types=None, criteria=None):
@@ -322,7 +325,7 @@ class HipEngine:
     def sample_loop(self, frac, types, lengths, angles, offsets, t_start, n_steps, seed, const_types, lattice_out,
                     use_graph=False, fixed_lengths=None, condition=None, next_table=None, lattice_clipmax=0.999, corrector=None,
                     resampling=None, length_tie=None, symmetry=None, eta=None, multistep=None, species=None, crystal_seeds=None,
-                    guidance=None):
+                    guidance=None, xrd_guidance=None):
         """n_steps iterations of the sampling loop in one library call (arreau_sample_loop; with any of the options below
         arreau_sample_loop_resampled, whose NULL options are the loop without them): in-place update of
         (frac, types, lengths); Philox noise keyed by (seed, timestep, draw, element).  `condition`: the device arrays of a
@@ -353,12 +356,19 @@ class HipEngine:
         or the pair (ContactGuidance, info) with info the dict of device arrays of contact_guidance.allocate_info, which then hold
         the last evaluation's energy, contacts and flags per crystal.  Every network evaluation of every step is followed by one
         launch that adds the gradient of the contact penalty to its eps.  The export is the keyed one plus the struct, so without
-        `species` the steps run under (every class, temperature 1).  None is the loop without it, through the export it used."""
+        `species` the steps run under (every class, temperature 1).  None is the loop without it, through the export it used.
+        `xrd_guidance`: XRD guidance (arreau_sample_loop_xrd_guided; rules in include/arreau_hip.h): an
+        xrd_guidance.DeviceGuidance -- the xrd parameters, the weight, the target patterns [B, n_points], the class amplitudes [S]
+        and, when given, the info arrays of xrd_guidance.allocate_info, which then hold the last evaluation's distance,
+        reflections and flags per crystal.  Every network evaluation of every step is followed, after contact guidance's launch,
+        by one launch that adds the gradient of the pattern distance to its eps.  The export is the guided one plus the struct.
+        None is the loop without it, through the export it used."""
         N, B = frac.shape[0], lengths.shape[0]
         guide = self._guidance_struct(guidance, B) if guidance is not None else None
+        xguide = self._xrd_guidance_struct(xrd_guidance, B, N) if xrd_guidance is not None else None
         if crystal_seeds is not None:
             self._check_seeds(crystal_seeds, B)
-        if (guide is not None or crystal_seeds is not None) and species is None:
+        if (guide is not None or xguide is not None or crystal_seeds is not None) and species is None:
             species = (None, 1.0)
         if multistep is not None:
             check_multistep(True, eta=eta, condition=condition, corrector_steps=corrector[0] if corrector is not None else 0,
@@ -396,10 +406,11 @@ class HipEngine:
         columns = {"tie": _hip.ptr(length_tie), "eta": eta_c, "eta_ref": _byref(eta_c), "seeds": _hip.ptr(crystal_seeds),
                    "sym": _byref(self._symmetry_struct(symmetry, N) if symmetry is not None else None),
                    "multistep": _byref(self._multistep_struct(multistep, N, B) if multistep is not None else None),
-                   "species": _byref(self._species_struct(species, B) if species is not None else None), "guidance": _byref(guide)}
-        given = {"guidance": guide, "seeds": crystal_seeds, "species": species, "multistep": multistep, "sym": symmetry, "eta": eta,
+                   "species": _byref(self._species_struct(species, B) if species is not None else None), "guidance": _byref(guide),
+                   "xrd_guidance": _byref(xguide)}
+        given = {"xrd_guidance": xguide, "guidance": guide, "seeds": crystal_seeds, "species": species, "multistep": multistep, "sym": symmetry, "eta": eta,
                  "tie": length_tie, "common": next((o for o in common if o is not None), None)}
-        name, _, takes = next(row for row in _LOOP_EXPORTS if row[1] is None or given[row[1]] is not None)
+        name, _, takes = next(row for row in (_XRD_LOOP_EXPORT,) + _LOOP_EXPORTS if row[1] is None or given[row[1]] is not None)
         opts = common + tuple(columns[c] for c in takes) if takes is not None else ()
         _hip.check(getattr(_hip.lib(), name)(*args, *opts, _hip.stream_ptr(self.device)), name)
 
@@ -431,6 +442,51 @@ class HipEngine:
         _hip.check(_hip.lib().arreau_contact_guidance_step(
             self._handle, _hip.ptr(frac), _hip.ptr(lattice), _hip.ptr(t_crystal), _hip.ptr(offsets), B, N, _hip.ptr(eps),
             ctypes.byref(guide), _hip.stream_ptr(self.device)), "arreau_contact_guidance_step")
+        return eps
+
+    def _xrd_guidance_struct(self, guidance, B, N, step=False):
+        """arreau_xrd_guidance of an xrd_guidance.DeviceGuidance, with its tensors' shape, dtype and device checked; keeps the
+        nested parameter struct alive with the result."""
+        g = guidance
+        if not isinstance(g, xrd_guidance_mod.DeviceGuidance) or not isinstance(g.params, xrd_mod.XrdParams):
+            raise ValueError(f"xrd_guidance must be an xrd_guidance.DeviceGuidance, got {guidance!r}")
+        p = g.params
+        _require("xrd guidance", "target", g.target, (B, p.n_points), torch.float32, self.device)
+        if (g.class_weights is None) == (g.atom_weights is None) or (g.atom_weights is not None and not step):
+            raise ValueError("xrd guidance: exactly one of class_weights and atom_weights (the step export alone) is required")
+        if g.class_weights is not None:
+            _require("xrd guidance", "class_weights", g.class_weights, (self.S,), torch.float32, self.device)
+        else:
+            _require("xrd guidance", "atom_weights", g.atom_weights, (N,), torch.float32, self.device)
+        ptrs = [None, None, None]
+        if g.info is not None:
+            if not isinstance(g.info, dict) or set(g.info) != set(xrd_guidance_mod.INFO_KEYS):
+                raise ValueError(f"xrd guidance info: expected a dict with exactly the keys {xrd_guidance_mod.INFO_KEYS}")
+            for q, name in enumerate(xrd_guidance_mod.INFO_KEYS):
+                _require("xrd guidance info", name, g.info[name], (B,), torch.float32 if name == "distance" else torch.int32, self.device)
+                ptrs[q] = _hip.ptr(g.info[name]).value
+        params = _hip.XrdParamsC(p.wavelength, p.two_theta_min, p.two_theta_max, p.fwhm, p.b_iso, p.n_points, p.max_index)
+        value = lambda t: _hip.ptr(t).value if t is not None else None
+        return _hip.XrdGuidanceC(params, g.weight, value(g.target), value(g.class_weights), value(g.atom_weights), *ptrs)
+
+    def xrd_guidance_step(self, frac, types, lattice, t_crystal, offsets, eps, guidance, gradient=None):
+        """XRD guidance on eps [N,3] in place (arreau_xrd_guidance_step; rules in include/arreau_hip.h): frac [N,3] f32, types [N]
+        i32 (None with atom weights), lattice [B,3,3] f32 (the cells the evaluation saw, rows a, b, c), t_crystal [B] i32, offsets
+        [B+1] i32, `guidance` an xrd_guidance.DeviceGuidance (class or atom weights), gradient [N,3] f32 or None: receives g.
+        Between predict_scores (and contact_guidance_step) and a step export it is the guided loop's step bit for bit.  Returns eps."""
+        B, N = int(t_crystal.shape[0]), int(frac.shape[0])
+        guide = self._xrd_guidance_struct(guidance, B, N, step=True)
+        want = [("frac", frac, (N, 3), torch.float32), ("lattice", lattice, (B, 3, 3), torch.float32), ("t_crystal", t_crystal, (B,), torch.int32),
+                ("offsets", offsets, (B + 1,), torch.int32), ("eps", eps, (N, 3), torch.float32)]
+        if types is not None or guidance.atom_weights is None:
+            want.append(("types", types, (N,), torch.int32))
+        if gradient is not None:
+            want.append(("gradient", gradient, (N, 3), torch.float32))
+        for name, t, shape, dtype in want:
+            _require("xrd_guidance_step", name, t, shape, dtype, self.device)
+        _hip.check(_hip.lib().arreau_xrd_guidance_step(
+            self._handle, _hip.ptr(frac), _hip.ptr(types), _hip.ptr(lattice), _hip.ptr(t_crystal), _hip.ptr(offsets), B, N, _hip.ptr(eps),
+            ctypes.byref(guide), _hip.ptr(gradient), _hip.stream_ptr(self.device)), "arreau_xrd_guidance_step")
         return eps
 
     def sample_loop_species(self, frac, types, lengths, angles, offsets, t_start, n_steps, seed, const_types, lattice_out, species,

@@ -87,6 +87,11 @@ index in the file times `--samples_per_template` plus the copy.  Without `--keye
 Contact guidance: `--guide_contacts [--guide_min_distance D --guide_weight W]` steers every step away from contacts shorter than D
 (diffusion/contact_guidance.py): where `--require_valid` throws a crystal with a short contact away and samples again, this pushes
 the contact apart while the crystal is sampled.  With every other option (an `--invert` run guides the decode, not the encode).
+XRD guidance: `--guide_xrd TARGETS.npz [--guide_xrd_weight W]` steers the positions towards a target powder pattern
+(diffusion/xrd_guidance.py) on the grid of the `--xrd_*` flags: TARGETS.npz holds `pattern`, one row for every crystal or one per
+crystal of a batch (any other file is read as a crystals file, whose patterns are computed under the same flags).  Structure solution
+from a powder pattern: give the cell (`--template --fix lattice`, `--lattice_system`) and the composition.  Prints the mean,
+minimum and maximum distance to the target at the last network evaluation and the flags, per rank and in total.
 It prints, per rank and in total, the contacts below D, the penalty and the flags of the last network evaluation; `--screen`
 still judges the final state.
 """
@@ -501,7 +506,30 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--guide_min_distance", type=float, default=0.5, help="guide_contacts: contacts below this many A are pushed apart")
     ap.add_argument("--guide_weight", type=float, default=0.5,
                     help="guide_contacts: the descent step on the predicted clean structure (0.5 resolves an isolated contact)")
+    ap.add_argument("--guide_xrd", type=str, default=None, metavar="TARGETS.npz",
+                    help="XRD guidance: steer the positions towards the powder pattern(s) `pattern` of this file ([n_points] or one row per "
+                         "crystal of a batch, on the grid of the --xrd_* flags; another file type: a crystals file, whose patterns are "
+                         "computed); prints the distance to the target and the flags of the last network evaluation per rank and in total")
+    ap.add_argument("--guide_xrd_weight", type=float, default=2.0,
+                    help="guide_xrd: the descent step in A^2 on the predicted clean structure (2.0: a starting value, not a claim)")
     return ap
+
+
+def check_xrd_guidance_arguments(args, error):
+    """The XrdGuidance --guide_xrd asks for, or None; `error(message)` reports a bad value or a file that cannot be read."""
+    if not args.guide_xrd:
+        return None
+    from .diffusion.xrd_guidance import XrdGuidance
+    params = instrument_params("xrd", args, error)
+    try:
+        if args.guide_xrd.endswith(".npz"):
+            with np.load(args.guide_xrd) as z:
+                target = np.array(z["pattern"])
+        else:
+            target = load_targets(args.guide_xrd, error, "--guide_xrd")
+        return XrdGuidance(target, weight=args.guide_xrd_weight, params=params)
+    except (OSError, KeyError, ValueError) as e:
+        error(f"--guide_xrd: {e}")
 
 
 def check_guidance_arguments(args, error):
@@ -719,6 +747,8 @@ def main():
     slots = check_keyed_arguments(args, ap.error)
     guide = check_guidance_arguments(args, ap.error)
     guide_parts = []  # contact guidance: the last-evaluation statistics of every batch this rank sampled
+    xguide = check_xrd_guidance_arguments(args, ap.error)
+    xguide_parts = []  # XRD guidance: the same
     spec = load_symmetry(args, ap.error)
     if spec is not None and args.eta is not None:
         ap.error("--eta is not supported with --symops")
@@ -790,6 +820,9 @@ def main():
         if guide is not None:
             from .diffusion import contact_guidance as guidance_mod
             guide_parts.append(guidance_mod.stats_of(res.info["contact_guidance"], rank))
+        if xguide is not None:
+            from .diffusion import xrd_guidance as xrd_guidance_mod
+            xguide_parts.append(xrd_guidance_mod.stats_of(res.info["xrd_guidance"], rank))
         return res
 
     def fn(n, b, cond=None, keys=None):
@@ -798,7 +831,7 @@ def main():
                                        corrector_steps=args.corrector_steps, corrector_snr=args.corrector_snr,
                                        resample_passes=args.resample_passes, jump_length=args.jump_length,
                                        lattice_system=args.lattice_system, symmetry=spec, eta=args.eta, multistep=args.multistep,
-                                       contact_guidance=guide, **species_kw, **keywords))
+                                       contact_guidance=guide, xrd_guidance=xguide, **species_kw, **keywords))
     def start_fn(crystals):
         with _device_turn(lock_path) if lock_path else contextlib.nullcontext():
             keys = crystals.crystal_keys if args.keyed else None  # (the crystal's index in the file: set below)
@@ -809,7 +842,7 @@ def main():
                                        use_constant_atomic_symbols=True if args.invert else None, corrector_steps=args.corrector_steps,
                                        corrector_snr=args.corrector_snr, resample_passes=args.resample_passes,
                                        jump_length=args.jump_length, eta=args.eta, multistep=args.multistep, contact_guidance=guide,
-                                       **species_kw, **keywords))
+                                       xrd_guidance=xguide, **species_kw, **keywords))
     n_atoms = spec.n_atoms if spec is not None else args.num_atoms
     if start:
         if args.keyed:  # the key of a crystal: its index in the file
@@ -831,9 +864,12 @@ def main():
         res = generate_valid_crystals(fn, args.num_crystals, n_atoms, args.batch, rank, world, max_rounds=args.max_rounds, unique=unique)
     else:
         res = generate_n_crystals(fn, args.num_crystals, n_atoms, args.batch, rank, world, unique=unique)
-    if guide is not None:  # every rank's batches summed, gathered like the results; rank 0 prints
-        from .diffusion import contact_guidance as guidance_mod
-        mine = guidance_mod.total_stats(guide_parts, rank)
+    from .diffusion import contact_guidance, xrd_guidance
+    # every rank's batches summed, gathered like the results; rank 0 prints
+    for guidance_mod, parts in ((contact_guidance, guide_parts if guide is not None else None), (xrd_guidance, xguide_parts if xguide is not None else None)):
+        if parts is None:
+            continue
+        mine = guidance_mod.total_stats(parts, rank)
         ranks = [mine]
         if world > 1:
             ranks = [None] * world if rank == 0 else None

@@ -397,7 +397,8 @@ class PONITA_DIFFUSION(nn.Module):
                lattice_system=None, symmetry=None, screen=None, unique=None, find_symmetry=None, reduce_cell=None,
                symmetrize=None, match_to=None, eta: Optional[float] = None, initial_state=None,
                multistep: bool = False, elements=None, species_temperature: float = 1.0, crystal_keys=None,
-               conventional_cell=None, coordination=None, bond_order=None, contact_guidance=None, voronoi=None, xrd=None) -> SampleResult:
+               conventional_cell=None, coordination=None, bond_order=None, contact_guidance=None, voronoi=None, xrd=None,
+               xrd_guidance=None) -> SampleResult:
         """lightning_wrappers/diffusion.py:220-253.  `num_atoms_per_sample` may also be a sequence with one atom count
         per crystal of the batch (extension; the reference supports a single int).  Frames of a visualization_setting
         other than NONE go to `<DIFFUSION_DIR>/step_<timestep>.cif` like the reference's PNGs (`vis_name` overrides the
@@ -502,7 +503,7 @@ class PONITA_DIFFUSION(nn.Module):
 
     @torch.no_grad()
     def encode(self, crystals, t: Optional[int] = None, num_steps: Optional[int] = None, timesteps=None, fixed_cell: bool = False,
-               use_graph: Optional[bool] = None, contact_guidance=None):
+               use_graph: Optional[bool] = None, contact_guidance=None, xrd_guidance=None):
         """DDIM inversion (Song, Meng & Ermon 2021, section 4.3): crystal -> latent, the inverse map of `sample(eta=0)` on
         positions and lengths.  The crystals are taken as the state at the lowest level visited (1 by default) and climb to level
         t (default T-1), one network evaluation per visited level below the top (arreau_invert_loop; rules in
@@ -512,10 +513,11 @@ class PONITA_DIFFUSION(nn.Module):
         (use_constant_atomic_symbols=True).  fixed_cell: the lengths are held.  use_graph: replay one captured step (default: from
         200 steps).  No exact inverse of the final 1 -> 0 denoise step, no ties, symmetry or conditions, no likelihood; no claim
         on reconstruction quality is made.  `contact_guidance` other than None is rejected before any work: an inversion has no
-        clean-structure prediction to guide (the library's inversion loop rejects the option too).  Returns a
+        clean-structure prediction to guide (the library's inversion loop rejects the option too); `xrd_guidance` likewise.  Returns a
         diffusion.inversion.SamplerState at level t."""
-        from ..diffusion import contact_guidance as guidance_mod, inversion
+        from ..diffusion import contact_guidance as guidance_mod, inversion, xrd_guidance as xrd_guidance_mod
         guidance_mod.check_sampling(guidance_mod.resolve(contact_guidance), inversion=True)
+        xrd_guidance_mod.check_sampling(xrd_guidance_mod.resolve(xrd_guidance), inversion=True)
         T = self.diffusion_loss.T
         levels = inversion.encode_levels(T, t=t, num_steps=num_steps, timesteps=timesteps)  # (raises before any work)
         state = self._crystal_state(crystals, levels[-1], "encode")

@@ -1860,6 +1860,91 @@ int arreau_contact_guidance_step(const arreau_model* model, const float* d_frac,
                                  const int32_t* d_crystal_offsets, int32_t B, int32_t N, float* d_eps /* in place */,
                                  const arreau_contact_guidance* guidance, void* stream);
 
+/* ---- XRD guidance (steer the sampler towards a target powder pattern) -----------------------------------------------------
+ * Training-free guidance of the positions by an observable: every network evaluation of a step is followed by one launch that
+ * adds the gradient of the distance between the crystal's powder pattern and a target pattern to the predicted eps, so that the
+ * pattern of what the step predicts as the clean structure approaches the target.  The use is structure solution from a powder
+ * pattern: the cell (fixed, conditioned or of a lattice system) and the composition are given, where the atoms sit is left to
+ * the sampler.  The reference has no such option; the rules are the library's own (restated in float64 in
+ * arreau_amd/diffusion/xrd_guidance.py).  Parameters: `params`, an arreau_xrd_params with the xrd launch's meaning and
+ * validation; weight w in A^2 (finite, >= 0); d_target [B, n_points] float32, the target pattern of every crystal on that grid;
+ * the amplitudes as d_class_weights [S] float32, one per species class -- the amplitude of an atom is that of its current class
+ * (d_types as the evaluation saw them; a class outside 0..S-1 weighs 0), so a class of weight 0, such as the mask class, does not
+ * scatter and gets no push -- or, for the step export only, as d_atom_weights [N]; exactly one of the two.  Per crystal, on the
+ * wrapped positions and the cell that the step's network evaluation saw:
+ *   1. PATTERN: P is the pattern of arreau_crystal_xrd for these atoms and amplitudes, its rules 2-7, bit for bit (the two
+ *      kernels run one reflection walk, csrc/xrd_dev.h).
+ *   2. DISTANCE: dist = (1 - P.Q / (|P| |Q|)) / 2, Q the target row.  The three sums P.Q, P.P, Q.Q are float64 of the float32
+ *      values in a fixed order: thread t adds the points p = t (mod 256) in ascending order, then the butterfly xor 32, 16, ..., 1
+ *      within a wave, then the four waves in wave order.
+ *   3. DERIVATIVE WITH RESPECT TO THE PATTERN: u(p) = -(1/2) (Q(p) / (|P||Q|) - (P.Q) P(p) / (|P|^3 |Q|)), float64, rounded to
+ *      float32 (it replaces P in LDS).
+ *   4. PER KEPT REFLECTION (the forward walk's half space, cuts and box order; Re F, Im F, 2 theta and the window are formed
+ *      again by the same code, the same bits): c = sum over the window's grid points, in ascending p, of u(p) G(p), with G(p) =
+ *      expf(-0.5 z^2) and the 6 sigma test of rule 7 of the xrd section, the products and the sum float64; kappa = 2 DW LP /
+ *      V^2 / (sigma sqrt(2 pi)), the factor that multiplies |F|^2 in rule 6 there (Friedel's 2 inside), float64.
+ *   5. CARTESIAN GRADIENT on atom a: D_a = -4 pi w_a sum over the kept reflections of kappa c (Re F sin phi_a - Im F cos phi_a)
+ *      G_hkl, with (sin, cos) = sincospi(2 r_a) of the reflection's reduced float32 phase r_a at atom a (rule 5 of the xrd
+ *      section) and G_hkl = (h b_1 + k b_2) + l b_3 the float64 reciprocal vector of the walk.  Everything after the sincospi is
+ *      float64.  D_a = d dist / d r_a: the peak positions depend on the cell alone.
+ *   6. FRACTIONAL GRADIENT AND GUIDED EPS: g_a = D_a L^-1, g_a,k = (D_a . b_k) (contact guidance's rule 4; the b_k of rule 2 of
+ *      the xrd section), rounded to float32; eps'_a = eps_a + (w / sigma_t^2) g_a in float32, coefficient and timestep clamp as
+ *      in contact guidance's rule 5, and every consumer of the step's eps reads eps'.  The predictor's clean-position estimate
+ *      moves -w g: one descent step of size w on the distance.
+ *   7. ORDER WITHIN A STEP: evaluate, contact guidance if given, XRD guidance, then the corrector or the predictor; after a
+ *      corrector's re-evaluations too.
+ *   8. FLAGS (int32 per crystal, one at most, in this order): NONFINITE (an amplitude counts), CELL, EMPTY, RANGE with the xrd
+ *      launch's meaning and values; LARGE more than 256 atoms (the per-atom accumulators are LDS-resident: a stated limit);
+ *      NO_TARGET the target row has an entry that is not finite or is negative, or is all zero; DARK |P|^2 is zero or not
+ *      finite: nothing scatters in range.  A flagged crystal keeps its eps bit for bit; its distance is NaN, its reflections 0,
+ *      its g (d_gradient) 0.
+ *   9. weight == 0 or a NULL struct is the loop without the option: no launch is added, bit identical.  An inversion loop
+ *      rejects the option; bad parameters, a NULL target, none or both of the amplitude arrays, and atom weights in a loop are
+ *      ARREAU_EINVAL before any work.  The parameters and the pointers are part of what a cached hipGraph was captured for.
+ * Summation order (fixed, so eager runs, graph replay and a crystal's place in the batch give the same bits): one workgroup of four
+ * waves per crystal.  The second walk runs in rounds of 256 box entries; a round's kept reflections are compacted in thread order
+ * into a list, as the forward walk compacts them.  Wave v owns atoms v, v + 4, ...; for atom a lane l adds the list entries l,
+ * l + 64, ... in ascending order, the 64 partial sums are folded by the butterfly xor 32, 16, ..., 1, and the round's sum is added
+ * to the atom's accumulator, rounds in ascending order.  No float atomics.
+ * Diagnostics (device, each may be NULL, of the last evaluation): d_distance [B] float32 of rule 2's value, d_reflections [B]
+ * (2 * the kept, the xrd launch's n_reflections), d_flags [B].
+ * What this is not: positions only -- a wrong cell cannot be repaired (fix the cell); no guidance of species; no intensity
+ * scale or background fit (the cosine distance is scale free); no weight schedule other than 1 / sigma_t^2; no claim on sample
+ * quality. */
+#define ARREAU_XGUIDE_NO_TARGET 16
+#define ARREAU_XGUIDE_DARK 32
+#define ARREAU_XGUIDE_LARGE 64
+typedef struct arreau_xrd_guidance {
+    arreau_xrd_params params;     /* the grid, wavelength, fwhm, b_iso, max_index */
+    float weight;                 /* w in A^2: finite, >= 0; 0 is the loop without the option */
+    const float* d_target;        /* [B, n_points] (device) */
+    const float* d_class_weights; /* [S] (device), or NULL with d_atom_weights */
+    const float* d_atom_weights;  /* [N] (device), arreau_xrd_guidance_step only, or NULL */
+    float* d_distance;            /* [B] (device), or NULL */
+    int32_t* d_reflections;       /* [B] (device), or NULL */
+    int32_t* d_flags;             /* [B] ARREAU_XRD_* | ARREAU_XGUIDE_* (device), or NULL */
+} arreau_xrd_guidance;
+
+/* arreau_sample_loop_guided plus `xrd_guidance`, a HOST pointer to the struct above; NULL (or weight == 0) is that loop bit for
+ * bit.  Every combination that loop accepts, both loop forms, the shape-general path, eager and graph replay. */
+int arreau_sample_loop_xrd_guided(arreau_model* model, float* d_frac, int32_t* d_types, float* d_lengths, const float* d_angles,
+                                  const int32_t* d_crystal_offsets, int32_t B, int32_t N, int32_t t_start, int32_t n_steps,
+                                  uint64_t seed, const int32_t* d_const_types, const float* d_fixed_lengths, float* d_lattice,
+                                  void* d_workspace, size_t workspace_bytes, int32_t use_graph,
+                                  const arreau_sample_condition* cond, const arreau_sample_schedule* schedule,
+                                  const arreau_corrector* corrector, const arreau_resampling* resampling, const int32_t* d_length_tie,
+                                  const arreau_symmetry* symmetry, const float* eta, const arreau_multistep* multistep,
+                                  const arreau_species_control* species, const uint64_t* d_crystal_seeds,
+                                  const arreau_contact_guidance* guidance, const arreau_xrd_guidance* xrd_guidance, void* stream);
+/* Rules 1-6 and 8 on the caller's arrays: d_eps [N,3] in place, at the per-crystal timesteps d_t [B], with the cells d_lattice
+ * [B,3,3] (rows a, b, c) and the classes d_types [N] (may be NULL with d_atom_weights).  d_gradient [N,3] (may be NULL) receives
+ * g itself.  `guidance` is required; weight == 0 launches too (eps + 0 g, g and the diagnostics).  For tests and host-driven
+ * loops: between arreau_predict_scores (and arreau_contact_guidance_step) and a step export it is the guided loop's step bit
+ * for bit. */
+int arreau_xrd_guidance_step(const arreau_model* model, const float* d_frac, const int32_t* d_types, const float* d_lattice,
+                             const int32_t* d_t, const int32_t* d_crystal_offsets, int32_t B, int32_t N, float* d_eps /* in place */,
+                             const arreau_xrd_guidance* guidance, float* d_gradient, void* stream);
+
 /* ---- score-matching training loss, forward part (BASELINE config 5) ------------------------------------------ */
 
 /* The forward-noising half of DiffusionLoss.__call__ (diffusion/diffusion_loss.py:222-234), random draws supplied by
