@@ -42,6 +42,7 @@ EXPORTS = [
     "arreau_sample_loop_keyed", "arreau_noise_state_keyed", "arreau_condition_initial_state_keyed", "arreau_philox_fill_crystals",
     "arreau_sample_loop_guided", "arreau_contact_guidance_step",
     "arreau_sample_loop_xrd_guided", "arreau_xrd_guidance_step",
+    "arreau_crystal_ewald",
 ]
 
 STATUS_NONFINITE, STATUS_BAD_TIMESTEP, STATUS_BAD_TYPE, STATUS_BAD_TIE, STATUS_BAD_SYMMETRY = 1, 2, 4, 8, 16
@@ -163,6 +164,17 @@ class XrdParamsC(Structure):
 class XrdResultC(Structure):
     """arreau_xrd_result: the pattern [B, n_points] and the four per-crystal device arrays the diffraction launch writes."""
     _fields_ = [(name, c_void_p) for name in ("pattern", "n_reflections", "volume", "weight_sum", "flags")]
+
+
+class EwaldParamsC(Structure):
+    """arreau_ewald_params: the accuracy, the splitting parameter (0: per crystal) and the two caps of the Ewald sum."""
+    _fields_ = [("accuracy", c_double), ("alpha", c_double), ("max_shells", c_int32), ("max_index", c_int32)]
+
+
+class EwaldResultC(Structure):
+    """arreau_ewald_result: the eleven per-crystal device arrays the Ewald launch writes, the potential [N] and its scratch [N]."""
+    _fields_ = [(name, c_void_p) for name in ("energy", "real", "reciprocal", "self", "background", "net_charge", "alpha", "volume",
+                                                "n_pairs", "n_reciprocal", "flags", "potential", "work")]
 
 
 class XrdGuidanceC(Structure):
@@ -331,6 +343,7 @@ def _prototypes():
         "arreau_crystal_bond_order": [vp] * 3 + [i32, i32, vp, vp, POINTER(BondOrderParamsC), POINTER(BondOrderResultC), vp],
         "arreau_crystal_voronoi": [vp] * 3 + [i32, i32, POINTER(VoronoiParamsC), POINTER(VoronoiResultC), vp],
         "arreau_crystal_xrd": [vp] * 4 + [i32, i32, POINTER(XrdParamsC), POINTER(XrdResultC), vp],
+        "arreau_crystal_ewald": [vp] * 4 + [i32, i32, POINTER(EwaldParamsC), POINTER(EwaldResultC), vp],
         "arreau_crystal_fingerprint": [vp] * 4 + [i32, i32, POINTER(FingerprintParamsC), POINTER(FingerprintResultC), vp],
         "arreau_fingerprint_match": [POINTER(FingerprintResultC), i32, POINTER(FingerprintResultC), i32, f32, POINTER(MatchResultC), vp],
         "arreau_crystal_symmetry": [vp] * 4 + [i32, i32, POINTER(SymmetryParamsC), POINTER(SymmetryResultC), vp],

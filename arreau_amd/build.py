@@ -12,7 +12,7 @@ import sys
 import time
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-SOURCES = ["model.hip", "graph.hip", "screen.hip", "coordination.hip", "bond_order.hip", "voronoi.hip", "xrd.hip", "fingerprint.hip", "symfind.hip", "reduce.hip", "symmetrize.hip", "conventional.hip", "match.hip", "edge.hip", "edge_bf16.hip", "edge_f16.hip", "node.hip", "node_bf16.hip", "node_f16m.hip", "conv_proj.hip", "update.hip", "corrector.hip", "contact_guide.hip", "xrd_guide.hip", "resample.hip", "train.hip", "train_net.hip", "optim.hip", "api.hip"]
+SOURCES = ["model.hip", "graph.hip", "screen.hip", "coordination.hip", "bond_order.hip", "voronoi.hip", "xrd.hip", "ewald.hip", "fingerprint.hip", "symfind.hip", "reduce.hip", "symmetrize.hip", "conventional.hip", "match.hip", "edge.hip", "edge_bf16.hip", "edge_f16.hip", "node.hip", "node_bf16.hip", "node_f16m.hip", "conv_proj.hip", "update.hip", "corrector.hip", "contact_guide.hip", "xrd_guide.hip", "resample.hip", "train.hip", "train_net.hip", "optim.hip", "api.hip"]
 HEADERS = ["internal.h", "score_plan.h", "edge_rows.h", "bf16x6.h", "f16x3.h", os.path.join("..", "..", "include", "arreau_hip.h"), "sgemm.h", "train_kernels.h", "philox.h", "embed_dev.h", "prep_dev.h", "graph_dev.h", "crystal_dev.h", "xrd_dev.h", "symfind_table.h", "update_dev.h", "readout_dev.h"]
 LIB = os.path.join(CSRC, "libarreau_hip.so")
 # Debug twin: the same sources with -DARREAU_DEBUG_WAIT_ALL (every hand-counted `s_waitcnt vmcnt(N)` becomes vmcnt(0)).
@@ -31,7 +31,7 @@ NO_SCRATCH = {"edge_f16.hip": None, "node.hip": ["conv_kernel_streamed"], "node_
 # states around every asm instruction (store-data, VALU-written SGPR -> VMEM, M0 -> LDS-DMA, ...), asm loads' destination
 # registers untouched until their wait, no compiler use of M0, no unmodelled instruction kind inside asm.  hipcc pads and
 # counts none of that for inline asm; a violation fails the build.
-ASM_LINT = ("edge_f16.hip", "node.hip", "node_f16m.hip", "graph.hip", "screen.hip", "api.hip", "conv_proj.hip", "train_net.hip", "xrd.hip", "xrd_guide.hip")
+ASM_LINT = ("edge_f16.hip", "node.hip", "node_f16m.hip", "graph.hip", "screen.hip", "api.hip", "conv_proj.hip", "train_net.hip", "xrd.hip", "xrd_guide.hip", "ewald.hip")
 # -Wno-inline-asm: the lean LDS-DMA asm lists "m0" as clobbered (it overwrites M0 and does not restore it); clang warns
 # that reserved registers in a clobber list are not preserved for us -- which is what is declared, not asked for.  The
 # ISA check below verifies that the compiler itself never uses M0 in those kernels.

@@ -1,6 +1,6 @@
 // Device helpers shared by the per-crystal kernels (one workgroup of CRYSTAL_WAVES waves per crystal): screen.hip, fingerprint.hip,
-// coordination.hip, bond_order.hip, voronoi.hip, contact_guide.hip, symfind.hip, reduce.hip, symmetrize.hip, conventional.hip and
-// match.hip.  What is here: the image walk (the flattened range e = j M + m dealt to threads by stride or in chunks, with 32-bit
+// coordination.hip, bond_order.hip, voronoi.hip, contact_guide.hip, symfind.hip, reduce.hip, symmetrize.hip, conventional.hip,
+// match.hip, xrd.hip and ewald.hip.  What is here: the image walk (the flattened range e = j M + m dealt to threads by stride or in chunks, with 32-bit
 // index arithmetic where the range allows it); the launch shape; the prologue; the wrap of a fractional coordinate and the
 // Cartesian position; the positions staged in LDS; the cell and its image range; one periodic contact; the wave's butterfly sum and
 // its self-synchronisation; the compaction of a workgroup's hits in thread order; the rarest species; the squared length of a

@@ -3,6 +3,8 @@
 // reflection (rules 4-6), one Gaussian term (rule 7's expression and its 6 sigma test) and the whole forward walk into a pattern
 // in LDS (rule 7).  Both kernels run this code and no copy of it, so the guidance kernel's pattern is the xrd launch's bit for
 // bit.  The flat range dealt to the threads (crystal_walk_chunks) is the box index e = (h W_2 + (k + H_2)) W_3 + (l + H_3).
+// ewald.hip (arreau_crystal_ewald) takes the parts that know nothing of a pattern: the cell (xrd_cell_rows), the box under its own
+// cut (xrd_cell_box), the box walk, a box entry's lattice point (xrd_point_at), the atoms and the reduced phase.
 #pragma once
 #include "internal.h"
 #include "crystal_dev.h"
@@ -28,11 +30,10 @@ struct xrd_cell {
     float volume;
 };
 
-// 0, or the one of ARREAU_XRD_CELL / EMPTY / RANGE that applies (in that order); every thread computes the same values
-__device__ __forceinline__ int xrd_cell_measure(const float* Lm, int n, const xrd_plan& P, xrd_cell& c) {
-    // ---- rule 2: the cell in float64 from the float32 entries, the reciprocal rows b_k = (a_i x a_j) / det
+// rule 2: the cell A[9] in float64 from the float32 entries, the unnormalised reciprocal rows a_i x a_j in c.R, det and the float32
+// volume; false when the cell has no volume (the callers' CELL).  xrd_cell_box finishes c.
+__device__ __forceinline__ bool xrd_cell_rows(const float* Lm, xrd_cell& c, double* A, double& det) {
     c.volume = crystal_volume(Lm);
-    double A[9];
 #pragma unroll
     for (int q = 0; q < 9; ++q) A[q] = (double)Lm[q];
 #pragma unroll
@@ -41,22 +42,36 @@ __device__ __forceinline__ int xrd_cell_measure(const float* Lm, int n, const xr
         const double* v = A + 3 * ((k + 2) % 3);
         c.R[3 * k] = u[1] * v[2] - u[2] * v[1]; c.R[3 * k + 1] = u[2] * v[0] - u[0] * v[2]; c.R[3 * k + 2] = u[0] * v[1] - u[1] * v[0];
     }
-    const double det = (A[0] * c.R[0] + A[1] * c.R[1]) + A[2] * c.R[2], V = fabs(det);
-    if (!(c.volume > 0.f) || !isfinite(c.volume) || !(V > 0.) || !isfinite(V)) return ARREAU_XRD_CELL;
-    if (n == 0) return ARREAU_XRD_EMPTY;
-    // ---- rule 3: the box, H_k = floor(d*_max |a_k|) from the direct cell's lengths
+    det = (A[0] * c.R[0] + A[1] * c.R[1]) + A[2] * c.R[2];
+    const double V = fabs(det);
+    return c.volume > 0.f && isfinite(c.volume) && V > 0. && isfinite(V);
+}
+
+// rule 3: the box H_k = floor(g_max |a_k|) from the direct cell's lengths, then b_k = (a_i x a_j) / det and 1 / V^2; false when
+// an H_k exceeds max_index (the callers' RANGE; c.R is then left unnormalised)
+__device__ __forceinline__ bool xrd_cell_box(const double* A, double det, double g_max, int max_index, xrd_cell& c) {
     double Hd[3];
     bool wide = false;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        Hd[k] = floor(P.dhi * sqrt((A[3 * k] * A[3 * k] + A[3 * k + 1] * A[3 * k + 1]) + A[3 * k + 2] * A[3 * k + 2]));
-        wide |= !(Hd[k] <= (double)P.max_index);
+        Hd[k] = floor(g_max * sqrt((A[3 * k] * A[3 * k] + A[3 * k + 1] * A[3 * k + 1]) + A[3 * k + 2] * A[3 * k + 2]));
+        wide |= !(Hd[k] <= (double)max_index);
     }
-    if (wide) return ARREAU_XRD_RANGE;
+    if (wide) return false;
     c.H1 = (int)Hd[0]; c.H2 = (int)Hd[1]; c.H3 = (int)Hd[2];  // <= max_index <= 127
 #pragma unroll
     for (int q = 0; q < 9; ++q) c.R[q] /= det;
+    const double V = fabs(det);
     c.inv_v2 = 1.0 / (V * V);
+    return true;
+}
+
+// 0, or the one of ARREAU_XRD_CELL / EMPTY / RANGE that applies (in that order); every thread computes the same values
+__device__ __forceinline__ int xrd_cell_measure(const float* Lm, int n, const xrd_plan& P, xrd_cell& c) {
+    double A[9], det;
+    if (!xrd_cell_rows(Lm, c, A, det)) return ARREAU_XRD_CELL;
+    if (n == 0) return ARREAU_XRD_EMPTY;
+    if (!xrd_cell_box(A, det, P.dhi, P.max_index, c)) return ARREAU_XRD_RANGE;
     return 0;
 }
 
@@ -91,25 +106,42 @@ struct xrd_reflection {
     float re, im, amp;
 };
 
-__device__ __forceinline__ xrd_reflection xrd_reflection_at(const xrd_plan& P, const xrd_cell& c, int n, const xrd_atoms& atoms, bool valid,
-                                                            unsigned uh, unsigned m) {
+// the lattice point of box entry (uh, m) (rule 4): its indices, whether it lies in the walked half space and then G and d*^2, float64
+struct xrd_point {
+    bool half;
+    int h, k, l;
+    double gx, gy, gz, d2;
+};
+
+__device__ __forceinline__ xrd_point xrd_point_at(const xrd_cell& c, bool valid, unsigned uh, unsigned m) {
     const unsigned W3 = 2u * c.H3 + 1u;
     const unsigned uk = m / W3;
     const double* R = c.R;
-    xrd_reflection r{};
+    xrd_point p{};
     const int h = (int)uh, k = (int)uk - c.H2, l = (int)(m - uk * W3) - c.H3;
+    p.h = h; p.k = k; p.l = l;
+    p.half = valid && (h > 0 || k > 0 || (k == 0 && l > 0));  // (h >= 0 in the box)
+    if (p.half) {
+        p.gx = ((double)h * R[0] + (double)k * R[3]) + (double)l * R[6];
+        p.gy = ((double)h * R[1] + (double)k * R[4]) + (double)l * R[7];
+        p.gz = ((double)h * R[2] + (double)k * R[5]) + (double)l * R[8];
+        p.d2 = (p.gx * p.gx + p.gy * p.gy) + p.gz * p.gz;
+    }
+    return p;
+}
+
+__device__ __forceinline__ xrd_reflection xrd_reflection_at(const xrd_plan& P, const xrd_cell& c, int n, const xrd_atoms& atoms, bool valid,
+                                                            unsigned uh, unsigned m) {
+    xrd_reflection r{};
+    // ---- rule 4: the half space, d*^2 and the cut, float64
+    const xrd_point pt = xrd_point_at(c, valid, uh, m);
+    const int h = pt.h, k = pt.k, l = pt.l;
     r.h = h; r.k = k; r.l = l;
     r.lo = 0; r.hi = -1;
-    // ---- rule 4: the half space, d*^2 and the cut, float64
-    bool keep = valid && (h > 0 || k > 0 || (k == 0 && l > 0));  // (h >= 0 in the box)
-    double d2 = 0.;
-    if (keep) {
-        const double gx = ((double)h * R[0] + (double)k * R[3]) + (double)l * R[6];
-        const double gy = ((double)h * R[1] + (double)k * R[4]) + (double)l * R[7];
-        const double gz = ((double)h * R[2] + (double)k * R[5]) + (double)l * R[8];
-        d2 = (gx * gx + gy * gy) + gz * gz;
-        keep = d2 >= P.dlo2 && d2 <= P.dhi2;
-        r.gx = gx; r.gy = gy; r.gz = gz;
+    const double d2 = pt.d2;
+    const bool keep = pt.half && d2 >= P.dlo2 && d2 <= P.dhi2;
+    if (pt.half) {
+        r.gx = pt.gx; r.gy = pt.gy; r.gz = pt.gz;
     }
     r.keep = keep;
     if (keep) {

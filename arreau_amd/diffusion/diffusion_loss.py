@@ -95,6 +95,10 @@ class SampleResult:
     # [.., n_points], n_reflections, volume, weight_sum, flags, max_intensity, two_theta_peak and grid [.., 5] (the grid-defining
     # parameters: the 2 theta values are xrd.grid(row)), one row per crystal; None when it was not asked for
     xrd: Optional[dict] = None
+    # extension: the Ewald electrostatics of the final state (sample(ewald=...); diffusion/ewald.py) -- numpy arrays energy, real,
+    # reciprocal, self, background (eV), net_charge, alpha, volume, n_pairs, n_reciprocal, flags and energy_per_atom, one row per
+    # crystal, and potential (V), charge and species, one row per atom; None when it was not asked for
+    ewald: Optional[dict] = None
 
 
 class _PinnedRing:
@@ -549,7 +553,7 @@ class DiffusionLoss(nn.Module):
                symmetrize=None, match_to=None, eta: Optional[float] = None, initial_state=None,
                multistep: bool = False, elements=None, species_temperature: float = 1.0, crystal_keys=None,
                conventional_cell=None, coordination=None, bond_order=None, contact_guidance=None, voronoi=None, xrd=None,
-               xrd_guidance=None) -> SampleResult:
+               xrd_guidance=None, ewald=None) -> SampleResult:
         """diffusion_loss.py:276-377.  The initial state is drawn on the host exactly like the reference (numpy
         uniforms for the angles, then randn lengths, randn fractional coordinates from torch's global CPU generator):
         draw_initial_state, which a caller may also use on its own.
@@ -741,6 +745,14 @@ class DiffusionLoss(nn.Module):
         point scatterers, Lorentz-polarisation factor, Gaussians of one width.  SampleResult.xrd then holds the arrays
         (xrd.STORED_KEYS).  It reads the state as sampled.  No form-factor tables, no anomalous dispersion, no peak list, no K
         alpha 2.  None: no launch is added, xrd is None and the results are what they were, bit for bit.
+        `ewald` (extension, every noise mode and option): an ewald.EwaldParams(charges={"Na": 1, "Cl": -1} or "Na=1,Cl=-1",
+        accuracy, alpha, max_shells, max_index) -- one more launch on the final device state (arreau_crystal_ewald; rules in
+        include/arreau_hip.h) writes every crystal's Ewald energy of those point charges, its four parts and every atom's site
+        potential.  SampleResult.ewald then holds the arrays (ewald.STORED_KEYS).  A crystal with a species that has no charge
+        (the mask state included) is flagged UNASSIGNED, one that is not neutral CHARGED (a neutralising background is in its
+        number).  It reads the state as sampled.  No forces, no guidance, no oxidation-state guessing, no short-range repulsion.
+        There are no default charges: True is rejected.  None: no launch is added, ewald is None and the results are what they
+        were, bit for bit.
         `contact_guidance` (extension, every noise mode and option): a contact_guidance.ContactGuidance (min_distance, weight,
         max_shells), or True for its defaults -- training-free guidance away from short contacts (rules in include/arreau_hip.h,
         "contact guidance"; arreau_sample_loop_guided).  Every network evaluation of every step, a corrector's included, is followed
@@ -828,7 +840,7 @@ class DiffusionLoss(nn.Module):
         final = instruments.DeviceState(eng, buf.frac_d, buf.lattice_d, buf.off_d, buf.types_d, z_table, plan.num_atoms.numpy(),
                                         atomic_numbers, mask_type=-1 if constant_atoms is not None else plan.S - 1)
         fields = {e.field: e.run(final, plan.instruments[e.keyword]) if plan.instruments[e.keyword] is not None else None
-                  for e in instruments.FULL}
+                  for e in instruments.COMPLETE}
         return SampleResult(num_atoms=plan.num_atoms.numpy(), frac_x=buf.frac_d.cpu().numpy().astype(np.float64),
                             atomic_numbers=atomic_numbers, lattice=buf.lattice_d.cpu().numpy().astype(np.float64), info=info,
                             crystal_keys=np.array(plan.crystal_keys, dtype=np.int64) if plan.crystal_keys is not None else None,

@@ -9,10 +9,10 @@ each crystal), num_atoms [B] int64.  HDF5 when h5py is importable (it is not in 
 with the same five keys otherwise.
 
 A result that carries an instrument's arrays (diffusion/instruments.py: SampleResult.metrics, .uniqueness, .symmetry, .reduced,
-.symmetrized, .match, .conventional, .coordination, .bond_order, .voronoi, .xrd) gets one more array per stored key, <prefix><key>: screen_*, unique_*, sym_*, reduced_*,
-symmetrized_*, match_*, conventional_*, coord_*, order_*, voronoi_*, xrd_*, in that order, each instrument's keys in the order of its module's tuple (screening.STORED_KEYS, uniqueness.UNIQUE_KEYS,
+.symmetrized, .match, .conventional, .coordination, .bond_order, .voronoi, .xrd, .ewald) gets one more array per stored key, <prefix><key>: screen_*, unique_*, sym_*, reduced_*,
+symmetrized_*, match_*, conventional_*, coord_*, order_*, voronoi_*, xrd_*, ewald_*, in that order, each instrument's keys in the order of its module's tuple (screening.STORED_KEYS, uniqueness.UNIQUE_KEYS,
 symmetry_search.SYM_KEYS, cell_reduction.REDUCED_KEYS, symmetrize.SYMMETRIZED_KEYS, structure_match.MATCH_KEYS,
-conventional_cell.CONVENTIONAL_KEYS, coordination.STORED_KEYS, bond_order.STORED_KEYS, voronoi.STORED_KEYS, xrd.STORED_KEYS; the modules say what each holds).  One row per crystal, except the per-atom keys: of the
+conventional_cell.CONVENTIONAL_KEYS, coordination.STORED_KEYS, bond_order.STORED_KEYS, voronoi.STORED_KEYS, xrd.STORED_KEYS, ewald.STORED_KEYS; the modules say what each holds).  One row per crystal, except the per-atom keys: of the
 result's atoms [sum n] for symmetrized_*, match_*, coord_*, order_* and voronoi_*, of the reduced crystals' [sum reduced_num_atoms] for reduced_*, of the
 conventional crystals' [sum conventional_num_atoms] for conventional_*.  Readers of the five keys above are not affected; a result without an
 instrument's arrays is written without them, and a reader gets back None.  A reader gets the symmetry search's arrays back with
@@ -25,7 +25,7 @@ import os
 import numpy as np
 
 from ..diffusion_loss import SampleResult
-from ..instruments import FULL as INSTRUMENTS, file_fields
+from ..instruments import COMPLETE as INSTRUMENTS, file_fields
 
 KEYS = ("frac_x", "atomic_numbers", "lattice", "idx_start", "num_atoms")
 _DTYPES = dict(frac_x=np.float64, atomic_numbers=np.float64, lattice=np.float64, idx_start=np.int64,

@@ -6,7 +6,9 @@ is built on a LOCAL one's neighbour lists (the bond angles and order parameters)
 KEYWORDS maps a sample() keyword to its entry.  CELLS holds what builds each atom's Voronoi cell (its own launch, after the
 bond order); WHOLE is TABLE and CELLS -- what the file layer, the batch driver, the screen and sample() loop over -- and
 WHOLE_KEYWORDS its keyword map.  PATTERNS holds what walks reciprocal space (the powder diffraction pattern: its own launch,
-after the cells); FULL is WHOLE and PATTERNS -- what those four loop over now -- and FULL_KEYWORDS its keyword map.  An entry holds what the
+after the cells); FULL is WHOLE and PATTERNS, and FULL_KEYWORDS its keyword map.  ENERGIES holds what needs the user's charges
+besides the geometry (the Ewald sum: its own launch, after the pattern); COMPLETE is FULL and ENERGIES -- what those four loop
+over now -- and COMPLETE_KEYWORDS its keyword map.  An entry holds what the
 instruments differ in for the host-side plumbing: the file layer (inference/process_generated_crystals.py), the batch driver
 (generate.py) and `python -m arreau_amd.screen` loop over it, and so does DiffusionLoss.sample, which calls every asked-for
 entry's `run` on the final device state (DeviceState) in table order: an entry that shares a launch comes after the entry that
@@ -17,8 +19,8 @@ from typing import Callable, Optional
 
 import numpy as np
 
-from . import (bond_order, cell_reduction, conventional_cell, coordination, screening, structure_match, symmetrize, symmetry_search,
-               uniqueness, voronoi, xrd)
+from . import (bond_order, cell_reduction, conventional_cell, coordination, ewald, screening, structure_match, symmetrize,
+               symmetry_search, uniqueness, voronoi, xrd)
 from .tools.atomic_number_table import atomic_number_indexes_to_atomic_numbers
 
 
@@ -96,6 +98,13 @@ def _run_xrd(s, params):  # (the atomic numbers are the amplitudes: one small up
     import torch
     weights = torch.as_tensor(xrd.host_weights(s.atomic_numbers, params), device=s.frac.device)
     return xrd.sample_arrays(xrd.result_to_numpy(s.eng.xrd(s.frac, s.lattice, s.offsets, weights, xrd.for_weights(params))), params)
+
+
+def _run_ewald(s, params):  # (the charges of the atomic numbers: one small upload)
+    import torch
+    charges = ewald.host_charges(s.atomic_numbers, params)
+    found = ewald.result_to_numpy(s.eng.ewald(s.frac, s.lattice, s.offsets, torch.as_tensor(charges, device=s.frac.device), params))
+    return ewald.sample_arrays(found, charges, s.atomic_numbers, s.num_atoms)
 
 
 @dataclass(frozen=True)
@@ -177,8 +186,16 @@ PATTERNS = (
                 ("two_theta_max", "xrd_two_theta_max"), ("n_points", "xrd_points"), ("b_iso", "xrd_b_iso"),
                 ("scattering", "xrd_scattering")), "xrd", shape=(), shapes=(("pattern", 2), ("grid", (len(xrd.GRID_KEYS),))), run=_run_xrd),
 )
-FULL = WHOLE + PATTERNS  # every instrument: what the file layer, the batch driver, the screen and sample() loop over
+FULL = WHOLE + PATTERNS  # every instrument that reads geometry alone
 FULL_KEYWORDS = {e.keyword: e for e in FULL}
+# what needs more than the geometry -- the user's charges: a launch of its own, after the pattern; its arrays after xrd_*
+ENERGIES = (
+    Instrument("ewald", "ewald", "ewald_", "ewald_stats", ewald, ewald.STORED_KEYS, "EwaldParams",
+               (("charges", "ewald_charges"), ("accuracy", "ewald_accuracy"), ("alpha", "ewald_alpha")), "ewald",
+               atom_keys=ewald.ATOM_KEYS, shape=(), run=_run_ewald),
+)
+COMPLETE = FULL + ENERGIES  # every instrument: what the file layer, the batch driver, the screen and sample() loop over
+COMPLETE_KEYWORDS = {e.keyword: e for e in COMPLETE}
 
 
 def concat(entry, parts):

@@ -80,7 +80,7 @@ def atom_counts(num_atoms_per_sample, B):
 
 def _resolve_instruments(asked):
     """{keyword: resolved parameters or None} of the instrument keywords, then the three rules of the shared launches."""
-    out = {e.keyword: e.module.resolve(asked[e.keyword]) for e in instruments.FULL}
+    out = {e.keyword: e.module.resolve(asked[e.keyword]) for e in instruments.COMPLETE}
     instruments.bond_order.check_shared(out["bond_order"], out["coordination"])
     instruments.symmetrize.check_shared_search(out["symmetrize"], out["find_symmetry"])
     instruments.conventional_cell.check_shared(out["conventional_cell"], out["reduce_cell"], out["find_symmetry"], out["symmetrize"])
@@ -169,7 +169,7 @@ def check_options(*, vis_name="", visualization_setting=VisualizationSetting.NON
     guidance = guidance_mod.resolve(contact_guidance)
     xrd_guidance = xrd_guidance_mod.resolve(xrd_guidance)
     xrd_guidance_mod.check_sampling(xrd_guidance)
-    resolved = _resolve_instruments({k: others.get(k) for k in instruments.FULL_KEYWORDS})
+    resolved = _resolve_instruments({k: others.get(k) for k in instruments.COMPLETE_KEYWORDS})
     if crystal_keys is not None:  # (the count: resolve)
         crystal_keys = keyed_mod.validate_keys(crystal_keys, None, seed, noise if noise in NOISE_MODES else "philox")
     if visualization_setting != VisualizationSetting.NONE and not vis_name:

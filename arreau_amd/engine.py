@@ -13,6 +13,7 @@ from . import _hip
 from .diffusion import (bond_order as bond_order_mod, cell_reduction, conventional_cell as conventional_mod,
                         coordination as coordination_mod, screening, symmetrize as symmetrize_mod, symmetry_search,
                         voronoi as voronoi_mod, xrd as xrd_mod)
+from .diffusion import ewald as ewald_mod
 from .diffusion import xrd_guidance as xrd_guidance_mod
 from .diffusion.contact_guidance import INFO_KEYS, ContactGuidance
 from .diffusion.corrector import check_corrector
@@ -90,6 +91,11 @@ def coordination(frac, lattice, offsets, params=None):
 def voronoi(frac, lattice, offsets, params=None):
     """The Voronoi cells without an engine (arreau_crystal_voronoi needs no model): diffusion.voronoi.voronoi."""
     return voronoi_mod.voronoi(frac, lattice, offsets, params)
+
+
+def ewald(frac, lattice, offsets, charges_or_atomic_numbers, params=None):
+    """The Ewald sums without an engine (arreau_crystal_ewald needs no model): diffusion.ewald.ewald."""
+    return ewald_mod.ewald(frac, lattice, offsets, charges_or_atomic_numbers, params)
 
 
 def xrd(frac, lattice, offsets, weights_or_atomic_numbers, params=None):
@@ -1144,6 +1150,14 @@ class HipEngine:
         synchronise."""
         self._on_device("xrd", frac)
         return xrd_mod.xrd(frac, lattice, offsets, weights_or_atomic_numbers, params)
+
+    def ewald(self, frac, lattice, offsets, charges_or_atomic_numbers, params=None):
+        """The Ewald sums of a batch on this engine's device (arreau_crystal_ewald; diffusion/ewald.py: `ewald`, which needs no
+        engine): frac [N,3] f32, lattice [B,3,3] f32, offsets [B+1] i32, the charges [N] (a floating dtype) or the atomic numbers
+        [N] (an integer dtype, turned into charges by params.charges), params an EwaldParams.  Returns its dict of device tensors.
+        Does not synchronise."""
+        self._on_device("ewald", frac)
+        return ewald_mod.ewald(frac, lattice, offsets, charges_or_atomic_numbers, params)
 
     def find_symmetry(self, frac, lattice, offsets, types, params=None):
         """The symmetry search of a batch on this engine's device (arreau_crystal_symmetry; diffusion/symmetry_search.py:

@@ -75,6 +75,11 @@ Powder diffraction: `--xrd` (`--xrd_wavelength`, `--xrd_fwhm`, `--xrd_two_theta_
 `--xrd_b_iso`, `--xrd_scattering`) writes every crystal's powder X-ray diffraction pattern on a fixed 2 theta grid on the device
 (diffusion/xrd.py): the count per flag, the mean number of lattice points kept and the mean, minimum and maximum 2 theta of the
 strongest peak, and xrd_* arrays.  Z-weighted point scatterers: no form-factor tables, no anomalous dispersion, no K alpha 2.
+Electrostatics: `--ewald --ewald_charges Na=1,Cl=-1` (`--ewald_accuracy`, `--ewald_alpha`) writes every crystal's Ewald energy of
+those point charges and every atom's site potential on the device (diffusion/ewald.py): the count per flag, the mean, minimum and
+maximum energy per atom in eV, the share of crystals that are not neutral (CHARGED: a neutralising background is in the number),
+the mean |potential| per element, and ewald_* arrays.  A crystal with an element that has no charge is flagged UNASSIGNED.  No
+forces, no short-range repulsion (the energy alone favours collapse), no oxidation-state guessing.
 
 Keyed sampling: `--keyed` (needs `--seed`) makes every crystal a function of (seed, key) alone (diffusion/keyed.py).  Every rank
 uses the same seed; output slot k of `--num_crystals` has key k on its first attempt.  With `--require_valid`, attempt a of slot k
@@ -104,7 +109,7 @@ import numpy as np
 
 from .diffusion import instruments
 from .diffusion.diffusion_loss import SampleResult
-from .diffusion.instruments import FULL as INSTRUMENTS
+from .diffusion.instruments import COMPLETE as INSTRUMENTS
 
 
 def shard_range(num_items: int, world_size: int, rank: int):
@@ -499,6 +504,11 @@ def build_parser() -> argparse.ArgumentParser:
                          "--xrd_fwhm, --xrd_two_theta_min, --xrd_two_theta_max, --xrd_points, --xrd_b_iso, --xrd_scattering): flags, mean "
                          "lattice points kept and the strongest peak's 2 theta per rank and in total + xrd_* arrays in the output file")
     add_xrd_arguments(ap)
+    ap.add_argument("--ewald", action="store_true",
+                    help="write every crystal's Ewald electrostatic energy and every atom's site potential on the device, for the point "
+                         "charges of --ewald_charges (--ewald_accuracy, --ewald_alpha): flags, energy per atom, the share of charged "
+                         "crystals and the mean |potential| per element per rank and in total + ewald_* arrays in the output file")
+    add_ewald_arguments(ap)
     ap.add_argument("--guide_contacts", action="store_true",
                     help="contact guidance: steer every sampling step away from contacts shorter than --guide_min_distance (the "
                          "gradient of a contact penalty added to the predicted eps on the device); prints the contacts and flags of "
@@ -571,6 +581,21 @@ def add_xrd_arguments(ap):
                     help="xrd: an atom's amplitude: its atomic number (the forward-scattering limit of the form factor) or 1")
 
 
+def add_ewald_arguments(ap):
+    """The flags of the Ewald sum, shared with `python -m arreau_amd.screen`."""
+    ap.add_argument("--ewald_charges", type=str, default=None, metavar="Na=1,Cl=-1",
+                    help="ewald: the charge in e of every element, by symbol or atomic number; an element without one flags its crystals UNASSIGNED")
+    ap.add_argument("--ewald_accuracy", type=float, default=1e-8, help="ewald: both sums drop terms of about this relative size")
+    ap.add_argument("--ewald_alpha", type=float, default=None,
+                    help="ewald: the splitting parameter in 1/A for every crystal (default: per crystal sqrt(pi) (n / V^2)^(1/6))")
+
+
+def check_ewald_arguments(asked, error):
+    """--ewald needs charges: `error(message)` reports their absence before any work."""
+    if asked.get("ewald") is not None and not asked["ewald"].charges:
+        error("--ewald needs --ewald_charges (for instance Na=1,Cl=-1)")
+
+
 def add_structure_match_arguments(ap):
     """The tolerance flags of the structure match, shared with `python -m arreau_amd.screen`."""
     ap.add_argument("--ltol", type=float, default=0.2, help="match_to: relative tolerance on the cell lengths (StructureMatcher's default)")
@@ -582,10 +607,10 @@ def add_structure_match_arguments(ap):
 
 
 def instrument_params(keyword, args, error):
-    """The parameters of one instrument (its sample() keyword: instruments.FULL_KEYWORDS) from its flags -- screen: a ScreenCriteria,
+    """The parameters of one instrument (its sample() keyword: instruments.COMPLETE_KEYWORDS) from its flags -- screen: a ScreenCriteria,
     unique: a FingerprintParams, find_symmetry: a SymmetrySearchParams, reduce_cell: a CellReductionParams, symmetrize: a
-    SymmetrizeParams, match_to: a StructureMatchParams, conventional_cell: a ConventionalCellParams, coordination: a CoordinationParams, bond_order: a BondOrderParams, voronoi: a VoronoiParams, xrd: an XrdParams; what has no flag keeps its default.  `error(message)` reports a bad value."""
-    e = instruments.FULL_KEYWORDS[keyword]
+    SymmetrizeParams, match_to: a StructureMatchParams, conventional_cell: a ConventionalCellParams, coordination: a CoordinationParams, bond_order: a BondOrderParams, voronoi: a VoronoiParams, xrd: an XrdParams, ewald: an EwaldParams; what has no flag keeps its default.  `error(message)` reports a bad value."""
+    e = instruments.COMPLETE_KEYWORDS[keyword]
     try:
         return getattr(e.module, e.params)(**{name: getattr(args, flag) for name, flag in e.flags})
     except ValueError as err:
@@ -595,7 +620,7 @@ def instrument_params(keyword, args, error):
 def instrument_lines(keyword, res, parts=None):
     """The lines one instrument's flag prints for a result that holds its arrays: its statistics per rank (`parts`: what the ranks
     carried; None: the result as one set) and in total."""
-    e = instruments.FULL_KEYWORDS[keyword]
+    e = instruments.COMPLETE_KEYWORDS[keyword]
     return instruments.summary_lines(e, getattr(res, e.field), parts)
 
 
@@ -762,6 +787,7 @@ def main():
     asked = {"screen": check_screen_arguments(args, ap.error)}  # per instrument, by its sample() keyword: its parameters, or None
     for e in INSTRUMENTS[1:]:
         asked[e.keyword] = instrument_params(e.keyword, args, ap.error) if getattr(args, e.keyword) else None
+    check_ewald_arguments(asked, ap.error)
     if args.match_to:
         asked["match_to"] = (load_targets(args.match_to, ap.error), asked["match_to"], "any")
     unique = asked["unique"]  # (no sample() keyword here: every rank matches its own crystals, rank 0 the whole set)

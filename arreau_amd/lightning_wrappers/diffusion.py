@@ -398,7 +398,7 @@ class PONITA_DIFFUSION(nn.Module):
                symmetrize=None, match_to=None, eta: Optional[float] = None, initial_state=None,
                multistep: bool = False, elements=None, species_temperature: float = 1.0, crystal_keys=None,
                conventional_cell=None, coordination=None, bond_order=None, contact_guidance=None, voronoi=None, xrd=None,
-               xrd_guidance=None) -> SampleResult:
+               xrd_guidance=None, ewald=None) -> SampleResult:
         """lightning_wrappers/diffusion.py:220-253.  `num_atoms_per_sample` may also be a sequence with one atom count
         per crystal of the batch (extension; the reference supports a single int).  Frames of a visualization_setting
         other than NONE go to `<DIFFUSION_DIR>/step_<timestep>.cif` like the reference's PNGs (`vis_name` overrides the

@@ -55,13 +55,18 @@ points kept and the mean, minimum and maximum 2 theta of the strongest peak, and
 same crystals.  `--xrd_against TARGETS` gives every crystal of TARGETS a pattern under the same parameters: with as many targets as
 crystals it prints the paired mean and median distance ((1 - cos) / 2 of the two patterns), otherwise each crystal's smallest distance to
 any target.  Z-weighted point scatterers: no form-factor tables, no anomalous dispersion, no peak list, no K alpha 2.
+`--ewald --ewald_charges Na=1,Cl=-1 [--ewald_accuracy 1e-8] [--ewald_alpha A]` adds every crystal's Ewald electrostatic energy of
+those point charges and every atom's site potential (diffusion/ewald.py): the count per flag, the mean, minimum and maximum energy
+per atom in eV, the share of crystals that are not neutral (CHARGED), the mean |potential| per element, and the ewald_* arrays with
+`--out`.  It runs last, on the same crystals.  No forces, no short-range repulsion (the energy alone favours collapse), no
+oxidation-state guessing: an element without a charge flags its crystals UNASSIGNED.
 """
 import argparse
 
 
 def build_parser() -> argparse.ArgumentParser:
-    from .generate import (add_coordination_arguments, add_fingerprint_arguments, add_voronoi_arguments, add_xrd_arguments, add_screen_arguments, add_structure_match_arguments,
-                           add_symmetry_search_arguments)
+    from .generate import (add_coordination_arguments, add_ewald_arguments, add_fingerprint_arguments, add_voronoi_arguments, add_xrd_arguments, add_screen_arguments,
+                           add_structure_match_arguments, add_symmetry_search_arguments)
     ap = argparse.ArgumentParser(prog="python -m arreau_amd.screen", description="structural screen of a crystals file")
     ap.add_argument("file", type=str, help="crystals.npz / .h5")
     add_screen_arguments(ap)
@@ -101,6 +106,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="with --xrd: a crystals file whose patterns (same parameters) the crystals' are compared with: paired mean and "
                          "median distance with as many targets as crystals, else each crystal's smallest distance to any target")
     add_xrd_arguments(ap)
+    ap.add_argument("--ewald", action="store_true",
+                    help="also write every crystal's Ewald energy and every atom's site potential for the point charges of --ewald_charges "
+                         "(last: on the crystals --out writes)")
+    add_ewald_arguments(ap)
     return ap
 
 
@@ -108,8 +117,8 @@ def main(argv=None):
     from .diffusion import cell_reduction, screening, structure_match, symmetry_search
     from .diffusion.inference.process_generated_crystals import load_sample_results_from_hdf5, save_sample_results_to_hdf5
     from .diffusion.diffusion_loss import SampleResult
-    from .diffusion.instruments import FULL as INSTRUMENTS
-    from .generate import instrument_lines, instrument_params, unique_lines
+    from .diffusion.instruments import COMPLETE as INSTRUMENTS
+    from .generate import check_ewald_arguments, instrument_lines, instrument_params, unique_lines
     ap = build_parser()
     args = ap.parse_args(argv)
     if args.against is not None and not args.unique:
@@ -123,6 +132,7 @@ def main(argv=None):
                  "turn, each on the file the one before wrote")
     asked = {e.keyword: instrument_params(e.keyword, args, ap.error) if getattr(args, e.keyword, True) else None
              for e in INSTRUMENTS}  # (by sample() keyword; None: not asked for.  The screen has no flag here: it always runs)
+    check_ewald_arguments(asked, ap.error)
 
     def load(name):
         try:
@@ -192,6 +202,10 @@ def main(argv=None):
         if xrd_targets is not None:
             for line in xrd.against_lines(current.xrd["pattern"], xrd.xrd_sample_result(xrd_targets, asked["xrd"], args.device)["pattern"]):
                 print(line)
+    if asked["ewald"] is not None:  # (of the same crystals)
+        from .diffusion import ewald
+        current.ewald = ewald.ewald_sample_result(current, asked["ewald"], args.device)
+        report("ewald", current)
     if args.out:
         print("wrote", save_sample_results_to_hdf5(current, args.out))
     return res

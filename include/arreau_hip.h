@@ -613,6 +613,83 @@ typedef struct arreau_xrd_result { /* DEVICE arrays */
 int arreau_crystal_xrd(const float* d_frac, const float* d_lattice, const int32_t* d_crystal_offsets, const float* d_weights,
                        int32_t B, int32_t N, const arreau_xrd_params* params, arreau_xrd_result* out, void* stream);
 
+/* ---- Ewald electrostatics of generated crystals ----------------------------------------------------------------------
+ * Per crystal the electrostatic energy of point charges q_a (the caller's [N] floats, in units of e) on the sites of the periodic
+ * crystal, its real-space, reciprocal-space, self and background parts, and per atom the site potential: the first physical
+ * question asked of a generated ionic crystal.  Table free: the caller supplies the charges; no oxidation-state guessing, no
+ * charge-balance check.  Tin-foil boundary conditions and, for a crystal that is not neutral, a neutralising background; no
+ * dipole correction, no forces, no stress, no short-range repulsion (the energy alone favours collapse).  The screen's exact
+ * real-space image walk and the powder pattern's reciprocal-space box walk in one launch, one workgroup of four waves per
+ * crystal, no atomics, no arreau_model.  The order of every sum is fixed, so a crystal's numbers are the same bits alone, in any
+ * batch and at any place in it.  arreau_amd/diffusion/ewald.py restates the rules in float64 and with the same split of precisions.
+ * Units: charges in e, lengths in A, K = ARREAU_EWALD_K = 14.399645 eV A = V A / e, potentials in V (the sums of rules 3-5 are in
+ * e / A; rule 6 multiplies them by K), energies in eV.
+ *   1. PARAMETERS (float64, on the host, once per launch): s = sqrt(-ln accuracy).  Per crystal alpha = params.alpha where that
+ *      is > 0, else sqrt(pi) cbrt(sqrt(n) / V) = sqrt(pi) (n / V^2)^(1/6) (n atoms); r_cut = s / alpha; G_cut = alpha s / pi.  Both
+ *      sums then drop terms of relative size about `accuracy`.
+ *   2. CELL: the powder pattern's rule 2 (float64 from the float32 entries: det, V = |det|, the reciprocal rows b_k, no 2 pi).
+ *      NONFINITE: a cell entry or a coordinate of the crystal is not finite.  CELL: V or the float32 volume is zero or not
+ *      finite.  EMPTY: no atoms.  CELL again: not (q_k <= max_shells) for an axis, q_k the screen's rule 1 with search_radius =
+ *      (float)r_cut.  RANGE: an H_k = floor(G_cut |a_k|) > max_index (the powder pattern's rule 3 with d*_hi = G_cut).
+ *      UNASSIGNED: a charge of the crystal is not finite (the host's marker for a species without a given charge).  In that
+ *      order, one flag at most; nothing else is computed.
+ *   3. REAL SPACE: images and positions by the screen's rules 4 and 5 with search_radius = (float)r_cut.  For receiver a, every
+ *      atom b and image m, the entry e = b M + m without (b = a, m = (0, 0, 0)): displacement and d2 by the screen's rule 6,
+ *      float32, one rounding per operation.  KEPT iff d2 <= (float)(r_cut^2).  A kept d2 = 0 sets OVERLAP and adds nothing.
+ *      Otherwise r = sqrt((double)d2) and the term q_b erfc(alpha r) / r, float64.  One wave owns an atom (wave w: a = w, w + 4,
+ *      ...); lane t adds its entries e = t, t + 64, ... in ascending order; the wave's sum is the butterfly v + shuffle_xor(v, 32
+ *      .. 1).  n_pairs = the kept terms of the crystal with d2 > 0 (ordered pairs: each contact counts from both ends).
+ *   4. RECIPROCAL SPACE: the powder pattern's rule 4 over the box of 2: the half space in ascending box index, G and |G|^2 in
+ *      float64, KEPT iff 0 < |G|^2 <= G_cut^2; n_reciprocal = 2 * the kept.  S(G) = sum_b q_b (c_b + i s_b), (s_b, c_b) =
+ *      sincospi(2 r_b) in float32 with r_b the reduced float32 phase of the powder pattern's rule 5; products and sums float64, in
+ *      atom order.  w(G) = (2 / (pi V)) exp(-pi^2 |G|^2 / alpha^2) / |G|^2 (the 2 is Friedel's).  phi_a receives w Re S c_a + w Im
+ *      S s_a for every kept G in ascending box index (thread t owns atoms t, t + 256, ...).
+ *   5. SELF AND BACKGROUND: Q = sum q_a, A = sum |q_a|, float64 in atom order.  The self part of atom a is -2 alpha q_a / sqrt(pi),
+ *      the background part -pi Q / (V alpha^2).  CHARGED (informational): |Q| > 1e-6 A; the neutralising background is in the number.
+ *   6. POTENTIALS AND ENERGIES: each of the four parts of atom a is multiplied by K, and potential_a = ((K real + K reciprocal) +
+ *      K self) + K background, in volts.  energy = (1 / 2) sum_a q_a potential_a -- the textbook (K / 2) sum q phi with K inside the
+ *      potential --, every product and every sum one float64 operation rounded to nearest, in atom order; real, reciprocal, self,
+ *      background the same sum over that part of the potential alone.  net_charge = Q; alpha and volume
+ *      (V, float64) are reported.  A crystal with any flag but CHARGED has NaN reals, NaN potentials and zero counts.
+ * Offsets are clamped as in the screen.  The defaults (accuracy 1e-8, alpha 0, max_shells 8, max_index 64) are starting values,
+ * not claims.
+ * Argument errors (ARREAU_EINVAL, nothing launched): NULL params / result / arrays, negative sizes, accuracy not in (0, 1),
+ * alpha not finite or < 0, max_shells outside 1..ARREAU_SCREEN_MAX_SHELLS, max_index outside 1..ARREAU_XRD_MAX_INDEX.  B == 0
+ * returns ARREAU_OK. */
+#define ARREAU_EWALD_NONFINITE 1
+#define ARREAU_EWALD_CELL 2
+#define ARREAU_EWALD_EMPTY 4
+#define ARREAU_EWALD_RANGE 8
+#define ARREAU_EWALD_UNASSIGNED 16
+#define ARREAU_EWALD_OVERLAP 32
+#define ARREAU_EWALD_CHARGED 64 /* informational */
+#define ARREAU_EWALD_K 14.399645 /* e^2 / (4 pi eps_0) in eV A */
+typedef struct arreau_ewald_params {
+    double accuracy;     /* in (0, 1); default 1e-8 */
+    double alpha;        /* 1/A; 0: per crystal sqrt(pi) (n / V^2)^(1/6); default 0 */
+    int32_t max_shells;  /* cap on the images per axis, 1..ARREAU_SCREEN_MAX_SHELLS; default 8 */
+    int32_t max_index;   /* 1..ARREAU_XRD_MAX_INDEX; default 64 */
+} arreau_ewald_params;
+typedef struct arreau_ewald_result { /* DEVICE arrays */
+    double* energy;         /* [B] eV */
+    double* real;           /* [B] */
+    double* reciprocal;     /* [B] */
+    double* self;           /* [B] */
+    double* background;     /* [B] */
+    double* net_charge;     /* [B] e */
+    double* alpha;          /* [B] 1/A */
+    double* volume;         /* [B] A^3 */
+    int64_t* n_pairs;       /* [B] */
+    int32_t* n_reciprocal;  /* [B] */
+    int32_t* flags;         /* [B] ARREAU_EWALD_* */
+    double* potential;      /* [N] V */
+    double* work;           /* [N] scratch: the reciprocal part of the potential while the launch runs */
+} arreau_ewald_result;
+/* d_frac, d_lattice, d_crystal_offsets as for the coordination search; d_charges [N] float32.  `params` and `out` are HOST
+ * pointers to the structs; the arrays `out` names are device arrays. */
+int arreau_crystal_ewald(const float* d_frac, const float* d_lattice, const int32_t* d_crystal_offsets, const float* d_charges,
+                         int32_t B, int32_t N, const arreau_ewald_params* params, arreau_ewald_result* out, void* stream);
+
 /* ---- duplicate detection: structure fingerprints and their all-pairs match ------------------------------------------
  * The screen's sibling: per crystal a reduced formula and a fingerprint of its pair distribution (Oganov & Valle, J. Chem.
  * Phys. 130, 104504 (2009), with the normalisation taken at the bin centre so that it is finite for every input), and for
